@@ -14,11 +14,17 @@ builds the split's tables over it, receives the start of its first block from ra
 encodes the blocks that start in its range; the encoded bit strings are gathered to rank 0 over RCCL
 (torch.distributed backend "nccl") and funnel-shifted into the stream there.
 
-Timed region: K steps with profiling OFF (the product's default path).  Stage timings, the radix-pass
-roofline (HIP events on the context's stream) and the counters of `roofline.path_frac` come from a
-second, untimed pass of the same K steps with profiling on.
+Timed region: K steps with profiling OFF (the product's default path).
 
-Output: ONE JSON line on rank 0 (see the driver contract) with `roofline` (the kernel class that took the most time
+A plain run does only what the headline needs: it sets up, takes one first-touch step (the library sizes its arena) and
+the W warm-up steps, times the K steps and prints ONE JSON line on rank 0 (`metric`, `value`, `unit`, `ms_per_step`,
+`higher_is_better`, `dtype`, the configuration and `compressed_bytes`).  `--dump-outputs DIR` writes the stream of the
+last timed step beside it (dump_outputs).  Everything else is measured and checked with `--full` only, as follows.
+
+Stage timings, the radix-pass roofline (HIP events on the context's stream) and the counters of `roofline.path_frac`
+come from a second, untimed pass of the same K steps with profiling on.
+
+Output with --full: ONE JSON line on rank 0 (see the driver contract) with `roofline` (the kernel class that took the most time
 in the profiled pass -- chunk_finish since the bucket-first initial sort -- its launches timed by HIP events on the
 stream it runs on, the ten most expensive classes beside it, and the whole path by SURVEY 8(d)'s fixed accounting),
 `cpu_baseline` (the oracle =
@@ -43,6 +49,10 @@ SEGMENT = 100_000_000          # bytes per GPU (enwik8 size)
 LEVEL = 9
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 SORT_BYTES_PER_ELEM = 16.0     # one radix pass moves an 8-byte (key, suffix) pair: read 8 + write 8
+METRIC = "encode MB/s (input) at level 9, enwik8, 1/2/4/8 MI355X; bit-exact vs CPU"
+DUMP_BYTES = 8_000_000         # stream bytes --dump-outputs writes at most (as float32: 32 MB of the 64 MB allowed)
+DUMP_PIECE = 1 << 20           # --dump-outputs sums the stream per piece of this many bytes
+DUMP_SEED = 20061
 
 
 def parse_args():
@@ -53,9 +63,14 @@ def parse_args():
     ap.add_argument("--bytes", type=int, default=SEGMENT, help="bytes per GPU")
     ap.add_argument("--total-bytes", type=int, default=0,
                     help="size of the ONE stream all ranks share (overrides --bytes; 1000000000 = BASELINE config 4)")
-    ap.add_argument("--cpu-sample", type=int, default=100_000_000, help="bytes of the workload timed on the CPU oracle")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the oracle (no cpu_baseline, no bit-exactness checks)")
-    ap.add_argument("--no-extra", action="store_true", help="skip extra_workloads and value_host_inclusive")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the profiled pass (stage times, roofline), the checks, the oracle "
+                         "(cpu_baseline) and the other workloads and entry points")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the stream of the last one to DIR/*.npy (see dump_outputs)")
+    ap.add_argument("--cpu-sample", type=int, default=100_000_000, help="--full: bytes of the workload timed on the CPU oracle")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the oracle (no cpu_baseline, no bit-exactness checks)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip extra_workloads and value_host_inclusive")
     ap.add_argument("--single-process", action="store_true",
                     help="--gpus N inside ONE process: bzh_create_multi (one host thread and context per device inside the "
                          "library) instead of one rank per GPU over torch.distributed")
@@ -83,6 +98,32 @@ def path_alg_bytes(st):
     """B_alg = N_in + 97 n + 96 A + 6 m + 3 o (bytes), from the counters of one step."""
     return (st["raw_bytes"] + 97 * st["rle_bytes"] + 96 * st["bwt_active_sum"] + 6 * st["mtf_syms"]
             + 3 * ((st["out_bits"] + 7) // 8))
+
+
+def dump_outputs(out_dir, stream):
+    """--dump-outputs: what a caller of the timed path receives, the .bz2 stream (uint8), as float arrays that two builds
+    can be compared by, file for file:
+      stream_length.npy       float64 [1]: its length in bytes
+      stream_bytes.npy        float32: every byte if there are at most DUMP_BYTES, else the bytes at DUMP_BYTES positions
+                              drawn with DUMP_SEED (sorted, the same positions for the same length)
+      stream_piece_sums.npy   float64 [pieces, 2]: the sum and the position-weighted sum (weights 1, 2, ...) of the bytes of
+                              every DUMP_PIECE-byte piece, which every byte enters (integers below 2^53: exact)"""
+    import numpy as np
+    s = np.asarray(stream, dtype=np.uint8).reshape(-1)
+    n = int(s.size)
+    if n > DUMP_BYTES:
+        s_out = s[np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_BYTES))]
+    else:
+        s_out = s
+    w = np.arange(1, DUMP_PIECE + 1, dtype=np.float64)
+    sums = np.zeros((-(-n // DUMP_PIECE), 2), dtype=np.float64)
+    for k in range(sums.shape[0]):
+        p = s[k * DUMP_PIECE:(k + 1) * DUMP_PIECE].astype(np.float64)
+        sums[k] = (p.sum(), p @ w[:p.size])
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "stream_length.npy"), np.array([n], dtype=np.float64))
+    np.save(os.path.join(out_dir, "stream_bytes.npy"), s_out.astype(np.float32))
+    np.save(os.path.join(out_dir, "stream_piece_sums.npy"), sums)
 
 
 def single_process(args):
@@ -119,20 +160,22 @@ def single_process(args):
         dt = time.perf_counter() - t0
         per_worker = m.times()
         stream = m.fetch(out_len)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, np.frombuffer(stream, dtype=np.uint8))
     checks = {}
-    if total <= 200_000_000:
-        checks["libbz2_roundtrip"] = bool(bz2.decompress(stream) == data.tobytes())
-    dev = torch.device("cuda", devices[0])
-    with nv.Context(devices[0], LEVEL) as ctx:
-        d_in = torch.zeros(total + 16, dtype=torch.uint8, device=dev)
-        d_in[:total] = torch.from_numpy(data).to(dev)
-        cap = (total // 3 + total // 8 + (1 << 20)) & ~3
-        d_out = torch.zeros(cap, dtype=torch.uint8, device=dev)
-        ln = ctx.encode_device(d_in.data_ptr(), total, d_out.data_ptr(), cap)
-        checks["sharded_equals_single_gpu"] = bool(d_out[:ln].cpu().numpy().tobytes() == stream)
+    if args.full:
+        if total <= 200_000_000:
+            checks["libbz2_roundtrip"] = bool(bz2.decompress(stream) == data.tobytes())
+        dev = torch.device("cuda", devices[0])
+        with nv.Context(devices[0], LEVEL) as ctx:
+            d_in = torch.zeros(total + 16, dtype=torch.uint8, device=dev)
+            d_in[:total] = torch.from_numpy(data).to(dev)
+            cap = (total // 3 + total // 8 + (1 << 20)) & ~3
+            d_out = torch.zeros(cap, dtype=torch.uint8, device=dev)
+            ln = ctx.encode_device(d_in.data_ptr(), total, d_out.data_ptr(), cap)
+            checks["sharded_equals_single_gpu"] = bool(d_out[:ln].cpu().numpy().tobytes() == stream)
     ms = dt * 1e3 / args.steps
-    result = {"metric": "encode MB/s (input) at level 9, enwik8, 1/2/4/8 MI355X; bit-exact vs CPU",
-              "value": round(total * args.steps / dt / 1e6, 2), "unit": "MB/s", "n_gpus": world, "steps": args.steps,
+    result = {"metric": METRIC, "value": round(total * args.steps / dt / 1e6, 2), "unit": "MB/s", "n_gpus": world, "steps": args.steps,
               "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
               "scaling": "strong" if args.total_bytes else "weak", "vs_baseline": None, "dtype": "u8",
               "data": "synthetic" if wname != "enwik8" else "enwik8",
@@ -140,7 +183,9 @@ def single_process(args):
                                      "full RLE1->BWT->MTF->Huffman pipeline",
                          "parallelism": f"block-sharded x{world}, single process (bzh_create_multi), devices {devices}"},
               "per_worker_ms": per_worker, "collective_backend": "none: chain by host variables, strings by hipMemcpyPeer",
-              "compressed_bytes": out_len, "checks": checks}
+              "compressed_bytes": out_len}
+    if args.full:
+        result["checks"] = checks
     print(json.dumps(result), flush=True)
     if not all(checks.values()):
         raise SystemExit("bench: correctness check failed")
@@ -297,38 +342,39 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- untimed, FIRST: the same K steps with profiling on (HIP events on the context's stream): stage timings and the
+    out_len = step()  # (first touch: the library sizes and allocates its arena and workspaces inside this call)
+    # ---- untimed, FIRST (--full): the same K steps with profiling on (HIP events on the context's stream): stage timings and the
     # per-kernel table -- and the device has reached its clocks by the time the W warm-up steps and the timed region run
     # (a fresh box measured 1-2 % slower when the timed region came first)
-    out_len = step()  # (first touch: the library sizes and allocates its arena and workspaces inside this call)
-    ctx.set_profiling(True)
-    sort_ms = sort_launches = sort_elems = 0.0
-    stage, counters = {}, {}
-    kern = {}
-    rank_ms = {}
-    barrier()
-    tp0 = time.perf_counter()
-    for _ in range(args.steps):
-        out_len = step()
-        st = ctx.stats()
-        if engine is not None:
-            for k, v in engine.times.items():
-                rank_ms[k] = rank_ms.get(k, 0.0) + v
-        for ks in ctx.kernel_stats():
-            acc = kern.setdefault(ks["name"], {"ms": 0.0, "launches": 0, "alg_bytes": 0})
-            acc["ms"] += ks["ms"]
-            acc["launches"] += ks["launches"]
-            acc["alg_bytes"] += ks["alg_bytes"]
-        sort_ms += st["ms_bwt_sort"]
-        sort_launches += st["bwt_sort_launches"]
-        sort_elems += st["bwt_sort_elems"]
-        nblocks = st["blocks"]
-        for k in ("ms_plan", "ms_rle1", "ms_bwt", "ms_mtf", "ms_huff", "ms_pack"):
-            stage[k] = stage.get(k, 0.0) + st[k]
-        counters = {k: st[k] for k in ("raw_bytes", "rle_bytes", "bwt_active_sum", "mtf_syms", "out_bits", "bwt_rounds")}
-    barrier()
-    ms_profiled = (time.perf_counter() - tp0) * 1e3 / args.steps
-    ctx.set_profiling(False)
+    if args.full:
+        ctx.set_profiling(True)
+        sort_ms = sort_launches = sort_elems = 0.0
+        stage, counters = {}, {}
+        kern = {}
+        rank_ms = {}
+        barrier()
+        tp0 = time.perf_counter()
+        for _ in range(args.steps):
+            out_len = step()
+            st = ctx.stats()
+            if engine is not None:
+                for k, v in engine.times.items():
+                    rank_ms[k] = rank_ms.get(k, 0.0) + v
+            for ks in ctx.kernel_stats():
+                acc = kern.setdefault(ks["name"], {"ms": 0.0, "launches": 0, "alg_bytes": 0})
+                acc["ms"] += ks["ms"]
+                acc["launches"] += ks["launches"]
+                acc["alg_bytes"] += ks["alg_bytes"]
+            sort_ms += st["ms_bwt_sort"]
+            sort_launches += st["bwt_sort_launches"]
+            sort_elems += st["bwt_sort_elems"]
+            nblocks = st["blocks"]
+            for k in ("ms_plan", "ms_rle1", "ms_bwt", "ms_mtf", "ms_huff", "ms_pack"):
+                stage[k] = stage.get(k, 0.0) + st[k]
+            counters = {k: st[k] for k in ("raw_bytes", "rle_bytes", "bwt_active_sum", "mtf_syms", "out_bits", "bwt_rounds")}
+        barrier()
+        ms_profiled = (time.perf_counter() - tp0) * 1e3 / args.steps
+        ctx.set_profiling(False)
 
     ctx.set_profiling(False)
     for _ in range(args.warmup):
@@ -346,6 +392,28 @@ def main():
         dt = float(tmax.item())
     ms_per_step = dt * 1e3 / args.steps
     value = total * args.steps / dt / 1e6
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out[:out_len].cpu().numpy())
+    head = {"metric": METRIC, "value": round(value, 2), "unit": "MB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong" if args.total_bytes else "weak",
+            "ranks_seen": dist.get_world_size() if multi else 1,
+            "chain_calibration": ({"split_ms_per_block": round(calib[0], 5), "encode_ms_per_block": round(calib[1], 5),
+                                   "input_bytes_per_block": round(calib[2]), "plan_cost": round(sharded.PLAN_COST, 5)}
+                                  if calib and calib[1] > 0 else None),
+            "collective_backend": dist.get_backend() if multi else None,
+            "vs_baseline": None, "dtype": "u8", "data": "synthetic" if wname != "enwik8" else "enwik8",
+            "config": {"workload": f"level {LEVEL} {wname}, {seg_bytes} bytes per GPU, {total} bytes in one stream, "
+                                   "full RLE1->BWT->MTF->Huffman pipeline",
+                       "parallelism": f"block-sharded x{world}",
+                       "input_resident_on_rank0": int(resident)}}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(dict(head, compressed_bytes=out_len)), flush=True)
+        ctx.close()
+        if multi:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # whole-path accounting needs every rank's counters
     alg = float(path_alg_bytes(counters))
@@ -681,21 +749,8 @@ def main():
         v_range = [v for v in (value, (extras or {}).get("enwik8-synthetic-v1", {}).get("MB/s"),
                                (extras or {}).get("real-text-100MB", {}).get("MB/s")) if v]
         result = {
-            "metric": "encode MB/s (input) at level 9, enwik8, 1/2/4/8 MI355X; bit-exact vs CPU",
-            "value": round(value, 2), "unit": "MB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": "strong" if args.total_bytes else "weak",
-            "ranks_seen": dist.get_world_size() if multi else 1, "per_rank": per_rank,
-            "chain_calibration": ({"split_ms_per_block": round(calib[0], 5), "encode_ms_per_block": round(calib[1], 5),
-                                   "input_bytes_per_block": round(calib[2]), "plan_cost": round(sharded.PLAN_COST, 5)}
-                                  if calib and calib[1] > 0 else None),
-            "collective_backend": dist.get_backend() if multi else None,
-            "vs_baseline": None, "dtype": "u8", "data": "synthetic" if wname != "enwik8" else "enwik8",
-            "config": {"workload": f"level {LEVEL} {wname}, {seg_bytes} bytes per GPU, {total} bytes in one stream, "
-                                   "full RLE1->BWT->MTF->Huffman pipeline",
-                       "blocks_on_rank0": int(nblocks),
-                       "parallelism": f"block-sharded x{world}",
-                       "input_resident_on_rank0": int(resident)},
+            **head, "per_rank": per_rank,
+            "config": dict(head["config"], blocks_on_rank0=int(nblocks)),
             # text-like 100 MB inputs span this range on one MI355X: the calibrated stand-in, the rounds 1-3 generator, real text
             # of the image (the stand-in is the EASIEST of the three for the suffix sort: see `sensitivity`)
             "value_range": {"min": round(min(v_range), 1), "max": round(max(v_range), 1),

@@ -1,16 +1,19 @@
 #!/bin/bash
+#   scripts/pmc.sh [OUTDIR]   FETCH_SIZE / WRITE_SIZE per kernel of the --full bench run (traces under OUTDIR, default $TMPDIR/bzh_pmc)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+OUT=${1:-$TMPDIR/bzh_pmc}
+mkdir -p "$OUT"
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d gpurun_out/pmc_$c -- python3 bench.py --steps 1 --warmup 1 --no-cpu > gpurun_out/pmc_$c.log 2>&1
-  ls gpurun_out/pmc_$c/*/ | head
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT/pmc_$c" -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu > "$OUT/pmc_$c.log" 2>&1
+  ls "$OUT/pmc_$c"/*/ | head
 done
-python3 - <<'PY'
-import csv, glob, collections
+python3 - "$OUT" <<'PY'
+import csv, glob, collections, sys
 res = {}
 for c in ("FETCH_SIZE", "WRITE_SIZE"):
-    f = glob.glob(f'gpurun_out/pmc_{c}/*/*counter_collection.csv')
+    f = glob.glob(f'{sys.argv[1]}/pmc_{c}/*/*counter_collection.csv')
     if not f:
-        print("no counter file for", c, glob.glob(f'gpurun_out/pmc_{c}/*/*')); continue
+        print("no counter file for", c, glob.glob(f'{sys.argv[1]}/pmc_{c}/*/*')); continue
     rows = list(csv.DictReader(open(f[0])))
     if c == "FETCH_SIZE": print(rows[0].keys())
     agg = collections.defaultdict(lambda: [0, 0.0])

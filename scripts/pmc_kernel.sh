@@ -1,11 +1,12 @@
 #!/bin/bash
-# usage: pmc_kernel.sh "<COUNTER ...>" <kernel-name-substring>   (runs on the GPU box)
+# usage: pmc_kernel.sh "<COUNTER ...>" <kernel-name-substring> [OUTDIR]   (on an MI355X; trace under OUTDIR, default $TMPDIR/bzh_pmc_k)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rm -rf gpurun_out/pmc_k
-rocprofv3 --pmc $1 --kernel-trace --output-format csv -d gpurun_out/pmc_k -- python3 bench.py --steps 1 --warmup 0 --no-cpu > gpurun_out/pmc_k.log 2>&1
-python3 - "$2" <<'PY'
+OUT=${3:-$TMPDIR/bzh_pmc_k}
+rm -rf "$OUT/trace" && mkdir -p "$OUT"
+rocprofv3 --pmc $1 --kernel-trace --output-format csv -d "$OUT/trace" -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu > "$OUT/pmc_k.log" 2>&1
+python3 - "$2" "$OUT/trace" <<'PY'
 import csv, glob, collections, sys, os
-f = max(glob.glob('gpurun_out/pmc_k/*/*counter_collection.csv'), key=os.path.getsize)
+f = max(glob.glob(f'{sys.argv[2]}/*/*counter_collection.csv'), key=os.path.getsize)
 agg = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.Counter()
 for r in csv.DictReader(open(f)):
     k = r['Kernel_Name'].split('(')[0].replace('void ', '')

@@ -1043,7 +1043,7 @@ def test_bench_multi_rank_flow_over_rccl_with_one_rank():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "BZH_BENCH_SHARED_GPU"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--cpu-sample", "4000000", "--no-extra", "--bytes", "30000000"], capture_output=True, text=True,
+                        "--full", "--cpu-sample", "4000000", "--no-extra", "--bytes", "30000000"], capture_output=True, text=True,
                        timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
@@ -1067,7 +1067,7 @@ def test_bench_multi_rank_flow_on_one_gpu(extra):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1",
-                        "--cpu-sample", "4000000", "--no-extra"] + extra, capture_output=True, text=True, timeout=900, env=env)
+                        "--full", "--cpu-sample", "4000000", "--no-extra"] + extra, capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 3 and line["ranks_seen"] == 3 and len(line["per_rank"]) == 3
@@ -1092,7 +1092,7 @@ def test_bench_world_eight_on_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1",
-                        "--cpu-sample", "4000000", "--no-extra", "--total-bytes", "400000000"], capture_output=True, text=True,
+                        "--full", "--cpu-sample", "4000000", "--no-extra", "--total-bytes", "400000000"], capture_output=True, text=True,
                        timeout=1500, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
@@ -1107,6 +1107,27 @@ def test_bench_world_eight_on_one_gpu():
     assert 0 < cal["split_ms_per_block"] < cal["encode_ms_per_block"] and 0 <= cal["plan_cost"] <= 0.05
     waits = [r["model"]["wait"] for r in line["per_rank"]]
     assert waits[0] == 0 and all(a < b for a, b in zip(waits, waits[1:]))
+
+
+@pytest.mark.parametrize("flow", [[], ["--single-process"]])
+def test_bench_plain_run_dumps_the_stream_of_its_last_step(oracle, native, tmp_path, flow):
+    """`bench.py` without --full prints the headline only, and --dump-outputs writes the stream the timed steps computed
+    (whole at this size): the oracle's stream of the same workload, byte for byte"""
+    import subprocess
+    import sys
+    from banzai_amd import corpus
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n = 4_000_000
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--bytes", str(n), "--dump-outputs", str(tmp_path)] + flow, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "MB/s" and line["dtype"] == "u8"
+    assert abs(line["value"] - n / line["ms_per_step"] / 1e3) / line["value"] < 0.01
+    assert not {"roofline", "cpu_baseline", "checks", "extra_workloads"} & set(line)
+    got = np.load(tmp_path / "stream_bytes.npy")
+    assert got.dtype == np.float32 and np.load(tmp_path / "stream_length.npy").tolist() == [line["compressed_bytes"]]
+    assert got.astype(np.uint8).tobytes() == oracle.encode(corpus.workload(n)[0].tobytes(), 9)
 
 
 def test_multi_device_handle_bit_exact(oracle, native):
