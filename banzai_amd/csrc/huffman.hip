@@ -690,7 +690,8 @@ __global__ void __launch_bounds__(64) fx_pack_headers(Batch bt, uint32_t *out, u
 // and so never gets beyond 3 (:318-326) --, the equal-frequency initial partition (:333-376), and four refinement
 // iterations that keep the tables between iterations and restart the frequency lists, where the reference zeroes the
 // tables (:402-409) and ends up with one effective table.  Code lengths come from the same exact heap as the default
-// mode (any valid length assignment decodes; this one is already here).
+// mode (any valid length assignment decodes; this one is already here).  The bytes this mode writes are defined by
+// the CPU model tests/fixed_model.py, which the GPU tests hold these kernels to bit for bit.
 // ================================================================================================================
 __global__ void __launch_bounds__(64) fx_init(Batch bt)
 {
@@ -705,25 +706,15 @@ __global__ void __launch_bounds__(64) fx_init(Batch bt)
     uint8_t *lens = bt.fx_lens + (size_t)b * FX_TABLES * HUF_SYMS;
     uint32_t remaining = m, left = 0;
     for (uint32_t t = 0; t < ntab; t++) {
+        // symbols [left, right) while the frequencies taken stay below the target: a target of 0 (fewer symbols left
+        // than tables, remaining < ntab - t) takes none, and the table starts without a range of its own, all lengths 15
+        const uint32_t target = remaining / (ntab - t);
         uint32_t right = left, acc = 0;
-        bool empty = left >= nsyms; // fewer symbols than tables: the table starts without a range of its own
-        if (!empty) {
-            const uint32_t target = remaining / (ntab - t);
-            for (;;) {
-                acc += F[right];
-                if (acc >= target || right + 1 == nsyms) break;
-                right++;
-            }
-            if (right > left && t != 0 && t != ntab - 1 && (t & 1u)) {
-                acc -= F[right];
-                right--;
-            }
-        }
-        for (uint32_t s = 0; s < nsyms; s++) lens[t * HUF_SYMS + s] = (!empty && s >= left && s <= right) ? 0 : 15;
-        if (!empty) {
-            left = right + 1;
-            remaining -= acc;
-        }
+        while (acc < target && right < nsyms) acc += F[right++];
+        if (right > left + 1 && t != 0 && t != ntab - 1 && (t & 1u)) acc -= F[--right];
+        for (uint32_t s = 0; s < nsyms; s++) lens[t * HUF_SYMS + s] = (s >= left && s < right) ? 0 : 15;
+        left = right;
+        remaining -= acc;
     }
 }
 

@@ -613,6 +613,7 @@ def test_fixed_huffman_mode(oracle, native):
     to the input, must not be larger than the default mode's (beyond tiny streams), and switching back restores the
     reference's bytes."""
     from banzai_amd import corpus
+    from tests import fixed_model
     inputs = [b"", b"x", b"abab", cases.gen(60_000, "text", 1), cases.gen(250_000, "random", 2),
               cases.gen(300_000, "longruns", 3), cases.gen(180_000, "shortruns", 4), cases.gen(99_999, "same", 5),
               corpus.enwik_synthetic(2_700_000, seed=9).tobytes(), bytes([1, 2, 3, 2, 1] * 700)]
@@ -626,6 +627,7 @@ def test_fixed_huffman_mode(oracle, native):
                 fx = ctx.encode(d)
                 ctx.set_mode(False)
                 assert bz2.decompress(fx) == d and oracle.decode(fx, cap=len(d) + 64) == d
+                assert fx == fixed_model.encode(d, level)  # the mode's bytes are the model's
                 # (six table headers and real selectors cost a few hundred bytes per block: a block of a few hundred
                 # symbols, or incompressible bytes, can lose that much -- as with libbz2)
                 assert len(fx) <= len(ref) + 16 + len(ref) // 200, (level, len(d), len(fx), len(ref))
