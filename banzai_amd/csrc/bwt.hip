@@ -187,11 +187,11 @@ __device__ __forceinline__ bool wg_map(uint32_t T, const Lst &l, uint32_t &b, ui
 // XCD's L2 (the random 4-byte gathers and stores of the rounds, the one-byte scatter of bwt_emit: 177 -> 78 us for 16
 // blocks), which outweighs idle XCDs from 6 blocks on -- whole encodes of 6 / 8 / 16 / 24 / 31 text blocks 2.21 / 2.42 /
 // 3.09 / 3.73 / 4.38 ms spread against 2.14 / 2.27 / 2.87 / 3.38 / 3.94 ms pinned, 5 blocks the same, 4 blocks 1.73
-// against 1.82 ms.  (BZH_SPREAD_MAX moves the limit: A/B timing.)
+// against 1.82 ms.
+constexpr uint32_t SPREAD_MAX = 6;
 static inline bool few_blocks(uint32_t NB)
 {
-    static const uint32_t lim = getenv("BZH_SPREAD_MAX") ? (uint32_t)atoi(getenv("BZH_SPREAD_MAX")) : 6u;
-    return NB < lim;
+    return NB < SPREAD_MAX;
 }
 
 static inline uint32_t xcd_grid(uint32_t tiles, uint32_t NB)
@@ -199,7 +199,7 @@ static inline uint32_t xcd_grid(uint32_t tiles, uint32_t NB)
     return (tiles & WG_SPREAD) ? (tiles & ~WG_SPREAD) * NB : 8u * ((NB + 7u) / 8u) * tiles;
 }
 
-// The host sizes every launch of a round from a summary that is one round old (bounds, see bwt_run).  A launch that
+// The host sizes every launch of a round from a summary that is one round old (bounds: SortAttempt::read_summary).  A launch that
 // turned out too small would silently skip blocks or tiles; this makes it loud instead (bit 2 of the error word):
 // workgroup 0 compares the list length with the blocks the grid covers, every block's first tile compares the tiles
 // it needs with the tiles launched.
@@ -2257,6 +2257,13 @@ __global__ void __launch_bounds__(1024) period_expand(Batch bt, const uint32_t *
 constexpr uint32_t QUAD_BIT = 0x80000000u; // in st_ntail-derived gates: this round runs at depth x4
 enum ListId : int { L_S = 0, L_A = 1, L_R = 2, L_T = 3, L_Q = 4, L_P = 5 };
 
+// A block on the 8 passes with fewer than n / SWEEP_DIV groups after them starts in SWEEP mode (round_begin's `sweep_div`).
+// Rounds 2-3 drew the line at n / 8; measured in round 4: the periodic and run-heavy inputs SWEEP mode exists for have a
+// few hundred to a thousand times fewer groups than suffixes and do not care (they break at n / 2048), while merely
+// repetitive text is 3-9 % faster in SPLIT mode (real text with every block on the 8 passes 15.85 -> 14.60 ms, with the
+// buckets 14.73 -> 14.36 ms: two of its blocks keep the 8 passes).
+constexpr uint32_t SWEEP_DIV = 256;
+
 __global__ void __launch_bounds__(1024) round_begin(Batch bt, uint32_t B, uint32_t round, uint32_t *actP, uint32_t *hsum, uint32_t seq, uint32_t sweep_div,
                                                     uint32_t r0_fused, uint32_t mid_on)
 {
@@ -2451,18 +2458,38 @@ struct ClearList {
     }
 };
 
+// ---- environment switches (measurement and tests only), read once --------------------------------------------------
+struct BwtSwitches {
+    bool init_lsd, init_msd; // BZH_INIT=lsd|msd: every block on the 8 passes / the bucket-first sort for any batch
+    bool r0_off;             // BZH_R0=0: chunk_finish leaves the first doubling step to round 0
+    bool mid_off;            // BZH_MID=0: no mid_sort, the global passes order every big list
+    bool no_overlap;         // BZH_NO_OVERLAP: the suffix sort stays on one stream
+    bool trace;              // BZH_TRACE_ROUNDS: a line per round on stderr (waits for the device)
+    uint32_t msd_dbg;        // BZH_MSD_DBG (bwt_msd.h)
+};
+static const BwtSwitches &bwt_switches()
+{
+    static const BwtSwitches sw = [] {
+        const auto is = [](const char *name, const char *v) { const char *e = getenv(name); return e && !strcmp(e, v); };
+        const char *dbg = getenv("BZH_MSD_DBG");
+        return BwtSwitches{is("BZH_INIT", "lsd"), is("BZH_INIT", "msd"), is("BZH_R0", "0"), is("BZH_MID", "0"),
+                           getenv("BZH_NO_OVERLAP") != nullptr, getenv("BZH_TRACE_ROUNDS") != nullptr, dbg ? (uint32_t)atoi(dbg) : 0u};
+    }();
+    return sw;
+}
+
 #include "bwt_msd.h"
 
 // ---- host driver -----------------------------------------------------------------------------------
 // one radix pass = one kernel (look-back scatter)
 template <int BITS, int MODE>
-static void launch_pass(bzh_ctx *ctx, SortArgs &a, uint32_t NB, uint32_t maxcnt)
+static void launch_pass(bzh_ctx *ctx, hipStream_t st, SortArgs &a, uint32_t NB, uint32_t maxcnt)
 {
     const uint32_t tiles = (maxcnt + SORT_TILE - 1) / SORT_TILE;
     if (tiles == 0 || NB == 0) return;
     a.T = tiles | ((few_blocks(NB) && !ctx->no_spread) ? WG_SPREAD : 0u); // (look-back: see bwt_run on no_spread)
     a.pass++;
-    radix_scatter<BITS, MODE><<<dim3(xcd_grid(a.T, NB)), SORT_THREADS, 0, ctx->stream>>>(a);
+    radix_scatter<BITS, MODE><<<dim3(xcd_grid(a.T, NB)), SORT_THREADS, 0, st>>>(a);
     if (ctx->profiling) ctx->stats.bwt_sort_launches++; // every launch issued, also the ones that find their list empty
 }
 
@@ -2519,15 +2546,15 @@ __global__ void __launch_bounds__(768) sweep_bases(RefineArgs a, uint32_t *dbase
     if (!seg) dbase[(size_t)b * DB_STRIDE + col] = ex - part[col & ~127u];
 }
 
-static void launch_refine(bzh_ctx *ctx, RefineArgs &r, uint32_t NB, uint32_t maxcnt, bool bases)
+static void launch_refine(bzh_ctx *ctx, hipStream_t st, RefineArgs &r, uint32_t NB, uint32_t maxcnt, bool bases)
 {
     const uint32_t tiles = (maxcnt + SORT_TILE - 1) / SORT_TILE;
     if (tiles == 0 || NB == 0) return;
     r.T = tiles | ((few_blocks(NB) && !ctx->no_spread) ? WG_SPREAD : 0u);
-    flag_tiles<<<dim3(xcd_grid(r.T, NB)), SORT_THREADS, 0, ctx->stream>>>(r);
-    flag_carry<<<dim3(NB), 1024, 0, ctx->stream>>>(r);
-    refine<<<dim3(xcd_grid(r.T, NB)), SORT_THREADS, 0, ctx->stream>>>(r);
-    if (bases) sweep_bases<<<dim3(NB), 768, 0, ctx->stream>>>(r, ctx->bt.dbase);
+    flag_tiles<<<dim3(xcd_grid(r.T, NB)), SORT_THREADS, 0, st>>>(r);
+    flag_carry<<<dim3(NB), 1024, 0, st>>>(r);
+    refine<<<dim3(xcd_grid(r.T, NB)), SORT_THREADS, 0, st>>>(r);
+    if (bases) sweep_bases<<<dim3(NB), 768, 0, st>>>(r, ctx->bt.dbase);
 }
 
 // ---- initial ranks: binned by destination, then applied -------------------------------------------------------
@@ -2577,44 +2604,219 @@ __global__ void __launch_bounds__(256) rank_apply(const u64 *binned, const uint3
 }
 
 template <bool INIT>
-static void launch_refine_one(bzh_ctx *ctx, RefineArgs &r, uint32_t NB, uint32_t maxcnt, u64 *recs = nullptr)
+static void launch_refine_one(bzh_ctx *ctx, hipStream_t st, RefineArgs &r, uint32_t NB, uint32_t maxcnt, u64 *recs = nullptr)
 {
     const uint32_t tiles = (maxcnt + SORT_TILE - 1) / SORT_TILE;
     if (tiles == 0 || NB == 0) return;
     r.T = tiles | ((few_blocks(NB) && !ctx->no_spread) ? WG_SPREAD : 0u);
-    refine_one<INIT><<<dim3(xcd_grid(r.T, NB)), SORT_THREADS, 0, ctx->stream>>>(r, ctx->bt.c_groups, recs);
+    refine_one<INIT><<<dim3(xcd_grid(r.T, NB)), SORT_THREADS, 0, st>>>(r, ctx->bt.c_groups, recs);
 }
 
-// Suffix-sort and emit the last column for blocks 0..B-1 of the batch (bt.rle / bt.n filled).
-// nmax = largest block length in the batch, ntotal = sum of block lengths (statistics only).
-int bwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal, bool is_retry)
-{
-    Batch &bt = ctx->bt;
-    if (B == 0) return BZH_OK;
-    hipStream_t st = ctx->stream;
-    const uint32_t mb = ctx->max_batch;
-    // (what a retry must not count twice: see the look-back retry at the end)
-    const bzh_stats stats_in = ctx->stats;
-    const size_t spans_in = ctx->sort_spans.size(), kspans_in = ctx->kspans.size();
-    uint64_t kb_in[K_COUNT], kl_in[K_COUNT];
-    memcpy(kb_in, ctx->k_bytes, sizeof kb_in);
-    memcpy(kl_in, ctx->k_launch, sizeof kl_in);
+// One attempt at the suffix sort of blocks 0..B-1 (bwt_run below): the state its phases share.
+struct SortAttempt {
+    bzh_ctx *ctx;
+    Batch &bt;
+    const BwtSwitches &sw = bwt_switches();
+    uint32_t B, nmax;
+    uint64_t ntotal, ntotal_old = 0; // (statistics only)
+    const Lst all{nullptr, nullptr, B};
     u64 *bufA = reinterpret_cast<u64 *>(bt.listA), *bufB = reinterpret_cast<u64 *>(bt.listB);
     u64 *bufC = reinterpret_cast<u64 *>(bt.listC), *bufD = reinterpret_cast<u64 *>(bt.listD);
-    const Lst all{nullptr, nullptr, B};
+    u64 *binned = reinterpret_cast<u64 *>(bt.binned);
     uint32_t *actP = bt.actQ + bt.B; // sixth list, behind the five named ones (rows of the layout are bt.B apart)
-
+    volatile uint32_t *hsum = ctx->h_pinned + (size_t)ctx->max_batch * 8 + 64; // [MAX_ROUNDS][SUMMARY_WORDS] (+ one record of the initial sort's plan)
+    uint32_t epoch = (++ctx->bwt_epoch & 0xFFFFFFu) << 6;
+    hipStream_t st = ctx->stream, side = nullptr, side2 = nullptr;
+    bool side_busy = false, side2_busy = false; // given work that the main stream has not waited for yet
     SortArgs a{};
-    a.blk = bt.rle;
-    a.n = bt.n;
-    a.rank = bt.rank;
-    a.sa = bt.sa;
-    a.headp = bt.headp;
-    a.hb = bt.st_h;
-    a.S = bt.S;
-    a.TPB = bt.TPB;
-    a.gwide = bt.gwide;
-    a.gidof = bt.gidof;
+    RefineArgs r{};
+    TailArgs ta{};
+    u64 *cur = bufA, *oth = bufB;
+    bool had_fault, use_msd, mid_on;
+    uint32_t r0_fused;
+    bool msd_deeper = false; // the levels behind the first ran: a block may hold a group that spans several units
+    uint32_t nOld = B;
+    Lst oldl = all;
+    Msd msd_keep{};
+    // bounds for the launches of the round being queued (exact lists live on the device)
+    uint32_t nS = B, nA = B, nT = B, nQ = B, maxS = nmax, maxA = nmax, maxT = nmax;
+    // do the blocks of mid_sort / the blocks of the global passes have big lists?  (round 0: what the initial sort's plan says;
+    // later: the sums of the last summary -- a big list only shrinks, and only a block in SWEEP mode can still join the others)
+    bool have_mid, have_glob;
+    // (all_quad: the last summary read shows no block in SWEEP mode, none with a big list and every block that holds small
+    // groups on the depth x4 form -- all of which only ever stays so --: the plain form has no block to work on and is not
+    // launched; the depth x4 kernel checks the list it would have had)
+    bool all_quad = false;
+    uint32_t err = 0;
+    bool finished = false;
+    uint64_t emitted = 0; // rotations whose last-column byte the initial sort wrote (statistics)
+    uint32_t s[SUMMARY_WORDS] = {}; // the last summary read
+
+    SortAttempt(bzh_ctx *c, uint32_t nb, uint32_t nm, uint64_t nt) : ctx(c), bt(c->bt), B(nb), nmax(nm), ntotal(nt)
+    {
+        a.blk = bt.rle;
+        a.n = bt.n;
+        a.rank = bt.rank;
+        a.sa = bt.sa;
+        a.headp = bt.headp;
+        a.hb = bt.st_h;
+        a.S = bt.S;
+        a.TPB = bt.TPB;
+        a.gwide = bt.gwide;
+        a.gidof = bt.gidof;
+        a.cnt = bt.n;
+        a.lst = all;
+        a.shift = 20;
+        a.gst = reinterpret_cast<u64 *>(bt.tagg); // (flag_tiles / flag_carry use it after the initial sort only)
+        a.chain = bt.chain;
+        a.fault = ctx->debug_fault; // (one batch only)
+        a.patient = ctx->no_spread ? 1u : 0u;
+        had_fault = a.fault == 1u; // (kind 2: the fault of a shared GPU -- the sort is expected to recover by itself)
+        ctx->debug_fault = 0;
+        a.clist = reinterpret_cast<const uint32_t *>(bt.listD); // (a block in SWEEP mode has no small-group lists)
+        a.src = nullptr;
+        a.dst = bufA;
+        a.look = reinterpret_cast<u64 *>(bt.hist);
+        a.dbase = bt.dbase;
+        a.doff = 0;
+        a.err = bt.errflag;
+        a.pass = 0;
+
+        // The second stream of the suffix sort (created once): the big-list path of a round runs on it beside the small-group
+        // kernel, and so do the 8 passes of the blocks that keep them when the rest of the batch takes the bucket-first
+        // initial sort.  (With profiling on everything stays on one stream, or the per-kernel spans would overlap.)
+        if (!ctx->profiling && !sw.no_overlap) {
+            side = bzh_side_stream(ctx);
+            if (side && !ctx->side2_stream) { // (optional: without it the global passes follow mid_sort on the second stream)
+                if (hipStreamCreateWithFlags(&ctx->side2_stream, hipStreamNonBlocking) != hipSuccess) ctx->side2_stream = nullptr;
+                if (ctx->side2_stream && hipEventCreateWithFlags(&ctx->side_ev[2], hipEventDisableTiming) != hipSuccess) {
+                    hipStreamDestroy(ctx->side2_stream);
+                    ctx->side2_stream = nullptr;
+                }
+            }
+        }
+        side2 = side ? ctx->side2_stream : nullptr;
+
+        // ---- which blocks take which initial sort (bwt_msd.h): text-like blocks the bucket-first one (the plan decides per
+        // block, on the device), repetitive, random and binary blocks the 8 passes (`oldl`; all blocks at level 1, whose
+        // blocks are too short for the tables to pay).  BZH_INIT=lsd keeps every block on the 8 passes (A/B timing).
+        // (a batch of fewer than 12 blocks keeps the 8 passes: the bucket tables' fixed work -- histogram, plan, five levels --
+        // does not pay below that: 1 / 2 / 4 / 8 / 16 text blocks 1.56 / 1.62 / 2.08 / 2.55 / 3.07 ms with the buckets, 1.45 / 1.51 /
+        // 1.94 / 2.47 / 3.11 ms with the 8 passes, one random block 1.36 / 1.26 ms; BZH_INIT=msd overrides)
+        use_msd = ctx->M >= MS_MIN_N && !a.fault && !sw.init_lsd && (B >= 12u || sw.init_msd);
+        // chunk_finish takes the first doubling step of the small groups itself, keyed on the text (BZH_R0=0: A/B timing)
+        r0_fused = (use_msd && !sw.r0_off) ? 1u : 0u;
+        // round 0 orders the large groups of a bucket-first block unit by unit in LDS (mid_sort; BZH_MID=0: the global passes, A/B timing)
+        mid_on = use_msd && !sw.mid_off;
+
+        r.n = bt.n;
+        r.cnt = bt.n;
+        r.tail0 = bufC;
+        r.tail1 = bufD;
+        r.tdst = bt.st_tdst;
+        r.tbase = bt.c_tail;
+        r.mode = bt.st_mode;
+        r.blk = bt.rle;
+        r.bwt = bt.bwt;
+        r.rank = bt.rank;
+        r.sa = bt.sa;
+        r.headp = bt.headp;
+        r.flg = bt.flg;
+        r.tagg = bt.tagg;
+        r.dig = bt.hist;
+        r.c_big = bt.c_big;
+        r.c_small = bt.c_small;
+        r.c_prog = bt.c_prog;
+        r.c_nolist = bt.c_nolist;
+        r.nbig_in = bt.st_nbig;
+        r.S = bt.S;
+        r.TPB = bt.TPB;
+        r.gout = GidOut{bt.gidof, bt.grank, bt.gcount, bt.gwide, bt.S, bt.B, 0u}; // (the initial refinement writes round 0's lists)
+        r.grank = bt.grank;
+        r.gwide = bt.gwide;
+        r.init = 1;
+        r.cstat = reinterpret_cast<u64 *>(bt.hist);
+        r.carry = reinterpret_cast<u64 *>(bt.tagg);
+        r.err = bt.errflag;
+        r.patient = a.patient;
+
+        ta.n = bt.n;
+        ta.len = bt.st_ntail; // (gateT carries the QUAD bit; the plain length lives here)
+        ta.buf0 = bufC; // a block's small-group list moves between bufC and bufD, one hop per round in which it is worked on
+        ta.buf1 = bufD; // (round_begin keeps track per block: st_tdst)
+        ta.tdst = bt.st_tdst;
+        ta.rank = bt.rank;
+        ta.c_tail = bt.c_tail;
+        ta.c_prog = bt.c_prog;
+        ta.err = bt.errflag;
+        ta.hb = bt.st_h;
+        ta.S = bt.S;
+#ifdef BZH_EXPERIMENTS
+        ta.dbg = getenv("BZH_TAIL_DBG") ? (uint32_t)atoi(getenv("BZH_TAIL_DBG")) : 0u;
+#endif
+    }
+
+    // ---- side streams.  fork: `to` starts behind what the main stream was given up to side_ev[0] (recorded now, unless
+    // the caller did so earlier); done: the main stream waits for what `from` was given at the next join_side.
+    hipStream_t fork(hipStream_t to, bool record = true)
+    {
+        if (record) hipEventRecord(ctx->side_ev[0], st);
+        hipStreamWaitEvent(to, ctx->side_ev[0], 0);
+        return to;
+    }
+    void done(hipStream_t from) // (the second stream's work ends at side_ev[1], the third's at side_ev[2])
+    {
+        hipEventRecord(ctx->side_ev[from == side ? 1 : 2], from);
+        (from == side ? side_busy : side2_busy) = true;
+    }
+    void join_side() // the main stream goes on only behind what the side streams were given
+    {
+        if (side_busy) hipStreamWaitEvent(st, ctx->side_ev[1], 0);
+        if (side2_busy) hipStreamWaitEvent(st, ctx->side_ev[2], 0);
+        side_busy = side2_busy = false;
+    }
+    // An error return hands the context back: nothing of this call may still be running on the second stream
+    // against the arena when the next call queues its memsets (bzh_debug_fault promises a usable context).
+    int fail_wait(hipError_t e)
+    {
+        if (side_busy && side) hipStreamSynchronize(side);
+        if (side2_busy && side2) hipStreamSynchronize(side2);
+        side_busy = side2_busy = false;
+        bzh_set_error(ctx, "%s:%d waiting for a round summary -> %s", __FILE__, __LINE__, hipGetErrorString(e));
+        return BZH_E_HIP;
+    }
+
+    // ---- one launch clears everything the sort starts from; period_detect
+    int clear(bool retry)
+    {
+        ClearList clr;
+        clr.add(bt.errflag, sizeof(uint32_t));
+        clr.add(a.look, (size_t)B * bt.TPB * NBMAX * sizeof(u64));
+        clr.add(bt.tagg, (size_t)B * bt.TPB * sizeof(int4));
+        clr.add(bt.dtot, (size_t)B * DB_STRIDE * sizeof(uint32_t));
+        // round state: everything from st_mode to the 64-bit counter (one contiguous carve, see layout_batch)
+        clr.add(bt.st_mode, (size_t)((uint8_t *)(bt.stat_A + 1) - (uint8_t *)bt.st_mode));
+        clr.add(bt.hasbyte, (size_t)B * 256); // (bwt_emit ORs into it at the very end)
+        clr.add(bt.gcount, (size_t)bt.B * sizeof(uint32_t)); // (no large group numbered yet; the two "ran out of numbers" words
+        clr.add(bt.gwide, 16);                                //  lie behind it)
+        if (use_msd) { // (its counters, rank-window cursors and bigram counts join the one clearing launch)
+            clr.add(bt.ms_cnt, (MS_CNT_WORDS + (size_t)(MS_LEVELS + 7) * B) * sizeof(uint32_t)); // (the counters; the tables of runs and tiles behind them are written before they are read)
+            clr.add(bt.ms_bincur, (size_t)B * 256 * sizeof(uint32_t));
+            clr.add(bt.ms_bgcur, (size_t)B * MS_BG * sizeof(uint32_t));
+        } else {
+            clr.add(bt.ms_np, (size_t)B * sizeof(uint32_t));
+        }
+        if (clr.overflow) { // (more regions than the clearing kernel takes: sort state would stay dirty -- loud, not wrong bytes)
+            bzh_set_error(ctx, "BWT: the clearing list is full (internal error)");
+            return BZH_E_HIP;
+        }
+        clr.launch(st);
+        // near-periodic blocks are sorted as eight of their periods (period_detect shrinks bt.n[b] before anything reads it,
+        // period_expand behind bwt_emit writes the whole block's last column); a retry after a look-back gave up finds the blocks
+        // shrunk already
+        if (!retry) period_detect<<<dim3(B), 1024, 0, st>>>(bt.rle, bt.n, bt.pshrink, bt.S);
+        return BZH_OK;
+    }
 
     // ---- initial sort on the 8-byte cyclic prefix: LSD, 8 passes of 8 bits.  Passes 0-4 order by bytes 3..7 of
     // the rotation (the element carries all five); pass 5 finds each element's 5-byte group on the way in (the list
@@ -2624,289 +2826,107 @@ int bwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal, bool is_re
     // suffix, so this replaces "4-byte sort + refine + first doubling round".
     // The passes run as single look-back kernels (no histogram / scan launches): their digit bases
     // are the block's byte counts.
-    a.cnt = bt.n;
-    a.lst = all;
-    a.shift = 20;
-    a.gst = reinterpret_cast<u64 *>(bt.tagg); // (flag_tiles / flag_carry use it after the initial sort only)
-    a.chain = bt.chain;
-    a.fault = ctx->debug_fault; // (one batch only)
-    a.patient = ctx->no_spread ? 1u : 0u;
-    const bool had_fault = a.fault == 1u; // (kind 2: the fault of a shared GPU -- the sort is expected to recover by itself)
-    ctx->debug_fault = 0;
-    a.clist = reinterpret_cast<const uint32_t *>(bt.listD); // (a block in SWEEP mode has no small-group lists)
-    a.src = nullptr;
-    a.dst = bufA;
-    a.look = reinterpret_cast<u64 *>(bt.hist);
-    a.dbase = bt.dbase;
-    a.doff = 0;
-    a.err = bt.errflag;
-    a.pass = 0;
-    ClearList clr; // launched below, once it is known whether the bucket tables are used
-    clr.add(bt.errflag, sizeof(uint32_t));
-    clr.add(a.look, (size_t)B * bt.TPB * NBMAX * sizeof(u64));
-    clr.add(bt.tagg, (size_t)B * bt.TPB * sizeof(int4));
-    clr.add(bt.dtot, (size_t)B * DB_STRIDE * sizeof(uint32_t));
-    // round state: everything from st_mode to the 64-bit counter (one contiguous carve, see layout_batch)
-    clr.add(bt.st_mode, (size_t)((uint8_t *)(bt.stat_A + 1) - (uint8_t *)bt.st_mode));
-    clr.add(bt.hasbyte, (size_t)B * 256); // (bwt_emit ORs into it at the very end)
-    clr.add(bt.gcount, (size_t)bt.B * sizeof(uint32_t)); // (no large group numbered yet; the two "ran out of numbers" words
-    clr.add(bt.gwide, 16);                                //  lie behind it)
-    // The second stream of the suffix sort (created once): the big-list path of a round runs on it beside the small-group
-    // kernel, and so do the 8 passes of the blocks that keep them when the rest of the batch takes the bucket-first
-    // initial sort.  (With profiling on everything stays on one stream, or the per-kernel spans would overlap.)
-    static const bool no_overlap = getenv("BZH_NO_OVERLAP") != nullptr;
-    hipStream_t side = nullptr;
-    if (!ctx->profiling && !no_overlap) {
-        side = bzh_side_stream(ctx);
-        if (side && !ctx->side2_stream) { // (optional: without it the global passes follow mid_sort on the second stream)
-            if (hipStreamCreateWithFlags(&ctx->side2_stream, hipStreamNonBlocking) != hipSuccess) ctx->side2_stream = nullptr;
-            if (ctx->side2_stream && hipEventCreateWithFlags(&ctx->side_ev[2], hipEventDisableTiming) != hipSuccess) {
-                hipStreamDestroy(ctx->side2_stream);
-                ctx->side2_stream = nullptr;
-            }
-        }
-    }
-    hipStream_t side2 = side ? ctx->side2_stream : nullptr;
-    // ---- which blocks take which initial sort (bwt_msd.h): text-like blocks the bucket-first one (the plan decides per
-    // block, on the device), repetitive, random and binary blocks the 8 passes below (`oldl`; all blocks at level 1,
-    // whose blocks are too short for the tables to pay).  BZH_INIT=lsd keeps every block on the 8 passes (A/B timing).
-    static const bool init_lsd = []() {
-        const char *e = getenv("BZH_INIT");
-        return e && !strcmp(e, "lsd");
-    }();
-    static const bool init_msd = []() {
-        const char *e = getenv("BZH_INIT");
-        return e && !strcmp(e, "msd");
-    }();
-    // (a batch of fewer than 12 blocks keeps the 8 passes: the bucket tables' fixed work -- histogram, plan, five levels --
-    // does not pay below that: 1 / 2 / 4 / 8 / 16 text blocks 1.56 / 1.62 / 2.08 / 2.55 / 3.07 ms with the buckets, 1.45 / 1.51 /
-    // 1.94 / 2.47 / 3.11 ms with the 8 passes, one random block 1.36 / 1.26 ms; BZH_INIT=msd overrides)
-    const bool use_msd = ctx->M >= MS_MIN_N && !a.fault && !init_lsd && (B >= 12u || init_msd);
-    // chunk_finish takes the first doubling step of the small groups itself, keyed on the text (BZH_R0=0: A/B timing)
-    static const bool r0_off = getenv("BZH_R0") && !strcmp(getenv("BZH_R0"), "0");
-    const uint32_t r0_fused = (use_msd && !r0_off) ? 1u : 0u;
-    // round 0 orders the large groups of a bucket-first block unit by unit in LDS (mid_sort; BZH_MID=0: the global passes, A/B timing)
-    static const bool mid_off = getenv("BZH_MID") && !strcmp(getenv("BZH_MID"), "0");
-    const bool mid_on = use_msd && !mid_off;
-    bool msd_deeper = false; // the levels behind the first ran: a block may hold a group that spans several units
-    uint32_t nOld = B;
-    Lst oldl = all;
-    u64 *const binned = reinterpret_cast<u64 *>(bt.binned);
-    volatile uint32_t *const hrec0 = ctx->h_pinned + (size_t)mb * 8 + 64; // [MAX_ROUNDS + 1][SUMMARY_WORDS]
-    const uint32_t epoch = (++ctx->bwt_epoch & 0xFFFFFFu) << 6;
-    Msd msd_keep{};
-    if (use_msd) { // (its counters, rank-window cursors and bigram counts join the one clearing launch)
-        clr.add(bt.ms_cnt, (MS_CNT_WORDS + (size_t)(MS_LEVELS + 7) * B) * sizeof(uint32_t)); // (the counters; the tables of runs and tiles behind them are written before they are read)
-        clr.add(bt.ms_bincur, (size_t)B * 256 * sizeof(uint32_t));
-        clr.add(bt.ms_bgcur, (size_t)B * MS_BG * sizeof(uint32_t));
-    } else {
-        clr.add(bt.ms_np, (size_t)B * sizeof(uint32_t));
-    }
-    if (clr.overflow) { // (more regions than the clearing kernel takes: sort state would stay dirty -- loud, not wrong bytes)
-        bzh_set_error(ctx, "BWT: the clearing list is full (internal error)");
-        return BZH_E_HIP;
-    }
-    clr.launch(st);
-    // near-periodic blocks are sorted as eight of their periods (period_detect shrinks bt.n[b] before anything reads it,
-    // period_expand behind bwt_emit writes the whole block's last column); a retry after a look-back gave up finds the blocks
-    // shrunk already
-    if (!is_retry) period_detect<<<dim3(B), 1024, 0, st>>>(bt.rle, bt.n, bt.pshrink, bt.S);
-    if (use_msd) {
-        BZH_TRY(msd_sort_begin(ctx, B, nmax, ntotal, bufB, bufD, bufA, bufC, binned, false, r0_fused,
-                               hrec0 + (size_t)MAX_ROUNDS * SUMMARY_WORDS, epoch + 63u, &nOld, side ? ctx->side_ev[0] : nullptr, &msd_keep));
-        oldl = Lst{bt.ms_old, bt.ms_cnt + MC_OLD, B};
-        a.lst = oldl;
-    }
-    const uint64_t ntotal_old = nOld == B ? ntotal : ntotal * nOld / B; // (statistics only)
-    u64 *cur = bufA, *oth = bufB;
-    hipEvent_t ev_init = span_begin(ctx);
-    // A mixed batch: the few blocks on the 8 passes cannot fill the device (one block alone takes ~3 ms for them), so
-    // they run on the second stream beside the bucket-first kernels of the others, from the plan's end on.
-    const bool old_beside = use_msd && side && nOld && nOld < B;
-    hipStream_t so = st;
-    if (old_beside) {
-        hipStreamWaitEvent(side, ctx->side_ev[0], 0);
-        so = side;
-        ctx->stream = side; // (launch_pass / launch_refine_one launch on the context's stream)
-    }
-    if (nOld) {
-        {
-            KSpan ks(ctx, K_BYTE_COUNT, ntotal_old, 2);
-            byte_count<<<dim3(BYTE_SEGS, B), 1024, 0, so>>>(bt.rle, bt.n, bt.dtot, bt.S);
-            active_bases<<<dim3(B), 256, 0, so>>>(bt.dtot, bt.dbase, all, 1);
-        }
-        {
-            KSpan ks(ctx, K_RADIX_INIT, 13 * ntotal_old); // 5 text bytes in, one element out
-            launch_pass<8, GEN_BYTES5>(ctx, a, nOld, nmax);
-        }
-        for (int p = 1; p < 8; p++) {
-            a.shift = p < 5 ? 20 + 8 * p : 40 + 8 * (p - 5);
-            a.src = cur;
-            a.dst = oth;
-            KSpan ks(ctx, p == 5 ? K_RADIX_GID : K_RADIX_INIT, (p == 5 ? 20 : 16) * ntotal_old); // (re-key: + one 4-byte gather)
-            if (p == 5)
-                launch_pass<8, GEN_GID>(ctx, a, nOld, nmax);
-            else
-                launch_pass<8, GEN_LIST>(ctx, a, nOld, nmax);
-            u64 *t = cur;
-            cur = oth;
-            oth = t;
-        }
-        if (ctx->profiling) ctx->stats.bwt_sort_elems += 8 * ntotal_old;
-    } else {
-        cur = bufB; // (where the 8 passes leave the sorted list; the big lists are in bufA either way)
-        oth = bufA;
-    }
-    span_end(ctx, ev_init);
-
-    RefineArgs r{};
-    r.n = bt.n;
-    r.cnt = bt.n;
-    r.list = cur;
-    r.big = oth;
-    r.tail0 = bufC;
-    r.tail1 = bufD;
-    r.tdst = bt.st_tdst;
-    r.tbase = bt.c_tail;
-    r.mode = bt.st_mode;
-    r.blk = bt.rle;
-    r.bwt = bt.bwt;
-    r.rank = bt.rank;
-    r.sa = bt.sa;
-    r.headp = bt.headp;
-    r.flg = bt.flg;
-    r.tagg = bt.tagg;
-    r.dig = bt.hist;
-    r.c_big = bt.c_big;
-    r.c_small = bt.c_small;
-    r.c_prog = bt.c_prog;
-    r.c_nolist = bt.c_nolist;
-    r.nbig_in = bt.st_nbig;
-    r.S = bt.S;
-    r.TPB = bt.TPB;
-    r.gout = GidOut{bt.gidof, bt.grank, bt.gcount, bt.gwide, bt.S, bt.B, 0u}; // (the initial refinement writes round 0's lists)
-    r.grank = bt.grank;
-    r.gwide = bt.gwide;
-    r.init = 1;
-    r.cstat = reinterpret_cast<u64 *>(bt.hist);
-    r.carry = reinterpret_cast<u64 *>(bt.tagg);
-    r.cpass = ++a.pass;
-    r.err = bt.errflag;
-    r.patient = a.patient;
-    r.lst = oldl;
-    // lists of every block + (rank word, suffix) pairs in list order; the blocks that start in SWEEP mode get their
-    // SA order and digit bases in round 0 (below)
+    void eight_passes(hipStream_t so)
     {
+        hipEvent_t ev_init = span_begin(ctx);
+        if (nOld) {
+            {
+                KSpan ks(ctx, K_BYTE_COUNT, ntotal_old, 2);
+                byte_count<<<dim3(BYTE_SEGS, B), 1024, 0, so>>>(bt.rle, bt.n, bt.dtot, bt.S);
+                active_bases<<<dim3(B), 256, 0, so>>>(bt.dtot, bt.dbase, all, 1);
+            }
+            {
+                KSpan ks(ctx, K_RADIX_INIT, 13 * ntotal_old); // 5 text bytes in, one element out
+                launch_pass<8, GEN_BYTES5>(ctx, so, a, nOld, nmax);
+            }
+            for (int p = 1; p < 8; p++) {
+                a.shift = p < 5 ? 20 + 8 * p : 40 + 8 * (p - 5);
+                a.src = cur;
+                a.dst = oth;
+                KSpan ks(ctx, p == 5 ? K_RADIX_GID : K_RADIX_INIT, (p == 5 ? 20 : 16) * ntotal_old); // (re-key: + one 4-byte gather)
+                if (p == 5)
+                    launch_pass<8, GEN_GID>(ctx, so, a, nOld, nmax);
+                else
+                    launch_pass<8, GEN_LIST>(ctx, so, a, nOld, nmax);
+                std::swap(cur, oth);
+            }
+            if (ctx->profiling) ctx->stats.bwt_sort_elems += 8 * ntotal_old;
+        } else {
+            cur = bufB; // (where the 8 passes leave the sorted list; the big lists are in bufA either way)
+            oth = bufA;
+        }
+        span_end(ctx, ev_init);
+    }
+
+    int initial_sort()
+    {
+        volatile uint32_t *const plan_rec = hsum + (size_t)MAX_ROUNDS * SUMMARY_WORDS;
+        if (use_msd) {
+            BZH_TRY(msd_sort_begin(ctx, B, nmax, ntotal, bufB, bufD, bufA, bufC, binned, false, r0_fused, plan_rec, epoch + 63u, &nOld,
+                                   side ? ctx->side_ev[0] : nullptr, &msd_keep));
+            oldl = Lst{bt.ms_old, bt.ms_cnt + MC_OLD, B};
+            a.lst = oldl;
+        }
+        ntotal_old = nOld == B ? ntotal : ntotal * nOld / B;
+        // A mixed batch: the few blocks on the 8 passes cannot fill the device (one block alone takes ~3 ms for them), so
+        // they run on the second stream beside the bucket-first kernels of the others, from the plan's end on
+        // (msd_sort_begin records side_ev[0] there).
+        const bool old_beside = use_msd && side && nOld && nOld < B;
+        const hipStream_t so = old_beside ? fork(side, false) : st;
+        eight_passes(so);
+
         // list in, one (rank word, suffix) pair out per suffix -- binned by 4096-suffix window of the rank array, into
         // sa|headp, which nobody needs before round 0 -- plus the list records of the unresolved ones (their bytes are
         // added when round 0's summary is in); the blocks that start in SWEEP mode get SA order and digit bases in
-        // round 0 (below).  rank_apply then writes the rank array as whole lines.
+        // round 0 (run_S).  rank_apply then writes the rank array as whole lines.
+        r.list = cur;
+        r.big = oth;
+        r.cpass = ++a.pass;
+        r.lst = oldl;
         r.bpass = ++a.pass;
         if (nOld) {
             KSpan ks(ctx, K_REFINE_INIT, 24 * ntotal_old);
             r.dig = reinterpret_cast<uint32_t *>(bt.flg); // (the digit rows of the initial refinement: the flag bytes are free, `hist` holds its look-back words)
             r.dig_stride = bt.S / 4;
-            launch_refine_one<true>(ctx, r, nOld, nmax, binned);
+            launch_refine_one<true>(ctx, so, r, nOld, nmax, binned);
             r.dig = bt.hist;
             r.dig_stride = 0;
         }
-        if (old_beside) {
-            ctx->stream = st;
-            hipEventRecord(ctx->side_ev[1], side);
-        }
+        if (old_beside) done(side);
         if (use_msd) { // the rest of the bucket-first sort: deeper levels if level 1 left any, the finishing kernel
-            BZH_TRY(msd_sort_finish(ctx, st, msd_keep, ntotal, hrec0 + (size_t)MAX_ROUNDS * SUMMARY_WORDS, epoch + 63u, &msd_deeper));
-        static const bool trace_init = getenv("BZH_TRACE_ROUNDS") != nullptr;
-        if (trace_init) { // (debugging aid: waits for the device)
-            uint32_t c[MS_CNT_WORDS];
-            if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(c, bt.ms_cnt, sizeof c, hipMemcpyDeviceToHost) == hipSuccess)
-                fprintf(stderr, "[bzhip] initial sort: %u blocks bucket-first, %u blocks 8-pass; %u units; %.1f %% of the suffixes in oversized 2-byte buckets; oversized buckets per level %u %u %u %u %u (tiles %u %u %u %u %u)\n",
-                        c[MC_NEW], c[MC_OLD], c[MC_UNITS], 100.0 * 1024.0 * c[23] / (double)std::max<uint64_t>(1, ntotal), c[MC_SEGS + 1], c[MC_SEGS + 2], c[MC_SEGS + 3], c[MC_SEGS + 4], c[MC_SEGS + 5],
-                        c[MC_ITEMS + 1], c[MC_ITEMS + 2], c[MC_ITEMS + 3], c[MC_ITEMS + 4], c[MC_ITEMS + 5]);
-            if (c[32] | c[35])
-                fprintf(stderr, "[bzhip] chunk_finish, 16-cycle ticks over all workgroups: ticket+load+bucket index %u, ranking %u, stage scatter+barrier %u, reload %u, heads+suffix table %u, suffixes+extents+bins %u, keys+bin scan %u, all pairs %u, rank pairs out %u, lists out %u\n",
-                        c[32], c[33], c[34], c[35], c[36], c[37], c[38], c[39], c[40], c[41]);
+            BZH_TRY(msd_sort_finish(ctx, st, msd_keep, ntotal, plan_rec, epoch + 63u, &msd_deeper));
+            if (sw.trace) { // (debugging aid: waits for the device)
+                uint32_t c[MS_CNT_WORDS];
+                if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(c, bt.ms_cnt, sizeof c, hipMemcpyDeviceToHost) == hipSuccess)
+                    fprintf(stderr, "[bzhip] initial sort: %u blocks bucket-first, %u blocks 8-pass; %u units; %.1f %% of the suffixes in oversized 2-byte buckets; oversized buckets per level %u %u %u %u %u (tiles %u %u %u %u %u)\n",
+                            c[MC_NEW], c[MC_OLD], c[MC_UNITS], 100.0 * 1024.0 * c[23] / (double)std::max<uint64_t>(1, ntotal), c[MC_SEGS + 1], c[MC_SEGS + 2], c[MC_SEGS + 3], c[MC_SEGS + 4], c[MC_SEGS + 5],
+                            c[MC_ITEMS + 1], c[MC_ITEMS + 2], c[MC_ITEMS + 3], c[MC_ITEMS + 4], c[MC_ITEMS + 5]);
+                if (c[32] | c[35])
+                    fprintf(stderr, "[bzhip] chunk_finish, 16-cycle ticks over all workgroups: ticket+load+bucket index %u, ranking %u, stage scatter+barrier %u, reload %u, heads+suffix table %u, suffixes+extents+bins %u, keys+bin scan %u, all pairs %u, rank pairs out %u, lists out %u\n",
+                            c[32], c[33], c[34], c[35], c[36], c[37], c[38], c[39], c[40], c[41]);
+            }
         }
-        }
-        if (old_beside) hipStreamWaitEvent(st, ctx->side_ev[1], 0); // the main stream goes on only behind the second stream's work
+        join_side();
         KSpan ks(ctx, K_RANK_APPLY, 12 * ntotal);
         rank_apply<<<dim3((nmax + APPLY_W - 1) / APPLY_W, B), 256, 0, st>>>(binned, bt.n, bt.rank, bt.S);
-    }
-    { // the big lists of the first round are in `oth`
-        u64 *t = cur;
-        cur = oth;
-        oth = t;
-    }
-    r.init = 0;
-    r.cnt = bt.gateR;
-    if (mid_on) {
-        r.mid_np = bt.ms_np;
-        r.mid_spans = msc_row(bt.ms_cnt, B, MSR_SPANS);
-        r.mid_tiles = msc_tiles(bt.ms_cnt, B);
-        r.mid_ntiles = msc_row(bt.ms_cnt, B, MSR_MTILES);
-    }
-    // (greedy packing: two neighbouring tiles hold more than SORT_TILE records, so a list of L records makes at most
-    // 2 L / SORT_TILE + 1 tiles -- the bound refine_one's launch is sized with when such blocks exist)
-    auto refine_bound = [&](uint32_t maxcnt) { return mid_on ? (2u * ((maxcnt + SORT_TILE - 1) / SORT_TILE) + 1u) * SORT_TILE : maxcnt; };
-
-    TailArgs ta{};
-    ta.n = bt.n;
-    ta.len = bt.st_ntail; // (gateT carries the QUAD bit; the plain length lives here)
-    ta.buf0 = bufC; // a block's small-group list moves between bufC and bufD, one hop per round in which it is worked on
-    ta.buf1 = bufD; // (round_begin keeps track per block: st_tdst)
-    ta.tdst = bt.st_tdst;
-    ta.rank = bt.rank;
-    ta.c_tail = bt.c_tail;
-    ta.c_prog = bt.c_prog;
-    ta.err = bt.errflag;
-    ta.hb = bt.st_h;
-    ta.S = bt.S;
-#ifdef BZH_EXPERIMENTS
-    ta.dbg = getenv("BZH_TAIL_DBG") ? (uint32_t)atoi(getenv("BZH_TAIL_DBG")) : 0u;
-#endif
-
-    // ---- doubling rounds, queued one ahead of the summaries ---------------------------------------------
-    // round_begin writes its summary straight into pinned host memory and sets the record's last word to
-    // round + 1 behind a system-scope release: no copy, no event -- the host looks at the word.
-    // (The word also carries the number of this call: the round_begin queued last by the call before may still
-    // be on its way when this one starts.)
-    volatile uint32_t *hsum = hrec0; // [MAX_ROUNDS][SUMMARY_WORDS] (+ one record of the initial sort's plan)
-    auto wait_summary = [&](uint32_t rd, uint32_t *out) -> hipError_t { // normally there already
-        volatile uint32_t *rec = hsum + (size_t)rd * SUMMARY_WORDS;
-        const uint32_t want = epoch + rd + 1u;
-        int idle = 0;
-        for (uint64_t it = 0; rec[SUMMARY_WORDS - 1] != want; it++) {
-            if ((it & 0xFFFu) == 0xFFFu) { // a kernel fault would leave us here for ever: ask the stream now and then
-                const hipError_t e = hipStreamQuery(st);
-                if (e != hipSuccess && e != hipErrorNotReady) return e;
-                if (e == hipSuccess && ++idle > 64) return hipErrorUnknown; // stream drained, still no record
-            }
-            __builtin_ia32_pause();
+        std::swap(cur, oth); // the big lists of the first round are in `oth`
+        r.init = 0;
+        r.cnt = bt.gateR;
+        if (mid_on) {
+            r.mid_np = bt.ms_np;
+            r.mid_spans = msc_row(bt.ms_cnt, B, MSR_SPANS);
+            r.mid_tiles = msc_tiles(bt.ms_cnt, B);
+            r.mid_ntiles = msc_row(bt.ms_cnt, B, MSR_MTILES);
         }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        for (int k = 0; k < SUMMARY_WORDS; k++) out[k] = rec[k];
-        return hipSuccess;
-    };
-    static const bool trace = getenv("BZH_TRACE_ROUNDS") != nullptr;
-    // A block on the 8 passes with fewer than n / 256 groups after them starts in SWEEP mode (BZH_SWEEP_DIV: A/B timing).
-    // Rounds 2-3 drew the line at n / 8; measured in round 4 (scripts/gpu_sweep_ab.py): the periodic and run-heavy inputs
-    // SWEEP mode exists for have a few hundred to a thousand times fewer groups than suffixes and do not care (they
-    // break at n / 2048), while merely repetitive text is 3-9 % faster in SPLIT mode (real text with every block on the
-    // 8 passes 15.85 -> 14.60 ms, with the buckets 14.73 -> 14.36 ms: two of its blocks keep the 8 passes).
-    static const uint32_t sweep_div = getenv("BZH_SWEEP_DIV") ? (uint32_t)atoi(getenv("BZH_SWEEP_DIV")) : 256u;
-    // bounds for the launches of the round being queued (exact lists live on the device)
-    uint32_t nS = B, nA = B, nT = B, nQ = B, maxS = nmax, maxA = nmax, maxT = nmax;
-    // do the blocks of mid_sort / the blocks of the global passes have big lists?  (round 0: what the initial sort's plan says;
-    // later: the sums of the last summary -- a big list only shrinks, and only a block in SWEEP mode can still join the others)
-    bool have_mid = mid_on, have_glob = !mid_on || nOld != 0u || msd_deeper;
-    uint32_t err = 0;
-    bool finished = false;
-    uint32_t s[SUMMARY_WORDS];
+        return BZH_OK;
+    }
 
     // -- blocks in SWEEP mode: three look-back passes; the last refine left the digit bases (sweep_bases)
-    auto run_S = [&](uint32_t round) {
+    void run_S(uint32_t round)
+    {
         if (!nS) return;
         KSpan ks(ctx, K_SWEEP, 0, 3);
+        const Lst ls{bt.actS, bt.nlist + L_S, B};
         if (round == 0) {
             // round_begin has just picked the blocks that start in SWEEP mode: SA order, heads by position and digit rows are
             // there (refine_one<init> leaves them for every block on the 8 passes); the rows become the bases of the passes
@@ -2914,93 +2934,50 @@ int bwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal, bool is_re
             r0.cnt = bt.n;
             r0.dig = reinterpret_cast<uint32_t *>(bt.flg);
             r0.dig_stride = bt.S / 4;
-            r0.lst = Lst{bt.actS, bt.nlist + L_S, B};
+            r0.lst = ls;
             sweep_bases<<<dim3(nS), 768, 0, st>>>(r0, bt.dbase); // (before period_probe: it uses the flag bytes next)
         }
-        {
-            // near-periodic blocks are finished in this round (period_probe sets their depth to "h >= n")
-            ProbeArgs pr{bt.rle, bt.n, bt.rank, bt.sa, bt.headp, bt.st_h, bt.chain, reinterpret_cast<uint32_t *>(bt.listD),
-                         bt.flg, bt.S, Lst{bt.actS, bt.nlist + L_S, B}};
-            period_probe<<<dim3(nS), 1024, 0, st>>>(pr);
-        }
-        a.lst = Lst{bt.actS, bt.nlist + L_S, B};
+        // near-periodic blocks are finished in this round (period_probe sets their depth to "h >= n")
+        const ProbeArgs pr{bt.rle, bt.n, bt.rank, bt.sa, bt.headp, bt.st_h, bt.chain, reinterpret_cast<uint32_t *>(bt.listD), bt.flg, bt.S, ls};
+        period_probe<<<dim3(nS), 1024, 0, st>>>(pr);
+        a.lst = ls;
         a.cnt = bt.n; // enumerate SA positions
         a.shift = 40;
         a.doff = 0;
         a.src = nullptr;
         a.dst = cur;
         hipEvent_t e0 = span_begin(ctx);
-        launch_pass<7, GEN_SWEEP>(ctx, a, nS, nmax);
+        launch_pass<7, GEN_SWEEP>(ctx, st, a, nS, nmax);
         a.cnt = bt.gateS;
         a.shift = 47;
         a.doff = 128;
         a.src = cur;
         a.dst = oth;
-        launch_pass<7, GEN_LIST>(ctx, a, nS, maxS);
+        launch_pass<7, GEN_LIST>(ctx, st, a, nS, maxS);
         a.shift = 54;
         a.doff = 256;
         a.src = oth;
         a.dst = cur;
-        launch_pass<7, GEN_LIST>(ctx, a, nS, maxS);
+        launch_pass<7, GEN_LIST>(ctx, st, a, nS, maxS);
         span_end(ctx, e0);
-    };
+    }
+
     // -- SPLIT-mode blocks with large groups: re-key the big list once, then five look-back passes on bits
     //    20..59; gen: cur -> oth, passes: oth -> cur -> oth -> cur -> oth -> cur
     // The big-list path (re-key + five passes) and the small-group kernel of a round touch different lists, and the
     // one thing they share -- the rank array, read by the first, written by the second -- keeps both versions of a
     // word (rank_at), so the two run side by side: the big-list path on a second stream between two events.  (With
     // profiling on everything stays on one stream, or the per-kernel spans would overlap.)
-    bool side_busy = false, side2_busy = false;
-    auto join_side = [&]() { // the main stream goes on only behind what the side streams were given
-        if (side_busy) hipStreamWaitEvent(st, ctx->side_ev[1], 0);
-        if (side2_busy) hipStreamWaitEvent(st, ctx->side_ev[2], 0);
-        side_busy = side2_busy = false;
-    };
-    // An error return hands the context back: nothing of this call may still be running on the second stream
-    // against the arena when the next call queues its memsets (bzh_debug_fault promises a usable context).
-    auto fail_wait = [&](hipError_t e) -> int {
-        if (side_busy && side) hipStreamSynchronize(side);
-        if (side2_busy && side2) hipStreamSynchronize(side2);
-        side_busy = side2_busy = false;
-        ctx->stream = st;
-        bzh_set_error(ctx, "%s:%d waiting for a round summary -> %s", __FILE__, __LINE__, hipGetErrorString(e));
-        return BZH_E_HIP;
-    };
-    // The tiles of the NEXT round's big lists, planned as soon as this round's refinement has written them -- on the second
-    // stream, beside round_begin: mid_sort can then start with its round (a plan queued in front of it started it late, when
-    // tail_round held every CU's LDS, and it waited for room: 374 us for 2 M records).
-    auto plan_ahead = [&](uint32_t round) {
-        if (!(mid_on && have_mid)) return;
-        KSpan ks(ctx, K_MID_SORT, 0);
-        Msd mp = msd_keep;
-        mp.runq = msc_row(bt.ms_cnt, B, MSR_RUNQ + ((round + 1u) & 1u));
-        mp.runs = msc_runs(bt.ms_cnt, B, (round + 1u) & 1u);
-        hipStream_t sp = st;
-        if (side) {
-            hipEventRecord(ctx->side_ev[0], st);
-            hipStreamWaitEvent(side, ctx->side_ev[0], 0);
-            sp = side;
-        }
-        mid_plan<<<dim3(B), 256, 0, sp>>>(mp, 0u);
-        if (side) { // (the plan is part of what the second stream was given: join_side, fail_wait and the end of the sort wait for it)
-            hipEventRecord(ctx->side_ev[1], side);
-            side_busy = true;
-        }
-    };
-    auto run_A = [&](uint32_t round) {
+    void run_A(uint32_t round)
+    {
         const uint32_t gt = (maxA + SORT_TILE - 1) / SORT_TILE;
         if (!nA || !gt) return;
-        hipStream_t sa = st;
+        const bool mid = mid_on && have_mid, global_path = !mid_on || have_glob;
         // (round 0 with mid_sort alone -- no block for the global passes, no small-group kernel beside it: it stays on the main
         // stream, a fork and a join between streams are 20 us)
-        const bool alone = round == 0 && mid_on && have_mid && !have_glob && r0_fused && nOld == 0;
+        const bool alone = round == 0 && mid && !have_glob && r0_fused && nOld == 0;
         const bool forked = side && !alone;
-        if (forked) {
-            hipEventRecord(ctx->side_ev[0], st);
-            hipStreamWaitEvent(side, ctx->side_ev[0], 0);
-            sa = side;
-            ctx->stream = side; // (launch_pass launches on the context's stream)
-        }
+        hipStream_t sa = forked ? fork(side) : st;
         a.lst = Lst{bt.actA, bt.nlist + L_A, B};
         a.cnt = bt.gateA;
         a.src = cur;
@@ -3013,7 +2990,6 @@ int bwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal, bool is_re
         // Round 0 has the device to itself (the small groups of a bucket-first block sit it out): two workgroups a CU, and
         // the few blocks left to the global passes run them on the main stream; from round 1 on tail_round runs beside it
         // and needs room on every CU: one workgroup a CU.
-        const bool mid = mid_on && have_mid;
         if (mid) {
             KSpan ks(ctx, K_MID_SORT, 0); // (the tiles were planned behind the refinement that wrote the lists: plan_ahead)
             MidArgs ma{cur, bt.rank, bt.st_h, bt.gateA, a.tag, msc_tiles(bt.ms_cnt, B), msc_row(bt.ms_cnt, B, MSR_MTILES), msc_row(bt.ms_cnt, B, MSR_SPANS),
@@ -3023,71 +2999,56 @@ int bwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal, bool is_re
 #endif
             mid_sort<<<dim3(round ? 256 : 512), MS_THREADS, 0, sa>>>(ma);
         }
-        const bool global_path = !mid_on || have_glob;
         a.mid_np = mid_on ? bt.ms_np : nullptr;
         a.mid_spans = mid_on ? msc_row(bt.ms_cnt, B, MSR_SPANS) : nullptr;
         bool on_side2 = false;
         if (mid && forked && round == 0) {
             sa = st;
-            ctx->stream = st;
         } else if (mid && forked && side2 && global_path) { // (from round 1 on the main stream is tail_round's: a third stream)
-            hipStreamWaitEvent(side2, ctx->side_ev[0], 0);
-            sa = side2;
-            ctx->stream = side2;
+            sa = fork(side2, false);
             on_side2 = true;
         }
         if (global_path) {
-        // A large group has more than TAIL_G members (and a group that spans several units of the initial sort draws one
-        // number a unit: at most two more per 8192 records), so a list of at most 250,000 records cannot run out of
-        // GID_MAX numbers: the fifth pass is then not even launched.
-        const int npass = maxA <= 250000u ? 4 : 5;
-        a.only4 = npass == 4 ? 1u : 0u;
-        {
-            KSpan ks(ctx, K_ACTIVE_GEN, 0, 2);
-            active_gen<<<dim3(xcd_grid(a.T, nA)), SORT_THREADS, 0, sa>>>(a, bt.dtot);
-            active_bases<<<dim3(nA), 256, 0, sa>>>(bt.dtot, bt.dbase, a.lst, 5);
+            // A large group has more than TAIL_G members (and a group that spans several units of the initial sort draws one
+            // number a unit: at most two more per 8192 records), so a list of at most 250,000 records cannot run out of
+            // GID_MAX numbers: the fifth pass is then not even launched.
+            const int npass = maxA <= 250000u ? 4 : 5;
+            a.only4 = npass == 4 ? 1u : 0u;
+            {
+                KSpan ks(ctx, K_ACTIVE_GEN, 0, 2);
+                active_gen<<<dim3(xcd_grid(a.T, nA)), SORT_THREADS, 0, sa>>>(a, bt.dtot);
+                active_bases<<<dim3(nA), 256, 0, sa>>>(bt.dtot, bt.dbase, a.lst, 5);
+            }
+            // five passes on [rank][key2] from `oth` (where active_gen put the re-keyed list) -- or, the groups being numbered
+            // densely (the usual case, decided on the device: *gwide), four passes on [number][key2] from `cur` (active_gen wrote
+            // in place); either way the sorted list ends in `cur`
+            u64 *c = oth, *o = cur;
+            hipEvent_t e0 = span_begin(ctx);
+            KSpan ks(ctx, K_RADIX_ROUNDS, 0, 5);
+            a.has_n = 1u;
+            for (int p = 0; p < npass; p++) {
+                a.shift = 20 + 8 * p;
+                a.doff = 256 * p;
+                a.src = c;
+                a.dst = o;
+                a.src_n = p < 4 ? o : nullptr; // (the narrow chain runs the other way round: cur -> oth -> cur -> oth -> cur)
+                a.dst_n = p < 4 ? c : nullptr;
+                launch_pass<8, GEN_LIST>(ctx, sa, a, nA, maxA);
+                std::swap(c, o);
+            }
+            a.has_n = 0u;
+            span_end(ctx, e0);
         }
-        // five passes on [rank][key2] from `oth` (where active_gen put the re-keyed list) -- or, the groups being numbered
-        // densely (the usual case, decided on the device: *gwide), four passes on [number][key2] from `cur` (active_gen wrote
-        // in place); either way the sorted list ends in `cur`
-        u64 *c = oth, *o = cur;
-        hipEvent_t e0 = span_begin(ctx);
-        KSpan ks(ctx, K_RADIX_ROUNDS, 0, 5);
-        a.has_n = 1u;
-        // (a large group has more than TAIL_G members: lists of at most GID_MAX * (TAIL_G + 1) records cannot run out of
-        // numbers, and the fifth pass is not even launched)
-        for (int p = 0; p < npass; p++) {
-            a.shift = 20 + 8 * p;
-            a.doff = 256 * p;
-            a.src = c;
-            a.dst = o;
-            a.src_n = p < 4 ? o : nullptr; // (the narrow chain runs the other way round: cur -> oth -> cur -> oth -> cur)
-            a.dst_n = p < 4 ? c : nullptr;
-            launch_pass<8, GEN_LIST>(ctx, a, nA, maxA);
-            u64 *t = c;
-            c = o;
-            o = t;
-        }
-        a.has_n = 0u;
-        span_end(ctx, e0);
-        } // (global_path)
         a.mid_np = a.mid_spans = nullptr;
         if (forked) {
-            ctx->stream = st;
-            hipEventRecord(ctx->side_ev[1], side);
-            side_busy = true;
-            if (on_side2) {
-                hipEventRecord(ctx->side_ev[2], side2);
-                side2_busy = true;
-            }
+            done(side);
+            if (on_side2) done(side2);
         }
-    };
+    }
+
     // -- small groups: one kernel per form (depth x2 / depth x4); survivors move to the other list buffer
-    // (all_quad: the last summary read shows no block in SWEEP mode, none with a big list and every block that holds small
-    // groups on the depth x4 form -- all of which only ever stays so --: the plain form has no block to work on and is not
-    // launched; the depth x4 kernel checks the list it would have had)
-    bool all_quad = false;
-    auto run_T = [&]() {
+    void run_T()
+    {
         const uint32_t tt = (maxT + TR_T - 1) / TR_T;
         if (!nT || !tt) return;
         KSpan ks(ctx, K_TAIL_ROUND, 0, nQ ? 2 : 1);
@@ -3104,9 +3065,52 @@ int bwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal, bool is_re
             ta.lst = Lst{bt.actQ, bt.nlist + L_Q, B};
             tail_round<true><<<dim3(xcd_grid(ta.T, nQ)), TR_THREADS, 0, st>>>(ta);
         }
-    };
-    uint64_t emitted = 0; // rotations whose last-column byte the initial sort wrote (statistics)
-    auto account = [&](const uint32_t *sm) { // statistics of the round a summary describes
+    }
+
+    // (greedy packing: two neighbouring tiles hold more than SORT_TILE records, so a list of L records makes at most
+    // 2 L / SORT_TILE + 1 tiles -- the bound refine_one's launch is sized with when such blocks exist)
+    uint32_t refine_bound(uint32_t maxcnt) const { return mid_on ? (2u * ((maxcnt + SORT_TILE - 1) / SORT_TILE) + 1u) * SORT_TILE : maxcnt; }
+
+    // The tiles of the NEXT round's big lists, planned as soon as this round's refinement has written them -- on the second
+    // stream, beside round_begin: mid_sort can then start with its round (a plan queued in front of it started it late, when
+    // tail_round held every CU's LDS, and it waited for room: 374 us for 2 M records).
+    void plan_ahead(uint32_t round)
+    {
+        if (!(mid_on && have_mid)) return;
+        KSpan ks(ctx, K_MID_SORT, 0);
+        Msd mp = msd_keep;
+        mp.runq = msc_row(bt.ms_cnt, B, MSR_RUNQ + ((round + 1u) & 1u));
+        mp.runs = msc_runs(bt.ms_cnt, B, (round + 1u) & 1u);
+        const hipStream_t sp = side ? fork(side) : st;
+        mid_plan<<<dim3(B), 256, 0, sp>>>(mp, 0u);
+        if (side) done(side); // (the plan is part of what the second stream was given: join_side, fail_wait and the end of the sort wait for it)
+    }
+
+    // -- every block that went through radix passes: flags, group extents, ranks, routing (SWEEP-mode blocks in
+    //    three kernels with SA order and digit counts, the big lists of SPLIT-mode blocks in one)
+    void refine_passes(uint32_t round, uint32_t na, uint32_t maxa)
+    {
+        if (!(nS | na)) return;
+        r.list = cur;
+        r.big = oth;
+        if (nS) {
+            r.cpass = ++a.pass;
+            r.lst = Lst{bt.actS, bt.nlist + L_S, B};
+            KSpan ks(ctx, K_SWEEP, 0, 4);
+            launch_refine(ctx, st, r, nS, maxS, true);
+        }
+        if (na) {
+            r.cpass = ++a.pass;
+            r.lst = Lst{bt.actA, bt.nlist + L_A, B};
+            KSpan ks(ctx, K_REFINE_ROUNDS, 0);
+            launch_refine_one<false>(ctx, st, r, na, refine_bound(maxa));
+            plan_ahead(round);
+        }
+        std::swap(cur, oth);
+    }
+
+    void account(const uint32_t *sm) // statistics of the round a summary describes
+    {
         if (!ctx->profiling) return;
         const uint64_t tot = (uint64_t)sm[8], eS = (uint64_t)sm[10], eAm = (uint64_t)sm[19], eA = (uint64_t)sm[12] - eAm; // (eAm: mid_sort's records, round 0)
         if (sm[2]) { // the big lists of this round: four passes on group numbers, five on ranks (word 11)
@@ -3126,182 +3130,179 @@ int bwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal, bool is_re
             // byte gathered, one byte stored each; bwt_emit stores the rest)
             emitted = ntotal > tot ? ntotal - tot : 0;
             ctx->k_bytes[nOld == B ? K_REFINE_INIT : K_MSD_FINISH] += emitted * 2;
+            ctx->k_bytes[nOld == B ? K_REFINE_INIT : K_MSD_FINISH] += tot * 8 + (uint64_t)sm[13] * 8; // the list records the initial refinement wrote + the 8 text bytes each member of a small group was keyed on
         }
-        if (sm[0] == 0) ctx->k_bytes[nOld == B ? K_REFINE_INIT : K_MSD_FINISH] += tot * 8 + (uint64_t)sm[13] * 8; // the list records the initial refinement wrote + the 8 text bytes each member of a small group was keyed on
-    };
+    }
 
-    for (uint32_t round = 0; round < (uint32_t)MAX_ROUNDS; round++) {
-        a.tag = 1u + round % 31u; // (a block is at work for fewer than 31 rounds: its depth doubles every time)
-        // the numbers of the large groups: this round's lists carry the half written by the round before; this round's
-        // refinement draws the numbers of the next round's groups into the other half
-        a.gwide = r.gwide = bt.gwide + (round & 1u);
-        r.grank = bt.grank + (size_t)(round & 1u) * bt.B * GID_MAX;
-        r.gout.par = (round + 1u) & 1u;
-        if (mid_on) { // (the runs this round's refinement writes are the next round's list)
-            r.mid_runq = msc_row(bt.ms_cnt, B, MSR_RUNQ + ((round + 1u) & 1u));
-            r.mid_runs = msc_runs(bt.ms_cnt, B, (round + 1u) & 1u);
+    // The summary of round rd: where every block stood when that round began.  round_begin writes it straight into pinned
+    // host memory and sets the record's last word to rd + 1 behind a system-scope release: no copy, no event -- the host
+    // looks at the word.  (The word also carries the number of this attempt: the round_begin queued last by the call
+    // before may still be on its way when this one starts.)  Ends the rounds (`finished` or `err`), or bounds the next
+    // round's launches.
+    int read_summary(uint32_t rd)
+    {
+        volatile uint32_t *rec = hsum + (size_t)rd * SUMMARY_WORDS;
+        const uint32_t want = epoch + rd + 1u;
+        int idle = 0;
+        for (uint64_t it = 0; rec[SUMMARY_WORDS - 1] != want; it++) { // normally there already
+            if ((it & 0xFFFu) == 0xFFFu) { // a kernel fault would leave us here for ever: ask the stream now and then
+                const hipError_t e = hipStreamQuery(st);
+                if (e != hipSuccess && e != hipErrorNotReady) return fail_wait(e);
+                if (e == hipSuccess && ++idle > 64) return fail_wait(hipErrorUnknown); // stream drained, still no record
+            }
+            __builtin_ia32_pause();
         }
-        {
-        KSpan ks(ctx, K_ROUND_BEGIN, 0);
-        round_begin<<<1, (B + 63u) / 64u * 64u, 0, st>>>(bt, B, round, actP,
-                                                          const_cast<uint32_t *>(hsum) + (size_t)round * SUMMARY_WORDS, epoch + round + 1u,
-                                                          sweep_div, r0_fused, mid_on ? 1u : 0u);
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        for (int k = 0; k < SUMMARY_WORDS; k++) s[k] = rec[k];
+        const uint64_t total = (uint64_t)s[8];
+        err |= s[14];
+        if (sw.trace)
+            fprintf(stderr, "[bzhip] round %u h<=%u unresolved=%llu  S blocks=%u (max %u)  A blocks=%u (max %u, %s)  T blocks=%u (quad %u, max %u)\n",
+                    s[0], s[15], (unsigned long long)total, s[1], s[5], s[2], s[6], s[11] ? "on ranks" : "on group numbers", s[3], s[4], s[7]);
+        if (err) return BZH_OK; // a kernel reported an internal error: nothing after it can be trusted
+        if (total == 0) { // nothing was left when round rd began (round 0: the initial sort resolved everything)
+            finished = true;
+            return BZH_OK;
         }
+        ctx->stats.bwt_rounds = std::max<uint64_t>(ctx->stats.bwt_rounds, rd + 1u);
+        account(s);
+        // One round on: SWEEP blocks can only leave; their unresolved suffixes may turn up in the big or the
+        // small lists; big lists shrink, small lists gain at most what the big lists lose.
+        // SWEEP blocks only leave that mode with lists in hand: cS of them wrote lists in the round before.
+        const uint32_t pS = s[1], pA = s[2], pT = s[3], mS = s[5], mA = s[6], mT = s[7], cS = s[16];
+        have_mid = mid_on && s[19] != 0u;
+        have_glob = !mid_on || s[12] != s[19] || pS != 0u || cS != 0u;
+        nS = pS;
+        maxS = mS;
+        nA = std::min(B, pA + cS);
+        maxA = std::max(mA, cS ? mS : 0u);
+        nT = std::min(B, pT + pA + cS);
+        nQ = nT;
+        maxT = std::min(nmax, mT + std::max(mA, cS ? mS : 0u));
+        all_quad = rd > 0 && pS == 0u && pA == 0u && cS == 0u && pT != 0u && s[4] == pT; // (not from round 0's: round 1 launches the plain form)
+        return BZH_OK;
+    }
+
+    // Round 0.  Nothing is known yet, and text-like batches have no block in SWEEP mode: the big-list and small-group
+    // paths go first with full-size launches (they take a millisecond), by then round 0's own summary is there and the
+    // SWEEP path runs with exact sizes -- or, mostly, not at all.
+    int round_zero()
+    {
+        run_A(0);
+        if (!(r0_fused && nOld == 0)) run_T(); // (every block on the bucket-first sort: all small groups sit round 0 out -- not even an empty launch)
+        BZH_TRY(read_summary(0));
+        if (finished || err) return BZH_OK;
+        run_S(0);
+        join_side();
+        refine_passes(0, s[2], s[6]); // (round 0's exact figures: nA / maxA bound round 1 already)
+        return BZH_OK;
+    }
+
+    // A later round, bounded by the summary of the round before the previous one (round 1: by round 0's).
+    int later_round(uint32_t round)
+    {
         if (round > 1) {
-            // the summary of the PREVIOUS round: where every block stood when that round began
-            if (const hipError_t we = wait_summary(round - 1, s); we != hipSuccess) return fail_wait(we);
-            const uint64_t total = (uint64_t)s[8];
-            err |= s[14];
-            if (trace)
-                fprintf(stderr, "[bzhip] round %u h<=%u unresolved=%llu  S blocks=%u (max %u)  A blocks=%u (max %u, %s)  T blocks=%u (quad %u, max %u)\n",
-                        s[0], s[15], (unsigned long long)total, s[1], s[5], s[2], s[6], s[11] ? "on ranks" : "on group numbers", s[3], s[4], s[7]);
-            if (err) break; // a kernel reported an internal error: nothing after it can be trusted
-            if (total == 0) { // nothing was left when round-1 began: it and this round_begin were no-ops
-                finished = true;
-                break;
-            }
-            ctx->stats.bwt_rounds = (uint64_t)round > ctx->stats.bwt_rounds ? (uint64_t)round : ctx->stats.bwt_rounds;
-            account(s);
-            // One round on: SWEEP blocks can only leave; their unresolved suffixes may turn up in the big or the
-            // small lists; big lists shrink, small lists gain at most what the big lists lose.
-            // SWEEP blocks only leave that mode with lists in hand: cS of them wrote lists in the round before.
-            const uint32_t pS = s[1], pA = s[2], pT = s[3], mS = s[5], mA = s[6], mT = s[7], cS = s[16];
-            have_mid = mid_on && s[19] != 0u;
-            have_glob = !mid_on || s[12] != s[19] || pS != 0u || cS != 0u;
-            nS = pS;
-            maxS = mS;
-            nA = std::min(B, pA + cS);
-            maxA = std::max(mA, cS ? mS : 0u);
-            nT = std::min(B, pT + pA + cS);
-            nQ = nT;
-            maxT = std::min(nmax, mT + std::max(mA, cS ? mS : 0u));
-            all_quad = pS == 0u && pA == 0u && cS == 0u && pT != 0u && s[4] == pT;
-        }
-        if (round == 0) {
-            // Nothing is known yet, and text-like batches have no block in SWEEP mode: the big-list and small-group
-            // paths go first with full-size launches (they take a millisecond), by then round 0's own summary is
-            // there and the SWEEP path runs with exact sizes -- or, mostly, not at all.
-            run_A(0);
-            if (!(r0_fused && nOld == 0)) run_T(); // (every block on the bucket-first sort: all small groups sit round 0 out -- not even an empty launch)
-            if (const hipError_t we = wait_summary(0, s); we != hipSuccess) return fail_wait(we);
-            const uint64_t total = (uint64_t)s[8];
-            err |= s[14];
-            if (trace)
-                fprintf(stderr, "[bzhip] round %u h<=%u unresolved=%llu  S blocks=%u (max %u)  A blocks=%u (max %u, %s)  T blocks=%u (quad %u, max %u)\n",
-                        s[0], s[15], (unsigned long long)total, s[1], s[5], s[2], s[6], s[11] ? "on ranks" : "on group numbers", s[3], s[4], s[7]);
-            if (total == 0) { // the initial sort resolved everything
-                finished = true;
-                break;
-            }
-            ctx->stats.bwt_rounds = std::max<uint64_t>(ctx->stats.bwt_rounds, 1);
-            account(s);
-            nS = s[1];
-            maxS = s[5];
-            run_S(0);
-            // exact figures of round 0 from here on (they also bound round 1, as above)
-            const uint32_t pA = s[2], pT = s[3], mA = s[6], mT = s[7], cS = s[16];
-            nA = pA;
-            maxA = mA;
-            have_mid = mid_on && s[19] != 0u;
-            have_glob = !mid_on || s[12] != s[19] || s[1] != 0u || cS != 0u;
-            join_side();
-            if (nS | nA) {
-                r.list = cur;
-                r.big = oth;
-                if (nS) {
-                    r.cpass = ++a.pass;
-                    r.lst = Lst{bt.actS, bt.nlist + L_S, B};
-                    KSpan ks(ctx, K_SWEEP, 0, 4);
-                    launch_refine(ctx, r, nS, maxS, true);
-                }
-                if (nA) {
-                    r.cpass = ++a.pass;
-                    r.lst = Lst{bt.actA, bt.nlist + L_A, B};
-                    KSpan ks(ctx, K_REFINE_ROUNDS, 0);
-                    launch_refine_one<false>(ctx, r, nA, refine_bound(maxA));
-                    plan_ahead(0);
-                }
-                std::swap(cur, oth);
-            }
-            // bounds of round 1
-            nA = std::min(B, pA + cS);
-            maxA = std::max(mA, cS ? maxS : 0u);
-            nT = std::min(B, pT + pA + cS);
-            nQ = nT;
-            maxT = std::min(nmax, mT + std::max(mA, cS ? maxS : 0u));
-            continue;
+            BZH_TRY(read_summary(round - 1));
+            if (finished || err) return BZH_OK;
         }
         run_S(round);
         run_A(round);
         run_T();
         join_side();
-        // -- every block that went through radix passes: flags, group extents, ranks, routing (SWEEP-mode blocks in
-        //    three kernels with SA order and digit counts, the big lists of SPLIT-mode blocks in one)
-        if (nS | nA) {
-            r.list = cur;
-            r.big = oth;
-            if (nS) {
-                r.cpass = ++a.pass;
-                r.lst = Lst{bt.actS, bt.nlist + L_S, B};
-                KSpan ks2(ctx, K_SWEEP, 0, 4);
-                launch_refine(ctx, r, nS, maxS, true);
+        refine_passes(round, nA, maxA);
+        return BZH_OK;
+    }
+
+    // ---- doubling rounds, queued one ahead of the summaries
+    int rounds()
+    {
+        have_mid = mid_on;
+        have_glob = !mid_on || nOld != 0u || msd_deeper;
+        for (uint32_t round = 0; round < (uint32_t)MAX_ROUNDS; round++) {
+            a.tag = 1u + round % 31u; // (a block is at work for fewer than 31 rounds: its depth doubles every time)
+            // the numbers of the large groups: this round's lists carry the half written by the round before; this round's
+            // refinement draws the numbers of the next round's groups into the other half
+            a.gwide = r.gwide = bt.gwide + (round & 1u);
+            r.grank = bt.grank + (size_t)(round & 1u) * bt.B * GID_MAX;
+            r.gout.par = (round + 1u) & 1u;
+            if (mid_on) { // (the runs this round's refinement writes are the next round's list)
+                r.mid_runq = msc_row(bt.ms_cnt, B, MSR_RUNQ + ((round + 1u) & 1u));
+                r.mid_runs = msc_runs(bt.ms_cnt, B, (round + 1u) & 1u);
             }
-            if (nA) {
-                r.cpass = ++a.pass;
-                r.lst = Lst{bt.actA, bt.nlist + L_A, B};
-                KSpan ks(ctx, K_REFINE_ROUNDS, 0);
-                launch_refine_one<false>(ctx, r, nA, refine_bound(maxA));
-                plan_ahead(round);
+            {
+                KSpan ks(ctx, K_ROUND_BEGIN, 0);
+                round_begin<<<1, (B + 63u) / 64u * 64u, 0, st>>>(bt, B, round, actP, const_cast<uint32_t *>(hsum) + (size_t)round * SUMMARY_WORDS,
+                                                                  epoch + round + 1u, SWEEP_DIV, r0_fused, mid_on ? 1u : 0u);
             }
-            std::swap(cur, oth);
+            BZH_TRY(round == 0 ? round_zero() : later_round(round));
+            if (finished || err) break;
         }
+        join_side();
+        if (!finished && !err) { // MAX_ROUNDS is far beyond log2(n) + the rounds queued ahead
+            HIP_TRY(ctx, bzh_stream_wait(st));
+            bzh_set_error(ctx, "BWT: the doubling rounds did not terminate (internal error)");
+            return BZH_E_HIP;
+        }
+        if (err) HIP_TRY(ctx, bzh_stream_wait(st)); // (what was queued behind the faulty kernel ends before the error is reported)
+        return BZH_OK;
     }
-    join_side();
-    if (!finished && !err) { // MAX_ROUNDS is far beyond log2(n) + the rounds queued ahead
-        HIP_TRY(ctx, bzh_stream_wait(st));
-        bzh_set_error(ctx, "BWT: the doubling rounds did not terminate (internal error)");
-        return BZH_E_HIP;
+
+    // ---- the error report, or the last column of every block
+    int finish()
+    {
+        // (the last summary read is the one of a round that found nothing to do: every kernel before it has run, so
+        // its error word and its sum of unresolved suffixes are final)
+        ctx->stats.bwt_active_sum += (uint64_t)s[17] | ((uint64_t)s[18] << 32);
+        if (err) {
+            bzh_set_error(ctx, err & 8   ? "BWT: the bucket-first initial sort broke one of its invariants (internal error)"
+                               : err & 4 ? "BWT: a launch was sized for fewer blocks or tiles than the round had (internal error)"
+                               : err & 2 ? "BWT: a look-back gave up waiting (internal error)"
+                                         : "BWT: a small-group window saw a group larger than its guarantee (internal error)");
+            return BZH_E_HIP;
+        }
+        uint32_t gx = std::clamp((nmax + 1023) / 1024, 1u, 256u);
+        if (few_blocks(B)) gx |= WG_SPREAD;
+        KSpan ks(ctx, K_BWT_EMIT, 6 * ntotal - emitted); // rank word and text byte in for every rotation, one byte out for those not yet written
+        bwt_emit<<<dim3(xcd_grid(gx, B)), 256, 0, st>>>(bt, gx, B);
+        period_expand<<<dim3(PX_WGS, B), 1024, 0, st>>>(bt, bt.pshrink);
+        HIP_TRY(ctx, hipGetLastError());
+        return BZH_OK;
     }
-    if (err) HIP_TRY(ctx, bzh_stream_wait(st)); // (what was queued behind the faulty kernel ends before the error is reported)
-    // A look-back that gave up although nothing was injected: seen only when several PROCESSES compute on this GPU at once
-    // and a launch covers few blocks (few_blocks: fewer than 6; fewer than 32 when this was seen).  Their tiles are dealt over
-    // all XCDs, so a tile may wait for a predecessor that is still queued on another XCD -- whose slots another process's workgroups hold, waiting in the same
-    // way for tiles queued behind ours.  Blocks pinned to one XCD each (the mapping of larger batches) only ever wait for
-    // workgroups that are resident already.  The sort starts from bt.rle and re-initialises everything it uses, so it is
-    // simply run again with that mapping, which this context then keeps.
-    // (Whatever else the kernels behind the give-up reported -- they ran on garbage lists -- does not matter: the sort
-    // restarts from bt.rle and clears the error word.)
-    if ((err & 2u) && !had_fault && !ctx->no_spread) { // (late rounds of a large batch also launch over few blocks)
+};
+
+// Suffix-sort and emit the last column for blocks 0..B-1 of the batch (bt.rle / bt.n filled).
+// nmax = largest block length in the batch, ntotal = sum of block lengths (statistics only).
+int bwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal)
+{
+    if (B == 0) return BZH_OK;
+    // (what a second attempt must not count twice)
+    const bzh_stats stats_in = ctx->stats;
+    const size_t spans_in = ctx->sort_spans.size(), kspans_in = ctx->kspans.size();
+    uint64_t kb_in[K_COUNT], kl_in[K_COUNT];
+    memcpy(kb_in, ctx->k_bytes, sizeof kb_in);
+    memcpy(kl_in, ctx->k_launch, sizeof kl_in);
+    for (bool retry = false;; retry = true) {
+        SortAttempt at(ctx, B, nmax, ntotal);
+        BZH_TRY(at.clear(retry));
+        BZH_TRY(at.initial_sort());
+        BZH_TRY(at.rounds());
+        // A look-back that gave up although nothing was injected: seen only when several PROCESSES compute on this GPU at once
+        // and a launch covers few blocks (few_blocks: fewer than 6; fewer than 32 when this was seen).  Their tiles are dealt over
+        // all XCDs, so a tile may wait for a predecessor that is still queued on another XCD -- whose slots another process's workgroups hold, waiting in the same
+        // way for tiles queued behind ours.  Blocks pinned to one XCD each (the mapping of larger batches) only ever wait for
+        // workgroups that are resident already.  The sort starts from bt.rle and re-initialises everything it uses, so it is
+        // simply run again with that mapping, which this context then keeps (no_spread: so there is one second attempt at most).
+        // (Whatever else the kernels behind the give-up reported -- they ran on garbage lists -- does not matter: the sort
+        // restarts from bt.rle and clears the error word.)  Late rounds of a large batch also launch over few blocks.
+        if (!(at.err & 2u) || at.had_fault || ctx->no_spread) return at.finish();
         ctx->no_spread = true;
         ctx->stats = stats_in; // the abandoned attempt is not counted
         ctx->sort_spans.resize(spans_in);
         ctx->kspans.resize(kspans_in);
         memcpy(ctx->k_bytes, kb_in, sizeof kb_in);
         memcpy(ctx->k_launch, kl_in, sizeof kl_in);
-        static const bool say = getenv("BZH_TRACE_ROUNDS") != nullptr;
-        if (say) fprintf(stderr, "[bzhip] a look-back gave up: the suffix sort runs again with every block on one XCD\n");
-        return bwt_run(ctx, B, nmax, ntotal, true);
+        if (bwt_switches().trace) fprintf(stderr, "[bzhip] a look-back gave up: the suffix sort runs again with every block on one XCD\n");
     }
-    // (the last summary read is the one of a round that found nothing to do: every kernel before it has run, so
-    // its error word and its sum of unresolved suffixes are final)
-    ctx->stats.bwt_active_sum += (uint64_t)s[17] | ((uint64_t)s[18] << 32);
-    if (err) {
-        bzh_set_error(ctx, err & 8   ? "BWT: the bucket-first initial sort broke one of its invariants (internal error)"
-                           : err & 4 ? "BWT: a launch was sized for fewer blocks or tiles than the round had (internal error)"
-                           : err & 2 ? "BWT: a look-back gave up waiting (internal error)"
-                                     : "BWT: a small-group window saw a group larger than its guarantee (internal error)");
-        return BZH_E_HIP;
-    }
-
-    uint32_t gx = (nmax + 1023) / 1024;
-    if (gx > 256) gx = 256;
-    if (gx == 0) gx = 1;
-    if (few_blocks(B)) gx |= WG_SPREAD;
-    KSpan ks(ctx, K_BWT_EMIT, 6 * ntotal - emitted); // rank word and text byte in for every rotation, one byte out for those not yet written
-    bwt_emit<<<dim3(xcd_grid(gx, B)), 256, 0, st>>>(bt, gx, B);
-    period_expand<<<dim3(PX_WGS, B), 1024, 0, st>>>(bt, bt.pshrink);
-    HIP_TRY(ctx, hipGetLastError());
-    return BZH_OK;
 }
 
 
@@ -3395,7 +3396,7 @@ int unbwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax)
     HIP_TRY(ctx, hipMemsetAsync(bt.dtot, 0, (size_t)B * DB_STRIDE * sizeof(uint32_t), st));
     byte_count<<<dim3(BYTE_SEGS, B), 1024, 0, st>>>(bt.bwt, bt.n, bt.dtot, bt.S);
     active_bases<<<dim3(B), 256, 0, st>>>(bt.dtot, bt.dbase, all, 1);
-    launch_pass<8, GEN_LCOL>(ctx, a, B, nmax);
+    launch_pass<8, GEN_LCOL>(ctx, st, a, B, nmax);
     UnbwtArgs u{};
     u.L = bt.bwt;
     u.n = bt.n;

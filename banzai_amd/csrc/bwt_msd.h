@@ -1639,22 +1639,14 @@ static int msd_sort_begin(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntot
 #endif
     m.force_old = force_old ? 1u : 0u;
     m.fuse = fuse;
-    {
-        static const bool init_msd = []() {
-            const char *e = getenv("BZH_INIT");
-            return e && !strcmp(e, "msd");
-        }();
-        m.force_new = init_msd ? 1u : 0u;
-    }
-    {   // (16 = cycles per phase of chunk_finish, bit-exact; the bits that leave work out exist with -DBZH_EXPERIMENTS only)
-        static const uint32_t msd_dbg = getenv("BZH_MSD_DBG") ? (uint32_t)atoi(getenv("BZH_MSD_DBG")) : 0u;
+    m.force_new = bwt_switches().init_msd ? 1u : 0u;
+    // (BZH_MSD_DBG: 16 = cycles per phase of chunk_finish, bit-exact; the bits that leave work out exist with -DBZH_EXPERIMENTS only)
 #ifdef BZH_EXPERIMENTS
-        m.dbg = msd_dbg;
+    m.dbg = bwt_switches().msd_dbg;
 #else
-        m.dbg = msd_dbg & 16u;
+    m.dbg = bwt_switches().msd_dbg & 16u;
 #endif
-    }
-    // (bt.ms_cnt, bt.ms_bincur and bt.ms_bgcur arrive cleared: bwt_run's one clearing launch)
+    // (bt.ms_cnt, bt.ms_bincur and bt.ms_bgcur arrive cleared: SortAttempt::clear, bwt.hip)
     {
         KSpan ks(ctx, K_MSD_PLAN, force_old ? 0 : ntotal, 2);
         if (!force_old) {

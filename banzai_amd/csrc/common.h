@@ -293,7 +293,7 @@ struct bzh_ctx {
     bzh_stats stats{};
     uint32_t debug_fault = 0;         // bzh_debug_fault: fault to inject into the next suffix sort
     bool no_spread = false;           // look-back kernels keep every block on one XCD (set for good after a look-back gave up: bwt_run)
-    uint32_t bwt_epoch = 0;           // calls of bwt_run so far (tags the round summaries in pinned memory)
+    uint32_t bwt_epoch = 0;           // suffix-sort attempts so far (SortAttempt: tags the round summaries in pinned memory)
     std::vector<hipEvent_t> evpool;
     size_t evnext = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> sort_spans;
@@ -501,7 +501,7 @@ __device__ __forceinline__ int block_excl_min_rev(int v, int *lds)
 }
 
 // ---- stage entry points (host side, defined in the stage files) ---------------------------------
-int bwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal, bool is_retry = false); // bwt.hip
+int bwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal); // bwt.hip
 int unbwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax);               // bwt.hip: inverse transform, bt.bwt/ptr -> bt.mtfpos
 int unbwt_compare(bzh_ctx *ctx, uint32_t B, uint32_t nmax, unsigned long long *d_acc); // bwt.hip: bt.rle vs bt.mtfpos
 int mtf_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal = 0); // mtf.hip (ntotal: statistics only)
