@@ -2861,6 +2861,14 @@ struct SortAttempt {
     int initial_sort()
     {
         volatile uint32_t *const plan_rec = hsum + (size_t)MAX_ROUNDS * SUMMARY_WORDS;
+        if (sw.trace) { // (debugging aid: waits for period_detect) the blocks sorted as a few of their periods
+            std::vector<uint32_t> pr((size_t)B * 4);
+            if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(pr.data(), bt.pshrink, pr.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess)
+                for (uint32_t b = 0; b < B; b++)
+                    if (pr[(size_t)b * 4] & 1u)
+                        fprintf(stderr, "[bzhip] block %u: near-periodic, sorted as %u periods of %u bytes + %u (n %u)\n", b, pr[(size_t)b * 4 + 3],
+                                pr[(size_t)b * 4 + 1], pr[(size_t)b * 4 + 2] % pr[(size_t)b * 4 + 1], pr[(size_t)b * 4 + 2]);
+        }
         if (use_msd) {
             BZH_TRY(msd_sort_begin(ctx, B, nmax, ntotal, bufB, bufD, bufA, bufC, binned, false, r0_fused, plan_rec, epoch + 63u, &nOld,
                                    side ? ctx->side_ev[0] : nullptr, &msd_keep));
@@ -2901,11 +2909,21 @@ struct SortAttempt {
                     fprintf(stderr, "[bzhip] initial sort: %u blocks bucket-first, %u blocks 8-pass; %u units; %.1f %% of the suffixes in oversized 2-byte buckets; oversized buckets per level %u %u %u %u %u (tiles %u %u %u %u %u)\n",
                             c[MC_NEW], c[MC_OLD], c[MC_UNITS], 100.0 * 1024.0 * c[23] / (double)std::max<uint64_t>(1, ntotal), c[MC_SEGS + 1], c[MC_SEGS + 2], c[MC_SEGS + 3], c[MC_SEGS + 4], c[MC_SEGS + 5],
                             c[MC_ITEMS + 1], c[MC_ITEMS + 2], c[MC_ITEMS + 3], c[MC_ITEMS + 4], c[MC_ITEMS + 5]);
+                // per block: which initial sort, its units, a group that spans several units; and whether levels 2-5 ran
+                std::vector<uint32_t> np(B), nu(B), sp(B);
+                if (hipMemcpy(np.data(), bt.ms_np, B * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess &&
+                    hipMemcpy(nu.data(), bt.ms_cnt + MS_CNT_WORDS, B * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess &&
+                    hipMemcpy(sp.data(), msc_row(bt.ms_cnt, B, MSR_SPANS), B * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess) {
+                    fprintf(stderr, "[bzhip] initial sort: levels 2-5 %s\n", msd_deeper ? "ran" : "skipped");
+                    for (uint32_t b = 0; b < B; b++)
+                        fprintf(stderr, "[bzhip] initial sort, block %u: %s, %u units, spans %u\n", b, np[b] ? "bucket-first" : "8-pass", nu[b], sp[b]);
+                }
                 if (c[32] | c[35])
                     fprintf(stderr, "[bzhip] chunk_finish, 16-cycle ticks over all workgroups: ticket+load+bucket index %u, ranking %u, stage scatter+barrier %u, reload %u, heads+suffix table %u, suffixes+extents+bins %u, keys+bin scan %u, all pairs %u, rank pairs out %u, lists out %u\n",
                             c[32], c[33], c[34], c[35], c[36], c[37], c[38], c[39], c[40], c[41]);
             }
         }
+        if (sw.trace && !use_msd) fprintf(stderr, "[bzhip] initial sort: 0 blocks bucket-first, %u blocks 8-pass (the batch rule)\n", B);
         join_side();
         KSpan ks(ctx, K_RANK_APPLY, 12 * ntotal);
         rank_apply<<<dim3((nmax + APPLY_W - 1) / APPLY_W, B), 256, 0, st>>>(binned, bt.n, bt.rank, bt.S);
@@ -3014,6 +3032,7 @@ struct SortAttempt {
             // GID_MAX numbers: the fifth pass is then not even launched.
             const int npass = maxA <= 250000u ? 4 : 5;
             a.only4 = npass == 4 ? 1u : 0u;
+            if (sw.trace) fprintf(stderr, "[bzhip] round %u: global passes over big lists of at most %u records: %d passes\n", round, maxA, npass);
             {
                 KSpan ks(ctx, K_ACTIVE_GEN, 0, 2);
                 active_gen<<<dim3(xcd_grid(a.T, nA)), SORT_THREADS, 0, sa>>>(a, bt.dtot);

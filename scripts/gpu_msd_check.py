@@ -1,10 +1,11 @@
 """The two initial sorts of the suffix sorter (argv[1] = msd: bucket-first, banzai_amd/csrc/bwt_msd.h, the default; lsd: the 8
 passes for every block) against the oracle: last column + origin
 pointer of single blocks and whole streams at levels 2, 5 and 9 (level 1's blocks keep the 8-pass path), over inputs
-that reach every part of it -- text (units of packed small buckets, oversized buckets split level by level), runs of
-one byte (a bucket that stays oversized through all five levels: the "one group" units), repetitive blocks (kept on
-the 8-pass path by the sample test), random bytes (all 65,536 buckets: the window packing), short and tiny blocks,
-mixed batches.  Run by tests/test_gpu_parity.py::test_bucket_first_initial_sort in a process of its own: the switch is
+that reach many parts of it -- text (units of packed small buckets, oversized buckets split level by level), runs of
+one byte and other repetitive blocks (kept on the 8-pass path by the sample test; the indented code and the periodic
+block are near-periodic and sorted as a few of their periods), random bytes (more than MS_NE_MAX buckets: the 8 passes),
+short and tiny blocks, mixed batches.  Which path each block takes: tests/bwt_paths_model.py (test_gpu_msd_check_blocks);
+the blocks that reach a group spanning several units, and every other edge of the plan, are in tests/test_gpu_bwt_edges.py.  Run by tests/test_gpu_parity.py::test_bucket_first_initial_sort in a process of its own: the switch is
 read once per process.  Exit code 1 on any mismatch."""
 import os
 import sys
