@@ -4,6 +4,7 @@ Mirrors the public surface of jgbyrne/banzai v0.3.1 (reference lib/lib.rs:84-153
 
     encode(reader, writer, level) -> bytes consumed      (lib/lib.rs:84-132)
     encode_file(in_path, out_path) -> bytes consumed     (lib/lib.rs:141-153, level 9)
+    encode_many(inputs, level) -> [bytes]               (encode() once per input, in one GPU pass)
 
 Everything is computed by hand-written HIP kernels behind the C ABI in include/bzhip.h
 (libbzhip.so); there is no CPU path.  `reader` is any object with .read(), `writer` any object
@@ -13,7 +14,7 @@ import io
 
 from . import _native
 
-__all__ = ["encode", "encode_file", "Context", "MultiContext", "BzhError"]
+__all__ = ["encode", "encode_many", "encode_file", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
 MultiContext = _native.MultiContext
@@ -22,6 +23,8 @@ BzhError = _native.BzhError
 _ctx_cache = {}
 _multi_cache = {}
 READ_CHUNK = 16 << 20
+# encode_many: bytes (+ one per input) of one bzh_encode_many call -- the plan's 32-bit position range (include/bzhip.h)
+MANY_GROUP_LIMIT = 0xFFFF0000
 
 
 def _ctx(level, device=0):
@@ -126,6 +129,34 @@ def encode(reader, writer, level, device=0, devices=None):
     if hasattr(writer, "flush"):
         writer.flush()
     return ctx.stream_consumed()
+
+
+def encode_many(inputs, level, device=0):
+    """bzip2-encode every item of `inputs` (bytes-like) into a stream of its own -> [bytes], stream k bit-identical to what
+    encode() writes for item k alone.  One pass on the GPU per group of inputs (bzh_encode_many): groups stay inside the
+    plan's position range, MANY_GROUP_LIMIT bytes with one more per input."""
+    if isinstance(level, bool) or not isinstance(level, int) or not 1 <= level <= 9:
+        raise ValueError("level must be in 1..=9")
+    views = []
+    for x in inputs:
+        if isinstance(x, str):
+            raise TypeError("encode_many takes bytes-like items, not str")
+        try:
+            views.append(memoryview(x).cast("B"))
+        except TypeError:
+            raise TypeError(f"encode_many takes bytes-like items, not {type(x).__name__}") from None
+    if not views:
+        return []
+    ctx = _ctx(level, device)
+    out, group, size = [], [], 0
+    for v in views:
+        if group and size + len(v) + 1 > MANY_GROUP_LIMIT:
+            out.extend(ctx.encode_many(group))
+            group, size = [], 0
+        group.append(v)
+        size += len(v) + 1
+    out.extend(ctx.encode_many(group))
+    return out
 
 
 def encode_file(in_path, out_path, device=0, devices=None):

@@ -66,6 +66,12 @@ SIGNATURES = {
     "bzh_encode": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u8p, ctypes.c_size_t, szp, szp]),
     "bzh_encode_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                          ctypes.c_size_t, szp, szp]),
+    "bzh_encode_many_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, szp, ctypes.c_size_t, ctypes.c_void_p,
+                                              ctypes.c_size_t, szp, szp]),
+    "bzh_encode_many": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(u8p), szp, ctypes.c_size_t, u8p, ctypes.c_size_t,
+                                       szp, szp]),
+    "bzh_encode_many_bound": (ctypes.c_size_t, [ctypes.c_int, szp, ctypes.c_size_t]),
+    "bzh_plan_many_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, szp, ctypes.c_size_t, szp]),
     "bzh_stream_begin": (ctypes.c_int, [ctypes.c_void_p]),
     "bzh_stream_feed": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, u8p, ctypes.c_size_t, szp]),
     "bzh_stream_bound": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_size_t]),
@@ -119,6 +125,12 @@ def build(force=False):
 
 _lib = None
 MISSING = []
+
+
+def encode_many_bound(level, lens):
+    """bzh_encode_many_bound: upper bound of the output of bzh_encode_many for these input lengths (0 for a bad level)"""
+    lens = np.ascontiguousarray(lens, dtype=np.uint64)
+    return int(lib().bzh_encode_many_bound(level, ptr(lens, szp) if lens.size else None, lens.size))
 
 
 def lib():
@@ -313,6 +325,40 @@ class Context:
         self.check(lib().bzh_encode(self._h, ptr(a), n, ptr(out), cap, ctypes.byref(olen), ctypes.byref(used)))
         assert used.value == n
         return out[:olen.value].tobytes()
+
+    def encode_many(self, items):
+        """bzh_encode_many: one complete .bz2 stream per item (host buffers, one pass) -> [bytes]"""
+        arrs = [np.frombuffer(x, dtype=np.uint8) for x in items]
+        count = len(arrs)
+        if count == 0:
+            return []
+        lens = np.array([a.size for a in arrs], dtype=np.uint64)
+        ins = (u8p * count)(*[ptr(a) for a in arrs])
+        cap = encode_many_bound(self.level, lens)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        offs = np.zeros(count, dtype=np.uint64)
+        olens = np.zeros(count, dtype=np.uint64)
+        self.check(lib().bzh_encode_many(self._h, ins, ptr(lens, szp), count, ptr(out), cap, ptr(offs, szp), ptr(olens, szp)))
+        return [out[int(o):int(o) + int(n)].tobytes() for o, n in zip(offs, olens)]
+
+    def encode_many_device(self, d_in, lens, d_out, cap):
+        """bzh_encode_many_device on integer device addresses -> (offsets, lengths) of the streams"""
+        lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        count = lens.size
+        offs = np.zeros(max(count, 1), dtype=np.uint64)
+        olens = np.zeros(max(count, 1), dtype=np.uint64)
+        self.check(lib().bzh_encode_many_device(self._h, ctypes.c_void_p(d_in), ptr(lens, szp), count, ctypes.c_void_p(d_out),
+                                                cap, ptr(offs, szp), ptr(olens, szp)))
+        return offs[:count].tolist(), olens[:count].tolist()
+
+    def plan_many_device(self, d_in, lens):
+        """bzh_plan_many_device: the plan of inputs lying back to back at d_in -> [(in_off, in_len, rle_len, crc)] in input
+        order, in_off relative to d_in"""
+        lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        nb = ctypes.c_size_t(0)
+        self.check(lib().bzh_plan_many_device(self._h, ctypes.c_void_p(d_in), ptr(lens, szp), lens.size, ctypes.byref(nb)))
+        self._nblocks = nb.value
+        return self.plan_blocks()
 
     def encode_host_ptr(self, in_ptr, n, out_ptr, cap):
         """bzh_encode on raw host addresses (e.g. pinned buffers): H2D + encode + D2H.  -> stream length."""

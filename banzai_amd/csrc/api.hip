@@ -334,6 +334,8 @@ extern "C" void bzh_destroy(bzh_ctx *ctx)
     }
     if (ctx->arena) hipFree(ctx->arena);
     if (ctx->plan_ws) hipFree(ctx->plan_ws);
+    if (ctx->many_ws) hipFree(ctx->many_ws);
+    if (ctx->many_out) hipFree(ctx->many_out);
     if (ctx->d_stage_in) hipFree(ctx->d_stage_in);
     if (ctx->d_stage_out) hipFree(ctx->d_stage_out);
     if (ctx->h_pinned) hipHostFree(ctx->h_pinned);
@@ -1161,7 +1163,11 @@ extern "C" int bzh_plan_blocks(const bzh_ctx *ctx, bzh_block *out, size_t max_bl
     return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
     if (!ctx || !out) return BZH_E_ARG;
     if (max_blocks < ctx->plan_blocks.size()) return BZH_E_CAP;
-    for (size_t k = 0; k < ctx->plan_blocks.size(); k++) out[k] = ctx->plan_blocks[k];
+    const bool many = ctx->plan_input.size() == ctx->plan_blocks.size(); // (a plan of many inputs: offsets in its guarded buffer)
+    for (size_t k = 0; k < ctx->plan_blocks.size(); k++) {
+        out[k] = ctx->plan_blocks[k];
+        if (many) out[k].in_off -= ctx->plan_input[k];
+    }
     return BZH_OK;
     });
 }
@@ -1389,6 +1395,260 @@ extern "C" int bzh_crc32(bzh_ctx *ctx, const uint8_t *in, size_t n, uint32_t *cr
     });
 }
 
+
+// ================================================================================================
+// Many inputs, one stream each (bzh_encode_many*): N calls of banzai::encode (lib/lib.rs:84-132) in one pass -- one plan over
+// all inputs (rle1_plan_many), then batches of blocks of any inputs, laid out, packed and framed on the device
+// (huff_many_batch); the host waits for the plan and, at the end, for the offsets and lengths.  One lane (bzh_set_lanes does
+// not apply).
+// ================================================================================================
+static size_t many_stream_bound(size_t len, size_t M)
+{
+    if (len == 0) return 14 + 3; // "BZh"+level, footer magic, CRC 0; alignment
+    const size_t blocks = len / ((M - 1) * 4 / 5) + 1;
+    const size_t rle = len + len / 4 + blocks * 8; // RLE1 grows by at most 5/4 (+ a run restarted at every cut)
+    // at most one symbol per RLE1 byte + EOB, <= 17 bits each + 6 selector bits per 50 (2.2 bytes cover it), header and tables
+    // of a block < 4,400 bytes (the comment above worst_case_slab, multi.hip), frame, alignment
+    return rle * 22 / 10 + blocks * 4400 + 14 + 3;
+}
+
+extern "C" size_t bzh_encode_many_bound(int level, const size_t *lens, size_t count)
+{
+    if (level < 1 || level > 9 || (count && !lens)) return 0;
+    const size_t M = 100000u * (size_t)level - 1u;
+    size_t sum = 0;
+    for (size_t k = 0; k < count; k++) sum += many_stream_bound(lens[k], M);
+    return sum;
+}
+
+// The inputs' bytes must fit the plan's 32-bit positions together with one guard byte an input (rle1_plan_many).
+static int many_range(bzh_ctx *ctx, const size_t *lens, size_t count, size_t *total)
+{
+    if (count && !lens) {
+        bzh_set_error(ctx, "lens is null");
+        return BZH_E_ARG;
+    }
+    const uint64_t lim = 0xFFFF0000ull;
+    uint64_t tot = count;
+    for (size_t k = 0; k < count; k++) {
+        if (lens[k] > lim || tot + lens[k] > lim) {
+            bzh_set_error(ctx, "%zu inputs exceed the 32-bit position range of one plan (bytes + one per input <= %llu)", count,
+                          (unsigned long long)lim);
+            return BZH_E_ARG;
+        }
+        tot += lens[k];
+    }
+    *total = (size_t)(tot - count);
+    return BZH_OK;
+}
+
+static int many_in_args(bzh_ctx *ctx, const void *d_in, const size_t *lens, size_t count, size_t *total)
+{
+    BZH_TRY(many_range(ctx, lens, count, total));
+    if (*total && !d_in) {
+        bzh_set_error(ctx, "device input is null");
+        return BZH_E_ARG;
+    }
+    return check_in_ptr(ctx, d_in);
+}
+
+extern "C" int bzh_plan_many_device(bzh_ctx *ctx, const void *d_in, const size_t *lens, size_t count, size_t *nblocks)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || !nblocks) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    size_t total = 0;
+    BZH_TRY(many_in_args(ctx, d_in, lens, count, &total));
+    BZH_TRY(rle1_plan_many(ctx, (const uint8_t *)d_in, lens, count));
+    *nblocks = ctx->plan_blocks.size();
+    return BZH_OK;
+    });
+}
+
+static int encode_many(bzh_ctx *ctx, const void *d_in, const size_t *lens, size_t count, void *d_out, size_t cap, size_t *out_offs,
+                       size_t *out_lens)
+{
+    size_t total = 0;
+    BZH_TRY(many_in_args(ctx, d_in, lens, count, &total));
+    if (count && (!d_out || !out_offs || !out_lens)) {
+        bzh_set_error(ctx, "output pointers are null");
+        return BZH_E_ARG;
+    }
+    if (((uintptr_t)d_out & 3u) != 0) {
+        bzh_set_error(ctx, "output buffer must be 4-byte aligned");
+        return BZH_E_ARG;
+    }
+    hipStream_t st = ctx->stream;
+    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
+    ctx->evnext = 0;
+    ctx->sort_spans.clear();
+    kstats_reset(ctx);
+    memset(&ctx->stats, 0, sizeof ctx->stats);
+    if (count == 0) return BZH_OK;
+    if (ctx->profiling) {
+        t0 = bzh_event(ctx);
+        hipEventRecord(t0, st);
+    }
+    BZH_TRY(rle1_plan_many(ctx, (const uint8_t *)d_in, lens, count));
+    if (ctx->profiling) {
+        t1 = bzh_event(ctx);
+        hipEventRecord(t1, st);
+    }
+    // state | offs | lens | body | crc
+    const size_t words = MST_WORDS + 3 * count + (count + 1) / 2;
+    if (words * 8 > ctx->many_out_size) {
+        if (ctx->many_out) hipFree(ctx->many_out);
+        ctx->many_out = nullptr;
+        ctx->many_out_size = 0;
+        if (hipMalloc((void **)&ctx->many_out, words * 8) != hipSuccess) {
+            bzh_set_error(ctx, "hipMalloc(%zu) for the layout of %zu streams failed", words * 8, count);
+            return BZH_E_NOMEM;
+        }
+        ctx->many_out_size = words * 8;
+    }
+    ManyOut mo;
+    mo.state = reinterpret_cast<uint64_t *>(ctx->many_out);
+    mo.offs = mo.state + MST_WORDS;
+    mo.lens = mo.offs + count;
+    mo.body = mo.lens + count;
+    mo.crc = reinterpret_cast<uint32_t *>(mo.body + count);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->many_out, 0, words * 8, st));
+    const size_t nb = ctx->plan_blocks.size();
+    const uint32_t per = ctx->max_batch;
+    BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(nb, 1), per)));
+    ManyBatch mb{};
+    mb.level = (uint32_t)ctx->level;
+    mb.cap_words = cap / 4;
+    int status = BZH_OK;
+    std::vector<std::unique_ptr<RangeJob>> jobs;
+    if (nb == 0) { // every input is empty: no batch, only frames
+        mb.close_hi = mb.hi = (uint32_t)count;
+        status = huff_many_batch(ctx, mb, nullptr, (uint8_t *)d_out, 0, mo);
+    }
+    uint32_t cur = 0; // first input not complete
+    for (size_t k0 = 0; k0 < nb && status == BZH_OK; k0 += per) {
+        auto j = std::make_unique<RangeJob>();
+        j->k0 = k0;
+        j->B = (uint32_t)std::min<size_t>(per, nb - k0);
+        for (uint32_t b = 0; b < j->B; b++) {
+            const bzh_block &pb = ctx->plan_blocks[k0 + b];
+            j->nmax = std::max(j->nmax, pb.rle_len);
+            j->ntotal += pb.rle_len;
+            ctx->stats.rle_bytes += pb.rle_len;
+            ctx->stats.raw_bytes += pb.in_len;
+        }
+        j->mmax = j->nmax + 1; // m <= n + 1 (lib/mtf.rs:36)
+        ctx->stats.blocks += j->B;
+        status = prepare_batch(ctx, *j, false);
+        if (status != BZH_OK) break;
+        const size_t kl = k0 + j->B - 1;
+        const uint32_t il = ctx->plan_input[kl];
+        const bool last = kl + 1 == nb, closes = last || ctx->plan_input[kl + 1] != il;
+        mb.B = j->B;
+        mb.lo = cur;
+        mb.lo_started = (k0 > 0 && ctx->plan_input[k0 - 1] == cur) ? 1u : 0u;
+        mb.close_hi = last ? (uint32_t)count : (closes ? il + 1 : il);
+        mb.hi = closes ? mb.close_hi : il + 1;
+        status = huff_many_batch(ctx, mb, ctx->many_binp + k0, (uint8_t *)d_out, j->mmax, mo);
+        if (ctx->profiling && status == BZH_OK) {
+            j->ev[5] = bzh_event(ctx);
+            hipEventRecord(j->ev[5], st);
+        }
+        cur = mb.close_hi;
+        jobs.push_back(std::move(j));
+    }
+    if (status != BZH_OK) {
+        (void)bzh_stream_wait(st); // (nothing of this call may still run when the error is reported)
+        return status;
+    }
+    ctx->many_host.resize(MST_WORDS + 2 * count);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->many_host.data(), mo.state, ctx->many_host.size() * 8, hipMemcpyDeviceToHost, st));
+    if (ctx->profiling) {
+        t2 = bzh_event(ctx);
+        hipEventRecord(t2, st);
+    }
+    HIP_TRY(ctx, bzh_stream_wait(st));
+    const uint64_t *hs = ctx->many_host.data();
+    if (hs[MST_OVER]) {
+        bzh_set_error(ctx, "output needs %llu bytes, more than the %zu given", (unsigned long long)hs[MST_OFF], cap);
+        return BZH_E_CAP;
+    }
+    for (size_t k = 0; k < count; k++) {
+        out_offs[k] = (size_t)hs[MST_WORDS + k];
+        out_lens[k] = (size_t)hs[MST_WORDS + count + k];
+    }
+    ctx->stats.out_bits = hs[MST_BITS];
+    if (ctx->profiling) {
+        for (auto &jp : jobs) {
+            RangeJob &job = *jp;
+            ctx->stats.ms_rle1 += span_ms(job.ev[0], job.ev[1]);
+            ctx->stats.ms_bwt += span_ms(job.ev[1], job.ev[2]);
+            ctx->stats.ms_mtf += span_ms(job.ev[2], job.ev[3]);
+            ctx->stats.ms_huff += span_ms(job.ev[3], job.ev[4]);
+            ctx->stats.ms_pack += span_ms(job.ev[4], job.ev[5]);
+        }
+        stats_collect_sort(ctx);
+        ctx->stats.ms_plan = span_ms(t0, t1);
+        ctx->stats.ms_total = span_ms(t0, t2);
+    }
+    return BZH_OK;
+}
+
+extern "C" int bzh_encode_many_device(bzh_ctx *ctx, const void *d_in, const size_t *lens, size_t count, void *d_out, size_t cap,
+                                      size_t *out_offs, size_t *out_lens)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return encode_many(ctx, d_in, lens, count, d_out, cap, out_offs, out_lens);
+    });
+}
+
+extern "C" int bzh_encode_many(bzh_ctx *ctx, const uint8_t *const *ins, const size_t *lens, size_t count, uint8_t *out, size_t cap,
+                               size_t *out_offs, size_t *out_lens)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx) return BZH_E_ARG;
+    size_t total = 0;
+    BZH_TRY(many_range(ctx, lens, count, &total));
+    if (count && (!ins || !out || !out_offs || !out_lens)) {
+        bzh_set_error(ctx, "null pointer among ins, out, out_offs, out_lens");
+        return BZH_E_ARG;
+    }
+    for (size_t k = 0; k < count; k++)
+        if (lens[k] && !ins[k]) {
+            bzh_set_error(ctx, "input %zu is null", k);
+            return BZH_E_ARG;
+        }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, total + 16));
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, bzh_encode_many_bound(ctx->level, lens, count) + 16));
+    if (total) { // all inputs in one copy
+        ctx->many_pack.resize(total);
+        size_t pos = 0;
+        for (size_t k = 0; k < count; k++) {
+            if (lens[k]) memcpy(ctx->many_pack.data() + pos, ins[k], lens[k]);
+            pos += lens[k];
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, ctx->many_pack.data(), total, hipMemcpyHostToDevice, st));
+    }
+    BZH_TRY(encode_many(ctx, ctx->d_stage_in, lens, count, ctx->d_stage_out, ctx->stage_out_size & ~(size_t)3, out_offs, out_lens));
+    const size_t need = count ? out_offs[count - 1] + out_lens[count - 1] : 0;
+    if (need > cap) {
+        bzh_set_error(ctx, "output needs %zu bytes, more than the %zu given", need, cap);
+        return BZH_E_CAP;
+    }
+    if (need) {
+        HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, need, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, bzh_stream_wait(st));
+    }
+    return BZH_OK;
+    });
+}
 
 // ================================================================================================
 // Streaming

@@ -202,6 +202,37 @@ struct Timer {
     hipEvent_t a = nullptr, b = nullptr;
 };
 
+// ---- many inputs, one stream each (bzh_encode_many*) ------------------------------------------------------------
+// Stream k lies at byte offs[k] of the output, offs[k+1] = align4(offs[k] + lens[k]).  A stream may span several batches, so the
+// layout is carried from batch to batch in a small device record (many_layout writes it, the next batch's many_layout reads it).
+enum ManyState : int {
+    MST_OFF = 0, // byte offset of the stream the next batch continues or starts (input ManyBatch::lo)
+    MST_BODY,    // its body bits so far (0: not started)
+    MST_CRC,     // its partial CRC fold (crc = block ^ rotl(crc, 1), lib/lib.rs:107-108)
+    MST_ZEROED,  // first output word not yet zeroed
+    MST_OVER,    // 1: some batch did not fit the output (every later pack is gated off)
+    MST_BITS,    // block bits written so far (bzh_stats::out_bits)
+    MST_Z0,      // this batch zeroes words [Z0, Z1)
+    MST_Z1,
+    MST_WORDS    // (record size in 64-bit words)
+};
+struct ManyOut { // device arrays of a call over many inputs: state | offs | lens | body | crc (state, offs, lens: ONE copy back)
+    uint64_t *state; // [MST_WORDS]
+    uint64_t *offs;  // [count] byte offset of every stream
+    uint64_t *lens;  // [count] bytes of every stream
+    uint64_t *body;  // [count] body bits of every stream complete so far (0 for an empty one)
+    uint32_t *crc;   // [count] its stream CRC
+};
+struct ManyBatch { // what the plan tells the host about a batch (kernel argument)
+    uint32_t B;          // blocks
+    uint32_t lo;         // the first input the batch places: the stream it continues or the next one to start
+    uint32_t close_hi;   // inputs [lo, close_hi) are complete behind this batch (offsets, lengths, footers)
+    uint32_t hi;         // inputs [lo, hi) get their offsets: close_hi + 1 while the batch's last stream stays open
+    uint32_t lo_started; // 1: input lo's header was written by an earlier batch
+    uint32_t level;
+    uint64_t cap_words;  // output capacity in 32-bit words
+};
+
 struct bzh_ctx {
     bzh_ctx *parent = nullptr;        // lanes: the context that owns the plan and the arena
     std::vector<bzh_ctx *> lanes;     // two half-batch workers (own stream, half of the arena each)
@@ -241,6 +272,17 @@ struct bzh_ctx {
     std::vector<uint8_t> plan_crc_ok;   // per block: CRC computed (bzh_plan_device_nocrc leaves them to the encoder)
     void *plan_ws = nullptr;            // device scratch of the plan (run tables)
     size_t plan_ws_size = 0;
+    uint32_t plan_extra = 0;            // block records the plan holds beyond one stream's bound (a plan of many inputs: one an input)
+    std::vector<uint32_t> plan_input;   // a plan of many inputs: the input of every block (empty for a plan of one buffer)
+    // many inputs (bzh_encode_many*, rle1_plan_many)
+    uint8_t *many_ws = nullptr;         // device: guarded input buffer, input table, split records, block -> input
+    size_t many_ws_size = 0;
+    uint32_t *many_binp = nullptr;      // [blocks] input of every block of the plan (in many_ws)
+    std::vector<uint32_t> many_tab;     // host copy of the input table (source of an async copy: lives in the context)
+    uint8_t *many_out = nullptr;        // device: ManyOut arrays
+    size_t many_out_size = 0;
+    std::vector<uint64_t> many_host;    // state | offs | lens read back at the end of a call
+    std::vector<uint8_t> many_pack;     // bzh_encode_many: the host inputs back to back (one H2D)
     // staging
     uint8_t *d_stage_in = nullptr;
     size_t stage_in_size = 0;
@@ -513,7 +555,10 @@ int huff_pack_gate(bzh_ctx *ctx, uint32_t B, uint8_t *d_out, uint64_t bit_base, 
                    uint64_t *hostrec, uint32_t tail_bits = 0);
 int huff_frame_stream(bzh_ctx *ctx, uint32_t B, uint8_t *d_out); // huffman.hip: stream header + footer of a one-batch stream, on the device
 int rle1_plan(bzh_ctx *ctx, const uint8_t *d_in, size_t n, bool with_crc = true, bool crc_async = false); // rle1.hip: tables + split from 0
-int rle1_plan_tables(bzh_ctx *ctx, const uint8_t *d_in, size_t n);                 // rle1.hip
+int rle1_plan_tables(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t extra_blocks = 0); // rle1.hip
+int rle1_plan_many(bzh_ctx *ctx, const uint8_t *d_in, const size_t *lens, size_t count); // rle1.hip: plan of many inputs (bzh_plan_many_device)
+// (one batch of a call over many inputs: stream layout, zeroing + capacity gate, pack, frames -- no host in between)
+int huff_many_batch(bzh_ctx *ctx, const ManyBatch &mb, const uint32_t *d_binp, uint8_t *d_out, uint32_t mmax, const ManyOut &mo); // huffman.hip
 int rle1_plan_split(bzh_ctx *ctx, size_t start, bool with_crc, size_t stop, bool crc_async = false); // rle1.hip
 int rle1_plan_crc_join(bzh_ctx *ctx);                                             // rle1.hip: CRCs queued on the side stream -> plan_blocks
 hipStream_t bzh_side_stream(bzh_ctx *ctx);                                        // api.hip: the context's second stream (created once; null: none to be had)

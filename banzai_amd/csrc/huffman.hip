@@ -1015,3 +1015,167 @@ int huff_pack(bzh_ctx *ctx, uint32_t B, uint32_t mmax, uint8_t *d_out, uint64_t 
     HIP_TRY(ctx, hipGetLastError());
     return BZH_OK;
 }
+
+// ================================================================================================================
+// Many streams (bzh_encode_many*): what block_scan, pack_gate and frame_stream do for one stream, for batches whose blocks belong
+// to many streams -- the layout carried from batch to batch in a device record (ManyOut::state), no host in between
+// ================================================================================================================
+__device__ __forceinline__ uint32_t rotl32(uint32_t v, uint32_t r)
+{
+    r &= 31u;
+    return r ? (v << r) | (v >> (32u - r)) : v;
+}
+
+// Inclusive scan of one value per thread over a workgroup of 1,024 threads in v[] (Hillis-Steele, as block_scan); returns the
+// thread's result, v[] holds all of them.
+template <typename T, typename Op>
+__device__ __forceinline__ T scan1024(T *v, T x, Op op)
+{
+    const uint32_t t = threadIdx.x;
+    v[t] = x;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        const T y = t >= d ? v[t - d] : T(0);
+        __syncthreads();
+        if (t >= d) v[t] = op(v[t], y);
+        __syncthreads();
+    }
+    return v[t];
+}
+
+// The layout of one batch (one workgroup; a batch has at most 1,024 blocks).  Per block its global bit offset: 8 offs(s) + 32 +
+// the bits of stream s's blocks before it (for the pack kernels with bit_base 0; replaces block_scan).  Per input the batch
+// places ([lo, hi)): its offset, offs(s+1) = align4(offs(s) + lens(s)), and -- for those it completes -- its length
+// ceil((32 + body + 80) / 8) and its CRC fold; an empty input is the 14-byte stream of body 0 and CRC 0.  Then the words the
+// batch writes (from the first one no earlier batch zeroed: a stream that goes on from the batch before ORs into its last
+// word), the capacity check that gates the pack kernels, and the record the next batch goes on from.
+__global__ void __launch_bounds__(1024) many_layout(Batch bt, const uint32_t *binp, ManyBatch mb, ManyOut mo)
+{
+    __shared__ uint64_t q[1024];
+    __shared__ uint32_t x[1024], segL[1024];
+    __shared__ uint64_t s_open_body;
+    __shared__ uint32_t s_open_crc;
+    const uint32_t t = threadIdx.x, B = mb.B;
+    uint64_t *st = mo.state;
+    const uint64_t off0 = st[MST_OFF], body0 = st[MST_BODY];
+    const uint32_t crc0 = (uint32_t)st[MST_CRC];
+    const bool act = t < B;
+    const uint32_t in = act ? binp[t] : 0xFFFFFFFFu;
+    const uint64_t bits = act ? bt.bits[t] : 0;
+    const uint32_t c = act ? bt.pdesc[t].crc : 0u;
+    // segments = the blocks of one input inside the batch; only the first can go on from the batch before (body0, crc0)
+    x[t] = in;
+    if (t == 0) {
+        s_open_body = 0;
+        s_open_crc = 0;
+    }
+    __syncthreads();
+    const bool segend = act && (t + 1 == B || x[t + 1] != in);
+    const bool first = act && (t == 0 || x[t - 1] != in);
+    __syncthreads();
+    const uint32_t f = scan1024<uint32_t>(x, first ? t : 0u, [](uint32_t a, uint32_t b) { return a > b ? a : b; }); // segment start
+    if (segend) segL[f] = t;
+    const uint64_t Q = scan1024<uint64_t>(q, bits, [](uint64_t a, uint64_t b) { return a + b; });
+    const uint64_t batch_bits = q[1023];
+    const uint64_t before = f ? q[f - 1] : 0;
+    __syncthreads();
+    const uint32_t L = act ? segL[f] : t; // segment end
+    const uint64_t carry = f == 0 ? body0 : 0;
+    const uint64_t rel = Q - bits - before + carry; // bits of the stream before this block
+    // stream CRC: crc = c ^ rotl(crc, 1) in block order, so block t adds rotl(c, L - t) to the fold at the segment's end
+    const uint32_t X = scan1024<uint32_t>(x, act ? rotl32(c, L - t) : 0u, [](uint32_t a, uint32_t b) { return a ^ b; });
+    if (segend) {
+        const uint64_t sbody = Q - before + carry;
+        const uint32_t scrc = X ^ (f ? x[f - 1] : 0u) ^ (f == 0 ? rotl32(crc0, t + 1) : 0u);
+        if (t + 1 < B || in < mb.close_hi) { // the stream is complete
+            mo.body[in] = sbody;
+            mo.crc[in] = scrc;
+        } else { // the batch's last stream goes on in the next batch
+            s_open_body = sbody;
+            s_open_crc = scrc;
+        }
+    }
+    __syncthreads();
+    // offsets of the inputs [lo, hi), 1,024 at a time; the complete ones get their lengths
+    uint64_t base = off0;
+    for (uint32_t j0 = mb.lo; j0 < mb.hi; j0 += 1024) {
+        const uint32_t j = j0 + t;
+        const bool done = j < mb.close_hi;
+        const uint64_t len = done ? (112u + mo.body[j] + 7u) / 8u : 0u;
+        const uint64_t pad = (len + 3u) & ~3ull;
+        const uint64_t inc = scan1024<uint64_t>(q, pad, [](uint64_t a, uint64_t b) { return a + b; });
+        if (j < mb.hi) {
+            mo.offs[j] = base + inc - pad;
+            if (done) mo.lens[j] = len;
+        }
+        base += q[1023];
+        __syncthreads();
+    }
+    if (act) bt.bitoff[t] = 8u * mo.offs[in] + 32u + rel;
+    if (t == 0) {
+        const bool open = mb.hi > mb.close_hi; // (then `base` is the open stream's offset)
+        const uint64_t end_bit = open ? 8u * base + 32u + s_open_body : 8u * base;
+        const uint64_t E = (end_bit + 31u) / 32u, z0 = st[MST_ZEROED];
+        const bool over = st[MST_OVER] != 0 || E > mb.cap_words;
+        st[MST_Z0] = z0;
+        st[MST_Z1] = over ? z0 : E;
+        st[MST_ZEROED] = over ? z0 : E;
+        st[MST_OVER] = over ? 1u : 0u;
+        st[MST_OFF] = base;
+        st[MST_BODY] = open ? s_open_body : 0u;
+        st[MST_CRC] = open ? s_open_crc : 0u;
+        st[MST_BITS] += batch_bits;
+        *bt.packgate = over ? 0u : 1u;
+    }
+}
+
+// Zeroes the words of the batch (many_layout: [Z0, Z1), empty when it does not fit).
+__global__ void __launch_bounds__(256) many_gate(uint32_t *out, const uint64_t *st)
+{
+    const uint64_t z1 = st[MST_Z1];
+    for (uint64_t w = st[MST_Z0] + (uint64_t)blockIdx.x * 256 + threadIdx.x; w < z1; w += (uint64_t)gridDim.x * 256) out[w] = 0u;
+}
+
+// Frames of the inputs the batch places: "BZh" + level in the first word of every stream it starts (lib/lib.rs:18-22; a whole
+// word: the blocks start in the next one), footer magic + stream CRC behind the body of every stream it completes (:66-70).
+__global__ void __launch_bounds__(256) many_frame(uint32_t *out, ManyBatch mb, ManyOut mo, const uint32_t *gate)
+{
+    if (*gate == 0u) return;
+    for (uint32_t j = mb.lo + blockIdx.x * 256 + threadIdx.x; j < mb.hi; j += gridDim.x * 256) {
+        const uint64_t off = mo.offs[j];
+        if (j != mb.lo || !mb.lo_started) out[off / 4] = __builtin_bswap32(0x425A6800u | ('0' + mb.level));
+        if (j < mb.close_hi) {
+            const uint32_t crc = mo.crc[j];
+            const uint32_t words[3] = {0x17724538u, 0x50900000u | (crc >> 16), crc << 16}; // 80 bits
+            const uint64_t pos = 8u * off + 32u + mo.body[j];
+            const uint32_t sh = (uint32_t)(pos & 31u);
+            const uint64_t w0 = pos >> 5;
+            for (int k = 0; k < 3; k++) {
+                const uint32_t hi = words[k] >> sh, lo = sh ? words[k] << (32 - sh) : 0u;
+                if (hi) atomicOr(out + w0 + k, __builtin_bswap32(hi));
+                if (lo) atomicOr(out + w0 + k + 1, __builtin_bswap32(lo));
+            }
+        }
+    }
+}
+
+int huff_many_batch(bzh_ctx *ctx, const ManyBatch &mb, const uint32_t *d_binp, uint8_t *d_out, uint32_t mmax, const ManyOut &mo)
+{
+    Batch &bt = ctx->bt;
+    hipStream_t st = ctx->stream;
+    uint32_t *out = reinterpret_cast<uint32_t *>(d_out);
+    {
+        KSpan ks(ctx, K_PACK, 0, 2);
+        many_layout<<<dim3(1), 1024, 0, st>>>(bt, d_binp, mb, mo);
+        many_gate<<<dim3(2048), 256, 0, st>>>(out, mo.state);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    BZH_TRY(huff_pack(ctx, mb.B, mmax, d_out, 0, true));
+    const uint32_t span = mb.hi - mb.lo;
+    if (span) {
+        KSpan ks(ctx, K_PACK, 0, 1);
+        many_frame<<<dim3(std::min<uint32_t>((span + 255) / 256, 1024)), 256, 0, st>>>(out, mb, mo, bt.packgate);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return BZH_OK;
+}

@@ -551,10 +551,12 @@ struct CutRec {
 // One block cut from input position s (lib/rle.rs:102-253 in closed form, see the head of this file): descriptor + what
 // the emit kernel needs.  Returns the bytes consumed; *origin = lim - M of this cut, the canonical offset the block's
 // budget is counted from (valid unless the budget ran out inside the block's first run: *origin = ~0).
-__device__ __forceinline__ uint32_t cut_block(const PlanArrays &pa, uint32_t lane, uint32_t s, uint64_t total, CutState &cs, CutRec &rec,
-                                              uint64_t *origin)
+// `N`: where the input the block is cut from ends (a run starts there), `total`: the canonical offset at N -- the buffer's end
+// for one stream (cut_block), an input's end inside the guarded buffer of many (plan_many_split).
+__device__ __forceinline__ uint32_t cut_block_to(const PlanArrays &pa, uint32_t lane, uint32_t s, uint32_t N, uint64_t total, CutState &cs,
+                                                 CutRec &rec, uint64_t *origin)
 {
-    const uint32_t N = (uint32_t)pa.n, M = pa.M;
+    const uint32_t M = pa.M;
     const uint32_t e_first = (s / GRAN == cs.idx) ? next_start_in(pa, cs.ev, cs.idx, s) : next_start_after(pa, s, lane);
     const uint32_t Lr = e_first - s;
     const uint32_t A = canon_len(Lr);
@@ -602,6 +604,12 @@ __device__ __forceinline__ uint32_t cut_block(const PlanArrays &pa, uint32_t lan
     rec.ax.open = open;
     rec.ax.pad = 0;
     return consumed;
+}
+
+__device__ __forceinline__ uint32_t cut_block(const PlanArrays &pa, uint32_t lane, uint32_t s, uint64_t total, CutState &cs, CutRec &rec,
+                                              uint64_t *origin)
+{
+    return cut_block_to(pa, lane, s, (uint32_t)pa.n, total, cs, rec, origin);
 }
 
 // ---- the split: SP_W wavefronts cut SP_K blocks each, from starts that are right unless a cut gave bytes away ---------
@@ -1099,12 +1107,13 @@ struct PlanWs { // layout of ctx->plan_ws
 
 static size_t a256(size_t v) { return (v + 255) / 256 * 256; }
 
-static PlanWs plan_layout(uint8_t *base, uint64_t n, uint32_t M)
+// (`extra`: block records beyond the bound of one stream -- a plan over many inputs may cut one more block per input)
+static PlanWs plan_layout(uint8_t *base, uint64_t n, uint32_t M, uint32_t extra)
 {
     PlanWs w{};
     const uint64_t ntiles = (n + RL_TILE - 1) / RL_TILE;
     const uint64_t ngran = ntiles * GRAN_PER_TILE;
-    const uint64_t maxblocks = n / ((uint64_t)(M - 1) * 4 / 5) + 4;
+    const uint64_t maxblocks = n / ((uint64_t)(M - 1) * 4 / 5) + 4 + extra;
     uint8_t *p = base;
     auto take = [&](size_t bytes) {
         uint8_t *r = p;
@@ -1135,7 +1144,7 @@ static PlanWs plan_layout(uint8_t *base, uint64_t n, uint32_t M)
 // 16-byte aligned.  They describe the runs of the input, not the blocks, so they hold for a split that begins at
 // any block start inside the buffer (rle1_plan_split) -- a sharded rank builds them while its first block's start
 // is still on its way from the rank before.
-int rle1_plan_tables(bzh_ctx *ctx, const uint8_t *d_in, size_t n)
+int rle1_plan_tables(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t extra_blocks)
 {
     hipStream_t st = ctx->stream;
     if (ctx->crc_pending) { // (a call that failed before it collected its CRCs: the second stream must be done with the workspace)
@@ -1145,6 +1154,8 @@ int rle1_plan_tables(bzh_ctx *ctx, const uint8_t *d_in, size_t n)
     ctx->plan_blocks.clear();
     ctx->plan_open.clear();
     ctx->plan_crc_ok.clear();
+    ctx->plan_input.clear();
+    ctx->plan_extra = extra_blocks;
     // (the buffer becomes the plan's input only once its tables are queued: a failure below must not leave a later
     // bzh_plan_split_device with a length it accepts and a workspace that is missing or too small)
     ctx->plan_in = nullptr;
@@ -1157,7 +1168,7 @@ int rle1_plan_tables(bzh_ctx *ctx, const uint8_t *d_in, size_t n)
         bzh_set_error(ctx, "input of %zu bytes exceeds the 32-bit position range of one plan", n);
         return BZH_E_ARG;
     }
-    PlanWs probe = plan_layout(nullptr, n, ctx->M);
+    PlanWs probe = plan_layout(nullptr, n, ctx->M, ctx->plan_extra);
     if (probe.bytes > ctx->plan_ws_size) {
         if (ctx->plan_ws) hipFree(ctx->plan_ws);
         ctx->plan_ws = nullptr;
@@ -1168,7 +1179,7 @@ int rle1_plan_tables(bzh_ctx *ctx, const uint8_t *d_in, size_t n)
         }
         ctx->plan_ws_size = probe.bytes;
     }
-    PlanWs w = plan_layout((uint8_t *)ctx->plan_ws, n, ctx->M);
+    PlanWs w = plan_layout((uint8_t *)ctx->plan_ws, n, ctx->M, ctx->plan_extra);
     PlanArrays &pa = w.pa;
     pa.in = d_in;
     KSpan ks(ctx, K_PLAN, 2 * n, 4); // two sweeps of the input
@@ -1199,9 +1210,10 @@ int rle1_plan_split(bzh_ctx *ctx, size_t start, bool with_crc, size_t stop, bool
     ctx->plan_blocks.clear();
     ctx->plan_open.clear();
     ctx->plan_crc_ok.clear();
+    ctx->plan_input.clear();
     if (start > n) return BZH_E_ARG;
     if (n == 0 || start == n) return BZH_OK;
-    PlanWs w = plan_layout((uint8_t *)ctx->plan_ws, n, ctx->M);
+    PlanWs w = plan_layout((uint8_t *)ctx->plan_ws, n, ctx->M, ctx->plan_extra);
     PlanArrays &pa = w.pa;
     pa.in = d_in;
     pa.start = (uint32_t)start;
@@ -1314,7 +1326,7 @@ int rle1_plan_crc(bzh_ctx *ctx, size_t b0, size_t b1)
     while (b1 > b0 && ctx->plan_crc_ok[b1 - 1]) b1--;
     if (b0 == b1) return BZH_OK;
     hipStream_t st = ctx->stream;
-    PlanWs w = plan_layout((uint8_t *)ctx->plan_ws, ctx->plan_n, ctx->M);
+    PlanWs w = plan_layout((uint8_t *)ctx->plan_ws, ctx->plan_n, ctx->M, ctx->plan_extra);
     PlanArrays &pa = w.pa;
     const uint32_t nb = (uint32_t)(b1 - b0);
     uint64_t maxlen = 0;
@@ -1344,7 +1356,7 @@ int rle1_emit(bzh_ctx *ctx, size_t b0, uint32_t B)
 {
     if (B == 0) return BZH_OK;
     const bzh_ctx *pc = ctx->parent ? ctx->parent : ctx; // lanes read the owner's plan
-    PlanWs w = plan_layout((uint8_t *)pc->plan_ws, pc->plan_n, pc->M);
+    PlanWs w = plan_layout((uint8_t *)pc->plan_ws, pc->plan_n, pc->M, pc->plan_extra);
     EmitArgs ea{};
     ea.in = pc->plan_in;
     ea.n = pc->plan_n;
@@ -1382,5 +1394,213 @@ int crc_device(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t *crc_out)
     HIP_TRY(ctx, hipMemcpyAsync(&d, dd, sizeof d, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, bzh_stream_wait(st));
     *crc_out = d.crc;
+    return BZH_OK;
+}
+
+// ================================================================================================================
+// Many inputs in one plan (bzh_plan_many_device, bzh_encode_many*): every input is cut from its own start to its own end
+// ================================================================================================================
+// The inputs are staged in one GUARDED buffer: input k at gs = (its offset among the caller's back-to-back inputs) + k,
+// followed by one guard byte that differs from the input's last byte and from the next input's first.  A run then never
+// continues from one input into the next, so the run tables of rle1_plan_tables describe every input as its own buffer
+// would, and a cut (cut_block_to) only ever takes differences of canonical offsets inside one input.
+struct ManyInput {
+    uint32_t gs;   // first byte in the guarded buffer (its guard is at gs + len)
+    uint32_t len;  // bytes of the input
+    uint32_t slot; // first record slot of the input in the split's record area (room for len / ((M-1) 4/5) + 1 blocks)
+    uint32_t cnt;  // blocks cut (plan_many_split); 0xFFFFFFFF: more than that room
+};
+
+__device__ __forceinline__ uint32_t many_room(uint32_t len, uint32_t M) { return len ? len / ((M - 1u) * 4u / 5u) + 1u : 0u; }
+
+// The guarded buffer from the caller's inputs: one thread per 16 bytes of it (dst is 16-byte aligned and padded to 16).
+__global__ void __launch_bounds__(256) many_stage(const uint8_t *src, uint8_t *dst, uint64_t ng, const ManyInput *inp, uint32_t count)
+{
+    const uint64_t q0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 16;
+    if (q0 >= ng) return;
+    uint32_t lo = 0, hi = count - 1; // the last input whose range [gs, gs + len] starts at or before q0
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1) / 2;
+        if (inp[mid].gs <= q0)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    uint32_t k = lo;
+    ManyInput in = inp[k];
+    uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (uint32_t j = 0; j < 16; j++) {
+        const uint64_t q = q0 + j;
+        if (q < ng) {
+            while (q > (uint64_t)in.gs + in.len) in = inp[++k];
+            uint32_t byte;
+            if (q < (uint64_t)in.gs + in.len) {
+                byte = src[q - k];
+            } else { // the guard: neither the input's last byte nor the next input's first
+                const uint32_t last = in.len ? src[q - 1 - k] : 0x100u;
+                const uint32_t next = (k + 1 < count && inp[k + 1].len) ? src[q - k] : 0x100u;
+                byte = 0;
+                while (byte == last || byte == next) byte++;
+            }
+            w[j >> 2] |= byte << ((j & 3) * 8);
+        }
+    }
+    *reinterpret_cast<uint4 *>(dst + q0) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+constexpr uint32_t MANY_WAVES = 4; // inputs per workgroup of plan_many_split, one wavefront each
+
+// Every input cut from its own start to its own end, one wavefront per input: its guard stands in for n, the canonical offset
+// there for the total, and the "open" rule does not apply (every input is complete).  A cut costs about 2 us (one chain of
+// dependent table reads, as in plan_split); plan_split's speculative windows are not used, so a long input is cut block by block.
+__global__ void __launch_bounds__(64 * MANY_WAVES) plan_many_split(PlanArrays pa, ManyInput *inp, uint32_t count, BlockDesc *sb, BlockAux *sa)
+{
+    const uint32_t lane = threadIdx.x & 63u, k = blockIdx.x * MANY_WAVES + (threadIdx.x >> 6);
+    if (k >= count) return;
+    const ManyInput in = inp[k];
+    const uint32_t room = many_room(in.len, pa.M);
+    uint32_t nb = 0;
+    if (in.len) {
+        const uint32_t N = in.gs + in.len;
+        CutState cs;
+        cs.ev = gran_eval(pa, N / GRAN, lane);
+        cs.idx = N / GRAN;
+        const uint64_t total = __shfl(cs.ev.cpos, (int)(N % GRAN), 64);
+        for (uint32_t s = in.gs; s < N;) {
+            if (nb == room) {
+                nb = 0xFFFFFFFFu;
+                break;
+            }
+            CutRec rec;
+            uint64_t origin;
+            s += cut_block_to(pa, lane, s, N, total, cs, rec, &origin);
+            rec.ax.open = 0;
+            rec.ax.pad = k; // the block's input
+            if (lane == 0) {
+                sb[in.slot + nb] = rec.d;
+                sa[in.slot + nb] = rec.ax;
+            }
+            nb++;
+        }
+    }
+    if (lane == 0) inp[k].cnt = nb;
+}
+
+// The records in input order without gaps, where rle1_emit and the CRC kernels read a plan (one workgroup, 1,024 inputs at a
+// time: the records of input k go behind the blocks of the inputs before it); binp[b] = the input of block b.
+__global__ void __launch_bounds__(1024) plan_many_compact(PlanArrays pa, const ManyInput *inp, uint32_t count, const BlockDesc *sb,
+                                                          const BlockAux *sa, uint32_t *binp)
+{
+    __shared__ uint32_t ls[1024 / 64 + 2];
+    __shared__ uint32_t s_bad;
+    if (threadIdx.x == 0) s_bad = 0;
+    __syncthreads();
+    uint32_t carry = 0;
+    for (uint32_t k0 = 0; k0 < count; k0 += 1024) {
+        const uint32_t k = k0 + threadIdx.x;
+        const ManyInput in = k < count ? inp[k] : ManyInput{0, 0, 0, 0};
+        if (in.cnt == 0xFFFFFFFFu) s_bad = 1;
+        const uint32_t c = in.cnt == 0xFFFFFFFFu ? 0u : in.cnt;
+        uint32_t tot;
+        const uint32_t ex = carry + block_excl_add(c, ls, &tot);
+        for (uint32_t j = 0; j < c && ex + j < pa.maxblocks; j++) {
+            pa.blocks[ex + j] = sb[in.slot + j];
+            pa.aux[ex + j] = sa[in.slot + j];
+            binp[ex + j] = k;
+        }
+        carry += tot;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) *pa.nblocks = (s_bad || carry > pa.maxblocks) ? 0xFFFFFFFFu : carry; // (overflow marker, as plan_split)
+}
+
+// Plan of `count` inputs lying back to back at d_in (16-byte aligned): the guarded buffer, its run tables, every input's split,
+// the records in input order, their CRCs -- one wait.  plan_blocks holds offsets in the GUARDED buffer (what rle1_emit reads);
+// plan_input[b] is the block's input, so its offset in d_in is in_off - plan_input[b].  The caller has checked that
+// total + count fits the plan's positions.
+int rle1_plan_many(bzh_ctx *ctx, const uint8_t *d_in, const size_t *lens, size_t count)
+{
+    hipStream_t st = ctx->stream;
+    uint64_t total = 0;
+    for (size_t k = 0; k < count; k++) total += lens[k];
+    if (total == 0) return rle1_plan_tables(ctx, d_in, 0, 0); // (no blocks: every stream is empty)
+    const uint64_t ng = total + count;
+    const uint32_t D = (ctx->M - 1u) * 4u / 5u;
+    ctx->many_tab.resize(count * 4);
+    ManyInput *tab = reinterpret_cast<ManyInput *>(ctx->many_tab.data());
+    uint64_t pos = 0, slots = 0;
+    for (size_t k = 0; k < count; k++) {
+        tab[k] = ManyInput{(uint32_t)(pos + k), (uint32_t)lens[k], (uint32_t)slots, 0u};
+        slots += lens[k] ? lens[k] / D + 1 : 0;
+        pos += lens[k];
+    }
+    // workspace: guarded buffer | inputs | split records | block -> input (the plan's bound: plan_layout with one extra block an input)
+    const uint64_t maxblocks = ng / D + 4 + count;
+    const size_t o_tab = a256(ng + 32), o_sb = o_tab + a256(count * sizeof(ManyInput)), o_sa = o_sb + a256(slots * sizeof(BlockDesc)),
+                 o_bin = o_sa + a256(slots * sizeof(BlockAux)), bytes = o_bin + a256(maxblocks * 4);
+    if (bytes > ctx->many_ws_size) {
+        if (ctx->many_ws) hipFree(ctx->many_ws);
+        ctx->many_ws = nullptr;
+        ctx->many_ws_size = 0;
+        if (hipMalloc((void **)&ctx->many_ws, bytes) != hipSuccess) {
+            bzh_set_error(ctx, "hipMalloc(%zu) for the plan of %zu inputs failed", bytes, count);
+            return BZH_E_NOMEM;
+        }
+        ctx->many_ws_size = bytes;
+    }
+    uint8_t *gbuf = ctx->many_ws;
+    ManyInput *d_tab = reinterpret_cast<ManyInput *>(ctx->many_ws + o_tab);
+    BlockDesc *d_sb = reinterpret_cast<BlockDesc *>(ctx->many_ws + o_sb);
+    BlockAux *d_sa = reinterpret_cast<BlockAux *>(ctx->many_ws + o_sa);
+    ctx->many_binp = reinterpret_cast<uint32_t *>(ctx->many_ws + o_bin);
+    HIP_TRY(ctx, hipMemcpyAsync(d_tab, tab, count * sizeof(ManyInput), hipMemcpyHostToDevice, st));
+    {
+        KSpan ks(ctx, K_PLAN, 2 * ng, 1);
+        many_stage<<<dim3((uint32_t)((ng + 16 * 256 - 1) / (16 * 256))), 256, 0, st>>>(d_in, gbuf, ng, d_tab, (uint32_t)count);
+    }
+    BZH_TRY(rle1_plan_tables(ctx, gbuf, ng, (uint32_t)count));
+    PlanWs w = plan_layout((uint8_t *)ctx->plan_ws, ng, ctx->M, ctx->plan_extra);
+    PlanArrays &pa = w.pa;
+    pa.in = gbuf;
+    {
+        KSpan ks(ctx, K_PLAN, 0, 2);
+        plan_many_split<<<dim3((uint32_t)((count + MANY_WAVES - 1) / MANY_WAVES)), 64 * MANY_WAVES, 0, st>>>(pa, d_tab, (uint32_t)count, d_sb, d_sa);
+        plan_many_compact<<<dim3(1), 1024, 0, st>>>(pa, d_tab, (uint32_t)count, d_sb, d_sa, ctx->many_binp);
+    }
+    const CrcTables *ct = nullptr;
+    BZH_TRY(crc_tables(ctx, &ct));
+    {
+        KSpan ks(ctx, K_CRC, ng, 2);
+        HIP_TRY(ctx, hipMemsetAsync(w.crcacc, 0, (size_t)pa.maxblocks * 4, st));
+        const uint64_t ranges = ng / ((uint64_t)CRC_TILE * CRC_WG_TILES) + pa.maxblocks + 1;
+        crc_tiles_flat<<<dim3((uint32_t)ranges), RL_THREADS, 0, st>>>(gbuf, pa.blocks, w.crcacc, ct, pa.nblocks);
+        crc_finish<<<dim3(pa.maxblocks), 64, 0, st>>>(pa.blocks, w.crcacc, 0, ct, pa.nblocks);
+    }
+    // blocks | aux | nblocks are consecutive in the workspace (plan_layout): one copy back
+    const size_t span = (size_t)((const uint8_t *)pa.nblocks - (const uint8_t *)pa.blocks) + 4;
+    ctx->plan_host.resize(span);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->plan_host.data(), pa.blocks, span, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, bzh_stream_wait(st));
+    HIP_TRY(ctx, hipGetLastError());
+    uint32_t nb = 0;
+    memcpy(&nb, ctx->plan_host.data() + span - 4, 4);
+    if (nb == 0 || nb == 0xFFFFFFFFu || nb > pa.maxblocks) {
+        bzh_set_error(ctx, "block split of %zu inputs failed (nb=%u)", count, nb);
+        return BZH_E_HIP;
+    }
+    const BlockDesc *hb = reinterpret_cast<const BlockDesc *>(ctx->plan_host.data());
+    const BlockAux *hax = reinterpret_cast<const BlockAux *>(ctx->plan_host.data() + ((const uint8_t *)pa.aux - (const uint8_t *)pa.blocks));
+    ctx->plan_blocks.resize(nb);
+    ctx->plan_input.resize(nb);
+    for (uint32_t b = 0; b < nb; b++) {
+        ctx->plan_blocks[b].in_off = hb[b].in_off;
+        ctx->plan_blocks[b].in_len = hb[b].in_len;
+        ctx->plan_blocks[b].rle_len = hb[b].rle_len;
+        ctx->plan_blocks[b].crc = hb[b].crc;
+        ctx->plan_input[b] = hax[b].pad;
+    }
+    ctx->plan_open.assign(nb, 0);
+    ctx->plan_crc_ok.assign(nb, 1);
     return BZH_OK;
 }

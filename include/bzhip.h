@@ -120,6 +120,32 @@ BZH_API int bzh_encode(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out, 
 BZH_API int bzh_encode_device(bzh_ctx *ctx, const void *d_in, size_t n, void *d_out, size_t cap, size_t *out_len,
                       size_t *consumed);
 
+/* ---- many inputs, one stream each: N calls of banzai::encode in one pass -------------------- */
+
+/* Inputs back to back in d_in (16-byte aligned); input k is lens[k] bytes.  Stream k -- bit-identical to bzh_encode of input k
+ * alone, in either Huffman mode -- is written at d_out + out_offs[k] (host arrays out).  Streams are laid back to back:
+ * out_offs[0] = 0, out_offs[k+1] = align4(out_offs[k] + out_lens[k]), padding bytes zero; an empty input gets the 14-byte empty
+ * stream ("BZh" + level, footer magic, CRC 0).  d_out must be 4-byte aligned and hold the streams' words:
+ * cap >= align4(out_offs[count-1] + out_lens[count-1]), which bzh_encode_many_bound never falls below; otherwise BZH_E_CAP
+ * (known only once everything is encoded).  count == 0 succeeds and writes nothing.  BZH_E_ARG (with bzh_last_error) for a
+ * misaligned d_in or d_out, a null pointer where lengths are non-zero, or inputs whose bytes plus one per input exceed
+ * 0xFFFF0000 (the plan's 32-bit positions).  The call runs on ONE lane (bzh_set_lanes does not apply), joins a streaming pass
+ * in flight like every entry point, and fills bzh_get_stats / bzh_get_kernel_stats as bzh_encode_device does.  After an
+ * error the context stays usable. */
+BZH_API int bzh_encode_many_device(bzh_ctx *ctx, const void *d_in, const size_t *lens, size_t count, void *d_out, size_t cap,
+                                   size_t *out_offs, size_t *out_lens);
+/* Host buffers: ins[k][0..lens[k]) in, the same layout in out (one H2D of all inputs, one pass, one D2H); cap >=
+ * out_offs[count-1] + out_lens[count-1] (else BZH_E_CAP). */
+BZH_API int bzh_encode_many(bzh_ctx *ctx, const uint8_t *const *ins, const size_t *lens, size_t count, uint8_t *out, size_t cap,
+                            size_t *out_offs, size_t *out_lens);
+/* Upper bound of the total output for these lengths at this level (pure host arithmetic; 0 for a bad level): per stream the
+ * blocks' RLE1 bytes (5/4 of the input + 8 a block) x 2.2 bytes (17-bit codes + 6 selector bits per 50 symbols), 4,400 bytes of
+ * header and tables a block, 14 bytes of frame, 3 of alignment. */
+BZH_API size_t bzh_encode_many_bound(int level, const size_t *lens, size_t count);
+/* Seam: the plan alone.  bzh_plan_blocks then lists every input's blocks in input order, in_off relative to d_in; for every
+ * input they equal what bzh_rle1_split returns for that input alone (offsets shifted by where it starts). */
+BZH_API int bzh_plan_many_device(bzh_ctx *ctx, const void *d_in, const size_t *lens, size_t count, size_t *nblocks);
+
 /* ---- streaming: encode() fed by a reader that yields arbitrary chunks (lib/rle.rs:30-92) ------- */
 
 /* Starts a stream on the context.  Then call bzh_stream_feed any number of times; the bytes it
