@@ -142,7 +142,8 @@ struct Batch {
     uint32_t *ms_old, *ms_new; // [B] ids of the blocks on the 8-pass path / on the bucket-first path
     uint32_t *ms_bincur; // [B][256] rank binning: pairs already claimed in each 4096-suffix window
     // MTF / RLE2
-    uint8_t *mtfpos;   // [B][S]   MTF position of every BWT byte
+    uint8_t *mtfpos;   // [B][S]   where the inverse-BWT tooling leaves its blocks (unbwt_run / unbwt_compare, bzh_unbwt: api.hip); MTF + RLE2
+                       //          keep no position per byte (mtf.hip)
     uint8_t *tilelist; // [B][MT][256] recency list at each MTF tile entry
     uint32_t *tinfo;   // [B][MT][4] per-tile zero-run bookkeeping
     uint16_t *syms;    // [B][S+64]
@@ -187,13 +188,13 @@ constexpr uint32_t FX_HDR_BYTES = 64 + 6 * 1152; // + up to 6 delta-coded tables
 enum KClass : int {
     K_PLAN = 0, K_CRC, K_RLE1_EMIT, K_BYTE_COUNT, K_RADIX_INIT, K_RADIX_GID, K_REFINE_INIT, K_RANK_APPLY,
     K_ROUND_BEGIN, K_SWEEP, K_ACTIVE_GEN, K_RADIX_ROUNDS, K_TAIL_ROUND, K_REFINE_ROUNDS, K_BWT_EMIT, K_MTF_LAST,
-    K_MTF_WALK, K_RLE2, K_HUFF, K_PACK, K_MSD_PLAN, K_MSD_SCATTER, K_MSD_LEVELS, K_MSD_FINISH, K_MID_SORT, K_COUNT
+    K_MTF_WALK, K_HUFF, K_PACK, K_MSD_PLAN, K_MSD_SCATTER, K_MSD_LEVELS, K_MSD_FINISH, K_MID_SORT, K_COUNT
 };
 static const char *const KCLASS_NAME[K_COUNT] = {
     "plan (granules, carries, split)", "crc_tiles", "rle1_emit", "byte_count", "radix_scatter (initial sort)",
     "radix_scatter<GID> (re-key pass)", "refine_one<init> (+ rank binning)", "rank_apply", "round_begin",
     "SWEEP path (3 passes + 3-kernel refine)", "active_gen", "radix_scatter (big-list rounds)", "tail_round",
-    "refine_one (rounds)", "bwt_emit", "mtf_tile_last + mtf_prefix", "mtf_walk", "rle2 (tiles, block, emit)",
+    "refine_one (rounds)", "bwt_emit", "mtf_tile_last + mtf_prefix (+ RLE2 layout)", "mtf_walk (+ RLE2 emit)",
     "huffman (segments, build, header)", "pack_symbols", "bigram_hist + bigram_plan", "bigram_scatter (2-byte buckets)",
     "seg_count/plan/scatter (oversized buckets)", "chunk_finish (bucket sort + ranks in LDS)",
     "mid_sort (round 0: large groups in LDS)"};
@@ -450,6 +451,30 @@ __device__ __forceinline__ uint32_t wave_incl_or(uint32_t v)
     v = BZH_DPP_OR(v, 0x118, 0xF); // row_shr:8
     v = BZH_DPP_OR(v, 0x142, 0xA); // row_bcast:15 -> rows 1 and 3
     v = BZH_DPP_OR(v, 0x143, 0xC); // row_bcast:31 -> rows 2 and 3
+    return v;
+}
+// The same doubling for sums and for unsigned maxima (a lane without a source reads 0, the identity of both): inside a row
+// the shifted adds are the plain inclusive scan, then rows 1 and 3 take the total of the row before them, then rows 2 and 3
+// the total of rows 0-1.  Six vector instructions, no LDS crossbar: what a kernel bound by instruction issue wants.
+#define BZH_DPP_SRC(v, ctrl, rowmask) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), (ctrl), (rowmask), 0xF, true))
+__device__ __forceinline__ uint32_t wave_incl_add_dpp(uint32_t v)
+{
+    v += BZH_DPP_SRC(v, 0x111, 0xF);
+    v += BZH_DPP_SRC(v, 0x112, 0xF);
+    v += BZH_DPP_SRC(v, 0x114, 0xF);
+    v += BZH_DPP_SRC(v, 0x118, 0xF);
+    v += BZH_DPP_SRC(v, 0x142, 0xA);
+    v += BZH_DPP_SRC(v, 0x143, 0xC);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_incl_umax_dpp(uint32_t v)
+{
+    v = max(v, BZH_DPP_SRC(v, 0x111, 0xF));
+    v = max(v, BZH_DPP_SRC(v, 0x112, 0xF));
+    v = max(v, BZH_DPP_SRC(v, 0x114, 0xF));
+    v = max(v, BZH_DPP_SRC(v, 0x118, 0xF));
+    v = max(v, BZH_DPP_SRC(v, 0x142, 0xA));
+    v = max(v, BZH_DPP_SRC(v, 0x143, 0xC));
     return v;
 }
 // the value of the lane below (0 into lane 0)

@@ -12,16 +12,21 @@
 // lane c&63, register c>>6); one step = scalar readlane + 4 ballots/popcounts.  A byte equal to
 // the current front symbol (zero run, the common case after a BWT) costs one scalar compare.
 //
-// RLE2 is then fully parallel over the position array: every non-zero position emits the
-// bijective base-2 digits (lib/mtf.rs:46-65) of the zero run that ends just before it, then its
-// own symbol pos+1; offsets by scan; the trailing run and EOB are written by the per-block kernel.
+// RLE2 needs no pass of its own.  A position is non-zero exactly at a run head (a byte that differs from the
+// byte before it; position 0 of a block: from name 0, the front of the initial list), so which positions emit
+// a symbol, the zero run in front of each, its bijective base-2 digits (lib/mtf.rs:46-65) and every output
+// offset follow from the bytes alone: mtf_tile_last counts them per tile, mtf_prefix turns the counts into
+// offsets (and writes the trailing run and EOB), and the walk stores the digits and pos+1 of the run heads it
+// visits anyway, with the symbol histogram.
 #include "common.h"
-#include <cstdlib>
-#include <cstring>
 
-constexpr int RLE_THREADS = 256;
-constexpr int RLE_ITEMS = 16;
-constexpr int RLE_TILE = RLE_THREADS * RLE_ITEMS; // S is a multiple of it: S / RLE_TILE tiles per block
+// RLE2 layout of one MTF tile (mtf_tile_last -> mtf_prefix -> mtf_walk_par)
+struct MtfTile {
+    int first;    // position in the block of the tile's first run head, -1 if none
+    int last;     // of its last one, -1 if none; after mtf_prefix: the last run head BEFORE the tile
+    uint32_t cnt; // symbols the tile emits, not counting the zero-run digits in front of `first`
+    uint32_t off; // after mtf_prefix: output offset of the tile
+};
 
 __device__ __forceinline__ uint32_t run_digits(uint32_t z) // symbols emitted for a zero run of length z
 {
@@ -48,8 +53,13 @@ __device__ __forceinline__ uint32_t build_names(const uint8_t *hasbyte, uint8_t 
     return total;
 }
 
-// ---- per-tile last occurrence (indexed by name) -----------------------------------------------------
-__global__ void __launch_bounds__(256) mtf_tile_last(Batch bt, int32_t *tlast, uint32_t MT, uint32_t TL)
+// ---- per-tile last occurrence (indexed by name) and RLE2 layout -------------------------------------
+// The layout: a run head is a byte that differs from the byte before it (the walk compares names: the same thing, the
+// renaming is one to one on the present bytes).  A run crosses threads, sweeps and tiles, so
+// the zero run in front of a head is measured from the last head before it: a max-scan over the threads, carried from
+// sweep to sweep; the digits in front of the tile's first head wait for mtf_prefix, which knows the last head of the
+// tiles before.
+__global__ void __launch_bounds__(256) mtf_tile_last(Batch bt, int32_t *tlast, MtfTile *rt, uint32_t MT, uint32_t TL)
 {
     const uint32_t b = blockIdx.y, tile = blockIdx.x;
     const uint32_t n = bt.n[b];
@@ -57,36 +67,87 @@ __global__ void __launch_bounds__(256) mtf_tile_last(Batch bt, int32_t *tlast, u
     __shared__ int last[256];
     __shared__ uint8_t names[256];
     __shared__ uint32_t ls[8];
+    __shared__ uint32_t lm[2][4]; // per sweep (two sets, in turn: one barrier a sweep) and wavefront: its last run head + 1
+    __shared__ int s_first;
+    __shared__ uint32_t s_cnt;
     last[threadIdx.x] = -1;
+    if (threadIdx.x == 0) {
+        s_first = -1;
+        s_cnt = 0;
+    }
     (void)build_names(bt.hasbyte + (size_t)b * 256, names, ls);
     const uint8_t *s = bt.bwt + (size_t)b * bt.S;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t tcarry = 0; // the tile's last run head in the sweeps before this one, + 1 (0: none)
+    uint32_t cnt = 0;    // symbols of my heads
     static_assert(MTF_TILE % 2048 == 0, "256 threads x 8 bytes per sweep");
 #pragma unroll 1
     for (uint32_t sub = 0; sub < TL; sub += 2048) {
-    const uint32_t p0 = tile * TL + sub + threadIdx.x * 8;
-    if (sub + threadIdx.x * 8 < TL && p0 < n) { // (a tile may be shorter than one sweep of the workgroup: 512 bytes in tiny batches)
-        uint2 w = *reinterpret_cast<const uint2 *>(s + p0);
-        // only the last byte of a run inside my 8 bytes can be its symbol's last occurrence among them (after a
-        // BWT most bytes repeat their neighbour, and equal symbols from one wavefront queue on one LDS word)
-        const uint64_t w64 = ((uint64_t)w.y << 32) | w.x;
+        const uint32_t p0 = tile * TL + sub + threadIdx.x * 8;
+        // (a tile may be shorter than one sweep of the workgroup: 512 bytes in tiny batches)
+        const bool live = sub + threadIdx.x * 8 < TL && p0 < n;
+        uint32_t hm = 0; // bit k: byte k of my eight is a run head
+        uint2 w = make_uint2(0u, 0u);
+        if (live) w = *reinterpret_cast<const uint2 *>(s + p0);
+        uint32_t pb = wave_from_below(w.y) >> 24; // the byte before my eight (a live thread's lower neighbour is live)
+        if (live) {
+            const uint64_t w64 = ((uint64_t)w.y << 32) | w.x;
+            if (lane == 0 && p0 > 0) pb = s[p0 - 1];
+            const uint64_t df = w64 ^ ((w64 << 8) | pb);
+#pragma unroll
+            for (int k = 0; k < 8; k++)
+                if (p0 + k < n && ((uint32_t)(df >> (8 * k)) & 255u)) hm |= 1u << k;
+            // position 0 of the block follows the front of the initial list, name 0 (lib/mtf.rs:39-43)
+            if (p0 == 0) hm = (hm & ~1u) | (names[w.x & 255u] ? 1u : 0u);
+            // only the last byte of a run inside my 8 bytes can be its symbol's last occurrence among them (after a
+            // BWT most bytes repeat their neighbour, and equal symbols from one wavefront queue on one LDS word)
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const uint32_t p = p0 + k;
+                if (p < n) {
+                    const bool more = k < 7 && p + 1 < n && !((hm >> (k + 1)) & 1u);
+                    if (!more) atomicMax(&last[names[(uint32_t)(w64 >> (8 * k)) & 255u]], (int)p);
+                }
+            }
+        }
+        // the last run head before each thread's bytes (+ 1), then the symbols of its heads
+        const uint32_t inc = wave_incl_umax_dpp(hm ? p0 + 32u - (uint32_t)__clz(hm) : 0u);
+        uint32_t *lw = lm[(sub >> 11) & 1u];
+        if (lane == 63) lw[wave] = inc;
+        __syncthreads();
+        uint32_t before = max(tcarry, wave_from_below(inc));
+        for (int q = 0; q < wave; q++) before = max(before, lw[q]);
+        tcarry = max(max(tcarry, max(lw[0], lw[1])), max(lw[2], lw[3]));
+        if (hm && before == 0u) s_first = (int)(p0 + (uint32_t)__builtin_ctz(hm)); // (one thread of the tile at most)
+        int cur = (int)before - 1;
 #pragma unroll
         for (int k = 0; k < 8; k++) {
-            uint32_t p = p0 + k;
-            if (p < n) {
-                const uint32_t c = (uint32_t)(w64 >> (8 * k)) & 255u;
-                const bool more = k < 7 && p + 1 < n && ((uint32_t)(w64 >> (8 * (k + 1))) & 255u) == c;
-                if (!more) atomicMax(&last[names[c]], (int)p);
+            if ((hm >> k) & 1u) {
+                const int p = (int)(p0 + k);
+                cnt += 1u + (cur >= 0 ? run_digits((uint32_t)(p - 1 - cur)) : 0u);
+                cur = p;
             }
         }
     }
-    }
+    cnt = wave_all_add(cnt);
+    if (lane == 0 && cnt) atomicAdd(&s_cnt, cnt);
     __syncthreads();
     tlast[((size_t)b * MT + tile) * 256 + threadIdx.x] = last[threadIdx.x];
+    if (threadIdx.x == 0) {
+        MtfTile t;
+        t.first = s_first;
+        t.last = (int)tcarry - 1;
+        t.cnt = s_cnt;
+        t.off = 0;
+        rt[(size_t)b * MT + tile] = t;
+    }
 }
 
 // One workgroup per block: turn per-tile last occurrences into keys at tile entry (exclusive
-// running "latest occurrence"), seeded with the initial order; also num_syms.
-__global__ void __launch_bounds__(256) mtf_prefix(Batch bt, int32_t *tlast, uint32_t MT, uint32_t TL)
+// running "latest occurrence"), seeded with the initial order; also num_syms.  And the RLE2 layout across the
+// tiles: the last run head before every tile, the digits of the run that crosses into it, every tile's output
+// offset, the trailing run, EOB and m.  freqs is zeroed here: the walk adds to it.
+__global__ void __launch_bounds__(256) mtf_prefix(Batch bt, int32_t *tlast, MtfTile *rt, uint32_t MT, uint32_t TL)
 {
     const uint32_t b = blockIdx.x;
     const uint32_t n = bt.n[b];
@@ -99,6 +160,55 @@ __global__ void __launch_bounds__(256) mtf_prefix(Batch bt, int32_t *tlast, uint
     __syncthreads();
     const uint32_t num_names = w[0] + w[1] + w[2] + w[3];
     if (threadIdx.x == 0) bt.nsyms[b] = num_names + 2; // lib/mtf.rs:118
+    uint32_t *freqs = bt.freqs + (size_t)b * 258;
+    for (uint32_t k = c; k < 258; k += 256) freqs[k] = 0;
+    { // the layout, 256 tiles at a time (a block has at most S / 2048 = 440)
+        MtfTile *rb = rt + (size_t)b * MT;
+        __shared__ int lm[4];
+        __shared__ int incl[256];
+        __shared__ uint32_t ls[6];
+        int carry_in = -1;     // last run head before these 256 tiles
+        uint32_t off_base = 0; // symbols before them
+        for (uint32_t t0 = 0; t0 < ntile; t0 += 256) {
+            const uint32_t t = t0 + c;
+            MtfTile me{-1, -1, 0, 0};
+            if (t < ntile) me = rb[t];
+            incl[c] = max(carry_in, block_incl_max(me.last, lm));
+            __syncthreads();
+            const int carry = c ? incl[c - 1] : carry_in;
+            uint32_t tc = me.cnt;
+            if (me.first >= 0) tc += run_digits((uint32_t)(me.first - 1 - carry));
+            uint32_t total;
+            const uint32_t off = off_base + block_excl_add(tc, ls, &total);
+            if (t < ntile) {
+                me.last = carry;
+                me.off = off;
+                rb[t] = me;
+            }
+            carry_in = incl[255];
+            off_base += total;
+            __syncthreads();
+        }
+        if (c == 0) { // the run behind the last head, EOB
+            const uint32_t z = (uint32_t)((int)n - 1 - carry_in);
+            const uint32_t d = run_digits(z);
+            uint16_t *out = bt.syms + (size_t)b * (bt.S + 64);
+            uint32_t fa = 0, fb = 0;
+            for (uint32_t k = 0; k < d; k++) {
+                const uint32_t bit = ((z + 1) >> k) & 1u;
+                out[off_base + k] = (uint16_t)bit;
+                fa += bit ^ 1u;
+                fb += bit;
+            }
+            const uint32_t eob = num_names + 1; // lib/mtf.rs:30
+            out[off_base + d] = (uint16_t)eob;
+            bt.m[b] = off_base + d + 1;
+            // (freqs were zeroed above by other threads of this workgroup, barriers since)
+            atomicAdd(&freqs[0], fa);
+            atomicAdd(&freqs[1], fb);
+            atomicAdd(&freqs[eob], 1u);
+        }
+    }
     // thread = name: a never-seen name j sits behind every seen one, in name order (lib/mtf.rs:39-43)
     int run = c < num_names ? -1 - (int)c : INT32_MIN;
     int32_t *t = tlast + (size_t)b * MT * 256 + c;
@@ -123,153 +233,9 @@ __global__ void __launch_bounds__(256) mtf_prefix(Batch bt, int32_t *tlast, uint
 // ---- the walk: one wavefront per tile ---------------------------------------------------------------
 __device__ __forceinline__ int rdlane(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
 
-// NR = key registers in use (names < 64*NR).  All control flow is wave-uniform (scalar).
-template <int NR>
-__device__ __forceinline__ void walk_tile(const uint8_t *s, uint8_t *o, const int32_t *keys, const uint8_t *names,
-                                          int *lkeys, uint32_t base_p, uint32_t tile_len, int lane)
-{
-    int k0 = keys[lane], k1 = NR > 1 ? keys[64 + lane] : INT32_MIN, k2 = NR > 2 ? keys[128 + lane] : INT32_MIN,
-        k3 = NR > 2 ? keys[192 + lane] : INT32_MIN;
-    if (NR > 1) { // LDS copy of the keys (one wavefront per workgroup: program order is enough)
-        lkeys[lane] = k0;
-        lkeys[64 + lane] = k1;
-        lkeys[128 + lane] = k2;
-        lkeys[192 + lane] = k3;
-    }
-    int front; // name at the head of the recency list = arg max key
-    {
-        int best = k0, bsym = lane;
-        if (NR > 1 && k1 > best) { best = k1; bsym = 64 + lane; }
-        if (NR > 2 && k2 > best) { best = k2; bsym = 128 + lane; }
-        if (NR > 2 && k3 > best) { best = k3; bsym = 192 + lane; }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            int ob = __shfl_xor(best, d, 64), os = __shfl_xor(bsym, d, 64);
-            if (ob > best) {
-                best = ob;
-                bsym = os;
-            }
-        }
-        front = __builtin_amdgcn_readfirstlane(bsym); // keys are distinct, every lane agrees
-    }
-    // A byte equal to its predecessor is at the front of the list: position 0, nothing to update.
-    // The lanes find those in parallel (change mask); the scalar walk below only visits the others.
-    uint32_t carry_last = (uint32_t)front; // name of the byte before the chunk (list head at tile entry)
-#pragma unroll 1
-    for (uint32_t cbase = 0; cbase < tile_len; cbase += 1024) {
-        // 16 bytes per lane (S is padded so the vector load stays inside the arena), renamed once
-        const uint4 raw = *reinterpret_cast<const uint4 *>(s + cbase + lane * 16);
-        uint32_t in[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-            const uint32_t w = in[d];
-            in[d] = (uint32_t)names[w & 255u] | ((uint32_t)names[(w >> 8) & 255u] << 8) |
-                    ((uint32_t)names[(w >> 16) & 255u] << 16) | ((uint32_t)names[w >> 24] << 24);
-        }
-        const uint32_t clen = tile_len - cbase < 1024 ? tile_len - cbase : 1024;
-        const uint32_t nl = (clen + 15) / 16;
-        // change mask: bit k = (byte k of this lane != the byte before it)
-        uint32_t pw = (uint32_t)__shfl_up((int)in[3], 1, 64);
-        if (lane == 0) pw = carry_last << 24;
-        uint32_t chg = 0;
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-            const uint32_t x = in[d];
-            const uint32_t df = x ^ ((x << 8) | (pw >> 24));
-            chg |= ((df & 0xFFu) ? 1u : 0u) << (4 * d);
-            chg |= ((df & 0xFF00u) ? 2u : 0u) << (4 * d);
-            chg |= ((df & 0xFF0000u) ? 4u : 0u) << (4 * d);
-            chg |= ((df & 0xFF000000u) ? 8u : 0u) << (4 * d);
-            pw = x;
-        }
-        {
-            const uint32_t lo = (uint32_t)lane * 16u;
-            const uint32_t nv = clen > lo ? (clen - lo < 16u ? clen - lo : 16u) : 0u;
-            chg &= (1u << nv) - 1u; // bytes past the end of the tile are never visited
-        }
-        { // name of the chunk's last byte, for the next chunk's first comparison
-            const uint32_t e = clen - 1;
-            const uint32_t w = (uint32_t)rdlane((int)(((e >> 2) & 3u) == 0 ? in[0] : ((e >> 2) & 3u) == 1 ? in[1] : ((e >> 2) & 3u) == 2 ? in[2] : in[3]),
-                                                (int)(e >> 4));
-            carry_last = (w >> (8 * (e & 3u))) & 255u;
-        }
-        int o0 = 0, o1 = 0, o2 = 0, o3 = 0;
-#pragma unroll 1
-        for (uint32_t li = 0; li < nl; li++) {
-            const uint32_t m = (uint32_t)rdlane((int)chg, (int)li);
-            if (m == 0) continue; // 16 bytes at the front of the list
-            const bool me = (uint32_t)lane == li;
-#pragma unroll
-            for (int d = 0; d < 4; d++) {
-                if (((m >> (4 * d)) & 15u) == 0) continue;
-                const uint32_t w = (uint32_t)rdlane((int)in[d], (int)li);
-                uint32_t ow = 0;
-#pragma unroll
-                for (int kb = 0; kb < 4; kb++) {
-                    if (m & (1u << (4 * d + kb))) {
-                        const int c = (int)((w >> (8 * kb)) & 255u);
-                        const int p = (int)(base_p + cbase + li * 16 + d * 4 + kb);
-                        int prev;
-                        if (NR == 1) { // names < 64: the key sits in lane c
-                            prev = rdlane(k0, c);
-                            k0 = lane == c ? p : k0;
-                        } else {
-                            // old key through the LDS copy (all lanes read / write the same word), new key
-                            // into the one lane whose name index matches: no scalar register selection
-                            prev = __builtin_amdgcn_readfirstlane(lkeys[c]);
-                            lkeys[c] = p;
-                            k0 = lane == c ? p : k0;
-                            k1 = lane + 64 == c ? p : k1;
-                            if (NR > 2) {
-                                k2 = lane + 128 == c ? p : k2;
-                                k3 = lane + 192 == c ? p : k3;
-                            }
-                        }
-                        // c's own key is already p (> prev), every other key is unchanged:
-                        // position = (keys above prev) - 1 for the symbol itself.
-                        uint32_t cnt = (uint32_t)__popcll(__ballot(k0 > prev)) - 1u;
-                        if (NR > 1) cnt += (uint32_t)__popcll(__ballot(k1 > prev));
-                        if (NR > 2) cnt += (uint32_t)__popcll(__ballot(k2 > prev)) + (uint32_t)__popcll(__ballot(k3 > prev));
-                        ow |= cnt << (8 * kb);
-                    }
-                }
-                if (d == 0) o0 = me ? (int)ow : o0;
-                else if (d == 1) o1 = me ? (int)ow : o1;
-                else if (d == 2) o2 = me ? (int)ow : o2;
-                else o3 = me ? (int)ow : o3;
-            }
-        }
-        if ((uint32_t)lane < nl) *reinterpret_cast<uint4 *>(o + cbase + lane * 16) = make_uint4(o0, o1, o2, o3);
-    }
-}
-
-__global__ void __launch_bounds__(64) mtf_walk(Batch bt, const int32_t *tlast, uint32_t MT, uint32_t TL)
-{
-    const uint32_t b = blockIdx.y, tile = blockIdx.x;
-    const uint32_t n = bt.n[b];
-    const uint32_t base_p = tile * TL;
-    if (base_p >= n) return;
-    const int lane = threadIdx.x;
-    __shared__ uint8_t names[256];
-    __shared__ int lkeys[256];
-    __shared__ uint32_t ls[4];
-    const uint32_t num_names = build_names(bt.hasbyte + (size_t)b * 256, names, ls);
-    const int32_t *keys = tlast + ((size_t)b * MT + tile) * 256;
-    const uint8_t *s = bt.bwt + (size_t)b * bt.S + base_p;
-    uint8_t *o = bt.mtfpos + (size_t)b * bt.S + base_p;
-    const uint32_t remain = n - base_p;
-    const uint32_t tile_len = remain < TL ? remain : TL;
-    if (num_names <= 64)
-        walk_tile<1>(s, o, keys, names, lkeys, base_p, tile_len, lane);
-    else if (num_names <= 128)
-        walk_tile<2>(s, o, keys, names, lkeys, base_p, tile_len, lane);
-    else
-        walk_tile<4>(s, o, keys, names, lkeys, base_p, tile_len, lane);
-}
-
 // ---- the walk, parallel form: 64 run heads at a time ------------------------------------------------------------
-// mtf_walk above visits the changed bytes of a tile one after the other (a scalar chain per byte: with ~160 byte
-// values and ~45 % changed bytes it is the second most expensive stage of a step).  Here the lanes of the wavefront
+// Visiting the changed bytes of a tile one after the other is a scalar chain per byte (with ~160 byte values and
+// ~45 % changed bytes it was the second most expensive stage of a step).  Here the lanes of the wavefront
 // ARE 64 consecutive run heads (bytes that differ from their predecessor; every other byte has position 0 and leaves
 // the list alone).  With E[s] = position of symbol s in the recency list when the chunk begins:
 //   * a head whose symbol occurred before in the chunk, last at lane p: its position is the number of distinct symbols
@@ -281,7 +247,10 @@ __global__ void __launch_bounds__(64) mtf_walk(Batch bt, const int32_t *tlast, u
 //   * the list for the next chunk: a seen symbol's position = the distinct symbols whose last occurrence in the chunk
 //     is later; an unseen symbol moves back by the seen symbols that were behind it.
 // The list at tile entry is the rank of mtf_prefix's keys (lib/mtf.rs:39-43 for the first tile).
-__global__ void __launch_bounds__(64) mtf_walk_par(Batch bt, const int32_t *tlast, uint32_t MT, uint32_t TL)
+// The same 64 lanes emit RLE2: the zero run in front of a head ends at the head before it (the lane below, the last
+// head of the 64 before, or the tile's carry from mtf_prefix), its digits and the head's pos+1 go to bt.syms from a
+// running offset that starts at the tile's, found by one scan over the lanes' symbol counts.
+__global__ void __launch_bounds__(64) mtf_walk_par(Batch bt, const int32_t *tlast, const MtfTile *rt, uint32_t MT, uint32_t TL)
 {
     const uint32_t b = blockIdx.y, tile = blockIdx.x;
     const uint32_t n = bt.n[b];
@@ -296,13 +265,23 @@ __global__ void __launch_bounds__(64) mtf_walk_par(Batch bt, const int32_t *tlas
     // dependent steps per wavefront, what hides its latency is the number of wavefronts a compute unit can hold)
     __shared__ uint8_t hsym[1024];     // names of the run heads of the half, in order
     __shared__ uint16_t hoff[1024];    // their offsets in the half
-    __shared__ __attribute__((aligned(16))) uint8_t opos[1024]; // positions of the half's bytes
+    __shared__ uint32_t hist[128];     // the tile's heads by position, two 16-bit counters a word (a tile has at most 4,096 heads)
     const uint32_t num_names = build_names(bt.hasbyte + (size_t)b * 256, names, ls);
     const int32_t *keys = tlast + ((size_t)b * MT + tile) * 256;
     const uint8_t *s = bt.bwt + (size_t)b * bt.S + base_p;
-    uint8_t *o = bt.mtfpos + (size_t)b * bt.S + base_p;
+    uint16_t *out = bt.syms + (size_t)b * (bt.S + 64);
     const uint32_t remain = n - base_p;
     const uint32_t tile_len = remain < TL ? remain : TL;
+    hist[lane] = 0u;
+    hist[64 + lane] = 0u;
+    uint32_t woff;    // where the next symbol of the tile goes
+    int prevhead;     // the last run head before the 64 in hand (position in the block, -1: none)
+    {
+        const MtfTile me = rt[(size_t)b * MT + tile];
+        woff = (uint32_t)__builtin_amdgcn_readfirstlane((int)me.off);
+        prevhead = __builtin_amdgcn_readfirstlane(me.last);
+    }
+    uint32_t fa = 0, fb = 0; // digits of my lanes' runs, and the RUNB among them
     // ---- list at tile entry: E[name] = names with a larger key
     int k[4] = {keys[lane], keys[64 + lane], keys[128 + lane], keys[192 + lane]};
     int front;
@@ -379,7 +358,7 @@ __global__ void __launch_bounds__(64) mtf_walk_par(Batch bt, const int32_t *tlas
             carry_last = (w >> (8 * (e & 3u))) & 255u;
         }
         const uint32_t mine = (uint32_t)__popc(chg);
-        const uint32_t inc = wave_incl_add(mine, lane);
+        const uint32_t inc = wave_incl_add_dpp(mine);
         uint32_t at = inc - mine;
 #pragma unroll
         for (int kb = 0; kb < 16; kb++) {
@@ -389,8 +368,7 @@ __global__ void __launch_bounds__(64) mtf_walk_par(Batch bt, const int32_t *tlas
                 at++;
             }
         }
-        const uint32_t H = (uint32_t)__shfl((int)inc, 63, 64);
-        *reinterpret_cast<uint4 *>(&opos[lane * 16]) = make_uint4(0u, 0u, 0u, 0u);
+        const uint32_t H = (uint32_t)rdlane((int)inc, 63);
         const bool last_half = cbase + 1024 >= tile_len;
         // 64 run heads at a time (one wavefront: program order is enough between the LDS phases)
 #pragma unroll 1
@@ -469,7 +447,28 @@ __global__ void __launch_bounds__(64) mtf_walk_par(Batch bt, const int32_t *tlas
         }
         // a symbol seen before in the chunk, last at lane p: the distinct symbols between p and me
         pos = p < 0 ? Eown + cntB : (int)__popcll(A & ~((2ull << p) - 1ull));
-        if (act) opos[hoff[idx]] = (uint8_t)pos;
+        { // RLE2: digits of the zero run in front of every head (bijective base 2, lib/mtf.rs:46-65), then pos+1 (lib/mtf.rs:91-92)
+            const int g = (int)(base_p + cbase) + (act ? (int)hoff[idx] : 0);
+            int pg = (int)wave_from_below((uint32_t)g);
+            if (lane == 0) pg = prevhead;
+            const uint32_t zz = (uint32_t)(g - pg); // run length + 1
+            const uint32_t d = act ? 31u - (uint32_t)__clz(zz) : 0u;
+            const uint32_t tot = act ? d + 1u : 0u;
+            const uint32_t sc = wave_incl_add_dpp(tot);
+            // (a 32-bit byte offset from a scalar base: no 64-bit address arithmetic per store)
+            char *ob = reinterpret_cast<char *>(out + woff);
+            const uint32_t rel = (sc - tot) << 1;
+            for (uint32_t j = 0; j < d; j++) *reinterpret_cast<uint16_t *>(ob + (rel + 2u * j)) = (uint16_t)((zz >> j) & 1u);
+            if (act) {
+                *reinterpret_cast<uint16_t *>(ob + (rel + 2u * d)) = (uint16_t)(pos + 1);
+                atomicAdd(&hist[(uint32_t)pos >> 1], 1u << (16u * ((uint32_t)pos & 1u)));
+            }
+            fb += (uint32_t)__popc(zz & ((1u << d) - 1u));
+            fa += d;
+            const uint32_t nact = H - hb < 64u ? H - hb : 64u;
+            prevhead = rdlane(g, (int)nact - 1);
+            woff += (uint32_t)rdlane((int)sc, 63);
+        }
         if (more) { // the list when the next chunk begins
 #pragma unroll
             for (int q = 0; q < 4; q++)
@@ -479,202 +478,25 @@ __global__ void __launch_bounds__(64) mtf_walk_par(Batch bt, const int32_t *tlas
             if (islast) Etab[c] = (uint16_t)__popcll(lasts & ~upto);
         }
     }
-        if (cbase + (uint32_t)lane * 16u < tile_len) *reinterpret_cast<uint4 *>(o + cbase + lane * 16) = *reinterpret_cast<const uint4 *>(&opos[lane * 16]);
     }
-}
-
-// ---- RLE2 --------------------------------------------------------------------------------------------
-struct RleTile {
-    int first_nz; // global position of the first non-zero MTF position in the tile, -1 if none
-    int last_nz;  // last one, -1 if none; after rle_block: last non-zero position BEFORE the tile
-    uint32_t cnt; // symbols emitted by the tile, not counting the zero-run digits of first_nz
-    uint32_t off; // after rle_block: output offset of the tile
-};
-
-// Loads 16 positions of the tile into v[], returns the number valid.
-__device__ __forceinline__ uint32_t rle_load(const uint8_t *r, uint32_t q0, uint32_t n, uint32_t v[4])
-{
-    if (q0 >= n) return 0;
-    uint4 w = *reinterpret_cast<const uint4 *>(r + q0);
-    v[0] = w.x;
-    v[1] = w.y;
-    v[2] = w.z;
-    v[3] = w.w;
-    return n - q0 < 16 ? n - q0 : 16;
-}
-
-__global__ void __launch_bounds__(RLE_THREADS) rle_tiles(Batch bt, RleTile *rt)
-{
-    const uint32_t b = blockIdx.y, tile = blockIdx.x;
-    const uint32_t n = bt.n[b];
-    if (tile * RLE_TILE >= n) return;
-    const uint8_t *r = bt.mtfpos + (size_t)b * bt.S;
-    const uint32_t q0 = tile * RLE_TILE + threadIdx.x * RLE_ITEMS;
-    uint32_t v[4];
-    const uint32_t valid = rle_load(r, q0, n, v);
-    int tfirst = INT32_MAX, tlastnz = -1;
-#pragma unroll
-    for (int k = 0; k < RLE_ITEMS; k++) {
-        if ((uint32_t)k < valid && ((v[k >> 2] >> ((k & 3) * 8)) & 255u)) {
-            if (tfirst == INT32_MAX) tfirst = (int)(q0 + k);
-            tlastnz = (int)(q0 + k);
-        }
-    }
-    __shared__ int lm[RLE_THREADS / 64];
-    __shared__ int ex[RLE_THREADS];
-    int inc = block_incl_max(tlastnz, lm);
-    ex[threadIdx.x] = inc;
-    __syncthreads();
-    int cur = threadIdx.x ? ex[threadIdx.x - 1] : -1;
-    uint32_t cnt = 0;
-#pragma unroll
-    for (int k = 0; k < RLE_ITEMS; k++) {
-        if ((uint32_t)k < valid && ((v[k >> 2] >> ((k & 3) * 8)) & 255u)) {
-            const int p = (int)(q0 + k);
-            cnt += 1 + (cur >= 0 ? run_digits((uint32_t)(p - 1 - cur)) : 0u);
-            cur = p;
-        }
-    }
-    // reductions: sum cnt, min first, max last
-    __shared__ uint32_t ls[RLE_THREADS / 64 + 2];
-    __shared__ int lf[RLE_THREADS / 64];
-    uint32_t tot;
-    (void)block_excl_add(cnt, ls, &tot);
-    int f = tfirst;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) f = min(f, __shfl_xor(f, d, 64));
-    if ((threadIdx.x & 63) == 0) lf[threadIdx.x >> 6] = f;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < RLE_THREADS / 64; w++) f = min(f, lf[w]);
-        RleTile t;
-        t.first_nz = f == INT32_MAX ? -1 : f;
-        t.last_nz = ex[RLE_THREADS - 1];
-        t.cnt = tot;
-        t.off = 0;
-        rt[(size_t)b * (bt.S / RLE_TILE) + tile] = t;
-    }
-}
-
-// One workgroup per block: carries across tiles, output offsets, trailing run + EOB, m, freqs init.
-__global__ void __launch_bounds__(1024) rle_block(Batch bt, RleTile *rt)
-{
-    const uint32_t b = blockIdx.x;
-    const uint32_t n = bt.n[b];
-    const uint32_t ntile = (n + RLE_TILE - 1) / RLE_TILE; // <= S / RLE_TILE <= 1024
-    const uint32_t t = threadIdx.x;
+    // ---- the tile's histogram: one atomic per non-empty bin
     uint32_t *freqs = bt.freqs + (size_t)b * 258;
-    for (uint32_t k = t; k < 258; k += 1024) freqs[k] = 0;
-    RleTile me{-1, -1, 0, 0};
-    if (t < ntile) me = rt[(size_t)b * (bt.S / RLE_TILE) + t];
-    __shared__ int lm[16];
-    __shared__ int incl[1024];
-    incl[t] = block_incl_max(me.last_nz, lm);
-    __syncthreads();
-    const int carry = t ? incl[t - 1] : -1;
-    uint32_t cnt = me.cnt;
-    if (me.first_nz >= 0) cnt += run_digits((uint32_t)(me.first_nz - 1 - carry));
-    __shared__ uint32_t ls[20];
-    uint32_t total;
-    const uint32_t off = block_excl_add(cnt, ls, &total);
-    if (t < ntile) {
-        me.last_nz = carry;
-        me.off = off;
-        rt[(size_t)b * (bt.S / RLE_TILE) + t] = me;
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const uint32_t hw = hist[q * 64 + lane], lo = hw & 0xFFFFu, hi = hw >> 16;
+        const uint32_t pos0 = 2u * (uint32_t)(q * 64 + lane);
+        if (lo) atomicAdd(&freqs[pos0 + 1u], lo);
+        if (hi) atomicAdd(&freqs[pos0 + 2u], hi);
     }
-    if (t == 0) {
-        const int lastnz = incl[1023];
-        const uint32_t z = (uint32_t)((int)n - 1 - lastnz);
-        const uint32_t d = run_digits(z);
-        uint16_t *out = bt.syms + (size_t)b * (bt.S + 64);
-        uint32_t fa = 0, fb = 0;
-        for (uint32_t k = 0; k < d; k++) {
-            uint32_t bit = ((z + 1) >> k) & 1u;
-            out[total + k] = (uint16_t)bit;
-            fa += bit ^ 1u;
-            fb += bit;
-        }
-        const uint32_t eob = bt.nsyms[b] - 1; // names + 1 (lib/mtf.rs:30)
-        out[total + d] = (uint16_t)eob;
-        bt.m[b] = total + d + 1;
-        // freqs were zeroed above by other threads of this workgroup
-        __threadfence_block();
-        atomicAdd(&freqs[0], fa);
-        atomicAdd(&freqs[1], fb);
-        atomicAdd(&freqs[eob], 1u);
+    fb = wave_all_add(fb);
+    fa = wave_all_add(fa) - fb;
+    if (lane == 0) {
+        if (fa) atomicAdd(&freqs[0], fa);
+        if (fb) atomicAdd(&freqs[1], fb);
     }
 }
 
-__global__ void __launch_bounds__(RLE_THREADS) rle_emit(Batch bt, const RleTile *rt)
-{
-    const uint32_t b = blockIdx.y, tile = blockIdx.x;
-    const uint32_t n = bt.n[b];
-    if (tile * RLE_TILE >= n) return;
-    const RleTile me = rt[(size_t)b * (bt.S / RLE_TILE) + tile];
-    const uint8_t *r = bt.mtfpos + (size_t)b * bt.S;
-    const uint32_t q0 = tile * RLE_TILE + threadIdx.x * RLE_ITEMS;
-    uint32_t v[4];
-    const uint32_t valid = rle_load(r, q0, n, v);
-    int tlastnz = -1;
-#pragma unroll
-    for (int k = 0; k < RLE_ITEMS; k++)
-        if ((uint32_t)k < valid && ((v[k >> 2] >> ((k & 3) * 8)) & 255u)) tlastnz = (int)(q0 + k);
-
-    __shared__ int lm[RLE_THREADS / 64];
-    __shared__ int ex[RLE_THREADS];
-    __shared__ uint32_t hist[258];
-    for (int k = threadIdx.x; k < 258; k += RLE_THREADS) hist[k] = 0;
-    int inc = block_incl_max(tlastnz, lm);
-    ex[threadIdx.x] = inc;
-    __syncthreads();
-    const int cur0 = max(me.last_nz, threadIdx.x ? ex[threadIdx.x - 1] : -1);
-    int cur = cur0;
-    uint32_t cnt = 0;
-#pragma unroll
-    for (int k = 0; k < RLE_ITEMS; k++) {
-        if ((uint32_t)k < valid && ((v[k >> 2] >> ((k & 3) * 8)) & 255u)) {
-            const int p = (int)(q0 + k);
-            cnt += 1 + run_digits((uint32_t)(p - 1 - cur));
-            cur = p;
-        }
-    }
-    __shared__ uint32_t ls[RLE_THREADS / 64 + 2];
-    uint32_t tot;
-    uint32_t off = me.off + block_excl_add(cnt, ls, &tot);
-    uint16_t *out = bt.syms + (size_t)b * (bt.S + 64);
-    cur = cur0;
-    uint32_t fa = 0, fb = 0;
-#pragma unroll
-    for (int k = 0; k < RLE_ITEMS; k++) {
-        const uint32_t pos = (uint32_t)k < valid ? ((v[k >> 2] >> ((k & 3) * 8)) & 255u) : 0u;
-        if (pos) {
-            const int p = (int)(q0 + k);
-            const uint32_t z = (uint32_t)(p - 1 - cur);
-            const uint32_t d = run_digits(z);
-            for (uint32_t j = 0; j < d; j++) {
-                uint32_t bit = ((z + 1) >> j) & 1u;
-                out[off++] = (uint16_t)bit;
-                fa += bit ^ 1u;
-                fb += bit;
-            }
-            out[off++] = (uint16_t)(pos + 1); // lib/mtf.rs:91-92
-            atomicAdd(&hist[pos + 1], 1u);
-            cur = p;
-        }
-    }
-    fa = wave_reduce_add(fa);
-    fb = wave_reduce_add(fb);
-    if ((threadIdx.x & 63) == 0) {
-        if (fa) atomicAdd(&hist[0], fa);
-        if (fb) atomicAdd(&hist[1], fb);
-    }
-    __syncthreads();
-    uint32_t *freqs = bt.freqs + (size_t)b * 258;
-    for (int k = threadIdx.x; k < 258; k += RLE_THREADS)
-        if (hist[k]) atomicAdd(&freqs[k], hist[k]);
-}
-
-// MTF + RLE2 for blocks 0..B-1 (bt.bwt / bt.n / bt.hasbyte filled).  tlast and RleTile scratch
+// MTF + RLE2 for blocks 0..B-1 (bt.bwt / bt.n / bt.hasbyte filled).  tlast and the tiles' layout records
 // live in the sort lists, which are free once the BWT is emitted.
 int mtf_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal)
 {
@@ -691,29 +513,15 @@ int mtf_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal)
     const uint32_t TL = B >= 64u ? 2u * MTF_TILE : MTF_TILE;
     const uint32_t MT = (bt.S + TL - 1) / TL;
     int32_t *tlast = reinterpret_cast<int32_t *>(bt.listA);  // B*MT*256*4 <= B*S*8
-    RleTile *rt = reinterpret_cast<RleTile *>(bt.listB);     // B*(S/RLE_TILE)*16 bytes
+    MtfTile *rt = reinterpret_cast<MtfTile *>(bt.listB);     // B*MT*16 bytes
     const uint32_t mt = (nmax + TL - 1) / TL;
-    const uint32_t rtiles = (nmax + RLE_TILE - 1) / RLE_TILE;
     {
         KSpan ks(ctx, K_MTF_LAST, ntotal, 2);
-        mtf_tile_last<<<dim3(mt, B), 256, 0, st>>>(bt, tlast, MT, TL);
-        mtf_prefix<<<dim3(B), 256, 0, st>>>(bt, tlast, MT, TL);
+        mtf_tile_last<<<dim3(mt, B), 256, 0, st>>>(bt, tlast, rt, MT, TL);
+        mtf_prefix<<<dim3(B), 256, 0, st>>>(bt, tlast, rt, MT, TL);
     }
-    {
-        KSpan ks(ctx, K_MTF_WALK, 2 * ntotal);
-        static const bool serial_walk = []() {
-            const char *e = getenv("BZH_MTF");
-            return e && !strcmp(e, "serial");
-        }();
-        if (serial_walk)
-            mtf_walk<<<dim3(mt, B), 64, 0, st>>>(bt, tlast, MT, TL);
-        else
-            mtf_walk_par<<<dim3(mt, B), 64, 0, st>>>(bt, tlast, MT, TL);
-    }
-    KSpan ks(ctx, K_RLE2, 4 * ntotal, 3); // positions in twice, symbols (<= n, 2 bytes) out
-    rle_tiles<<<dim3(rtiles, B), RLE_THREADS, 0, st>>>(bt, rt);
-    rle_block<<<dim3(B), 1024, 0, st>>>(bt, rt);
-    rle_emit<<<dim3(rtiles, B), RLE_THREADS, 0, st>>>(bt, rt);
+    KSpan ks(ctx, K_MTF_WALK, 3 * ntotal); // the last column in, symbols (<= n, 2 bytes) out
+    mtf_walk_par<<<dim3(mt, B), 64, 0, st>>>(bt, tlast, rt, MT, TL);
     HIP_TRY(ctx, hipGetLastError());
     return BZH_OK;
 }
