@@ -6,6 +6,11 @@ Mirrors the public surface of jgbyrne/banzai v0.3.1 (reference lib/lib.rs:84-153
     encode_file(in_path, out_path) -> bytes consumed     (lib/lib.rs:141-153, level 9)
     encode_many(inputs, level) -> [bytes]               (encode() once per input, in one GPU pass)
 
+and, beyond the reference (which "(currently)" has no decompressor, README.md:9), the way back:
+
+    decompress(data) -> bytes                            (one or more .bz2 streams, as bz2.decompress)
+    decode(reader, writer) -> bytes written
+
 Everything is computed by hand-written HIP kernels behind the C ABI in include/bzhip.h
 (libbzhip.so); there is no CPU path.  `reader` is any object with .read(), `writer` any object
 with .write() (the Rust signature takes BufRead / BufWriter<W>).
@@ -14,7 +19,7 @@ import io
 
 from . import _native
 
-__all__ = ["encode", "encode_many", "encode_file", "Context", "MultiContext", "BzhError"]
+__all__ = ["encode", "encode_many", "encode_file", "decompress", "decode", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
 MultiContext = _native.MultiContext
@@ -163,3 +168,32 @@ def encode_file(in_path, out_path, device=0, devices=None):
     """bzip2-encode a file into another file at level 9 (banzai::encode_file)."""
     with open(in_path, "rb") as inf, open(out_path, "wb") as outf:
         return encode(inf, outf, 9, device, devices)
+
+
+def decompress(data, device=0):
+    """Decode one or more complete bzip2 streams lying back to back in `data` (bytes-like) -> the decoded bytes, as
+    bz2.decompress does: any level, any encoder.  Bytes behind the last stream that do not start another one are ignored.
+    A damaged stream raises BzhError with status -6 (bzh_last_error's text says what and where).  Computed on the GPU on a
+    level-9 context (bzh_decode); the output buffer is sized from the input, then once more from what the library reports."""
+    if isinstance(data, str):
+        raise TypeError("decompress takes a bytes-like object, not str")
+    try:
+        view = memoryview(data).cast("B")
+    except TypeError:
+        raise TypeError(f"decompress takes a bytes-like object, not {type(data).__name__}") from None
+    return _ctx(9, device).decode(view)
+
+
+def decode(reader, writer, device=0):
+    """Decode everything `reader` yields (one or more bzip2 streams) and write the bytes to `writer` -> bytes written.
+    This path reads the whole input first (the block boundaries of a stream are found by a scan of all of it)."""
+    data = reader.getvalue()[reader.tell():] if isinstance(reader, io.BytesIO) else reader.read()
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError("reader.read() must return bytes")
+    out = decompress(data, device)
+    if isinstance(reader, io.BytesIO):
+        reader.seek(0, io.SEEK_END)
+    writer.write(out)
+    if hasattr(writer, "flush"):
+        writer.flush()
+    return len(out)

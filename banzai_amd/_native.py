@@ -44,6 +44,15 @@ class Stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class DecodeStats(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in ("ms_scan", "ms_entropy", "ms_unbwt", "ms_unrle", "ms_crc", "ms_total")] + \
+               [(k, ctypes.c_uint64) for k in ("streams", "blocks", "candidates", "candidates_off_chain", "in_bytes",
+                                               "out_bytes")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class KStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("ms", ctypes.c_double), ("launches", ctypes.c_uint64),
                 ("alg_bytes", ctypes.c_uint64)]
@@ -72,6 +81,11 @@ SIGNATURES = {
                                        szp, szp]),
     "bzh_encode_many_bound": (ctypes.c_size_t, [ctypes.c_int, szp, ctypes.c_size_t]),
     "bzh_plan_many_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, szp, ctypes.c_size_t, szp]),
+    "bzh_decode": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u8p, ctypes.c_size_t, szp, szp]),
+    "bzh_decode_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                         ctypes.c_size_t, szp, szp]),
+    "bzh_get_decode_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DecodeStats)]),
+    "bzh_decode_scan": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u64p, u8p, ctypes.c_size_t, szp]),
     "bzh_stream_begin": (ctypes.c_int, [ctypes.c_void_p]),
     "bzh_stream_feed": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, u8p, ctypes.c_size_t, szp]),
     "bzh_stream_bound": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_size_t]),
@@ -350,6 +364,59 @@ class Context:
         self.check(lib().bzh_encode_many_device(self._h, ctypes.c_void_p(d_in), ptr(lens, szp), count, ctypes.c_void_p(d_out),
                                                 cap, ptr(offs, szp), ptr(olens, szp)))
         return offs[:count].tolist(), olens[:count].tolist()
+
+    # ---- decode (bzh_decode*) ----
+    def decode_raw(self, data, cap):
+        """one bzh_decode call into a buffer of `cap` bytes -> (status, bytes or None, size reported, input bytes consumed)"""
+        a = np.frombuffer(data, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        olen = ctypes.c_size_t(0)
+        used = ctypes.c_size_t(0)
+        st = lib().bzh_decode(self._h, ptr(src), n, ptr(out) if cap else None, cap, ctypes.byref(olen), ctypes.byref(used))
+        return st, (out[:olen.value].tobytes() if st == 0 else None), int(olen.value), int(used.value)
+
+    def decode(self, data, size_hint=None, with_consumed=False):
+        """bzh_decode: the bytes of the bzip2 stream(s) in `data` (host buffers).  The output is sized by a first guess
+        from the input size, then by one retry with the size BZH_E_CAP reports."""
+        n = len(data)
+        cap = size_hint if size_hint is not None else 6 * n + (1 << 16)
+        st, out, need, used = self.decode_raw(data, cap)
+        if st == -4:
+            st, out, need, used = self.decode_raw(data, need)
+        self.check(st)
+        return (out, used) if with_consumed else out
+
+    def decode_device(self, d_in, n, d_out, cap):
+        """bzh_decode_device on integer device addresses -> (decoded bytes, input bytes consumed)"""
+        olen = ctypes.c_size_t(0)
+        used = ctypes.c_size_t(0)
+        self.check(lib().bzh_decode_device(self._h, ctypes.c_void_p(d_in), n, ctypes.c_void_p(d_out), cap, ctypes.byref(olen),
+                                           ctypes.byref(used)))
+        return int(olen.value), int(used.value)
+
+    def decode_stats(self):
+        s = DecodeStats()
+        self.check(lib().bzh_get_decode_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
+
+    def decode_scan(self, data):
+        """bzh_decode_scan -> [(bit position, kind)] of every block (0) and footer (1) magic in `data`, ascending"""
+        a = np.frombuffer(data, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        cnt = ctypes.c_size_t(0)
+        cap = 1024
+        while True:
+            pos = np.zeros(cap, dtype=np.uint64)
+            kind = np.zeros(cap, dtype=np.uint8)
+            st = lib().bzh_decode_scan(self._h, ptr(src), n, ptr(pos, u64p), ptr(kind), cap, ctypes.byref(cnt))
+            if st == -4 and cnt.value > cap:
+                cap = cnt.value
+                continue
+            self.check(st)
+            return list(zip(pos[:cnt.value].tolist(), kind[:cnt.value].tolist()))
 
     def plan_many_device(self, d_in, lens):
         """bzh_plan_many_device: the plan of inputs lying back to back at d_in -> [(in_off, in_len, rle_len, crc)] in input

@@ -79,6 +79,7 @@ extern "C" const char *bzh_strerror(int status)
     case BZH_E_HIP: return "HIP runtime error or no usable gfx950 device";
     case BZH_E_CAP: return "output buffer too small";
     case BZH_E_STATE: return "call sequence error";
+    case BZH_E_DATA: return "not a valid bzip2 stream";
     default: return "unknown status";
     }
 }
@@ -341,6 +342,8 @@ extern "C" void bzh_destroy(bzh_ctx *ctx)
     if (ctx->h_pinned) hipHostFree(ctx->h_pinned);
     if (ctx->crc_host) hipHostFree(ctx->crc_host);
     if (ctx->d_crctab) hipFree(ctx->d_crctab);
+    if (ctx->dec_ws) hipFree(ctx->dec_ws);
+    if (ctx->dec_list) hipFree(ctx->dec_list);
     for (int k = 0; k < 2; k++)
         if (ctx->strm.d_buf[k]) hipFree(ctx->strm.d_buf[k]);
     if (ctx->strm.h_out) hipHostFree(ctx->strm.h_out);
@@ -1392,6 +1395,97 @@ extern "C" int bzh_crc32(bzh_ctx *ctx, const uint8_t *in, size_t n, uint32_t *cr
     if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, ctx->stream));
     BZH_TRY(ensure_arena(ctx, 1)); // (crc_device borrows two words of it)
     return crc_device(ctx, ctx->d_stage_in, n, crc);
+    });
+}
+
+// ================================================================================================
+// Decode (decode.hip): scan, then the arena for as many blocks as there are candidates, then the chain
+// ================================================================================================
+extern "C" int bzh_decode_device(bzh_ctx *ctx, const void *d_in, size_t n, void *d_out, size_t cap, size_t *out_len, size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n) || (!d_out && cap) || !out_len) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    ctx->evnext = 0;
+    ctx->sort_spans.clear();
+    kstats_reset(ctx);
+    memset(&ctx->dstats, 0, sizeof ctx->dstats);
+    ctx->dstats.in_bytes = n;
+    *out_len = 0;
+    if (consumed) *consumed = 0;
+    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
+    if (ctx->profiling) {
+        t0 = bzh_event(ctx);
+        hipEventRecord(t0, st);
+    }
+    std::vector<uint64_t> cands;
+    BZH_TRY(decode_scan_run(ctx, (const uint8_t *)d_in, n, cands));
+    if (ctx->profiling) {
+        t1 = bzh_event(ctx);
+        hipEventRecord(t1, st);
+    }
+    ctx->dstats.candidates = cands.size();
+    BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(cands.size(), 1), ctx->max_batch)));
+    const int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, (uint8_t *)d_out, cap, out_len, consumed, cands);
+    if (ctx->profiling) {
+        t2 = bzh_event(ctx);
+        hipEventRecord(t2, st);
+        HIP_TRY(ctx, bzh_stream_wait(st));
+        ctx->dstats.ms_scan = span_ms(t0, t1);
+        ctx->dstats.ms_total = span_ms(t0, t2);
+    }
+    return rc;
+    });
+}
+
+extern "C" int bzh_decode(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len, size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n) || (!out && cap) || !out_len) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, n + 16));
+    if (cap) BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, cap));
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, st));
+    size_t len = 0;
+    const int rc = bzh_decode_device(ctx, ctx->d_stage_in, n, cap ? ctx->d_stage_out : nullptr, cap, &len, consumed);
+    *out_len = len; // (BZH_E_CAP: the size needed)
+    if (rc != BZH_OK) return rc;
+    if (len) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, len, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, bzh_stream_wait(st));
+    return BZH_OK;
+    });
+}
+
+extern "C" int bzh_get_decode_stats(const bzh_ctx *ctx, bzh_decode_stats *out)
+{
+    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
+    if (!ctx || !out) return BZH_E_ARG;
+    *out = ctx->dstats;
+    return BZH_OK;
+    });
+}
+
+extern "C" int bzh_decode_scan(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t *bitpos, uint8_t *kind, size_t max, size_t *count)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n) || !count || (max && (!bitpos || !kind))) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, n + 16));
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<uint64_t> cands;
+    BZH_TRY(decode_scan_run(ctx, ctx->d_stage_in, n, cands));
+    *count = cands.size();
+    if (cands.size() > max) return BZH_E_CAP;
+    for (size_t k = 0; k < cands.size(); k++) {
+        bitpos[k] = cands[k] >> 1;
+        kind[k] = (uint8_t)(cands[k] & 1u);
+    }
+    return BZH_OK;
     });
 }
 

@@ -40,6 +40,7 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "  options:\n"
             "     --output <path.bz2>    write the stream to this file\n"
             "     --stdout    or   -c    write the stream to standard out\n"
+            "     --decompress or  -d    decode <input_path> (one or more .bz2 streams) instead\n"
             "     --keep      or   -k    keep the input file\n"
             "     --remove    or   -r    remove the input file\n\n"
             "     -1 to -9               block size in 100 kB units (default -9)\n"
@@ -51,7 +52,9 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "  notes:\n"
             "     '-' as input path reads standard in.  Without --output / --stdout the file\n"
             "     '<input_path>.bz2' is written and the input removed; with an explicit output the\n"
-            "     input is kept unless --remove is given.  GPU: $BZHIP_DEVICE (default 0), or\n"
+            "     input is kept unless --remove is given.  With --decompress the input must end in\n"
+            "     '.bz2' unless --output / --stdout is given; the default output is the path without\n"
+            "     that suffix, and the same keep / remove policy applies.  GPU: $BZHIP_DEVICE (default 0), or\n"
             "     $BZHIP_DEVICES=0,1,2,... to spread the blocks over several GPUs of this node;\n"
             "     BZHIP_HUFFMAN=fixed: 2-6 Huffman tables with refinement (smaller, not banzai's exact bytes).\n\n%s\n",
             VERSION);
@@ -67,6 +70,7 @@ int main(int argc, char **argv)
     std::string in_path, out_path;
     bool have_in = false, in_stdin = false, out_stdout = false, have_out = false;
     int keep = -1, level = 9;
+    bool decompress = false;
     auto set_input = [&](const std::string &p, bool is_stdin) {
         if (have_in) die(ERR_ARGS, "Only one input may be specified");
         have_in = true;
@@ -94,6 +98,7 @@ int main(int argc, char **argv)
                                  "coded and Huffman coded by HIP kernels (libbzhip.so); the stream is bit-identical\n"
                                  "to banzai 0.3.1's.\n\n" + VERSION);
             else if (a == "--verbose") {}
+            else if (a == "--decompress") decompress = true;
             else if (a == "--keep") keep = 1;
             else if (a == "--remove") keep = 0;
             else if (a == "--fast") level = 1;
@@ -109,6 +114,7 @@ int main(int argc, char **argv)
                 for (size_t c = 1; c < a.size(); c++) {
                     const char f = a[c];
                     if (f == 'c') set_output("", true);
+                    else if (f == 'd') decompress = true;
                     else if (f == 'k') keep = 1;
                     else if (f == 'r') keep = 0;
                     else if (f == 'v') {}
@@ -124,6 +130,60 @@ int main(int argc, char **argv)
 
     FILE *inf = in_stdin ? stdin : fopen(in_path.c_str(), "rb");
     if (!inf) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + in_path + ": " + strerror(errno));
+
+    if (decompress) { // the whole input, one bzh_decode on a level-9 context (a second one if the first size guess was short)
+        std::string dpath = out_path;
+        if (!have_out && !in_stdin) {
+            if (in_path.size() < 5 || in_path.compare(in_path.size() - 4, 4, ".bz2") != 0)
+                die(ERR_ARGS, "With --decompress the input path must end in '.bz2' unless --output or --stdout is given");
+            dpath = in_path.substr(0, in_path.size() - 4);
+        }
+        std::vector<uint8_t> data;
+        {
+            std::unique_ptr<uint8_t[]> buf(new uint8_t[(size_t)16 << 20]);
+            for (;;) {
+                const size_t k = fread(buf.get(), 1, (size_t)16 << 20, inf);
+                data.insert(data.end(), buf.get(), buf.get() + k);
+                if (k < ((size_t)16 << 20)) {
+                    if (ferror(inf)) die(ERR_OUTPUT, "error during decompression: read failed");
+                    break;
+                }
+            }
+        }
+        if (!in_stdin) fclose(inf);
+        const char *dv = getenv("BZHIP_DEVICE");
+        bzh_ctx *dctx = nullptr;
+        int ds = bzh_create(&dctx, dv ? atoi(dv) : 0, 9, 0);
+        if (ds != BZH_OK) die(ERR_OUTPUT, std::string("error during decompression: ") + bzh_strerror(ds));
+        static const uint8_t none = 0;
+        const size_t n = data.size();
+        size_t cap = 6 * n + 65536, got = 0;
+        std::unique_ptr<uint8_t[]> out;
+        for (int attempt = 0; attempt < 2; attempt++) {
+            out.reset(new (std::nothrow) uint8_t[cap ? cap : 1]);
+            ds = out ? bzh_decode(dctx, n ? data.data() : &none, n, out.get(), cap, &got, nullptr) : BZH_E_NOMEM;
+            if (ds != BZH_E_CAP) break;
+            cap = got; // the size the library reports
+        }
+        if (ds != BZH_OK) { // the input stays where it is, and no output is created
+            const std::string msg = std::string("error during decompression: ") + bzh_strerror(ds) + ": " + bzh_last_error(dctx);
+            bzh_destroy(dctx);
+            die(ERR_OUTPUT, msg);
+        }
+        bzh_destroy(dctx);
+        FILE *df = stdout;
+        if (!(have_out && out_stdout) && !(in_stdin && !have_out)) {
+            df = fopen(dpath.c_str(), "wb");
+            if (!df) die(ERR_FILESYSTEM, "[filesystem error] cannot create " + dpath + ": " + strerror(errno));
+        }
+        if (got && fwrite(out.get(), 1, got, df) != got) die(ERR_OUTPUT, "error during decompression: write failed");
+        if (fflush(df) != 0) die(ERR_OUTPUT, "error during decompression: write failed");
+        if (df != stdout) fclose(df);
+        const bool keep_in = keep >= 0 ? keep == 1 : have_out; // bnz/src/main.rs:292-300
+        if (!keep_in && !in_stdin && remove(in_path.c_str()) != 0)
+            die(ERR_OUTPUT, "error deleting input file: " + std::string(strerror(errno)));
+        return SUCCESS;
+    }
 
     FILE *outf = stdout;
     if (have_out && !out_stdout) {

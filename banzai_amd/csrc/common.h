@@ -291,6 +291,12 @@ struct bzh_ctx {
     size_t stage_out_size = 0;
     uint32_t *h_pinned = nullptr; // small pinned readback area
     void *d_crctab = nullptr;     // GF(2) tables of the block CRC (rle1.hip)
+    // decode (decode.hip): allocated by the first decode, so an encode-only user pays nothing
+    uint8_t *dec_ws = nullptr;    // per-batch tables: candidates, results, tile maps / counts / offsets, CRC descriptors
+    size_t dec_ws_size = 0;
+    uint64_t *dec_list = nullptr; // the scan's hit list
+    size_t dec_list_cap = 0;
+    bzh_decode_stats dstats{};
     // streaming encode (bzh_stream_*)
     struct Stream {
         bool active = false, header_done = false;
@@ -590,5 +596,12 @@ hipStream_t bzh_side_stream(bzh_ctx *ctx);                                      
 int rle1_plan_crc(bzh_ctx *ctx, size_t b0, size_t b1);               // rle1.hip: CRCs of plan blocks [b0, b1)
 int rle1_emit(bzh_ctx *ctx, size_t b0, uint32_t B);                   // rle1.hip: fill bt.rle / bt.n / bt.desc
 int crc_device(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t *crc_out); // rle1.hip
+// rle1.hip: CRCs of nb byte ranges of d_in (d_blocks[k].in_off / in_len, the longest maxlen bytes) into d_blocks[k].crc; no wait
+int crc_blocks_device(bzh_ctx *ctx, const uint8_t *d_in, BlockDesc *d_blocks, uint32_t *d_acc, uint32_t nb, uint64_t maxlen);
+// decode.hip: every block / footer magic of d_in[0..n) as (bit position << 1 | kind), ascending; then the chain walk and the
+// back of the decoder over that list (the arena laid out for min(candidates, max_batch) blocks)
+int decode_scan_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, std::vector<uint64_t> &cands);
+int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t cap, size_t *out_len, size_t *consumed,
+                     const std::vector<uint64_t> &cands);
 
 hipEvent_t bzh_event(bzh_ctx *ctx);

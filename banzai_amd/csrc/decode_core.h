@@ -1,0 +1,359 @@
+// decode_core.h -- the serial front of the bzip2 decoder: bit reader, block header parser, canonical decode tables, the
+// symbol loop with the inverse MTF / RLE2, the footer, and the state model of the inverse RLE1.
+//
+// One source, two builds.  decode.hip compiles it for gfx950, where ONE WAVEFRONT decodes one block: every lane runs the
+// same serial code on the same values (so the bit window and the counters can live on the scalar side), and the lanes
+// split what is parallel -- filling the look-up tables, shifting the MTF list, storing a run.  tests/decode_host compiles
+// the very same text with g++ -fsanitize=address,undefined as a one-lane machine, which is where damaged streams are
+// thrown at it by the thousand (sanitizers are a CPU affair).  Every read of the input is bounded by its length `n`, every
+// index by the size of the table it goes into, every byte written by `block_max`: a damaged stream ends in a status.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define BZD_LANES 64u
+#define BZD_LANE (threadIdx.x & 63u)
+#define BZD_SYNC() __syncthreads() // (the decode kernel is one wavefront a workgroup)
+#define BZD_UNI(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x))) // the lanes agree: keep the value on the scalar side
+#else
+#define BZD_LANES 1u
+#define BZD_LANE 0u
+#define BZD_SYNC() ((void)0)
+#define BZD_UNI(x) ((uint32_t)(x))
+#endif
+#if defined(__HIPCC__)
+#define BZD_FN __host__ __device__ __forceinline__
+#else
+#define BZD_FN static inline
+#endif
+
+enum BzdKind : uint32_t { // what went wrong (bzh_last_error names it); 0 = the block decoded
+    BZD_OK = 0,
+    BZD_K_MAGIC = 1,      // no "BZh1".."BZh9" / no block or footer magic where the chain needs one
+    BZD_K_TRUNC = 2,      // the input ends inside the stream
+    BZD_K_FORMAT = 3,     // a field outside what the format allows
+    BZD_K_BLOCK_CRC = 4,
+    BZD_K_STREAM_CRC = 5,
+    BZD_K_RANDOMISED = 6  // a randomised block (bzip2 0.9.0; no current encoder writes one)
+};
+
+constexpr uint32_t BZD_MAX_SEL = 32767, BZD_MAX_LEN = 20, BZD_GROUP = 50, BZD_LUT_BITS = 10;
+constexpr uint64_t BZD_BLOCK_MAGIC = 0x314159265359ull, BZD_FOOTER_MAGIC = 0x177245385090ull;
+
+struct BzdResult {
+    uint32_t kind;    // BzdKind
+    uint32_t crc;     // the stored CRC (block: of its bytes; footer: of the stream)
+    uint64_t errpos;  // bit position where the parse gave up
+    uint64_t end_bit; // first bit behind the block (footer: behind the padding)
+    uint32_t nblock;  // bytes of the last column
+    uint32_t origptr;
+    uint32_t follow;  // footer only: 0 = the input ends behind it, 0x100 | level = "BZh<level>" follows, 2 = foreign bytes
+    uint32_t pad;
+};
+
+struct BzdWork { // tables of the block being decoded (LDS on the GPU: 51 KB)
+    uint16_t lut[6][1u << BZD_LUT_BITS]; // first 10 bits -> len << 9 | symbol (0: longer code, or none)
+    int32_t limit[6][BZD_MAX_LEN + 2], base[6][BZD_MAX_LEN + 2];
+    uint16_t perm[6][258];
+    uint8_t len[6][258];
+    uint32_t cnt[BZD_MAX_LEN + 2], start[BZD_MAX_LEN + 2];
+    uint32_t minlen[6], maxlen[6];
+    uint32_t bad;
+    uint8_t sel[BZD_MAX_SEL + 1];
+    uint8_t mtf[256];
+};
+
+// ---- bit reader: MSB first; `buf` holds the next `cnt` bits left-aligned, (pos + cnt) is a byte boundary.  Bits behind the
+// input read as zero and bzd_over() turns true: callers check it wherever a decision has been taken on such bits.
+struct BzdBits {
+    const uint8_t *p;
+    uint64_t n, pos, buf;
+    uint32_t cnt;
+};
+
+BZD_FN uint32_t bzd_load32(const uint8_t *p, uint64_t n, uint64_t byte)
+{
+    uint32_t w = 0;
+    if (byte + 4 <= n) {
+        __builtin_memcpy(&w, p + byte, 4);
+        return __builtin_bswap32(w);
+    }
+    for (uint32_t k = 0; k < 4; k++) w = (w << 8) | (byte + k < n ? (uint32_t)p[byte + k] : 0u);
+    return w;
+}
+
+BZD_FN void bzd_seek(BzdBits &r, const uint8_t *p, uint64_t n, uint64_t pos)
+{
+    r.p = p;
+    r.n = n;
+    r.pos = pos;
+    r.buf = 0;
+    r.cnt = 0;
+    const uint32_t sh = (uint32_t)(pos & 7u);
+    if (sh) {
+        const uint64_t byte = pos >> 3;
+        const uint32_t b = byte < n ? BZD_UNI(p[byte]) : 0u;
+        r.buf = (uint64_t)b << (56 + sh);
+        r.cnt = 8 - sh;
+    }
+}
+
+BZD_FN uint32_t bzd_peek(BzdBits &r, uint32_t k) // 1 <= k <= 32
+{
+    if (r.cnt < 32) {
+        const uint32_t w = BZD_UNI(bzd_load32(r.p, r.n, (r.pos + r.cnt) >> 3));
+        r.buf |= (uint64_t)w << (32 - r.cnt);
+        r.cnt += 32;
+    }
+    return (uint32_t)(r.buf >> (64 - k));
+}
+BZD_FN void bzd_skip(BzdBits &r, uint32_t k) // after a peek of at least k bits
+{
+    r.buf <<= k;
+    r.cnt -= k;
+    r.pos += k;
+}
+BZD_FN uint32_t bzd_get(BzdBits &r, uint32_t k)
+{
+    const uint32_t v = bzd_peek(r, k);
+    bzd_skip(r, k);
+    return v;
+}
+BZD_FN bool bzd_over(const BzdBits &r) { return r.pos > r.n * 8; }
+
+// ---- one block: `pos` = bit position of its magic.  Leaves the last column in L[0 .. nblock), nblock <= block_max.
+BZD_FN void bzd_decode_block(BzdWork &w, const uint8_t *in, uint64_t n, uint64_t pos, uint32_t block_max, uint8_t *L, BzdResult &res)
+{
+    const uint32_t lane = BZD_LANE;
+    const bool l0 = lane == 0;
+    BzdBits r;
+    bzd_seek(r, in, n, pos + 48);
+    res.kind = BZD_OK;
+    res.errpos = 0;
+    res.end_bit = 0;
+    res.nblock = 0;
+    res.follow = 0;
+    res.pad = 0;
+#define BZD_FAIL(k)         \
+    do {                    \
+        res.kind = (k);     \
+        res.errpos = r.pos; \
+        return;             \
+    } while (0)
+    res.crc = bzd_get(r, 32);
+    const uint32_t randomised = bzd_get(r, 1);
+    const uint32_t origptr = bzd_get(r, 24);
+    res.origptr = origptr;
+    const uint32_t groups16 = bzd_get(r, 16);
+    if (bzd_over(r)) BZD_FAIL(BZD_K_TRUNC);
+    if (randomised) BZD_FAIL(BZD_K_RANDOMISED);
+    // symbol map: the bytes in use, in order, straight into the MTF list
+    uint32_t nin = 0;
+    for (uint32_t g = 0; g < 16; g++) {
+        if (!((groups16 >> (15 - g)) & 1u)) continue;
+        const uint32_t bits = bzd_get(r, 16);
+        for (uint32_t k = 0; k < 16; k++)
+            if ((bits >> (15 - k)) & 1u) {
+                if (l0) w.mtf[nin] = (uint8_t)(g * 16 + k);
+                nin++;
+            }
+    }
+    if (bzd_over(r)) BZD_FAIL(BZD_K_TRUNC);
+    if (nin == 0) BZD_FAIL(BZD_K_FORMAT);
+    const uint32_t alpha = nin + 2;
+    const uint32_t ngroups = bzd_get(r, 3), nsel = bzd_get(r, 15);
+    if (bzd_over(r)) BZD_FAIL(BZD_K_TRUNC);
+    if (ngroups < 2 || ngroups > 6 || nsel < 1) BZD_FAIL(BZD_K_FORMAT);
+    { // selectors: unary-coded positions in a move-to-front list of the tables (six nibbles of one word)
+        uint32_t order = 0x543210u;
+        for (uint32_t i = 0; i < nsel; i++) {
+            uint32_t j = 0;
+            while (bzd_get(r, 1)) {
+                if (++j >= ngroups) BZD_FAIL(BZD_K_FORMAT);
+            }
+            if (bzd_over(r)) BZD_FAIL(BZD_K_TRUNC);
+            const uint32_t v = (order >> (4 * j)) & 15u, low = order & ((1u << (4 * j)) - 1u);
+            order = (order & ~((1u << (4 * (j + 1))) - 1u)) | (low << 4) | v;
+            if (l0) w.sel[i] = (uint8_t)v;
+        }
+    }
+    for (uint32_t t = 0; t < ngroups; t++) { // delta-coded code lengths
+        uint32_t cur = bzd_get(r, 5);
+        for (uint32_t s = 0; s < alpha; s++) {
+            for (;;) {
+                if (cur < 1 || cur > BZD_MAX_LEN) BZD_FAIL(bzd_over(r) ? BZD_K_TRUNC : BZD_K_FORMAT);
+                if (!bzd_get(r, 1)) break;
+                cur = bzd_get(r, 1) ? cur - 1 : cur + 1;
+                if (bzd_over(r)) BZD_FAIL(BZD_K_TRUNC);
+            }
+            if (l0) w.len[t][s] = (uint8_t)cur;
+        }
+        if (bzd_over(r)) BZD_FAIL(BZD_K_TRUNC);
+    }
+    if (l0) w.bad = 0;
+    BZD_SYNC();
+    // canonical codes: the symbols of one length are numbered in symbol order; an over-subscribed code is refused
+    for (uint32_t t = 0; t < ngroups; t++) {
+        if (l0) {
+            for (uint32_t l = 0; l < BZD_MAX_LEN + 2; l++) w.cnt[l] = 0;
+            uint32_t mn = 32, mx = 0;
+            for (uint32_t s = 0; s < alpha; s++) {
+                const uint32_t l = w.len[t][s];
+                w.cnt[l]++;
+                mn = l < mn ? l : mn;
+                mx = l > mx ? l : mx;
+            }
+            int32_t code = 0, idx = 0;
+            for (uint32_t l = mn; l <= mx; l++) {
+                const int32_t c = (int32_t)w.cnt[l];
+                w.base[t][l] = idx - code; // index into perm = code + base[l]
+                w.start[l] = (uint32_t)idx;
+                code += c;
+                idx += c;
+                w.limit[t][l] = code - 1; // largest code of this length
+                if (code > (1 << l)) {
+                    w.bad = 1;
+                    break;
+                }
+                code <<= 1;
+            }
+            if (!w.bad)
+                for (uint32_t s = 0; s < alpha; s++) {
+                    const uint32_t l = w.len[t][s];
+                    w.perm[t][w.start[l]++] = (uint16_t)s;
+                }
+            w.minlen[t] = mn;
+            w.maxlen[t] = mx;
+        }
+        BZD_SYNC();
+        if (BZD_UNI(w.bad)) BZD_FAIL(BZD_K_FORMAT);
+        const uint32_t mn = BZD_UNI(w.minlen[t]), mx = BZD_UNI(w.maxlen[t]);
+        for (uint32_t e = lane; e < (1u << BZD_LUT_BITS); e += BZD_LANES) { // the lanes fill the look-up table
+            uint32_t entry = 0;
+            for (uint32_t l = mn; l <= mx && l <= BZD_LUT_BITS; l++) {
+                const int32_t code = (int32_t)(e >> (BZD_LUT_BITS - l));
+                if (code <= w.limit[t][l]) {
+                    const uint32_t idx = (uint32_t)(code + w.base[t][l]);
+                    if (idx < alpha) entry = (l << 9) | w.perm[t][idx];
+                    break;
+                }
+            }
+            w.lut[t][e] = (uint16_t)entry;
+        }
+        BZD_SYNC();
+    }
+    // symbols -> inverse RLE2 and MTF -> last column
+    const uint32_t eob = alpha - 1;
+    uint32_t nblock = 0, run = 0, run_weight = 1, gi = 0, group_left = 0, t = 0, mn = 0, mx = 0;
+    for (;;) {
+        if (group_left == 0) {
+            if (gi >= nsel) BZD_FAIL(BZD_K_FORMAT);
+            t = BZD_UNI(w.sel[gi]);
+            gi++;
+            group_left = BZD_GROUP;
+            mn = BZD_UNI(w.minlen[t]);
+            mx = BZD_UNI(w.maxlen[t]);
+        }
+        group_left--;
+        const uint32_t bits = bzd_peek(r, BZD_MAX_LEN);
+        const uint32_t e = BZD_UNI(w.lut[t][bits >> (BZD_MAX_LEN - BZD_LUT_BITS)]);
+        uint32_t l, sym;
+        if (e) {
+            l = e >> 9;
+            sym = e & 511u;
+        } else { // a code longer than the table's index, or none at all
+            l = mn;
+            while (l <= mx && (int32_t)(bits >> (BZD_MAX_LEN - l)) > (int32_t)BZD_UNI(w.limit[t][l])) l++;
+            if (l > mx) BZD_FAIL(r.pos + mx > r.n * 8 ? BZD_K_TRUNC : BZD_K_FORMAT);
+            const uint32_t idx = (bits >> (BZD_MAX_LEN - l)) + BZD_UNI(w.base[t][l]);
+            if (idx >= alpha) BZD_FAIL(BZD_K_FORMAT);
+            sym = BZD_UNI(w.perm[t][idx]);
+        }
+        bzd_skip(r, l);
+        if (bzd_over(r)) BZD_FAIL(BZD_K_TRUNC);
+        if (sym <= 1) { // RUNA / RUNB: bijective base-2 digits of a run of the front byte
+            if (run_weight > (1u << 21)) BZD_FAIL(BZD_K_FORMAT);
+            run += run_weight << sym;
+            run_weight <<= 1;
+            continue;
+        }
+        if (run) {
+            const uint32_t b = BZD_UNI(w.mtf[0]);
+            if (run > block_max - nblock) BZD_FAIL(BZD_K_FORMAT);
+            for (uint32_t i = lane; i < run; i += BZD_LANES) L[nblock + i] = (uint8_t)b; // whole-wave stores
+            nblock += run;
+            run = 0;
+            run_weight = 1;
+        }
+        if (sym == eob) break;
+        const uint32_t p = sym - 1; // MTF position, >= 1
+        if (p >= nin) BZD_FAIL(BZD_K_FORMAT);
+        const uint32_t v = BZD_UNI(w.mtf[p]);
+        // mtf[1 .. p] = mtf[0 .. p-1], from the top down, 64 entries at a time: a slice reads before it writes, and what it
+        // reads lies below what the slices before it wrote
+        for (uint32_t j0 = 0; j0 < p; j0 += BZD_LANES) {
+            const uint32_t j = j0 + lane;
+            const bool act = j < p;
+            const uint8_t tv = act ? w.mtf[p - j - 1] : (uint8_t)0;
+            BZD_SYNC();
+            if (act) w.mtf[p - j] = tv;
+            BZD_SYNC();
+        }
+        if (l0) w.mtf[0] = (uint8_t)v;
+        BZD_SYNC();
+        if (nblock >= block_max) BZD_FAIL(BZD_K_FORMAT);
+        if (l0) L[nblock] = (uint8_t)v;
+        nblock++;
+    }
+    res.nblock = nblock;
+    if (nblock == 0 || origptr >= nblock) BZD_FAIL(BZD_K_FORMAT);
+    res.end_bit = r.pos;
+#undef BZD_FAIL
+}
+
+// ---- the footer at bit `pos` (its magic): stream CRC, padding to a byte, and what follows
+BZD_FN void bzd_parse_footer(const uint8_t *in, uint64_t n, uint64_t pos, BzdResult &res)
+{
+    BzdBits r;
+    bzd_seek(r, in, n, pos + 48);
+    res.kind = BZD_OK;
+    res.errpos = 0;
+    res.nblock = 0;
+    res.origptr = 0;
+    res.follow = 0;
+    res.pad = 0;
+    res.crc = bzd_get(r, 32);
+    const uint64_t end = (r.pos + 7) >> 3;
+    res.end_bit = end * 8;
+    if (bzd_over(r)) {
+        res.kind = BZD_K_TRUNC;
+        res.errpos = r.n * 8;
+        return;
+    }
+    if (end == n) return;
+    res.follow = 2;
+    if (end + 4 <= n) {
+        const uint32_t h = BZD_UNI(bzd_load32(in, n, end));
+        const uint32_t lv = h & 255u;
+        if ((h >> 8) == 0x425A68u && lv >= '1' && lv <= '9') res.follow = 0x100u | (lv - '0');
+    }
+}
+
+// ---- inverse RLE1 as a state machine: four equal bytes, then a count byte (libbz2's rule; the state resets behind a count
+// byte and at the block start).  State = equal bytes seen so far, 0..4; the byte met in state 4 is a count byte.  A byte's
+// transition depends only on whether it equals the byte before it, so a stretch of bytes is a map {0..4} -> {0..4} (three
+// bits a state) and maps compose: which bytes are count bytes comes out of a scan, not out of a walk.
+constexpr uint32_t BZD_RL_EQ = 1u | 2u << 3 | 3u << 6 | 4u << 9 | 0u << 12; // the byte equals its predecessor
+constexpr uint32_t BZD_RL_NE = 1u | 1u << 3 | 1u << 6 | 1u << 9 | 0u << 12; // it does not (or the block starts)
+constexpr uint32_t BZD_RL_ID = 0u | 1u << 3 | 2u << 6 | 3u << 9 | 4u << 12;
+BZD_FN uint32_t bzd_rl_apply(uint32_t m, uint32_t s) { return (m >> (3 * s)) & 7u; }
+BZD_FN uint32_t bzd_rl_compose(uint32_t first, uint32_t then)
+{
+    uint32_t r = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t s = 0; s < 5; s++) r |= bzd_rl_apply(then, bzd_rl_apply(first, s)) << (3 * s);
+    return r;
+}
+BZD_FN uint32_t bzd_rl_step(uint32_t s, bool eq) { return s == 4 ? 0u : (eq && s >= 1 ? s + 1 : 1u); }

@@ -1397,6 +1397,26 @@ int crc_device(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t *crc_out)
     return BZH_OK;
 }
 
+// CRCs of nb byte ranges of d_in (the decoder's output blocks): d_blocks[k].in_off / in_len in, d_blocks[k].crc out.  Queued on
+// the context's stream; the caller waits.
+int crc_blocks_device(bzh_ctx *ctx, const uint8_t *d_in, BlockDesc *d_blocks, uint32_t *d_acc, uint32_t nb, uint64_t maxlen)
+{
+    if (nb == 0) return BZH_OK;
+    hipStream_t st = ctx->stream;
+    const CrcTables *ct = nullptr;
+    BZH_TRY(crc_tables(ctx, &ct));
+    HIP_TRY(ctx, hipMemsetAsync(d_acc, 0, (size_t)nb * 4, st));
+    const uint32_t ctiles = (uint32_t)((maxlen + CRC_TILE - 1) / CRC_TILE);
+    if (ctiles)
+        for (uint32_t k0 = 0; k0 < nb; k0 += 32768) { // grid.y limit
+            const uint32_t cnt = nb - k0 < 32768 ? nb - k0 : 32768;
+            crc_tiles<<<dim3(std::min(1024u, (ctiles + CRC_WG_TILES - 1) / CRC_WG_TILES), cnt), RL_THREADS, 0, st>>>(d_in, d_blocks + k0, d_acc + k0, ct, nullptr);
+        }
+    crc_finish<<<dim3(nb), 64, 0, st>>>(d_blocks, d_acc, nb, ct, nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    return BZH_OK;
+}
+
 // ================================================================================================================
 // Many inputs in one plan (bzh_plan_many_device, bzh_encode_many*): every input is cut from its own start to its own end
 // ================================================================================================================

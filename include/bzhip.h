@@ -1,6 +1,7 @@
 /*
  * bzhip.h -- C ABI of libbzhip.so: an MI355X (gfx950) bzip2 block encoder that emits the
- * same bits as jgbyrne/banzai v0.3.1.
+ * same bits as jgbyrne/banzai v0.3.1 -- and, since the reference only "(currently)" lacks one, a
+ * decoder for what it, libbz2 and this library write (bzh_decode*, below the encode entry points).
  *
  * The reference has no FFI; its boundary is the crate's public functions and the private
  * per-stage functions.  Each entry point below names the reference
@@ -35,7 +36,8 @@ typedef enum {
     BZH_E_NOMEM = -2, /* host or device allocation failed */
     BZH_E_HIP = -3,   /* HIP runtime error / no usable device */
     BZH_E_CAP = -4,   /* output buffer too small; *out_len holds the size needed where stated */
-    BZH_E_STATE = -5  /* call sequence error (e.g. encode_range without a plan) */
+    BZH_E_STATE = -5, /* call sequence error (e.g. encode_range without a plan) */
+    BZH_E_DATA = -6   /* the input is not a valid bzip2 stream; bzh_last_error says what and where */
 } bzh_status;
 
 /* One bzip2 block of a plan: which raw bytes it consumes and what RLE1 makes of them.
@@ -145,6 +147,40 @@ BZH_API size_t bzh_encode_many_bound(int level, const size_t *lens, size_t count
 /* Seam: the plan alone.  bzh_plan_blocks then lists every input's blocks in input order, in_off relative to d_in; for every
  * input they equal what bzh_rle1_split returns for that input alone (offsets shifted by where it starts). */
 BZH_API int bzh_plan_many_device(bzh_ctx *ctx, const void *d_in, const size_t *lens, size_t count, size_t *nblocks);
+
+/* ---- decode: the inverse of the whole path.  The reference has no counterpart (README.md:9) ---------- */
+
+/* in[0..n) holds one or more complete bzip2 streams back to back, as `bzip2 -d` accepts: of any level up to the context's
+ * (a higher one: BZH_E_ARG), by any encoder (libbz2: 2..6 tables and real selectors; this library in either Huffman mode;
+ * banzai).  Concatenation is handled inside the call: a pbzip2 file is thousands of streams.  out receives the decoded bytes
+ * of all streams, *out_len their count, *consumed the bytes of `in` that belong to the decoded streams.
+ * Where the input ends: behind a stream's footer, remaining bytes that begin with "BZh1".."BZh9" ARE the next stream and its
+ * errors are errors; any other bytes are foreign, and decoding stops there with BZH_OK and *consumed < n.  Not one decoded
+ * stream is BZH_E_DATA.
+ * BZH_E_CAP: the output does not fit.  The call still finishes sizing and reports the total needed in *out_len (known only
+ * once every block is decoded, as for bzh_encode_many); out[0..cap) is then unspecified; repeat the call with that size.
+ * BZH_E_DATA: bad magic, truncation, a field outside the format (selectors 1..32767, code lengths 1..20, an over-subscribed
+ * code, origPtr >= nblock, more bytes than the level's block size, a block that ends in four equal bytes without the count
+ * byte libbz2 insists on), a block or stream CRC mismatch, and a RANDOMISED block: no current encoder writes one (a bzip2
+ * 0.9.0 feature), so they are refused, not decoded.  bzh_last_error names the kind, the stream, the block and the bit
+ * position.  Every read and write of the decode kernels is bounded by construction, so a damaged stream yields a status and
+ * the context stays usable.  Like every entry point the call joins a streaming pass in flight, runs on the context's stream
+ * and honours bzh_set_profiling. */
+BZH_API int bzh_decode(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len, size_t *consumed);
+/* Same, input and output resident in HBM (d_out may be null when cap is 0: sizing only). */
+BZH_API int bzh_decode_device(bzh_ctx *ctx, const void *d_in, size_t n, void *d_out, size_t cap, size_t *out_len,
+                              size_t *consumed);
+
+/* Stage timings (milliseconds, HIP events, filled when profiling is enabled) and counters of the last bzh_decode* call.  A struct
+ * of its own: bzh_stats keeps its layout. */
+typedef struct {
+    double ms_scan, ms_entropy, ms_unbwt, ms_unrle, ms_crc, ms_total;
+    uint64_t streams, blocks;      /* decoded */
+    uint64_t candidates;           /* magics the scan found, at any bit alignment */
+    uint64_t candidates_off_chain; /* of those: inside a block's payload or behind the end, dropped by the chain walk */
+    uint64_t in_bytes, out_bytes;
+} bzh_decode_stats;
+BZH_API int bzh_get_decode_stats(const bzh_ctx *ctx, bzh_decode_stats *out);
 
 /* ---- streaming: encode() fed by a reader that yields arbitrary chunks (lib/rle.rs:30-92) ------- */
 
@@ -283,6 +319,10 @@ BZH_API int bzh_mtf(bzh_ctx *ctx, const uint8_t *bwt, size_t n, const uint8_t *h
  * code_lengths (optional) receives num_tables x 258 final lengths, *num_tables the count. */
 BZH_API int bzh_huffman(bzh_ctx *ctx, const uint16_t *syms, size_t m, uint32_t num_syms, const uint32_t *freqs,
                 uint8_t *bits_out, size_t cap, uint64_t *nbits, uint8_t *code_lengths, uint32_t *num_tables);
+
+/* The decoder's scan: the bit positions, ascending, of every occurrence of the block magic 0x314159265359 (kind 0) and of
+ * the footer magic 0x177245385090 (kind 1) in in[0..n), at any bit alignment.  *count = occurrences; BZH_E_CAP if max is smaller. */
+BZH_API int bzh_decode_scan(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t *bitpos, uint8_t *kind, size_t max, size_t *count);
 
 #ifdef __cplusplus
 }

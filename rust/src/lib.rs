@@ -37,6 +37,57 @@ extern "C" {
         out_len: *mut usize,
     ) -> c_int;
     fn bzh_stream_consumed(ctx: *const BzhCtx) -> usize;
+    // The decoder (beyond the reference, which has none): `decompress` at the end of this file wraps bzh_decode; the rest is declared
+    // for callers that need the device path, the statistics or the scan.  BZH_E_CAP (-4) reports the size needed in *out_len; BZH_E_DATA (-6) is a damaged stream.
+    fn bzh_decode(
+        ctx: *mut BzhCtx,
+        input: *const u8,
+        n: usize,
+        out: *mut u8,
+        cap: usize,
+        out_len: *mut usize,
+        consumed: *mut usize,
+    ) -> c_int;
+    #[allow(dead_code)]
+    fn bzh_decode_device(
+        ctx: *mut BzhCtx,
+        d_in: *const std::os::raw::c_void,
+        n: usize,
+        d_out: *mut std::os::raw::c_void,
+        cap: usize,
+        out_len: *mut usize,
+        consumed: *mut usize,
+    ) -> c_int;
+    #[allow(dead_code)]
+    fn bzh_get_decode_stats(ctx: *const BzhCtx, out: *mut BzhDecodeStats) -> c_int;
+    #[allow(dead_code)]
+    fn bzh_decode_scan(
+        ctx: *mut BzhCtx,
+        input: *const u8,
+        n: usize,
+        bitpos: *mut u64,
+        kind: *mut u8,
+        max: usize,
+        count: *mut usize,
+    ) -> c_int;
+}
+
+/// `bzh_decode_stats` of include/bzhip.h.
+#[repr(C)]
+#[allow(dead_code)]
+pub struct BzhDecodeStats {
+    pub ms_scan: f64,
+    pub ms_entropy: f64,
+    pub ms_unbwt: f64,
+    pub ms_unrle: f64,
+    pub ms_crc: f64,
+    pub ms_total: f64,
+    pub streams: u64,
+    pub blocks: u64,
+    pub candidates: u64,
+    pub candidates_off_chain: u64,
+    pub in_bytes: u64,
+    pub out_bytes: u64,
 }
 
 // A context and the two host buffers an encode works with.  They stay together in the pool: the output buffer is sized by
@@ -180,4 +231,33 @@ where
     let outf = fs::File::create(out_path.as_ref())?;
     // large reads: each fill_buf slice becomes one H2D copy (see encode)
     encode(io::BufReader::with_capacity(16 << 20, inf), io::BufWriter::new(outf), 9)
+}
+
+/// Decode one or more complete bzip2 streams lying back to back in `data` (any level, any encoder), as `bzip2 -d` does.
+///
+/// Beyond banzai 0.3.1, which has no decompressor.  A damaged stream is an `io::Error` that names the kind, the stream,
+/// the block and the bit position.  The output is sized from the input, then once more from what the library reports.
+pub fn decompress(data: &[u8]) -> io::Result<Vec<u8>> {
+    let device: c_int = std::env::var("BZHIP_DEVICE").ok().and_then(|s| s.parse().ok()).unwrap_or(0);
+    let ctx = checkout(device, 9)?; // (an error below drops it)
+    let handle = ctx.handle;
+    let mut cap = data.len() * 6 + 65536;
+    let mut out: Vec<u8> = Vec::new();
+    let mut status: c_int = 0;
+    for _ in 0..2 {
+        out.resize(cap, 0);
+        let (mut out_len, mut consumed) = (0usize, 0usize);
+        status = unsafe { bzh_decode(handle, data.as_ptr(), data.len(), out.as_mut_ptr(), cap, &mut out_len, &mut consumed) };
+        if status == -4 {
+            cap = out_len; // BZH_E_CAP: the size needed
+            continue;
+        }
+        out.truncate(out_len);
+        break;
+    }
+    if status != 0 {
+        return Err(to_io_error(handle, status));
+    }
+    checkin(device, 9, ctx);
+    Ok(out)
 }
