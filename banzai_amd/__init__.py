@@ -11,15 +11,25 @@ and, beyond the reference (which "(currently)" has no decompressor, README.md:9)
     decompress(data) -> bytes                            (one or more .bz2 streams, as bz2.decompress)
     decode(reader, writer) -> bytes written
 
+and random access into a .bz2 without decoding all of it (bzip2 blocks are independent once their start bit is known):
+
+    build_index(data) -> BlockIndex                      (every block: where it starts, what it decodes to; verified)
+    decompress_range(data, index, offset, length) -> bytes
+    IndexedReader(source, index=None)                    (read / seek over the decoded bytes of bytes or a file)
+
 Everything is computed by hand-written HIP kernels behind the C ABI in include/bzhip.h
 (libbzhip.so); there is no CPU path.  `reader` is any object with .read(), `writer` any object
 with .write() (the Rust signature takes BufRead / BufWriter<W>).
 """
 import io
+import struct
+
+import numpy as np
 
 from . import _native
 
-__all__ = ["encode", "encode_many", "encode_file", "decompress", "decode", "Context", "MultiContext", "BzhError"]
+__all__ = ["encode", "encode_many", "encode_file", "decompress", "decode", "build_index", "decompress_range", "BlockIndex",
+           "IndexedReader", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
 MultiContext = _native.MultiContext
@@ -197,3 +207,196 @@ def decode(reader, writer, device=0):
     if hasattr(writer, "flush"):
         writer.flush()
     return len(out)
+
+
+def _bytes_view(data, who):
+    if isinstance(data, str):
+        raise TypeError(f"{who} takes a bytes-like object, not str")
+    try:
+        return memoryview(data).cast("B")
+    except TypeError:
+        raise TypeError(f"{who} takes a bytes-like object, not {type(data).__name__}") from None
+
+
+def _int_arg(v, name):
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise TypeError(f"{name} must be an int, not {type(v).__name__}")
+    if v < 0:
+        raise ValueError(f"{name} must not be negative")
+    return v
+
+
+class BlockIndex:
+    """The blocks of an indexed .bz2 input (bzh_decode_index): `.entries` is a numpy structured array of the 40-byte
+    bzh_index_entry layout (bit_pos, end_bit, out_off, out_len, crc, stream, level), `.size` the decoded bytes of all streams,
+    `.consumed` the bytes of the input that belong to them; len() counts the blocks.  Built once per file, kept beside it with
+    to_bytes() / from_bytes()."""
+
+    MAGIC = b"BZhIDX\r\n"
+    VERSION = 1
+    _HEAD = struct.Struct("<8sIIQQ")  # magic, version, reserved, entries, consumed
+
+    def __init__(self, entries, consumed=0):
+        self.entries = np.ascontiguousarray(entries, dtype=_native.INDEX_DTYPE)
+        what = self._ill_formed(self.entries)
+        if what:
+            raise ValueError(f"block index: {what}")
+        self.consumed = int(consumed)
+        self.size = int(self.entries["out_off"][-1]) + int(self.entries["out_len"][-1]) if self.entries.size else 0
+
+    @staticmethod
+    def _ill_formed(e):
+        """what bzh_decode_range refuses an index for (None: well formed)"""
+        if e.size == 0:
+            return None
+        if np.any(e["end_bit"] <= e["bit_pos"]):
+            return "end_bit is not behind bit_pos"
+        if np.any(e["bit_pos"][1:] <= e["bit_pos"][:-1]):
+            return "bit_pos does not ascend"
+        sums = np.concatenate([np.zeros(1, np.uint64), np.cumsum(e["out_len"][:-1], dtype=np.uint64)])  # (uint64 throughout)
+        if np.any(e["out_off"] != sums):
+            return "out_off is not the running sum of the sizes before it"
+        if np.any((e["level"] < 1) | (e["level"] > 9)):
+            return "a level outside 1..9"
+        return None
+
+    def __len__(self):
+        return int(self.entries.size)
+
+    def span(self, off, length):
+        """(first, last, byte_lo, byte_hi): the entries [first, last) that decoded bytes [off, off + length) touch and the
+        bytes [byte_lo, byte_hi) of the compressed input that hold them (bzh_index_span; an empty range: first == last)"""
+        return _native.index_span(self.entries, _int_arg(off, "offset"), _int_arg(length, "length"))
+
+    def to_bytes(self):
+        return self._HEAD.pack(self.MAGIC, self.VERSION, 0, len(self), self.consumed) + self.entries.tobytes()
+
+    @classmethod
+    def from_bytes(cls, blob):
+        view = _bytes_view(blob, "BlockIndex.from_bytes")
+        if len(view) < cls._HEAD.size:
+            raise ValueError("block index: truncated header")
+        magic, version, _, count, consumed = cls._HEAD.unpack_from(view, 0)
+        if magic != cls.MAGIC:
+            raise ValueError("block index: bad magic")
+        if version != cls.VERSION:
+            raise ValueError(f"block index: version {version}, this library reads version {cls.VERSION}")
+        if len(view) != cls._HEAD.size + count * _native.INDEX_DTYPE.itemsize:
+            raise ValueError(f"block index: {len(view)} bytes do not hold a header and {count} entries")
+        return cls(np.frombuffer(view, dtype=_native.INDEX_DTYPE, count=count, offset=cls._HEAD.size).copy(), consumed)
+
+
+def build_index(data, device=0):
+    """Index the bzip2 stream(s) in `data` (bytes-like; the same inputs decompress() takes) -> BlockIndex.  Everything a full
+    decode verifies is verified while the index is built, every block and stream CRC included, but nothing is expanded: no
+    output buffer is needed.  A damaged stream raises BzhError with status -6."""
+    view = _bytes_view(data, "build_index")
+    entries, _, consumed = _ctx(9, device).decode_index(view)
+    return BlockIndex(entries, consumed)
+
+
+def _index_arg(index):
+    if not isinstance(index, BlockIndex):
+        raise TypeError(f"index must be a BlockIndex, not {type(index).__name__}")
+    return index
+
+
+def decompress_range(data, index, offset, length, device=0):
+    """Decoded bytes [offset, offset + length) of the indexed `data` (bytes-like), clipped to the decoded size -> bytes.  Only
+    the blocks the range touches are decoded, from only their compressed bytes; each one's CRC is verified, stream CRCs are not
+    (build_index has), and damage in other blocks goes unseen.  A block that does not match its entry raises BzhError -6."""
+    view = _bytes_view(data, "decompress_range")
+    index = _index_arg(index)
+    offset, length = _int_arg(offset, "offset"), _int_arg(length, "length")
+    _, _, lo, hi = index.span(offset, length)
+    return _ctx(9, device).decode_range(view[lo:hi], index.entries, offset, length, in_byte_base=lo)
+
+
+class IndexedReader(io.RawIOBase):
+    """A seekable, read-only file of the DECODED bytes of `source`: bytes-like, or a seekable binary file holding .bz2
+    stream(s).  Every read decodes just the blocks it touches (decompress_range); with a file source it fetches from the file
+    only the compressed bytes of those blocks.  index=None reads the source once and builds the index."""
+
+    def __init__(self, source, index=None, device=0):
+        super().__init__()
+        if hasattr(source, "read") and hasattr(source, "seek"):
+            self._file, self._view = source, None
+        else:
+            self._file, self._view = None, _bytes_view(source, "IndexedReader")
+        if index is None:
+            if self._file is not None:
+                self._file.seek(0)
+                data = self._file.read()
+                if not isinstance(data, (bytes, bytearray, memoryview)):
+                    raise TypeError("source.read() must return bytes")
+            else:
+                data = self._view
+            index = build_index(data, device)
+        self.index = _index_arg(index)
+        self._device = device
+        self._pos = 0
+
+    @property
+    def size(self):
+        return self.index.size
+
+    def readable(self):
+        return True
+
+    def seekable(self):
+        return True
+
+    def writable(self):
+        return False
+
+    def tell(self):
+        return self._pos
+
+    def seek(self, offset, whence=io.SEEK_SET):
+        if isinstance(offset, bool) or not isinstance(offset, int):
+            raise TypeError(f"offset must be an int, not {type(offset).__name__}")
+        if whence == io.SEEK_SET:
+            pos = offset
+        elif whence == io.SEEK_CUR:
+            pos = self._pos + offset
+        elif whence == io.SEEK_END:
+            pos = self.index.size + offset
+        else:
+            raise ValueError(f"invalid whence ({whence})")
+        if pos < 0:
+            raise ValueError(f"negative seek position {pos}")
+        self._pos = pos
+        return pos
+
+    def _fetch(self, n):
+        """the next n decoded bytes (fewer at the end), the position moved behind them"""
+        n = max(0, min(n, self.index.size - self._pos))
+        if n == 0:
+            return b""
+        _, _, lo, hi = self.index.span(self._pos, n)
+        if self._file is not None:
+            self._file.seek(lo)
+            comp = self._file.read(hi - lo)
+            if not isinstance(comp, (bytes, bytearray, memoryview)):
+                raise TypeError("source.read() must return bytes")
+            if len(comp) != hi - lo:
+                raise EOFError(f"the source holds {len(comp)} of the {hi - lo} bytes from {lo} on that the index names")
+        else:
+            comp = self._view[lo:hi]
+        out = _ctx(9, self._device).decode_range(comp, self.index.entries, self._pos, n, in_byte_base=lo)
+        self._pos += len(out)
+        return out
+
+    def read(self, n=-1):
+        if n is None or n < 0:
+            n = max(0, self.index.size - self._pos)
+        return self._fetch(n)
+
+    def readall(self):
+        return self.read(-1)
+
+    def readinto(self, b):
+        m = memoryview(b).cast("B")
+        out = self._fetch(len(m))
+        m[:len(out)] = out
+        return len(out)

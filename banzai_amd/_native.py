@@ -53,6 +53,18 @@ class DecodeStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class IndexEntry(ctypes.Structure):
+    """bzh_index_entry: one decoded block of an indexed input"""
+    _fields_ = [("bit_pos", ctypes.c_uint64), ("end_bit", ctypes.c_uint64), ("out_off", ctypes.c_uint64),
+                ("out_len", ctypes.c_uint32), ("crc", ctypes.c_uint32), ("stream", ctypes.c_uint32), ("level", ctypes.c_uint32)]
+
+
+INDEX_DTYPE = np.dtype([("bit_pos", "<u8"), ("end_bit", "<u8"), ("out_off", "<u8"), ("out_len", "<u4"), ("crc", "<u4"),
+                        ("stream", "<u4"), ("level", "<u4")])
+assert INDEX_DTYPE.itemsize == ctypes.sizeof(IndexEntry) == 40
+idxp = ctypes.POINTER(IndexEntry)
+
+
 class KStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("ms", ctypes.c_double), ("launches", ctypes.c_uint64),
                 ("alg_bytes", ctypes.c_uint64)]
@@ -85,6 +97,15 @@ SIGNATURES = {
     "bzh_decode_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                          ctypes.c_size_t, szp, szp]),
     "bzh_get_decode_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DecodeStats)]),
+    "bzh_decode_index": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, idxp, ctypes.c_size_t, szp, u64p, szp]),
+    "bzh_decode_index_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, idxp, ctypes.c_size_t, szp,
+                                               u64p, szp]),
+    "bzh_index_span": (ctypes.c_int, [idxp, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, szp, szp, u64p, u64p]),
+    "bzh_decode_range": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64, idxp, ctypes.c_size_t,
+                                        ctypes.c_uint64, ctypes.c_uint64, u8p, ctypes.c_size_t, szp]),
+    "bzh_decode_range_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, idxp,
+                                               ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                               ctypes.c_size_t, szp]),
     "bzh_decode_scan": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u64p, u8p, ctypes.c_size_t, szp]),
     "bzh_stream_begin": (ctypes.c_int, [ctypes.c_void_p]),
     "bzh_stream_feed": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, u8p, ctypes.c_size_t, szp]),
@@ -145,6 +166,26 @@ def encode_many_bound(level, lens):
     """bzh_encode_many_bound: upper bound of the output of bzh_encode_many for these input lengths (0 for a bad level)"""
     lens = np.ascontiguousarray(lens, dtype=np.uint64)
     return int(lib().bzh_encode_many_bound(level, ptr(lens, szp) if lens.size else None, lens.size))
+
+
+def _entries(entries):
+    """a contiguous array of the 40-byte entries (no copy when it already is one) and its ctypes pointer"""
+    e = np.ascontiguousarray(entries, dtype=INDEX_DTYPE)
+    return e, (e.ctypes.data_as(idxp) if e.size else None)
+
+
+def index_span(entries, off, length):
+    """bzh_index_span (host arithmetic, no GPU): (first, last, byte_lo, byte_hi) -- the entries [first, last) that output bytes
+    [off, off + length) touch, and the bytes of the indexed input that hold them"""
+    if off < 0 or length < 0:
+        raise ValueError("offset and length must not be negative")
+    e, p = _entries(entries)
+    first, last = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    lo, hi = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    st = lib().bzh_index_span(p, e.size, off, length, ctypes.byref(first), ctypes.byref(last), ctypes.byref(lo), ctypes.byref(hi))
+    if st != 0:
+        raise BzhError(st, lib().bzh_strerror(st).decode())
+    return int(first.value), int(last.value), int(lo.value), int(hi.value)
 
 
 def lib():
@@ -395,6 +436,52 @@ class Context:
         self.check(lib().bzh_decode_device(self._h, ctypes.c_void_p(d_in), n, ctypes.c_void_p(d_out), cap, ctypes.byref(olen),
                                            ctypes.byref(used)))
         return int(olen.value), int(used.value)
+
+    def decode_index(self, data):
+        """bzh_decode_index: the verified block index of the stream(s) in `data` -> (entries as a structured array of
+        INDEX_DTYPE, decoded bytes in total, input bytes consumed)"""
+        a = np.frombuffer(data, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        cnt, used, total = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint64(0)
+        # room for every block the input can hold, so that the build runs once: a block is at least 174 bits (magic, CRC,
+        # origPtr, one sector of the symbol map, one selector, two tables of three lengths, one symbol and the end of block).
+        # (np.empty: pages the library does not write are never touched)
+        cap = n // 21 + 1
+        while True:
+            ent = np.empty(cap, dtype=INDEX_DTYPE)
+            st = lib().bzh_decode_index(self._h, ptr(src), n, ent.ctypes.data_as(idxp), cap, ctypes.byref(cnt), ctypes.byref(total),
+                                        ctypes.byref(used))
+            if st == -4 and cnt.value > cap:
+                cap = cnt.value
+                continue
+            self.check(st)
+            return ent[:cnt.value].copy(), int(total.value), int(used.value)
+
+    def decode_range(self, data, entries, off, length, in_byte_base=0):
+        """bzh_decode_range: output bytes [off, off + length) of the indexed input, clipped to its total; `data` holds the
+        compressed bytes from byte `in_byte_base` of that input on (all of it, or just the span of the range)"""
+        if off < 0 or length < 0:
+            raise ValueError("offset and length must not be negative")
+        a = np.frombuffer(data, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        e, p = _entries(entries)
+        total = int(e["out_off"][-1]) + int(e["out_len"][-1]) if e.size else 0
+        cap = max(0, min(length, total - off))
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        got = ctypes.c_size_t(0)
+        self.check(lib().bzh_decode_range(self._h, ptr(src), n, in_byte_base, p, e.size, off, length, ptr(out), cap,
+                                          ctypes.byref(got)))
+        return out[:got.value].tobytes()
+
+    def decode_range_device(self, d_in, n, entries, off, length, d_out, cap, in_byte_base=0):
+        """bzh_decode_range_device on integer device addresses -> bytes written at d_out"""
+        e, p = _entries(entries)
+        got = ctypes.c_size_t(0)
+        self.check(lib().bzh_decode_range_device(self._h, ctypes.c_void_p(d_in), n, in_byte_base, p, e.size, off, length,
+                                                 ctypes.c_void_p(d_out), cap, ctypes.byref(got)))
+        return int(got.value)
 
     def decode_stats(self):
         s = DecodeStats()

@@ -1460,6 +1460,144 @@ extern "C" int bzh_decode(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *ou
     });
 }
 
+// ---- random access (decode.hip): the index is bzh_decode_device's flow with no output, a range needs neither scan nor chain
+extern "C" int bzh_decode_index_device(bzh_ctx *ctx, const void *d_in, size_t n, bzh_index_entry *idx, size_t max, size_t *count,
+                                       uint64_t *out_total, size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n) || (!idx && max) || !count || !out_total) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    ctx->evnext = 0;
+    ctx->sort_spans.clear();
+    kstats_reset(ctx);
+    memset(&ctx->dstats, 0, sizeof ctx->dstats);
+    ctx->dstats.in_bytes = n;
+    *count = 0;
+    *out_total = 0;
+    if (consumed) *consumed = 0;
+    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
+    if (ctx->profiling) {
+        t0 = bzh_event(ctx);
+        hipEventRecord(t0, st);
+    }
+    std::vector<uint64_t> cands;
+    BZH_TRY(decode_scan_run(ctx, (const uint8_t *)d_in, n, cands));
+    if (ctx->profiling) {
+        t1 = bzh_event(ctx);
+        hipEventRecord(t1, st);
+    }
+    ctx->dstats.candidates = cands.size();
+    BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(cands.size(), 1), ctx->max_batch)));
+    std::vector<bzh_index_entry> entries;
+    size_t total = 0;
+    const int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, &entries);
+    if (ctx->profiling) {
+        t2 = bzh_event(ctx);
+        hipEventRecord(t2, st);
+        HIP_TRY(ctx, bzh_stream_wait(st));
+        ctx->dstats.ms_scan = span_ms(t0, t1);
+        ctx->dstats.ms_total = span_ms(t0, t2);
+    }
+    if (rc != BZH_OK) return rc;
+    *count = entries.size();
+    *out_total = total;
+    if (entries.size() > max) {
+        bzh_set_error(ctx, "decode index: %zu entries, room for %zu", entries.size(), max);
+        return BZH_E_CAP;
+    }
+    if (!entries.empty()) memcpy(idx, entries.data(), entries.size() * sizeof(bzh_index_entry));
+    return BZH_OK;
+    });
+}
+
+extern "C" int bzh_decode_index(bzh_ctx *ctx, const uint8_t *in, size_t n, bzh_index_entry *idx, size_t max, size_t *count,
+                                uint64_t *out_total, size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n) || (!idx && max) || !count || !out_total) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, n + 16));
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, ctx->stream));
+    return bzh_decode_index_device(ctx, ctx->d_stage_in, n, idx, max, count, out_total, consumed);
+    });
+}
+
+extern "C" int bzh_decode_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                                       size_t count, uint64_t off, uint64_t len, void *d_out, size_t cap, size_t *out_len)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n) || (!d_out && cap) || (!idx && count) || !out_len) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    ctx->evnext = 0;
+    ctx->sort_spans.clear();
+    kstats_reset(ctx);
+    memset(&ctx->dstats, 0, sizeof ctx->dstats);
+    ctx->dstats.in_bytes = n;
+    *out_len = 0;
+    hipEvent_t t0 = nullptr, t2 = nullptr;
+    if (ctx->profiling) {
+        t0 = bzh_event(ctx);
+        hipEventRecord(t0, st);
+    }
+    BZH_TRY(decode_index_check(ctx, idx, count)); // (before any arithmetic on the entries)
+    size_t first = 0, last = 0;
+    uint64_t lo, hi;
+    BZH_TRY(bzh_index_span(idx, count, off, len, &first, &last, &lo, &hi));
+    BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(last - first, 1), ctx->max_batch)));
+    const int rc = decode_range_run(ctx, (const uint8_t *)d_in, n, in_byte_base, idx, count, off, len, (uint8_t *)d_out, cap, out_len);
+    if (ctx->profiling) {
+        t2 = bzh_event(ctx);
+        hipEventRecord(t2, st);
+        HIP_TRY(ctx, bzh_stream_wait(st));
+        ctx->dstats.ms_total = span_ms(t0, t2);
+    }
+    return rc;
+    });
+}
+
+extern "C" int bzh_decode_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                                uint64_t off, uint64_t len, uint8_t *out, size_t cap, size_t *out_len)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n) || (!out && cap) || (!idx && count) || !out_len) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    *out_len = 0;
+    BZH_TRY(decode_index_check(ctx, idx, count)); // (before any arithmetic on the entries)
+    // only the span goes up (a buffer that does not cover it goes up whole: the device call says what is missing)
+    size_t first = 0, last = 0;
+    uint64_t lo = 0, hi = 0;
+    BZH_TRY(bzh_index_span(idx, count, off, len, &first, &last, &lo, &hi));
+    const uint64_t total = count ? idx[count - 1].out_off + idx[count - 1].out_len : 0;
+    const uint64_t want = off < total ? std::min<uint64_t>(len, total - off) : 0;
+    if (want > cap) {
+        bzh_set_error(ctx, "decode range: the range holds %llu bytes, the buffer %zu", (unsigned long long)want, cap);
+        return BZH_E_ARG;
+    }
+    const bool covered = lo <= hi && in_byte_base <= lo && hi - in_byte_base <= n;
+    const uint64_t base = covered ? lo : in_byte_base;
+    const size_t un = covered ? (size_t)(hi - lo) : n;
+    const uint8_t *src = covered ? in + (lo - in_byte_base) : in;
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, un + 16));
+    if (want) BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, (size_t)want));
+    if (un) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, src, un, hipMemcpyHostToDevice, st));
+    size_t got = 0;
+    const int rc = bzh_decode_range_device(ctx, ctx->d_stage_in, un, base, idx, count, off, len, want ? ctx->d_stage_out : nullptr,
+                                           (size_t)want, &got);
+    if (rc != BZH_OK) return rc;
+    if (got) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, got, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, bzh_stream_wait(st));
+    *out_len = got;
+    return BZH_OK;
+    });
+}
+
 extern "C" int bzh_get_decode_stats(const bzh_ctx *ctx, bzh_decode_stats *out)
 {
     return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {

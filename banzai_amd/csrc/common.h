@@ -598,10 +598,16 @@ int rle1_emit(bzh_ctx *ctx, size_t b0, uint32_t B);                   // rle1.hi
 int crc_device(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t *crc_out); // rle1.hip
 // rle1.hip: CRCs of nb byte ranges of d_in (d_blocks[k].in_off / in_len, the longest maxlen bytes) into d_blocks[k].crc; no wait
 int crc_blocks_device(bzh_ctx *ctx, const uint8_t *d_in, BlockDesc *d_blocks, uint32_t *d_acc, uint32_t nb, uint64_t maxlen);
+struct CrcTables;                                                     // crc_gf.h
+int crc_tables(bzh_ctx *ctx, const CrcTables **out);                  // rle1.hip: the context's device copy of the GF(2) tables
 // decode.hip: every block / footer magic of d_in[0..n) as (bit position << 1 | kind), ascending; then the chain walk and the
 // back of the decoder over that list (the arena laid out for min(candidates, max_batch) blocks)
 int decode_scan_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, std::vector<uint64_t> &cands);
 int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t cap, size_t *out_len, size_t *consumed,
-                     const std::vector<uint64_t> &cands);
+                     const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index = nullptr);
+// decode.hip: the blocks of a verified index that [off, off + len) touches, from d_in = the indexed input from byte in_byte_base on
+int decode_index_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count); // BZH_E_ARG naming the entry that is ill formed
+int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                     uint64_t off, uint64_t len, uint8_t *d_out, size_t cap, size_t *out_len);
 
 hipEvent_t bzh_event(bzh_ctx *ctx);

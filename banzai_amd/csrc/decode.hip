@@ -7,11 +7,15 @@
 //   unbwt    : the inverse transform of the batch                                            (unbwt_run, bwt.hip)
 //   unrle    : inverse RLE1 -- roles by a scan of state maps, sizes, then the expansion      (unrle_maps / unrle_walk)
 //   crc      : block CRCs over the output ranges (rle1.hip), folded per stream on the host
+// Random access (bzh_decode_index*, bzh_decode_range*): the index is the chain walk with no output, every block's CRC taken
+// from the bytes behind the inverse BWT (unrle_crc); a range decodes the blocks its index entries name, no scan and no walk,
+// and clips the blocks at its two edges to the range (unrle_walk_win).
 #include <algorithm>
 #include <type_traits>
 #include <vector>
 
 #include "common.h"
+#include "crc_gf.h"
 #include "decode_core.h"
 
 // ---- scan ------------------------------------------------------------------------------------------------------
@@ -261,6 +265,135 @@ __global__ void __launch_bounds__(UR_THREADS) unrle_walk(UrArgs a)
     if (tail0 + threadIdx.x < tile_total) g[tail0 + threadIdx.x] = stage[tail0 + threadIdx.x];
 }
 
+// ---- random access: the expansion clipped to a window, and its CRC without the expansion -------------------------------
+struct UwArgs {
+    const uint32_t *wlo, *whi; // [K] the window of the block, in bytes of its own output
+    const int64_t *wbase;      // [K] out + wbase = where the block's first byte would lie (before `out` when the window cuts its head)
+    const uint32_t *bsize;     // [K] decoded bytes of the block
+    uint32_t *acc, *crc;       // [K] CRC accumulator (zeroed by the host), finished CRC
+    const CrcTables *ct;
+};
+
+static_assert(UR_ITEMS == BZD_UR_ITEMS, "decode_core.h walks the same 16 bytes a thread");
+
+// unrle_walk<true> for a block of which only [wlo, whi) is wanted.  Not one byte outside the window is stored: the staged tile
+// is copied out from the window's first byte to its last, the byte stores of a tile too large to stage are clipped run by run.
+__global__ void __launch_bounds__(UR_THREADS) unrle_walk_win(UrArgs a, UwArgs wa)
+{
+    __shared__ uint32_t lds[8];
+    __shared__ uint8_t stage[UR_STAGE];
+    const uint32_t b = a.slots[blockIdx.y], t = blockIdx.x, n = a.n[b];
+    const size_t ti = (size_t)b * a.T + t;
+    const uint32_t tile_total = a.tout[ti];
+    if (tile_total == 0) return;
+    const uint32_t toff = a.toff[ti], lo = wa.wlo[blockIdx.y], hi = wa.whi[blockIdx.y];
+    uint32_t ca, cb;
+    bzd_clip(toff, tile_total, lo, hi, &ca, &cb);
+    if (ca == cb) return; // the tile lies outside the window
+    const uint32_t tlo = ca - toff, thi = cb - toff; // the window inside the tile
+    const uint32_t entry = a.tstate[ti];
+    const UrBytes u = ur_load(a.x + (size_t)b * a.S, n, t * UR_TILE + threadIdx.x * UR_ITEMS);
+    uint32_t total;
+    const uint32_t ex = ur_scan(ur_thread_map(u), lds, &total);
+    const uint32_t s = bzd_rl_apply(ex, entry);
+    uint32_t outn = 0, sw = s, prev = u.prev;
+#pragma unroll
+    for (int k = 0; k < (int)UR_ITEMS; k++) {
+        if ((uint32_t)k < u.cnt) {
+            const uint32_t c = u.at(k);
+            outn += sw == 4 ? c : 1u;
+            sw = bzd_rl_step(sw, c == prev);
+            prev = c;
+        }
+    }
+    uint32_t summed;
+    const uint32_t o0 = block_excl_add(outn, lds, &summed);
+    // (tile_total is a.tout, what unrle_walk<false> summed over these same bytes and the host laid the output out by: it is
+    // needed before anything is loaded, for the early return, and it decides staged or not.  `summed` is this walk's own sum and
+    // equals it by construction; clipping to it as well keeps every position below both without relying on that.)
+    const uint32_t whi_t = min(thi, summed);
+    uint8_t *g = reinterpret_cast<uint8_t *>((uintptr_t)a.out + (uintptr_t)(wa.wbase[blockIdx.y] + (int64_t)toff));
+    if (tile_total > UR_STAGE) {
+        bzd_ur_emit(u.w, u.cnt, u.prev, s, o0, tlo, whi_t, [&](uint32_t q, uint8_t v) { g[q] = v; });
+        return;
+    }
+    bzd_ur_emit(u.w, u.cnt, u.prev, s, o0, tlo, whi_t, [&](uint32_t q, uint8_t v) { stage[q] = v; });
+    __syncthreads();
+    if (whi_t <= tlo) return;
+    // stage[tlo, whi_t) goes out in aligned words, its ragged edges byte by byte
+    uint8_t *gw = g + tlo;
+    const uint8_t *sw0 = stage + tlo;
+    const uint32_t len = whi_t - tlo;
+    const uint32_t head = min(len, (uint32_t)((0 - (uintptr_t)gw) & 3u));
+    const uint32_t words = (len - head) / 4, tail0 = head + words * 4;
+    if (threadIdx.x < head) gw[threadIdx.x] = sw0[threadIdx.x];
+    for (uint32_t i = threadIdx.x; i < words; i += UR_THREADS) {
+        const uint8_t *sp = sw0 + head + 4 * i;
+        *reinterpret_cast<uint32_t *>(gw + head + 4 * i) = (uint32_t)sp[0] | (uint32_t)sp[1] << 8 | (uint32_t)sp[2] << 16 | (uint32_t)sp[3] << 24;
+    }
+    if (tail0 + threadIdx.x < len) gw[tail0 + threadIdx.x] = sw0[tail0 + threadIdx.x];
+}
+
+// The CRC of a block's expansion from the bytes behind its inverse BWT.  The CRC is linear: a thread folds what its 16 bytes
+// stand for (literals and runs, entered in the state the scan hands it) into a register of its own, and that register times
+// x^(8 * bytes behind the thread's piece in the block) is the piece's share of the block's CRC.  The power splits in two: the
+// bytes behind the piece inside the tile (below 2^20: a product over the set bits, a thread each) and the bytes behind the tile
+// (one gf_pow_x a tile, wave 0).  The shares are XORed: over the workgroup, then into the block's accumulator.
+__global__ void __launch_bounds__(UR_THREADS) unrle_crc(UrArgs a, UwArgs wa)
+{
+    __shared__ uint32_t lds[8];
+    __shared__ uint32_t tab[256];
+    __shared__ uint32_t wred[UR_THREADS / 64];
+    const uint32_t b = a.slots[blockIdx.y], t = blockIdx.x, n = a.n[b];
+    const size_t ti = (size_t)b * a.T + t;
+    const uint32_t tile_total = a.tout[ti];
+    if (tile_total == 0) return;
+    {
+        uint32_t c = threadIdx.x << 24;
+#pragma unroll
+        for (int k = 0; k < 8; k++) c = (c << 1) ^ ((c >> 31) ? CRC_POLY : 0u);
+        tab[threadIdx.x] = c;
+    }
+    const uint32_t entry = a.tstate[ti];
+    const UrBytes u = ur_load(a.x + (size_t)b * a.S, n, t * UR_TILE + threadIdx.x * UR_ITEMS);
+    uint32_t total;
+    const uint32_t ex = ur_scan(ur_thread_map(u), lds, &total); // (its barriers also publish the table)
+    uint32_t outn;
+    uint32_t crc = bzd_ur_fold(tab, u.w, u.cnt, u.prev, bzd_rl_apply(ex, entry), &outn);
+    uint32_t summed;
+    const uint32_t o0 = block_excl_add(outn, lds, &summed);
+    if (outn) crc = gf_mul(crc, gf_pow_x_serial(wa.ct->pow2 + 3, summed - o0 - outn, 20)); // x^(8 m), m < 4096 * 255 < 2^20
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) crc ^= __shfl_xor(crc, d, 64);
+    if ((threadIdx.x & 63u) == 0) wred[threadIdx.x >> 6] = crc;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        uint32_t c = 0;
+        for (uint32_t k = 0; k < UR_THREADS / 64; k++) c ^= wred[k];
+        const uint32_t bs = wa.bsize[blockIdx.y], behind = a.toff[ti] + summed; // (the host has checked that the tiles sum to bsize)
+        const uint32_t pw = gf_pow_x(*wa.ct, 8ull * (bs > behind ? bs - behind : 0u), threadIdx.x);
+        if (threadIdx.x == 0) atomicXor(&wa.acc[blockIdx.y], gf_mul(c, pw));
+    }
+}
+
+// init and final XOR of CRC-32/BZIP2, as crc_finish (rle1.hip) folds them in
+__global__ void __launch_bounds__(64) unrle_crc_finish(UwArgs wa)
+{
+    const uint32_t pw = gf_pow_x(*wa.ct, 8ull * wa.bsize[blockIdx.x], threadIdx.x);
+    if (threadIdx.x == 0) wa.crc[blockIdx.x] = wa.acc[blockIdx.x] ^ gf_mul(0xFFFFFFFFu, pw) ^ 0xFFFFFFFFu;
+}
+
+// bad[k] = the 48 bits at candidate k are not the block magic (the scan vouches for that in a full decode, an index entry does not)
+__global__ void __launch_bounds__(64) range_magic_kernel(const uint8_t *in, uint64_t n, const uint64_t *cand, uint32_t B, uint32_t *bad)
+{
+    const uint32_t k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= B) return;
+    const uint64_t pos = cand[k] >> 1, byte = pos >> 3;
+    uint64_t v = 0;
+    for (uint32_t j = 0; j < 7; j++) v = v << 8 | (byte + j < n ? (uint64_t)in[byte + j] : 0ull);
+    bad[k] = ((v >> (8 - (pos & 7u))) & 0xFFFFFFFFFFFFull) != BZD_BLOCK_MAGIC || pos + 48 > n * 8;
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------
 struct DecWs { // carved from ctx->dec_ws (allocated on the first decode: an encode-only user pays nothing)
     uint64_t *cand;    // [B]
@@ -270,6 +403,8 @@ struct DecWs { // carved from ctx->dec_ws (allocated on the first decode: an enc
     uint64_t *obase;   // [B]
     BlockDesc *desc;   // [B]
     uint32_t *scancnt; // [1]
+    uint32_t *wslots, *wlo, *whi, *bsize, *wacc, *wcrc, *magic; // [B] random access: clipped blocks, CRCs of expansions not written
+    int64_t *wbase;    // [B]
     uint32_t B, T;
 };
 
@@ -277,7 +412,7 @@ static int dec_ws(bzh_ctx *ctx, DecWs &w)
 {
     const size_t B = ctx->max_batch, T = ctx->S / UR_TILE;
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t need = up(B * 8) + up(B * sizeof(BzdResult)) + 4 * up(B * T * 4) + 3 * up(B * 4) + up(B * 8) + up(B * sizeof(BlockDesc)) + 256;
+    const size_t need = up(B * 8) + up(B * sizeof(BzdResult)) + 4 * up(B * T * 4) + 10 * up(B * 4) + 2 * up(B * 8) + up(B * sizeof(BlockDesc)) + 256;
     if (!ctx->dec_ws || ctx->dec_ws_size < need) {
         if (ctx->dec_ws) hipFree(ctx->dec_ws);
         ctx->dec_ws = nullptr;
@@ -305,6 +440,14 @@ static int dec_ws(bzh_ctx *ctx, DecWs &w)
     take(w.obase, B * 8);
     take(w.desc, B * sizeof(BlockDesc));
     take(w.scancnt, 4);
+    take(w.wslots, B * 4);
+    take(w.wlo, B * 4);
+    take(w.whi, B * 4);
+    take(w.bsize, B * 4);
+    take(w.wacc, B * 4);
+    take(w.wcrc, B * 4);
+    take(w.magic, B * 4);
+    take(w.wbase, B * 8);
     w.B = (uint32_t)B;
     w.T = (uint32_t)T;
     return BZH_OK;
@@ -376,12 +519,64 @@ struct ChainItem { // what the chain walk met in a batch, in order
     uint32_t crc;    // stored CRC
     size_t stream, block;
     uint64_t bitpos;
+    uint64_t end_bit; // first bit behind it
+    uint32_t level;   // of its stream
+};
+struct StageClock { // HIP events around the stages of a decode call, summed into bzh_decode_stats when profiling is on
+    bzh_ctx *ctx;
+    std::vector<StageSpan> spans;
+    hipEvent_t mark()
+    {
+        if (!ctx->profiling) return nullptr;
+        hipEvent_t e = bzh_event(ctx);
+        hipEventRecord(e, ctx->stream);
+        return e;
+    }
+    void span(int stage, hipEvent_t a)
+    {
+        if (a) spans.push_back({stage, a, mark()});
+    }
+    void collect()
+    {
+        bzh_decode_stats &ds = ctx->dstats;
+        double *dst[5] = {&ds.ms_scan, &ds.ms_entropy, &ds.ms_unbwt, &ds.ms_unrle, &ds.ms_crc};
+        for (auto &s : spans) {
+            float t = 0;
+            if (hipEventElapsedTime(&t, s.a, s.b) == hipSuccess) *dst[s.stage] += t;
+        }
+        spans.clear();
+    }
 };
 } // namespace
 
+// CRCs of the expansions of K blocks of the batch (slots hslots, hsizes decoded bytes each) from the bytes behind the inverse
+// BWT: a.tstate / a.tout are unrle_walk<false>'s, a.toff the host's sums (uploaded).  Queued; the caller waits, then reads hcrc.
+static int unrle_crc_run(bzh_ctx *ctx, const DecWs &w, UrArgs a, uint32_t Tn, uint32_t K, const uint32_t *hslots, const uint32_t *hsizes,
+                         uint32_t *hcrc)
+{
+    if (K == 0) return BZH_OK;
+    hipStream_t st = ctx->stream;
+    UwArgs wa{};
+    BZH_TRY(crc_tables(ctx, &wa.ct));
+    wa.bsize = w.bsize;
+    wa.acc = w.wacc;
+    wa.crc = w.wcrc;
+    a.slots = w.wslots;
+    HIP_TRY(ctx, hipMemcpyAsync(w.wslots, hslots, (size_t)K * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(w.bsize, hsizes, (size_t)K * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(w.wacc, 0, (size_t)K * 4, st));
+    unrle_crc<<<dim3(Tn, K), UR_THREADS, 0, st>>>(a, wa);
+    unrle_crc_finish<<<dim3(K), 64, 0, st>>>(wa);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(hcrc, w.wcrc, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+    return BZH_OK;
+}
+
 // The chain walk and the back of the decoder.  cands: decode_scan_run's list.  The arena holds min(cands, max_batch) blocks.
+// index: the call builds a block index (bzh_decode_index*) -- cap is 0, nothing is expanded, every block's CRC comes from
+// unrle_crc and is checked like a full decode's, and the entries are appended in chain order.
 int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t cap, size_t *out_len, size_t *consumed,
-                     const std::vector<uint64_t> &cands)
+                     const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index)
 {
     hipStream_t st = ctx->stream;
     Batch &bt = ctx->bt;
@@ -392,24 +587,9 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
         bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
         return BZH_E_STATE;
     }
-    std::vector<StageSpan> spans;
-    auto mark = [&]() -> hipEvent_t {
-        if (!ctx->profiling) return nullptr;
-        hipEvent_t e = bzh_event(ctx);
-        hipEventRecord(e, st);
-        return e;
-    };
-    auto span = [&](int stage, hipEvent_t a) {
-        if (a) spans.push_back({stage, a, mark()});
-    };
-    auto collect = [&]() {
-        double *dst[5] = {&ds.ms_scan, &ds.ms_entropy, &ds.ms_unbwt, &ds.ms_unrle, &ds.ms_crc};
-        for (auto &s : spans) {
-            float t = 0;
-            if (hipEventElapsedTime(&t, s.a, s.b) == hipSuccess) *dst[s.stage] += t;
-        }
-        spans.clear();
-    };
+    StageClock clock{ctx, {}};
+    auto mark = [&]() { return clock.mark(); };
+    auto span = [&](int stage, hipEvent_t a) { clock.span(stage, a); };
     size_t stream = 0, block = 0;
     auto data_error = [&](uint32_t kind, uint64_t bitpos, const char *what = nullptr) {
         bzh_set_error(ctx, "decode: %s%s%s in stream %zu, block %zu, at bit %llu", kind_name(kind), what ? ": " : "", what ? what : "", stream,
@@ -437,7 +617,7 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
     bool finished = false, over = false;
     std::vector<BzdResult> res;
     std::vector<ChainItem> items;
-    std::vector<uint32_t> slots, hout, hoff, hend;
+    std::vector<uint32_t> slots, hout, hoff, hend, hsize32, hcrc;
     std::vector<uint64_t> hbase, hsize;
     std::vector<BlockDesc> hdesc;
     while (!finished) {
@@ -470,14 +650,14 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
             if (r.kind != BZD_OK) return data_error(r.kind, r.errpos);
             if (!(cands[ci + k] & 1ull)) {
                 if (r.nblock > 100000u * level) return data_error(BZD_K_FORMAT, cpos, "more bytes than the stream's block size");
-                items.push_back({false, k, r.crc, stream, block, cpos});
+                items.push_back({false, k, r.crc, stream, block, cpos, r.end_bit, level});
                 slots.push_back(k);
                 block++;
                 ds.blocks++;
                 pos = r.end_bit;
                 continue;
             }
-            items.push_back({true, k, r.crc, stream, block, cpos});
+            items.push_back({true, k, r.crc, stream, block, cpos, r.end_bit, level});
             ds.streams++;
             if (consumed) *consumed = (size_t)(r.end_bit / 8);
             if (r.follow & 0x100u) { // the next stream: its errors are errors
@@ -565,6 +745,15 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
                 HIP_TRY(ctx, hipMemcpyAsync(hdesc.data(), w.desc, (size_t)K * sizeof(BlockDesc), hipMemcpyDeviceToHost, st));
                 span(4, e3);
                 HIP_TRY(ctx, bzh_stream_wait(st));
+            } else if (index) { // the CRCs of the expansions, with nothing expanded
+                HIP_TRY(ctx, hipMemcpyAsync(w.toff, hoff.data(), hoff.size() * 4, hipMemcpyHostToDevice, st));
+                span(3, e2);
+                hipEvent_t e3 = mark();
+                hsize32.assign(hsize.begin(), hsize.end());
+                hcrc.resize(K);
+                BZH_TRY(unrle_crc_run(ctx, w, a, Tn, K, slots.data(), hsize32.data(), hcrc.data()));
+                span(4, e3);
+                HIP_TRY(ctx, bzh_stream_wait(st));
             } else {
                 span(3, e2);
             }
@@ -577,6 +766,10 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
             block = it.block;
             if (!it.footer) {
                 if (!over && hdesc[q].crc != it.crc) return data_error(BZD_K_BLOCK_CRC, it.bitpos);
+                if (index) {
+                    if (hcrc[q] != it.crc) return data_error(BZD_K_BLOCK_CRC, it.bitpos);
+                    index->push_back({it.bitpos, it.end_bit, hbase[q], (uint32_t)hsize[q], it.crc, (uint32_t)it.stream, it.level});
+                }
                 stream_crc = ((stream_crc << 1) | (stream_crc >> 31)) ^ it.crc;
                 q++;
             } else {
@@ -588,13 +781,273 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
         block = block_at;
         if (finished) break;
     }
-    collect();
+    clock.collect();
     ds.candidates_off_chain += nc - ci; // (magics in foreign bytes behind the last stream)
     ds.out_bytes = total_out;
     *out_len = (size_t)total_out;
-    if (over) {
+    if (over && !index) {
         bzh_set_error(ctx, "decode: the output needs %llu bytes, the buffer holds %zu", (unsigned long long)total_out, cap);
         return BZH_E_CAP;
     }
+    return BZH_OK;
+}
+
+// ================================================================================================================
+// Random access: bzh_index_span, and the decode of the blocks a range touches (bzh_decode_range*)
+// ================================================================================================================
+// The entries [*first, *last) that [off, off + len) touches, *clipped = min(len, total - off), and the bytes of the indexed input
+// that hold them.  Offsets ascend, so both ends are binary searches.
+static void index_span(const bzh_index_entry *idx, size_t count, uint64_t off, uint64_t len, size_t *first, size_t *last,
+                       uint64_t *byte_lo, uint64_t *byte_hi, uint64_t *clipped)
+{
+    const uint64_t total = count ? idx[count - 1].out_off + idx[count - 1].out_len : 0;
+    *clipped = off < total ? std::min<uint64_t>(len, total - off) : 0;
+    // the first entry that ends behind `off`
+    size_t lo = 0, hi = count;
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo) / 2;
+        if (idx[mid].out_off + idx[mid].out_len <= off)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    *first = *last = lo;
+    *byte_lo = *byte_hi = 0;
+    if (*clipped == 0) return;
+    const uint64_t end = off + *clipped; // the first entry that starts at or behind the end of the range
+    hi = count;
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo) / 2;
+        if (idx[mid].out_off < end)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    *last = lo;
+    if (*last <= *first) { // (only an index whose offsets are not the running sum from 0 gets here: no entry holds the range)
+        *last = *first;
+        return;
+    }
+    *byte_lo = idx[*first].bit_pos / 8;
+    *byte_hi = (idx[*last - 1].end_bit + 7) / 8;
+}
+
+extern "C" int bzh_index_span(const bzh_index_entry *idx, size_t count, uint64_t off, uint64_t len, size_t *first, size_t *last,
+                              uint64_t *byte_lo, uint64_t *byte_hi)
+{
+    if ((!idx && count) || !first || !last || !byte_lo || !byte_hi) return BZH_E_ARG;
+    uint64_t clipped;
+    index_span(idx, count, off, len, first, last, byte_lo, byte_hi, &clipped);
+    return BZH_OK;
+}
+
+// The index, well formed as a whole, whatever the range: BZH_E_ARG naming the first entry that is not.  Both entry points call
+// this before any arithmetic on the entries.
+int decode_index_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count)
+{
+    uint64_t sum = 0;
+    for (size_t k = 0; k < count; k++) {
+        const bzh_index_entry &e = idx[k];
+        const char *what = nullptr;
+        if (e.end_bit <= e.bit_pos)
+            what = "end_bit is not behind bit_pos";
+        else if (k && e.bit_pos <= idx[k - 1].bit_pos)
+            what = "bit_pos does not ascend";
+        else if (e.out_off != sum)
+            what = "out_off is not the running sum of the sizes before it";
+        else if (e.level < 1 || e.level > 9)
+            what = "a level outside 1..9";
+        else if ((int)e.level > ctx->level)
+            what = "a level above the context's";
+        if (what) {
+            bzh_set_error(ctx, "decode range: index entry %zu: %s", k, what);
+            return BZH_E_ARG;
+        }
+        sum += e.out_len;
+    }
+    return BZH_OK;
+}
+
+// (idx has passed decode_index_check)
+int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                     uint64_t off, uint64_t len, uint8_t *d_out, size_t cap, size_t *out_len)
+{
+    hipStream_t st = ctx->stream;
+    Batch &bt = ctx->bt;
+    bzh_decode_stats &ds = ctx->dstats;
+    *out_len = 0;
+    size_t first, last;
+    uint64_t byte_lo, byte_hi, clipped;
+    index_span(idx, count, off, len, &first, &last, &byte_lo, &byte_hi, &clipped);
+    if (clipped == 0) return BZH_OK;
+    if (clipped > cap) {
+        bzh_set_error(ctx, "decode range: the range holds %llu bytes, the buffer %zu", (unsigned long long)clipped, cap);
+        return BZH_E_ARG;
+    }
+    if (in_byte_base > byte_lo || byte_hi - in_byte_base > n) {
+        bzh_set_error(ctx, "decode range: index entries %zu..%zu lie in bytes [%llu, %llu) of the indexed input, the buffer holds [%llu, %llu)",
+                      first, last - 1, (unsigned long long)byte_lo, (unsigned long long)byte_hi, (unsigned long long)in_byte_base,
+                      (unsigned long long)(in_byte_base + n));
+        return BZH_E_ARG;
+    }
+    DecWs w;
+    BZH_TRY(dec_ws(ctx, w));
+    if (w.T > UR_THREADS) {
+        bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
+        return BZH_E_STATE;
+    }
+    StageClock clock{ctx, {}};
+    size_t at = 0; // the entry an error is about
+    auto mismatch = [&](const char *what) {
+        bzh_set_error(ctx, "decode range: index entry %zu (stream %u, bit %llu) does not match its block: %s", at, idx[at].stream,
+                      (unsigned long long)idx[at].bit_pos, what);
+        return BZH_E_DATA;
+    };
+    const uint32_t Bmax = (uint32_t)std::min<size_t>(ctx->max_batch, ctx->arena_blocks);
+    const uint64_t end = off + clipped;
+    std::vector<uint64_t> hcand, fbase;
+    std::vector<BzdResult> res;
+    std::vector<uint32_t> hmagic, all, hout, hend, hoff, fslots, eslots, elo, ehi, esize, ecrc;
+    std::vector<int64_t> ebase;
+    std::vector<BlockDesc> fdesc;
+    std::vector<size_t> fentry, eentry;
+    for (size_t e0 = first; e0 < last;) {
+        const uint32_t B = (uint32_t)std::min<size_t>(Bmax, last - e0);
+        // entropy stage: the entries are the candidates
+        hcand.resize(B);
+        for (uint32_t k = 0; k < B; k++) hcand[k] = (idx[e0 + k].bit_pos - 8 * in_byte_base) << 1;
+        hipEvent_t t1 = clock.mark();
+        HIP_TRY(ctx, hipMemcpyAsync(w.cand, hcand.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
+        decode_block_kernel<<<dim3(B), 64, 0, st>>>(d_in, n, w.cand, bt, w.res, 100000u * (uint32_t)ctx->level);
+        range_magic_kernel<<<dim3((B + 63) / 64), 64, 0, st>>>(d_in, n, w.cand, B, w.magic);
+        HIP_TRY(ctx, hipGetLastError());
+        clock.span(1, t1);
+        res.resize(B);
+        hmagic.resize(B);
+        HIP_TRY(ctx, hipMemcpyAsync(res.data(), w.res, (size_t)B * sizeof(BzdResult), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(hmagic.data(), w.magic, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, bzh_stream_wait(st));
+        uint32_t nmax = 1;
+        for (uint32_t k = 0; k < B; k++) {
+            at = e0 + k;
+            const bzh_index_entry &e = idx[at];
+            const BzdResult &r = res[k];
+            if (hmagic[k]) return mismatch("no block magic at bit_pos");
+            if (r.kind != BZD_OK) return mismatch(kind_name(r.kind));
+            if (r.end_bit + 8 * in_byte_base != e.end_bit) return mismatch("it ends at another bit than end_bit");
+            if (r.crc != e.crc) return mismatch("its stored CRC differs");
+            if (r.nblock > 100000u * e.level) return mismatch("more bytes than the level's block size");
+            nmax = std::max(nmax, r.nblock);
+        }
+        ds.blocks += B;
+        hipEvent_t t2 = clock.mark();
+        BZH_TRY(unbwt_run(ctx, B, nmax));
+        clock.span(2, t2);
+        // sizes: as the chain takes them
+        hipEvent_t t3 = clock.mark();
+        UrArgs a{};
+        a.x = bt.mtfpos;
+        a.n = bt.n;
+        a.slots = w.slots;
+        a.S = bt.S;
+        a.T = w.T;
+        a.tmap = w.tmap;
+        a.tout = w.tout;
+        a.tstate = w.tstate;
+        a.endstate = w.endstate;
+        a.toff = w.toff;
+        a.obase = w.obase;
+        a.out = d_out;
+        const uint32_t Tn = (nmax + UR_TILE - 1) / UR_TILE;
+        all.resize(B);
+        for (uint32_t k = 0; k < B; k++) all[k] = k;
+        HIP_TRY(ctx, hipMemcpyAsync(w.slots, all.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+        unrle_maps<<<dim3(Tn, B), UR_THREADS, 0, st>>>(a);
+        unrle_walk<false><<<dim3(Tn, B), UR_THREADS, 0, st>>>(a);
+        HIP_TRY(ctx, hipGetLastError());
+        hout.resize((size_t)B * w.T);
+        hend.resize(B);
+        HIP_TRY(ctx, hipMemcpyAsync(hout.data(), w.tout, hout.size() * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(hend.data(), w.endstate, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, bzh_stream_wait(st));
+        hoff.assign((size_t)B * w.T, 0);
+        fslots.clear(), fbase.clear(), fdesc.clear(), fentry.clear();
+        eslots.clear(), elo.clear(), ehi.clear(), esize.clear(), ebase.clear(), eentry.clear();
+        uint64_t maxsize = 0;
+        for (uint32_t k = 0; k < B; k++) {
+            at = e0 + k;
+            const bzh_index_entry &e = idx[at];
+            const uint32_t tn = (res[k].nblock + UR_TILE - 1) / UR_TILE;
+            uint64_t sz = 0;
+            for (uint32_t t = 0; t < tn; t++) {
+                hoff[(size_t)k * w.T + t] = (uint32_t)sz;
+                sz += hout[(size_t)k * w.T + t];
+            }
+            if (hend[k] == 4) return mismatch("the block ends in four equal bytes without a count");
+            if (sz != e.out_len) return mismatch("it decodes to another size than out_len");
+            // the window of the range inside this block; a block wholly inside is expanded where it belongs and checked there
+            const uint64_t lo = std::max(off, e.out_off) - e.out_off, hi = std::min(end, e.out_off + e.out_len) - e.out_off;
+            if (lo == 0 && hi == e.out_len) {
+                fslots.push_back(k);
+                fbase.push_back(e.out_off - off);
+                fdesc.push_back(BlockDesc{e.out_off - off, e.out_len, 0, 0});
+                fentry.push_back(at);
+                maxsize = std::max<uint64_t>(maxsize, e.out_len);
+            } else {
+                eslots.push_back(k);
+                elo.push_back((uint32_t)lo);
+                ehi.push_back((uint32_t)hi);
+                esize.push_back(e.out_len);
+                ebase.push_back((int64_t)e.out_off - (int64_t)off);
+                eentry.push_back(at);
+            }
+        }
+        const uint32_t KF = (uint32_t)fslots.size(), KE = (uint32_t)eslots.size();
+        HIP_TRY(ctx, hipMemcpyAsync(w.toff, hoff.data(), hoff.size() * 4, hipMemcpyHostToDevice, st));
+        UwArgs wa{};
+        if (KF) {
+            HIP_TRY(ctx, hipMemcpyAsync(w.slots, fslots.data(), (size_t)KF * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(w.obase, fbase.data(), (size_t)KF * 8, hipMemcpyHostToDevice, st));
+            unrle_walk<true><<<dim3(Tn, KF), UR_THREADS, 0, st>>>(a);
+        }
+        if (KE) { // the blocks the range cuts: clipped, and (below) checked without their expansion
+            wa.wlo = w.wlo;
+            wa.whi = w.whi;
+            wa.wbase = w.wbase;
+            UrArgs ae = a;
+            ae.slots = w.wslots;
+            HIP_TRY(ctx, hipMemcpyAsync(w.wslots, eslots.data(), (size_t)KE * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(w.wlo, elo.data(), (size_t)KE * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(w.whi, ehi.data(), (size_t)KE * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(w.wbase, ebase.data(), (size_t)KE * 8, hipMemcpyHostToDevice, st));
+            unrle_walk_win<<<dim3(Tn, KE), UR_THREADS, 0, st>>>(ae, wa);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        clock.span(3, t3);
+        hipEvent_t t4 = clock.mark();
+        if (KF) {
+            HIP_TRY(ctx, hipMemcpyAsync(w.desc, fdesc.data(), (size_t)KF * sizeof(BlockDesc), hipMemcpyHostToDevice, st));
+            BZH_TRY(crc_blocks_device(ctx, d_out, w.desc, w.crcacc, KF, maxsize));
+            HIP_TRY(ctx, hipMemcpyAsync(fdesc.data(), w.desc, (size_t)KF * sizeof(BlockDesc), hipMemcpyDeviceToHost, st));
+        }
+        ecrc.resize(KE);
+        BZH_TRY(unrle_crc_run(ctx, w, a, Tn, KE, eslots.data(), esize.data(), ecrc.data()));
+        clock.span(4, t4);
+        HIP_TRY(ctx, bzh_stream_wait(st));
+        for (uint32_t q = 0; q < KF; q++)
+            if (fdesc[q].crc != idx[fentry[q]].crc) {
+                at = fentry[q];
+                return mismatch(kind_name(BZD_K_BLOCK_CRC));
+            }
+        for (uint32_t q = 0; q < KE; q++)
+            if (ecrc[q] != idx[eentry[q]].crc) {
+                at = eentry[q];
+                return mismatch(kind_name(BZD_K_BLOCK_CRC));
+            }
+        e0 += B;
+    }
+    clock.collect();
+    ds.out_bytes = clipped;
+    *out_len = (size_t)clipped;
     return BZH_OK;
 }

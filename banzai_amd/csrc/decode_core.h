@@ -1,5 +1,6 @@
 // decode_core.h -- the serial front of the bzip2 decoder: bit reader, block header parser, canonical decode tables, the
-// symbol loop with the inverse MTF / RLE2, the footer, and the state model of the inverse RLE1.
+// symbol loop with the inverse MTF / RLE2, the footer, the state model of the inverse RLE1, and what one thread of the inverse
+// RLE1 does with its 16 bytes: count, fold into a CRC, expand clipped to a window.
 //
 // One source, two builds.  decode.hip compiles it for gfx950, where ONE WAVEFRONT decodes one block: every lane runs the
 // same serial code on the same values (so the bit window and the counters can live on the scalar side), and the lanes
@@ -357,3 +358,66 @@ BZD_FN uint32_t bzd_rl_compose(uint32_t first, uint32_t then)
     return r;
 }
 BZD_FN uint32_t bzd_rl_step(uint32_t s, bool eq) { return s == 4 ? 0u : (eq && s >= 1 ? s + 1 : 1u); }
+
+// ---- one thread's stretch of a block behind the inverse BWT: cnt <= 16 bytes, byte k in bits 8*(k&3) of w[k>>2]; `prev` the
+// byte before them (256: none), `s` the state they are entered in.  In state 4 a byte is a count: it stands for that many
+// copies of the byte before it (0..255); any other byte stands for itself.
+constexpr uint32_t BZD_UR_ITEMS = 16;
+BZD_FN uint32_t bzd_ur_at(const uint32_t *w, uint32_t k) { return (w[k >> 2] >> (8 * (k & 3))) & 255u; }
+
+// The CRC register (CRC-32/BZIP2 without its init and final XOR: the polynomial of the bytes alone) over what the stretch
+// expands to, *outn = how many bytes that is.  tab[v] = v * x^32 mod P.  Nothing is written: at most 16 * 255 table steps.
+BZD_FN uint32_t bzd_ur_fold(const uint32_t *tab, const uint32_t *w, uint32_t cnt, uint32_t prev, uint32_t s, uint32_t *outn)
+{
+    uint32_t crc = 0, o = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t k = 0; k < BZD_UR_ITEMS; k++) {
+        if (k < cnt) {
+            const uint32_t c = bzd_ur_at(w, k);
+            if (s == 4) {
+                for (uint32_t q = 0; q < c; q++) crc = (crc << 8) ^ tab[(crc >> 24) ^ prev];
+                o += c;
+            } else {
+                crc = (crc << 8) ^ tab[(crc >> 24) ^ c];
+                o++;
+            }
+            s = bzd_rl_step(s, c == prev);
+            prev = c;
+        }
+    }
+    *outn = o;
+    return crc;
+}
+
+// [*a, *b) = the part of [o, o + len) inside the window [lo, hi); empty (*a == *b) when they do not meet
+BZD_FN void bzd_clip(uint32_t o, uint32_t len, uint32_t lo, uint32_t hi, uint32_t *a, uint32_t *b)
+{
+    const uint32_t e = o + len;
+    *a = o > lo ? o : lo;
+    *b = e < hi ? e : hi;
+    if (*b < *a) *b = *a;
+}
+
+// The expansion of the stretch, which begins at output position o: put(position, byte) for every position inside [lo, hi) and
+// for no other.  A run that lies outside the window costs nothing.
+template <class Put>
+BZD_FN void bzd_ur_emit(const uint32_t *w, uint32_t cnt, uint32_t prev, uint32_t s, uint32_t o, uint32_t lo, uint32_t hi, Put put)
+{
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t k = 0; k < BZD_UR_ITEMS; k++) {
+        if (k < cnt) {
+            const uint32_t c = bzd_ur_at(w, k);
+            const uint32_t len = s == 4 ? c : 1u, byte = s == 4 ? prev : c;
+            uint32_t a, b;
+            bzd_clip(o, len, lo, hi, &a, &b);
+            for (uint32_t q = a; q < b; q++) put(q, (uint8_t)byte);
+            o += len;
+            s = bzd_rl_step(s, c == prev);
+            prev = c;
+        }
+    }
+}

@@ -23,6 +23,7 @@
 // by x^(8*bytes_after) with GF(2) multiplies, XOR-reduced (CRC is linear), init/xorout folded in.
 // Emit (per batch): one thread per 16 input bytes, offsets by in-tile scans, output staged in LDS.
 #include "common.h"
+#include "crc_gf.h"
 
 constexpr int RL_THREADS = 256;
 constexpr int RL_ITEMS = 16;
@@ -726,36 +727,10 @@ __global__ void __launch_bounds__(64 * SP_W) plan_split(PlanArrays pa)
 }
 
 // ---- CRC-32/BZIP2 ----------------------------------------------------------------------------------------
-constexpr uint32_t CRC_POLY = 0x04C11DB7u;
+// (CRC_POLY, CrcTables, gf_mul and gf_pow_x: crc_gf.h, shared with the decoder)
 constexpr uint32_t CRC_PIECE = 32;                         // bytes per thread
 constexpr uint32_t CRC_TILE = RL_THREADS * CRC_PIECE;      // 8192 bytes per workgroup
 constexpr uint32_t CRC_WG_TILES = 8;                       // adjacent tiles a workgroup folds (at least)
-
-struct CrcTables {
-    uint32_t pow2[40];   // x^(2^k) mod P, k = 0..39 (bit exponents)
-    uint32_t shift[256]; // x^(8*32*i) mod P: moves a 32-byte piece i pieces to the left
-};
-
-__device__ __forceinline__ uint32_t gf_mul(uint32_t a, uint32_t b) // a*b mod P, bit 31 = x^31
-{
-    uint32_t r = 0;
-#pragma unroll 8
-    for (int i = 31; i >= 0; i--) {
-        r = (r << 1) ^ ((r >> 31) ? CRC_POLY : 0u);
-        if ((b >> i) & 1u) r ^= a;
-    }
-    return r;
-}
-
-// x^e mod P for a wave-uniform exponent e (< 2^40): lanes take one bit each, product by butterfly.
-__device__ __forceinline__ uint32_t gf_pow_x(const CrcTables &ct, uint64_t e, uint32_t lane)
-{
-    uint32_t f = 1u; // polynomial 1
-    if (lane < 40 && ((e >> lane) & 1ull)) f = ct.pow2[lane];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) f = gf_mul(f, __shfl_xor(f, d, 64));
-    return f;
-}
 
 // The CRC of the block's tiles [tA, tB) (adjacent 8 KiB pieces of its input), shifted to the block's end and XORed
 // into *accb.  The tiles fold into one value (acc * x^(8 * tile bytes) + tile), so a workgroup pays one power of x and
@@ -898,7 +873,6 @@ __global__ void __launch_bounds__(64) crc_finish(BlockDesc *blocks, const uint32
 }
 
 // Device copy of the GF(2) tables, created on first use (one context = one GPU).
-static int crc_tables(bzh_ctx *ctx, const CrcTables **out);
 
 static CrcTables make_crc_tables()
 {
@@ -925,7 +899,7 @@ static CrcTables make_crc_tables()
     return ct;
 }
 
-static int crc_tables(bzh_ctx *ctx, const CrcTables **out)
+int crc_tables(bzh_ctx *ctx, const CrcTables **out)
 {
     if (!ctx->d_crctab) {
         const CrcTables ct = make_crc_tables();

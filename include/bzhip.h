@@ -182,6 +182,56 @@ typedef struct {
 } bzh_decode_stats;
 BZH_API int bzh_get_decode_stats(const bzh_ctx *ctx, bzh_decode_stats *out);
 
+/* ---- random access: a verified block index, and the decode of a byte range of the output ---------- */
+
+/* One decoded block.  bzip2 blocks are independent once the bit they start at is known: the index records that bit for every
+ * block of every stream of an input, where its bytes lie in the concatenated output, and its stored CRC. */
+typedef struct {
+    uint64_t bit_pos;  /* of the block magic, in the coordinates of the input the index was built from */
+    uint64_t end_bit;  /* first bit behind the block */
+    uint64_t out_off;  /* of its first decoded byte in the concatenated output of all streams */
+    uint32_t out_len;  /* decoded bytes */
+    uint32_t crc;      /* stored block CRC */
+    uint32_t stream;   /* 0-based stream number */
+    uint32_t level;    /* of that stream, 1..9 */
+} bzh_index_entry;     /* 40 bytes */
+
+/* Builds the index of in[0..n): same input contract as bzh_decode (several streams, foreign bytes behind them, the level gate,
+ * the error kinds).  Everything a full decode verifies is verified -- every block CRC and every stream CRC included -- without
+ * an output buffer: a block's CRC is computed from the bytes behind its inverse BWT, its expansion is never written.  Empty
+ * streams contribute no entry.  *count = entries (set also when max is too small: BZH_E_CAP, idx then unspecified), *out_total =
+ * decoded bytes of all streams, *consumed as bzh_decode reports it (may be null).  idx may be null when max is 0. */
+BZH_API int bzh_decode_index(bzh_ctx *ctx, const uint8_t *in, size_t n, bzh_index_entry *idx, size_t max, size_t *count,
+                             uint64_t *out_total, size_t *consumed);
+BZH_API int bzh_decode_index_device(bzh_ctx *ctx, const void *d_in, size_t n, bzh_index_entry *idx, size_t max, size_t *count,
+                                    uint64_t *out_total, size_t *consumed);
+
+/* Pure host arithmetic (no context, no GPU): the entries [*first, *last) that the output range [off, off + len) touches, the
+ * range clipped to the indexed total, and the bytes [*byte_lo, *byte_hi) = [bit_pos / 8, ceil(end_bit / 8)) of the indexed input
+ * that hold them.  An empty range (len 0, off at or behind the total, no entries) gives *first == *last and *byte_lo ==
+ * *byte_hi.  The entries must be ordered as bzh_decode_index writes them.  BZH_E_ARG for a null pointer. */
+BZH_API int bzh_index_span(const bzh_index_entry *idx, size_t count, uint64_t off, uint64_t len, size_t *first, size_t *last,
+                           uint64_t *byte_lo, uint64_t *byte_hi);
+
+/* Decodes output bytes [off, off + len) of the indexed input, clipped to its total: exactly min(len, total - off) bytes go to
+ * out and *out_len (off >= total: none, BZH_OK).  in[0..n) holds the compressed bytes FROM BYTE in_byte_base of the indexed
+ * input: all of it with base 0, or just the span bzh_index_span names.  Only the touched blocks are decoded -- no scan, no
+ * walk along the chain -- and no decoded byte outside the range is written anywhere: whole blocks inside the range are
+ * expanded in place, the at most two blocks at its edges are clipped to it.  The host variant uploads only the span.
+ * BZH_E_ARG, with bzh_last_error naming the entry: an index that is not well formed (bit_pos not ascending, end_bit <= bit_pos,
+ * out_off not the running sum from 0, a level outside 1..9 or above the context's), a buffer that does not cover the span, a
+ * cap below the bytes to write.  BZH_E_DATA, naming the entry and the check, when a touched block does not match its entry: no
+ * block magic at bit_pos, another end_bit, stored CRC or decoded size, more bytes than its level allows, an end in four equal
+ * bytes without a count, a computed CRC that differs from the stored one.
+ * WHAT IS VERIFIED: the CRC of every touched block, over all of its bytes.  Stream CRCs are NOT verified (they need every
+ * block of the stream: bzh_decode_index has checked them), and damage in a block the range does not touch is not seen.
+ * After any error the context stays usable.  bzh_get_decode_stats: blocks = blocks touched, candidates = 0. */
+BZH_API int bzh_decode_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                             size_t count, uint64_t off, uint64_t len, uint8_t *out, size_t cap, size_t *out_len);
+/* Same, compressed bytes and output resident in HBM (idx is a host array). */
+BZH_API int bzh_decode_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                                    size_t count, uint64_t off, uint64_t len, void *d_out, size_t cap, size_t *out_len);
+
 /* ---- streaming: encode() fed by a reader that yields arbitrary chunks (lib/rle.rs:30-92) ------- */
 
 /* Starts a stream on the context.  Then call bzh_stream_feed any number of times; the bytes it

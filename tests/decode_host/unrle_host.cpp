@@ -1,0 +1,187 @@
+// unrle_host.cpp -- what one thread of the decoder's random-access kernels does (banzai_amd/csrc/decode_core.h: bzd_ur_fold,
+// bzd_clip, bzd_ur_emit) and the CRC algebra around it (banzai_amd/csrc/crc_gf.h), as a CPU program built by
+// tests/test_index_api.py with -fsanitize=address,undefined.  The GPU kernels unrle_crc and unrle_walk_win compile the same
+// text; this file lays the threads out as they do -- tiles of 4,096 bytes, 16 a thread, entry states by composing state maps,
+// offsets by prefix sums -- and runs them one after the other.
+//
+//   unrle_host <cases> <results>   cases: [u32 n][n bytes]... (a block behind the inverse BWT each)
+//                                  results: [u32 crc][u32 end state][u32 len][len bytes]... (CRC from the fold, never from the bytes)
+// Every case is also expanded through windows -- all of them for an expansion of at most 48 bytes, 300 seeded ones and the
+// bytes around every tile seam otherwise -- each into a heap buffer of exactly the window's size, and compared with the same
+// bytes of the full expansion: a byte outside the window is a sanitizer report, a wrong one exit status 1.
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../../banzai_amd/csrc/crc_gf.h"
+#include "../../banzai_amd/csrc/decode_core.h"
+
+constexpr uint32_t ITEMS = BZD_UR_ITEMS, THREADS = 256, TILE = ITEMS * THREADS;
+
+struct Thread {
+    uint32_t w[4], cnt, prev, state, outn, off; // off: of its first output byte inside its tile
+};
+struct Tile {
+    uint32_t toff, total;
+    std::vector<Thread> th;
+};
+
+static uint32_t g_tab[256], g_pow2[40];
+
+static void tables()
+{
+    for (uint32_t i = 0; i < 256; i++) {
+        uint32_t c = i << 24;
+        for (int k = 0; k < 8; k++) c = (c << 1) ^ ((c >> 31) ? CRC_POLY : 0u);
+        g_tab[i] = c;
+    }
+    uint32_t p = 2u;
+    for (int k = 0; k < 40; k++) {
+        g_pow2[k] = p;
+        p = gf_mul(p, p);
+    }
+}
+
+// the layout the kernels work from: per thread its bytes, entry state, size and offset; per tile its offset in the block
+static uint32_t lay_out(const uint8_t *x, uint32_t n, std::vector<Tile> &tiles, uint32_t *bsize)
+{
+    tiles.clear();
+    uint32_t pre = BZD_RL_ID, sum = 0;
+    for (uint32_t t0 = 0; t0 < n; t0 += TILE) {
+        Tile tl;
+        tl.toff = sum;
+        tl.total = 0;
+        for (uint32_t i0 = t0; i0 < n && i0 < t0 + TILE; i0 += ITEMS) {
+            Thread th;
+            memset(th.w, 0, sizeof th.w);
+            th.cnt = n - i0 < ITEMS ? n - i0 : ITEMS;
+            th.prev = i0 ? x[i0 - 1] : 256u;
+            for (uint32_t k = 0; k < th.cnt; k++) th.w[k >> 2] |= (uint32_t)x[i0 + k] << (8 * (k & 3));
+            th.state = bzd_rl_apply(pre, 0);
+            uint32_t st[5] = {0, 1, 2, 3, 4}, prev = th.prev;
+            for (uint32_t k = 0; k < th.cnt; k++) {
+                const uint32_t c = bzd_ur_at(th.w, k);
+                for (int s = 0; s < 5; s++) st[s] = bzd_rl_step(st[s], c == prev);
+                prev = c;
+            }
+            pre = bzd_rl_compose(pre, st[0] | st[1] << 3 | st[2] << 6 | st[3] << 9 | st[4] << 12);
+            (void)bzd_ur_fold(g_tab, th.w, th.cnt, th.prev, th.state, &th.outn);
+            th.off = tl.total;
+            tl.total += th.outn;
+            tl.th.push_back(th);
+        }
+        sum += tl.total;
+        tiles.push_back(tl);
+    }
+    *bsize = sum;
+    return bzd_rl_apply(pre, 0);
+}
+
+// unrle_crc + unrle_crc_finish
+static uint32_t crc_of_expansion(const std::vector<Tile> &tiles, uint32_t bsize)
+{
+    uint32_t acc = 0;
+    for (const Tile &tl : tiles) {
+        uint32_t c = 0;
+        for (const Thread &th : tl.th) {
+            uint32_t outn;
+            uint32_t crc = bzd_ur_fold(g_tab, th.w, th.cnt, th.prev, th.state, &outn);
+            if (outn) crc = gf_mul(crc, gf_pow_x_serial(g_pow2 + 3, tl.total - th.off - outn, 20));
+            c ^= crc;
+        }
+        acc ^= gf_mul(c, gf_pow_x_serial(g_pow2, 8ull * (bsize - tl.toff - tl.total), 40));
+    }
+    return acc ^ gf_mul(0xFFFFFFFFu, gf_pow_x_serial(g_pow2, 8ull * bsize, 40)) ^ 0xFFFFFFFFu;
+}
+
+// unrle_walk_win: the window [lo, hi) of the block into a buffer that holds exactly those bytes
+static void expand_window(const std::vector<Tile> &tiles, uint32_t lo, uint32_t hi, std::vector<uint8_t> &out, uint32_t *tiles_walked)
+{
+    uint8_t *buf = (uint8_t *)malloc(hi - lo ? hi - lo : 1); // (exact size: ASan guards both ends)
+    memset(buf, 0xEE, hi - lo ? hi - lo : 1);
+    *tiles_walked = 0;
+    for (const Tile &tl : tiles) {
+        if (tl.total == 0) continue;
+        uint32_t ca, cb;
+        bzd_clip(tl.toff, tl.total, lo, hi, &ca, &cb);
+        if (ca == cb) continue; // the tile lies outside the window
+        ++*tiles_walked;
+        const uint32_t tlo = ca - tl.toff, thi = cb - tl.toff;
+        // g + q = where byte q of the tile belongs; it may point before the buffer, only window positions are touched
+        const intptr_t g = (intptr_t)buf + ((intptr_t)tl.toff - (intptr_t)lo);
+        for (const Thread &th : tl.th)
+            bzd_ur_emit(th.w, th.cnt, th.prev, th.state, th.off, tlo, thi, [&](uint32_t q, uint8_t v) { *(uint8_t *)(g + (intptr_t)q) = v; });
+    }
+    out.assign(buf, buf + (hi - lo));
+    free(buf);
+}
+
+int main(int argc, char **argv)
+{
+    if (argc != 3) {
+        fprintf(stderr, "usage: unrle_host <cases> <results>\n");
+        return 2;
+    }
+    tables();
+    FILE *fi = fopen(argv[1], "rb"), *fo = fopen(argv[2], "wb");
+    if (!fi || !fo) return 2;
+    uint64_t rs = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&]() {
+        rs ^= rs << 13;
+        rs ^= rs >> 7;
+        rs ^= rs << 17;
+        return rs;
+    };
+    std::vector<Tile> tiles;
+    std::vector<uint8_t> full, part;
+    for (long c = 0;; c++) {
+        uint32_t n;
+        if (fread(&n, 4, 1, fi) != 1) break;
+        uint8_t *x = (uint8_t *)malloc(n ? n : 1);
+        if (n && fread(x, 1, n, fi) != n) return 2;
+        uint32_t bsize, walked;
+        const uint32_t end = lay_out(x, n, tiles, &bsize);
+        free(x);
+        const uint32_t crc = crc_of_expansion(tiles, bsize);
+        expand_window(tiles, 0, bsize, full, &walked);
+        fwrite(&crc, 4, 1, fo);
+        fwrite(&end, 4, 1, fo);
+        fwrite(&bsize, 4, 1, fo);
+        if (bsize) fwrite(full.data(), 1, bsize, fo);
+        auto window = [&](uint32_t lo, uint32_t hi) {
+            expand_window(tiles, lo, hi, part, &walked);
+            if (part.size() != hi - lo || (hi > lo && memcmp(part.data(), full.data() + lo, hi - lo) != 0)) {
+                fprintf(stderr, "unrle_host: case %ld, window [%u, %u) of %u bytes differs from the full expansion\n", c, lo, hi, bsize);
+                exit(1);
+            }
+            uint32_t meet = 0; // tiles the window meets: no other may have been walked
+            for (const Tile &tl : tiles) meet += tl.total && tl.toff < hi && tl.toff + tl.total > lo && hi > lo;
+            if (walked != meet) {
+                fprintf(stderr, "unrle_host: case %ld, window [%u, %u): %u tiles walked, %u meet it\n", c, lo, hi, walked, meet);
+                exit(1);
+            }
+        };
+        if (bsize <= 48) {
+            for (uint32_t lo = 0; lo <= bsize; lo++)
+                for (uint32_t hi = lo; hi <= bsize; hi++) window(lo, hi);
+        } else {
+            for (int k = 0; k < 300; k++) {
+                const uint32_t lo = (uint32_t)(rnd() % (bsize + 1)), len = (uint32_t)(rnd() % (k % 3 ? 70 : 20000));
+                window(lo, lo + len < bsize ? lo + len : bsize);
+            }
+            for (const Tile &tl : tiles) // around every tile seam, and from a seam to the block's end
+                for (uint32_t d = 0; d < 5; d++) {
+                    const uint32_t lo = tl.toff > 2 ? tl.toff - 2 + d : d;
+                    if (lo > bsize) continue;
+                    for (uint32_t len = 0; len < 6; len++) window(lo, lo + len < bsize ? lo + len : bsize);
+                    window(lo, bsize);
+                    window(0, lo);
+                }
+        }
+    }
+    fclose(fi);
+    return fclose(fo) ? 2 : 0;
+}
