@@ -16,6 +16,8 @@ and random access into a .bz2 without decoding all of it (bzip2 blocks are indep
     build_index(data) -> BlockIndex                      (every block: where it starts, what it decodes to; verified)
     decompress_range(data, index, offset, length) -> bytes
     IndexedReader(source, index=None)                    (read / seek over the decoded bytes of bytes or a file)
+    build_sync_index(data, interval=256) -> SyncIndex    (a BlockIndex plus sync points inside the blocks: a read decodes
+                                                          its blocks in parallel segments; accepted wherever a BlockIndex is)
 
 Everything is computed by hand-written HIP kernels behind the C ABI in include/bzhip.h
 (libbzhip.so); there is no CPU path.  `reader` is any object with .read(), `writer` any object
@@ -23,13 +25,14 @@ with .write() (the Rust signature takes BufRead / BufWriter<W>).
 """
 import io
 import struct
+import zlib
 
 import numpy as np
 
 from . import _native
 
 __all__ = ["encode", "encode_many", "encode_file", "decompress", "decode", "build_index", "decompress_range", "BlockIndex",
-           "IndexedReader", "Context", "MultiContext", "BzhError"]
+           "IndexedReader", "build_sync_index", "SyncIndex", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
 MultiContext = _native.MultiContext
@@ -295,10 +298,132 @@ def build_index(data, device=0):
     return BlockIndex(entries, consumed)
 
 
+class SyncIndex:
+    """A BlockIndex (`.blocks`) with sync points inside the blocks (bzh_decode_index_sync): `.points` is a numpy structured array
+    of the 288-byte bzh_sync_point layout (bit_pos, entry, group, out_pos, run, run_weight, reserved, mtf), one in front of every
+    group whose number is a multiple of `.interval`.  With it a read decodes each block it touches in parallel segments.  The
+    points are checked against the bytes by every read that uses them (bzh_decode_range_sync), so a blob from a file needs no
+    trust; to_bytes() / from_bytes() refuse what is not a whole, well-formed blob."""
+
+    MAGIC = b"BZhSYN\r\n"
+    VERSION = 1
+    _HEAD = struct.Struct("<8sIIQQII")  # magic, version, interval, bytes of the block index, points, CRC-32 of all the rest, 0
+
+    def __init__(self, blocks, points, interval):
+        if not isinstance(blocks, BlockIndex):
+            raise TypeError(f"blocks must be a BlockIndex, not {type(blocks).__name__}")
+        self.blocks = blocks
+        self.points = np.ascontiguousarray(points, dtype=_native.SYNC_DTYPE)
+        self.interval = int(interval)
+        if not 1 <= self.interval <= 32767:
+            raise ValueError(f"sync index: an interval of {self.interval} groups, outside 1..32767")
+        what = self._ill_formed(self.blocks.entries, self.points)
+        if what:
+            raise ValueError(f"sync index: {what}")
+
+    @staticmethod
+    def _ill_formed(e, p):
+        """what bzh_decode_range_sync refuses the points for (None: well formed)"""
+        if p.size == 0:
+            return None
+        if np.any(p["reserved"] != 0):
+            return "reserved is not 0"
+        if np.any((p["group"] == 0) | (p["group"] > 32766)):
+            return "group outside 1..32766"
+        if np.any(p["entry"] >= e.size):
+            return "entry outside the index"
+        same = p["entry"][1:] == p["entry"][:-1]
+        if np.any(p["entry"][1:] < p["entry"][:-1]) or np.any(same & (p["group"][1:] <= p["group"][:-1])):
+            return "(entry, group) does not ascend"
+        own = e[p["entry"]]
+        if np.any((p["bit_pos"] <= own["bit_pos"]) | (p["bit_pos"] >= own["end_bit"])):
+            return "bit_pos is not inside its entry"
+        if np.any(same & (p["bit_pos"][1:] <= p["bit_pos"][:-1])):
+            return "bit_pos does not ascend"
+        if np.any(same & (p["out_pos"][1:] < p["out_pos"][:-1])):
+            return "out_pos descends"
+        if np.any(p["out_pos"].astype(np.uint64) > 100000 * own["level"].astype(np.uint64)):
+            return "out_pos beyond the level's block size"
+        rw, run1 = p["run_weight"].astype(np.uint64), p["run"].astype(np.uint64) + 1
+        if np.any((rw == 0) | ((rw & (rw - np.uint64(1))) != 0) | (rw > (1 << 22))):
+            return "run_weight is no power of two up to 2^22"
+        if np.any((run1 < rw) | (run1 > 2 * rw - 1)):
+            return "run and run_weight do not belong together"
+        return None
+
+    # what a BlockIndex answers, so that a SyncIndex stands wherever one does
+    @property
+    def entries(self):
+        return self.blocks.entries
+
+    @property
+    def size(self):
+        return self.blocks.size
+
+    @property
+    def consumed(self):
+        return self.blocks.consumed
+
+    def __len__(self):
+        return len(self.blocks)
+
+    def span(self, off, length):
+        return self.blocks.span(off, length)
+
+    @classmethod
+    def _crc(cls, head_fields, body):
+        """CRC-32 of the header (its CRC field 0) and everything behind it: no flipped bit passes"""
+        return zlib.crc32(body, zlib.crc32(cls._HEAD.pack(*head_fields, 0, 0)))
+
+    def to_bytes(self):
+        inner = self.blocks.to_bytes()
+        fields = (self.MAGIC, self.VERSION, self.interval, len(inner), int(self.points.size))
+        body = inner + self.points.tobytes()
+        return self._HEAD.pack(*fields, self._crc(fields, body), 0) + body
+
+    @classmethod
+    def from_bytes(cls, blob):
+        view = _bytes_view(blob, "SyncIndex.from_bytes")
+        if len(view) < cls._HEAD.size:
+            raise ValueError("sync index: truncated header")
+        magic, version, interval, inner, count, crc, zero = cls._HEAD.unpack_from(view, 0)
+        if magic != cls.MAGIC:
+            raise ValueError("sync index: bad magic")
+        if version != cls.VERSION:
+            raise ValueError(f"sync index: version {version}, this library reads version {cls.VERSION}")
+        item = _native.SYNC_DTYPE.itemsize
+        if inner > len(view) or count > len(view) // item or len(view) != cls._HEAD.size + inner + count * item:
+            raise ValueError(f"sync index: {len(view)} bytes do not hold a header, a block index of {inner} bytes and {count} points")
+        if zero != 0 or crc != cls._crc((magic, version, interval, inner, count), view[cls._HEAD.size:]):
+            raise ValueError("sync index: the blob is damaged (its CRC differs)")
+        blocks = BlockIndex.from_bytes(view[cls._HEAD.size:cls._HEAD.size + inner])
+        points = np.frombuffer(view, dtype=_native.SYNC_DTYPE, count=count, offset=cls._HEAD.size + inner).copy()
+        return cls(blocks, points, interval)
+
+
+def build_sync_index(data, interval=256, device=0):
+    """build_index that also records the sync points (bzh_decode_index_sync): one every `interval` groups of 50 symbols inside
+    every block, 288 bytes each -- about 55 a level-9 block of text at the default.  Verified like build_index."""
+    view = _bytes_view(data, "build_sync_index")
+    if isinstance(interval, bool) or not isinstance(interval, int):
+        raise TypeError(f"interval must be an int, not {type(interval).__name__}")
+    if not 1 <= interval <= 32767:
+        raise ValueError(f"interval must be 1..32767 groups, not {interval}")
+    entries, points, _, consumed = _ctx(9, device).decode_index_sync(view, interval)
+    return SyncIndex(BlockIndex(entries, consumed), points, interval)
+
+
 def _index_arg(index):
-    if not isinstance(index, BlockIndex):
-        raise TypeError(f"index must be a BlockIndex, not {type(index).__name__}")
+    if not isinstance(index, (BlockIndex, SyncIndex)):
+        raise TypeError(f"index must be a BlockIndex or a SyncIndex, not {type(index).__name__}")
     return index
+
+
+def _decode_range(ctx, comp, index, offset, length, lo):
+    """bzh_decode_range, or bzh_decode_range_sync when the index has sync points to offer"""
+    if isinstance(index, SyncIndex):
+        return ctx.decode_range_sync(comp, index.entries, index.points, offset, length, in_byte_base=lo)
+    return ctx.decode_range(comp, index.entries, offset, length, in_byte_base=lo)
 
 
 def decompress_range(data, index, offset, length, device=0):
@@ -309,7 +434,7 @@ def decompress_range(data, index, offset, length, device=0):
     index = _index_arg(index)
     offset, length = _int_arg(offset, "offset"), _int_arg(length, "length")
     _, _, lo, hi = index.span(offset, length)
-    return _ctx(9, device).decode_range(view[lo:hi], index.entries, offset, length, in_byte_base=lo)
+    return _decode_range(_ctx(9, device), view[lo:hi], index, offset, length, lo)
 
 
 class IndexedReader(io.RawIOBase):
@@ -383,7 +508,7 @@ class IndexedReader(io.RawIOBase):
                 raise EOFError(f"the source holds {len(comp)} of the {hi - lo} bytes from {lo} on that the index names")
         else:
             comp = self._view[lo:hi]
-        out = _ctx(9, self._device).decode_range(comp, self.index.entries, self._pos, n, in_byte_base=lo)
+        out = _decode_range(_ctx(9, self._device), comp, self.index, self._pos, n, lo)
         self._pos += len(out)
         return out
 

@@ -65,6 +65,18 @@ assert INDEX_DTYPE.itemsize == ctypes.sizeof(IndexEntry) == 40
 idxp = ctypes.POINTER(IndexEntry)
 
 
+class SyncPoint(ctypes.Structure):
+    """bzh_sync_point: the entropy stage's state at a group boundary inside a block"""
+    _fields_ = [("bit_pos", ctypes.c_uint64), ("entry", ctypes.c_uint32), ("group", ctypes.c_uint32), ("out_pos", ctypes.c_uint32),
+                ("run", ctypes.c_uint32), ("run_weight", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("mtf", ctypes.c_uint8 * 256)]
+
+
+SYNC_DTYPE = np.dtype([("bit_pos", "<u8"), ("entry", "<u4"), ("group", "<u4"), ("out_pos", "<u4"), ("run", "<u4"),
+                       ("run_weight", "<u4"), ("reserved", "<u4"), ("mtf", "u1", (256,))])
+assert SYNC_DTYPE.itemsize == ctypes.sizeof(SyncPoint) == 288
+syncp = ctypes.POINTER(SyncPoint)
+
+
 class KStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("ms", ctypes.c_double), ("launches", ctypes.c_uint64),
                 ("alg_bytes", ctypes.c_uint64)]
@@ -100,6 +112,15 @@ SIGNATURES = {
     "bzh_decode_index": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, idxp, ctypes.c_size_t, szp, u64p, szp]),
     "bzh_decode_index_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, idxp, ctypes.c_size_t, szp,
                                                u64p, szp]),
+    "bzh_decode_index_sync": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint32, idxp, ctypes.c_size_t, szp, syncp,
+                                             ctypes.c_size_t, szp, u64p, szp]),
+    "bzh_decode_index_sync_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, idxp,
+                                                    ctypes.c_size_t, szp, syncp, ctypes.c_size_t, szp, u64p, szp]),
+    "bzh_decode_range_sync": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64, idxp, ctypes.c_size_t, syncp,
+                                             ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, u8p, ctypes.c_size_t, szp]),
+    "bzh_decode_range_sync_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, idxp,
+                                                    ctypes.c_size_t, syncp, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
+                                                    ctypes.c_void_p, ctypes.c_size_t, szp]),
     "bzh_index_span": (ctypes.c_int, [idxp, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, szp, szp, u64p, u64p]),
     "bzh_decode_range": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64, idxp, ctypes.c_size_t,
                                         ctypes.c_uint64, ctypes.c_uint64, u8p, ctypes.c_size_t, szp]),
@@ -172,6 +193,12 @@ def _entries(entries):
     """a contiguous array of the 40-byte entries (no copy when it already is one) and its ctypes pointer"""
     e = np.ascontiguousarray(entries, dtype=INDEX_DTYPE)
     return e, (e.ctypes.data_as(idxp) if e.size else None)
+
+
+def _points(points):
+    """a contiguous array of the 288-byte sync points and its ctypes pointer"""
+    p = np.ascontiguousarray(points, dtype=SYNC_DTYPE)
+    return p, (p.ctypes.data_as(syncp) if p.size else None)
 
 
 def index_span(entries, off, length):
@@ -481,6 +508,52 @@ class Context:
         got = ctypes.c_size_t(0)
         self.check(lib().bzh_decode_range_device(self._h, ctypes.c_void_p(d_in), n, in_byte_base, p, e.size, off, length,
                                                  ctypes.c_void_p(d_out), cap, ctypes.byref(got)))
+        return int(got.value)
+
+    def decode_index_sync(self, data, interval):
+        """bzh_decode_index_sync: decode_index that also records a sync point every `interval` groups of every block ->
+        (entries, points as a structured array of SYNC_DTYPE, decoded bytes in total, input bytes consumed).  One call sizes
+        the two arrays, a second fills them."""
+        a = np.frombuffer(data, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        cnt, npts, used, total = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint64(0)
+        st = lib().bzh_decode_index_sync(self._h, ptr(src), n, interval, None, 0, ctypes.byref(cnt), None, 0, ctypes.byref(npts),
+                                         ctypes.byref(total), ctypes.byref(used))
+        if st != -4:
+            self.check(st)
+        ent = np.empty(cnt.value, dtype=INDEX_DTYPE)
+        pts = np.empty(npts.value, dtype=SYNC_DTYPE)
+        if st == -4:
+            self.check(lib().bzh_decode_index_sync(self._h, ptr(src), n, interval, ent.ctypes.data_as(idxp) if ent.size else None, ent.size,
+                                                   ctypes.byref(cnt), pts.ctypes.data_as(syncp) if pts.size else None, pts.size,
+                                                   ctypes.byref(npts), ctypes.byref(total), ctypes.byref(used)))
+        return ent[:cnt.value], pts[:npts.value], int(total.value), int(used.value)
+
+    def decode_range_sync(self, data, entries, points, off, length, in_byte_base=0):
+        """bzh_decode_range_sync: decode_range with the blocks' entropy stage split at the sync points"""
+        if off < 0 or length < 0:
+            raise ValueError("offset and length must not be negative")
+        a = np.frombuffer(data, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        e, p = _entries(entries)
+        q, pp = _points(points)
+        total = int(e["out_off"][-1]) + int(e["out_len"][-1]) if e.size else 0
+        cap = max(0, min(length, total - off))
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        got = ctypes.c_size_t(0)
+        self.check(lib().bzh_decode_range_sync(self._h, ptr(src), n, in_byte_base, p, e.size, pp, q.size, off, length, ptr(out), cap,
+                                               ctypes.byref(got)))
+        return out[:got.value].tobytes()
+
+    def decode_range_sync_device(self, d_in, n, entries, points, off, length, d_out, cap, in_byte_base=0):
+        """bzh_decode_range_sync_device on integer device addresses -> bytes written at d_out"""
+        e, p = _entries(entries)
+        q, pp = _points(points)
+        got = ctypes.c_size_t(0)
+        self.check(lib().bzh_decode_range_sync_device(self._h, ctypes.c_void_p(d_in), n, in_byte_base, p, e.size, pp, q.size, off, length,
+                                                      ctypes.c_void_p(d_out), cap, ctypes.byref(got)))
         return int(got.value)
 
     def decode_stats(self):

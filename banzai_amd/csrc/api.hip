@@ -344,6 +344,7 @@ extern "C" void bzh_destroy(bzh_ctx *ctx)
     if (ctx->d_crctab) hipFree(ctx->d_crctab);
     if (ctx->dec_ws) hipFree(ctx->dec_ws);
     if (ctx->dec_list) hipFree(ctx->dec_list);
+    if (ctx->sync_ws) hipFree(ctx->sync_ws);
     for (int k = 0; k < 2; k++)
         if (ctx->strm.d_buf[k]) hipFree(ctx->strm.d_buf[k]);
     if (ctx->strm.h_out) hipHostFree(ctx->strm.h_out);
@@ -1461,12 +1462,13 @@ extern "C" int bzh_decode(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *ou
 }
 
 // ---- random access (decode.hip): the index is bzh_decode_device's flow with no output, a range needs neither scan nor chain
-extern "C" int bzh_decode_index_device(bzh_ctx *ctx, const void *d_in, size_t n, bzh_index_entry *idx, size_t max, size_t *count,
-                                       uint64_t *out_total, size_t *consumed)
+// interval 0: no sync points (bzh_decode_index_device); else bzh_decode_index_sync_device
+static int decode_index_device_impl(bzh_ctx *ctx, const void *d_in, size_t n, uint32_t interval, bzh_index_entry *idx, size_t max, size_t *count,
+                                    bzh_sync_point *pts, size_t max_pts, size_t *npts, uint64_t *out_total, size_t *consumed)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
-    if (!ctx || (!d_in && n) || (!idx && max) || !count || !out_total) return BZH_E_ARG;
+    if (!ctx || (!d_in && n) || (!idx && max) || !count || !out_total || (!pts && max_pts) || (interval && !npts)) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     ctx->evnext = 0;
@@ -1476,6 +1478,7 @@ extern "C" int bzh_decode_index_device(bzh_ctx *ctx, const void *d_in, size_t n,
     ctx->dstats.in_bytes = n;
     *count = 0;
     *out_total = 0;
+    if (npts) *npts = 0;
     if (consumed) *consumed = 0;
     hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
     if (ctx->profiling) {
@@ -1492,7 +1495,8 @@ extern "C" int bzh_decode_index_device(bzh_ctx *ctx, const void *d_in, size_t n,
     BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(cands.size(), 1), ctx->max_batch)));
     std::vector<bzh_index_entry> entries;
     size_t total = 0;
-    const int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, &entries);
+    SyncBuild sync{interval, {}};
+    const int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, &entries, interval ? &sync : nullptr);
     if (ctx->profiling) {
         t2 = bzh_event(ctx);
         hipEventRecord(t2, st);
@@ -1503,12 +1507,54 @@ extern "C" int bzh_decode_index_device(bzh_ctx *ctx, const void *d_in, size_t n,
     if (rc != BZH_OK) return rc;
     *count = entries.size();
     *out_total = total;
+    if (npts) *npts = sync.pts.size();
     if (entries.size() > max) {
         bzh_set_error(ctx, "decode index: %zu entries, room for %zu", entries.size(), max);
         return BZH_E_CAP;
     }
+    if (sync.pts.size() > max_pts) {
+        bzh_set_error(ctx, "decode index: %zu sync points, room for %zu", sync.pts.size(), max_pts);
+        return BZH_E_CAP;
+    }
     if (!entries.empty()) memcpy(idx, entries.data(), entries.size() * sizeof(bzh_index_entry));
+    if (!sync.pts.empty()) memcpy(pts, sync.pts.data(), sync.pts.size() * sizeof(bzh_sync_point));
     return BZH_OK;
+    });
+}
+
+extern "C" int bzh_decode_index_device(bzh_ctx *ctx, const void *d_in, size_t n, bzh_index_entry *idx, size_t max, size_t *count,
+                                       uint64_t *out_total, size_t *consumed)
+{
+    return decode_index_device_impl(ctx, d_in, n, 0, idx, max, count, nullptr, 0, nullptr, out_total, consumed);
+}
+
+static bool sync_interval_ok(bzh_ctx *ctx, uint32_t interval)
+{
+    if (interval >= 1 && interval <= 32767) return true;
+    if (ctx) bzh_set_error(ctx, "decode index: a sync interval of %u groups, outside 1..32767", interval);
+    return false;
+}
+
+extern "C" int bzh_decode_index_sync_device(bzh_ctx *ctx, const void *d_in, size_t n, uint32_t interval, bzh_index_entry *idx, size_t max,
+                                            size_t *count, bzh_sync_point *pts, size_t max_pts, size_t *npts, uint64_t *out_total,
+                                            size_t *consumed)
+{
+    if (!ctx || !npts) return BZH_E_ARG;
+    if (!sync_interval_ok(ctx, interval)) return BZH_E_ARG;
+    return decode_index_device_impl(ctx, d_in, n, interval, idx, max, count, pts, max_pts, npts, out_total, consumed);
+}
+
+extern "C" int bzh_decode_index_sync(bzh_ctx *ctx, const uint8_t *in, size_t n, uint32_t interval, bzh_index_entry *idx, size_t max,
+                                     size_t *count, bzh_sync_point *pts, size_t max_pts, size_t *npts, uint64_t *out_total, size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n) || (!idx && max) || !count || !out_total || (!pts && max_pts) || !npts) return BZH_E_ARG;
+    if (!sync_interval_ok(ctx, interval)) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, n + 16));
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, ctx->stream));
+    return decode_index_device_impl(ctx, ctx->d_stage_in, n, interval, idx, max, count, pts, max_pts, npts, out_total, consumed);
     });
 }
 
@@ -1525,12 +1571,14 @@ extern "C" int bzh_decode_index(bzh_ctx *ctx, const uint8_t *in, size_t n, bzh_i
     });
 }
 
-extern "C" int bzh_decode_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
-                                       size_t count, uint64_t off, uint64_t len, void *d_out, size_t cap, size_t *out_len)
+// npts 0: bzh_decode_range_device; else bzh_decode_range_sync_device
+static int decode_range_device_impl(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                                    const bzh_sync_point *pts, size_t npts, uint64_t off, uint64_t len, void *d_out, size_t cap,
+                                    size_t *out_len)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
-    if (!ctx || (!d_in && n) || (!d_out && cap) || (!idx && count) || !out_len) return BZH_E_ARG;
+    if (!ctx || (!d_in && n) || (!d_out && cap) || (!idx && count) || (!pts && npts) || !out_len) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     ctx->evnext = 0;
@@ -1545,11 +1593,13 @@ extern "C" int bzh_decode_range_device(bzh_ctx *ctx, const void *d_in, size_t n,
         hipEventRecord(t0, st);
     }
     BZH_TRY(decode_index_check(ctx, idx, count)); // (before any arithmetic on the entries)
+    BZH_TRY(decode_sync_check(ctx, idx, count, pts, npts));
     size_t first = 0, last = 0;
     uint64_t lo, hi;
     BZH_TRY(bzh_index_span(idx, count, off, len, &first, &last, &lo, &hi));
     BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(last - first, 1), ctx->max_batch)));
-    const int rc = decode_range_run(ctx, (const uint8_t *)d_in, n, in_byte_base, idx, count, off, len, (uint8_t *)d_out, cap, out_len);
+    const int rc = decode_range_run(ctx, (const uint8_t *)d_in, n, in_byte_base, idx, count, off, len, (uint8_t *)d_out, cap, out_len, pts,
+                                     npts);
     if (ctx->profiling) {
         t2 = bzh_event(ctx);
         hipEventRecord(t2, st);
@@ -1560,16 +1610,30 @@ extern "C" int bzh_decode_range_device(bzh_ctx *ctx, const void *d_in, size_t n,
     });
 }
 
-extern "C" int bzh_decode_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
-                                uint64_t off, uint64_t len, uint8_t *out, size_t cap, size_t *out_len)
+extern "C" int bzh_decode_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                                       size_t count, uint64_t off, uint64_t len, void *d_out, size_t cap, size_t *out_len)
+{
+    return decode_range_device_impl(ctx, d_in, n, in_byte_base, idx, count, nullptr, 0, off, len, d_out, cap, out_len);
+}
+
+extern "C" int bzh_decode_range_sync_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                                            size_t count, const bzh_sync_point *pts, size_t npts, uint64_t off, uint64_t len, void *d_out,
+                                            size_t cap, size_t *out_len)
+{
+    return decode_range_device_impl(ctx, d_in, n, in_byte_base, idx, count, pts, npts, off, len, d_out, cap, out_len);
+}
+
+static int decode_range_impl(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                             const bzh_sync_point *pts, size_t npts, uint64_t off, uint64_t len, uint8_t *out, size_t cap, size_t *out_len)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
-    if (!ctx || (!in && n) || (!out && cap) || (!idx && count) || !out_len) return BZH_E_ARG;
+    if (!ctx || (!in && n) || (!out && cap) || (!idx && count) || (!pts && npts) || !out_len) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     *out_len = 0;
     BZH_TRY(decode_index_check(ctx, idx, count)); // (before any arithmetic on the entries)
+    BZH_TRY(decode_sync_check(ctx, idx, count, pts, npts));
     // only the span goes up (a buffer that does not cover it goes up whole: the device call says what is missing)
     size_t first = 0, last = 0;
     uint64_t lo = 0, hi = 0;
@@ -1588,14 +1652,27 @@ extern "C" int bzh_decode_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint6
     if (want) BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, (size_t)want));
     if (un) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, src, un, hipMemcpyHostToDevice, st));
     size_t got = 0;
-    const int rc = bzh_decode_range_device(ctx, ctx->d_stage_in, un, base, idx, count, off, len, want ? ctx->d_stage_out : nullptr,
-                                           (size_t)want, &got);
+    const int rc = decode_range_device_impl(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, off, len,
+                                            want ? ctx->d_stage_out : nullptr, (size_t)want, &got);
     if (rc != BZH_OK) return rc;
     if (got) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, got, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, bzh_stream_wait(st));
     *out_len = got;
     return BZH_OK;
     });
+}
+
+extern "C" int bzh_decode_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                                uint64_t off, uint64_t len, uint8_t *out, size_t cap, size_t *out_len)
+{
+    return decode_range_impl(ctx, in, n, in_byte_base, idx, count, nullptr, 0, off, len, out, cap, out_len);
+}
+
+extern "C" int bzh_decode_range_sync(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                                     size_t count, const bzh_sync_point *pts, size_t npts, uint64_t off, uint64_t len, uint8_t *out,
+                                     size_t cap, size_t *out_len)
+{
+    return decode_range_impl(ctx, in, n, in_byte_base, idx, count, pts, npts, off, len, out, cap, out_len);
 }
 
 extern "C" int bzh_get_decode_stats(const bzh_ctx *ctx, bzh_decode_stats *out)

@@ -296,6 +296,8 @@ struct bzh_ctx {
     size_t dec_ws_size = 0;
     uint64_t *dec_list = nullptr; // the scan's hit list
     size_t dec_list_cap = 0;
+    uint8_t *sync_ws = nullptr;   // sync points (allocated on first use): the recorder's slots, or a range's headers, points and segments
+    size_t sync_ws_size = 0;
     bzh_decode_stats dstats{};
     // streaming encode (bzh_stream_*)
     struct Stream {
@@ -603,11 +605,18 @@ int crc_tables(bzh_ctx *ctx, const CrcTables **out);                  // rle1.hi
 // decode.hip: every block / footer magic of d_in[0..n) as (bit position << 1 | kind), ascending; then the chain walk and the
 // back of the decoder over that list (the arena laid out for min(candidates, max_batch) blocks)
 int decode_scan_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, std::vector<uint64_t> &cands);
+struct SyncBuild { // bzh_decode_index_sync*: the chain walk records a point every `interval` groups of every block on the chain
+    uint32_t interval;
+    std::vector<bzh_sync_point> pts;
+};
 int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t cap, size_t *out_len, size_t *consumed,
-                     const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index = nullptr);
+                     const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index = nullptr, SyncBuild *sync = nullptr);
 // decode.hip: the blocks of a verified index that [off, off + len) touches, from d_in = the indexed input from byte in_byte_base on
 int decode_index_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count); // BZH_E_ARG naming the entry that is ill formed
+int decode_sync_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts, size_t npts); // same, the point
+// (pts: sync points that have passed decode_sync_check; none: one wavefront a block)
 int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
-                     uint64_t off, uint64_t len, uint8_t *d_out, size_t cap, size_t *out_len);
+                     uint64_t off, uint64_t len, uint8_t *d_out, size_t cap, size_t *out_len, const bzh_sync_point *pts = nullptr,
+                     size_t npts = 0);
 
 hipEvent_t bzh_event(bzh_ctx *ctx);

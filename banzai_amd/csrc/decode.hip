@@ -10,6 +10,9 @@
 // Random access (bzh_decode_index*, bzh_decode_range*): the index is the chain walk with no output, every block's CRC taken
 // from the bytes behind the inverse BWT (unrle_crc); a range decodes the blocks its index entries name, no scan and no walk,
 // and clips the blocks at its two edges to the range (unrle_walk_win).
+// Sync points (bzh_decode_index_sync*, bzh_decode_range_sync*): the index build also writes the entropy stage's state down every
+// `interval` groups (decode_block_sync_kernel); a range then parses each touched block's header once (decode_header_kernel) and
+// decodes every segment, from point to point, in a wavefront of its own (decode_segment_kernel).
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -89,6 +92,201 @@ __global__ void __launch_bounds__(64) decode_block_kernel(const uint8_t *in, uin
         bt.ptr[b] = ok ? r.origptr : 0u;
         if (!ok) L[0] = 0;
     }
+}
+
+// ---- sync points: recording --------------------------------------------------------------------------------------------
+// The recorder of the index build: the points of a candidate go to its slot's region, `cap` of them at most.
+struct SyncRecorder {
+    static constexpr bool ON = true;
+    uint32_t interval;
+    bzh_sync_point *pts;
+    uint32_t cap, count;
+    __host__ __device__ __forceinline__ void point(uint64_t pos, uint32_t gi, uint32_t nblock, uint32_t run, uint32_t run_weight, const uint8_t *mtf)
+    {
+        if (count >= cap) return;
+        bzh_sync_point *p = pts + count;
+        if (BZD_LANE == 0) {
+            p->bit_pos = pos;
+            p->entry = 0; // (the host numbers the entries: the chain decides which candidates are blocks)
+            p->group = gi;
+            p->out_pos = nblock;
+            p->run = run;
+            p->run_weight = run_weight;
+            p->reserved = 0;
+        }
+        for (uint32_t i = BZD_LANE; i < 256; i += BZD_LANES) p->mtf[i] = mtf[i];
+        count++;
+    }
+};
+
+// decode_block_kernel with the recorder: one wavefront per candidate, the same bounds.  cnt[b] = points of slot b.
+__global__ void __launch_bounds__(64) decode_block_sync_kernel(const uint8_t *in, uint64_t n, const uint64_t *cand, Batch bt, BzdResult *res,
+                                                                uint32_t block_max, uint32_t interval, bzh_sync_point *pts, uint32_t cap,
+                                                                uint32_t *cnt)
+{
+    __shared__ BzdWork w;
+    const uint32_t b = blockIdx.x;
+    const uint64_t c0 = cand[b];
+    const uint64_t c = (uint64_t)BZD_UNI((uint32_t)c0) | (uint64_t)BZD_UNI((uint32_t)(c0 >> 32)) << 32;
+    uint8_t *L = bt.bwt + (size_t)b * bt.S;
+    BzdResult r;
+    SyncRecorder rec{interval, pts + (size_t)b * cap, cap, 0};
+    if (c & 1ull)
+        bzd_parse_footer(in, n, c >> 1, r);
+    else
+        bzd_decode_block_rec(w, in, n, c >> 1, block_max, L, r, rec);
+    if (threadIdx.x == 0) {
+        const bool ok = !(c & 1ull) && r.kind == BZD_OK;
+        res[b] = r;
+        bt.n[b] = ok ? r.nblock : 1u;
+        bt.ptr[b] = ok ? r.origptr : 0u;
+        cnt[b] = ok ? rec.count : 0u;
+        if (!ok) L[0] = 0;
+    }
+}
+
+// ---- sync points: the segmented entropy stage ------------------------------------------------------------------------------
+// What decode_header_kernel leaves of a block for its segments (global memory).
+struct BzdHead {
+    uint16_t lut[6][1u << BZD_LUT_BITS];
+    int32_t limit[6][BZD_MAX_LEN + 2], base[6][BZD_MAX_LEN + 2];
+    uint16_t perm[6][258];
+    uint32_t minlen[6], maxlen[6];
+    uint32_t nin, nsel, ngroups, origptr;
+    uint64_t first_bit; // of the first code
+    uint8_t mtf[256];   // the initial MTF list
+    uint8_t sel[BZD_MAX_SEL + 1];
+};
+
+// The tables a segment keeps in LDS: 16,744 bytes a wavefront (BzdWork: 51 KB).  The selectors stay in global memory -- one
+// wave-uniform byte load per 50 symbols -- and the code lengths are not needed behind the header.
+struct BzdSegWork {
+    uint16_t lut[6][1u << BZD_LUT_BITS];
+    int32_t limit[6][BZD_MAX_LEN + 2], base[6][BZD_MAX_LEN + 2];
+    uint16_t perm[6][258];
+    uint32_t minlen[6], maxlen[6];
+    uint8_t mtf[256];
+};
+static_assert(sizeof(BzdSegWork) <= 17 * 1024, "the segment kernel's LDS budget");
+
+template <class D, class S>
+__device__ __forceinline__ void seg_copy_tables(D &d, const S &s, uint32_t ngroups, uint32_t alpha)
+{
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t t = 0; t < ngroups; t++) {
+        const uint32_t *ls = reinterpret_cast<const uint32_t *>(s.lut[t]);
+        uint32_t *ld = reinterpret_cast<uint32_t *>(d.lut[t]);
+        for (uint32_t i = lane; i < (1u << BZD_LUT_BITS) / 2; i += 64) ld[i] = ls[i];
+        for (uint32_t i = lane; i < BZD_MAX_LEN + 2; i += 64) {
+            d.limit[t][i] = s.limit[t][i];
+            d.base[t][i] = s.base[t][i];
+        }
+        for (uint32_t i = lane; i < alpha; i += 64) d.perm[t][i] = s.perm[t][i];
+    }
+    if (lane < ngroups) {
+        d.minlen[lane] = s.minlen[lane];
+        d.maxlen[lane] = s.maxlen[lane];
+    }
+}
+
+// One wavefront per touched block: the header, parsed once.  res[b]: kind / errpos / crc / origptr (end_bit and nblock come from
+// the block's last segment).
+__global__ void __launch_bounds__(64) decode_header_kernel(const uint8_t *in, uint64_t n, const uint64_t *cand, BzdHead *heads, BzdResult *res)
+{
+    __shared__ BzdWork w;
+    const uint32_t b = blockIdx.x, lane = threadIdx.x;
+    const uint64_t c0 = cand[b];
+    const uint64_t c = (uint64_t)BZD_UNI((uint32_t)c0) | (uint64_t)BZD_UNI((uint32_t)(c0 >> 32)) << 32;
+    BzdResult r;
+    r.kind = BZD_OK;
+    r.crc = 0;
+    r.errpos = 0;
+    r.end_bit = 0;
+    r.nblock = 0;
+    r.origptr = 0;
+    r.follow = 0;
+    r.pad = 0;
+    BzdBits rd;
+    bzd_seek(rd, in, n, (c >> 1) + 48);
+    BzdHdr h;
+    if (bzd_parse_header(w, rd, r, h)) {
+        BzdHead &H = heads[b];
+        seg_copy_tables(H, w, h.ngroups, h.nin + 2);
+        for (uint32_t i = lane; i < 256; i += 64) H.mtf[i] = w.mtf[i];
+        for (uint32_t i = lane; i < h.nsel; i += 64) H.sel[i] = w.sel[i];
+        if (lane == 0) {
+            H.nin = h.nin;
+            H.nsel = h.nsel;
+            H.ngroups = h.ngroups;
+            H.origptr = r.origptr;
+            H.first_bit = rd.pos;
+        }
+    }
+    if (lane == 0) res[b] = r;
+}
+
+struct SegDesc {
+    uint32_t slot;      // of its block in the batch
+    int32_t from, to;   // points of the batch it runs between; -1: the header's state / the end of the block
+    uint32_t block_max; // bytes a block of its entry's level may hold
+};
+
+__device__ __forceinline__ BzdSyncState seg_state(const bzh_sync_point *p, uint64_t bit_base)
+{
+    BzdSyncState s;
+    const uint64_t pos = p->bit_pos - bit_base; // (the host has checked: inside its entry, which lies inside the buffer)
+    s.bit_pos = (uint64_t)BZD_UNI((uint32_t)pos) | (uint64_t)BZD_UNI((uint32_t)(pos >> 32)) << 32;
+    s.group = BZD_UNI(p->group);
+    s.out_pos = BZD_UNI(p->out_pos);
+    s.run = BZD_UNI(p->run);
+    s.run_weight = BZD_UNI(p->run_weight);
+    s.mtf = p->mtf;
+    return s;
+}
+
+// One wavefront per segment of every touched block of the batch.  It writes bytes [from.out_pos, to.out_pos) of its block's last
+// column and nothing else of it; the block's last segment also leaves the block's size and origPtr for the inverse transform.
+__global__ void __launch_bounds__(64) decode_segment_kernel(const uint8_t *in, uint64_t n, uint64_t bit_base, const BzdHead *heads,
+                                                             const bzh_sync_point *pts, const SegDesc *segs, Batch bt, BzdResult *res,
+                                                             BzdSegResult *sres)
+{
+    __shared__ BzdSegWork w;
+    const uint32_t g = blockIdx.x;
+    const uint32_t slot = BZD_UNI(segs[g].slot), block_max = BZD_UNI(segs[g].block_max);
+    const int32_t from_i = (int32_t)BZD_UNI(segs[g].from), to_i = (int32_t)BZD_UNI(segs[g].to);
+    BzdSegResult sr;
+    sr.kind = BZD_UNI(res[slot].kind);
+    sr.miss = BZD_SEG_OK;
+    sr.errpos = 0;
+    sr.end_bit = 0;
+    sr.nblock = 0;
+    sr.pad = 0;
+    if (sr.kind == BZD_OK) { // (a header that did not parse left no tables: the host reports it for the block)
+        const BzdHead &H = heads[slot];
+        const uint32_t nin = BZD_UNI(H.nin), nsel = BZD_UNI(H.nsel), ngroups = BZD_UNI(H.ngroups), origptr = BZD_UNI(H.origptr);
+        seg_copy_tables(w, H, ngroups, nin + 2);
+        BzdSyncState from, to = {};
+        if (from_i >= 0) {
+            from = seg_state(pts + from_i, bit_base);
+        } else {
+            const uint64_t fb = H.first_bit;
+            from.bit_pos = (uint64_t)BZD_UNI((uint32_t)fb) | (uint64_t)BZD_UNI((uint32_t)(fb >> 32)) << 32;
+            from.group = 0;
+            from.out_pos = 0;
+            from.run = 0;
+            from.run_weight = 1;
+            from.mtf = H.mtf;
+        }
+        if (to_i >= 0) to = seg_state(pts + to_i, bit_base);
+        uint8_t *L = bt.bwt + (size_t)slot * bt.S;
+        // (from.out_pos <= block_max <= S is checked inside before anything is stored)
+        bzd_decode_segment(w, H.sel, in, n, nin, nsel, origptr, from, to_i >= 0, to, block_max, L + from.out_pos, sr);
+        if (threadIdx.x == 0 && to_i < 0 && sr.kind == BZD_OK && sr.miss == BZD_SEG_OK) {
+            bt.n[slot] = sr.nblock;
+            bt.ptr[slot] = origptr;
+        }
+    }
+    if (threadIdx.x == 0) sres[g] = sr;
 }
 
 // ---- inverse RLE1 ----------------------------------------------------------------------------------------------
@@ -453,6 +651,26 @@ static int dec_ws(bzh_ctx *ctx, DecWs &w)
     return BZH_OK;
 }
 
+// ctx->sync_ws of at least `need` bytes (allocated on first use, grown when a call needs more; the stream is idle then)
+static int sync_ws_reserve(bzh_ctx *ctx, size_t need)
+{
+    if (ctx->sync_ws && ctx->sync_ws_size >= need) return BZH_OK;
+    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+    if (ctx->sync_ws) hipFree(ctx->sync_ws);
+    ctx->sync_ws = nullptr;
+    ctx->sync_ws_size = 0;
+    need = (need + 0xFFFFF) & ~(size_t)0xFFFFF;
+    if (hipMalloc((void **)&ctx->sync_ws, need) != hipSuccess) {
+        bzh_set_error(ctx, "hipMalloc(%zu) for the sync points failed", need);
+        return BZH_E_NOMEM;
+    }
+    ctx->sync_ws_size = need;
+    return BZH_OK;
+}
+// The recorder's workspace is bounded by shrinking the batch, whatever the interval: a slot holds every point a block can have,
+// (BZD_MAX_SEL - 1) / interval of 288 bytes -- 9.4 MB at interval 1 -- and a batch has as many slots as fit in this many bytes.
+constexpr size_t SYNC_REC_BYTES = 64u << 20;
+
 // Every magic in d_in[0..n): (bit position << 1 | kind), ascending.
 int decode_scan_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, std::vector<uint64_t> &cands)
 {
@@ -576,7 +794,7 @@ static int unrle_crc_run(bzh_ctx *ctx, const DecWs &w, UrArgs a, uint32_t Tn, ui
 // index: the call builds a block index (bzh_decode_index*) -- cap is 0, nothing is expanded, every block's CRC comes from
 // unrle_crc and is checked like a full decode's, and the entries are appended in chain order.
 int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t cap, size_t *out_len, size_t *consumed,
-                     const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index)
+                     const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index, SyncBuild *sync)
 {
     hipStream_t st = ctx->stream;
     Batch &bt = ctx->bt;
@@ -609,6 +827,20 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
     if (hdr[0] != 'B' || hdr[1] != 'Z' || hdr[2] != 'h' || hdr[3] < '1' || hdr[3] > '9') return data_error(BZD_K_MAGIC, 0, "no \"BZh1\"..\"BZh9\"");
     uint32_t level = hdr[3] - '0';
     if ((int)level > ctx->level) return level_error(level);
+    // sync points: a region per batch slot, and no more slots than the workspace's bound holds
+    uint32_t sync_cap = 0, sync_slots = 0;
+    uint32_t *d_ptcnt = nullptr;
+    bzh_sync_point *d_pts = nullptr;
+    std::vector<uint32_t> hptcnt;
+    if (sync) {
+        sync_cap = std::max<uint32_t>(1u, (BZD_MAX_SEL - 1) / sync->interval);
+        const size_t slot_bytes = (size_t)sync_cap * sizeof(bzh_sync_point);
+        sync_slots = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(ctx->max_batch, ctx->arena_blocks), SYNC_REC_BYTES / slot_bytes));
+        const size_t cnt_bytes = ((size_t)sync_slots * 4 + 255) / 256 * 256;
+        BZH_TRY(sync_ws_reserve(ctx, cnt_bytes + sync_slots * slot_bytes));
+        d_ptcnt = reinterpret_cast<uint32_t *>(ctx->sync_ws);
+        d_pts = reinterpret_cast<bzh_sync_point *>(ctx->sync_ws + cnt_bytes);
+    }
     const size_t nc = cands.size();
     const uint64_t nbits = (uint64_t)n * 8;
     uint64_t pos = 32, total_out = 0;
@@ -626,14 +858,23 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
             ci++;
         }
         if (ci == nc || (cands[ci] >> 1) != pos) return data_error(pos + 48 > nbits ? BZD_K_TRUNC : BZD_K_MAGIC, pos, "neither a block nor a footer");
-        const uint32_t B = (uint32_t)std::min<size_t>(std::min<size_t>(ctx->max_batch, ctx->arena_blocks), nc - ci);
+        uint32_t B = (uint32_t)std::min<size_t>(std::min<size_t>(ctx->max_batch, ctx->arena_blocks), nc - ci);
+        if (sync) B = std::min(B, sync_slots);
         hipEvent_t e0 = mark();
         HIP_TRY(ctx, hipMemcpyAsync(w.cand, cands.data() + ci, (size_t)B * 8, hipMemcpyHostToDevice, st));
-        decode_block_kernel<<<dim3(B), 64, 0, st>>>(d_in, n, w.cand, bt, w.res, 100000u * (uint32_t)ctx->level);
+        if (sync)
+            decode_block_sync_kernel<<<dim3(B), 64, 0, st>>>(d_in, n, w.cand, bt, w.res, 100000u * (uint32_t)ctx->level, sync->interval, d_pts,
+                                                             sync_cap, d_ptcnt);
+        else
+            decode_block_kernel<<<dim3(B), 64, 0, st>>>(d_in, n, w.cand, bt, w.res, 100000u * (uint32_t)ctx->level);
         HIP_TRY(ctx, hipGetLastError());
         span(1, e0);
         res.resize(B);
         HIP_TRY(ctx, hipMemcpyAsync(res.data(), w.res, (size_t)B * sizeof(BzdResult), hipMemcpyDeviceToHost, st));
+        if (sync) {
+            hptcnt.resize(B);
+            HIP_TRY(ctx, hipMemcpyAsync(hptcnt.data(), d_ptcnt, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+        }
         HIP_TRY(ctx, bzh_stream_wait(st));
         // the chain through this batch
         items.clear();
@@ -768,6 +1009,15 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
                 if (!over && hdesc[q].crc != it.crc) return data_error(BZD_K_BLOCK_CRC, it.bitpos);
                 if (index) {
                     if (hcrc[q] != it.crc) return data_error(BZD_K_BLOCK_CRC, it.bitpos);
+                    if (sync) { // the points of the block's slot, numbered by the entry they belong to (the stream is idle here)
+                        const uint32_t c = std::min(hptcnt[it.slot], sync_cap);
+                        const size_t at = sync->pts.size();
+                        sync->pts.resize(at + c);
+                        if (c)
+                            HIP_TRY(ctx, hipMemcpy(sync->pts.data() + at, d_pts + (size_t)it.slot * sync_cap, (size_t)c * sizeof(bzh_sync_point),
+                                                   hipMemcpyDeviceToHost));
+                        for (size_t p = at; p < at + c; p++) sync->pts[p].entry = (uint32_t)index->size();
+                    }
                     index->push_back({it.bitpos, it.end_bit, hbase[q], (uint32_t)hsize[q], it.crc, (uint32_t)it.stream, it.level});
                 }
                 stream_crc = ((stream_crc << 1) | (stream_crc >> 31)) ^ it.crc;
@@ -868,9 +1118,23 @@ int decode_index_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count)
     return BZH_OK;
 }
 
+// The sync points, well formed as a whole against the index (which has passed decode_index_check), whatever the range: BZH_E_ARG
+// naming the first point that is not.  The rule itself is decode_core.h's, shared with the host model.
+int decode_sync_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts, size_t npts)
+{
+    for (size_t i = 0; i < npts; i++) {
+        const char *what = bzd_sync_point_check(idx, count, pts, i);
+        if (what) {
+            bzh_set_error(ctx, "decode range: sync point %zu: %s", i, what);
+            return BZH_E_ARG;
+        }
+    }
+    return BZH_OK;
+}
+
 // (idx has passed decode_index_check)
 int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
-                     uint64_t off, uint64_t len, uint8_t *d_out, size_t cap, size_t *out_len)
+                     uint64_t off, uint64_t len, uint8_t *d_out, size_t cap, size_t *out_len, const bzh_sync_point *pts, size_t npts)
 {
     hipStream_t st = ctx->stream;
     Batch &bt = ctx->bt;
@@ -903,8 +1167,18 @@ int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_by
                       (unsigned long long)idx[at].bit_pos, what);
         return BZH_E_DATA;
     };
+    size_t seg_point = 0; // the sync point a segment's error is about
+    auto seg_mismatch = [&](bool named, const char *what) {
+        if (!named) return mismatch(what);
+        bzh_set_error(ctx, "decode range: index entry %zu (stream %u, bit %llu) does not match its block: sync point %zu: %s", at, idx[at].stream,
+                      (unsigned long long)idx[at].bit_pos, seg_point, what);
+        return BZH_E_DATA;
+    };
     const uint32_t Bmax = (uint32_t)std::min<size_t>(ctx->max_batch, ctx->arena_blocks);
     const uint64_t end = off + clipped;
+    std::vector<SegDesc> hseg;
+    std::vector<BzdSegResult> hsres;
+    std::vector<uint32_t> seg0; // [B + 1] first segment of every block of the batch
     std::vector<uint64_t> hcand, fbase;
     std::vector<BzdResult> res;
     std::vector<uint32_t> hmagic, all, hout, hend, hoff, fslots, eslots, elo, ehi, esize, ecrc;
@@ -916,14 +1190,58 @@ int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_by
         // entropy stage: the entries are the candidates
         hcand.resize(B);
         for (uint32_t k = 0; k < B; k++) hcand[k] = (idx[e0 + k].bit_pos - 8 * in_byte_base) << 1;
+        // with sync points: the segments of the batch's blocks, between the points [p0, p1) of its entries
+        size_t p0 = 0, p1 = 0;
+        BzdHead *d_heads = nullptr;
+        bzh_sync_point *d_pts = nullptr;
+        SegDesc *d_segs = nullptr;
+        BzdSegResult *d_sres = nullptr;
+        if (npts) {
+            auto by_entry = [](const bzh_sync_point &p, size_t e) { return (size_t)p.entry < e; };
+            p0 = (size_t)(std::lower_bound(pts, pts + npts, e0, by_entry) - pts);
+            p1 = (size_t)(std::lower_bound(pts + p0, pts + npts, e0 + B, by_entry) - pts);
+            hseg.clear();
+            seg0.assign(B + 1, 0);
+            size_t q = p0;
+            for (uint32_t k = 0; k < B; k++) {
+                seg0[k] = (uint32_t)hseg.size();
+                const uint32_t bmax = 100000u * idx[e0 + k].level;
+                int32_t prev = -1;
+                for (; q < p1 && pts[q].entry == e0 + k; q++) {
+                    hseg.push_back({k, prev, (int32_t)(q - p0), bmax});
+                    prev = (int32_t)(q - p0);
+                }
+                hseg.push_back({k, prev, -1, bmax});
+            }
+            seg0[B] = (uint32_t)hseg.size();
+            auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+            const size_t b_heads = up((size_t)B * sizeof(BzdHead)), b_pts = up((p1 - p0) * sizeof(bzh_sync_point)),
+                         b_segs = up(hseg.size() * sizeof(SegDesc)), b_sres = up(hseg.size() * sizeof(BzdSegResult));
+            BZH_TRY(sync_ws_reserve(ctx, b_heads + b_pts + b_segs + b_sres)); // (the stream is idle between batches)
+            d_heads = reinterpret_cast<BzdHead *>(ctx->sync_ws);
+            d_pts = reinterpret_cast<bzh_sync_point *>(ctx->sync_ws + b_heads);
+            d_segs = reinterpret_cast<SegDesc *>(ctx->sync_ws + b_heads + b_pts);
+            d_sres = reinterpret_cast<BzdSegResult *>(ctx->sync_ws + b_heads + b_pts + b_segs);
+        }
         hipEvent_t t1 = clock.mark();
         HIP_TRY(ctx, hipMemcpyAsync(w.cand, hcand.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
-        decode_block_kernel<<<dim3(B), 64, 0, st>>>(d_in, n, w.cand, bt, w.res, 100000u * (uint32_t)ctx->level);
+        if (npts) {
+            if (p1 > p0) HIP_TRY(ctx, hipMemcpyAsync(d_pts, pts + p0, (p1 - p0) * sizeof(bzh_sync_point), hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(d_segs, hseg.data(), hseg.size() * sizeof(SegDesc), hipMemcpyHostToDevice, st));
+            decode_header_kernel<<<dim3(B), 64, 0, st>>>(d_in, n, w.cand, d_heads, w.res);
+            decode_segment_kernel<<<dim3((uint32_t)hseg.size()), 64, 0, st>>>(d_in, n, 8 * in_byte_base, d_heads, d_pts, d_segs, bt, w.res, d_sres);
+        } else {
+            decode_block_kernel<<<dim3(B), 64, 0, st>>>(d_in, n, w.cand, bt, w.res, 100000u * (uint32_t)ctx->level);
+        }
         range_magic_kernel<<<dim3((B + 63) / 64), 64, 0, st>>>(d_in, n, w.cand, B, w.magic);
         HIP_TRY(ctx, hipGetLastError());
         clock.span(1, t1);
         res.resize(B);
         hmagic.resize(B);
+        if (npts) {
+            hsres.resize(hseg.size());
+            HIP_TRY(ctx, hipMemcpyAsync(hsres.data(), d_sres, hseg.size() * sizeof(BzdSegResult), hipMemcpyDeviceToHost, st));
+        }
         HIP_TRY(ctx, hipMemcpyAsync(res.data(), w.res, (size_t)B * sizeof(BzdResult), hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipMemcpyAsync(hmagic.data(), w.magic, (size_t)B * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, bzh_stream_wait(st));
@@ -931,9 +1249,28 @@ int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_by
         for (uint32_t k = 0; k < B; k++) {
             at = e0 + k;
             const bzh_index_entry &e = idx[at];
-            const BzdResult &r = res[k];
+            BzdResult &r = res[k];
             if (hmagic[k]) return mismatch("no block magic at bit_pos");
             if (r.kind != BZD_OK) return mismatch(kind_name(r.kind));
+            if (npts) { // every segment in order: the first that fails names the point it could not start from or arrive at
+                for (uint32_t g = seg0[k]; g < seg0[k + 1]; g++) {
+                    const BzdSegResult &sr = hsres[g];
+                    const SegDesc &d = hseg[g];
+                    const bool named = d.from >= 0 || d.to >= 0;
+                    if (sr.miss == BZD_SEG_START) {
+                        seg_point = p0 + (size_t)(d.from >= 0 ? d.from : d.to);
+                        return seg_mismatch(named, "it is no state of this block");
+                    }
+                    seg_point = p0 + (size_t)(d.to >= 0 ? d.to : d.from);
+                    if (sr.kind != BZD_OK) return seg_mismatch(named, kind_name(sr.kind));
+                    if (sr.miss == BZD_SEG_EOB) return seg_mismatch(named, "the block ends in front of it");
+                    if (sr.miss == BZD_SEG_ARRIVE) return seg_mismatch(named, "the segment in front of it arrives in another state");
+                    if (d.to < 0) {
+                        r.end_bit = sr.end_bit;
+                        r.nblock = sr.nblock;
+                    }
+                }
+            }
             if (r.end_bit + 8 * in_byte_base != e.end_bit) return mismatch("it ends at another bit than end_bit");
             if (r.crc != e.crc) return mismatch("its stored CRC differs");
             if (r.nblock > 100000u * e.level) return mismatch("more bytes than the level's block size");

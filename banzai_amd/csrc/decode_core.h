@@ -9,6 +9,7 @@
 // thrown at it by the thousand (sanitizers are a CPU affair).  Every read of the input is bounded by its length `n`, every
 // index by the size of the table it goes into, every byte written by `block_max`: a damaged stream ends in a status.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -16,11 +17,13 @@
 #define BZD_LANE (threadIdx.x & 63u)
 #define BZD_SYNC() __syncthreads() // (the decode kernel is one wavefront a workgroup)
 #define BZD_UNI(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x))) // the lanes agree: keep the value on the scalar side
+#define BZD_ANY(x) (__any((int)(x)) != 0)                                // true in some lane
 #else
 #define BZD_LANES 1u
 #define BZD_LANE 0u
 #define BZD_SYNC() ((void)0)
 #define BZD_UNI(x) ((uint32_t)(x))
+#define BZD_ANY(x) (x)
 #endif
 #if defined(__HIPCC__)
 #define BZD_FN __host__ __device__ __forceinline__
@@ -122,24 +125,23 @@ BZD_FN uint32_t bzd_get(BzdBits &r, uint32_t k)
 }
 BZD_FN bool bzd_over(const BzdBits &r) { return r.pos > r.n * 8; }
 
-// ---- one block: `pos` = bit position of its magic.  Leaves the last column in L[0 .. nblock), nblock <= block_max.
-BZD_FN void bzd_decode_block(BzdWork &w, const uint8_t *in, uint64_t n, uint64_t pos, uint32_t block_max, uint8_t *L, BzdResult &res)
+// ---- the front of a block, behind its magic: stored CRC, origPtr, symbol map, selectors, code lengths, and the canonical
+// tables and look-up tables built from them.  `r` stands behind the 48 bits of the magic and is left at the first code.  True:
+// `w` holds the tables, the selectors and the initial MTF list (the bytes in use, then zeros), h what the symbol loop needs;
+// false: res.kind / res.errpos say what went wrong.  res.crc and res.origptr are set either way once they are read.
+struct BzdHdr {
+    uint32_t nin, nsel, ngroups;
+};
+
+BZD_FN bool bzd_parse_header(BzdWork &w, BzdBits &r, BzdResult &res, BzdHdr &h)
 {
     const uint32_t lane = BZD_LANE;
     const bool l0 = lane == 0;
-    BzdBits r;
-    bzd_seek(r, in, n, pos + 48);
-    res.kind = BZD_OK;
-    res.errpos = 0;
-    res.end_bit = 0;
-    res.nblock = 0;
-    res.follow = 0;
-    res.pad = 0;
 #define BZD_FAIL(k)         \
     do {                    \
         res.kind = (k);     \
         res.errpos = r.pos; \
-        return;             \
+        return false;       \
     } while (0)
     res.crc = bzd_get(r, 32);
     const uint32_t randomised = bzd_get(r, 1);
@@ -161,6 +163,7 @@ BZD_FN void bzd_decode_block(BzdWork &w, const uint8_t *in, uint64_t n, uint64_t
     }
     if (bzd_over(r)) BZD_FAIL(BZD_K_TRUNC);
     if (nin == 0) BZD_FAIL(BZD_K_FORMAT);
+    for (uint32_t i = nin + lane; i < 256; i += BZD_LANES) w.mtf[i] = 0; // (never read by the loop: a sync point holds all 256)
     const uint32_t alpha = nin + 2;
     const uint32_t ngroups = bzd_get(r, 3), nsel = bzd_get(r, 15);
     if (bzd_over(r)) BZD_FAIL(BZD_K_TRUNC);
@@ -243,13 +246,58 @@ BZD_FN void bzd_decode_block(BzdWork &w, const uint8_t *in, uint64_t n, uint64_t
         }
         BZD_SYNC();
     }
-    // symbols -> inverse RLE2 and MTF -> last column
-    const uint32_t eob = alpha - 1;
-    uint32_t nblock = 0, run = 0, run_weight = 1, gi = 0, group_left = 0, t = 0, mn = 0, mx = 0;
+#undef BZD_FAIL
+    h.nin = nin;
+    h.nsel = nsel;
+    h.ngroups = ngroups;
+    return true;
+}
+
+// ---- symbols -> inverse RLE2 and MTF -> last column.  The loop's whole state between two symbols is the bit position, the
+// selector index `gi`, the bytes written, the pending run and the MTF list: small enough to write down (a SYNC POINT) and to
+// start from again.  W holds the tables and the MTF list (BzdWork, or a smaller set without selectors and lengths); `sel` the
+// block's selectors, wherever they lie.
+struct BzdSym {
+    uint32_t gi;         // selector index of the next group
+    uint32_t nblock;     // bytes written so far, counted from L (a pending run not included)
+    uint32_t run;        // RUNA / RUNB run accumulated so far, 0 = none
+    uint32_t run_weight; // weight of the next run digit, 1 = none pending
+    uint32_t eob;        // the end-of-block symbol was met
+};
+
+struct BzdNoRec { // the recorder that records nothing
+    static constexpr bool ON = false;
+    uint32_t interval = 1;
+    BZD_FN void point(uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint8_t *) {}
+};
+
+// Runs from the state in `s` (r at its bit position, at a group boundary) to the end of the block, or, with gi_stop != 0, to
+// the boundary in front of group gi_stop.  Not more than out_max bytes are written to L.  Returns a BzdKind (r.pos is where);
+// `s` is the state it stopped in.  Where a group begins whose index is a multiple of rec.interval, the recorder is handed
+// the state first (recording builds only).
+template <class W, class Rec>
+BZD_FN uint32_t bzd_symbols(W &w, const uint8_t *sel, BzdBits &r, uint32_t nin, uint32_t nsel, uint32_t gi_stop, uint32_t out_max, uint8_t *L,
+                            BzdSym &s, Rec &rec)
+{
+    const uint32_t lane = BZD_LANE;
+    const bool l0 = lane == 0;
+    const uint32_t alpha = nin + 2, eob = alpha - 1;
+    uint32_t nblock = s.nblock, run = s.run, run_weight = s.run_weight, gi = s.gi, group_left = 0, t = 0, mn = 0, mx = 0;
+#define BZD_FAIL(k)                  \
+    do {                             \
+        s.gi = gi;                   \
+        s.nblock = nblock;           \
+        s.run = run;                 \
+        s.run_weight = run_weight;   \
+        return (k);                  \
+    } while (0)
+    s.eob = 0;
     for (;;) {
         if (group_left == 0) {
+            if (gi_stop && gi == gi_stop) BZD_FAIL(BZD_OK); // (not a failure: the segment ends here)
             if (gi >= nsel) BZD_FAIL(BZD_K_FORMAT);
-            t = BZD_UNI(w.sel[gi]);
+            if (Rec::ON && gi > 0 && gi % rec.interval == 0) rec.point(r.pos, gi, nblock, run, run_weight, w.mtf);
+            t = BZD_UNI(sel[gi]);
             gi++;
             group_left = BZD_GROUP;
             mn = BZD_UNI(w.minlen[t]);
@@ -280,7 +328,7 @@ BZD_FN void bzd_decode_block(BzdWork &w, const uint8_t *in, uint64_t n, uint64_t
         }
         if (run) {
             const uint32_t b = BZD_UNI(w.mtf[0]);
-            if (run > block_max - nblock) BZD_FAIL(BZD_K_FORMAT);
+            if (run > out_max - nblock) BZD_FAIL(BZD_K_FORMAT);
             for (uint32_t i = lane; i < run; i += BZD_LANES) L[nblock + i] = (uint8_t)b; // whole-wave stores
             nblock += run;
             run = 0;
@@ -302,14 +350,146 @@ BZD_FN void bzd_decode_block(BzdWork &w, const uint8_t *in, uint64_t n, uint64_t
         }
         if (l0) w.mtf[0] = (uint8_t)v;
         BZD_SYNC();
-        if (nblock >= block_max) BZD_FAIL(BZD_K_FORMAT);
+        if (nblock >= out_max) BZD_FAIL(BZD_K_FORMAT);
         if (l0) L[nblock] = (uint8_t)v;
         nblock++;
     }
-    res.nblock = nblock;
-    if (nblock == 0 || origptr >= nblock) BZD_FAIL(BZD_K_FORMAT);
-    res.end_bit = r.pos;
+    s.eob = 1;
+    BZD_FAIL(BZD_OK);
 #undef BZD_FAIL
+}
+
+// ---- one block: `pos` = bit position of its magic.  Leaves the last column in L[0 .. nblock), nblock <= block_max.
+template <class Rec>
+BZD_FN void bzd_decode_block_rec(BzdWork &w, const uint8_t *in, uint64_t n, uint64_t pos, uint32_t block_max, uint8_t *L, BzdResult &res,
+                                 Rec &rec)
+{
+    BzdBits r;
+    bzd_seek(r, in, n, pos + 48);
+    res.kind = BZD_OK;
+    res.errpos = 0;
+    res.end_bit = 0;
+    res.nblock = 0;
+    res.follow = 0;
+    res.pad = 0;
+    BzdHdr h;
+    if (!bzd_parse_header(w, r, res, h)) return;
+    BzdSym s = {0, 0, 0, 1, 0};
+    const uint32_t kind = bzd_symbols(w, w.sel, r, h.nin, h.nsel, 0u, block_max, L, s, rec);
+    if (kind != BZD_OK) {
+        res.kind = kind;
+        res.errpos = r.pos;
+        return;
+    }
+    res.nblock = s.nblock;
+    if (s.nblock == 0 || res.origptr >= s.nblock) {
+        res.kind = BZD_K_FORMAT;
+        res.errpos = r.pos;
+        return;
+    }
+    res.end_bit = r.pos;
+}
+
+BZD_FN void bzd_decode_block(BzdWork &w, const uint8_t *in, uint64_t n, uint64_t pos, uint32_t block_max, uint8_t *L, BzdResult &res)
+{
+    BzdNoRec rec;
+    bzd_decode_block_rec(w, in, n, pos, block_max, L, res, rec);
+}
+
+// ---- a SEGMENT of a block: from one sync point (or from the header's state, group 0) to the next (or to the end of the block).
+// The state of a point, as the symbol loop hands it to a recorder; bit_pos in the coordinates of `in`.
+struct BzdSyncState {
+    uint64_t bit_pos;
+    uint32_t group, out_pos, run, run_weight;
+    const uint8_t *mtf; // 256 bytes
+};
+
+enum BzdSegMiss : uint32_t { // why a segment does not fit its points (0: it does)
+    BZD_SEG_OK = 0,
+    BZD_SEG_START = 1, // the point it starts from cannot be a state of this block
+    BZD_SEG_EOB = 2,   // the block ends in front of the next point
+    BZD_SEG_ARRIVE = 3 // it arrives at the next point's group in another state than the point holds
+};
+
+struct BzdSegResult {
+    uint32_t kind; // BzdKind of the symbol loop
+    uint32_t miss; // BzdSegMiss
+    uint64_t errpos;
+    uint64_t end_bit; // last segment: first bit behind the block
+    uint32_t nblock;  // last segment: bytes of the whole last column
+    uint32_t pad;
+};
+
+// Decodes from `from` to `to` (has_to false: to the end of the block, `to` is not looked at).  `out` is where byte from.out_pos of the last column goes: at most
+// to.out_pos - from.out_pos bytes are written there (last segment: block_max - from.out_pos).  Points are untrusted: whatever
+// they hold, every index stays inside its table and every store inside that room, and a segment that does not arrive exactly
+// at `to` says so.  w: tables of the block's header; its MTF list is loaded from the point here.
+template <class W>
+BZD_FN void bzd_decode_segment(W &w, const uint8_t *sel, const uint8_t *in, uint64_t n, uint32_t nin, uint32_t nsel, uint32_t origptr,
+                               const BzdSyncState &from, bool has_to, const BzdSyncState &to, uint32_t block_max, uint8_t *out,
+                               BzdSegResult &res)
+{
+    const uint32_t lane = BZD_LANE;
+    res.kind = BZD_OK;
+    res.miss = BZD_SEG_OK;
+    res.errpos = from.bit_pos;
+    res.end_bit = 0;
+    res.nblock = 0;
+    res.pad = 0;
+    const uint32_t out_end = has_to ? to.out_pos : block_max, gi_stop = has_to ? to.group : 0u;
+    if (from.out_pos > out_end || out_end > block_max || from.group >= nsel || (has_to && to.group <= from.group) || from.bit_pos > n * 8 ||
+        from.run_weight == 0 || from.run_weight > (1u << 22)) {
+        res.miss = BZD_SEG_START;
+        return;
+    }
+    for (uint32_t i = lane; i < 256; i += BZD_LANES) w.mtf[i] = from.mtf[i];
+    BZD_SYNC();
+    BzdBits r;
+    bzd_seek(r, in, n, from.bit_pos);
+    BzdSym s = {from.group, 0, from.run, from.run_weight, 0};
+    BzdNoRec rec;
+    const uint32_t kind = bzd_symbols(w, sel, r, nin, nsel, gi_stop, out_end - from.out_pos, out, s, rec);
+    res.errpos = r.pos;
+    if (kind != BZD_OK) {
+        res.kind = kind;
+        return;
+    }
+    if (!has_to) {
+        res.nblock = from.out_pos + s.nblock;
+        res.end_bit = r.pos;
+        if (res.nblock == 0 || origptr >= res.nblock) res.kind = BZD_K_FORMAT;
+        return;
+    }
+    if (s.eob) {
+        res.miss = BZD_SEG_EOB;
+        return;
+    }
+    bool differs = false;
+    for (uint32_t i = lane; i < 256; i += BZD_LANES) differs |= w.mtf[i] != to.mtf[i];
+    if (BZD_ANY(differs) || r.pos != to.bit_pos || from.out_pos + s.nblock != to.out_pos || s.run != to.run || s.run_weight != to.run_weight)
+        res.miss = BZD_SEG_ARRIVE;
+}
+
+// ---- sync points are untrusted input (they may come from a file): what makes point i of pts[0 .. npts) ill formed against the
+// index idx[0 .. count), whatever the bytes hold (null: nothing).  E: bzh_index_entry, P: bzh_sync_point (include/bzhip.h).
+template <class E, class P>
+static inline const char *bzd_sync_point_check(const E *idx, size_t count, const P *pts, size_t i)
+{
+    const P &p = pts[i];
+    if (p.reserved != 0) return "reserved is not 0";
+    if (p.group == 0 || p.group >= BZD_MAX_SEL) return "group outside 1..32766";
+    if (p.entry >= count) return "entry outside the index";
+    const E &e = idx[p.entry];
+    const bool same = i > 0 && pts[i - 1].entry == p.entry;
+    if (i > 0 && (pts[i - 1].entry > p.entry || (same && pts[i - 1].group >= p.group))) return "(entry, group) does not ascend";
+    if (p.bit_pos <= e.bit_pos || p.bit_pos >= e.end_bit) return "bit_pos is not inside its entry";
+    if (same && p.bit_pos <= pts[i - 1].bit_pos) return "bit_pos does not ascend";
+    if (same && p.out_pos < pts[i - 1].out_pos) return "out_pos descends";
+    if (e.level < 1 || e.level > 9 || p.out_pos > 100000u * e.level) return "out_pos beyond the level's block size";
+    const uint32_t rw = p.run_weight;
+    if (rw == 0 || (rw & (rw - 1)) != 0 || rw > (1u << 22)) return "run_weight is no power of two up to 2^22";
+    if (p.run + 1 < rw || p.run + 1 > 2 * rw - 1) return "run and run_weight do not belong together";
+    return nullptr;
 }
 
 // ---- the footer at bit `pos` (its magic): stream CRC, padding to a byte, and what follows

@@ -232,6 +232,55 @@ BZH_API int bzh_decode_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t
 BZH_API int bzh_decode_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
                                     size_t count, uint64_t off, uint64_t len, void *d_out, size_t cap, size_t *out_len);
 
+/* ---- sync points: states of the entropy stage inside a block, so that a read decodes its blocks in parallel segments ---- */
+
+/* The entropy stage of a block is serial: the bit position, the Huffman table in use (it switches every 50 symbols, by the
+ * block's selectors), the inverse MTF list and the RLE2 run accumulator all carry from symbol to symbol.  That state is small.
+ * A sync point is that state at the boundary in front of group `group` of a block: with it the symbols from there on decode
+ * without the ones before.  The index build walks every block once anyway and writes a point every `interval` groups; a range
+ * decode then starts one wavefront per segment (from point to point) instead of one per block. */
+typedef struct {
+    uint64_t bit_pos;    /* of the first code of group `group`, in the coordinates of the indexed input */
+    uint32_t entry;      /* the bzh_index_entry it belongs to */
+    uint32_t group;      /* selector index of the first group decoded from here, 1 .. nsel-1 */
+    uint32_t out_pos;    /* bytes of the block's last column written before it (a pending run NOT included) */
+    uint32_t run;        /* RUNA/RUNB run accumulated so far, 0 = none */
+    uint32_t run_weight; /* weight of the next run digit, 1 = none pending */
+    uint32_t reserved;   /* 0 */
+    uint8_t mtf[256];    /* the MTF list: the bytes in use in list order, then zeros */
+} bzh_sync_point;        /* 288 bytes */
+
+/* bzh_decode_index that also writes the sync points: one in front of every group whose selector index is a multiple of
+ * `interval` (1..32767, else BZH_E_ARG), ordered by (entry, group).  The state behind a block's header (group 0) is not stored,
+ * every decode parses the header anyway; a block of fewer groups than the interval has no point.  The input contract, the
+ * verification, the errors and idx / *count / *out_total / *consumed are bzh_decode_index's, and the entries are the same.
+ * *count and *npts are both set on success and on BZH_E_CAP, which is returned when either array is too small (both are then
+ * unspecified): size with one call, fill with a second.  idx may be null when max is 0, pts when max_pts is 0. */
+BZH_API int bzh_decode_index_sync(bzh_ctx *ctx, const uint8_t *in, size_t n, uint32_t interval, bzh_index_entry *idx, size_t max,
+                                  size_t *count, bzh_sync_point *pts, size_t max_pts, size_t *npts, uint64_t *out_total,
+                                  size_t *consumed);
+BZH_API int bzh_decode_index_sync_device(bzh_ctx *ctx, const void *d_in, size_t n, uint32_t interval, bzh_index_entry *idx,
+                                         size_t max, size_t *count, bzh_sync_point *pts, size_t max_pts, size_t *npts,
+                                         uint64_t *out_total, size_t *consumed);
+
+/* bzh_decode_range with sync points: the same bytes, the same clipping, nothing written outside the range, the same checks of
+ * every touched block against its entry, every touched block's CRC verified, stream CRCs not.  Only the entropy stage differs:
+ * one wavefront parses each touched block's header, then one wavefront per segment decodes from its point to the next.
+ * npts == 0 is bzh_decode_range.  The points are untrusted (they may come from a file) and are checked as a whole, whatever the
+ * range, before anything is launched.  BZH_E_ARG, with bzh_last_error naming the point: (entry, group) not ascending, an entry
+ * outside the index, group 0 or above 32766, reserved not 0, a bit_pos not strictly inside its entry or not ascending, an out_pos
+ * that descends or exceeds the level's block size, a run / run_weight pair the decoder cannot be in (run_weight a power of two
+ * up to 2^22, run + 1 in [run_weight, 2 run_weight - 1]).  A point that is well formed but wrong for the bytes is BZH_E_DATA
+ * naming the entry and the point: every segment must arrive exactly at the next point's bit_pos, out_pos, run, run_weight and
+ * MTF list, so each point is checked by the segment in front of it, and the first by the header; behind that stand the entry's
+ * checks and the block CRC.  No point, whatever it holds, makes a kernel read or write outside its tables and its block's slot. */
+BZH_API int bzh_decode_range_sync(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                                  size_t count, const bzh_sync_point *pts, size_t npts, uint64_t off, uint64_t len, uint8_t *out,
+                                  size_t cap, size_t *out_len);
+BZH_API int bzh_decode_range_sync_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                                         size_t count, const bzh_sync_point *pts, size_t npts, uint64_t off, uint64_t len,
+                                         void *d_out, size_t cap, size_t *out_len);
+
 /* ---- streaming: encode() fed by a reader that yields arbitrary chunks (lib/rle.rs:30-92) ------- */
 
 /* Starts a stream on the context.  Then call bzh_stream_feed any number of times; the bytes it
