@@ -18,6 +18,8 @@ and random access into a .bz2 without decoding all of it (bzip2 blocks are indep
     IndexedReader(source, index=None)                    (read / seek over the decoded bytes of bytes or a file)
     build_sync_index(data, interval=256) -> SyncIndex    (a BlockIndex plus sync points inside the blocks: a read decodes
                                                           its blocks in parallel segments; accepted wherever a BlockIndex is)
+    encode_indexed(reader, writer, level, interval=256)  (encode() that returns that index of the stream it writes: the
+                                                          encoder holds it all, no decode pass) -> SyncIndex / BlockIndex
 
 Everything is computed by hand-written HIP kernels behind the C ABI in include/bzhip.h
 (libbzhip.so); there is no CPU path.  `reader` is any object with .read(), `writer` any object
@@ -32,7 +34,7 @@ import numpy as np
 from . import _native
 
 __all__ = ["encode", "encode_many", "encode_file", "decompress", "decode", "build_index", "decompress_range", "BlockIndex",
-           "IndexedReader", "build_sync_index", "SyncIndex", "Context", "MultiContext", "BzhError"]
+           "IndexedReader", "build_sync_index", "SyncIndex", "encode_indexed", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
 MultiContext = _native.MultiContext
@@ -411,6 +413,30 @@ def build_sync_index(data, interval=256, device=0):
         raise ValueError(f"interval must be 1..32767 groups, not {interval}")
     entries, points, _, consumed = _ctx(9, device).decode_index_sync(view, interval)
     return SyncIndex(BlockIndex(entries, consumed), points, interval)
+
+
+def encode_indexed(reader, writer, level, interval=256, device=0):
+    """encode() that also returns the index of the stream it writes, with no decode pass: a SyncIndex with a sync point every
+    `interval` groups (what build_sync_index(stream, interval) would build, byte for byte), or a BlockIndex when interval is 0
+    (build_index's).  The encoder holds everything an index records while it encodes (bzh_encode_index); the result goes
+    straight into decompress_range / IndexedReader.  This path reads the whole input first."""
+    if isinstance(level, bool) or not isinstance(level, int) or not 1 <= level <= 9:
+        raise ValueError("level must be in 1..=9")
+    if isinstance(interval, bool) or not isinstance(interval, int):
+        raise TypeError(f"interval must be an int, not {type(interval).__name__}")
+    if not 0 <= interval <= 32767:
+        raise ValueError(f"interval must be 0 (no sync points) or 1..32767 groups, not {interval}")
+    data = reader.getvalue()[reader.tell():] if isinstance(reader, io.BytesIO) else reader.read()
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError("reader.read() must return bytes")
+    stream, entries, points = _ctx(level, device).encode_index(data, interval)
+    if isinstance(reader, io.BytesIO):
+        reader.seek(0, io.SEEK_END)
+    writer.write(stream)
+    if hasattr(writer, "flush"):
+        writer.flush()
+    blocks = BlockIndex(entries, len(stream))
+    return SyncIndex(blocks, points, interval) if interval else blocks
 
 
 def _index_arg(index):

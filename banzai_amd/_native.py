@@ -105,6 +105,11 @@ SIGNATURES = {
                                        szp, szp]),
     "bzh_encode_many_bound": (ctypes.c_size_t, [ctypes.c_int, szp, ctypes.c_size_t]),
     "bzh_plan_many_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, szp, ctypes.c_size_t, szp]),
+    "bzh_encode_index_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, szp,
+                                               szp, ctypes.c_uint32, idxp, ctypes.c_size_t, szp, syncp, ctypes.c_size_t, szp]),
+    "bzh_encode_index": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u8p, ctypes.c_size_t, szp, szp, ctypes.c_uint32, idxp,
+                                        ctypes.c_size_t, szp, syncp, ctypes.c_size_t, szp]),
+    "bzh_encode_index_bound": (ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32, szp, szp]),
     "bzh_decode": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u8p, ctypes.c_size_t, szp, szp]),
     "bzh_decode_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                          ctypes.c_size_t, szp, szp]),
@@ -187,6 +192,15 @@ def encode_many_bound(level, lens):
     """bzh_encode_many_bound: upper bound of the output of bzh_encode_many for these input lengths (0 for a bad level)"""
     lens = np.ascontiguousarray(lens, dtype=np.uint64)
     return int(lib().bzh_encode_many_bound(level, ptr(lens, szp) if lens.size else None, lens.size))
+
+
+def encode_index_bound(level, n, interval):
+    """bzh_encode_index_bound (host arithmetic, no GPU): (entries, sync points) that bzh_encode_index never exceeds"""
+    me, mp = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    st = lib().bzh_encode_index_bound(level, n, interval, ctypes.byref(me), ctypes.byref(mp))
+    if st != 0:
+        raise BzhError(st, lib().bzh_strerror(st).decode())
+    return int(me.value), int(mp.value)
 
 
 def _entries(entries):
@@ -407,6 +421,42 @@ class Context:
         self.check(lib().bzh_encode(self._h, ptr(a), n, ptr(out), cap, ctypes.byref(olen), ctypes.byref(used)))
         assert used.value == n
         return out[:olen.value].tobytes()
+
+    def encode_index(self, data, interval):
+        """bzh_encode_index: (stream, entries as an array of INDEX_DTYPE, points as an array of SYNC_DTYPE) -- the stream
+        encode() writes, with the index bzh_decode_index_sync(stream, interval) would build (interval 0: no points).  The
+        entries are sized by bzh_encode_index_bound, the points by the symbols the input can make (far below the bound of
+        an interval of 1), and once more by the count BZH_E_CAP reports should that ever fall short."""
+        n = len(data)
+        a = np.frombuffer(bytes(data), dtype=np.uint8).copy() if n else np.zeros(1, np.uint8)
+        cap = n + n // 4 + 65536 + (n // 70000 + 2) * 4096
+        out = np.empty(cap, dtype=np.uint8)
+        olen, used, cnt, npts = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        max_ent, max_pts = encode_index_bound(self.level, n, interval)
+        # (points of a block <= its symbols / 50 / interval, its symbols <= its RLE1 bytes + 1, those <= 5/4 of its input)
+        room = min(max_pts, (n + n // 4 + max_ent) // 50 // max(interval, 1) + 1)
+        while True:
+            ent = np.empty(max(max_ent, 1), dtype=INDEX_DTYPE)
+            pts = np.empty(max(room, 1), dtype=SYNC_DTYPE)
+            st = lib().bzh_encode_index(self._h, ptr(a), n, ptr(out), cap, ctypes.byref(olen), ctypes.byref(used), interval,
+                                        ent.ctypes.data_as(idxp), max_ent, ctypes.byref(cnt), pts.ctypes.data_as(syncp), room,
+                                        ctypes.byref(npts))
+            if st == -4 and npts.value > room:
+                room = npts.value
+                continue
+            self.check(st)
+            assert used.value == n
+            return out[:olen.value].tobytes(), ent[:cnt.value].copy(), pts[:npts.value].copy()
+
+    def encode_index_device(self, d_in, n, d_out, cap, interval, max_entries, max_pts):
+        """bzh_encode_index_device on integer device addresses, arrays of the given room -> (stream length, entries, points)"""
+        olen, used, cnt, npts = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        ent = np.empty(max(max_entries, 1), dtype=INDEX_DTYPE)
+        pts = np.empty(max(max_pts, 1), dtype=SYNC_DTYPE)
+        self.check(lib().bzh_encode_index_device(self._h, ctypes.c_void_p(d_in), n, ctypes.c_void_p(d_out), cap, ctypes.byref(olen),
+                                                 ctypes.byref(used), interval, ent.ctypes.data_as(idxp), max_entries, ctypes.byref(cnt),
+                                                 pts.ctypes.data_as(syncp), max_pts, ctypes.byref(npts)))
+        return int(olen.value), ent[:cnt.value], pts[:npts.value]
 
     def encode_many(self, items):
         """bzh_encode_many: one complete .bz2 stream per item (host buffers, one pass) -> [bytes]"""

@@ -854,8 +854,10 @@ static int prepare_batch(bzh_ctx *lane, RangeJob &j, bool wait_total = true)
 // bit_base/32 on are zeroed here as needed (words before that are the caller's).
 // (`framed`: in/out -- the caller wants the whole stream's header and footer around these blocks; set back to false unless
 // this call wrote them on the device: one batch, one lane, all blocks of the plan from bit 32 on)
+// (`ix`: the caller wants the index of what is written -- bzh_encode_index*; every batch is handed to sync_emit_batch behind its
+// pack, while its arena still holds it; one lane whatever bzh_set_lanes says)
 static int encode_range(bzh_ctx *ctx, size_t b0, size_t b1, uint8_t *d_out, size_t cap, uint64_t bit_base,
-                        uint64_t *nbits, const uint32_t *seed_word = nullptr, bool *framed = nullptr)
+                        uint64_t *nbits, const uint32_t *seed_word = nullptr, bool *framed = nullptr, EncIndex *ix = nullptr)
 {
     const bool want_frame = framed && *framed;
     if (framed) *framed = false;
@@ -865,7 +867,7 @@ static int encode_range(bzh_ctx *ctx, size_t b0, size_t b1, uint8_t *d_out, size
     }
     // default: one lane = this context (whole arena, caller's stream, no extra threads)
     std::vector<bzh_ctx *> lanes{ctx};
-    if (ctx->nlanes == 2) {
+    if (ctx->nlanes == 2 && !ix) {
         BZH_TRY(ensure_lanes(ctx));
         lanes = ctx->lanes;
     }
@@ -994,6 +996,7 @@ static int encode_range(bzh_ctx *ctx, size_t b0, size_t b1, uint8_t *d_out, size
                         status = BZH_E_CAP;
                     } else {
                         for (uint32_t b = 0; b < (uint32_t)hm.size(); b++) ctx->stats.mtf_syms += hm[b];
+                        if (ix) status = sync_emit_batch(lane, job.B, job.k0, bit_base, *ix);
                         cur += job.T;
                     }
                 }
@@ -1026,6 +1029,8 @@ static int encode_range(bzh_ctx *ctx, size_t b0, size_t b1, uint8_t *d_out, size
                 if (he != hipSuccess) {
                     bzh_set_error(ctx, "pack: %s", hipGetErrorString(he));
                     status = BZH_E_HIP;
+                } else if (ix) {
+                    status = sync_emit_batch(lane, job.B, job.k0, bit_base + cur, *ix);
                 }
                 cur += job.T;
             }
@@ -1252,8 +1257,9 @@ extern "C" int bzh_assemble_device(bzh_ctx *ctx, const void *const *d_segs, cons
     });
 }
 
-extern "C" int bzh_encode_device(bzh_ctx *ctx, const void *d_in, size_t n, void *d_out, size_t cap, size_t *out_len,
-                                 size_t *consumed)
+// bzh_encode_device; with `ix` also the index of the stream (bzh_encode_index_device)
+static int encode_device_impl(bzh_ctx *ctx, const void *d_in, size_t n, void *d_out, size_t cap, size_t *out_len, size_t *consumed,
+                              EncIndex *ix)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
@@ -1282,7 +1288,8 @@ extern "C" int bzh_encode_device(bzh_ctx *ctx, const void *d_in, size_t n, void 
     const size_t nb = ctx->plan_blocks.size();
     bool framed = true; // (a stream of one batch gets its header and footer on the device, behind the pack: no host round trip)
     if (nb) {
-        BZH_TRY(encode_range(ctx, 0, nb, (uint8_t *)d_out, cap, 32, &body, nullptr, &framed));
+        if (ix) BZH_TRY(rle1_plan_crc_join(ctx)); // (the entries carry the block CRCs)
+        BZH_TRY(encode_range(ctx, 0, nb, (uint8_t *)d_out, cap, 32, &body, nullptr, &framed, ix));
     } else {
         framed = false;
         HIP_TRY(ctx, hipMemsetAsync(d_out, 0, 16, st));
@@ -1326,6 +1333,12 @@ extern "C" int bzh_encode_device(bzh_ctx *ctx, const void *d_in, size_t n, void 
     });
 }
 
+extern "C" int bzh_encode_device(bzh_ctx *ctx, const void *d_in, size_t n, void *d_out, size_t cap, size_t *out_len,
+                                 size_t *consumed)
+{
+    return encode_device_impl(ctx, d_in, n, d_out, cap, out_len, consumed, nullptr);
+}
+
 extern "C" int bzh_encode(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len,
                           size_t *consumed)
 {
@@ -1346,6 +1359,86 @@ extern "C" int bzh_encode(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *ou
     HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, len, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, bzh_stream_wait(st));
     return BZH_OK;
+    });
+}
+
+// ---- the encoder writes the index of its own stream (sync_emit.hip) --------------------------------------------------------
+extern "C" int bzh_encode_index_bound(int level, size_t n, uint32_t interval, size_t *max_entries, size_t *max_pts)
+{
+    if (level < 1 || level > 9 || interval > 32767 || !max_entries || !max_pts) return BZH_E_ARG;
+    const size_t M = (size_t)100000 * level - 1;
+    const size_t blocks = n / (M * 4 / 5) + 2;       // a block consumes at least M * 4 / 5 raw bytes (bzh_encode sizes its output so)
+    const size_t groups = (M + 1 + 49) / 50;         // m <= M + 1 symbols (lib/mtf.rs:36), 50 a group
+    *max_entries = blocks;
+    *max_pts = interval ? blocks * ((groups - 1) / interval) : 0;
+    return BZH_OK;
+}
+
+static int encode_index_args(bzh_ctx *ctx, uint32_t interval, bzh_index_entry *idx, size_t max, size_t *count, bzh_sync_point *pts,
+                             size_t max_pts, size_t *npts)
+{
+    if (!ctx || !count || !npts || (!idx && max) || (!pts && max_pts)) return BZH_E_ARG;
+    if (interval > 32767) {
+        bzh_set_error(ctx, "encode index: a sync interval of %u groups, outside 0..32767", interval);
+        return BZH_E_ARG;
+    }
+    *count = 0;
+    *npts = 0;
+    return BZH_OK;
+}
+
+static int encode_index_out(bzh_ctx *ctx, const EncIndex &ix, bzh_index_entry *idx, size_t max, size_t *count, bzh_sync_point *pts,
+                            size_t max_pts, size_t *npts)
+{
+    *count = ix.entries.size();
+    *npts = ix.pts.size();
+    if (ix.entries.size() > max) {
+        bzh_set_error(ctx, "encode index: %zu entries, room for %zu", ix.entries.size(), max);
+        return BZH_E_CAP;
+    }
+    if (ix.pts.size() > max_pts) {
+        bzh_set_error(ctx, "encode index: %zu sync points, room for %zu", ix.pts.size(), max_pts);
+        return BZH_E_CAP;
+    }
+    if (!ix.entries.empty()) memcpy(idx, ix.entries.data(), ix.entries.size() * sizeof(bzh_index_entry));
+    if (!ix.pts.empty()) memcpy(pts, ix.pts.data(), ix.pts.size() * sizeof(bzh_sync_point));
+    return BZH_OK;
+}
+
+extern "C" int bzh_encode_index_device(bzh_ctx *ctx, const void *d_in, size_t n, void *d_out, size_t cap, size_t *out_len,
+                                       size_t *consumed, uint32_t interval, bzh_index_entry *idx, size_t max, size_t *count,
+                                       bzh_sync_point *pts, size_t max_pts, size_t *npts)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    BZH_TRY(encode_index_args(ctx, interval, idx, max, count, pts, max_pts, npts));
+    EncIndex ix{interval, {}, {}};
+    BZH_TRY(encode_device_impl(ctx, d_in, n, d_out, cap, out_len, consumed, &ix));
+    return encode_index_out(ctx, ix, idx, max, count, pts, max_pts, npts);
+    });
+}
+
+extern "C" int bzh_encode_index(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len,
+                                size_t *consumed, uint32_t interval, bzh_index_entry *idx, size_t max, size_t *count,
+                                bzh_sync_point *pts, size_t max_pts, size_t *npts)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    BZH_TRY(encode_index_args(ctx, interval, idx, max, count, pts, max_pts, npts));
+    stream_join(ctx);
+    if ((!in && n) || !out || !out_len) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, n + 16));
+    const size_t dcap = n + n / 4 + (n / ((size_t)ctx->M * 4 / 5) + 2) * 4096 + 65536; // (as bzh_encode)
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, dcap));
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, st));
+    size_t len = 0;
+    EncIndex ix{interval, {}, {}};
+    BZH_TRY(encode_device_impl(ctx, ctx->d_stage_in, n, ctx->d_stage_out, ctx->stage_out_size & ~(size_t)3, &len, consumed, &ix));
+    *out_len = len;
+    if (len > cap) return BZH_E_CAP;
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, len, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, bzh_stream_wait(st));
+    return encode_index_out(ctx, ix, idx, max, count, pts, max_pts, npts);
     });
 }
 

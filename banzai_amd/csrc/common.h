@@ -176,6 +176,14 @@ struct Batch {
 };
 
 constexpr uint32_t MTF_TILE = 2048;  // BWT bytes walked by one wavefront (twice that in batches of 64 blocks and more: mtf_run)
+static inline uint32_t mtf_tile_bytes(uint32_t B) { return B >= 64u ? 2u * MTF_TILE : MTF_TILE; } // the tile of a batch of B blocks (mtf_run)
+// RLE2 layout of one MTF tile (mtf_tile_last -> mtf_prefix -> mtf_walk_par; read back by sync_emit)
+struct MtfTile {
+    int first;    // position in the block of the tile's first run head, -1 if none
+    int last;     // of its last one, -1 if none; after mtf_prefix: the last run head BEFORE the tile
+    uint32_t cnt; // symbols the tile emits, not counting the zero-run digits in front of `first`
+    uint32_t off; // after mtf_prefix: output offset of the tile
+};
 constexpr uint32_t HDR_BYTES = 4160; // 64 B block header/symbol map/counts + up to 3 delta-coded tables (< 25.6 kbit)
 constexpr uint32_t PACK_TILE = 4096; // MTF symbols packed by one workgroup
 constexpr uint32_t FX_TABLES = 6;         // lib/huffman.rs:319-326 allows 2..6 tables
@@ -379,6 +387,11 @@ struct KSpan {
 };
 
 // ---- wavefront-64 primitives ----------------------------------------------------------------
+__device__ __forceinline__ uint32_t run_digits(uint32_t z) // symbols emitted for a zero run of length z
+{
+    return z ? (31u - __clz(z + 1u)) : 0u;
+}
+
 __device__ __forceinline__ uint32_t wave_incl_add(uint32_t v, int lane)
 {
 #pragma unroll
@@ -618,5 +631,14 @@ int decode_sync_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count, co
 int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
                      uint64_t off, uint64_t len, uint8_t *d_out, size_t cap, size_t *out_len, const bzh_sync_point *pts = nullptr,
                      size_t npts = 0);
+
+// sync_emit.hip: the index of the stream being encoded (bzh_encode_index*).  encode_range hands every batch over once its bits
+// are packed and before its arena is reused: the entries of its blocks, and a sync point every `interval` groups (0: none)
+struct EncIndex {
+    uint32_t interval;
+    std::vector<bzh_index_entry> entries;
+    std::vector<bzh_sync_point> pts;
+};
+int sync_emit_batch(bzh_ctx *ctx, uint32_t B, size_t k0, uint64_t bit_base, EncIndex &ix);
 
 hipEvent_t bzh_event(bzh_ctx *ctx);

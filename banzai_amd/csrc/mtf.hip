@@ -20,18 +20,7 @@
 // visits anyway, with the symbol histogram.
 #include "common.h"
 
-// RLE2 layout of one MTF tile (mtf_tile_last -> mtf_prefix -> mtf_walk_par)
-struct MtfTile {
-    int first;    // position in the block of the tile's first run head, -1 if none
-    int last;     // of its last one, -1 if none; after mtf_prefix: the last run head BEFORE the tile
-    uint32_t cnt; // symbols the tile emits, not counting the zero-run digits in front of `first`
-    uint32_t off; // after mtf_prefix: output offset of the tile
-};
-
-__device__ __forceinline__ uint32_t run_digits(uint32_t z) // symbols emitted for a zero run of length z
-{
-    return z ? (31u - __clz(z + 1u)) : 0u;
-}
+// (MtfTile, the RLE2 layout of one tile, and run_digits: common.h -- sync_emit.hip reads the layout back)
 
 // ---- dense names ------------------------------------------------------------------------------------
 // names[c] = rank of byte c among the present bytes (lib/mtf.rs:17-24).  MTF positions are the same
@@ -510,7 +499,7 @@ int mtf_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal)
     // (Tiles of 512 bytes for batches of one to four blocks -- more wavefronts for a batch that cannot fill the device -- measured
     // SLOWER: config 2 1.062 -> 1.099 ms, one text block 1.258 -> 1.304 ms: the list a tile's walk starts from costs more than
     // the extra wavefronts return.)
-    const uint32_t TL = B >= 64u ? 2u * MTF_TILE : MTF_TILE;
+    const uint32_t TL = mtf_tile_bytes(B);
     const uint32_t MT = (bt.S + TL - 1) / TL;
     int32_t *tlast = reinterpret_cast<int32_t *>(bt.listA);  // B*MT*256*4 <= B*S*8
     MtfTile *rt = reinterpret_cast<MtfTile *>(bt.listB);     // B*MT*16 bytes

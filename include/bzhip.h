@@ -281,6 +281,34 @@ BZH_API int bzh_decode_range_sync_device(bzh_ctx *ctx, const void *d_in, size_t 
                                          size_t count, const bzh_sync_point *pts, size_t npts, uint64_t off, uint64_t len,
                                          void *d_out, size_t cap, size_t *out_len);
 
+/* ---- the encoder writes the index of its own stream: no decode pass to rediscover what it held -------------------------- */
+
+/* bzh_encode_device that also returns the index of the stream it writes: the entries bzh_decode_index would return for
+ * d_out[0..*out_len), and, with interval in 1..32767, the sync points bzh_decode_index_sync would return for that interval,
+ * byte for byte (one in front of every group whose index is a positive multiple of interval, ordered by (entry, group), mtf =
+ * the bytes in use in list order, then zeros, reserved 0).  interval 0: entries only (pts may be null, *npts = 0).  The stream
+ * is bit-identical to bzh_encode_device's, in either Huffman mode.  An entry's bit_pos is 32 + the bits of the blocks before
+ * it, its end_bit the next block's bit_pos (the last one's: the bit of the footer magic), out_off / out_len the raw bytes the
+ * block consumed, crc its block CRC, stream 0, level the context's.  An empty input gives *count = 0, *npts = 0 and the 14-byte
+ * stream.  The points are computed from what the encoder holds when a batch is packed (one wavefront a point), not by decoding.
+ * BZH_E_ARG: an interval above 32767, a null count / npts, a null array with room claimed, and what bzh_encode_device refuses.
+ * BZH_E_CAP: the output does not fit (as bzh_encode_device), or either array is too small: *count and *npts are then set and
+ * everything else is unspecified, as for bzh_decode_index_sync.  Arrays sized by bzh_encode_index_bound never are too small.
+ * The call runs on ONE lane (bzh_set_lanes does not apply), joins a streaming pass in flight and honours bzh_set_profiling
+ * like every entry point.  After any error the context stays usable. */
+BZH_API int bzh_encode_index_device(bzh_ctx *ctx, const void *d_in, size_t n, void *d_out, size_t cap, size_t *out_len,
+                                    size_t *consumed, uint32_t interval, bzh_index_entry *idx, size_t max, size_t *count,
+                                    bzh_sync_point *pts, size_t max_pts, size_t *npts);
+/* Same, host buffers in and out (as bzh_encode). */
+BZH_API int bzh_encode_index(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len,
+                             size_t *consumed, uint32_t interval, bzh_index_entry *idx, size_t max, size_t *count,
+                             bzh_sync_point *pts, size_t max_pts, size_t *npts);
+/* Pure host arithmetic, no context: array sizes that the call never exceeds for n input bytes at this level and interval.
+ * With M = 100000 * level - 1: a block consumes at least M * 4 / 5 raw bytes, so *max_entries = n / (M * 4 / 5) + 2 (what
+ * bzh_encode sizes its output by); a block has at most ceil((M + 1) / 50) = 2000 * level groups, so *max_pts = *max_entries *
+ * ((2000 * level - 1) / interval), 0 for interval 0.  BZH_E_ARG: a level outside 1..9, an interval above 32767, a null pointer. */
+BZH_API int bzh_encode_index_bound(int level, size_t n, uint32_t interval, size_t *max_entries, size_t *max_pts);
+
 /* ---- streaming: encode() fed by a reader that yields arbitrary chunks (lib/rle.rs:30-92) ------- */
 
 /* Starts a stream on the context.  Then call bzh_stream_feed any number of times; the bytes it
