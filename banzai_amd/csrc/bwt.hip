@@ -3332,14 +3332,16 @@ int bwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal)
 // radix_scatter as the forward sort) yields T = LF^-1 (row r -> row of the rotation one byte further on);
 // the walk X[i] = T^i(ptr) is then computed for all i at once by doubling: with X[0..m) and P = T^m known,
 // X[m+i] = P[X[i]] and T^2m = P o P -- log2 n rounds of gathers, no serial list traversal, and blocks made of
-// repeated words (several cycles in T) need no special care.  S[i] = L[X[i+1]].
+// repeated words (several cycles in T) need no special care.  S[i] = L[X[i+1]] for i < n: n + 1 values of X.  The last of them,
+// T^n(ptr), is ptr itself for the BWT of anything, but the decoder also meets columns that are no BWT of anything (a cycle of T
+// whose length does not divide n), where libbz2's walk -- the yardstick -- ends on L[T^n(ptr)] all the same.
 struct UnbwtArgs {
     const uint8_t *L;    // [B][S] last column
     const uint32_t *n;   // [B]
     const uint32_t *ptr; // [B]
     const u64 *list;     // [B][S] sorted (byte, position) pairs
     uint32_t *P, *P2;    // [B][S] T^m and T^2m
-    uint32_t *X;         // [B][S] X[i] = T^i(ptr)
+    uint32_t *X;         // [B][S] X[i] = T^i(ptr), i <= n (n < S: a block is shorter than its stride)
     uint8_t *out;        // [B][S]
     uint32_t S, m;
 };
@@ -3355,11 +3357,11 @@ __global__ void __launch_bounds__(256) unbwt_init(UnbwtArgs a)
 __global__ void __launch_bounds__(256) unbwt_round(UnbwtArgs a)
 {
     const uint32_t b = blockIdx.y, n = a.n[b], m = a.m;
-    if (m >= n) return;
+    if (m > n) return; // X[0 .. n] is complete
     const size_t base = (size_t)b * a.S;
     const uint32_t *P = a.P + base;
-    const bool need_sq = 2u * m < n; // T^2m is only needed if another round follows
-    const uint32_t ext = min(m, n - m);
+    const bool need_sq = 2u * m <= n; // T^2m is only needed if another round follows
+    const uint32_t ext = min(m, n + 1 - m);
     for (uint32_t r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) {
         if (need_sq) a.P2[base + r] = P[P[r]];
         if (r < ext) a.X[base + m + r] = P[a.X[base + r]];
@@ -3371,8 +3373,7 @@ __global__ void __launch_bounds__(256) unbwt_emit(UnbwtArgs a)
     const uint32_t b = blockIdx.y, n = a.n[b];
     const size_t base = (size_t)b * a.S;
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const uint32_t nx = i + 1 < n ? a.X[base + i + 1] : a.ptr[b];
-        a.out[base + i] = a.L[base + nx];
+        a.out[base + i] = a.L[base + a.X[base + i + 1]];
     }
 }
 
@@ -3392,6 +3393,10 @@ int unbwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax)
 {
     Batch &bt = ctx->bt;
     if (B == 0 || nmax == 0) return BZH_OK;
+    if (nmax >= bt.S) { // (never: S is the first multiple of the sort tile above the largest block)
+        bzh_set_error(ctx, "inverse BWT: a block of %u bytes leaves no room for its last walk position (stride %u)", nmax, bt.S);
+        return BZH_E_STATE;
+    }
     hipStream_t st = ctx->stream;
     const Lst all{nullptr, nullptr, B};
     u64 *bufA = reinterpret_cast<u64 *>(bt.listA);
@@ -3428,7 +3433,7 @@ int unbwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax)
     u.S = bt.S;
     const dim3 grid(std::min<uint32_t>((nmax + 1023) / 1024, 512), B);
     unbwt_init<<<grid, 256, 0, st>>>(u);
-    for (uint32_t m = 1; m < nmax; m <<= 1) {
+    for (uint32_t m = 1; m <= nmax; m <<= 1) {
         u.m = m;
         unbwt_round<<<grid, 256, 0, st>>>(u);
         uint32_t *t = u.P;

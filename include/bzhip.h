@@ -162,7 +162,9 @@ BZH_API int bzh_plan_many_device(bzh_ctx *ctx, const void *d_in, const size_t *l
  * BZH_E_DATA: bad magic, truncation, a field outside the format (selectors 1..32767, code lengths 1..20, an over-subscribed
  * code, origPtr >= nblock, more bytes than the level's block size, a block that ends in four equal bytes without the count
  * byte libbz2 insists on), a block or stream CRC mismatch, and a RANDOMISED block: no current encoder writes one (a bzip2
- * 0.9.0 feature), so they are refused, not decoded.  bzh_last_error names the kind, the stream, the block and the bit
+ * 0.9.0 feature), so they are refused, not decoded.  Every table of a block is built and checked up front: an over-subscribed
+ * table is refused even where no selector names it; libbz2, which never checks a table, accepts that unused-table form.
+ * bzh_last_error names the kind, the stream, the block and the bit
  * position.  Every read and write of the decode kernels is bounded by construction, so a damaged stream yields a status and
  * the context stays usable.  Like every entry point the call joins a streaming pass in flight, runs on the context's stream
  * and honours bzh_set_profiling. */
