@@ -1495,42 +1495,74 @@ extern "C" int bzh_crc32(bzh_ctx *ctx, const uint8_t *in, size_t n, uint32_t *cr
 // ================================================================================================
 // Decode (decode.hip): scan, then the arena for as many blocks as there are candidates, then the chain
 // ================================================================================================
-extern "C" int bzh_decode_device(bzh_ctx *ctx, const void *d_in, size_t n, void *d_out, size_t cap, size_t *out_len, size_t *consumed)
+// What every decode call does around its work: the device, fresh statistics, and with profiling on the events of the whole call
+// and of its scan (a range has none).
+struct DecodeCall {
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+};
+
+static hipEvent_t decode_call_mark(bzh_ctx *ctx)
 {
-    return bzh_guard(ctx, [&]() -> int {
-    if (ctx) stream_join(ctx);
-    if (!ctx || (!d_in && n) || (!d_out && cap) || !out_len) return BZH_E_ARG;
+    if (!ctx->profiling) return nullptr;
+    hipEvent_t e = bzh_event(ctx);
+    hipEventRecord(e, ctx->stream);
+    return e;
+}
+
+static int decode_call_begin(bzh_ctx *ctx, size_t n, DecodeCall &c)
+{
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
     ctx->evnext = 0;
     ctx->sort_spans.clear();
     kstats_reset(ctx);
     memset(&ctx->dstats, 0, sizeof ctx->dstats);
     ctx->dstats.in_bytes = n;
+    c.t0 = decode_call_mark(ctx);
+    return BZH_OK;
+}
+
+// the scan, and the arena for as many blocks as it found candidates
+static int decode_call_scan(bzh_ctx *ctx, DecodeCall &c, const void *d_in, size_t n, std::vector<uint64_t> &cands)
+{
+    BZH_TRY(decode_scan_run(ctx, (const uint8_t *)d_in, n, cands));
+    c.t1 = decode_call_mark(ctx);
+    ctx->dstats.candidates = cands.size();
+    return ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(cands.size(), 1), ctx->max_batch));
+}
+
+// rc: the status of the work, handed through
+static int decode_call_end(bzh_ctx *ctx, const DecodeCall &c, int rc)
+{
+    if (!ctx->profiling) return rc;
+    hipEvent_t t2 = decode_call_mark(ctx);
+    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+    if (c.t1) ctx->dstats.ms_scan = span_ms(c.t0, c.t1);
+    ctx->dstats.ms_total = span_ms(c.t0, t2);
+    return rc;
+}
+
+// The host variants: the input into the staging buffer (queued), room for out_bytes of output in the other one.
+static int decode_stage(bzh_ctx *ctx, const uint8_t *in, size_t n, size_t out_bytes = 0)
+{
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, n + 16));
+    if (out_bytes) BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, out_bytes));
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, ctx->stream));
+    return BZH_OK;
+}
+
+extern "C" int bzh_decode_device(bzh_ctx *ctx, const void *d_in, size_t n, void *d_out, size_t cap, size_t *out_len, size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n) || (!d_out && cap) || !out_len) return BZH_E_ARG;
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
     *out_len = 0;
     if (consumed) *consumed = 0;
-    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
-    if (ctx->profiling) {
-        t0 = bzh_event(ctx);
-        hipEventRecord(t0, st);
-    }
     std::vector<uint64_t> cands;
-    BZH_TRY(decode_scan_run(ctx, (const uint8_t *)d_in, n, cands));
-    if (ctx->profiling) {
-        t1 = bzh_event(ctx);
-        hipEventRecord(t1, st);
-    }
-    ctx->dstats.candidates = cands.size();
-    BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(cands.size(), 1), ctx->max_batch)));
+    BZH_TRY(decode_call_scan(ctx, call, d_in, n, cands));
     const int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, (uint8_t *)d_out, cap, out_len, consumed, cands);
-    if (ctx->profiling) {
-        t2 = bzh_event(ctx);
-        hipEventRecord(t2, st);
-        HIP_TRY(ctx, bzh_stream_wait(st));
-        ctx->dstats.ms_scan = span_ms(t0, t1);
-        ctx->dstats.ms_total = span_ms(t0, t2);
-    }
-    return rc;
+    return decode_call_end(ctx, call, rc);
     });
 }
 
@@ -1540,16 +1572,13 @@ extern "C" int bzh_decode(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *ou
     if (ctx) stream_join(ctx);
     if (!ctx || (!in && n) || (!out && cap) || !out_len) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, n + 16));
-    if (cap) BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, cap));
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, st));
+    BZH_TRY(decode_stage(ctx, in, n, cap));
     size_t len = 0;
     const int rc = bzh_decode_device(ctx, ctx->d_stage_in, n, cap ? ctx->d_stage_out : nullptr, cap, &len, consumed);
     *out_len = len; // (BZH_E_CAP: the size needed)
     if (rc != BZH_OK) return rc;
-    if (len) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, len, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, bzh_stream_wait(st));
+    if (len) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, len, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
     return BZH_OK;
     });
 }
@@ -1562,41 +1591,19 @@ static int decode_index_device_impl(bzh_ctx *ctx, const void *d_in, size_t n, ui
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_in && n) || (!idx && max) || !count || !out_total || (!pts && max_pts) || (interval && !npts)) return BZH_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    ctx->evnext = 0;
-    ctx->sort_spans.clear();
-    kstats_reset(ctx);
-    memset(&ctx->dstats, 0, sizeof ctx->dstats);
-    ctx->dstats.in_bytes = n;
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
     *count = 0;
     *out_total = 0;
     if (npts) *npts = 0;
     if (consumed) *consumed = 0;
-    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
-    if (ctx->profiling) {
-        t0 = bzh_event(ctx);
-        hipEventRecord(t0, st);
-    }
     std::vector<uint64_t> cands;
-    BZH_TRY(decode_scan_run(ctx, (const uint8_t *)d_in, n, cands));
-    if (ctx->profiling) {
-        t1 = bzh_event(ctx);
-        hipEventRecord(t1, st);
-    }
-    ctx->dstats.candidates = cands.size();
-    BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(cands.size(), 1), ctx->max_batch)));
+    BZH_TRY(decode_call_scan(ctx, call, d_in, n, cands));
     std::vector<bzh_index_entry> entries;
     size_t total = 0;
     SyncBuild sync{interval, {}};
-    const int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, &entries, interval ? &sync : nullptr);
-    if (ctx->profiling) {
-        t2 = bzh_event(ctx);
-        hipEventRecord(t2, st);
-        HIP_TRY(ctx, bzh_stream_wait(st));
-        ctx->dstats.ms_scan = span_ms(t0, t1);
-        ctx->dstats.ms_total = span_ms(t0, t2);
-    }
+    int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, &entries, interval ? &sync : nullptr);
+    rc = decode_call_end(ctx, call, rc);
     if (rc != BZH_OK) return rc;
     *count = entries.size();
     *out_total = total;
@@ -1645,8 +1652,7 @@ extern "C" int bzh_decode_index_sync(bzh_ctx *ctx, const uint8_t *in, size_t n, 
     if (!ctx || (!in && n) || (!idx && max) || !count || !out_total || (!pts && max_pts) || !npts) return BZH_E_ARG;
     if (!sync_interval_ok(ctx, interval)) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, n + 16));
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, ctx->stream));
+    BZH_TRY(decode_stage(ctx, in, n));
     return decode_index_device_impl(ctx, ctx->d_stage_in, n, interval, idx, max, count, pts, max_pts, npts, out_total, consumed);
     });
 }
@@ -1658,8 +1664,7 @@ extern "C" int bzh_decode_index(bzh_ctx *ctx, const uint8_t *in, size_t n, bzh_i
     if (ctx) stream_join(ctx);
     if (!ctx || (!in && n) || (!idx && max) || !count || !out_total) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, n + 16));
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, ctx->stream));
+    BZH_TRY(decode_stage(ctx, in, n));
     return bzh_decode_index_device(ctx, ctx->d_stage_in, n, idx, max, count, out_total, consumed);
     });
 }
@@ -1672,19 +1677,9 @@ static int decode_range_device_impl(bzh_ctx *ctx, const void *d_in, size_t n, ui
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_in && n) || (!d_out && cap) || (!idx && count) || (!pts && npts) || !out_len) return BZH_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    ctx->evnext = 0;
-    ctx->sort_spans.clear();
-    kstats_reset(ctx);
-    memset(&ctx->dstats, 0, sizeof ctx->dstats);
-    ctx->dstats.in_bytes = n;
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
     *out_len = 0;
-    hipEvent_t t0 = nullptr, t2 = nullptr;
-    if (ctx->profiling) {
-        t0 = bzh_event(ctx);
-        hipEventRecord(t0, st);
-    }
     BZH_TRY(decode_index_check(ctx, idx, count)); // (before any arithmetic on the entries)
     BZH_TRY(decode_sync_check(ctx, idx, count, pts, npts));
     size_t first = 0, last = 0;
@@ -1693,13 +1688,7 @@ static int decode_range_device_impl(bzh_ctx *ctx, const void *d_in, size_t n, ui
     BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(last - first, 1), ctx->max_batch)));
     const int rc = decode_range_run(ctx, (const uint8_t *)d_in, n, in_byte_base, idx, count, off, len, (uint8_t *)d_out, cap, out_len, pts,
                                      npts);
-    if (ctx->profiling) {
-        t2 = bzh_event(ctx);
-        hipEventRecord(t2, st);
-        HIP_TRY(ctx, bzh_stream_wait(st));
-        ctx->dstats.ms_total = span_ms(t0, t2);
-    }
-    return rc;
+    return decode_call_end(ctx, call, rc);
     });
 }
 
@@ -1723,7 +1712,6 @@ static int decode_range_impl(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t
     if (ctx) stream_join(ctx);
     if (!ctx || (!in && n) || (!out && cap) || (!idx && count) || (!pts && npts) || !out_len) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
     *out_len = 0;
     BZH_TRY(decode_index_check(ctx, idx, count)); // (before any arithmetic on the entries)
     BZH_TRY(decode_sync_check(ctx, idx, count, pts, npts));
@@ -1740,16 +1728,13 @@ static int decode_range_impl(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t
     const bool covered = lo <= hi && in_byte_base <= lo && hi - in_byte_base <= n;
     const uint64_t base = covered ? lo : in_byte_base;
     const size_t un = covered ? (size_t)(hi - lo) : n;
-    const uint8_t *src = covered ? in + (lo - in_byte_base) : in;
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, un + 16));
-    if (want) BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, (size_t)want));
-    if (un) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, src, un, hipMemcpyHostToDevice, st));
+    BZH_TRY(decode_stage(ctx, covered ? in + (lo - in_byte_base) : in, un, (size_t)want));
     size_t got = 0;
     const int rc = decode_range_device_impl(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, off, len,
                                             want ? ctx->d_stage_out : nullptr, (size_t)want, &got);
     if (rc != BZH_OK) return rc;
-    if (got) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, got, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, bzh_stream_wait(st));
+    if (got) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, got, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
     *out_len = got;
     return BZH_OK;
     });
@@ -1783,8 +1768,7 @@ extern "C" int bzh_decode_scan(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64
     if (ctx) stream_join(ctx);
     if (!ctx || (!in && n) || !count || (max && (!bitpos || !kind))) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, n + 16));
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, ctx->stream));
+    BZH_TRY(decode_stage(ctx, in, n));
     std::vector<uint64_t> cands;
     BZH_TRY(decode_scan_run(ctx, ctx->d_stage_in, n, cands));
     *count = cands.size();

@@ -615,8 +615,9 @@ int crc_device(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t *crc_out); 
 int crc_blocks_device(bzh_ctx *ctx, const uint8_t *d_in, BlockDesc *d_blocks, uint32_t *d_acc, uint32_t nb, uint64_t maxlen);
 struct CrcTables;                                                     // crc_gf.h
 int crc_tables(bzh_ctx *ctx, const CrcTables **out);                  // rle1.hip: the context's device copy of the GF(2) tables
-// decode.hip: every block / footer magic of d_in[0..n) as (bit position << 1 | kind), ascending; then the chain walk and the
-// back of the decoder over that list (the arena laid out for min(candidates, max_batch) blocks)
+// decode.hip: every block / footer magic of d_in[0..n) as (bit position << 1 | kind), ascending; then the entropy stage and the
+// chain walk over that list (the arena laid out for min(candidates, max_batch) blocks).  The back of the decoder -- inverse BWT,
+// inverse RLE1, block CRCs -- is decode.hip's back_sizes / back_emit, which this and decode_range_run both call per batch.
 int decode_scan_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, std::vector<uint64_t> &cands);
 struct SyncBuild { // bzh_decode_index_sync*: the chain walk records a point every `interval` groups of every block on the chain
     uint32_t interval;
@@ -624,7 +625,8 @@ struct SyncBuild { // bzh_decode_index_sync*: the chain walk records a point eve
 };
 int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t cap, size_t *out_len, size_t *consumed,
                      const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index = nullptr, SyncBuild *sync = nullptr);
-// decode.hip: the blocks of a verified index that [off, off + len) touches, from d_in = the indexed input from byte in_byte_base on
+// decode.hip: the two checks of an index and its sync points as a whole, then the blocks of a verified index that
+// [off, off + len) touches, from d_in = the indexed input from byte in_byte_base on (windows and segments: decode_plan.h)
 int decode_index_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count); // BZH_E_ARG naming the entry that is ill formed
 int decode_sync_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts, size_t npts); // same, the point
 // (pts: sync points that have passed decode_sync_check; none: one wavefront a block)

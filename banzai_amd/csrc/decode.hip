@@ -20,6 +20,7 @@
 #include "common.h"
 #include "crc_gf.h"
 #include "decode_core.h"
+#include "decode_plan.h"
 
 // ---- scan ------------------------------------------------------------------------------------------------------
 // 16 start bytes a lane, all 8 shifts of each against both 48-bit magics.  Hits are rare: an atomic append (the host sorts).
@@ -224,12 +225,6 @@ __global__ void __launch_bounds__(64) decode_header_kernel(const uint8_t *in, ui
     }
     if (lane == 0) res[b] = r;
 }
-
-struct SegDesc {
-    uint32_t slot;      // of its block in the batch
-    int32_t from, to;   // points of the batch it runs between; -1: the header's state / the end of the block
-    uint32_t block_max; // bytes a block of its entry's level may hold
-};
 
 __device__ __forceinline__ BzdSyncState seg_state(const bzh_sync_point *p, uint64_t bit_base)
 {
@@ -601,8 +596,12 @@ struct DecWs { // carved from ctx->dec_ws (allocated on the first decode: an enc
     uint64_t *obase;   // [B]
     BlockDesc *desc;   // [B]
     uint32_t *scancnt; // [1]
-    uint32_t *wslots, *wlo, *whi, *bsize, *wacc, *wcrc, *magic; // [B] random access: clipped blocks, CRCs of expansions not written
+    // [B] the blocks of a batch that are not expanded whole (back_emit): cut by a range's edge, or not written at all.  wslots /
+    // wbase / wacc / wcrc are twins of slots / obase / crcacc / desc[].crc because a range's batch has whole and cut blocks in flight
+    // together: both walks and both CRC passes are queued before the one wait.
+    uint32_t *wslots, *wlo, *whi, *bsize, *wacc, *wcrc;
     int64_t *wbase;    // [B]
+    uint32_t *magic;   // [B] range_magic_kernel's verdicts
     uint32_t B, T;
 };
 
@@ -767,26 +766,130 @@ struct StageClock { // HIP events around the stages of a decode call, summed int
 };
 } // namespace
 
-// CRCs of the expansions of K blocks of the batch (slots hslots, hsizes decoded bytes each) from the bytes behind the inverse
-// BWT: a.tstate / a.tout are unrle_walk<false>'s, a.toff the host's sums (uploaded).  Queued; the caller waits, then reads hcrc.
-static int unrle_crc_run(bzh_ctx *ctx, const DecWs &w, UrArgs a, uint32_t Tn, uint32_t K, const uint32_t *hslots, const uint32_t *hsizes,
-                         uint32_t *hcrc)
+// ---- the back of the decoder: inverse BWT, inverse RLE1, block CRCs -- one place, in two steps, because the host has to know
+// every block's size before anything can be placed.  decode_chain_run and decode_range_run both go through it.
+struct BackBlock {
+    uint32_t slot, nblock; // in: its batch slot, the bytes of its last column
+    uint64_t size;         // back_sizes: its decoded bytes
+    bool bad_end;          // back_sizes: it ends in state 4, four equal bytes without a count (libbz2 refuses the block)
+    int64_t base;          // back_emit, in: out + base = where its first byte lies (before `out` when the window cuts its head)
+    uint32_t lo, hi;       // back_emit, in: the window wanted, in bytes of its own output
+    uint32_t crc;          // back_emit: of all its decoded bytes, whatever the window
+    bool whole() const { return lo == 0 && hi == size; }
+};
+struct Back { // a batch between its two steps; the vectors are scratch kept from batch to batch
+    UrArgs a;
+    uint32_t Tn;
+    hipEvent_t t_unrle; // the unrle stage's span opens in back_sizes; back_emit closes it, or the caller that stops at the sizes
+    std::vector<uint32_t> hslots, hout, hend, hoff, fq, eq, fslots, eslots, elo, ehi, esize, ecrc;
+    std::vector<uint64_t> fbase;
+    std::vector<int64_t> ebase;
+    std::vector<BlockDesc> fdesc;
+};
+
+// Step one.  The inverse BWT of batch slots [0, Bu), blocks of up to nmax_all bytes -- a chain's batch also holds candidates
+// off the chain that decoded cleanly, and the transform runs over slots, not over a list --, then the state maps and sizes of
+// the listed blocks.  One copy back, one wait; bk.hoff is the host image of toff.  Reports nothing: the callers word the errors.
+static int back_sizes(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk, uint32_t Bu, uint32_t nmax_all, std::vector<BackBlock> &blocks)
 {
-    if (K == 0) return BZH_OK;
     hipStream_t st = ctx->stream;
-    UwArgs wa{};
-    BZH_TRY(crc_tables(ctx, &wa.ct));
-    wa.bsize = w.bsize;
-    wa.acc = w.wacc;
-    wa.crc = w.wcrc;
-    a.slots = w.wslots;
-    HIP_TRY(ctx, hipMemcpyAsync(w.wslots, hslots, (size_t)K * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(w.bsize, hsizes, (size_t)K * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemsetAsync(w.wacc, 0, (size_t)K * 4, st));
-    unrle_crc<<<dim3(Tn, K), UR_THREADS, 0, st>>>(a, wa);
-    unrle_crc_finish<<<dim3(K), 64, 0, st>>>(wa);
+    const Batch &bt = ctx->bt;
+    const uint32_t K = (uint32_t)blocks.size();
+    uint32_t nmax = 1;
+    bk.hslots.clear();
+    for (const BackBlock &b : blocks) {
+        bk.hslots.push_back(b.slot);
+        nmax = std::max(nmax, b.nblock);
+    }
+    hipEvent_t t2 = clock.mark();
+    BZH_TRY(unbwt_run(ctx, Bu, nmax_all));
+    clock.span(2, t2);
+    bk.t_unrle = clock.mark();
+    bk.a = UrArgs{bt.mtfpos, bt.n, w.slots, bt.S, w.T, w.tmap, w.tout, w.tstate, w.endstate, w.toff, w.obase, nullptr};
+    bk.Tn = (nmax + UR_TILE - 1) / UR_TILE;
+    HIP_TRY(ctx, hipMemcpyAsync(w.slots, bk.hslots.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
+    unrle_maps<<<dim3(bk.Tn, K), UR_THREADS, 0, st>>>(bk.a);
+    unrle_walk<false><<<dim3(bk.Tn, K), UR_THREADS, 0, st>>>(bk.a);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(hcrc, w.wcrc, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+    bk.hout.resize((size_t)Bu * w.T);
+    bk.hend.resize(Bu);
+    HIP_TRY(ctx, hipMemcpyAsync(bk.hout.data(), w.tout, bk.hout.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(bk.hend.data(), w.endstate, (size_t)Bu * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, bzh_stream_wait(st));
+    bk.hoff.assign((size_t)Bu * w.T, 0);
+    for (BackBlock &b : blocks) {
+        b.size = bzp_tile_sums(bk.hout.data() + (size_t)b.slot * w.T, bk.hoff.data() + (size_t)b.slot * w.T, b.nblock, UR_TILE);
+        b.bad_end = bk.hend[b.slot] == 4;
+    }
+    return BZH_OK;
+}
+
+// Step two, over the list back_sizes filled (every block, same order), each with its base and window.  A window that is the
+// whole block: expanded where it belongs and checked there (unrle_walk<true>, crc_blocks_device).  A part of it: clipped
+// (unrle_walk_win), and its CRC folded from the bytes behind the inverse BWT with nothing more written (unrle_crc).  Empty: the
+// CRC alone -- the index build.  Only the kernels some block needs are launched.  crcs false: no CRC is taken.  One wait.
+static int back_emit(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk, uint8_t *d_out, bool crcs, std::vector<BackBlock> &blocks)
+{
+    hipStream_t st = ctx->stream;
+    auto up = [&](void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st); };
+    bk.fq.clear(), bk.fslots.clear(), bk.fbase.clear(), bk.fdesc.clear();
+    bk.eq.clear(), bk.eslots.clear(), bk.elo.clear(), bk.ehi.clear(), bk.esize.clear(), bk.ebase.clear();
+    uint64_t maxsize = 0;
+    uint32_t KW = 0; // whole blocks; cut blocks; behind them, where the clipped walk does not look, the blocks with nothing to write
+    for (int pass = 0; pass < (crcs ? 3 : 2); pass++)
+        for (uint32_t q = 0; q < blocks.size(); q++) {
+            const BackBlock &b = blocks[q];
+            if ((b.whole() ? 0 : b.lo < b.hi ? 1 : 2) != pass) continue;
+            if (pass == 0) {
+                bk.fq.push_back(q), bk.fslots.push_back(b.slot), bk.fbase.push_back((uint64_t)b.base);
+                bk.fdesc.push_back(BlockDesc{(uint64_t)b.base, b.size, 0, 0});
+                maxsize = std::max(maxsize, b.size);
+            } else {
+                bk.eq.push_back(q), bk.eslots.push_back(b.slot), bk.esize.push_back((uint32_t)b.size);
+                bk.elo.push_back(b.lo), bk.ehi.push_back(b.hi), bk.ebase.push_back(b.base);
+                KW += pass == 1;
+            }
+        }
+    const uint32_t KF = (uint32_t)bk.fq.size(), KE = (uint32_t)bk.eq.size();
+    UrArgs &a = bk.a, ae = bk.a;
+    a.out = ae.out = d_out;
+    ae.slots = w.wslots;
+    UwArgs wa{w.wlo, w.whi, w.wbase, w.bsize, w.wacc, w.wcrc, nullptr};
+    HIP_TRY(ctx, up(w.toff, bk.hoff.data(), bk.hoff.size() * 4));
+    if (KF) {
+        if (KF != blocks.size()) HIP_TRY(ctx, up(w.slots, bk.fslots.data(), (size_t)KF * 4)); // (else it holds them since back_sizes)
+        HIP_TRY(ctx, up(w.obase, bk.fbase.data(), (size_t)KF * 8));
+        unrle_walk<true><<<dim3(bk.Tn, KF), UR_THREADS, 0, st>>>(a);
+    }
+    if (KE) HIP_TRY(ctx, up(w.wslots, bk.eslots.data(), (size_t)KE * 4));
+    if (KW) {
+        HIP_TRY(ctx, up(w.wlo, bk.elo.data(), (size_t)KW * 4));
+        HIP_TRY(ctx, up(w.whi, bk.ehi.data(), (size_t)KW * 4));
+        HIP_TRY(ctx, up(w.wbase, bk.ebase.data(), (size_t)KW * 8));
+        unrle_walk_win<<<dim3(bk.Tn, KW), UR_THREADS, 0, st>>>(ae, wa);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    clock.span(3, bk.t_unrle);
+    hipEvent_t t4 = clock.mark();
+    if (crcs && KF) {
+        HIP_TRY(ctx, up(w.desc, bk.fdesc.data(), (size_t)KF * sizeof(BlockDesc)));
+        BZH_TRY(crc_blocks_device(ctx, d_out, w.desc, w.crcacc, KF, maxsize));
+        HIP_TRY(ctx, hipMemcpyAsync(bk.fdesc.data(), w.desc, (size_t)KF * sizeof(BlockDesc), hipMemcpyDeviceToHost, st));
+    }
+    bk.ecrc.resize(KE);
+    if (crcs && KE) {
+        BZH_TRY(crc_tables(ctx, &wa.ct));
+        HIP_TRY(ctx, up(w.bsize, bk.esize.data(), (size_t)KE * 4));
+        HIP_TRY(ctx, hipMemsetAsync(w.wacc, 0, (size_t)KE * 4, st));
+        unrle_crc<<<dim3(bk.Tn, KE), UR_THREADS, 0, st>>>(ae, wa);
+        unrle_crc_finish<<<dim3(KE), 64, 0, st>>>(wa);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(bk.ecrc.data(), w.wcrc, (size_t)KE * 4, hipMemcpyDeviceToHost, st));
+    }
+    clock.span(4, t4);
+    HIP_TRY(ctx, bzh_stream_wait(st));
+    for (uint32_t f = 0; crcs && f < KF; f++) blocks[bk.fq[f]].crc = bk.fdesc[f].crc;
+    for (uint32_t e = 0; crcs && e < KE; e++) blocks[bk.eq[e]].crc = bk.ecrc[e];
     return BZH_OK;
 }
 
@@ -849,9 +952,8 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
     bool finished = false, over = false;
     std::vector<BzdResult> res;
     std::vector<ChainItem> items;
-    std::vector<uint32_t> slots, hout, hoff, hend, hsize32, hcrc;
-    std::vector<uint64_t> hbase, hsize;
-    std::vector<BlockDesc> hdesc;
+    std::vector<BackBlock> blocks; // the blocks the chain met in a batch, in order
+    Back bk;
     while (!finished) {
         while (ci < nc && (cands[ci] >> 1) < pos) {
             ds.candidates_off_chain++;
@@ -878,7 +980,7 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
         HIP_TRY(ctx, bzh_stream_wait(st));
         // the chain through this batch
         items.clear();
-        slots.clear();
+        blocks.clear();
         uint32_t k = 0;
         for (; k < B && !finished; k++) {
             const uint64_t cpos = cands[ci + k] >> 1;
@@ -892,7 +994,7 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
             if (!(cands[ci + k] & 1ull)) {
                 if (r.nblock > 100000u * level) return data_error(BZD_K_FORMAT, cpos, "more bytes than the stream's block size");
                 items.push_back({false, k, r.crc, stream, block, cpos, r.end_bit, level});
-                slots.push_back(k);
+                blocks.push_back(BackBlock{k, r.nblock, 0, false, 0, 0, 0, 0});
                 block++;
                 ds.blocks++;
                 pos = r.end_bit;
@@ -913,90 +1015,30 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
         }
         ci += k;
         // the back of the decoder for the blocks on the chain
-        const uint32_t K = (uint32_t)slots.size();
-        if (K) {
-            const uint32_t Bu = slots.back() + 1;
-            uint32_t nmax_all = 1, nmax = 1;
+        if (!blocks.empty()) {
+            const uint32_t Bu = blocks.back().slot + 1;
+            uint32_t nmax_all = 1; // (the inverse BWT runs over slots: the clean candidates off the chain among them set its size too)
             for (uint32_t s = 0; s < Bu; s++)
                 if (!(cands[ci - k + s] & 1ull) && res[s].kind == BZD_OK) nmax_all = std::max(nmax_all, res[s].nblock);
-            for (uint32_t s : slots) nmax = std::max(nmax, res[s].nblock);
-            hipEvent_t e1 = mark();
-            BZH_TRY(unbwt_run(ctx, Bu, nmax_all));
-            span(2, e1);
-            hipEvent_t e2 = mark();
-            UrArgs a{};
-            a.x = bt.mtfpos;
-            a.n = bt.n;
-            a.slots = w.slots;
-            a.S = bt.S;
-            a.T = w.T;
-            a.tmap = w.tmap;
-            a.tout = w.tout;
-            a.tstate = w.tstate;
-            a.endstate = w.endstate;
-            a.toff = w.toff;
-            a.obase = w.obase;
-            a.out = d_out;
-            const uint32_t Tn = (nmax + UR_TILE - 1) / UR_TILE;
-            HIP_TRY(ctx, hipMemcpyAsync(w.slots, slots.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
-            unrle_maps<<<dim3(Tn, K), UR_THREADS, 0, st>>>(a);
-            unrle_walk<false><<<dim3(Tn, K), UR_THREADS, 0, st>>>(a);
-            HIP_TRY(ctx, hipGetLastError());
-            hout.resize((size_t)Bu * w.T);
-            hend.resize(Bu);
-            HIP_TRY(ctx, hipMemcpyAsync(hout.data(), w.tout, hout.size() * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipMemcpyAsync(hend.data(), w.endstate, (size_t)Bu * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, bzh_stream_wait(st));
-            hoff.assign((size_t)Bu * w.T, 0);
-            hbase.resize(K);
-            hsize.resize(K);
-            uint64_t maxsize = 0;
-            for (uint32_t q = 0; q < K; q++) {
-                const uint32_t s = slots[q], tn = (res[s].nblock + UR_TILE - 1) / UR_TILE;
-                uint64_t sz = 0;
-                for (uint32_t t = 0; t < tn; t++) {
-                    hoff[(size_t)s * w.T + t] = (uint32_t)sz;
-                    sz += hout[(size_t)s * w.T + t];
-                }
-                if (hend[s] == 4) { // libbz2 refuses the block; the state machine says where
+            BZH_TRY(back_sizes(ctx, w, clock, bk, Bu, nmax_all, blocks));
+            for (BackBlock &b : blocks) {
+                if (b.bad_end) { // libbz2 refuses the block; the state machine says where
                     for (const ChainItem &it : items)
-                        if (!it.footer && it.slot == s) {
+                        if (!it.footer && it.slot == b.slot) {
                             stream = it.stream;
                             block = it.block;
                             return data_error(BZD_K_FORMAT, it.bitpos, "the block ends in four equal bytes without a count");
                         }
                 }
-                hbase[q] = total_out;
-                hsize[q] = sz;
-                total_out += sz;
-                maxsize = std::max(maxsize, sz);
+                b.base = (int64_t)total_out;
+                total_out += b.size;
             }
             if (total_out > cap) over = true; // (sizing goes on: the caller learns the total)
-            if (!over) {
-                HIP_TRY(ctx, hipMemcpyAsync(w.toff, hoff.data(), hoff.size() * 4, hipMemcpyHostToDevice, st));
-                HIP_TRY(ctx, hipMemcpyAsync(w.obase, hbase.data(), (size_t)K * 8, hipMemcpyHostToDevice, st));
-                unrle_walk<true><<<dim3(Tn, K), UR_THREADS, 0, st>>>(a);
-                HIP_TRY(ctx, hipGetLastError());
-                span(3, e2);
-                hipEvent_t e3 = mark();
-                hdesc.resize(K);
-                for (uint32_t q = 0; q < K; q++) hdesc[q] = BlockDesc{hbase[q], hsize[q], 0, 0};
-                HIP_TRY(ctx, hipMemcpyAsync(w.desc, hdesc.data(), (size_t)K * sizeof(BlockDesc), hipMemcpyHostToDevice, st));
-                BZH_TRY(crc_blocks_device(ctx, d_out, w.desc, w.crcacc, K, maxsize));
-                HIP_TRY(ctx, hipMemcpyAsync(hdesc.data(), w.desc, (size_t)K * sizeof(BlockDesc), hipMemcpyDeviceToHost, st));
-                span(4, e3);
-                HIP_TRY(ctx, bzh_stream_wait(st));
-            } else if (index) { // the CRCs of the expansions, with nothing expanded
-                HIP_TRY(ctx, hipMemcpyAsync(w.toff, hoff.data(), hoff.size() * 4, hipMemcpyHostToDevice, st));
-                span(3, e2);
-                hipEvent_t e3 = mark();
-                hsize32.assign(hsize.begin(), hsize.end());
-                hcrc.resize(K);
-                BZH_TRY(unrle_crc_run(ctx, w, a, Tn, K, slots.data(), hsize32.data(), hcrc.data()));
-                span(4, e3);
-                HIP_TRY(ctx, bzh_stream_wait(st));
+            if (index || !over) { // an index: the CRCs of the expansions, with nothing expanded
+                for (BackBlock &b : blocks) b.lo = 0, b.hi = index ? 0 : (uint32_t)b.size;
+                BZH_TRY(back_emit(ctx, w, clock, bk, d_out, true, blocks));
             } else {
-                span(3, e2);
+                span(3, bk.t_unrle);
             }
         }
         // CRCs in chain order: every block's against its header, every stream's fold against its footer
@@ -1006,9 +1048,8 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
             stream = it.stream;
             block = it.block;
             if (!it.footer) {
-                if (!over && hdesc[q].crc != it.crc) return data_error(BZD_K_BLOCK_CRC, it.bitpos);
+                if ((index || !over) && blocks[q].crc != it.crc) return data_error(BZD_K_BLOCK_CRC, it.bitpos);
                 if (index) {
-                    if (hcrc[q] != it.crc) return data_error(BZD_K_BLOCK_CRC, it.bitpos);
                     if (sync) { // the points of the block's slot, numbered by the entry they belong to (the stream is idle here)
                         const uint32_t c = std::min(hptcnt[it.slot], sync_cap);
                         const size_t at = sync->pts.size();
@@ -1018,7 +1059,7 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
                                                    hipMemcpyDeviceToHost));
                         for (size_t p = at; p < at + c; p++) sync->pts[p].entry = (uint32_t)index->size();
                     }
-                    index->push_back({it.bitpos, it.end_bit, hbase[q], (uint32_t)hsize[q], it.crc, (uint32_t)it.stream, it.level});
+                    index->push_back({it.bitpos, it.end_bit, (uint64_t)blocks[q].base, (uint32_t)blocks[q].size, it.crc, (uint32_t)it.stream, it.level});
                 }
                 stream_crc = ((stream_crc << 1) | (stream_crc >> 31)) ^ it.crc;
                 q++;
@@ -1179,12 +1220,11 @@ int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_by
     std::vector<SegDesc> hseg;
     std::vector<BzdSegResult> hsres;
     std::vector<uint32_t> seg0; // [B + 1] first segment of every block of the batch
-    std::vector<uint64_t> hcand, fbase;
+    std::vector<uint64_t> hcand;
     std::vector<BzdResult> res;
-    std::vector<uint32_t> hmagic, all, hout, hend, hoff, fslots, eslots, elo, ehi, esize, ecrc;
-    std::vector<int64_t> ebase;
-    std::vector<BlockDesc> fdesc;
-    std::vector<size_t> fentry, eentry;
+    std::vector<uint32_t> hmagic;
+    std::vector<BackBlock> blocks;
+    Back bk;
     for (size_t e0 = first; e0 < last;) {
         const uint32_t B = (uint32_t)std::min<size_t>(Bmax, last - e0);
         // entropy stage: the entries are the candidates
@@ -1200,20 +1240,7 @@ int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_by
             auto by_entry = [](const bzh_sync_point &p, size_t e) { return (size_t)p.entry < e; };
             p0 = (size_t)(std::lower_bound(pts, pts + npts, e0, by_entry) - pts);
             p1 = (size_t)(std::lower_bound(pts + p0, pts + npts, e0 + B, by_entry) - pts);
-            hseg.clear();
-            seg0.assign(B + 1, 0);
-            size_t q = p0;
-            for (uint32_t k = 0; k < B; k++) {
-                seg0[k] = (uint32_t)hseg.size();
-                const uint32_t bmax = 100000u * idx[e0 + k].level;
-                int32_t prev = -1;
-                for (; q < p1 && pts[q].entry == e0 + k; q++) {
-                    hseg.push_back({k, prev, (int32_t)(q - p0), bmax});
-                    prev = (int32_t)(q - p0);
-                }
-                hseg.push_back({k, prev, -1, bmax});
-            }
-            seg0[B] = (uint32_t)hseg.size();
+            bzp_segments(idx, e0, B, pts, p0, p1, hseg, seg0);
             auto up = [](size_t v) { return (v + 255) / 256 * 256; };
             const size_t b_heads = up((size_t)B * sizeof(BzdHead)), b_pts = up((p1 - p0) * sizeof(bzh_sync_point)),
                          b_segs = up(hseg.size() * sizeof(SegDesc)), b_sres = up(hseg.size() * sizeof(BzdSegResult));
@@ -1277,108 +1304,25 @@ int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_by
             nmax = std::max(nmax, r.nblock);
         }
         ds.blocks += B;
-        hipEvent_t t2 = clock.mark();
-        BZH_TRY(unbwt_run(ctx, B, nmax));
-        clock.span(2, t2);
-        // sizes: as the chain takes them
-        hipEvent_t t3 = clock.mark();
-        UrArgs a{};
-        a.x = bt.mtfpos;
-        a.n = bt.n;
-        a.slots = w.slots;
-        a.S = bt.S;
-        a.T = w.T;
-        a.tmap = w.tmap;
-        a.tout = w.tout;
-        a.tstate = w.tstate;
-        a.endstate = w.endstate;
-        a.toff = w.toff;
-        a.obase = w.obase;
-        a.out = d_out;
-        const uint32_t Tn = (nmax + UR_TILE - 1) / UR_TILE;
-        all.resize(B);
-        for (uint32_t k = 0; k < B; k++) all[k] = k;
-        HIP_TRY(ctx, hipMemcpyAsync(w.slots, all.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
-        unrle_maps<<<dim3(Tn, B), UR_THREADS, 0, st>>>(a);
-        unrle_walk<false><<<dim3(Tn, B), UR_THREADS, 0, st>>>(a);
-        HIP_TRY(ctx, hipGetLastError());
-        hout.resize((size_t)B * w.T);
-        hend.resize(B);
-        HIP_TRY(ctx, hipMemcpyAsync(hout.data(), w.tout, hout.size() * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(hend.data(), w.endstate, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, bzh_stream_wait(st));
-        hoff.assign((size_t)B * w.T, 0);
-        fslots.clear(), fbase.clear(), fdesc.clear(), fentry.clear();
-        eslots.clear(), elo.clear(), ehi.clear(), esize.clear(), ebase.clear(), eentry.clear();
-        uint64_t maxsize = 0;
+        blocks.clear();
+        for (uint32_t k = 0; k < B; k++) blocks.push_back(BackBlock{k, res[k].nblock, 0, false, 0, 0, 0, 0});
+        BZH_TRY(back_sizes(ctx, w, clock, bk, B, nmax, blocks));
         for (uint32_t k = 0; k < B; k++) {
             at = e0 + k;
             const bzh_index_entry &e = idx[at];
-            const uint32_t tn = (res[k].nblock + UR_TILE - 1) / UR_TILE;
-            uint64_t sz = 0;
-            for (uint32_t t = 0; t < tn; t++) {
-                hoff[(size_t)k * w.T + t] = (uint32_t)sz;
-                sz += hout[(size_t)k * w.T + t];
-            }
-            if (hend[k] == 4) return mismatch("the block ends in four equal bytes without a count");
-            if (sz != e.out_len) return mismatch("it decodes to another size than out_len");
+            BackBlock &b = blocks[k];
+            if (b.bad_end) return mismatch("the block ends in four equal bytes without a count");
+            if (b.size != e.out_len) return mismatch("it decodes to another size than out_len");
             // the window of the range inside this block; a block wholly inside is expanded where it belongs and checked there
-            const uint64_t lo = std::max(off, e.out_off) - e.out_off, hi = std::min(end, e.out_off + e.out_len) - e.out_off;
-            if (lo == 0 && hi == e.out_len) {
-                fslots.push_back(k);
-                fbase.push_back(e.out_off - off);
-                fdesc.push_back(BlockDesc{e.out_off - off, e.out_len, 0, 0});
-                fentry.push_back(at);
-                maxsize = std::max<uint64_t>(maxsize, e.out_len);
-            } else {
-                eslots.push_back(k);
-                elo.push_back((uint32_t)lo);
-                ehi.push_back((uint32_t)hi);
-                esize.push_back(e.out_len);
-                ebase.push_back((int64_t)e.out_off - (int64_t)off);
-                eentry.push_back(at);
-            }
+            bzp_window(e.out_off, e.out_len, off, end, &b.lo, &b.hi);
+            b.base = (int64_t)e.out_off - (int64_t)off;
         }
-        const uint32_t KF = (uint32_t)fslots.size(), KE = (uint32_t)eslots.size();
-        HIP_TRY(ctx, hipMemcpyAsync(w.toff, hoff.data(), hoff.size() * 4, hipMemcpyHostToDevice, st));
-        UwArgs wa{};
-        if (KF) {
-            HIP_TRY(ctx, hipMemcpyAsync(w.slots, fslots.data(), (size_t)KF * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(w.obase, fbase.data(), (size_t)KF * 8, hipMemcpyHostToDevice, st));
-            unrle_walk<true><<<dim3(Tn, KF), UR_THREADS, 0, st>>>(a);
-        }
-        if (KE) { // the blocks the range cuts: clipped, and (below) checked without their expansion
-            wa.wlo = w.wlo;
-            wa.whi = w.whi;
-            wa.wbase = w.wbase;
-            UrArgs ae = a;
-            ae.slots = w.wslots;
-            HIP_TRY(ctx, hipMemcpyAsync(w.wslots, eslots.data(), (size_t)KE * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(w.wlo, elo.data(), (size_t)KE * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(w.whi, ehi.data(), (size_t)KE * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(w.wbase, ebase.data(), (size_t)KE * 8, hipMemcpyHostToDevice, st));
-            unrle_walk_win<<<dim3(Tn, KE), UR_THREADS, 0, st>>>(ae, wa);
-        }
-        HIP_TRY(ctx, hipGetLastError());
-        clock.span(3, t3);
-        hipEvent_t t4 = clock.mark();
-        if (KF) {
-            HIP_TRY(ctx, hipMemcpyAsync(w.desc, fdesc.data(), (size_t)KF * sizeof(BlockDesc), hipMemcpyHostToDevice, st));
-            BZH_TRY(crc_blocks_device(ctx, d_out, w.desc, w.crcacc, KF, maxsize));
-            HIP_TRY(ctx, hipMemcpyAsync(fdesc.data(), w.desc, (size_t)KF * sizeof(BlockDesc), hipMemcpyDeviceToHost, st));
-        }
-        ecrc.resize(KE);
-        BZH_TRY(unrle_crc_run(ctx, w, a, Tn, KE, eslots.data(), esize.data(), ecrc.data()));
-        clock.span(4, t4);
-        HIP_TRY(ctx, bzh_stream_wait(st));
-        for (uint32_t q = 0; q < KF; q++)
-            if (fdesc[q].crc != idx[fentry[q]].crc) {
-                at = fentry[q];
-                return mismatch(kind_name(BZD_K_BLOCK_CRC));
-            }
-        for (uint32_t q = 0; q < KE; q++)
-            if (ecrc[q] != idx[eentry[q]].crc) {
-                at = eentry[q];
+        BZH_TRY(back_emit(ctx, w, clock, bk, d_out, true, blocks));
+        for (int cut = 0; cut < 2; cut++) // (the whole blocks first)
+            for (uint32_t k = 0; k < B; k++) {
+                const BackBlock &b = blocks[k];
+                if (b.whole() != (cut == 0) || b.crc == idx[e0 + k].crc) continue;
+                at = e0 + k;
                 return mismatch(kind_name(BZD_K_BLOCK_CRC));
             }
         e0 += B;
