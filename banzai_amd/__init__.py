@@ -33,7 +33,7 @@ import numpy as np
 
 from . import _native
 
-__all__ = ["encode", "encode_many", "encode_file", "decompress", "decode", "build_index", "decompress_range", "BlockIndex",
+__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "build_index", "decompress_range", "BlockIndex",
            "IndexedReader", "build_sync_index", "SyncIndex", "encode_indexed", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
@@ -197,6 +197,43 @@ def decompress(data, device=0):
     except TypeError:
         raise TypeError(f"decompress takes a bytes-like object, not {type(data).__name__}") from None
     return _ctx(9, device).decode(view)
+
+
+def decompress_many(inputs, device=0, errors="raise"):
+    """Decode every item of `inputs` (bytes-like; each one or more complete bzip2 streams, as decompress takes) -> [bytes], item
+    k decoded exactly as decompress(item k) would, in one pass on the GPU per group of inputs (bzh_decode_many): one scan, and
+    batches that take the blocks of many inputs together.  A damaged item does not touch the others.  errors="raise": the
+    first failed item raises BzhError naming it; errors="return": the BzhError instance stands in that item's place.  Groups
+    keep a call's inputs below MANY_GROUP_LIMIT bytes, as encode_many's do."""
+    if errors not in ("raise", "return"):
+        raise ValueError('errors must be "raise" or "return"')
+    views = [_bytes_view(x, "decompress_many") for x in inputs]
+    if not views:
+        return []
+    ctx = _ctx(9, device)
+    out, group, size = [], [], 0
+
+    def run(group):
+        res, status, _ = ctx.decode_many(group, with_status=True)
+        text, first = ctx.last_error(), True
+        for k, (r, st) in enumerate(zip(res, status)):
+            if st != 0:  # (the library words the first failure of a call; the others carry their status)
+                err = BzhError(st, text if first else f"decode: input {k} failed")
+                first = False
+                if errors == "raise":
+                    err.args = (f"{err.args[0]} (item {len(out) + k} of decompress_many)",)
+                    raise err
+                res[k] = err
+        out.extend(res)
+
+    for v in views:
+        if group and size + len(v) + 1 > MANY_GROUP_LIMIT:
+            run(group)
+            group, size = [], 0
+        group.append(v)
+        size += len(v) + 1
+    run(group)
+    return out
 
 
 def decode(reader, writer, device=0):

@@ -53,6 +53,15 @@ class DecodeStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DecodeManyStats(ctypes.Structure):
+    """bzh_decode_many_stats"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("inputs", "inputs_failed", "streams", "blocks", "blocks_small", "batches")] + \
+               [("ms_unbwt_small", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class IndexEntry(ctypes.Structure):
     """bzh_index_entry: one decoded block of an indexed input"""
     _fields_ = [("bit_pos", ctypes.c_uint64), ("end_bit", ctypes.c_uint64), ("out_off", ctypes.c_uint64),
@@ -114,6 +123,12 @@ SIGNATURES = {
     "bzh_decode_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                          ctypes.c_size_t, szp, szp]),
     "bzh_get_decode_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DecodeStats)]),
+    "bzh_decode_many_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, szp, szp, ctypes.c_size_t,
+                                              ctypes.c_void_p, ctypes.c_size_t, szp, szp, ctypes.POINTER(ctypes.c_int), szp]),
+    "bzh_decode_many": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(u8p), szp, ctypes.c_size_t, u8p, ctypes.c_size_t, szp, szp,
+                                       ctypes.POINTER(ctypes.c_int), szp]),
+    "bzh_decode_many_small_max": (ctypes.c_size_t, []),
+    "bzh_get_decode_many_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DecodeManyStats)]),
     "bzh_decode_index": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, idxp, ctypes.c_size_t, szp, u64p, szp]),
     "bzh_decode_index_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, idxp, ctypes.c_size_t, szp,
                                                u64p, szp]),
@@ -192,6 +207,11 @@ def encode_many_bound(level, lens):
     """bzh_encode_many_bound: upper bound of the output of bzh_encode_many for these input lengths (0 for a bad level)"""
     lens = np.ascontiguousarray(lens, dtype=np.uint64)
     return int(lib().bzh_encode_many_bound(level, ptr(lens, szp) if lens.size else None, lens.size))
+
+
+def decode_many_small_max():
+    """bzh_decode_many_small_max (pure host): the largest block, in bytes of its last column, the LDS inverse BWT takes"""
+    return int(lib().bzh_decode_many_small_max())
 
 
 def encode_index_bound(level, n, interval):
@@ -513,6 +533,60 @@ class Context:
         self.check(lib().bzh_decode_device(self._h, ctypes.c_void_p(d_in), n, ctypes.c_void_p(d_out), cap, ctypes.byref(olen),
                                            ctypes.byref(used)))
         return int(olen.value), int(used.value)
+
+    def decode_many_raw(self, items, cap):
+        """one bzh_decode_many call into a buffer of `cap` bytes -> (status of the call, buffer, out_offs, out_lens, statuses,
+        consumed), the last four as lists; the buffer is None unless the call returned 0"""
+        arrs = [np.frombuffer(x, dtype=np.uint8) for x in items]
+        count = len(arrs)
+        keep = [np.ascontiguousarray(a) if a.size else np.zeros(1, np.uint8) for a in arrs]
+        lens = np.array([a.size for a in arrs], dtype=np.uint64)
+        ins = (u8p * max(count, 1))(*[ptr(a) for a in keep])
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        offs, olens, used = (np.zeros(max(count, 1), dtype=np.uint64) for _ in range(3))
+        status = np.zeros(max(count, 1), dtype=np.int32)
+        st = lib().bzh_decode_many(self._h, ins, ptr(lens, szp) if count else None, count, ptr(out) if cap else None, cap, ptr(offs, szp),
+                                   ptr(olens, szp), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ptr(used, szp))
+        return (st, out if st == 0 else None, offs[:count].tolist(), olens[:count].tolist(), status[:count].tolist(),
+                used[:count].tolist())
+
+    def decode_many(self, items, with_status=False):
+        """bzh_decode_many: every item decoded as bzh_decode would decode it alone, in one pass -> [bytes], with None where an
+        input failed; with_status: (that list, [status], [input bytes consumed]).  The output is sized by a first guess, then by
+        one retry with the size BZH_E_CAP reports."""
+        items = list(items)
+        cap = 6 * sum(len(x) for x in items) + (1 << 16)
+        st, out, offs, olens, status, used = self.decode_many_raw(items, cap)
+        if st == -4:
+            st, out, offs, olens, status, used = self.decode_many_raw(items, offs[-1] + olens[-1])
+        self.check(st)
+        res = [out[o:o + n].tobytes() if s == 0 else None for o, n, s in zip(offs, olens, status)]
+        return (res, status, used) if with_status else res
+
+    def decode_many_device(self, d_in, n, offs, lens, d_out, cap):
+        """bzh_decode_many_device on integer device addresses -> (status of the call, out_offs, out_lens, statuses, consumed).
+        BZH_E_CAP (-4) is handed back, not raised: the arrays are set then too."""
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        if offs.size != lens.size:
+            raise ValueError("as many offsets as lengths")
+        count = offs.size
+        ooffs, olens, used = (np.zeros(max(count, 1), dtype=np.uint64) for _ in range(3))
+        status = np.zeros(max(count, 1), dtype=np.int32)
+        st = lib().bzh_decode_many_device(self._h, ctypes.c_void_p(d_in), n, ptr(offs, szp) if count else None,
+                                          ptr(lens, szp) if count else None, count, ctypes.c_void_p(d_out), cap, ptr(ooffs, szp),
+                                          ptr(olens, szp), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ptr(used, szp))
+        if st not in (0, -4):
+            self.check(st)
+        return st, ooffs[:count].tolist(), olens[:count].tolist(), status[:count].tolist(), used[:count].tolist()
+
+    def last_error(self):
+        return lib().bzh_last_error(self._h).decode()
+
+    def decode_many_stats(self):
+        s = DecodeManyStats()
+        self.check(lib().bzh_get_decode_many_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
 
     def decode_index(self, data):
         """bzh_decode_index: the verified block index of the stream(s) in `data` -> (entries as a structured array of

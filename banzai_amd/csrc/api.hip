@@ -1762,6 +1762,89 @@ extern "C" int bzh_get_decode_stats(const bzh_ctx *ctx, bzh_decode_stats *out)
     });
 }
 
+// ---- many inputs (decode.hip's decode_many_run): one scan of the whole buffer, the arena for a batch of its candidates
+extern "C" int bzh_decode_many_device(bzh_ctx *ctx, const void *d_in, size_t n, const size_t *in_offs, const size_t *in_lens, size_t count,
+                                      void *d_out, size_t cap, size_t *out_offs, size_t *out_lens, int *status, size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n) || (!d_out && cap)) return BZH_E_ARG;
+    if (count && (!in_offs || !in_lens || !out_offs || !out_lens || !status)) {
+        bzh_set_error(ctx, "decode many: a null array for %zu inputs", count);
+        return BZH_E_ARG;
+    }
+    if (count > 0x7FFFFFFFull) {
+        bzh_set_error(ctx, "decode many: %zu inputs are beyond one call", count);
+        return BZH_E_ARG;
+    }
+    size_t end = 0; // of the slices so far
+    for (size_t k = 0; k < count; k++) {
+        if (in_offs[k] < end || in_offs[k] > n || in_lens[k] > n - in_offs[k]) {
+            bzh_set_error(ctx, "decode many: input %zu is bytes [%zu, +%zu): %s", k, in_offs[k], in_lens[k],
+                          in_offs[k] < end ? "the slices must ascend and must not overlap" : "past the end of the buffer");
+            return BZH_E_ARG;
+        }
+        end = in_offs[k] + in_lens[k];
+    }
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
+    memset(&ctx->mstats, 0, sizeof ctx->mstats);
+    if (count == 0) return decode_call_end(ctx, call, BZH_OK);
+    std::vector<uint64_t> cands;
+    BZH_TRY(decode_call_scan(ctx, call, d_in, n, cands));
+    const int rc = decode_many_run(ctx, (const uint8_t *)d_in, n, in_offs, in_lens, count, (uint8_t *)d_out, cap, out_offs, out_lens, status,
+                                   consumed, cands);
+    return decode_call_end(ctx, call, rc);
+    });
+}
+
+extern "C" int bzh_decode_many(bzh_ctx *ctx, const uint8_t *const *ins, const size_t *lens, size_t count, uint8_t *out, size_t cap,
+                               size_t *out_offs, size_t *out_lens, int *status, size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!out && cap)) return BZH_E_ARG;
+    if (count && (!ins || !lens || !out_offs || !out_lens || !status)) {
+        bzh_set_error(ctx, "decode many: a null array for %zu inputs", count);
+        return BZH_E_ARG;
+    }
+    size_t total = 0;
+    std::vector<size_t> offs(count);
+    for (size_t k = 0; k < count; k++) {
+        if (!ins[k] && lens[k]) {
+            bzh_set_error(ctx, "decode many: input %zu is null with %zu bytes claimed", k, lens[k]);
+            return BZH_E_ARG;
+        }
+        offs[k] = total;
+        total += lens[k];
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, total + 16));
+    if (cap) BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, cap));
+    if (total) { // all inputs in one copy, back to back
+        ctx->many_pack.resize(total);
+        for (size_t k = 0; k < count; k++)
+            if (lens[k]) memcpy(ctx->many_pack.data() + offs[k], ins[k], lens[k]);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, ctx->many_pack.data(), total, hipMemcpyHostToDevice, ctx->stream));
+    }
+    BZH_TRY(bzh_decode_many_device(ctx, ctx->d_stage_in, total, offs.data(), lens, count, cap ? ctx->d_stage_out : nullptr, cap, out_offs,
+                                   out_lens, status, consumed));
+    const size_t len = count ? out_offs[count - 1] + out_lens[count - 1] : 0;
+    if (len) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, len, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+    return BZH_OK;
+    });
+}
+
+extern "C" int bzh_get_decode_many_stats(const bzh_ctx *ctx, bzh_decode_many_stats *out)
+{
+    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
+    if (!ctx || !out) return BZH_E_ARG;
+    *out = ctx->mstats;
+    return BZH_OK;
+    });
+}
+
 extern "C" int bzh_decode_scan(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t *bitpos, uint8_t *kind, size_t max, size_t *count)
 {
     return bzh_guard(ctx, [&]() -> int {

@@ -307,6 +307,7 @@ struct bzh_ctx {
     uint8_t *sync_ws = nullptr;   // sync points (allocated on first use): the recorder's slots, or a range's headers, points and segments
     size_t sync_ws_size = 0;
     bzh_decode_stats dstats{};
+    bzh_decode_many_stats mstats{}; // of the last bzh_decode_many* call
     // streaming encode (bzh_stream_*)
     struct Stream {
         bool active = false, header_done = false;
@@ -633,6 +634,14 @@ int decode_sync_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count, co
 int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
                      uint64_t off, uint64_t len, uint8_t *d_out, size_t cap, size_t *out_len, const bzh_sync_point *pts = nullptr,
                      size_t npts = 0);
+// decode.hip: many inputs, one chain each, batches across them (the walk itself: decode_many_plan.h).  The slices have been checked.
+int decode_many_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const size_t *in_offs, const size_t *in_lens, size_t count, uint8_t *d_out,
+                    size_t cap, size_t *out_offs, size_t *out_lens, int *status, size_t *consumed, const std::vector<uint64_t> &cands);
+// unbwt_small.hip: the inverse BWT in LDS of the K listed batch slots, blocks of at most bzh_decode_many_small_max() bytes each
+// (bt.bwt / bt.n / bt.ptr -> bt.mtfpos, as unbwt_run); its switch; the first four bytes of many slices in one launch
+int unbwt_small_run(bzh_ctx *ctx, const uint32_t *d_slots, uint32_t K);
+bool unbwt_small_enabled();
+int many_heads_run(bzh_ctx *ctx, const uint8_t *d_in, const uint64_t *d_offs, const uint64_t *d_lens, uint32_t count, uint32_t *d_heads);
 
 // sync_emit.hip: the index of the stream being encoded (bzh_encode_index*).  encode_range hands every batch over once its bits
 // are packed and before its arena is reused: the entries of its blocks, and a sync point every `interval` groups (0: none)

@@ -21,6 +21,7 @@
 #include "crc_gf.h"
 #include "decode_core.h"
 #include "decode_plan.h"
+#include "decode_many_plan.h"
 
 // ---- scan ------------------------------------------------------------------------------------------------------
 // 16 start bytes a lane, all 8 shifts of each against both 48-bit magics.  Hits are rare: an atomic append (the host sorts).
@@ -602,6 +603,7 @@ struct DecWs { // carved from ctx->dec_ws (allocated on the first decode: an enc
     uint32_t *wslots, *wlo, *whi, *bsize, *wacc, *wcrc;
     int64_t *wbase;    // [B]
     uint32_t *magic;   // [B] range_magic_kernel's verdicts
+    uint32_t *small;   // [B] bzh_decode_many: the batch slots whose blocks the LDS inverse BWT takes
     uint32_t B, T;
 };
 
@@ -609,7 +611,7 @@ static int dec_ws(bzh_ctx *ctx, DecWs &w)
 {
     const size_t B = ctx->max_batch, T = ctx->S / UR_TILE;
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t need = up(B * 8) + up(B * sizeof(BzdResult)) + 4 * up(B * T * 4) + 10 * up(B * 4) + 2 * up(B * 8) + up(B * sizeof(BlockDesc)) + 256;
+    const size_t need = up(B * 8) + up(B * sizeof(BzdResult)) + 4 * up(B * T * 4) + 11 * up(B * 4) + 2 * up(B * 8) + up(B * sizeof(BlockDesc)) + 256;
     if (!ctx->dec_ws || ctx->dec_ws_size < need) {
         if (ctx->dec_ws) hipFree(ctx->dec_ws);
         ctx->dec_ws = nullptr;
@@ -645,6 +647,7 @@ static int dec_ws(bzh_ctx *ctx, DecWs &w)
     take(w.wcrc, B * 4);
     take(w.magic, B * 4);
     take(w.wbase, B * 8);
+    take(w.small, B * 4);
     w.B = (uint32_t)B;
     w.T = (uint32_t)T;
     return BZH_OK;
@@ -756,7 +759,7 @@ struct StageClock { // HIP events around the stages of a decode call, summed int
     void collect()
     {
         bzh_decode_stats &ds = ctx->dstats;
-        double *dst[5] = {&ds.ms_scan, &ds.ms_entropy, &ds.ms_unbwt, &ds.ms_unrle, &ds.ms_crc};
+        double *dst[6] = {&ds.ms_scan, &ds.ms_entropy, &ds.ms_unbwt, &ds.ms_unrle, &ds.ms_crc, &ctx->mstats.ms_unbwt_small};
         for (auto &s : spans) {
             float t = 0;
             if (hipEventElapsedTime(&t, s.a, s.b) == hipSuccess) *dst[s.stage] += t;
@@ -781,7 +784,7 @@ struct Back { // a batch between its two steps; the vectors are scratch kept fro
     UrArgs a;
     uint32_t Tn;
     hipEvent_t t_unrle; // the unrle stage's span opens in back_sizes; back_emit closes it, or the caller that stops at the sizes
-    std::vector<uint32_t> hslots, hout, hend, hoff, fq, eq, fslots, eslots, elo, ehi, esize, ecrc;
+    std::vector<uint32_t> hslots, hout, hend, hoff, fq, eq, fslots, eslots, elo, ehi, esize, ecrc, hsmall;
     std::vector<uint64_t> fbase;
     std::vector<int64_t> ebase;
     std::vector<BlockDesc> fdesc;
@@ -790,7 +793,16 @@ struct Back { // a batch between its two steps; the vectors are scratch kept fro
 // Step one.  The inverse BWT of batch slots [0, Bu), blocks of up to nmax_all bytes -- a chain's batch also holds candidates
 // off the chain that decoded cleanly, and the transform runs over slots, not over a list --, then the state maps and sizes of
 // the listed blocks.  One copy back, one wait; bk.hoff is the host image of toff.  Reports nothing: the callers word the errors.
-static int back_sizes(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk, uint32_t Bu, uint32_t nmax_all, std::vector<BackBlock> &blocks)
+// split (bzh_decode_many only): the listed blocks of at most split->small_max bytes go through the LDS transform, which takes a
+// list and so leaves the candidates off the chain alone; unbwt_run then runs over slots [0, split->Bl) only -- up to the last
+// listed block above the bound, sized by split->nmax_l -- and first: where both write a small block's slot they write the same.
+struct BackSplit {
+    uint32_t small_max;
+    uint32_t Bl, nmax_l; // Bl 0: no listed block above the bound
+    uint32_t nsmall;     // out: blocks the LDS transform took
+};
+static int back_sizes(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk, uint32_t Bu, uint32_t nmax_all, std::vector<BackBlock> &blocks,
+                      BackSplit *split = nullptr)
 {
     hipStream_t st = ctx->stream;
     const Batch &bt = ctx->bt;
@@ -802,7 +814,21 @@ static int back_sizes(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk,
         nmax = std::max(nmax, b.nblock);
     }
     hipEvent_t t2 = clock.mark();
-    BZH_TRY(unbwt_run(ctx, Bu, nmax_all));
+    if (!split) {
+        BZH_TRY(unbwt_run(ctx, Bu, nmax_all));
+    } else {
+        if (split->Bl) BZH_TRY(unbwt_run(ctx, split->Bl, split->nmax_l));
+        bk.hsmall.clear();
+        for (const BackBlock &b : blocks)
+            if (b.nblock <= split->small_max) bk.hsmall.push_back(b.slot);
+        split->nsmall = (uint32_t)bk.hsmall.size();
+        if (split->nsmall) {
+            HIP_TRY(ctx, hipMemcpyAsync(w.small, bk.hsmall.data(), (size_t)split->nsmall * 4, hipMemcpyHostToDevice, st));
+            hipEvent_t t5 = clock.mark();
+            BZH_TRY(unbwt_small_run(ctx, w.small, split->nsmall));
+            clock.span(5, t5);
+        }
+    }
     clock.span(2, t2);
     bk.t_unrle = clock.mark();
     bk.a = UrArgs{bt.mtfpos, bt.n, w.slots, bt.S, w.T, w.tmap, w.tout, w.tstate, w.endstate, w.toff, w.obase, nullptr};
@@ -1078,6 +1104,153 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
     *out_len = (size_t)total_out;
     if (over && !index) {
         bzh_set_error(ctx, "decode: the output needs %llu bytes, the buffer holds %zu", (unsigned long long)total_out, cap);
+        return BZH_E_CAP;
+    }
+    return BZH_OK;
+}
+
+// ================================================================================================================
+// Many inputs (bzh_decode_many*): one scan, one chain per input, batches across the inputs.  The walk is decode_many_plan.h's;
+// this feeds it the entropy stage's results batch by batch and runs the back of the decoder for the blocks it met.
+// ================================================================================================================
+static_assert(BZM_OK == BZH_OK && BZM_E_ARG == BZH_E_ARG && BZM_E_DATA == BZH_E_DATA, "decode_many_plan.h names bzh_status values");
+
+int decode_many_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const size_t *in_offs, const size_t *in_lens, size_t count, uint8_t *d_out,
+                    size_t cap, size_t *out_offs, size_t *out_lens, int *status, size_t *consumed, const std::vector<uint64_t> &cands)
+{
+    static_assert(sizeof(size_t) == 8, "the slices go to the device as 64-bit words");
+    hipStream_t st = ctx->stream;
+    Batch &bt = ctx->bt;
+    bzh_decode_stats &ds = ctx->dstats;
+    bzh_decode_many_stats &ms = ctx->mstats;
+    DecWs w;
+    BZH_TRY(dec_ws(ctx, w));
+    if (w.T > UR_THREADS) {
+        bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
+        return BZH_E_STATE;
+    }
+    StageClock clock{ctx, {}};
+    // the stream headers of all inputs: one launch, one copy back
+    std::vector<BzmInput> ins(count);
+    {
+        auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+        BZH_TRY(sync_ws_reserve(ctx, 2 * up(count * 8) + up(count * 4))); // (no sync points in this call: the workspace is free)
+        uint64_t *d_offs = reinterpret_cast<uint64_t *>(ctx->sync_ws), *d_lens = reinterpret_cast<uint64_t *>(ctx->sync_ws + up(count * 8));
+        uint32_t *d_heads = reinterpret_cast<uint32_t *>(ctx->sync_ws + 2 * up(count * 8));
+        std::vector<uint32_t> heads(count);
+        HIP_TRY(ctx, hipMemcpyAsync(d_offs, in_offs, count * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d_lens, in_lens, count * 8, hipMemcpyHostToDevice, st));
+        BZH_TRY(many_heads_run(ctx, d_in, d_offs, d_lens, (uint32_t)count, d_heads));
+        HIP_TRY(ctx, hipMemcpyAsync(heads.data(), d_heads, count * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, bzh_stream_wait(st));
+        for (size_t k = 0; k < count; k++) {
+            ins[k].off = in_offs[k];
+            ins[k].len = in_lens[k];
+            for (int j = 0; j < 4; j++) ins[k].head[j] = (uint8_t)(heads[k] >> (8 * j));
+        }
+    }
+    BzmWalk walk;
+    walk.cands = cands.data();
+    walk.nc = cands.size();
+    walk.in = ins.data();
+    walk.count = count;
+    walk.ctx_level = ctx->level;
+    walk.start();
+    const uint32_t Bmax = (uint32_t)std::min<size_t>(ctx->max_batch, ctx->arena_blocks);
+    const bool small_on = unbwt_small_enabled();
+    const uint32_t small_max = (uint32_t)bzh_decode_many_small_max();
+    std::vector<BzdResult> res;
+    std::vector<BackBlock> blocks;
+    std::vector<BzmItem *> of; // the item of every listed block
+    Back bk;
+    size_t first;
+    uint32_t B;
+    while (walk.next_batch(Bmax, &first, &B)) {
+        hipEvent_t e0 = clock.mark();
+        HIP_TRY(ctx, hipMemcpyAsync(w.cand, cands.data() + first, (size_t)B * 8, hipMemcpyHostToDevice, st));
+        decode_block_kernel<<<dim3(B), 64, 0, st>>>(d_in, n, w.cand, bt, w.res, 100000u * (uint32_t)ctx->level);
+        HIP_TRY(ctx, hipGetLastError());
+        clock.span(1, e0);
+        res.resize(B);
+        HIP_TRY(ctx, hipMemcpyAsync(res.data(), w.res, (size_t)B * sizeof(BzdResult), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, bzh_stream_wait(st));
+        ms.batches++;
+        walk.feed(res.data());
+        blocks.clear();
+        of.clear();
+        for (BzmItem &it : walk.items)
+            if (!it.footer && !it.dead) {
+                blocks.push_back(BackBlock{it.slot, it.nblock, 0, false, 0, 0, 0, 0});
+                of.push_back(&it);
+            }
+        if (!blocks.empty()) {
+            // (the inverse BWT runs over slots: the clean candidates off the chain among them set its size too)
+            auto nmax_upto = [&](uint32_t Bu) {
+                uint32_t m = 1;
+                for (uint32_t s = 0; s < Bu; s++)
+                    if (!(cands[first + s] & 1ull) && res[s].kind == BZD_OK) m = std::max(m, res[s].nblock);
+                return m;
+            };
+            const uint32_t Bu = blocks.back().slot + 1;
+            if (small_on) {
+                BackSplit split{small_max, 0, 1, 0};
+                for (const BackBlock &b : blocks)
+                    if (b.nblock > small_max) split.Bl = b.slot + 1;
+                split.nmax_l = nmax_upto(split.Bl);
+                BZH_TRY(back_sizes(ctx, w, clock, bk, Bu, 0, blocks, &split));
+                ms.blocks_small += split.nsmall;
+            } else {
+                BZH_TRY(back_sizes(ctx, w, clock, bk, Bu, nmax_upto(Bu), blocks));
+            }
+            for (size_t q = 0; q < blocks.size(); q++) {
+                of[q]->size = blocks[q].size;
+                of[q]->bad_end = blocks[q].bad_end;
+            }
+        }
+        walk.place(cap);
+        if (!blocks.empty()) {
+            if (!walk.over) { // a block of an input that has failed by now is not written (an empty window)
+                for (size_t q = 0; q < blocks.size(); q++) {
+                    blocks[q].base = (int64_t)of[q]->base;
+                    blocks[q].lo = 0;
+                    blocks[q].hi = of[q]->placed ? (uint32_t)blocks[q].size : 0;
+                }
+                BZH_TRY(back_emit(ctx, w, clock, bk, d_out, true, blocks));
+                for (size_t q = 0; q < blocks.size(); q++) of[q]->got_crc = blocks[q].crc;
+            } else {
+                clock.span(3, bk.t_unrle);
+            }
+        }
+        walk.check(!walk.over);
+    }
+    walk.finish();
+    clock.collect();
+    ds.candidates_off_chain = walk.off_chain;
+    ds.streams = walk.streams;
+    ds.blocks = walk.blocks;
+    ds.out_bytes = walk.total_out;
+    ms.inputs = count;
+    ms.inputs_failed = walk.failed;
+    ms.streams = walk.streams;
+    ms.blocks = walk.blocks;
+    bool named = false;
+    for (size_t k = 0; k < count; k++) {
+        const BzmState &s = walk.st[k];
+        out_offs[k] = (size_t)s.out_off;
+        out_lens[k] = (size_t)s.out_len;
+        status[k] = s.status;
+        if (consumed) consumed[k] = (size_t)s.consumed;
+        if (s.status == BZH_OK || named) continue;
+        named = true;
+        const BzmError &e = s.err;
+        if (e.kind == BZD_OK)
+            bzh_set_error(ctx, "decode: input %zu: stream %zu is of level %u, the context of level %d", k, e.stream, e.level, ctx->level);
+        else
+            bzh_set_error(ctx, "decode: input %zu: %s%s%s in stream %zu, block %zu, at bit %llu", k, kind_name(e.kind), e.what ? ": " : "",
+                          e.what ? e.what : "", e.stream, e.block, (unsigned long long)e.bit);
+    }
+    if (walk.over) {
+        bzh_set_error(ctx, "decode: the output needs %llu bytes, the buffer holds %zu", (unsigned long long)walk.total_out, cap);
         return BZH_E_CAP;
     }
     return BZH_OK;

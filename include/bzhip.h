@@ -184,6 +184,51 @@ typedef struct {
 } bzh_decode_stats;
 BZH_API int bzh_get_decode_stats(const bzh_ctx *ctx, bzh_decode_stats *out);
 
+/* ---- many inputs, one decode each: N calls of bzh_decode in one pass (the inverse of bzh_encode_many) ---------- */
+
+/* Input k is d_in[in_offs[k] .. in_offs[k] + in_lens[k]) and is judged exactly as bzh_decode judges that slice alone: one or
+ * more streams of any encoder, foreign bytes behind them tolerated, nothing outside the slice looked at.  The slices ascend and
+ * do not overlap; gaps between them are allowed, so bzh_encode_many_device's out_offs / out_lens are valid in_offs / in_lens as
+ * they stand (its padding is the gaps).  BZH_E_ARG for the call, with nothing launched: a slice that reaches past n, slices that
+ * descend or overlap, a null array with count > 0 (consumed alone may be null), a null buffer where bytes are claimed.
+ * status[k] is what bzh_decode of input k alone returns with ample room: BZH_OK, BZH_E_DATA (an empty slice included), or
+ * BZH_E_ARG for a stream above the context's level.  A failed input does not touch the others: it gets out_lens[k] = 0, and
+ * consumed[k] as bzh_decode reports it (the end of the last stream the walk had passed when the failure was found).
+ * bzh_last_error holds the text of the first failed input, prefixed with its number, positions counted inside its slice.  The
+ * call itself returns BZH_OK when it ran to the end, even if every input failed: the statuses say what happened.
+ * Output: the decoded inputs lie back to back from out_offs[0] = 0, no padding: out_offs[k+1] = out_offs[k] + out_lens[k];
+ * when every input decodes, d_out / out_lens are bzh_encode_many_device's d_in / lens.  An input that fails after some of its
+ * blocks were placed may leave a gap of at most the bytes it had decoded: the gap's bytes are unspecified, its out_lens[k] is 0,
+ * and out_offs[k+1] lies behind the gap.
+ * BZH_E_CAP as for bzh_decode: the call finishes sizing, all of out_offs / out_lens / status are set, the room needed is
+ * out_offs[count-1] + out_lens[count-1] (gaps included), d_out is unspecified, and repeating the call with that room succeeds.
+ * cap == 0 with a null d_out is a sizing call; like bzh_decode's it checks no CRC (blocks behind the point where the output
+ * stops fitting are sized, not verified).
+ * One scan covers the whole buffer and a batch takes the candidates of many inputs together: 4,096 one-block inputs are a few
+ * batches, not 4,096 calls.  Blocks of at most bzh_decode_many_small_max() bytes go through an inverse BWT that works in LDS,
+ * one workgroup a block; larger ones through the transform bzh_decode uses.  count == 0 succeeds.  After any outcome the context
+ * stays usable.  The call joins a streaming pass in flight, runs on the context's stream and honours bzh_set_profiling, like
+ * every entry point; bzh_get_decode_stats is filled as for bzh_decode, summed over the inputs. */
+BZH_API int bzh_decode_many_device(bzh_ctx *ctx, const void *d_in, size_t n, const size_t *in_offs, const size_t *in_lens, size_t count,
+                                   void *d_out, size_t cap, size_t *out_offs, size_t *out_lens, int *status, size_t *consumed);
+/* Host buffers: ins[k][0..lens[k]) in (one H2D of all inputs, laid back to back without gaps), the decoded inputs in out as
+ * above (one D2H).  BZH_E_ARG also for a null ins[k] with lens[k] > 0. */
+BZH_API int bzh_decode_many(bzh_ctx *ctx, const uint8_t *const *ins, const size_t *lens, size_t count, uint8_t *out, size_t cap,
+                            size_t *out_offs, size_t *out_lens, int *status, size_t *consumed);
+/* The largest block (bytes of its last column, i.e. behind RLE1) the LDS inverse BWT takes: pure host, no context. */
+BZH_API size_t bzh_decode_many_small_max(void);
+
+/* Counters of the last bzh_decode_many* call; ms_unbwt_small (milliseconds, HIP events) is filled when profiling is enabled and
+ * is part of bzh_decode_stats::ms_unbwt. */
+typedef struct {
+    uint64_t inputs, inputs_failed;
+    uint64_t streams, blocks; /* met on the chains of all inputs */
+    uint64_t blocks_small;    /* of those: through the LDS inverse BWT */
+    uint64_t batches;         /* entropy-stage launches */
+    double ms_unbwt_small;
+} bzh_decode_many_stats;
+BZH_API int bzh_get_decode_many_stats(const bzh_ctx *ctx, bzh_decode_many_stats *out);
+
 /* ---- random access: a verified block index, and the decode of a byte range of the output ---------- */
 
 /* One decoded block.  bzip2 blocks are independent once the bit they start at is known: the index records that bit for every
