@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import cases
+from tests import huff_paths_model
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
@@ -126,14 +127,23 @@ def test_huffman_seam(oracle, ctx9, mode):
 
 
 def test_huffman_three_tables_and_rescale(oracle, ctx9):
-    """>= 200 symbols -> 3 tables (T10); a geometric histogram forces the > 17-bit rescale loop (T13)"""
+    """a geometric histogram forces the > 17-bit rescale loop (T13): first with 56 symbols -- two tables, table 0 accepted at
+    scaling 8 --, then with rare bytes of every value mixed in, 212 symbols -- three tables (>= 200 symbols, T10), table 0
+    accepted at scaling 4 (exponents as tests/huff_paths_model.py reports them)"""
     rng = np.random.default_rng(3)
     d = np.minimum(rng.geometric(0.35, 400_000) - 1 + rng.integers(0, 2, 400_000) * 128, 255).astype(np.uint8).tobytes()
-    b, _, hb = oracle.bwt(d)
-    s, f, ns = oracle.mtf_and_rle(b, hb)
-    gbits, gn, glens = ctx9.huffman(s, ns, f)
-    obits, on, olens = oracle.huffman_block(s, ns, f)
-    assert gn == on and gbits == obits and np.array_equal(glens[:, :ns], olens[:, :ns])
+    rng = np.random.default_rng(4)
+    g = np.minimum(rng.geometric(0.6, 200_000) - 1, 255)
+    d3 = np.where(rng.random(200_000) < 0.002, rng.integers(0, 256, 200_000), g).astype(np.uint8).tobytes()
+    for data, tables in ((d, 2), (d3, 3)):
+        b, _, hb = oracle.bwt(data)
+        s, f, ns = oracle.mtf_and_rle(b, hb)
+        assert (ns >= 200) == (tables == 3)
+        assert huff_paths_model.analyse(s, ns)[1]["exps"][0] == (3 if tables == 2 else 2)  # the rescale loop is needed
+        gbits, gn, glens = ctx9.huffman(s, ns, f)
+        obits, on, olens = oracle.huffman_block(s, ns, f)
+        assert gn == on and gbits == obits and np.array_equal(glens[:, :ns], olens[:, :ns])
+        assert glens.shape[0] == olens.shape[0] == tables
     # direct check of the code-length builder on Fibonacci-like weights (needs scaling > 1)
     fib = [1, 1]
     while len(fib) < 40:
@@ -146,8 +156,9 @@ def test_huffman_three_tables_and_rescale(oracle, ctx9):
 def test_huffman_scaling_attempts_of_both_halves(oracle, ctx9):
     """huff_build runs the scaling attempts 1, 2, 4, ... of a table side by side, the lower and the upper exponents in two
     workgroups a block, and huff_header takes the lower half's table if it has one: symbol streams whose counts double from
-    symbol to symbol (codes up to 19 bits at scaling 1) need scaling 8 .. 64 -- tables decided by the lower half, by the
-    upper half, with 2 tables and with 3 (>= 200 symbols)"""
+    symbol to symbol (codes up to 19 bits at scaling 1).  As tests/huff_paths_model.py reports them, the six inputs are accepted at
+    the exponents (0, 0), (0, 0), (3, 2), (4, 2), (4, 3) with two tables and (4, 0, 3) with three (>= 200 symbols): table 0 decided
+    by the lower half and by the upper half, never by the carry-on tail (tests/test_gpu_huffman_edges.py reaches the rest)"""
     rng = np.random.default_rng(17)
     for top, extra in ((13, 0), (15, 0), (17, 0), (18, 0), (18, 100), (18, 230)):
         counts = np.array([1 << i for i in range(top + 1)] + [1] * extra, dtype=np.int64)
