@@ -10,12 +10,12 @@
 #include <algorithm>
 #include <atomic>
 #include <future>
-#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
 
 #include "common.h"
+#include "encode_plan.h"
 
 static void stream_join(bzh_ctx *ctx); // waits for a streaming pass in flight (defined with bzh_stream_*)
 
@@ -68,6 +68,15 @@ hipEvent_t bzh_event(bzh_ctx *ctx)
         ctx->evpool.push_back(e);
     }
     return ctx->evpool[ctx->evnext++];
+}
+
+// Profiling: an event of the pool recorded on the context's stream now (nullptr otherwise).
+static hipEvent_t call_mark(bzh_ctx *ctx)
+{
+    if (!ctx->profiling) return nullptr;
+    hipEvent_t e = bzh_event(ctx);
+    hipEventRecord(e, ctx->stream);
+    return e;
 }
 
 extern "C" const char *bzh_strerror(int status)
@@ -412,19 +421,11 @@ extern "C" int bzh_get_stats(const bzh_ctx *ctx, bzh_stats *out)
     });
 }
 
-static void kstats_reset(bzh_ctx *ctx);
-static void stats_begin(bzh_ctx *ctx)
-{
-    memset(&ctx->stats, 0, sizeof ctx->stats);
-    ctx->evnext = 0;
-    ctx->sort_spans.clear();
-    kstats_reset(ctx);
-}
-
-static void kstats_reset(bzh_ctx *ctx)
+static void kstats_reset(bzh_ctx *ctx, bool keep_plan = false) // (keep_plan: the plan's classes stay in the table)
 {
     ctx->kspans.clear();
     for (int k = 0; k < K_COUNT; k++) {
+        if (keep_plan && (k == K_PLAN || k == K_CRC)) continue;
         ctx->k_ms[k] = 0;
         ctx->k_bytes[k] = 0;
         ctx->k_launch[k] = 0;
@@ -439,6 +440,25 @@ static void kstats_collect(bzh_ctx *ctx)
         if (hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) ctx->k_ms[r.cls] += t;
     }
     ctx->kspans.clear();
+}
+
+// The start of every call that counts or times: fresh statistics and kernel classes, the event pool rewound (every such call
+// takes its events from the start of the pool), no span recorded against the old use of those events.
+// (`keep_plan`: bzh_encode_range_device -- the plan calls in front of it belong to the same encode: ms_plan stays, and so do the
+// plan's kernel classes, whose spans are turned into milliseconds now, before the pool is rewound under them)
+static int stats_begin(bzh_ctx *ctx, bool keep_plan = false)
+{
+    const double ms_plan = keep_plan ? ctx->stats.ms_plan : 0;
+    memset(&ctx->stats, 0, sizeof ctx->stats);
+    ctx->stats.ms_plan = ms_plan;
+    ctx->sort_spans.clear();
+    if (keep_plan && ctx->profiling) {
+        HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+        kstats_collect(ctx);
+    }
+    kstats_reset(ctx, keep_plan && ctx->profiling);
+    ctx->evnext = 0;
+    return BZH_OK;
 }
 
 extern "C" int bzh_get_kernel_stats(const bzh_ctx *ctx, bzh_kstat *out, size_t max, size_t *count)
@@ -595,17 +615,12 @@ extern "C" int bzh_bwt_roundtrip_device(bzh_ctx *ctx, size_t b0, size_t b1, uint
     unsigned long long total = 0;
     for (size_t k0 = b0; k0 < b1; k0 += ctx->max_batch) {
         const uint32_t B = (uint32_t)std::min<size_t>(ctx->max_batch, b1 - k0);
-        uint32_t nmax = 0;
-        uint64_t ntotal = 0;
-        for (uint32_t b = 0; b < B; b++) {
-            nmax = std::max(nmax, ctx->plan_blocks[k0 + b].rle_len);
-            ntotal += ctx->plan_blocks[k0 + b].rle_len;
-        }
+        const BzeSums s = bze_job_sums(ctx->plan_blocks.data(), k0, B);
         BZH_TRY(rle1_emit(ctx, k0, B));
-        BZH_TRY(bwt_run(ctx, B, nmax, ntotal));
-        BZH_TRY(unbwt_run(ctx, B, nmax));
+        BZH_TRY(bwt_run(ctx, B, s.nmax, s.ntotal));
+        BZH_TRY(unbwt_run(ctx, B, s.nmax));
         HIP_TRY(ctx, hipMemsetAsync(d_acc, 0, sizeof(unsigned long long), st));
-        BZH_TRY(unbwt_compare(ctx, B, nmax, d_acc));
+        BZH_TRY(unbwt_compare(ctx, B, s.nmax, d_acc));
         unsigned long long part = 0;
         HIP_TRY(ctx, hipMemcpyAsync(&part, d_acc, sizeof part, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, bzh_stream_wait(st));
@@ -817,37 +832,106 @@ struct RangeJob {
     uint64_t ntotal = 0, T = 0;
     int status = BZH_OK;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    std::promise<void> ready, packed;
 };
+
+// Plan blocks [b0, b1) as jobs of `per` blocks (encode_plan.h), counted into the call's statistics.
+static void build_jobs(bzh_ctx *ctx, size_t b0, size_t b1, size_t per, std::vector<RangeJob> &jobs)
+{
+    std::vector<BzeSpan> spans;
+    bze_split(b0, b1, per, spans);
+    for (const BzeSpan &sp : spans) {
+        const BzeSums s = bze_job_sums(ctx->plan_blocks.data(), sp.k0, sp.B);
+        ctx->stats.rle_bytes += s.ntotal;
+        ctx->stats.raw_bytes += s.raw;
+        ctx->stats.blocks += sp.B;
+        jobs.push_back({sp.k0, sp.B, s.nmax, s.mmax, s.ntotal});
+    }
+}
+
+// The jobs' events -> the stage times of the call (profiling; the streams have been waited for).
+static void jobs_ms(bzh_ctx *ctx, const std::vector<RangeJob> &jobs)
+{
+    for (const RangeJob &job : jobs) {
+        ctx->stats.ms_rle1 += span_ms(job.ev[0], job.ev[1]);
+        ctx->stats.ms_bwt += span_ms(job.ev[1], job.ev[2]);
+        ctx->stats.ms_mtf += span_ms(job.ev[2], job.ev[3]);
+        ctx->stats.ms_huff += span_ms(job.ev[3], job.ev[4]);
+        ctx->stats.ms_pack += span_ms(job.ev[4], job.ev[5]);
+    }
+}
 
 // Everything of a batch up to its bit total, on the lane's stream and arena.
 static int prepare_batch(bzh_ctx *lane, RangeJob &j, bool wait_total = true)
 {
     hipStream_t st = lane->stream;
-    auto mark = [&](int i) {
-        if (lane->profiling) {
-            j.ev[i] = bzh_event(lane);
-            hipEventRecord(j.ev[i], st);
-        }
-    };
     lane->k_cur_ntotal = j.ntotal;
-    mark(0);
+    j.ev[0] = call_mark(lane);
     BZH_TRY(rle1_emit(lane, j.k0, j.B));
-    mark(1);
+    j.ev[1] = call_mark(lane);
     BZH_TRY(bwt_run(lane, j.B, j.nmax, j.ntotal));
-    mark(2);
+    j.ev[2] = call_mark(lane);
     BZH_TRY(mtf_run(lane, j.B, j.nmax, j.ntotal));
-    mark(3);
+    j.ev[3] = call_mark(lane);
     {   // the block headers carry the block CRCs: a whole-path plan left them to the owner's second stream (rle1_plan_split)
         bzh_ctx *pc = lane->parent ? lane->parent : lane;
         if (pc->crc_pending) HIP_TRY(lane, hipStreamWaitEvent(st, pc->plan_ev[1], 0));
     }
     BZH_TRY(huff_prepare(lane, j.B, j.mmax));
-    mark(4);
+    j.ev[4] = call_mark(lane);
     if (!wait_total) return BZH_OK; // (a call of one batch: the device carries on by itself, encode_range reads the total at the end)
     HIP_TRY(lane, hipMemcpyAsync(&j.T, lane->bt.bitoff + j.B, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(lane, bzh_stream_wait(st));
     return BZH_OK;
+}
+
+// Two lanes: lane k prepares jobs k, k + 2, ... on a thread of its own while this thread packs them in order; a lane may reuse
+// its arena only after its job was packed.  -> the first failure (`keep`: the statistics to go back to where no thread could be
+// started)
+template <typename Pack>
+static int run_lanes(bzh_ctx *ctx, const std::vector<bzh_ctx *> &lanes, std::vector<RangeJob> &jobs, const bzh_stats &keep, Pack &&pack)
+{
+    struct Turn {
+        std::promise<void> ready, packed;
+    };
+    const size_t NL = lanes.size();
+    std::vector<Turn> turns(jobs.size());
+    std::atomic<bool> abort{false}; // set when not every lane thread could be started: the ones that did start do nothing
+    auto worker = [&](int k) {
+        hipSetDevice(ctx->device);
+        bool dead = false;
+        for (size_t j = k; j < jobs.size(); j += NL) {
+            jobs[j].status = (dead || abort.load()) ? BZH_E_STATE : prepare_batch(lanes[k], jobs[j]);
+            if (jobs[j].status != BZH_OK) dead = true;
+            turns[j].ready.set_value();
+            turns[j].packed.get_future().wait();
+        }
+    };
+    std::vector<std::thread> threads;
+    try {
+        threads.reserve(NL);
+        for (size_t k = 0; k < NL; k++) threads.emplace_back(worker, (int)k);
+    } catch (...) { // no thread to be had: release the workers that did start (they skip their jobs), then report
+        abort.store(true);
+        for (Turn &t : turns) t.packed.set_value();
+        for (auto &t : threads) t.join();
+        for (bzh_ctx *l : lanes) hipStreamSynchronize(l->stream); // (a job may have been in flight already)
+        ctx->stats = keep;
+        bzh_set_error(ctx, "could not start the lane threads");
+        return BZH_E_NOMEM;
+    }
+    int status = BZH_OK;
+    for (size_t j = 0; j < jobs.size(); j++) {
+        bzh_ctx *lane = lanes[j % NL];
+        turns[j].ready.get_future().wait();
+        if (status == BZH_OK && jobs[j].status != BZH_OK) {
+            status = jobs[j].status;
+            bzh_set_error(ctx, "%s", lane->err);
+        }
+        if (status == BZH_OK) status = pack(lane, jobs[j]);
+        turns[j].packed.set_value();
+    }
+    for (auto &t : threads) t.join();
+    return status;
 }
 
 // Encodes plan blocks [b0, b1) into d_out starting at bit `bit_base`; words of d_out from
@@ -873,181 +957,99 @@ static int encode_range(bzh_ctx *ctx, size_t b0, size_t b1, uint8_t *d_out, size
     }
     const size_t NL = lanes.size();
     if (NL > 1) HIP_TRY(ctx, bzh_stream_wait(ctx->stream)); // the plan and whatever produced the input: the lanes' streams start behind it (one lane = this stream: in order anyway)
-    const bzh_stats stats_in = ctx->stats;
-    const size_t nb = b1 - b0;
-    const uint32_t lane_mb = lanes[0]->max_batch;
-    size_t njobs = (nb + lane_mb - 1) / lane_mb;
-    if (njobs < NL && nb >= NL) njobs = NL; // give every lane work
-    const size_t per = (nb + njobs - 1) / njobs;
+    const bzh_stats keep = ctx->stats; // what the counters were before this call touched them
+    const size_t per = bze_per(b1 - b0, lanes[0]->max_batch, NL);
     if (NL == 1) BZH_TRY(ensure_arena(ctx, (uint32_t)per));
-    std::vector<std::unique_ptr<RangeJob>> jobs;
-    for (size_t k0 = b0; k0 < b1; k0 += per) {
-        auto j = std::make_unique<RangeJob>();
-        j->k0 = k0;
-        j->B = (uint32_t)std::min<size_t>(per, b1 - k0);
-        for (uint32_t b = 0; b < j->B; b++) {
-            const bzh_block &pb = ctx->plan_blocks[k0 + b];
-            j->nmax = std::max(j->nmax, pb.rle_len);
-            j->ntotal += pb.rle_len;
-            ctx->stats.rle_bytes += pb.rle_len;
-            ctx->stats.raw_bytes += pb.in_len;
-        }
-        j->mmax = j->nmax + 1; // m <= n + 1 (lib/mtf.rs:36)
-        ctx->stats.blocks += j->B;
-        jobs.push_back(std::move(j));
-    }
-    bzh_stats keep = stats_in; // what the counters were before this call touched them
+    std::vector<RangeJob> jobs;
+    build_jobs(ctx, b0, b1, per, jobs);
     for (bzh_ctx *l : lanes) {
         l->profiling = ctx->profiling;
-        l->sort_spans.clear();
-        if (l != ctx) kstats_reset(l);
         if (l != ctx) {
-            l->evnext = 0;
-            memset(&l->stats, 0, sizeof l->stats);
+            stats_begin(l);
             l->err[0] = 0;
         } else {
+            ctx->sort_spans.clear();
             ctx->stats.bwt_active_sum = 0;
             ctx->stats.bwt_rounds = 0;
             ctx->stats.bwt_sort_launches = 0;
             ctx->stats.bwt_sort_elems = 0;
         }
     }
-    // lane k prepares jobs k, k+2, ...; it may reuse its arena only after the job was packed
-    std::atomic<bool> abort{false}; // set when not every lane thread could be started: the ones that did start do nothing
-    auto worker = [&](int k) {
-        hipSetDevice(ctx->device);
-        bool dead = false;
-        for (size_t j = k; j < jobs.size(); j += NL) {
-            RangeJob &job = *jobs[j];
-            job.status = (dead || abort.load()) ? BZH_E_STATE : prepare_batch(lanes[k], job);
-            if (job.status != BZH_OK) dead = true;
-            job.ready.set_value();
-            job.packed.get_future().wait();
-        }
-    };
-    std::vector<std::thread> threads;
-    if (NL > 1) {
-        try {
-            threads.reserve(NL);
-            for (size_t k = 0; k < NL; k++) threads.emplace_back(worker, (int)k);
-        } catch (...) { // no thread to be had: release the workers that did start (they skip their jobs), then report
-            abort.store(true);
-            for (auto &jp : jobs) jp->packed.set_value();
-            for (auto &t : threads) t.join();
-            for (bzh_ctx *l : lanes) hipStreamSynchronize(l->stream); // (a job may have been in flight already)
-            ctx->stats = keep;
-            bzh_set_error(ctx, "could not start the lane threads");
-            return BZH_E_NOMEM;
-        }
-    }
 
     const uint64_t cap_words = cap / 4;
     uint64_t zeroed_upto = bit_base / 32; // first word not yet known to be zero
     uint64_t cur = 0;
-    int status = BZH_OK;
     // A call of ONE batch (the usual case: up to max_batch blocks) needs the host for nothing between the Huffman tables and
     // the packed bits: the output words are zeroed, the capacity checked and the pack kernels gated on the device
     // (huff_pack_gate), and the bit total is read once, at the end -- instead of a copy, a wait, a memset and a launch in the
-    // middle of the step (35-40 us of idle device).
-    const bool one_batch = NL == 1 && jobs.size() == 1;
-    for (size_t j = 0; j < jobs.size(); j++) {
-        RangeJob &job = *jobs[j];
-        bzh_ctx *lane = lanes[j % NL];
-        if (NL == 1) { // no worker thread: prepare here
-            job.status = status == BZH_OK ? prepare_batch(lane, job, !one_batch) : BZH_E_STATE;
-            job.ready.set_value();
-        }
-        job.ready.get_future().wait();
-        if (status == BZH_OK && job.status != BZH_OK) {
-            status = job.status;
-            if (lane != ctx) bzh_set_error(ctx, "%s", lane->err);
-        }
-        if (status == BZH_OK && one_batch) {
-            hipStream_t st = lane->stream;
-            uint64_t *rec = reinterpret_cast<uint64_t *>(lane->h_pinned); // (the first 64 words of the pinned block are free)
+    // middle of the step (35-40 us of idle device).  With several batches the host has every batch's total before its pack
+    // (prepare_batch waited for it: the next batch's position depends on it), so it zeroes and checks the capacity itself.
+    const bool gated = NL == 1 && jobs.size() == 1;
+    // The pack step of one job, behind its prepare_batch: the job's bits at bit_base + cur, the lane's arena free again.
+    auto pack = [&](bzh_ctx *lane, RangeJob &job) -> int {
+        hipStream_t st = lane->stream;
+        uint64_t *rec = reinterpret_cast<uint64_t *>(lane->h_pinned); // (the first 64 words of the pinned block are free)
+        const uint64_t at = bit_base + cur;
+        bool over = false;
+        hipError_t he = hipSuccess;
+        int rc = BZH_OK;
+        if (gated) {
             const bool frame = want_frame && bit_base == 32 && b0 == 0 && !seed_word; // (block CRCs of the batch = of the stream)
-            status = huff_pack_gate(lane, job.B, d_out, bit_base, cap_words, seed_word ? *seed_word : 0u, seed_word != nullptr, rec, frame ? 80u : 0u);
-            if (status == BZH_OK) {
-                status = huff_pack(lane, job.B, job.mmax, d_out, bit_base, true);
-                if (status == BZH_OK && frame) {
-                    status = huff_frame_stream(lane, job.B, d_out);
-                    if (status == BZH_OK) *framed = true;
-                }
-                if (status != BZH_OK) (void)bzh_stream_wait(st); // (pack_gate is queued: nothing of this call may still run when the error is reported)
+            rc = huff_pack_gate(lane, job.B, d_out, at, cap_words, seed_word ? *seed_word : 0u, seed_word != nullptr, rec, frame ? 80u : 0u);
+            if (rc == BZH_OK) rc = huff_pack(lane, job.B, job.mmax, d_out, at, true);
+            if (rc == BZH_OK && frame && (rc = huff_frame_stream(lane, job.B, d_out)) == BZH_OK) *framed = true;
+        } else {
+            const BzeZero z = bze_zero_batch(bit_base, cur, job.T, zeroed_upto, cap_words);
+            over = z.over;
+            if (!over && z.to > z.from) {
+                he = hipMemsetAsync(d_out + z.from * 4, 0, (size_t)(z.to - z.from) * 4, st);
+                if (he == hipSuccess && seed_word && z.from == bit_base / 32) // bits owed to the first word
+                    he = hipMemcpyAsync(d_out + z.from * 4, seed_word, 4, hipMemcpyHostToDevice, st);
+                zeroed_upto = z.to;
             }
-            hipError_t he = hipSuccess;
-            std::vector<uint32_t> hm;
-            if (lane->profiling && status == BZH_OK) {
-                job.ev[5] = bzh_event(lane);
-                hipEventRecord(job.ev[5], st);
+            if (!over && he == hipSuccess) rc = huff_pack(lane, job.B, job.mmax, d_out, at);
+        }
+        if (rc != BZH_OK) {
+            (void)bzh_stream_wait(st); // (nothing of this call may still run when the error is reported)
+            return rc;
+        }
+        std::vector<uint32_t> hm;
+        if (!over) {
+            if (lane->profiling && he == hipSuccess) {
+                job.ev[5] = call_mark(lane);
                 hm.resize(job.B);
                 he = hipMemcpyAsync(hm.data(), lane->bt.m, job.B * 4, hipMemcpyDeviceToHost, st);
             }
-            if (status == BZH_OK) {
-                if (he == hipSuccess) he = bzh_stream_wait(st);
-                if (he != hipSuccess) {
-                    bzh_set_error(ctx, "pack: %s", hipGetErrorString(he));
-                    status = BZH_E_HIP;
-                } else {
-                    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-                    job.T = reinterpret_cast<volatile uint64_t *>(rec)[0];
-                    if (reinterpret_cast<volatile uint64_t *>(rec)[1] == 0) {
-                        bzh_set_error(ctx, "output needs more than %zu bytes", cap);
-                        status = BZH_E_CAP;
-                    } else {
-                        for (uint32_t b = 0; b < (uint32_t)hm.size(); b++) ctx->stats.mtf_syms += hm[b];
-                        if (ix) status = sync_emit_batch(lane, job.B, job.k0, bit_base, *ix);
-                        cur += job.T;
-                    }
-                }
+            if (he == hipSuccess) he = bzh_stream_wait(st); // the lane's arena is free again
+            if (he != hipSuccess) {
+                bzh_set_error(ctx, "pack: %s", hipGetErrorString(he));
+                return BZH_E_HIP;
             }
-        } else
-        if (status == BZH_OK) {
-            hipStream_t st = lane->stream;
-            const uint64_t need_upto = (bit_base + cur + job.T + 31) / 32 + 1;
-            hipError_t he = hipSuccess;
-            if (need_upto > cap_words) {
-                bzh_set_error(ctx, "output needs more than %zu bytes", cap);
-                status = BZH_E_CAP;
-            } else {
-                if (need_upto > zeroed_upto) {
-                    he = hipMemsetAsync(d_out + zeroed_upto * 4, 0, (size_t)(need_upto - zeroed_upto) * 4, st);
-                    if (he == hipSuccess && seed_word && zeroed_upto == bit_base / 32) // bits owed to the first word
-                        he = hipMemcpyAsync(d_out + zeroed_upto * 4, seed_word, 4, hipMemcpyHostToDevice, st);
-                    zeroed_upto = need_upto;
-                }
-                if (he == hipSuccess) status = huff_pack(lane, job.B, job.mmax, d_out, bit_base + cur);
-                if (lane->profiling && status == BZH_OK) {
-                    job.ev[5] = bzh_event(lane);
-                    hipEventRecord(job.ev[5], st);
-                    std::vector<uint32_t> hm(job.B);
-                    he = hipMemcpyAsync(hm.data(), lane->bt.m, job.B * 4, hipMemcpyDeviceToHost, st);
-                    if (he == hipSuccess) he = bzh_stream_wait(st);
-                    for (uint32_t b = 0; b < job.B; b++) ctx->stats.mtf_syms += hm[b];
-                }
-                if (he == hipSuccess) he = bzh_stream_wait(st); // the lane's arena is free again
-                if (he != hipSuccess) {
-                    bzh_set_error(ctx, "pack: %s", hipGetErrorString(he));
-                    status = BZH_E_HIP;
-                } else if (ix) {
-                    status = sync_emit_batch(lane, job.B, job.k0, bit_base + cur, *ix);
-                }
-                cur += job.T;
+            if (gated) { // what the gate found: the batch's bits, and whether they fit
+                __atomic_thread_fence(__ATOMIC_ACQUIRE);
+                job.T = reinterpret_cast<volatile uint64_t *>(rec)[0];
+                over = reinterpret_cast<volatile uint64_t *>(rec)[1] == 0;
             }
         }
-        job.packed.set_value();
+        if (over) {
+            bzh_set_error(ctx, "output needs more than %zu bytes", cap);
+            return BZH_E_CAP;
+        }
+        for (uint32_t m : hm) ctx->stats.mtf_syms += m;
+        if (ix) BZH_TRY(sync_emit_batch(lane, job.B, job.k0, at, *ix));
+        cur += job.T;
+        return BZH_OK;
+    };
+    if (NL == 1) {
+        for (RangeJob &job : jobs) {
+            BZH_TRY(prepare_batch(ctx, job, !gated));
+            BZH_TRY(pack(ctx, job));
+        }
+    } else {
+        BZH_TRY(run_lanes(ctx, lanes, jobs, keep, pack));
     }
-    for (auto &t : threads) t.join();
-    if (status != BZH_OK) return status;
     if (ctx->profiling) {
-        for (auto &jp : jobs) {
-            RangeJob &job = *jp;
-            ctx->stats.ms_rle1 += span_ms(job.ev[0], job.ev[1]);
-            ctx->stats.ms_bwt += span_ms(job.ev[1], job.ev[2]);
-            ctx->stats.ms_mtf += span_ms(job.ev[2], job.ev[3]);
-            ctx->stats.ms_huff += span_ms(job.ev[3], job.ev[4]);
-            ctx->stats.ms_pack += span_ms(job.ev[4], job.ev[5]);
-        }
+        jobs_ms(ctx, jobs);
         for (bzh_ctx *l : lanes) {
             stats_collect_sort(l);
             if (l == ctx) continue;
@@ -1086,16 +1088,11 @@ static int plan_device(bzh_ctx *ctx, const void *d_in, size_t n, size_t *nblocks
     if (!ctx || (!d_in && n) || !nblocks) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     BZH_TRY(check_in_ptr(ctx, d_in));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ctx->profiling) {
-        ctx->evnext = 0;
-        e0 = bzh_event(ctx);
-        hipEventRecord(e0, ctx->stream);
-    }
+    if (ctx->profiling) ctx->evnext = 0;
+    hipEvent_t e0 = call_mark(ctx);
     BZH_TRY(rle1_plan(ctx, (const uint8_t *)d_in, n, with_crc));
     if (ctx->profiling) {
-        e1 = bzh_event(ctx);
-        hipEventRecord(e1, ctx->stream);
+        hipEvent_t e1 = call_mark(ctx);
         HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
         memset(&ctx->stats, 0, sizeof ctx->stats);
         ctx->stats.ms_plan = span_ms(e0, e1);
@@ -1189,33 +1186,7 @@ extern "C" int bzh_encode_range_device(bzh_ctx *ctx, size_t b0, size_t b1, void 
     if (!ctx || !d_out || !nbits || b0 > b1) return BZH_E_ARG;
     if (b1 > ctx->plan_blocks.size()) return BZH_E_STATE;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const double keep_plan = ctx->stats.ms_plan;
-    memset(&ctx->stats, 0, sizeof ctx->stats);
-    ctx->stats.ms_plan = keep_plan;
-    ctx->sort_spans.clear();
-    // the plan's kernel classes (bzh_plan_tables_device / bzh_plan_split_device recorded them) stay in the table: their
-    // spans are turned into milliseconds now, before the event pool is rewound under them
-    double keep_ms[2];
-    uint64_t keep_bytes[2], keep_launch[2];
-    if (!ctx->profiling) {
-        kstats_reset(ctx);
-    } else {
-        HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
-        kstats_collect(ctx);
-        const int cls[2] = {K_PLAN, K_CRC};
-        for (int k = 0; k < 2; k++) {
-            keep_ms[k] = ctx->k_ms[cls[k]];
-            keep_bytes[k] = ctx->k_bytes[cls[k]];
-            keep_launch[k] = ctx->k_launch[cls[k]];
-        }
-        kstats_reset(ctx);
-        for (int k = 0; k < 2; k++) {
-            ctx->k_ms[cls[k]] = keep_ms[k];
-            ctx->k_bytes[cls[k]] = keep_bytes[k];
-            ctx->k_launch[cls[k]] = keep_launch[k];
-        }
-    }
-    ctx->evnext = 0;
+    BZH_TRY(stats_begin(ctx, true));
     *nbits = 0;
     if (b0 == b1) return BZH_OK;
     BZH_TRY(rle1_plan_crc(ctx, b0, b1)); // no-op unless the plan left the CRCs to the encoder
@@ -1267,21 +1238,11 @@ static int encode_device_impl(bzh_ctx *ctx, const void *d_in, size_t n, void *d_
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     if (((uintptr_t)d_out & 3u) != 0 || cap < 16) return BZH_E_ARG;
-    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
-    ctx->evnext = 0;
-    ctx->sort_spans.clear();
-    kstats_reset(ctx);
-    memset(&ctx->stats, 0, sizeof ctx->stats);
-    if (ctx->profiling) {
-        t0 = bzh_event(ctx);
-        hipEventRecord(t0, st);
-    }
+    stats_begin(ctx);
+    hipEvent_t t0 = call_mark(ctx);
     BZH_TRY(check_in_ptr(ctx, d_in));
     BZH_TRY(rle1_plan(ctx, (const uint8_t *)d_in, n, true, true)); // (the block CRCs beside the main stream: joined below)
-    if (ctx->profiling) {
-        t1 = bzh_event(ctx);
-        hipEventRecord(t1, st);
-    }
+    hipEvent_t t1 = call_mark(ctx);
     // words 0 and 1 hold the stream header and the first body bits
     HIP_TRY(ctx, hipMemsetAsync(d_out, 0, 4, st));
     uint64_t body = 0;
@@ -1299,31 +1260,19 @@ static int encode_device_impl(bzh_ctx *ctx, const void *d_in, size_t n, void *d_
     *out_len = bytes;
     if (framed) { // (everything is written and waited for; the CRCs are collected for bzh_plan_blocks' sake)
         BZH_TRY(rle1_plan_crc_join(ctx));
-        if (ctx->profiling) {
-            t2 = bzh_event(ctx);
-            hipEventRecord(t2, st);
-            HIP_TRY(ctx, bzh_stream_wait(st));
-            ctx->stats.ms_plan = span_ms(t0, t1);
-            ctx->stats.ms_total = span_ms(t0, t2);
-        }
-        if (consumed) *consumed = n;
-        return BZH_OK;
+    } else {
+        // the footer may reach one word past what encode_range zeroed
+        const BzeZero z = bze_zero_footer(32 + body, nb != 0, cap / 4);
+        if (z.over) return BZH_E_CAP;
+        if (z.to > z.from) HIP_TRY(ctx, hipMemsetAsync((uint8_t *)d_out + z.from * 4, 0, (size_t)(z.to - z.from) * 4, st));
+        BZH_TRY(rle1_plan_crc_join(ctx));
+        std::vector<uint32_t> crcs(nb);
+        for (size_t k = 0; k < nb; k++) crcs[k] = ctx->plan_blocks[k].crc;
+        stream_frame<<<1, 64, 0, st>>>((uint32_t *)d_out, ctx->level, body, fold_stream_crc(crcs.data(), nb));
+        HIP_TRY(ctx, hipGetLastError());
     }
-    // the footer may reach one word past what encode_range zeroed
-    const uint64_t zero_from = (32 + body + 31) / 32 + (nb ? 1 : 0), zero_to = (total_bits + 31) / 32 + 1;
-    if (zero_to * 4 > cap) return BZH_E_CAP;
-    if (zero_to > zero_from && nb)
-        HIP_TRY(ctx, hipMemsetAsync((uint8_t *)d_out + zero_from * 4, 0, (size_t)(zero_to - zero_from) * 4, st));
-    BZH_TRY(rle1_plan_crc_join(ctx));
-    std::vector<uint32_t> crcs(nb);
-    for (size_t k = 0; k < nb; k++) crcs[k] = ctx->plan_blocks[k].crc;
-    stream_frame<<<1, 64, 0, st>>>((uint32_t *)d_out, ctx->level, body, fold_stream_crc(crcs.data(), nb));
-    HIP_TRY(ctx, hipGetLastError());
-    if (ctx->profiling) {
-        t2 = bzh_event(ctx);
-        hipEventRecord(t2, st);
-    }
-    HIP_TRY(ctx, bzh_stream_wait(st));
+    hipEvent_t t2 = call_mark(ctx);
+    if (!framed || ctx->profiling) HIP_TRY(ctx, bzh_stream_wait(st));
     if (ctx->profiling) {
         ctx->stats.ms_plan = span_ms(t0, t1);
         ctx->stats.ms_total = span_ms(t0, t2);
@@ -1339,10 +1288,10 @@ extern "C" int bzh_encode_device(bzh_ctx *ctx, const void *d_in, size_t n, void 
     return encode_device_impl(ctx, d_in, n, d_out, cap, out_len, consumed, nullptr);
 }
 
-extern "C" int bzh_encode(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len,
-                          size_t *consumed)
+// bzh_encode; with `ix` also the index of the stream (bzh_encode_index): host buffers, through the staging buffers
+static int encode_host(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len, size_t *consumed,
+                       EncIndex *ix)
 {
-    return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!in && n) || !out || !out_len) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1352,14 +1301,18 @@ extern "C" int bzh_encode(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *ou
     BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, dcap));
     if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, st));
     size_t len = 0;
-    BZH_TRY(bzh_encode_device(ctx, ctx->d_stage_in, n, ctx->d_stage_out, ctx->stage_out_size & ~(size_t)3, &len,
-                              consumed));
+    BZH_TRY(encode_device_impl(ctx, ctx->d_stage_in, n, ctx->d_stage_out, ctx->stage_out_size & ~(size_t)3, &len, consumed, ix));
     *out_len = len;
     if (len > cap) return BZH_E_CAP;
     HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, len, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, bzh_stream_wait(st));
     return BZH_OK;
-    });
+}
+
+extern "C" int bzh_encode(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len,
+                          size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int { return encode_host(ctx, in, n, out, cap, out_len, consumed, nullptr); });
 }
 
 // ---- the encoder writes the index of its own stream (sync_emit.hip) --------------------------------------------------------
@@ -1423,21 +1376,8 @@ extern "C" int bzh_encode_index(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8
 {
     return bzh_guard(ctx, [&]() -> int {
     BZH_TRY(encode_index_args(ctx, interval, idx, max, count, pts, max_pts, npts));
-    stream_join(ctx);
-    if ((!in && n) || !out || !out_len) return BZH_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, n + 16));
-    const size_t dcap = n + n / 4 + (n / ((size_t)ctx->M * 4 / 5) + 2) * 4096 + 65536; // (as bzh_encode)
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, dcap));
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, st));
-    size_t len = 0;
     EncIndex ix{interval, {}, {}};
-    BZH_TRY(encode_device_impl(ctx, ctx->d_stage_in, n, ctx->d_stage_out, ctx->stage_out_size & ~(size_t)3, &len, consumed, &ix));
-    *out_len = len;
-    if (len > cap) return BZH_E_CAP;
-    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, len, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, bzh_stream_wait(st));
+    BZH_TRY(encode_host(ctx, in, n, out, cap, out_len, consumed, &ix));
     return encode_index_out(ctx, ix, idx, max, count, pts, max_pts, npts);
     });
 }
@@ -1501,14 +1441,6 @@ struct DecodeCall {
     hipEvent_t t0 = nullptr, t1 = nullptr;
 };
 
-static hipEvent_t decode_call_mark(bzh_ctx *ctx)
-{
-    if (!ctx->profiling) return nullptr;
-    hipEvent_t e = bzh_event(ctx);
-    hipEventRecord(e, ctx->stream);
-    return e;
-}
-
 static int decode_call_begin(bzh_ctx *ctx, size_t n, DecodeCall &c)
 {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1517,7 +1449,7 @@ static int decode_call_begin(bzh_ctx *ctx, size_t n, DecodeCall &c)
     kstats_reset(ctx);
     memset(&ctx->dstats, 0, sizeof ctx->dstats);
     ctx->dstats.in_bytes = n;
-    c.t0 = decode_call_mark(ctx);
+    c.t0 = call_mark(ctx);
     return BZH_OK;
 }
 
@@ -1525,7 +1457,7 @@ static int decode_call_begin(bzh_ctx *ctx, size_t n, DecodeCall &c)
 static int decode_call_scan(bzh_ctx *ctx, DecodeCall &c, const void *d_in, size_t n, std::vector<uint64_t> &cands)
 {
     BZH_TRY(decode_scan_run(ctx, (const uint8_t *)d_in, n, cands));
-    c.t1 = decode_call_mark(ctx);
+    c.t1 = call_mark(ctx);
     ctx->dstats.candidates = cands.size();
     return ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(cands.size(), 1), ctx->max_batch));
 }
@@ -1534,7 +1466,7 @@ static int decode_call_scan(bzh_ctx *ctx, DecodeCall &c, const void *d_in, size_
 static int decode_call_end(bzh_ctx *ctx, const DecodeCall &c, int rc)
 {
     if (!ctx->profiling) return rc;
-    hipEvent_t t2 = decode_call_mark(ctx);
+    hipEvent_t t2 = call_mark(ctx);
     HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
     if (c.t1) ctx->dstats.ms_scan = span_ms(c.t0, c.t1);
     ctx->dstats.ms_total = span_ms(c.t0, t2);
@@ -1949,21 +1881,11 @@ static int encode_many(bzh_ctx *ctx, const void *d_in, const size_t *lens, size_
         return BZH_E_ARG;
     }
     hipStream_t st = ctx->stream;
-    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
-    ctx->evnext = 0;
-    ctx->sort_spans.clear();
-    kstats_reset(ctx);
-    memset(&ctx->stats, 0, sizeof ctx->stats);
+    stats_begin(ctx);
     if (count == 0) return BZH_OK;
-    if (ctx->profiling) {
-        t0 = bzh_event(ctx);
-        hipEventRecord(t0, st);
-    }
+    hipEvent_t t0 = call_mark(ctx);
     BZH_TRY(rle1_plan_many(ctx, (const uint8_t *)d_in, lens, count));
-    if (ctx->profiling) {
-        t1 = bzh_event(ctx);
-        hipEventRecord(t1, st);
-    }
+    hipEvent_t t1 = call_mark(ctx);
     // state | offs | lens | body | crc
     const size_t words = MST_WORDS + 3 * count + (count + 1) / 2;
     if (words * 8 > ctx->many_out_size) {
@@ -1989,43 +1911,21 @@ static int encode_many(bzh_ctx *ctx, const void *d_in, const size_t *lens, size_
     ManyBatch mb{};
     mb.level = (uint32_t)ctx->level;
     mb.cap_words = cap / 4;
-    int status = BZH_OK;
-    std::vector<std::unique_ptr<RangeJob>> jobs;
-    if (nb == 0) { // every input is empty: no batch, only frames
-        mb.close_hi = mb.hi = (uint32_t)count;
-        status = huff_many_batch(ctx, mb, nullptr, (uint8_t *)d_out, 0, mo);
-    }
-    uint32_t cur = 0; // first input not complete
-    for (size_t k0 = 0; k0 < nb && status == BZH_OK; k0 += per) {
-        auto j = std::make_unique<RangeJob>();
-        j->k0 = k0;
-        j->B = (uint32_t)std::min<size_t>(per, nb - k0);
-        for (uint32_t b = 0; b < j->B; b++) {
-            const bzh_block &pb = ctx->plan_blocks[k0 + b];
-            j->nmax = std::max(j->nmax, pb.rle_len);
-            j->ntotal += pb.rle_len;
-            ctx->stats.rle_bytes += pb.rle_len;
-            ctx->stats.raw_bytes += pb.in_len;
-        }
-        j->mmax = j->nmax + 1; // m <= n + 1 (lib/mtf.rs:36)
-        ctx->stats.blocks += j->B;
-        status = prepare_batch(ctx, *j, false);
-        if (status != BZH_OK) break;
-        const size_t kl = k0 + j->B - 1;
-        const uint32_t il = ctx->plan_input[kl];
-        const bool last = kl + 1 == nb, closes = last || ctx->plan_input[kl + 1] != il;
-        mb.B = j->B;
-        mb.lo = cur;
-        mb.lo_started = (k0 > 0 && ctx->plan_input[k0 - 1] == cur) ? 1u : 0u;
-        mb.close_hi = last ? (uint32_t)count : (closes ? il + 1 : il);
-        mb.hi = closes ? mb.close_hi : il + 1;
-        status = huff_many_batch(ctx, mb, ctx->many_binp + k0, (uint8_t *)d_out, j->mmax, mo);
-        if (ctx->profiling && status == BZH_OK) {
-            j->ev[5] = bzh_event(ctx);
-            hipEventRecord(j->ev[5], st);
-        }
-        cur = mb.close_hi;
-        jobs.push_back(std::move(j));
+    std::vector<RangeJob> jobs;
+    build_jobs(ctx, 0, nb, per, jobs);
+    auto place = [&](size_t k0, uint32_t B, uint32_t mmax) -> int { // the streams of a batch (encode_plan.h), laid out and framed on the device
+        const BzeMany d = bze_many_batch(ctx->plan_input.data(), k0, B, nb, count, mb.close_hi); // (close_hi: first input not complete)
+        mb.B = B;
+        mb.lo = d.lo;
+        mb.lo_started = d.lo_started;
+        mb.close_hi = d.close_hi;
+        mb.hi = d.hi;
+        return huff_many_batch(ctx, mb, B ? ctx->many_binp + k0 : nullptr, (uint8_t *)d_out, mmax, mo);
+    };
+    int status = nb ? BZH_OK : place(0, 0, 0); // (every input is empty: no batch, only frames)
+    for (RangeJob &j : jobs) {
+        if ((status = prepare_batch(ctx, j, false)) != BZH_OK || (status = place(j.k0, j.B, j.mmax)) != BZH_OK) break;
+        j.ev[5] = call_mark(ctx);
     }
     if (status != BZH_OK) {
         (void)bzh_stream_wait(st); // (nothing of this call may still run when the error is reported)
@@ -2033,10 +1933,7 @@ static int encode_many(bzh_ctx *ctx, const void *d_in, const size_t *lens, size_
     }
     ctx->many_host.resize(MST_WORDS + 2 * count);
     HIP_TRY(ctx, hipMemcpyAsync(ctx->many_host.data(), mo.state, ctx->many_host.size() * 8, hipMemcpyDeviceToHost, st));
-    if (ctx->profiling) {
-        t2 = bzh_event(ctx);
-        hipEventRecord(t2, st);
-    }
+    hipEvent_t t2 = call_mark(ctx);
     HIP_TRY(ctx, bzh_stream_wait(st));
     const uint64_t *hs = ctx->many_host.data();
     if (hs[MST_OVER]) {
@@ -2049,14 +1946,7 @@ static int encode_many(bzh_ctx *ctx, const void *d_in, const size_t *lens, size_
     }
     ctx->stats.out_bits = hs[MST_BITS];
     if (ctx->profiling) {
-        for (auto &jp : jobs) {
-            RangeJob &job = *jp;
-            ctx->stats.ms_rle1 += span_ms(job.ev[0], job.ev[1]);
-            ctx->stats.ms_bwt += span_ms(job.ev[1], job.ev[2]);
-            ctx->stats.ms_mtf += span_ms(job.ev[2], job.ev[3]);
-            ctx->stats.ms_huff += span_ms(job.ev[3], job.ev[4]);
-            ctx->stats.ms_pack += span_ms(job.ev[4], job.ev[5]);
-        }
+        jobs_ms(ctx, jobs);
         stats_collect_sort(ctx);
         ctx->stats.ms_plan = span_ms(t0, t1);
         ctx->stats.ms_total = span_ms(t0, t2);
@@ -2241,10 +2131,7 @@ static void stream_pass(bzh_ctx *ctx)
         put_be32(seed_be, p.seed);
         uint32_t seed;
         memcpy(&seed, seed_be, 4);
-        memset(&ctx->stats, 0, sizeof ctx->stats);
-        ctx->sort_spans.clear();
-        ctx->evnext = 0;
-        kstats_reset(ctx);
+        stats_begin(ctx);
         BZH_TRY(encode_range(ctx, 0, F, d_o, s.d_out_cap[p.obuf] & ~(size_t)3, p.phase, &p.nbits, p.phase ? &seed : nullptr));
         const uint64_t bits_in_buf = p.phase + p.nbits;
         const size_t full_words = (size_t)(bits_in_buf / 32);
