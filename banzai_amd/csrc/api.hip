@@ -126,133 +126,34 @@ hipStream_t bzh_side_stream(bzh_ctx *ctx)
     return s;
 }
 
-template <typename T>
-static void carve(uint8_t *&p, T *&dst, size_t count)
-{
-    dst = reinterpret_cast<T *>(p);
-    p += align_up(count * sizeof(T), 256);
-}
-
-// Lays the batch arrays out in the arena; with base == nullptr only measures.
-static size_t layout_batch(Batch &bt, uint8_t *base, uint32_t B, uint32_t M)
-{
-    bt.B = B;
-    bt.M = M;
-    bt.S = (uint32_t)align_up((size_t)M + 1, SORT_TILE);
-    bt.TPB = bt.S / SORT_TILE;
-    const size_t S = bt.S, NB = B;
-    const size_t MT = (S + MTF_TILE - 1) / MTF_TILE;
-    const size_t PT = (S + 64 + PACK_TILE - 1) / PACK_TILE;
-    uint8_t *p = base;
-    carve(p, bt.rle, NB * S);
-    carve(p, bt.n, NB);
-    carve(p, bt.bwt, NB * S);
-    carve(p, bt.ptr, NB);
-    carve(p, bt.hasbyte, NB * 256);
-    carve(p, bt.rank, NB * S);
-    carve(p, bt.sa, NB * S);
-    carve(p, bt.headp, NB * S);
-    carve(p, bt.binned, NB * S);
-    carve(p, bt.listA, NB * S);
-    carve(p, bt.listB, NB * S);
-    carve(p, bt.listC, NB * S);
-    carve(p, bt.listD, NB * S);
-    carve(p, bt.hist, NB * 512 * bt.TPB);
-    carve(p, bt.dbase, NB * DB_STRIDE);
-    carve(p, bt.dtot, NB * DB_STRIDE);
-    carve(p, bt.flg, NB * S);
-    carve(p, bt.tagg, NB * bt.TPB);
-    { // round state of the suffix sort: RS_ROWS words per block, contiguous (one memset clears it)
-        uint32_t *rs = nullptr;
-        const size_t oA = (RS_ROWS * NB + 8 + SUMMARY_WORDS + 1) & ~(size_t)1; // 64-bit counter: even word index
-        carve(p, rs, oA + 4);
-        uint32_t **f[RS_ROWS] = {&bt.st_mode, &bt.st_h, &bt.st_nbig, &bt.st_ntail, &bt.c_big, &bt.c_small, &bt.c_tail,
-                                 &bt.c_prog, &bt.gateS, &bt.gateA, &bt.gateR, &bt.gateT, &bt.actS, &bt.actA, &bt.actR,
-                                 &bt.actT, &bt.actQ, nullptr, &bt.c_nolist, &bt.c_groups, &bt.scratch, &bt.st_tdst}; // row 17: sixth list (bwt.hip)
-        for (int k = 0; k < RS_ROWS; k++)
-            if (f[k]) *f[k] = rs ? rs + (size_t)k * NB : nullptr;
-        bt.nlist = rs ? rs + RS_ROWS * NB : nullptr;
-        bt.summary = rs ? rs + RS_ROWS * NB + 8 : nullptr;
-        bt.stat_A = rs ? reinterpret_cast<unsigned long long *>(rs + oA) : nullptr;
-    }
-    carve(p, bt.chain, NB * 4);
-    carve(p, bt.pshrink, NB * 4);
-    carve(p, bt.errflag, 64);
-    carve(p, bt.gidof, NB * S);
-    carve(p, bt.grank, 2 * NB * GID_MAX);
-    carve(p, bt.gcount, NB);
-    carve(p, bt.gwide, 64);
-    { // bucket-first initial sort (bwt_msd.h): only levels whose blocks can reach MS_MIN_N bytes ever use it
-        const size_t MB = M >= MS_MIN_N ? NB : 0;
-        carve(p, bt.ms_bgcur, MB * 65536);
-        carve(p, bt.ms_pool, MB * MS_BG_ROW + (size_t)MS_LEVELS * MB * MS_SEG_SLOTS * MS_SEG_ROW);
-        carve(p, bt.ms_segcur, (size_t)MS_LEVELS * MB * MS_SEG_SLOTS * 256);
-        carve(p, bt.ms_units, MB * MS_UNIT_CAP);
-        carve(p, bt.ms_segs, (size_t)(MS_LEVELS + 1) * MB * MS_SEG_SLOTS);
-        carve(p, bt.ms_items, (size_t)(MS_LEVELS + 1) * MB * MS_ITEM_CAP);
-        carve(p, bt.ms_cnt, MS_CNT_WORDS + (size_t)(MS_LEVELS + 7) * NB + 2 + 6 * NB * MS_UNIT_CAP);
-        carve(p, bt.ms_np, NB);
-        carve(p, bt.ms_old, NB);
-        carve(p, bt.ms_new, NB);
-        carve(p, bt.ms_bincur, NB * 256);
-    }
-    carve(p, bt.mtfpos, NB * S);
-    carve(p, bt.tilelist, NB * MT * 256);
-    carve(p, bt.tinfo, NB * MT * 4);
-    carve(p, bt.syms, NB * (S + 64));
-    carve(p, bt.m, NB);
-    carve(p, bt.freqs, NB * 258);
-    carve(p, bt.nsyms, NB);
-    carve(p, bt.tfreq, NB * 3 * 258);
-    carve(p, bt.lens, NB * 3 * 258);
-    carve(p, bt.lens2, 2 * NB * 3 * 258);
-    carve(p, bt.lfit, 2 * NB * 3);
-    carve(p, bt.ntab, NB);
-    carve(p, bt.codes, NB * 258);
-    carve(p, bt.hdr, NB * HDR_BYTES);
-    carve(p, bt.hdrbits, NB * 4);
-    carve(p, bt.bits, NB);
-    carve(p, bt.bitoff, NB + 1);
-    carve(p, bt.packgate, 4);
-    carve(p, bt.symbits, NB * PT);
-    carve(p, bt.desc, NB);
-    bt.pdesc = bt.desc; // (rle1_emit points it at the plan's descriptors of the batch)
-    { // "fixed" Huffman mode (optional)
-        const size_t selmax = (S + 64 + 49) / 50 + 2;
-        carve(p, bt.fx_tfreq, NB * FX_TABLES * 258);
-        carve(p, bt.fx_lens, NB * FX_TABLES * 258);
-        carve(p, bt.fx_codes, NB * FX_TABLES * 258);
-        carve(p, bt.fx_sel, NB * selmax);
-        carve(p, bt.fx_selbits, NB * align_up((selmax * 6 + 7) / 8 + 8, 64));
-        carve(p, bt.fx_hdr, NB * FX_HDR_BYTES);
-    }
-    return (size_t)(p - base);
-}
-
 // Makes the arena hold batches of `blocks` blocks (at most max_batch).  It only ever grows: to the size asked for,
 // rounded up so that a stream of growing batches does not reallocate every time.  Nothing is in flight on the
 // arena when this is called (every entry point waits for its own work before it returns).
 static int ensure_arena(bzh_ctx *ctx, uint32_t blocks, size_t min_bytes = 0)
 {
     blocks = std::max<uint32_t>(1, std::min<uint32_t>(blocks, ctx->max_batch));
-    if (ctx->arena && blocks <= ctx->arena_blocks && min_bytes <= ctx->arena_size) return BZH_OK;
-    uint32_t want = std::min<uint32_t>(ctx->max_batch, std::max<uint32_t>(blocks, 8));
-    if (want > 8) want = std::min<uint32_t>(ctx->max_batch, (want + 15u) & ~15u);
+    if (ctx->arena && blocks <= ctx->arena_blocks && min_bytes <= ctx->arena.cap) return BZH_OK;
+    const uint32_t want = arena_batch(blocks, ctx->max_batch);
     Batch probe{};
-    const size_t bytes = std::max(layout_batch(probe, nullptr, want, ctx->M), min_bytes);
-    if (ctx->arena) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        hipFree(ctx->arena);
-        ctx->arena = nullptr;
-        ctx->arena_blocks = 0;
+    const char *misfit = nullptr;
+    const size_t bytes = std::max(layout_batch(probe, nullptr, want, ctx->M, &misfit), min_bytes);
+    if (misfit) {
+        bzh_set_error(ctx, "a %u-block workspace at level %d has no room for %s (batch_views)", want, ctx->level, misfit);
+        return BZH_E_STATE;
     }
-    if (hipMalloc((void **)&ctx->arena, bytes) != hipSuccess) {
-        bzh_set_error(ctx, "hipMalloc(%zu) for a %u-block workspace failed", bytes, want);
-        return BZH_E_NOMEM;
-    }
-    ctx->arena_size = bytes;
+    ctx->arena_blocks = 0;
+    BZH_TRY(ctx->arena.reserve(ctx, bytes, "the batch workspace"));
     ctx->arena_blocks = want;
     layout_batch(ctx->bt, ctx->arena, want, ctx->M);
+    return BZH_OK;
+}
+
+// The context's (or a lane's) pinned readback area, cleared: no stale sequence words.
+static int pinned_alloc(bzh_ctx *c)
+{
+    c->h_pinned.flags = hipHostMallocCoherent;
+    BZH_TRY(c->h_pinned.reserve(c, pinned_words(c->max_batch) * sizeof(uint32_t), "the readback area"));
+    memset(c->h_pinned, 0, c->h_pinned.cap);
     return BZH_OK;
 }
 
@@ -275,7 +176,7 @@ extern "C" int bzh_create(bzh_ctx **out, int device, int level, int max_batch)
     // costs about half a millisecond of latency chains whatever its size (the plan, the late doubling rounds, the Huffman
     // heaps), so a long stream is cheaper in few, large batches -- 1 GB on one MI355X: 87.8 ms in batches of 128 blocks,
     // 81.6 ms in 256s, 78.2 ms in 576s (profiles/r06_multibatch.txt).  The arena is sized for the batch actually planned
-    // (ensure_arena: 45 MB a block), so only an input that fills such a batch pays for it: 26 GB of 288 GB.
+    // (ensure_arena: 56 MB a block), so only an input that fills such a batch pays for it: 32 GB of 288 GB.
     ctx->max_batch = max_batch ? (uint32_t)max_batch : std::min<uint32_t>(1024u, 576u * 9u / (uint32_t)level);
     // a streaming pass is worth launching once a full batch of input is pending
     ctx->strm.min_feed = std::min<size_t>((size_t)128 << 20, (size_t)ctx->max_batch * (ctx->M + 1));
@@ -285,17 +186,16 @@ extern "C" int bzh_create(bzh_ctx **out, int device, int level, int max_batch)
         delete ctx;
         return BZH_E_ARG;
     }
-    // The workspace arena (about 45 MB per block of a batch, 5.8 GB for the 112 blocks of a 100 MB input) is NOT allocated here:
+    // The workspace arena (about 56 MB per block of a batch, 6.3 GB for the 112 blocks of a 100 MB input) is NOT allocated here:
     // ensure_arena sizes it for the batches actually planned, so a 1 MB file does not pay for a 128-block arena.
     ctx->S = probe.S;
     ctx->bt.S = probe.S;
     ctx->bt.TPB = probe.TPB;
     ctx->bt.M = ctx->M;
-    if (hipHostMalloc((void **)&ctx->h_pinned, sizeof(uint32_t) * (ctx->max_batch * 8 + 64 + (MAX_ROUNDS + 1) * SUMMARY_WORDS), hipHostMallocCoherent) != hipSuccess) {
+    if (pinned_alloc(ctx) != BZH_OK) {
         delete ctx;
         return BZH_E_NOMEM;
     }
-    memset(ctx->h_pinned, 0, sizeof(uint32_t) * (ctx->max_batch * 8 + 64 + (MAX_ROUNDS + 1) * SUMMARY_WORDS)); // (no stale sequence words)
     *out = ctx;
     return BZH_OK;
     });
@@ -339,28 +239,10 @@ extern "C" void bzh_destroy(bzh_ctx *ctx)
     for (bzh_ctx *l : ctx->lanes) {
         for (hipEvent_t e : l->evpool) hipEventDestroy(e);
         if (l->stream) hipStreamDestroy(l->stream);
-        if (l->h_pinned) hipHostFree(l->h_pinned);
         delete l;
     }
-    if (ctx->arena) hipFree(ctx->arena);
-    if (ctx->plan_ws) hipFree(ctx->plan_ws);
-    if (ctx->many_ws) hipFree(ctx->many_ws);
-    if (ctx->many_out) hipFree(ctx->many_out);
-    if (ctx->d_stage_in) hipFree(ctx->d_stage_in);
-    if (ctx->d_stage_out) hipFree(ctx->d_stage_out);
-    if (ctx->h_pinned) hipHostFree(ctx->h_pinned);
-    if (ctx->crc_host) hipHostFree(ctx->crc_host);
-    if (ctx->d_crctab) hipFree(ctx->d_crctab);
-    if (ctx->dec_ws) hipFree(ctx->dec_ws);
-    if (ctx->dec_list) hipFree(ctx->dec_list);
-    if (ctx->sync_ws) hipFree(ctx->sync_ws);
-    for (int k = 0; k < 2; k++)
-        if (ctx->strm.d_buf[k]) hipFree(ctx->strm.d_buf[k]);
-    if (ctx->strm.h_out) hipHostFree(ctx->strm.h_out);
-    for (int k = 0; k < 2; k++)
-        if (ctx->strm.d_out[k]) hipFree(ctx->strm.d_out[k]);
     if (ctx->strm.copy_stream) hipStreamDestroy(ctx->strm.copy_stream);
-    delete ctx;
+    delete ctx; // (its buffers with it: GrowBuf, common.h)
 }
 
 extern "C" int bzh_set_stream(bzh_ctx *ctx, void *hip_stream)
@@ -489,20 +371,7 @@ static void stats_collect_sort(bzh_ctx *ctx)
     ctx->stats.ms_bwt_sort = ms;
 }
 
-static int ensure_stage(bzh_ctx *ctx, uint8_t *&buf, size_t &cur, size_t need)
-{
-    if (need <= cur) return BZH_OK;
-    if (buf) hipFree(buf);
-    buf = nullptr;
-    cur = 0;
-    size_t want = align_up(need + need / 8 + 4096, 4096);
-    if (hipMalloc((void **)&buf, want) != hipSuccess) {
-        bzh_set_error(ctx, "hipMalloc(%zu) failed", want);
-        return BZH_E_NOMEM;
-    }
-    cur = want;
-    return BZH_OK;
-}
+static int ensure_stage(bzh_ctx *ctx, DevBuf &buf, size_t need) { return buf.reserve(ctx, need, "a staging buffer", grow_eighth); }
 
 // ---- stage seam: BWT ---------------------------------------------------------------------------------
 extern "C" int bzh_bwt_batch(bzh_ctx *ctx, const uint8_t *in, const uint64_t *offs, const uint32_t *lens,
@@ -589,7 +458,7 @@ extern "C" int bzh_unbwt_batch(bzh_ctx *ctx, const uint8_t *bwt, const uint64_t 
         HIP_TRY(ctx, hipMemcpyAsync(bt.ptr, ptr + k0, B * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
         BZH_TRY(unbwt_run(ctx, B, nmax));
         for (uint32_t b = 0; b < B; b++)
-            HIP_TRY(ctx, hipMemcpyAsync(out + offs[k0 + b], bt.mtfpos + (size_t)b * bt.S, lens[k0 + b], hipMemcpyDeviceToHost,
+            HIP_TRY(ctx, hipMemcpyAsync(out + offs[k0 + b], bt.unbwt_out + (size_t)b * bt.S, lens[k0 + b], hipMemcpyDeviceToHost,
                                         ctx->stream));
         HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
     }
@@ -705,7 +574,7 @@ extern "C" int bzh_huffman(bzh_ctx *ctx, const uint16_t *syms, size_t m, uint32_
     HIP_TRY(ctx, hipMemcpyAsync(&total, bt.bitoff + 1, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, bzh_stream_wait(st));
     const size_t bytes = (size_t)((total + 31) / 32 * 4);
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, bytes));
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, bytes));
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_stage_out, 0, bytes, st));
     BZH_TRY(huff_pack(ctx, 1, m32, ctx->d_stage_out, 0));
     std::vector<uint8_t> tmp(bytes + 8, 0);
@@ -813,14 +682,12 @@ static int ensure_lanes(bzh_ctx *ctx)
         l->M = ctx->M;
         l->max_batch = lane_mb;
         l->mode = ctx->mode;
-        layout_batch(l->bt, ctx->arena + (size_t)k * half, lane_mb, ctx->M);
+        layout_batch(l->bt, ctx->arena.p + (size_t)k * half, lane_mb, ctx->M);
         l->S = l->bt.S;
-        if (hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking) != hipSuccess ||
-            hipHostMalloc((void **)&l->h_pinned, sizeof(uint32_t) * (lane_mb * 8 + 64 + (MAX_ROUNDS + 1) * SUMMARY_WORDS), hipHostMallocCoherent) != hipSuccess) {
+        if (hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking) != hipSuccess || pinned_alloc(l) != BZH_OK) {
             delete l;
             return BZH_E_NOMEM;
         }
-        memset(l->h_pinned, 0, sizeof(uint32_t) * (lane_mb * 8 + 64 + (MAX_ROUNDS + 1) * SUMMARY_WORDS));
         ctx->lanes.push_back(l);
     }
     return BZH_OK;
@@ -988,7 +855,7 @@ static int encode_range(bzh_ctx *ctx, size_t b0, size_t b1, uint8_t *d_out, size
     // The pack step of one job, behind its prepare_batch: the job's bits at bit_base + cur, the lane's arena free again.
     auto pack = [&](bzh_ctx *lane, RangeJob &job) -> int {
         hipStream_t st = lane->stream;
-        uint64_t *rec = reinterpret_cast<uint64_t *>(lane->h_pinned); // (the first 64 words of the pinned block are free)
+        uint64_t *rec = lane->h_pinned.as<uint64_t>(); // (the first 64 words of the pinned block are free)
         const uint64_t at = bit_base + cur;
         bool over = false;
         hipError_t he = hipSuccess;
@@ -1296,12 +1163,12 @@ static int encode_host(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out, 
     if (!ctx || (!in && n) || !out || !out_len) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, n + 16));
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, n + 16));
     const size_t dcap = n + n / 4 + (n / ((size_t)ctx->M * 4 / 5) + 2) * 4096 + 65536;
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, dcap));
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, dcap));
     if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, st));
     size_t len = 0;
-    BZH_TRY(encode_device_impl(ctx, ctx->d_stage_in, n, ctx->d_stage_out, ctx->stage_out_size & ~(size_t)3, &len, consumed, ix));
+    BZH_TRY(encode_device_impl(ctx, ctx->d_stage_in, n, ctx->d_stage_out, ctx->d_stage_out.cap & ~(size_t)3, &len, consumed, ix));
     *out_len = len;
     if (len > cap) return BZH_E_CAP;
     HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, len, hipMemcpyDeviceToHost, st));
@@ -1392,7 +1259,7 @@ extern "C" int bzh_rle1_split(bzh_ctx *ctx, const uint8_t *in, size_t n, bzh_blo
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     stats_begin(ctx);
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, n + 16));
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, n + 16));
     if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, st));
     BZH_TRY(rle1_plan(ctx, ctx->d_stage_in, n));
     const size_t nb = ctx->plan_blocks.size();
@@ -1425,7 +1292,7 @@ extern "C" int bzh_crc32(bzh_ctx *ctx, const uint8_t *in, size_t n, uint32_t *cr
     if (ctx) stream_join(ctx);
     if (!ctx || (!in && n) || !crc) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, n + 16));
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, n + 16));
     if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, ctx->stream));
     BZH_TRY(ensure_arena(ctx, 1)); // (crc_device borrows two words of it)
     return crc_device(ctx, ctx->d_stage_in, n, crc);
@@ -1476,8 +1343,8 @@ static int decode_call_end(bzh_ctx *ctx, const DecodeCall &c, int rc)
 // The host variants: the input into the staging buffer (queued), room for out_bytes of output in the other one.
 static int decode_stage(bzh_ctx *ctx, const uint8_t *in, size_t n, size_t out_bytes = 0)
 {
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, n + 16));
-    if (out_bytes) BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, out_bytes));
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, n + 16));
+    if (out_bytes) BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, out_bytes));
     if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, in, n, hipMemcpyHostToDevice, ctx->stream));
     return BZH_OK;
 }
@@ -1751,8 +1618,8 @@ extern "C" int bzh_decode_many(bzh_ctx *ctx, const uint8_t *const *ins, const si
         total += lens[k];
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, total + 16));
-    if (cap) BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, cap));
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, total + 16));
+    if (cap) BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, cap));
     if (total) { // all inputs in one copy, back to back
         ctx->many_pack.resize(total);
         for (size_t k = 0; k < count; k++)
@@ -1888,18 +1755,9 @@ static int encode_many(bzh_ctx *ctx, const void *d_in, const size_t *lens, size_
     hipEvent_t t1 = call_mark(ctx);
     // state | offs | lens | body | crc
     const size_t words = MST_WORDS + 3 * count + (count + 1) / 2;
-    if (words * 8 > ctx->many_out_size) {
-        if (ctx->many_out) hipFree(ctx->many_out);
-        ctx->many_out = nullptr;
-        ctx->many_out_size = 0;
-        if (hipMalloc((void **)&ctx->many_out, words * 8) != hipSuccess) {
-            bzh_set_error(ctx, "hipMalloc(%zu) for the layout of %zu streams failed", words * 8, count);
-            return BZH_E_NOMEM;
-        }
-        ctx->many_out_size = words * 8;
-    }
+    BZH_TRY(ctx->many_out.reserve(ctx, words * 8, "the layout of the streams"));
     ManyOut mo;
-    mo.state = reinterpret_cast<uint64_t *>(ctx->many_out);
+    mo.state = ctx->many_out.as<uint64_t>();
     mo.offs = mo.state + MST_WORDS;
     mo.lens = mo.offs + count;
     mo.body = mo.lens + count;
@@ -1984,8 +1842,8 @@ extern "C" int bzh_encode_many(bzh_ctx *ctx, const uint8_t *const *ins, const si
         }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, ctx->stage_in_size, total + 16));
-    BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, ctx->stage_out_size, bzh_encode_many_bound(ctx->level, lens, count) + 16));
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, total + 16));
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, bzh_encode_many_bound(ctx->level, lens, count) + 16));
     if (total) { // all inputs in one copy
         ctx->many_pack.resize(total);
         size_t pos = 0;
@@ -1995,7 +1853,7 @@ extern "C" int bzh_encode_many(bzh_ctx *ctx, const uint8_t *const *ins, const si
         }
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, ctx->many_pack.data(), total, hipMemcpyHostToDevice, st));
     }
-    BZH_TRY(encode_many(ctx, ctx->d_stage_in, lens, count, ctx->d_stage_out, ctx->stage_out_size & ~(size_t)3, out_offs, out_lens));
+    BZH_TRY(encode_many(ctx, ctx->d_stage_in, lens, count, ctx->d_stage_out, ctx->d_stage_out.cap & ~(size_t)3, out_offs, out_lens));
     const size_t need = count ? out_offs[count - 1] + out_lens[count - 1] : 0;
     if (need > cap) {
         bzh_set_error(ctx, "output needs %zu bytes, more than the %zu given", need, cap);
@@ -2080,19 +1938,14 @@ static int stream_reserve(bzh_ctx *ctx, size_t head, size_t extra)
 {
     auto &s = ctx->strm;
     const int f = s.fill;
-    if (s.d_buf[f] && head <= s.head && s.head + s.pending + extra + 16 <= s.cap[f]) return BZH_OK;
+    if (s.d_buf[f] && head <= s.head && s.head + s.pending + extra + 16 <= s.d_buf[f].cap) return BZH_OK;
     const size_t nhead = align_up(std::max(head, std::max(s.head, STREAM_HEAD)), 4096);
     const size_t want = align_up(nhead + std::max(s.pending + extra, s.min_feed) + ((size_t)16 << 20), 4096);
-    uint8_t *nb = nullptr;
-    if (hipMalloc((void **)&nb, want) != hipSuccess) {
-        bzh_set_error(ctx, "hipMalloc(%zu) failed", want);
-        return BZH_E_NOMEM;
-    }
-    if (s.pending) HIP_TRY(ctx, hipMemcpyAsync(nb + nhead, s.d_buf[f] + s.head, s.pending, hipMemcpyDeviceToDevice, s.copy_stream));
+    DevBuf nb; // (a fresh one: the pending bytes move over on the copy stream, the pass in flight on ctx->stream is not waited for)
+    BZH_TRY(nb.reserve(ctx, want, "the fed bytes of a stream"));
+    if (s.pending) HIP_TRY(ctx, hipMemcpyAsync(nb.p + nhead, s.d_buf[f].p + s.head, s.pending, hipMemcpyDeviceToDevice, s.copy_stream));
     HIP_TRY(ctx, bzh_stream_wait(s.copy_stream));
-    if (s.d_buf[f]) hipFree(s.d_buf[f]);
-    s.d_buf[f] = nb;
-    s.cap[f] = want;
+    std::swap(nb.p, s.d_buf[f].p), std::swap(nb.cap, s.d_buf[f].cap);
     s.head = nhead;
     return BZH_OK;
 }
@@ -2125,23 +1978,17 @@ static void stream_pass(bzh_ctx *ctx)
         size_t raw = 0;
         for (size_t k = 0; k < F; k++) raw += ctx->plan_blocks[k].in_len;
         const size_t dcap = (raw + raw / 4 + (F + 2) * 4096 + 65536) & ~(size_t)3;
-        BZH_TRY(ensure_stage(ctx, s.d_out[p.obuf], s.d_out_cap[p.obuf], dcap));
+        BZH_TRY(ensure_stage(ctx, s.d_out[p.obuf], dcap));
         uint8_t *d_o = s.d_out[p.obuf];
         uint8_t seed_be[4];
         put_be32(seed_be, p.seed);
         uint32_t seed;
         memcpy(&seed, seed_be, 4);
         stats_begin(ctx);
-        BZH_TRY(encode_range(ctx, 0, F, d_o, s.d_out_cap[p.obuf] & ~(size_t)3, p.phase, &p.nbits, p.phase ? &seed : nullptr));
+        BZH_TRY(encode_range(ctx, 0, F, d_o, s.d_out[p.obuf].cap & ~(size_t)3, p.phase, &p.nbits, p.phase ? &seed : nullptr));
         const uint64_t bits_in_buf = p.phase + p.nbits;
         const size_t full_words = (size_t)(bits_in_buf / 32);
-        if (!s.h_out) {
-            if (hipHostMalloc((void **)&s.h_out, 4096) != hipSuccess) {
-                bzh_set_error(ctx, "hipHostMalloc(4096) failed");
-                return BZH_E_NOMEM;
-            }
-            s.h_out_cap = 4096;
-        }
+        BZH_TRY(s.h_out.reserve(ctx, 4096, "a pass's last word"));
         // the whole words stay on the device until the caller's next feed collects them; only the partial word behind
         // them (it seeds the next pass) comes back now
         if (bits_in_buf & 31u) HIP_TRY(ctx, hipMemcpyAsync(s.h_out, d_o + full_words * 4, 4, hipMemcpyDeviceToHost, st));

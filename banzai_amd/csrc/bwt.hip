@@ -2421,7 +2421,7 @@ __global__ void __launch_bounds__(1024) round_begin(Batch bt, uint32_t B, uint32
 // (a hipMemsetAsync is a kernel of its own, about 5 us each back to back: eight of them were 45 us of every step)
 constexpr int CLEAR_MAX = 16;
 struct ClearArgs {
-    uint4 *p[CLEAR_MAX];         // 16-byte aligned regions (carved at 256-byte boundaries: layout_batch, api.hip -- a length
+    uint4 *p[CLEAR_MAX];         // 16-byte aligned regions (carved at 256-byte boundaries: layout_batch, batch.h -- a length
                                  // rounded up to 16 bytes stays inside the region's own carve)
     unsigned long long q[CLEAR_MAX]; // their lengths in 16-byte words, as a running total (region k = [q[k-1], q[k]))
     int n;
@@ -2620,11 +2620,10 @@ struct SortAttempt {
     uint32_t B, nmax;
     uint64_t ntotal, ntotal_old = 0; // (statistics only)
     const Lst all{nullptr, nullptr, B};
-    u64 *bufA = reinterpret_cast<u64 *>(bt.listA), *bufB = reinterpret_cast<u64 *>(bt.listB);
-    u64 *bufC = reinterpret_cast<u64 *>(bt.listC), *bufD = reinterpret_cast<u64 *>(bt.listD);
-    u64 *binned = reinterpret_cast<u64 *>(bt.binned);
+    u64 *bufA = list_words(bt.listA), *bufB = list_words(bt.listB), *bufC = list_words(bt.listC), *bufD = list_words(bt.listD);
+    u64 *binned = list_words(bt.binned);
     uint32_t *actP = bt.actQ + bt.B; // sixth list, behind the five named ones (rows of the layout are bt.B apart)
-    volatile uint32_t *hsum = ctx->h_pinned + (size_t)ctx->max_batch * 8 + 64; // [MAX_ROUNDS][SUMMARY_WORDS] (+ one record of the initial sort's plan)
+    volatile uint32_t *hsum = ctx->h_pinned.as<uint32_t>() + (size_t)ctx->max_batch * 8 + 64; // [MAX_ROUNDS][SUMMARY_WORDS] (+ one record of the initial sort's plan)
     uint32_t epoch = (++ctx->bwt_epoch & 0xFFFFFFu) << 6;
     hipStream_t st = ctx->stream, side = nullptr, side2 = nullptr;
     bool side_busy = false, side2_busy = false; // given work that the main stream has not waited for yet
@@ -2667,16 +2666,16 @@ struct SortAttempt {
         a.cnt = bt.n;
         a.lst = all;
         a.shift = 20;
-        a.gst = reinterpret_cast<u64 *>(bt.tagg); // (flag_tiles / flag_carry use it after the initial sort only)
+        a.gst = refine_carry(bt); // (flag_tiles / flag_carry use it after the initial sort only)
         a.chain = bt.chain;
         a.fault = ctx->debug_fault; // (one batch only)
         a.patient = ctx->no_spread ? 1u : 0u;
         had_fault = a.fault == 1u; // (kind 2: the fault of a shared GPU -- the sort is expected to recover by itself)
         ctx->debug_fault = 0;
-        a.clist = reinterpret_cast<const uint32_t *>(bt.listD); // (a block in SWEEP mode has no small-group lists)
+        a.clist = sweep_clist(bt); // (a block in SWEEP mode has no small-group lists)
         a.src = nullptr;
         a.dst = bufA;
-        a.look = reinterpret_cast<u64 *>(bt.hist);
+        a.look = sort_look(bt);
         a.dbase = bt.dbase;
         a.doff = 0;
         a.err = bt.errflag;
@@ -2735,8 +2734,8 @@ struct SortAttempt {
         r.grank = bt.grank;
         r.gwide = bt.gwide;
         r.init = 1;
-        r.cstat = reinterpret_cast<u64 *>(bt.hist);
-        r.carry = reinterpret_cast<u64 *>(bt.tagg);
+        r.cstat = sort_look(bt);
+        r.carry = refine_carry(bt);
         r.err = bt.errflag;
         r.patient = a.patient;
 
@@ -2894,7 +2893,7 @@ struct SortAttempt {
         r.bpass = ++a.pass;
         if (nOld) {
             KSpan ks(ctx, K_REFINE_INIT, 24 * ntotal_old);
-            r.dig = reinterpret_cast<uint32_t *>(bt.flg); // (the digit rows of the initial refinement: the flag bytes are free, `hist` holds its look-back words)
+            r.dig = init_digits(bt); // (the digit rows of the initial refinement: the flag bytes are free, `hist` holds its look-back words)
             r.dig_stride = bt.S / 4;
             launch_refine_one<true>(ctx, so, r, nOld, nmax, binned);
             r.dig = bt.hist;
@@ -2950,13 +2949,13 @@ struct SortAttempt {
             // there (refine_one<init> leaves them for every block on the 8 passes); the rows become the bases of the passes
             RefineArgs r0 = r;
             r0.cnt = bt.n;
-            r0.dig = reinterpret_cast<uint32_t *>(bt.flg);
+            r0.dig = init_digits(bt);
             r0.dig_stride = bt.S / 4;
             r0.lst = ls;
             sweep_bases<<<dim3(nS), 768, 0, st>>>(r0, bt.dbase); // (before period_probe: it uses the flag bytes next)
         }
         // near-periodic blocks are finished in this round (period_probe sets their depth to "h >= n")
-        const ProbeArgs pr{bt.rle, bt.n, bt.rank, bt.sa, bt.headp, bt.st_h, bt.chain, reinterpret_cast<uint32_t *>(bt.listD), bt.flg, bt.S, ls};
+        const ProbeArgs pr{bt.rle, bt.n, bt.rank, bt.sa, bt.headp, bt.st_h, bt.chain, sweep_clist(bt), bt.flg, bt.S, ls};
         period_probe<<<dim3(nS), 1024, 0, st>>>(pr);
         a.lst = ls;
         a.cnt = bt.n; // enumerate SA positions
@@ -3387,7 +3386,7 @@ __global__ void __launch_bounds__(256) count_mismatch(const uint8_t *x, const ui
     if ((threadIdx.x & 63) == 0 && bad) atomicAdd(acc, (unsigned long long)bad);
 }
 
-// Inverse BWT of blocks 0..B-1 of the batch: reads bt.bwt / bt.ptr / bt.n, leaves the blocks in bt.mtfpos
+// Inverse BWT of blocks 0..B-1 of the batch: reads bt.bwt / bt.ptr / bt.n, leaves the blocks in bt.unbwt_out
 // (scratch of the forward path).  Uses the sort buffers and rank / sa / headp as work arrays.
 int unbwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax)
 {
@@ -3399,7 +3398,7 @@ int unbwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax)
     }
     hipStream_t st = ctx->stream;
     const Lst all{nullptr, nullptr, B};
-    u64 *bufA = reinterpret_cast<u64 *>(bt.listA);
+    u64 *bufA = list_words(bt.listA);
     SortArgs a{};
     a.blk = bt.bwt;
     a.n = bt.n;
@@ -3410,7 +3409,7 @@ int unbwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax)
     a.shift = 32;
     a.src = nullptr;
     a.dst = bufA;
-    a.look = reinterpret_cast<u64 *>(bt.hist);
+    a.look = sort_look(bt);
     a.dbase = bt.dbase;
     a.doff = 0;
     a.err = bt.errflag;
@@ -3429,7 +3428,7 @@ int unbwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax)
     u.P = bt.rank;
     u.P2 = bt.sa;
     u.X = bt.headp;
-    u.out = bt.mtfpos;
+    u.out = bt.unbwt_out;
     u.S = bt.S;
     const dim3 grid(std::min<uint32_t>((nmax + 1023) / 1024, 512), B);
     unbwt_init<<<grid, 256, 0, st>>>(u);
@@ -3451,7 +3450,7 @@ int unbwt_compare(bzh_ctx *ctx, uint32_t B, uint32_t nmax, unsigned long long *d
     Batch &bt = ctx->bt;
     if (B == 0 || nmax == 0) return BZH_OK;
     const dim3 grid(std::min<uint32_t>((nmax + 1023) / 1024, 512), B);
-    count_mismatch<<<grid, 256, 0, ctx->stream>>>(bt.rle, bt.mtfpos, bt.n, bt.S, d_acc);
+    count_mismatch<<<grid, 256, 0, ctx->stream>>>(bt.rle, bt.unbwt_out, bt.n, bt.S, d_acc);
     HIP_TRY(ctx, hipGetLastError());
     return BZH_OK;
 }

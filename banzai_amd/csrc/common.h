@@ -44,151 +44,32 @@ static inline hipError_t bzh_stream_wait(hipStream_t st)
         if (s_ != BZH_OK) return s_;                                                               \
     } while (0)
 
-// ---- geometry -----------------------------------------------------------------------------
-// Every per-block device array uses one stride S (bytes/elements per bzip2 block), a multiple
-// of the sort tile so tiles never straddle blocks.
-constexpr int SORT_THREADS = 512;
-constexpr int DB_STRIDE = 1280; // digit-base entries per block: up to 5 digits x 256 values
-constexpr int SORT_ITEMS = 16;
-constexpr int SORT_TILE = SORT_THREADS * SORT_ITEMS; // 8192 elements per workgroup (512 x 16: halves the look-back /
-                                                     // scan overhead per element against 256 x 16, -7 % on the bench)
-constexpr uint32_t RANK_RESOLVED = 0x80000000u;      // suffix is alone in its group
-constexpr uint32_t RANK_EMITTED = 31u << 26;         // (with RANK_RESOLVED, less = 0) its byte of the last column has been written (chunk_finish)
-constexpr int SUMMARY_WORDS = 24; // round summary: see round_begin (bwt.hip)
-constexpr uint32_t GID_MAX = 4096;  // large groups of a block a round can number densely (12 key bits)
-constexpr int RS_ROWS = 22;       // per-block rows of the suffix sort's round state (layout_batch, api.hip)
-constexpr uint32_t MS_BG_ROW = 65552, MS_LEVELS = 5, MS_SEG_SLOTS = 112, MS_SEG_ROW = 264, MS_UNIT_CAP = 4096, MS_ITEM_CAP = 224,
-                   MS_CNT_WORDS = 48, MS_MIN_N = 131072; // (levels whose blocks stay below MS_MIN_N bytes keep the 8-pass path: no tables for them)
-constexpr int MAX_ROUNDS = 30; // depth 8 doubles every round and ends at 2^20; < 31 keeps the rank words' round tags unique
-
-struct BlockDesc { // device-side description of one planned block (mirrors bzh_block + restart info)
-    uint64_t in_off;
-    uint64_t in_len;
-    uint32_t rle_len;
-    uint32_t crc;
+// ---- grow-only buffers ---------------------------------------------------------------------------------------------------
+// Memory a context keeps between calls and only ever grows: device memory, or pinned host memory (PinnedBuf).  reserve() is the
+// one place that allocates: nothing happens while the capacity suffices; otherwise the context's stream is waited for, the old
+// allocation freed and `grow(need)` bytes -- `need` itself without a policy -- allocated.  On failure the buffer is left empty,
+// the error text names `what`, BZH_E_NOMEM comes back.  The destructor frees (bzh_destroy makes the device current first).
+static inline size_t grow_eighth(size_t need) { return (need + need / 8 + 4096 + 4095) / 4096 * 4096; } // staging: a stream of growing calls does not reallocate every time
+static inline size_t grow_mib(size_t need) { return (need + 0xFFFFF) & ~(size_t)0xFFFFF; }               // the sync-point recorder
+static inline size_t grow_double(size_t need) { return need * 2; }                                        // the pinned landing place of the block CRCs
+template <bool PINNED>
+struct GrowBuf {
+    uint8_t *p = nullptr;
+    size_t cap = 0;
+    unsigned flags = 0; // PinnedBuf: hipHostMalloc flags
+    GrowBuf() = default;
+    GrowBuf(GrowBuf &&o) noexcept : p(o.p), cap(o.cap), flags(o.flags) { o.p = nullptr, o.cap = 0; }
+    ~GrowBuf() { release(); }
+    int reserve(bzh_ctx *ctx, size_t need, const char *what, size_t (*grow)(size_t) = nullptr); // (ctx may be null: no stream to wait for, no text)
+    void release() { if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p)); p = nullptr, cap = 0; }
+    template <typename T>
+    T *as() const { return reinterpret_cast<T *>(p); }
+    operator uint8_t *() const { return p; }
 };
+using DevBuf = GrowBuf<false>;
+using PinnedBuf = GrowBuf<true>;
 
-// Device arrays of one batch of B blocks.  Passed to kernels by value.
-struct Batch {
-    uint32_t B;       // blocks in this batch
-    uint32_t S;       // stride (elements) between blocks in per-block arrays
-    uint32_t TPB;     // sort tiles per block stride (S / SORT_TILE)
-    uint32_t M;       // max RLE1 bytes per block (100000*level-1)
-    uint8_t *rle;     // [B][S]  RLE1 output = BWT input
-    uint32_t *n;      // [B]     RLE1 length per block
-    uint8_t *bwt;     // [B][S]
-    uint32_t *ptr;    // [B]
-    uint8_t *hasbyte; // [B][256]
-    // suffix sorting
-    uint32_t *rank; // [B][S]
-    uint32_t *sa;   // [B][S]
-    uint32_t *headp; // [B][S] group rank by SA position (SWEEP rounds read it instead of gathering)
-    uint2 *binned;   // [B][S] (rank word, suffix) pairs of the initial sort, binned by 4096-suffix window (rank_apply); memory of
-                     //        its own since round 5: a block on the 8 passes leaves its SA order in sa / headp at the same time
-    uint2 *listA;   // [B][S] sort elements (ping-pong of the radix passes; the big-group list between rounds)
-    uint2 *listB;   // [B][S]
-    uint2 *listC;   // [B][S] small-group (TAIL) list of the block
-    uint2 *listD;   // [B][S] TAIL records of the round in flight
-    uint32_t *hist; // [B][TPB][512]: 2 KiB per sort tile -- look-back status words (256 x u64) or refine digit rows
-    uint32_t *dbase; // [B][DB_STRIDE] digit bases of the look-back passes
-    uint32_t *dtot;  // [B][DB_STRIDE] digit totals of an ACTIVE round (5 digits x 256)
-    uint8_t *flg;   // [B][S]
-    int4 *tagg;     // [B][TPB] tile carries: last group start / last boundary before the tile, first boundary after it
-    // Round state of the suffix sort, all [B] unless noted.  The rounds are driven from the device: round_begin
-    // turns the counters of the round before into this round's work lists, the host only sizes the launches
-    // from a summary it reads one round late.
-    uint32_t *st_mode;  // 0: whole block on the radix path, SA-order enumeration (SWEEP); 1: groups routed by size (SPLIT)
-    uint32_t *st_h;     // depth of the block's next round
-    uint32_t *st_nbig;  // records in the big-group list (SPLIT) / unresolved suffixes (SWEEP)
-    uint32_t *st_ntail; // records in the small-group list
-    uint32_t *st_tdst;  // which of listC (0) / listD (1) receives the block's small-group records this round: the survivors of
-                        // tail_round (which reads the other one) and what refine appends; a block whose small groups sit a
-                        // round out keeps its list where it is (round_begin)
-    uint32_t *c_big, *c_small, *c_tail, *c_prog; // produced by a round: list lengths, "some group was refined"
-    uint32_t *c_nolist; // produced by a round: refine did not write the block's lists (SWEEP mode, mostly large groups)
-    uint32_t *c_groups; // groups of the block after the initial sort (refine_one<init>; round_begin picks the first mode)
-    uint32_t *scratch;  // a row nobody reads
-    uint32_t *chain;    // [B][4] near-periodic blocks: flags, period, leading tails (period_probe, bwt.hip)
-    uint32_t *pshrink;  // [B][4] blocks sorted as eight of their periods: flags, period, the block's real length, periods kept (period_detect / period_expand)
-    uint32_t *gateS, *gateA, *gateR, *gateT;     // this round: sorted-list length per path (0 = not on that path)
-    uint32_t *actS, *actA, *actR, *actT, *actQ;  // this round: ids of the blocks on each path (Q: TAIL at depth x4)
-    uint32_t *nlist;    // [8] lengths of those lists (S, A, R, T, Q)
-    uint32_t *summary;  // [SUMMARY_WORDS] what the host reads, one round late
-    unsigned long long *stat_A; // [1] sum over rounds of the unresolved suffixes entering them
-    uint32_t *errflag; // [1]
-    // Numbers for the large groups of a round (bwt.hip): whoever writes a large group to a big list (chunk_finish,
-    // refine_one, refine) draws a number for it -- one atomic add per GROUP -- and leaves number -> rank and rank -> number;
-    // the big lists are then sorted on [number : 12][key2 : 20] in FOUR 8-bit passes instead of on [rank : 20][key2 : 20]
-    // in five.  (The order of the groups among each other does not matter: only that a group's records meet.)
-    uint16_t *gidof;   // [B][S]  number of the large group whose rank this is (written for the ranks of large groups only)
-    uint32_t *grank;   // [2][B][GID_MAX] rank of every numbered group; [round & 1]: a round's refine_one reads one half
-                       //         while it fills the other for the next round
-    uint32_t *gcount;  // [B]     numbers drawn for the lists being written (round_begin clears it)
-    uint32_t *gwide;   // [2]     [round & 1] != 0: some block ran out of numbers for that round: its lists are sorted on ranks
-    // bucket-first initial sort (bwt_msd.h): 2-byte buckets, oversized buckets split level by level, every bucket
-    // that fits a tile finished inside one workgroup
-    uint32_t *ms_bgcur;  // [B][65536] bigram counts, then claim cursors of the partition
-    uint32_t *ms_pool;   // bucket starts: [B][MS_BG_ROW] (2-byte buckets), then [MS_LEVELS][B][MS_SEG_SLOTS][MS_SEG_ROW]
-    uint32_t *ms_segcur; // [MS_LEVELS][B][MS_SEG_SLOTS][256] digit counts of an oversized bucket, then claim cursors
-    uint4 *ms_units;     // [B * MS_UNIT_CAP] work list of the finishing kernel
-    uint4 *ms_segs;      // [MS_LEVELS + 1][B * MS_SEG_SLOTS] oversized buckets per level
-    uint32_t *ms_items;  // [MS_LEVELS + 1][B * MS_ITEM_CAP] (oversized bucket, tile) pairs per level
-    uint32_t *ms_cnt;    // [MS_CNT_WORDS + (MS_LEVELS + 7) * B] counters; behind the first MS_CNT_WORDS per block: units, slot counters
-                         // of the levels, unit tickets, "holds a group that spans several units", tickets and tile counts of
-                         // mid_sort, records | runs << 20 of the big list being written (two rows, by round parity); then
-                         // [3][B][MS_UNIT_CAP] x 2 words: the runs of those lists (two halves) and the tiles mid_plan packs them
-                         // into (bwt.hip: msc_* accessors)
-    uint32_t *ms_np;     // [B] 1: the block takes the bucket-first path (its first doubling round has depth 7)
-    uint32_t *ms_old, *ms_new; // [B] ids of the blocks on the 8-pass path / on the bucket-first path
-    uint32_t *ms_bincur; // [B][256] rank binning: pairs already claimed in each 4096-suffix window
-    // MTF / RLE2
-    uint8_t *mtfpos;   // [B][S]   where the inverse-BWT tooling leaves its blocks (unbwt_run / unbwt_compare, bzh_unbwt: api.hip); MTF + RLE2
-                       //          keep no position per byte (mtf.hip)
-    uint8_t *tilelist; // [B][MT][256] recency list at each MTF tile entry
-    uint32_t *tinfo;   // [B][MT][4] per-tile zero-run bookkeeping
-    uint16_t *syms;    // [B][S+64]
-    uint32_t *m;       // [B]   symbol count incl. EOB
-    uint32_t *freqs;   // [B][258]
-    uint32_t *nsyms;   // [B]
-    // Huffman
-    uint32_t *tfreq;   // [B][3][258]
-    uint8_t *lens;     // [B][3][258]
-    uint8_t *lens2;    // [2][B][3][258] huff_build: what each half of a block's attempts found (huff_header picks)
-    uint32_t *lfit;    // [2][B][3] the scaling exponent that half found to fit (0xFFFFFFFF: none)
-    uint32_t *ntab;    // [B]
-    uint32_t *codes;   // [B][258]  (len << 24 | word) for table 0
-    uint8_t *hdr;      // [B][HDR_BYTES] per-block header bits (block header .. coding tables)
-    uint32_t *hdrbits; // [B][4] bits of part A, selector count, bits of part B, payload bits
-    uint64_t *bits;    // [B]   total bits of the block
-    uint64_t *bitoff;  // [B+1] exclusive scan of bits
-    uint32_t *packgate; // [1] pack_gate: 1 = the batch's bits fit the output (the pack kernels of a gated call write nothing otherwise)
-    uint32_t *symbits; // [B][PT] per pack tile bit counts
-    BlockDesc *desc;   // [B]
-    const BlockDesc *pdesc; // [B] where the block CRCs are read from: the plan's descriptors of this batch (rle1_emit; the CRCs may
-                            //     arrive there on a side stream while the batch is already being sorted) or `desc` itself (stage seams)
-    // "fixed" Huffman mode only (bzh_set_mode) -- the default path never touches these
-    uint32_t *fx_tfreq;  // [B][6][258]
-    uint8_t *fx_lens;    // [B][6][258]
-    uint32_t *fx_codes;  // [B][6][258] (len << 24 | word)
-    uint8_t *fx_sel;     // [B][FX_SELMAX] table of every 50-symbol segment
-    uint8_t *fx_selbits; // [B][FX_SELBYTES] selectors, MTF + unary coded, as a bit string
-    uint8_t *fx_hdr;     // [B][FX_HDR_BYTES] block header .. selector count, then the delta-coded tables
-};
-
-constexpr uint32_t MTF_TILE = 2048;  // BWT bytes walked by one wavefront (twice that in batches of 64 blocks and more: mtf_run)
-static inline uint32_t mtf_tile_bytes(uint32_t B) { return B >= 64u ? 2u * MTF_TILE : MTF_TILE; } // the tile of a batch of B blocks (mtf_run)
-// RLE2 layout of one MTF tile (mtf_tile_last -> mtf_prefix -> mtf_walk_par; read back by sync_emit)
-struct MtfTile {
-    int first;    // position in the block of the tile's first run head, -1 if none
-    int last;     // of its last one, -1 if none; after mtf_prefix: the last run head BEFORE the tile
-    uint32_t cnt; // symbols the tile emits, not counting the zero-run digits in front of `first`
-    uint32_t off; // after mtf_prefix: output offset of the tile
-};
-constexpr uint32_t HDR_BYTES = 4160; // 64 B block header/symbol map/counts + up to 3 delta-coded tables (< 25.6 kbit)
-constexpr uint32_t PACK_TILE = 4096; // MTF symbols packed by one workgroup
-constexpr uint32_t FX_TABLES = 6;         // lib/huffman.rs:319-326 allows 2..6 tables
-constexpr uint32_t FX_HDR_A = 64;         // bytes reserved for the part before the selectors
-constexpr uint32_t FX_HDR_BYTES = 64 + 6 * 1152; // + up to 6 delta-coded tables (<= 5 + 258 * 35 bits each)
+#include "batch.h" // geometry, Batch and its layout, the carver: host-only text (tests/workspace_host)
 
 // Kernel classes of the per-kernel roofline table (bzh_get_kernel_stats).  With profiling on, the launches of a
 // class are bracketed by HIP events on the context's stream (KSpan); `bytes` = ALGORITHMIC bytes the launches move
@@ -259,16 +140,15 @@ struct bzh_ctx {
     // written -- and the table prefetch of the split run on the second stream between these events
     hipEvent_t plan_ev[2] = {nullptr, nullptr};
     bool crc_pending = false;           // the CRCs of the current plan are on their way (rle1_plan_crc_join collects them)
-    uint8_t *crc_host = nullptr;        // their landing place: PINNED (a copy to pageable memory holds the host until it is done)
-    size_t crc_host_cap = 0, crc_host_len = 0;
+    PinnedBuf crc_host;                 // their landing place: PINNED (a copy to pageable memory holds the host until it is done)
+    size_t crc_host_len = 0;
     int profiling = 0;
     int mode = 0;                     // BZH_MODE_REFERENCE / BZH_MODE_FIXED (bzh_set_mode)
     char err[512] = {0};      // last failure (guarded by err_mu: the streaming worker writes it too)
     char err_out[512] = {0};  // copy handed out by bzh_last_error
     std::mutex err_mu;
     // arena
-    uint8_t *arena = nullptr;
-    size_t arena_size = 0;
+    DevBuf arena;
     uint32_t arena_blocks = 0;        // blocks per batch the arena is laid out for (ensure_arena, api.hip)
     Batch bt{};
     // plan
@@ -279,33 +159,24 @@ struct bzh_ctx {
     std::vector<uint8_t> plan_open;     // per block: 1 = cut not final unless the input ends here
     std::vector<uint8_t> plan_host;     // host copy of the plan's device records (scratch of rle1_plan)
     std::vector<uint8_t> plan_crc_ok;   // per block: CRC computed (bzh_plan_device_nocrc leaves them to the encoder)
-    void *plan_ws = nullptr;            // device scratch of the plan (run tables)
-    size_t plan_ws_size = 0;
+    DevBuf plan_ws;                     // device scratch of the plan (run tables)
     uint32_t plan_extra = 0;            // block records the plan holds beyond one stream's bound (a plan of many inputs: one an input)
     std::vector<uint32_t> plan_input;   // a plan of many inputs: the input of every block (empty for a plan of one buffer)
     // many inputs (bzh_encode_many*, rle1_plan_many)
-    uint8_t *many_ws = nullptr;         // device: guarded input buffer, input table, split records, block -> input
-    size_t many_ws_size = 0;
+    DevBuf many_ws;                     // device: guarded input buffer, input table, split records, block -> input
     uint32_t *many_binp = nullptr;      // [blocks] input of every block of the plan (in many_ws)
     std::vector<uint32_t> many_tab;     // host copy of the input table (source of an async copy: lives in the context)
-    uint8_t *many_out = nullptr;        // device: ManyOut arrays
-    size_t many_out_size = 0;
+    DevBuf many_out;                    // device: ManyOut arrays
     std::vector<uint64_t> many_host;    // state | offs | lens read back at the end of a call
     std::vector<uint8_t> many_pack;     // bzh_encode_many: the host inputs back to back (one H2D)
     // staging
-    uint8_t *d_stage_in = nullptr;
-    size_t stage_in_size = 0;
-    uint8_t *d_stage_out = nullptr;
-    size_t stage_out_size = 0;
-    uint32_t *h_pinned = nullptr; // small pinned readback area
-    void *d_crctab = nullptr;     // GF(2) tables of the block CRC (rle1.hip)
+    DevBuf d_stage_in, d_stage_out;
+    PinnedBuf h_pinned;           // small pinned readback area: pinned_words(max_batch) 32-bit words (pinned_alloc, api.hip)
+    DevBuf d_crctab;              // GF(2) tables of the block CRC (rle1.hip)
     // decode (decode.hip): allocated by the first decode, so an encode-only user pays nothing
-    uint8_t *dec_ws = nullptr;    // per-batch tables: candidates, results, tile maps / counts / offsets, CRC descriptors
-    size_t dec_ws_size = 0;
-    uint64_t *dec_list = nullptr; // the scan's hit list
-    size_t dec_list_cap = 0;
-    uint8_t *sync_ws = nullptr;   // sync points (allocated on first use): the recorder's slots, or a range's headers, points and segments
-    size_t sync_ws_size = 0;
+    DevBuf dec_ws;                // per-batch tables: candidates, results, tile maps / counts / offsets, CRC descriptors
+    DevBuf dec_list;              // the scan's hit list (64-bit words)
+    DevBuf sync_ws;               // sync points (allocated on first use): the recorder's slots, a range's headers, points and segments, or an encoded batch's points
     bzh_decode_stats dstats{};
     bzh_decode_many_stats mstats{}; // of the last bzh_decode_many* call
     // streaming encode (bzh_stream_*)
@@ -314,8 +185,7 @@ struct bzh_ctx {
         // Two device buffers.  d_buf[fill] receives the fed bytes from offset `head` on (copy stream);
         // when a pass starts, the unconsumed tail of the previous pass is placed right before `head`,
         // so the pass sees one contiguous range.  The previous pass's buffer is free again by then.
-        uint8_t *d_buf[2] = {nullptr, nullptr};
-        size_t cap[2] = {0, 0};
+        DevBuf d_buf[2];
         int fill = 0;
         size_t head = 0;                // offset of the first fed byte in d_buf[fill]
         size_t pending = 0;             // fed bytes waiting in d_buf[fill]
@@ -342,12 +212,10 @@ struct bzh_ctx {
             uint32_t lastw = 0;         // the partial word after them (big-endian value)
             std::vector<uint32_t> crcs; // CRCs of the final blocks, in order
         } pass;
-        uint8_t *h_out = nullptr;       // pinned: the partial last word of a pass's output
-        size_t h_out_cap = 0;
+        PinnedBuf h_out;                // pinned: the partial last word of a pass's output
         // A pass leaves its bits on the device (two buffers, alternating): the next pass is started first, then the
         // finished one's words go straight to the caller's buffer while the GPU is already at work again.
-        uint8_t *d_out[2] = {nullptr, nullptr};
-        size_t d_out_cap[2] = {0, 0};
+        DevBuf d_out[2];
         int osel = 0;
     } strm;
     bzh_stats stats{};
@@ -363,6 +231,39 @@ struct bzh_ctx {
     double k_ms[K_COUNT] = {0};        // collected by kstats_collect
     uint64_t k_bytes[K_COUNT] = {0}, k_launch[K_COUNT] = {0};
 };
+
+template <bool PINNED>
+int GrowBuf<PINNED>::reserve(bzh_ctx *ctx, size_t need, const char *what, size_t (*grow)(size_t))
+{
+    if (need <= cap) return BZH_OK;
+    if (p) {
+        if (ctx) HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+        release();
+    }
+    const size_t want = grow ? grow(need) : need;
+    if ((PINNED ? hipHostMalloc((void **)&p, want, flags) : hipMalloc((void **)&p, want)) != hipSuccess) {
+        p = nullptr;
+        bzh_set_error(ctx, "%s(%zu) for %s failed", PINNED ? "hipHostMalloc" : "hipMalloc", want, what);
+        return BZH_E_NOMEM;
+    }
+    cap = want;
+    return BZH_OK;
+}
+
+// A buffer reserved for, and cut into, the arrays `cut` takes from the carver it is given: a measuring pass sizes it, a second one cuts.
+template <typename F>
+static inline int reserve_cut(bzh_ctx *ctx, DevBuf &buf, const char *what, size_t (*grow)(size_t), F cut)
+{
+    Carver measure(nullptr);
+    cut(measure);
+    BZH_TRY(buf.reserve(ctx, measure.bytes(), what, grow));
+    Carver carve(buf.p);
+    cut(carve);
+    return BZH_OK;
+}
+
+// words of a context's pinned readback area: 8 a block and 64 free ones (api.hip), the round summaries and the initial sort's plan record (bwt.hip)
+static inline size_t pinned_words(uint32_t max_batch) { return (size_t)max_batch * 8 + 64 + (size_t)(MAX_ROUNDS + 1) * SUMMARY_WORDS; }
 
 hipEvent_t bzh_event(bzh_ctx *ctx);
 // Brackets the launches issued during its lifetime (one class) with events when profiling is on.
@@ -591,8 +492,8 @@ __device__ __forceinline__ int block_excl_min_rev(int v, int *lds)
 
 // ---- stage entry points (host side, defined in the stage files) ---------------------------------
 int bwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal); // bwt.hip
-int unbwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax);               // bwt.hip: inverse transform, bt.bwt/ptr -> bt.mtfpos
-int unbwt_compare(bzh_ctx *ctx, uint32_t B, uint32_t nmax, unsigned long long *d_acc); // bwt.hip: bt.rle vs bt.mtfpos
+int unbwt_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax);               // bwt.hip: inverse transform, bt.bwt/ptr -> bt.unbwt_out
+int unbwt_compare(bzh_ctx *ctx, uint32_t B, uint32_t nmax, unsigned long long *d_acc); // bwt.hip: bt.rle vs bt.unbwt_out
 int mtf_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal = 0); // mtf.hip (ntotal: statistics only)
 int huff_prepare(bzh_ctx *ctx, uint32_t B, uint32_t mmax);            // huffman.hip: tables, header bits, bit totals
 int huff_pack(bzh_ctx *ctx, uint32_t B, uint32_t mmax, uint8_t *d_out, uint64_t bit_base, bool gated = false); // huffman.hip
@@ -638,7 +539,7 @@ int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_by
 int decode_many_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const size_t *in_offs, const size_t *in_lens, size_t count, uint8_t *d_out,
                     size_t cap, size_t *out_offs, size_t *out_lens, int *status, size_t *consumed, const std::vector<uint64_t> &cands);
 // unbwt_small.hip: the inverse BWT in LDS of the K listed batch slots, blocks of at most bzh_decode_many_small_max() bytes each
-// (bt.bwt / bt.n / bt.ptr -> bt.mtfpos, as unbwt_run); its switch; the first four bytes of many slices in one launch
+// (bt.bwt / bt.n / bt.ptr -> bt.unbwt_out, as unbwt_run); its switch; the first four bytes of many slices in one launch
 int unbwt_small_run(bzh_ctx *ctx, const uint32_t *d_slots, uint32_t K);
 bool unbwt_small_enabled();
 int many_heads_run(bzh_ctx *ctx, const uint8_t *d_in, const uint64_t *d_offs, const uint64_t *d_lens, uint32_t count, uint32_t *d_heads);
@@ -651,5 +552,3 @@ struct EncIndex {
     std::vector<bzh_sync_point> pts;
 };
 int sync_emit_batch(bzh_ctx *ctx, uint32_t B, size_t k0, uint64_t bit_base, EncIndex &ix);
-
-hipEvent_t bzh_event(bzh_ctx *ctx);

@@ -589,86 +589,14 @@ __global__ void __launch_bounds__(64) range_magic_kernel(const uint8_t *in, uint
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-struct DecWs { // carved from ctx->dec_ws (allocated on the first decode: an encode-only user pays nothing)
-    uint64_t *cand;    // [B]
-    BzdResult *res;    // [B]
-    uint32_t *tmap, *tout, *tstate, *toff; // [B][T]
-    uint32_t *endstate, *slots, *crcacc;   // [B]
-    uint64_t *obase;   // [B]
-    BlockDesc *desc;   // [B]
-    uint32_t *scancnt; // [1]
-    // [B] the blocks of a batch that are not expanded whole (back_emit): cut by a range's edge, or not written at all.  wslots /
-    // wbase / wacc / wcrc are twins of slots / obase / crcacc / desc[].crc because a range's batch has whole and cut blocks in flight
-    // together: both walks and both CRC passes are queued before the one wait.
-    uint32_t *wslots, *wlo, *whi, *bsize, *wacc, *wcrc;
-    int64_t *wbase;    // [B]
-    uint32_t *magic;   // [B] range_magic_kernel's verdicts
-    uint32_t *small;   // [B] bzh_decode_many: the batch slots whose blocks the LDS inverse BWT takes
-    uint32_t B, T;
-};
-
 static int dec_ws(bzh_ctx *ctx, DecWs &w)
 {
-    const size_t B = ctx->max_batch, T = ctx->S / UR_TILE;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t need = up(B * 8) + up(B * sizeof(BzdResult)) + 4 * up(B * T * 4) + 11 * up(B * 4) + 2 * up(B * 8) + up(B * sizeof(BlockDesc)) + 256;
-    if (!ctx->dec_ws || ctx->dec_ws_size < need) {
-        if (ctx->dec_ws) hipFree(ctx->dec_ws);
-        ctx->dec_ws = nullptr;
-        ctx->dec_ws_size = 0;
-        if (hipMalloc((void **)&ctx->dec_ws, need) != hipSuccess) {
-            bzh_set_error(ctx, "hipMalloc(%zu) for the decode tables failed", need);
-            return BZH_E_NOMEM;
-        }
-        ctx->dec_ws_size = need;
-    }
-    uint8_t *p = ctx->dec_ws;
-    auto take = [&](auto *&dst, size_t bytes) {
-        dst = reinterpret_cast<std::remove_reference_t<decltype(dst)>>(p);
-        p += up(bytes);
-    };
-    take(w.cand, B * 8);
-    take(w.res, B * sizeof(BzdResult));
-    take(w.tmap, B * T * 4);
-    take(w.tout, B * T * 4);
-    take(w.tstate, B * T * 4);
-    take(w.toff, B * T * 4);
-    take(w.endstate, B * 4);
-    take(w.slots, B * 4);
-    take(w.crcacc, B * 4);
-    take(w.obase, B * 8);
-    take(w.desc, B * sizeof(BlockDesc));
-    take(w.scancnt, 4);
-    take(w.wslots, B * 4);
-    take(w.wlo, B * 4);
-    take(w.whi, B * 4);
-    take(w.bsize, B * 4);
-    take(w.wacc, B * 4);
-    take(w.wcrc, B * 4);
-    take(w.magic, B * 4);
-    take(w.wbase, B * 8);
-    take(w.small, B * 4);
-    w.B = (uint32_t)B;
-    w.T = (uint32_t)T;
+    const uint32_t B = ctx->max_batch, T = ctx->S / UR_TILE;
+    BZH_TRY(ctx->dec_ws.reserve(ctx, dec_layout(w, nullptr, B, T), "the decode tables"));
+    dec_layout(w, ctx->dec_ws, B, T);
     return BZH_OK;
 }
 
-// ctx->sync_ws of at least `need` bytes (allocated on first use, grown when a call needs more; the stream is idle then)
-static int sync_ws_reserve(bzh_ctx *ctx, size_t need)
-{
-    if (ctx->sync_ws && ctx->sync_ws_size >= need) return BZH_OK;
-    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
-    if (ctx->sync_ws) hipFree(ctx->sync_ws);
-    ctx->sync_ws = nullptr;
-    ctx->sync_ws_size = 0;
-    need = (need + 0xFFFFF) & ~(size_t)0xFFFFF;
-    if (hipMalloc((void **)&ctx->sync_ws, need) != hipSuccess) {
-        bzh_set_error(ctx, "hipMalloc(%zu) for the sync points failed", need);
-        return BZH_E_NOMEM;
-    }
-    ctx->sync_ws_size = need;
-    return BZH_OK;
-}
 // The recorder's workspace is bounded by shrinking the batch, whatever the interval: a slot holds every point a block can have,
 // (BZD_MAX_SEL - 1) / interval of 288 bytes -- 9.4 MB at interval 1 -- and a batch has as many slots as fit in this many bytes.
 constexpr size_t SYNC_REC_BYTES = 64u << 20;
@@ -686,30 +614,22 @@ int decode_scan_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, std::vector<uin
         bzh_set_error(ctx, "decode: an input of %zu bytes is beyond one scan launch", n);
         return BZH_E_ARG;
     }
+    size_t list_cap = std::max<size_t>(65536, ctx->dec_list.cap / 8); // hits the list holds
     for (int attempt = 0; attempt < 2; attempt++) {
-        if (!ctx->dec_list || ctx->dec_list_cap == 0) {
-            const size_t cap = 65536;
-            if (hipMalloc((void **)&ctx->dec_list, cap * 8) != hipSuccess) return BZH_E_NOMEM;
-            ctx->dec_list_cap = cap;
-        }
+        BZH_TRY(ctx->dec_list.reserve(ctx, list_cap * 8, "the scan's hit list"));
         HIP_TRY(ctx, hipMemsetAsync(w.scancnt, 0, 4, st));
-        decode_scan_kernel<<<dim3((uint32_t)wgs), SCAN_THREADS, 0, st>>>(d_in, n, ctx->dec_list, (uint32_t)ctx->dec_list_cap, w.scancnt);
+        decode_scan_kernel<<<dim3((uint32_t)wgs), SCAN_THREADS, 0, st>>>(d_in, n, ctx->dec_list.as<uint64_t>(), (uint32_t)list_cap, w.scancnt);
         HIP_TRY(ctx, hipGetLastError());
         uint32_t cnt = 0;
         HIP_TRY(ctx, hipMemcpyAsync(&cnt, w.scancnt, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, bzh_stream_wait(st));
-        if (cnt <= ctx->dec_list_cap) {
+        if (cnt <= list_cap) {
             cands.resize(cnt);
             if (cnt) HIP_TRY(ctx, hipMemcpy(cands.data(), ctx->dec_list, (size_t)cnt * 8, hipMemcpyDeviceToHost));
             std::sort(cands.begin(), cands.end());
             return BZH_OK;
         }
-        hipFree(ctx->dec_list); // more hits than the list holds: once more with one that does
-        ctx->dec_list = nullptr;
-        ctx->dec_list_cap = 0;
-        const size_t cap = (size_t)cnt + 1024;
-        if (hipMalloc((void **)&ctx->dec_list, cap * 8) != hipSuccess) return BZH_E_NOMEM;
-        ctx->dec_list_cap = cap;
+        list_cap = (size_t)cnt + 1024; // more hits than the list holds: once more with one that does
     }
     bzh_set_error(ctx, "decode: the scan's hit list overflowed twice (internal error)");
     return BZH_E_STATE;
@@ -831,7 +751,7 @@ static int back_sizes(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk,
     }
     clock.span(2, t2);
     bk.t_unrle = clock.mark();
-    bk.a = UrArgs{bt.mtfpos, bt.n, w.slots, bt.S, w.T, w.tmap, w.tout, w.tstate, w.endstate, w.toff, w.obase, nullptr};
+    bk.a = UrArgs{bt.unbwt_out, bt.n, w.slots, bt.S, w.T, w.tmap, w.tout, w.tstate, w.endstate, w.toff, w.obase, nullptr};
     bk.Tn = (nmax + UR_TILE - 1) / UR_TILE;
     HIP_TRY(ctx, hipMemcpyAsync(w.slots, bk.hslots.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
     unrle_maps<<<dim3(bk.Tn, K), UR_THREADS, 0, st>>>(bk.a);
@@ -965,10 +885,7 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
         sync_cap = std::max<uint32_t>(1u, (BZD_MAX_SEL - 1) / sync->interval);
         const size_t slot_bytes = (size_t)sync_cap * sizeof(bzh_sync_point);
         sync_slots = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(ctx->max_batch, ctx->arena_blocks), SYNC_REC_BYTES / slot_bytes));
-        const size_t cnt_bytes = ((size_t)sync_slots * 4 + 255) / 256 * 256;
-        BZH_TRY(sync_ws_reserve(ctx, cnt_bytes + sync_slots * slot_bytes));
-        d_ptcnt = reinterpret_cast<uint32_t *>(ctx->sync_ws);
-        d_pts = reinterpret_cast<bzh_sync_point *>(ctx->sync_ws + cnt_bytes);
+        BZH_TRY(reserve_cut(ctx, ctx->sync_ws, "the sync points", grow_mib, [&](Carver &c) { c.put(d_ptcnt, sync_slots); c.put(d_pts, (size_t)sync_slots * sync_cap); }));
     }
     const size_t nc = cands.size();
     const uint64_t nbits = (uint64_t)n * 8;
@@ -1130,13 +1047,12 @@ int decode_many_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const size_t *i
         return BZH_E_STATE;
     }
     StageClock clock{ctx, {}};
-    // the stream headers of all inputs: one launch, one copy back
+    // the stream headers of all inputs: one launch, one copy back (no sync points in this call: their workspace is free)
     std::vector<BzmInput> ins(count);
     {
-        auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-        BZH_TRY(sync_ws_reserve(ctx, 2 * up(count * 8) + up(count * 4))); // (no sync points in this call: the workspace is free)
-        uint64_t *d_offs = reinterpret_cast<uint64_t *>(ctx->sync_ws), *d_lens = reinterpret_cast<uint64_t *>(ctx->sync_ws + up(count * 8));
-        uint32_t *d_heads = reinterpret_cast<uint32_t *>(ctx->sync_ws + 2 * up(count * 8));
+        uint64_t *d_offs, *d_lens;
+        uint32_t *d_heads;
+        BZH_TRY(reserve_cut(ctx, ctx->sync_ws, "the sync points", grow_mib, [&](Carver &c) { c.put(d_offs, count); c.put(d_lens, count); c.put(d_heads, count); }));
         std::vector<uint32_t> heads(count);
         HIP_TRY(ctx, hipMemcpyAsync(d_offs, in_offs, count * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemcpyAsync(d_lens, in_lens, count * 8, hipMemcpyHostToDevice, st));
@@ -1414,14 +1330,10 @@ int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_by
             p0 = (size_t)(std::lower_bound(pts, pts + npts, e0, by_entry) - pts);
             p1 = (size_t)(std::lower_bound(pts + p0, pts + npts, e0 + B, by_entry) - pts);
             bzp_segments(idx, e0, B, pts, p0, p1, hseg, seg0);
-            auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-            const size_t b_heads = up((size_t)B * sizeof(BzdHead)), b_pts = up((p1 - p0) * sizeof(bzh_sync_point)),
-                         b_segs = up(hseg.size() * sizeof(SegDesc)), b_sres = up(hseg.size() * sizeof(BzdSegResult));
-            BZH_TRY(sync_ws_reserve(ctx, b_heads + b_pts + b_segs + b_sres)); // (the stream is idle between batches)
-            d_heads = reinterpret_cast<BzdHead *>(ctx->sync_ws);
-            d_pts = reinterpret_cast<bzh_sync_point *>(ctx->sync_ws + b_heads);
-            d_segs = reinterpret_cast<SegDesc *>(ctx->sync_ws + b_heads + b_pts);
-            d_sres = reinterpret_cast<BzdSegResult *>(ctx->sync_ws + b_heads + b_pts + b_segs);
+            BZH_TRY(reserve_cut(ctx, ctx->sync_ws, "the sync points", grow_mib, [&](Carver &c) { // (the stream is idle between batches)
+                c.put(d_heads, B), c.put(d_pts, p1 - p0);               // the batch's headers and its sync points,
+                c.put(d_segs, hseg.size()), c.put(d_sres, hseg.size()); // the segments they cut its blocks into and their results
+            }));
         }
         hipEvent_t t1 = clock.mark();
         HIP_TRY(ctx, hipMemcpyAsync(w.cand, hcand.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));

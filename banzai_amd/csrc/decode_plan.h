@@ -7,6 +7,9 @@
 #include <stdint.h>
 #include <vector>
 
+#include "batch.h"       // BlockDesc, the carver
+#include "decode_core.h" // BzdResult
+
 struct SegDesc {
     uint32_t slot;      // of its block in the batch
     int32_t from, to;   // points of the batch it runs between; -1: the header's state / the end of the block
@@ -58,4 +61,55 @@ static inline void bzp_segments(const E *idx, size_t e0, uint32_t B, const P *pt
         segs.push_back({k, prev, -1, bmax});
     }
     seg0[B] = (uint32_t)segs.size();
+}
+
+// ---- the decoder's per-batch tables (decode.hip) ---------------------------------------------------------------------------
+struct DecWs { // carved from ctx->dec_ws by dec_layout (allocated on the first decode: an encode-only user pays nothing)
+    uint64_t *cand;    // [B]
+    BzdResult *res;    // [B]
+    uint32_t *tmap, *tout, *tstate, *toff; // [B][T]
+    uint32_t *endstate, *slots, *crcacc;   // [B]
+    uint64_t *obase;   // [B]
+    BlockDesc *desc;   // [B]
+    uint32_t *scancnt; // [1]
+    // [B] the blocks of a batch that are not expanded whole (back_emit): cut by a range's edge, or not written at all.  wslots /
+    // wbase / wacc / wcrc are twins of slots / obase / crcacc / desc[].crc because a range's batch has whole and cut blocks in flight
+    // together: both walks and both CRC passes are queued before the one wait.
+    uint32_t *wslots, *wlo, *whi, *bsize, *wacc, *wcrc;
+    int64_t *wbase;    // [B]
+    uint32_t *magic;   // [B] range_magic_kernel's verdicts
+    uint32_t *small;   // [B] bzh_decode_many: the batch slots whose blocks the LDS inverse BWT takes
+    uint32_t B, T;
+};
+
+// Lays the tables of batches of B blocks of T inverse-RLE1 tiles out at `base` (nullptr: only measures); the bytes they take.
+static inline size_t dec_layout(DecWs &w, void *base, uint32_t B, uint32_t T, std::vector<CarveSpan> *log = nullptr)
+{
+    Carver c(base);
+    c.log = log;
+    const size_t BT = (size_t)B * T;
+    c.put(w.cand, B);
+    c.put(w.res, B);
+    c.put(w.tmap, BT);
+    c.put(w.tout, BT);
+    c.put(w.tstate, BT);
+    c.put(w.toff, BT);
+    c.put(w.endstate, B);
+    c.put(w.slots, B);
+    c.put(w.crcacc, B);
+    c.put(w.obase, B);
+    c.put(w.desc, B);
+    c.put(w.scancnt, 1);
+    c.put(w.wslots, B);
+    c.put(w.wlo, B);
+    c.put(w.whi, B);
+    c.put(w.bsize, B);
+    c.put(w.wacc, B);
+    c.put(w.wcrc, B);
+    c.put(w.magic, B);
+    c.put(w.wbase, B);
+    c.put(w.small, B);
+    w.B = B;
+    w.T = T;
+    return c.bytes();
 }

@@ -1,12 +1,14 @@
 // encode_plan.h -- the host arithmetic between the encoder's kernels: how a range of plan blocks is cut into jobs, what a job's
-// blocks add up to, which output words are zeroed before which pack ORs its bits into them, and which inputs a batch of a
-// many-streams call opens and closes.  No HIP types: api.hip's encode drivers call these, and tests/encode_host/plan_host.cpp
+// blocks add up to, which output words are zeroed before which pack ORs its bits into them, which inputs a batch of a
+// many-streams call opens and closes, and how the plan's two workspaces are laid out (rle1.hip).  No HIP types: api.hip's encode drivers call these, and tests/encode_host/plan_host.cpp
 // compiles the same text with g++ -fsanitize=address,undefined and holds each against brute force.  An off-by-one here is a bit
 // ORed into a word that was never zeroed, or that was zeroed after it was written.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 #include <vector>
+
+#include "batch.h" // BlockDesc, the carver
 
 struct BzeSpan { // a job
     size_t k0;  // its first plan block
@@ -86,4 +88,112 @@ static inline BzeMany bze_many_batch(const uint32_t *plan_input, size_t k0, uint
     const bool last = kl + 1 == nb, closes = last || plan_input[kl + 1] != il;
     const uint32_t close_hi = last ? (uint32_t)count : (closes ? il + 1 : il);
     return {cur, (k0 > 0 && plan_input[k0 - 1] == cur) ? 1u : 0u, close_hi, closes ? close_hi : il + 1};
+}
+
+// ---- the plan's workspaces (rle1.hip) -------------------------------------------------------------------------------------
+constexpr int RL_THREADS = 256;
+constexpr int RL_ITEMS = 16;
+constexpr uint32_t RL_TILE = RL_THREADS * RL_ITEMS; // 4096 input bytes per workgroup
+constexpr uint32_t GRAN = 64;                       // bytes per granule = one wavefront of the splitter
+constexpr uint32_t GRAN_PER_TILE = RL_TILE / GRAN;  // 64
+constexpr uint32_t NONE32 = 0xFFFFFFFFu;
+
+struct BlockAux { // per planned block: what the emit kernel needs about the run the block starts in
+    uint64_t Ce;      // canonical offset at the end of that run
+    uint32_t A;       // RLE1 bytes of that run's remainder (chunking restarted at in_off)
+    uint32_t e_first; // end of that run
+    uint32_t open;    // 1 = the cut could move if more input followed (streaming: not final yet)
+    uint32_t pad;
+};
+
+struct PlanArrays {
+    const uint8_t *in;
+    uint64_t n;
+    uint32_t ntiles;
+    uint32_t ngran;
+    uint32_t M;
+    uint32_t maxblocks;
+    uint32_t start;    // input offset the split begins at (a block start; 0 unless a sharded rank continues a chain)
+    uint32_t stop;     // the split ends with the first block that starts at or after this offset (a sharded rank's range end)
+    uint32_t *lrs;     // [ntiles]   last run start inside the tile (NONE32 if none); then exclusive prefix max
+    uint32_t *frs;     // [ntiles+1] first run start inside the tile; then suffix min (frs[ntiles] = n)
+    uint32_t *csum;    // [ntiles]   canonical bytes emitted by the tile
+    uint64_t *tc;      // [ntiles+1] exclusive scan of csum
+    uint32_t *cg;      // [ngran]
+    uint32_t *rsg;     // [ngran]
+    uint32_t *nrsg;    // [ngran+1]  nrsg[ngran] = n
+    BlockDesc *blocks; // [maxblocks]
+    BlockAux *aux;     // [maxblocks]
+    uint32_t *nblocks; // [1]
+};
+
+struct PlanWs { // layout of ctx->plan_ws
+    PlanArrays pa;
+    uint32_t *crcacc;
+    size_t bytes;
+};
+
+// (`extra`: block records beyond the bound of one stream -- a plan over many inputs may cut one more block per input)
+static inline PlanWs plan_layout(void *base, uint64_t n, uint32_t M, uint32_t extra, std::vector<CarveSpan> *log = nullptr)
+{
+    PlanWs w{};
+    const uint64_t ntiles = (n + RL_TILE - 1) / RL_TILE;
+    const uint64_t ngran = ntiles * GRAN_PER_TILE;
+    const uint64_t maxblocks = n / ((uint64_t)(M - 1) * 4 / 5) + 4 + extra;
+    Carver c(base);
+    c.log = log;
+    w.pa.n = n;
+    w.pa.M = M;
+    w.pa.ntiles = (uint32_t)ntiles;
+    w.pa.ngran = (uint32_t)ngran;
+    w.pa.maxblocks = (uint32_t)maxblocks;
+    c.put(w.pa.lrs, ntiles + 2);
+    c.put(w.pa.frs, ntiles + 2);
+    c.put(w.pa.csum, ntiles + 2);
+    c.put(w.pa.tc, ntiles + 2);
+    c.put(w.pa.cg, ngran + 2);
+    c.put(w.pa.rsg, ngran + 2);
+    c.put(w.pa.nrsg, ngran + 2);
+    c.put(w.pa.blocks, maxblocks); // blocks | aux | nblocks stay consecutive: one copy brings them back (rle1_plan_split)
+    c.put(w.pa.aux, maxblocks);
+    c.put(w.pa.nblocks, 64);
+    c.put(w.crcacc, maxblocks);
+    w.bytes = c.bytes();
+    return w;
+}
+
+struct ManyInput {
+    uint32_t gs;   // first byte in the guarded buffer (its guard is at gs + len)
+    uint32_t len;  // bytes of the input
+    uint32_t slot; // first record slot of the input in the split's record area (room for len / ((M-1) 4/5) + 1 blocks)
+    uint32_t cnt;  // blocks cut (plan_many_split); 0xFFFFFFFF: more than that room
+};
+struct ManyWs { // layout of ctx->many_ws: guarded buffer | inputs | split records | block -> input
+    uint8_t *gbuf;  // [ng + 32] the inputs, one guard byte behind each
+    ManyInput *tab; // [count]
+    BlockDesc *sb;  // [slots] what every input's split cuts, at the input's first slot
+    BlockAux *sa;   // [slots]
+    uint32_t *binp; // [maxblocks] input of every block of the plan
+    uint64_t ng, slots, maxblocks; // (the plan's bound: plan_layout with one extra block an input)
+    size_t bytes;
+};
+static inline uint64_t many_slots(uint64_t len, uint32_t M) { return len ? len / ((M - 1u) * 4u / 5u) + 1 : 0; } // record slots of one input
+static inline ManyWs many_layout(void *base, const size_t *lens, size_t count, uint32_t M, std::vector<CarveSpan> *log = nullptr)
+{
+    ManyWs w{};
+    for (size_t k = 0; k < count; k++) {
+        w.ng += lens[k];
+        w.slots += many_slots(lens[k], M);
+    }
+    w.ng += count;
+    w.maxblocks = w.ng / ((M - 1u) * 4u / 5u) + 4 + count;
+    Carver c(base);
+    c.log = log;
+    c.put(w.gbuf, w.ng + 32);
+    c.put(w.tab, count);
+    c.put(w.sb, w.slots);
+    c.put(w.sa, w.slots);
+    c.put(w.binp, w.maxblocks);
+    w.bytes = c.bytes();
+    return w;
 }

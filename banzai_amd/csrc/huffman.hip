@@ -900,12 +900,12 @@ int huff_prepare(bzh_ctx *ctx, uint32_t B, uint32_t mmax)
     Batch &bt = ctx->bt;
     if (B == 0) return BZH_OK;
     hipStream_t st = ctx->stream;
-    uint32_t *ranges = reinterpret_cast<uint32_t *>(bt.tagg); // B*8 words <= B*TPB*2
+    uint32_t *ranges = huff_ranges(bt);
     const uint32_t nsegmax = (mmax + SEG - 1) / SEG;
     const uint32_t PT = (bt.S + 64 + PACK_TILE - 1) / PACK_TILE;
     const uint32_t ptiles = (mmax + PACK_TILE - 1) / PACK_TILE;
     const uint32_t selmax = (bt.S + 64 + 49) / 50 + 2;
-    const uint32_t selbytes = (uint32_t)((((size_t)selmax * 6 + 7) / 8 + 8 + 63) / 64 * 64); // as laid out in api.hip
+    const uint32_t selbytes = (uint32_t)((((size_t)selmax * 6 + 7) / 8 + 8 + 63) / 64 * 64); // as laid out in batch.h
     if (ctx->mode == BZH_MODE_FIXED) {
         fx_init<<<dim3(B), 64, 0, st>>>(bt);
         for (int it = 0; it < 4; it++) {

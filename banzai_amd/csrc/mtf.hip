@@ -501,8 +501,8 @@ int mtf_run(bzh_ctx *ctx, uint32_t B, uint32_t nmax, uint64_t ntotal)
     // the extra wavefronts return.)
     const uint32_t TL = mtf_tile_bytes(B);
     const uint32_t MT = (bt.S + TL - 1) / TL;
-    int32_t *tlast = reinterpret_cast<int32_t *>(bt.listA);  // B*MT*256*4 <= B*S*8
-    MtfTile *rt = reinterpret_cast<MtfTile *>(bt.listB);     // B*MT*16 bytes
+    int32_t *tlast = mtf_tlast(bt);
+    MtfTile *rt = mtf_tiles(bt);
     const uint32_t mt = (nmax + TL - 1) / TL;
     {
         KSpan ks(ctx, K_MTF_LAST, ntotal, 2);

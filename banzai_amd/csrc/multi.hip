@@ -31,11 +31,11 @@ constexpr double ROOT_DISCOUNT = 0.96;         // worker 0 also receives the str
 struct Worker {
     int device = 0;
     bzh_ctx *ctx = nullptr;
-    uint8_t *d_in = nullptr;   // input[lo, lo + resident)
-    size_t in_cap = 0;
-    uint8_t *d_part = nullptr; // the worker's bit string (its slab)
-    size_t part_cap = 0;
-    uint8_t *d_seg = nullptr;  // where the string lands on device 0 (worker 0: its slab itself)
+    DevBuf d_in;               // input[lo, lo + resident)
+    DevBuf d_part;             // the worker's bit string (its slab)
+    size_t part_cap = 0;       // what of it the worker offers the encoder (all of it, or the test hook's size)
+    DevBuf seg;                // workers behind the first: where the string lands on device 0
+    uint8_t *d_seg = nullptr;  // (worker 0: its slab itself)
     size_t seg_cap = 0;
     // the call in flight
     size_t lo = 0, own_hi = 0, resident = 0;
@@ -51,8 +51,8 @@ struct Worker {
 struct bzh_multi {
     int level = 9;
     std::vector<Worker> w;
-    uint8_t *d_out = nullptr; // the assembled stream, on device 0
-    size_t out_cap = 0, out_len = 0;
+    DevBuf d_out;             // the assembled stream, on device 0
+    size_t out_len = 0;
     size_t n = 0;             // bytes of the loaded input
     bool loaded = false;
     std::vector<size_t> bounds;
@@ -108,17 +108,8 @@ size_t worst_case_slab(const std::vector<size_t> &b, int level)
     return ((rle + M) * 22 / 10 + blocks * 4400 + 65536 + 3) & ~(size_t)3;
 }
 
-int ensure_dev(uint8_t *&p, size_t &cap, size_t need)
-{
-    if (need <= cap) return BZH_OK;
-    if (p) hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = (need + need / 8 + 4096 + 255) & ~(size_t)255;
-    if (hipMalloc((void **)&p, want) != hipSuccess) return BZH_E_NOMEM;
-    cap = want;
-    return BZH_OK;
-}
+size_t grow_eighth_256(size_t need) { return (need + need / 8 + 4096 + 255) & ~(size_t)255; }
+int ensure_dev(DevBuf &b, size_t need) { return b.reserve(nullptr, need, "", grow_eighth_256); } // (no context: the workers' calls have returned, the caller words the failure)
 
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -139,7 +130,7 @@ void load_one(bzh_multi *m, int r, const uint8_t *in)
     k.lo = m->bounds[r];
     k.own_hi = m->bounds[r + 1];
     k.resident = std::min(m->n, k.own_hi + LOOKAHEAD) - k.lo;
-    if (ensure_dev(k.d_in, k.in_cap, k.resident + 16) != BZH_OK) return fail(k, BZH_E_NOMEM, "hipMalloc for the input range failed");
+    if (ensure_dev(k.d_in, k.resident + 16) != BZH_OK) return fail(k, BZH_E_NOMEM, "hipMalloc for the input range failed");
     if (k.resident && hipMemcpy(k.d_in, in + k.lo, k.resident, hipMemcpyHostToDevice) != hipSuccess)
         return fail(k, BZH_E_HIP, "H2D copy of the input range failed");
     k.ms_load = now_ms() - t0;
@@ -232,10 +223,12 @@ void run_one(bzh_multi *m, int r)
             if (st != BZH_E_CAP || attempt) break;
             // a slab that turned out too small (the slab size is a heuristic): once more with twice the room
             const size_t want = k.part_cap * 2;
-            if (ensure_dev(k.d_part, k.part_cap, want) != BZH_OK) {
+            k.d_part.release(); // (twice what was offered, which under the test hook may be less than what is there)
+            if (ensure_dev(k.d_part, want) != BZH_OK) {
                 st = BZH_E_NOMEM;
                 break;
             }
+            k.part_cap = k.d_part.cap;
             if (r == 0) {
                 k.d_seg = k.d_part;
                 k.seg_cap = k.part_cap;
@@ -344,15 +337,14 @@ extern "C" void bzh_destroy_multi(bzh_multi *m)
     for (Worker &k : m->w) {
         if (!k.ctx) continue; // (a handle whose creation failed half way: nothing was ever done on that device)
         bzh_destroy(k.ctx);   // (waits for the context's own streams)
-        if ((k.d_in || k.d_part) && hipSetDevice(k.device) == hipSuccess) {
-            if (k.d_in) hipFree(k.d_in);
-            if (k.d_part) hipFree(k.d_part);
+        if ((k.d_in || k.d_part) && hipSetDevice(k.device) == hipSuccess) { // (freed with their own device current)
+            k.d_in.release();
+            k.d_part.release();
         }
     }
     if (!m->w.empty() && m->w[0].ctx && hipSetDevice(m->w[0].device) == hipSuccess) {
-        for (size_t r = 1; r < m->w.size(); r++)
-            if (m->w[r].d_seg) hipFree(m->w[r].d_seg);
-        if (m->d_out) hipFree(m->d_out);
+        for (size_t r = 1; r < m->w.size(); r++) m->w[r].seg.release();
+        m->d_out.release();
     }
     (void)hipGetLastError(); // (no sticky status of this teardown is left for the thread's next HIP call to trip over)
     delete m;
@@ -402,24 +394,25 @@ extern "C" int bzh_multi_run(bzh_multi *m, size_t *out_len)
         for (int r = 0; r < W; r++) {
             Worker &k = m->w[r];
             if (m->slab_override && k.d_part) { // (the hook wants exactly this size: a buffer that only grows would hide it)
-                if (hipSetDevice(k.device) == hipSuccess) hipFree(k.d_part);
-                k.d_part = nullptr;
-                k.part_cap = 0;
+                if (hipSetDevice(k.device) == hipSuccess) k.d_part.release();
             }
-            if (hipSetDevice(k.device) != hipSuccess || ensure_dev(k.d_part, k.part_cap, slab) != BZH_OK) {
+            if (hipSetDevice(k.device) != hipSuccess || ensure_dev(k.d_part, slab) != BZH_OK) {
                 set_err(m, "hipMalloc for a worker's slab failed");
                 return BZH_E_NOMEM;
             }
-            if (m->slab_override) k.part_cap = slab; // (what the worker offers the encoder)
+            k.part_cap = m->slab_override ? slab : k.d_part.cap;
         }
         if (hipSetDevice(m->w[0].device) != hipSuccess) return BZH_E_HIP;
         m->w[0].d_seg = m->w[0].d_part;
         m->w[0].seg_cap = m->w[0].part_cap;
-        for (int r = 1; r < W; r++)
-            if (ensure_dev(m->w[r].d_seg, m->w[r].seg_cap, m->slab_override ? 2 * slab : slab) != BZH_OK) { // (the test hook's slab may be doubled)
+        for (int r = 1; r < W; r++) {
+            if (ensure_dev(m->w[r].seg, m->slab_override ? 2 * slab : slab) != BZH_OK) { // (the test hook's slab may be doubled)
                 set_err(m, "hipMalloc for a landing buffer on device 0 failed");
                 return BZH_E_NOMEM;
             }
+            m->w[r].d_seg = m->w[r].seg;
+            m->w[r].seg_cap = m->w[r].seg.cap;
+        }
         m->start.assign(W, 0);
         m->ready.assign(W, 0);
         m->ready[0] = 1;
@@ -458,12 +451,12 @@ extern "C" int bzh_multi_run(bzh_multi *m, size_t *out_len)
         }
         if (hipSetDevice(m->w[0].device) != hipSuccess) return BZH_E_HIP;
         const size_t need = (size_t)((32 + body + 80 + 31) / 32 + 2) * 4;
-        if (ensure_dev(m->d_out, m->out_cap, need) != BZH_OK) {
+        if (ensure_dev(m->d_out, need) != BZH_OK) {
             set_err(m, "hipMalloc for the stream failed");
             return BZH_E_NOMEM;
         }
         size_t len = 0;
-        st = bzh_assemble_device(m->w[0].ctx, segs.data(), bits.data(), segs.size(), crcs.data(), crcs.size(), m->d_out, m->out_cap & ~(size_t)3, &len);
+        st = bzh_assemble_device(m->w[0].ctx, segs.data(), bits.data(), segs.size(), crcs.data(), crcs.size(), m->d_out, m->d_out.cap & ~(size_t)3, &len);
         if (st != BZH_OK) {
             snprintf(m->err, sizeof m->err, "assembly: %s: %s", bzh_strerror(st), bzh_last_error(m->w[0].ctx));
             return st;
@@ -488,7 +481,7 @@ extern "C" int bzh_multi_fetch(bzh_multi *m, uint8_t *out, size_t cap)
     });
 }
 
-extern "C" const void *bzh_multi_output_device(const bzh_multi *m) { return m ? m->d_out : nullptr; }
+extern "C" const void *bzh_multi_output_device(const bzh_multi *m) { return m ? m->d_out.p : nullptr; }
 
 // Test hook: the slab a worker encodes into is `bytes` instead of the heuristic's size (0: the heuristic again) -- a slab that is
 // too small makes the worker's encode return BZH_E_CAP, which it answers ONCE with a slab of twice the size.

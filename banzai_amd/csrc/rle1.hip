@@ -24,42 +24,7 @@
 // Emit (per batch): one thread per 16 input bytes, offsets by in-tile scans, output staged in LDS.
 #include "common.h"
 #include "crc_gf.h"
-
-constexpr int RL_THREADS = 256;
-constexpr int RL_ITEMS = 16;
-constexpr uint32_t RL_TILE = RL_THREADS * RL_ITEMS; // 4096 input bytes per workgroup
-constexpr uint32_t GRAN = 64;                       // bytes per granule = one wavefront of the splitter
-constexpr uint32_t GRAN_PER_TILE = RL_TILE / GRAN;  // 64
-constexpr uint32_t NONE32 = 0xFFFFFFFFu;
-
-struct BlockAux { // per planned block: what the emit kernel needs about the run the block starts in
-    uint64_t Ce;      // canonical offset at the end of that run
-    uint32_t A;       // RLE1 bytes of that run's remainder (chunking restarted at in_off)
-    uint32_t e_first; // end of that run
-    uint32_t open;    // 1 = the cut could move if more input followed (streaming: not final yet)
-    uint32_t pad;
-};
-
-struct PlanArrays {
-    const uint8_t *in;
-    uint64_t n;
-    uint32_t ntiles;
-    uint32_t ngran;
-    uint32_t M;
-    uint32_t maxblocks;
-    uint32_t start;    // input offset the split begins at (a block start; 0 unless a sharded rank continues a chain)
-    uint32_t stop;     // the split ends with the first block that starts at or after this offset (a sharded rank's range end)
-    uint32_t *lrs;     // [ntiles]   last run start inside the tile (NONE32 if none); then exclusive prefix max
-    uint32_t *frs;     // [ntiles+1] first run start inside the tile; then suffix min (frs[ntiles] = n)
-    uint32_t *csum;    // [ntiles]   canonical bytes emitted by the tile
-    uint64_t *tc;      // [ntiles+1] exclusive scan of csum
-    uint32_t *cg;      // [ngran]
-    uint32_t *rsg;     // [ngran]
-    uint32_t *nrsg;    // [ngran+1]  nrsg[ngran] = n
-    BlockDesc *blocks; // [maxblocks]
-    BlockAux *aux;     // [maxblocks]
-    uint32_t *nblocks; // [1]
-};
+#include "encode_plan.h"
 
 __device__ __forceinline__ uint32_t canon_len(uint32_t L) // RLE1 bytes of a run of L equal bytes
 {
@@ -903,10 +868,10 @@ int crc_tables(bzh_ctx *ctx, const CrcTables **out)
 {
     if (!ctx->d_crctab) {
         const CrcTables ct = make_crc_tables();
-        if (hipMalloc(&ctx->d_crctab, sizeof ct) != hipSuccess) return BZH_E_NOMEM;
+        BZH_TRY(ctx->d_crctab.reserve(ctx, sizeof ct, "the CRC tables"));
         HIP_TRY(ctx, hipMemcpy(ctx->d_crctab, &ct, sizeof ct, hipMemcpyHostToDevice));
     }
-    *out = (const CrcTables *)ctx->d_crctab;
+    *out = ctx->d_crctab.as<const CrcTables>();
     return BZH_OK;
 }
 
@@ -1073,47 +1038,6 @@ __global__ void __launch_bounds__(RL_THREADS) rle1_emit_kernel(EmitArgs ea, Batc
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-struct PlanWs { // layout of ctx->plan_ws
-    PlanArrays pa;
-    uint32_t *crcacc;
-    size_t bytes;
-};
-
-static size_t a256(size_t v) { return (v + 255) / 256 * 256; }
-
-// (`extra`: block records beyond the bound of one stream -- a plan over many inputs may cut one more block per input)
-static PlanWs plan_layout(uint8_t *base, uint64_t n, uint32_t M, uint32_t extra)
-{
-    PlanWs w{};
-    const uint64_t ntiles = (n + RL_TILE - 1) / RL_TILE;
-    const uint64_t ngran = ntiles * GRAN_PER_TILE;
-    const uint64_t maxblocks = n / ((uint64_t)(M - 1) * 4 / 5) + 4 + extra;
-    uint8_t *p = base;
-    auto take = [&](size_t bytes) {
-        uint8_t *r = p;
-        p += a256(bytes);
-        return r;
-    };
-    w.pa.n = n;
-    w.pa.M = M;
-    w.pa.ntiles = (uint32_t)ntiles;
-    w.pa.ngran = (uint32_t)ngran;
-    w.pa.maxblocks = (uint32_t)maxblocks;
-    w.pa.lrs = (uint32_t *)take((ntiles + 2) * 4);
-    w.pa.frs = (uint32_t *)take((ntiles + 2) * 4);
-    w.pa.csum = (uint32_t *)take((ntiles + 2) * 4);
-    w.pa.tc = (uint64_t *)take((ntiles + 2) * 8);
-    w.pa.cg = (uint32_t *)take((ngran + 2) * 4);
-    w.pa.rsg = (uint32_t *)take((ngran + 2) * 4);
-    w.pa.nrsg = (uint32_t *)take((ngran + 2) * 4);
-    w.pa.blocks = (BlockDesc *)take(maxblocks * sizeof(BlockDesc));
-    w.pa.aux = (BlockAux *)take(maxblocks * sizeof(BlockAux));
-    w.pa.nblocks = (uint32_t *)take(256);
-    w.crcacc = (uint32_t *)take(maxblocks * 4);
-    w.bytes = (size_t)(p - base);
-    return w;
-}
-
 // The split's tables (run starts and canonical RLE1 offsets per tile and per granule) over d_in[0..n): d_in must be
 // 16-byte aligned.  They describe the runs of the input, not the blocks, so they hold for a split that begins at
 // any block start inside the buffer (rle1_plan_split) -- a sharded rank builds them while its first block's start
@@ -1142,18 +1066,8 @@ int rle1_plan_tables(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t extra
         bzh_set_error(ctx, "input of %zu bytes exceeds the 32-bit position range of one plan", n);
         return BZH_E_ARG;
     }
-    PlanWs probe = plan_layout(nullptr, n, ctx->M, ctx->plan_extra);
-    if (probe.bytes > ctx->plan_ws_size) {
-        if (ctx->plan_ws) hipFree(ctx->plan_ws);
-        ctx->plan_ws = nullptr;
-        ctx->plan_ws_size = 0;
-        if (hipMalloc(&ctx->plan_ws, probe.bytes) != hipSuccess) {
-            bzh_set_error(ctx, "hipMalloc(%zu) for the plan failed", probe.bytes);
-            return BZH_E_NOMEM;
-        }
-        ctx->plan_ws_size = probe.bytes;
-    }
-    PlanWs w = plan_layout((uint8_t *)ctx->plan_ws, n, ctx->M, ctx->plan_extra);
+    BZH_TRY(ctx->plan_ws.reserve(ctx, plan_layout(nullptr, n, ctx->M, ctx->plan_extra).bytes, "the plan"));
+    PlanWs w = plan_layout(ctx->plan_ws, n, ctx->M, ctx->plan_extra);
     PlanArrays &pa = w.pa;
     pa.in = d_in;
     KSpan ks(ctx, K_PLAN, 2 * n, 4); // two sweeps of the input
@@ -1187,7 +1101,7 @@ int rle1_plan_split(bzh_ctx *ctx, size_t start, bool with_crc, size_t stop, bool
     ctx->plan_input.clear();
     if (start > n) return BZH_E_ARG;
     if (n == 0 || start == n) return BZH_OK;
-    PlanWs w = plan_layout((uint8_t *)ctx->plan_ws, n, ctx->M, ctx->plan_extra);
+    PlanWs w = plan_layout(ctx->plan_ws, n, ctx->M, ctx->plan_extra);
     PlanArrays &pa = w.pa;
     pa.in = d_in;
     pa.start = (uint32_t)start;
@@ -1234,16 +1148,7 @@ int rle1_plan_split(bzh_ctx *ctx, size_t start, bool with_crc, size_t stop, bool
         crc_finish<<<dim3(pa.maxblocks), 64, 0, sc>>>(pa.blocks, w.crcacc, 0, ct, pa.nblocks);
         if (beside) {
             const size_t need = (size_t)pa.maxblocks * sizeof(BlockDesc);
-            if (need > ctx->crc_host_cap) {
-                if (ctx->crc_host) hipHostFree(ctx->crc_host);
-                ctx->crc_host = nullptr;
-                ctx->crc_host_cap = 0;
-                if (hipHostMalloc((void **)&ctx->crc_host, need * 2, hipHostMallocDefault) != hipSuccess) {
-                    bzh_set_error(ctx, "hipHostMalloc(%zu) for the block CRCs failed", need * 2);
-                    return BZH_E_NOMEM;
-                }
-                ctx->crc_host_cap = need * 2;
-            }
+            BZH_TRY(ctx->crc_host.reserve(ctx, need, "the block CRCs", grow_double));
             ctx->crc_host_len = need;
             HIP_TRY(ctx, hipMemcpyAsync(ctx->crc_host, pa.blocks, need, hipMemcpyDeviceToHost, side));
             hipEventRecord(ctx->plan_ev[1], side);
@@ -1281,7 +1186,7 @@ int rle1_plan_crc_join(bzh_ctx *ctx)
     if (!ctx->crc_pending) return BZH_OK;
     ctx->crc_pending = false;
     HIP_TRY(ctx, hipEventSynchronize(ctx->plan_ev[1]));
-    const BlockDesc *hb = reinterpret_cast<const BlockDesc *>(ctx->crc_host);
+    const BlockDesc *hb = ctx->crc_host.as<const BlockDesc>();
     const size_t nb = std::min(ctx->plan_blocks.size(), ctx->crc_host_len / sizeof(BlockDesc));
     for (size_t b = 0; b < nb; b++) {
         ctx->plan_blocks[b].crc = hb[b].crc;
@@ -1300,7 +1205,7 @@ int rle1_plan_crc(bzh_ctx *ctx, size_t b0, size_t b1)
     while (b1 > b0 && ctx->plan_crc_ok[b1 - 1]) b1--;
     if (b0 == b1) return BZH_OK;
     hipStream_t st = ctx->stream;
-    PlanWs w = plan_layout((uint8_t *)ctx->plan_ws, ctx->plan_n, ctx->M, ctx->plan_extra);
+    PlanWs w = plan_layout(ctx->plan_ws, ctx->plan_n, ctx->M, ctx->plan_extra);
     PlanArrays &pa = w.pa;
     const uint32_t nb = (uint32_t)(b1 - b0);
     uint64_t maxlen = 0;
@@ -1330,7 +1235,7 @@ int rle1_emit(bzh_ctx *ctx, size_t b0, uint32_t B)
 {
     if (B == 0) return BZH_OK;
     const bzh_ctx *pc = ctx->parent ? ctx->parent : ctx; // lanes read the owner's plan
-    PlanWs w = plan_layout((uint8_t *)pc->plan_ws, pc->plan_n, pc->M, pc->plan_extra);
+    PlanWs w = plan_layout(pc->plan_ws, pc->plan_n, pc->M, pc->plan_extra);
     EmitArgs ea{};
     ea.in = pc->plan_in;
     ea.n = pc->plan_n;
@@ -1398,12 +1303,6 @@ int crc_blocks_device(bzh_ctx *ctx, const uint8_t *d_in, BlockDesc *d_blocks, ui
 // followed by one guard byte that differs from the input's last byte and from the next input's first.  A run then never
 // continues from one input into the next, so the run tables of rle1_plan_tables describe every input as its own buffer
 // would, and a cut (cut_block_to) only ever takes differences of canonical offsets inside one input.
-struct ManyInput {
-    uint32_t gs;   // first byte in the guarded buffer (its guard is at gs + len)
-    uint32_t len;  // bytes of the input
-    uint32_t slot; // first record slot of the input in the split's record area (room for len / ((M-1) 4/5) + 1 blocks)
-    uint32_t cnt;  // blocks cut (plan_many_split); 0xFFFFFFFF: more than that room
-};
 
 __device__ __forceinline__ uint32_t many_room(uint32_t len, uint32_t M) { return len ? len / ((M - 1u) * 4u / 5u) + 1u : 0u; }
 
@@ -1519,48 +1418,31 @@ int rle1_plan_many(bzh_ctx *ctx, const uint8_t *d_in, const size_t *lens, size_t
     uint64_t total = 0;
     for (size_t k = 0; k < count; k++) total += lens[k];
     if (total == 0) return rle1_plan_tables(ctx, d_in, 0, 0); // (no blocks: every stream is empty)
-    const uint64_t ng = total + count;
-    const uint32_t D = (ctx->M - 1u) * 4u / 5u;
+    BZH_TRY(ctx->many_ws.reserve(ctx, many_layout(nullptr, lens, count, ctx->M).bytes, "the plan of many inputs"));
+    const ManyWs mw = many_layout(ctx->many_ws, lens, count, ctx->M);
+    const uint64_t ng = mw.ng;
     ctx->many_tab.resize(count * 4);
     ManyInput *tab = reinterpret_cast<ManyInput *>(ctx->many_tab.data());
     uint64_t pos = 0, slots = 0;
     for (size_t k = 0; k < count; k++) {
         tab[k] = ManyInput{(uint32_t)(pos + k), (uint32_t)lens[k], (uint32_t)slots, 0u};
-        slots += lens[k] ? lens[k] / D + 1 : 0;
+        slots += many_slots(lens[k], ctx->M);
         pos += lens[k];
     }
-    // workspace: guarded buffer | inputs | split records | block -> input (the plan's bound: plan_layout with one extra block an input)
-    const uint64_t maxblocks = ng / D + 4 + count;
-    const size_t o_tab = a256(ng + 32), o_sb = o_tab + a256(count * sizeof(ManyInput)), o_sa = o_sb + a256(slots * sizeof(BlockDesc)),
-                 o_bin = o_sa + a256(slots * sizeof(BlockAux)), bytes = o_bin + a256(maxblocks * 4);
-    if (bytes > ctx->many_ws_size) {
-        if (ctx->many_ws) hipFree(ctx->many_ws);
-        ctx->many_ws = nullptr;
-        ctx->many_ws_size = 0;
-        if (hipMalloc((void **)&ctx->many_ws, bytes) != hipSuccess) {
-            bzh_set_error(ctx, "hipMalloc(%zu) for the plan of %zu inputs failed", bytes, count);
-            return BZH_E_NOMEM;
-        }
-        ctx->many_ws_size = bytes;
-    }
-    uint8_t *gbuf = ctx->many_ws;
-    ManyInput *d_tab = reinterpret_cast<ManyInput *>(ctx->many_ws + o_tab);
-    BlockDesc *d_sb = reinterpret_cast<BlockDesc *>(ctx->many_ws + o_sb);
-    BlockAux *d_sa = reinterpret_cast<BlockAux *>(ctx->many_ws + o_sa);
-    ctx->many_binp = reinterpret_cast<uint32_t *>(ctx->many_ws + o_bin);
-    HIP_TRY(ctx, hipMemcpyAsync(d_tab, tab, count * sizeof(ManyInput), hipMemcpyHostToDevice, st));
+    ctx->many_binp = mw.binp;
+    HIP_TRY(ctx, hipMemcpyAsync(mw.tab, tab, count * sizeof(ManyInput), hipMemcpyHostToDevice, st));
     {
         KSpan ks(ctx, K_PLAN, 2 * ng, 1);
-        many_stage<<<dim3((uint32_t)((ng + 16 * 256 - 1) / (16 * 256))), 256, 0, st>>>(d_in, gbuf, ng, d_tab, (uint32_t)count);
+        many_stage<<<dim3((uint32_t)((ng + 16 * 256 - 1) / (16 * 256))), 256, 0, st>>>(d_in, mw.gbuf, ng, mw.tab, (uint32_t)count);
     }
-    BZH_TRY(rle1_plan_tables(ctx, gbuf, ng, (uint32_t)count));
-    PlanWs w = plan_layout((uint8_t *)ctx->plan_ws, ng, ctx->M, ctx->plan_extra);
+    BZH_TRY(rle1_plan_tables(ctx, mw.gbuf, ng, (uint32_t)count));
+    PlanWs w = plan_layout(ctx->plan_ws, ng, ctx->M, ctx->plan_extra);
     PlanArrays &pa = w.pa;
-    pa.in = gbuf;
+    pa.in = mw.gbuf;
     {
         KSpan ks(ctx, K_PLAN, 0, 2);
-        plan_many_split<<<dim3((uint32_t)((count + MANY_WAVES - 1) / MANY_WAVES)), 64 * MANY_WAVES, 0, st>>>(pa, d_tab, (uint32_t)count, d_sb, d_sa);
-        plan_many_compact<<<dim3(1), 1024, 0, st>>>(pa, d_tab, (uint32_t)count, d_sb, d_sa, ctx->many_binp);
+        plan_many_split<<<dim3((uint32_t)((count + MANY_WAVES - 1) / MANY_WAVES)), 64 * MANY_WAVES, 0, st>>>(pa, mw.tab, (uint32_t)count, mw.sb, mw.sa);
+        plan_many_compact<<<dim3(1), 1024, 0, st>>>(pa, mw.tab, (uint32_t)count, mw.sb, mw.sa, ctx->many_binp);
     }
     const CrcTables *ct = nullptr;
     BZH_TRY(crc_tables(ctx, &ct));
@@ -1568,7 +1450,7 @@ int rle1_plan_many(bzh_ctx *ctx, const uint8_t *d_in, const size_t *lens, size_t
         KSpan ks(ctx, K_CRC, ng, 2);
         HIP_TRY(ctx, hipMemsetAsync(w.crcacc, 0, (size_t)pa.maxblocks * 4, st));
         const uint64_t ranges = ng / ((uint64_t)CRC_TILE * CRC_WG_TILES) + pa.maxblocks + 1;
-        crc_tiles_flat<<<dim3((uint32_t)ranges), RL_THREADS, 0, st>>>(gbuf, pa.blocks, w.crcacc, ct, pa.nblocks);
+        crc_tiles_flat<<<dim3((uint32_t)ranges), RL_THREADS, 0, st>>>(mw.gbuf, pa.blocks, w.crcacc, ct, pa.nblocks);
         crc_finish<<<dim3(pa.maxblocks), 64, 0, st>>>(pa.blocks, w.crcacc, 0, ct, pa.nblocks);
     }
     // blocks | aux | nblocks are consecutive in the workspace (plan_layout): one copy back

@@ -178,21 +178,6 @@ __global__ void __launch_bounds__(64) sync_emit(Batch bt, const int32_t *tlast, 
     if (lane < 8) o[64 + lane] = pw[64 + lane];
 }
 
-// ctx->sync_ws of at least `need` bytes (the stream is idle: the caller has waited for the batch)
-static int emit_ws_reserve(bzh_ctx *ctx, size_t need)
-{
-    if (ctx->sync_ws && ctx->sync_ws_size >= need) return BZH_OK;
-    if (ctx->sync_ws) hipFree(ctx->sync_ws);
-    ctx->sync_ws = nullptr;
-    ctx->sync_ws_size = 0;
-    if (hipMalloc((void **)&ctx->sync_ws, need) != hipSuccess) {
-        bzh_set_error(ctx, "hipMalloc(%zu) for the sync points of a batch failed", need);
-        return BZH_E_NOMEM;
-    }
-    ctx->sync_ws_size = need;
-    return BZH_OK;
-}
-
 // Blocks 0..B-1 of the batch in the arena are plan blocks k0.., packed from stream bit `bit_base` on, and the stream has been
 // waited for: their entries and sync points are appended to ix.
 int sync_emit_batch(bzh_ctx *ctx, uint32_t B, size_t k0, uint64_t bit_base, EncIndex &ix)
@@ -232,7 +217,7 @@ int sync_emit_batch(bzh_ctx *ctx, uint32_t B, size_t k0, uint64_t bit_base, EncI
         bzh_set_error(ctx, "%zu sync points in one batch", npts);
         return BZH_E_NOMEM;
     }
-    BZH_TRY(emit_ws_reserve(ctx, npts * sizeof(bzh_sync_point)));
+    BZH_TRY(ctx->sync_ws.reserve(ctx, npts * sizeof(bzh_sync_point), "the sync points of a batch"));
     SyncEmitArgs a;
     a.interval = ix.interval;
     a.TL = mtf_tile_bytes(B);
@@ -241,9 +226,9 @@ int sync_emit_batch(bzh_ctx *ctx, uint32_t B, size_t k0, uint64_t bit_base, EncI
     a.selmax = (bt.S + 64 + 49) / 50 + 2;
     a.entry_base = entry_base;
     a.bit_base = bit_base;
-    const int32_t *tlast = reinterpret_cast<const int32_t *>(bt.listA); // (mtf_run)
-    const MtfTile *rt = reinterpret_cast<const MtfTile *>(bt.listB);
-    bzh_sync_point *d_pts = reinterpret_cast<bzh_sync_point *>(ctx->sync_ws);
+    const int32_t *tlast = mtf_tlast(bt); // (as mtf_run left them)
+    const MtfTile *rt = mtf_tiles(bt);
+    bzh_sync_point *d_pts = ctx->sync_ws.as<bzh_sync_point>();
     if (ctx->mode == BZH_MODE_FIXED)
         sync_emit<true><<<dim3(maxper, B), 64, 0, st>>>(bt, tlast, rt, a, d_pts, (uint32_t)npts);
     else

@@ -10,7 +10,7 @@
 //   rank     the stable LF^-1 permutation T: T[base[L[i]]++] = i, 64 positions a step by wavefront ballots
 //   walk     X[i] = T^i(ptr) by pointer doubling, as unbwt_round does: with X[0..m) and P = T^m known, X[m + i] = P[X[i]] and
 //            T^2m = P o P (squared through registers, so one array holds it)
-//   emit     S[i] = L[X[i + 1]], i < n, into bt.mtfpos where unrle_maps expects the block
+//   emit     S[i] = L[X[i + 1]], i < n, into bt.unbwt_out where unrle_maps expects the block
 //
 // The rule is unbwt_run's to the letter: the last byte is L[T^n(ptr)], not L[ptr], so a column that is no BWT of anything (a
 // cycle of T whose length does not divide n) comes out as libbz2's walk gives it.  tests/unbwt_small_model.py restates these
@@ -140,12 +140,12 @@ bool unbwt_small_enabled()
     return !(e && !strcmp(e, "0"));
 }
 
-// The inverse BWT of the K batch slots listed at d_slots, each of at most UNBWT_SMALL_MAX bytes: bt.bwt / bt.n / bt.ptr -> bt.mtfpos
+// The inverse BWT of the K batch slots listed at d_slots, each of at most UNBWT_SMALL_MAX bytes: bt.bwt / bt.n / bt.ptr -> bt.unbwt_out
 int unbwt_small_run(bzh_ctx *ctx, const uint32_t *d_slots, uint32_t K)
 {
     if (K == 0) return BZH_OK;
     const Batch &bt = ctx->bt;
-    unbwt_small_kernel<<<dim3(K), US_THREADS, 0, ctx->stream>>>(bt.bwt, bt.n, bt.ptr, bt.mtfpos, bt.S, d_slots);
+    unbwt_small_kernel<<<dim3(K), US_THREADS, 0, ctx->stream>>>(bt.bwt, bt.n, bt.ptr, bt.unbwt_out, bt.S, d_slots);
     HIP_TRY(ctx, hipGetLastError());
     return BZH_OK;
 }

@@ -109,7 +109,7 @@ impl Drop for Ctx {
 unsafe impl Send for Ctx {}
 
 // Process-wide pool of contexts, keyed by (device, level) -- what banzai_amd/__init__.py keeps in `_contexts`.
-// A context owns its workspace arena (45 MB per bzip2 block of a batch: 5.8 GB for a 100 MB input), allocated and
+// A context owns its workspace arena (56 MB per bzip2 block of a batch: 6.3 GB for a 100 MB input), allocated and
 // first-touched on the first encode that needs it; a caller that loops over files through `encode` must not pay that --
 // nor `bzh_create` -- per call.  `encode` checks a context OUT of the pool (two threads never share one), and back
 // IN when its stream ended cleanly; a context whose stream failed is dropped.  At most POOL_KEEP idle contexts a key.
