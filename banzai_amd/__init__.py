@@ -11,6 +11,12 @@ and, beyond the reference (which "(currently)" has no decompressor, README.md:9)
     decompress(data) -> bytes                            (one or more .bz2 streams, as bz2.decompress)
     decode(reader, writer) -> bytes written
 
+and, for a damaged archive, per block what decompress is per input (what bzip2recover is for):
+
+    recover(data) -> Recovered                           (the bytes of every block that verifies, a report of every one that
+                                                          does not; .kept, .lost, .complete)
+    recover_stream(data, report=None) -> bytes           (the kept blocks, bit for bit, as one valid .bz2 stream)
+
 and random access into a .bz2 without decoding all of it (bzip2 blocks are independent once their start bit is known):
 
     build_index(data) -> BlockIndex                      (every block: where it starts, what it decodes to; verified)
@@ -25,6 +31,7 @@ Everything is computed by hand-written HIP kernels behind the C ABI in include/b
 (libbzhip.so); there is no CPU path.  `reader` is any object with .read(), `writer` any object
 with .write() (the Rust signature takes BufRead / BufWriter<W>).
 """
+import collections
 import io
 import struct
 import zlib
@@ -34,7 +41,7 @@ import numpy as np
 from . import _native
 
 __all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "build_index", "decompress_range", "BlockIndex",
-           "IndexedReader", "build_sync_index", "SyncIndex", "encode_indexed", "Context", "MultiContext", "BzhError"]
+           "IndexedReader", "build_sync_index", "SyncIndex", "encode_indexed", "recover", "recover_stream", "Recovered", "RecoveredBlock", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
 MultiContext = _native.MultiContext
@@ -234,6 +241,72 @@ def decompress_many(inputs, device=0, errors="raise"):
         size += len(v) + 1
     run(group)
     return out
+
+
+RecoveredBlock = collections.namedtuple("RecoveredBlock", "bit_pos end_bit out_off out_len crc kind flags err_bit")
+RecoveredBlock.__doc__ = """One entry of a recovery report (bzh_recover_entry).  kind 0: kept -- its bytes are data[out_off : out_off +
+out_len]; else lost, and why (_native.LOST_*).  flags, on kept blocks: _native.REC_JOINED / REC_STREAM_END / REC_STREAM_OK."""
+
+
+class Recovered(collections.namedtuple("Recovered", "data blocks stats")):
+    """What recover() returns: `data`, the bytes of the kept blocks back to back; `blocks`, one RecoveredBlock per block magic
+    that is not another block's payload, ascending; `stats`, bzh_recover_stats as a dict."""
+    __slots__ = ()
+
+    @property
+    def kept(self):
+        return [b for b in self.blocks if b.kind == 0]
+
+    @property
+    def lost(self):
+        return [b for b in self.blocks if b.kind != 0]
+
+    @property
+    def complete(self):
+        """Nothing is lost, and every kept block lies in a stream that checks out as a whole (STREAM_OK): every block is
+        joined to a stream header or to the block before it, and every run of joined blocks ends in an intact footer."""
+        bl = self.blocks
+        for i, b in enumerate(bl):
+            if b.kind != 0 or not b.flags & _native.REC_JOINED:
+                return False
+            runs_on = i + 1 < len(bl) and bl[i + 1].bit_pos == b.end_bit
+            if not runs_on and not b.flags & _native.REC_STREAM_OK:
+                return False
+        return True
+
+
+def _blocks_of(entries):
+    return [RecoveredBlock(*(int(e[k]) for k in RecoveredBlock._fields)) for e in entries]
+
+
+def recover(data, device=0):
+    """Every block of a damaged .bz2 that still verifies (bzh_recover): `data` (bytes-like) is scanned for block magics at any
+    bit alignment and every block is judged on its own -- entropy decode, size, CRC -- whatever became of its neighbours, its
+    stream header or its footer.  -> Recovered(data, blocks, stats).  Nothing is raised for damage: an input without one
+    block gives empty data and no blocks.  Computed on the GPU on a level-9 context."""
+    view = _bytes_view(data, "recover")
+    ctx = _ctx(9, device)
+    out, ent = ctx.recover(view)
+    return Recovered(out, _blocks_of(ent), ctx.recover_stats())
+
+
+def recover_stream(data, report=None, device=0):
+    """The salvage of a damaged .bz2 as one valid .bz2 stream (bzh_recover_stream): "BZh9", the kept blocks' own bits in order,
+    a footer with the fold of their CRCs -- bz2.decompress of it gives recover(data).data.  report: a Recovered of the same
+    data, its blocks, or a structured array of _native.RECOVER_DTYPE; None: recover(data) is run first.  A report that is not
+    well formed for the data raises BzhError (-1; -6 where an entry points at no block magic)."""
+    view = _bytes_view(data, "recover_stream")
+    if report is not None and not isinstance(report, (Recovered, list, tuple, np.ndarray)):
+        raise TypeError(f"report must be a Recovered, a list of RecoveredBlock or an array of RECOVER_DTYPE, not {type(report).__name__}")
+    ctx = _ctx(9, device)
+    if report is None:
+        entries = ctx.recover(view)[1]
+    elif isinstance(report, np.ndarray):
+        entries = report
+    else:
+        blocks = report.blocks if isinstance(report, Recovered) else report
+        entries = np.array([tuple(b) for b in blocks], dtype=_native.RECOVER_DTYPE)
+    return ctx.recover_stream(view, entries)
 
 
 def decode(reader, writer, device=0):

@@ -74,6 +74,32 @@ assert INDEX_DTYPE.itemsize == ctypes.sizeof(IndexEntry) == 40
 idxp = ctypes.POINTER(IndexEntry)
 
 
+class RecoverEntry(ctypes.Structure):
+    """bzh_recover_entry: one block magic of a damaged input, kept (kind 0) or lost"""
+    _fields_ = [("bit_pos", ctypes.c_uint64), ("end_bit", ctypes.c_uint64), ("out_off", ctypes.c_uint64),
+                ("out_len", ctypes.c_uint32), ("crc", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("err_bit", ctypes.c_uint64)]
+
+
+RECOVER_DTYPE = np.dtype([("bit_pos", "<u8"), ("end_bit", "<u8"), ("out_off", "<u8"), ("out_len", "<u4"), ("crc", "<u4"),
+                          ("kind", "<u4"), ("flags", "<u4"), ("err_bit", "<u8")])
+assert RECOVER_DTYPE.itemsize == ctypes.sizeof(RecoverEntry) == 48
+recp = ctypes.POINTER(RecoverEntry)
+LOST_TRUNC, LOST_FORMAT, LOST_BLOCK_CRC, LOST_RANDOMISED = 2, 3, 4, 6
+LOST_NAMES = {LOST_TRUNC: "truncated", LOST_FORMAT: "field outside the format", LOST_BLOCK_CRC: "block CRC mismatch",
+              LOST_RANDOMISED: "randomised block"}
+REC_JOINED, REC_STREAM_END, REC_STREAM_OK = 1, 2, 4
+
+
+class RecoverStats(ctypes.Structure):
+    """bzh_recover_stats"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("candidates", "kept", "lost", "shadowed", "footers", "streams_ok", "batches",
+                                               "out_bytes")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class SyncPoint(ctypes.Structure):
     """bzh_sync_point: the entropy stage's state at a group boundary inside a block"""
     _fields_ = [("bit_pos", ctypes.c_uint64), ("entry", ctypes.c_uint32), ("group", ctypes.c_uint32), ("out_pos", ctypes.c_uint32),
@@ -129,6 +155,13 @@ SIGNATURES = {
                                        ctypes.POINTER(ctypes.c_int), szp]),
     "bzh_decode_many_small_max": (ctypes.c_size_t, []),
     "bzh_get_decode_many_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DecodeManyStats)]),
+    "bzh_recover_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, szp, recp,
+                                          ctypes.c_size_t, szp]),
+    "bzh_recover": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u8p, ctypes.c_size_t, szp, recp, ctypes.c_size_t, szp]),
+    "bzh_get_recover_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RecoverStats)]),
+    "bzh_recover_stream_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, recp, ctypes.c_size_t, ctypes.c_void_p,
+                                                 ctypes.c_size_t, szp]),
+    "bzh_recover_stream": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, recp, ctypes.c_size_t, u8p, ctypes.c_size_t, szp]),
     "bzh_decode_index": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, idxp, ctypes.c_size_t, szp, u64p, szp]),
     "bzh_decode_index_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, idxp, ctypes.c_size_t, szp,
                                                u64p, szp]),
@@ -227,6 +260,12 @@ def _entries(entries):
     """a contiguous array of the 40-byte entries (no copy when it already is one) and its ctypes pointer"""
     e = np.ascontiguousarray(entries, dtype=INDEX_DTYPE)
     return e, (e.ctypes.data_as(idxp) if e.size else None)
+
+
+def _report(entries):
+    """a contiguous array of the 48-byte recovery entries and its ctypes pointer"""
+    e = np.ascontiguousarray(entries, dtype=RECOVER_DTYPE)
+    return e, (e.ctypes.data_as(recp) if e.size else None)
 
 
 def _points(points):
@@ -587,6 +626,84 @@ class Context:
         s = DecodeManyStats()
         self.check(lib().bzh_get_decode_many_stats(self._h, ctypes.byref(s)))
         return s.as_dict()
+
+    # ---- recovery (bzh_recover*) ----
+    def recover_raw(self, data, cap, max_entries):
+        """one bzh_recover call into a buffer of `cap` bytes and a report of `max_entries` entries -> (status, bytes or None,
+        size reported, entries as a structured array of RECOVER_DTYPE or None, entries reported).  The bytes are None unless
+        they fit, the entries unless they do."""
+        a = np.frombuffer(data, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        ent = np.empty(max(max_entries, 1), dtype=RECOVER_DTYPE)
+        olen, cnt = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        st = lib().bzh_recover(self._h, ptr(src), n, ptr(out) if cap else None, cap, ctypes.byref(olen),
+                               ent.ctypes.data_as(recp) if max_entries else None, max_entries, ctypes.byref(cnt))
+        if st not in (0, -4):
+            self.check(st)
+        return (st, out[:olen.value].tobytes() if olen.value <= cap else None, int(olen.value),
+                ent[:cnt.value].copy() if cnt.value <= max_entries else None, int(cnt.value))
+
+    def recover(self, data):
+        """bzh_recover: (the bytes of every block of `data` that verifies, the report as a structured array of RECOVER_DTYPE).
+        One call with a guessed room for the bytes and for the report; BZH_E_CAP names what either needs, and the call is
+        repeated with that."""
+        n = len(data)
+        cap, room = 6 * n + (1 << 16), n // 1000 + 64
+        for _ in range(3):
+            st, out, need, ent, cnt = self.recover_raw(data, cap, room)
+            if st != -4:
+                break
+            cap, room = max(cap, need), max(room, cnt)
+        self.check(st)
+        return out, ent
+
+    def recover_device(self, d_in, n, d_out, cap, max_entries):
+        """bzh_recover_device on integer device addresses -> (status, size reported, entries or None, entries reported);
+        BZH_E_CAP (-4) is handed back, not raised"""
+        ent = np.empty(max(max_entries, 1), dtype=RECOVER_DTYPE)
+        olen, cnt = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        st = lib().bzh_recover_device(self._h, ctypes.c_void_p(d_in), n, ctypes.c_void_p(d_out), cap, ctypes.byref(olen),
+                                      ent.ctypes.data_as(recp) if max_entries else None, max_entries, ctypes.byref(cnt))
+        if st not in (0, -4):
+            self.check(st)
+        return st, int(olen.value), (ent[:cnt.value].copy() if cnt.value <= max_entries else None), int(cnt.value)
+
+    def recover_stats(self):
+        s = RecoverStats()
+        self.check(lib().bzh_get_recover_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
+
+    def recover_stream_raw(self, data, entries, cap):
+        """one bzh_recover_stream call into a buffer of `cap` bytes -> (status, bytes or None, size reported)"""
+        a = np.frombuffer(data, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        e, p = _report(entries)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        olen = ctypes.c_size_t(0)
+        st = lib().bzh_recover_stream(self._h, ptr(src), n, p, e.size, ptr(out) if cap else None, cap, ctypes.byref(olen))
+        return st, (out[:olen.value].tobytes() if st == 0 else None), int(olen.value)
+
+    def recover_stream(self, data, entries):
+        """bzh_recover_stream: the kept blocks of the report, bit for bit, as one .bz2 stream of the context's level"""
+        e, _ = _report(entries)
+        kept = e[e["kind"] == 0]
+        bits = int((kept["end_bit"].astype(object) - kept["bit_pos"].astype(object)).sum()) if kept.size else 0
+        st, out, need = self.recover_stream_raw(data, e, 4 + max(0, bits + 80 + 7) // 8)
+        if st == -4:
+            st, out, need = self.recover_stream_raw(data, e, need)
+        self.check(st)
+        return out
+
+    def recover_stream_device(self, d_in, n, entries, d_out, cap):
+        """bzh_recover_stream_device on integer device addresses -> (status, size reported); nothing is raised"""
+        e, p = _report(entries)
+        olen = ctypes.c_size_t(0)
+        st = lib().bzh_recover_stream_device(self._h, ctypes.c_void_p(d_in), n, p, e.size, ctypes.c_void_p(d_out), cap,
+                                             ctypes.byref(olen))
+        return st, int(olen.value)
 
     def decode_index(self, data):
         """bzh_decode_index: the verified block index of the stream(s) in `data` -> (entries as a structured array of

@@ -15,7 +15,9 @@
 #include <thread>
 
 #include "common.h"
+#include "decode_recover_plan.h"
 #include "encode_plan.h"
+#include "recover_gather.h"
 
 static void stream_join(bzh_ctx *ctx); // waits for a streaming pass in flight (defined with bzh_stream_*)
 
@@ -1640,6 +1642,159 @@ extern "C" int bzh_get_decode_many_stats(const bzh_ctx *ctx, bzh_decode_many_sta
     return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
     if (!ctx || !out) return BZH_E_ARG;
     *out = ctx->mstats;
+    return BZH_OK;
+    });
+}
+
+// ---- recovery (decode.hip's decode_recover_run; recover.hip's gather): per block what bzh_decode is per input
+extern "C" int bzh_recover_device(bzh_ctx *ctx, const void *d_in, size_t n, void *d_out, size_t cap, size_t *out_len, bzh_recover_entry *ent,
+                                  size_t max, size_t *count)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n) || (!d_out && cap) || !out_len || (!ent && max) || !count) return BZH_E_ARG;
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
+    memset(&ctx->rstats, 0, sizeof ctx->rstats);
+    *out_len = 0;
+    *count = 0;
+    std::vector<uint64_t> cands;
+    BZH_TRY(decode_call_scan(ctx, call, d_in, n, cands));
+    std::vector<bzh_recover_entry> entries;
+    int rc = decode_recover_run(ctx, (const uint8_t *)d_in, n, (uint8_t *)d_out, cap, out_len, entries, ctx->rstats, cands);
+    rc = decode_call_end(ctx, call, rc);
+    if (rc != BZH_OK && rc != BZH_E_CAP) return rc;
+    bzh_decode_stats &ds = ctx->dstats;
+    ds.blocks = ctx->rstats.kept;
+    ds.streams = ctx->rstats.streams_ok;
+    ds.candidates_off_chain = ctx->rstats.shadowed;
+    ds.out_bytes = ctx->rstats.out_bytes;
+    *count = entries.size();
+    if (entries.size() > max) {
+        bzh_set_error(ctx, "recover: %zu entries, room for %zu", entries.size(), max);
+        return BZH_E_CAP;
+    }
+    if (!entries.empty()) memcpy(ent, entries.data(), entries.size() * sizeof(bzh_recover_entry));
+    return rc;
+    });
+}
+
+extern "C" int bzh_recover(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len, bzh_recover_entry *ent,
+                           size_t max, size_t *count)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n) || (!out && cap) || !out_len || (!ent && max) || !count) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BZH_TRY(decode_stage(ctx, in, n, cap));
+    size_t len = 0;
+    const int rc = bzh_recover_device(ctx, ctx->d_stage_in, n, cap ? ctx->d_stage_out : nullptr, cap, &len, ent, max, count);
+    *out_len = len; // (BZH_E_CAP: the size needed)
+    if (len > cap || (rc != BZH_OK && rc != BZH_E_CAP)) return rc;
+    if (len) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, len, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+    return rc;
+    });
+}
+
+extern "C" int bzh_get_recover_stats(const bzh_ctx *ctx, bzh_recover_stats *out)
+{
+    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
+    if (!ctx || !out) return BZH_E_ARG;
+    *out = ctx->rstats;
+    return BZH_OK;
+    });
+}
+
+// The report is checked as a whole and the size set before anything is launched; then the magics, the gather and the frame.
+extern "C" int bzh_recover_stream_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_recover_entry *ent, size_t count, void *d_out,
+                                         size_t cap, size_t *out_len)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n) || (!d_out && cap) || (!ent && count) || !out_len) return BZH_E_ARG;
+    *out_len = 0;
+    size_t bad = 0, kept = 0;
+    uint64_t body = 0;
+    if (const char *what = bzr_report_check(ent, count, n, &bad, &body, &kept)) {
+        bzh_set_error(ctx, "recover stream: entry %zu: %s", bad, what);
+        return BZH_E_ARG;
+    }
+    if (kept > 0x7FFFFFFFull) {
+        bzh_set_error(ctx, "recover stream: %zu kept blocks are beyond one launch", kept);
+        return BZH_E_ARG;
+    }
+    const uint64_t total_bits = 32 + body + 80;
+    const size_t bytes = (size_t)((total_bits + 7) / 8), words = (size_t)((total_bits + 31) / 32);
+    *out_len = bytes;
+    if (words * 4 > cap) {
+        bzh_set_error(ctx, "recover stream: the stream needs %zu bytes (%zu as whole words), the buffer holds %zu", bytes, words * 4, cap);
+        return BZH_E_CAP;
+    }
+    if (((uintptr_t)d_out & 3u) != 0) {
+        bzh_set_error(ctx, "recover stream: the output is not 4-byte aligned");
+        return BZH_E_ARG;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    std::vector<BzrDesc> descs;
+    std::vector<uint64_t> pos;
+    std::vector<size_t> entry_of;
+    std::vector<uint32_t> crcs;
+    descs.reserve(kept), pos.reserve(kept), entry_of.reserve(kept), crcs.reserve(kept);
+    uint64_t at = 32;
+    for (size_t k = 0; k < count; k++) {
+        if (ent[k].kind != 0) continue;
+        descs.push_back(BzrDesc{ent[k].bit_pos, at, ent[k].end_bit - ent[k].bit_pos});
+        at += ent[k].end_bit - ent[k].bit_pos;
+        pos.push_back(ent[k].bit_pos);
+        entry_of.push_back(k);
+        crcs.push_back(ent[k].crc);
+    }
+    size_t first_bad = kept;
+    BZH_TRY(decode_magic_run(ctx, (const uint8_t *)d_in, n, pos.data(), kept, &first_bad));
+    if (first_bad < kept) {
+        bzh_set_error(ctx, "recover stream: entry %zu: no block magic at bit %llu", entry_of[first_bad], (unsigned long long)pos[first_bad]);
+        return BZH_E_DATA;
+    }
+    // the gather writes the body's words whole; the header's word and the words the footer touches are ORed into
+    const size_t wtail = (size_t)((32 + body) / 32);
+    HIP_TRY(ctx, hipMemsetAsync(d_out, 0, 4, st));
+    HIP_TRY(ctx, hipMemsetAsync((uint8_t *)d_out + wtail * 4, 0, (words - wtail) * 4, st));
+    BZH_TRY(recover_gather_run(ctx, (const uint8_t *)d_in, n, descs, body, (uint32_t *)d_out));
+    stream_frame<<<1, 64, 0, st>>>((uint32_t *)d_out, ctx->level, body, fold_stream_crc(crcs.data(), crcs.size()));
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, bzh_stream_wait(st));
+    return BZH_OK;
+    });
+}
+
+extern "C" int bzh_recover_stream(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_recover_entry *ent, size_t count, uint8_t *out, size_t cap,
+                                  size_t *out_len)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n) || (!out && cap) || (!ent && count) || !out_len) return BZH_E_ARG;
+    *out_len = 0;
+    size_t bad = 0, kept = 0;
+    uint64_t body = 0;
+    if (const char *what = bzr_report_check(ent, count, n, &bad, &body, &kept)) {
+        bzh_set_error(ctx, "recover stream: entry %zu: %s", bad, what);
+        return BZH_E_ARG;
+    }
+    const size_t bytes = (size_t)((32 + body + 80 + 7) / 8), room = (bytes + 3) / 4 * 4;
+    *out_len = bytes;
+    if (bytes > cap) {
+        bzh_set_error(ctx, "recover stream: the stream needs %zu bytes, the buffer holds %zu", bytes, cap);
+        return BZH_E_CAP;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BZH_TRY(decode_stage(ctx, in, n, room));
+    size_t len = 0;
+    BZH_TRY(bzh_recover_stream_device(ctx, ctx->d_stage_in, n, ent, count, ctx->d_stage_out, room, &len));
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, len, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+    *out_len = len;
     return BZH_OK;
     });
 }

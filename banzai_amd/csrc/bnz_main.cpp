@@ -17,6 +17,7 @@
 
 namespace {
 const int SUCCESS = 0, ERR_ARGS = 1, ERR_FILESYSTEM = 2, ERR_OUTPUT = 3; // bnz/src/main.rs:11-14
+const int LOST_BLOCKS = 4; // --recover: the salvage is written, blocks were lost (no counterpart in the reference)
 
 const char *TAGLINE = "bnzhip: bzip2 encoder with banzai's output, computed on an AMD MI355X";
 const char *VERSION = "version alpha 0.3.1-hip";
@@ -41,6 +42,7 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "     --output <path.bz2>    write the stream to this file\n"
             "     --stdout    or   -c    write the stream to standard out\n"
             "     --decompress or  -d    decode <input_path> (one or more .bz2 streams) instead\n"
+            "     --recover              decode every block of a damaged <input_path> that still verifies\n"
             "     --keep      or   -k    keep the input file\n"
             "     --remove    or   -r    remove the input file\n\n"
             "     -1 to -9               block size in 100 kB units (default -9)\n"
@@ -54,7 +56,10 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "     '<input_path>.bz2' is written and the input removed; with an explicit output the\n"
             "     input is kept unless --remove is given.  With --decompress the input must end in\n"
             "     '.bz2' unless --output / --stdout is given; the default output is the path without\n"
-            "     that suffix, and the same keep / remove policy applies.  GPU: $BZHIP_DEVICE (default 0), or\n"
+            "     that suffix, and the same keep / remove policy applies.  --recover takes the paths of\n"
+            "     --decompress, writes the bytes of the intact blocks, names every lost block on standard\n"
+            "     error (bit position, reason) and exits with 0 when nothing was lost, with 4 (salvage\n"
+            "     written, blocks lost: the input is then kept) otherwise; it takes no level and no -d.  GPU: $BZHIP_DEVICE (default 0), or\n"
             "     $BZHIP_DEVICES=0,1,2,... to spread the blocks over several GPUs of this node;\n"
             "     BZHIP_HUFFMAN=fixed: 2-6 Huffman tables with refinement (smaller, not banzai's exact bytes).\n\n%s\n",
             VERSION);
@@ -70,7 +75,7 @@ int main(int argc, char **argv)
     std::string in_path, out_path;
     bool have_in = false, in_stdin = false, out_stdout = false, have_out = false;
     int keep = -1, level = 9;
-    bool decompress = false;
+    bool decompress = false, recover = false, level_given = false;
     auto set_input = [&](const std::string &p, bool is_stdin) {
         if (have_in) die(ERR_ARGS, "Only one input may be specified");
         have_in = true;
@@ -99,10 +104,11 @@ int main(int argc, char **argv)
                                  "to banzai 0.3.1's.\n\n" + VERSION);
             else if (a == "--verbose") {}
             else if (a == "--decompress") decompress = true;
+            else if (a == "--recover") recover = true;
             else if (a == "--keep") keep = 1;
             else if (a == "--remove") keep = 0;
-            else if (a == "--fast") level = 1;
-            else if (a == "--best") level = 9;
+            else if (a == "--fast") level = 1, level_given = true;
+            else if (a == "--best") level = 9, level_given = true;
             else if (a == "--output") expect = OUTPATH;
             else if (a == "--stdout") set_output("", true);
             else if (a == "--") expect = NOARGS;
@@ -118,7 +124,7 @@ int main(int argc, char **argv)
                     else if (f == 'k') keep = 1;
                     else if (f == 'r') keep = 0;
                     else if (f == 'v') {}
-                    else if (f >= '1' && f <= '9') level = f - '0';
+                    else if (f >= '1' && f <= '9') level = f - '0', level_given = true;
                     else die(ERR_ARGS, std::string("Flag '") + f + "' is not valid");
                 }
             }
@@ -127,15 +133,19 @@ int main(int argc, char **argv)
         }
     }
     if (!have_in) die(ERR_ARGS, "An input must be specified");
+    if (recover && decompress) die(ERR_ARGS, "'--recover' and '--decompress' exclude each other");
+    if (recover && level_given) die(ERR_ARGS, "'--recover' takes no block size: a block is held to what the format allows");
 
     FILE *inf = in_stdin ? stdin : fopen(in_path.c_str(), "rb");
     if (!inf) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + in_path + ": " + strerror(errno));
 
-    if (decompress) { // the whole input, one bzh_decode on a level-9 context (a second one if the first size guess was short)
+    if (decompress || recover) { // the whole input in memory, a level-9 context, one call (more where a size guess was short)
+        const char *doing = recover ? "error during recovery: " : "error during decompression: ";
         std::string dpath = out_path;
         if (!have_out && !in_stdin) {
             if (in_path.size() < 5 || in_path.compare(in_path.size() - 4, 4, ".bz2") != 0)
-                die(ERR_ARGS, "With --decompress the input path must end in '.bz2' unless --output or --stdout is given");
+                die(ERR_ARGS, std::string("With ") + (recover ? "--recover" : "--decompress") +
+                                  " the input path must end in '.bz2' unless --output or --stdout is given");
             dpath = in_path.substr(0, in_path.size() - 4);
         }
         std::vector<uint8_t> data;
@@ -145,7 +155,7 @@ int main(int argc, char **argv)
                 const size_t k = fread(buf.get(), 1, (size_t)16 << 20, inf);
                 data.insert(data.end(), buf.get(), buf.get() + k);
                 if (k < ((size_t)16 << 20)) {
-                    if (ferror(inf)) die(ERR_OUTPUT, "error during decompression: read failed");
+                    if (ferror(inf)) die(ERR_OUTPUT, std::string(doing) + "read failed");
                     break;
                 }
             }
@@ -154,31 +164,63 @@ int main(int argc, char **argv)
         const char *dv = getenv("BZHIP_DEVICE");
         bzh_ctx *dctx = nullptr;
         int ds = bzh_create(&dctx, dv ? atoi(dv) : 0, 9, 0);
-        if (ds != BZH_OK) die(ERR_OUTPUT, std::string("error during decompression: ") + bzh_strerror(ds));
+        if (ds != BZH_OK) die(ERR_OUTPUT, std::string(doing) + bzh_strerror(ds));
         static const uint8_t none = 0;
         const size_t n = data.size();
         size_t cap = 6 * n + 65536, got = 0;
         std::unique_ptr<uint8_t[]> out;
-        for (int attempt = 0; attempt < 2; attempt++) {
-            out.reset(new (std::nothrow) uint8_t[cap ? cap : 1]);
-            ds = out ? bzh_decode(dctx, n ? data.data() : &none, n, out.get(), cap, &got, nullptr) : BZH_E_NOMEM;
-            if (ds != BZH_E_CAP) break;
-            cap = got; // the size the library reports
+        size_t lost = 0;
+        if (recover) { // one bzh_recover with a guessed room for the bytes and for the report; BZH_E_CAP names what either needs
+            size_t count = 0, kept = 0;
+            std::vector<bzh_recover_entry> ent(n / 1000 + 64);
+            for (int attempt = 0; attempt < 3; attempt++) {
+                out.reset(new (std::nothrow) uint8_t[cap ? cap : 1]);
+                ds = out ? bzh_recover(dctx, n ? data.data() : &none, n, out.get(), cap, &got, ent.data(), ent.size(), &count) : BZH_E_NOMEM;
+                if (ds != BZH_E_CAP) break;
+                if (got > cap) cap = got;
+                if (count > ent.size()) ent.resize(count);
+            }
+            bzh_recover_stats rs{};
+            if (ds == BZH_OK) ds = bzh_get_recover_stats(dctx, &rs);
+            if (ds == BZH_OK) {
+                for (size_t k = 0; k < count; k++) {
+                    const bzh_recover_entry &e = ent[k];
+                    if (e.kind == 0) {
+                        kept++;
+                        continue;
+                    }
+                    lost++;
+                    const char *why = e.kind == BZH_LOST_TRUNC ? "truncated" : e.kind == BZH_LOST_FORMAT ? "field outside the format"
+                                    : e.kind == BZH_LOST_BLOCK_CRC ? "block CRC mismatch" : e.kind == BZH_LOST_RANDOMISED ? "randomised block" : "error";
+                    fprintf(stderr, "lost: block at bit %llu: %s (found at bit %llu)\n", (unsigned long long)e.bit_pos, why,
+                            (unsigned long long)e.err_bit);
+                }
+                fprintf(stderr, "recovered: %zu blocks kept, %zu lost, %zu bytes, %llu streams whole\n", kept, lost, got,
+                        (unsigned long long)rs.streams_ok);
+            }
+        } else { // one bzh_decode, a second one if the first size guess was short
+            for (int attempt = 0; attempt < 2; attempt++) {
+                out.reset(new (std::nothrow) uint8_t[cap ? cap : 1]);
+                ds = out ? bzh_decode(dctx, n ? data.data() : &none, n, out.get(), cap, &got, nullptr) : BZH_E_NOMEM;
+                if (ds != BZH_E_CAP) break;
+                cap = got; // the size the library reports
+            }
         }
         if (ds != BZH_OK) { // the input stays where it is, and no output is created
-            const std::string msg = std::string("error during decompression: ") + bzh_strerror(ds) + ": " + bzh_last_error(dctx);
+            const std::string msg = std::string(doing) + bzh_strerror(ds) + ": " + bzh_last_error(dctx);
             bzh_destroy(dctx);
             die(ERR_OUTPUT, msg);
         }
-        bzh_destroy(dctx);
+        bzh_destroy(dctx); // (both ways out below leave nothing open)
         FILE *df = stdout;
         if (!(have_out && out_stdout) && !(in_stdin && !have_out)) {
             df = fopen(dpath.c_str(), "wb");
             if (!df) die(ERR_FILESYSTEM, "[filesystem error] cannot create " + dpath + ": " + strerror(errno));
         }
-        if (got && fwrite(out.get(), 1, got, df) != got) die(ERR_OUTPUT, "error during decompression: write failed");
-        if (fflush(df) != 0) die(ERR_OUTPUT, "error during decompression: write failed");
+        if (got && fwrite(out.get(), 1, got, df) != got) die(ERR_OUTPUT, std::string(doing) + "write failed");
+        if (fflush(df) != 0) die(ERR_OUTPUT, std::string(doing) + "write failed");
         if (df != stdout) fclose(df);
+        if (lost) return LOST_BLOCKS; // (a damaged archive of which blocks were lost is never removed)
         const bool keep_in = keep >= 0 ? keep == 1 : have_out; // bnz/src/main.rs:292-300
         if (!keep_in && !in_stdin && remove(in_path.c_str()) != 0)
             die(ERR_OUTPUT, "error deleting input file: " + std::string(strerror(errno)));

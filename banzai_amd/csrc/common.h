@@ -179,6 +179,7 @@ struct bzh_ctx {
     DevBuf sync_ws;               // sync points (allocated on first use): the recorder's slots, a range's headers, points and segments, or an encoded batch's points
     bzh_decode_stats dstats{};
     bzh_decode_many_stats mstats{}; // of the last bzh_decode_many* call
+    bzh_recover_stats rstats{};     // of the last bzh_recover* call
     // streaming encode (bzh_stream_*)
     struct Stream {
         bool active = false, header_done = false;
@@ -538,6 +539,13 @@ int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_by
 // decode.hip: many inputs, one chain each, batches across them (the walk itself: decode_many_plan.h).  The slices have been checked.
 int decode_many_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const size_t *in_offs, const size_t *in_lens, size_t count, uint8_t *d_out,
                     size_t cap, size_t *out_offs, size_t *out_lens, int *status, size_t *consumed, const std::vector<uint64_t> &cands);
+// decode.hip: every block magic judged on its own (the walk itself: decode_recover_plan.h); the block magics at `count` bit positions
+int decode_recover_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t cap, size_t *out_len,
+                       std::vector<bzh_recover_entry> &entries, bzh_recover_stats &stats, const std::vector<uint64_t> &cands);
+int decode_magic_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const uint64_t *pos, size_t count, size_t *first_bad);
+// recover.hip: the bits of the kept blocks, end to end from bit 32 of d_out, in one launch (the per-word rule: recover_gather.h)
+struct BzrDesc;
+int recover_gather_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const std::vector<BzrDesc> &descs, uint64_t body, uint32_t *d_out);
 // unbwt_small.hip: the inverse BWT in LDS of the K listed batch slots, blocks of at most bzh_decode_many_small_max() bytes each
 // (bt.bwt / bt.n / bt.ptr -> bt.unbwt_out, as unbwt_run); its switch; the first four bytes of many slices in one launch
 int unbwt_small_run(bzh_ctx *ctx, const uint32_t *d_slots, uint32_t K);

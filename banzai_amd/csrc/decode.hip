@@ -22,6 +22,7 @@
 #include "decode_core.h"
 #include "decode_plan.h"
 #include "decode_many_plan.h"
+#include "decode_recover_plan.h"
 
 // ---- scan ------------------------------------------------------------------------------------------------------
 // 16 start bytes a lane, all 8 shifts of each against both 48-bit magics.  Hits are rare: an atomic append (the host sorts).
@@ -774,7 +775,10 @@ static int back_sizes(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk,
 // whole block: expanded where it belongs and checked there (unrle_walk<true>, crc_blocks_device).  A part of it: clipped
 // (unrle_walk_win), and its CRC folded from the bytes behind the inverse BWT with nothing more written (unrle_crc).  Empty: the
 // CRC alone -- the index build.  Only the kernels some block needs are launched.  crcs false: no CRC is taken.  One wait.
-static int back_emit(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk, uint8_t *d_out, bool crcs, std::vector<BackBlock> &blocks)
+// relist: `blocks` is not the list back_sizes was given but some of its blocks (bzh_recover's second emit, of the blocks the first
+// one's CRCs kept): the whole blocks' slots go up again.
+static int back_emit(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk, uint8_t *d_out, bool crcs, std::vector<BackBlock> &blocks,
+                     bool relist = false)
 {
     hipStream_t st = ctx->stream;
     auto up = [&](void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st); };
@@ -803,7 +807,7 @@ static int back_emit(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk, 
     UwArgs wa{w.wlo, w.whi, w.wbase, w.bsize, w.wacc, w.wcrc, nullptr};
     HIP_TRY(ctx, up(w.toff, bk.hoff.data(), bk.hoff.size() * 4));
     if (KF) {
-        if (KF != blocks.size()) HIP_TRY(ctx, up(w.slots, bk.fslots.data(), (size_t)KF * 4)); // (else it holds them since back_sizes)
+        if (KF != blocks.size() || relist) HIP_TRY(ctx, up(w.slots, bk.fslots.data(), (size_t)KF * 4)); // (else it holds them since back_sizes)
         HIP_TRY(ctx, up(w.obase, bk.fbase.data(), (size_t)KF * 8));
         unrle_walk<true><<<dim3(bk.Tn, KF), UR_THREADS, 0, st>>>(a);
     }
@@ -1169,6 +1173,127 @@ int decode_many_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const size_t *i
         bzh_set_error(ctx, "decode: the output needs %llu bytes, the buffer holds %zu", (unsigned long long)walk.total_out, cap);
         return BZH_E_CAP;
     }
+    return BZH_OK;
+}
+
+// ================================================================================================================
+// Recovery (bzh_recover*): every block magic judged on its own.  The walk is decode_recover_plan.h's; this feeds it the entropy
+// stage's results batch by batch, the sizes of the clean candidates and -- the verdict before the placement -- their CRCs folded
+// from the bytes behind the inverse BWT (an empty window: unrle_crc), and then expands the blocks it kept where they belong.
+// ================================================================================================================
+int decode_recover_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t cap, size_t *out_len,
+                       std::vector<bzh_recover_entry> &entries, bzh_recover_stats &stats, const std::vector<uint64_t> &cands)
+{
+    hipStream_t st = ctx->stream;
+    Batch &bt = ctx->bt;
+    DecWs w;
+    BZH_TRY(dec_ws(ctx, w));
+    if (w.T > UR_THREADS) {
+        bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
+        return BZH_E_STATE;
+    }
+    StageClock clock{ctx, {}};
+    BzrWalk walk;
+    walk.cands = cands.data();
+    walk.nc = cands.size();
+    walk.n = n;
+    walk.ctx_level = ctx->level;
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(walk.head, d_in, std::min<size_t>(n, 4), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, bzh_stream_wait(st));
+    walk.start();
+    const uint32_t Bmax = (uint32_t)std::min<size_t>(ctx->max_batch, ctx->arena_blocks);
+    std::vector<BzdResult> res;
+    std::vector<BackBlock> blocks, sub;
+    std::vector<size_t> sub_of; // the block of every listed one
+    Back bk;
+    size_t first;
+    uint32_t B;
+    while (walk.next_batch(Bmax, &first, &B)) {
+        hipEvent_t e0 = clock.mark();
+        HIP_TRY(ctx, hipMemcpyAsync(w.cand, cands.data() + first, (size_t)B * 8, hipMemcpyHostToDevice, st));
+        decode_block_kernel<<<dim3(B), 64, 0, st>>>(d_in, n, w.cand, bt, w.res, 100000u * (uint32_t)ctx->level);
+        HIP_TRY(ctx, hipGetLastError());
+        clock.span(1, e0);
+        res.resize(B);
+        HIP_TRY(ctx, hipMemcpyAsync(res.data(), w.res, (size_t)B * sizeof(BzdResult), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, bzh_stream_wait(st));
+        walk.feed(res.data());
+        blocks.clear();
+        for (const BzrItem &it : walk.items) blocks.push_back(BackBlock{it.slot, it.nblock, 0, false, 0, 0, 0, 0});
+        if (!blocks.empty()) {
+            const uint32_t Bu = blocks.back().slot + 1;
+            uint32_t nmax_all = 1; // (the inverse BWT runs over slots: every clean candidate among them sets its size)
+            for (uint32_t s = 0; s < Bu; s++)
+                if (!(cands[first + s] & 1ull) && res[s].kind == BZD_OK) nmax_all = std::max(nmax_all, res[s].nblock);
+            BZH_TRY(back_sizes(ctx, w, clock, bk, Bu, nmax_all, blocks));
+            // the verdict: the CRC of every block that does not end in four equal bytes without a count, nothing written
+            sub.clear(), sub_of.clear();
+            for (size_t q = 0; q < blocks.size(); q++) {
+                walk.items[q].size = blocks[q].size;
+                walk.items[q].bad_end = blocks[q].bad_end;
+                if (blocks[q].bad_end) continue;
+                sub.push_back(blocks[q]); // (lo == hi == 0: the empty window)
+                sub_of.push_back(q);
+            }
+            if (!sub.empty()) {
+                BZH_TRY(back_emit(ctx, w, clock, bk, nullptr, true, sub));
+                for (size_t q = 0; q < sub.size(); q++) walk.items[sub_of[q]].got_crc = sub[q].crc;
+            } else {
+                clock.span(3, bk.t_unrle);
+            }
+        }
+        walk.select();
+        walk.place(cap);
+        if (!walk.over) { // the placement: the kept blocks, whole
+            sub.clear();
+            for (size_t q = 0; q < blocks.size(); q++) {
+                if (!walk.items[q].kept) continue;
+                BackBlock b = blocks[q];
+                b.base = (int64_t)walk.items[q].base;
+                b.lo = 0;
+                b.hi = (uint32_t)b.size;
+                sub.push_back(b);
+            }
+            if (!sub.empty()) {
+                bk.t_unrle = clock.mark();
+                BZH_TRY(back_emit(ctx, w, clock, bk, d_out, false, sub, true));
+            }
+        }
+    }
+    walk.finish();
+    clock.collect();
+    entries.swap(walk.entries);
+    stats = walk.stats;
+    *out_len = (size_t)walk.total_out;
+    if (walk.over) {
+        bzh_set_error(ctx, "recover: the output needs %llu bytes, the buffer holds %zu", (unsigned long long)walk.total_out, cap);
+        return BZH_E_CAP;
+    }
+    return BZH_OK;
+}
+
+// first_bad: the first of the `count` bit positions at which no block magic stands (count: every one holds one)
+int decode_magic_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const uint64_t *pos, size_t count, size_t *first_bad)
+{
+    hipStream_t st = ctx->stream;
+    *first_bad = count;
+    if (count == 0) return BZH_OK;
+    uint64_t *d_cand = nullptr;
+    uint32_t *d_bad = nullptr;
+    BZH_TRY(reserve_cut(ctx, ctx->sync_ws, "the sync points", grow_mib, [&](Carver &c) { c.put(d_cand, count); c.put(d_bad, count); }));
+    std::vector<uint64_t> hc(count);
+    for (size_t k = 0; k < count; k++) hc[k] = pos[k] << 1;
+    std::vector<uint32_t> hbad(count);
+    HIP_TRY(ctx, hipMemcpyAsync(d_cand, hc.data(), count * 8, hipMemcpyHostToDevice, st));
+    range_magic_kernel<<<dim3((uint32_t)((count + 63) / 64)), 64, 0, st>>>(d_in, n, d_cand, (uint32_t)count, d_bad);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(hbad.data(), d_bad, count * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, bzh_stream_wait(st));
+    for (size_t k = 0; k < count; k++)
+        if (hbad[k]) {
+            *first_bad = k;
+            break;
+        }
     return BZH_OK;
 }
 

@@ -229,6 +229,92 @@ typedef struct {
 } bzh_decode_many_stats;
 BZH_API int bzh_get_decode_many_stats(const bzh_ctx *ctx, bzh_decode_many_stats *out);
 
+/* ---- recovery: every block of a damaged input that verifies, and a report of every one that does not ---------- */
+
+/* bzh_decode is all or nothing for an input, bzh_decode_many for each of its inputs; this is per BLOCK (what bzip2recover is
+ * for).  One report entry per block magic that is not another block's payload, in ascending bit_pos. */
+typedef struct {
+    uint64_t bit_pos;  /* of the block magic */
+    uint64_t end_bit;  /* kept: first bit behind the block; lost: 0 */
+    uint64_t out_off;  /* kept: where its bytes lie in out; lost: the running total there (where the hole falls) */
+    uint32_t out_len;  /* kept: decoded bytes; lost: 0 */
+    uint32_t crc;      /* stored block CRC (the 32 bits behind the magic; 0 if the input ends before them) */
+    uint32_t kind;     /* 0 = kept; else why it is lost: BZH_LOST_TRUNC 2, _FORMAT 3, _BLOCK_CRC 4, _RANDOMISED 6 */
+    uint32_t flags;    /* kept entries only: BZH_REC_* */
+    uint64_t err_bit;  /* lost: where the failure was found; kept: 0 */
+} bzh_recover_entry;   /* 48 bytes */
+
+enum { BZH_LOST_TRUNC = 2, BZH_LOST_FORMAT = 3, BZH_LOST_BLOCK_CRC = 4, BZH_LOST_RANDOMISED = 6 };
+enum { BZH_REC_JOINED = 1, BZH_REC_STREAM_END = 2, BZH_REC_STREAM_OK = 4 };
+
+/* The rules:
+ * 1. Candidates.  The candidates are the block magics of the scan (bzh_decode_scan), at any bit alignment, ascending.  A magic
+ *    of either kind that lies inside [bit_pos, end_bit) of the most recent KEPT block is that block's payload: it gets no entry
+ *    (bzh_recover_stats::shadowed counts it).  Every other block magic gets exactly one entry, kept or lost.  A false magic inside
+ *    the bytes of a LOST block cannot be told from a real one -- where a lost block ends is not known -- and is reported as lost.
+ * 2. Kept.  A block is kept when the entropy stage decodes it, it holds at most 100000 x the CONTEXT's level bytes (a stream
+ *    header may be gone, so no stream's level is asked), it does not end in four equal bytes without a count, and the CRC of its
+ *    decoded bytes equals the stored one.  Otherwise it is lost, `kind` naming the first of these checks that failed (a truncated
+ *    or malformed field or a RANDOMISED block: what the entropy stage says; too large or the open run: FORMAT).  Nothing about its
+ *    neighbours decides this: a block is kept even if no magic follows it -- the entropy stage knows where a block ends by itself,
+ *    so the block in front of a damaged magic is kept, which a split at the next magic would lose.
+ * 3. Output.  The kept blocks' bytes lie back to back in out, in ascending order, no gaps: out_off is the running sum.  A lost
+ *    block writes nothing anywhere.
+ * 4. Verdict before placement.  Every clean candidate's CRC is folded from the bytes behind its inverse BWT with nothing
+ *    written; only then are the kept blocks placed and expanded.  So cap == 0 with a null out is a complete verification run:
+ *    *out_len is the exact size needed and the report is whole (the status is BZH_E_CAP unless nothing was kept).  BZH_E_CAP for
+ *    a small out still returns every entry and *out_len (out is then unspecified); BZH_E_CAP for a small ent sets *count and
+ *    *out_len (ent is then unspecified, out is written if it fits).
+ * 5. Flags, on kept entries.  JOINED: the block starts 32 bits behind a stream header the walk accepts -- "BZh1".."BZh9" at
+ *    byte 0 of the input, or the one an intact footer outside every kept block reports behind itself, as bzh_decode finds the
+ *    next stream -- or it starts at the end_bit of the preceding entry and that entry is kept (the header, where both hold).
+ *    STREAM_END: a footer magic lies at end_bit.  STREAM_OK, on a STREAM_END entry: that footer parses, the run of kept JOINED
+ *    entries back from here reaches a stream header, every block of the run is within that header's level, and the fold of their
+ *    stored CRCs equals the footer's -- the streams bzh_decode would accept alone.  streams_ok counts them, and the empty streams
+ *    (an accepted header, an intact footer with CRC 0 right behind it), which have no entry.
+ * 6. Status.  BZH_OK whenever the call ran to the end: no magic at all (*count == 0, *out_len == 0) and every block lost
+ *    included -- the entries say what happened.  A stream above the context's level is not BZH_E_ARG here: its blocks that are
+ *    too large are lost as FORMAT.  BZH_E_ARG: a null pointer where a size is claimed, a null out_len or count.
+ * Not attempted: a second try at a kept block's end_bit when the magic there is damaged; RANDOMISED blocks (refused as by
+ * bzh_decode, here reported as lost).  Like every entry point the call joins a streaming pass in flight, runs on the context's
+ * stream, honours bzh_set_profiling and leaves the context usable after any outcome.  bzh_get_decode_stats: blocks = kept,
+ * streams = streams_ok, candidates = all magics, candidates_off_chain = shadowed. */
+BZH_API int bzh_recover_device(bzh_ctx *ctx, const void *d_in, size_t n, void *d_out, size_t cap, size_t *out_len,
+                               bzh_recover_entry *ent, size_t max, size_t *count);
+/* Same, host buffers in and out. */
+BZH_API int bzh_recover(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len,
+                        bzh_recover_entry *ent, size_t max, size_t *count);
+
+/* Counters of the last bzh_recover* call. */
+typedef struct {
+    uint64_t candidates; /* block magics the scan found */
+    uint64_t kept, lost; /* entries */
+    uint64_t shadowed;   /* magics of either kind inside a kept block */
+    uint64_t footers;    /* footer magics outside every kept block */
+    uint64_t streams_ok; /* rule 5 */
+    uint64_t batches;    /* entropy-stage launches */
+    uint64_t out_bytes;
+} bzh_recover_stats;
+BZH_API int bzh_get_recover_stats(const bzh_ctx *ctx, bzh_recover_stats *out);
+
+/* The salvage as ONE valid .bz2 stream, built from the kept blocks' own bits: "BZh" + the context's level, the bits
+ * [bit_pos, end_bit) of every kept entry (kind 0) concatenated in order, the footer magic, the fold of the entries' crc fields,
+ * zero padding to a byte.  An archive stays an archive, and any bzip2 decoder can check the result.  in[0..n) is the input the
+ * report was made from.  *out_len = 4 + ceil((sum of the kept entries' bits + 80) / 8) is pure arithmetic over the entries: it is
+ * set before anything is launched, and on BZH_E_CAP too; with no kept entry the result is the 14-byte empty stream.  Every block
+ * must be within the context's level for the stream to be valid: use the context the report was made with.
+ * The entries are untrusted (they may come from a file) and are checked as a whole first.  BZH_E_ARG, with bzh_last_error naming
+ * the entry: kept entries that do not ascend or that overlap, end_bit <= bit_pos + 80, end_bit > 8 n, a lost entry (kind != 0)
+ * with a non-zero end_bit.  BZH_E_DATA, naming the entry: no block magic at a kept entry's bit_pos.  Lost entries are otherwise
+ * ignored, and out_off / out_len / flags / err_bit of all.  No entry, whatever it holds, makes a kernel read outside in[0..n) or
+ * write outside the words of *out_len.  The gather is one launch for all blocks (recover.hip).
+ * Device variant: d_out must be 4-byte aligned (else BZH_E_ARG) and hold the stream's words, cap >= align4(*out_len), else
+ * BZH_E_CAP; the bytes between *out_len and align4(*out_len) are written as zero.  Host variant: cap >= *out_len. */
+BZH_API int bzh_recover_stream_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_recover_entry *ent, size_t count,
+                                      void *d_out, size_t cap, size_t *out_len);
+BZH_API int bzh_recover_stream(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_recover_entry *ent, size_t count,
+                               uint8_t *out, size_t cap, size_t *out_len);
+
 /* ---- random access: a verified block index, and the decode of a byte range of the output ---------- */
 
 /* One decoded block.  bzip2 blocks are independent once the bit they start at is known: the index records that bit for every
