@@ -40,7 +40,7 @@ import numpy as np
 
 from . import _native
 
-__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "build_index", "decompress_range", "BlockIndex",
+__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "BlockIndex",
            "IndexedReader", "build_sync_index", "SyncIndex", "encode_indexed", "recover", "recover_stream", "Recovered", "RecoveredBlock", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
@@ -311,7 +311,7 @@ def recover_stream(data, report=None, device=0):
 
 def decode(reader, writer, device=0):
     """Decode everything `reader` yields (one or more bzip2 streams) and write the bytes to `writer` -> bytes written.
-    This path reads the whole input first (the block boundaries of a stream are found by a scan of all of it)."""
+    This path reads the whole input first and writes nothing on damage; decode_stream reads and writes in chunks."""
     data = reader.getvalue()[reader.tell():] if isinstance(reader, io.BytesIO) else reader.read()
     if not isinstance(data, (bytes, bytearray, memoryview)):
         raise TypeError("reader.read() must return bytes")
@@ -322,6 +322,106 @@ def decode(reader, writer, device=0):
     if hasattr(writer, "flush"):
         writer.flush()
     return len(out)
+
+
+class StreamDecompressor:
+    """Incremental decode of one or more bzip2 streams fed in chunks of any size (bzh_dstream_*), in the shape of
+    bz2.BZ2Decompressor: bounded memory whatever the input's size.  window / staging: the targets of the compressed window and
+    of the decoded staging buffer on the device, in bytes (None: the library's defaults).  It has a context of its own.
+
+    A damaged input raises BzhError from the call whose pass finds the defect; what earlier calls returned is a prefix of the
+    true output made of whole, CRC-verified blocks, and the object is then closed (any later call raises BzhError -5)."""
+
+    OUT_CHUNK = 4 << 20
+
+    def __init__(self, device=0, window=None, staging=None):
+        self._ctx = _native.Context(device, 9, 0)
+        self._ctx.dstream_set_room(window or 0, staging or 0)
+        self._ctx.dstream_begin()
+        self._pending = b""
+        self._more_out = False
+        self._buf = np.empty(self.OUT_CHUNK, dtype=np.uint8)
+        self.done = False
+
+    @property
+    def needs_input(self):
+        """False while decompress(b"", n) can still return bytes without new input, and once the input is finished"""
+        return not (self.done or self._pending or self._more_out)
+
+    @property
+    def consumed(self):
+        """input bytes up to the end of the last stream passed (bzh_decode's consumed)"""
+        return self._consumed if self._ctx is None else self._ctx.dstream_consumed()
+
+    def stats(self):
+        """bzh_dstream_stats as a dict"""
+        return self._ctx.dstream_stats()
+
+    def close(self):
+        """Frees the context (the window, the staging buffer, the batch workspace); idempotent"""
+        if self._ctx is not None:
+            self._consumed = self._ctx.dstream_consumed()
+            self._ctx.close()
+            self._ctx = None
+            self._pending = b""
+            self._more_out = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _run(self, eof, max_length):
+        parts, total = [], 0
+        while not self.done:
+            room = self._buf.size if max_length < 0 else min(self._buf.size, max_length - total)
+            if room == 0:
+                break
+            out = self._buf[:room]
+            used, got, self.done = self._ctx.dstream_feed(self._pending, eof, out)
+            self._pending = self._pending[used:]
+            parts.append(out[:got].tobytes())
+            total += got
+            self._more_out = got == room and not self.done
+            if not self._pending and got < room and not eof:
+                break
+        return b"".join(parts)
+
+    def decompress(self, data, max_length=-1):
+        """Feed `data` (bytes-like) -> the decoded bytes that are ready, at most max_length of them when it is >= 0; input not yet
+        taken is kept for the next call (needs_input is then False).  After `done`, data is ignored."""
+        view = _bytes_view(data, "StreamDecompressor.decompress")
+        self._pending = self._pending + view.tobytes() if self._pending else view.tobytes()
+        return self._run(False, max_length)
+
+    def finish(self, max_length=-1):
+        """The input has ended: the remaining bytes, at most max_length of them; call until `done`.  A truncated input raises."""
+        return self._run(True, max_length)
+
+
+def decode_stream(reader, writer, chunk=8 << 20, device=0):
+    """Decode everything `reader` yields (one or more bzip2 streams), reading `chunk` bytes at a time and writing the decoded bytes
+    as they arrive -> bytes written.  Memory is bounded whatever the sizes (StreamDecompressor).  Unlike decode(), which writes
+    nothing on damage, the bytes in front of a defect that earlier passes verified have been written when BzhError is raised."""
+    written = 0
+    with StreamDecompressor(device) as d:
+        while not d.done:
+            data = reader.read(chunk)
+            if not isinstance(data, (bytes, bytearray, memoryview)):
+                raise TypeError("reader.read() must return bytes")
+            if not data:
+                break
+            out = d.decompress(data)
+            written += len(out)
+            writer.write(out)
+        while not d.done:
+            out = d.finish()
+            written += len(out)
+            writer.write(out)
+    if hasattr(writer, "flush"):
+        writer.flush()
+    return written
 
 
 def _bytes_view(data, who):

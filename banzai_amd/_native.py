@@ -100,6 +100,15 @@ class RecoverStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DStreamStats(ctypes.Structure):
+    """bzh_dstream_stats"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("passes", "blocks", "streams", "blocks_redone", "tail_moves", "window_grows",
+                                               "staging_grows", "in_bytes", "out_bytes", "window_peak", "staging_peak")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class SyncPoint(ctypes.Structure):
     """bzh_sync_point: the entropy stage's state at a group boundary inside a block"""
     _fields_ = [("bit_pos", ctypes.c_uint64), ("entry", ctypes.c_uint32), ("group", ctypes.c_uint32), ("out_pos", ctypes.c_uint32),
@@ -186,6 +195,13 @@ SIGNATURES = {
     "bzh_stream_bound": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_size_t]),
     "bzh_stream_set_chunk": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),
     "bzh_stream_consumed": (ctypes.c_size_t, [ctypes.c_void_p]),
+    "bzh_dstream_set_room": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t]),
+    "bzh_dstream_begin": (ctypes.c_int, [ctypes.c_void_p]),
+    "bzh_dstream_feed": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, szp, u8p, ctypes.c_size_t, szp,
+                                        ctypes.POINTER(ctypes.c_int)]),
+    "bzh_dstream_consumed": (ctypes.c_size_t, [ctypes.c_void_p]),
+    "bzh_dstream_get_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DStreamStats)]),
+    "bzh_dstream_end": (ctypes.c_int, [ctypes.c_void_p]),
     "bzh_plan_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, szp]),
     "bzh_plan_tables_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
     "bzh_plan_split_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, szp]),
@@ -959,6 +975,41 @@ class Context:
 
     def stream_consumed(self):
         return int(lib().bzh_stream_consumed(self._h))
+
+    # ---- streaming decode (bzh_dstream_*) ----
+    def dstream_set_room(self, window=0, staging=0):
+        """targets of the window and the staging buffer for the next dstream_begin (0: the library's default)"""
+        self.check(lib().bzh_dstream_set_room(self._h, window, staging))
+
+    def dstream_begin(self):
+        self.check(lib().bzh_dstream_begin(self._h))
+
+    def dstream_feed_raw(self, data, eof, out):
+        """one bzh_dstream_feed call: `data` bytes-like, `out` a uint8 array whose size is the call's cap ->
+        (status, input bytes used, bytes written to out, done); nothing is raised"""
+        a = np.frombuffer(data, dtype=np.uint8)
+        n = a.size
+        used, got, done = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_int(0)
+        st = lib().bzh_dstream_feed(self._h, ptr(np.ascontiguousarray(a)) if n else None, n, 1 if eof else 0, ctypes.byref(used),
+                                    ptr(out) if out.size else None, out.size, ctypes.byref(got), ctypes.byref(done))
+        return st, int(used.value), int(got.value), bool(done.value)
+
+    def dstream_feed(self, data, eof, out):
+        """bzh_dstream_feed -> (input bytes used, bytes written to out, done)"""
+        st, used, got, done = self.dstream_feed_raw(data, eof, out)
+        self.check(st)
+        return used, got, done
+
+    def dstream_consumed(self):
+        return int(lib().bzh_dstream_consumed(self._h))
+
+    def dstream_stats(self):
+        st = DStreamStats()
+        self.check(lib().bzh_dstream_get_stats(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
+    def dstream_end(self):
+        self.check(lib().bzh_dstream_end(self._h))
 
 
 class MultiContext:

@@ -244,6 +244,7 @@ extern "C" void bzh_destroy(bzh_ctx *ctx)
         delete l;
     }
     if (ctx->strm.copy_stream) hipStreamDestroy(ctx->strm.copy_stream);
+    dstream_free(ctx);
     delete ctx; // (its buffers with it: GrowBuf, common.h)
 }
 
@@ -1380,6 +1381,63 @@ extern "C" int bzh_decode(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *ou
     if (rc != BZH_OK) return rc;
     if (len) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, len, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+    return BZH_OK;
+    });
+}
+
+// ---- streaming decode (decode.hip's dstream_*; the walk and the feed loop: decode_stream_plan.h) ----
+static int dstream_arena(bzh_ctx *ctx, uint32_t blocks) { return ensure_arena(ctx, blocks); }
+
+extern "C" int bzh_dstream_set_room(bzh_ctx *ctx, size_t window_bytes, size_t staging_bytes)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (!ctx) return BZH_E_ARG;
+    if ((window_bytes && window_bytes < 1024) || (staging_bytes && staging_bytes < 1024)) {
+        bzh_set_error(ctx, "dstream: a room of %zu / %zu bytes, below 1024", window_bytes, staging_bytes);
+        return BZH_E_ARG;
+    }
+    ctx->dstrm_window = window_bytes;
+    ctx->dstrm_staging = staging_bytes;
+    return BZH_OK;
+    });
+}
+
+extern "C" int bzh_dstream_begin(bzh_ctx *ctx)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (!ctx) return BZH_E_ARG;
+    stream_join(ctx);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return dstream_begin(ctx);
+    });
+}
+
+extern "C" int bzh_dstream_feed(bzh_ctx *ctx, const uint8_t *in, size_t n, int eof, size_t *in_used, uint8_t *out, size_t cap, size_t *out_len,
+                                int *done)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (!ctx || (!in && n) || (!out && cap) || !in_used || !out_len || !done) return BZH_E_ARG;
+    stream_join(ctx);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return dstream_feed(ctx, dstream_arena, in, n, eof, in_used, out, cap, out_len, done);
+    });
+}
+
+extern "C" size_t bzh_dstream_consumed(const bzh_ctx *ctx) { return ctx ? dstream_consumed(ctx) : 0; }
+
+extern "C" int bzh_dstream_get_stats(const bzh_ctx *ctx, bzh_dstream_stats *out)
+{
+    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
+    if (!ctx || !out) return BZH_E_ARG;
+    return dstream_stats(ctx, out);
+    });
+}
+
+extern "C" int bzh_dstream_end(bzh_ctx *ctx)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (!ctx) return BZH_E_ARG;
+    dstream_end(ctx);
     return BZH_OK;
     });
 }

@@ -42,6 +42,7 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "     --output <path.bz2>    write the stream to this file\n"
             "     --stdout    or   -c    write the stream to standard out\n"
             "     --decompress or  -d    decode <input_path> (one or more .bz2 streams) instead\n"
+            "     --stream               with -d: decode in fixed-size buffers, writing as bytes arrive\n"
             "     --recover              decode every block of a damaged <input_path> that still verifies\n"
             "     --keep      or   -k    keep the input file\n"
             "     --remove    or   -r    remove the input file\n\n"
@@ -59,7 +60,11 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "     that suffix, and the same keep / remove policy applies.  --recover takes the paths of\n"
             "     --decompress, writes the bytes of the intact blocks, names every lost block on standard\n"
             "     error (bit position, reason) and exits with 0 when nothing was lost, with 4 (salvage\n"
-            "     written, blocks lost: the input is then kept) otherwise; it takes no level and no -d.  GPU: $BZHIP_DEVICE (default 0), or\n"
+            "     written, blocks lost: the input is then kept) otherwise; it takes no level and no -d.\n"
+            "     -d --stream takes the paths and the keep / remove policy of -d and bounded memory whatever\n"
+            "     the sizes: a pipe is decoded as it arrives.  On a damaged input the exit status is -d's\n"
+            "     and a partial output FILE is removed; on standard out the bytes decoded so far -- whole\n"
+            "     blocks in front of the defect, their CRCs verified -- have been written.  GPU: $BZHIP_DEVICE (default 0), or\n"
             "     $BZHIP_DEVICES=0,1,2,... to spread the blocks over several GPUs of this node;\n"
             "     BZHIP_HUFFMAN=fixed: 2-6 Huffman tables with refinement (smaller, not banzai's exact bytes).\n\n%s\n",
             VERSION);
@@ -75,7 +80,7 @@ int main(int argc, char **argv)
     std::string in_path, out_path;
     bool have_in = false, in_stdin = false, out_stdout = false, have_out = false;
     int keep = -1, level = 9;
-    bool decompress = false, recover = false, level_given = false;
+    bool decompress = false, recover = false, level_given = false, dstream = false;
     auto set_input = [&](const std::string &p, bool is_stdin) {
         if (have_in) die(ERR_ARGS, "Only one input may be specified");
         have_in = true;
@@ -105,6 +110,7 @@ int main(int argc, char **argv)
             else if (a == "--verbose") {}
             else if (a == "--decompress") decompress = true;
             else if (a == "--recover") recover = true;
+            else if (a == "--stream") dstream = true;
             else if (a == "--keep") keep = 1;
             else if (a == "--remove") keep = 0;
             else if (a == "--fast") level = 1, level_given = true;
@@ -134,12 +140,14 @@ int main(int argc, char **argv)
     }
     if (!have_in) die(ERR_ARGS, "An input must be specified");
     if (recover && decompress) die(ERR_ARGS, "'--recover' and '--decompress' exclude each other");
+    if (dstream && recover) die(ERR_ARGS, "'--stream' and '--recover' exclude each other");
+    if (dstream && !decompress) die(ERR_ARGS, "'--stream' goes with '--decompress'");
     if (recover && level_given) die(ERR_ARGS, "'--recover' takes no block size: a block is held to what the format allows");
 
     FILE *inf = in_stdin ? stdin : fopen(in_path.c_str(), "rb");
     if (!inf) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + in_path + ": " + strerror(errno));
 
-    if (decompress || recover) { // the whole input in memory, a level-9 context, one call (more where a size guess was short)
+    if (decompress || recover) { // the whole input in memory, a level-9 context, one call (more where a size guess was short); --stream: neither
         const char *doing = recover ? "error during recovery: " : "error during decompression: ";
         std::string dpath = out_path;
         if (!have_out && !in_stdin) {
@@ -147,6 +155,65 @@ int main(int argc, char **argv)
                 die(ERR_ARGS, std::string("With ") + (recover ? "--recover" : "--decompress") +
                                   " the input path must end in '.bz2' unless --output or --stdout is given");
             dpath = in_path.substr(0, in_path.size() - 4);
+        }
+        if (dstream) { // bzh_dstream_feed through two fixed buffers: 8 MiB reads, 16 MiB writes
+            const bool to_file = !(have_out && out_stdout) && !(in_stdin && !have_out);
+            const char *sv = getenv("BZHIP_DEVICE");
+            bzh_ctx *sctx = nullptr;
+            int ss = bzh_create(&sctx, sv ? atoi(sv) : 0, 9, 0);
+            if (ss != BZH_OK) die(ERR_OUTPUT, std::string(doing) + bzh_strerror(ss));
+            FILE *sf = stdout;
+            auto sfail = [&](const std::string &what) { // no partial output file is left behind
+                const std::string msg = std::string(doing) + what;
+                bzh_destroy(sctx);
+                if (sf != stdout) {
+                    fclose(sf);
+                    remove(dpath.c_str());
+                }
+                die(ERR_OUTPUT, msg);
+            };
+            ss = bzh_dstream_begin(sctx);
+            if (ss != BZH_OK) sfail(std::string(bzh_strerror(ss)) + ": " + bzh_last_error(sctx));
+            if (to_file) {
+                sf = fopen(dpath.c_str(), "wb");
+                if (!sf) {
+                    bzh_destroy(sctx);
+                    die(ERR_FILESYSTEM, "[filesystem error] cannot create " + dpath + ": " + strerror(errno));
+                }
+            }
+            const size_t IN_CHUNK = (size_t)8 << 20, OUT_CHUNK = (size_t)16 << 20;
+            std::unique_ptr<uint8_t[]> ibuf(new uint8_t[IN_CHUNK]), obuf(new uint8_t[OUT_CHUNK]);
+            int done = 0;
+            for (bool eof = false; !done;) {
+                size_t k = 0;
+                if (!eof) {
+                    k = fread(ibuf.get(), 1, IN_CHUNK, inf);
+                    if (k < IN_CHUNK) {
+                        if (ferror(inf)) sfail("read failed");
+                        eof = true;
+                    }
+                }
+                for (size_t off = 0;;) { // until the chunk is used and nothing more comes out
+                    size_t used = 0, got = 0;
+                    ss = bzh_dstream_feed(sctx, ibuf.get() + off, k - off, eof ? 1 : 0, &used, obuf.get(), OUT_CHUNK, &got, &done);
+                    if (ss != BZH_OK) sfail(std::string(bzh_strerror(ss)) + ": " + bzh_last_error(sctx));
+                    if (got && fwrite(obuf.get(), 1, got, sf) != got) sfail("write failed");
+                    off += used;
+                    if (done || (off == k && got < OUT_CHUNK && !eof)) break;
+                }
+            }
+            bzh_destroy(sctx);
+            sctx = nullptr;
+            if (!in_stdin) fclose(inf);
+            if (fflush(sf) != 0) {
+                if (sf != stdout) fclose(sf), remove(dpath.c_str());
+                die(ERR_OUTPUT, std::string(doing) + "write failed");
+            }
+            if (sf != stdout) fclose(sf);
+            const bool keep_in = keep >= 0 ? keep == 1 : have_out; // bnz/src/main.rs:292-300
+            if (!keep_in && !in_stdin && remove(in_path.c_str()) != 0)
+                die(ERR_OUTPUT, "error deleting input file: " + std::string(strerror(errno)));
+            return SUCCESS;
         }
         std::vector<uint8_t> data;
         {

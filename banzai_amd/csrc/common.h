@@ -180,6 +180,8 @@ struct bzh_ctx {
     bzh_decode_stats dstats{};
     bzh_decode_many_stats mstats{}; // of the last bzh_decode_many* call
     bzh_recover_stats rstats{};     // of the last bzh_recover* call
+    struct DStream *dstrm = nullptr; // streaming decode (bzh_dstream_*, decode.hip): made by the first begin, freed by dstream_free
+    size_t dstrm_window = 0, dstrm_staging = 0; // bzh_dstream_set_room: targets of the next begin (0: the defaults)
     // streaming encode (bzh_stream_*)
     struct Stream {
         bool active = false, header_done = false;
@@ -543,6 +545,15 @@ int decode_many_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const size_t *i
 int decode_recover_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t cap, size_t *out_len,
                        std::vector<bzh_recover_entry> &entries, bzh_recover_stats &stats, const std::vector<uint64_t> &cands);
 int decode_magic_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const uint64_t *pos, size_t count, size_t *first_bad);
+// decode.hip: the streaming decode (the walk and the feed loop: decode_stream_plan.h).  arena: api.hip's ensure_arena, called by
+// every pass for the candidates it takes.  The pointers have been checked.
+int dstream_begin(bzh_ctx *ctx);
+int dstream_feed(bzh_ctx *ctx, int (*arena)(bzh_ctx *, uint32_t), const uint8_t *in, size_t n, int eof, size_t *in_used, uint8_t *out, size_t cap,
+                 size_t *out_len, int *done);
+size_t dstream_consumed(const bzh_ctx *ctx);
+int dstream_stats(const bzh_ctx *ctx, bzh_dstream_stats *out);
+void dstream_end(bzh_ctx *ctx);  // abandon: the buffers stay for the next begin
+void dstream_free(bzh_ctx *ctx); // bzh_destroy
 // recover.hip: the bits of the kept blocks, end to end from bit 32 of d_out, in one launch (the per-word rule: recover_gather.h)
 struct BzrDesc;
 int recover_gather_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const std::vector<BzrDesc> &descs, uint64_t body, uint32_t *d_out);

@@ -23,6 +23,7 @@
 #include "decode_plan.h"
 #include "decode_many_plan.h"
 #include "decode_recover_plan.h"
+#include "decode_stream_plan.h"
 
 // ---- scan ------------------------------------------------------------------------------------------------------
 // 16 start bytes a lane, all 8 shifts of each against both 48-bit magics.  Hits are rare: an atomic append (the host sorts).
@@ -1028,6 +1029,190 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
         return BZH_E_CAP;
     }
     return BZH_OK;
+}
+
+// ================================================================================================================
+// Streaming decode (bzh_dstream_*): decode_chain_run's walk over a sliding window of the input.  The walk and the feed loop are
+// decode_stream_plan.h's; this is its device: the window (two buffers -- the tail of a pass is copied from one to the front of
+// the other, so no copy overlaps), the staging buffer, the scan of the appended bytes, and a pass's batch through the entropy
+// stage and the back of the decoder.  No kernel of its own.  The buffers are the stream's, so between two feeds every other
+// entry point may use the context; what a pass borrows of the context (decode tables, hit list, arena) it asks for anew.
+// ================================================================================================================
+static_assert(BZS_OK == BZH_OK && BZS_E_ARG == BZH_E_ARG && BZS_E_STATE == BZH_E_STATE && BZS_E_DATA == BZH_E_DATA,
+              "decode_stream_plan.h names bzh_status values");
+static_assert(sizeof(BzsStats) >= sizeof(bzh_dstream_stats) && offsetof(BzsStats, staging_peak) == offsetof(bzh_dstream_stats, staging_peak),
+              "BzsStats begins with the fields of bzh_dstream_stats");
+constexpr size_t DSTREAM_WINDOW = (size_t)32 << 20, DSTREAM_STAGING = (size_t)128 << 20; // the defaults bzhip.h documents
+constexpr size_t DSTREAM_PAD = 16;
+
+struct DStreamDev {
+    bzh_ctx *ctx = nullptr;
+    int (*arena)(bzh_ctx *, uint32_t) = nullptr;
+    DevBuf win[2], staging;
+    int cur = 0;
+    uint64_t room = 0; // bytes the window is to hold
+    DecWs w;
+    Back bk;
+    std::vector<uint64_t> found;
+    std::vector<BackBlock> bb;
+
+    uint32_t max_batch() const { return ctx->max_batch; }
+    int win_reserve(uint64_t cap, uint64_t keep)
+    {
+        room = cap;
+        if (win[cur].cap >= cap + DSTREAM_PAD) return BZH_OK;
+        BZH_TRY(win[1 - cur].reserve(ctx, cap + DSTREAM_PAD, "the stream's window"));
+        if (keep) HIP_TRY(ctx, hipMemcpyAsync(win[1 - cur], win[cur], keep, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+        cur = 1 - cur;
+        return BZH_OK;
+    }
+    int win_append(uint64_t at, const uint8_t *src, uint64_t n)
+    {
+        if (at + n > room) return BZH_E_STATE;
+        HIP_TRY(ctx, hipMemcpyAsync(win[cur] + at, src, n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, bzh_stream_wait(ctx->stream)); // (the caller's bytes are his again when the call returns)
+        return BZH_OK;
+    }
+    int win_move(uint64_t from, uint64_t len)
+    {
+        if (from + len > room) return BZH_E_STATE;
+        BZH_TRY(win[1 - cur].reserve(ctx, room + DSTREAM_PAD, "the stream's window"));
+        HIP_TRY(ctx, hipMemcpyAsync(win[1 - cur], win[cur] + from, len, hipMemcpyDeviceToDevice, ctx->stream));
+        cur = 1 - cur;
+        return BZH_OK;
+    }
+    int scan(uint64_t from, uint64_t to, std::vector<uint64_t> &hits)
+    {
+        hits.clear();
+        if (to > room || from > to) return BZH_E_STATE;
+        BZH_TRY(decode_scan_run(ctx, win[cur] + from, to - from, found));
+        for (uint64_t h : found) hits.push_back(h + (16 * from)); // (bit << 1: 8 * from bits)
+        return BZH_OK;
+    }
+    int entropy(const uint64_t *cands, uint32_t B, uint64_t held, BzdResult *res)
+    {
+        hipStream_t st = ctx->stream;
+        if (held > room || B == 0 || B > ctx->max_batch) return BZH_E_STATE;
+        if (ctx->profiling) ctx->evnext = 0; // (the back's stage clock takes events of the pool; nobody reads them here)
+        BZH_TRY(arena(ctx, B));
+        if (B > ctx->arena_blocks) return BZH_E_STATE;
+        BZH_TRY(dec_ws(ctx, w));
+        if (w.T > UR_THREADS) {
+            bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
+            return BZH_E_STATE;
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(w.cand, cands, (size_t)B * 8, hipMemcpyHostToDevice, st));
+        decode_block_kernel<<<dim3(B), 64, 0, st>>>(win[cur], held, w.cand, ctx->bt, w.res, 100000u * (uint32_t)ctx->level);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(res, w.res, (size_t)B * sizeof(BzdResult), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, bzh_stream_wait(st));
+        return BZH_OK;
+    }
+    int sizes(std::vector<BzsBlock> &blocks, uint32_t Bu, uint32_t nmax_all)
+    {
+        StageClock clock{ctx, {}};
+        bb.clear();
+        for (const BzsBlock &b : blocks) bb.push_back(BackBlock{b.slot, b.nblock, 0, false, 0, 0, 0, 0});
+        BZH_TRY(back_sizes(ctx, w, clock, bk, Bu, nmax_all, bb));
+        for (size_t q = 0; q < blocks.size(); q++) {
+            blocks[q].size = bb[q].size;
+            blocks[q].bad_end = bb[q].bad_end;
+        }
+        return BZH_OK;
+    }
+    int stage_reserve(uint64_t cap) { return staging.reserve(ctx, cap + DSTREAM_PAD, "the stream's staging buffer"); }
+    int emit(std::vector<BzsBlock> &blocks, size_t taken)
+    {
+        StageClock clock{ctx, {}};
+        bb.resize(taken);
+        uint64_t end = 0;
+        for (size_t q = 0; q < taken; q++) {
+            bb[q].base = (int64_t)blocks[q].base;
+            bb[q].lo = 0;
+            bb[q].hi = (uint32_t)bb[q].size;
+            end = std::max(end, blocks[q].base + bb[q].size);
+        }
+        if (end + DSTREAM_PAD > staging.cap) return BZH_E_STATE;
+        BZH_TRY(back_emit(ctx, w, clock, bk, staging, true, bb, true));
+        for (size_t q = 0; q < taken; q++) blocks[q].crc = bb[q].crc;
+        return BZH_OK;
+    }
+    int handout(uint64_t off, uint8_t *out, uint64_t n)
+    {
+        if (off + n + DSTREAM_PAD > staging.cap) return BZH_E_STATE;
+        HIP_TRY(ctx, hipMemcpy(out, staging + off, n, hipMemcpyDeviceToHost));
+        return BZH_OK;
+    }
+};
+
+struct DStream {
+    DStreamDev dev;
+    BzsStream<DStreamDev> walk;
+};
+
+int dstream_begin(bzh_ctx *ctx)
+{
+    if (!ctx->dstrm) ctx->dstrm = new DStream();
+    DStream &d = *ctx->dstrm;
+    d.dev.ctx = ctx;
+    const int rc = d.walk.begin(&d.dev, ctx->level, ctx->dstrm_window ? ctx->dstrm_window : DSTREAM_WINDOW,
+                                ctx->dstrm_staging ? ctx->dstrm_staging : DSTREAM_STAGING);
+    if (rc != BZH_OK) d.walk.open = false;
+    return rc;
+}
+
+int dstream_feed(bzh_ctx *ctx, int (*arena)(bzh_ctx *, uint32_t), const uint8_t *in, size_t n, int eof, size_t *in_used, uint8_t *out, size_t cap,
+                 size_t *out_len, int *done)
+{
+    *in_used = *out_len = 0;
+    *done = 0;
+    if (!ctx->dstrm || !ctx->dstrm->walk.open) {
+        bzh_set_error(ctx, "dstream: no stream is open (no begin, or the stream has ended in an error)");
+        return BZH_E_STATE;
+    }
+    DStream &d = *ctx->dstrm;
+    d.dev.arena = arena;
+    uint64_t used = 0, got = 0;
+    bool fin = false;
+    const int rc = d.walk.feed(in, n, eof != 0, &used, out, cap, &got, &fin);
+    *in_used = (size_t)used;
+    *out_len = (size_t)got;
+    *done = fin ? 1 : 0;
+    if (rc == BZH_OK) return rc;
+    if (d.walk.open) { // a failure of the device, which has left its own text: the stream is closed all the same
+        d.walk.open = false;
+        return rc;
+    }
+    const BzsError &e = d.walk.err;
+    if (rc == BZH_E_ARG)
+        bzh_set_error(ctx, "decode: stream %zu is of level %u, the context of level %d", e.stream, e.level, ctx->level);
+    else if (rc == BZH_E_DATA)
+        bzh_set_error(ctx, "decode: %s%s%s in stream %zu, block %zu, at bit %llu", kind_name(e.kind), e.what ? ": " : "", e.what ? e.what : "",
+                      e.stream, e.block, (unsigned long long)e.bit);
+    else
+        bzh_set_error(ctx, "dstream: %s", e.what ? e.what : "internal error");
+    return rc;
+}
+
+size_t dstream_consumed(const bzh_ctx *ctx) { return ctx->dstrm ? (size_t)ctx->dstrm->walk.consumed : 0; }
+
+int dstream_stats(const bzh_ctx *ctx, bzh_dstream_stats *out)
+{
+    memset(out, 0, sizeof *out);
+    if (ctx->dstrm) memcpy(out, &ctx->dstrm->walk.st, sizeof *out);
+    return BZH_OK;
+}
+
+void dstream_end(bzh_ctx *ctx)
+{
+    if (ctx->dstrm) ctx->dstrm->walk.open = false;
+}
+
+void dstream_free(bzh_ctx *ctx)
+{
+    delete ctx->dstrm;
+    ctx->dstrm = nullptr;
 }
 
 // ================================================================================================================

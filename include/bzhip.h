@@ -473,6 +473,71 @@ BZH_API int bzh_stream_set_chunk(bzh_ctx *ctx, size_t bytes);
 /* Input bytes encoded so far (after the eof feed: the total, encode()'s return value). */
 BZH_API size_t bzh_stream_consumed(const bzh_ctx *ctx);
 
+/* ---- streaming decode: bzh_decode fed in chunks, bounded memory ------------------------------------------------ */
+
+/* A stream decode holds a WINDOW of compressed bytes and a STAGING buffer of decoded bytes on the device, both its own (not
+ * views of the decode workspace).  A PASS decodes what the window holds as far as it can be decided -- whole blocks, as many as
+ * the staging buffer takes --, releases the input in front of the first item it could not decide and moves the rest to the
+ * front of the window.  Only the bytes appended since the last pass are scanned for magics (from 6 bytes before them).
+ * Memory: on the input side max(window target, the largest block the parser accepts: 4.1 MB) -- twice that while the tail is
+ * moved, which goes from one buffer to another --, on the output side max(staging target, one block's decoded bytes: an RLE1
+ * block of 900 kB can expand 51-fold), plus the batch workspace bzh_decode uses for as many candidates as the window holds.
+ * The window grows, by what the call in hand still holds, only when it is full and its first item is still undecided; the
+ * staging buffer grows only to a block that exceeds it.
+ *
+ * EQUIVALENCE.  For every split of an input into feeds and every sequence of cap values, the concatenated output is bzh_decode's
+ * of the whole input, bzh_dstream_consumed its *consumed, the final status its status (BZH_E_ARG for a stream above the context's
+ * level), and for an input with one defect bzh_last_error names the same kind, stream, block and absolute bit.  (With several
+ * defects the one bzh_decode names depends on its batches; only the status is the same.)
+ *
+ * ERRORS.  The pass that finds a defect hands out nothing, the call returns the status, and the stream is closed: later feeds
+ * are BZH_E_STATE until the next begin.  What earlier passes handed out is a prefix of the true output made of whole blocks whose
+ * CRCs were verified; a STREAM CRC mismatch is found only at the stream's footer, after its blocks have gone out.  Unlike
+ * bzh_decode a stream decode is therefore not all or nothing.  After an error bzh_dstream_consumed is the end of the last
+ * footer the walk had passed up to the defect.
+ *
+ * Not here: a pass on an internal thread beside the caller's I/O (as bzh_stream_feed has), device-pointer variants, recovery
+ * and index building on a stream, the multi-device handle. */
+typedef struct {
+    uint64_t passes, blocks, streams;
+    uint64_t blocks_redone;   /* blocks whose entropy decode ran in more than one pass */
+    uint64_t tail_moves, window_grows, staging_grows;
+    uint64_t in_bytes, out_bytes;
+    uint64_t window_peak, staging_peak;   /* bytes */
+} bzh_dstream_stats;
+
+/* Targets of the window and the staging buffer for the next bzh_dstream_begin.  0 = the default: 32 MiB of window, 128 MiB of
+ * staging.  A non-zero value below 1024: BZH_E_ARG.  Small rooms mean many passes, and every pass costs at least one block's
+ * serial entropy decode. */
+BZH_API int bzh_dstream_set_room(bzh_ctx *ctx, size_t window_bytes, size_t staging_bytes);
+
+/* Starts a stream decode on the context (abandoning one that is open).  Joins a streaming encode pass in flight. */
+BZH_API int bzh_dstream_begin(bzh_ctx *ctx);
+
+/* zlib-shaped: any n, any cap, no bound function.  In a loop the call hands staged bytes to out, returns when out is full,
+ * copies input into the window while there is room (`in` may be reused on return), runs a pass when nothing is staged and the
+ * window is full or eof has taken effect, and returns when all of `in` is used and nothing more can be handed out.
+ * *in_used <= n: bytes of `in` taken; repeat the call with the rest when it is less.  eof != 0: `in` ends the input; it takes
+ * effect once all n bytes of that call are used, so repeat the call with the rest and with eof again.  *out_len <= cap.
+ * *done is set once the input is finished -- a footer followed by foreign bytes, or by the end of the input at eof -- and every
+ * byte has been handed out; feeds after that succeed, use all of `in` and ignore it.
+ * A call with n > 0 or pending output, and cap > 0, never returns BZH_OK having used no input, produced no output and not
+ * set *done.  Passes are synchronous inside the call; between calls the context is idle and every other entry point may be
+ * used on it (they do not disturb the stream).
+ * BZH_E_ARG: a null ctx, in with n > 0, out with cap > 0, in_used, out_len or done; a stream above the context's level.
+ * BZH_E_STATE: no begin, or the stream has ended in an error.  BZH_E_DATA as bzh_decode. */
+BZH_API int bzh_dstream_feed(bzh_ctx *ctx, const uint8_t *in, size_t n, int eof, size_t *in_used, uint8_t *out, size_t cap,
+                             size_t *out_len, int *done);
+
+/* bzh_decode's *consumed, absolute: the first byte behind the padding of the last footer passed (0 for a null ctx). */
+BZH_API size_t bzh_dstream_consumed(const bzh_ctx *ctx);
+
+/* Counters of the stream since its begin (zeros before the first).  window_peak / staging_peak: the largest rooms held. */
+BZH_API int bzh_dstream_get_stats(const bzh_ctx *ctx, bzh_dstream_stats *out);
+
+/* Abandons the stream; always allowed (also with none open).  The buffers stay with the context for the next begin. */
+BZH_API int bzh_dstream_end(bzh_ctx *ctx);
+
 /* ---- block-sharded path (one rank per GPU) -------------------------- */
 
 /* Split d_in[0..n) into blocks: the sequential part of the loop at lib/lib.rs:101-126, i.e.
