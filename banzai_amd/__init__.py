@@ -21,7 +21,8 @@ and random access into a .bz2 without decoding all of it (bzip2 blocks are indep
 
     build_index(data) -> BlockIndex                      (every block: where it starts, what it decodes to; verified)
     decompress_range(data, index, offset, length) -> bytes
-    IndexedReader(source, index=None)                    (read / seek over the decoded bytes of bytes or a file)
+    decompress_ranges(data, index, ranges) -> [bytes]    (many (offset, length) reads in one pass: every touched block once)
+    IndexedReader(source, index=None)                    (read / seek / readv over the decoded bytes of bytes or a file)
     build_sync_index(data, interval=256) -> SyncIndex    (a BlockIndex plus sync points inside the blocks: a read decodes
                                                           its blocks in parallel segments; accepted wherever a BlockIndex is)
     encode_indexed(reader, writer, level, interval=256)  (encode() that returns that index of the stream it writes: the
@@ -40,7 +41,7 @@ import numpy as np
 
 from . import _native
 
-__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "BlockIndex",
+__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex",
            "IndexedReader", "build_sync_index", "SyncIndex", "encode_indexed", "recover", "recover_stream", "Recovered", "RecoveredBlock", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
@@ -673,6 +674,76 @@ def decompress_range(data, index, offset, length, device=0):
     return _decode_range(_ctx(9, device), view[lo:hi], index, offset, length, lo)
 
 
+def _points_arg(index):
+    return index.points if isinstance(index, SyncIndex) else None
+
+
+def _split(blob, offs, lens):
+    return [blob[o:o + n] for o, n in zip(offs, lens)]
+
+
+def decompress_ranges(data, index, ranges, device=0):
+    """decompress_range for many (offset, length) pairs in ONE call -> a list of bytes, one per range in the order given, each
+    clipped to the decoded size.  The ranges may overlap, repeat, be empty and come in any order; every block they touch is
+    decoded and verified once, all of them in shared batches, so many short reads cost about what one costs
+    (bzh_decode_ranges).  Of `data` the bytes from the first touched block to the last go to the device: for sparse reads over a
+    large archive use IndexedReader.readv, which hands over the touched blocks alone."""
+    view = _bytes_view(data, "decompress_ranges")
+    index = _index_arg(index)
+    r, _ = _native._ranges(ranges)
+    _, lo, hi, _ = _native.index_spans(index.entries, r)
+    blob, offs, lens = _ctx(9, device).decode_ranges(view[lo:hi], index.entries, r, _points_arg(index), in_byte_base=lo)
+    return _split(blob, offs, lens)
+
+
+_SubIndex = collections.namedtuple("_SubIndex", "touched entries points ranges runs")
+
+
+def _subindex(index, ranges):
+    """The index of the touched blocks alone, for compressed bytes that hold nothing else (host arithmetic over the arrays, no
+    device).  -> touched: the entries the ranges touch, ascending; runs: an (n, 2) array of the byte spans [lo, hi) of the
+    source to lay back to back, one per run of adjacent touched entries; entries: those of `touched`, bit positions rebased to
+    that buffer and out_off the running sum from 0; points: the sync points of those entries, renumbered and rebased the same
+    way (None for a BlockIndex); ranges: the ranges, clipped, in the sub-index's output coordinates -- the same bytes."""
+    e = index.entries
+    r, _ = _native._ranges(ranges)
+    touched, _, _, _ = _native.index_spans(e, r)
+    t = touched.astype(np.int64)
+    se = e[t].copy()
+    byte_lo, byte_hi = se["bit_pos"] // np.uint64(8), (se["end_bit"] + np.uint64(7)) // np.uint64(8)
+    first = np.ones(t.size, dtype=bool)  # of a run of adjacent entries
+    first[1:] = t[1:] != t[:-1] + 1
+    last = np.ones(t.size, dtype=bool)
+    last[:-1] = first[1:]
+    runs = np.stack([byte_lo[first], byte_hi[last]], axis=1) if t.size else np.zeros((0, 2), np.uint64)
+    run_base = np.concatenate([np.zeros(1, np.uint64), np.cumsum(runs[:, 1] - runs[:, 0], dtype=np.uint64)[:-1]])
+    # what an entry's bit positions lose: its run starts at run_base of the buffer, not at runs[., 0] of the source
+    shift = (np.uint64(8) * (runs[:, 0] - run_base))[np.cumsum(first) - 1] if t.size else np.zeros(0, np.uint64)
+    se["bit_pos"] -= shift
+    se["end_bit"] -= shift
+    old_off = se["out_off"].copy()
+    se["out_off"] = np.concatenate([np.zeros(1, np.uint64), np.cumsum(se["out_len"][:-1], dtype=np.uint64)])
+    # a range's entries are adjacent in both indexes, so it moves as its first entry moves
+    total = np.uint64(index.size)
+    off = np.minimum(r["off"], total)
+    length = np.minimum(r["len"], total - off)
+    sub = np.zeros(r.size, dtype=_native.RANGE_DTYPE)
+    live = length > 0
+    if t.size:
+        ends = e["out_off"] + e["out_len"].astype(np.uint64)
+        j = np.searchsorted(t, np.searchsorted(ends, off[live], side="right"))  # the touched number of the range's first entry
+        sub["off"][live] = off[live] - old_off[j] + se["out_off"][j]
+        sub["len"][live] = length[live]
+    points = None
+    if isinstance(index, SyncIndex):
+        p = index.points
+        points = p[np.isin(p["entry"], touched)].copy()
+        j = np.searchsorted(t, points["entry"])
+        points["entry"] = j
+        points["bit_pos"] -= shift[j]
+    return _SubIndex(touched, se, points, sub, runs)
+
+
 class IndexedReader(io.RawIOBase):
     """A seekable, read-only file of the DECODED bytes of `source`: bytes-like, or a seekable binary file holding .bz2
     stream(s).  Every read decodes just the blocks it touches (decompress_range); with a file source it fetches from the file
@@ -747,6 +818,26 @@ class IndexedReader(io.RawIOBase):
         out = _decode_range(_ctx(9, self._device), comp, self.index, self._pos, n, lo)
         self._pos += len(out)
         return out
+
+    def readv(self, ranges):
+        """The decoded bytes of many (offset, length) pairs in one call -> a list of bytes in the order given, each clipped to
+        the size; the position does not move.  Every touched block is decoded once (decompress_ranges), and of the source only
+        the touched blocks' compressed bytes are fetched and handed over: one seek and read per run of adjacent blocks."""
+        sub = _subindex(self.index, ranges)
+        parts = []
+        for lo, hi in sub.runs.tolist():
+            if self._file is not None:
+                self._file.seek(lo)
+                comp = self._file.read(hi - lo)
+                if not isinstance(comp, (bytes, bytearray, memoryview)):
+                    raise TypeError("source.read() must return bytes")
+                if len(comp) != hi - lo:
+                    raise EOFError(f"the source holds {len(comp)} of the {hi - lo} bytes from {lo} on that the index names")
+            else:
+                comp = self._view[lo:hi]
+            parts.append(comp)
+        blob, offs, lens = _ctx(9, self._device).decode_ranges(b"".join(parts), sub.entries, sub.ranges, sub.points)
+        return _split(blob, offs, lens)
 
     def read(self, n=-1):
         if n is None or n < 0:

@@ -121,6 +121,24 @@ assert SYNC_DTYPE.itemsize == ctypes.sizeof(SyncPoint) == 288
 syncp = ctypes.POINTER(SyncPoint)
 
 
+class Range(ctypes.Structure):
+    """bzh_range: output bytes [off, off + len)"""
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64)]
+
+
+RANGE_DTYPE = np.dtype([("off", "<u8"), ("len", "<u8")])
+assert RANGE_DTYPE.itemsize == ctypes.sizeof(Range) == 16
+rangep = ctypes.POINTER(Range)
+
+
+class DecodeRangesStats(ctypes.Structure):
+    """bzh_decode_ranges_stats"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("ranges", "pieces", "blocks_touched", "blocks_whole", "batches")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class KStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("ms", ctypes.c_double), ("launches", ctypes.c_uint64),
                 ("alg_bytes", ctypes.c_uint64)]
@@ -189,6 +207,13 @@ SIGNATURES = {
     "bzh_decode_range_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, idxp,
                                                ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
                                                ctypes.c_size_t, szp]),
+    "bzh_index_spans": (ctypes.c_int, [idxp, ctypes.c_size_t, rangep, ctypes.c_size_t, u32p, ctypes.c_size_t, szp, u64p, u64p, u64p]),
+    "bzh_decode_ranges": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64, idxp, ctypes.c_size_t, syncp,
+                                         ctypes.c_size_t, rangep, ctypes.c_size_t, u8p, ctypes.c_size_t, szp, szp, szp]),
+    "bzh_decode_ranges_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, idxp,
+                                                ctypes.c_size_t, syncp, ctypes.c_size_t, rangep, ctypes.c_size_t, ctypes.c_void_p,
+                                                ctypes.c_size_t, szp, szp, szp]),
+    "bzh_get_decode_ranges_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DecodeRangesStats)]),
     "bzh_decode_scan": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u64p, u8p, ctypes.c_size_t, szp]),
     "bzh_stream_begin": (ctypes.c_int, [ctypes.c_void_p]),
     "bzh_stream_feed": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, u8p, ctypes.c_size_t, szp]),
@@ -302,6 +327,39 @@ def index_span(entries, off, length):
     if st != 0:
         raise BzhError(st, lib().bzh_strerror(st).decode())
     return int(first.value), int(last.value), int(lo.value), int(hi.value)
+
+
+def _ranges(ranges):
+    """a contiguous array of the 16-byte ranges, from (off, len) pairs or such an array, and its ctypes pointer; len saturates
+    at 2^64 - 1"""
+    if isinstance(ranges, np.ndarray) and ranges.dtype == RANGE_DTYPE:
+        r = np.ascontiguousarray(ranges)
+    else:
+        pairs = list(ranges)
+        r = np.empty(len(pairs), dtype=RANGE_DTYPE)
+        for k, pair in enumerate(pairs):
+            off, length = pair
+            for v in (off, length):
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                    raise TypeError(f"a range is a pair of ints, not {type(v).__name__}")
+            if off < 0 or length < 0:
+                raise ValueError("offset and length must not be negative")
+            r[k] = (min(int(off), 2**64 - 1), min(int(length), 2**64 - 1))
+    return r, (r.ctypes.data_as(rangep) if r.size else None)
+
+
+def index_spans(entries, ranges):
+    """bzh_index_spans (host arithmetic, no GPU): (touched, byte_lo, byte_hi, out_total) -- the entries the ranges touch,
+    ascending and unique, as a uint32 array; the hull of their bytes in the indexed input; the bytes the ranges hold"""
+    e, p = _entries(entries)
+    r, rp = _ranges(ranges)
+    cnt, lo, hi, total = ctypes.c_size_t(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    touched = np.empty(max(int(e.size), 1), dtype=np.uint32)  # (the list is unique: never more than the entries)
+    st = lib().bzh_index_spans(p, e.size, rp, r.size, ptr(touched, u32p), e.size, ctypes.byref(cnt), ctypes.byref(lo), ctypes.byref(hi),
+                               ctypes.byref(total))
+    if st != 0:
+        raise BzhError(st, lib().bzh_strerror(st).decode())
+    return touched[:cnt.value].copy(), int(lo.value), int(hi.value), int(total.value)
 
 
 def lib():
@@ -812,6 +870,43 @@ class Context:
         self.check(lib().bzh_decode_range_sync_device(self._h, ctypes.c_void_p(d_in), n, in_byte_base, p, e.size, pp, q.size, off, length,
                                                       ctypes.c_void_p(d_out), cap, ctypes.byref(got)))
         return int(got.value)
+
+    def decode_ranges(self, comp, entries, ranges, points=None, in_byte_base=0):
+        """bzh_decode_ranges: the output bytes of every (off, len) of `ranges` in one call, every touched block decoded once ->
+        (bytes of all ranges back to back, their offsets in it, their lengths).  `comp` holds the compressed bytes from byte
+        `in_byte_base` of the indexed input on; `points`: sync points, or None"""
+        a = np.frombuffer(comp, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        e, p = _entries(entries)
+        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
+        r, rp = _ranges(ranges)
+        total = int(e["out_off"][-1]) + int(e["out_len"][-1]) if e.size else 0
+        off, ln = r["off"].astype(object), r["len"].astype(object)  # (Python ints: off + len does not wrap)
+        cap = sum(max(0, min(int(l), total - int(o))) for o, l in zip(off, ln))
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        offs, lens = np.zeros(max(r.size, 1), dtype=np.uintp), np.zeros(max(r.size, 1), dtype=np.uintp)
+        got = ctypes.c_size_t(0)
+        self.check(lib().bzh_decode_ranges(self._h, ptr(src), n, in_byte_base, p, e.size, pp, q.size, rp, r.size, ptr(out), cap,
+                                           ptr(offs, szp), ptr(lens, szp), ctypes.byref(got)))
+        return out[:got.value].tobytes(), [int(v) for v in offs[:r.size]], [int(v) for v in lens[:r.size]]
+
+    def decode_ranges_device(self, d_in, n, entries, ranges, d_out, cap, points=None, in_byte_base=0):
+        """bzh_decode_ranges_device on integer device addresses -> (status, out_total, offsets, lengths); the status is not
+        raised, so that a caller can look at the sizes a BZH_E_CAP leaves"""
+        e, p = _entries(entries)
+        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
+        r, rp = _ranges(ranges)
+        offs, lens = np.zeros(max(r.size, 1), dtype=np.uintp), np.zeros(max(r.size, 1), dtype=np.uintp)
+        got = ctypes.c_size_t(0)
+        st = lib().bzh_decode_ranges_device(self._h, ctypes.c_void_p(d_in), n, in_byte_base, p, e.size, pp, q.size, rp, r.size,
+                                            ctypes.c_void_p(d_out), cap, ptr(offs, szp), ptr(lens, szp), ctypes.byref(got))
+        return st, int(got.value), [int(v) for v in offs[:r.size]], [int(v) for v in lens[:r.size]]
+
+    def decode_ranges_stats(self):
+        s = DecodeRangesStats()
+        self.check(lib().bzh_get_decode_ranges_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
 
     def decode_stats(self):
         s = DecodeStats()

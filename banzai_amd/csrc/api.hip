@@ -15,6 +15,7 @@
 #include <thread>
 
 #include "common.h"
+#include "decode_plan.h"
 #include "decode_recover_plan.h"
 #include "encode_plan.h"
 #include "recover_gather.h"
@@ -1610,6 +1611,84 @@ extern "C" int bzh_decode_range_sync(bzh_ctx *ctx, const uint8_t *in, size_t n, 
                                      size_t cap, size_t *out_len)
 {
     return decode_range_impl(ctx, in, n, in_byte_base, idx, count, pts, npts, off, len, out, cap, out_len);
+}
+
+// ---- many ranges (decode.hip's decode_ranges_run; the arithmetic: decode_plan.h)
+extern "C" int bzh_decode_ranges_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                                        size_t count, const bzh_sync_point *pts, size_t npts, const bzh_range *ranges, size_t nranges,
+                                        void *d_out, size_t cap, size_t *out_offs, size_t *out_lens, size_t *out_total)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n) || (!d_out && cap) || (!idx && count) || (!pts && npts) || (!ranges && nranges) || (!out_offs && nranges) ||
+        (!out_lens && nranges) || !out_total)
+        return BZH_E_ARG;
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
+    memset(&ctx->qstats, 0, sizeof ctx->qstats);
+    // where the bytes go: arithmetic that stays inside the arrays whatever they hold, so it comes before the checks and holds on
+    // every error behind this line
+    std::vector<uint32_t> touched;
+    uint64_t lo = 0, hi = 0;
+    const uint64_t total = count <= 0xFFFFFFFFull ? bzp_spans(idx, count, ranges, nranges, out_offs, out_lens, touched, &lo, &hi)
+                                                  : bzp_spans(idx, 0, ranges, nranges, out_offs, out_lens, touched, &lo, &hi);
+    *out_total = (size_t)total;
+    if (count > 0xFFFFFFFFull) {
+        bzh_set_error(ctx, "decode ranges: an index of %zu entries, 2^32 or more", count);
+        return BZH_E_ARG;
+    }
+    BZH_TRY(decode_index_check(ctx, idx, count));
+    BZH_TRY(decode_sync_check(ctx, idx, count, pts, npts));
+    ctx->qstats.ranges = nranges;
+    ctx->qstats.blocks_touched = touched.size();
+    if (total > cap) {
+        bzh_set_error(ctx, "decode ranges: the ranges hold %llu bytes, the buffer %zu", (unsigned long long)total, cap);
+        return BZH_E_CAP;
+    }
+    BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(touched.size(), 1), ctx->max_batch)));
+    const int rc = decode_ranges_run(ctx, (const uint8_t *)d_in, n, in_byte_base, idx, count, pts, npts, ranges, nranges, out_offs, touched,
+                                     (uint8_t *)d_out, total);
+    return decode_call_end(ctx, call, rc);
+    });
+}
+
+extern "C" int bzh_decode_ranges(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                                 const bzh_sync_point *pts, size_t npts, const bzh_range *ranges, size_t nranges, uint8_t *out, size_t cap,
+                                 size_t *out_offs, size_t *out_lens, size_t *out_total)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n) || (!out && cap) || (!idx && count) || (!pts && npts) || (!ranges && nranges) || (!out_offs && nranges) ||
+        (!out_lens && nranges) || !out_total)
+        return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // only the hull goes up (a buffer that does not cover it goes up whole: the device call says what is missing)
+    uint64_t lo = 0, hi = 0, total = 0;
+    if (count <= 0xFFFFFFFFull) {
+        std::vector<uint32_t> touched;
+        total = bzp_spans(idx, count, ranges, nranges, nullptr, nullptr, touched, &lo, &hi);
+    }
+    const bool covered = lo <= hi && in_byte_base <= lo && hi - in_byte_base <= n;
+    const uint64_t base = covered ? lo : in_byte_base;
+    const size_t un = covered ? (size_t)(hi - lo) : n;
+    const size_t room = total <= cap ? (size_t)total : 0; // (too small: the device call sets the sizes and says so)
+    BZH_TRY(decode_stage(ctx, covered ? in + (lo - in_byte_base) : in, un, room));
+    const int rc = bzh_decode_ranges_device(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, ranges, nranges,
+                                            room ? ctx->d_stage_out : nullptr, room, out_offs, out_lens, out_total);
+    if (rc != BZH_OK) return rc;
+    if (*out_total) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, *out_total, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+    return BZH_OK;
+    });
+}
+
+extern "C" int bzh_get_decode_ranges_stats(const bzh_ctx *ctx, bzh_decode_ranges_stats *out)
+{
+    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
+    if (!ctx || !out) return BZH_E_ARG;
+    *out = ctx->qstats;
+    return BZH_OK;
+    });
 }
 
 extern "C" int bzh_get_decode_stats(const bzh_ctx *ctx, bzh_decode_stats *out)

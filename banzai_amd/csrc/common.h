@@ -180,6 +180,8 @@ struct bzh_ctx {
     bzh_decode_stats dstats{};
     bzh_decode_many_stats mstats{}; // of the last bzh_decode_many* call
     bzh_recover_stats rstats{};     // of the last bzh_recover* call
+    bzh_decode_ranges_stats qstats{}; // of the last bzh_decode_ranges* call
+    DevBuf ranges_ws;               // bzh_decode_ranges*: a batch's piece tables (allocated on first use)
     struct DStream *dstrm = nullptr; // streaming decode (bzh_dstream_*, decode.hip): made by the first begin, freed by dstream_free
     size_t dstrm_window = 0, dstrm_staging = 0; // bzh_dstream_set_room: targets of the next begin (0: the defaults)
     // streaming encode (bzh_stream_*)
@@ -538,6 +540,11 @@ int decode_sync_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count, co
 int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
                      uint64_t off, uint64_t len, uint8_t *d_out, size_t cap, size_t *out_len, const bzh_sync_point *pts = nullptr,
                      size_t npts = 0);
+// decode.hip: the same over many ranges at once, every touched block decoded once.  touched / out_offs / out_total: what
+// decode_plan.h's bzp_spans made of the ranges, out_total within the room at d_out
+int decode_ranges_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                      const bzh_sync_point *pts, size_t npts, const bzh_range *ranges, size_t nranges, const size_t *out_offs,
+                      const std::vector<uint32_t> &touched, uint8_t *d_out, uint64_t out_total);
 // decode.hip: many inputs, one chain each, batches across them (the walk itself: decode_many_plan.h).  The slices have been checked.
 int decode_many_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const size_t *in_offs, const size_t *in_lens, size_t count, uint8_t *d_out,
                     size_t cap, size_t *out_offs, size_t *out_lens, int *status, size_t *consumed, const std::vector<uint64_t> &cands);

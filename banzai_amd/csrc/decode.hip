@@ -530,6 +530,86 @@ __global__ void __launch_bounds__(UR_THREADS) unrle_walk_win(UrArgs a, UwArgs wa
     if (tail0 + threadIdx.x < len) gw[tail0 + threadIdx.x] = sw0[tail0 + threadIdx.x];
 }
 
+// ---- many ranges: one expansion of a tile, many destinations --------------------------------------------------------------
+struct UpArgs {
+    const uint32_t *tile_first; // [K * Tp + 1] bzp_pieces' table: the references of tile t of block k
+    const PieceRef *refs;       // each cut to its tile, in the block's own output coordinates
+    uint32_t Tp, nrefs;
+    uint64_t out_total;         // bytes of `out`: no store at or behind it
+};
+
+// n bytes of LDS to global memory by the `nth` threads of which this is thread `tid`: aligned words, the ragged edges byte by byte
+__device__ __forceinline__ void ur_copy_out(uint8_t *g, const uint8_t *s, uint32_t n, uint32_t tid, uint32_t nth)
+{
+    const uint32_t head = min(n, (uint32_t)((0 - (uintptr_t)g) & 3u));
+    const uint32_t words = (n - head) / 4, tail0 = head + words * 4;
+    if (tid < head) g[tid] = s[tid];
+    for (uint32_t i = tid; i < words; i += nth) {
+        const uint8_t *sp = s + head + 4 * i;
+        *reinterpret_cast<uint32_t *>(g + head + 4 * i) = (uint32_t)sp[0] | (uint32_t)sp[1] << 8 | (uint32_t)sp[2] << 16 | (uint32_t)sp[3] << 24;
+    }
+    if (tail0 + tid < n) g[tail0 + tid] = s[tail0 + tid];
+}
+
+// unrle_walk_win for a block of which several pieces are wanted, each somewhere else: the tile is loaded, scanned and expanded
+// once, then stage[piece] goes to every piece that meets the tile -- a wavefront a piece where there are many, the workgroup
+// where there are few.  A tile too large to stage is emitted piece by piece, clipped run by run.  No reference is trusted: every
+// position is clipped to the reference, to the tile's total and to this walk's own sum, every destination to out_total.
+__global__ void __launch_bounds__(UR_THREADS) unrle_walk_pieces(UrArgs a, UpArgs pa)
+{
+    __shared__ uint32_t lds[8];
+    __shared__ uint8_t stage[UR_STAGE];
+    const uint32_t b = a.slots[blockIdx.y], t = blockIdx.x, n = a.n[b];
+    const size_t ti = (size_t)b * a.T + t;
+    const uint32_t tile_total = a.tout[ti];
+    if (tile_total == 0 || t >= pa.Tp) return;
+    const size_t cell = (size_t)blockIdx.y * pa.Tp + t;
+    const uint32_t f1 = min(pa.tile_first[cell + 1], pa.nrefs), f0 = min(pa.tile_first[cell], f1);
+    if (f0 == f1) return; // no piece meets the tile
+    const uint32_t toff = a.toff[ti], entry = a.tstate[ti];
+    const UrBytes u = ur_load(a.x + (size_t)b * a.S, n, t * UR_TILE + threadIdx.x * UR_ITEMS);
+    uint32_t total;
+    const uint32_t ex = ur_scan(ur_thread_map(u), lds, &total);
+    const uint32_t s = bzd_rl_apply(ex, entry);
+    uint32_t outn = 0, sw = s, prev = u.prev;
+#pragma unroll
+    for (int k = 0; k < (int)UR_ITEMS; k++) {
+        if ((uint32_t)k < u.cnt) {
+            const uint32_t c = u.at(k);
+            outn += sw == 4 ? c : 1u;
+            sw = bzd_rl_step(sw, c == prev);
+            prev = c;
+        }
+    }
+    uint32_t summed;
+    const uint32_t o0 = block_excl_add(outn, lds, &summed);
+    const uint32_t lim = min(tile_total, summed); // (equal by construction, as in unrle_walk_win)
+    const bool staged = tile_total <= UR_STAGE;
+    if (staged) {
+        bzd_ur_emit(u.w, u.cnt, u.prev, s, o0, 0u, lim, [&](uint32_t q, uint8_t v) { stage[q] = v; });
+        __syncthreads();
+    }
+    // (bzd_piece_cut: the piece inside the tile, [ca, cb) of the tile's own bytes, and where its first byte goes)
+    auto cut = [&](const PieceRef &r, uint32_t *ca, uint32_t *cb, uint8_t **g) {
+        uint64_t dst;
+        if (!bzd_piece_cut(toff, lim, r.lo, r.hi, r.base, pa.out_total, ca, cb, &dst)) return false;
+        *g = a.out + dst;
+        return true;
+    };
+    uint32_t ca, cb;
+    uint8_t *g;
+    if (!staged) {
+        for (uint32_t f = f0; f < f1; f++)
+            if (cut(pa.refs[f], &ca, &cb, &g)) bzd_ur_emit(u.w, u.cnt, u.prev, s, o0, ca, cb, [&](uint32_t q, uint8_t v) { g[q - ca] = v; });
+    } else if (f1 - f0 < UR_THREADS / 64) {
+        for (uint32_t f = f0; f < f1; f++)
+            if (cut(pa.refs[f], &ca, &cb, &g)) ur_copy_out(g, stage + ca, cb - ca, threadIdx.x, UR_THREADS);
+    } else {
+        for (uint32_t f = f0 + (threadIdx.x >> 6); f < f1; f += UR_THREADS / 64)
+            if (cut(pa.refs[f], &ca, &cb, &g)) ur_copy_out(g, stage + ca, cb - ca, threadIdx.x & 63u, 64);
+    }
+}
+
 // The CRC of a block's expansion from the bytes behind its inverse BWT.  The CRC is linear: a thread folds what its 16 bytes
 // stand for (literals and runs, entered in the state the scan hands it) into a register of its own, and that register times
 // x^(8 * bytes behind the thread's piece in the block) is the piece's share of the block's CRC.  The power splits in two: the
@@ -778,8 +858,14 @@ static int back_sizes(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk,
 // CRC alone -- the index build.  Only the kernels some block needs are launched.  crcs false: no CRC is taken.  One wait.
 // relist: `blocks` is not the list back_sizes was given but some of its blocks (bzh_recover's second emit, of the blocks the first
 // one's CRCs kept): the whole blocks' slots go up again.
+// pieces (bzh_decode_ranges only): blocks of the list with an empty window here, emitted piece by piece beside the others.
+struct BackPieces {
+    const uint32_t *slots; // [K] device: their batch slots
+    uint32_t K;
+    UpArgs args;
+};
 static int back_emit(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk, uint8_t *d_out, bool crcs, std::vector<BackBlock> &blocks,
-                     bool relist = false)
+                     bool relist = false, const BackPieces *pieces = nullptr)
 {
     hipStream_t st = ctx->stream;
     auto up = [&](void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st); };
@@ -818,6 +904,11 @@ static int back_emit(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk, 
         HIP_TRY(ctx, up(w.whi, bk.ehi.data(), (size_t)KW * 4));
         HIP_TRY(ctx, up(w.wbase, bk.ebase.data(), (size_t)KW * 8));
         unrle_walk_win<<<dim3(bk.Tn, KW), UR_THREADS, 0, st>>>(ae, wa);
+    }
+    if (pieces && pieces->K) {
+        UrArgs ap = bk.a;
+        ap.slots = pieces->slots;
+        unrle_walk_pieces<<<dim3(bk.Tn, pieces->K), UR_THREADS, 0, st>>>(ap, pieces->args);
     }
     HIP_TRY(ctx, hipGetLastError());
     clock.span(3, bk.t_unrle);
@@ -1725,5 +1816,240 @@ int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_by
     clock.collect();
     ds.out_bytes = clipped;
     *out_len = (size_t)clipped;
+    return BZH_OK;
+}
+
+// ================================================================================================================
+// Many ranges in one call (bzh_decode_ranges*): decode_range_run over a list of entries, each block decoded once
+// ================================================================================================================
+extern "C" int bzh_index_spans(const bzh_index_entry *idx, size_t count, const bzh_range *ranges, size_t nranges, uint32_t *touched,
+                               size_t max, size_t *ntouched, uint64_t *byte_lo, uint64_t *byte_hi, uint64_t *out_total)
+{
+    if ((!idx && count) || (!ranges && nranges) || (!touched && max) || !ntouched || !byte_lo || !byte_hi || !out_total) return BZH_E_ARG;
+    if (count > 0xFFFFFFFFull) return BZH_E_ARG;
+    std::vector<uint32_t> list;
+    *out_total = bzp_spans(idx, count, ranges, nranges, nullptr, nullptr, list, byte_lo, byte_hi);
+    *ntouched = list.size();
+    if (list.size() > max) return BZH_E_CAP;
+    if (!list.empty()) memcpy(touched, list.data(), list.size() * sizeof(uint32_t));
+    return BZH_OK;
+}
+
+// (idx has passed decode_index_check, pts decode_sync_check; touched and out_offs are bzp_spans', whose sum is out_total <= the
+// room at d_out)
+int decode_ranges_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                      const bzh_sync_point *pts, size_t npts, const bzh_range *ranges, size_t nranges, const size_t *out_offs,
+                      const std::vector<uint32_t> &touched, uint8_t *d_out, uint64_t out_total)
+{
+    hipStream_t st = ctx->stream;
+    Batch &bt = ctx->bt;
+    bzh_decode_stats &ds = ctx->dstats;
+    bzh_decode_ranges_stats &qs = ctx->qstats;
+    if (touched.empty()) return BZH_OK;
+    const uint64_t byte_lo = idx[touched.front()].bit_pos / 8, byte_hi = (idx[touched.back()].end_bit + 7) / 8;
+    if (in_byte_base > byte_lo || byte_hi - in_byte_base > n) {
+        bzh_set_error(ctx, "decode range: index entries %zu..%zu lie in bytes [%llu, %llu) of the indexed input, the buffer holds [%llu, %llu)",
+                      (size_t)touched.front(), (size_t)touched.back(), (unsigned long long)byte_lo, (unsigned long long)byte_hi,
+                      (unsigned long long)in_byte_base, (unsigned long long)(in_byte_base + n));
+        return BZH_E_ARG;
+    }
+    DecWs w;
+    BZH_TRY(dec_ws(ctx, w));
+    if (w.T > UR_THREADS) {
+        bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
+        return BZH_E_STATE;
+    }
+    // what every range wants of every touched block
+    std::vector<size_t> pfirst;
+    std::vector<PieceRef> pc;
+    std::vector<uint32_t> prange;
+    bzp_block_pieces(idx, count, ranges, nranges, out_offs, touched, pfirst, pc, prange);
+    qs.pieces = pc.size();
+    StageClock clock{ctx, {}};
+    size_t at = 0; // the entry an error is about
+    auto mismatch = [&](const char *what) {
+        bzh_set_error(ctx, "decode range: index entry %zu (stream %u, bit %llu) does not match its block: %s", at, idx[at].stream,
+                      (unsigned long long)idx[at].bit_pos, what);
+        return BZH_E_DATA;
+    };
+    size_t seg_point = 0; // the sync point a segment's error is about
+    auto seg_mismatch = [&](bool named, const char *what) {
+        if (!named) return mismatch(what);
+        bzh_set_error(ctx, "decode range: index entry %zu (stream %u, bit %llu) does not match its block: sync point %zu: %s", at, idx[at].stream,
+                      (unsigned long long)idx[at].bit_pos, seg_point, what);
+        return BZH_E_DATA;
+    };
+    const uint32_t Bmax = (uint32_t)std::min<size_t>(ctx->max_batch, ctx->arena_blocks);
+    std::vector<SegDesc> hseg;
+    std::vector<BzdSegResult> hsres;
+    std::vector<uint32_t> seg0; // [B + 1] first segment of every block of the batch
+    std::vector<size_t> pmap;   // the batch's points, gathered: which of pts each is
+    std::vector<bzh_sync_point> hpts;
+    std::vector<uint64_t> hcand;
+    std::vector<BzdResult> res;
+    std::vector<uint32_t> hmagic, pslots, ptiles, tile_first;
+    std::vector<size_t> pf;     // the pieces of the batch's blocks that are emitted piece by piece: pc[pf[k] .. pf[k + 1])
+    std::vector<PieceRef> bpc, refs;
+    std::vector<BackBlock> blocks;
+    Back bk;
+    for (size_t t0 = 0; t0 < touched.size();) {
+        const uint32_t B = (uint32_t)std::min<size_t>(Bmax, touched.size() - t0);
+        const uint32_t *ent = touched.data() + t0;
+        qs.batches++;
+        // entropy stage: the entries are the candidates
+        hcand.resize(B);
+        for (uint32_t k = 0; k < B; k++) hcand[k] = (idx[ent[k]].bit_pos - 8 * in_byte_base) << 1;
+        BzdHead *d_heads = nullptr;
+        bzh_sync_point *d_pts = nullptr;
+        SegDesc *d_segs = nullptr;
+        BzdSegResult *d_sres = nullptr;
+        if (npts) {
+            bzp_segments(idx, ent, B, pts, npts, hseg, seg0, pmap);
+            hpts.resize(pmap.size());
+            for (size_t j = 0; j < pmap.size(); j++) hpts[j] = pts[pmap[j]];
+            BZH_TRY(reserve_cut(ctx, ctx->sync_ws, "the sync points", grow_mib, [&](Carver &c) { // (the stream is idle between batches)
+                c.put(d_heads, B), c.put(d_pts, hpts.size());
+                c.put(d_segs, hseg.size()), c.put(d_sres, hseg.size());
+            }));
+        }
+        hipEvent_t t1 = clock.mark();
+        HIP_TRY(ctx, hipMemcpyAsync(w.cand, hcand.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
+        if (npts) {
+            if (!hpts.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_pts, hpts.data(), hpts.size() * sizeof(bzh_sync_point), hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(d_segs, hseg.data(), hseg.size() * sizeof(SegDesc), hipMemcpyHostToDevice, st));
+            decode_header_kernel<<<dim3(B), 64, 0, st>>>(d_in, n, w.cand, d_heads, w.res);
+            decode_segment_kernel<<<dim3((uint32_t)hseg.size()), 64, 0, st>>>(d_in, n, 8 * in_byte_base, d_heads, d_pts, d_segs, bt, w.res, d_sres);
+        } else {
+            decode_block_kernel<<<dim3(B), 64, 0, st>>>(d_in, n, w.cand, bt, w.res, 100000u * (uint32_t)ctx->level);
+        }
+        range_magic_kernel<<<dim3((B + 63) / 64), 64, 0, st>>>(d_in, n, w.cand, B, w.magic);
+        HIP_TRY(ctx, hipGetLastError());
+        clock.span(1, t1);
+        res.resize(B);
+        hmagic.resize(B);
+        if (npts) {
+            hsres.resize(hseg.size());
+            HIP_TRY(ctx, hipMemcpyAsync(hsres.data(), d_sres, hseg.size() * sizeof(BzdSegResult), hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(res.data(), w.res, (size_t)B * sizeof(BzdResult), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(hmagic.data(), w.magic, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, bzh_stream_wait(st));
+        uint32_t nmax = 1;
+        for (uint32_t k = 0; k < B; k++) {
+            at = ent[k];
+            const bzh_index_entry &e = idx[at];
+            BzdResult &r = res[k];
+            if (hmagic[k]) return mismatch("no block magic at bit_pos");
+            if (r.kind != BZD_OK) return mismatch(kind_name(r.kind));
+            if (npts) { // every segment in order: the first that fails names the point it could not start from or arrive at
+                for (uint32_t g = seg0[k]; g < seg0[k + 1]; g++) {
+                    const BzdSegResult &sr = hsres[g];
+                    const SegDesc &d = hseg[g];
+                    const bool named = d.from >= 0 || d.to >= 0;
+                    if (sr.miss == BZD_SEG_START) {
+                        if (named) seg_point = pmap[(size_t)(d.from >= 0 ? d.from : d.to)];
+                        return seg_mismatch(named, "it is no state of this block");
+                    }
+                    if (named) seg_point = pmap[(size_t)(d.to >= 0 ? d.to : d.from)];
+                    if (sr.kind != BZD_OK) return seg_mismatch(named, kind_name(sr.kind));
+                    if (sr.miss == BZD_SEG_EOB) return seg_mismatch(named, "the block ends in front of it");
+                    if (sr.miss == BZD_SEG_ARRIVE) return seg_mismatch(named, "the segment in front of it arrives in another state");
+                    if (d.to < 0) {
+                        r.end_bit = sr.end_bit;
+                        r.nblock = sr.nblock;
+                    }
+                }
+            }
+            if (r.end_bit + 8 * in_byte_base != e.end_bit) return mismatch("it ends at another bit than end_bit");
+            if (r.crc != e.crc) return mismatch("its stored CRC differs");
+            if (r.nblock > 100000u * e.level) return mismatch("more bytes than the level's block size");
+            nmax = std::max(nmax, r.nblock);
+        }
+        ds.blocks += B;
+        blocks.clear();
+        for (uint32_t k = 0; k < B; k++) blocks.push_back(BackBlock{k, res[k].nblock, 0, false, 0, 0, 0, 0});
+        BZH_TRY(back_sizes(ctx, w, clock, bk, B, nmax, blocks));
+        // A block that one range wants whole and no other touches is expanded where it belongs and checked there; every other one
+        // goes out piece by piece, its window here empty: back_emit takes its CRC from the bytes behind the inverse BWT.
+        pslots.clear(), ptiles.clear(), bpc.clear();
+        pf.assign(1, 0);
+        for (uint32_t k = 0; k < B; k++) {
+            at = ent[k];
+            const bzh_index_entry &e = idx[at];
+            BackBlock &b = blocks[k];
+            if (b.bad_end) return mismatch("the block ends in four equal bytes without a count");
+            if (b.size != e.out_len) return mismatch("it decodes to another size than out_len");
+            const size_t q0 = pfirst[t0 + k], q1 = pfirst[t0 + k + 1];
+            if (q1 - q0 == 1 && pc[q0].lo == 0 && pc[q0].hi == e.out_len) {
+                b.hi = e.out_len;
+                b.base = (int64_t)pc[q0].base;
+                qs.blocks_whole++;
+                continue;
+            }
+            pslots.push_back(k);
+            ptiles.push_back((b.nblock + UR_TILE - 1) / UR_TILE);
+            bpc.insert(bpc.end(), pc.begin() + q0, pc.begin() + q1);
+            pf.push_back(bpc.size());
+        }
+        BackPieces bp{nullptr, (uint32_t)pslots.size(), UpArgs{nullptr, nullptr, bk.Tn, 0, out_total}};
+        if (bp.K) {
+            if (!bzp_pieces(pslots.data(), ptiles.data(), bp.K, bk.hout.data(), bk.hoff.data(), w.T, bk.Tn, pf.data(), bpc.data(), tile_first,
+                            refs)) {
+                bzh_set_error(ctx, "decode ranges: the ranges meet the tiles of one batch more than 2^32 times");
+                return BZH_E_ARG;
+            }
+            uint32_t *d_slots = nullptr, *d_first = nullptr;
+            PieceRef *d_refs = nullptr;
+            BZH_TRY(reserve_cut(ctx, ctx->ranges_ws, "the pieces of the ranges", grow_mib, [&](Carver &c) {
+                c.put(d_refs, refs.size()), c.put(d_first, tile_first.size()), c.put(d_slots, bp.K);
+            }));
+            HIP_TRY(ctx, hipMemcpyAsync(d_slots, pslots.data(), (size_t)bp.K * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(d_first, tile_first.data(), tile_first.size() * 4, hipMemcpyHostToDevice, st));
+            if (!refs.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_refs, refs.data(), refs.size() * sizeof(PieceRef), hipMemcpyHostToDevice, st));
+            bp.slots = d_slots;
+            bp.args.tile_first = d_first;
+            bp.args.refs = d_refs;
+            bp.args.nrefs = (uint32_t)refs.size();
+        }
+#ifdef BZH_EXPERIMENTS
+        // scripts/gpu_ranges.py: the pieces through unrle_walk_win, a grid row each, to set beside unrle_walk_pieces
+        const bool by_window = bp.K && getenv("BZH_RANGES_WIN");
+        const uint32_t P = by_window ? (uint32_t)bpc.size() : 0;
+        if (by_window) bp.K = 0;
+#endif
+        BZH_TRY(back_emit(ctx, w, clock, bk, d_out, true, blocks, false, &bp));
+#ifdef BZH_EXPERIMENTS
+        if (P) {
+            std::vector<uint32_t> xs, xlo, xhi;
+            std::vector<int64_t> xbase;
+            for (size_t k = 0; k + 1 < pf.size(); k++)
+                for (size_t q = pf[k]; q < pf[k + 1]; q++) {
+                    xs.push_back(pslots[k]), xlo.push_back(bpc[q].lo), xhi.push_back(bpc[q].hi);
+                    xbase.push_back((int64_t)bpc[q].base - (int64_t)bpc[q].lo);
+                }
+            uint32_t *d_xs = nullptr, *d_xlo = nullptr, *d_xhi = nullptr;
+            int64_t *d_xbase = nullptr;
+            BZH_TRY(reserve_cut(ctx, ctx->ranges_ws, "the pieces of the ranges", grow_mib,
+                                [&](Carver &c) { c.put(d_xbase, P), c.put(d_xs, P), c.put(d_xlo, P), c.put(d_xhi, P); }));
+            HIP_TRY(ctx, hipMemcpyAsync(d_xs, xs.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(d_xlo, xlo.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(d_xhi, xhi.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(d_xbase, xbase.data(), (size_t)P * 8, hipMemcpyHostToDevice, st));
+            UrArgs ax = bk.a;
+            ax.slots = d_xs;
+            unrle_walk_win<<<dim3(bk.Tn, P), UR_THREADS, 0, st>>>(ax, UwArgs{d_xlo, d_xhi, d_xbase, nullptr, nullptr, nullptr, nullptr});
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, bzh_stream_wait(st));
+        }
+#endif
+        for (uint32_t k = 0; k < B; k++) { // (ascending: the first entry that fails is named)
+            if (blocks[k].crc == idx[ent[k]].crc) continue;
+            at = ent[k];
+            return mismatch(kind_name(BZD_K_BLOCK_CRC));
+        }
+        t0 += B;
+    }
+    clock.collect();
+    ds.out_bytes = out_total;
     return BZH_OK;
 }

@@ -580,6 +580,21 @@ BZD_FN void bzd_clip(uint32_t o, uint32_t len, uint32_t lo, uint32_t hi, uint32_
     if (*b < *a) *b = *a;
 }
 
+// What a tile of `len` output bytes at `toff` of its block owes a piece: bytes [lo, hi) of the block's own output, wanted at
+// `base` of an output of out_total bytes.  [*a, *b) = the piece inside the tile, in the tile's own bytes; *dst = where byte *a
+// goes.  False: the two do not meet -- or the bytes would not lie inside the output, which no table may make a kernel leave.
+BZD_FN bool bzd_piece_cut(uint32_t toff, uint32_t len, uint32_t lo, uint32_t hi, uint64_t base, uint64_t out_total, uint32_t *a, uint32_t *b,
+                          uint64_t *dst)
+{
+    bzd_clip(toff, len, lo, hi, a, b);
+    if (*a >= *b) return false;
+    *dst = base + (*a - lo);
+    if (*dst < base || *dst >= out_total || *b - *a > out_total - *dst) return false;
+    *a -= toff;
+    *b -= toff;
+    return true;
+}
+
 // The expansion of the stretch, which begins at output position o: put(position, byte) for every position inside [lo, hi) and
 // for no other.  A run that lies outside the window costs nothing.
 template <class Put>

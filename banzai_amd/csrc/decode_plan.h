@@ -5,6 +5,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <algorithm>
 #include <vector>
 
 #include "batch.h"       // BlockDesc, the carver
@@ -61,6 +62,198 @@ static inline void bzp_segments(const E *idx, size_t e0, uint32_t B, const P *pt
         segs.push_back({k, prev, -1, bmax});
     }
     seg0[B] = (uint32_t)segs.size();
+}
+
+// The same for a batch whose blocks are the entries idx[ent[0 .. B)] (ascending, not necessarily adjacent) and whose points are
+// gathered: pmap[j] = the point of pts[0 .. npts) that lies at j of the gathered array, which from / to count in.
+template <class E, class P>
+static inline void bzp_segments(const E *idx, const uint32_t *ent, uint32_t B, const P *pts, size_t npts, std::vector<SegDesc> &segs,
+                                std::vector<uint32_t> &seg0, std::vector<size_t> &pmap)
+{
+    segs.clear();
+    pmap.clear();
+    seg0.assign((size_t)B + 1, 0);
+    for (uint32_t k = 0; k < B; k++) {
+        seg0[k] = (uint32_t)segs.size();
+        const uint32_t bmax = 100000u * idx[ent[k]].level;
+        size_t lo = 0, hi = npts; // the first point of entry ent[k] or behind
+        while (lo < hi) {
+            const size_t mid = lo + (hi - lo) / 2;
+            if (pts[mid].entry < ent[k])
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        int32_t prev = -1;
+        for (size_t q = lo; q < npts && pts[q].entry == ent[k]; q++) {
+            segs.push_back({k, prev, (int32_t)pmap.size(), bmax});
+            prev = (int32_t)pmap.size();
+            pmap.push_back(q);
+        }
+        segs.push_back({k, prev, -1, bmax});
+    }
+    seg0[B] = (uint32_t)segs.size();
+}
+
+// ---- many ranges in one call (bzh_decode_ranges*, bzh_index_spans) ---------------------------------------------------------
+// The bytes of [off, off + len) inside an output of `total` bytes; off + len saturates.
+static inline uint64_t bzp_clip_len(uint64_t total, uint64_t off, uint64_t len)
+{
+    return off < total ? (len < total - off ? len : total - off) : 0;
+}
+
+// The entries [*first, *last) that hold output bytes [off, off + clipped), clipped > 0 and inside the indexed total (E:
+// bzh_index_entry).  Two binary searches that stay inside idx[0 .. count) whatever the entries hold.
+template <class E>
+static inline void bzp_entry_span(const E *idx, size_t count, uint64_t off, uint64_t clipped, size_t *first, size_t *last)
+{
+    size_t lo = 0, hi = count; // the first entry that ends behind `off`
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo) / 2;
+        if (idx[mid].out_off + idx[mid].out_len <= off)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    *first = lo;
+    const uint64_t end = off + clipped; // the first entry that starts at or behind the end
+    hi = count;
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo) / 2;
+        if (idx[mid].out_off < end)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    *last = lo;
+}
+
+// Where the ranges' bytes go and which entries they touch (R: bzh_range).  out_lens[r] = the range clipped to the indexed total,
+// out_offs[r] = the running sum (either may be null); touched = the union of the ranges' entries, ascending and unique;
+// [*byte_lo, *byte_hi) = the bytes of the indexed input from the first touched entry's bit_pos / 8 to the last one's
+// ceil(end_bit / 8), 0 and 0 with nothing touched.  Returns the sum of the clipped lengths.
+template <class E, class R>
+static inline uint64_t bzp_spans(const E *idx, size_t count, const R *ranges, size_t nranges, size_t *out_offs, size_t *out_lens,
+                                 std::vector<uint32_t> &touched, uint64_t *byte_lo, uint64_t *byte_hi)
+{
+    const uint64_t total = count ? idx[count - 1].out_off + idx[count - 1].out_len : 0;
+    std::vector<uint64_t> runs; // first << 32 | last, one a range that touches anything
+    uint64_t sum = 0;
+    for (size_t r = 0; r < nranges; r++) {
+        const uint64_t c = bzp_clip_len(total, ranges[r].off, ranges[r].len);
+        if (out_offs) out_offs[r] = (size_t)sum;
+        if (out_lens) out_lens[r] = (size_t)c;
+        sum += c;
+        if (c == 0) continue;
+        size_t first, last;
+        bzp_entry_span(idx, count, ranges[r].off, c, &first, &last);
+        if (first < last) runs.push_back((uint64_t)first << 32 | (uint64_t)last);
+    }
+    std::sort(runs.begin(), runs.end());
+    touched.clear();
+    uint32_t next = 0; // entries below it are listed
+    for (uint64_t run : runs)
+        for (uint32_t e = std::max(next, (uint32_t)(run >> 32)); e < (uint32_t)run; e++) {
+            touched.push_back(e);
+            next = e + 1;
+        }
+    *byte_lo = touched.empty() ? 0 : idx[touched.front()].bit_pos / 8;
+    *byte_hi = touched.empty() ? 0 : (idx[touched.back()].end_bit + 7) / 8;
+    return sum;
+}
+
+// A piece: bytes [lo, hi) of a block's own output, wanted at out[base .. base + hi - lo).
+struct PieceRef {
+    uint32_t lo, hi;
+    uint64_t base;
+};
+
+// The pieces of every touched block, a piece being what one range wants of one block: block touched[j] has pieces
+// pc[pfirst[j] .. pfirst[j + 1]), in the order of their ranges; prange names each piece's range.  out_offs: bzp_spans'.
+template <class E, class R>
+static inline void bzp_block_pieces(const E *idx, size_t count, const R *ranges, size_t nranges, const size_t *out_offs,
+                                    const std::vector<uint32_t> &touched, std::vector<size_t> &pfirst, std::vector<PieceRef> &pc,
+                                    std::vector<uint32_t> &prange)
+{
+    const uint64_t total = count ? idx[count - 1].out_off + idx[count - 1].out_len : 0;
+    pfirst.assign(touched.size() + 1, 0);
+    std::vector<size_t> cursor;
+    for (int pass = 0; pass < 2; pass++) {
+        for (size_t r = 0; r < nranges; r++) {
+            const uint64_t off = ranges[r].off, c = bzp_clip_len(total, off, ranges[r].len);
+            if (c == 0) continue;
+            size_t first, last;
+            bzp_entry_span(idx, count, off, c, &first, &last);
+            if (first >= last) continue;
+            // (every entry of the range is listed, and the list ascends without gaps inside a range)
+            const size_t j0 = (size_t)(std::lower_bound(touched.begin(), touched.end(), (uint32_t)first) - touched.begin());
+            for (size_t e = first; e < last; e++) {
+                const size_t j = j0 + (e - first);
+                if (pass == 0) {
+                    pfirst[j + 1]++;
+                    continue;
+                }
+                PieceRef p;
+                bzp_window(idx[e].out_off, idx[e].out_len, off, off + c, &p.lo, &p.hi);
+                p.base = (uint64_t)out_offs[r] + (idx[e].out_off + p.lo - off);
+                pc[cursor[j]] = p;
+                prange[cursor[j]++] = (uint32_t)r;
+            }
+        }
+        if (pass == 0) {
+            for (size_t j = 0; j < touched.size(); j++) pfirst[j + 1] += pfirst[j];
+            pc.resize(pfirst.back());
+            prange.resize(pfirst.back());
+            cursor.assign(pfirst.begin(), pfirst.end() - 1);
+        }
+    }
+}
+
+// Which pieces meet which tile, for the K blocks of a batch that are emitted piece by piece.  Block k has the pieces
+// pc[pf[k] .. pf[k + 1]) and ntiles[k] tiles, tile t putting out tout[k][t] bytes at toff[k][t] of the block (rows of `stride`
+// words at tout + rows[k] * stride: the host image of the device tables).  refs[tile_first[k * Tn + t] .. tile_first[k * Tn + t
+// + 1]) = the pieces that meet tile t of block k, each cut to the tile: [lo, hi) inside [toff, toff + tout), base moved along.
+// A tile without output meets none.  False: more references than 32 bits count.
+static inline bool bzp_pieces(const uint32_t *rows, const uint32_t *ntiles, uint32_t K, const uint32_t *tout, const uint32_t *toff,
+                              uint32_t stride, uint32_t Tn, const size_t *pf, const PieceRef *pc, std::vector<uint32_t> &tile_first,
+                              std::vector<PieceRef> &refs)
+{
+    tile_first.assign((size_t)K * Tn + 1, 0);
+    std::vector<uint32_t> cursor;
+    for (int pass = 0; pass < 2; pass++) {
+        for (uint32_t k = 0; k < K; k++) {
+            const uint32_t *o = tout + (size_t)rows[k] * stride, *f = toff + (size_t)rows[k] * stride;
+            const uint32_t tn = std::min(ntiles[k], Tn);
+            for (size_t q = pf[k]; q < pf[k + 1]; q++) {
+                const PieceRef &p = pc[q];
+                if (p.lo >= p.hi || tn == 0) continue;
+                // the last tile that starts at or in front of lo; from there on while tiles start in front of hi
+                uint32_t t = (uint32_t)(std::upper_bound(f, f + tn, p.lo) - f);
+                t = t ? t - 1 : 0;
+                for (; t < tn && f[t] < p.hi; t++) {
+                    const uint32_t a = std::max(p.lo, f[t]), b = std::min(p.hi, f[t] + o[t]);
+                    if (a >= b) continue;
+                    const size_t cell = (size_t)k * Tn + t;
+                    if (pass == 0) {
+                        if (++tile_first[cell + 1] == 0) return false;
+                        continue;
+                    }
+                    refs[cursor[cell]++] = PieceRef{a, b, p.base + (a - p.lo)};
+                }
+            }
+        }
+        if (pass == 0) {
+            uint64_t sum = 0;
+            for (size_t c = 1; c < tile_first.size(); c++) {
+                sum += tile_first[c];
+                if (sum > 0xFFFFFFFFull) return false;
+                tile_first[c] = (uint32_t)sum;
+            }
+            refs.resize((size_t)sum);
+            cursor.assign(tile_first.begin(), tile_first.end() - 1);
+        }
+    }
+    return true;
 }
 
 // ---- the decoder's per-batch tables (decode.hip) ---------------------------------------------------------------------------

@@ -414,6 +414,64 @@ BZH_API int bzh_decode_range_sync_device(bzh_ctx *ctx, const void *d_in, size_t 
                                          size_t count, const bzh_sync_point *pts, size_t npts, uint64_t off, uint64_t len,
                                          void *d_out, size_t cap, size_t *out_len);
 
+/* ---- many ranges in one call: every touched block is decoded once, in shared batches ---------------------------------- */
+
+/* Output bytes [off, off + len) of the indexed input.  off + len saturates: a range that would end behind 2^64 - 1 ends there. */
+typedef struct {
+    uint64_t off, len;
+} bzh_range;
+
+/* Pure host arithmetic (no context, no GPU): the entries the ranges touch -- the union over the ranges, ascending and unique,
+ * as entry numbers in touched[0 .. *ntouched) --, the bytes [*byte_lo, *byte_hi) of the indexed input from the first touched
+ * entry's bit_pos / 8 to the last one's ceil(end_bit / 8) (the hull: what lies between two touched entries is inside it), and
+ * *out_total = the sum over the ranges of min(len, total - off).  Nothing touched: *ntouched = 0, *byte_lo == *byte_hi == 0.
+ * *ntouched is set also when max is too small: BZH_E_CAP, touched then unspecified; touched may be null when max is 0.
+ * BZH_E_ARG: a null pointer, 2^32 entries or more.  The entries must be ordered as bzh_decode_index writes them. */
+BZH_API int bzh_index_spans(const bzh_index_entry *idx, size_t count, const bzh_range *ranges, size_t nranges, uint32_t *touched,
+                            size_t max, size_t *ntouched, uint64_t *byte_lo, uint64_t *byte_hi, uint64_t *out_total);
+
+/* bzh_decode_range_sync_device for nranges ranges at once.  A single-range read costs one block's serial entropy stage however
+ * short it is; here all ranges share their batches, so N short reads cost about what one costs.
+ * RANGES.  Each is clipped to the indexed total exactly as bzh_decode_range clips: out_lens[r] = min(len, total - off), 0 for
+ * off >= total.  They come in any order and may overlap, nest, repeat and be empty.
+ * OUTPUT.  The ranges' bytes lie back to back in d_out in the order given, no padding: out_offs[0] = 0, out_offs[r + 1] =
+ * out_offs[r] + out_lens[r], *out_total their sum.  All three are pure arithmetic over idx and ranges: they are set before
+ * anything is launched and on every error below except a null-pointer BZH_E_ARG.  cap < *out_total: BZH_E_CAP, nothing
+ * launched.  No byte outside d_out[0, *out_total) is written.
+ * ONE DECODE PER BLOCK.  The touched blocks are bzh_index_spans' list.  Each goes through the entropy stage, the inverse BWT
+ * and the CRC exactly once per call, however many ranges want it: bzh_get_decode_stats().blocks == blocks_touched.  A block
+ * that exactly one range wants whole and no other range touches is expanded in place (blocks_whole counts these); of every
+ * other one the tiles are expanded once and copied to each piece -- the intersection of one range with one block -- that meets
+ * them.
+ * VERIFIED: every touched block against its entry as by bzh_decode_range (the magic, end_bit, the stored CRC, the size, the
+ * level's block size, the open run of four), and its CRC over all of its bytes.  Stream CRCs are NOT verified, untouched blocks
+ * not looked at.  BZH_E_DATA names the first failing entry in ascending order, in bzh_decode_range's words.  The call is all or
+ * nothing: after an error d_out is unspecified; the context stays usable.
+ * d_in[0..n) holds the compressed bytes from byte in_byte_base of the indexed input and must cover [byte_lo, byte_hi) of
+ * bzh_index_spans, else BZH_E_ARG.  npts == 0: one wavefront a block; otherwise the points are checked as a whole and every
+ * touched block is decoded in segments, as by bzh_decode_range_sync.  The index is checked as a whole first, whatever the
+ * ranges (BZH_E_ARG as bzh_decode_range; also for 2^32 entries or more).  nranges == 0 or nothing touched: BZH_OK, *out_total =
+ * 0.  Like every entry point the call joins a streaming pass in flight, runs on the context's stream and honours
+ * bzh_set_profiling.  idx, pts, ranges, out_offs and out_lens are host arrays. */
+BZH_API int bzh_decode_ranges_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                                     size_t count, const bzh_sync_point *pts, size_t npts, const bzh_range *ranges, size_t nranges,
+                                     void *d_out, size_t cap, size_t *out_offs, size_t *out_lens, size_t *out_total);
+/* Same, host buffers.  Only [byte_lo, byte_hi) goes up (a buffer that does not cover it goes up whole: the device call says what
+ * is missing); sparse reads over a large input should hand in the touched blocks' bytes alone, with a sub-index. */
+BZH_API int bzh_decode_ranges(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                              size_t count, const bzh_sync_point *pts, size_t npts, const bzh_range *ranges, size_t nranges,
+                              uint8_t *out, size_t cap, size_t *out_offs, size_t *out_lens, size_t *out_total);
+
+/* Counters of the last bzh_decode_ranges* call. */
+typedef struct {
+    uint64_t ranges;         /* given */
+    uint64_t pieces;         /* (range, block) pairs that meet */
+    uint64_t blocks_touched; /* bzh_index_spans' list */
+    uint64_t blocks_whole;   /* of those: expanded in place */
+    uint64_t batches;        /* entropy-stage launches */
+} bzh_decode_ranges_stats;
+BZH_API int bzh_get_decode_ranges_stats(const bzh_ctx *ctx, bzh_decode_ranges_stats *out);
+
 /* ---- the encoder writes the index of its own stream: no decode pass to rediscover what it held -------------------------- */
 
 /* bzh_encode_device that also returns the index of the stream it writes: the entries bzh_decode_index would return for
