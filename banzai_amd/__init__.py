@@ -28,6 +28,10 @@ and random access into a .bz2 without decoding all of it (bzip2 blocks are indep
     encode_indexed(reader, writer, level, interval=256)  (encode() that returns that index of the stream it writes: the
                                                           encoder holds it all, no decode pass) -> SyncIndex / BlockIndex
 
+    encode_indexed_stream(reader, writer, level, interval=256)
+                                                         (the same index from the streaming encoder: the input is read in
+                                                          chunks and never held as a whole)
+
 Everything is computed by hand-written HIP kernels behind the C ABI in include/bzhip.h
 (libbzhip.so); there is no CPU path.  `reader` is any object with .read(), `writer` any object
 with .write() (the Rust signature takes BufRead / BufWriter<W>).
@@ -42,7 +46,7 @@ import numpy as np
 from . import _native
 
 __all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex",
-           "IndexedReader", "build_sync_index", "SyncIndex", "encode_indexed", "recover", "recover_stream", "Recovered", "RecoveredBlock", "Context", "MultiContext", "BzhError"]
+           "IndexedReader", "build_sync_index", "SyncIndex", "encode_indexed", "encode_indexed_stream", "recover", "recover_stream", "Recovered", "RecoveredBlock", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
 MultiContext = _native.MultiContext
@@ -648,6 +652,58 @@ def encode_indexed(reader, writer, level, interval=256, device=0):
         writer.flush()
     blocks = BlockIndex(entries, len(stream))
     return SyncIndex(blocks, points, interval) if interval else blocks
+
+
+def encode_indexed_stream(reader, writer, level, interval=256, chunk=READ_CHUNK, device=0):
+    """encode_indexed for inputs that are never held as a whole: encode()'s feed loop -- `chunk` bytes are read at a time, stream
+    bytes are written as they become final -- on a stream that records its index (bzh_stream_begin_index), which is taken after
+    every feed (bzh_stream_index_take), so the library holds no more of it than one pass found.  Returns what encode_indexed
+    returns for the same input, byte for byte: a SyncIndex, or a BlockIndex when interval is 0, `consumed` the stream's length."""
+    if isinstance(level, bool) or not isinstance(level, int) or not 1 <= level <= 9:
+        raise ValueError("level must be in 1..=9")
+    if isinstance(interval, bool) or not isinstance(interval, int):
+        raise TypeError(f"interval must be an int, not {type(interval).__name__}")
+    if not 0 <= interval <= 32767:
+        raise ValueError(f"interval must be 0 (no sync points) or 1..32767 groups, not {interval}")
+    if isinstance(chunk, bool) or not isinstance(chunk, int):
+        raise TypeError(f"chunk must be an int, not {type(chunk).__name__}")
+    if chunk < 1:
+        raise ValueError(f"chunk must be at least 1 byte, not {chunk}")
+    ctx = _ctx(level, device)
+    put = writer.write if _copying_sink(writer) else (lambda view: writer.write(bytes(view)))
+    ents, pts, written = [], [], 0
+    ctx.stream_begin_index(interval)
+    view = pos = None
+    if isinstance(reader, io.BytesIO):  # (lends its buffer, as in encode)
+        view, pos = memoryview(reader.getvalue()), reader.tell()
+    while True:
+        if view is not None:
+            data = view[pos:pos + chunk]
+            pos += len(data)
+        else:
+            data = reader.read(chunk)
+            if not isinstance(data, (bytes, bytearray, memoryview)):
+                raise TypeError("reader.read() must return bytes")
+        eof = len(data) == 0
+        out = ctx.stream_feed_view(data, eof)
+        if len(out):
+            written += len(out)
+            put(out)
+        e, p = ctx.stream_index_take()
+        if e.size:
+            ents.append(e)
+        if p.size:
+            pts.append(p)
+        if eof:
+            break
+    if view is not None:
+        reader.seek(pos)
+    if hasattr(writer, "flush"):
+        writer.flush()
+    blocks = BlockIndex(np.concatenate(ents) if ents else np.zeros(0, dtype=_native.INDEX_DTYPE), written)
+    if not interval:
+        return blocks
+    return SyncIndex(blocks, np.concatenate(pts) if pts else np.zeros(0, dtype=_native.SYNC_DTYPE), interval)
 
 
 def _index_arg(index):

@@ -220,6 +220,13 @@ SIGNATURES = {
     "bzh_stream_bound": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_size_t]),
     "bzh_stream_set_chunk": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),
     "bzh_stream_consumed": (ctypes.c_size_t, [ctypes.c_void_p]),
+    "bzh_stream_begin_index": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
+    "bzh_stream_index_pending": (ctypes.c_int, [ctypes.c_void_p, szp, szp]),
+    "bzh_stream_index_take": (ctypes.c_int, [ctypes.c_void_p, idxp, ctypes.c_size_t, szp, syncp, ctypes.c_size_t, szp]),
+    "bzh_index_blob_size": (ctypes.c_size_t, [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32]),
+    "bzh_index_blob_write": (ctypes.c_int, [idxp, ctypes.c_size_t, syncp, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint64, u8p,
+                                            ctypes.c_size_t, szp]),
+    "bzh_index_blob_read": (ctypes.c_int, [u8p, ctypes.c_size_t, idxp, ctypes.c_size_t, szp, syncp, ctypes.c_size_t, szp, u32p, u64p]),
     "bzh_dstream_set_room": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t]),
     "bzh_dstream_begin": (ctypes.c_int, [ctypes.c_void_p]),
     "bzh_dstream_feed": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, szp, u8p, ctypes.c_size_t, szp,
@@ -313,6 +320,46 @@ def _points(points):
     """a contiguous array of the 288-byte sync points and its ctypes pointer"""
     p = np.ascontiguousarray(points, dtype=SYNC_DTYPE)
     return p, (p.ctypes.data_as(syncp) if p.size else None)
+
+
+def index_blob_write(entries, points=None, interval=0, consumed=0):
+    """bzh_index_blob_write (pure host): the index file of these arrays -> bytes; interval 0: a block index blob (no points)"""
+    e, ep = _entries(entries)
+    q, qp = _points(points if points is not None else np.zeros(0, dtype=SYNC_DTYPE))
+    need = int(lib().bzh_index_blob_size(e.size, q.size, interval))
+    out = np.empty(max(need, 1), dtype=np.uint8)
+    olen = ctypes.c_size_t(0)
+    st = lib().bzh_index_blob_write(ep, e.size, qp, q.size, interval, consumed, ptr(out), need, ctypes.byref(olen))
+    if st != 0:
+        raise BzhError(st, lib().bzh_strerror(st).decode())
+    return out[:olen.value].tobytes()
+
+
+def index_blob_read_raw(blob, max_entries, max_pts):
+    """one bzh_index_blob_read call with arrays of the given room -> (status, entries, points, count, npts, interval, consumed);
+    nothing is raised, the arrays are cut to the counts only on status 0"""
+    a = np.frombuffer(bytes(blob), dtype=np.uint8)
+    ent = np.zeros(max(max_entries, 1), dtype=INDEX_DTYPE)
+    pts = np.zeros(max(max_pts, 1), dtype=SYNC_DTYPE)
+    cnt, npts, iv, cons = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
+    st = lib().bzh_index_blob_read(ptr(a) if a.size else ptr(np.zeros(1, np.uint8)), a.size,
+                                   ent.ctypes.data_as(idxp) if max_entries else None, max_entries, ctypes.byref(cnt),
+                                   pts.ctypes.data_as(syncp) if max_pts else None, max_pts, ctypes.byref(npts), ctypes.byref(iv),
+                                   ctypes.byref(cons))
+    if st == 0:
+        ent, pts = ent[:cnt.value], pts[:npts.value]
+    return st, ent, pts, int(cnt.value), int(npts.value), int(iv.value), int(cons.value)
+
+
+def index_blob_read(blob):
+    """bzh_index_blob_read (pure host): (entries, points, interval, consumed) of an index file of either kind (a block index:
+    no points, interval 0); BzhError -6 for what is not a whole, undamaged blob"""
+    st, ent, pts, cnt, npts, iv, cons = index_blob_read_raw(blob, 0, 0)  # (sizes; an empty index is read by this call)
+    if st == -4:
+        st, ent, pts, cnt, npts, iv, cons = index_blob_read_raw(blob, cnt, npts)
+    if st != 0:
+        raise BzhError(st, lib().bzh_strerror(st).decode())
+    return ent.copy(), pts.copy(), iv, cons
 
 
 def index_span(entries, off, length):
@@ -1070,6 +1117,40 @@ class Context:
 
     def stream_consumed(self):
         return int(lib().bzh_stream_consumed(self._h))
+
+    def stream_begin_index(self, interval, chunk_bytes=None):
+        """bzh_stream_begin_index: stream_begin for a stream that records its index (interval 0: entries only)"""
+        if chunk_bytes is not None:
+            self.check(lib().bzh_stream_set_chunk(self._h, chunk_bytes))
+        self.check(lib().bzh_stream_begin_index(self._h, interval))
+        if not hasattr(self, "_sbuf"):
+            self._sbuf = None
+
+    def stream_index_pending(self):
+        """bzh_stream_index_pending -> (entries, sync points) that are final and not yet taken"""
+        cnt, npts = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        self.check(lib().bzh_stream_index_pending(self._h, ctypes.byref(cnt), ctypes.byref(npts)))
+        return int(cnt.value), int(npts.value)
+
+    def stream_index_take_raw(self, max_entries, max_pts):
+        """one bzh_stream_index_take call with arrays of the given room -> (status, entries, points, count, npts); nothing is
+        raised, the arrays are cut to the counts only on status 0"""
+        ent = np.empty(max(max_entries, 1), dtype=INDEX_DTYPE)
+        pts = np.empty(max(max_pts, 1), dtype=SYNC_DTYPE)
+        cnt, npts = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        st = lib().bzh_stream_index_take(self._h, ent.ctypes.data_as(idxp) if max_entries else None, max_entries, ctypes.byref(cnt),
+                                         pts.ctypes.data_as(syncp) if max_pts else None, max_pts, ctypes.byref(npts))
+        if st == 0:
+            ent, pts = ent[:cnt.value], pts[:npts.value]
+        return st, ent, pts, int(cnt.value), int(npts.value)
+
+    def stream_index_take(self):
+        """bzh_stream_index_take, sized by bzh_stream_index_pending -> (entries as an array of INDEX_DTYPE, points as an array
+        of SYNC_DTYPE): what has become final since the last take, in stream coordinates"""
+        ne, npt = self.stream_index_pending()
+        st, ent, pts, _, _ = self.stream_index_take_raw(ne, npt)
+        self.check(st)
+        return ent.copy(), pts.copy()
 
     # ---- streaming decode (bzh_dstream_*) ----
     def dstream_set_room(self, window=0, staging=0):

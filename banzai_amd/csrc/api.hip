@@ -19,6 +19,7 @@
 #include "decode_recover_plan.h"
 #include "encode_plan.h"
 #include "recover_gather.h"
+#include "stream_index.h"
 
 static void stream_join(bzh_ctx *ctx); // waits for a streaming pass in flight (defined with bzh_stream_*)
 
@@ -2178,10 +2179,15 @@ static void stream_join(bzh_ctx *ctx)
     if (s.worker.joinable()) s.worker.join();
 }
 
-extern "C" int bzh_stream_begin(bzh_ctx *ctx)
+// bzh_stream_begin, bzh_stream_begin_index (`index`: the stream records its index, with sync points every `interval` groups)
+static int stream_begin(bzh_ctx *ctx, bool index, uint32_t interval)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (!ctx) return BZH_E_ARG;
+    if (interval > 32767) {
+        bzh_set_error(ctx, "stream index: a sync interval of %u groups, outside 0..32767", interval);
+        return BZH_E_ARG;
+    }
     auto &s = ctx->strm;
     stream_join(ctx);
     s.inflight = false;
@@ -2194,8 +2200,62 @@ extern "C" int bzh_stream_begin(bzh_ctx *ctx)
     s.carry_word = 0;
     s.stream_crc = 0;
     s.consumed = 0;
+    s.index = index;
+    s.interval = interval;
+    s.ix_entries.clear();
+    s.ix_pts.clear();
+    s.ix_blocks = 0;
     return BZH_OK;
     });
+}
+
+extern "C" int bzh_stream_begin(bzh_ctx *ctx) { return stream_begin(ctx, false, 0); }
+
+// ---- the streaming encoder records its index (stream_index.h) --------------------------------------------------------------
+extern "C" int bzh_stream_begin_index(bzh_ctx *ctx, uint32_t interval) { return stream_begin(ctx, true, interval); }
+
+// (No join: the fields read here belong to the feeding thread; the pass in flight fills strm.pass alone.)
+extern "C" int bzh_stream_index_pending(const bzh_ctx *ctx, size_t *count, size_t *npts)
+{
+    if (!ctx) return BZH_E_ARG;
+    if (count) *count = ctx->strm.ix_entries.size();
+    if (npts) *npts = ctx->strm.ix_pts.size();
+    return BZH_OK;
+}
+
+extern "C" int bzh_stream_index_take(bzh_ctx *ctx, bzh_index_entry *idx, size_t max, size_t *count, bzh_sync_point *pts, size_t max_pts,
+                                     size_t *npts)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (!ctx || !count || !npts || (!idx && max) || (!pts && max_pts)) return BZH_E_ARG;
+    auto &s = ctx->strm;
+    *count = 0;
+    *npts = 0;
+    if (!s.index) {
+        bzh_set_error(ctx, "stream index: the stream was not begun with bzh_stream_begin_index");
+        return BZH_E_STATE;
+    }
+    if (!bzs_take(s.ix_entries, s.ix_pts, idx, max, count, pts, max_pts, npts)) {
+        bzh_set_error(ctx, "stream index: %zu entries and %zu sync points pending, room for %zu and %zu", *count, *npts, max, max_pts);
+        return BZH_E_CAP;
+    }
+    return BZH_OK;
+    });
+}
+
+// ---- index files: host only, no context (stream_index.h) -------------------------------------------------------------------
+extern "C" size_t bzh_index_blob_size(size_t count, size_t npts, uint32_t interval) { return bzs_blob_size(count, npts, interval); }
+
+extern "C" int bzh_index_blob_write(const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts, size_t npts, uint32_t interval,
+                                    uint64_t consumed, uint8_t *out, size_t cap, size_t *out_len)
+{
+    return bzs_blob_write(idx, count, pts, npts, interval, consumed, out, cap, out_len);
+}
+
+extern "C" int bzh_index_blob_read(const uint8_t *blob, size_t n, bzh_index_entry *idx, size_t max, size_t *count, bzh_sync_point *pts,
+                                   size_t max_pts, size_t *npts, uint32_t *interval, uint64_t *consumed)
+{
+    return bzs_blob_read(blob, n, idx, max, count, pts, max_pts, npts, interval, consumed);
 }
 
 extern "C" size_t bzh_stream_bound(const bzh_ctx *ctx, size_t n)
@@ -2254,6 +2314,8 @@ static void stream_pass(bzh_ctx *ctx)
     p.out_bytes = 0;
     p.lastw = 0;
     p.crcs.clear();
+    p.entries.clear();
+    p.pts.clear();
     p.rc = bzh_guard(ctx, [&]() -> int {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
@@ -2277,7 +2339,12 @@ static void stream_pass(bzh_ctx *ctx)
         uint32_t seed;
         memcpy(&seed, seed_be, 4);
         stats_begin(ctx);
-        BZH_TRY(encode_range(ctx, 0, F, d_o, s.d_out[p.obuf].cap & ~(size_t)3, p.phase, &p.nbits, p.phase ? &seed : nullptr));
+        EncIndex ix{s.interval, {}, {}};
+        if (s.index) BZH_TRY(rle1_plan_crc_join(ctx)); // (the entries carry the block CRCs, as in encode_device_impl)
+        BZH_TRY(encode_range(ctx, 0, F, d_o, s.d_out[p.obuf].cap & ~(size_t)3, p.phase, &p.nbits, p.phase ? &seed : nullptr, nullptr,
+                             s.index ? &ix : nullptr));
+        p.entries.swap(ix.entries);
+        p.pts.swap(ix.pts);
         const uint64_t bits_in_buf = p.phase + p.nbits;
         const size_t full_words = (size_t)(bits_in_buf / 32);
         BZH_TRY(s.h_out.reserve(ctx, 4096, "a pass's last word"));
@@ -2374,6 +2441,14 @@ extern "C" int bzh_stream_feed(bzh_ctx *ctx, const uint8_t *in, size_t n, int eo
             return p.rc;
         }
         if (p.out_bytes) done[ndone++] = {p.obuf, p.out_bytes};
+        if (s.index && !p.entries.empty()) { // the pass's entries and points, in stream coordinates, behind what is pending
+            const size_t e0 = s.ix_entries.size(), p0 = s.ix_pts.size();
+            s.ix_entries.insert(s.ix_entries.end(), p.entries.begin(), p.entries.end());
+            s.ix_pts.insert(s.ix_pts.end(), p.pts.begin(), p.pts.end());
+            bzs_rebase(bzs_base(s.bitpos, s.consumed, s.ix_blocks), s.ix_entries.data() + e0, p.entries.size(), s.ix_pts.data() + p0,
+                       p.pts.size());
+            s.ix_blocks += p.entries.size();
+        }
         if (p.nbits) {
             s.carry_word = p.lastw;
             s.bitpos += p.nbits;

@@ -4,10 +4,14 @@
 // No compression logic lives here: the input is fed to bzh_stream_feed in 16 MiB reads (like
 // the reference's BufRead loop, memory stays bounded, pipes and inputs larger than memory work, and reading
 // overlaps with the GPU passes) and the stream bytes are written as they become final.
+// Random access: --index writes the index the streaming encoder records beside the stream (bzh_stream_begin_index),
+// --make-index builds one for an existing .bz2 (bzh_decode_index_sync), -d --index --range reads byte ranges of the decoded
+// data from just the compressed bytes that hold them (bzh_index_spans, bzh_decode_ranges); the files are bzh_index_blob_*'s.
 #include <cstdio>
 #include <cstdlib>
 #include <cerrno>
 #include <cstring>
+#include <sys/stat.h>
 #include <memory>
 #include <new>
 #include <string>
@@ -44,6 +48,13 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "     --decompress or  -d    decode <input_path> (one or more .bz2 streams) instead\n"
             "     --stream               with -d: decode in fixed-size buffers, writing as bytes arrive\n"
             "     --recover              decode every block of a damaged <input_path> that still verifies\n"
+            "     --index <path>         compressing: also write the index of the stream to <path>;\n"
+            "                            with -d and --range: the index of <input_path> to read by\n"
+            "     --interval <n>         with --index while compressing, or --make-index: a sync point every <n>\n"
+            "                            groups of 50 symbols inside each block (default 256; 0: blocks only)\n"
+            "     --make-index <path>    write the index of <input_path> (a .bz2) to <path>; nothing is decoded\n"
+            "                            to an output, and the input is kept\n"
+            "     --range <off>:<len>    with -d --index: write only these bytes of the decoded data; may repeat\n"
             "     --keep      or   -k    keep the input file\n"
             "     --remove    or   -r    remove the input file\n\n"
             "     -1 to -9               block size in 100 kB units (default -9)\n"
@@ -64,7 +75,15 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "     -d --stream takes the paths and the keep / remove policy of -d and bounded memory whatever\n"
             "     the sizes: a pipe is decoded as it arrives.  On a damaged input the exit status is -d's\n"
             "     and a partial output FILE is removed; on standard out the bytes decoded so far -- whole\n"
-            "     blocks in front of the defect, their CRCs verified -- have been written.  GPU: $BZHIP_DEVICE (default 0), or\n"
+            "     blocks in front of the defect, their CRCs verified -- have been written.\n"
+            "     --index while compressing holds the index in memory (40 bytes a block, 288 bytes a sync\n"
+            "     point: some 2 %% of the input at the default interval) and writes the file once, at the\n"
+            "     end; it runs on one GPU.  -d --index --range needs --output or --stdout and a regular\n"
+            "     file as input, of which it reads only the bytes from the first block a range touches to\n"
+            "     the last; the ranges' bytes are written back to back in the order given, each clipped to\n"
+            "     the decoded size, and the input is kept.  An index file that is not a whole, undamaged\n"
+            "     index is a filesystem error; one that does not fit the input exits as -d does for a\n"
+            "     damaged input.  GPU: $BZHIP_DEVICE (default 0), or\n"
             "     $BZHIP_DEVICES=0,1,2,... to spread the blocks over several GPUs of this node;\n"
             "     BZHIP_HUFFMAN=fixed: 2-6 Huffman tables with refinement (smaller, not banzai's exact bytes).\n\n%s\n",
             VERSION);
@@ -76,8 +95,24 @@ const char *VERSION = "version alpha 0.3.1-hip";
 int main(int argc, char **argv)
 {
     if (argc <= 1) usage(false);
-    enum { ANY, NOARGS, OUTPATH } expect = ANY;
-    std::string in_path, out_path;
+    enum { ANY, NOARGS, OUTPATH, IDXPATH, MKIDXPATH, INTERVAL, RANGE } expect = ANY;
+    std::string in_path, out_path, index_path, mkindex_path;
+    bool interval_given = false;
+    uint32_t interval = 256;
+    std::vector<bzh_range> ranges;
+    // a decimal number of at most 20 digits that fits 64 bits, nothing else
+    auto number = [](const std::string &t, uint64_t *v) {
+        if (t.empty() || t.size() > 20) return false;
+        uint64_t x = 0;
+        for (char ch : t) {
+            if (ch < '0' || ch > '9') return false;
+            const uint64_t d = (uint64_t)(ch - '0');
+            if (x > (UINT64_MAX - d) / 10) return false;
+            x = x * 10 + d;
+        }
+        *v = x;
+        return true;
+    };
     bool have_in = false, in_stdin = false, out_stdout = false, have_out = false;
     int keep = -1, level = 9;
     bool decompress = false, recover = false, level_given = false, dstream = false;
@@ -99,6 +134,26 @@ int main(int argc, char **argv)
             if (!a.empty() && a[0] == '-') die(ERR_ARGS, "Argument '--output' requires a file path");
             set_output(a, false);
             expect = ANY;
+        } else if (expect == IDXPATH || expect == MKIDXPATH) {
+            const char *opt = expect == IDXPATH ? "--index" : "--make-index";
+            std::string &dst = expect == IDXPATH ? index_path : mkindex_path;
+            if (a.empty() || a[0] == '-') die(ERR_ARGS, std::string("Argument '") + opt + "' requires a file path");
+            if (!dst.empty()) die(ERR_ARGS, std::string("'") + opt + "' may be given once");
+            dst = a;
+            expect = ANY;
+        } else if (expect == INTERVAL) {
+            uint64_t v = 0;
+            if (!number(a, &v) || v > 32767) die(ERR_ARGS, "Argument '--interval' requires a number of groups, 0 to 32767");
+            interval = (uint32_t)v;
+            interval_given = true;
+            expect = ANY;
+        } else if (expect == RANGE) {
+            const size_t colon = a.find(':');
+            bzh_range r{0, 0};
+            if (colon == std::string::npos || !number(a.substr(0, colon), &r.off) || !number(a.substr(colon + 1), &r.len))
+                die(ERR_ARGS, "Argument '--range' requires <offset>:<length>, both in bytes");
+            ranges.push_back(r);
+            expect = ANY;
         } else if (expect == ANY && a.rfind("--", 0) == 0) {
             if (a == "--help") usage(true);
             else if (a == "--version") die(SUCCESS, VERSION);
@@ -116,6 +171,10 @@ int main(int argc, char **argv)
             else if (a == "--fast") level = 1, level_given = true;
             else if (a == "--best") level = 9, level_given = true;
             else if (a == "--output") expect = OUTPATH;
+            else if (a == "--index") expect = IDXPATH;
+            else if (a == "--make-index") expect = MKIDXPATH;
+            else if (a == "--interval") expect = INTERVAL;
+            else if (a == "--range") expect = RANGE;
             else if (a == "--stdout") set_output("", true);
             else if (a == "--") expect = NOARGS;
             else die(ERR_ARGS, "Unrecognised argument " + a);
@@ -138,14 +197,154 @@ int main(int argc, char **argv)
             set_input(a, false);
         }
     }
+    if (expect == IDXPATH || expect == MKIDXPATH) die(ERR_ARGS, "Arguments '--index' and '--make-index' require a file path");
+    if (expect == INTERVAL) die(ERR_ARGS, "Argument '--interval' requires a number of groups, 0 to 32767");
+    if (expect == RANGE) die(ERR_ARGS, "Argument '--range' requires <offset>:<length>, both in bytes");
     if (!have_in) die(ERR_ARGS, "An input must be specified");
+    const bool by_range = !ranges.empty(), make_index = !mkindex_path.empty();
+    if (by_range && index_path.empty()) die(ERR_ARGS, "'--range' needs the '--index' of the input");
+    if (by_range && (dstream || recover)) die(ERR_ARGS, "'--range' goes with neither '--stream' nor '--recover'");
+    if (by_range && !decompress) die(ERR_ARGS, "'--range' goes with '--decompress'");
+    if (by_range && in_stdin) die(ERR_ARGS, "'--range' reads parts of a file: standard in cannot be the input");
+    if (by_range && !have_out) die(ERR_ARGS, "'--range' needs '--output' or '--stdout'");
+    if (!index_path.empty() && !by_range && (decompress || recover)) die(ERR_ARGS, "With '--decompress' an '--index' is read by '--range'; '--recover' takes none");
+    if (make_index && (decompress || recover || dstream || have_out || !index_path.empty() || level_given))
+        die(ERR_ARGS, "'--make-index' takes an input, a path and '--interval', nothing else");
+    if (interval_given && !make_index && (index_path.empty() || decompress)) die(ERR_ARGS, "'--interval' goes with '--make-index', or with '--index' while compressing");
     if (recover && decompress) die(ERR_ARGS, "'--recover' and '--decompress' exclude each other");
     if (dstream && recover) die(ERR_ARGS, "'--stream' and '--recover' exclude each other");
     if (dstream && !decompress) die(ERR_ARGS, "'--stream' goes with '--decompress'");
     if (recover && level_given) die(ERR_ARGS, "'--recover' takes no block size: a block is held to what the format allows");
 
+    // a whole file -> memory (the index files, the input of --make-index)
+    auto slurp = [](FILE *f, std::vector<uint8_t> &data) {
+        std::unique_ptr<uint8_t[]> buf(new uint8_t[(size_t)16 << 20]);
+        for (;;) {
+            const size_t k = fread(buf.get(), 1, (size_t)16 << 20, f);
+            data.insert(data.end(), buf.get(), buf.get() + k);
+            if (k < ((size_t)16 << 20)) return !ferror(f);
+        }
+    };
+    // entries, points, interval, consumed -> an index file; -> what went wrong ("" = nothing)
+    auto write_index = [](const std::string &path, const std::vector<bzh_index_entry> &ent, const std::vector<bzh_sync_point> &pts,
+                          uint32_t iv, uint64_t consumed) -> std::string {
+        const size_t need = bzh_index_blob_size(ent.size(), pts.size(), iv);
+        std::unique_ptr<uint8_t[]> blob(need ? new (std::nothrow) uint8_t[need] : nullptr);
+        size_t got = 0;
+        if (!blob || bzh_index_blob_write(ent.data(), ent.size(), pts.data(), pts.size(), iv, consumed, blob.get(), need, &got) != BZH_OK)
+            return "the index does not fit in memory";
+        FILE *xf = fopen(path.c_str(), "wb");
+        if (!xf) return "cannot create " + path + ": " + strerror(errno);
+        const bool ok = fwrite(blob.get(), 1, got, xf) == got;
+        if (fclose(xf) != 0 || !ok) {
+            remove(path.c_str());
+            return "write to " + path + " failed";
+        }
+        return "";
+    };
+
+    if (by_range) { // -d --index --range: the index file, the hull of the touched blocks' bytes, one bzh_decode_ranges
+        const char *doing = "error during decompression: ";
+        std::vector<uint8_t> blob;
+        FILE *xf = fopen(index_path.c_str(), "rb");
+        if (!xf) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + index_path + ": " + strerror(errno));
+        const bool xok = slurp(xf, blob);
+        fclose(xf);
+        if (!xok) die(ERR_FILESYSTEM, "[filesystem error] cannot read " + index_path);
+        static const uint8_t none = 0;
+        size_t count = 0, npts = 0;
+        uint32_t iv = 0;
+        uint64_t consumed = 0;
+        int rs = bzh_index_blob_read(blob.empty() ? &none : blob.data(), blob.size(), nullptr, 0, &count, nullptr, 0, &npts, &iv, &consumed);
+        std::vector<bzh_index_entry> ent(count);
+        std::vector<bzh_sync_point> pts(npts);
+        if (rs == BZH_E_CAP) rs = bzh_index_blob_read(blob.data(), blob.size(), ent.data(), count, &count, pts.data(), npts, &npts, &iv, &consumed);
+        if (rs != BZH_OK) die(ERR_FILESYSTEM, "[filesystem error] " + index_path + " is not a whole, undamaged index file");
+        blob = std::vector<uint8_t>();
+        struct stat sb;
+        if (stat(in_path.c_str(), &sb) != 0) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + in_path + ": " + strerror(errno));
+        if (!S_ISREG(sb.st_mode)) die(ERR_ARGS, "'--range' reads parts of a regular file: " + in_path + " is none");
+        FILE *rf = fopen(in_path.c_str(), "rb");
+        if (!rf) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + in_path + ": " + strerror(errno));
+        std::vector<uint32_t> touched(count);
+        size_t ntouched = 0;
+        uint64_t lo = 0, hi = 0, total = 0;
+        rs = bzh_index_spans(ent.data(), count, ranges.data(), ranges.size(), touched.data(), touched.size(), &ntouched, &lo, &hi, &total);
+        if (rs != BZH_OK) die(ERR_OUTPUT, std::string(doing) + bzh_strerror(rs));
+        if (hi < lo || hi > (uint64_t)sb.st_size) // (before anything is sized by them)
+            die(ERR_OUTPUT, std::string(doing) + "the index names bytes behind the end of " + in_path + ": it is not this file's");
+        const size_t span = (size_t)(hi - lo);
+        std::unique_ptr<uint8_t[]> comp(new (std::nothrow) uint8_t[span ? span : 1]), out(new (std::nothrow) uint8_t[total ? total : 1]);
+        if (!comp || !out) die(ERR_OUTPUT, std::string(doing) + "out of memory");
+        if (span) {
+            if (fseeko(rf, (off_t)lo, SEEK_SET) != 0 || fread(comp.get(), 1, span, rf) != span) die(ERR_OUTPUT, std::string(doing) + "read failed");
+        }
+        fclose(rf);
+        size_t got = 0;
+        if (ntouched) {
+            const char *dv = getenv("BZHIP_DEVICE");
+            bzh_ctx *rctx = nullptr;
+            rs = bzh_create(&rctx, dv ? atoi(dv) : 0, 9, 0);
+            if (rs != BZH_OK) die(ERR_OUTPUT, std::string(doing) + bzh_strerror(rs));
+            std::vector<size_t> offs(ranges.size()), lens(ranges.size());
+            rs = bzh_decode_ranges(rctx, comp.get(), span, lo, ent.data(), count, pts.data(), npts, ranges.data(), ranges.size(), out.get(),
+                                   (size_t)total, offs.data(), lens.data(), &got);
+            if (rs != BZH_OK) { // (no output is created)
+                const std::string msg = std::string(doing) + bzh_strerror(rs) + ": " + bzh_last_error(rctx);
+                bzh_destroy(rctx);
+                die(ERR_OUTPUT, msg);
+            }
+            bzh_destroy(rctx);
+        }
+        FILE *df = stdout;
+        if (!out_stdout) {
+            df = fopen(out_path.c_str(), "wb");
+            if (!df) die(ERR_FILESYSTEM, "[filesystem error] cannot create " + out_path + ": " + strerror(errno));
+        }
+        if (got && fwrite(out.get(), 1, got, df) != got) die(ERR_OUTPUT, std::string(doing) + "write failed");
+        if (fflush(df) != 0) die(ERR_OUTPUT, std::string(doing) + "write failed");
+        if (df != stdout) fclose(df);
+        return SUCCESS; // (the input is kept: a part of it was read)
+    }
+
     FILE *inf = in_stdin ? stdin : fopen(in_path.c_str(), "rb");
     if (!inf) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + in_path + ": " + strerror(errno));
+
+    if (make_index) { // the whole input in memory, a level-9 context, bzh_decode_index[_sync]: sized by a guess, then by what it reports
+        const char *doing = "error during indexing: ";
+        std::vector<uint8_t> data;
+        if (!slurp(inf, data)) die(ERR_OUTPUT, std::string(doing) + "read failed");
+        if (!in_stdin) fclose(inf);
+        const char *dv = getenv("BZHIP_DEVICE");
+        bzh_ctx *xctx = nullptr;
+        int xs = bzh_create(&xctx, dv ? atoi(dv) : 0, 9, 0);
+        if (xs != BZH_OK) die(ERR_OUTPUT, std::string(doing) + bzh_strerror(xs));
+        static const uint8_t none = 0;
+        const size_t n = data.size();
+        std::vector<bzh_index_entry> ent(n / 1000 + 64);
+        std::vector<bzh_sync_point> pts(interval ? n / 8 / interval + 64 : 0);
+        size_t count = 0, npts = 0, consumed = 0;
+        uint64_t total = 0;
+        for (int attempt = 0; attempt < 2; attempt++) {
+            xs = interval ? bzh_decode_index_sync(xctx, n ? data.data() : &none, n, interval, ent.data(), ent.size(), &count, pts.data(),
+                                                  pts.size(), &npts, &total, &consumed)
+                          : bzh_decode_index(xctx, n ? data.data() : &none, n, ent.data(), ent.size(), &count, &total, &consumed);
+            if (xs != BZH_E_CAP) break;
+            if (count > ent.size()) ent.resize(count);
+            if (npts > pts.size()) pts.resize(npts);
+        }
+        if (xs != BZH_OK) {
+            const std::string msg = std::string(doing) + bzh_strerror(xs) + ": " + bzh_last_error(xctx);
+            bzh_destroy(xctx);
+            die(ERR_OUTPUT, msg);
+        }
+        bzh_destroy(xctx);
+        ent.resize(count);
+        pts.resize(npts);
+        const std::string bad = write_index(mkindex_path, ent, pts, interval, consumed);
+        if (!bad.empty()) die(ERR_FILESYSTEM, "[filesystem error] " + bad);
+        return SUCCESS; // (the input is kept)
+    }
 
     if (decompress || recover) { // the whole input in memory, a level-9 context, one call (more where a size guess was short); --stream: neither
         const char *doing = recover ? "error during recovery: " : "error during decompression: ";
@@ -318,7 +517,7 @@ int main(int argc, char **argv)
             if (*e && *e != ',') break;
         }
         const char *hm = getenv("BZHIP_HUFFMAN");
-        if (devices.size() > 1 && !(hm && std::string(hm) == "fixed")) {
+        if (devices.size() > 1 && !(hm && std::string(hm) == "fixed") && index_path.empty()) { // (an index comes from the streaming path)
             std::vector<uint8_t> data;
             std::unique_ptr<uint8_t[]> buf(new uint8_t[(size_t)16 << 20]);
             for (;;) {
@@ -369,8 +568,14 @@ int main(int argc, char **argv)
         st = bzh_set_mode(ctx, BZH_MODE_FIXED);
         if (st != BZH_OK) fail(bzh_strerror(st));
     }
-    st = bzh_stream_begin(ctx);
+    const bool with_index = !index_path.empty();
+    st = with_index ? bzh_stream_begin_index(ctx, interval) : bzh_stream_begin(ctx);
     if (st != BZH_OK) fail(bzh_strerror(st));
+    // --index: what every feed made final is taken at once, so the library holds one pass's worth; the whole index waits here
+    // and is written once, at the end (the file's header holds the counts and a CRC over everything)
+    std::vector<bzh_index_entry> ix_ent;
+    std::vector<bzh_sync_point> ix_pts;
+    uint64_t written = 0;
     const size_t CHUNK = (size_t)16 << 20;
     // plain arrays, not vectors: the output bound is a worst case of a few hundred megabytes of which a feed fills a
     // fraction -- value-initialising it (and copying it when it grows) cost more than encoding a 100 MB file
@@ -393,8 +598,23 @@ int main(int argc, char **argv)
         st = bzh_stream_feed(ctx, in.get(), k, eof ? 1 : 0, out.get(), out_cap, &got);
         if (st != BZH_OK) fail(std::string(bzh_strerror(st)) + ": " + bzh_last_error(ctx));
         if (got && fwrite(out.get(), 1, got, outf) != got) fail("write failed");
+        written += got;
+        if (with_index) {
+            size_t ne = 0, np = 0;
+            st = bzh_stream_index_pending(ctx, &ne, &np);
+            if (st != BZH_OK) fail(bzh_strerror(st));
+            const size_t e0 = ix_ent.size(), p0 = ix_pts.size();
+            ix_ent.resize(e0 + ne);
+            ix_pts.resize(p0 + np);
+            st = bzh_stream_index_take(ctx, ix_ent.data() + e0, ne, &ne, ix_pts.data() + p0, np, &np);
+            if (st != BZH_OK) fail(std::string(bzh_strerror(st)) + ": " + bzh_last_error(ctx));
+        }
     }
     bzh_destroy(ctx);
+    if (with_index) {
+        const std::string bad = write_index(index_path, ix_ent, ix_pts, interval, written);
+        if (!bad.empty()) die(ERR_FILESYSTEM, "[filesystem error] " + bad);
+    }
     if (!in_stdin) fclose(inf);
     if (fflush(outf) != 0) die(ERR_OUTPUT, "error during compression: write failed");
     if (outf != stdout) fclose(outf);

@@ -216,7 +216,16 @@ struct bzh_ctx {
             size_t out_bytes = 0;       // whole words copied to h_out
             uint32_t lastw = 0;         // the partial word after them (big-endian value)
             std::vector<uint32_t> crcs; // CRCs of the final blocks, in order
+            std::vector<bzh_index_entry> entries; // an indexed stream: the final blocks' entries and sync points, in the
+            std::vector<bzh_sync_point> pts;      // PASS's coordinates (the feed that collects the pass rebases them: stream_index.h)
         } pass;
+        // bzh_stream_begin_index: the stream records its index.  What the collected passes found waits here, in stream
+        // coordinates, until bzh_stream_index_take moves it out (kept after a failure and after eof, dropped by the next begin).
+        bool index = false;
+        uint32_t interval = 0;
+        std::vector<bzh_index_entry> ix_entries;
+        std::vector<bzh_sync_point> ix_pts;
+        uint64_t ix_blocks = 0;         // blocks of the collected passes: taken + pending
         PinnedBuf h_out;                // pinned: the partial last word of a pass's output
         // A pass leaves its bits on the device (two buffers, alternating): the next pass is started first, then the
         // finished one's words go straight to the caller's buffer while the GPU is already at work again.

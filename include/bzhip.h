@@ -531,6 +531,55 @@ BZH_API int bzh_stream_set_chunk(bzh_ctx *ctx, size_t bytes);
 /* Input bytes encoded so far (after the eof feed: the total, encode()'s return value). */
 BZH_API size_t bzh_stream_consumed(const bzh_ctx *ctx);
 
+/* ---- the streaming encoder records its index: bzh_encode_index for inputs that are never resident as a whole ---------- */
+
+/* bzh_stream_begin that also records the index of the stream being written: entries, and with interval in 1..32767 the sync
+ * points of bzh_encode_index at that interval.  interval 0: entries only.  interval > 32767: BZH_E_ARG (the stream the context
+ * had stays as it was).  The feeds, bzh_stream_bound, bzh_stream_set_chunk and bzh_stream_consumed are used as after
+ * bzh_stream_begin, and the stream bytes are the same, whatever the chunking, in either Huffman mode.
+ * Entries and points become FINAL when a feed collects the pass that encoded their blocks; after the eof feed everything is.
+ * They are in STREAM coordinates, whatever the pass: bit_pos / end_bit count from bit 0 of the stream (the last block's end_bit
+ * is the bit of the footer magic), out_off from byte 0 of the input, a point's entry is the block's number in the stream.  The
+ * concatenation of everything taken equals, byte for byte, the arrays bzh_encode_index returns for the whole input at that
+ * interval -- which are bzh_decode_index_sync's for the stream.  With an index a pass runs on ONE lane (bzh_set_lanes does not
+ * apply), as bzh_encode_index does. */
+BZH_API int bzh_stream_begin_index(bzh_ctx *ctx, uint32_t interval);
+
+/* Entries and points that have become final and were not yet taken (both may be null).  A stream without index has none. */
+BZH_API int bzh_stream_index_pending(const bzh_ctx *ctx, size_t *count, size_t *npts);
+
+/* Moves them out, in order.  Either array too small: BZH_E_CAP, *count / *npts set, nothing removed.  A stream begun with
+ * bzh_stream_begin (no index), or no stream at all: BZH_E_STATE.  idx may be null when max is 0, pts when max_pts is 0.
+ * Allowed between feeds, after the eof feed and after a failed feed: a failed stream keeps what was pending until the next
+ * begin.  Taking after every feed keeps the context's memory bounded: what waits is 40 bytes a block and 288 bytes per
+ * `interval` x 50 symbols, some 2 % of the input at interval 256. */
+BZH_API int bzh_stream_index_take(bzh_ctx *ctx, bzh_index_entry *idx, size_t max, size_t *count, bzh_sync_point *pts, size_t max_pts,
+                                  size_t *npts);
+
+/* ---- index files: pure host, no context, no GPU ----------------------------------------------------------------------- */
+
+/* The file formats banzai_amd.BlockIndex.to_bytes() and SyncIndex.to_bytes() write, byte for byte.  All fields little-endian:
+ *   interval 0 (block index):  "BZhIDX\r\n" | u32 version 1 | u32 reserved 0 | u64 entries | u64 consumed | the entries (40 bytes each)
+ *   interval 1..32767:         "BZhSYN\r\n" | u32 version 1 | u32 interval | u64 bytes of the block index blob that follows | u64 points
+ *                              | u32 CRC-32 | u32 reserved 0 | that block index blob | the points (288 bytes each)
+ * `consumed` is the length of the indexed stream(s) in bytes (bzh_decode_index's *consumed, bzh_encode's *out_len).  The CRC-32
+ * is zlib's, over the 40 header bytes with the CRC field zero and everything behind them.
+ * bzh_index_blob_size: the bytes of the blob; 0 for an interval above 32767, points with interval 0, or a size beyond size_t. */
+BZH_API size_t bzh_index_blob_size(size_t count, size_t npts, uint32_t interval);
+/* Writes the blob to out[0..*out_len).  BZH_E_ARG: what bzh_index_blob_size answers with 0, a null out_len, a null array with a
+ * count.  BZH_E_CAP: cap is below the size, which *out_len then holds.  The entries and points are written as given: whether
+ * they are well formed is the decode calls' business. */
+BZH_API int bzh_index_blob_write(const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts, size_t npts, uint32_t interval,
+                                 uint64_t consumed, uint8_t *out, size_t cap, size_t *out_len);
+/* Reads a blob of either kind: a block index gives *interval = 0 and *npts = 0.  BZH_E_DATA: neither magic, another version, sizes
+ * that do not add up to n exactly, a non-zero reserved field, an interval outside 1..32767 in a sync index, a CRC mismatch.
+ * BZH_E_CAP: idx or pts is too small; *count and *npts are both set (as are *interval and *consumed), the arrays untouched: size
+ * with one call (max = max_pts = 0, null arrays), fill with a second.  BZH_E_ARG: a null blob, count, npts, interval or
+ * consumed, a null array with room claimed.  A block index blob carries no CRC: damage inside its entries is found by the
+ * decode calls, which check every entry they use against the bytes. */
+BZH_API int bzh_index_blob_read(const uint8_t *blob, size_t n, bzh_index_entry *idx, size_t max, size_t *count, bzh_sync_point *pts,
+                                size_t max_pts, size_t *npts, uint32_t *interval, uint64_t *consumed);
+
 /* ---- streaming decode: bzh_decode fed in chunks, bounded memory ------------------------------------------------ */
 
 /* A stream decode holds a WINDOW of compressed bytes and a STAGING buffer of decoded bytes on the device, both its own (not
