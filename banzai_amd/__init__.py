@@ -45,7 +45,7 @@ import numpy as np
 
 from . import _native
 
-__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex",
+__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex", "RecordIndex", "build_record_index", "record_index_of", "decompress_records",
            "IndexedReader", "build_sync_index", "SyncIndex", "encode_indexed", "encode_indexed_stream", "recover", "recover_stream", "Recovered", "RecoveredBlock", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
@@ -800,6 +800,194 @@ def _subindex(index, ranges):
     return _SubIndex(touched, se, points, sub, runs)
 
 
+class RecordIndex:
+    """A BlockIndex or SyncIndex (`.index`) with a record table beside it (bzh_decode_index_records): `.rec_cum` is a uint64 array
+    of len(index) + 1 words, rec_cum[e] = the `.delim` bytes of the decoded output in front of block e, rec_cum[-1] all of them.
+    Record r is the bytes behind delimiter r up to and with delimiter r + 1 (the delimiter belongs to the record it ends); a
+    last record without a delimiter counts when it is not empty: len() is `.nrecords`.  The table is checked against the bytes by
+    every read that uses it; to_bytes() / from_bytes() refuse what is not a whole, well-formed blob."""
+
+    MAGIC = b"BZhREC\r\n"
+    VERSION = 1
+    _HEAD = struct.Struct("<8sIIQQII")  # magic, version, delim, entries, nrecords, CRC-32 of all the rest, 0
+
+    def __init__(self, index, delim, rec_cum, nrecords):
+        self.index = _index_arg(index)
+        self.delim = _delim_arg(delim)
+        self.rec_cum = np.ascontiguousarray(rec_cum, dtype=np.uint64)
+        self.nrecords = int(nrecords)
+        what = self._ill_formed(self.index.entries, self.rec_cum, self.nrecords, self.index.size)
+        if what:
+            raise ValueError(f"record index: {what}")
+
+    @staticmethod
+    def _ill_formed(e, t, nrecords, total):
+        """what bzh_decode_records refuses a table for, and a record count that cannot belong to it (None: well formed)"""
+        if t.ndim != 1 or t.size != e.size + 1:
+            return f"a table of {t.size} words beside {e.size} entries"
+        if t[0] != 0:
+            return "rec_cum[0] is not 0"
+        if np.any(t[1:] < t[:-1]):
+            return "the counts descend"
+        if np.any(t[1:] - t[:-1] > e["out_len"]):
+            return "more delimiters than an entry has bytes"
+        d = int(t[-1])
+        if nrecords not in ((d,) if total == 0 or d == total else (d, d + 1)):
+            return f"{nrecords} records over {d} delimiters"
+        return None
+
+    # what the wrapped index answers, so that a RecordIndex stands wherever one does
+    @property
+    def entries(self):
+        return self.index.entries
+
+    @property
+    def size(self):
+        return self.index.size
+
+    @property
+    def consumed(self):
+        return self.index.consumed
+
+    def __len__(self):
+        return self.nrecords
+
+    def spans(self, ranges):
+        """(touched, byte_lo, byte_hi): the blocks a read of these (first record, count) ranges decodes, and the hull of their
+        compressed bytes (bzh_record_spans)"""
+        return _native.record_spans(self.entries, self.rec_cum, ranges)
+
+    @classmethod
+    def _crc(cls, head_fields, body):
+        return zlib.crc32(body, zlib.crc32(cls._HEAD.pack(*head_fields, 0, 0)))
+
+    def to_bytes(self):
+        fields = (self.MAGIC, self.VERSION, self.delim, len(self.index), self.nrecords)
+        body = self.index.to_bytes() + self.rec_cum.tobytes()
+        return self._HEAD.pack(*fields, self._crc(fields, body), 0) + body
+
+    @classmethod
+    def from_bytes(cls, blob):
+        view = _bytes_view(blob, "RecordIndex.from_bytes")
+        if len(view) < cls._HEAD.size:
+            raise ValueError("record index: truncated header")
+        magic, version, delim, count, nrecords, crc, zero = cls._HEAD.unpack_from(view, 0)
+        if magic != cls.MAGIC:
+            raise ValueError("record index: bad magic")
+        if version != cls.VERSION:
+            raise ValueError(f"record index: version {version}, this library reads version {cls.VERSION}")
+        if delim > 255:
+            raise ValueError(f"record index: a delimiter of {delim}, no byte value")
+        table = 8 * (count + 1)
+        if count >= len(view) // 8 or len(view) < cls._HEAD.size + table:
+            raise ValueError(f"record index: {len(view)} bytes do not hold a header, an index and a table of {count} entries")
+        if zero != 0 or crc != cls._crc((magic, version, delim, count, nrecords), view[cls._HEAD.size:]):
+            raise ValueError("record index: the blob is damaged (its CRC differs)")
+        inner = view[cls._HEAD.size:len(view) - table]
+        index = (SyncIndex if bytes(inner[:8]) == SyncIndex.MAGIC else BlockIndex).from_bytes(inner)
+        if len(index) != count:
+            raise ValueError(f"record index: a table of {count} entries beside an index of {len(index)}")
+        rec_cum = np.frombuffer(view, dtype=np.uint64, count=count + 1, offset=len(view) - table).copy()
+        return cls(index, delim, rec_cum, nrecords)
+
+
+def _delim_arg(delim):
+    if isinstance(delim, (bytes, bytearray)) and len(delim) == 1:
+        return delim[0]
+    if isinstance(delim, int) and not isinstance(delim, bool) and 0 <= delim <= 255:
+        return delim
+    raise ValueError("delim must be one byte (bytes of length 1, or an int 0..255)")
+
+
+def _record_index_arg(rindex):
+    if not isinstance(rindex, RecordIndex):
+        raise TypeError(f"rindex must be a RecordIndex, not {type(rindex).__name__}")
+    return rindex
+
+
+def build_record_index(data, delim=b"\n", interval=256, device=0):
+    """build_sync_index (interval 0: build_index) that also counts the `delim` bytes of every block (bzh_decode_index_records)
+    -> RecordIndex.  The count is folded from the bytes behind each block's inverse BWT where its CRC is: nothing is expanded."""
+    view = _bytes_view(data, "build_record_index")
+    d = _delim_arg(delim)
+    if isinstance(interval, bool) or not isinstance(interval, int):
+        raise TypeError(f"interval must be an int, not {type(interval).__name__}")
+    if not 0 <= interval <= 32767:
+        raise ValueError(f"interval must be 0 (no sync points) or 1..32767 groups, not {interval}")
+    entries, points, rec_cum, nrecords, _, consumed = _ctx(9, device).decode_index_records(view, interval, d)
+    blocks = BlockIndex(entries, consumed)
+    return RecordIndex(SyncIndex(blocks, points, interval) if interval else blocks, d, rec_cum, nrecords)
+
+
+def record_index_of(raw, index, delim=b"\n", device=0):
+    """The RecordIndex of `index` from the DECODED bytes it indexes -- after encode_indexed the encoder's own input --, as one
+    pass over them at memory bandwidth instead of a decode (bzh_count_records_device).  `raw` is a device tensor of bytes
+    (anything with data_ptr() and numel(), as a torch uint8 tensor on the GPU), or bytes-like, which is uploaded with torch."""
+    index = _index_arg(index)
+    d = _delim_arg(delim)
+    if hasattr(raw, "data_ptr") and hasattr(raw, "numel"):
+        keep, addr, n = raw, int(raw.data_ptr()), int(raw.numel()) * int(raw.element_size())
+    else:
+        import torch
+        view = _bytes_view(raw, "record_index_of")
+        keep = torch.frombuffer(bytearray(view) or bytearray(1), dtype=torch.uint8).to(f"cuda:{device}")
+        addr, n = int(keep.data_ptr()), len(view)
+        torch.cuda.synchronize(device)
+    rec_cum, nrecords = _ctx(9, device).count_records_device(addr, n, index.entries, d)
+    del keep
+    return RecordIndex(index, d, rec_cum, nrecords)
+
+
+def _record_atoms(ranges, nrecords):
+    """Cuts (first, count) ranges of records -- in any order, overlapping, repeated, empty, behind the end -- at every boundary
+    into ascending disjoint atoms, what bzh_decode_records takes.  -> (atoms, spans): atoms is a list of (first, count), spans[r]
+    = (i0, i1) says that range r is atoms[i0:i1] joined.  Everything is clipped at nrecords: the empty tail is no record."""
+    clipped = []
+    for pair in ranges:
+        first, count = pair
+        first, count = _int_arg(first, "first"), _int_arg(count, "count")
+        a = min(first, nrecords)
+        clipped.append((a, min(a + count, nrecords)))
+    cuts = sorted({c for a, b in clipped if a < b for c in (a, b)})
+    at = {c: i for i, c in enumerate(cuts)}
+    covered = [0] * (len(cuts) + 1)  # a difference array over the intervals between the cuts
+    for a, b in clipped:
+        if a < b:
+            covered[at[a]] += 1
+            covered[at[b]] -= 1
+    atoms, atom_of, depth = [], [0] * (len(cuts) + 1), 0
+    for i in range(len(cuts) - 1):
+        depth += covered[i]
+        atom_of[i] = len(atoms)
+        if depth > 0:
+            atoms.append((cuts[i], cuts[i + 1] - cuts[i]))
+    if cuts:
+        atom_of[len(cuts) - 1] = len(atoms)
+    spans = [(atom_of[at[a]], atom_of[at[b]]) if a < b else (0, 0) for a, b in clipped]
+    return atoms, spans
+
+
+def _read_records(rindex, ranges, fetch, device):
+    """decompress_records over `fetch(lo, hi)`, which hands over bytes [lo, hi) of the compressed source"""
+    atoms, spans = _record_atoms(ranges, rindex.nrecords)
+    if not atoms:
+        return [b"" for _ in spans]
+    _, lo, hi = rindex.spans(atoms)
+    blob, offs, lens = _ctx(9, device).decode_records(fetch(lo, hi), rindex.entries, rindex.rec_cum, atoms, _points_arg(rindex.index),
+                                                      in_byte_base=lo, delim=rindex.delim)
+    parts = _split(blob, offs, lens)
+    return [b"".join(parts[i0:i1]) for i0, i1 in spans]
+
+
+def decompress_records(data, rindex, ranges, device=0):
+    """The records of many (first, count) pairs of the indexed `data` in ONE call -> a list of bytes, one per pair in the order
+    given: records first .. first + count - 1, delimiters included, clipped at len(rindex).  The pairs may come in any order,
+    overlap, repeat, be empty or lie behind the end.  Only the blocks that hold them are decoded, each once and verified
+    (bzh_decode_records); the record boundaries are found on the device."""
+    view = _bytes_view(data, "decompress_records")
+    return _read_records(_record_index_arg(rindex), ranges, lambda lo, hi: view[lo:hi], device)
+
+
 class IndexedReader(io.RawIOBase):
     """A seekable, read-only file of the DECODED bytes of `source`: bytes-like, or a seekable binary file holding .bz2
     stream(s).  Every read decodes just the blocks it touches (decompress_range); with a file source it fetches from the file
@@ -820,7 +1008,8 @@ class IndexedReader(io.RawIOBase):
             else:
                 data = self._view
             index = build_index(data, device)
-        self.index = _index_arg(index)
+        self.records = index if isinstance(index, RecordIndex) else None  # (read_records / readv_records need one)
+        self.index = _index_arg(index.index if self.records is not None else index)
         self._device = device
         self._pos = 0
 
@@ -894,6 +1083,30 @@ class IndexedReader(io.RawIOBase):
             parts.append(comp)
         blob, offs, lens = _ctx(9, self._device).decode_ranges(b"".join(parts), sub.entries, sub.ranges, sub.points)
         return _split(blob, offs, lens)
+
+    def readv_records(self, ranges):
+        """The records of many (first, count) pairs in one call (decompress_records) -> a list of bytes in the order given; the
+        position does not move.  The reader must have been given a RecordIndex.  Of a file source only the hull of the touched
+        blocks' compressed bytes is read (bzh_record_spans)."""
+        if self.records is None:
+            raise ValueError("reading by records needs a RecordIndex (build_record_index) as the reader's index")
+
+        def fetch(lo, hi):
+            if self._file is None:
+                return self._view[lo:hi]
+            self._file.seek(lo)
+            comp = self._file.read(hi - lo)
+            if not isinstance(comp, (bytes, bytearray, memoryview)):
+                raise TypeError("source.read() must return bytes")
+            if len(comp) != hi - lo:
+                raise EOFError(f"the source holds {len(comp)} of the {hi - lo} bytes from {lo} on that the index names")
+            return comp
+
+        return _read_records(self.records, ranges, fetch, self._device)
+
+    def read_records(self, first, count):
+        """records first .. first + count - 1 as one bytes object (readv_records of one pair)"""
+        return self.readv_records([(first, count)])[0]
 
     def read(self, n=-1):
         if n is None or n < 0:

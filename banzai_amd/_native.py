@@ -214,6 +214,20 @@ SIGNATURES = {
                                                 ctypes.c_size_t, syncp, ctypes.c_size_t, rangep, ctypes.c_size_t, ctypes.c_void_p,
                                                 ctypes.c_size_t, szp, szp, szp]),
     "bzh_get_decode_ranges_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DecodeRangesStats)]),
+    "bzh_decode_index_records": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint8, idxp, ctypes.c_size_t,
+                                                szp, syncp, ctypes.c_size_t, szp, u64p, ctypes.c_size_t, u64p, u64p, szp]),
+    "bzh_decode_index_records_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint8,
+                                                       idxp, ctypes.c_size_t, szp, syncp, ctypes.c_size_t, szp, u64p, ctypes.c_size_t, u64p,
+                                                       u64p, szp]),
+    "bzh_count_records_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint8, idxp, ctypes.c_size_t,
+                                                u64p, u64p]),
+    "bzh_record_spans": (ctypes.c_int, [idxp, ctypes.c_size_t, u64p, rangep, ctypes.c_size_t, u32p, ctypes.c_size_t, szp, u64p, u64p]),
+    "bzh_decode_records": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64, idxp, ctypes.c_size_t, syncp,
+                                          ctypes.c_size_t, u64p, ctypes.c_uint8, rangep, ctypes.c_size_t, u8p, ctypes.c_size_t, szp, szp,
+                                          szp]),
+    "bzh_decode_records_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, idxp, ctypes.c_size_t,
+                                                 syncp, ctypes.c_size_t, u64p, ctypes.c_uint8, rangep, ctypes.c_size_t, ctypes.c_void_p,
+                                                 ctypes.c_size_t, szp, szp, szp]),
     "bzh_decode_scan": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u64p, u8p, ctypes.c_size_t, szp]),
     "bzh_stream_begin": (ctypes.c_int, [ctypes.c_void_p]),
     "bzh_stream_feed": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, u8p, ctypes.c_size_t, szp]),
@@ -407,6 +421,28 @@ def index_spans(entries, ranges):
     if st != 0:
         raise BzhError(st, lib().bzh_strerror(st).decode())
     return touched[:cnt.value].copy(), int(lo.value), int(hi.value), int(total.value)
+
+
+def _table(entries, rec_cum):
+    """the record table beside `entries` as a contiguous uint64 array of entries + 1 words, and its ctypes pointer"""
+    t = np.ascontiguousarray(rec_cum, dtype=np.uint64)
+    if t.ndim != 1 or t.size != len(entries) + 1:
+        raise ValueError(f"a record table of {t.size} words beside {len(entries)} entries (one more is needed)")
+    return t, t.ctypes.data_as(u64p)
+
+
+def record_spans(entries, rec_cum, ranges):
+    """bzh_record_spans (host arithmetic, no GPU): (touched, byte_lo, byte_hi) -- the entries a read of these (first record,
+    count) ranges must decode, ascending and unique, and the hull of their compressed bytes"""
+    e, p = _entries(entries)
+    t, tp = _table(e, rec_cum)
+    r, rp = _ranges(ranges)
+    cnt, lo, hi = ctypes.c_size_t(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    touched = np.empty(max(int(e.size), 1), dtype=np.uint32)
+    st = lib().bzh_record_spans(p, e.size, tp, rp, r.size, ptr(touched, u32p), e.size, ctypes.byref(cnt), ctypes.byref(lo), ctypes.byref(hi))
+    if st != 0:
+        raise BzhError(st, lib().bzh_strerror(st).decode())
+    return touched[:cnt.value].copy(), int(lo.value), int(hi.value)
 
 
 def lib():
@@ -948,6 +984,91 @@ class Context:
         got = ctypes.c_size_t(0)
         st = lib().bzh_decode_ranges_device(self._h, ctypes.c_void_p(d_in), n, in_byte_base, p, e.size, pp, q.size, rp, r.size,
                                             ctypes.c_void_p(d_out), cap, ptr(offs, szp), ptr(lens, szp), ctypes.byref(got))
+        return st, int(got.value), [int(v) for v in offs[:r.size]], [int(v) for v in lens[:r.size]]
+
+    def decode_index_records(self, data, interval=0, delim=10):
+        """bzh_decode_index_records: decode_index_sync (interval 0: entries only) that also fills the record table ->
+        (entries, points, rec_cum as a uint64 array of entries + 1 words, nrecords, decoded bytes in total, input bytes
+        consumed).  One call sizes the arrays, a second fills them."""
+        a = np.frombuffer(data, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        cnt, npts, used = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        total, nrec = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        st = lib().bzh_decode_index_records(self._h, ptr(src), n, interval, delim, None, 0, ctypes.byref(cnt), None, 0, ctypes.byref(npts),
+                                            None, 0, ctypes.byref(nrec), ctypes.byref(total), ctypes.byref(used))
+        if st != -4:
+            self.check(st)
+        ent = np.empty(cnt.value, dtype=INDEX_DTYPE)
+        pts = np.empty(npts.value, dtype=SYNC_DTYPE)
+        cum = np.zeros(cnt.value + 1, dtype=np.uint64)
+        self.check(lib().bzh_decode_index_records(self._h, ptr(src), n, interval, delim, ent.ctypes.data_as(idxp) if ent.size else None,
+                                                  ent.size, ctypes.byref(cnt), pts.ctypes.data_as(syncp) if pts.size else None, pts.size,
+                                                  ctypes.byref(npts), ptr(cum, u64p), cum.size, ctypes.byref(nrec), ctypes.byref(total),
+                                                  ctypes.byref(used)))
+        return ent[:cnt.value], pts[:npts.value], cum[:cnt.value + 1], int(nrec.value), int(total.value), int(used.value)
+
+    def decode_index_records_device(self, d_in, n, interval, delim, max_entries, max_pts):
+        """bzh_decode_index_records_device on an integer device address, arrays of the given room -> (entries, points, rec_cum,
+        nrecords, total, consumed)"""
+        ent = np.empty(max(max_entries, 1), dtype=INDEX_DTYPE)
+        pts = np.empty(max(max_pts, 1), dtype=SYNC_DTYPE)
+        cum = np.zeros(max_entries + 1, dtype=np.uint64)
+        cnt, npts, used = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        total, nrec = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.check(lib().bzh_decode_index_records_device(self._h, ctypes.c_void_p(d_in), n, interval, delim, ent.ctypes.data_as(idxp),
+                                                         max_entries, ctypes.byref(cnt), pts.ctypes.data_as(syncp), max_pts,
+                                                         ctypes.byref(npts), ptr(cum, u64p), cum.size, ctypes.byref(nrec),
+                                                         ctypes.byref(total), ctypes.byref(used)))
+        return ent[:cnt.value], pts[:npts.value], cum[:cnt.value + 1], int(nrec.value), int(total.value), int(used.value)
+
+    def count_records_device(self, d_raw, n, entries, delim=10):
+        """bzh_count_records_device: the record table of the decoded bytes at the integer device address d_raw under an index
+        of them -> (rec_cum, nrecords)"""
+        e, p = _entries(entries)
+        cum = np.zeros(e.size + 1, dtype=np.uint64)
+        nrec = ctypes.c_uint64(0)
+        self.check(lib().bzh_count_records_device(self._h, ctypes.c_void_p(d_raw), n, delim, p, e.size, ptr(cum, u64p), ctypes.byref(nrec)))
+        return cum, int(nrec.value)
+
+    def decode_records_raw(self, comp, entries, rec_cum, ranges, cap, points=None, in_byte_base=0, delim=10):
+        """one bzh_decode_records call with room for `cap` bytes -> (status, out_total, offsets, lengths, the buffer); nothing
+        is raised, so that a caller can look at the sizes a BZH_E_CAP leaves"""
+        a = np.frombuffer(comp, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        e, p = _entries(entries)
+        t, tp = _table(e, rec_cum)
+        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
+        r, rp = _ranges(ranges)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        offs, lens = np.zeros(max(r.size, 1), dtype=np.uintp), np.zeros(max(r.size, 1), dtype=np.uintp)
+        got = ctypes.c_size_t(0)
+        st = lib().bzh_decode_records(self._h, ptr(src), n, in_byte_base, p, e.size, pp, q.size, tp, delim, rp, r.size, ptr(out), cap,
+                                      ptr(offs, szp), ptr(lens, szp), ctypes.byref(got))
+        return st, int(got.value), [int(v) for v in offs[:r.size]], [int(v) for v in lens[:r.size]], out
+
+    def decode_records(self, comp, entries, rec_cum, ranges, points=None, in_byte_base=0, delim=10):
+        """bzh_decode_records: the bytes of every (first record, count) of `ranges` -- ascending, not overlapping -- in one call
+        -> (bytes of all ranges back to back, their offsets in it, their lengths).  The room is the touched blocks' decoded
+        size, which disjoint ranges never exceed."""
+        e, _ = _entries(entries)
+        touched, _, _ = record_spans(e, rec_cum, ranges)
+        cap = int(e["out_len"][touched.astype(np.int64)].sum(dtype=np.uint64)) if touched.size else 0
+        st, got, offs, lens, out = self.decode_records_raw(comp, e, rec_cum, ranges, cap, points, in_byte_base, delim)
+        self.check(st)
+        return out[:got].tobytes(), offs, lens
+
+    def decode_records_device(self, d_in, n, entries, rec_cum, ranges, d_out, cap, points=None, in_byte_base=0, delim=10):
+        """bzh_decode_records_device on integer device addresses -> (status, out_total, offsets, lengths); not raised"""
+        e, p = _entries(entries)
+        t, tp = _table(e, rec_cum)
+        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
+        r, rp = _ranges(ranges)
+        offs, lens = np.zeros(max(r.size, 1), dtype=np.uintp), np.zeros(max(r.size, 1), dtype=np.uintp)
+        got = ctypes.c_size_t(0)
+        st = lib().bzh_decode_records_device(self._h, ctypes.c_void_p(d_in), n, in_byte_base, p, e.size, pp, q.size, tp, delim, rp, r.size,
+                                             ctypes.c_void_p(d_out), cap, ptr(offs, szp), ptr(lens, szp), ctypes.byref(got))
         return st, int(got.value), [int(v) for v in offs[:r.size]], [int(v) for v in lens[:r.size]]
 
     def decode_ranges_stats(self):

@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include "decode_plan.h"
+#include "decode_records_plan.h"
 #include "decode_recover_plan.h"
 #include "encode_plan.h"
 #include "recover_gather.h"
@@ -1446,8 +1447,16 @@ extern "C" int bzh_dstream_end(bzh_ctx *ctx)
 
 // ---- random access (decode.hip): the index is bzh_decode_device's flow with no output, a range needs neither scan nor chain
 // interval 0: no sync points (bzh_decode_index_device); else bzh_decode_index_sync_device
+// rec: also the record table (bzh_decode_index_records_device)
+struct RecOut {
+    uint8_t delim;
+    uint64_t *rec_cum;
+    size_t max_cum;
+    uint64_t *nrecords;
+};
 static int decode_index_device_impl(bzh_ctx *ctx, const void *d_in, size_t n, uint32_t interval, bzh_index_entry *idx, size_t max, size_t *count,
-                                    bzh_sync_point *pts, size_t max_pts, size_t *npts, uint64_t *out_total, size_t *consumed)
+                                    bzh_sync_point *pts, size_t max_pts, size_t *npts, uint64_t *out_total, size_t *consumed,
+                                    const RecOut *rec = nullptr)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
@@ -1463,7 +1472,10 @@ static int decode_index_device_impl(bzh_ctx *ctx, const void *d_in, size_t n, ui
     std::vector<bzh_index_entry> entries;
     size_t total = 0;
     SyncBuild sync{interval, {}};
-    int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, &entries, interval ? &sync : nullptr);
+    RecBuild rb{rec ? rec->delim : 0u, {}, false};
+    if (rec) *rec->nrecords = 0;
+    int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, &entries, interval ? &sync : nullptr,
+                              rec ? &rb : nullptr);
     rc = decode_call_end(ctx, call, rc);
     if (rc != BZH_OK) return rc;
     *count = entries.size();
@@ -1477,8 +1489,16 @@ static int decode_index_device_impl(bzh_ctx *ctx, const void *d_in, size_t n, ui
         bzh_set_error(ctx, "decode index: %zu sync points, room for %zu", sync.pts.size(), max_pts);
         return BZH_E_CAP;
     }
+    if (rec && entries.size() + 1 > rec->max_cum) {
+        bzh_set_error(ctx, "decode index: a record table of %zu words, room for %zu", entries.size() + 1, rec->max_cum);
+        return BZH_E_CAP;
+    }
     if (!entries.empty()) memcpy(idx, entries.data(), entries.size() * sizeof(bzh_index_entry));
     if (!sync.pts.empty()) memcpy(pts, sync.pts.data(), sync.pts.size() * sizeof(bzh_sync_point));
+    if (rec) {
+        memcpy(rec->rec_cum, rb.cum.data(), rb.cum.size() * sizeof(uint64_t));
+        *rec->nrecords = rb.cum.back() + (total > 0 && !rb.last_is_delim);
+    }
     return BZH_OK;
     });
 }
@@ -1676,6 +1696,129 @@ extern "C" int bzh_decode_ranges(bzh_ctx *ctx, const uint8_t *in, size_t n, uint
     BZH_TRY(decode_stage(ctx, covered ? in + (lo - in_byte_base) : in, un, room));
     const int rc = bzh_decode_ranges_device(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, ranges, nranges,
                                             room ? ctx->d_stage_out : nullptr, room, out_offs, out_lens, out_total);
+    if (rc != BZH_OK) return rc;
+    if (*out_total) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, *out_total, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+    return BZH_OK;
+    });
+}
+
+// ---- records (decode.hip: the count in the chain walk, decode_records_run, count_records_run; the arithmetic: decode_records_plan.h)
+extern "C" int bzh_decode_index_records_device(bzh_ctx *ctx, const void *d_in, size_t n, uint32_t interval, uint8_t delim, bzh_index_entry *idx,
+                                               size_t max, size_t *count, bzh_sync_point *pts, size_t max_pts, size_t *npts, uint64_t *rec_cum,
+                                               size_t max_cum, uint64_t *nrecords, uint64_t *out_total, size_t *consumed)
+{
+    if (!ctx || !npts || !nrecords || (!rec_cum && max_cum)) return BZH_E_ARG;
+    if (interval && !sync_interval_ok(ctx, interval)) return BZH_E_ARG;
+    const RecOut rec{delim, rec_cum, max_cum, nrecords};
+    return decode_index_device_impl(ctx, d_in, n, interval, idx, max, count, pts, max_pts, npts, out_total, consumed, &rec);
+}
+
+extern "C" int bzh_decode_index_records(bzh_ctx *ctx, const uint8_t *in, size_t n, uint32_t interval, uint8_t delim, bzh_index_entry *idx,
+                                        size_t max, size_t *count, bzh_sync_point *pts, size_t max_pts, size_t *npts, uint64_t *rec_cum,
+                                        size_t max_cum, uint64_t *nrecords, uint64_t *out_total, size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n) || (!idx && max) || !count || !out_total || (!pts && max_pts) || !npts || !nrecords || (!rec_cum && max_cum))
+        return BZH_E_ARG;
+    if (interval && !sync_interval_ok(ctx, interval)) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BZH_TRY(decode_stage(ctx, in, n));
+    return bzh_decode_index_records_device(ctx, ctx->d_stage_in, n, interval, delim, idx, max, count, pts, max_pts, npts, rec_cum, max_cum,
+                                           nrecords, out_total, consumed);
+    });
+}
+
+extern "C" int bzh_count_records_device(bzh_ctx *ctx, const void *d_raw, size_t n, uint8_t delim, const bzh_index_entry *idx, size_t count,
+                                        uint64_t *rec_cum, uint64_t *nrecords)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_raw && n) || (!idx && count) || !rec_cum || !nrecords) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (count > 0xFFFFFFFFull) {
+        bzh_set_error(ctx, "count records: an index of %zu entries, 2^32 or more", count);
+        return BZH_E_ARG;
+    }
+    BZH_TRY(decode_index_check(ctx, idx, count));
+    const uint64_t total = count ? idx[count - 1].out_off + idx[count - 1].out_len : 0;
+    if (total != n) {
+        bzh_set_error(ctx, "count records: the index holds %llu bytes, the buffer %zu", (unsigned long long)total, n);
+        return BZH_E_ARG;
+    }
+    return count_records_run(ctx, (const uint8_t *)d_raw, n, delim, idx, count, rec_cum, nrecords);
+    });
+}
+
+// the checks both variants make before any arithmetic on the arrays; the touched entries
+static int decode_records_args(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts, size_t npts,
+                               const uint64_t *rec_cum, const bzh_range *ranges, size_t nranges, std::vector<uint32_t> &touched, uint64_t *lo,
+                               uint64_t *hi)
+{
+    if (count > 0xFFFFFFFFull) {
+        bzh_set_error(ctx, "decode records: an index of %zu entries, 2^32 or more", count);
+        return BZH_E_ARG;
+    }
+    BZH_TRY(decode_index_check(ctx, idx, count));
+    BZH_TRY(decode_sync_check(ctx, idx, count, pts, npts));
+    size_t bad = 0;
+    if (const char *what = bzq_table_check(idx, count, rec_cum, &bad)) {
+        bzh_set_error(ctx, "decode records: record table, entry %zu: %s", bad, what);
+        return BZH_E_ARG;
+    }
+    bzq_spans(idx, count, rec_cum, ranges, nranges, touched, lo, hi);
+    return BZH_OK;
+}
+
+extern "C" int bzh_decode_records_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                                         size_t count, const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint8_t delim,
+                                         const bzh_range *ranges, size_t nranges, void *d_out, size_t cap, size_t *out_offs, size_t *out_lens,
+                                         size_t *out_total)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n) || (!d_out && cap) || (!idx && count) || (!pts && npts) || !rec_cum || (!ranges && nranges) ||
+        (!out_offs && nranges) || (!out_lens && nranges) || !out_total)
+        return BZH_E_ARG;
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
+    memset(&ctx->qstats, 0, sizeof ctx->qstats);
+    *out_total = 0;
+    for (size_t r = 0; r < nranges; r++) out_offs[r] = out_lens[r] = 0;
+    std::vector<uint32_t> touched;
+    uint64_t lo = 0, hi = 0;
+    BZH_TRY(decode_records_args(ctx, idx, count, pts, npts, rec_cum, ranges, nranges, touched, &lo, &hi));
+    ctx->qstats.ranges = nranges;
+    ctx->qstats.blocks_touched = touched.size();
+    BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(touched.size(), 1), ctx->max_batch)));
+    const int rc = decode_records_run(ctx, (const uint8_t *)d_in, n, in_byte_base, idx, count, pts, npts, rec_cum, delim, ranges, nranges, touched,
+                                      (uint8_t *)d_out, cap, out_offs, out_lens, out_total);
+    return decode_call_end(ctx, call, rc);
+    });
+}
+
+extern "C" int bzh_decode_records(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                                  const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint8_t delim, const bzh_range *ranges,
+                                  size_t nranges, uint8_t *out, size_t cap, size_t *out_offs, size_t *out_lens, size_t *out_total)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n) || (!out && cap) || (!idx && count) || (!pts && npts) || !rec_cum || (!ranges && nranges) ||
+        (!out_offs && nranges) || (!out_lens && nranges) || !out_total)
+        return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    *out_total = 0;
+    // only the hull goes up (a buffer that does not cover it goes up whole: the device call says what is missing)
+    std::vector<uint32_t> touched;
+    uint64_t lo = 0, hi = 0;
+    BZH_TRY(decode_records_args(ctx, idx, count, pts, npts, rec_cum, ranges, nranges, touched, &lo, &hi));
+    const bool covered = lo <= hi && in_byte_base <= lo && hi - in_byte_base <= n;
+    const uint64_t base = covered ? lo : in_byte_base;
+    const size_t un = covered ? (size_t)(hi - lo) : n;
+    BZH_TRY(decode_stage(ctx, covered ? in + (lo - in_byte_base) : in, un, cap));
+    const int rc = bzh_decode_records_device(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, rec_cum, delim, ranges, nranges,
+                                             cap ? ctx->d_stage_out : nullptr, cap, out_offs, out_lens, out_total);
     if (rc != BZH_OK) return rc;
     if (*out_total) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, *out_total, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, bzh_stream_wait(ctx->stream));

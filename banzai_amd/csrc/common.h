@@ -182,6 +182,7 @@ struct bzh_ctx {
     bzh_recover_stats rstats{};     // of the last bzh_recover* call
     bzh_decode_ranges_stats qstats{}; // of the last bzh_decode_ranges* call
     DevBuf ranges_ws;               // bzh_decode_ranges*: a batch's piece tables (allocated on first use)
+    DevBuf records_ws;              // records (bzh_decode_index_records*, bzh_decode_records*, bzh_count_records_device): tile counts, last-byte flags, queries, positions
     struct DStream *dstrm = nullptr; // streaming decode (bzh_dstream_*, decode.hip): made by the first begin, freed by dstream_free
     size_t dstrm_window = 0, dstrm_staging = 0; // bzh_dstream_set_room: targets of the next begin (0: the defaults)
     // streaming encode (bzh_stream_*)
@@ -539,8 +540,14 @@ struct SyncBuild { // bzh_decode_index_sync*: the chain walk records a point eve
     uint32_t interval;
     std::vector<bzh_sync_point> pts;
 };
+struct RecBuild { // bzh_decode_index_records*: the index build also counts the delimiters of every block on the chain
+    uint32_t delim;
+    std::vector<uint64_t> cum; // [entries + 1] delimiters in front of every entry, and of the end
+    bool last_is_delim;        // the last byte of the output is one
+};
 int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t cap, size_t *out_len, size_t *consumed,
-                     const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index = nullptr, SyncBuild *sync = nullptr);
+                     const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index = nullptr, SyncBuild *sync = nullptr,
+                     RecBuild *rec = nullptr);
 // decode.hip: the two checks of an index and its sync points as a whole, then the blocks of a verified index that
 // [off, off + len) touches, from d_in = the indexed input from byte in_byte_base on (windows and segments: decode_plan.h)
 int decode_index_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count); // BZH_E_ARG naming the entry that is ill formed
@@ -554,6 +561,12 @@ int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_by
 int decode_ranges_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
                       const bzh_sync_point *pts, size_t npts, const bzh_range *ranges, size_t nranges, const size_t *out_offs,
                       const std::vector<uint32_t> &touched, uint8_t *d_out, uint64_t out_total);
+// decode.hip: a read by record number over ascending ranges of records (the walk: decode_records_plan.h); the record table of raw bytes
+int decode_records_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                       const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint8_t delim, const bzh_range *ranges, size_t nranges,
+                       const std::vector<uint32_t> &touched, uint8_t *d_out, size_t cap, size_t *out_offs, size_t *out_lens, size_t *out_total);
+int count_records_run(bzh_ctx *ctx, const uint8_t *d_raw, size_t n, uint8_t delim, const bzh_index_entry *idx, size_t count, uint64_t *rec_cum,
+                      uint64_t *nrecords);
 // decode.hip: many inputs, one chain each, batches across them (the walk itself: decode_many_plan.h).  The slices have been checked.
 int decode_many_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const size_t *in_offs, const size_t *in_lens, size_t count, uint8_t *d_out,
                     size_t cap, size_t *out_offs, size_t *out_lens, int *status, size_t *consumed, const std::vector<uint64_t> &cands);

@@ -13,6 +13,9 @@
 // Sync points (bzh_decode_index_sync*, bzh_decode_range_sync*): the index build also writes the entropy stage's state down every
 // `interval` groups (decode_block_sync_kernel); a range then parses each touched block's header once (decode_header_kernel) and
 // decodes every segment, from point to point, in a wavefront of its own (decode_segment_kernel).
+// Records (bzh_decode_index_records*, bzh_decode_records*, bzh_count_records_device): the index build also counts every block's
+// delimiter bytes where it folds the CRC (unrle_count); a read by record number decodes the blocks the table names, finds the
+// boundary delimiters on the device (unrle_select) and emits the records' bytes through the pieces of the range decode.
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -22,6 +25,7 @@
 #include "decode_core.h"
 #include "decode_plan.h"
 #include "decode_many_plan.h"
+#include "decode_records_plan.h"
 #include "decode_recover_plan.h"
 #include "decode_stream_plan.h"
 
@@ -659,6 +663,119 @@ __global__ void __launch_bounds__(64) unrle_crc_finish(UwArgs wa)
     if (threadIdx.x == 0) wa.crc[blockIdx.x] = wa.acc[blockIdx.x] ^ gf_mul(0xFFFFFFFFu, pw) ^ 0xFFFFFFFFu;
 }
 
+// ---- records: the delimiters of a block's expansion, counted and located from the bytes behind its inverse BWT ----------------
+struct UcArgs {
+    uint32_t delim;
+    uint32_t *tcount; // [B][T] delimiters the tile expands to
+    uint32_t *last;   // [B] the block's last output byte is the delimiter
+};
+
+// unrle_crc's grid and entry states, folding a count instead of a CRC: what a thread's 16 bytes stand for (bzd_ur_count), summed
+// over the workgroup and stored plainly, a word a tile -- the host sums the tiles, and unrle_select wants them one by one.
+__global__ void __launch_bounds__(UR_THREADS) unrle_count(UrArgs a, UcArgs ca)
+{
+    __shared__ uint32_t lds[8];
+    __shared__ uint32_t wred[UR_THREADS / 64];
+    const uint32_t b = a.slots[blockIdx.y], t = blockIdx.x, n = a.n[b];
+    const size_t ti = (size_t)b * a.T + t;
+    const uint32_t entry = a.tstate[ti], i0 = t * UR_TILE + threadIdx.x * UR_ITEMS;
+    const UrBytes u = ur_load(a.x + (size_t)b * a.S, n, i0);
+    uint32_t total;
+    const uint32_t ex = ur_scan(ur_thread_map(u), lds, &total);
+    uint32_t outn, last = 256;
+    uint32_t d = bzd_ur_count(u.w, u.cnt, u.prev, bzd_rl_apply(ex, entry), ca.delim, &outn, &last);
+    if (u.cnt && i0 + u.cnt == n) ca.last[b] = last == ca.delim; // (one thread of one tile holds the block's last byte)
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) d += __shfl_xor(d, s, 64);
+    if ((threadIdx.x & 63u) == 0) wred[threadIdx.x >> 6] = d;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t c = 0;
+        for (uint32_t k = 0; k < UR_THREADS / 64; k++) c += wred[k];
+        ca.tcount[ti] = c; // (a tile behind the block's last counts nothing: every word of the grid is written)
+    }
+}
+
+struct UsArgs {
+    const BzqQuery *q;
+    uint32_t *pos; // [queries] the delimiter's position in its block's output, BZQ_NONE where no thread holds it
+    uint32_t nslots, delim;
+};
+
+// One workgroup a query: the k-th delimiter of one tile.  The same load and scan, an exclusive sum of the threads' counts, and the
+// one thread whose share holds the k-th walks its 16 bytes again (bzd_ur_select).  Whatever the query holds, every read is
+// bounded by n[b] inside the slot's stride and the only store is the query's own word.
+__global__ void __launch_bounds__(UR_THREADS) unrle_select(UrArgs a, UsArgs sa)
+{
+    __shared__ uint32_t lds[8];
+    __shared__ uint32_t found;
+    const BzqQuery q = sa.q[blockIdx.x];
+    if (threadIdx.x == 0) found = BZQ_NONE;
+    if (q.slot >= sa.nslots || q.tile >= a.T) { // (the same for every thread)
+        if (threadIdx.x == 0) sa.pos[blockIdx.x] = BZQ_NONE;
+        return;
+    }
+    const uint32_t b = q.slot, n = min(a.n[b], a.S);
+    const size_t ti = (size_t)b * a.T + q.tile;
+    const uint32_t entry = a.tstate[ti];
+    const UrBytes u = ur_load(a.x + (size_t)b * a.S, n, q.tile * UR_TILE + threadIdx.x * UR_ITEMS);
+    uint32_t total;
+    const uint32_t ex = ur_scan(ur_thread_map(u), lds, &total); // (its barriers also publish `found`)
+    const uint32_t s = bzd_rl_apply(ex, entry);
+    uint32_t outn, last = 256, dsum, osum;
+    const uint32_t d = bzd_ur_count(u.w, u.cnt, u.prev, s, sa.delim, &outn, &last);
+    const uint32_t d0 = block_excl_add(d, lds, &dsum);
+    const uint32_t o0 = block_excl_add(outn, lds, &osum);
+    if (q.k > d0 && q.k - d0 <= d) found = a.toff[ti] + o0 + bzd_ur_select(u.w, u.cnt, u.prev, s, sa.delim, q.k - d0);
+    __syncthreads();
+    if (threadIdx.x == 0) sa.pos[blockIdx.x] = found;
+}
+
+// The same table from decoded bytes (bzh_count_records_device): the delimiters of raw[offs[e], offs[e] + lens[e]), a word a tile
+// of CB_TILE bytes, summed on the host.  No state machine: aligned 16-byte loads, the ragged edges byte by byte, one reduction a
+// workgroup.  The host has checked that every entry lies inside the buffer.
+constexpr uint32_t CB_THREADS = 256, CB_TILE = 16384;
+
+__device__ __forceinline__ uint32_t cb_eq4(uint32_t w, uint32_t pat) // bytes of w equal to the byte pat repeats
+{
+    const uint32_t x = w ^ pat;
+    return (uint32_t)__popc(~((((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) | 0x7F7F7F7Fu));
+}
+
+// (the grid is the tiles of all entries end to end, tfirst[e] = the first tile of entry e, tfirst[count] = their number: the work
+// is the bytes' whatever the entries' sizes are)
+__global__ void __launch_bounds__(CB_THREADS) count_bytes_blocks(const uint8_t *raw, const uint64_t *offs, const uint32_t *lens,
+                                                                  const uint32_t *tfirst, uint32_t count, uint32_t delim, uint32_t *tcount)
+{
+    __shared__ uint32_t wred[CB_THREADS / 64];
+    uint32_t e = 0, hi = count - 1; // the last entry whose first tile is this one or lies in front of it
+    while (e < hi) {
+        const uint32_t mid = e + (hi - e + 1) / 2;
+        if (tfirst[mid] <= blockIdx.x)
+            e = mid;
+        else
+            hi = mid - 1;
+    }
+    const uint32_t t = blockIdx.x - tfirst[e], len = lens[e], lo = t * CB_TILE;
+    uint32_t c = 0;
+    if (t < (len + CB_TILE - 1) / CB_TILE) {
+        const uint8_t *p = raw + offs[e] + lo;
+        const uint32_t m = min(CB_TILE, len - lo), head = min(m, (uint32_t)((0 - (uintptr_t)p) & 15u));
+        const uint32_t nv = (m - head) / 16, tail0 = head + nv * 16, pat = delim * 0x01010101u;
+        if (threadIdx.x < head) c += p[threadIdx.x] == delim;
+        for (uint32_t i = threadIdx.x; i < nv; i += CB_THREADS) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(p + head + 16 * i);
+            c += cb_eq4(v.x, pat) + cb_eq4(v.y, pat) + cb_eq4(v.z, pat) + cb_eq4(v.w, pat);
+        }
+        if (tail0 + threadIdx.x < m) c += p[tail0 + threadIdx.x] == delim;
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s, 64);
+    if ((threadIdx.x & 63u) == 0) wred[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) tcount[blockIdx.x] = wred[0] + wred[1] + wred[2] + wred[3];
+}
+
 // bad[k] = the 48 bits at candidate k are not the block magic (the scan vouches for that in a full decode, an index entry does not)
 __global__ void __launch_bounds__(64) range_magic_kernel(const uint8_t *in, uint64_t n, const uint64_t *cand, uint32_t B, uint32_t *bad)
 {
@@ -798,13 +915,44 @@ struct Back { // a batch between its two steps; the vectors are scratch kept fro
 // split (bzh_decode_many only): the listed blocks of at most split->small_max bytes go through the LDS transform, which takes a
 // list and so leaves the candidates off the chain alone; unbwt_run then runs over slots [0, split->Bl) only -- up to the last
 // listed block above the bound, sized by split->nmax_l -- and first: where both write a small block's slot they write the same.
+struct BackCount { // the delimiters of the listed blocks beside their sizes or CRCs (unrle_count): a record table, a read by records
+    uint32_t delim;
+    uint32_t *d_tcount, *d_last; // [B][T], [B] device (ctx->records_ws)
+    std::vector<uint32_t> tcount, last; // their host images, by batch slot, behind the step's wait
+};
+// queued behind the kernels that leave the entry states; `a` names the blocks' slots, Bu = slots the images cover
+static int back_count_queue(bzh_ctx *ctx, const UrArgs &a, uint32_t Tn, uint32_t K, uint32_t Bu, BackCount &bc)
+{
+    hipStream_t st = ctx->stream;
+    unrle_count<<<dim3(Tn, K), UR_THREADS, 0, st>>>(a, UcArgs{bc.delim, bc.d_tcount, bc.d_last});
+    HIP_TRY(ctx, hipGetLastError());
+    bc.tcount.resize((size_t)Bu * a.T);
+    bc.last.resize(Bu);
+    HIP_TRY(ctx, hipMemcpyAsync(bc.tcount.data(), bc.d_tcount, bc.tcount.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(bc.last.data(), bc.d_last, (size_t)Bu * 4, hipMemcpyDeviceToHost, st));
+    return BZH_OK;
+}
+// the two tables, for batches of the context's size (the stream is idle between batches)
+// and, for a read, its queries and their answers: nq of each at most in the whole call, so nothing moves between its batches
+static int back_count_ws(bzh_ctx *ctx, BackCount &bc, size_t nq = 0, BzqQuery **d_q = nullptr, uint32_t **d_pos = nullptr)
+{
+    const size_t B = ctx->max_batch, T = ctx->S / UR_TILE;
+    BzqQuery *q = nullptr;
+    uint32_t *pos = nullptr;
+    BZH_TRY(reserve_cut(ctx, ctx->records_ws, "the record tables", grow_mib, [&](Carver &c) {
+        c.put(q, nq), c.put(bc.d_tcount, B * T), c.put(bc.d_last, B), c.put(pos, nq);
+    }));
+    if (d_q) *d_q = q;
+    if (d_pos) *d_pos = pos;
+    return BZH_OK;
+}
 struct BackSplit {
     uint32_t small_max;
     uint32_t Bl, nmax_l; // Bl 0: no listed block above the bound
     uint32_t nsmall;     // out: blocks the LDS transform took
 };
 static int back_sizes(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk, uint32_t Bu, uint32_t nmax_all, std::vector<BackBlock> &blocks,
-                      BackSplit *split = nullptr)
+                      BackSplit *split = nullptr, BackCount *count = nullptr)
 {
     hipStream_t st = ctx->stream;
     const Batch &bt = ctx->bt;
@@ -843,6 +991,7 @@ static int back_sizes(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk,
     bk.hend.resize(Bu);
     HIP_TRY(ctx, hipMemcpyAsync(bk.hout.data(), w.tout, bk.hout.size() * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(bk.hend.data(), w.endstate, (size_t)Bu * 4, hipMemcpyDeviceToHost, st));
+    if (count) BZH_TRY(back_count_queue(ctx, bk.a, bk.Tn, K, Bu, *count)); // (a read by records: before this step's wait, not behind one of its own)
     HIP_TRY(ctx, bzh_stream_wait(st));
     bk.hoff.assign((size_t)Bu * w.T, 0);
     for (BackBlock &b : blocks) {
@@ -859,13 +1008,14 @@ static int back_sizes(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk,
 // relist: `blocks` is not the list back_sizes was given but some of its blocks (bzh_recover's second emit, of the blocks the first
 // one's CRCs kept): the whole blocks' slots go up again.
 // pieces (bzh_decode_ranges only): blocks of the list with an empty window here, emitted piece by piece beside the others.
+// count (bzh_decode_index_records only): the delimiters of the blocks with nothing to write, where their CRCs are folded.
 struct BackPieces {
     const uint32_t *slots; // [K] device: their batch slots
     uint32_t K;
     UpArgs args;
 };
 static int back_emit(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk, uint8_t *d_out, bool crcs, std::vector<BackBlock> &blocks,
-                     bool relist = false, const BackPieces *pieces = nullptr)
+                     bool relist = false, const BackPieces *pieces = nullptr, BackCount *count = nullptr)
 {
     hipStream_t st = ctx->stream;
     auto up = [&](void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st); };
@@ -928,6 +1078,13 @@ static int back_emit(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk, 
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(bk.ecrc.data(), w.wcrc, (size_t)KE * 4, hipMemcpyDeviceToHost, st));
     }
+    if (count && KE > KW) { // (the blocks behind the cut ones in the list; their slots are what the images are indexed by)
+        UrArgs ac = ae;
+        ac.slots = w.wslots + KW;
+        uint32_t Bu = 0;
+        for (uint32_t e = KW; e < KE; e++) Bu = std::max(Bu, bk.eslots[e] + 1);
+        BZH_TRY(back_count_queue(ctx, ac, bk.Tn, KE - KW, Bu, *count));
+    }
     clock.span(4, t4);
     HIP_TRY(ctx, bzh_stream_wait(st));
     for (uint32_t f = 0; crcs && f < KF; f++) blocks[bk.fq[f]].crc = bk.fdesc[f].crc;
@@ -939,7 +1096,7 @@ static int back_emit(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk, 
 // index: the call builds a block index (bzh_decode_index*) -- cap is 0, nothing is expanded, every block's CRC comes from
 // unrle_crc and is checked like a full decode's, and the entries are appended in chain order.
 int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t cap, size_t *out_len, size_t *consumed,
-                     const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index, SyncBuild *sync)
+                     const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index, SyncBuild *sync, RecBuild *rec)
 {
     hipStream_t st = ctx->stream;
     Batch &bt = ctx->bt;
@@ -982,6 +1139,12 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
         const size_t slot_bytes = (size_t)sync_cap * sizeof(bzh_sync_point);
         sync_slots = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(ctx->max_batch, ctx->arena_blocks), SYNC_REC_BYTES / slot_bytes));
         BZH_TRY(reserve_cut(ctx, ctx->sync_ws, "the sync points", grow_mib, [&](Carver &c) { c.put(d_ptcnt, sync_slots); c.put(d_pts, (size_t)sync_slots * sync_cap); }));
+    }
+    BackCount bc{rec ? rec->delim : 0u, nullptr, nullptr, {}, {}};
+    if (rec) {
+        BZH_TRY(back_count_ws(ctx, bc));
+        rec->cum.assign(1, 0);
+        rec->last_is_delim = false;
     }
     const size_t nc = cands.size();
     const uint64_t nbits = (uint64_t)n * 8;
@@ -1075,7 +1238,7 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
             if (total_out > cap) over = true; // (sizing goes on: the caller learns the total)
             if (index || !over) { // an index: the CRCs of the expansions, with nothing expanded
                 for (BackBlock &b : blocks) b.lo = 0, b.hi = index ? 0 : (uint32_t)b.size;
-                BZH_TRY(back_emit(ctx, w, clock, bk, d_out, true, blocks));
+                BZH_TRY(back_emit(ctx, w, clock, bk, d_out, true, blocks, false, nullptr, index && rec ? &bc : nullptr));
             } else {
                 span(3, bk.t_unrle);
             }
@@ -1099,6 +1262,12 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
                         for (size_t p = at; p < at + c; p++) sync->pts[p].entry = (uint32_t)index->size();
                     }
                     index->push_back({it.bitpos, it.end_bit, (uint64_t)blocks[q].base, (uint32_t)blocks[q].size, it.crc, (uint32_t)it.stream, it.level});
+                    if (rec) { // the tiles of the block, summed behind the entries before it
+                        uint64_t d = 0;
+                        for (uint32_t t = 0; t < (blocks[q].nblock + UR_TILE - 1) / UR_TILE; t++) d += bc.tcount[(size_t)it.slot * w.T + t];
+                        rec->cum.push_back(rec->cum.back() + d);
+                        rec->last_is_delim = bc.last[it.slot] != 0;
+                    }
                 }
                 stream_crc = ((stream_crc << 1) | (stream_crc >> 31)) ^ it.crc;
                 q++;
@@ -1835,51 +2004,21 @@ extern "C" int bzh_index_spans(const bzh_index_entry *idx, size_t count, const b
     return BZH_OK;
 }
 
-// (idx has passed decode_index_check, pts decode_sync_check; touched and out_offs are bzp_spans', whose sum is out_total <= the
-// room at d_out)
-int decode_ranges_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
-                      const bzh_sync_point *pts, size_t npts, const bzh_range *ranges, size_t nranges, const size_t *out_offs,
-                      const std::vector<uint32_t> &touched, uint8_t *d_out, uint64_t out_total)
-{
-    hipStream_t st = ctx->stream;
-    Batch &bt = ctx->bt;
-    bzh_decode_stats &ds = ctx->dstats;
-    bzh_decode_ranges_stats &qs = ctx->qstats;
-    if (touched.empty()) return BZH_OK;
-    const uint64_t byte_lo = idx[touched.front()].bit_pos / 8, byte_hi = (idx[touched.back()].end_bit + 7) / 8;
-    if (in_byte_base > byte_lo || byte_hi - in_byte_base > n) {
-        bzh_set_error(ctx, "decode range: index entries %zu..%zu lie in bytes [%llu, %llu) of the indexed input, the buffer holds [%llu, %llu)",
-                      (size_t)touched.front(), (size_t)touched.back(), (unsigned long long)byte_lo, (unsigned long long)byte_hi,
-                      (unsigned long long)in_byte_base, (unsigned long long)(in_byte_base + n));
-        return BZH_E_ARG;
-    }
-    DecWs w;
-    BZH_TRY(dec_ws(ctx, w));
-    if (w.T > UR_THREADS) {
-        bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
-        return BZH_E_STATE;
-    }
-    // what every range wants of every touched block
-    std::vector<size_t> pfirst;
-    std::vector<PieceRef> pc;
-    std::vector<uint32_t> prange;
-    bzp_block_pieces(idx, count, ranges, nranges, out_offs, touched, pfirst, pc, prange);
-    qs.pieces = pc.size();
-    StageClock clock{ctx, {}};
-    size_t at = 0; // the entry an error is about
-    auto mismatch = [&](const char *what) {
-        bzh_set_error(ctx, "decode range: index entry %zu (stream %u, bit %llu) does not match its block: %s", at, idx[at].stream,
-                      (unsigned long long)idx[at].bit_pos, what);
-        return BZH_E_DATA;
-    };
+// The front of a batch of a read by index entries (decode_ranges_run, decode_records_run): the entropy stage of the entries
+// idx[ent[0 .. B)] -- ascending, block k in batch slot k --, every block checked against its entry, then back_sizes and the sizes
+// checked too.  BZH_E_DATA names the first entry that fails, in bzh_decode_range's words.  count: back_sizes' (null: none).
+struct RangeFront {
+    bzh_ctx *ctx;
+    const DecWs &w;
+    StageClock &clock;
+    const uint8_t *d_in;
+    size_t n;
+    uint64_t in_byte_base;
+    const bzh_index_entry *idx;
+    const bzh_sync_point *pts;
+    size_t npts;
+    size_t at = 0;        // the entry an error is about
     size_t seg_point = 0; // the sync point a segment's error is about
-    auto seg_mismatch = [&](bool named, const char *what) {
-        if (!named) return mismatch(what);
-        bzh_set_error(ctx, "decode range: index entry %zu (stream %u, bit %llu) does not match its block: sync point %zu: %s", at, idx[at].stream,
-                      (unsigned long long)idx[at].bit_pos, seg_point, what);
-        return BZH_E_DATA;
-    };
-    const uint32_t Bmax = (uint32_t)std::min<size_t>(ctx->max_batch, ctx->arena_blocks);
     std::vector<SegDesc> hseg;
     std::vector<BzdSegResult> hsres;
     std::vector<uint32_t> seg0; // [B + 1] first segment of every block of the batch
@@ -1887,15 +2026,27 @@ int decode_ranges_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_b
     std::vector<bzh_sync_point> hpts;
     std::vector<uint64_t> hcand;
     std::vector<BzdResult> res;
-    std::vector<uint32_t> hmagic, pslots, ptiles, tile_first;
-    std::vector<size_t> pf;     // the pieces of the batch's blocks that are emitted piece by piece: pc[pf[k] .. pf[k + 1])
-    std::vector<PieceRef> bpc, refs;
+    std::vector<uint32_t> hmagic;
     std::vector<BackBlock> blocks;
     Back bk;
-    for (size_t t0 = 0; t0 < touched.size();) {
-        const uint32_t B = (uint32_t)std::min<size_t>(Bmax, touched.size() - t0);
-        const uint32_t *ent = touched.data() + t0;
-        qs.batches++;
+
+    int mismatch(const char *what)
+    {
+        bzh_set_error(ctx, "decode range: index entry %zu (stream %u, bit %llu) does not match its block: %s", at, idx[at].stream,
+                      (unsigned long long)idx[at].bit_pos, what);
+        return BZH_E_DATA;
+    }
+    int seg_mismatch(bool named, const char *what)
+    {
+        if (!named) return mismatch(what);
+        bzh_set_error(ctx, "decode range: index entry %zu (stream %u, bit %llu) does not match its block: sync point %zu: %s", at, idx[at].stream,
+                      (unsigned long long)idx[at].bit_pos, seg_point, what);
+        return BZH_E_DATA;
+    }
+    int run(const uint32_t *ent, uint32_t B, BackCount *count = nullptr)
+    {
+        hipStream_t st = ctx->stream;
+        Batch &bt = ctx->bt;
         // entropy stage: the entries are the candidates
         hcand.resize(B);
         for (uint32_t k = 0; k < B; k++) hcand[k] = (idx[ent[k]].bit_pos - 8 * in_byte_base) << 1;
@@ -1965,25 +2116,36 @@ int decode_ranges_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_b
             if (r.nblock > 100000u * e.level) return mismatch("more bytes than the level's block size");
             nmax = std::max(nmax, r.nblock);
         }
-        ds.blocks += B;
+        ctx->dstats.blocks += B;
         blocks.clear();
         for (uint32_t k = 0; k < B; k++) blocks.push_back(BackBlock{k, res[k].nblock, 0, false, 0, 0, 0, 0});
-        BZH_TRY(back_sizes(ctx, w, clock, bk, B, nmax, blocks));
+        BZH_TRY(back_sizes(ctx, w, clock, bk, B, nmax, blocks, nullptr, count));
+        for (uint32_t k = 0; k < B; k++) {
+            at = ent[k];
+            if (blocks[k].bad_end) return mismatch("the block ends in four equal bytes without a count");
+            if (blocks[k].size != idx[at].out_len) return mismatch("it decodes to another size than out_len");
+        }
+        return BZH_OK;
+    }
+    // The windows of the batch's blocks for back_emit, from their pieces: block k wants pc[pfirst[k] .. pfirst[k + 1]), each somewhere
+    // in an output of out_total bytes.
+    std::vector<uint32_t> pslots, ptiles, tile_first;
+    std::vector<size_t> pf;     // the pieces of the batch's blocks that are emitted piece by piece: bpc[pf[k] .. pf[k + 1])
+    std::vector<PieceRef> bpc, refs;
+    int pieces(const size_t *pfirst, const std::vector<PieceRef> &pc, uint32_t B, uint64_t out_total, BackPieces &bp, uint64_t *whole)
+    {
         // A block that one range wants whole and no other touches is expanded where it belongs and checked there; every other one
         // goes out piece by piece, its window here empty: back_emit takes its CRC from the bytes behind the inverse BWT.
         pslots.clear(), ptiles.clear(), bpc.clear();
         pf.assign(1, 0);
         for (uint32_t k = 0; k < B; k++) {
-            at = ent[k];
-            const bzh_index_entry &e = idx[at];
+            const uint32_t out_len = (uint32_t)blocks[k].size; // (== its entry's: run has checked)
             BackBlock &b = blocks[k];
-            if (b.bad_end) return mismatch("the block ends in four equal bytes without a count");
-            if (b.size != e.out_len) return mismatch("it decodes to another size than out_len");
-            const size_t q0 = pfirst[t0 + k], q1 = pfirst[t0 + k + 1];
-            if (q1 - q0 == 1 && pc[q0].lo == 0 && pc[q0].hi == e.out_len) {
-                b.hi = e.out_len;
+            const size_t q0 = pfirst[k], q1 = pfirst[k + 1];
+            if (q1 - q0 == 1 && pc[q0].lo == 0 && pc[q0].hi == out_len) {
+                b.hi = out_len;
                 b.base = (int64_t)pc[q0].base;
-                qs.blocks_whole++;
+                (*whole)++;
                 continue;
             }
             pslots.push_back(k);
@@ -1991,13 +2153,14 @@ int decode_ranges_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_b
             bpc.insert(bpc.end(), pc.begin() + q0, pc.begin() + q1);
             pf.push_back(bpc.size());
         }
-        BackPieces bp{nullptr, (uint32_t)pslots.size(), UpArgs{nullptr, nullptr, bk.Tn, 0, out_total}};
+        bp = BackPieces{nullptr, (uint32_t)pslots.size(), UpArgs{nullptr, nullptr, bk.Tn, 0, out_total}};
         if (bp.K) {
             if (!bzp_pieces(pslots.data(), ptiles.data(), bp.K, bk.hout.data(), bk.hoff.data(), w.T, bk.Tn, pf.data(), bpc.data(), tile_first,
                             refs)) {
                 bzh_set_error(ctx, "decode ranges: the ranges meet the tiles of one batch more than 2^32 times");
                 return BZH_E_ARG;
             }
+            hipStream_t st = ctx->stream;
             uint32_t *d_slots = nullptr, *d_first = nullptr;
             PieceRef *d_refs = nullptr;
             BZH_TRY(reserve_cut(ctx, ctx->ranges_ws, "the pieces of the ranges", grow_mib, [&](Carver &c) {
@@ -2011,8 +2174,66 @@ int decode_ranges_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_b
             bp.args.refs = d_refs;
             bp.args.nrefs = (uint32_t)refs.size();
         }
+        return BZH_OK;
+    }
+    // behind back_emit: every block's CRC against its entry's (ascending: the first entry that fails is named)
+    int crcs(const uint32_t *ent, uint32_t B)
+    {
+        for (uint32_t k = 0; k < B; k++) {
+            if (blocks[k].crc == idx[ent[k]].crc) continue;
+            at = ent[k];
+            return mismatch(kind_name(BZD_K_BLOCK_CRC));
+        }
+        return BZH_OK;
+    }
+};
+
+// (idx has passed decode_index_check, pts decode_sync_check; touched and out_offs are bzp_spans', whose sum is out_total <= the
+// room at d_out)
+int decode_ranges_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                      const bzh_sync_point *pts, size_t npts, const bzh_range *ranges, size_t nranges, const size_t *out_offs,
+                      const std::vector<uint32_t> &touched, uint8_t *d_out, uint64_t out_total)
+{
+    bzh_decode_stats &ds = ctx->dstats;
+    bzh_decode_ranges_stats &qs = ctx->qstats;
+    if (touched.empty()) return BZH_OK;
+    const uint64_t byte_lo = idx[touched.front()].bit_pos / 8, byte_hi = (idx[touched.back()].end_bit + 7) / 8;
+    if (in_byte_base > byte_lo || byte_hi - in_byte_base > n) {
+        bzh_set_error(ctx, "decode range: index entries %zu..%zu lie in bytes [%llu, %llu) of the indexed input, the buffer holds [%llu, %llu)",
+                      (size_t)touched.front(), (size_t)touched.back(), (unsigned long long)byte_lo, (unsigned long long)byte_hi,
+                      (unsigned long long)in_byte_base, (unsigned long long)(in_byte_base + n));
+        return BZH_E_ARG;
+    }
+    DecWs w;
+    BZH_TRY(dec_ws(ctx, w));
+    if (w.T > UR_THREADS) {
+        bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
+        return BZH_E_STATE;
+    }
+    // what every range wants of every touched block
+    std::vector<size_t> pfirst;
+    std::vector<PieceRef> pc;
+    std::vector<uint32_t> prange;
+    bzp_block_pieces(idx, count, ranges, nranges, out_offs, touched, pfirst, pc, prange);
+    qs.pieces = pc.size();
+    StageClock clock{ctx, {}};
+    const uint32_t Bmax = (uint32_t)std::min<size_t>(ctx->max_batch, ctx->arena_blocks);
+    RangeFront fr{ctx, w, clock, d_in, n, in_byte_base, idx, pts, npts};
+    std::vector<BackBlock> &blocks = fr.blocks;
+    Back &bk = fr.bk;
+    for (size_t t0 = 0; t0 < touched.size();) {
+        const uint32_t B = (uint32_t)std::min<size_t>(Bmax, touched.size() - t0);
+        const uint32_t *ent = touched.data() + t0;
+        qs.batches++;
+        BZH_TRY(fr.run(ent, B));
+        BackPieces bp;
+        BZH_TRY(fr.pieces(pfirst.data() + t0, pc, B, out_total, bp, &qs.blocks_whole));
 #ifdef BZH_EXPERIMENTS
         // scripts/gpu_ranges.py: the pieces through unrle_walk_win, a grid row each, to set beside unrle_walk_pieces
+        hipStream_t st = ctx->stream;
+        const std::vector<uint32_t> &pslots = fr.pslots;
+        const std::vector<size_t> &pf = fr.pf;
+        const std::vector<PieceRef> &bpc = fr.bpc;
         const bool by_window = bp.K && getenv("BZH_RANGES_WIN");
         const uint32_t P = by_window ? (uint32_t)bpc.size() : 0;
         if (by_window) bp.K = 0;
@@ -2042,14 +2263,163 @@ int decode_ranges_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_b
             HIP_TRY(ctx, bzh_stream_wait(st));
         }
 #endif
-        for (uint32_t k = 0; k < B; k++) { // (ascending: the first entry that fails is named)
-            if (blocks[k].crc == idx[ent[k]].crc) continue;
-            at = ent[k];
-            return mismatch(kind_name(BZD_K_BLOCK_CRC));
-        }
+        BZH_TRY(fr.crcs(ent, B));
         t0 += B;
     }
     clock.collect();
     ds.out_bytes = out_total;
+    return BZH_OK;
+}
+
+// ================================================================================================================
+// Reads by record number (bzh_record_spans, bzh_decode_records*, bzh_count_records_device); the arithmetic: decode_records_plan.h
+// ================================================================================================================
+extern "C" int bzh_record_spans(const bzh_index_entry *idx, size_t count, const uint64_t *rec_cum, const bzh_range *ranges, size_t nranges,
+                                uint32_t *touched, size_t max, size_t *ntouched, uint64_t *byte_lo, uint64_t *byte_hi)
+{
+    if ((!idx && count) || !rec_cum || (!ranges && nranges) || (!touched && max) || !ntouched || !byte_lo || !byte_hi) return BZH_E_ARG;
+    if (count > 0xFFFFFFFFull) return BZH_E_ARG;
+    size_t bad;
+    if (bzq_table_check(idx, count, rec_cum, &bad)) return BZH_E_ARG;
+    std::vector<uint32_t> list;
+    bzq_spans(idx, count, rec_cum, ranges, nranges, list, byte_lo, byte_hi);
+    *ntouched = list.size();
+    if (list.size() > max) return BZH_E_CAP;
+    if (!list.empty()) memcpy(touched, list.data(), list.size() * sizeof(uint32_t));
+    return BZH_OK;
+}
+
+// (idx has passed decode_index_check, pts decode_sync_check, rec_cum bzq_table_check; touched is bzq_spans' list)
+int decode_records_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                       const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint8_t delim, const bzh_range *ranges, size_t nranges,
+                       const std::vector<uint32_t> &touched, uint8_t *d_out, size_t cap, size_t *out_offs, size_t *out_lens, size_t *out_total)
+{
+    hipStream_t st = ctx->stream;
+    bzh_decode_stats &ds = ctx->dstats;
+    bzh_decode_ranges_stats &qs = ctx->qstats;
+    BzqWalk<bzh_index_entry, bzh_range> walk;
+    size_t bad = 0;
+    if (!walk.start(idx, count, rec_cum, ranges, nranges, &bad)) {
+        bzh_set_error(ctx, "decode records: range %zu begins in front of the end of the range before it", bad);
+        return BZH_E_ARG;
+    }
+    bool over = false;
+    if (!touched.empty()) {
+        const uint64_t byte_lo = idx[touched.front()].bit_pos / 8, byte_hi = (idx[touched.back()].end_bit + 7) / 8;
+        if (in_byte_base > byte_lo || byte_hi - in_byte_base > n) {
+            bzh_set_error(ctx, "decode range: index entries %zu..%zu lie in bytes [%llu, %llu) of the indexed input, the buffer holds [%llu, %llu)",
+                          (size_t)touched.front(), (size_t)touched.back(), (unsigned long long)byte_lo, (unsigned long long)byte_hi,
+                          (unsigned long long)in_byte_base, (unsigned long long)(in_byte_base + n));
+            return BZH_E_ARG;
+        }
+        DecWs w;
+        BZH_TRY(dec_ws(ctx, w));
+        if (w.T > UR_THREADS) {
+            bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
+            return BZH_E_STATE;
+        }
+        BackCount bc{delim, nullptr, nullptr, {}, {}};
+        BzqQuery *d_q = nullptr;
+        uint32_t *d_pos = nullptr;
+        BZH_TRY(back_count_ws(ctx, bc, walk.bounds.size(), &d_q, &d_pos));
+        StageClock clock{ctx, {}};
+        const uint32_t Bmax = (uint32_t)std::min<size_t>(ctx->max_batch, ctx->arena_blocks);
+        RangeFront fr{ctx, w, clock, d_in, n, in_byte_base, idx, pts, npts};
+        std::vector<uint32_t> ntiles, hpos;
+        std::vector<BzqQuery> hq;
+        std::vector<size_t> pfirst;
+        std::vector<PieceRef> pc;
+        auto table_mismatch = [&]() {
+            bzh_set_error(ctx, "decode records: the record table does not match entry %zu", bad);
+            return BZH_E_DATA;
+        };
+        for (size_t t0 = 0; t0 < touched.size();) {
+            const uint32_t B = (uint32_t)std::min<size_t>(Bmax, touched.size() - t0);
+            const uint32_t *ent = touched.data() + t0;
+            qs.batches++;
+            BZH_TRY(fr.run(ent, B, &bc)); // (the delimiters of every tile come back with the sizes: no wait of their own)
+            ntiles.resize(B);
+            for (uint32_t k = 0; k < B; k++) ntiles[k] = (fr.blocks[k].nblock + UR_TILE - 1) / UR_TILE;
+            if (!walk.queries(ent, B, bc.tcount.data(), w.T, ntiles.data(), hq, &bad)) return table_mismatch();
+            hpos.assign(hq.size(), BZQ_NONE);
+            if (!hq.empty()) { // the boundary delimiters of this batch: the one wait a read by bytes does not pay
+                HIP_TRY(ctx, hipMemcpyAsync(w.toff, fr.bk.hoff.data(), fr.bk.hoff.size() * 4, hipMemcpyHostToDevice, st));
+                HIP_TRY(ctx, hipMemcpyAsync(d_q, hq.data(), hq.size() * sizeof(BzqQuery), hipMemcpyHostToDevice, st));
+                unrle_select<<<dim3((uint32_t)hq.size()), UR_THREADS, 0, st>>>(fr.bk.a, UsArgs{d_q, d_pos, B, delim});
+                HIP_TRY(ctx, hipGetLastError());
+                HIP_TRY(ctx, hipMemcpyAsync(hpos.data(), d_pos, hq.size() * 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(ctx, bzh_stream_wait(st));
+            }
+            uint64_t batch_end = 0;
+            if (!walk.place(ent, B, hpos.data(), out_offs, out_lens, pfirst, pc, &batch_end, &bad)) return table_mismatch();
+            if (batch_end > cap) over = true; // (locating goes on: the caller learns the room needed)
+            if (over) {
+                pc.clear();
+                pfirst.assign((size_t)B + 1, 0);
+            }
+            qs.pieces += pc.size();
+            BackPieces bp;
+            BZH_TRY(fr.pieces(pfirst.data(), pc, B, cap, bp, &qs.blocks_whole));
+            BZH_TRY(back_emit(ctx, w, clock, fr.bk, d_out, true, fr.blocks, false, &bp));
+            BZH_TRY(fr.crcs(ent, B));
+            t0 += B;
+        }
+        clock.collect();
+    }
+    walk.finish(out_offs, out_lens);
+    *out_total = (size_t)walk.run_off;
+    if (over || walk.run_off > cap) {
+        bzh_set_error(ctx, "decode records: the records hold %llu bytes, the buffer %zu", (unsigned long long)walk.run_off, cap);
+        return BZH_E_CAP;
+    }
+    ds.out_bytes = walk.run_off;
+    return BZH_OK;
+}
+
+// The record table of decoded bytes d_raw[0 .. n) under an index of them (idx has passed decode_index_check and sums to n).
+int count_records_run(bzh_ctx *ctx, const uint8_t *d_raw, size_t n, uint8_t delim, const bzh_index_entry *idx, size_t count, uint64_t *rec_cum,
+                      uint64_t *nrecords)
+{
+    hipStream_t st = ctx->stream;
+    rec_cum[0] = 0;
+    *nrecords = 0;
+    if (count == 0) return BZH_OK;
+    std::vector<uint64_t> offs(count);
+    std::vector<uint32_t> lens(count), tfirst(count + 1);
+    uint64_t tiles = 0;
+    for (size_t e = 0; e < count; e++) {
+        offs[e] = idx[e].out_off;
+        lens[e] = idx[e].out_len;
+        tfirst[e] = (uint32_t)tiles;
+        tiles += ((uint64_t)idx[e].out_len + CB_TILE - 1) / CB_TILE;
+        if (tiles > 0x7FFFFFFFull) {
+            bzh_set_error(ctx, "count records: %zu bytes under %zu entries are beyond one launch", n, count);
+            return BZH_E_ARG;
+        }
+    }
+    tfirst[count] = (uint32_t)tiles;
+    uint8_t lastb = 0;
+    std::vector<uint32_t> tcount((size_t)tiles);
+    if (tiles) {
+        uint64_t *d_offs = nullptr;
+        uint32_t *d_lens = nullptr, *d_tfirst = nullptr, *d_tcount = nullptr;
+        BZH_TRY(reserve_cut(ctx, ctx->records_ws, "the record tables", grow_mib, [&](Carver &c) {
+            c.put(d_offs, count), c.put(d_lens, count), c.put(d_tfirst, count + 1), c.put(d_tcount, (size_t)tiles);
+        }));
+        HIP_TRY(ctx, hipMemcpyAsync(d_offs, offs.data(), count * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d_lens, lens.data(), count * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d_tfirst, tfirst.data(), (count + 1) * 4, hipMemcpyHostToDevice, st));
+        count_bytes_blocks<<<dim3((uint32_t)tiles), CB_THREADS, 0, st>>>(d_raw, d_offs, d_lens, d_tfirst, (uint32_t)count, delim, d_tcount);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(tcount.data(), d_tcount, (size_t)tiles * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(&lastb, d_raw + (n - 1), 1, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, bzh_stream_wait(st));
+    }
+    for (size_t e = 0; e < count; e++) {
+        uint64_t d = 0;
+        for (uint32_t t = tfirst[e]; t < tfirst[e + 1]; t++) d += tcount[t];
+        rec_cum[e + 1] = rec_cum[e] + d;
+    }
+    *nrecords = rec_cum[count] + (n > 0 && lastb != delim);
     return BZH_OK;
 }

@@ -1,6 +1,6 @@
 // decode_core.h -- the serial front of the bzip2 decoder: bit reader, block header parser, canonical decode tables, the
 // symbol loop with the inverse MTF / RLE2, the footer, the state model of the inverse RLE1, and what one thread of the inverse
-// RLE1 does with its 16 bytes: count, fold into a CRC, expand clipped to a window.
+// RLE1 does with its 16 bytes: count, fold into a CRC, expand clipped to a window, count and locate a delimiter byte.
 //
 // One source, two builds.  decode.hip compiles it for gfx950, where ONE WAVEFRONT decodes one block: every lane runs the
 // same serial code on the same values (so the bit window and the counters can live on the scalar side), and the lanes
@@ -615,4 +615,54 @@ BZD_FN void bzd_ur_emit(const uint32_t *w, uint32_t cnt, uint32_t prev, uint32_t
             prev = c;
         }
     }
+}
+
+// ---- records: the delimiter bytes of the expansion, counted and located with nothing written (unrle_count / unrle_select).
+// A count byte is never a literal: met in state 4, the byte c stands for c copies of the byte before it and for nothing else, so
+// "aaaa\x0a" is fourteen 'a' and no newline, and "\n\n\n\n\x03" is seven newlines.
+// How many bytes equal to `delim` the stretch expands to; *outn = how many bytes it expands to, *last = the last byte of the
+// expansion of everything up to the stretch's end (a count byte of 0 writes nothing, and the byte in front of it is its run's),
+// left as it is by an empty stretch.
+BZD_FN uint32_t bzd_ur_count(const uint32_t *w, uint32_t cnt, uint32_t prev, uint32_t s, uint32_t delim, uint32_t *outn, uint32_t *last)
+{
+    uint32_t d = 0, o = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t k = 0; k < BZD_UR_ITEMS; k++) {
+        if (k < cnt) {
+            const uint32_t c = bzd_ur_at(w, k);
+            const uint32_t len = s == 4 ? c : 1u, byte = s == 4 ? prev : c;
+            d += byte == delim ? len : 0u;
+            o += len;
+            *last = byte;
+            s = bzd_rl_step(s, c == prev);
+            prev = c;
+        }
+    }
+    *outn = o;
+    return d;
+}
+
+// Where the k-th (1-based) delimiter of the stretch lies, counted in bytes of the stretch's own expansion; inside a run, the exact
+// byte of the run.  0xFFFFFFFF: the stretch holds fewer than k, or k is 0.
+BZD_FN uint32_t bzd_ur_select(const uint32_t *w, uint32_t cnt, uint32_t prev, uint32_t s, uint32_t delim, uint32_t k)
+{
+    uint32_t o = 0, at = 0xFFFFFFFFu;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t i = 0; i < BZD_UR_ITEMS; i++) {
+        if (i < cnt) {
+            const uint32_t c = bzd_ur_at(w, i);
+            const uint32_t len = s == 4 ? c : 1u, byte = s == 4 ? prev : c;
+            const uint32_t here = byte == delim ? len : 0u;
+            if (k >= 1 && k <= here && at == 0xFFFFFFFFu) at = o + k - 1;
+            k = k > here ? k - here : 0u; // (0 once found or once impossible: nothing behind it matches)
+            o += len;
+            s = bzd_rl_step(s, c == prev);
+            prev = c;
+        }
+    }
+    return at;
 }

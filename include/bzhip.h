@@ -472,6 +472,75 @@ typedef struct {
 } bzh_decode_ranges_stats;
 BZH_API int bzh_get_decode_ranges_stats(const bzh_ctx *ctx, bzh_decode_ranges_stats *out);
 
+/* ---- records: a table of delimiter counts beside the index, and reads by record number ------------------------------------ */
+
+/* DEFINITIONS.  `delim` is one byte value, `total` the indexed output's size, D the number of delimiter bytes in the output,
+ * numbered 1..D by position p_1 < .. < p_D.  Record r, 0 <= r <= D, is the bytes [s_r, e_r) with s_0 = 0, s_r = p_r + 1,
+ * e_r = p_(r+1) + 1 for r < D and e_D = total: the delimiter belongs to the record it ends, and record D is the unterminated
+ * tail, which may be empty.  nrecords = D + (total > 0 && the last byte != delim): the records a reader of lines counts.
+ * THE RECORD TABLE is uint64_t rec_cum[count + 1] beside an index of `count` entries: rec_cum[e] = the delimiters in output
+ * bytes [0, idx[e].out_off), rec_cum[count] = D.
+ * A RANGE OF RECORDS is a bzh_range {off = first record, len = number of records}: the bytes [s_off, s_(off+len)), with
+ * s_k = total for k > D; off + len saturates.  It is clipped to the D + 1 records there are. */
+
+/* bzh_decode_index_sync that also fills the record table and *nrecords.  interval 0: entries only (*npts = 0).  The input
+ * contract, the verification, the errors, idx / *count, pts / *npts, *out_total and *consumed are byte for byte those of
+ * bzh_decode_index_sync.  The delimiters are counted from the bytes behind each block's inverse BWT where its CRC is folded:
+ * nothing is expanded, nothing more is waited for.  BZH_E_CAP also when max_cum < *count + 1 (*count is set). */
+BZH_API int bzh_decode_index_records(bzh_ctx *ctx, const uint8_t *in, size_t n, uint32_t interval, uint8_t delim,
+                                     bzh_index_entry *idx, size_t max, size_t *count, bzh_sync_point *pts, size_t max_pts,
+                                     size_t *npts, uint64_t *rec_cum, size_t max_cum, uint64_t *nrecords, uint64_t *out_total,
+                                     size_t *consumed);
+BZH_API int bzh_decode_index_records_device(bzh_ctx *ctx, const void *d_in, size_t n, uint32_t interval, uint8_t delim,
+                                            bzh_index_entry *idx, size_t max, size_t *count, bzh_sync_point *pts,
+                                            size_t max_pts, size_t *npts, uint64_t *rec_cum, size_t max_cum,
+                                            uint64_t *nrecords, uint64_t *out_total, size_t *consumed);
+
+/* The same table from the decoded bytes d_raw[0..n) (device memory) and an index of them: after bzh_encode_index_device the
+ * encoder's input is at hand, and the table costs one pass over it at memory bandwidth instead of a decode.  rec_cum holds
+ * count + 1 words (host).  BZH_E_ARG: an index that is not well formed (as bzh_decode_range), or whose total is not n. */
+BZH_API int bzh_count_records_device(bzh_ctx *ctx, const void *d_raw, size_t n, uint8_t delim, const bzh_index_entry *idx,
+                                     size_t count, uint64_t *rec_cum, uint64_t *nrecords);
+
+/* Pure host arithmetic (no context, no GPU), in the style of bzh_index_spans: the entries a read of these ranges of records
+ * must decode -- ascending and unique -- and the hull [*byte_lo, *byte_hi) of their compressed bytes.  A range touches the block
+ * that holds delimiter `off` (entry 0 for off == 0), the block that holds delimiter `off + len` (the last entry when that
+ * exceeds D), and every block between them.  A BLOCK WHOSE LAST BYTE IS THE BOUNDARY DELIMITER IS TOUCHED ALTHOUGH IT GIVES THE
+ * RANGE NO BYTES: the table says which block holds the delimiter, only the decode says where in it.  A range that is empty after
+ * clipping (len 0, off > D) touches nothing.  The ranges need not ascend here.  *ntouched is set also when max is too small
+ * (BZH_E_CAP).  BZH_E_ARG: a null pointer, 2^32 entries or more, a table that is not well formed (see below). */
+BZH_API int bzh_record_spans(const bzh_index_entry *idx, size_t count, const uint64_t *rec_cum, const bzh_range *ranges,
+                             size_t nranges, uint32_t *touched, size_t max, size_t *ntouched, uint64_t *byte_lo,
+                             uint64_t *byte_hi);
+
+/* Reads ranges of records: only the touched blocks (bzh_record_spans' list) are decoded, once each, the boundary delimiters are
+ * located on the device, and exactly the records' bytes go to d_out.
+ * RANGES are in records, clipped as above.  They must ascend and must not overlap: after clipping, ranges[r + 1].off >=
+ * ranges[r].off + ranges[r].len, else BZH_E_ARG naming the range.  Adjacent and empty ranges are allowed.  Because they ascend,
+ * one pass over the touched blocks in ascending batches places everything: no block goes through the entropy stage twice.
+ * OUTPUT.  The records' bytes lie back to back in range order: out_offs[r], out_lens[r] and *out_total are set on success and
+ * on BZH_E_CAP.  When cap is too small the call stops emitting, goes on locating, and returns BZH_E_CAP with *out_total the room
+ * needed (d_out is then unspecified), as bzh_decode does.  No byte outside d_out[0, *out_total) is written, and whole blocks
+ * are not expanded into scratch.
+ * VERIFIED: everything bzh_decode_ranges verifies -- every touched block against its entry, its CRC over all of its bytes, the
+ * sync points (npts == 0: one wavefront a block) -- and, for every touched block, the table: the delimiters counted in the block
+ * must be rec_cum[e + 1] - rec_cum[e], else BZH_E_DATA "record table does not match entry e".  The table is untrusted and is
+ * checked as a whole first: rec_cum[0] == 0, ascending, no difference above its entry's out_len, else BZH_E_ARG.  The index and
+ * the points are checked as by bzh_decode_ranges.  After any error the context stays usable.
+ * bzh_get_decode_stats and bzh_get_decode_ranges_stats are filled as by bzh_decode_ranges: ranges, pieces, blocks_touched,
+ * blocks_whole and batches keep their meanings.  A batch costs at most one wait more than bzh_decode_ranges pays.
+ * d_in[0..n) holds the compressed bytes from byte in_byte_base of the indexed input and must cover bzh_record_spans' hull. */
+BZH_API int bzh_decode_records_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base,
+                                      const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts, size_t npts,
+                                      const uint64_t *rec_cum, uint8_t delim, const bzh_range *ranges, size_t nranges, void *d_out,
+                                      size_t cap, size_t *out_offs, size_t *out_lens, size_t *out_total);
+/* Same, host buffers.  Only the hull goes up (a buffer that does not cover it goes up whole: the device call says what is
+ * missing). */
+BZH_API int bzh_decode_records(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                               size_t count, const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint8_t delim,
+                               const bzh_range *ranges, size_t nranges, uint8_t *out, size_t cap, size_t *out_offs,
+                               size_t *out_lens, size_t *out_total);
+
 /* ---- the encoder writes the index of its own stream: no decode pass to rediscover what it held -------------------------- */
 
 /* bzh_encode_device that also returns the index of the stream it writes: the entries bzh_decode_index would return for
