@@ -1355,6 +1355,26 @@ static int decode_stage(bzh_ctx *ctx, const uint8_t *in, size_t n, size_t out_by
     return BZH_OK;
 }
 
+// decode_stage for the host variants of a read by index (range, ranges, records): of the caller's n bytes, which begin at byte
+// in_byte_base of the indexed input, only the hull [lo, hi) of the touched blocks goes up.  A buffer that does not cover it goes up
+// whole: the device call says what is missing.  *base, *un: where in the indexed input the staged bytes begin, and their number.
+static int decode_stage_hull(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, uint64_t lo, uint64_t hi, size_t out_bytes,
+                             uint64_t *base, size_t *un)
+{
+    const bool covered = lo <= hi && in_byte_base <= lo && hi - in_byte_base <= n;
+    *base = covered ? lo : in_byte_base;
+    *un = covered ? (size_t)(hi - lo) : n;
+    return decode_stage(ctx, covered ? in + (lo - in_byte_base) : in, *un, out_bytes);
+}
+
+// ... and their tail: `len` bytes of the staged output to the caller's buffer, and the wait.
+static int decode_unstage(bzh_ctx *ctx, uint8_t *out, size_t len)
+{
+    if (len) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, len, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+    return BZH_OK;
+}
+
 extern "C" int bzh_decode_device(bzh_ctx *ctx, const void *d_in, size_t n, void *d_out, size_t cap, size_t *out_len, size_t *consumed)
 {
     return bzh_guard(ctx, [&]() -> int {
@@ -1561,6 +1581,10 @@ static int decode_range_device_impl(bzh_ctx *ctx, const void *d_in, size_t n, ui
     DecodeCall call;
     BZH_TRY(decode_call_begin(ctx, n, call));
     *out_len = 0;
+    if (count > 0xFFFFFFFFull) { // (the front numbers the entries of a batch in 32 bits, as a sync point does its own)
+        bzh_set_error(ctx, "decode range: an index of %zu entries, 2^32 or more", count);
+        return BZH_E_ARG;
+    }
     BZH_TRY(decode_index_check(ctx, idx, count)); // (before any arithmetic on the entries)
     BZH_TRY(decode_sync_check(ctx, idx, count, pts, npts));
     size_t first = 0, last = 0;
@@ -1596,7 +1620,7 @@ static int decode_range_impl(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t
     *out_len = 0;
     BZH_TRY(decode_index_check(ctx, idx, count)); // (before any arithmetic on the entries)
     BZH_TRY(decode_sync_check(ctx, idx, count, pts, npts));
-    // only the span goes up (a buffer that does not cover it goes up whole: the device call says what is missing)
+    // only the span goes up
     size_t first = 0, last = 0;
     uint64_t lo = 0, hi = 0;
     BZH_TRY(bzh_index_span(idx, count, off, len, &first, &last, &lo, &hi));
@@ -1606,16 +1630,12 @@ static int decode_range_impl(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t
         bzh_set_error(ctx, "decode range: the range holds %llu bytes, the buffer %zu", (unsigned long long)want, cap);
         return BZH_E_ARG;
     }
-    const bool covered = lo <= hi && in_byte_base <= lo && hi - in_byte_base <= n;
-    const uint64_t base = covered ? lo : in_byte_base;
-    const size_t un = covered ? (size_t)(hi - lo) : n;
-    BZH_TRY(decode_stage(ctx, covered ? in + (lo - in_byte_base) : in, un, (size_t)want));
-    size_t got = 0;
-    const int rc = decode_range_device_impl(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, off, len,
-                                            want ? ctx->d_stage_out : nullptr, (size_t)want, &got);
-    if (rc != BZH_OK) return rc;
-    if (got) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, got, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+    uint64_t base;
+    size_t un, got = 0;
+    BZH_TRY(decode_stage_hull(ctx, in, n, in_byte_base, lo, hi, (size_t)want, &base, &un));
+    BZH_TRY(decode_range_device_impl(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, off, len, want ? ctx->d_stage_out : nullptr,
+                                     (size_t)want, &got));
+    BZH_TRY(decode_unstage(ctx, out, got));
     *out_len = got;
     return BZH_OK;
     });
@@ -1683,23 +1703,19 @@ extern "C" int bzh_decode_ranges(bzh_ctx *ctx, const uint8_t *in, size_t n, uint
         (!out_lens && nranges) || !out_total)
         return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // only the hull goes up (a buffer that does not cover it goes up whole: the device call says what is missing)
+    // only the hull goes up
     uint64_t lo = 0, hi = 0, total = 0;
     if (count <= 0xFFFFFFFFull) {
         std::vector<uint32_t> touched;
         total = bzp_spans(idx, count, ranges, nranges, nullptr, nullptr, touched, &lo, &hi);
     }
-    const bool covered = lo <= hi && in_byte_base <= lo && hi - in_byte_base <= n;
-    const uint64_t base = covered ? lo : in_byte_base;
-    const size_t un = covered ? (size_t)(hi - lo) : n;
     const size_t room = total <= cap ? (size_t)total : 0; // (too small: the device call sets the sizes and says so)
-    BZH_TRY(decode_stage(ctx, covered ? in + (lo - in_byte_base) : in, un, room));
-    const int rc = bzh_decode_ranges_device(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, ranges, nranges,
-                                            room ? ctx->d_stage_out : nullptr, room, out_offs, out_lens, out_total);
-    if (rc != BZH_OK) return rc;
-    if (*out_total) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, *out_total, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
-    return BZH_OK;
+    uint64_t base;
+    size_t un;
+    BZH_TRY(decode_stage_hull(ctx, in, n, in_byte_base, lo, hi, room, &base, &un));
+    BZH_TRY(bzh_decode_ranges_device(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, ranges, nranges,
+                                     room ? ctx->d_stage_out : nullptr, room, out_offs, out_lens, out_total));
+    return decode_unstage(ctx, out, *out_total);
     });
 }
 
@@ -1809,20 +1825,16 @@ extern "C" int bzh_decode_records(bzh_ctx *ctx, const uint8_t *in, size_t n, uin
         return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     *out_total = 0;
-    // only the hull goes up (a buffer that does not cover it goes up whole: the device call says what is missing)
+    // only the hull goes up
     std::vector<uint32_t> touched;
     uint64_t lo = 0, hi = 0;
     BZH_TRY(decode_records_args(ctx, idx, count, pts, npts, rec_cum, ranges, nranges, touched, &lo, &hi));
-    const bool covered = lo <= hi && in_byte_base <= lo && hi - in_byte_base <= n;
-    const uint64_t base = covered ? lo : in_byte_base;
-    const size_t un = covered ? (size_t)(hi - lo) : n;
-    BZH_TRY(decode_stage(ctx, covered ? in + (lo - in_byte_base) : in, un, cap));
-    const int rc = bzh_decode_records_device(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, rec_cum, delim, ranges, nranges,
-                                             cap ? ctx->d_stage_out : nullptr, cap, out_offs, out_lens, out_total);
-    if (rc != BZH_OK) return rc;
-    if (*out_total) HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_stage_out, *out_total, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
-    return BZH_OK;
+    uint64_t base;
+    size_t un;
+    BZH_TRY(decode_stage_hull(ctx, in, n, in_byte_base, lo, hi, cap, &base, &un));
+    BZH_TRY(bzh_decode_records_device(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, rec_cum, delim, ranges, nranges,
+                                      cap ? ctx->d_stage_out : nullptr, cap, out_offs, out_lens, out_total));
+    return decode_unstage(ctx, out, *out_total);
     });
 }
 

@@ -20,6 +20,8 @@ constexpr int DB_STRIDE = 1280; // digit-base entries per block: up to 5 digits 
 constexpr int SORT_ITEMS = 16;
 constexpr int SORT_TILE = SORT_THREADS * SORT_ITEMS; // 8192 elements per workgroup (512 x 16: halves the look-back /
                                                      // scan overhead per element against 256 x 16, -7 % on the bench)
+// The stride of blocks of at most M RLE1 bytes (layout_batch); the largest a context can have is a level-9 block's, M = 899,999.
+constexpr uint32_t batch_stride(uint32_t M) { return (uint32_t)(((size_t)M + 1 + SORT_TILE - 1) / SORT_TILE * SORT_TILE); }
 constexpr uint32_t RANK_RESOLVED = 0x80000000u;      // suffix is alone in its group
 constexpr uint32_t RANK_EMITTED = 31u << 26;         // (with RANK_RESOLVED, less = 0) its byte of the last column has been written (chunk_finish)
 constexpr int SUMMARY_WORDS = 24; // round summary: see round_begin (bwt.hip)
@@ -215,7 +217,7 @@ static inline size_t layout_batch(Batch &bt, void *base, uint32_t B, uint32_t M,
     c.log = log;
     bt.B = B;
     bt.M = M;
-    bt.S = (uint32_t)(((size_t)M + 1 + SORT_TILE - 1) / SORT_TILE * SORT_TILE);
+    bt.S = batch_stride(M);
     bt.TPB = bt.S / SORT_TILE;
     const size_t S = bt.S, NB = B;
     const size_t PT = (S + 64 + PACK_TILE - 1) / PACK_TILE;

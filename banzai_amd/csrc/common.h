@@ -552,7 +552,7 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
 // [off, off + len) touches, from d_in = the indexed input from byte in_byte_base on (windows and segments: decode_plan.h)
 int decode_index_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count); // BZH_E_ARG naming the entry that is ill formed
 int decode_sync_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts, size_t npts); // same, the point
-// (pts: sync points that have passed decode_sync_check; none: one wavefront a block)
+// (pts: sync points that have passed decode_sync_check; none: one wavefront a block.  count < 2^32, here and in the two below)
 int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
                      uint64_t off, uint64_t len, uint8_t *d_out, size_t cap, size_t *out_len, const bzh_sync_point *pts = nullptr,
                      size_t npts = 0);

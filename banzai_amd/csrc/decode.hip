@@ -16,6 +16,8 @@
 // Records (bzh_decode_index_records*, bzh_decode_records*, bzh_count_records_device): the index build also counts every block's
 // delimiter bytes where it folds the CRC (unrle_count); a read by record number decodes the blocks the table names, finds the
 // boundary delimiters on the device (unrle_select) and emits the records' bytes through the pieces of the range decode.
+// Every read by index -- one range, many ranges, records -- takes its batches through one front (IndexedFront: the entropy stage
+// of a list of entries, every block checked against its entry, back_sizes) and differs in what it asks of back_emit behind it.
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -393,7 +395,7 @@ __global__ void __launch_bounds__(UR_THREADS) unrle_walk(UrArgs a)
     uint32_t entry, total;
     if (EXPAND) {
         entry = a.tstate[ti];
-    } else { // the tiles before this one, a thread each (T <= UR_THREADS: the host checks)
+    } else { // the tiles before this one, a thread each (T <= UR_THREADS: dec_ws's static_assert)
         const uint32_t m = threadIdx.x < t ? a.tmap[(size_t)b * a.T + threadIdx.x] : BZD_RL_ID;
         (void)ur_scan(m, lds, &total);
         entry = bzd_rl_apply(total, 0);
@@ -788,6 +790,9 @@ __global__ void __launch_bounds__(64) range_magic_kernel(const uint8_t *in, uint
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
+// unrle_walk sums the tiles in front of its own a thread each: no context's stride holds more tiles than the kernel has threads.
+static_assert(batch_stride(100000u * 9u - 1u) / UR_TILE <= UR_THREADS, "a level-9 block's tiles exceed the walk kernel's threads");
+
 static int dec_ws(bzh_ctx *ctx, DecWs &w)
 {
     const uint32_t B = ctx->max_batch, T = ctx->S / UR_TILE;
@@ -795,6 +800,9 @@ static int dec_ws(bzh_ctx *ctx, DecWs &w)
     dec_layout(w, ctx->dec_ws, B, T);
     return BZH_OK;
 }
+
+// The blocks a batch may hold: the context's, and no more than the arena was sized for.
+static uint32_t batch_max(const bzh_ctx *ctx) { return (uint32_t)std::min<size_t>(ctx->max_batch, ctx->arena_blocks); }
 
 // The recorder's workspace is bounded by shrinking the batch, whatever the interval: a slot holds every point a block can have,
 // (BZD_MAX_SEL - 1) / interval of 288 bytes -- 9.4 MB at interval 1 -- and a batch has as many slots as fit in this many bytes.
@@ -1103,10 +1111,6 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
     bzh_decode_stats &ds = ctx->dstats;
     DecWs w;
     BZH_TRY(dec_ws(ctx, w));
-    if (w.T > UR_THREADS) {
-        bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
-        return BZH_E_STATE;
-    }
     StageClock clock{ctx, {}};
     auto mark = [&]() { return clock.mark(); };
     auto span = [&](int stage, hipEvent_t a) { clock.span(stage, a); };
@@ -1137,7 +1141,7 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
     if (sync) {
         sync_cap = std::max<uint32_t>(1u, (BZD_MAX_SEL - 1) / sync->interval);
         const size_t slot_bytes = (size_t)sync_cap * sizeof(bzh_sync_point);
-        sync_slots = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(ctx->max_batch, ctx->arena_blocks), SYNC_REC_BYTES / slot_bytes));
+        sync_slots = (uint32_t)std::max<size_t>(1, std::min<size_t>(batch_max(ctx), SYNC_REC_BYTES / slot_bytes));
         BZH_TRY(reserve_cut(ctx, ctx->sync_ws, "the sync points", grow_mib, [&](Carver &c) { c.put(d_ptcnt, sync_slots); c.put(d_pts, (size_t)sync_slots * sync_cap); }));
     }
     BackCount bc{rec ? rec->delim : 0u, nullptr, nullptr, {}, {}};
@@ -1162,7 +1166,7 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
             ci++;
         }
         if (ci == nc || (cands[ci] >> 1) != pos) return data_error(pos + 48 > nbits ? BZD_K_TRUNC : BZD_K_MAGIC, pos, "neither a block nor a footer");
-        uint32_t B = (uint32_t)std::min<size_t>(std::min<size_t>(ctx->max_batch, ctx->arena_blocks), nc - ci);
+        uint32_t B = (uint32_t)std::min<size_t>(batch_max(ctx), nc - ci);
         if (sync) B = std::min(B, sync_slots);
         hipEvent_t e0 = mark();
         HIP_TRY(ctx, hipMemcpyAsync(w.cand, cands.data() + ci, (size_t)B * 8, hipMemcpyHostToDevice, st));
@@ -1358,10 +1362,6 @@ struct DStreamDev {
         BZH_TRY(arena(ctx, B));
         if (B > ctx->arena_blocks) return BZH_E_STATE;
         BZH_TRY(dec_ws(ctx, w));
-        if (w.T > UR_THREADS) {
-            bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
-            return BZH_E_STATE;
-        }
         HIP_TRY(ctx, hipMemcpyAsync(w.cand, cands, (size_t)B * 8, hipMemcpyHostToDevice, st));
         decode_block_kernel<<<dim3(B), 64, 0, st>>>(win[cur], held, w.cand, ctx->bt, w.res, 100000u * (uint32_t)ctx->level);
         HIP_TRY(ctx, hipGetLastError());
@@ -1491,10 +1491,6 @@ int decode_many_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const size_t *i
     bzh_decode_many_stats &ms = ctx->mstats;
     DecWs w;
     BZH_TRY(dec_ws(ctx, w));
-    if (w.T > UR_THREADS) {
-        bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
-        return BZH_E_STATE;
-    }
     StageClock clock{ctx, {}};
     // the stream headers of all inputs: one launch, one copy back (no sync points in this call: their workspace is free)
     std::vector<BzmInput> ins(count);
@@ -1521,7 +1517,7 @@ int decode_many_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const size_t *i
     walk.count = count;
     walk.ctx_level = ctx->level;
     walk.start();
-    const uint32_t Bmax = (uint32_t)std::min<size_t>(ctx->max_batch, ctx->arena_blocks);
+    const uint32_t Bmax = batch_max(ctx);
     const bool small_on = unbwt_small_enabled();
     const uint32_t small_max = (uint32_t)bzh_decode_many_small_max();
     std::vector<BzdResult> res;
@@ -1633,10 +1629,6 @@ int decode_recover_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_o
     Batch &bt = ctx->bt;
     DecWs w;
     BZH_TRY(dec_ws(ctx, w));
-    if (w.T > UR_THREADS) {
-        bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
-        return BZH_E_STATE;
-    }
     StageClock clock{ctx, {}};
     BzrWalk walk;
     walk.cands = cands.data();
@@ -1646,7 +1638,7 @@ int decode_recover_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_o
     if (n) HIP_TRY(ctx, hipMemcpyAsync(walk.head, d_in, std::min<size_t>(n, 4), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, bzh_stream_wait(st));
     walk.start();
-    const uint32_t Bmax = (uint32_t)std::min<size_t>(ctx->max_batch, ctx->arena_blocks);
+    const uint32_t Bmax = batch_max(ctx);
     std::vector<BzdResult> res;
     std::vector<BackBlock> blocks, sub;
     std::vector<size_t> sub_of; // the block of every listed one
@@ -1832,182 +1824,22 @@ int decode_sync_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count, co
     return BZH_OK;
 }
 
-// (idx has passed decode_index_check)
-int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
-                     uint64_t off, uint64_t len, uint8_t *d_out, size_t cap, size_t *out_len, const bzh_sync_point *pts, size_t npts)
+// The entries first .. last that a read touches lie in the buffer: n bytes of the indexed input from byte in_byte_base on.
+static int index_covered(bzh_ctx *ctx, const bzh_index_entry *idx, size_t first, size_t last, uint64_t in_byte_base, size_t n)
 {
-    hipStream_t st = ctx->stream;
-    Batch &bt = ctx->bt;
-    bzh_decode_stats &ds = ctx->dstats;
-    *out_len = 0;
-    size_t first, last;
-    uint64_t byte_lo, byte_hi, clipped;
-    index_span(idx, count, off, len, &first, &last, &byte_lo, &byte_hi, &clipped);
-    if (clipped == 0) return BZH_OK;
-    if (clipped > cap) {
-        bzh_set_error(ctx, "decode range: the range holds %llu bytes, the buffer %zu", (unsigned long long)clipped, cap);
-        return BZH_E_ARG;
-    }
-    if (in_byte_base > byte_lo || byte_hi - in_byte_base > n) {
-        bzh_set_error(ctx, "decode range: index entries %zu..%zu lie in bytes [%llu, %llu) of the indexed input, the buffer holds [%llu, %llu)",
-                      first, last - 1, (unsigned long long)byte_lo, (unsigned long long)byte_hi, (unsigned long long)in_byte_base,
-                      (unsigned long long)(in_byte_base + n));
-        return BZH_E_ARG;
-    }
-    DecWs w;
-    BZH_TRY(dec_ws(ctx, w));
-    if (w.T > UR_THREADS) {
-        bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
-        return BZH_E_STATE;
-    }
-    StageClock clock{ctx, {}};
-    size_t at = 0; // the entry an error is about
-    auto mismatch = [&](const char *what) {
-        bzh_set_error(ctx, "decode range: index entry %zu (stream %u, bit %llu) does not match its block: %s", at, idx[at].stream,
-                      (unsigned long long)idx[at].bit_pos, what);
-        return BZH_E_DATA;
-    };
-    size_t seg_point = 0; // the sync point a segment's error is about
-    auto seg_mismatch = [&](bool named, const char *what) {
-        if (!named) return mismatch(what);
-        bzh_set_error(ctx, "decode range: index entry %zu (stream %u, bit %llu) does not match its block: sync point %zu: %s", at, idx[at].stream,
-                      (unsigned long long)idx[at].bit_pos, seg_point, what);
-        return BZH_E_DATA;
-    };
-    const uint32_t Bmax = (uint32_t)std::min<size_t>(ctx->max_batch, ctx->arena_blocks);
-    const uint64_t end = off + clipped;
-    std::vector<SegDesc> hseg;
-    std::vector<BzdSegResult> hsres;
-    std::vector<uint32_t> seg0; // [B + 1] first segment of every block of the batch
-    std::vector<uint64_t> hcand;
-    std::vector<BzdResult> res;
-    std::vector<uint32_t> hmagic;
-    std::vector<BackBlock> blocks;
-    Back bk;
-    for (size_t e0 = first; e0 < last;) {
-        const uint32_t B = (uint32_t)std::min<size_t>(Bmax, last - e0);
-        // entropy stage: the entries are the candidates
-        hcand.resize(B);
-        for (uint32_t k = 0; k < B; k++) hcand[k] = (idx[e0 + k].bit_pos - 8 * in_byte_base) << 1;
-        // with sync points: the segments of the batch's blocks, between the points [p0, p1) of its entries
-        size_t p0 = 0, p1 = 0;
-        BzdHead *d_heads = nullptr;
-        bzh_sync_point *d_pts = nullptr;
-        SegDesc *d_segs = nullptr;
-        BzdSegResult *d_sres = nullptr;
-        if (npts) {
-            auto by_entry = [](const bzh_sync_point &p, size_t e) { return (size_t)p.entry < e; };
-            p0 = (size_t)(std::lower_bound(pts, pts + npts, e0, by_entry) - pts);
-            p1 = (size_t)(std::lower_bound(pts + p0, pts + npts, e0 + B, by_entry) - pts);
-            bzp_segments(idx, e0, B, pts, p0, p1, hseg, seg0);
-            BZH_TRY(reserve_cut(ctx, ctx->sync_ws, "the sync points", grow_mib, [&](Carver &c) { // (the stream is idle between batches)
-                c.put(d_heads, B), c.put(d_pts, p1 - p0);               // the batch's headers and its sync points,
-                c.put(d_segs, hseg.size()), c.put(d_sres, hseg.size()); // the segments they cut its blocks into and their results
-            }));
-        }
-        hipEvent_t t1 = clock.mark();
-        HIP_TRY(ctx, hipMemcpyAsync(w.cand, hcand.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
-        if (npts) {
-            if (p1 > p0) HIP_TRY(ctx, hipMemcpyAsync(d_pts, pts + p0, (p1 - p0) * sizeof(bzh_sync_point), hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(d_segs, hseg.data(), hseg.size() * sizeof(SegDesc), hipMemcpyHostToDevice, st));
-            decode_header_kernel<<<dim3(B), 64, 0, st>>>(d_in, n, w.cand, d_heads, w.res);
-            decode_segment_kernel<<<dim3((uint32_t)hseg.size()), 64, 0, st>>>(d_in, n, 8 * in_byte_base, d_heads, d_pts, d_segs, bt, w.res, d_sres);
-        } else {
-            decode_block_kernel<<<dim3(B), 64, 0, st>>>(d_in, n, w.cand, bt, w.res, 100000u * (uint32_t)ctx->level);
-        }
-        range_magic_kernel<<<dim3((B + 63) / 64), 64, 0, st>>>(d_in, n, w.cand, B, w.magic);
-        HIP_TRY(ctx, hipGetLastError());
-        clock.span(1, t1);
-        res.resize(B);
-        hmagic.resize(B);
-        if (npts) {
-            hsres.resize(hseg.size());
-            HIP_TRY(ctx, hipMemcpyAsync(hsres.data(), d_sres, hseg.size() * sizeof(BzdSegResult), hipMemcpyDeviceToHost, st));
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(res.data(), w.res, (size_t)B * sizeof(BzdResult), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(hmagic.data(), w.magic, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, bzh_stream_wait(st));
-        uint32_t nmax = 1;
-        for (uint32_t k = 0; k < B; k++) {
-            at = e0 + k;
-            const bzh_index_entry &e = idx[at];
-            BzdResult &r = res[k];
-            if (hmagic[k]) return mismatch("no block magic at bit_pos");
-            if (r.kind != BZD_OK) return mismatch(kind_name(r.kind));
-            if (npts) { // every segment in order: the first that fails names the point it could not start from or arrive at
-                for (uint32_t g = seg0[k]; g < seg0[k + 1]; g++) {
-                    const BzdSegResult &sr = hsres[g];
-                    const SegDesc &d = hseg[g];
-                    const bool named = d.from >= 0 || d.to >= 0;
-                    if (sr.miss == BZD_SEG_START) {
-                        seg_point = p0 + (size_t)(d.from >= 0 ? d.from : d.to);
-                        return seg_mismatch(named, "it is no state of this block");
-                    }
-                    seg_point = p0 + (size_t)(d.to >= 0 ? d.to : d.from);
-                    if (sr.kind != BZD_OK) return seg_mismatch(named, kind_name(sr.kind));
-                    if (sr.miss == BZD_SEG_EOB) return seg_mismatch(named, "the block ends in front of it");
-                    if (sr.miss == BZD_SEG_ARRIVE) return seg_mismatch(named, "the segment in front of it arrives in another state");
-                    if (d.to < 0) {
-                        r.end_bit = sr.end_bit;
-                        r.nblock = sr.nblock;
-                    }
-                }
-            }
-            if (r.end_bit + 8 * in_byte_base != e.end_bit) return mismatch("it ends at another bit than end_bit");
-            if (r.crc != e.crc) return mismatch("its stored CRC differs");
-            if (r.nblock > 100000u * e.level) return mismatch("more bytes than the level's block size");
-            nmax = std::max(nmax, r.nblock);
-        }
-        ds.blocks += B;
-        blocks.clear();
-        for (uint32_t k = 0; k < B; k++) blocks.push_back(BackBlock{k, res[k].nblock, 0, false, 0, 0, 0, 0});
-        BZH_TRY(back_sizes(ctx, w, clock, bk, B, nmax, blocks));
-        for (uint32_t k = 0; k < B; k++) {
-            at = e0 + k;
-            const bzh_index_entry &e = idx[at];
-            BackBlock &b = blocks[k];
-            if (b.bad_end) return mismatch("the block ends in four equal bytes without a count");
-            if (b.size != e.out_len) return mismatch("it decodes to another size than out_len");
-            // the window of the range inside this block; a block wholly inside is expanded where it belongs and checked there
-            bzp_window(e.out_off, e.out_len, off, end, &b.lo, &b.hi);
-            b.base = (int64_t)e.out_off - (int64_t)off;
-        }
-        BZH_TRY(back_emit(ctx, w, clock, bk, d_out, true, blocks));
-        for (int cut = 0; cut < 2; cut++) // (the whole blocks first)
-            for (uint32_t k = 0; k < B; k++) {
-                const BackBlock &b = blocks[k];
-                if (b.whole() != (cut == 0) || b.crc == idx[e0 + k].crc) continue;
-                at = e0 + k;
-                return mismatch(kind_name(BZD_K_BLOCK_CRC));
-            }
-        e0 += B;
-    }
-    clock.collect();
-    ds.out_bytes = clipped;
-    *out_len = (size_t)clipped;
-    return BZH_OK;
+    const uint64_t byte_lo = idx[first].bit_pos / 8, byte_hi = (idx[last].end_bit + 7) / 8;
+    if (in_byte_base <= byte_lo && byte_hi - in_byte_base <= n) return BZH_OK;
+    bzh_set_error(ctx, "decode range: index entries %zu..%zu lie in bytes [%llu, %llu) of the indexed input, the buffer holds [%llu, %llu)",
+                  first, last, (unsigned long long)byte_lo, (unsigned long long)byte_hi, (unsigned long long)in_byte_base,
+                  (unsigned long long)(in_byte_base + n));
+    return BZH_E_ARG;
 }
 
-// ================================================================================================================
-// Many ranges in one call (bzh_decode_ranges*): decode_range_run over a list of entries, each block decoded once
-// ================================================================================================================
-extern "C" int bzh_index_spans(const bzh_index_entry *idx, size_t count, const bzh_range *ranges, size_t nranges, uint32_t *touched,
-                               size_t max, size_t *ntouched, uint64_t *byte_lo, uint64_t *byte_hi, uint64_t *out_total)
-{
-    if ((!idx && count) || (!ranges && nranges) || (!touched && max) || !ntouched || !byte_lo || !byte_hi || !out_total) return BZH_E_ARG;
-    if (count > 0xFFFFFFFFull) return BZH_E_ARG;
-    std::vector<uint32_t> list;
-    *out_total = bzp_spans(idx, count, ranges, nranges, nullptr, nullptr, list, byte_lo, byte_hi);
-    *ntouched = list.size();
-    if (list.size() > max) return BZH_E_CAP;
-    if (!list.empty()) memcpy(touched, list.data(), list.size() * sizeof(uint32_t));
-    return BZH_OK;
-}
-
-// The front of a batch of a read by index entries (decode_ranges_run, decode_records_run): the entropy stage of the entries
-// idx[ent[0 .. B)] -- ascending, block k in batch slot k --, every block checked against its entry, then back_sizes and the sizes
-// checked too.  BZH_E_DATA names the first entry that fails, in bzh_decode_range's words.  count: back_sizes' (null: none).
-struct RangeFront {
+// The front of a batch of every read by index (decode_range_run, decode_ranges_run, decode_records_run): the entropy stage of the
+// entries idx[ent[0 .. B)] -- ascending, block k in batch slot k --, every block checked against its entry, then back_sizes and the
+// sizes checked too.  BZH_E_DATA names the first entry that fails, and a sync point by its number in pts.  count: back_sizes' (null:
+// none).  The caller sets the blocks' windows (or asks `pieces` for them), calls back_emit and then `crcs`.
+struct IndexedFront {
     bzh_ctx *ctx;
     const DecWs &w;
     StageClock &clock;
@@ -2176,17 +2008,125 @@ struct RangeFront {
         }
         return BZH_OK;
     }
-    // behind back_emit: every block's CRC against its entry's (ascending: the first entry that fails is named)
-    int crcs(const uint32_t *ent, uint32_t B)
+    // behind back_emit: every block's CRC against its entry's, the first entry that fails named -- ascending, or (whole_first: the
+    // single range) the whole blocks in front of the cut ones
+    int crcs(const uint32_t *ent, uint32_t B, bool whole_first = false)
     {
-        for (uint32_t k = 0; k < B; k++) {
-            if (blocks[k].crc == idx[ent[k]].crc) continue;
-            at = ent[k];
-            return mismatch(kind_name(BZD_K_BLOCK_CRC));
-        }
+        for (int cut = 0; cut < (whole_first ? 2 : 1); cut++)
+            for (uint32_t k = 0; k < B; k++) {
+                if ((whole_first && blocks[k].whole() != (cut == 0)) || blocks[k].crc == idx[ent[k]].crc) continue;
+                at = ent[k];
+                return mismatch(kind_name(BZD_K_BLOCK_CRC));
+            }
         return BZH_OK;
     }
 };
+
+// (idx has passed decode_index_check -- a range that holds bytes touches an entry --, pts decode_sync_check; count < 2^32)
+int decode_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                     uint64_t off, uint64_t len, uint8_t *d_out, size_t cap, size_t *out_len, const bzh_sync_point *pts, size_t npts)
+{
+    bzh_decode_stats &ds = ctx->dstats;
+    *out_len = 0;
+    size_t first, last;
+    uint64_t byte_lo, byte_hi, clipped;
+    index_span(idx, count, off, len, &first, &last, &byte_lo, &byte_hi, &clipped);
+    if (clipped == 0) return BZH_OK;
+    if (clipped > cap) {
+        bzh_set_error(ctx, "decode range: the range holds %llu bytes, the buffer %zu", (unsigned long long)clipped, cap);
+        return BZH_E_ARG;
+    }
+    BZH_TRY(index_covered(ctx, idx, first, last - 1, in_byte_base, n));
+    DecWs w;
+    BZH_TRY(dec_ws(ctx, w));
+    StageClock clock{ctx, {}};
+    const uint32_t Bmax = batch_max(ctx);
+    const uint64_t end = off + clipped;
+    std::vector<uint32_t> touched(last - first); // first .. last - 1
+    for (size_t t = 0; t < touched.size(); t++) touched[t] = (uint32_t)(first + t);
+    IndexedFront fr{ctx, w, clock, d_in, n, in_byte_base, idx, pts, npts};
+    for (size_t t0 = 0; t0 < touched.size();) {
+        const uint32_t B = (uint32_t)std::min<size_t>(Bmax, touched.size() - t0);
+        const uint32_t *ent = touched.data() + t0;
+        BZH_TRY(fr.run(ent, B));
+        for (uint32_t k = 0; k < B; k++) {
+            // the window of the range inside this block; a block wholly inside is expanded where it belongs and checked there
+            const bzh_index_entry &e = idx[ent[k]];
+            BackBlock &b = fr.blocks[k];
+            bzp_window(e.out_off, e.out_len, off, end, &b.lo, &b.hi);
+            b.base = (int64_t)e.out_off - (int64_t)off;
+        }
+        BZH_TRY(back_emit(ctx, w, clock, fr.bk, d_out, true, fr.blocks));
+        BZH_TRY(fr.crcs(ent, B, true));
+        t0 += B;
+    }
+    clock.collect();
+    ds.out_bytes = clipped;
+    *out_len = (size_t)clipped;
+    return BZH_OK;
+}
+
+// ================================================================================================================
+// Many ranges in one call (bzh_decode_ranges*): the front over the union of the ranges' entries, each block decoded once
+// ================================================================================================================
+extern "C" int bzh_index_spans(const bzh_index_entry *idx, size_t count, const bzh_range *ranges, size_t nranges, uint32_t *touched,
+                               size_t max, size_t *ntouched, uint64_t *byte_lo, uint64_t *byte_hi, uint64_t *out_total)
+{
+    if ((!idx && count) || (!ranges && nranges) || (!touched && max) || !ntouched || !byte_lo || !byte_hi || !out_total) return BZH_E_ARG;
+    if (count > 0xFFFFFFFFull) return BZH_E_ARG;
+    std::vector<uint32_t> list;
+    *out_total = bzp_spans(idx, count, ranges, nranges, nullptr, nullptr, list, byte_lo, byte_hi);
+    *ntouched = list.size();
+    if (list.size() > max) return BZH_E_CAP;
+    if (!list.empty()) memcpy(touched, list.data(), list.size() * sizeof(uint32_t));
+    return BZH_OK;
+}
+
+#ifdef BZH_EXPERIMENTS
+// scripts/gpu_ranges.py: the pieces of a batch (IndexedFront::pieces has listed them) through unrle_walk_win, a grid row each, to
+// set beside unrle_walk_pieces.  Behind back_emit, which was given no pieces; one wait more.
+static int pieces_by_window(bzh_ctx *ctx, const IndexedFront &fr)
+{
+    hipStream_t st = ctx->stream;
+    std::vector<uint32_t> xs, xlo, xhi;
+    std::vector<int64_t> xbase;
+    for (size_t k = 0; k + 1 < fr.pf.size(); k++)
+        for (size_t q = fr.pf[k]; q < fr.pf[k + 1]; q++) {
+            xs.push_back(fr.pslots[k]), xlo.push_back(fr.bpc[q].lo), xhi.push_back(fr.bpc[q].hi);
+            xbase.push_back((int64_t)fr.bpc[q].base - (int64_t)fr.bpc[q].lo);
+        }
+    const uint32_t P = (uint32_t)fr.bpc.size();
+    if (!P) return BZH_OK;
+    uint32_t *d_xs = nullptr, *d_xlo = nullptr, *d_xhi = nullptr;
+    int64_t *d_xbase = nullptr;
+    BZH_TRY(reserve_cut(ctx, ctx->ranges_ws, "the pieces of the ranges", grow_mib,
+                        [&](Carver &c) { c.put(d_xbase, P), c.put(d_xs, P), c.put(d_xlo, P), c.put(d_xhi, P); }));
+    HIP_TRY(ctx, hipMemcpyAsync(d_xs, xs.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_xlo, xlo.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_xhi, xhi.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_xbase, xbase.data(), (size_t)P * 8, hipMemcpyHostToDevice, st));
+    UrArgs ax = fr.bk.a; // (out: back_emit has set it)
+    ax.slots = d_xs;
+    unrle_walk_win<<<dim3(fr.bk.Tn, P), UR_THREADS, 0, st>>>(ax, UwArgs{d_xlo, d_xhi, d_xbase, nullptr, nullptr, nullptr, nullptr});
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, bzh_stream_wait(st));
+    return BZH_OK;
+}
+#endif
+
+// back_emit for a batch of decode_ranges_run.  A build with BZH_EXPERIMENTS sends the pieces through pieces_by_window instead
+// where BZH_RANGES_WIN is set.
+static int ranges_emit(bzh_ctx *ctx, const DecWs &w, StageClock &clock, IndexedFront &fr, uint8_t *d_out, BackPieces &bp)
+{
+#ifdef BZH_EXPERIMENTS
+    if (bp.K && getenv("BZH_RANGES_WIN")) {
+        bp.K = 0;
+        BZH_TRY(back_emit(ctx, w, clock, fr.bk, d_out, true, fr.blocks, false, &bp));
+        return pieces_by_window(ctx, fr);
+    }
+#endif
+    return back_emit(ctx, w, clock, fr.bk, d_out, true, fr.blocks, false, &bp);
+}
 
 // (idx has passed decode_index_check, pts decode_sync_check; touched and out_offs are bzp_spans', whose sum is out_total <= the
 // room at d_out)
@@ -2197,19 +2137,9 @@ int decode_ranges_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_b
     bzh_decode_stats &ds = ctx->dstats;
     bzh_decode_ranges_stats &qs = ctx->qstats;
     if (touched.empty()) return BZH_OK;
-    const uint64_t byte_lo = idx[touched.front()].bit_pos / 8, byte_hi = (idx[touched.back()].end_bit + 7) / 8;
-    if (in_byte_base > byte_lo || byte_hi - in_byte_base > n) {
-        bzh_set_error(ctx, "decode range: index entries %zu..%zu lie in bytes [%llu, %llu) of the indexed input, the buffer holds [%llu, %llu)",
-                      (size_t)touched.front(), (size_t)touched.back(), (unsigned long long)byte_lo, (unsigned long long)byte_hi,
-                      (unsigned long long)in_byte_base, (unsigned long long)(in_byte_base + n));
-        return BZH_E_ARG;
-    }
+    BZH_TRY(index_covered(ctx, idx, touched.front(), touched.back(), in_byte_base, n));
     DecWs w;
     BZH_TRY(dec_ws(ctx, w));
-    if (w.T > UR_THREADS) {
-        bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
-        return BZH_E_STATE;
-    }
     // what every range wants of every touched block
     std::vector<size_t> pfirst;
     std::vector<PieceRef> pc;
@@ -2217,10 +2147,8 @@ int decode_ranges_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_b
     bzp_block_pieces(idx, count, ranges, nranges, out_offs, touched, pfirst, pc, prange);
     qs.pieces = pc.size();
     StageClock clock{ctx, {}};
-    const uint32_t Bmax = (uint32_t)std::min<size_t>(ctx->max_batch, ctx->arena_blocks);
-    RangeFront fr{ctx, w, clock, d_in, n, in_byte_base, idx, pts, npts};
-    std::vector<BackBlock> &blocks = fr.blocks;
-    Back &bk = fr.bk;
+    const uint32_t Bmax = batch_max(ctx);
+    IndexedFront fr{ctx, w, clock, d_in, n, in_byte_base, idx, pts, npts};
     for (size_t t0 = 0; t0 < touched.size();) {
         const uint32_t B = (uint32_t)std::min<size_t>(Bmax, touched.size() - t0);
         const uint32_t *ent = touched.data() + t0;
@@ -2228,41 +2156,7 @@ int decode_ranges_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_b
         BZH_TRY(fr.run(ent, B));
         BackPieces bp;
         BZH_TRY(fr.pieces(pfirst.data() + t0, pc, B, out_total, bp, &qs.blocks_whole));
-#ifdef BZH_EXPERIMENTS
-        // scripts/gpu_ranges.py: the pieces through unrle_walk_win, a grid row each, to set beside unrle_walk_pieces
-        hipStream_t st = ctx->stream;
-        const std::vector<uint32_t> &pslots = fr.pslots;
-        const std::vector<size_t> &pf = fr.pf;
-        const std::vector<PieceRef> &bpc = fr.bpc;
-        const bool by_window = bp.K && getenv("BZH_RANGES_WIN");
-        const uint32_t P = by_window ? (uint32_t)bpc.size() : 0;
-        if (by_window) bp.K = 0;
-#endif
-        BZH_TRY(back_emit(ctx, w, clock, bk, d_out, true, blocks, false, &bp));
-#ifdef BZH_EXPERIMENTS
-        if (P) {
-            std::vector<uint32_t> xs, xlo, xhi;
-            std::vector<int64_t> xbase;
-            for (size_t k = 0; k + 1 < pf.size(); k++)
-                for (size_t q = pf[k]; q < pf[k + 1]; q++) {
-                    xs.push_back(pslots[k]), xlo.push_back(bpc[q].lo), xhi.push_back(bpc[q].hi);
-                    xbase.push_back((int64_t)bpc[q].base - (int64_t)bpc[q].lo);
-                }
-            uint32_t *d_xs = nullptr, *d_xlo = nullptr, *d_xhi = nullptr;
-            int64_t *d_xbase = nullptr;
-            BZH_TRY(reserve_cut(ctx, ctx->ranges_ws, "the pieces of the ranges", grow_mib,
-                                [&](Carver &c) { c.put(d_xbase, P), c.put(d_xs, P), c.put(d_xlo, P), c.put(d_xhi, P); }));
-            HIP_TRY(ctx, hipMemcpyAsync(d_xs, xs.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(d_xlo, xlo.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(d_xhi, xhi.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(d_xbase, xbase.data(), (size_t)P * 8, hipMemcpyHostToDevice, st));
-            UrArgs ax = bk.a;
-            ax.slots = d_xs;
-            unrle_walk_win<<<dim3(bk.Tn, P), UR_THREADS, 0, st>>>(ax, UwArgs{d_xlo, d_xhi, d_xbase, nullptr, nullptr, nullptr, nullptr});
-            HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, bzh_stream_wait(st));
-        }
-#endif
+        BZH_TRY(ranges_emit(ctx, w, clock, fr, d_out, bp));
         BZH_TRY(fr.crcs(ent, B));
         t0 += B;
     }
@@ -2305,26 +2199,16 @@ int decode_records_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_
     }
     bool over = false;
     if (!touched.empty()) {
-        const uint64_t byte_lo = idx[touched.front()].bit_pos / 8, byte_hi = (idx[touched.back()].end_bit + 7) / 8;
-        if (in_byte_base > byte_lo || byte_hi - in_byte_base > n) {
-            bzh_set_error(ctx, "decode range: index entries %zu..%zu lie in bytes [%llu, %llu) of the indexed input, the buffer holds [%llu, %llu)",
-                          (size_t)touched.front(), (size_t)touched.back(), (unsigned long long)byte_lo, (unsigned long long)byte_hi,
-                          (unsigned long long)in_byte_base, (unsigned long long)(in_byte_base + n));
-            return BZH_E_ARG;
-        }
+        BZH_TRY(index_covered(ctx, idx, touched.front(), touched.back(), in_byte_base, n));
         DecWs w;
         BZH_TRY(dec_ws(ctx, w));
-        if (w.T > UR_THREADS) {
-            bzh_set_error(ctx, "decode: %u tiles a block exceed the walk kernel's %u threads (internal error)", w.T, UR_THREADS);
-            return BZH_E_STATE;
-        }
         BackCount bc{delim, nullptr, nullptr, {}, {}};
         BzqQuery *d_q = nullptr;
         uint32_t *d_pos = nullptr;
         BZH_TRY(back_count_ws(ctx, bc, walk.bounds.size(), &d_q, &d_pos));
         StageClock clock{ctx, {}};
-        const uint32_t Bmax = (uint32_t)std::min<size_t>(ctx->max_batch, ctx->arena_blocks);
-        RangeFront fr{ctx, w, clock, d_in, n, in_byte_base, idx, pts, npts};
+        const uint32_t Bmax = batch_max(ctx);
+        IndexedFront fr{ctx, w, clock, d_in, n, in_byte_base, idx, pts, npts};
         std::vector<uint32_t> ntiles, hpos;
         std::vector<BzqQuery> hq;
         std::vector<size_t> pfirst;

@@ -41,31 +41,11 @@ static inline bool bzp_window(uint64_t out_off, uint32_t out_len, uint64_t off, 
     return *lo == 0 && *hi == out_len;
 }
 
-// The segments of the B blocks of a batch, entries idx[e0 .. e0 + B), between the sync points pts[p0 .. p1) of those entries
-// (ascending by entry; E: bzh_index_entry, P: bzh_sync_point).  A block with c points has c + 1 consecutive segments, header ->
-// first point -> .. -> end of block; from / to count from p0.  seg0[k] = the first segment of block k, seg0[B] = their number.
-template <class E, class P>
-static inline void bzp_segments(const E *idx, size_t e0, uint32_t B, const P *pts, size_t p0, size_t p1, std::vector<SegDesc> &segs,
-                                std::vector<uint32_t> &seg0)
-{
-    segs.clear();
-    seg0.assign((size_t)B + 1, 0);
-    size_t q = p0;
-    for (uint32_t k = 0; k < B; k++) {
-        seg0[k] = (uint32_t)segs.size();
-        const uint32_t bmax = 100000u * idx[e0 + k].level;
-        int32_t prev = -1;
-        for (; q < p1 && pts[q].entry == e0 + k; q++) {
-            segs.push_back({k, prev, (int32_t)(q - p0), bmax});
-            prev = (int32_t)(q - p0);
-        }
-        segs.push_back({k, prev, -1, bmax});
-    }
-    seg0[B] = (uint32_t)segs.size();
-}
-
-// The same for a batch whose blocks are the entries idx[ent[0 .. B)] (ascending, not necessarily adjacent) and whose points are
-// gathered: pmap[j] = the point of pts[0 .. npts) that lies at j of the gathered array, which from / to count in.
+// The segments of the B blocks of a batch, the entries idx[ent[0 .. B)] (ascending, not necessarily adjacent), between those of
+// the sync points pts[0 .. npts) that belong to them (ascending by entry; E: bzh_index_entry, P: bzh_sync_point).  A block with c
+// points has c + 1 consecutive segments, header -> first point -> .. -> end of block.  seg0[k] = the first segment of block k,
+// seg0[B] = their number.  The batch's points are gathered: pmap[j] = the point of pts that lies at j of the gathered array, which
+// from / to count in (adjacent entries: pmap[j] = pmap[0] + j).
 template <class E, class P>
 static inline void bzp_segments(const E *idx, const uint32_t *ent, uint32_t B, const P *pts, size_t npts, std::vector<SegDesc> &segs,
                                 std::vector<uint32_t> &seg0, std::vector<size_t> &pmap)

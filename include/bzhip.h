@@ -353,7 +353,7 @@ BZH_API int bzh_index_span(const bzh_index_entry *idx, size_t count, uint64_t of
  * expanded in place, the at most two blocks at its edges are clipped to it.  The host variant uploads only the span.
  * BZH_E_ARG, with bzh_last_error naming the entry: an index that is not well formed (bit_pos not ascending, end_bit <= bit_pos,
  * out_off not the running sum from 0, a level outside 1..9 or above the context's), a buffer that does not cover the span, a
- * cap below the bytes to write.  BZH_E_DATA, naming the entry and the check, when a touched block does not match its entry: no
+ * cap below the bytes to write; also for 2^32 entries or more.  BZH_E_DATA, naming the entry and the check, when a touched block does not match its entry: no
  * block magic at bit_pos, another end_bit, stored CRC or decoded size, more bytes than its level allows, an end in four equal
  * bytes without a count, a computed CRC that differs from the stored one.
  * WHAT IS VERIFIED: the CRC of every touched block, over all of its bytes.  Stream CRCs are NOT verified (they need every

@@ -153,10 +153,15 @@ static void segments_case(size_t e0, const std::vector<uint32_t> &per, uint32_t 
     }
     std::vector<SegDesc> segs(3, SegDesc{9, 9, 9, 9}); // (what an earlier batch left)
     std::vector<uint32_t> seg0(1, 5);
-    bzp_segments(idx.data(), e0, B, pts.data(), p0, p1, segs, seg0);
+    std::vector<size_t> pmap(2, 7);
+    std::vector<uint32_t> ent(B); // e0 .. e0 + B - 1
+    for (uint32_t k = 0; k < B; k++) ent[k] = (uint32_t)(e0 + k);
+    bzp_segments(idx.data(), ent.data(), B, pts.data(), pts.size(), segs, seg0, pmap);
     CHECK(seg0.size() == (size_t)B + 1 && seg0[0] == 0 && seg0[B] == segs.size(), "seg0 of %zu for %u blocks, ends at %u of %zu", seg0.size(), B,
           seg0.empty() ? 0 : seg0.back(), segs.size());
     CHECK(segs.size() == B + (p1 - p0), "%zu segments for %u blocks and %zu points", segs.size(), B, p1 - p0);
+    CHECK(pmap.size() == p1 - p0, "%zu points gathered of %zu", pmap.size(), p1 - p0);
+    for (size_t j = 0; j < pmap.size(); j++) CHECK(pmap[j] == p0 + j, "gathered point %zu is point %zu, not %zu", j, pmap[j], p0 + j);
     int32_t next_point = 0; // points are used once each, in order
     for (uint32_t k = 0; k < B; k++) {
         CHECK(seg0[k + 1] - seg0[k] == per[k] + 1, "block %u with %u points has %u segments", k, per[k], seg0[k + 1] - seg0[k]);
@@ -167,7 +172,7 @@ static void segments_case(size_t e0, const std::vector<uint32_t> &per, uint32_t 
                   d.block_max, k, idx[e0 + k].level);
             CHECK(d.from == from, "segment %u of block %u starts at point %d, the one in front of it ends at %d", g, k, d.from, from);
             if (g + 1 < seg0[k + 1]) {
-                CHECK(d.to == next_point && (size_t)d.to < p1 - p0 && pts[p0 + (size_t)d.to].entry == e0 + k, "segment %u of block %u ends at point %d", g, k, d.to);
+                CHECK(d.to == next_point && (size_t)d.to < pmap.size() && pts[pmap[(size_t)d.to]].entry == e0 + k, "segment %u of block %u ends at point %d", g, k, d.to);
                 next_point++;
             } else {
                 CHECK(d.to == -1, "the last segment of block %u ends at point %d", k, d.to);

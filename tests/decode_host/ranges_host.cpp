@@ -1,6 +1,6 @@
 // ranges_host.cpp -- the host arithmetic of a call over many ranges (banzai_amd/csrc/decode_plan.h: bzp_spans, which is
 // bzh_index_spans and the output layout of bzh_decode_ranges; bzp_block_pieces and bzp_pieces, which tell unrle_walk_pieces what to
-// store where; the entry-list form of bzp_segments) against brute force, built with g++ -fsanitize=address,undefined.  The brute
+// store where; bzp_segments over a list of entries) against brute force, built with g++ -fsanitize=address,undefined.  The brute
 // force is per output byte: which ranges want it, and where it goes.  The decoded bytes of the synthetic index are their own
 // positions, so a byte in the wrong place shows as a wrong value.
 //
@@ -244,19 +244,14 @@ static void segments_case(uint32_t count, uint32_t maxpts, bool adjacent)
         }
     }
     CHECK(j == pmap.size(), "%zu gathered points, %zu met", pmap.size(), j);
-    if (adjacent && !ent.empty()) { // the same batch through the form decode_range_run uses
+    if (adjacent && !ent.empty()) { // a single range's batch: its points are the run [p0, p1) of the array, every one of them used
         size_t p0 = 0, p1 = 0;
         while (p0 < pts.size() && pts[p0].entry < ent.front()) p0++;
         for (p1 = p0; p1 < pts.size() && pts[p1].entry <= ent.back(); p1++) {}
-        std::vector<SegDesc> segs2;
-        std::vector<uint32_t> seg02;
-        bzp_segments(idx.data(), (size_t)ent.front(), (uint32_t)ent.size(), pts.data(), p0, p1, segs2, seg02);
-        CHECK(seg02 == seg0 && segs2.size() == segs.size(), "the two forms differ in shape");
-        for (size_t g = 0; g < segs.size(); g++)
-            CHECK(segs2[g].slot == segs[g].slot && segs2[g].from == segs[g].from && segs2[g].to == segs[g].to &&
-                      segs2[g].block_max == segs[g].block_max,
-                  "the two forms differ at segment %zu", g);
+        CHECK(pmap.size() == p1 - p0 && segs.size() == ent.size() + (p1 - p0), "%zu points gathered and %zu segments for %zu blocks and %zu points",
+              pmap.size(), segs.size(), ent.size(), p1 - p0);
         for (size_t q = 0; q < pmap.size(); q++) CHECK(pmap[q] == p0 + q, "an adjacent batch's points are not a run");
+        // (so from / to, which the loop above has held to the gathered numbering, are the points' numbers counted from p0)
     }
 }
 

@@ -447,3 +447,27 @@ def test_mismatch_is_a_status(dec, native, four):
     for e in (e_full, e_index, e_py):
         assert e.value.status == -6 and "block CRC mismatch" in str(e.value) and "block 2" in str(e.value)
     assert dec.decode_index(s)[0].tobytes() == ent.tobytes()
+
+
+def test_crc_verdict_order(dec, native, four):
+    """Two blocks of one batch whose computed CRCs differ from their entries': a single range reads the verdicts of the whole
+    blocks first, then those of the cut ones; decode_ranges reads them in ascending entry order."""
+    s, truth, ent = four
+    damaged = bytearray(s)
+    for k in (0, 1):  # one flipped bit in the stored CRC of blocks 0 and 1 ...
+        flip = int(ent[k]["bit_pos"]) + 48 + 13
+        damaged[flip // 8] ^= 0x80 >> (flip % 8)
+    damaged = bytes(damaged)
+    trusting = ent.copy()
+    for k in (0, 1):  # ... and the damaged CRCs in the entries as well: the computed CRC is what differs
+        trusting["crc"][k] = bits_at(damaged, int(ent[k]["bit_pos"]) + 48, 32)
+    off = int(ent[0]["out_off"]) + 5  # block 0 cut at its head, block 1 whole
+    n = int(ent[2]["out_off"]) - off
+    with pytest.raises(native.BzhError) as e:
+        dec.decode_range(damaged, trusting, off, n)
+    assert e.value.status == -6 and "block CRC mismatch" in str(e.value) and "index entry 1 " in str(e.value), str(e.value)
+    assert dec.decode_range(s, ent, 5, 20) == truth[5:25]  # the context goes on
+    with pytest.raises(native.BzhError) as e:
+        dec.decode_ranges(damaged, trusting, [(off, n)])
+    assert e.value.status == -6 and "block CRC mismatch" in str(e.value) and "index entry 0 " in str(e.value), str(e.value)
+    assert dec.decode_range(s, ent, 5, 20) == truth[5:25]

@@ -127,6 +127,25 @@ def test_single_range_and_whole_blocks(dec, four):
     assert st["blocks_whole"] == 1 and st["blocks_touched"] == 2
 
 
+def test_one_range_is_one_range(dec, four):
+    """decode_range[_sync] and decode_ranges of the same one range: the same bytes, the truth's, with and without sync points"""
+    s, truth, ent, pts = four
+    b1, n1 = int(ent[1]["out_off"]), int(ent[1]["out_len"])
+    b2, n2 = int(ent[2]["out_off"]), int(ent[2]["out_len"])
+    windows = [(b1, n1),                  # a whole block
+               (b1 + 5, n1 - 5),          # a block cut at its head
+               (b1, n1 - 5),              # a block cut at its tail
+               (b1 + n1 // 2, 10),        # 10 bytes inside one block
+               (0, len(truth)),           # the whole output: two batches
+               (b1 + 100, n1 + n2 // 2)]  # from inside block 1 to inside block 2: a batch of two cut blocks
+    assert b1 + 100 + n1 + n2 // 2 < b2 + n2
+    for points in (None, pts):
+        for off, n in windows:
+            one = dec.decode_range(s, ent, off, n) if points is None else dec.decode_range_sync(s, ent, points, off, n)
+            blob, offs, lens = dec.decode_ranges(s, ent, [(off, n)], points)
+            assert one == blob == truth[off:off + n] and offs == [0] and lens == [n], (off, n, points is not None)
+
+
 # ---- 4. several streams ----------------------------------------------------------------------------------------------
 def test_several_streams(dec):
     a, b = text(250_000, 51), text(300_000, 52)

@@ -303,3 +303,34 @@ def test_wrong_points_are_a_status(dec, native, model):
         dec.decode_range_sync(s, ent, opts, 0, total)
     assert e.value.status in (-1, -6)
     assert dec.decode_range_sync(s, ent, pts, 0, total) == truth
+
+
+def test_wrong_point_behind_the_first_batch(native, model):
+    """the same flips in the blocks of a second batch (4 blocks, 2 a batch): the message names the point by its number in the
+    caller's array, not by its number among the batch's points"""
+    exe, tmp = model
+    s = bz2.compress(text(350_000, 41), 1)
+    truth = bz2.decompress(s)
+    res, _ = sync_model.run(exe, tmp, [s], 16)
+    blocks, wpts, flips, _ = res[0]
+    with native.Context(0, 1, 2) as c2:
+        ent, pts, total, _ = c2.decode_index_sync(s, 16)
+        assert pts.tobytes() == wpts.tobytes() and blocks == len(ent) == 4
+        by_field = {}
+        for point, byte, bit in flips:  # one flip for every field and point of entries 2 and 3 the model reached
+            if int(pts["entry"][point]) < 2:
+                continue
+            field = "mtf" if byte >= 32 else ("bit_pos" if byte < 8 else ("entry", "group", "out_pos", "run", "run_weight", "reserved")[(byte - 8) // 4])
+            by_field.setdefault((field, point), (point, byte, bit))
+        chosen = sorted(by_field.values())
+        chosen = chosen[::max(1, len(chosen) // 6)][:8]
+        assert len(chosen) >= 4 and {int(pts["entry"][c[0]]) for c in chosen} == {2, 3}
+        assert int(np.flatnonzero(pts["entry"] >= 2)[0]) > 0  # (the batch's first point is not the array's)
+        for point, byte, bit in chosen:
+            bad = pts.copy()
+            bad.view(np.uint8).reshape(len(pts), 288)[point, byte] ^= 1 << bit
+            entry = int(pts["entry"][point])
+            with pytest.raises(native.BzhError) as e:
+                c2.decode_range_sync(s, ent, bad, 0, total)
+            assert e.value.status == -6 and f"index entry {entry} " in str(e.value) and f"sync point {point}:" in str(e.value), (point, byte, bit, str(e.value))
+            assert c2.decode_range_sync(s, ent, pts, 5, 20) == truth[5:25]  # the context goes on

@@ -1,6 +1,6 @@
 """CPU: the host arithmetic of a call over many ranges (banzai_amd/csrc/decode_plan.h -- bzp_spans, which is bzh_index_spans and the
-output layout of bzh_decode_ranges; bzp_block_pieces and bzp_pieces, the tables unrle_walk_pieces stores by; the entry-list form
-of bzp_segments) against brute force per output byte, as a stand-alone program with AddressSanitizer and UBSan
+output layout of bzh_decode_ranges; bzp_block_pieces and bzp_pieces, the tables unrle_walk_pieces stores by; bzp_segments
+over a list of entries) against brute force per output byte, as a stand-alone program with AddressSanitizer and UBSan
 (tests/decode_host/ranges_host.cpp).  What these compute are destinations of stores on the device.  And what unrle_walk_pieces
 does with those tables, thread by thread in the kernel's layout, from the text it shares with the kernel -- decode_core.h's
 bzd_ur_emit and bzd_piece_cut -- against the serial expansion (tests/decode_host/pieces_host.cpp)."""
