@@ -45,7 +45,7 @@ import numpy as np
 
 from . import _native
 
-__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex", "RecordIndex", "build_record_index", "record_index_of", "decompress_records",
+__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex", "RecordIndex", "build_record_index", "record_index_of", "decompress_records", "search", "search_range",
            "IndexedReader", "build_sync_index", "SyncIndex", "encode_indexed", "encode_indexed_stream", "recover", "recover_stream", "Recovered", "RecoveredBlock", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
@@ -988,6 +988,51 @@ def decompress_records(data, rindex, ranges, device=0):
     return _read_records(_record_index_arg(rindex), ranges, lambda lo, hi: view[lo:hi], device)
 
 
+def _pattern_arg(pattern):
+    if not isinstance(pattern, (bytes, bytearray, memoryview)):
+        raise TypeError(f"pattern must be bytes-like, not {type(pattern).__name__}")
+    pattern = bytes(pattern)
+    if not 1 <= len(pattern) <= _native.SEARCH_MAX_PATTERN:
+        raise ValueError(f"pattern must hold 1..{_native.SEARCH_MAX_PATTERN} bytes, not {len(pattern)}")
+    return pattern
+
+
+def _limit_arg(limit):
+    return None if limit is None else _int_arg(limit, "limit")
+
+
+def search(data, pattern, delim=None, limit=None, device=0):
+    """Every occurrence of the byte string `pattern` (1..256 bytes) in the DECODED bytes of `data` (bytes-like .bz2 stream(s)),
+    overlapping ones included -> (hits, nhits): hits is a structured array with fields `off` (the offset in the decoded output)
+    and `record`, ascending; nhits the exact count.  With `delim` (one byte) `record` is the number of delimiters in front of the
+    hit -- the record number read_records takes --, else 0.  `limit` caps the hits returned, not the count.  The decoded bytes
+    stay on the device, and everything decompress verifies is verified (bzh_search)."""
+    view = _bytes_view(data, "search")
+    d = None if delim is None else _delim_arg(delim)
+    return _ctx(9, device).search(view, _pattern_arg(pattern), d, _limit_arg(limit))
+
+
+def _search_range(index, fetch, pattern, offset, length, limit, device):
+    """search_range over `fetch(lo, hi)`, which hands over bytes [lo, hi) of the compressed source"""
+    rindex = index if isinstance(index, RecordIndex) else None
+    index = _index_arg(rindex.index if rindex is not None else index)
+    pattern, limit = _pattern_arg(pattern), _limit_arg(limit)
+    offset = _int_arg(offset, "offset")
+    length = max(0, index.size - offset) if length is None else _int_arg(length, "length")
+    _, _, lo, hi = index.span(offset, length)
+    return _ctx(9, device).search_range(fetch(lo, hi), index.entries, pattern, offset, length, _points_arg(index),
+                                        rindex.rec_cum if rindex is not None else None, rindex.delim if rindex is not None else None,
+                                        limit, in_byte_base=lo)
+
+
+def search_range(data, index, pattern, offset=0, length=None, limit=None, device=0):
+    """search() inside decoded bytes [offset, offset + length) of the indexed `data`: the hits that lie wholly inside the range,
+    from only the blocks it touches, each decoded once and verified against its entry (bzh_search_range).  `index` is a
+    BlockIndex, a SyncIndex or a RecordIndex; record numbers come when it is a RecordIndex."""
+    view = _bytes_view(data, "search_range")
+    return _search_range(index, lambda lo, hi: view[lo:hi], pattern, offset, length, limit, device)
+
+
 class IndexedReader(io.RawIOBase):
     """A seekable, read-only file of the DECODED bytes of `source`: bytes-like, or a seekable binary file holding .bz2
     stream(s).  Every read decodes just the blocks it touches (decompress_range); with a file source it fetches from the file
@@ -1103,6 +1148,37 @@ class IndexedReader(io.RawIOBase):
             return comp
 
         return _read_records(self.records, ranges, fetch, self._device)
+
+    def _fetch_comp(self, lo, hi):
+        """bytes [lo, hi) of the compressed source"""
+        if self._file is None:
+            return self._view[lo:hi]
+        self._file.seek(lo)
+        comp = self._file.read(hi - lo)
+        if not isinstance(comp, (bytes, bytearray, memoryview)):
+            raise TypeError("source.read() must return bytes")
+        if len(comp) != hi - lo:
+            raise EOFError(f"the source holds {len(comp)} of the {hi - lo} bytes from {lo} on that the index names")
+        return comp
+
+    def search(self, pattern, start=0, end=None, limit=None):
+        """The hits of `pattern` that lie wholly inside decoded bytes [start, end) (end None: the size) -> (hits, nhits) as
+        search_range; the position does not move.  Of a file source only the span's compressed bytes are read: one seek, one
+        read.  Record numbers come when the reader was given a RecordIndex."""
+        start = _int_arg(start, "start")
+        length = None if end is None else max(0, _int_arg(end, "end") - start)
+        return _search_range(self.records if self.records is not None else self.index, self._fetch_comp, pattern, start, length, limit,
+                             self._device)
+
+    def grep(self, pattern, limit=None):
+        """The records that hold a hit of `pattern` -> a list of (record number, bytes), ascending and unique; a match that spans
+        a delimiter belongs to the record of its first byte.  `limit` caps the hits looked at.  The reader must have been given
+        a RecordIndex; the records are fetched with one readv_records."""
+        if self.records is None:
+            raise ValueError("grep needs a RecordIndex (build_record_index) as the reader's index")
+        hits, _ = self.search(pattern, limit=limit)
+        recs = [int(r) for r in np.unique(hits["record"])]
+        return list(zip(recs, self.readv_records([(r, 1) for r in recs]))) if recs else []
 
     def read_records(self, first, count):
         """records first .. first + count - 1 as one bytes object (readv_records of one pair)"""

@@ -139,6 +139,26 @@ class DecodeRangesStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Hit(ctypes.Structure):
+    """bzh_hit: a match's offset in the output and, with SEARCH_RECORDS, the delimiters in front of it"""
+    _fields_ = [("off", ctypes.c_uint64), ("record", ctypes.c_uint64)]
+
+
+HIT_DTYPE = np.dtype([("off", "<u8"), ("record", "<u8")])
+assert HIT_DTYPE.itemsize == ctypes.sizeof(Hit) == 16
+hitp = ctypes.POINTER(Hit)
+SEARCH_RECORDS = 1
+SEARCH_MAX_PATTERN = 256
+
+
+class SearchStats(ctypes.Structure):
+    """bzh_search_stats"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("hits", "windows", "tiles", "staging_peak")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class KStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("ms", ctypes.c_double), ("launches", ctypes.c_uint64),
                 ("alg_bytes", ctypes.c_uint64)]
@@ -228,6 +248,20 @@ SIGNATURES = {
     "bzh_decode_records_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, idxp, ctypes.c_size_t,
                                                  syncp, ctypes.c_size_t, u64p, ctypes.c_uint8, rangep, ctypes.c_size_t, ctypes.c_void_p,
                                                  ctypes.c_size_t, szp, szp, szp]),
+    "bzh_search_raw_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, u8p, ctypes.c_size_t, ctypes.c_uint,
+                                             ctypes.c_uint8, hitp, ctypes.c_size_t, szp]),
+    "bzh_search_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, u8p, ctypes.c_size_t, ctypes.c_uint,
+                                         ctypes.c_uint8, hitp, ctypes.c_size_t, szp, u64p, szp]),
+    "bzh_search": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u8p, ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint8, hitp,
+                                  ctypes.c_size_t, szp, u64p, szp]),
+    "bzh_search_range_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, idxp, ctypes.c_size_t,
+                                               syncp, ctypes.c_size_t, u64p, ctypes.c_uint64, ctypes.c_uint64, u8p, ctypes.c_size_t,
+                                               ctypes.c_uint, ctypes.c_uint8, hitp, ctypes.c_size_t, szp]),
+    "bzh_search_range": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64, idxp, ctypes.c_size_t, syncp,
+                                        ctypes.c_size_t, u64p, ctypes.c_uint64, ctypes.c_uint64, u8p, ctypes.c_size_t, ctypes.c_uint,
+                                        ctypes.c_uint8, hitp, ctypes.c_size_t, szp]),
+    "bzh_search_set_room": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),
+    "bzh_get_search_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SearchStats)]),
     "bzh_decode_scan": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u64p, u8p, ctypes.c_size_t, szp]),
     "bzh_stream_begin": (ctypes.c_int, [ctypes.c_void_p]),
     "bzh_stream_feed": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, u8p, ctypes.c_size_t, szp]),
@@ -1070,6 +1104,98 @@ class Context:
         st = lib().bzh_decode_records_device(self._h, ctypes.c_void_p(d_in), n, in_byte_base, p, e.size, pp, q.size, tp, delim, rp, r.size,
                                              ctypes.c_void_p(d_out), cap, ptr(offs, szp), ptr(lens, szp), ctypes.byref(got))
         return st, int(got.value), [int(v) for v in offs[:r.size]], [int(v) for v in lens[:r.size]]
+
+    # ---- search: every call returns (hits as a HIT_DTYPE array, nhits); `limit` is the C call's max ---------------------------
+    SEARCH_GUESS = 1 << 16  # hit slots of the first try without a limit; more hits: once more, with the exact room
+
+    def _search(self, call, limit):
+        """call(hits pointer, max, nhits reference) -> status.  limit None: every hit (a second call when the first try's room
+        was too small); else at most `limit` hits and the exact count -- BZH_E_CAP is then the answer, not an error"""
+        if limit is not None and limit < 0:
+            raise ValueError("search: a negative limit")
+        room = self.SEARCH_GUESS if limit is None else int(limit)
+        for _ in range(2):
+            hits = np.zeros(max(room, 1), dtype=HIT_DTYPE)
+            got = ctypes.c_size_t(0)
+            st = call(hits.ctypes.data_as(hitp) if room else None, room, ctypes.byref(got))
+            self.search_status = st  # (of the last C call: BZH_E_CAP where the limit cut the hits)
+            if st == -4 and limit is None and got.value > room:
+                room = int(got.value)
+                continue
+            if st != -4 or not 0 < room < got.value:  # (BZH_E_CAP with more hits than room: the first `room` are there)
+                self.check(st)
+            return hits[:min(room, int(got.value))].copy(), int(got.value)
+        raise BzhError(-5, "search: the second call found more hits than the first")
+
+    @staticmethod
+    def _pattern(pattern):
+        b = bytes(pattern)
+        return np.frombuffer(b, dtype=np.uint8) if b else np.zeros(1, np.uint8), len(b)
+
+    @staticmethod
+    def _delim(delim):
+        """(flags, delimiter byte) of a delimiter given as None, an int or one byte"""
+        if delim is None:
+            return 0, 0
+        d = delim[0] if isinstance(delim, (bytes, bytearray)) and len(delim) == 1 else delim
+        if not isinstance(d, int) or not 0 <= d <= 255:
+            raise ValueError("search: the delimiter is one byte value")
+        return SEARCH_RECORDS, d
+
+    def search_raw_device(self, d_raw, n, pattern, delim=None, limit=None, flags=None):
+        """bzh_search_raw_device on the integer device address d_raw -> (hits, nhits)"""
+        pat, plen = self._pattern(pattern)
+        fl, d = self._delim(delim)
+        fl = fl if flags is None else flags
+        return self._search(lambda h, m, g: lib().bzh_search_raw_device(self._h, ctypes.c_void_p(d_raw), n, ptr(pat), plen, fl, d, h, m, g), limit)
+
+    def search_device(self, d_in, n, pattern, delim=None, limit=None, with_total=False):
+        """bzh_search_device on the integer device address of the compressed bytes -> (hits, nhits[, out_total, consumed])"""
+        pat, plen = self._pattern(pattern)
+        fl, d = self._delim(delim)
+        total, used = ctypes.c_uint64(0), ctypes.c_size_t(0)
+        r = self._search(lambda h, m, g: lib().bzh_search_device(self._h, ctypes.c_void_p(d_in), n, ptr(pat), plen, fl, d, h, m, g,
+                                                                 ctypes.byref(total), ctypes.byref(used)), limit)
+        return r + (int(total.value), int(used.value)) if with_total else r
+
+    def search(self, data, pattern, delim=None, limit=None, with_total=False):
+        """bzh_search: every occurrence of `pattern` in the decoded bytes of `data` -> (hits, nhits[, out_total, consumed])"""
+        a = np.frombuffer(data, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        pat, plen = self._pattern(pattern)
+        fl, d = self._delim(delim)
+        total, used = ctypes.c_uint64(0), ctypes.c_size_t(0)
+        r = self._search(lambda h, m, g: lib().bzh_search(self._h, ptr(src), n, ptr(pat), plen, fl, d, h, m, g, ctypes.byref(total),
+                                                          ctypes.byref(used)), limit)
+        return r + (int(total.value), int(used.value)) if with_total else r
+
+    def search_range(self, comp, entries, pattern, off=0, length=None, points=None, rec_cum=None, delim=None, limit=None, in_byte_base=0,
+                     d_in=None):
+        """bzh_search_range (d_in: an integer device address and comp the byte count -> bzh_search_range_device): the hits wholly
+        inside output [off, off + length) of the indexed input -> (hits, nhits).  Record numbers with rec_cum and delim."""
+        e, p = _entries(entries)
+        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
+        pat, plen = self._pattern(pattern)
+        fl, d = self._delim(delim)
+        tp = _table(e, rec_cum)[1] if rec_cum is not None else None
+        length = 2**64 - 1 if length is None else length
+        if d_in is not None:
+            return self._search(lambda h, m, g: lib().bzh_search_range_device(self._h, ctypes.c_void_p(d_in), comp, in_byte_base, p, e.size, pp,
+                                                                              q.size, tp, off, length, ptr(pat), plen, fl, d, h, m, g), limit)
+        a = np.frombuffer(comp, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        return self._search(lambda h, m, g: lib().bzh_search_range(self._h, ptr(src), n, in_byte_base, p, e.size, pp, q.size, tp, off, length,
+                                                                   ptr(pat), plen, fl, d, h, m, g), limit)
+
+    def search_set_room(self, nbytes=0):
+        self.check(lib().bzh_search_set_room(self._h, nbytes))
+
+    def search_stats(self):
+        s = SearchStats()
+        self.check(lib().bzh_get_search_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
 
     def decode_ranges_stats(self):
         s = DecodeRangesStats()

@@ -1838,6 +1838,185 @@ extern "C" int bzh_decode_records(bzh_ctx *ctx, const uint8_t *in, size_t n, uin
     });
 }
 
+// ---- search (search.hip: the kernel, the passes over a window, the staging; the full search rides on decode_chain_run, the range
+// search on the indexed front: decode.hip; the windows: search_plan.h)
+static int search_begin(bzh_ctx *ctx, SearchSink &sink, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits,
+                        size_t max, size_t *nhits)
+{
+    if (!pat || !nhits || (!hits && max)) return BZH_E_ARG;
+    *nhits = 0;
+    if (plen == 0 || plen > BZH_SEARCH_MAX_PATTERN) {
+        bzh_set_error(ctx, "search: a pattern of %zu bytes, outside 1..%d", plen, BZH_SEARCH_MAX_PATTERN);
+        return BZH_E_ARG;
+    }
+    if (flags & ~(unsigned)BZH_SEARCH_RECORDS) {
+        bzh_set_error(ctx, "search: flags 0x%x, of which only BZH_SEARCH_RECORDS is defined", flags);
+        return BZH_E_ARG;
+    }
+    memset(&ctx->sstats, 0, sizeof ctx->sstats);
+    return search_job(sink.job, pat, plen, flags, delim, hits, max);
+}
+
+// rc: the status of the work.  The hits follow the stream to the caller's array: whatever the status, nothing is on its way to it
+// when the call returns.
+static int search_end(bzh_ctx *ctx, const SearchSink &sink, int rc, size_t *nhits)
+{
+    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+    if (rc != BZH_OK) return rc;
+    *nhits = (size_t)sink.walk.rank;
+    if (sink.walk.rank > sink.job.max && sink.job.max) {
+        bzh_set_error(ctx, "search: %llu hits, room for %llu", (unsigned long long)sink.walk.rank, (unsigned long long)sink.job.max);
+        return BZH_E_CAP;
+    }
+    return BZH_OK;
+}
+
+extern "C" int bzh_search_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                                     bzh_hit *hits, size_t max, size_t *nhits)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_raw && n)) return BZH_E_ARG;
+    SearchSink sink;
+    BZH_TRY(search_begin(ctx, sink, pat, plen, flags, delim, hits, max, nhits));
+    if ((uintptr_t)d_raw & 15u) {
+        bzh_set_error(ctx, "search: the buffer is not 16-byte aligned");
+        return BZH_E_ARG;
+    }
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
+    int rc = search_raw_run(ctx, sink, (const uint8_t *)d_raw, n);
+    rc = decode_call_end(ctx, call, rc);
+    return search_end(ctx, sink, rc, nhits);
+    });
+}
+
+extern "C" int bzh_search_device(bzh_ctx *ctx, const void *d_in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                                 bzh_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n)) return BZH_E_ARG;
+    SearchSink sink;
+    BZH_TRY(search_begin(ctx, sink, pat, plen, flags, delim, hits, max, nhits));
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
+    if (out_total) *out_total = 0;
+    if (consumed) *consumed = 0;
+    std::vector<uint64_t> cands;
+    BZH_TRY(decode_call_scan(ctx, call, d_in, n, cands));
+    sink.walk.begin(sink.job.plen, BZF_FRONT, sink.job.max, 0, ~0ull, 0, 0);
+    size_t total = 0;
+    int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, nullptr, nullptr, nullptr, &sink);
+    if (out_total) *out_total = total;
+    rc = decode_call_end(ctx, call, rc);
+    return search_end(ctx, sink, rc, nhits);
+    });
+}
+
+extern "C" int bzh_search(bzh_ctx *ctx, const uint8_t *in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                          bzh_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n)) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BZH_TRY(decode_stage(ctx, in, n));
+    return bzh_search_device(ctx, ctx->d_stage_in, n, pat, plen, flags, delim, hits, max, nhits, out_total, consumed);
+    });
+}
+
+// the checks both variants of the range search make before any arithmetic on the arrays
+static int search_range_args(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts, size_t npts,
+                             const uint64_t *rec_cum, unsigned flags)
+{
+    if (count > 0xFFFFFFFFull) {
+        bzh_set_error(ctx, "search range: an index of %zu entries, 2^32 or more", count);
+        return BZH_E_ARG;
+    }
+    BZH_TRY(decode_index_check(ctx, idx, count));
+    BZH_TRY(decode_sync_check(ctx, idx, count, pts, npts));
+    if (!(flags & BZH_SEARCH_RECORDS)) return BZH_OK;
+    if (!rec_cum) {
+        bzh_set_error(ctx, "search range: record numbers are asked for and no record table is given");
+        return BZH_E_ARG;
+    }
+    size_t bad = 0;
+    if (const char *what = bzq_table_check(idx, count, rec_cum, &bad)) {
+        bzh_set_error(ctx, "search range: record table, entry %zu: %s", bad, what);
+        return BZH_E_ARG;
+    }
+    return BZH_OK;
+}
+
+extern "C" int bzh_search_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                                       size_t count, const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off,
+                                       uint64_t len, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits,
+                                       size_t max, size_t *nhits)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n) || (!idx && count) || (!pts && npts)) return BZH_E_ARG;
+    SearchSink sink;
+    BZH_TRY(search_begin(ctx, sink, pat, plen, flags, delim, hits, max, nhits));
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
+    BZH_TRY(search_range_args(ctx, idx, count, pts, npts, rec_cum, flags));
+    size_t first = 0, last = 0;
+    uint64_t lo, hi;
+    BZH_TRY(bzh_index_span(idx, count, off, len, &first, &last, &lo, &hi));
+    BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(last - first, 1), ctx->max_batch)));
+    int rc = search_range_run(ctx, (const uint8_t *)d_in, n, in_byte_base, idx, count, pts, npts, sink.job.records ? rec_cum : nullptr, off, len,
+                              sink);
+    rc = decode_call_end(ctx, call, rc);
+    return search_end(ctx, sink, rc, nhits);
+    });
+}
+
+extern "C" int bzh_search_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                                const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len,
+                                const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits, size_t max, size_t *nhits)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n) || (!idx && count) || (!pts && npts)) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    SearchSink sink; // (the arguments are checked here too: nothing goes up for a call that is refused)
+    BZH_TRY(search_begin(ctx, sink, pat, plen, flags, delim, hits, max, nhits));
+    BZH_TRY(search_range_args(ctx, idx, count, pts, npts, rec_cum, flags));
+    // only the span goes up
+    size_t first = 0, last = 0;
+    uint64_t lo = 0, hi = 0, base;
+    size_t un;
+    BZH_TRY(bzh_index_span(idx, count, off, len, &first, &last, &lo, &hi));
+    BZH_TRY(decode_stage_hull(ctx, in, n, in_byte_base, lo, hi, 0, &base, &un));
+    return bzh_search_range_device(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, rec_cum, off, len, pat, plen, flags, delim, hits, max,
+                                   nhits);
+    });
+}
+
+extern "C" int bzh_search_set_room(bzh_ctx *ctx, size_t bytes)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (!ctx) return BZH_E_ARG;
+    if (bytes && bytes < 1024) {
+        bzh_set_error(ctx, "search: a room of %zu bytes, below 1024", bytes);
+        return BZH_E_ARG;
+    }
+    ctx->search_room = bytes;
+    return BZH_OK;
+    });
+}
+
+extern "C" int bzh_get_search_stats(const bzh_ctx *ctx, bzh_search_stats *out)
+{
+    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
+    if (!ctx || !out) return BZH_E_ARG;
+    *out = ctx->sstats;
+    return BZH_OK;
+    });
+}
+
 extern "C" int bzh_get_decode_ranges_stats(const bzh_ctx *ctx, bzh_decode_ranges_stats *out)
 {
     return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {

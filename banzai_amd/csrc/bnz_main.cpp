@@ -7,6 +7,8 @@
 // Random access: --index writes the index the streaming encoder records beside the stream (bzh_stream_begin_index),
 // --make-index builds one for an existing .bz2 (bzh_decode_index_sync), -d --index --range reads byte ranges of the decoded
 // data from just the compressed bytes that hold them (bzh_index_spans, bzh_decode_ranges); the files are bzh_index_blob_*'s.
+// Search: --search prints the offset and the line number of every occurrence of a byte string in the decoded data, which never
+// leaves the device (bzh_search; with --index bzh_search_range over just the span's compressed bytes).
 #include <cstdio>
 #include <cstdlib>
 #include <cerrno>
@@ -55,6 +57,10 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "     --make-index <path>    write the index of <input_path> (a .bz2) to <path>; nothing is decoded\n"
             "                            to an output, and the input is kept\n"
             "     --range <off>:<len>    with -d --index: write only these bytes of the decoded data; may repeat\n"
+            "     --search <string>      print 'offset<TAB>line' of every occurrence of <string> (1 to 256 bytes) in the\n"
+            "                            decoded data, lines counted from 0 by '\\n'; nothing is written, the input is kept\n"
+            "     --hex                  with --search: <string> is given as hex digits\n"
+            "     --count                with --search: print the number of occurrences alone\n"
             "     --keep      or   -k    keep the input file\n"
             "     --remove    or   -r    remove the input file\n\n"
             "     -1 to -9               block size in 100 kB units (default -9)\n"
@@ -83,7 +89,11 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "     the last; the ranges' bytes are written back to back in the order given, each clipped to\n"
             "     the decoded size, and the input is kept.  An index file that is not a whole, undamaged\n"
             "     index is a filesystem error; one that does not fit the input exits as -d does for a\n"
-            "     damaged input.  GPU: $BZHIP_DEVICE (default 0), or\n"
+            "     damaged input.  --search exits with 0 whether or not anything matched.  With --index (and at\n"
+            "     most one --range, the bytes a match must lie wholly inside) it decodes only the blocks the\n"
+            "     range touches and reads only their bytes of a regular input file; line numbers then need the\n"
+            "     index to be a record index with delimiter '\\n' (banzai_amd.RecordIndex.to_bytes()), else the\n"
+            "     second column is '-'.  GPU: $BZHIP_DEVICE (default 0), or\n"
             "     $BZHIP_DEVICES=0,1,2,... to spread the blocks over several GPUs of this node;\n"
             "     BZHIP_HUFFMAN=fixed: 2-6 Huffman tables with refinement (smaller, not banzai's exact bytes).\n\n%s\n",
             VERSION);
@@ -95,8 +105,9 @@ const char *VERSION = "version alpha 0.3.1-hip";
 int main(int argc, char **argv)
 {
     if (argc <= 1) usage(false);
-    enum { ANY, NOARGS, OUTPATH, IDXPATH, MKIDXPATH, INTERVAL, RANGE } expect = ANY;
-    std::string in_path, out_path, index_path, mkindex_path;
+    enum { ANY, NOARGS, OUTPATH, IDXPATH, MKIDXPATH, INTERVAL, RANGE, SEARCH } expect = ANY;
+    std::string in_path, out_path, index_path, mkindex_path, needle;
+    bool searching = false, needle_hex = false, count_only = false;
     bool interval_given = false;
     uint32_t interval = 256;
     std::vector<bzh_range> ranges;
@@ -154,6 +165,11 @@ int main(int argc, char **argv)
                 die(ERR_ARGS, "Argument '--range' requires <offset>:<length>, both in bytes");
             ranges.push_back(r);
             expect = ANY;
+        } else if (expect == SEARCH) {
+            if (searching) die(ERR_ARGS, "'--search' may be given once");
+            needle = a;
+            searching = true;
+            expect = ANY;
         } else if (expect == ANY && a.rfind("--", 0) == 0) {
             if (a == "--help") usage(true);
             else if (a == "--version") die(SUCCESS, VERSION);
@@ -175,6 +191,9 @@ int main(int argc, char **argv)
             else if (a == "--make-index") expect = MKIDXPATH;
             else if (a == "--interval") expect = INTERVAL;
             else if (a == "--range") expect = RANGE;
+            else if (a == "--search") expect = SEARCH;
+            else if (a == "--hex") needle_hex = true;
+            else if (a == "--count") count_only = true;
             else if (a == "--stdout") set_output("", true);
             else if (a == "--") expect = NOARGS;
             else die(ERR_ARGS, "Unrecognised argument " + a);
@@ -200,14 +219,33 @@ int main(int argc, char **argv)
     if (expect == IDXPATH || expect == MKIDXPATH) die(ERR_ARGS, "Arguments '--index' and '--make-index' require a file path");
     if (expect == INTERVAL) die(ERR_ARGS, "Argument '--interval' requires a number of groups, 0 to 32767");
     if (expect == RANGE) die(ERR_ARGS, "Argument '--range' requires <offset>:<length>, both in bytes");
+    if (expect == SEARCH) die(ERR_ARGS, "Argument '--search' requires a string");
     if (!have_in) die(ERR_ARGS, "An input must be specified");
-    const bool by_range = !ranges.empty(), make_index = !mkindex_path.empty();
+    if ((needle_hex || count_only) && !searching) die(ERR_ARGS, "'--hex' and '--count' go with '--search'");
+    if (searching) {
+        if (decompress || recover || dstream || have_out || !mkindex_path.empty() || level_given || interval_given || keep == 0)
+            die(ERR_ARGS, "'--search' takes an input, '--hex', '--count', '--index' and one '--range', nothing else");
+        if (ranges.size() > 1 || (!ranges.empty() && index_path.empty())) die(ERR_ARGS, "'--search' takes one '--range', with the '--index' of the input");
+        if (!index_path.empty() && in_stdin) die(ERR_ARGS, "'--search --index' reads parts of a file: standard in cannot be the input");
+        if (needle_hex) {
+            std::string raw;
+            auto nib = [](char ch) { return ch >= '0' && ch <= '9' ? ch - '0' : ch >= 'a' && ch <= 'f' ? ch - 'a' + 10 : ch >= 'A' && ch <= 'F' ? ch - 'A' + 10 : -1; };
+            if (needle.size() % 2) die(ERR_ARGS, "Argument '--search' with '--hex' requires an even number of hex digits");
+            for (size_t c = 0; c < needle.size(); c += 2) {
+                if (nib(needle[c]) < 0 || nib(needle[c + 1]) < 0) die(ERR_ARGS, "Argument '--search' with '--hex' requires hex digits");
+                raw.push_back((char)(nib(needle[c]) * 16 + nib(needle[c + 1])));
+            }
+            needle = raw;
+        }
+        if (needle.empty() || needle.size() > BZH_SEARCH_MAX_PATTERN) die(ERR_ARGS, "Argument '--search' requires a string of 1 to 256 bytes");
+    }
+    const bool by_range = !ranges.empty() && !searching, make_index = !mkindex_path.empty();
     if (by_range && index_path.empty()) die(ERR_ARGS, "'--range' needs the '--index' of the input");
     if (by_range && (dstream || recover)) die(ERR_ARGS, "'--range' goes with neither '--stream' nor '--recover'");
     if (by_range && !decompress) die(ERR_ARGS, "'--range' goes with '--decompress'");
     if (by_range && in_stdin) die(ERR_ARGS, "'--range' reads parts of a file: standard in cannot be the input");
     if (by_range && !have_out) die(ERR_ARGS, "'--range' needs '--output' or '--stdout'");
-    if (!index_path.empty() && !by_range && (decompress || recover)) die(ERR_ARGS, "With '--decompress' an '--index' is read by '--range'; '--recover' takes none");
+    if (!index_path.empty() && !by_range && !searching && (decompress || recover)) die(ERR_ARGS, "With '--decompress' an '--index' is read by '--range'; '--recover' takes none");
     if (make_index && (decompress || recover || dstream || have_out || !index_path.empty() || level_given))
         die(ERR_ARGS, "'--make-index' takes an input, a path and '--interval', nothing else");
     if (interval_given && !make_index && (index_path.empty() || decompress)) die(ERR_ARGS, "'--interval' goes with '--make-index', or with '--index' while compressing");
@@ -242,6 +280,114 @@ int main(int argc, char **argv)
         }
         return "";
     };
+
+    if (searching) { // --search: the whole input through bzh_search, or with --index the span of the range through bzh_search_range
+        const char *doing = "error during search: ";
+        const uint8_t *pat = (const uint8_t *)needle.data();
+        std::vector<uint8_t> comp, blob;
+        std::vector<bzh_index_entry> ent;
+        std::vector<bzh_sync_point> pts;
+        std::vector<uint64_t> cum;
+        uint64_t lo = 0, hi = 0;
+        const bzh_range want = ranges.empty() ? bzh_range{0, UINT64_MAX} : ranges[0];
+        bool records = true;
+        if (!index_path.empty()) {
+            FILE *xf = fopen(index_path.c_str(), "rb");
+            if (!xf) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + index_path + ": " + strerror(errno));
+            const bool xok = slurp(xf, blob);
+            fclose(xf);
+            if (!xok) die(ERR_FILESYSTEM, "[filesystem error] cannot read " + index_path);
+            const std::string damaged = "[filesystem error] " + index_path + " is not a whole, undamaged index file";
+            // a record index ("BZhREC\r\n" | u32 version 1 | u32 delim | u64 entries | u64 records | u32 CRC-32 | u32 0 | an index blob | the
+            // table of entries + 1 words): the blob inside it and the table; else a block or sync index, and no line numbers
+            const uint8_t *ib = blob.data();
+            size_t in = blob.size();
+            auto get = [&](size_t at, int bytes) {
+                uint64_t v = 0;
+                for (int j = bytes - 1; j >= 0; j--) v = v << 8 | blob[at + j];
+                return v;
+            };
+            records = blob.size() >= 40 && memcmp(blob.data(), "BZhREC\r\n", 8) == 0;
+            if (records) {
+                const uint64_t nent = get(16, 8);
+                if (get(8, 4) != 1 || get(36, 4) != 0 || nent >= blob.size() / 8 || blob.size() < 40 + 8 * (nent + 1)) die(ERR_FILESYSTEM, damaged);
+                uint32_t crc = 0xFFFFFFFFu; // zlib's CRC-32 over the header with its CRC field zero and everything behind it
+                for (size_t at = 0; at < blob.size(); at++) {
+                    crc ^= at >= 32 && at < 36 ? 0u : blob[at];
+                    for (int j = 0; j < 8; j++) crc = crc >> 1 ^ (0xEDB88320u & (0u - (crc & 1u)));
+                }
+                if ((crc ^ 0xFFFFFFFFu) != (uint32_t)get(32, 4)) die(ERR_FILESYSTEM, damaged);
+                if (get(12, 4) != '\n') die(ERR_ARGS, "'--search' counts lines: " + index_path + " holds records of another delimiter");
+                cum.resize((size_t)nent + 1);
+                for (size_t e = 0; e <= nent; e++) cum[e] = get(blob.size() - 8 * (nent + 1) + 8 * e, 8);
+                ib = blob.data() + 40;
+                in = blob.size() - 40 - 8 * ((size_t)nent + 1);
+            }
+            static const uint8_t none = 0;
+            size_t count = 0, npts = 0;
+            uint32_t iv = 0;
+            uint64_t consumed = 0;
+            int rs = bzh_index_blob_read(in ? ib : &none, in, nullptr, 0, &count, nullptr, 0, &npts, &iv, &consumed);
+            ent.resize(count), pts.resize(npts);
+            if (rs == BZH_E_CAP) rs = bzh_index_blob_read(ib, in, ent.data(), count, &count, pts.data(), npts, &npts, &iv, &consumed);
+            if (rs != BZH_OK || (records && cum.size() != count + 1)) die(ERR_FILESYSTEM, damaged);
+            struct stat sb;
+            if (stat(in_path.c_str(), &sb) != 0) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + in_path + ": " + strerror(errno));
+            if (!S_ISREG(sb.st_mode)) die(ERR_ARGS, "'--search --index' reads parts of a regular file: " + in_path + " is none");
+            size_t first = 0, last = 0;
+            rs = bzh_index_span(ent.data(), count, want.off, want.len, &first, &last, &lo, &hi);
+            if (rs != BZH_OK) die(ERR_OUTPUT, std::string(doing) + bzh_strerror(rs));
+            if (hi < lo || hi > (uint64_t)sb.st_size)
+                die(ERR_OUTPUT, std::string(doing) + "the index names bytes behind the end of " + in_path + ": it is not this file's");
+            FILE *rf = fopen(in_path.c_str(), "rb");
+            if (!rf) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + in_path + ": " + strerror(errno));
+            comp.resize((size_t)(hi - lo));
+            if (!comp.empty() && (fseeko(rf, (off_t)lo, SEEK_SET) != 0 || fread(comp.data(), 1, comp.size(), rf) != comp.size()))
+                die(ERR_OUTPUT, std::string(doing) + "read failed");
+            fclose(rf);
+        } else {
+            FILE *sf = in_stdin ? stdin : fopen(in_path.c_str(), "rb");
+            if (!sf) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + in_path + ": " + strerror(errno));
+            if (!slurp(sf, comp)) die(ERR_OUTPUT, std::string(doing) + "read failed");
+            if (sf != stdin) fclose(sf);
+        }
+        const char *dv = getenv("BZHIP_DEVICE");
+        bzh_ctx *sctx = nullptr;
+        int rs = bzh_create(&sctx, dv ? atoi(dv) : 0, 9, 0);
+        if (rs != BZH_OK) die(ERR_OUTPUT, std::string(doing) + bzh_strerror(rs));
+        static const uint8_t nothing = 0;
+        const uint8_t *cp = comp.empty() ? &nothing : comp.data();
+        const unsigned flags = records ? BZH_SEARCH_RECORDS : 0;
+        std::vector<bzh_hit> hits(count_only ? 0 : (size_t)1 << 16);
+        size_t nhits = 0;
+        for (int attempt = 0; attempt < 2; attempt++) { // (more hits than the first try's room: once more, with exactly theirs)
+            if (index_path.empty())
+                rs = bzh_search(sctx, cp, comp.size(), pat, needle.size(), flags, '\n', hits.data(), hits.size(), &nhits, nullptr, nullptr);
+            else
+                rs = bzh_search_range(sctx, cp, comp.size(), lo, ent.data(), ent.size(), pts.data(), pts.size(), records ? cum.data() : nullptr,
+                                      want.off, want.len, pat, needle.size(), flags, '\n', hits.data(), hits.size(), &nhits);
+            if (rs != BZH_E_CAP || count_only || attempt) break;
+            hits.resize(nhits);
+        }
+        if (rs != BZH_OK) {
+            const std::string msg = std::string(doing) + bzh_strerror(rs) + ": " + bzh_last_error(sctx);
+            bzh_destroy(sctx);
+            die(ERR_OUTPUT, msg);
+        }
+        bzh_destroy(sctx);
+        if (count_only) {
+            printf("%zu\n", nhits);
+        } else {
+            for (size_t k = 0; k < nhits; k++) {
+                if (records)
+                    printf("%llu\t%llu\n", (unsigned long long)hits[k].off, (unsigned long long)hits[k].record);
+                else
+                    printf("%llu\t-\n", (unsigned long long)hits[k].off);
+            }
+        }
+        if (fflush(stdout) != 0) die(ERR_OUTPUT, std::string(doing) + "write failed");
+        return SUCCESS; // (the input is kept: nothing was made of it)
+    }
 
     if (by_range) { // -d --index --range: the index file, the hull of the touched blocks' bytes, one bzh_decode_ranges
         const char *doing = "error during decompression: ";

@@ -69,6 +69,7 @@ struct GrowBuf {
 using DevBuf = GrowBuf<false>;
 using PinnedBuf = GrowBuf<true>;
 
+#include "search_plan.h" // the windows of a search and their carry: host-only text (tests/decode_host/search_host.cpp)
 #include "batch.h" // geometry, Batch and its layout, the carver: host-only text (tests/workspace_host)
 
 // Kernel classes of the per-kernel roofline table (bzh_get_kernel_stats).  With profiling on, the launches of a
@@ -183,6 +184,10 @@ struct bzh_ctx {
     bzh_decode_ranges_stats qstats{}; // of the last bzh_decode_ranges* call
     DevBuf ranges_ws;               // bzh_decode_ranges*: a batch's piece tables (allocated on first use)
     DevBuf records_ws;              // records (bzh_decode_index_records*, bzh_decode_records*, bzh_count_records_device): tile counts, last-byte flags, queries, positions
+    DevBuf search_ws;               // bzh_search*: the staging buffer the decoders expand a window into (allocated on first use)
+    DevBuf search_tab, search_out, search_carry; // ... a window's tile tables, its hit slots, the bytes carried to the next window
+    size_t search_room = 0;         // bzh_search_set_room: the staging target of the range search (0: the default)
+    bzh_search_stats sstats{};      // of the last bzh_search* call
     struct DStream *dstrm = nullptr; // streaming decode (bzh_dstream_*, decode.hip): made by the first begin, freed by dstream_free
     size_t dstrm_window = 0, dstrm_staging = 0; // bzh_dstream_set_room: targets of the next begin (0: the defaults)
     // streaming encode (bzh_stream_*)
@@ -545,9 +550,10 @@ struct RecBuild { // bzh_decode_index_records*: the index build also counts the 
     std::vector<uint64_t> cum; // [entries + 1] delimiters in front of every entry, and of the end
     bool last_is_delim;        // the last byte of the output is one
 };
+struct SearchSink; // bzh_search*: every batch is expanded into the search's staging buffer and searched there; nothing goes to d_out
 int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t cap, size_t *out_len, size_t *consumed,
                      const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index = nullptr, SyncBuild *sync = nullptr,
-                     RecBuild *rec = nullptr);
+                     RecBuild *rec = nullptr, SearchSink *srch = nullptr);
 // decode.hip: the two checks of an index and its sync points as a whole, then the blocks of a verified index that
 // [off, off + len) touches, from d_in = the indexed input from byte in_byte_base on (windows and segments: decode_plan.h)
 int decode_index_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count); // BZH_E_ARG naming the entry that is ill formed
@@ -583,6 +589,27 @@ size_t dstream_consumed(const bzh_ctx *ctx);
 int dstream_stats(const bzh_ctx *ctx, bzh_dstream_stats *out);
 void dstream_end(bzh_ctx *ctx);  // abandon: the buffers stay for the next begin
 void dstream_free(bzh_ctx *ctx); // bzh_destroy
+// search.hip: the search over decoded bytes in HBM.  A job is what is looked for and where the hits go; a sink is a job and the walk
+// over its windows (search_plan.h).  search_sink_room / search_sink_window: the staging buffer for the next window of `bytes` whole
+// blocks (the decoder expands at *d_stage + BZF_FRONT), and the two passes over it once it is verified.
+struct SearchJob {
+    uint8_t pat[256];
+    uint32_t plen, delim;
+    bool records;
+    bzh_hit *hits; // host
+    uint64_t max;
+};
+struct SearchSink {
+    SearchJob job;
+    BzfWalk walk;
+};
+int search_job(SearchJob &job, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits, size_t max);
+int search_sink_room(bzh_ctx *ctx, SearchSink &sink, uint64_t bytes, uint8_t **d_stage);
+int search_sink_window(bzh_ctx *ctx, SearchSink &sink, uint64_t bytes);
+int search_raw_run(bzh_ctx *ctx, SearchSink &sink, const uint8_t *d_raw, size_t n);
+// decode.hip: the hits wholly inside output [off, off + len) of an indexed input, window by window over the touched entries
+int search_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                     const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len, SearchSink &sink);
 // recover.hip: the bits of the kept blocks, end to end from bit 32 of d_out, in one launch (the per-word rule: recover_gather.h)
 struct BzrDesc;
 int recover_gather_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const std::vector<BzrDesc> &descs, uint64_t body, uint32_t *d_out);

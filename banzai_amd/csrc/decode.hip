@@ -1103,8 +1103,10 @@ static int back_emit(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk, 
 // The chain walk and the back of the decoder.  cands: decode_scan_run's list.  The arena holds min(cands, max_batch) blocks.
 // index: the call builds a block index (bzh_decode_index*) -- cap is 0, nothing is expanded, every block's CRC comes from
 // unrle_crc and is checked like a full decode's, and the entries are appended in chain order.
+// srch: the call is a search (bzh_search*) -- cap does not bound it, a batch's blocks are expanded behind the carry in the search's
+// staging buffer instead of at total_out in d_out, and behind the batch's CRC checks the sink runs its two passes over them.
 int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t cap, size_t *out_len, size_t *consumed,
-                     const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index, SyncBuild *sync, RecBuild *rec)
+                     const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index, SyncBuild *sync, RecBuild *rec, SearchSink *srch)
 {
     hipStream_t st = ctx->stream;
     Batch &bt = ctx->bt;
@@ -1152,7 +1154,7 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
     }
     const size_t nc = cands.size();
     const uint64_t nbits = (uint64_t)n * 8;
-    uint64_t pos = 32, total_out = 0;
+    uint64_t pos = 32, total_out = 0, batch_bytes = 0;
     uint32_t stream_crc = 0;
     size_t ci = 0;
     bool finished = false, over = false;
@@ -1227,6 +1229,7 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
             for (uint32_t s = 0; s < Bu; s++)
                 if (!(cands[ci - k + s] & 1ull) && res[s].kind == BZD_OK) nmax_all = std::max(nmax_all, res[s].nblock);
             BZH_TRY(back_sizes(ctx, w, clock, bk, Bu, nmax_all, blocks));
+            batch_bytes = 0;
             for (BackBlock &b : blocks) {
                 if (b.bad_end) { // libbz2 refuses the block; the state machine says where
                     for (const ChainItem &it : items)
@@ -1236,13 +1239,16 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
                             return data_error(BZD_K_FORMAT, it.bitpos, "the block ends in four equal bytes without a count");
                         }
                 }
-                b.base = (int64_t)total_out;
+                b.base = srch ? (int64_t)(BZF_FRONT + batch_bytes) : (int64_t)total_out;
+                batch_bytes += b.size;
                 total_out += b.size;
             }
-            if (total_out > cap) over = true; // (sizing goes on: the caller learns the total)
+            if (!srch && total_out > cap) over = true; // (sizing goes on: the caller learns the total)
+            uint8_t *d_to = d_out;
+            if (srch) BZH_TRY(search_sink_room(ctx, *srch, batch_bytes, &d_to)); // (the sizes are known: the staging grows to the batch)
             if (index || !over) { // an index: the CRCs of the expansions, with nothing expanded
                 for (BackBlock &b : blocks) b.lo = 0, b.hi = index ? 0 : (uint32_t)b.size;
-                BZH_TRY(back_emit(ctx, w, clock, bk, d_out, true, blocks, false, nullptr, index && rec ? &bc : nullptr));
+                BZH_TRY(back_emit(ctx, w, clock, bk, d_to, true, blocks, false, nullptr, index && rec ? &bc : nullptr));
             } else {
                 span(3, bk.t_unrle);
             }
@@ -1282,6 +1288,7 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
         }
         stream = stream_at;
         block = block_at;
+        if (srch && !blocks.empty()) BZH_TRY(search_sink_window(ctx, *srch, batch_bytes)); // (every block of the batch has passed its CRC)
         if (finished) break;
     }
     clock.collect();
@@ -2305,5 +2312,63 @@ int count_records_run(bzh_ctx *ctx, const uint8_t *d_raw, size_t n, uint8_t deli
         rec_cum[e + 1] = rec_cum[e] + d;
     }
     *nrecords = rec_cum[count] + (n > 0 && lastb != delim);
+    return BZH_OK;
+}
+
+// ================================================================================================================
+// Search in a range of an indexed input (bzh_search_range*): windows of consecutive touched entries through the indexed front and
+// the back, WHOLE blocks into the search's staging buffer; the range is applied by the search (the windows: search_plan.h)
+// ================================================================================================================
+constexpr size_t SEARCH_ROOM = (size_t)128 << 20; // the default bzhip.h documents
+
+// (idx has passed decode_index_check, pts decode_sync_check, rec_cum -- null without BZH_SEARCH_RECORDS -- bzq_table_check)
+int search_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                     const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len, SearchSink &sink)
+{
+    size_t first, last;
+    uint64_t byte_lo, byte_hi, clipped;
+    index_span(idx, count, off, len, &first, &last, &byte_lo, &byte_hi, &clipped);
+    if (clipped == 0 || last <= first) return BZH_OK;
+    BZH_TRY(index_covered(ctx, idx, first, last - 1, in_byte_base, n));
+    DecWs w;
+    BZH_TRY(dec_ws(ctx, w));
+    BackCount bc{sink.job.delim, nullptr, nullptr, {}, {}};
+    if (rec_cum) BZH_TRY(back_count_ws(ctx, bc));
+    StageClock clock{ctx, {}};
+    const size_t Bmax = batch_max(ctx);
+    const uint64_t room = ctx->search_room ? ctx->search_room : SEARCH_ROOM;
+    sink.walk.begin(sink.job.plen, BZF_FRONT, sink.job.max, off, off + clipped, idx[first].out_off, rec_cum ? rec_cum[first] : 0);
+    std::vector<uint32_t> ent;
+    IndexedFront fr{ctx, w, clock, d_in, n, in_byte_base, idx, pts, npts};
+    for (size_t at = first; at < last;) {
+        uint64_t bytes = 0;
+        const uint32_t B = (uint32_t)bzf_window_blocks(idx, at, last, room, Bmax, &bytes);
+        ent.resize(B);
+        for (uint32_t k = 0; k < B; k++) ent[k] = (uint32_t)(at + k);
+        BZH_TRY(fr.run(ent.data(), B, rec_cum ? &bc : nullptr)); // (the sizes are the entries': checked)
+        for (uint32_t k = 0; rec_cum && k < B; k++) {
+            uint64_t d = 0;
+            for (uint32_t t = 0; t < (fr.blocks[k].nblock + UR_TILE - 1) / UR_TILE; t++) d += bc.tcount[(size_t)k * w.T + t];
+            if (d != rec_cum[at + k + 1] - rec_cum[at + k]) {
+                bzh_set_error(ctx, "search range: the record table does not match entry %zu", at + k);
+                return BZH_E_DATA;
+            }
+        }
+        uint8_t *d_stage = nullptr;
+        BZH_TRY(search_sink_room(ctx, sink, bytes, &d_stage));
+        uint64_t local = 0;
+        for (uint32_t k = 0; k < B; k++) {
+            BackBlock &b = fr.blocks[k];
+            b.lo = 0, b.hi = (uint32_t)b.size;
+            b.base = (int64_t)(BZF_FRONT + local);
+            local += b.size;
+        }
+        BZH_TRY(back_emit(ctx, w, clock, fr.bk, d_stage, true, fr.blocks));
+        BZH_TRY(fr.crcs(ent.data(), B));
+        BZH_TRY(search_sink_window(ctx, sink, bytes));
+        at += B;
+    }
+    clock.collect();
+    ctx->dstats.out_bytes = clipped;
     return BZH_OK;
 }

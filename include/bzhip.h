@@ -541,6 +541,75 @@ BZH_API int bzh_decode_records(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64
                                const bzh_range *ranges, size_t nranges, uint8_t *out, size_t cap, size_t *out_offs,
                                size_t *out_lens, size_t *out_total);
 
+/* ---- search: the offsets and record numbers of every occurrence of a byte string, found on the device --------------------- */
+
+/* The decoded bytes exist in HBM at the moment they are verified; a search over them is one streaming pass at memory speed beside
+ * an entropy stage that is nine tenths of a decode.  These calls leave the bytes on the device and return only the hits.
+ * CONTRACT, for every call below.  A hit is an output offset o with out[o .. o + plen) == pat[0 .. plen).  Every occurrence is a
+ * hit, overlapping ones included: "aa" in "aaaa" has three hits.  Hits are reported in ascending off.  With BZH_SEARCH_RECORDS,
+ * `record` is the number of `delim` bytes in output [0, off): by the definitions above, the record that holds byte off; a match
+ * that spans a delimiter belongs to the record of its first byte.  Without the flag, record is 0.
+ * *nhits is always the exact number of hits.  If it exceeds max the status is BZH_E_CAP and hits[0 .. max) hold the first max hits:
+ * the call goes on counting, as bzh_decode goes on sizing.  max == 0 with null hits is a counting call and returns BZH_OK.
+ * BZH_E_ARG: plen == 0, plen > BZH_SEARCH_MAX_PATTERN, a flag bit that is not defined, a null pat or nhits, a null hits with
+ * max > 0.  A pattern longer than the output has no hits.  After any error hits is unspecified and the context stays usable.
+ * Like every entry point the calls join a streaming pass in flight, run on the context's stream and honour bzh_set_profiling.
+ * hits is a host array. */
+typedef struct {
+    uint64_t off;    /* of the match's first byte in the output */
+    uint64_t record; /* BZH_SEARCH_RECORDS: the delimiters in front of it; else 0 */
+} bzh_hit;           /* 16 bytes */
+enum { BZH_SEARCH_RECORDS = 1 };
+#define BZH_SEARCH_MAX_PATTERN 256
+
+/* Searches decoded bytes that already lie in HBM -- the encoder's input, a decoder's output: the seam the kernel is tested
+ * through.  d_raw must be 16-byte aligned, else BZH_E_ARG; any n, 0 included.  No read goes past d_raw[0, n) rounded up to the
+ * aligned 4-byte word that holds byte n - 1. */
+BZH_API int bzh_search_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const uint8_t *pat, size_t plen, unsigned flags,
+                                  uint8_t delim, bzh_hit *hits, size_t max, size_t *nhits);
+
+/* Searches the output of in[0..n) without an output buffer.  The input contract is bzh_decode's, word for word: several streams,
+ * foreign bytes behind them, the level gate, every error kind, and bzh_last_error's text.  Everything a full decode verifies is
+ * verified, block and stream CRCs included.  The output searched is the concatenation of all streams: a match may span a block
+ * boundary or a stream boundary.  *out_total = the decoded bytes, *consumed as bzh_decode reports it (either may be null).  The
+ * call is all or nothing: a stream CRC is known only at the footer, so no hit is trusted until the call returns BZH_OK or
+ * BZH_E_CAP.  Every batch is expanded into a staging buffer of the context's, which grows to the batch, and searched there behind
+ * its CRC checks: at most one host wait a batch beyond what the decode pays.  bzh_get_decode_stats is filled as by bzh_decode. */
+BZH_API int bzh_search_device(bzh_ctx *ctx, const void *d_in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                              bzh_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed);
+BZH_API int bzh_search(bzh_ctx *ctx, const uint8_t *in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                       bzh_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed);
+
+/* Finds the hits that lie wholly inside output [off, off + len) of the indexed input, clipped to the indexed total as
+ * bzh_decode_range clips.  in[0..n) holds the compressed bytes from byte in_byte_base of the indexed input.  Only the entries
+ * bzh_index_span names are decoded, each once, as WHOLE blocks into staging, in windows of consecutive entries up to the staging
+ * target; the range is applied by the search, not by the expansion.  The index and the points are checked as by bzh_decode_ranges;
+ * every touched block is checked against its entry, with its CRC over all of its bytes; stream CRCs are not checked, as there.
+ * npts == 0: one wavefront a block.  With BZH_SEARCH_RECORDS rec_cum is required, else BZH_E_ARG; it is checked whole for shape as
+ * bzh_decode_records checks it, supplies the delimiters in front of the first touched block, and every touched block's counted
+ * delimiters must equal rec_cum[e + 1] - rec_cum[e], else BZH_E_DATA "record table does not match entry e".  Without the flag
+ * rec_cum is not looked at.  The host variant uploads only the span.  bzh_get_decode_stats is filled as by bzh_decode_range. */
+BZH_API int bzh_search_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                                    size_t count, const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off,
+                                    uint64_t len, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits,
+                                    size_t max, size_t *nhits);
+BZH_API int bzh_search_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                             const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len,
+                             const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits, size_t max, size_t *nhits);
+
+/* The staging target of the range search: 0 = the default, 128 MiB (the stream decoder's staging default); a non-zero value below
+ * 1024: BZH_E_ARG.  A window always holds whole blocks and at least one block. */
+BZH_API int bzh_search_set_room(bzh_ctx *ctx, size_t bytes);
+
+/* Counters of the last bzh_search* call. */
+typedef struct {
+    uint64_t hits;         /* found (*nhits) */
+    uint64_t windows;      /* searched: one for raw bytes, one a batch of a full search, the range search's windows */
+    uint64_t tiles;        /* of 4,096 bytes, over all windows (the counting pass) */
+    uint64_t staging_peak; /* bytes of the staging buffer */
+} bzh_search_stats;
+BZH_API int bzh_get_search_stats(const bzh_ctx *ctx, bzh_search_stats *out);
+
 /* ---- the encoder writes the index of its own stream: no decode pass to rediscover what it held -------------------------- */
 
 /* bzh_encode_device that also returns the index of the stream it writes: the entries bzh_decode_index would return for
