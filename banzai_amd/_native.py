@@ -650,6 +650,7 @@ class Context:
         out = np.zeros(cap if want_bytes else 1, dtype=np.uint8)
         self.check(lib().bzh_rle1_split(self._h, ptr(a), n, blocks, maxb, ctypes.byref(nb),
                                         ptr(out) if want_bytes else None, cap))
+        self._nblocks = nb.value  # (plan_open / plan_blocks describe this plan now)
         infos = [(int(blocks[k].in_off), int(blocks[k].in_len), int(blocks[k].rle_len), int(blocks[k].crc))
                  for k in range(nb.value)]
         chunks = []

@@ -189,7 +189,7 @@ def test_rle1_split_and_crc_seam(oracle, request, level, ctxname):
 
 
 def test_rle1_boundary_residues(oracle, ctx1):
-    for d in cases.boundary_cases()[::3]:
+    for d in cases.boundary_cases():
         infos, chunks = ctx1.rle1_split(d)
         oi, oc = oracle_split(oracle, d, 1)
         assert infos == oi and chunks == oc
