@@ -45,7 +45,7 @@ import numpy as np
 
 from . import _native
 
-__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex", "RecordIndex", "build_record_index", "record_index_of", "decompress_records", "search", "search_range",
+__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex", "RecordIndex", "build_record_index", "record_index_of", "decompress_records", "search", "search_range", "grep", "grep_count",
            "IndexedReader", "build_sync_index", "SyncIndex", "encode_indexed", "encode_indexed_stream", "recover", "recover_stream", "Recovered", "RecoveredBlock", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
@@ -1031,6 +1031,32 @@ def search_range(data, index, pattern, offset=0, length=None, limit=None, device
     BlockIndex, a SyncIndex or a RecordIndex; record numbers come when it is a RecordIndex."""
     view = _bytes_view(data, "search_range")
     return _search_range(index, lambda lo, hi: view[lo:hi], pattern, offset, length, limit, device)
+
+
+def _grep(data, pattern, delim, invert, index, device, count_only):
+    view = _bytes_view(data, "grep")
+    pattern, d = _pattern_arg(pattern), _delim_arg(delim)
+    ctx = _ctx(9, device)
+    if index is None:
+        return ctx.grep(view, pattern, d, bool(invert), count_only)
+    index = _index_arg(index)
+    return ctx.grep_index(view, index.entries, pattern, _points_arg(index), d, bool(invert), count_only)
+
+
+def grep(data, pattern, delim=b"\n", invert=False, index=None, device=0):
+    """The records (lines) of the DECODED bytes of `data` (bytes-like .bz2 stream(s)) in which a match of the byte string
+    `pattern` (1..256 bytes) starts, or with `invert` those in which none does -> (bytes, entries): the selected records back to
+    back, each with its delimiter, and a structured array with fields `record` (the number read_records takes), `off` and `len`
+    (in the decoded output) and `out_off` (in the bytes returned).  The records are selected and compacted on the device: only
+    they cross to the host, and every block is decoded once.  Everything decompress verifies is verified (bzh_grep).  With
+    `index` (a BlockIndex or SyncIndex of `data`) the blocks go through the indexed front, in parallel segments where the index
+    has sync points, and are checked against their entries (bzh_grep_index)."""
+    return _grep(data, pattern, delim, invert, index, device, False)
+
+
+def grep_count(data, pattern, delim=b"\n", invert=False, index=None, device=0):
+    """The number of records grep() would return; nothing but two words crosses to the host."""
+    return _grep(data, pattern, delim, invert, index, device, True)[0]
 
 
 class IndexedReader(io.RawIOBase):

@@ -159,6 +159,25 @@ class SearchStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class GrepEntry(ctypes.Structure):
+    """bzh_grep_entry: a selected record's number, its offset and length in the decoded output, and where it lies in `out`"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("record", "off", "len", "out_off")]
+
+
+GREP_ENTRY_DTYPE = np.dtype([("record", "<u8"), ("off", "<u8"), ("len", "<u8"), ("out_off", "<u8")])
+assert GREP_ENTRY_DTYPE.itemsize == ctypes.sizeof(GrepEntry) == 32
+grepp = ctypes.POINTER(GrepEntry)
+GREP_INVERT = 1
+
+
+class GrepStats(ctypes.Structure):
+    """bzh_grep_stats"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("records", "selected", "out_bytes", "windows", "tiles", "carry_peak", "staging_peak")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class KStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("ms", ctypes.c_double), ("launches", ctypes.c_uint64),
                 ("alg_bytes", ctypes.c_uint64)]
@@ -260,6 +279,24 @@ SIGNATURES = {
     "bzh_search_range": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64, idxp, ctypes.c_size_t, syncp,
                                         ctypes.c_size_t, u64p, ctypes.c_uint64, ctypes.c_uint64, u8p, ctypes.c_size_t, ctypes.c_uint,
                                         ctypes.c_uint8, hitp, ctypes.c_size_t, szp]),
+    "bzh_grep_raw_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, u8p, ctypes.c_size_t, ctypes.c_uint,
+                                           ctypes.c_uint8, ctypes.c_void_p, ctypes.c_size_t, grepp, ctypes.c_size_t,
+                                           ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint64)]),
+    "bzh_grep_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, u8p, ctypes.c_size_t, ctypes.c_uint,
+                                       ctypes.c_uint8, ctypes.c_void_p, ctypes.c_size_t, grepp, ctypes.c_size_t,
+                                       ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                       ctypes.POINTER(ctypes.c_size_t)]),
+    "bzh_grep": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u8p, ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint8, u8p,
+                                ctypes.c_size_t, grepp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint64),
+                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_size_t)]),
+    "bzh_grep_index_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, idxp, ctypes.c_size_t, syncp,
+                                             ctypes.c_size_t, u8p, ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint8, ctypes.c_void_p,
+                                             ctypes.c_size_t, grepp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                                             ctypes.POINTER(ctypes.c_uint64)]),
+    "bzh_grep_index": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, idxp, ctypes.c_size_t, syncp, ctypes.c_size_t, u8p,
+                                      ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint8, u8p, ctypes.c_size_t, grepp, ctypes.c_size_t,
+                                      ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint64)]),
+    "bzh_get_grep_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(GrepStats)]),
     "bzh_search_set_room": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),
     "bzh_get_search_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SearchStats)]),
     "bzh_decode_scan": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u64p, u8p, ctypes.c_size_t, szp]),
@@ -1196,6 +1233,92 @@ class Context:
     def search_stats(self):
         s = SearchStats()
         self.check(lib().bzh_get_search_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
+
+    # ---- grep: the selected records' bytes and their entries (GREP_ENTRY_DTYPE) ---------------------------------------------------
+    GREP_GUESS = (1 << 20, 1 << 12)  # bytes and entries of the first try; more of either: once more, with the exact rooms
+
+    def _grep(self, call, count_only=False):
+        """call(out pointer, cap, entries pointer, max, nrecs reference, out_total reference) -> status.  Returns (bytes,
+        entries): a first try with GREP_GUESS, a second with the exact rooms when either was too small.  count_only: a counting
+        call (no room is asked for) -> (nrecs, out_total)."""
+        got, total = ctypes.c_size_t(0), ctypes.c_uint64(0)
+        if count_only:
+            self.check(call(None, 0, None, 0, ctypes.byref(got), ctypes.byref(total)))
+            return int(got.value), int(total.value)
+        cap, room = self.GREP_GUESS
+        for _ in range(2):
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            ent = np.zeros(max(room, 1), dtype=GREP_ENTRY_DTYPE)
+            st = call(ptr(out), cap, ent.ctypes.data_as(grepp), room, ctypes.byref(got), ctypes.byref(total))
+            self.grep_status = st  # (of the last C call)
+            if st == -4 and (total.value > cap or got.value > room):
+                cap, room = int(total.value), int(got.value)
+                continue
+            self.check(st)
+            return out[:int(total.value)].tobytes(), ent[:int(got.value)].copy()
+        raise BzhError(-5, "grep: the second call selected more than the first")
+
+    @staticmethod
+    def _grep_args(pattern, delim, invert):
+        pat, plen = Context._pattern(pattern)
+        fl, d = Context._delim(delim)
+        if not fl:
+            raise ValueError("grep: the delimiter is one byte value")
+        return pat, plen, GREP_INVERT if invert else 0, d
+
+    def grep(self, data, pattern, delim=b"\n", invert=False, count_only=False):
+        """bzh_grep: the records of the decoded bytes of `data` that hold `pattern` -> (bytes, entries), or (nrecs, out_total)"""
+        a = np.frombuffer(data, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        pat, plen, fl, d = self._grep_args(pattern, delim, invert)
+        return self._grep(lambda o, c, e, m, g, t: lib().bzh_grep(self._h, ptr(src), n, ptr(pat), plen, fl, d, o, c, e, m, g, t, None, None),
+                          count_only)
+
+    def grep_index(self, comp, entries, pattern, points=None, delim=b"\n", invert=False, count_only=False):
+        """bzh_grep_index over the whole indexed input `comp` -> as grep"""
+        e, p = _entries(entries)
+        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
+        a = np.frombuffer(comp, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        pat, plen, fl, d = self._grep_args(pattern, delim, invert)
+        return self._grep(lambda o, c, en, m, g, t: lib().bzh_grep_index(self._h, ptr(src), n, p, e.size, pp, q.size, ptr(pat), plen, fl, d, o, c,
+                                                                         en, m, g, t), count_only)
+
+    def _grep_device(self, call, room):
+        """the device variants: the bytes stay in the caller's device buffer -> (status, nrecs, out_total, entries)"""
+        got, total = ctypes.c_size_t(0), ctypes.c_uint64(0)
+        ent = np.zeros(max(room, 1), dtype=GREP_ENTRY_DTYPE)
+        st = call(ent.ctypes.data_as(grepp) if room else None, room, ctypes.byref(got), ctypes.byref(total))
+        return st, int(got.value), int(total.value), ent[:min(room, int(got.value))].copy()
+
+    def grep_raw_device(self, d_raw, n, pattern, d_out, cap, room, delim=b"\n", invert=False, flags=None):
+        """bzh_grep_raw_device on integer device addresses; `room` entries -> (status, nrecs, out_total, entries)"""
+        pat, plen, fl, d = self._grep_args(pattern, delim, invert)
+        fl = fl if flags is None else flags
+        return self._grep_device(lambda e, m, g, t: lib().bzh_grep_raw_device(self._h, ctypes.c_void_p(d_raw), n, ptr(pat), plen, fl, d,
+                                                                              ctypes.c_void_p(d_out), cap, e, m, g, t), room)
+
+    def grep_device(self, d_in, n, pattern, d_out, cap, room, delim=b"\n", invert=False):
+        """bzh_grep_device on integer device addresses; `room` entries -> (status, nrecs, out_total, entries)"""
+        pat, plen, fl, d = self._grep_args(pattern, delim, invert)
+        return self._grep_device(lambda e, m, g, t: lib().bzh_grep_device(self._h, ctypes.c_void_p(d_in), n, ptr(pat), plen, fl, d,
+                                                                          ctypes.c_void_p(d_out), cap, e, m, g, t, None, None), room)
+
+    def grep_index_device(self, d_in, n, entries, pattern, d_out, cap, room, points=None, delim=b"\n", invert=False):
+        """bzh_grep_index_device on integer device addresses; `room` entries -> (status, nrecs, out_total, entries)"""
+        e, p = _entries(entries)
+        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
+        pat, plen, fl, d = self._grep_args(pattern, delim, invert)
+        return self._grep_device(lambda en, m, g, t: lib().bzh_grep_index_device(self._h, ctypes.c_void_p(d_in), n, p, e.size, pp, q.size,
+                                                                                 ptr(pat), plen, fl, d, ctypes.c_void_p(d_out), cap, en, m, g,
+                                                                                 t), room)
+
+    def grep_stats(self):
+        s = GrepStats()
+        self.check(lib().bzh_get_grep_stats(self._h, ctypes.byref(s)))
         return s.as_dict()
 
     def decode_ranges_stats(self):

@@ -2017,6 +2017,163 @@ extern "C" int bzh_get_search_stats(const bzh_ctx *ctx, bzh_search_stats *out)
     });
 }
 
+// ---- grep (grep.hip: the kernels, the passes over a window, the staging and the carry; the full grep rides on decode_chain_run,
+// the indexed one on search_range_run, both through a search sink that hands over to the grep's; the windows: grep_plan.h)
+static int grep_begin(bzh_ctx *ctx, GrepSink &g, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, void *d_out, size_t cap,
+                      bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
+{
+    if (!pat || !nrecs || !out_total || (!d_out && cap) || (!ent && max)) return BZH_E_ARG;
+    *nrecs = 0;
+    *out_total = 0;
+    if (plen == 0 || plen > BZH_SEARCH_MAX_PATTERN) {
+        bzh_set_error(ctx, "grep: a pattern of %zu bytes, outside 1..%d", plen, BZH_SEARCH_MAX_PATTERN);
+        return BZH_E_ARG;
+    }
+    if (flags & ~(unsigned)BZH_GREP_INVERT) {
+        bzh_set_error(ctx, "grep: flags 0x%x, of which only BZH_GREP_INVERT is defined", flags);
+        return BZH_E_ARG;
+    }
+    if ((uintptr_t)d_out & 3u) {
+        bzh_set_error(ctx, "grep: the output buffer is not 4-byte aligned");
+        return BZH_E_ARG;
+    }
+    memset(&ctx->gstats, 0, sizeof ctx->gstats);
+    memset(g.pat, 0, sizeof g.pat);
+    memcpy(g.pat, pat, plen);
+    g.plen = (uint32_t)plen, g.delim = delim;
+    g.d_out = (uint8_t *)d_out, g.ent = ent;
+    g.front = 0, g.tail = nullptr, g.tail_ent = BzgEntry{};
+    g.walk.begin((uint32_t)plen, (flags & BZH_GREP_INVERT) != 0, d_out != nullptr, cap, ent != nullptr, max);
+    return BZH_OK;
+}
+
+// rc: the status of the windows.  Behind them the bytes held back and the open tail (grep_finish); bytes and entries follow the
+// stream: whatever the status, nothing is on its way to the caller's arrays when the call returns.
+static int grep_end(bzh_ctx *ctx, GrepSink &g, const DecodeCall &call, int rc, size_t *nrecs, uint64_t *out_total)
+{
+    bool tail_entry = false;
+    if (rc == BZH_OK) rc = grep_finish(ctx, g, &tail_entry);
+    rc = decode_call_end(ctx, call, rc);
+    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+    if (rc != BZH_OK) return rc;
+    if (tail_entry) memcpy(&g.ent[g.walk.sel - 1], &g.tail_ent, sizeof g.tail_ent);
+    *nrecs = (size_t)g.walk.sel;
+    *out_total = g.walk.out_bytes;
+    if (g.walk.overflow()) {
+        bzh_set_error(ctx, "grep: %llu records of %llu bytes, room for %llu and %llu", (unsigned long long)g.walk.sel,
+                      (unsigned long long)g.walk.out_bytes, (unsigned long long)g.walk.max, (unsigned long long)g.walk.cap);
+        return BZH_E_CAP;
+    }
+    return BZH_OK;
+}
+
+extern "C" int bzh_grep_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                                   void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_raw && n)) return BZH_E_ARG;
+    GrepSink g;
+    BZH_TRY(grep_begin(ctx, g, pat, plen, flags, delim, d_out, cap, ent, max, nrecs, out_total));
+    if ((uintptr_t)d_raw & 15u) {
+        bzh_set_error(ctx, "grep: the buffer is not 16-byte aligned");
+        return BZH_E_ARG;
+    }
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
+    const int rc = grep_raw_run(ctx, g, (const uint8_t *)d_raw, n);
+    return grep_end(ctx, g, call, rc, nrecs, out_total);
+    });
+}
+
+extern "C" int bzh_grep_device(bzh_ctx *ctx, const void *d_in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                               void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total,
+                               uint64_t *decoded_total, size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n)) return BZH_E_ARG;
+    GrepSink g;
+    BZH_TRY(grep_begin(ctx, g, pat, plen, flags, delim, d_out, cap, ent, max, nrecs, out_total));
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
+    if (decoded_total) *decoded_total = 0;
+    if (consumed) *consumed = 0;
+    std::vector<uint64_t> cands;
+    BZH_TRY(decode_call_scan(ctx, call, d_in, n, cands));
+    SearchSink sink;
+    BZH_TRY(search_job(sink.job, pat, plen, 0, delim, nullptr, 0));
+    sink.grep = &g;
+    size_t total = 0;
+    const int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, nullptr, nullptr, nullptr, &sink);
+    if (decoded_total) *decoded_total = total;
+    return grep_end(ctx, g, call, rc, nrecs, out_total);
+    });
+}
+
+// the host variants: room for the bytes in the staging buffer of the output (asked for with no room: a buffer all the same)
+static size_t grep_stage_room(const uint8_t *out, size_t cap) { return out ? std::max<size_t>(cap, 16) : 0; }
+
+extern "C" int bzh_grep(bzh_ctx *ctx, const uint8_t *in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                        uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total,
+                        uint64_t *decoded_total, size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n) || (!out && cap)) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BZH_TRY(decode_stage(ctx, in, n, grep_stage_room(out, cap)));
+    BZH_TRY(bzh_grep_device(ctx, ctx->d_stage_in, n, pat, plen, flags, delim, out ? ctx->d_stage_out.p : nullptr, cap, ent, max, nrecs, out_total,
+                            decoded_total, consumed));
+    return decode_unstage(ctx, out, out ? (size_t)*out_total : 0);
+    });
+}
+
+extern "C" int bzh_grep_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count,
+                                     const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                                     void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n) || (!idx && count) || (!pts && npts)) return BZH_E_ARG;
+    GrepSink g;
+    BZH_TRY(grep_begin(ctx, g, pat, plen, flags, delim, d_out, cap, ent, max, nrecs, out_total));
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
+    BZH_TRY(search_range_args(ctx, idx, count, pts, npts, nullptr, 0));
+    BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(count, 1), ctx->max_batch)));
+    SearchSink sink;
+    BZH_TRY(search_job(sink.job, pat, plen, 0, delim, nullptr, 0));
+    sink.grep = &g;
+    const int rc = search_range_run(ctx, (const uint8_t *)d_in, n, 0, idx, count, pts, npts, nullptr, 0, ~0ull, sink);
+    return grep_end(ctx, g, call, rc, nrecs, out_total);
+    });
+}
+
+extern "C" int bzh_grep_index(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count,
+                              const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                              uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n) || (!idx && count) || (!pts && npts) || (!out && cap)) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BZH_TRY(decode_stage(ctx, in, n, grep_stage_room(out, cap)));
+    BZH_TRY(bzh_grep_index_device(ctx, ctx->d_stage_in, n, idx, count, pts, npts, pat, plen, flags, delim, out ? ctx->d_stage_out.p : nullptr, cap,
+                                  ent, max, nrecs, out_total));
+    return decode_unstage(ctx, out, out ? (size_t)*out_total : 0);
+    });
+}
+
+extern "C" int bzh_get_grep_stats(const bzh_ctx *ctx, bzh_grep_stats *out)
+{
+    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
+    if (!ctx || !out) return BZH_E_ARG;
+    *out = ctx->gstats;
+    return BZH_OK;
+    });
+}
+
 extern "C" int bzh_get_decode_ranges_stats(const bzh_ctx *ctx, bzh_decode_ranges_stats *out)
 {
     return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {

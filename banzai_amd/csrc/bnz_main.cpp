@@ -9,6 +9,8 @@
 // data from just the compressed bytes that hold them (bzh_index_spans, bzh_decode_ranges); the files are bzh_index_blob_*'s.
 // Search: --search prints the offset and the line number of every occurrence of a byte string in the decoded data, which never
 // leaves the device (bzh_search; with --index bzh_search_range over just the span's compressed bytes).
+// Grep: --grep writes the lines that hold a byte string, selected and compacted on the device (bzh_grep; with --index
+// bzh_grep_index).
 #include <cstdio>
 #include <cstdlib>
 #include <cerrno>
@@ -59,8 +61,12 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "     --range <off>:<len>    with -d --index: write only these bytes of the decoded data; may repeat\n"
             "     --search <string>      print 'offset<TAB>line' of every occurrence of <string> (1 to 256 bytes) in the\n"
             "                            decoded data, lines counted from 0 by '\\n'; nothing is written, the input is kept\n"
-            "     --hex                  with --search: <string> is given as hex digits\n"
-            "     --count                with --search: print the number of occurrences alone\n"
+            "     --grep <string>        write the lines of the decoded data that hold <string> (1 to 256 bytes) to standard\n"
+            "                            out as they are, selected on the GPU; the input is kept\n"
+            "     --invert               with --grep: the lines that do not hold <string>\n"
+            "     --line-number          with --grep: prefix each line with its number, from 1, and ':'\n"
+            "     --hex                  with --search or --grep: <string> is given as hex digits\n"
+            "     --count                with --search: print the number of occurrences alone; with --grep: of lines\n"
             "     --keep      or   -k    keep the input file\n"
             "     --remove    or   -r    remove the input file\n\n"
             "     -1 to -9               block size in 100 kB units (default -9)\n"
@@ -93,7 +99,11 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "     most one --range, the bytes a match must lie wholly inside) it decodes only the blocks the\n"
             "     range touches and reads only their bytes of a regular input file; line numbers then need the\n"
             "     index to be a record index with delimiter '\\n' (banzai_amd.RecordIndex.to_bytes()), else the\n"
-            "     second column is '-'.  GPU: $BZHIP_DEVICE (default 0), or\n"
+            "     second column is '-'.  --grep exits with 0 whether or not anything matched, as --search does;\n"
+            "     a line is every byte up to and including its '\\n', a match that spans a '\\n' belongs to the line\n"
+            "     of its first byte, and an unterminated last line is written as it is.  With --index (a block,\n"
+            "     sync or record index of the input) the whole input goes through the indexed front and every\n"
+            "     block is checked against its entry; --grep takes no --range.  GPU: $BZHIP_DEVICE (default 0), or\n"
             "     $BZHIP_DEVICES=0,1,2,... to spread the blocks over several GPUs of this node;\n"
             "     BZHIP_HUFFMAN=fixed: 2-6 Huffman tables with refinement (smaller, not banzai's exact bytes).\n\n%s\n",
             VERSION);
@@ -105,9 +115,10 @@ const char *VERSION = "version alpha 0.3.1-hip";
 int main(int argc, char **argv)
 {
     if (argc <= 1) usage(false);
-    enum { ANY, NOARGS, OUTPATH, IDXPATH, MKIDXPATH, INTERVAL, RANGE, SEARCH } expect = ANY;
+    enum { ANY, NOARGS, OUTPATH, IDXPATH, MKIDXPATH, INTERVAL, RANGE, SEARCH, GREP } expect = ANY;
     std::string in_path, out_path, index_path, mkindex_path, needle;
     bool searching = false, needle_hex = false, count_only = false;
+    bool grepping = false, invert = false, line_number = false; // (--grep is a --search that writes lines: `searching` holds for both)
     bool interval_given = false;
     uint32_t interval = 256;
     std::vector<bzh_range> ranges;
@@ -165,10 +176,11 @@ int main(int argc, char **argv)
                 die(ERR_ARGS, "Argument '--range' requires <offset>:<length>, both in bytes");
             ranges.push_back(r);
             expect = ANY;
-        } else if (expect == SEARCH) {
-            if (searching) die(ERR_ARGS, "'--search' may be given once");
+        } else if (expect == SEARCH || expect == GREP) {
+            if (searching) die(ERR_ARGS, grepping != (expect == GREP) ? "'--grep' and '--search' exclude each other" : "'--search' and '--grep' may be given once");
             needle = a;
             searching = true;
+            grepping = expect == GREP;
             expect = ANY;
         } else if (expect == ANY && a.rfind("--", 0) == 0) {
             if (a == "--help") usage(true);
@@ -192,6 +204,9 @@ int main(int argc, char **argv)
             else if (a == "--interval") expect = INTERVAL;
             else if (a == "--range") expect = RANGE;
             else if (a == "--search") expect = SEARCH;
+            else if (a == "--grep") expect = GREP;
+            else if (a == "--invert") invert = true;
+            else if (a == "--line-number") line_number = true;
             else if (a == "--hex") needle_hex = true;
             else if (a == "--count") count_only = true;
             else if (a == "--stdout") set_output("", true);
@@ -220,11 +235,15 @@ int main(int argc, char **argv)
     if (expect == INTERVAL) die(ERR_ARGS, "Argument '--interval' requires a number of groups, 0 to 32767");
     if (expect == RANGE) die(ERR_ARGS, "Argument '--range' requires <offset>:<length>, both in bytes");
     if (expect == SEARCH) die(ERR_ARGS, "Argument '--search' requires a string");
+    if (expect == GREP) die(ERR_ARGS, "Argument '--grep' requires a string");
     if (!have_in) die(ERR_ARGS, "An input must be specified");
-    if ((needle_hex || count_only) && !searching) die(ERR_ARGS, "'--hex' and '--count' go with '--search'");
+    if ((needle_hex || count_only) && !searching) die(ERR_ARGS, "'--hex' and '--count' go with '--search' or '--grep'");
+    if ((invert || line_number) && !grepping) die(ERR_ARGS, "'--invert' and '--line-number' go with '--grep'");
+    if (grepping && !ranges.empty()) die(ERR_ARGS, "'--grep' takes an input, '--hex', '--invert', '--count', '--line-number' and '--index', nothing else");
     if (searching) {
         if (decompress || recover || dstream || have_out || !mkindex_path.empty() || level_given || interval_given || keep == 0)
-            die(ERR_ARGS, "'--search' takes an input, '--hex', '--count', '--index' and one '--range', nothing else");
+            die(ERR_ARGS, grepping ? "'--grep' takes an input, '--hex', '--invert', '--count', '--line-number' and '--index', nothing else"
+                                   : "'--search' takes an input, '--hex', '--count', '--index' and one '--range', nothing else");
         if (ranges.size() > 1 || (!ranges.empty() && index_path.empty())) die(ERR_ARGS, "'--search' takes one '--range', with the '--index' of the input");
         if (!index_path.empty() && in_stdin) die(ERR_ARGS, "'--search --index' reads parts of a file: standard in cannot be the input");
         if (needle_hex) {
@@ -317,7 +336,7 @@ int main(int argc, char **argv)
                     for (int j = 0; j < 8; j++) crc = crc >> 1 ^ (0xEDB88320u & (0u - (crc & 1u)));
                 }
                 if ((crc ^ 0xFFFFFFFFu) != (uint32_t)get(32, 4)) die(ERR_FILESYSTEM, damaged);
-                if (get(12, 4) != '\n') die(ERR_ARGS, "'--search' counts lines: " + index_path + " holds records of another delimiter");
+                if (get(12, 4) != '\n' && !grepping) die(ERR_ARGS, "'--search' counts lines: " + index_path + " holds records of another delimiter");
                 cum.resize((size_t)nent + 1);
                 for (size_t e = 0; e <= nent; e++) cum[e] = get(blob.size() - 8 * (nent + 1) + 8 * e, 8);
                 ib = blob.data() + 40;
@@ -341,6 +360,7 @@ int main(int argc, char **argv)
                 die(ERR_OUTPUT, std::string(doing) + "the index names bytes behind the end of " + in_path + ": it is not this file's");
             FILE *rf = fopen(in_path.c_str(), "rb");
             if (!rf) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + in_path + ": " + strerror(errno));
+            if (grepping) lo = 0, hi = (uint64_t)sb.st_size; // (the whole file is walked)
             comp.resize((size_t)(hi - lo));
             if (!comp.empty() && (fseeko(rf, (off_t)lo, SEEK_SET) != 0 || fread(comp.data(), 1, comp.size(), rf) != comp.size()))
                 die(ERR_OUTPUT, std::string(doing) + "read failed");
@@ -357,6 +377,45 @@ int main(int argc, char **argv)
         if (rs != BZH_OK) die(ERR_OUTPUT, std::string(doing) + bzh_strerror(rs));
         static const uint8_t nothing = 0;
         const uint8_t *cp = comp.empty() ? &nothing : comp.data();
+        if (grepping) { // --grep: the selected lines come back compacted; a first try with a guess, a second with the exact rooms
+            const unsigned gflags = invert ? BZH_GREP_INVERT : 0;
+            std::vector<uint8_t> out(count_only ? 0 : (size_t)16 << 20);
+            std::vector<bzh_grep_entry> lines(count_only || !line_number ? 0 : (size_t)1 << 16);
+            size_t nrecs = 0;
+            uint64_t total = 0;
+            for (int attempt = 0; attempt < 2; attempt++) {
+                uint8_t *op = out.empty() ? nullptr : out.data();
+                bzh_grep_entry *lp = lines.empty() ? nullptr : lines.data();
+                if (index_path.empty())
+                    rs = bzh_grep(sctx, cp, comp.size(), pat, needle.size(), gflags, '\n', op, out.size(), lp, lines.size(), &nrecs, &total, nullptr,
+                                  nullptr);
+                else
+                    rs = bzh_grep_index(sctx, cp, comp.size(), ent.data(), ent.size(), pts.data(), pts.size(), pat, needle.size(), gflags, '\n', op,
+                                        out.size(), lp, lines.size(), &nrecs, &total);
+                if (rs != BZH_E_CAP || count_only || attempt) break;
+                out.resize((size_t)total);
+                if (line_number) lines.resize(nrecs);
+            }
+            if (rs != BZH_OK) {
+                const std::string msg = std::string("error during grep: ") + bzh_strerror(rs) + ": " + bzh_last_error(sctx);
+                bzh_destroy(sctx);
+                die(ERR_OUTPUT, msg);
+            }
+            bzh_destroy(sctx);
+            bool ok = true;
+            if (count_only) {
+                printf("%zu\n", nrecs);
+            } else if (line_number) {
+                for (size_t k = 0; k < nrecs && ok; k++) {
+                    printf("%llu:", (unsigned long long)lines[k].record + 1);
+                    ok = fwrite(out.data() + lines[k].out_off, 1, (size_t)lines[k].len, stdout) == (size_t)lines[k].len;
+                }
+            } else if (total) {
+                ok = fwrite(out.data(), 1, (size_t)total, stdout) == (size_t)total;
+            }
+            if (!ok || fflush(stdout) != 0) die(ERR_OUTPUT, "error during grep: write failed");
+            return SUCCESS; // (the input is kept: nothing was made of it)
+        }
         const unsigned flags = records ? BZH_SEARCH_RECORDS : 0;
         std::vector<bzh_hit> hits(count_only ? 0 : (size_t)1 << 16);
         size_t nhits = 0;

@@ -70,6 +70,7 @@ using DevBuf = GrowBuf<false>;
 using PinnedBuf = GrowBuf<true>;
 
 #include "search_plan.h" // the windows of a search and their carry: host-only text (tests/decode_host/search_host.cpp)
+#include "grep_plan.h" // the windows of a grep and their carry: host-only text (tests/decode_host/grep_host.cpp)
 #include "batch.h" // geometry, Batch and its layout, the carver: host-only text (tests/workspace_host)
 
 // Kernel classes of the per-kernel roofline table (bzh_get_kernel_stats).  With profiling on, the launches of a
@@ -188,6 +189,8 @@ struct bzh_ctx {
     DevBuf search_tab, search_out, search_carry; // ... a window's tile tables, its hit slots, the bytes carried to the next window
     size_t search_room = 0;         // bzh_search_set_room: the staging target of the range search (0: the default)
     bzh_search_stats sstats{};      // of the last bzh_search* call
+    DevBuf grep_tab, grep_ent, grep_carry; // bzh_grep*: a window's tile tables, its entries, the open record carried to the next window (staging: search_ws)
+    bzh_grep_stats gstats{};        // of the last bzh_grep* call
     struct DStream *dstrm = nullptr; // streaming decode (bzh_dstream_*, decode.hip): made by the first begin, freed by dstream_free
     size_t dstrm_window = 0, dstrm_staging = 0; // bzh_dstream_set_room: targets of the next begin (0: the defaults)
     // streaming encode (bzh_stream_*)
@@ -599,9 +602,11 @@ struct SearchJob {
     bzh_hit *hits; // host
     uint64_t max;
 };
+struct GrepSink;
 struct SearchSink {
     SearchJob job;
     BzfWalk walk;
+    GrepSink *grep = nullptr; // the call is a grep (bzh_grep*): search_sink_room / search_sink_window hand over to grep.hip's
 };
 int search_job(SearchJob &job, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits, size_t max);
 int search_sink_room(bzh_ctx *ctx, SearchSink &sink, uint64_t bytes, uint8_t **d_stage);
@@ -610,6 +615,23 @@ int search_raw_run(bzh_ctx *ctx, SearchSink &sink, const uint8_t *d_raw, size_t 
 // decode.hip: the hits wholly inside output [off, off + len) of an indexed input, window by window over the touched entries
 int search_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
                      const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len, SearchSink &sink);
+// grep.hip: the selected records of decoded bytes in HBM, compacted into d_out.  A sink is what is looked for, where bytes and
+// entries go, and the walk over its windows (grep_plan.h).  grep_sink_room / grep_sink_window: as the search's, with the whole open
+// record carried; grep_finish: the bytes held back and the open tail, behind the last window.
+struct GrepSink {
+    uint8_t pat[256];
+    uint32_t plen, delim;
+    uint8_t *d_out;      // device (null: not asked for)
+    bzh_grep_entry *ent; // host (null: not asked for)
+    BzgWalk walk;
+    uint64_t front;      // staging position of the window's first new byte
+    const uint8_t *tail; // device: where the carry lies
+    BzgEntry tail_ent;   // grep_finish: the open tail's entry
+};
+int grep_sink_room(bzh_ctx *ctx, GrepSink &g, uint64_t bytes, uint8_t **d_stage);
+int grep_sink_window(bzh_ctx *ctx, GrepSink &g, uint64_t bytes);
+int grep_raw_run(bzh_ctx *ctx, GrepSink &g, const uint8_t *d_raw, size_t n);
+int grep_finish(bzh_ctx *ctx, GrepSink &g, bool *tail_entry);
 // recover.hip: the bits of the kept blocks, end to end from bit 32 of d_out, in one launch (the per-word rule: recover_gather.h)
 struct BzrDesc;
 int recover_gather_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const std::vector<BzrDesc> &descs, uint64_t body, uint32_t *d_out);

@@ -194,6 +194,7 @@ int search_window_run(bzh_ctx *ctx, const SearchJob &job, BzfWalk &walk, const u
 // grows it), the carry put in front of BZF_FRONT.  *d_stage = its base; the decoders expand at *d_stage + BZF_FRONT.
 int search_sink_room(bzh_ctx *ctx, SearchSink &sink, uint64_t bytes, uint8_t **d_stage)
 {
+    if (sink.grep) return grep_sink_room(ctx, *sink.grep, bytes, d_stage);
     uint8_t *base = nullptr;
     BZH_TRY(reserve_cut(ctx, ctx->search_ws, "the search's staging", grow_mib, [&](Carver &c) { c.put(base, (size_t)(BZF_FRONT + bytes + 16)); }));
     ctx->sstats.staging_peak = std::max<uint64_t>(ctx->sstats.staging_peak, ctx->search_ws.cap);
@@ -207,6 +208,7 @@ int search_sink_room(bzh_ctx *ctx, SearchSink &sink, uint64_t bytes, uint8_t **d
 // The window search_sink_room made room for has been expanded and verified: the two passes, then its tail is kept as the carry.
 int search_sink_window(bzh_ctx *ctx, SearchSink &sink, uint64_t bytes)
 {
+    if (sink.grep) return grep_sink_window(ctx, *sink.grep, bytes);
     const uint8_t *base = ctx->search_ws.p;
     const BzfWindow w = sink.walk.window(bytes);
     const uint64_t keep = sink.walk.carry_after(bytes);

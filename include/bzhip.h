@@ -610,6 +610,78 @@ typedef struct {
 } bzh_search_stats;
 BZH_API int bzh_get_search_stats(const bzh_ctx *ctx, bzh_search_stats *out);
 
+/* ---- grep: the records that hold a byte string, compacted on the device into the caller's buffer -------------------------- */
+
+/* A search returns offsets; what is wanted is the line.  A verified batch lies expanded in the search's staging buffer with every
+ * hit and every delimiter known: selecting the records that hold a hit and compacting their bytes are two more streaming passes
+ * over bytes that are already there, beside an entropy stage that is nine tenths of a decode.
+ * CONTRACT, for every call below.  Records are those of the records section: the delimiter belongs to the record it ends, the
+ * unterminated tail is the last record, an empty tail is not a record, nrecords = delimiters + (total > 0 && last byte != delim).
+ * A record is HIT when a match of pat starts inside it: a match that spans a delimiter belongs to the record of its first byte, and
+ * a pattern may contain the delimiter.  A record is SELECTED when it is hit, or with BZH_GREP_INVERT when it is not.
+ * OUTPUT.  The selected records' bytes lie back to back in out, in ascending record order, each with its delimiter; a selected
+ * tail comes as it is.  ent[k] describes the k-th selected record: `record` its number (the number bzh_decode_records takes), `off`
+ * its first byte's offset in the decoded output, `len` its length, `out_off` where it lies in out, the running sum of len.
+ * COUNTS AND ROOM.  *nrecs (selected records) and *out_total (their bytes) are always exact.  An array that is null with zero room
+ * is not asked for and never causes BZH_E_CAP; all of out, cap, ent, max null or zero is a counting call and returns BZH_OK.
+ * Room that is asked for and too small gives BZH_E_CAP: the call goes on counting, out and ent are then unspecified, and
+ * repeating the call with the exact room succeeds.
+ * BZH_E_ARG: plen == 0, plen > BZH_SEARCH_MAX_PATTERN, a flag bit that is not defined, a null pat, nrecs or out_total, a null
+ * array with room claimed; in the device variants a d_out that is not 4-byte aligned.
+ * BOUNDS.  No read goes past the aligned 4-byte word that holds byte n - 1 of a text; no store goes outside out[0, *out_total),
+ * ent[0, *nrecs) and the kernel's own tables.  Every workgroup copies only bytes of its own tile of 4,096: the cost of a call
+ * does not depend on the lengths of the records.
+ * Like every entry point the calls join a streaming pass in flight, run on the context's stream, honour bzh_set_profiling and
+ * leave the context usable after any outcome.  ent is a host array; out is a device buffer in the _device variants. */
+typedef struct {
+    uint64_t record;  /* the record's number, from 0 */
+    uint64_t off;     /* of its first byte in the decoded output */
+    uint64_t len;     /* its bytes, the delimiter included */
+    uint64_t out_off; /* of its first byte in out */
+} bzh_grep_entry;     /* 32 bytes */
+enum { BZH_GREP_INVERT = 1 };
+
+/* Greps decoded bytes that already lie in HBM: the seam the kernel is tested through.  d_raw must be 16-byte aligned, else
+ * BZH_E_ARG; any n, 0 included. */
+BZH_API int bzh_grep_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                                void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total);
+
+/* Greps the output of in[0..n).  The input contract, every check and every error text are bzh_decode's; block and stream CRCs are
+ * verified.  The call is all or nothing: on any error out is unspecified.  *decoded_total = the decoded bytes, *consumed as
+ * bzh_decode reports it (either may be null).  Every batch is expanded into the search's staging buffer behind the open record,
+ * which is carried from batch to batch: an input without any delimiter holds all of its output in the carry.  One host wait a
+ * batch beyond what the decode pays.  bzh_get_decode_stats is filled as by bzh_decode. */
+BZH_API int bzh_grep_device(bzh_ctx *ctx, const void *d_in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                            void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total,
+                            uint64_t *decoded_total, size_t *consumed);
+BZH_API int bzh_grep(bzh_ctx *ctx, const uint8_t *in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                     uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total,
+                     uint64_t *decoded_total, size_t *consumed);
+
+/* Greps the whole indexed input through the indexed front, in windows of whole blocks up to the staging target
+ * (bzh_search_set_room), as bzh_search_range walks them.  in[0..n) holds the whole indexed input.  The index and the points are
+ * checked as by bzh_decode_ranges; every block is checked against its entry, with its CRC over all of its bytes; stream CRCs are
+ * not checked, as there.  npts == 0: one wavefront a block.  It needs no record table: the whole file is walked, so record numbers
+ * count from 0. */
+BZH_API int bzh_grep_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count,
+                                  const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                                  void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total);
+BZH_API int bzh_grep_index(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count,
+                           const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                           uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total);
+
+/* Counters of the last bzh_grep* call. */
+typedef struct {
+    uint64_t records;      /* of the output (nrecords) */
+    uint64_t selected;     /* of them (*nrecs) */
+    uint64_t out_bytes;    /* their bytes (*out_total) */
+    uint64_t windows;      /* one for raw bytes, one a batch, the indexed walk's windows; one more where bytes were held back */
+    uint64_t tiles;        /* of 4,096 bytes, over all windows (the counting pass) */
+    uint64_t carry_peak;   /* bytes of the longest carry: the open record and the last plen - 1 bytes */
+    uint64_t staging_peak; /* bytes of the staging buffer */
+} bzh_grep_stats;
+BZH_API int bzh_get_grep_stats(const bzh_ctx *ctx, bzh_grep_stats *out);
+
 /* ---- the encoder writes the index of its own stream: no decode pass to rediscover what it held -------------------------- */
 
 /* bzh_encode_device that also returns the index of the stream it writes: the entries bzh_decode_index would return for

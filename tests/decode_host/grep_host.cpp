@@ -1,0 +1,449 @@
+// grep_host.cpp -- the grep without a device, built with g++ -fsanitize=address,undefined.
+// (a) What one thread, one tile and the scan of grep_tiles / grep_scan do (banzai_amd/csrc/grep_core.h), run thread by thread and
+//     tile by tile in the kernel's layout -- the tile and its halo in a model of the LDS, every phase for thread 0 .. 255 where the
+//     kernel has a barrier, the counting pass, the scan, the gather -- against a naive split-and-find.  Every buffer has its exact
+//     size, so a read or a store outside it is a sanitizer report.
+// (b) The windows and the carry (banzai_amd/csrc/grep_plan.h), with (a) as the device: blocks of seeded sizes expanded window by
+//     window into a staging buffer that is allocated anew for every window, against the same naive split-and-find.
+//
+//   grep_host <seed> <cases>     exit status 0: everything held
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/bzhip.h"
+#include "../../banzai_amd/csrc/grep_core.h"
+#include "../../banzai_amd/csrc/grep_plan.h"
+#include "../../banzai_amd/csrc/search_plan.h"
+
+static uint64_t rng_state;
+static uint64_t rnd()
+{
+    rng_state ^= rng_state << 13;
+    rng_state ^= rng_state >> 7;
+    rng_state ^= rng_state << 17;
+    return rng_state;
+}
+static uint64_t below(uint64_t n) { return n ? rnd() % n : 0; }
+
+#define CHECK(cond, ...)                                \
+    do {                                                \
+        if (!(cond)) {                                  \
+            fprintf(stderr, "grep_host: %s: ", #cond);  \
+            fprintf(stderr, __VA_ARGS__);               \
+            fprintf(stderr, "\n");                      \
+            exit(1);                                    \
+        }                                               \
+    } while (0)
+
+typedef std::vector<uint8_t> Bytes;
+struct Pattern {
+    uint8_t pat[BZF_MAX_PATTERN];
+    uint32_t plen, delim, invert;
+};
+static bool same(const BzgEntry &a, const BzgEntry &b) { return a.record == b.record && a.off == b.off && a.len == b.len && a.out_off == b.out_off; }
+
+// ---- the truth: split at the delimiter, find in every record ("a match belongs to the record of its first byte") ---------------
+struct Truth {
+    Bytes out;
+    std::vector<BzgEntry> ent;
+    uint64_t nrecords;
+};
+static Truth naive(const Bytes &text, const Pattern &p)
+{
+    Truth tr;
+    const uint64_t n = text.size();
+    uint64_t start = 0, rec = 0;
+    auto close = [&](uint64_t end) { // the record [start, end)
+        bool hit = false;
+        for (uint64_t s = start; s < end && !hit; s++) hit = s + p.plen <= n && memcmp(&text[s], p.pat, p.plen) == 0;
+        if (hit != (p.invert != 0)) {
+            tr.ent.push_back(BzgEntry{rec, start, end - start, tr.out.size()});
+            tr.out.insert(tr.out.end(), text.begin() + start, text.begin() + end);
+        }
+        rec++;
+        start = end;
+    };
+    for (uint64_t i = 0; i < n; i++)
+        if (text[i] == p.delim) close(i + 1);
+    if (start < n) close(n);
+    tr.nrecords = rec;
+    return tr;
+}
+
+// ---- (a) the device ---------------------------------------------------------------------------------------------------------------
+// gf_load16: the aligned 4-byte words that begin in front of n; of the last one the bytes behind n hold anything (0xEE here)
+static void load16(const uint8_t *d, uint64_t n, uint64_t p0, uint32_t *w)
+{
+    for (int k = 0; k < 4; k++) {
+        w[k] = 0;
+        if (p0 + 4 * k >= n) continue;
+        for (int j = 0; j < 4; j++) w[k] |= (uint32_t)(p0 + 4 * k + j < n ? d[p0 + 4 * k + j] : 0xEE) << (8 * j);
+    }
+}
+
+struct Group { // one workgroup: its LDS and its threads' registers
+    std::vector<uint8_t> lds;
+    BzgShared *sh;
+    BzgThread th[BZF_THREADS];
+    Group() : sh(new BzgShared) {}
+    ~Group() { delete sh; }
+};
+#define EVERY for (uint32_t tid = 0; tid < BZF_THREADS; tid++)
+
+// the front of grep_tiles: the tile, the masks, the forward scan
+static void tile_front(const uint8_t *d, const BzgWindow &w, const Pattern &p, uint64_t t, Group &g)
+{
+    g.lds.assign(BZF_TILE + BZF_MAX_PATTERN, 0xAA); // (what a thread does not store is not known)
+    memset(g.sh, 0xAA, sizeof *g.sh);
+    const uint64_t t0 = t * BZF_TILE;
+    EVERY {
+        uint32_t v[4];
+        load16(d, w.n, t0 + tid * BZF_ITEMS, v);
+        memcpy(&g.lds[tid * BZF_ITEMS], v, 16);
+        if (tid * BZF_ITEMS < p.plen - 1) {
+            load16(d, w.n, t0 + BZF_TILE + tid * BZF_ITEMS, v);
+            memcpy(&g.lds[BZF_TILE + tid * BZF_ITEMS], v, 16);
+        }
+    }
+    const uint32_t head = bzf_head_word(p.pat, p.plen), mask = bzf_head_mask(p.plen);
+    EVERY {
+        uint32_t v[5];
+        memcpy(v, &g.lds[tid * BZF_ITEMS], 20);
+        BzgThread &th = g.th[tid];
+        bzg_masks(th, w, t0 + tid * BZF_ITEMS, v[0], v[1], v[2], v[3], v[4], p.delim, head, mask);
+        if (p.plen > 4) {
+            const uint32_t cand = th.hm;
+            th.hm = 0;
+            for (uint32_t k = 0; k < 16; k++)
+                if ((cand >> k & 1u) && bzf_verify(&g.lds[tid * BZF_ITEMS + k], p.pat, p.plen)) th.hm |= 1u << k;
+        }
+        bzg_local(th, p.invert);
+    }
+    EVERY bzg_count_p0(*g.sh, tid, g.th[tid]);
+    for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_f(*g.sh, tid, k);
+}
+
+static void tile_count(const uint8_t *d, const BzgWindow &w, const Pattern &p, uint64_t t, Group &g, BzgTile &out)
+{
+    tile_front(d, w, p, t, g);
+    EVERY bzg_count_p1(*g.sh, tid, g.th[tid], p.invert);
+    for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_s(*g.sh, tid, k);
+    bzg_count_p2(*g.sh, out);
+}
+
+static void tile_gather(const uint8_t *d, const BzgWindow &w, const Pattern &p, uint64_t t, Group &g, const BzgTile &x, const BzgBase &base,
+                        uint8_t *out, BzgEntry *ent)
+{
+    if (x.bytes == 0) return;
+    tile_front(d, w, p, t, g);
+    bool sel_first[BZF_THREADS];
+    uint32_t sm[BZF_THREADS], sdm[BZF_THREADS];
+    EVERY bzg_gather_p1(*g.sh, tid, g.th[tid], x, p.invert, &sel_first[tid]);
+    for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_b(*g.sh, tid, k);
+    EVERY bzg_gather_p2(*g.sh, tid, g.th[tid], x, sel_first[tid], &sm[tid], &sdm[tid]);
+    for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_s(*g.sh, tid, k);
+    CHECK(bzg_bytes(g.sh->s[0][BZF_THREADS - 1]) == x.bytes, "tile %llu: the gather selects %u bytes, the scan said %u", (unsigned long long)t,
+          bzg_bytes(g.sh->s[0][BZF_THREADS - 1]), x.bytes);
+    uint8_t *dst = out ? out + w.out_base + base.out : nullptr;
+    const uint32_t shift = (uint32_t)((uintptr_t)dst & 3u);
+    EVERY bzg_gather_p3(*g.sh, tid, (uint32_t)t, g.th[tid], x, base, w, &g.lds[tid * BZF_ITEMS], sm[tid], sdm[tid], shift, dst != nullptr, ent);
+    if (dst) EVERY bzg_gather_p4(*g.sh, tid, dst, shift, x.bytes);
+}
+
+static void scan(std::vector<BzgTile> &tile, std::vector<BzgBase> &base, const BzgWindow &w, uint64_t *totals)
+{
+    BzgScanShared *sh = new BzgScanShared;
+    memset(sh, 0xAA, sizeof *sh);
+    const uint32_t tiles = (uint32_t)tile.size();
+    EVERY bzg_scan_a(*sh, tid, tile.data(), tiles);
+    bzg_scan_b(*sh, w, totals);
+    EVERY bzg_scan_c(*sh, tid, tile.data(), tiles, w);
+    bzg_scan_d(*sh);
+    EVERY bzg_scan_e(*sh, tid, tile.data(), tiles, w);
+    bzg_scan_f(*sh, totals);
+    EVERY bzg_scan_g(*sh, tid, tile.data(), tiles, base.data());
+    delete sh;
+}
+
+struct Sink { // GrepSink
+    Pattern p;
+    BzgWalk walk;
+    uint8_t *out;  // exactly walk.cap bytes (null: not asked for)
+    BzgEntry *ent; // exactly walk.max entries (null: not asked for)
+    uint64_t windows;
+};
+
+// grep_window_run: d holds exactly w.n bytes.  Returns where the tail starts.
+static uint64_t window_run(Sink &s, const uint8_t *d, const BzgWindow &w, uint64_t bytes)
+{
+    const uint64_t tiles = (w.n + BZF_TILE - 1) / BZF_TILE;
+    uint64_t totals[BZG_TOTALS] = {0, 0, 0, w.t_lo, w.open_hit};
+    s.windows++;
+    if (tiles && w.p_hi > w.p_lo) {
+        std::vector<BzgTile> tile(tiles);
+        std::vector<BzgBase> base(tiles);
+        Group g;
+        for (uint64_t t = 0; t < tiles; t++) tile_count(d, w, s.p, t, g, tile[t]);
+        scan(tile, base, w, totals);
+        if (s.walk.gather(totals)) {
+            std::vector<BzgEntry> ent((size_t)(s.walk.want_ent ? totals[BZG_T_SEL] : 0), BzgEntry{~0ull, ~0ull, ~0ull, ~0ull});
+            ent.shrink_to_fit();
+            for (uint64_t t = 0; t < tiles; t++)
+                tile_gather(d, w, s.p, t, g, tile[t], base[t], s.walk.want_out ? s.out : nullptr, s.walk.want_ent ? ent.data() : nullptr);
+            for (size_t k = 0; k < ent.size(); k++) s.ent[w.sel_base + k] = ent[k];
+        }
+    }
+    s.walk.advance(w, bytes, totals);
+    return totals[BZG_T_TAIL_START];
+}
+
+// grep_finish: tail = the carry's bytes
+static void finish(Sink &s, Bytes &carry)
+{
+    if (s.walk.held) {
+        CHECK(carry.size() == s.walk.carry, "the carry");
+        const uint64_t ts = window_run(s, carry.data(), s.walk.window(s.walk.carry, 0, true), 0);
+        carry.erase(carry.begin(), carry.begin() + ts);
+    }
+    CHECK(carry.size() == s.walk.carry && s.walk.held == 0, "the tail");
+    bool copy, entry;
+    s.walk.tail_rooms(&copy, &entry);
+    const BzgEntry te = s.walk.tail_entry();
+    if (copy && !carry.empty()) memcpy(s.out + s.walk.out_bytes, carry.data(), carry.size());
+    s.walk.tail_done();
+    if (entry) s.ent[s.walk.sel - 1] = te;
+}
+
+// rooms: 0 = not asked for, 1 = above the need, 2 = the need, 3 = one below it, 4 = asked for with no room
+static uint64_t room_of(int kind, uint64_t need) { return kind == 1 ? need + 5 : kind == 2 ? need : kind == 3 ? (need ? need - 1 : 0) : 0; }
+
+// one call: `blocks` lists the sizes of the windows' new bytes (empty: the raw call, one window over the text itself)
+static void run_call(const Bytes &text, const Pattern &p, const std::vector<uint64_t> &blocks, int out_kind, int ent_kind, const Truth &tr,
+                     uint64_t *carry_peak, uint64_t *windows)
+{
+    const uint64_t cap = room_of(out_kind, tr.out.size()), max = room_of(ent_kind, tr.ent.size());
+    uint8_t *out = out_kind ? (uint8_t *)malloc(cap ? cap : 1) : nullptr; // (4-byte aligned, exactly cap bytes: cap 0 has one nobody may touch)
+    std::vector<BzgEntry> ent((size_t)max);
+    ent.shrink_to_fit();
+    Sink s{p, BzgWalk{}, out, ent_kind ? ent.data() : nullptr, 0};
+    if (ent_kind && !max) s.ent = reinterpret_cast<BzgEntry *>(sizeof(BzgEntry)); // (asked for: non-null, never dereferenced)
+    s.walk.begin(p.plen, p.invert != 0, out_kind != 0, cap, ent_kind != 0, max);
+    Bytes carry;
+    if (blocks.empty()) {
+        Bytes d(text); // (exactly n bytes)
+        d.shrink_to_fit();
+        const uint64_t ts = window_run(s, d.data(), s.walk.window(0, text.size(), true), text.size());
+        carry.assign(d.begin() + ts, d.end());
+    } else {
+        uint64_t at = 0;
+        for (uint64_t bytes : blocks) {
+            // grep_sink_room: a staging buffer of its own for every window, the carry in front of the new bytes
+            const uint64_t extra = bzg_front_extra(s.walk.carry, BZF_FRONT), front = extra + BZF_FRONT;
+            Bytes stage(front + bytes, 0xCC);
+            stage.shrink_to_fit();
+            CHECK(carry.size() == s.walk.carry && front >= carry.size(), "the carry fits in front");
+            if (!carry.empty()) memcpy(&stage[front - carry.size()], carry.data(), carry.size());
+            if (bytes) memcpy(&stage[front], &text[at], bytes);
+            at += bytes;
+            const uint64_t ts = window_run(s, stage.data(), s.walk.window(front, bytes, false), bytes);
+            carry.assign(stage.begin() + ts, stage.end());
+        }
+        CHECK(at == text.size(), "the blocks are the text");
+    }
+    finish(s, carry);
+    CHECK(s.walk.sel == tr.ent.size() && s.walk.out_bytes == tr.out.size() && s.walk.nrecords() == tr.nrecords,
+          "counts: %llu selected of %llu bytes, %llu records; the truth %zu, %zu, %llu", (unsigned long long)s.walk.sel,
+          (unsigned long long)s.walk.out_bytes, (unsigned long long)s.walk.nrecords(), tr.ent.size(), tr.out.size(), (unsigned long long)tr.nrecords);
+    const bool over = (out_kind && tr.out.size() > cap) || (ent_kind && tr.ent.size() > max);
+    CHECK(s.walk.overflow() == over, "BZH_E_CAP exactly when a room that is asked for is too small");
+    if (!over) {
+        if (out_kind && !tr.out.empty()) CHECK(memcmp(out, tr.out.data(), tr.out.size()) == 0, "the selected bytes");
+        for (size_t k = 0; ent_kind && k < tr.ent.size(); k++)
+            CHECK(same(ent[k], tr.ent[k]), "entry %zu: record %llu off %llu len %llu out_off %llu, the truth %llu %llu %llu %llu", k,
+                  (unsigned long long)ent[k].record, (unsigned long long)ent[k].off, (unsigned long long)ent[k].len,
+                  (unsigned long long)ent[k].out_off, (unsigned long long)tr.ent[k].record, (unsigned long long)tr.ent[k].off,
+                  (unsigned long long)tr.ent[k].len, (unsigned long long)tr.ent[k].out_off);
+    }
+    if (carry_peak) *carry_peak = std::max(*carry_peak, s.walk.carry_peak);
+    if (windows) *windows = s.windows;
+    free(out);
+}
+
+// ---- texts -------------------------------------------------------------------------------------------------------------------------
+static void plant(Bytes &text, uint64_t at, const Pattern &p)
+{
+    if (at + p.plen <= text.size()) memcpy(&text[at], p.pat, p.plen);
+}
+static Pattern pattern(uint32_t plen, uint32_t delim, uint32_t invert, int kind) // kind 0: letters; 1: begins with the delimiter; 2: ends with it; 3: both
+{
+    Pattern p{};
+    p.plen = plen, p.delim = delim, p.invert = invert;
+    for (uint32_t j = 0; j < plen; j++) p.pat[j] = (uint8_t)('a' + below(2));
+    if (kind & 1) p.pat[0] = (uint8_t)delim;
+    if (kind & 2) p.pat[plen - 1] = (uint8_t)delim;
+    return p;
+}
+// density: one delimiter in `density` bytes (0: none)
+static Bytes letters(uint64_t n, uint32_t delim, uint64_t density)
+{
+    Bytes t(n);
+    for (auto &b : t) b = density && below(density) == 0 ? (uint8_t)delim : (uint8_t)('a' + below(2));
+    return t;
+}
+
+static uint64_t seen_selected, seen_left; // records the truth selects and leaves out
+static void raw_case(const Bytes &text, const Pattern &p, uint64_t *runs)
+{
+    const Truth tr = naive(text, p);
+    seen_selected += tr.ent.size(), seen_left += tr.nrecords - tr.ent.size();
+    run_call(text, p, {}, 2, 2, tr, nullptr, nullptr);
+    (*runs)++;
+}
+
+static void raw_cases()
+{
+    static const uint64_t ns[] = {0, 1, 15, 16, 17, 4095, 4096, 4097, 8192, 12289};
+    static const uint32_t plens[] = {1, 2, 3, 4, 5, 16, 17, 255, 256};
+    uint64_t runs = 0;
+    for (uint64_t n : ns)
+        for (uint32_t plen : plens)
+            for (uint32_t invert = 0; invert < 2; invert++) {
+                const uint32_t delim = '\n';
+                for (int kind = 0; kind < 4; kind++) { // seeded text of every delimiter density, the pattern planted at the edges
+                    const Pattern p = pattern(plen, delim, invert, kind);
+                    static const uint64_t dens[] = {0, 3, 40, 3000};
+                    Bytes text = letters(n, delim, dens[below(4)]);
+                    for (uint64_t edge : {(uint64_t)0, (uint64_t)16, (uint64_t)1024, (uint64_t)4096, (uint64_t)8192, n})
+                        if (below(2)) plant(text, edge >= plen / 2 ? edge - plen / 2 : 0, p);
+                    if (n >= plen && below(2)) plant(text, n - plen, p);
+                    raw_case(text, p, &runs);
+                }
+                const Pattern p = pattern(plen, delim, invert, 0);
+                // a delimiter as the last byte of a thread, of a wave and of a tile, and as the first byte of the next; a tail that is
+                // empty and one that is not
+                for (uint64_t edge : {(uint64_t)16, (uint64_t)1024, (uint64_t)4096})
+                    for (uint64_t at : {edge - 1, edge}) {
+                        Bytes text = letters(n, delim, 0);
+                        if (at < n) text[at] = (uint8_t)delim;
+                        if (below(2) && n) text[n - 1] = (uint8_t)delim;
+                        plant(text, below(n + 1), p);
+                        raw_case(text, p, &runs);
+                    }
+                // a record over three tiles with its only hit in the first, the middle and the last tile
+                if (n == 12289)
+                    for (uint64_t at : {(uint64_t)300, (uint64_t)5000, (uint64_t)9000}) {
+                        Bytes text(n, 'c');
+                        text[100] = text[101] = (uint8_t)delim, text[12000] = (uint8_t)delim;
+                        plant(text, at, p);
+                        raw_case(text, p, &runs);
+                    }
+                // delimiters only (empty records); the pattern is the delimiter; no delimiter at all
+                {
+                    Bytes text(n, (uint8_t)delim);
+                    raw_case(text, p, &runs);
+                    Pattern q = p;
+                    memset(q.pat, (int)delim, q.plen);
+                    raw_case(text, q, &runs);
+                    raw_case(letters(n, delim, 3), q, &runs);
+                    raw_case(letters(n, delim, 0), p, &runs);
+                }
+                // selected output that starts at every residue modulo 16: a first record of 1 .. 16 bytes, then the rest
+                for (uint64_t first = 1; first <= 16 && first < n; first++) {
+                    Bytes text = letters(n, delim, 30);
+                    for (uint64_t j = 0; j < first; j++) text[j] = 'c';
+                    text[first - 1] = (uint8_t)delim;
+                    Pattern q = pattern(1, delim, invert, 0);
+                    q.pat[0] = invert ? 'z' : 'c'; // (the first record is selected either way)
+                    if (first == 1) q.pat[0] = invert ? 'z' : (uint8_t)delim;
+                    raw_case(text, q, &runs);
+                }
+            }
+    // more tiles than the scan has threads: every thread of grep_scan walks a run of tiles, in batches and a rest
+    for (uint64_t tiles : {(uint64_t)700, (uint64_t)2400})
+        for (uint32_t invert = 0; invert < 2; invert++) {
+            const uint64_t n = tiles * BZF_TILE + 77;
+            const Pattern p = pattern(3, '\n', invert, invert ? 2 : 0);
+            Bytes text = letters(n, '\n', invert ? 30000 : 900);
+            for (uint64_t at = 5000; at + 3 < n; at += 70001) plant(text, at, p);
+            raw_case(text, p, &runs);
+        }
+    CHECK(seen_selected > runs && seen_left > runs, "the cases select and leave out: %llu, %llu", (unsigned long long)seen_selected,
+          (unsigned long long)seen_left);
+    printf("raw: %llu calls held (%llu records selected, %llu left out)\n", (unsigned long long)runs, (unsigned long long)seen_selected,
+           (unsigned long long)seen_left);
+}
+
+static void window_cases(uint64_t cases)
+{
+    uint64_t carry_peak = 0, most_windows = 0, over = 0;
+    for (uint64_t c = 0; c < cases; c++) {
+        // the blocks, and the windows of 1 to 4 of them
+        const uint32_t nb = 1 + (uint32_t)below(7);
+        std::vector<uint64_t> blocks, wins;
+        uint64_t n = 0;
+        for (uint32_t k = 0; k < nb; k++) blocks.push_back(1 + below(below(4) ? 600 : 9000)), n += blocks.back();
+        for (uint32_t k = 0; k < nb;) {
+            uint64_t sum = 0;
+            const uint32_t take = 1 + (uint32_t)below(4);
+            for (uint32_t j = 0; j < take && k < nb; j++, k++) sum += blocks[k];
+            wins.push_back(sum);
+        }
+        static const uint32_t plens[] = {1, 2, 3, 4, 5, 16, 17, 255, 256};
+        const uint32_t delim = below(4) ? '\n' : (uint32_t)below(256);
+        Pattern p = pattern(plens[below(9)], delim, (uint32_t)below(2), (int)below(4));
+        static const uint64_t dens[] = {0, 3, 40, 700, 20000};
+        Bytes text = letters(n, delim, dens[below(5)]);
+        if (delim == 'a' || delim == 'b')
+            for (auto &b : text) b = b == delim ? b : (uint8_t)('c' + (b & 1)); // (letters that are not the delimiter)
+        // a window edge with a carry of 1, 511, 512, 513 or 5,000 bytes behind its last delimiter; the only hit in that carry, or
+        // across the edge
+        uint64_t edge = 0;
+        for (size_t k = 0; k + 1 < wins.size(); k++) {
+            edge += wins[k];
+            static const uint64_t carries[] = {1, 511, 512, 513, 5000};
+            const uint64_t cy = carries[below(5)];
+            if (below(2) || edge < cy + 1) continue;
+            for (uint64_t j = edge - cy; j < edge; j++)
+                if (text[j] == delim) text[j] = 'c';
+            text[edge - cy - 1] = (uint8_t)delim;
+            const int how = (int)below(3);
+            if (how == 0 && cy >= p.plen) plant(text, edge - cy + below(cy - p.plen + 1), p);
+            if (how == 1) plant(text, edge >= 1 + below(p.plen) ? edge - 1 - below(p.plen) : 0, p);
+        }
+        edge = 0;
+        for (size_t k = 0; k + 1 < wins.size(); k++) { // a match across the window edge
+            edge += wins[k];
+            if (below(3) == 0) plant(text, edge >= p.plen / 2 ? edge - p.plen / 2 : 0, p);
+        }
+        if (below(4) == 0) { // a text without the pattern's letters but for one planted hit
+            for (auto &b : text) b = b == delim ? b : 'c';
+            plant(text, below(n), p);
+        }
+        const Truth tr = naive(text, p);
+        const int out_kind = (int)below(5), ent_kind = (int)below(5);
+        uint64_t windows = 0;
+        run_call(text, p, wins, out_kind, ent_kind, tr, &carry_peak, &windows);
+        run_call(text, p, wins, 2, 2, tr, nullptr, nullptr); // (and with the exact rooms)
+        most_windows = std::max(most_windows, windows);
+        over += (out_kind >= 3 && !tr.out.empty()) || (ent_kind >= 3 && !tr.ent.empty());
+    }
+    CHECK(carry_peak >= 5000 && most_windows >= 4 && over > cases / 20, "the cases reach the edges: carry %llu, windows %llu, too small %llu",
+          (unsigned long long)carry_peak, (unsigned long long)most_windows, (unsigned long long)over);
+    printf("windows: %llu cases held (longest carry %llu, most windows %llu, %llu with too little room)\n", (unsigned long long)cases,
+           (unsigned long long)carry_peak, (unsigned long long)most_windows, (unsigned long long)over);
+}
+
+int main(int argc, char **argv)
+{
+    rng_state = (argc > 1 ? strtoull(argv[1], nullptr, 10) : 1) * 0x9E3779B97F4A7C15ull + 1;
+    const uint64_t cases = argc > 2 ? strtoull(argv[2], nullptr, 10) : 200;
+    static_assert(sizeof(bzh_grep_entry) == sizeof(BzgEntry) && sizeof(BzgEntry) == 32, "an entry is four words");
+    raw_cases();
+    window_cases(cases);
+    return 0;
+}
