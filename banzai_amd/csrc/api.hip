@@ -1839,22 +1839,29 @@ extern "C" int bzh_decode_records(bzh_ctx *ctx, const uint8_t *in, size_t n, uin
 }
 
 // ---- search (search.hip: the kernel, the passes over a window, the staging; the full search rides on decode_chain_run, the range
-// search on the indexed front: decode.hip; the windows: search_plan.h)
-static int search_begin(bzh_ctx *ctx, SearchSink &sink, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits,
-                        size_t max, size_t *nhits)
+// search on decode_range_sink_run, both as a WindowSink: decode.hip; the windows: search_plan.h)
+// the pattern and the flags of a search or a grep: `who` names the call, `flag` / `flag_name` the one flag it defines
+static int scan_args(bzh_ctx *ctx, const char *who, size_t plen, unsigned flags, unsigned flag, const char *flag_name)
+{
+    if (plen == 0 || plen > BZH_SEARCH_MAX_PATTERN) {
+        bzh_set_error(ctx, "%s: a pattern of %zu bytes, outside 1..%d", who, plen, BZH_SEARCH_MAX_PATTERN);
+        return BZH_E_ARG;
+    }
+    if (flags & ~flag) {
+        bzh_set_error(ctx, "%s: flags 0x%x, of which only %s is defined", who, flags, flag_name);
+        return BZH_E_ARG;
+    }
+    return BZH_OK;
+}
+
+// the checks every search makes first; a sink is made of arguments that have passed them
+static int search_begin(bzh_ctx *ctx, const uint8_t *pat, size_t plen, unsigned flags, bzh_hit *hits, size_t max, size_t *nhits)
 {
     if (!pat || !nhits || (!hits && max)) return BZH_E_ARG;
     *nhits = 0;
-    if (plen == 0 || plen > BZH_SEARCH_MAX_PATTERN) {
-        bzh_set_error(ctx, "search: a pattern of %zu bytes, outside 1..%d", plen, BZH_SEARCH_MAX_PATTERN);
-        return BZH_E_ARG;
-    }
-    if (flags & ~(unsigned)BZH_SEARCH_RECORDS) {
-        bzh_set_error(ctx, "search: flags 0x%x, of which only BZH_SEARCH_RECORDS is defined", flags);
-        return BZH_E_ARG;
-    }
+    BZH_TRY(scan_args(ctx, "search", plen, flags, BZH_SEARCH_RECORDS, "BZH_SEARCH_RECORDS"));
     memset(&ctx->sstats, 0, sizeof ctx->sstats);
-    return search_job(sink.job, pat, plen, flags, delim, hits, max);
+    return BZH_OK;
 }
 
 // rc: the status of the work.  The hits follow the stream to the caller's array: whatever the status, nothing is on its way to it
@@ -1864,8 +1871,8 @@ static int search_end(bzh_ctx *ctx, const SearchSink &sink, int rc, size_t *nhit
     HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
     if (rc != BZH_OK) return rc;
     *nhits = (size_t)sink.walk.rank;
-    if (sink.walk.rank > sink.job.max && sink.job.max) {
-        bzh_set_error(ctx, "search: %llu hits, room for %llu", (unsigned long long)sink.walk.rank, (unsigned long long)sink.job.max);
+    if (sink.walk.rank > sink.max && sink.max) {
+        bzh_set_error(ctx, "search: %llu hits, room for %llu", (unsigned long long)sink.walk.rank, (unsigned long long)sink.max);
         return BZH_E_CAP;
     }
     return BZH_OK;
@@ -1877,8 +1884,8 @@ extern "C" int bzh_search_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, 
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_raw && n)) return BZH_E_ARG;
-    SearchSink sink;
-    BZH_TRY(search_begin(ctx, sink, pat, plen, flags, delim, hits, max, nhits));
+    BZH_TRY(search_begin(ctx, pat, plen, flags, hits, max, nhits));
+    SearchSink sink(pat, plen, flags, delim, hits, max);
     if ((uintptr_t)d_raw & 15u) {
         bzh_set_error(ctx, "search: the buffer is not 16-byte aligned");
         return BZH_E_ARG;
@@ -1897,15 +1904,14 @@ extern "C" int bzh_search_device(bzh_ctx *ctx, const void *d_in, size_t n, const
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_in && n)) return BZH_E_ARG;
-    SearchSink sink;
-    BZH_TRY(search_begin(ctx, sink, pat, plen, flags, delim, hits, max, nhits));
+    BZH_TRY(search_begin(ctx, pat, plen, flags, hits, max, nhits));
+    SearchSink sink(pat, plen, flags, delim, hits, max);
     DecodeCall call;
     BZH_TRY(decode_call_begin(ctx, n, call));
     if (out_total) *out_total = 0;
     if (consumed) *consumed = 0;
     std::vector<uint64_t> cands;
     BZH_TRY(decode_call_scan(ctx, call, d_in, n, cands));
-    sink.walk.begin(sink.job.plen, BZF_FRONT, sink.job.max, 0, ~0ull, 0, 0);
     size_t total = 0;
     int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, nullptr, nullptr, nullptr, &sink);
     if (out_total) *out_total = total;
@@ -1957,8 +1963,8 @@ extern "C" int bzh_search_range_device(bzh_ctx *ctx, const void *d_in, size_t n,
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_in && n) || (!idx && count) || (!pts && npts)) return BZH_E_ARG;
-    SearchSink sink;
-    BZH_TRY(search_begin(ctx, sink, pat, plen, flags, delim, hits, max, nhits));
+    BZH_TRY(search_begin(ctx, pat, plen, flags, hits, max, nhits));
+    SearchSink sink(pat, plen, flags, delim, hits, max);
     DecodeCall call;
     BZH_TRY(decode_call_begin(ctx, n, call));
     BZH_TRY(search_range_args(ctx, idx, count, pts, npts, rec_cum, flags));
@@ -1966,8 +1972,8 @@ extern "C" int bzh_search_range_device(bzh_ctx *ctx, const void *d_in, size_t n,
     uint64_t lo, hi;
     BZH_TRY(bzh_index_span(idx, count, off, len, &first, &last, &lo, &hi));
     BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(last - first, 1), ctx->max_batch)));
-    int rc = search_range_run(ctx, (const uint8_t *)d_in, n, in_byte_base, idx, count, pts, npts, sink.job.records ? rec_cum : nullptr, off, len,
-                              sink);
+    int rc = decode_range_sink_run(ctx, (const uint8_t *)d_in, n, in_byte_base, idx, count, pts, npts, sink.records ? rec_cum : nullptr, off, len,
+                                   sink);
     rc = decode_call_end(ctx, call, rc);
     return search_end(ctx, sink, rc, nhits);
     });
@@ -1981,8 +1987,7 @@ extern "C" int bzh_search_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint6
     if (ctx) stream_join(ctx);
     if (!ctx || (!in && n) || (!idx && count) || (!pts && npts)) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    SearchSink sink; // (the arguments are checked here too: nothing goes up for a call that is refused)
-    BZH_TRY(search_begin(ctx, sink, pat, plen, flags, delim, hits, max, nhits));
+    BZH_TRY(search_begin(ctx, pat, plen, flags, hits, max, nhits)); // (the arguments are checked here too: nothing goes up for a call that is refused)
     BZH_TRY(search_range_args(ctx, idx, count, pts, npts, rec_cum, flags));
     // only the span goes up
     size_t first = 0, last = 0;
@@ -2018,32 +2023,20 @@ extern "C" int bzh_get_search_stats(const bzh_ctx *ctx, bzh_search_stats *out)
 }
 
 // ---- grep (grep.hip: the kernels, the passes over a window, the staging and the carry; the full grep rides on decode_chain_run,
-// the indexed one on search_range_run, both through a search sink that hands over to the grep's; the windows: grep_plan.h)
-static int grep_begin(bzh_ctx *ctx, GrepSink &g, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, void *d_out, size_t cap,
-                      bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
+// the indexed one on decode_range_sink_run, as a WindowSink of its own; the windows: grep_plan.h)
+// the checks every grep makes first; a sink is made of arguments that have passed them
+static int grep_begin(bzh_ctx *ctx, const uint8_t *pat, size_t plen, unsigned flags, void *d_out, size_t cap, bzh_grep_entry *ent, size_t max,
+                      size_t *nrecs, uint64_t *out_total)
 {
     if (!pat || !nrecs || !out_total || (!d_out && cap) || (!ent && max)) return BZH_E_ARG;
     *nrecs = 0;
     *out_total = 0;
-    if (plen == 0 || plen > BZH_SEARCH_MAX_PATTERN) {
-        bzh_set_error(ctx, "grep: a pattern of %zu bytes, outside 1..%d", plen, BZH_SEARCH_MAX_PATTERN);
-        return BZH_E_ARG;
-    }
-    if (flags & ~(unsigned)BZH_GREP_INVERT) {
-        bzh_set_error(ctx, "grep: flags 0x%x, of which only BZH_GREP_INVERT is defined", flags);
-        return BZH_E_ARG;
-    }
+    BZH_TRY(scan_args(ctx, "grep", plen, flags, BZH_GREP_INVERT, "BZH_GREP_INVERT"));
     if ((uintptr_t)d_out & 3u) {
         bzh_set_error(ctx, "grep: the output buffer is not 4-byte aligned");
         return BZH_E_ARG;
     }
     memset(&ctx->gstats, 0, sizeof ctx->gstats);
-    memset(g.pat, 0, sizeof g.pat);
-    memcpy(g.pat, pat, plen);
-    g.plen = (uint32_t)plen, g.delim = delim;
-    g.d_out = (uint8_t *)d_out, g.ent = ent;
-    g.front = 0, g.tail = nullptr, g.tail_ent = BzgEntry{};
-    g.walk.begin((uint32_t)plen, (flags & BZH_GREP_INVERT) != 0, d_out != nullptr, cap, ent != nullptr, max);
     return BZH_OK;
 }
 
@@ -2073,8 +2066,8 @@ extern "C" int bzh_grep_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, co
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_raw && n)) return BZH_E_ARG;
-    GrepSink g;
-    BZH_TRY(grep_begin(ctx, g, pat, plen, flags, delim, d_out, cap, ent, max, nrecs, out_total));
+    BZH_TRY(grep_begin(ctx, pat, plen, flags, d_out, cap, ent, max, nrecs, out_total));
+    GrepSink g(pat, plen, flags, delim, d_out, cap, ent, max);
     if ((uintptr_t)d_raw & 15u) {
         bzh_set_error(ctx, "grep: the buffer is not 16-byte aligned");
         return BZH_E_ARG;
@@ -2093,19 +2086,16 @@ extern "C" int bzh_grep_device(bzh_ctx *ctx, const void *d_in, size_t n, const u
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_in && n)) return BZH_E_ARG;
-    GrepSink g;
-    BZH_TRY(grep_begin(ctx, g, pat, plen, flags, delim, d_out, cap, ent, max, nrecs, out_total));
+    BZH_TRY(grep_begin(ctx, pat, plen, flags, d_out, cap, ent, max, nrecs, out_total));
+    GrepSink g(pat, plen, flags, delim, d_out, cap, ent, max);
     DecodeCall call;
     BZH_TRY(decode_call_begin(ctx, n, call));
     if (decoded_total) *decoded_total = 0;
     if (consumed) *consumed = 0;
     std::vector<uint64_t> cands;
     BZH_TRY(decode_call_scan(ctx, call, d_in, n, cands));
-    SearchSink sink;
-    BZH_TRY(search_job(sink.job, pat, plen, 0, delim, nullptr, 0));
-    sink.grep = &g;
     size_t total = 0;
-    const int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, nullptr, nullptr, nullptr, &sink);
+    const int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, nullptr, nullptr, nullptr, &g);
     if (decoded_total) *decoded_total = total;
     return grep_end(ctx, g, call, rc, nrecs, out_total);
     });
@@ -2136,16 +2126,13 @@ extern "C" int bzh_grep_index_device(bzh_ctx *ctx, const void *d_in, size_t n, c
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_in && n) || (!idx && count) || (!pts && npts)) return BZH_E_ARG;
-    GrepSink g;
-    BZH_TRY(grep_begin(ctx, g, pat, plen, flags, delim, d_out, cap, ent, max, nrecs, out_total));
+    BZH_TRY(grep_begin(ctx, pat, plen, flags, d_out, cap, ent, max, nrecs, out_total));
+    GrepSink g(pat, plen, flags, delim, d_out, cap, ent, max);
     DecodeCall call;
     BZH_TRY(decode_call_begin(ctx, n, call));
     BZH_TRY(search_range_args(ctx, idx, count, pts, npts, nullptr, 0));
     BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(count, 1), ctx->max_batch)));
-    SearchSink sink;
-    BZH_TRY(search_job(sink.job, pat, plen, 0, delim, nullptr, 0));
-    sink.grep = &g;
-    const int rc = search_range_run(ctx, (const uint8_t *)d_in, n, 0, idx, count, pts, npts, nullptr, 0, ~0ull, sink);
+    const int rc = decode_range_sink_run(ctx, (const uint8_t *)d_in, n, 0, idx, count, pts, npts, nullptr, 0, ~0ull, g);
     return grep_end(ctx, g, call, rc, nrecs, out_total);
     });
 }

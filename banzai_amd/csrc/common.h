@@ -185,11 +185,12 @@ struct bzh_ctx {
     bzh_decode_ranges_stats qstats{}; // of the last bzh_decode_ranges* call
     DevBuf ranges_ws;               // bzh_decode_ranges*: a batch's piece tables (allocated on first use)
     DevBuf records_ws;              // records (bzh_decode_index_records*, bzh_decode_records*, bzh_count_records_device): tile counts, last-byte flags, queries, positions
-    DevBuf search_ws;               // bzh_search*: the staging buffer the decoders expand a window into (allocated on first use)
-    DevBuf search_tab, search_out, search_carry; // ... a window's tile tables, its hit slots, the bytes carried to the next window
+    DevBuf search_ws;               // bzh_search*, bzh_grep*: the staging buffer the decoders expand a window into (allocated on first use)
+    DevBuf scan_carry;              // ... and what is carried from one window to the next: the last plen - 1 bytes, or a grep's open record
+    DevBuf search_tab, search_out;  // bzh_search*: a window's tile tables, its hit slots
     size_t search_room = 0;         // bzh_search_set_room: the staging target of the range search (0: the default)
     bzh_search_stats sstats{};      // of the last bzh_search* call
-    DevBuf grep_tab, grep_ent, grep_carry; // bzh_grep*: a window's tile tables, its entries, the open record carried to the next window (staging: search_ws)
+    DevBuf grep_tab, grep_ent;      // bzh_grep*: a window's tile tables, its entries
     bzh_grep_stats gstats{};        // of the last bzh_grep* call
     struct DStream *dstrm = nullptr; // streaming decode (bzh_dstream_*, decode.hip): made by the first begin, freed by dstream_free
     size_t dstrm_window = 0, dstrm_staging = 0; // bzh_dstream_set_room: targets of the next begin (0: the defaults)
@@ -553,10 +554,26 @@ struct RecBuild { // bzh_decode_index_records*: the index build also counts the 
     std::vector<uint64_t> cum; // [entries + 1] delimiters in front of every entry, and of the end
     bool last_is_delim;        // the last byte of the output is one
 };
-struct SearchSink; // bzh_search*: every batch is expanded into the search's staging buffer and searched there; nothing goes to d_out
+// A consumer of decoded windows (bzh_search*, bzh_grep*): the decoders expand WHOLE blocks, window after window, into a staging
+// buffer that the sink owns, and hand every window over once all of its blocks have passed their CRCs.  This is all decode.hip
+// knows of a search or a grep (search.hip, grep.hip: SearchSink, GrepSink).
+struct WindowSink {
+    const uint64_t front; // the decoders expand at *d_stage + front (whatever is carried between two windows lies in front of it)
+    const uint32_t delim; // of the records, where the walk counts them (BackCount)
+    WindowSink(uint64_t front_, uint32_t delim_) : front(front_), delim(delim_) {}
+    // the wanted range [lo, hi) of the output; the output offset of the first window's first byte, the delimiters in front of it
+    virtual void begin(uint64_t lo, uint64_t hi, uint64_t out_start, uint64_t rec_start) = 0;
+    // the staging for the next window of `bytes` decoded bytes: whole blocks, at least one, so a block above the target grows it
+    virtual int room(bzh_ctx *ctx, uint64_t bytes, uint8_t **d_stage) = 0;
+    // the window room() made room for has been expanded and verified
+    virtual int window(bzh_ctx *ctx, uint64_t bytes) = 0;
+
+protected:
+    ~WindowSink() = default;
+};
 int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t cap, size_t *out_len, size_t *consumed,
                      const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index = nullptr, SyncBuild *sync = nullptr,
-                     RecBuild *rec = nullptr, SearchSink *srch = nullptr);
+                     RecBuild *rec = nullptr, WindowSink *sink = nullptr);
 // decode.hip: the two checks of an index and its sync points as a whole, then the blocks of a verified index that
 // [off, off + len) touches, from d_in = the indexed input from byte in_byte_base on (windows and segments: decode_plan.h)
 int decode_index_check(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count); // BZH_E_ARG naming the entry that is ill formed
@@ -592,44 +609,50 @@ size_t dstream_consumed(const bzh_ctx *ctx);
 int dstream_stats(const bzh_ctx *ctx, bzh_dstream_stats *out);
 void dstream_end(bzh_ctx *ctx);  // abandon: the buffers stay for the next begin
 void dstream_free(bzh_ctx *ctx); // bzh_destroy
-// search.hip: the search over decoded bytes in HBM.  A job is what is looked for and where the hits go; a sink is a job and the walk
-// over its windows (search_plan.h).  search_sink_room / search_sink_window: the staging buffer for the next window of `bytes` whole
-// blocks (the decoder expands at *d_stage + BZF_FRONT), and the two passes over it once it is verified.
-struct SearchJob {
-    uint8_t pat[256];
-    uint32_t plen, delim;
+// decode.hip: the blocks that output [off, off + len) of an indexed input touches, window by window into a sink, which applies the
+// range (rec_cum: the record table, for a sink that numbers records; null: none)
+int decode_range_sink_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                          const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len, WindowSink &sink);
+// search.hip: what the two sinks share on the host.  scan_room: ctx->search_ws grown to a window of `bytes` behind a carry of `carry`
+// bytes, which is copied from ctx->scan_carry in front of the new bytes; *front = their staging position, *d_stage as
+// WindowSink::room's.  scan_tiles: the tiles of a window of n bytes, counted into the call's statistics.
+int scan_room(bzh_ctx *ctx, const char *what, uint64_t carry, uint64_t bytes, uint64_t *staging_peak, uint8_t **d_stage, uint64_t *front);
+int scan_tiles(bzh_ctx *ctx, const char *who, uint64_t n, uint64_t *windows, uint64_t *tiles_sum, uint32_t *tiles);
+// search.hip: the search over decoded bytes in HBM.  A sink is what is looked for, where the hits go, and the walk over its windows
+// (search_plan.h): room() puts the carry in front of the window, window() runs the two passes and keeps the window's tail.
+struct SearchSink final : WindowSink {
+    BzfPattern pat;
     bool records;
     bzh_hit *hits; // host
     uint64_t max;
-};
-struct GrepSink;
-struct SearchSink {
-    SearchJob job;
     BzfWalk walk;
-    GrepSink *grep = nullptr; // the call is a grep (bzh_grep*): search_sink_room / search_sink_window hand over to grep.hip's
+    SearchSink(const uint8_t *pat_, size_t plen, unsigned flags, uint8_t delim_, bzh_hit *hits_, size_t max_)
+        : WindowSink(BZF_FRONT, delim_), pat(bzf_pattern(pat_, (uint32_t)plen, delim_)), records((flags & BZH_SEARCH_RECORDS) != 0), hits(hits_), max(max_) {}
+    void begin(uint64_t lo, uint64_t hi, uint64_t out_start, uint64_t rec_start) override { walk.begin(pat.plen, front, max, lo, hi, out_start, rec_start); }
+    int room(bzh_ctx *ctx, uint64_t bytes, uint8_t **d_stage) override;
+    int window(bzh_ctx *ctx, uint64_t bytes) override;
 };
-int search_job(SearchJob &job, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits, size_t max);
-int search_sink_room(bzh_ctx *ctx, SearchSink &sink, uint64_t bytes, uint8_t **d_stage);
-int search_sink_window(bzh_ctx *ctx, SearchSink &sink, uint64_t bytes);
 int search_raw_run(bzh_ctx *ctx, SearchSink &sink, const uint8_t *d_raw, size_t n);
-// decode.hip: the hits wholly inside output [off, off + len) of an indexed input, window by window over the touched entries
-int search_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
-                     const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len, SearchSink &sink);
 // grep.hip: the selected records of decoded bytes in HBM, compacted into d_out.  A sink is what is looked for, where bytes and
-// entries go, and the walk over its windows (grep_plan.h).  grep_sink_room / grep_sink_window: as the search's, with the whole open
-// record carried; grep_finish: the bytes held back and the open tail, behind the last window.
-struct GrepSink {
-    uint8_t pat[256];
-    uint32_t plen, delim;
+// entries go, and the walk over its windows (grep_plan.h): as the search's, with the whole open record carried (begin() has nothing
+// to say: a grep takes the whole output).  grep_finish: the bytes held back and the open tail, behind the last window.
+struct GrepSink final : WindowSink {
+    BzfPattern pat;
     uint8_t *d_out;      // device (null: not asked for)
     bzh_grep_entry *ent; // host (null: not asked for)
     BzgWalk walk;
-    uint64_t front;      // staging position of the window's first new byte
-    const uint8_t *tail; // device: where the carry lies
-    BzgEntry tail_ent;   // grep_finish: the open tail's entry
+    uint64_t at = 0;               // staging position of the window's first new byte
+    const uint8_t *tail = nullptr; // device: where the carry lies
+    BzgEntry tail_ent{};           // grep_finish: the open tail's entry
+    GrepSink(const uint8_t *pat_, size_t plen, unsigned flags, uint8_t delim_, void *d_out_, size_t cap, bzh_grep_entry *ent_, size_t max)
+        : WindowSink(BZF_FRONT, delim_), pat(bzf_pattern(pat_, (uint32_t)plen, delim_)), d_out((uint8_t *)d_out_), ent(ent_)
+    {
+        walk.begin((uint32_t)plen, (flags & BZH_GREP_INVERT) != 0, d_out != nullptr, cap, ent != nullptr, max);
+    }
+    void begin(uint64_t, uint64_t, uint64_t, uint64_t) override {}
+    int room(bzh_ctx *ctx, uint64_t bytes, uint8_t **d_stage) override;
+    int window(bzh_ctx *ctx, uint64_t bytes) override;
 };
-int grep_sink_room(bzh_ctx *ctx, GrepSink &g, uint64_t bytes, uint8_t **d_stage);
-int grep_sink_window(bzh_ctx *ctx, GrepSink &g, uint64_t bytes);
 int grep_raw_run(bzh_ctx *ctx, GrepSink &g, const uint8_t *d_raw, size_t n);
 int grep_finish(bzh_ctx *ctx, GrepSink &g, bool *tail_entry);
 // recover.hip: the bits of the kept blocks, end to end from bit 32 of d_out, in one launch (the per-word rule: recover_gather.h)

@@ -1103,11 +1103,13 @@ static int back_emit(bzh_ctx *ctx, const DecWs &w, StageClock &clock, Back &bk, 
 // The chain walk and the back of the decoder.  cands: decode_scan_run's list.  The arena holds min(cands, max_batch) blocks.
 // index: the call builds a block index (bzh_decode_index*) -- cap is 0, nothing is expanded, every block's CRC comes from
 // unrle_crc and is checked like a full decode's, and the entries are appended in chain order.
-// srch: the call is a search (bzh_search*) -- cap does not bound it, a batch's blocks are expanded behind the carry in the search's
-// staging buffer instead of at total_out in d_out, and behind the batch's CRC checks the sink runs its two passes over them.
+// sink: the call feeds a consumer of windows (bzh_search*, bzh_grep*: WindowSink, common.h) -- cap does not bound it, every batch is
+// a window: its blocks are expanded at sink->front of the sink's staging buffer instead of at total_out in d_out, and behind the
+// batch's CRC checks the sink is given the window.  The sink takes the whole output: begin(0, ~0, 0, 0), here and only here.
 int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t cap, size_t *out_len, size_t *consumed,
-                     const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index, SyncBuild *sync, RecBuild *rec, SearchSink *srch)
+                     const std::vector<uint64_t> &cands, std::vector<bzh_index_entry> *index, SyncBuild *sync, RecBuild *rec, WindowSink *sink)
 {
+    if (sink) sink->begin(0, ~0ull, 0, 0);
     hipStream_t st = ctx->stream;
     Batch &bt = ctx->bt;
     bzh_decode_stats &ds = ctx->dstats;
@@ -1239,13 +1241,13 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
                             return data_error(BZD_K_FORMAT, it.bitpos, "the block ends in four equal bytes without a count");
                         }
                 }
-                b.base = srch ? (int64_t)(BZF_FRONT + batch_bytes) : (int64_t)total_out;
+                b.base = sink ? (int64_t)(sink->front + batch_bytes) : (int64_t)total_out;
                 batch_bytes += b.size;
                 total_out += b.size;
             }
-            if (!srch && total_out > cap) over = true; // (sizing goes on: the caller learns the total)
+            if (!sink && total_out > cap) over = true; // (sizing goes on: the caller learns the total)
             uint8_t *d_to = d_out;
-            if (srch) BZH_TRY(search_sink_room(ctx, *srch, batch_bytes, &d_to)); // (the sizes are known: the staging grows to the batch)
+            if (sink) BZH_TRY(sink->room(ctx, batch_bytes, &d_to)); // (the sizes are known: the staging grows to the batch)
             if (index || !over) { // an index: the CRCs of the expansions, with nothing expanded
                 for (BackBlock &b : blocks) b.lo = 0, b.hi = index ? 0 : (uint32_t)b.size;
                 BZH_TRY(back_emit(ctx, w, clock, bk, d_to, true, blocks, false, nullptr, index && rec ? &bc : nullptr));
@@ -1288,7 +1290,7 @@ int decode_chain_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_out
         }
         stream = stream_at;
         block = block_at;
-        if (srch && !blocks.empty()) BZH_TRY(search_sink_window(ctx, *srch, batch_bytes)); // (every block of the batch has passed its CRC)
+        if (sink && !blocks.empty()) BZH_TRY(sink->window(ctx, batch_bytes)); // (every block of the batch has passed its CRC)
         if (finished) break;
     }
     clock.collect();
@@ -2316,14 +2318,17 @@ int count_records_run(bzh_ctx *ctx, const uint8_t *d_raw, size_t n, uint8_t deli
 }
 
 // ================================================================================================================
-// Search in a range of an indexed input (bzh_search_range*): windows of consecutive touched entries through the indexed front and
-// the back, WHOLE blocks into the search's staging buffer; the range is applied by the search (the windows: search_plan.h)
+// A range of an indexed input, window by window into a sink (bzh_search_range*, bzh_grep_index*): windows of consecutive touched
+// entries through the indexed front and the back, WHOLE blocks at sink.front of the sink's staging buffer.  The sink is told the
+// range -- begin(), here and only here -- and applies it; the walk knows the sink by WindowSink alone (the windows' sizes:
+// bzf_window_blocks, search_plan.h; the target: bzh_search_set_room).  With a record table the walk also holds every entry's
+// delimiters against it; only the range search passes one, and the text of that refusal is its own.
 // ================================================================================================================
 constexpr size_t SEARCH_ROOM = (size_t)128 << 20; // the default bzhip.h documents
 
 // (idx has passed decode_index_check, pts decode_sync_check, rec_cum -- null without BZH_SEARCH_RECORDS -- bzq_table_check)
-int search_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
-                     const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len, SearchSink &sink)
+int decode_range_sink_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                          const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len, WindowSink &sink)
 {
     size_t first, last;
     uint64_t byte_lo, byte_hi, clipped;
@@ -2332,12 +2337,12 @@ int search_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_by
     BZH_TRY(index_covered(ctx, idx, first, last - 1, in_byte_base, n));
     DecWs w;
     BZH_TRY(dec_ws(ctx, w));
-    BackCount bc{sink.job.delim, nullptr, nullptr, {}, {}};
+    BackCount bc{sink.delim, nullptr, nullptr, {}, {}};
     if (rec_cum) BZH_TRY(back_count_ws(ctx, bc));
     StageClock clock{ctx, {}};
     const size_t Bmax = batch_max(ctx);
     const uint64_t room = ctx->search_room ? ctx->search_room : SEARCH_ROOM;
-    sink.walk.begin(sink.job.plen, BZF_FRONT, sink.job.max, off, off + clipped, idx[first].out_off, rec_cum ? rec_cum[first] : 0);
+    sink.begin(off, off + clipped, idx[first].out_off, rec_cum ? rec_cum[first] : 0);
     std::vector<uint32_t> ent;
     IndexedFront fr{ctx, w, clock, d_in, n, in_byte_base, idx, pts, npts};
     for (size_t at = first; at < last;) {
@@ -2355,17 +2360,17 @@ int search_range_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t in_by
             }
         }
         uint8_t *d_stage = nullptr;
-        BZH_TRY(search_sink_room(ctx, sink, bytes, &d_stage));
+        BZH_TRY(sink.room(ctx, bytes, &d_stage));
         uint64_t local = 0;
         for (uint32_t k = 0; k < B; k++) {
             BackBlock &b = fr.blocks[k];
             b.lo = 0, b.hi = (uint32_t)b.size;
-            b.base = (int64_t)(BZF_FRONT + local);
+            b.base = (int64_t)(sink.front + local);
             local += b.size;
         }
         BZH_TRY(back_emit(ctx, w, clock, fr.bk, d_stage, true, fr.blocks));
         BZH_TRY(fr.crcs(ent.data(), B));
-        BZH_TRY(search_sink_window(ctx, sink, bytes));
+        BZH_TRY(sink.window(ctx, bytes));
         at += B;
     }
     clock.collect();

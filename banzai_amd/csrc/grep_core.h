@@ -1,7 +1,8 @@
 // grep_core.h -- what ONE THREAD and ONE TILE of grep_tiles (grep.hip) do, and the scan between the two passes (grep_scan): which
 // records of a window hold a match, and where their bytes go.  Plain C++ without a launch in it: the kernel compiles it for the
 // device, tests/decode_host/grep_host.cpp for the host, where it runs thread by thread and tile by tile in the kernel's layout
-// against a naive split-and-find.  The masks of a thread's 16 bytes are search_core.h's.
+// against a naive split-and-find.  The tile front -- the load, the staging, the filter and the verify -- and the masks of a
+// thread's 16 bytes are search_core.h's; what is here begins with a thread's hit starts and delimiters.
 //
 // THE WINDOW.  Positions are in the coordinates of the buffer the kernel is given (BzgWindow).  The text is [t_lo, n) and begins at
 // a record start.  A window PROCESSES the positions [p_lo, p_hi): their delimiters close records, and matches that start there are
@@ -104,13 +105,13 @@ struct BzgThread {
     uint32_t loc_bytes;    // ... and the sum of their lengths
 };
 
-// the masks of a thread's 16 bytes at position p0 (next: the word behind them; the verify of a pattern above 4 bytes is the
-// caller's: it reads the tile), and what it can say about its own bytes
-BZF_FN void bzg_masks(BzgThread &t, const BzgWindow &w, uint64_t p0, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t next,
-                      uint32_t delim, uint32_t head, uint32_t hmask)
+// the masks of a thread's 16 bytes `own` at position p0 (hm: its hit starts, bzf_match16 under bzg_starts), and what it can say
+// about its own bytes
+BZF_FN uint32_t bzg_starts(const BzgWindow &w, uint64_t p0) { return bzf_range_mask16(p0, w.p_lo, w.s_hi); }
+BZF_FN void bzg_masks(BzgThread &t, const BzgWindow &w, uint64_t p0, const BzfVec &own, uint32_t delim, uint32_t hm)
 {
-    t.dm = bzf_eq_mask16(w0, w1, w2, w3, delim) & bzf_range_mask16(p0, w.p_lo, w.p_hi);
-    t.hm = bzf_filter16(w0, w1, w2, w3, next, bzf_range_mask16(p0, w.p_lo, w.s_hi), head, hmask);
+    t.dm = bzf_eq_mask16(own.x, own.y, own.z, own.w, delim) & bzf_range_mask16(p0, w.p_lo, w.p_hi);
+    t.hm = hm;
     t.vm = bzf_range_mask16(p0, w.t_lo, w.p_hi);
 }
 BZF_FN void bzg_local(BzgThread &t, uint32_t invert)

@@ -1,6 +1,8 @@
 // search.hip -- every occurrence of a byte string in decoded bytes that lie in HBM (bzh_search*): the kernel, the two passes over
-// one window, and the staging buffer the decoders expand into (the windows and the carry: search_plan.h; what one thread does:
-// search_core.h).  The bytes never leave the device: what comes back is a word a window, and the hits.
+// one window, and the search as a WindowSink of the decoders (common.h), with the two host helpers it shares with the grep's sink:
+// the staging room and the tile count.  The windows and the carry: search_plan.h; the tile front -- load, staging, filter, verify,
+// shared with grep_tiles -- and what one thread does behind it: search_core.h.  The bytes never leave the device: what comes back
+// is a word a window, and the hits.
 #include "common.h"
 #include "search_core.h"
 
@@ -8,32 +10,14 @@ static_assert(BZF_MAX_PATTERN == BZH_SEARCH_MAX_PATTERN, "search_core.h and bzhi
 static_assert(BZF_FRONT % 16 == 0 && BZF_FRONT >= BZF_MAX_PATTERN, "a window begins aligned, its carry in front of it");
 static_assert(sizeof(bzh_hit) == 16, "a hit is two words");
 
-struct SfPat { // the pattern, by value in the kernel's arguments
-    uint32_t w[BZF_MAX_PATTERN / 4];
-};
-
 struct SfArgs {
     const uint8_t *d; // 16-byte aligned
     BzfWindow win;
-    uint32_t plen, delim, records;
-    uint32_t head, hmask;          // the filter's word and mask (search_core.h)
+    uint32_t records;
     uint32_t *thits, *tdel;        // [tiles] pass one: hits and delimiters of every tile
     const uint64_t *hbase, *dbase; // [tiles] search_scan: those in front of every tile
     bzh_hit *out;                  // the window's hit slots [0, win.emit)
 };
-
-// A thread's 16 bytes at position p0 of d[0, n).  Inside the text: one aligned 16-byte load.  At its end: the aligned 4-byte words
-// that begin in front of n, zeros behind them -- no read goes past the word that holds byte n - 1.
-__device__ __forceinline__ uint4 sf_load16(const uint8_t *d, uint64_t n, uint64_t p0)
-{
-    if (p0 + 16 <= n) return *reinterpret_cast<const uint4 *>(d + p0);
-    uint4 v;
-    v.x = p0 < n ? *reinterpret_cast<const uint32_t *>(d + p0) : 0u;
-    v.y = p0 + 4 < n ? *reinterpret_cast<const uint32_t *>(d + p0 + 4) : 0u;
-    v.z = p0 + 8 < n ? *reinterpret_cast<const uint32_t *>(d + p0 + 8) : 0u;
-    v.w = p0 + 12 < n ? *reinterpret_cast<const uint32_t *>(d + p0 + 12) : 0u;
-    return v;
-}
 
 // One workgroup a tile of 4,096 positions, 16 a thread.  The tile and the halo behind it are staged in LDS, the pattern too (every
 // lane reads the same byte of it).  EMIT false: the tile's hits and delimiters, reduced over the workgroup, a plain store each -- no
@@ -41,7 +25,7 @@ __device__ __forceinline__ uint4 sf_load16(const uint8_t *d, uint64_t n, uint64_
 // and every hit whose rank in the window is below win.emit stores itself at its rank: the output ascends, and "the first max" costs
 // nothing.  Stores: the tile's two words, or hit slots below win.emit.
 template <bool EMIT>
-__global__ void __launch_bounds__(BZF_THREADS) search_tiles(SfArgs a, SfPat p)
+__global__ void __launch_bounds__(BZF_THREADS) search_tiles(SfArgs a, BzfPattern p)
 {
     __shared__ __attribute__((aligned(16))) uint8_t tile[BZF_TILE + BZF_MAX_PATTERN];
     __shared__ __attribute__((aligned(4))) uint8_t pat[BZF_MAX_PATTERN];
@@ -49,24 +33,10 @@ __global__ void __launch_bounds__(BZF_THREADS) search_tiles(SfArgs a, SfPat p)
     const uint32_t tid = threadIdx.x;
     if (EMIT && (a.thits[blockIdx.x] == 0 || a.hbase[blockIdx.x] >= a.win.emit)) return; // (the same for every thread)
     const uint64_t n = a.win.n, t0 = (uint64_t)blockIdx.x * BZF_TILE, p0 = t0 + tid * BZF_ITEMS;
-    if (tid < BZF_MAX_PATTERN / 4) reinterpret_cast<uint32_t *>(pat)[tid] = p.w[tid];
-    const uint4 own = sf_load16(a.d, n, p0);
-    *reinterpret_cast<uint4 *>(tile + tid * BZF_ITEMS) = own;
-    if (tid * BZF_ITEMS < a.plen - 1) // the halo: the head of the next tile, as far as a match that starts in this one can reach
-        *reinterpret_cast<uint4 *>(tile + BZF_TILE + tid * BZF_ITEMS) = sf_load16(a.d, n, t0 + BZF_TILE + tid * BZF_ITEMS);
+    const BzfVec own = bzf_stage(a.d, n, t0, tid, p, tile, pat);
     __syncthreads();
-    const uint32_t next = *reinterpret_cast<const uint32_t *>(tile + tid * BZF_ITEMS + BZF_ITEMS); // (thread 255: the halo's first word, or what lies there)
-    const uint32_t dm = a.records ? bzf_eq_mask16(own.x, own.y, own.z, own.w, a.delim) & bzf_range_mask16(p0, a.win.d_lo, n) : 0u;
-    uint32_t cand = bzf_filter16(own.x, own.y, own.z, own.w, next, bzf_range_mask16(p0, a.win.s_lo, a.win.s_hi), a.head, a.hmask);
-    uint32_t hm = cand;
-    if (a.plen > 4) {
-        hm = 0;
-        while (cand) {
-            const uint32_t k = (uint32_t)__ffs((int)cand) - 1u;
-            cand &= cand - 1u;
-            if (bzf_verify(tile + tid * BZF_ITEMS + k, pat, a.plen)) hm |= 1u << k;
-        }
-    }
+    uint32_t hm = bzf_match16(own, tid, p, tile, pat, bzf_range_mask16(p0, a.win.s_lo, a.win.s_hi));
+    const uint32_t dm = a.records ? bzf_eq_mask16(own.x, own.y, own.z, own.w, p.delim) & bzf_range_mask16(p0, a.win.d_lo, n) : 0u;
     const uint32_t nh = (uint32_t)__popc(hm), nd = (uint32_t)__popc(dm);
     if (!EMIT) {
         const uint32_t sh = wave_reduce_add(nh), sd = wave_reduce_add(nd);
@@ -94,7 +64,7 @@ __global__ void __launch_bounds__(BZF_THREADS) search_tiles(SfArgs a, SfPat p)
                 } else { // a start in the carry: the delimiters between it and d_lo were counted by the window before
                     const uint32_t gap = (uint32_t)min(a.win.d_lo - pos, (uint64_t)(BZF_MAX_PATTERN - 1)); // (the halo holds them)
                     uint32_t c = 0;
-                    for (uint32_t j = 0; j < gap; j++) c += tile[tid * BZF_ITEMS + k + j] == a.delim;
+                    for (uint32_t j = 0; j < gap; j++) c += tile[tid * BZF_ITEMS + k + j] == p.delim;
                     rec = a.win.rec_base - c;
                 }
             }
@@ -132,96 +102,97 @@ __global__ void __launch_bounds__(BZF_THREADS) search_scan(const uint32_t *thits
     }
 }
 
-// ---- host side ---------------------------------------------------------------------------------------------------
-int search_job(SearchJob &job, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits, size_t max)
+// ---- host side: what the search's and the grep's sinks share --------------------------------------------------------------
+// The staging buffer for a window of `bytes` decoded bytes behind a carry of `carry` bytes: grown to them (whole blocks, at least
+// one, so a block above the target grows it), the carry copied in front of the new bytes.  The decoders expand at
+// *d_stage + BZF_FRONT = staging position *front; *d_stage lies as far inside the buffer as the carry exceeds BZF_FRONT (a search's
+// never does).
+int scan_room(bzh_ctx *ctx, const char *what, uint64_t carry, uint64_t bytes, uint64_t *staging_peak, uint8_t **d_stage, uint64_t *front)
 {
-    memset(&job, 0, sizeof job);
-    memcpy(job.pat, pat, plen);
-    job.plen = (uint32_t)plen;
-    job.delim = delim;
-    job.records = (flags & BZH_SEARCH_RECORDS) != 0;
-    job.hits = hits;
-    job.max = max;
+    const uint64_t extra = bzg_front_extra(carry, BZF_FRONT);
+    uint8_t *base = nullptr;
+    BZH_TRY(reserve_cut(ctx, ctx->search_ws, what, grow_mib, [&](Carver &c) { c.put(base, (size_t)(extra + BZF_FRONT + bytes + 16)); }));
+    *staging_peak = std::max<uint64_t>(*staging_peak, ctx->search_ws.cap);
+    *front = extra + BZF_FRONT;
+    if (carry) // (kept apart between two windows: the staging buffer may have moved)
+        HIP_TRY(ctx, hipMemcpyAsync(base + *front - carry, ctx->scan_carry, (size_t)carry, hipMemcpyDeviceToDevice, ctx->stream));
+    *d_stage = base + extra;
     return BZH_OK;
 }
 
+// The tiles of a window of n bytes, one launch's worth at most; the window and they are counted.  who: "search" or "grep".
+int scan_tiles(bzh_ctx *ctx, const char *who, uint64_t n, uint64_t *windows, uint64_t *tiles_sum, uint32_t *tiles)
+{
+    const uint64_t tiles64 = (n + BZF_TILE - 1) / BZF_TILE;
+    if (tiles64 > 0x7FFFFFFFull) {
+        bzh_set_error(ctx, "%s: a window of %llu bytes is beyond one launch", who, (unsigned long long)n);
+        return BZH_E_ARG;
+    }
+    *tiles = (uint32_t)tiles64;
+    (*windows)++;
+    *tiles_sum += tiles64;
+    return BZH_OK;
+}
+
+// ---- host side: the search ---------------------------------------------------------------------------------------------------------
 // The two passes over the window w of d (16-byte aligned; w.n bytes lie there, and the aligned word that holds the last of them).
 // One wait, for the window's two totals; the hits follow the stream to the caller's array and are there after the call's last wait.
-int search_window_run(bzh_ctx *ctx, const SearchJob &job, BzfWalk &walk, const uint8_t *d, BzfWindow w, uint64_t bytes)
+static int search_window_run(bzh_ctx *ctx, SearchSink &s, const uint8_t *d, BzfWindow w, uint64_t bytes)
 {
     hipStream_t st = ctx->stream;
     bzh_search_stats &ss = ctx->sstats;
-    const uint64_t tiles64 = (w.n + BZF_TILE - 1) / BZF_TILE;
-    if (tiles64 > 0x7FFFFFFFull) {
-        bzh_set_error(ctx, "search: a window of %llu bytes is beyond one launch", (unsigned long long)w.n);
-        return BZH_E_ARG;
-    }
-    const uint32_t tiles = (uint32_t)tiles64;
-    ss.windows++;
-    ss.tiles += tiles;
+    uint32_t tiles;
+    BZH_TRY(scan_tiles(ctx, "search", w.n, &ss.windows, &ss.tiles, &tiles));
     uint64_t totals[2] = {0, 0};
-    if (tiles && (w.s_hi > w.s_lo || job.records)) {
+    if (tiles && (w.s_hi > w.s_lo || s.records)) {
         uint32_t *thits = nullptr, *tdel = nullptr;
         uint64_t *hbase = nullptr, *dbase = nullptr, *d_tot = nullptr;
         BZH_TRY(reserve_cut(ctx, ctx->search_tab, "the search's tile tables", grow_mib, [&](Carver &c) {
             c.put(hbase, tiles), c.put(dbase, tiles), c.put(d_tot, 2), c.put(thits, tiles), c.put(tdel, tiles);
         }));
-        SfPat p;
-        memcpy(p.w, job.pat, sizeof p.w);
-        SfArgs a{d, w, job.plen, job.delim, job.records ? 1u : 0u, bzf_head_word(job.pat, job.plen), bzf_head_mask(job.plen), thits, tdel,
-                 hbase, dbase, nullptr};
-        search_tiles<false><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, p);
+        SfArgs a{d, w, s.records ? 1u : 0u, thits, tdel, hbase, dbase, nullptr};
+        search_tiles<false><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, s.pat);
         search_scan<<<dim3(1), BZF_THREADS, 0, st>>>(thits, tdel, tiles, hbase, dbase, d_tot);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(totals, d_tot, sizeof totals, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, bzh_stream_wait(st));
-        const uint64_t emit = walk.emit(totals[0]);
+        const uint64_t emit = s.walk.emit(totals[0]);
         if (emit) {
             BZH_TRY(ctx->search_out.reserve(ctx, (size_t)emit * sizeof(bzh_hit), "the search's hits", grow_mib));
             a.win.emit = emit;
             a.out = ctx->search_out.as<bzh_hit>();
-            search_tiles<true><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, p);
+            search_tiles<true><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, s.pat);
             HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipMemcpyAsync(job.hits + walk.rank, a.out, (size_t)emit * sizeof(bzh_hit), hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipMemcpyAsync(s.hits + s.walk.rank, a.out, (size_t)emit * sizeof(bzh_hit), hipMemcpyDeviceToHost, st));
         }
     }
-    walk.advance(bytes, totals[0], totals[1]);
-    ss.hits = walk.rank;
+    s.walk.advance(bytes, totals[0], totals[1]);
+    ss.hits = s.walk.rank;
     return BZH_OK;
 }
 
-// The staging buffer for a window of `bytes` decoded bytes: grown to it (whole blocks, at least one, so a block above the target
-// grows it), the carry put in front of BZF_FRONT.  *d_stage = its base; the decoders expand at *d_stage + BZF_FRONT.
-int search_sink_room(bzh_ctx *ctx, SearchSink &sink, uint64_t bytes, uint8_t **d_stage)
+int SearchSink::room(bzh_ctx *ctx, uint64_t bytes, uint8_t **d_stage)
 {
-    if (sink.grep) return grep_sink_room(ctx, *sink.grep, bytes, d_stage);
-    uint8_t *base = nullptr;
-    BZH_TRY(reserve_cut(ctx, ctx->search_ws, "the search's staging", grow_mib, [&](Carver &c) { c.put(base, (size_t)(BZF_FRONT + bytes + 16)); }));
-    ctx->sstats.staging_peak = std::max<uint64_t>(ctx->sstats.staging_peak, ctx->search_ws.cap);
-    const uint64_t carry = sink.walk.carry;
-    if (carry) // (kept apart between two windows: the staging buffer may have moved)
-        HIP_TRY(ctx, hipMemcpyAsync(base + BZF_FRONT - carry, ctx->search_carry, (size_t)carry, hipMemcpyDeviceToDevice, ctx->stream));
-    *d_stage = base;
-    return BZH_OK;
+    uint64_t at; // (front: a search's carry is shorter)
+    return scan_room(ctx, "the search's staging", walk.carry, bytes, &ctx->sstats.staging_peak, d_stage, &at);
 }
 
-// The window search_sink_room made room for has been expanded and verified: the two passes, then its tail is kept as the carry.
-int search_sink_window(bzh_ctx *ctx, SearchSink &sink, uint64_t bytes)
+// The two passes, and the window's tail is kept as the carry.
+int SearchSink::window(bzh_ctx *ctx, uint64_t bytes)
 {
-    if (sink.grep) return grep_sink_window(ctx, *sink.grep, bytes);
     const uint8_t *base = ctx->search_ws.p;
-    const BzfWindow w = sink.walk.window(bytes);
-    const uint64_t keep = sink.walk.carry_after(bytes);
+    const BzfWindow w = walk.window(bytes);
+    const uint64_t keep = walk.carry_after(bytes);
     if (keep) { // [n - keep, n): read before the passes' wait, written where no pass looks
-        BZH_TRY(ctx->search_carry.reserve(ctx, BZF_MAX_PATTERN, "the search's carry"));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->search_carry, base + w.n - keep, (size_t)keep, hipMemcpyDeviceToDevice, ctx->stream));
+        BZH_TRY(ctx->scan_carry.reserve(ctx, BZF_MAX_PATTERN, "the search's carry"));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->scan_carry, base + w.n - keep, (size_t)keep, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    return search_window_run(ctx, sink.job, sink.walk, base, w, bytes);
+    return search_window_run(ctx, *this, base, w, bytes);
 }
 
 // Decoded bytes that already lie in HBM: one window, no staging, no carry.
 int search_raw_run(bzh_ctx *ctx, SearchSink &sink, const uint8_t *d_raw, size_t n)
 {
-    sink.walk.begin(sink.job.plen, 0, sink.job.max, 0, n, 0, 0);
-    return search_window_run(ctx, sink.job, sink.walk, d_raw, sink.walk.window(n), n);
+    sink.walk.begin(sink.pat.plen, 0, sink.max, 0, n, 0, 0);
+    return search_window_run(ctx, sink, d_raw, sink.walk.window(n), n);
 }

@@ -1,8 +1,10 @@
 // grep_host.cpp -- the grep without a device, built with g++ -fsanitize=address,undefined.
-// (a) What one thread, one tile and the scan of grep_tiles / grep_scan do (banzai_amd/csrc/grep_core.h), run thread by thread and
-//     tile by tile in the kernel's layout -- the tile and its halo in a model of the LDS, every phase for thread 0 .. 255 where the
-//     kernel has a barrier, the counting pass, the scan, the gather -- against a naive split-and-find.  Every buffer has its exact
-//     size, so a read or a store outside it is a sanitizer report.
+// (a) What one thread, one tile and the scan of grep_tiles / grep_scan do, run thread by thread and tile by tile in the kernel's
+//     layout: the tile front that the kernel itself compiles (banzai_amd/csrc/search_core.h: bzf_stage, bzf_match16, over the model
+//     LDS of tile_host.h), then banzai_amd/csrc/grep_core.h -- every phase for thread 0 .. 255 where the kernel has a barrier, the
+//     counting pass, the scan, the gather -- against a naive split-and-find.  Every text is allocated as the kernel's contract
+//     states (16-byte aligned, up to the aligned word that holds its last byte) and every other buffer has its exact size, so a
+//     read or a store outside is a sanitizer report.
 // (b) The windows and the carry (banzai_amd/csrc/grep_plan.h), with (a) as the device: blocks of seeded sizes expanded window by
 //     window into a staging buffer that is allocated anew for every window, against the same naive split-and-find.
 //
@@ -19,6 +21,7 @@
 #include "../../banzai_amd/csrc/grep_core.h"
 #include "../../banzai_amd/csrc/grep_plan.h"
 #include "../../banzai_amd/csrc/search_plan.h"
+#include "tile_host.h"
 
 static uint64_t rng_state;
 static uint64_t rnd()
@@ -45,6 +48,7 @@ struct Pattern {
     uint8_t pat[BZF_MAX_PATTERN];
     uint32_t plen, delim, invert;
 };
+static uint8_t slack_of(const Pattern &p) { return p.delim == 0xEE ? 0xED : 0xEE; } // (the letters are 'a' .. 'd')
 static bool same(const BzgEntry &a, const BzgEntry &b) { return a.record == b.record && a.off == b.off && a.len == b.len && a.out_off == b.out_off; }
 
 // ---- the truth: split at the delimiter, find in every record ("a match belongs to the record of its first byte") ---------------
@@ -76,18 +80,7 @@ static Truth naive(const Bytes &text, const Pattern &p)
 }
 
 // ---- (a) the device ---------------------------------------------------------------------------------------------------------------
-// gf_load16: the aligned 4-byte words that begin in front of n; of the last one the bytes behind n hold anything (0xEE here)
-static void load16(const uint8_t *d, uint64_t n, uint64_t p0, uint32_t *w)
-{
-    for (int k = 0; k < 4; k++) {
-        w[k] = 0;
-        if (p0 + 4 * k >= n) continue;
-        for (int j = 0; j < 4; j++) w[k] |= (uint32_t)(p0 + 4 * k + j < n ? d[p0 + 4 * k + j] : 0xEE) << (8 * j);
-    }
-}
-
-struct Group { // one workgroup: its LDS and its threads' registers
-    std::vector<uint8_t> lds;
+struct Group : TileModel { // one workgroup: its LDS and its threads' registers
     BzgShared *sh;
     BzgThread th[BZF_THREADS];
     Group() : sh(new BzgShared) {}
@@ -98,31 +91,13 @@ struct Group { // one workgroup: its LDS and its threads' registers
 // the front of grep_tiles: the tile, the masks, the forward scan
 static void tile_front(const uint8_t *d, const BzgWindow &w, const Pattern &p, uint64_t t, Group &g)
 {
-    g.lds.assign(BZF_TILE + BZF_MAX_PATTERN, 0xAA); // (what a thread does not store is not known)
-    memset(g.sh, 0xAA, sizeof *g.sh);
-    const uint64_t t0 = t * BZF_TILE;
+    const BzfPattern bp = bzf_pattern(p.pat, p.plen, p.delim);
+    memset(g.sh, 0xAA, sizeof *g.sh); // (what a thread does not store is not known)
+    g.stage(d, w.n, t, bp);
     EVERY {
-        uint32_t v[4];
-        load16(d, w.n, t0 + tid * BZF_ITEMS, v);
-        memcpy(&g.lds[tid * BZF_ITEMS], v, 16);
-        if (tid * BZF_ITEMS < p.plen - 1) {
-            load16(d, w.n, t0 + BZF_TILE + tid * BZF_ITEMS, v);
-            memcpy(&g.lds[BZF_TILE + tid * BZF_ITEMS], v, 16);
-        }
-    }
-    const uint32_t head = bzf_head_word(p.pat, p.plen), mask = bzf_head_mask(p.plen);
-    EVERY {
-        uint32_t v[5];
-        memcpy(v, &g.lds[tid * BZF_ITEMS], 20);
-        BzgThread &th = g.th[tid];
-        bzg_masks(th, w, t0 + tid * BZF_ITEMS, v[0], v[1], v[2], v[3], v[4], p.delim, head, mask);
-        if (p.plen > 4) {
-            const uint32_t cand = th.hm;
-            th.hm = 0;
-            for (uint32_t k = 0; k < 16; k++)
-                if ((cand >> k & 1u) && bzf_verify(&g.lds[tid * BZF_ITEMS + k], p.pat, p.plen)) th.hm |= 1u << k;
-        }
-        bzg_local(th, p.invert);
+        const uint64_t p0 = t * BZF_TILE + tid * BZF_ITEMS;
+        bzg_masks(g.th[tid], w, p0, g.own[tid], p.delim, g.match(tid, bp, bzg_starts(w, p0)));
+        bzg_local(g.th[tid], p.invert);
     }
     EVERY bzg_count_p0(*g.sh, tid, g.th[tid]);
     for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_f(*g.sh, tid, k);
@@ -151,7 +126,7 @@ static void tile_gather(const uint8_t *d, const BzgWindow &w, const Pattern &p, 
           bzg_bytes(g.sh->s[0][BZF_THREADS - 1]), x.bytes);
     uint8_t *dst = out ? out + w.out_base + base.out : nullptr;
     const uint32_t shift = (uint32_t)((uintptr_t)dst & 3u);
-    EVERY bzg_gather_p3(*g.sh, tid, (uint32_t)t, g.th[tid], x, base, w, &g.lds[tid * BZF_ITEMS], sm[tid], sdm[tid], shift, dst != nullptr, ent);
+    EVERY bzg_gather_p3(*g.sh, tid, (uint32_t)t, g.th[tid], x, base, w, g.tile + tid * BZF_ITEMS, sm[tid], sdm[tid], shift, dst != nullptr, ent);
     if (dst) EVERY bzg_gather_p4(*g.sh, tid, dst, shift, x.bytes);
 }
 
@@ -178,7 +153,7 @@ struct Sink { // GrepSink
     uint64_t windows;
 };
 
-// grep_window_run: d holds exactly w.n bytes.  Returns where the tail starts.
+// grep_window_run: d is a Text of w.n bytes.  Returns where the tail starts.
 static uint64_t window_run(Sink &s, const uint8_t *d, const BzgWindow &w, uint64_t bytes)
 {
     const uint64_t tiles = (w.n + BZF_TILE - 1) / BZF_TILE;
@@ -207,7 +182,8 @@ static void finish(Sink &s, Bytes &carry)
 {
     if (s.walk.held) {
         CHECK(carry.size() == s.walk.carry, "the carry");
-        const uint64_t ts = window_run(s, carry.data(), s.walk.window(s.walk.carry, 0, true), 0);
+        const Text held(carry.data(), carry.size(), slack_of(s.p));
+        const uint64_t ts = window_run(s, held.p, s.walk.window(s.walk.carry, 0, true), 0);
         carry.erase(carry.begin(), carry.begin() + ts);
     }
     CHECK(carry.size() == s.walk.carry && s.walk.held == 0, "the tail");
@@ -235,23 +211,22 @@ static void run_call(const Bytes &text, const Pattern &p, const std::vector<uint
     s.walk.begin(p.plen, p.invert != 0, out_kind != 0, cap, ent_kind != 0, max);
     Bytes carry;
     if (blocks.empty()) {
-        Bytes d(text); // (exactly n bytes)
-        d.shrink_to_fit();
-        const uint64_t ts = window_run(s, d.data(), s.walk.window(0, text.size(), true), text.size());
-        carry.assign(d.begin() + ts, d.end());
+        const Text d(text.data(), text.size(), slack_of(p));
+        const uint64_t ts = window_run(s, d.p, s.walk.window(0, text.size(), true), text.size());
+        carry.assign(d.p + ts, d.p + text.size());
     } else {
         uint64_t at = 0;
         for (uint64_t bytes : blocks) {
-            // grep_sink_room: a staging buffer of its own for every window, the carry in front of the new bytes
+            // GrepSink::room: a staging buffer of its own for every window, the carry in front of the new bytes
             const uint64_t extra = bzg_front_extra(s.walk.carry, BZF_FRONT), front = extra + BZF_FRONT;
-            Bytes stage(front + bytes, 0xCC);
-            stage.shrink_to_fit();
+            const Text stage(front + bytes, slack_of(p));
+            memset(stage.p, 0xCC, front);
             CHECK(carry.size() == s.walk.carry && front >= carry.size(), "the carry fits in front");
-            if (!carry.empty()) memcpy(&stage[front - carry.size()], carry.data(), carry.size());
-            if (bytes) memcpy(&stage[front], &text[at], bytes);
+            if (!carry.empty()) memcpy(stage.p + front - carry.size(), carry.data(), carry.size());
+            if (bytes) memcpy(stage.p + front, &text[at], bytes);
             at += bytes;
-            const uint64_t ts = window_run(s, stage.data(), s.walk.window(front, bytes, false), bytes);
-            carry.assign(stage.begin() + ts, stage.end());
+            const uint64_t ts = window_run(s, stage.p, s.walk.window(front, bytes, false), bytes);
+            carry.assign(stage.p + ts, stage.p + front + bytes);
         }
         CHECK(at == text.size(), "the blocks are the text");
     }

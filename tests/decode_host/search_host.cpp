@@ -1,8 +1,9 @@
 // search_host.cpp -- the search without a device, built with g++ -fsanitize=address,undefined.
-// (a) What one thread of search_tiles does (banzai_amd/csrc/search_core.h: the delimiter bits, the filter, the verify, the count
-//     of delimiters in front of a position), run thread by thread and tile by tile in the kernel's layout -- the tile and its halo
-//     in a model of the LDS, the counting pass, the scan of the tiles, the emitting pass -- against a naive scan.  Every buffer has
-//     its exact size, so a read or a store outside it is a sanitizer report.
+// (a) What one thread of search_tiles does, run thread by thread and tile by tile in the kernel's layout: the tile front that the
+//     kernel itself compiles (banzai_amd/csrc/search_core.h: bzf_stage, bzf_match16, over the model LDS of tile_host.h), the
+//     delimiter bits and the count of delimiters in front of a position, the counting pass, the scan of the tiles, the emitting
+//     pass -- against a naive scan.  Every text is allocated as the kernel's contract states (16-byte aligned, up to the aligned
+//     word that holds its last byte) and every other buffer has its exact size, so a read or a store outside is a sanitizer report.
 // (b) The windows and the carry (banzai_amd/csrc/search_plan.h), with (a) as the device: blocks of seeded sizes expanded window by
 //     window into a staging buffer that is allocated anew for every window, against brute force per output byte.
 //
@@ -16,8 +17,8 @@
 #include <vector>
 
 #include "../../include/bzhip.h"
-#include "../../banzai_amd/csrc/search_core.h"
 #include "../../banzai_amd/csrc/search_plan.h"
+#include "tile_host.h"
 
 static uint64_t rng_state;
 static uint64_t rnd()
@@ -45,47 +46,20 @@ struct Pattern {
     bool records;
 };
 
-// sf_load16: the aligned 4-byte words that begin in front of n; of the last one the bytes behind n hold anything (0xEE here)
-static void load16(const uint8_t *d, uint64_t n, uint64_t p0, uint32_t *w)
-{
-    for (int k = 0; k < 4; k++) {
-        w[k] = 0;
-        if (p0 + 4 * k >= n) continue;
-        for (int j = 0; j < 4; j++) w[k] |= (uint32_t)(p0 + 4 * k + j < n ? d[p0 + 4 * k + j] : 0xEE) << (8 * j);
-    }
-}
-
-struct Tile { // one workgroup's LDS and what its threads found
-    std::vector<uint8_t> lds;
+struct Tile : TileModel { // one workgroup's LDS and what its threads found
     uint32_t hm[BZF_THREADS], dm[BZF_THREADS];
 };
 
+// the front of search_tiles, and the two masks of every thread
 static void tile_tests(const uint8_t *d, const BzfWindow &w, const Pattern &p, uint64_t t, Tile &tl)
 {
-    tl.lds.assign(BZF_TILE + BZF_MAX_PATTERN, 0xAA); // (what a thread does not store is not known)
-    const uint64_t t0 = t * BZF_TILE;
+    const BzfPattern bp = bzf_pattern(p.pat, p.plen, p.delim);
+    tl.stage(d, w.n, t, bp);
     for (uint32_t tid = 0; tid < BZF_THREADS; tid++) {
-        uint32_t v[4];
-        load16(d, w.n, t0 + tid * BZF_ITEMS, v);
-        memcpy(&tl.lds[tid * BZF_ITEMS], v, 16);
-        if (tid * BZF_ITEMS < p.plen - 1) {
-            load16(d, w.n, t0 + BZF_TILE + tid * BZF_ITEMS, v);
-            memcpy(&tl.lds[BZF_TILE + tid * BZF_ITEMS], v, 16);
-        }
-    }
-    const uint32_t head = bzf_head_word(p.pat, p.plen), mask = bzf_head_mask(p.plen);
-    for (uint32_t tid = 0; tid < BZF_THREADS; tid++) {
-        const uint64_t p0 = t0 + tid * BZF_ITEMS;
-        uint32_t v[5];
-        memcpy(v, &tl.lds[tid * BZF_ITEMS], 20);
-        tl.dm[tid] = p.records ? bzf_eq_mask16(v[0], v[1], v[2], v[3], p.delim) & bzf_range_mask16(p0, w.d_lo, w.n) : 0u;
-        uint32_t cand = bzf_filter16(v[0], v[1], v[2], v[3], v[4], bzf_range_mask16(p0, w.s_lo, w.s_hi), head, mask), hm = cand;
-        if (p.plen > 4) {
-            hm = 0;
-            for (uint32_t k = 0; k < 16; k++)
-                if ((cand >> k & 1u) && bzf_verify(&tl.lds[tid * BZF_ITEMS + k], p.pat, p.plen)) hm |= 1u << k;
-        }
-        tl.hm[tid] = hm;
+        const uint64_t p0 = t * BZF_TILE + tid * BZF_ITEMS;
+        const BzfVec &v = tl.own[tid];
+        tl.hm[tid] = tl.match(tid, bp, bzf_range_mask16(p0, w.s_lo, w.s_hi));
+        tl.dm[tid] = p.records ? bzf_eq_mask16(v.x, v.y, v.z, v.w, p.delim) & bzf_range_mask16(p0, w.d_lo, w.n) : 0u;
     }
 }
 
@@ -127,7 +101,7 @@ static void window_run(const uint8_t *d, BzfWindow w, const Pattern &p, const Bz
                         } else {
                             const uint32_t gap = (uint32_t)std::min<uint64_t>(w.d_lo - pos, BZF_MAX_PATTERN - 1);
                             uint32_t c = 0;
-                            for (uint32_t j = 0; j < gap; j++) c += tl.lds.at(tid * BZF_ITEMS + k + j) == p.delim;
+                            for (uint32_t j = 0; j < gap; j++) c += tl.tile[tid * BZF_ITEMS + k + j] == p.delim;
                             rec = w.rec_base - c;
                         }
                     }
@@ -168,8 +142,8 @@ static void same(const std::vector<bzh_hit> &got, const std::vector<bzh_hit> &wa
 // ---- (a) raw bytes: one window, no staging --------------------------------------------------------------------------------
 static uint64_t raw_case(const uint8_t *src, uint64_t n, const Pattern &p, uint64_t max)
 {
-    uint8_t *d = (uint8_t *)malloc(n ? n : 1); // exactly n bytes (malloc aligns to 16)
-    if (n) memcpy(d, src, n);
+    const Text text(src, n);
+    const uint8_t *d = text.p;
     BzfWalk walk;
     walk.begin(p.plen, 0, max, 0, n, 0, 0);
     std::vector<bzh_hit> out;
@@ -179,7 +153,6 @@ static uint64_t raw_case(const uint8_t *src, uint64_t n, const Pattern &p, uint6
     same(out, want, hits, max, "raw", n, p.plen);
     CHECK(!p.records || delims == (uint64_t)std::count(d, d + n, (uint8_t)p.delim), "raw (%llu): %llu delimiters", (unsigned long long)n,
           (unsigned long long)delims);
-    free(d);
     return hits;
 }
 
@@ -274,12 +247,13 @@ static void part_b(uint64_t cases)
             uint64_t bytes = 0;
             const size_t B = bzf_window_blocks(idx.data(), at, last, room, bmax, &bytes);
             CHECK(B >= 1 && B <= bmax && (B == 1 || bytes <= room), "a window of %zu blocks, %llu bytes", B, (unsigned long long)bytes);
-            // search_sink_room: a staging buffer of exactly these bytes, the carry in front of the window
-            uint8_t *stage = (uint8_t *)malloc((size_t)(BZF_FRONT + bytes));
+            // SearchSink::room: a staging buffer of exactly these bytes, the carry in front of the window
+            const Text staging(BZF_FRONT + bytes);
+            uint8_t *stage = staging.p;
             memset(stage, 0xCC, BZF_FRONT);
             if (walk.carry) memcpy(stage + BZF_FRONT - walk.carry, carry, (size_t)walk.carry);
             memcpy(stage + BZF_FRONT, &truth[at_out], (size_t)bytes);
-            // search_sink_window
+            // SearchSink::window
             const BzfWindow w = walk.window(bytes);
             CHECK(w.n == BZF_FRONT + bytes && w.s_lo <= w.s_hi && w.s_lo >= BZF_FRONT - walk.carry && (w.s_hi == w.s_lo || w.s_hi + plen - 1 <= w.n),
                   "window");
@@ -294,7 +268,6 @@ static void part_b(uint64_t cases)
             walk.advance(bytes, hits, delims);
             memcpy(carry, next, (size_t)keep);
             CHECK(walk.carry == keep, "carry kept");
-            free(stage);
             at_out += bytes, at += B, windows++, carried += keep != 0;
         }
         same(got, want, walk.rank, max, "windows", c, plen);

@@ -323,6 +323,44 @@ def test_grep_index(dec, inp, native, sync):
         dec.search_set_room(0)
 
 
+# ---- one context, every kind of call ---------------------------------------------------------------------------------------------
+def test_one_carry_buffer_across_call_kinds(dec, inp, native):
+    """A context keeps ONE buffer for what is carried from a window to the next: a search puts its last plen - 1 bytes there, a grep
+    its whole open record.  Searches, greps and range searches alternate on one context, every block a window of the indexed walks
+    (a room of 1,024) and every batch of two candidates one of the full calls, so the buffer is reused at 2, 11, 16 and more than
+    50,000 bytes: the grep for CARRIED carries the long record, far above BZF_FRONT, and the search behind it finds its own short
+    carry in the grown buffer.  Every result is what a context that has done nothing else returns."""
+    word = inp.truth[5000:5003]
+    lo, hi = inp.bounds[0] - 5000, inp.bounds[2] + 5000
+    calls = [
+        ("search", lambda c: c.search(inp.s, NEEDLE, b"\n")),
+        ("grep", lambda c: c.grep(inp.s, word)),
+        ("search range", lambda c: c.search_range(inp.s, inp.ent, NEEDLE, lo, hi - lo, inp.pts)),
+        ("grep, the hit in the carry", lambda c: c.grep_index(inp.s, inp.ent, CARRIED, inp.pts)),
+        ("search behind it", lambda c: c.search(inp.s, CARRIED)),
+        ("grep, inverted", lambda c: c.grep_index(inp.s, inp.ent, word, inp.pts, b"\n", True)),
+        ("search range, short pattern", lambda c: c.search_range(inp.s, inp.ent, word, lo, hi - lo)),
+        ("full grep, the hit in the carry", lambda c: c.grep(inp.s, CARRIED)),
+        ("search, short pattern", lambda c: c.search(inp.s, word)),
+    ]
+    plain = lambda r: tuple(x.tobytes() if isinstance(x, np.ndarray) else x for x in r)
+    dec.search_set_room(1024)
+    try:
+        for name, call in calls:
+            got = plain(call(dec))
+            if "carry" in name:
+                assert dec.grep_stats()["carry_peak"] > 50_000 and dec.grep_stats()["windows"] >= 3, name
+            elif "search" in name:
+                assert dec.search_stats()["windows"] >= 3, name
+            with native.Context(0, 9, 2) as fresh:
+                fresh.search_set_room(1024)
+                assert got == plain(call(fresh)), name
+    finally:
+        dec.search_set_room(0)
+    hits, nhits = dec.search(inp.s, CARRIED)
+    assert nhits == 1 and int(hits[0]["off"]) == inp.long[0] + 100
+
+
 # ---- Python and the command line -------------------------------------------------------------------------------------------------
 def test_python_grep(inp):
     import banzai_amd
