@@ -45,7 +45,7 @@ import numpy as np
 
 from . import _native
 
-__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex", "RecordIndex", "build_record_index", "record_index_of", "decompress_records", "search", "search_range", "grep", "grep_count",
+__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex", "RecordIndex", "build_record_index", "record_index_of", "decompress_records", "search", "search_range", "grep", "grep_count", "PatternSet",
            "IndexedReader", "build_sync_index", "SyncIndex", "encode_indexed", "encode_indexed_stream", "recover", "recover_stream", "Recovered", "RecoveredBlock", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
@@ -988,7 +988,24 @@ def decompress_records(data, rindex, ranges, device=0):
     return _read_records(_record_index_arg(rindex), ranges, lambda lo, hi: view[lo:hi], device)
 
 
+class PatternSet(_native.PatternSet):
+    """A set of byte strings (1..65536 of 1..256 bytes each) compiled for one pass: grep -F -f FILE, -e A -e B, and with
+    `ignore_case` -i over ASCII letters (nothing else folds).  search, search_range, grep, grep_count, IndexedReader.search and
+    IndexedReader.grep take it wherever they take `pattern`; the hits of a search then carry two more fields, `pattern` (the
+    pattern's index in `patterns`; of patterns that are equal after folding, the lowest) and `len`, and ascend by `off`, then
+    `len`.  The set lies on `device`; `.info` says what the compile made of it.  close() frees it (so does the collector)."""
+
+    def __init__(self, patterns, ignore_case=False, device=0):
+        pats = [_pattern_arg(p) for p in patterns]
+        if not 1 <= len(pats) <= _native.PATSET_MAX_PATTERNS:
+            raise ValueError(f"a pattern set holds 1..{_native.PATSET_MAX_PATTERNS} patterns, not {len(pats)}")
+        self.device = device
+        super().__init__(_ctx(9, device), pats, bool(ignore_case))
+
+
 def _pattern_arg(pattern):
+    if isinstance(pattern, _native.PatternSet):
+        return pattern
     if not isinstance(pattern, (bytes, bytearray, memoryview)):
         raise TypeError(f"pattern must be bytes-like, not {type(pattern).__name__}")
     pattern = bytes(pattern)
@@ -1006,7 +1023,8 @@ def search(data, pattern, delim=None, limit=None, device=0):
     overlapping ones included -> (hits, nhits): hits is a structured array with fields `off` (the offset in the decoded output)
     and `record`, ascending; nhits the exact count.  With `delim` (one byte) `record` is the number of delimiters in front of the
     hit -- the record number read_records takes --, else 0.  `limit` caps the hits returned, not the count.  The decoded bytes
-    stay on the device, and everything decompress verifies is verified (bzh_search)."""
+    stay on the device, and everything decompress verifies is verified (bzh_search).  `pattern` may be a PatternSet: every
+    (offset, pattern) pair in one pass, with the fields `pattern` and `len` beside the two, by offset, then length."""
     view = _bytes_view(data, "search")
     d = None if delim is None else _delim_arg(delim)
     return _ctx(9, device).search(view, _pattern_arg(pattern), d, _limit_arg(limit))
@@ -1050,7 +1068,8 @@ def grep(data, pattern, delim=b"\n", invert=False, index=None, device=0):
     (in the decoded output) and `out_off` (in the bytes returned).  The records are selected and compacted on the device: only
     they cross to the host, and every block is decoded once.  Everything decompress verifies is verified (bzh_grep).  With
     `index` (a BlockIndex or SyncIndex of `data`) the blocks go through the indexed front, in parallel segments where the index
-    has sync points, and are checked against their entries (bzh_grep_index)."""
+    has sync points, and are checked against their entries (bzh_grep_index).  `pattern` may be a PatternSet: the records in
+    which a match of any of its patterns starts, in one pass (grep -F -f FILE, -e A -e B, -i)."""
     return _grep(data, pattern, delim, invert, index, device, False)
 
 

@@ -170,6 +170,20 @@ grepp = ctypes.POINTER(GrepEntry)
 GREP_INVERT = 1
 
 
+class PatsetInfo(ctypes.Structure):
+    _fields_ = [("patterns", ctypes.c_uint64), ("distinct", ctypes.c_uint64), ("min_len", ctypes.c_uint32), ("max_len", ctypes.c_uint32),
+                ("states", ctypes.c_uint32), ("classes", ctypes.c_uint32), ("table_bytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+SET_HIT_DTYPE = np.dtype([("off", "<u8"), ("record", "<u8"), ("pattern", "<u4"), ("len", "<u4")])  # bzh_set_hit
+assert SET_HIT_DTYPE.itemsize == 24
+PATSET_FOLD_ASCII = 1
+PATSET_MAX_PATTERNS = 65536
+
+
 class GrepStats(ctypes.Structure):
     """bzh_grep_stats"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("records", "selected", "out_bytes", "windows", "tiles", "carry_peak", "staging_peak")]
@@ -297,6 +311,10 @@ SIGNATURES = {
                                       ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint8, u8p, ctypes.c_size_t, grepp, ctypes.c_size_t,
                                       ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint64)]),
     "bzh_get_grep_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(GrepStats)]),
+    "bzh_patset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.c_size_t, ctypes.c_uint,
+                                         ctypes.POINTER(ctypes.c_void_p)]),
+    "bzh_patset_destroy": (None, [ctypes.c_void_p]),
+    "bzh_patset_get_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PatsetInfo)]),
     "bzh_search_set_room": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),
     "bzh_get_search_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SearchStats)]),
     "bzh_decode_scan": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u64p, u8p, ctypes.c_size_t, szp]),
@@ -516,6 +534,19 @@ def record_spans(entries, rec_cum, ranges):
     return touched[:cnt.value].copy(), int(lo.value), int(hi.value)
 
 
+def _patset_twin(name):
+    """bzh_search* -> bzh_search_patset*, bzh_grep* -> bzh_grep_patset*"""
+    return name.replace("bzh_search", "bzh_search_patset", 1).replace("bzh_grep", "bzh_grep_patset", 1)
+
+
+# the calls that take a set: their twin's arguments with (pat, plen) replaced by the set, and the hits by bzh_set_hit
+for _name in ("bzh_search_raw_device", "bzh_search_device", "bzh_search", "bzh_search_range_device", "bzh_search_range",
+              "bzh_grep_raw_device", "bzh_grep_device", "bzh_grep", "bzh_grep_index_device", "bzh_grep_index"):
+    _res, _args = SIGNATURES[_name]
+    _at = next(k for k in range(len(_args) - 1) if _args[k] is u8p and _args[k + 1] is ctypes.c_size_t and _args[k + 2] is ctypes.c_uint)
+    SIGNATURES[_patset_twin(_name)] = (_res, [ctypes.c_void_p if a is hitp else a for a in _args[:_at] + [ctypes.c_void_p] + _args[_at + 2:]])
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -537,6 +568,44 @@ def lib():
 
 def ptr(a, t=u8p):
     return a.ctypes.data_as(t)
+
+
+class PatternSet:
+    """A compiled set of patterns on the device of `ctx` (bzh_patset_create / bzh_patset_destroy): what the search and grep
+    calls of a Context take in place of one pattern.  It outlives the context it was made with."""
+
+    def __init__(self, ctx, patterns, ignore_case=False, flags=None):
+        self._h = None
+        self._destroy = lib().bzh_patset_destroy  # kept so that close() still works during interpreter shutdown
+        pats = [bytes(p) for p in patterns]
+        arr = (ctypes.c_char_p * max(len(pats), 1))(*pats)
+        lens = np.array([len(p) for p in pats] or [0], dtype=np.uintp)
+        h = ctypes.c_void_p()
+        fl = (PATSET_FOLD_ASCII if ignore_case else 0) if flags is None else flags
+        ctx.check(lib().bzh_patset_create(ctx.handle, arr, ptr(lens, szp), len(pats), fl, ctypes.byref(h)))
+        self._h = h
+        i = PatsetInfo()
+        ctx.check(lib().bzh_patset_get_info(h, ctypes.byref(i)))
+        self.info = i.as_dict()
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise ValueError("the pattern set is closed")
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 class Context:
@@ -1146,16 +1215,16 @@ class Context:
     # ---- search: every call returns (hits as a HIT_DTYPE array, nhits); `limit` is the C call's max ---------------------------
     SEARCH_GUESS = 1 << 16  # hit slots of the first try without a limit; more hits: once more, with the exact room
 
-    def _search(self, call, limit):
+    def _search(self, call, limit, dtype=None):
         """call(hits pointer, max, nhits reference) -> status.  limit None: every hit (a second call when the first try's room
         was too small); else at most `limit` hits and the exact count -- BZH_E_CAP is then the answer, not an error"""
         if limit is not None and limit < 0:
             raise ValueError("search: a negative limit")
         room = self.SEARCH_GUESS if limit is None else int(limit)
         for _ in range(2):
-            hits = np.zeros(max(room, 1), dtype=HIT_DTYPE)
+            hits = np.zeros(max(room, 1), dtype=dtype or HIT_DTYPE)  # (dtype: SET_HIT_DTYPE, of a search for a set)
             got = ctypes.c_size_t(0)
-            st = call(hits.ctypes.data_as(hitp) if room else None, room, ctypes.byref(got))
+            st = call(hits.ctypes.data_as(ctypes.c_void_p if dtype else hitp) if room else None, room, ctypes.byref(got))
             self.search_status = st  # (of the last C call: BZH_E_CAP where the limit cut the hits)
             if st == -4 and limit is None and got.value > room:
                 room = int(got.value)
@@ -1171,6 +1240,15 @@ class Context:
         return np.frombuffer(b, dtype=np.uint8) if b else np.zeros(1, np.uint8), len(b)
 
     @staticmethod
+    def _what(name, pattern):
+        """What a search or a grep looks for -> (the C call, the arguments that name it, the hits' dtype): the call `name` with
+        (pat, plen) for a byte string, its patset twin with the set for a PatternSet"""
+        if isinstance(pattern, PatternSet):
+            return getattr(lib(), _patset_twin(name)), (pattern.handle,), SET_HIT_DTYPE
+        pat, plen = Context._pattern(pattern)
+        return getattr(lib(), name), (ptr(pat), plen), None
+
+    @staticmethod
     def _delim(delim):
         """(flags, delimiter byte) of a delimiter given as None, an int or one byte"""
         if delim is None:
@@ -1182,18 +1260,18 @@ class Context:
 
     def search_raw_device(self, d_raw, n, pattern, delim=None, limit=None, flags=None):
         """bzh_search_raw_device on the integer device address d_raw -> (hits, nhits)"""
-        pat, plen = self._pattern(pattern)
+        fn, what, dt = self._what("bzh_search_raw_device", pattern)
         fl, d = self._delim(delim)
         fl = fl if flags is None else flags
-        return self._search(lambda h, m, g: lib().bzh_search_raw_device(self._h, ctypes.c_void_p(d_raw), n, ptr(pat), plen, fl, d, h, m, g), limit)
+        return self._search(lambda h, m, g: fn(self._h, ctypes.c_void_p(d_raw), n, *what, fl, d, h, m, g), limit, dt)
 
     def search_device(self, d_in, n, pattern, delim=None, limit=None, with_total=False):
         """bzh_search_device on the integer device address of the compressed bytes -> (hits, nhits[, out_total, consumed])"""
-        pat, plen = self._pattern(pattern)
+        fn, what, dt = self._what("bzh_search_device", pattern)
         fl, d = self._delim(delim)
         total, used = ctypes.c_uint64(0), ctypes.c_size_t(0)
-        r = self._search(lambda h, m, g: lib().bzh_search_device(self._h, ctypes.c_void_p(d_in), n, ptr(pat), plen, fl, d, h, m, g,
-                                                                 ctypes.byref(total), ctypes.byref(used)), limit)
+        r = self._search(lambda h, m, g: fn(self._h, ctypes.c_void_p(d_in), n, *what, fl, d, h, m, g, ctypes.byref(total), ctypes.byref(used)),
+                         limit, dt)
         return r + (int(total.value), int(used.value)) if with_total else r
 
     def search(self, data, pattern, delim=None, limit=None, with_total=False):
@@ -1201,11 +1279,10 @@ class Context:
         a = np.frombuffer(data, dtype=np.uint8)
         n = a.size
         src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
-        pat, plen = self._pattern(pattern)
+        fn, what, dt = self._what("bzh_search", pattern)
         fl, d = self._delim(delim)
         total, used = ctypes.c_uint64(0), ctypes.c_size_t(0)
-        r = self._search(lambda h, m, g: lib().bzh_search(self._h, ptr(src), n, ptr(pat), plen, fl, d, h, m, g, ctypes.byref(total),
-                                                          ctypes.byref(used)), limit)
+        r = self._search(lambda h, m, g: fn(self._h, ptr(src), n, *what, fl, d, h, m, g, ctypes.byref(total), ctypes.byref(used)), limit, dt)
         return r + (int(total.value), int(used.value)) if with_total else r
 
     def search_range(self, comp, entries, pattern, off=0, length=None, points=None, rec_cum=None, delim=None, limit=None, in_byte_base=0,
@@ -1214,18 +1291,19 @@ class Context:
         inside output [off, off + length) of the indexed input -> (hits, nhits).  Record numbers with rec_cum and delim."""
         e, p = _entries(entries)
         q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
-        pat, plen = self._pattern(pattern)
         fl, d = self._delim(delim)
         tp = _table(e, rec_cum)[1] if rec_cum is not None else None
         length = 2**64 - 1 if length is None else length
         if d_in is not None:
-            return self._search(lambda h, m, g: lib().bzh_search_range_device(self._h, ctypes.c_void_p(d_in), comp, in_byte_base, p, e.size, pp,
-                                                                              q.size, tp, off, length, ptr(pat), plen, fl, d, h, m, g), limit)
+            fn, what, dt = self._what("bzh_search_range_device", pattern)
+            return self._search(lambda h, m, g: fn(self._h, ctypes.c_void_p(d_in), comp, in_byte_base, p, e.size, pp, q.size, tp, off, length,
+                                                   *what, fl, d, h, m, g), limit, dt)
+        fn, what, dt = self._what("bzh_search_range", pattern)
         a = np.frombuffer(comp, dtype=np.uint8)
         n = a.size
         src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
-        return self._search(lambda h, m, g: lib().bzh_search_range(self._h, ptr(src), n, in_byte_base, p, e.size, pp, q.size, tp, off, length,
-                                                                   ptr(pat), plen, fl, d, h, m, g), limit)
+        return self._search(lambda h, m, g: fn(self._h, ptr(src), n, in_byte_base, p, e.size, pp, q.size, tp, off, length, *what, fl, d, h, m, g),
+                            limit, dt)
 
     def search_set_room(self, nbytes=0):
         self.check(lib().bzh_search_set_room(self._h, nbytes))
@@ -1267,14 +1345,22 @@ class Context:
             raise ValueError("grep: the delimiter is one byte value")
         return pat, plen, GREP_INVERT if invert else 0, d
 
+    @staticmethod
+    def _grep_what(name, pattern, delim, invert):
+        """_grep_args for a byte string or a PatternSet -> (the C call, the arguments that name what is looked for, flags, delimiter)"""
+        fl, d = Context._delim(delim)
+        if not fl:
+            raise ValueError("grep: the delimiter is one byte value")
+        fn, what, _ = Context._what(name, pattern)
+        return fn, what, GREP_INVERT if invert else 0, d
+
     def grep(self, data, pattern, delim=b"\n", invert=False, count_only=False):
         """bzh_grep: the records of the decoded bytes of `data` that hold `pattern` -> (bytes, entries), or (nrecs, out_total)"""
         a = np.frombuffer(data, dtype=np.uint8)
         n = a.size
         src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
-        pat, plen, fl, d = self._grep_args(pattern, delim, invert)
-        return self._grep(lambda o, c, e, m, g, t: lib().bzh_grep(self._h, ptr(src), n, ptr(pat), plen, fl, d, o, c, e, m, g, t, None, None),
-                          count_only)
+        fn, what, fl, d = self._grep_what("bzh_grep", pattern, delim, invert)
+        return self._grep(lambda o, c, e, m, g, t: fn(self._h, ptr(src), n, *what, fl, d, o, c, e, m, g, t, None, None), count_only)
 
     def grep_index(self, comp, entries, pattern, points=None, delim=b"\n", invert=False, count_only=False):
         """bzh_grep_index over the whole indexed input `comp` -> as grep"""
@@ -1283,9 +1369,8 @@ class Context:
         a = np.frombuffer(comp, dtype=np.uint8)
         n = a.size
         src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
-        pat, plen, fl, d = self._grep_args(pattern, delim, invert)
-        return self._grep(lambda o, c, en, m, g, t: lib().bzh_grep_index(self._h, ptr(src), n, p, e.size, pp, q.size, ptr(pat), plen, fl, d, o, c,
-                                                                         en, m, g, t), count_only)
+        fn, what, fl, d = self._grep_what("bzh_grep_index", pattern, delim, invert)
+        return self._grep(lambda o, c, en, m, g, t: fn(self._h, ptr(src), n, p, e.size, pp, q.size, *what, fl, d, o, c, en, m, g, t), count_only)
 
     def _grep_device(self, call, room):
         """the device variants: the bytes stay in the caller's device buffer -> (status, nrecs, out_total, entries)"""
@@ -1296,25 +1381,24 @@ class Context:
 
     def grep_raw_device(self, d_raw, n, pattern, d_out, cap, room, delim=b"\n", invert=False, flags=None):
         """bzh_grep_raw_device on integer device addresses; `room` entries -> (status, nrecs, out_total, entries)"""
-        pat, plen, fl, d = self._grep_args(pattern, delim, invert)
+        fn, what, fl, d = self._grep_what("bzh_grep_raw_device", pattern, delim, invert)
         fl = fl if flags is None else flags
-        return self._grep_device(lambda e, m, g, t: lib().bzh_grep_raw_device(self._h, ctypes.c_void_p(d_raw), n, ptr(pat), plen, fl, d,
-                                                                              ctypes.c_void_p(d_out), cap, e, m, g, t), room)
+        return self._grep_device(lambda e, m, g, t: fn(self._h, ctypes.c_void_p(d_raw), n, *what, fl, d, ctypes.c_void_p(d_out), cap, e, m, g, t),
+                                 room)
 
     def grep_device(self, d_in, n, pattern, d_out, cap, room, delim=b"\n", invert=False):
         """bzh_grep_device on integer device addresses; `room` entries -> (status, nrecs, out_total, entries)"""
-        pat, plen, fl, d = self._grep_args(pattern, delim, invert)
-        return self._grep_device(lambda e, m, g, t: lib().bzh_grep_device(self._h, ctypes.c_void_p(d_in), n, ptr(pat), plen, fl, d,
-                                                                          ctypes.c_void_p(d_out), cap, e, m, g, t, None, None), room)
+        fn, what, fl, d = self._grep_what("bzh_grep_device", pattern, delim, invert)
+        return self._grep_device(lambda e, m, g, t: fn(self._h, ctypes.c_void_p(d_in), n, *what, fl, d, ctypes.c_void_p(d_out), cap, e, m, g, t,
+                                                       None, None), room)
 
     def grep_index_device(self, d_in, n, entries, pattern, d_out, cap, room, points=None, delim=b"\n", invert=False):
         """bzh_grep_index_device on integer device addresses; `room` entries -> (status, nrecs, out_total, entries)"""
         e, p = _entries(entries)
         q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
-        pat, plen, fl, d = self._grep_args(pattern, delim, invert)
-        return self._grep_device(lambda en, m, g, t: lib().bzh_grep_index_device(self._h, ctypes.c_void_p(d_in), n, p, e.size, pp, q.size,
-                                                                                 ptr(pat), plen, fl, d, ctypes.c_void_p(d_out), cap, en, m, g,
-                                                                                 t), room)
+        fn, what, fl, d = self._grep_what("bzh_grep_index_device", pattern, delim, invert)
+        return self._grep_device(lambda en, m, g, t: fn(self._h, ctypes.c_void_p(d_in), n, p, e.size, pp, q.size, *what, fl, d,
+                                                        ctypes.c_void_p(d_out), cap, en, m, g, t), room)
 
     def grep_stats(self):
         s = GrepStats()

@@ -1854,12 +1854,41 @@ static int scan_args(bzh_ctx *ctx, const char *who, size_t plen, unsigned flags,
     return BZH_OK;
 }
 
-// the checks every search makes first; a sink is made of arguments that have passed them
-static int search_begin(bzh_ctx *ctx, const uint8_t *pat, size_t plen, unsigned flags, bzh_hit *hits, size_t max, size_t *nhits)
+// What a search or a grep looks for: a byte string, or a compiled set (bzh_*_patset*).  Every entry point below is one body for
+// both; the public calls only say which.
+struct ScanWhat {
+    const uint8_t *pat;
+    size_t plen;
+    const bzh_patset *set;
+    bool is_set;
+    bool given() const { return is_set ? set != nullptr : pat != nullptr; }
+};
+static ScanWhat what_pat(const uint8_t *pat, size_t plen) { return ScanWhat{pat, plen, nullptr, false}; }
+static ScanWhat what_set(const bzh_patset *set) { return ScanWhat{nullptr, 0, set, true}; }
+static int scan_args(bzh_ctx *ctx, const char *who, const ScanWhat &q, unsigned flags, unsigned flag, const char *flag_name)
 {
-    if (!pat || !nhits || (!hits && max)) return BZH_E_ARG;
+    if (!q.is_set) return scan_args(ctx, who, q.plen, flags, flag, flag_name);
+    if (q.set->device != ctx->device) {
+        bzh_set_error(ctx, "%s: the pattern set lies on device %d, the context on device %d", who, q.set->device, ctx->device);
+        return BZH_E_ARG;
+    }
+    return scan_args(ctx, who, 1, flags, flag, flag_name);
+}
+static SearchSink search_sink(const ScanWhat &q, unsigned flags, uint8_t delim, void *hits, size_t max)
+{
+    return q.is_set ? SearchSink(q.set, flags, delim, (bzh_set_hit *)hits, max) : SearchSink(q.pat, q.plen, flags, delim, (bzh_hit *)hits, max);
+}
+static GrepSink grep_sink(const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap, bzh_grep_entry *ent, size_t max)
+{
+    return q.is_set ? GrepSink(q.set, flags, delim, d_out, cap, ent, max) : GrepSink(q.pat, q.plen, flags, delim, d_out, cap, ent, max);
+}
+
+// the checks every search makes first; a sink is made of arguments that have passed them
+static int search_begin(bzh_ctx *ctx, const ScanWhat &q, unsigned flags, void *hits, size_t max, size_t *nhits)
+{
+    if (!q.given() || !nhits || (!hits && max)) return BZH_E_ARG;
     *nhits = 0;
-    BZH_TRY(scan_args(ctx, "search", plen, flags, BZH_SEARCH_RECORDS, "BZH_SEARCH_RECORDS"));
+    BZH_TRY(scan_args(ctx, "search", q, flags, BZH_SEARCH_RECORDS, "BZH_SEARCH_RECORDS"));
     memset(&ctx->sstats, 0, sizeof ctx->sstats);
     return BZH_OK;
 }
@@ -1878,14 +1907,14 @@ static int search_end(bzh_ctx *ctx, const SearchSink &sink, int rc, size_t *nhit
     return BZH_OK;
 }
 
-extern "C" int bzh_search_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
-                                     bzh_hit *hits, size_t max, size_t *nhits)
+static int search_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, void *hits, size_t max,
+                             size_t *nhits)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_raw && n)) return BZH_E_ARG;
-    BZH_TRY(search_begin(ctx, pat, plen, flags, hits, max, nhits));
-    SearchSink sink(pat, plen, flags, delim, hits, max);
+    BZH_TRY(search_begin(ctx, q, flags, hits, max, nhits));
+    SearchSink sink = search_sink(q, flags, delim, hits, max);
     if ((uintptr_t)d_raw & 15u) {
         bzh_set_error(ctx, "search: the buffer is not 16-byte aligned");
         return BZH_E_ARG;
@@ -1898,14 +1927,14 @@ extern "C" int bzh_search_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, 
     });
 }
 
-extern "C" int bzh_search_device(bzh_ctx *ctx, const void *d_in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
-                                 bzh_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed)
+static int search_device(bzh_ctx *ctx, const void *d_in, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, void *hits, size_t max,
+                         size_t *nhits, uint64_t *out_total, size_t *consumed)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_in && n)) return BZH_E_ARG;
-    BZH_TRY(search_begin(ctx, pat, plen, flags, hits, max, nhits));
-    SearchSink sink(pat, plen, flags, delim, hits, max);
+    BZH_TRY(search_begin(ctx, q, flags, hits, max, nhits));
+    SearchSink sink = search_sink(q, flags, delim, hits, max);
     DecodeCall call;
     BZH_TRY(decode_call_begin(ctx, n, call));
     if (out_total) *out_total = 0;
@@ -1915,20 +1944,21 @@ extern "C" int bzh_search_device(bzh_ctx *ctx, const void *d_in, size_t n, const
     size_t total = 0;
     int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, nullptr, nullptr, nullptr, &sink);
     if (out_total) *out_total = total;
+    if (rc == BZH_OK) rc = search_finish(ctx, sink);
     rc = decode_call_end(ctx, call, rc);
     return search_end(ctx, sink, rc, nhits);
     });
 }
 
-extern "C" int bzh_search(bzh_ctx *ctx, const uint8_t *in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
-                          bzh_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed)
+static int search_host(bzh_ctx *ctx, const uint8_t *in, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, void *hits, size_t max,
+                       size_t *nhits, uint64_t *out_total, size_t *consumed)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!in && n)) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     BZH_TRY(decode_stage(ctx, in, n));
-    return bzh_search_device(ctx, ctx->d_stage_in, n, pat, plen, flags, delim, hits, max, nhits, out_total, consumed);
+    return search_device(ctx, ctx->d_stage_in, n, q, flags, delim, hits, max, nhits, out_total, consumed);
     });
 }
 
@@ -1955,16 +1985,15 @@ static int search_range_args(bzh_ctx *ctx, const bzh_index_entry *idx, size_t co
     return BZH_OK;
 }
 
-extern "C" int bzh_search_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
-                                       size_t count, const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off,
-                                       uint64_t len, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits,
-                                       size_t max, size_t *nhits)
+static int search_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                               const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len, const ScanWhat &q,
+                               unsigned flags, uint8_t delim, void *hits, size_t max, size_t *nhits)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_in && n) || (!idx && count) || (!pts && npts)) return BZH_E_ARG;
-    BZH_TRY(search_begin(ctx, pat, plen, flags, hits, max, nhits));
-    SearchSink sink(pat, plen, flags, delim, hits, max);
+    BZH_TRY(search_begin(ctx, q, flags, hits, max, nhits));
+    SearchSink sink = search_sink(q, flags, delim, hits, max);
     DecodeCall call;
     BZH_TRY(decode_call_begin(ctx, n, call));
     BZH_TRY(search_range_args(ctx, idx, count, pts, npts, rec_cum, flags));
@@ -1974,20 +2003,21 @@ extern "C" int bzh_search_range_device(bzh_ctx *ctx, const void *d_in, size_t n,
     BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(last - first, 1), ctx->max_batch)));
     int rc = decode_range_sink_run(ctx, (const uint8_t *)d_in, n, in_byte_base, idx, count, pts, npts, sink.records ? rec_cum : nullptr, off, len,
                                    sink);
+    if (rc == BZH_OK) rc = search_finish(ctx, sink);
     rc = decode_call_end(ctx, call, rc);
     return search_end(ctx, sink, rc, nhits);
     });
 }
 
-extern "C" int bzh_search_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
-                                const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len,
-                                const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits, size_t max, size_t *nhits)
+static int search_range_host(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                             const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len, const ScanWhat &q,
+                             unsigned flags, uint8_t delim, void *hits, size_t max, size_t *nhits)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!in && n) || (!idx && count) || (!pts && npts)) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BZH_TRY(search_begin(ctx, pat, plen, flags, hits, max, nhits)); // (the arguments are checked here too: nothing goes up for a call that is refused)
+    BZH_TRY(search_begin(ctx, q, flags, hits, max, nhits)); // (the arguments are checked here too: nothing goes up for a call that is refused)
     BZH_TRY(search_range_args(ctx, idx, count, pts, npts, rec_cum, flags));
     // only the span goes up
     size_t first = 0, last = 0;
@@ -1995,9 +2025,66 @@ extern "C" int bzh_search_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint6
     size_t un;
     BZH_TRY(bzh_index_span(idx, count, off, len, &first, &last, &lo, &hi));
     BZH_TRY(decode_stage_hull(ctx, in, n, in_byte_base, lo, hi, 0, &base, &un));
-    return bzh_search_range_device(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, rec_cum, off, len, pat, plen, flags, delim, hits, max,
-                                   nhits);
+    return search_range_device(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, rec_cum, off, len, q, flags, delim, hits, max, nhits);
     });
+}
+
+// the public calls: a byte string, or a set
+extern "C" int bzh_search_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                                     bzh_hit *hits, size_t max, size_t *nhits)
+{
+    return search_raw_device(ctx, d_raw, n, what_pat(pat, plen), flags, delim, hits, max, nhits);
+}
+extern "C" int bzh_search_patset_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                            bzh_set_hit *hits, size_t max, size_t *nhits)
+{
+    return search_raw_device(ctx, d_raw, n, what_set(set), flags, delim, hits, max, nhits);
+}
+extern "C" int bzh_search_device(bzh_ctx *ctx, const void *d_in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                                 bzh_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed)
+{
+    return search_device(ctx, d_in, n, what_pat(pat, plen), flags, delim, hits, max, nhits, out_total, consumed);
+}
+extern "C" int bzh_search_patset_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                        bzh_set_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed)
+{
+    return search_device(ctx, d_in, n, what_set(set), flags, delim, hits, max, nhits, out_total, consumed);
+}
+extern "C" int bzh_search(bzh_ctx *ctx, const uint8_t *in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                          bzh_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed)
+{
+    return search_host(ctx, in, n, what_pat(pat, plen), flags, delim, hits, max, nhits, out_total, consumed);
+}
+extern "C" int bzh_search_patset(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                 bzh_set_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed)
+{
+    return search_host(ctx, in, n, what_set(set), flags, delim, hits, max, nhits, out_total, consumed);
+}
+extern "C" int bzh_search_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                                       size_t count, const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off,
+                                       uint64_t len, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits,
+                                       size_t max, size_t *nhits)
+{
+    return search_range_device(ctx, d_in, n, in_byte_base, idx, count, pts, npts, rec_cum, off, len, what_pat(pat, plen), flags, delim, hits, max, nhits);
+}
+extern "C" int bzh_search_patset_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                                              size_t count, const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off,
+                                              uint64_t len, const bzh_patset *set, unsigned flags, uint8_t delim, bzh_set_hit *hits, size_t max,
+                                              size_t *nhits)
+{
+    return search_range_device(ctx, d_in, n, in_byte_base, idx, count, pts, npts, rec_cum, off, len, what_set(set), flags, delim, hits, max, nhits);
+}
+extern "C" int bzh_search_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                                const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len,
+                                const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits, size_t max, size_t *nhits)
+{
+    return search_range_host(ctx, in, n, in_byte_base, idx, count, pts, npts, rec_cum, off, len, what_pat(pat, plen), flags, delim, hits, max, nhits);
+}
+extern "C" int bzh_search_patset_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
+                                       const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len,
+                                       const bzh_patset *set, unsigned flags, uint8_t delim, bzh_set_hit *hits, size_t max, size_t *nhits)
+{
+    return search_range_host(ctx, in, n, in_byte_base, idx, count, pts, npts, rec_cum, off, len, what_set(set), flags, delim, hits, max, nhits);
 }
 
 extern "C" int bzh_search_set_room(bzh_ctx *ctx, size_t bytes)
@@ -2025,13 +2112,13 @@ extern "C" int bzh_get_search_stats(const bzh_ctx *ctx, bzh_search_stats *out)
 // ---- grep (grep.hip: the kernels, the passes over a window, the staging and the carry; the full grep rides on decode_chain_run,
 // the indexed one on decode_range_sink_run, as a WindowSink of its own; the windows: grep_plan.h)
 // the checks every grep makes first; a sink is made of arguments that have passed them
-static int grep_begin(bzh_ctx *ctx, const uint8_t *pat, size_t plen, unsigned flags, void *d_out, size_t cap, bzh_grep_entry *ent, size_t max,
+static int grep_begin(bzh_ctx *ctx, const ScanWhat &q, unsigned flags, void *d_out, size_t cap, bzh_grep_entry *ent, size_t max,
                       size_t *nrecs, uint64_t *out_total)
 {
-    if (!pat || !nrecs || !out_total || (!d_out && cap) || (!ent && max)) return BZH_E_ARG;
+    if (!q.given() || !nrecs || !out_total || (!d_out && cap) || (!ent && max)) return BZH_E_ARG;
     *nrecs = 0;
     *out_total = 0;
-    BZH_TRY(scan_args(ctx, "grep", plen, flags, BZH_GREP_INVERT, "BZH_GREP_INVERT"));
+    BZH_TRY(scan_args(ctx, "grep", q, flags, BZH_GREP_INVERT, "BZH_GREP_INVERT"));
     if ((uintptr_t)d_out & 3u) {
         bzh_set_error(ctx, "grep: the output buffer is not 4-byte aligned");
         return BZH_E_ARG;
@@ -2060,14 +2147,14 @@ static int grep_end(bzh_ctx *ctx, GrepSink &g, const DecodeCall &call, int rc, s
     return BZH_OK;
 }
 
-extern "C" int bzh_grep_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
-                                   void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
+static int grep_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap,
+                           bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_raw && n)) return BZH_E_ARG;
-    BZH_TRY(grep_begin(ctx, pat, plen, flags, d_out, cap, ent, max, nrecs, out_total));
-    GrepSink g(pat, plen, flags, delim, d_out, cap, ent, max);
+    BZH_TRY(grep_begin(ctx, q, flags, d_out, cap, ent, max, nrecs, out_total));
+    GrepSink g = grep_sink(q, flags, delim, d_out, cap, ent, max);
     if ((uintptr_t)d_raw & 15u) {
         bzh_set_error(ctx, "grep: the buffer is not 16-byte aligned");
         return BZH_E_ARG;
@@ -2079,15 +2166,14 @@ extern "C" int bzh_grep_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, co
     });
 }
 
-extern "C" int bzh_grep_device(bzh_ctx *ctx, const void *d_in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
-                               void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total,
-                               uint64_t *decoded_total, size_t *consumed)
+static int grep_device(bzh_ctx *ctx, const void *d_in, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap,
+                       bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total, uint64_t *decoded_total, size_t *consumed)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_in && n)) return BZH_E_ARG;
-    BZH_TRY(grep_begin(ctx, pat, plen, flags, d_out, cap, ent, max, nrecs, out_total));
-    GrepSink g(pat, plen, flags, delim, d_out, cap, ent, max);
+    BZH_TRY(grep_begin(ctx, q, flags, d_out, cap, ent, max, nrecs, out_total));
+    GrepSink g = grep_sink(q, flags, delim, d_out, cap, ent, max);
     DecodeCall call;
     BZH_TRY(decode_call_begin(ctx, n, call));
     if (decoded_total) *decoded_total = 0;
@@ -2104,30 +2190,29 @@ extern "C" int bzh_grep_device(bzh_ctx *ctx, const void *d_in, size_t n, const u
 // the host variants: room for the bytes in the staging buffer of the output (asked for with no room: a buffer all the same)
 static size_t grep_stage_room(const uint8_t *out, size_t cap) { return out ? std::max<size_t>(cap, 16) : 0; }
 
-extern "C" int bzh_grep(bzh_ctx *ctx, const uint8_t *in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
-                        uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total,
-                        uint64_t *decoded_total, size_t *consumed)
+static int grep_host(bzh_ctx *ctx, const uint8_t *in, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, uint8_t *out, size_t cap,
+                     bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total, uint64_t *decoded_total, size_t *consumed)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!in && n) || (!out && cap)) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     BZH_TRY(decode_stage(ctx, in, n, grep_stage_room(out, cap)));
-    BZH_TRY(bzh_grep_device(ctx, ctx->d_stage_in, n, pat, plen, flags, delim, out ? ctx->d_stage_out.p : nullptr, cap, ent, max, nrecs, out_total,
-                            decoded_total, consumed));
+    BZH_TRY(grep_device(ctx, ctx->d_stage_in, n, q, flags, delim, out ? ctx->d_stage_out.p : nullptr, cap, ent, max, nrecs, out_total,
+                        decoded_total, consumed));
     return decode_unstage(ctx, out, out ? (size_t)*out_total : 0);
     });
 }
 
-extern "C" int bzh_grep_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count,
-                                     const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
-                                     void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
+static int grep_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts,
+                             size_t npts, const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap, bzh_grep_entry *ent, size_t max,
+                             size_t *nrecs, uint64_t *out_total)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_in && n) || (!idx && count) || (!pts && npts)) return BZH_E_ARG;
-    BZH_TRY(grep_begin(ctx, pat, plen, flags, d_out, cap, ent, max, nrecs, out_total));
-    GrepSink g(pat, plen, flags, delim, d_out, cap, ent, max);
+    BZH_TRY(grep_begin(ctx, q, flags, d_out, cap, ent, max, nrecs, out_total));
+    GrepSink g = grep_sink(q, flags, delim, d_out, cap, ent, max);
     DecodeCall call;
     BZH_TRY(decode_call_begin(ctx, n, call));
     BZH_TRY(search_range_args(ctx, idx, count, pts, npts, nullptr, 0));
@@ -2137,19 +2222,79 @@ extern "C" int bzh_grep_index_device(bzh_ctx *ctx, const void *d_in, size_t n, c
     });
 }
 
-extern "C" int bzh_grep_index(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count,
-                              const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
-                              uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
+static int grep_index_host(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts,
+                           size_t npts, const ScanWhat &q, unsigned flags, uint8_t delim, uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max,
+                           size_t *nrecs, uint64_t *out_total)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!in && n) || (!idx && count) || (!pts && npts) || (!out && cap)) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     BZH_TRY(decode_stage(ctx, in, n, grep_stage_room(out, cap)));
-    BZH_TRY(bzh_grep_index_device(ctx, ctx->d_stage_in, n, idx, count, pts, npts, pat, plen, flags, delim, out ? ctx->d_stage_out.p : nullptr, cap,
-                                  ent, max, nrecs, out_total));
+    BZH_TRY(grep_index_device(ctx, ctx->d_stage_in, n, idx, count, pts, npts, q, flags, delim, out ? ctx->d_stage_out.p : nullptr, cap, ent, max,
+                              nrecs, out_total));
     return decode_unstage(ctx, out, out ? (size_t)*out_total : 0);
     });
+}
+
+// the public calls: a byte string, or a set
+extern "C" int bzh_grep_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                                   void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
+{
+    return grep_raw_device(ctx, d_raw, n, what_pat(pat, plen), flags, delim, d_out, cap, ent, max, nrecs, out_total);
+}
+extern "C" int bzh_grep_patset_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                          void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
+{
+    return grep_raw_device(ctx, d_raw, n, what_set(set), flags, delim, d_out, cap, ent, max, nrecs, out_total);
+}
+extern "C" int bzh_grep_device(bzh_ctx *ctx, const void *d_in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                               void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total,
+                               uint64_t *decoded_total, size_t *consumed)
+{
+    return grep_device(ctx, d_in, n, what_pat(pat, plen), flags, delim, d_out, cap, ent, max, nrecs, out_total, decoded_total, consumed);
+}
+extern "C" int bzh_grep_patset_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                      void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total,
+                                      uint64_t *decoded_total, size_t *consumed)
+{
+    return grep_device(ctx, d_in, n, what_set(set), flags, delim, d_out, cap, ent, max, nrecs, out_total, decoded_total, consumed);
+}
+extern "C" int bzh_grep(bzh_ctx *ctx, const uint8_t *in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                        uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total,
+                        uint64_t *decoded_total, size_t *consumed)
+{
+    return grep_host(ctx, in, n, what_pat(pat, plen), flags, delim, out, cap, ent, max, nrecs, out_total, decoded_total, consumed);
+}
+extern "C" int bzh_grep_patset(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim, uint8_t *out,
+                               size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total, uint64_t *decoded_total,
+                               size_t *consumed)
+{
+    return grep_host(ctx, in, n, what_set(set), flags, delim, out, cap, ent, max, nrecs, out_total, decoded_total, consumed);
+}
+extern "C" int bzh_grep_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count,
+                                     const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                                     void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
+{
+    return grep_index_device(ctx, d_in, n, idx, count, pts, npts, what_pat(pat, plen), flags, delim, d_out, cap, ent, max, nrecs, out_total);
+}
+extern "C" int bzh_grep_patset_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count,
+                                            const bzh_sync_point *pts, size_t npts, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                            void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
+{
+    return grep_index_device(ctx, d_in, n, idx, count, pts, npts, what_set(set), flags, delim, d_out, cap, ent, max, nrecs, out_total);
+}
+extern "C" int bzh_grep_index(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count,
+                              const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                              uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
+{
+    return grep_index_host(ctx, in, n, idx, count, pts, npts, what_pat(pat, plen), flags, delim, out, cap, ent, max, nrecs, out_total);
+}
+extern "C" int bzh_grep_patset_index(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count,
+                                     const bzh_sync_point *pts, size_t npts, const bzh_patset *set, unsigned flags, uint8_t delim, uint8_t *out,
+                                     size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
+{
+    return grep_index_host(ctx, in, n, idx, count, pts, npts, what_set(set), flags, delim, out, cap, ent, max, nrecs, out_total);
 }
 
 extern "C" int bzh_get_grep_stats(const bzh_ctx *ctx, bzh_grep_stats *out)

@@ -10,7 +10,7 @@
 // Search: --search prints the offset and the line number of every occurrence of a byte string in the decoded data, which never
 // leaves the device (bzh_search; with --index bzh_search_range over just the span's compressed bytes).
 // Grep: --grep writes the lines that hold a byte string, selected and compacted on the device (bzh_grep; with --index
-// bzh_grep_index).
+// bzh_grep_index).  Several strings (-e, --patterns) or --ignore-case: one compiled set, one pass (bzh_patset_create, bzh_*_patset*).
 #include <cstdio>
 #include <cstdlib>
 #include <cerrno>
@@ -67,6 +67,13 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "     --line-number          with --grep: prefix each line with its number, from 1, and ':'\n"
             "     --hex                  with --search or --grep: <string> is given as hex digits\n"
             "     --count                with --search: print the number of occurrences alone; with --grep: of lines\n"
+            "     -e <string>            with --search or --grep, in place of their <string> or beside it, any number of\n"
+            "                            times: look for every one of the strings in one pass ('--grep -e A -e B'; a\n"
+            "                            <string> that is itself '-e', '--patterns' or '--ignore-case' is given by -e)\n"
+            "     --patterns <file>      as -e for every line of <file> (not hex); an empty line is an error\n"
+            "     --ignore-case          with --search or --grep: 'A'..'Z' and 'a'..'z' compare equal, nothing else does\n"
+            "                            With any of these three --search prints a third column: the number of the\n"
+            "                            string, from 0 in the order given (of equal strings the first)\n"
             "     --keep      or   -k    keep the input file\n"
             "     --remove    or   -r    remove the input file\n\n"
             "     -1 to -9               block size in 100 kB units (default -9)\n"
@@ -115,8 +122,27 @@ const char *VERSION = "version alpha 0.3.1-hip";
 int main(int argc, char **argv)
 {
     if (argc <= 1) usage(false);
-    enum { ANY, NOARGS, OUTPATH, IDXPATH, MKIDXPATH, INTERVAL, RANGE, SEARCH, GREP } expect = ANY;
+    enum { ANY, NOARGS, OUTPATH, IDXPATH, MKIDXPATH, INTERVAL, RANGE, SEARCH, GREP, PATTERN, PATFILE } expect = ANY;
     std::string in_path, out_path, index_path, mkindex_path, needle;
+    std::vector<std::string> pats; // the strings of a set, in the order given (-e: hex with --hex; --patterns: as they stand)
+    std::vector<bool> pat_hex;
+    bool use_set = false, ignore_case = false;
+    auto read_patterns = [&](const std::string &path) {
+        FILE *pf = fopen(path.c_str(), "rb");
+        if (!pf) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + path + ": " + strerror(errno));
+        std::string all;
+        char buf[4096];
+        for (size_t got; (got = fread(buf, 1, sizeof buf, pf)) > 0;) all.append(buf, got);
+        fclose(pf);
+        size_t line = 1;
+        for (size_t at = 0; at < all.size(); line++) {
+            size_t end = all.find('\n', at);
+            if (end == std::string::npos) end = all.size();
+            if (end == at) die(ERR_ARGS, "'--patterns': line " + std::to_string(line) + " of " + path + " is empty");
+            pats.push_back(all.substr(at, end - at)), pat_hex.push_back(false);
+            at = end + 1;
+        }
+    };
     bool searching = false, needle_hex = false, count_only = false;
     bool grepping = false, invert = false, line_number = false; // (--grep is a --search that writes lines: `searching` holds for both)
     bool interval_given = false;
@@ -178,9 +204,20 @@ int main(int argc, char **argv)
             expect = ANY;
         } else if (expect == SEARCH || expect == GREP) {
             if (searching) die(ERR_ARGS, grepping != (expect == GREP) ? "'--grep' and '--search' exclude each other" : "'--search' and '--grep' may be given once");
-            needle = a;
             searching = true;
             grepping = expect == GREP;
+            expect = ANY;
+            if (a == "-e") expect = PATTERN;             // (no <string> of its own: the set's strings follow)
+            else if (a == "--patterns") expect = PATFILE;
+            else if (a == "--ignore-case") ignore_case = true;
+            else needle = a, pats.push_back(a), pat_hex.push_back(true);
+        } else if (expect == PATTERN) {
+            pats.push_back(a), pat_hex.push_back(true);
+            use_set = true;
+            expect = ANY;
+        } else if (expect == PATFILE) {
+            read_patterns(a);
+            use_set = true;
             expect = ANY;
         } else if (expect == ANY && a.rfind("--", 0) == 0) {
             if (a == "--help") usage(true);
@@ -209,12 +246,16 @@ int main(int argc, char **argv)
             else if (a == "--line-number") line_number = true;
             else if (a == "--hex") needle_hex = true;
             else if (a == "--count") count_only = true;
+            else if (a == "--patterns") expect = PATFILE;
+            else if (a == "--ignore-case") ignore_case = true;
             else if (a == "--stdout") set_output("", true);
             else if (a == "--") expect = NOARGS;
             else die(ERR_ARGS, "Unrecognised argument " + a);
         } else if (expect == ANY && !a.empty() && a[0] == '-') {
             if (a == "-") {
                 set_input("", true);
+            } else if (a == "-e") {
+                expect = PATTERN;
             } else {
                 for (size_t c = 1; c < a.size(); c++) {
                     const char f = a[c];
@@ -236,6 +277,11 @@ int main(int argc, char **argv)
     if (expect == RANGE) die(ERR_ARGS, "Argument '--range' requires <offset>:<length>, both in bytes");
     if (expect == SEARCH) die(ERR_ARGS, "Argument '--search' requires a string");
     if (expect == GREP) die(ERR_ARGS, "Argument '--grep' requires a string");
+    if (expect == PATTERN) die(ERR_ARGS, "Argument '-e' requires a string");
+    if (expect == PATFILE) die(ERR_ARGS, "Argument '--patterns' requires a file path");
+    use_set = use_set || ignore_case;
+    if (use_set && !searching) die(ERR_ARGS, "'-e', '--patterns' and '--ignore-case' go with '--search' or '--grep'");
+    if (use_set && pats.empty()) die(ERR_ARGS, "'--search' and '--grep' require a string, a '-e' or a '--patterns'");
     if (!have_in) die(ERR_ARGS, "An input must be specified");
     if ((needle_hex || count_only) && !searching) die(ERR_ARGS, "'--hex' and '--count' go with '--search' or '--grep'");
     if ((invert || line_number) && !grepping) die(ERR_ARGS, "'--invert' and '--line-number' go with '--grep'");
@@ -246,7 +292,7 @@ int main(int argc, char **argv)
                                    : "'--search' takes an input, '--hex', '--count', '--index' and one '--range', nothing else");
         if (ranges.size() > 1 || (!ranges.empty() && index_path.empty())) die(ERR_ARGS, "'--search' takes one '--range', with the '--index' of the input");
         if (!index_path.empty() && in_stdin) die(ERR_ARGS, "'--search --index' reads parts of a file: standard in cannot be the input");
-        if (needle_hex) {
+        auto unhex = [&](std::string &needle) {
             std::string raw;
             auto nib = [](char ch) { return ch >= '0' && ch <= '9' ? ch - '0' : ch >= 'a' && ch <= 'f' ? ch - 'a' + 10 : ch >= 'A' && ch <= 'F' ? ch - 'A' + 10 : -1; };
             if (needle.size() % 2) die(ERR_ARGS, "Argument '--search' with '--hex' requires an even number of hex digits");
@@ -255,8 +301,14 @@ int main(int argc, char **argv)
                 raw.push_back((char)(nib(needle[c]) * 16 + nib(needle[c + 1])));
             }
             needle = raw;
+        };
+        if (needle_hex && !use_set) unhex(needle);
+        if (!use_set && (needle.empty() || needle.size() > BZH_SEARCH_MAX_PATTERN)) die(ERR_ARGS, "Argument '--search' requires a string of 1 to 256 bytes");
+        for (size_t k = 0; use_set && k < pats.size(); k++) {
+            if (needle_hex && pat_hex[k]) unhex(pats[k]);
+            if (pats[k].empty() || pats[k].size() > BZH_SEARCH_MAX_PATTERN) die(ERR_ARGS, "string " + std::to_string(k) + " does not hold 1 to 256 bytes");
         }
-        if (needle.empty() || needle.size() > BZH_SEARCH_MAX_PATTERN) die(ERR_ARGS, "Argument '--search' requires a string of 1 to 256 bytes");
+        if (use_set && pats.size() > BZH_PATSET_MAX_PATTERNS) die(ERR_ARGS, "more than 65536 strings");
     }
     const bool by_range = !ranges.empty() && !searching, make_index = !mkindex_path.empty();
     if (by_range && index_path.empty()) die(ERR_ARGS, "'--range' needs the '--index' of the input");
@@ -377,6 +429,18 @@ int main(int argc, char **argv)
         if (rs != BZH_OK) die(ERR_OUTPUT, std::string(doing) + bzh_strerror(rs));
         static const uint8_t nothing = 0;
         const uint8_t *cp = comp.empty() ? &nothing : comp.data();
+        bzh_patset *set = nullptr; // several strings or --ignore-case: one compiled set; else the single-pattern calls, as ever
+        if (use_set) {
+            std::vector<const uint8_t *> pp;
+            std::vector<size_t> pl;
+            for (const std::string &q : pats) pp.push_back((const uint8_t *)q.data()), pl.push_back(q.size());
+            rs = bzh_patset_create(sctx, pp.data(), pl.data(), pp.size(), ignore_case ? BZH_PATSET_FOLD_ASCII : 0, &set);
+            if (rs != BZH_OK) {
+                const std::string msg = std::string(doing) + bzh_strerror(rs) + ": " + bzh_last_error(sctx);
+                bzh_destroy(sctx);
+                die(rs == BZH_E_ARG ? ERR_ARGS : ERR_OUTPUT, msg);
+            }
+        }
         if (grepping) { // --grep: the selected lines come back compacted; a first try with a guess, a second with the exact rooms
             const unsigned gflags = invert ? BZH_GREP_INVERT : 0;
             std::vector<uint8_t> out(count_only ? 0 : (size_t)16 << 20);
@@ -386,7 +450,12 @@ int main(int argc, char **argv)
             for (int attempt = 0; attempt < 2; attempt++) {
                 uint8_t *op = out.empty() ? nullptr : out.data();
                 bzh_grep_entry *lp = lines.empty() ? nullptr : lines.data();
-                if (index_path.empty())
+                if (set && index_path.empty())
+                    rs = bzh_grep_patset(sctx, cp, comp.size(), set, gflags, '\n', op, out.size(), lp, lines.size(), &nrecs, &total, nullptr, nullptr);
+                else if (set)
+                    rs = bzh_grep_patset_index(sctx, cp, comp.size(), ent.data(), ent.size(), pts.data(), pts.size(), set, gflags, '\n', op, out.size(),
+                                               lp, lines.size(), &nrecs, &total);
+                else if (index_path.empty())
                     rs = bzh_grep(sctx, cp, comp.size(), pat, needle.size(), gflags, '\n', op, out.size(), lp, lines.size(), &nrecs, &total, nullptr,
                                   nullptr);
                 else
@@ -398,9 +467,11 @@ int main(int argc, char **argv)
             }
             if (rs != BZH_OK) {
                 const std::string msg = std::string("error during grep: ") + bzh_strerror(rs) + ": " + bzh_last_error(sctx);
+                bzh_patset_destroy(set);
                 bzh_destroy(sctx);
                 die(ERR_OUTPUT, msg);
             }
+            bzh_patset_destroy(set);
             bzh_destroy(sctx);
             bool ok = true;
             if (count_only) {
@@ -417,25 +488,41 @@ int main(int argc, char **argv)
             return SUCCESS; // (the input is kept: nothing was made of it)
         }
         const unsigned flags = records ? BZH_SEARCH_RECORDS : 0;
-        std::vector<bzh_hit> hits(count_only ? 0 : (size_t)1 << 16);
+        std::vector<bzh_hit> hits(count_only || set ? 0 : (size_t)1 << 16);
+        std::vector<bzh_set_hit> shits(count_only || !set ? 0 : (size_t)1 << 16);
         size_t nhits = 0;
         for (int attempt = 0; attempt < 2; attempt++) { // (more hits than the first try's room: once more, with exactly theirs)
-            if (index_path.empty())
+            if (set && index_path.empty())
+                rs = bzh_search_patset(sctx, cp, comp.size(), set, flags, '\n', shits.data(), shits.size(), &nhits, nullptr, nullptr);
+            else if (set)
+                rs = bzh_search_patset_range(sctx, cp, comp.size(), lo, ent.data(), ent.size(), pts.data(), pts.size(), records ? cum.data() : nullptr,
+                                             want.off, want.len, set, flags, '\n', shits.data(), shits.size(), &nhits);
+            else if (index_path.empty())
                 rs = bzh_search(sctx, cp, comp.size(), pat, needle.size(), flags, '\n', hits.data(), hits.size(), &nhits, nullptr, nullptr);
             else
                 rs = bzh_search_range(sctx, cp, comp.size(), lo, ent.data(), ent.size(), pts.data(), pts.size(), records ? cum.data() : nullptr,
                                       want.off, want.len, pat, needle.size(), flags, '\n', hits.data(), hits.size(), &nhits);
             if (rs != BZH_E_CAP || count_only || attempt) break;
-            hits.resize(nhits);
+            if (set) shits.resize(nhits);
+            else hits.resize(nhits);
         }
         if (rs != BZH_OK) {
             const std::string msg = std::string(doing) + bzh_strerror(rs) + ": " + bzh_last_error(sctx);
+            bzh_patset_destroy(set);
             bzh_destroy(sctx);
             die(ERR_OUTPUT, msg);
         }
+        bzh_patset_destroy(set);
         bzh_destroy(sctx);
         if (count_only) {
             printf("%zu\n", nhits);
+        } else if (set) {
+            for (size_t k = 0; k < nhits; k++) {
+                if (records)
+                    printf("%llu\t%llu\t%u\n", (unsigned long long)shits[k].off, (unsigned long long)shits[k].record, shits[k].pattern);
+                else
+                    printf("%llu\t-\t%u\n", (unsigned long long)shits[k].off, shits[k].pattern);
+            }
         } else {
             for (size_t k = 0; k < nhits; k++) {
                 if (records)

@@ -618,26 +618,45 @@ int decode_range_sink_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t 
 // WindowSink::room's.  scan_tiles: the tiles of a window of n bytes, counted into the call's statistics.
 int scan_room(bzh_ctx *ctx, const char *what, uint64_t carry, uint64_t bytes, uint64_t *staging_peak, uint8_t **d_stage, uint64_t *front);
 int scan_tiles(bzh_ctx *ctx, const char *who, uint64_t n, uint64_t *windows, uint64_t *tiles_sum, uint32_t *tiles);
+// patset.hip: a compiled set of patterns (patset_plan.h), resident on its device in one allocation of its own -- it belongs to no
+// context.  set_matcher: the set as the kernels take it, for a window whose matches end at or in front of lim
+struct bzh_patset {
+    int device;
+    bzh_patset_info info;
+    uint8_t *d_mem; // cls[256], first[256], pat_no[distinct], table[states * classes]
+    const uint8_t *d_cls;
+    const uint16_t *d_first, *d_table;
+    const uint32_t *d_pat_no;
+};
+struct BzmMatcher;
+BzmMatcher set_matcher(const bzh_patset *set, uint32_t delim, uint64_t lim);
 // search.hip: the search over decoded bytes in HBM.  A sink is what is looked for, where the hits go, and the walk over its windows
 // (search_plan.h): room() puts the carry in front of the window, window() runs the two passes and keeps the window's tail.
 struct SearchSink final : WindowSink {
-    BzfPattern pat;
+    BzfPattern pat{};
+    const bzh_patset *set = nullptr; // what is looked for instead of pat: hits are bzh_set_hit, the windows BzmSetWalk::window_set's
     bool records;
-    bzh_hit *hits; // host
+    void *hits; // host: bzh_hit, or bzh_set_hit
     uint64_t max;
-    BzfWalk walk;
+    BzmSetWalk walk;
     SearchSink(const uint8_t *pat_, size_t plen, unsigned flags, uint8_t delim_, bzh_hit *hits_, size_t max_)
         : WindowSink(BZF_FRONT, delim_), pat(bzf_pattern(pat_, (uint32_t)plen, delim_)), records((flags & BZH_SEARCH_RECORDS) != 0), hits(hits_), max(max_) {}
-    void begin(uint64_t lo, uint64_t hi, uint64_t out_start, uint64_t rec_start) override { walk.begin(pat.plen, front, max, lo, hi, out_start, rec_start); }
+    SearchSink(const bzh_patset *set_, unsigned flags, uint8_t delim_, bzh_set_hit *hits_, size_t max_)
+        : WindowSink(BZF_FRONT, delim_), set(set_), records((flags & BZH_SEARCH_RECORDS) != 0), hits(hits_), max(max_) {}
+    uint32_t plen() const { return set ? set->info.max_len : pat.plen; } // (of a set: its longest pattern's)
+    size_t hit_size() const { return set ? sizeof(bzh_set_hit) : sizeof(bzh_hit); }
+    void begin(uint64_t lo, uint64_t hi, uint64_t out_start, uint64_t rec_start) override { walk.begin(plen(), front, max, lo, hi, out_start, rec_start); }
     int room(bzh_ctx *ctx, uint64_t bytes, uint8_t **d_stage) override;
     int window(bzh_ctx *ctx, uint64_t bytes) override;
 };
 int search_raw_run(bzh_ctx *ctx, SearchSink &sink, const uint8_t *d_raw, size_t n);
+int search_finish(bzh_ctx *ctx, SearchSink &sink); // of a set search: the starts held back, behind the last window
 // grep.hip: the selected records of decoded bytes in HBM, compacted into d_out.  A sink is what is looked for, where bytes and
 // entries go, and the walk over its windows (grep_plan.h): as the search's, with the whole open record carried (begin() has nothing
 // to say: a grep takes the whole output).  grep_finish: the bytes held back and the open tail, behind the last window.
 struct GrepSink final : WindowSink {
-    BzfPattern pat;
+    BzfPattern pat{};
+    const bzh_patset *set = nullptr; // what is looked for instead of pat; the walk keeps its rule with plen = the longest pattern's
     uint8_t *d_out;      // device (null: not asked for)
     bzh_grep_entry *ent; // host (null: not asked for)
     BzgWalk walk;
@@ -648,6 +667,11 @@ struct GrepSink final : WindowSink {
         : WindowSink(BZF_FRONT, delim_), pat(bzf_pattern(pat_, (uint32_t)plen, delim_)), d_out((uint8_t *)d_out_), ent(ent_)
     {
         walk.begin((uint32_t)plen, (flags & BZH_GREP_INVERT) != 0, d_out != nullptr, cap, ent != nullptr, max);
+    }
+    GrepSink(const bzh_patset *set_, unsigned flags, uint8_t delim_, void *d_out_, size_t cap, bzh_grep_entry *ent_, size_t max)
+        : WindowSink(BZF_FRONT, delim_), set(set_), d_out((uint8_t *)d_out_), ent(ent_)
+    {
+        walk.begin(set->info.max_len, (flags & BZH_GREP_INVERT) != 0, d_out != nullptr, cap, ent != nullptr, max);
     }
     void begin(uint64_t, uint64_t, uint64_t, uint64_t) override {}
     int room(bzh_ctx *ctx, uint64_t bytes, uint8_t **d_stage) override;

@@ -5,6 +5,7 @@
 // window, and the selected records.
 #include "common.h"
 #include "grep_core.h"
+#include "patset_core.h"
 
 static_assert(sizeof(bzh_grep_entry) == 32 && sizeof(BzgEntry) == sizeof(bzh_grep_entry), "an entry is four words");
 static_assert(sizeof(BzgTile) == 32 && sizeof(BzgBase) == 24, "the tile tables");
@@ -18,16 +19,17 @@ struct GfArgs {
     BzgEntry *ent;       // the window's entries [0, selected) (null: only bytes are asked for)
 };
 
-// One workgroup a tile of 4,096 positions, 16 a thread; the tile, the halo behind it and the pattern are staged in LDS by the front
-// it shares with search_tiles (search_core.h).  GATHER false: the tile's record (BzgTile), one plain store -- no atomics; grep_scan joins the tiles.  GATHER true,
+// One workgroup a tile of 4,096 positions, 16 a thread; the tile, the halo behind it and what the matcher M keeps beside them are
+// staged in LDS by the front it shares with search_tiles (search_core.h; the matchers: patset_core.h).  A set bounds its matches by
+// the text's end itself, so every processed position is one of its starts.  GATHER false: the tile's record (BzgTile), one plain store -- no atomics; grep_scan joins the tiles.  GATHER true,
 // in tiles that hold selected bytes: the same masks again, the selection of every byte, the selected ones compacted in LDS and
 // written to out[out_base + base.out ..) -- bytes of this tile only, to addresses no other workgroup writes: words inside the run,
 // single bytes at its two ends -- and an entry from every thread that holds a selected record's delimiter.
-template <bool GATHER>
-__global__ void __launch_bounds__(BZF_THREADS) grep_tiles(GfArgs a, BzfPattern p)
+template <bool GATHER, class M>
+__global__ void __launch_bounds__(BZF_THREADS) grep_tiles(GfArgs a, M m)
 {
     __shared__ __attribute__((aligned(16))) uint8_t tile[BZF_TILE + BZF_MAX_PATTERN];
-    __shared__ __attribute__((aligned(4))) uint8_t pat[BZF_MAX_PATTERN];
+    __shared__ typename M::Shared msh;
     __shared__ BzgShared sh;
     const uint32_t tid = threadIdx.x;
     BzgTile x{};
@@ -38,10 +40,11 @@ __global__ void __launch_bounds__(BZF_THREADS) grep_tiles(GfArgs a, BzfPattern p
         base = a.base[blockIdx.x];
     }
     const uint64_t t0 = (uint64_t)blockIdx.x * BZF_TILE, p0 = t0 + tid * BZF_ITEMS;
-    const BzfVec own = bzf_stage(a.d, a.win.n, t0, tid, p, tile, pat);
+    const BzfVec own = m.stage(a.d, a.win.n, t0, tid, tile, msh);
     __syncthreads();
     BzgThread t;
-    bzg_masks(t, a.win, p0, own, p.delim, bzf_match16(own, tid, p, tile, pat, bzg_starts(a.win, p0)));
+    const uint32_t starts = M::BY_LIM ? bzf_range_mask16(p0, a.win.p_lo, a.win.p_hi) : bzg_starts(a.win, p0);
+    bzg_masks(t, a.win, p0, own, m.delim(), m.match16(own, tid, p0, tile, msh, starts));
     bzg_local(t, a.win.invert);
     bzg_count_p0(sh, tid, t);
     __syncthreads();
@@ -107,6 +110,14 @@ __global__ void __launch_bounds__(BZF_THREADS) grep_scan(BzgTile *tile, uint32_t
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
+// f(the sink's matcher): its pattern, or its set bounded by the text's end
+template <class F>
+static void grep_matcher(const GrepSink &g, uint64_t n, F &&f)
+{
+    if (g.set) f(set_matcher(g.set, g.delim, n));
+    else f(BzfOne{g.pat});
+}
+
 // The passes over the window w of d (16-byte aligned; w.n bytes lie there, and the aligned word that holds the last of them).  One
 // wait, for the window's totals; bytes and entries follow the stream and are there after the call's last wait.
 static int grep_window_run(bzh_ctx *ctx, GrepSink &g, const uint8_t *d, const BzgWindow &w, uint64_t bytes)
@@ -123,7 +134,7 @@ static int grep_window_run(bzh_ctx *ctx, GrepSink &g, const uint8_t *d, const Bz
         BZH_TRY(reserve_cut(ctx, ctx->grep_tab, "the grep's tile tables", grow_mib,
                             [&](Carver &c) { c.put(tile, tiles), c.put(base, tiles), c.put(d_tot, BZG_TOTALS); }));
         GfArgs a{d, w, tile, base, nullptr, nullptr};
-        grep_tiles<false><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, g.pat);
+        grep_matcher(g, w.n, [&](const auto &m) { grep_tiles<false><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
         grep_scan<<<dim3(1), BZF_THREADS, 0, st>>>(tile, tiles, base, w, d_tot);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(totals, d_tot, sizeof totals, hipMemcpyDeviceToHost, st));
@@ -134,7 +145,7 @@ static int grep_window_run(bzh_ctx *ctx, GrepSink &g, const uint8_t *d, const Bz
                 BZH_TRY(ctx->grep_ent.reserve(ctx, (size_t)totals[BZG_T_SEL] * sizeof(BzgEntry), "the grep's entries", grow_mib));
                 a.ent = ctx->grep_ent.as<BzgEntry>();
             }
-            grep_tiles<true><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, g.pat);
+            grep_matcher(g, w.n, [&](const auto &m) { grep_tiles<true><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
             HIP_TRY(ctx, hipGetLastError());
             if (a.ent)
                 HIP_TRY(ctx, hipMemcpyAsync(g.ent + w.sel_base, a.ent, (size_t)totals[BZG_T_SEL] * sizeof(BzgEntry), hipMemcpyDeviceToHost, st));

@@ -5,10 +5,12 @@
 // is a word a window, and the hits.
 #include "common.h"
 #include "search_core.h"
+#include "patset_core.h"
 
 static_assert(BZF_MAX_PATTERN == BZH_SEARCH_MAX_PATTERN, "search_core.h and bzhip.h name the same bound");
 static_assert(BZF_FRONT % 16 == 0 && BZF_FRONT >= BZF_MAX_PATTERN, "a window begins aligned, its carry in front of it");
-static_assert(sizeof(bzh_hit) == 16, "a hit is two words");
+static_assert(sizeof(bzh_hit) == 16 && sizeof(BzfHit) == sizeof(bzh_hit), "a hit is two words");
+static_assert(sizeof(bzh_set_hit) == 24 && sizeof(BzmHit) == sizeof(bzh_set_hit), "a set's hit is three");
 
 struct SfArgs {
     const uint8_t *d; // 16-byte aligned
@@ -16,28 +18,29 @@ struct SfArgs {
     uint32_t records;
     uint32_t *thits, *tdel;        // [tiles] pass one: hits and delimiters of every tile
     const uint64_t *hbase, *dbase; // [tiles] search_scan: those in front of every tile
-    bzh_hit *out;                  // the window's hit slots [0, win.emit)
+    void *out;                     // the window's hit slots [0, win.emit): the matcher's Hit
 };
 
-// One workgroup a tile of 4,096 positions, 16 a thread.  The tile and the halo behind it are staged in LDS, the pattern too (every
-// lane reads the same byte of it).  EMIT false: the tile's hits and delimiters, reduced over the workgroup, a plain store each -- no
+// One workgroup a tile of 4,096 positions, 16 a thread.  The tile and the halo behind it are staged in LDS, and what the matcher M
+// keeps beside them (patset_core.h: BzfOne, the single pattern -- every lane reads the same byte of it; BzmMatcher, a set).  EMIT false: the tile's hits and delimiters, reduced over the workgroup, a plain store each -- no
 // atomics; search_scan sums the tiles.  EMIT true: the same tests again, in tiles that hold a hit in front of the caller's bound,
 // and every hit whose rank in the window is below win.emit stores itself at its rank: the output ascends, and "the first max" costs
 // nothing.  Stores: the tile's two words, or hit slots below win.emit.
-template <bool EMIT>
-__global__ void __launch_bounds__(BZF_THREADS) search_tiles(SfArgs a, BzfPattern p)
+template <bool EMIT, class M>
+__global__ void __launch_bounds__(BZF_THREADS) search_tiles(SfArgs a, M m)
 {
     __shared__ __attribute__((aligned(16))) uint8_t tile[BZF_TILE + BZF_MAX_PATTERN];
-    __shared__ __attribute__((aligned(4))) uint8_t pat[BZF_MAX_PATTERN];
+    __shared__ typename M::Shared msh;
     __shared__ uint32_t lds[8];
     const uint32_t tid = threadIdx.x;
     if (EMIT && (a.thits[blockIdx.x] == 0 || a.hbase[blockIdx.x] >= a.win.emit)) return; // (the same for every thread)
     const uint64_t n = a.win.n, t0 = (uint64_t)blockIdx.x * BZF_TILE, p0 = t0 + tid * BZF_ITEMS;
-    const BzfVec own = bzf_stage(a.d, n, t0, tid, p, tile, pat);
+    const BzfVec own = m.stage(a.d, n, t0, tid, tile, msh);
     __syncthreads();
-    uint32_t hm = bzf_match16(own, tid, p, tile, pat, bzf_range_mask16(p0, a.win.s_lo, a.win.s_hi));
-    const uint32_t dm = a.records ? bzf_eq_mask16(own.x, own.y, own.z, own.w, p.delim) & bzf_range_mask16(p0, a.win.d_lo, n) : 0u;
-    const uint32_t nh = (uint32_t)__popc(hm), nd = (uint32_t)__popc(dm);
+    uint32_t hm;
+    const uint32_t nh = m.count16(own, tid, p0, tile, msh, bzf_range_mask16(p0, a.win.s_lo, a.win.s_hi), &hm);
+    const uint32_t dm = a.records ? bzf_eq_mask16(own.x, own.y, own.z, own.w, m.delim()) & bzf_range_mask16(p0, a.win.d_lo, n) : 0u;
+    const uint32_t nd = (uint32_t)__popc(dm);
     if (!EMIT) {
         const uint32_t sh = wave_reduce_add(nh), sd = wave_reduce_add(nd);
         if ((tid & 63u) == 0) lds[tid >> 6] = sh, lds[4 + (tid >> 6)] = sd;
@@ -55,7 +58,7 @@ __global__ void __launch_bounds__(BZF_THREADS) search_tiles(SfArgs a, BzfPattern
     while (hm) {
         const uint32_t k = (uint32_t)__ffs((int)hm) - 1u;
         hm &= hm - 1u;
-        if (rank < a.win.emit) {
+        if (rank < a.win.emit) { // (a start's hits ascend: none of a start whose first is not stored is)
             const uint64_t pos = p0 + k;
             uint64_t rec = 0;
             if (a.records) {
@@ -64,13 +67,14 @@ __global__ void __launch_bounds__(BZF_THREADS) search_tiles(SfArgs a, BzfPattern
                 } else { // a start in the carry: the delimiters between it and d_lo were counted by the window before
                     const uint32_t gap = (uint32_t)min(a.win.d_lo - pos, (uint64_t)(BZF_MAX_PATTERN - 1)); // (the halo holds them)
                     uint32_t c = 0;
-                    for (uint32_t j = 0; j < gap; j++) c += tile[tid * BZF_ITEMS + k + j] == p.delim;
+                    for (uint32_t j = 0; j < gap; j++) c += tile[tid * BZF_ITEMS + k + j] == m.delim();
                     rec = a.win.rec_base - c;
                 }
             }
-            a.out[rank] = bzh_hit{a.win.off_base + pos, rec};
+            rank = m.emit1(msh, tile + tid * BZF_ITEMS + k, pos, a.win.off_base + pos, rec, static_cast<typename M::Hit *>(a.out), rank, a.win.emit);
+        } else {
+            break; // (the ranks ascend)
         }
-        rank++;
     }
 }
 
@@ -135,9 +139,18 @@ int scan_tiles(bzh_ctx *ctx, const char *who, uint64_t n, uint64_t *windows, uin
 }
 
 // ---- host side: the search ---------------------------------------------------------------------------------------------------------
+// f(the sink's matcher): its pattern, or its set bounded by lim
+template <class F>
+static void search_matcher(const SearchSink &s, uint64_t lim, F &&f)
+{
+    if (s.set) f(set_matcher(s.set, s.delim, lim));
+    else f(BzfOne{s.pat});
+}
+
 // The two passes over the window w of d (16-byte aligned; w.n bytes lie there, and the aligned word that holds the last of them).
 // One wait, for the window's two totals; the hits follow the stream to the caller's array and are there after the call's last wait.
-static int search_window_run(bzh_ctx *ctx, SearchSink &s, const uint8_t *d, BzfWindow w, uint64_t bytes)
+// lim: where a set's matches end (search_plan.h: BzmSetWalk).
+static int search_window_run(bzh_ctx *ctx, SearchSink &s, const uint8_t *d, BzfWindow w, uint64_t lim, uint64_t bytes)
 {
     hipStream_t st = ctx->stream;
     bzh_search_stats &ss = ctx->sstats;
@@ -151,19 +164,20 @@ static int search_window_run(bzh_ctx *ctx, SearchSink &s, const uint8_t *d, BzfW
             c.put(hbase, tiles), c.put(dbase, tiles), c.put(d_tot, 2), c.put(thits, tiles), c.put(tdel, tiles);
         }));
         SfArgs a{d, w, s.records ? 1u : 0u, thits, tdel, hbase, dbase, nullptr};
-        search_tiles<false><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, s.pat);
+        search_matcher(s, lim, [&](const auto &m) { search_tiles<false><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
         search_scan<<<dim3(1), BZF_THREADS, 0, st>>>(thits, tdel, tiles, hbase, dbase, d_tot);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(totals, d_tot, sizeof totals, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, bzh_stream_wait(st));
         const uint64_t emit = s.walk.emit(totals[0]);
         if (emit) {
-            BZH_TRY(ctx->search_out.reserve(ctx, (size_t)emit * sizeof(bzh_hit), "the search's hits", grow_mib));
+            const size_t hs = s.hit_size();
+            BZH_TRY(ctx->search_out.reserve(ctx, (size_t)emit * hs, "the search's hits", grow_mib));
             a.win.emit = emit;
-            a.out = ctx->search_out.as<bzh_hit>();
-            search_tiles<true><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, s.pat);
+            a.out = ctx->search_out.p;
+            search_matcher(s, lim, [&](const auto &m) { search_tiles<true><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
             HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipMemcpyAsync(s.hits + s.walk.rank, a.out, (size_t)emit * sizeof(bzh_hit), hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipMemcpyAsync((uint8_t *)s.hits + (size_t)s.walk.rank * hs, a.out, (size_t)emit * hs, hipMemcpyDeviceToHost, st));
         }
     }
     s.walk.advance(bytes, totals[0], totals[1]);
@@ -181,18 +195,32 @@ int SearchSink::room(bzh_ctx *ctx, uint64_t bytes, uint8_t **d_stage)
 int SearchSink::window(bzh_ctx *ctx, uint64_t bytes)
 {
     const uint8_t *base = ctx->search_ws.p;
-    const BzfWindow w = walk.window(bytes);
+    uint64_t lim = 0; // (of a set's window)
+    const BzfWindow w = set ? walk.window_set(bytes, false, &lim) : walk.window(bytes);
     const uint64_t keep = walk.carry_after(bytes);
     if (keep) { // [n - keep, n): read before the passes' wait, written where no pass looks
         BZH_TRY(ctx->scan_carry.reserve(ctx, BZF_MAX_PATTERN, "the search's carry"));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->scan_carry, base + w.n - keep, (size_t)keep, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    return search_window_run(ctx, *this, base, w, bytes);
+    return search_window_run(ctx, *this, base, w, lim, bytes);
 }
 
 // Decoded bytes that already lie in HBM: one window, no staging, no carry.
 int search_raw_run(bzh_ctx *ctx, SearchSink &sink, const uint8_t *d_raw, size_t n)
 {
-    sink.walk.begin(sink.pat.plen, 0, sink.max, 0, n, 0, 0);
-    return search_window_run(ctx, sink, d_raw, sink.walk.window(n), n);
+    sink.walk.begin(sink.plen(), 0, sink.max, 0, n, 0, 0);
+    uint64_t lim = 0;
+    const BzfWindow w = sink.set ? sink.walk.window_set(n, true, &lim) : sink.walk.window(n);
+    return search_window_run(ctx, sink, d_raw, w, lim, n);
+}
+
+// Behind the last window of a set search: the starts held back are processed where they lie, in the carry -- a window without new
+// bytes, its text the carry, every delimiter of which has been counted.
+int search_finish(bzh_ctx *ctx, SearchSink &sink)
+{
+    if (!sink.set || !sink.walk.carry) return BZH_OK;
+    sink.walk.front = sink.walk.carry;
+    uint64_t lim = 0;
+    const BzfWindow w = sink.walk.window_set(0, true, &lim);
+    return search_window_run(ctx, sink, ctx->scan_carry, w, lim, 0);
 }

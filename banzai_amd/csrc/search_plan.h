@@ -86,6 +86,40 @@ struct BzfWalk {
     }
 };
 
+// THE WALK OF A SET SEARCH (bzh_search_patset*).  Hits are pairs (start, pattern) and ascend by start, then by length; with several
+// lengths "a window reports the matches that end inside it" would break that order, so the grep's hold-back is used instead:
+//   * a window that is not the last processes the STARTS in front of its last max_len - 1 bytes; those bytes are carried, and the
+//     next window, which sees every match from there to its end, processes them;
+//   * the last window processes every start; a match is bounded by *lim, the end of the text or of the wanted range;
+//   * the call therefore ends with a finishing window over the carry, without new bytes, when bytes are held back.
+// The delimiters of the carry were counted by the window that held it back, as above.  plen holds max_len.
+struct BzmSetWalk : BzfWalk {
+    // the next window: `bytes` new bytes at `front`; last: nothing follows
+    BzfWindow window_set(uint64_t bytes, bool last, uint64_t *lim) const
+    {
+        BzfWindow w{};
+        w.n = front + bytes;
+        w.d_lo = front;
+        w.off_base = out_pos - front;
+        w.rank_base = rank;
+        w.rec_base = recs;
+        w.s_lo = w.s_hi = front;
+        *lim = w.n;
+        const uint64_t end = out_pos + bytes, keep = (uint64_t)plen - 1;
+        const uint64_t held = out_pos - carry;                              // the first start no window has processed
+        const uint64_t p_hi = last ? end : (end - held > keep ? end - keep : held);
+        const uint64_t from = held > lo ? held : lo;
+        const uint64_t bound = end < hi ? end : hi;                         // a reported match ends at or in front of it
+        const uint64_t upto = p_hi < bound ? p_hi : bound;
+        if (upto > from) {
+            w.s_lo = front + (from - out_pos);                              // (from may lie in the carry: the difference wraps and comes back)
+            w.s_hi = front + (upto - out_pos);
+            *lim = front + (bound - out_pos);
+        }
+        return w;
+    }
+};
+
 // The blocks of one window of a range search: as many consecutive entries from `at` on as the staging target takes, at least one,
 // at most bmax.  Returns their number, *bytes their decoded sizes' sum.
 template <class E>

@@ -682,6 +682,71 @@ typedef struct {
 } bzh_grep_stats;
 BZH_API int bzh_get_grep_stats(const bzh_ctx *ctx, bzh_grep_stats *out);
 
+/* ---- a set of patterns in one pass: grep -F -f FILE, -e A -e B, -i -------------------------------------------------------- */
+
+/* A pattern set is compiled on the host into a byte-class map and a trie without failure links, and lies on its device from
+ * bzh_patset_create on; every start position of the text walks the trie (PFAC).  count is 1..BZH_PATSET_MAX_PATTERNS, every
+ * pattern 1..BZH_SEARCH_MAX_PATTERN bytes.  With BZH_PATSET_FOLD_ASCII the bytes 'A'..'Z' and 'a'..'z' compare equal; nothing
+ * else folds.  Patterns that are equal after folding collapse into one, whose number is the lowest index among them.  The trie
+ * may hold 65,535 states beyond its root; above that, and for a null array, a pattern of zero or too many bytes, an undefined
+ * flag bit and count 0: BZH_E_ARG, bzh_last_error(ctx) names the figure.  The table is uploaded and waited for inside the call.
+ * A set belongs to no context: it may be used with every context on the device of the one it was made with (on another device
+ * the using call returns BZH_E_ARG) and may be destroyed before or after that context. */
+typedef struct bzh_patset bzh_patset;
+enum { BZH_PATSET_FOLD_ASCII = 1 };
+#define BZH_PATSET_MAX_PATTERNS 65536
+typedef struct {
+    uint64_t patterns, distinct;   /* given / after folding and removing equals */
+    uint32_t min_len, max_len;
+    uint32_t states, classes;      /* rows (the root included) and columns of the table */
+    uint64_t table_bytes;
+} bzh_patset_info;
+BZH_API int bzh_patset_create(bzh_ctx *ctx, const uint8_t *const *pats, const size_t *lens, size_t count, unsigned flags,
+                              bzh_patset **out);
+BZH_API void bzh_patset_destroy(bzh_patset *set); /* null allowed */
+BZH_API int bzh_patset_get_info(const bzh_patset *set, bzh_patset_info *out);
+
+/* A hit of a set is a pair (output offset, distinct pattern) with the pattern matching there: overlapping ones and several
+ * patterns at one offset included ({"ab","abc"} in "abc": two hits).  Hits ascend by off, then by len.  `pattern` is the
+ * pattern's number (see above), `record` as bzh_hit's. */
+typedef struct {
+    uint64_t off, record;
+    uint32_t pattern, len;
+} bzh_set_hit;       /* 24 bytes */
+
+/* The single-pattern calls above with (pat, plen) replaced by a set: every other argument, the counting call, BZH_E_CAP and the
+ * statistics are theirs word for word.  A range search reports the pairs with off >= the range's start and off + len <= its end.
+ * A grep selects the records inside which a match of any pattern starts. */
+BZH_API int bzh_search_patset_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const bzh_patset *set, unsigned flags,
+                                         uint8_t delim, bzh_set_hit *hits, size_t max, size_t *nhits);
+BZH_API int bzh_search_patset_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                     bzh_set_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed);
+BZH_API int bzh_search_patset(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
+                              bzh_set_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed);
+BZH_API int bzh_search_patset_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base,
+                                           const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts, size_t npts,
+                                           const uint64_t *rec_cum, uint64_t off, uint64_t len, const bzh_patset *set, unsigned flags,
+                                           uint8_t delim, bzh_set_hit *hits, size_t max, size_t *nhits);
+BZH_API int bzh_search_patset_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
+                                    size_t count, const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off,
+                                    uint64_t len, const bzh_patset *set, unsigned flags, uint8_t delim, bzh_set_hit *hits, size_t max,
+                                    size_t *nhits);
+BZH_API int bzh_grep_patset_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                       void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total);
+BZH_API int bzh_grep_patset_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                   void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total,
+                                   uint64_t *decoded_total, size_t *consumed);
+BZH_API int bzh_grep_patset(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
+                            uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total,
+                            uint64_t *decoded_total, size_t *consumed);
+BZH_API int bzh_grep_patset_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count,
+                                         const bzh_sync_point *pts, size_t npts, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                         void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs,
+                                         uint64_t *out_total);
+BZH_API int bzh_grep_patset_index(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count,
+                                  const bzh_sync_point *pts, size_t npts, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                  uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total);
+
 /* ---- the encoder writes the index of its own stream: no decode pass to rediscover what it held -------------------------- */
 
 /* bzh_encode_device that also returns the index of the stream it writes: the entries bzh_decode_index would return for
