@@ -45,7 +45,7 @@ import numpy as np
 
 from . import _native
 
-__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex", "RecordIndex", "build_record_index", "record_index_of", "decompress_records", "search", "search_range", "grep", "grep_count", "PatternSet",
+__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex", "RecordIndex", "build_record_index", "record_index_of", "decompress_records", "search", "search_range", "grep", "grep_count", "PatternSet", "Regex", "regex_check",
            "IndexedReader", "build_sync_index", "SyncIndex", "encode_indexed", "encode_indexed_stream", "recover", "recover_stream", "Recovered", "RecoveredBlock", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
@@ -1001,6 +1001,60 @@ class PatternSet(_native.PatternSet):
             raise ValueError(f"a pattern set holds 1..{_native.PATSET_MAX_PATTERNS} patterns, not {len(pats)}")
         self.device = device
         super().__init__(_ctx(9, device), pats, bool(ignore_case))
+
+
+def _regex_args(patterns, ignore_case, dotall, max_span):
+    """what Regex and regex_check are given -> (the expressions, the flags, the span), refused before a device is touched"""
+    if isinstance(patterns, str):
+        raise TypeError("a regular expression must be bytes-like, not str")
+    if isinstance(patterns, (bytes, bytearray, memoryview)):
+        patterns = [patterns]
+    exprs = []
+    for p in patterns:
+        if not isinstance(p, (bytes, bytearray, memoryview)):
+            raise TypeError(f"a regular expression must be bytes-like, not {type(p).__name__}")
+        p = bytes(p)
+        if not 1 <= len(p) <= _native.REGEX_MAX_EXPR:
+            raise ValueError(f"a regular expression must hold 1..{_native.REGEX_MAX_EXPR} bytes, not {len(p)}")
+        exprs.append(p)
+    if not 1 <= len(exprs) <= _native.PATSET_MAX_PATTERNS:
+        raise ValueError(f"1..{_native.PATSET_MAX_PATTERNS} regular expressions are compiled together, not {len(exprs)}")
+    span = _int_arg(max_span, "max_span")
+    if not 1 <= span <= _native.REGEX_MAX_SPAN:
+        raise ValueError(f"max_span must lie in 1..{_native.REGEX_MAX_SPAN}, not {span}")
+    flags = (_native.REGEX_FOLD_ASCII if ignore_case else 0) | (_native.REGEX_DOTALL if dotall else 0)
+    return exprs, flags, span
+
+
+class Regex(_native.PatternSet):
+    """Regular expressions (bytes, or a list of 1..65536 of them, 1..4096 bytes each) compiled into one DFA that every start
+    position of the decoded text walks on the device: grep -E.  The syntax is a subset of Python's `re` on bytes -- literals,
+    the usual escapes, \\d \\w \\s and their complements, `.`, classes, groups, `|`, `? * + {m} {m,} {m,n}`; anchors, \\b,
+    backreferences, lookaround and lazy quantifiers are refused with the expression's number and the byte.  It goes wherever
+    `pattern` goes: search, search_range, grep, grep_count, IndexedReader.search and IndexedReader.grep.  A search reports ONE hit
+    per start at which some expression matches: `len` is the longest match of at most `max_span` (1..256) bytes, `pattern` the
+    lowest-numbered expression that matches exactly that length; overlapping starts are all hits.  A match longer than
+    `max_span` is not found; `.info["unbounded"]` says that the expressions have such matches.  `ignore_case` folds ASCII
+    letters (re.IGNORECASE on bytes), `dotall` lets `.` take 0x0A.  `.info` carries the fields of bzh_regex_info."""
+
+    def __init__(self, patterns, ignore_case=False, dotall=False, max_span=256, device=0, _no_lds=False):
+        exprs, flags, span = _regex_args(patterns, ignore_case, dotall, max_span)
+        self.device = device
+        super().__init__(_ctx(9, device), exprs, flags=flags | (_native.REGEX_NO_LDS if _no_lds else 0), regex=True, max_span=span)
+
+
+def regex_check(patterns, ignore_case=False, dotall=False, max_span=256):
+    """The compile of Regex alone, on the host, without a device -> the dictionary Regex(...).info would hold; ValueError with the
+    compiler's message (the expression's number and the byte) for what it refuses (bzh_regex_check)."""
+    import ctypes
+    exprs, flags, span = _regex_args(patterns, ignore_case, dotall, max_span)
+    arr = (ctypes.c_char_p * len(exprs))(*exprs)
+    lens = (ctypes.c_size_t * len(exprs))(*[len(e) for e in exprs])
+    info, err = _native.RegexInfo(), ctypes.create_string_buffer(256)
+    st = _native.lib().bzh_regex_check(arr, lens, len(exprs), flags, span, ctypes.byref(info), err, len(err))
+    if st != 0:
+        raise ValueError(err.value.decode("latin-1"))
+    return info.as_dict()
 
 
 def _pattern_arg(pattern):

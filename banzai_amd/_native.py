@@ -184,6 +184,23 @@ PATSET_FOLD_ASCII = 1
 PATSET_MAX_PATTERNS = 65536
 
 
+class RegexInfo(ctypes.Structure):
+    """bzh_regex_info"""
+    _fields_ = [("expressions", ctypes.c_uint64), ("min_len", ctypes.c_uint32), ("max_len", ctypes.c_uint32), ("states", ctypes.c_uint32),
+                ("classes", ctypes.c_uint32), ("unbounded", ctypes.c_uint32), ("in_lds", ctypes.c_uint32), ("table_bytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert ctypes.sizeof(RegexInfo) == 40
+REGEX_FOLD_ASCII = 1
+REGEX_DOTALL = 2
+REGEX_NO_LDS = 4
+REGEX_MAX_SPAN = 256
+REGEX_MAX_EXPR = 4096
+
+
 class GrepStats(ctypes.Structure):
     """bzh_grep_stats"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("records", "selected", "out_bytes", "windows", "tiles", "carry_peak", "staging_peak")]
@@ -315,6 +332,11 @@ SIGNATURES = {
                                          ctypes.POINTER(ctypes.c_void_p)]),
     "bzh_patset_destroy": (None, [ctypes.c_void_p]),
     "bzh_patset_get_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PatsetInfo)]),
+    "bzh_regex_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint32,
+                                        ctypes.POINTER(ctypes.c_void_p)]),
+    "bzh_regex_get_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RegexInfo)]),
+    "bzh_regex_check": (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p), szp, ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint32,
+                                       ctypes.POINTER(RegexInfo), ctypes.c_char_p, ctypes.c_size_t]),
     "bzh_search_set_room": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),
     "bzh_get_search_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SearchStats)]),
     "bzh_decode_scan": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u64p, u8p, ctypes.c_size_t, szp]),
@@ -574,18 +596,22 @@ class PatternSet:
     """A compiled set of patterns on the device of `ctx` (bzh_patset_create / bzh_patset_destroy): what the search and grep
     calls of a Context take in place of one pattern.  It outlives the context it was made with."""
 
-    def __init__(self, ctx, patterns, ignore_case=False, flags=None):
+    def __init__(self, ctx, patterns, ignore_case=False, flags=None, regex=False, max_span=0):
+        """regex: `patterns` are regular expressions (bzh_regex_create; flags: BZH_REGEX_*), .info is bzh_regex_info's"""
         self._h = None
         self._destroy = lib().bzh_patset_destroy  # kept so that close() still works during interpreter shutdown
         pats = [bytes(p) for p in patterns]
         arr = (ctypes.c_char_p * max(len(pats), 1))(*pats)
         lens = np.array([len(p) for p in pats] or [0], dtype=np.uintp)
         h = ctypes.c_void_p()
-        fl = (PATSET_FOLD_ASCII if ignore_case else 0) if flags is None else flags
-        ctx.check(lib().bzh_patset_create(ctx.handle, arr, ptr(lens, szp), len(pats), fl, ctypes.byref(h)))
+        fl = ((REGEX_FOLD_ASCII if regex else PATSET_FOLD_ASCII) if ignore_case else 0) if flags is None else flags
+        if regex:
+            ctx.check(lib().bzh_regex_create(ctx.handle, arr, ptr(lens, szp), len(pats), fl, max_span, ctypes.byref(h)))
+        else:
+            ctx.check(lib().bzh_patset_create(ctx.handle, arr, ptr(lens, szp), len(pats), fl, ctypes.byref(h)))
         self._h = h
-        i = PatsetInfo()
-        ctx.check(lib().bzh_patset_get_info(h, ctypes.byref(i)))
+        i = RegexInfo() if regex else PatsetInfo()
+        ctx.check((lib().bzh_regex_get_info if regex else lib().bzh_patset_get_info)(h, ctypes.byref(i)))
         self.info = i.as_dict()
 
     @property

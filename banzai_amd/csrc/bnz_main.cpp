@@ -11,6 +11,7 @@
 // leaves the device (bzh_search; with --index bzh_search_range over just the span's compressed bytes).
 // Grep: --grep writes the lines that hold a byte string, selected and compacted on the device (bzh_grep; with --index
 // bzh_grep_index).  Several strings (-e, --patterns) or --ignore-case: one compiled set, one pass (bzh_patset_create, bzh_*_patset*).
+// -E: the strings are regular expressions, compiled into one automaton that goes the set's way (bzh_regex_create).
 #include <cstdio>
 #include <cstdlib>
 #include <cerrno>
@@ -72,6 +73,9 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "                            <string> that is itself '-e', '--patterns' or '--ignore-case' is given by -e)\n"
             "     --patterns <file>      as -e for every line of <file> (not hex); an empty line is an error\n"
             "     --ignore-case          with --search or --grep: 'A'..'Z' and 'a'..'z' compare equal, nothing else does\n"
+            "  -E --regex                with --search or --grep: <string>, every -e and every line of --patterns are regular\n"
+            "                            expressions (a subset of Python's re on bytes; no anchors); a start reports its longest\n"
+            "                            match of at most 256 bytes; not with --hex\n"
             "                            With any of these three --search prints a third column: the number of the\n"
             "                            string, from 0 in the order given (of equal strings the first)\n"
             "     --keep      or   -k    keep the input file\n"
@@ -126,7 +130,7 @@ int main(int argc, char **argv)
     std::string in_path, out_path, index_path, mkindex_path, needle;
     std::vector<std::string> pats; // the strings of a set, in the order given (-e: hex with --hex; --patterns: as they stand)
     std::vector<bool> pat_hex;
-    bool use_set = false, ignore_case = false;
+    bool use_set = false, ignore_case = false, regex = false; // regex: every string is a regular expression (bzh_regex_create)
     auto read_patterns = [&](const std::string &path) {
         FILE *pf = fopen(path.c_str(), "rb");
         if (!pf) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + path + ": " + strerror(errno));
@@ -210,6 +214,7 @@ int main(int argc, char **argv)
             if (a == "-e") expect = PATTERN;             // (no <string> of its own: the set's strings follow)
             else if (a == "--patterns") expect = PATFILE;
             else if (a == "--ignore-case") ignore_case = true;
+            else if (a == "-E" || a == "--regex") regex = true;
             else needle = a, pats.push_back(a), pat_hex.push_back(true);
         } else if (expect == PATTERN) {
             pats.push_back(a), pat_hex.push_back(true);
@@ -248,6 +253,7 @@ int main(int argc, char **argv)
             else if (a == "--count") count_only = true;
             else if (a == "--patterns") expect = PATFILE;
             else if (a == "--ignore-case") ignore_case = true;
+            else if (a == "--regex") regex = true;
             else if (a == "--stdout") set_output("", true);
             else if (a == "--") expect = NOARGS;
             else die(ERR_ARGS, "Unrecognised argument " + a);
@@ -256,6 +262,8 @@ int main(int argc, char **argv)
                 set_input("", true);
             } else if (a == "-e") {
                 expect = PATTERN;
+            } else if (a == "-E") {
+                regex = true;
             } else {
                 for (size_t c = 1; c < a.size(); c++) {
                     const char f = a[c];
@@ -279,8 +287,9 @@ int main(int argc, char **argv)
     if (expect == GREP) die(ERR_ARGS, "Argument '--grep' requires a string");
     if (expect == PATTERN) die(ERR_ARGS, "Argument '-e' requires a string");
     if (expect == PATFILE) die(ERR_ARGS, "Argument '--patterns' requires a file path");
-    use_set = use_set || ignore_case;
-    if (use_set && !searching) die(ERR_ARGS, "'-e', '--patterns' and '--ignore-case' go with '--search' or '--grep'");
+    use_set = use_set || ignore_case || regex;
+    if (use_set && !searching) die(ERR_ARGS, "'-e', '-E', '--patterns' and '--ignore-case' go with '--search' or '--grep'");
+    if (regex && needle_hex) die(ERR_ARGS, "'-E' and '--hex' exclude each other: a regular expression writes a byte as \\xHH");
     if (use_set && pats.empty()) die(ERR_ARGS, "'--search' and '--grep' require a string, a '-e' or a '--patterns'");
     if (!have_in) die(ERR_ARGS, "An input must be specified");
     if ((needle_hex || count_only) && !searching) die(ERR_ARGS, "'--hex' and '--count' go with '--search' or '--grep'");
@@ -306,7 +315,8 @@ int main(int argc, char **argv)
         if (!use_set && (needle.empty() || needle.size() > BZH_SEARCH_MAX_PATTERN)) die(ERR_ARGS, "Argument '--search' requires a string of 1 to 256 bytes");
         for (size_t k = 0; use_set && k < pats.size(); k++) {
             if (needle_hex && pat_hex[k]) unhex(pats[k]);
-            if (pats[k].empty() || pats[k].size() > BZH_SEARCH_MAX_PATTERN) die(ERR_ARGS, "string " + std::to_string(k) + " does not hold 1 to 256 bytes");
+            if (regex ? pats[k].empty() || pats[k].size() > BZH_REGEX_MAX_EXPR : pats[k].empty() || pats[k].size() > BZH_SEARCH_MAX_PATTERN)
+                die(ERR_ARGS, "string " + std::to_string(k) + (regex ? " does not hold 1 to 4096 bytes" : " does not hold 1 to 256 bytes"));
         }
         if (use_set && pats.size() > BZH_PATSET_MAX_PATTERNS) die(ERR_ARGS, "more than 65536 strings");
     }
@@ -434,12 +444,16 @@ int main(int argc, char **argv)
             std::vector<const uint8_t *> pp;
             std::vector<size_t> pl;
             for (const std::string &q : pats) pp.push_back((const uint8_t *)q.data()), pl.push_back(q.size());
-            rs = bzh_patset_create(sctx, pp.data(), pl.data(), pp.size(), ignore_case ? BZH_PATSET_FOLD_ASCII : 0, &set);
+            if (regex) rs = bzh_regex_create(sctx, pp.data(), pl.data(), pp.size(), ignore_case ? BZH_REGEX_FOLD_ASCII : 0, 0, &set);
+            else rs = bzh_patset_create(sctx, pp.data(), pl.data(), pp.size(), ignore_case ? BZH_PATSET_FOLD_ASCII : 0, &set);
             if (rs != BZH_OK) {
                 const std::string msg = std::string(doing) + bzh_strerror(rs) + ": " + bzh_last_error(sctx);
                 bzh_destroy(sctx);
                 die(rs == BZH_E_ARG ? ERR_ARGS : ERR_OUTPUT, msg);
             }
+            bzh_regex_info ri;
+            if (regex && bzh_regex_get_info(set, &ri) == BZH_OK && ri.unbounded)
+                fprintf(stderr, "bnzhip: the expressions have matches longer than %d bytes: those are not found\n", BZH_REGEX_MAX_SPAN);
         }
         if (grepping) { // --grep: the selected lines come back compacted; a first try with a guess, a second with the exact rooms
             const unsigned gflags = invert ? BZH_GREP_INVERT : 0;

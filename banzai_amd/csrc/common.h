@@ -623,6 +623,9 @@ int scan_tiles(bzh_ctx *ctx, const char *who, uint64_t n, uint64_t *windows, uin
 struct bzh_patset {
     int device;
     bzh_patset_info info;
+    bool regex = false;    // regex.hip made it: the table is a DFA's (regex_plan.h), the matcher BzrMatcher
+    bzh_regex_info rinfo{};
+    uint32_t nterm = 0;    // of a regex: the terminal rows 1 .. nterm (a set's: info.distinct)
     uint8_t *d_mem; // cls[256], first[256], pat_no[distinct], table[states * classes]
     const uint8_t *d_cls;
     const uint16_t *d_first, *d_table;
@@ -630,6 +633,11 @@ struct bzh_patset {
 };
 struct BzmMatcher;
 BzmMatcher set_matcher(const bzh_patset *set, uint32_t delim, uint64_t lim);
+// regex.hip: a set that bzh_regex_create made, as the kernels take it -- its table staged in LDS (set->rinfo.in_lds) or not
+template <bool LDS_ROWS>
+struct BzrMatcher;
+template <bool LDS_ROWS>
+BzrMatcher<LDS_ROWS> regex_matcher(const bzh_patset *set, uint32_t delim, uint64_t lim);
 // search.hip: the search over decoded bytes in HBM.  A sink is what is looked for, where the hits go, and the walk over its windows
 // (search_plan.h): room() puts the carry in front of the window, window() runs the two passes and keeps the window's tail.
 struct SearchSink final : WindowSink {

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "grep_core.h"
 #include "patset_core.h"
+#include "regex_core.h"
 
 static_assert(sizeof(bzh_grep_entry) == 32 && sizeof(BzgEntry) == sizeof(bzh_grep_entry), "an entry is four words");
 static_assert(sizeof(BzgTile) == 32 && sizeof(BzgBase) == 24, "the tile tables");
@@ -110,11 +111,14 @@ __global__ void __launch_bounds__(BZF_THREADS) grep_scan(BzgTile *tile, uint32_t
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-// f(the sink's matcher): its pattern, or its set bounded by the text's end
+// f(the sink's matcher): its pattern, or its set or automaton bounded by the text's end
 template <class F>
 static void grep_matcher(const GrepSink &g, uint64_t n, F &&f)
 {
-    if (g.set) f(set_matcher(g.set, g.delim, n));
+    if (g.set && g.set->regex) {
+        if (g.set->rinfo.in_lds) f(regex_matcher<true>(g.set, g.delim, n));
+        else f(regex_matcher<false>(g.set, g.delim, n));
+    } else if (g.set) f(set_matcher(g.set, g.delim, n));
     else f(BzfOne{g.pat});
 }
 

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "search_core.h"
 #include "patset_core.h"
+#include "regex_core.h"
 
 static_assert(BZF_MAX_PATTERN == BZH_SEARCH_MAX_PATTERN, "search_core.h and bzhip.h name the same bound");
 static_assert(BZF_FRONT % 16 == 0 && BZF_FRONT >= BZF_MAX_PATTERN, "a window begins aligned, its carry in front of it");
@@ -139,11 +140,14 @@ int scan_tiles(bzh_ctx *ctx, const char *who, uint64_t n, uint64_t *windows, uin
 }
 
 // ---- host side: the search ---------------------------------------------------------------------------------------------------------
-// f(the sink's matcher): its pattern, or its set bounded by lim
+// f(the sink's matcher): its pattern, or its set or automaton bounded by lim
 template <class F>
 static void search_matcher(const SearchSink &s, uint64_t lim, F &&f)
 {
-    if (s.set) f(set_matcher(s.set, s.delim, lim));
+    if (s.set && s.set->regex) {
+        if (s.set->rinfo.in_lds) f(regex_matcher<true>(s.set, s.delim, lim));
+        else f(regex_matcher<false>(s.set, s.delim, lim));
+    } else if (s.set) f(set_matcher(s.set, s.delim, lim));
     else f(BzfOne{s.pat});
 }
 

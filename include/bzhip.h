@@ -747,6 +747,42 @@ BZH_API int bzh_grep_patset_index(bzh_ctx *ctx, const uint8_t *in, size_t n, con
                                   const bzh_sync_point *pts, size_t npts, const bzh_patset *set, unsigned flags, uint8_t delim,
                                   uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total);
 
+/* ---- regular expressions: grep -E, a DFA walked on the device ------------------------------------------------------------- */
+
+/* 1..BZH_PATSET_MAX_PATTERNS expressions of 1..BZH_REGEX_MAX_EXPR bytes each are compiled on the host into ONE automaton for
+ * their union -- a DFA anchored at its start, in the shape of a set's trie -- which every start position of the text walks.  The
+ * syntax is a subset of Python's `re` on bytes: literal bytes; \\ \. \[ \] \( \) \| \* \+ \? \{ \} \^ \$ \- \/ \n \t \r \f \v \0
+ * \xHH and a backslash in front of any other ASCII byte that is no letter or digit; \d \D \w \W \s \S (ASCII); `.` (any byte but 0x0A; any byte with BZH_REGEX_DOTALL); [...] and [^...] with ranges;
+ * ( ) and (?: ), both plain grouping; | ; ? * + {m} {m,} {m,n}.  Anchors, \b, backreferences, lookaround, lazy and possessive
+ * quantifiers, named groups, inline flags, a { that opens no well-formed bound, a bound above 256, an unbalanced bracket, an
+ * expression that matches the empty string and one whose shortest match exceeds max_span are refused with BZH_E_ARG, the
+ * message naming the expression's number and the byte.  So is an automaton above 65,536 NFA positions or 65,535 DFA states.
+ * With BZH_REGEX_FOLD_ASCII 'A'..'Z' and 'a'..'z' compare equal, in literals and in classes (re.IGNORECASE on bytes).
+ *
+ * The result is a bzh_patset: every bzh_search_patset* and bzh_grep_patset* call takes it unchanged, bzh_patset_get_info fills
+ * patterns = distinct = the number of expressions, bzh_patset_destroy frees it.  THE RULE: a hit is a start o at which some
+ * expression matches out[o .. o + L) for some 1 <= L <= max_span (and o + L <= the end of the text or of the wanted range).  A
+ * start yields exactly ONE bzh_set_hit: len is the LONGEST such L, pattern the lowest-numbered expression that matches exactly
+ * that length.  Overlapping starts are all hits.  A match longer than max_span is not found; `unbounded` says that the
+ * expressions have such matches.  BZH_REGEX_NO_LDS keeps the table out of LDS (in_lds 0): for measurements. */
+enum { BZH_REGEX_FOLD_ASCII = 1, BZH_REGEX_DOTALL = 2, BZH_REGEX_NO_LDS = 4 };
+#define BZH_REGEX_MAX_SPAN 256      /* = BZH_SEARCH_MAX_PATTERN: the tile's halo and the carry stay as they are */
+#define BZH_REGEX_MAX_EXPR 4096
+typedef struct {
+    uint64_t expressions;
+    uint32_t min_len, max_len;     /* the shortest match; min(the longest, max_span) */
+    uint32_t states, classes;      /* rows (the root included) and columns of the table */
+    uint32_t unbounded, in_lds;    /* some match may exceed max_span; every workgroup stages the table into LDS */
+    uint64_t table_bytes;
+} bzh_regex_info;    /* 40 bytes */
+BZH_API int bzh_regex_create(bzh_ctx *ctx, const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags,
+                             uint32_t max_span /* 1..256, 0 = 256 */, bzh_patset **out);
+BZH_API int bzh_regex_get_info(const bzh_patset *set, bzh_regex_info *out); /* BZH_E_ARG for a set of plain strings */
+/* The compile alone: pure host, no context, no GPU.  BZH_OK and *info (null allowed), or BZH_E_ARG and the reason in
+ * err[0 .. errn) (null allowed). */
+BZH_API int bzh_regex_check(const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags, uint32_t max_span,
+                            bzh_regex_info *info, char *err, size_t errn);
+
 /* ---- the encoder writes the index of its own stream: no decode pass to rediscover what it held -------------------------- */
 
 /* bzh_encode_device that also returns the index of the stream it writes: the entries bzh_decode_index would return for
