@@ -5,7 +5,8 @@
 //   entropy  : one wavefront per candidate: header, tables, symbols -> last column           (decode_block_kernel, decode_core.h)
 //   chain    : the host walks from block end to block start; candidates inside a payload drop out
 //   unbwt    : the inverse transform of the batch                                            (unbwt_run, bwt.hip)
-//   unrle    : inverse RLE1 -- roles by a scan of state maps, sizes, then the expansion      (unrle_maps / unrle_walk)
+//   unrle    : inverse RLE1 -- roles by a scan of state maps, sizes, then the expansion      (unrle_maps / unrle_walk; one tile
+//              front, ur_enter / ur_place, under every unrle_* kernel of this file)
 //   crc      : block CRCs over the output ranges (rle1.hip), folded per stream on the host
 // Random access (bzh_decode_index*, bzh_decode_range*): the index is the chain walk with no output, every block's CRC taken
 // from the bytes behind the inverse BWT (unrle_crc); a range decodes the blocks its index entries name, no scan and no walk,
@@ -296,6 +297,9 @@ __global__ void __launch_bounds__(64) decode_segment_kernel(const uint8_t *in, u
 // ---- inverse RLE1 ----------------------------------------------------------------------------------------------
 // A tile = 4096 bytes of a block, 16 a thread.  unrle_maps: the tile's state map.  unrle_walk<false>: the tile's entry state
 // (the maps of the tiles before it, composed) and its output bytes; <true>: the expansion, at offsets the host has summed.
+// Every unrle_* kernel behind unrle_maps enters its tile through one front -- ur_enter: the load, the scan of the threads' maps,
+// the thread's state; ur_place on top of it for the three that store bytes: the thread's first position and the one bound on
+// every position -- and what a thread does with its 16 bytes is decode_core.h's text (bzd_ur_*), which the host harnesses run too.
 constexpr uint32_t UR_THREADS = 256, UR_ITEMS = 16, UR_TILE = UR_THREADS * UR_ITEMS, UR_STAGE = 8192;
 
 struct UrArgs {
@@ -314,7 +318,6 @@ struct UrBytes {
     uint32_t w[4];
     uint32_t cnt;  // bytes of this thread inside the block
     uint32_t prev; // the byte before them (256: none)
-    __device__ __forceinline__ uint32_t at(int k) const { return (w[k >> 2] >> (8 * (k & 3))) & 255u; }
 };
 
 __device__ __forceinline__ UrBytes ur_load(const uint8_t *x, uint32_t n, uint32_t i0)
@@ -332,23 +335,6 @@ __device__ __forceinline__ UrBytes ur_load(const uint8_t *x, uint32_t n, uint32_
         if (i0) u.prev = x[i0 - 1];
     }
     return u;
-}
-
-__device__ __forceinline__ uint32_t ur_thread_map(const UrBytes &u)
-{
-    uint32_t st[5] = {0, 1, 2, 3, 4};
-    uint32_t prev = u.prev;
-#pragma unroll
-    for (int k = 0; k < (int)UR_ITEMS; k++) {
-        if ((uint32_t)k < u.cnt) {
-            const uint32_t c = u.at(k);
-            const bool eq = c == prev;
-#pragma unroll
-            for (int s = 0; s < 5; s++) st[s] = bzd_rl_step(st[s], eq);
-            prev = c;
-        }
-    }
-    return st[0] | st[1] << 3 | st[2] << 6 | st[3] << 9 | st[4] << 12;
 }
 
 // exclusive scan of state maps over the workgroup (composition in thread order); *total = all of them.  lds: 4 words.
@@ -375,13 +361,61 @@ __device__ __forceinline__ uint32_t ur_scan(uint32_t m, uint32_t *lds, uint32_t 
     return bzd_rl_compose(carry, ex);
 }
 
+static_assert(UR_ITEMS == BZD_UR_ITEMS, "decode_core.h walks the same 16 bytes a thread");
+
+// The tile front of every kernel that is handed its entry state.  Thread threadIdx.x of tile t of slot b, a block of n bytes:
+// its 16 bytes, the scan of the threads' maps, *s = the state the thread's first byte is met in.  Slot, tile and n are the
+// caller's (a grid cell, or a query that the caller has bounded), and every read lies below n inside the slot's stride.
+__device__ __forceinline__ UrBytes ur_enter(const UrArgs &a, uint32_t n, uint32_t b, uint32_t t, uint32_t entry, uint32_t *lds, uint32_t *s)
+{
+    const UrBytes u = ur_load(a.x + (size_t)b * a.S, n, t * UR_TILE + threadIdx.x * UR_ITEMS);
+    uint32_t total;
+    const uint32_t ex = ur_scan(bzd_ur_map(u.w, u.cnt, u.prev), lds, &total);
+    *s = bzd_rl_apply(ex, entry);
+    return u;
+}
+
+// The front of the kernels that place bytes: ur_enter, then where this thread's bytes begin inside the tile's expansion.
+// `lim` bounds every position a caller stores at, in LDS or in global memory: it is the smaller of tile_total -- a.tout, what
+// unrle_walk<false> summed over these same bytes and the host laid the output out by, known before anything is loaded and the
+// one that decides staged or not -- and this walk's own sum.  The two are equal by construction; clipping to both keeps every
+// position below both without relying on that.  (unrle_walk<false>, which makes a.tout, passes no bound: lim is its sum.)
+struct UrPlace {
+    UrBytes u;
+    uint32_t s, s_end; // the state the thread's bytes are entered in, and the one behind them
+    uint32_t o0, lim;
+};
+
+__device__ __forceinline__ UrPlace ur_place(const UrArgs &a, uint32_t n, uint32_t b, uint32_t t, uint32_t entry, uint32_t tile_total, uint32_t *lds)
+{
+    UrPlace p;
+    p.u = ur_enter(a, n, b, t, entry, lds, &p.s);
+    uint32_t summed;
+    p.o0 = block_excl_add(bzd_ur_size(p.u.w, p.u.cnt, p.u.prev, p.s, &p.s_end), lds, &summed);
+    p.lim = min(tile_total, summed);
+    return p;
+}
+
+// n bytes of LDS to global memory by the `nth` threads of which this is thread `tid`: aligned words, the ragged edges byte by byte
+__device__ __forceinline__ void ur_copy_out(uint8_t *g, const uint8_t *s, uint32_t n, uint32_t tid, uint32_t nth)
+{
+    const uint32_t head = min(n, (uint32_t)((0 - (uintptr_t)g) & 3u));
+    const uint32_t words = (n - head) / 4, tail0 = head + words * 4;
+    if (tid < head) g[tid] = s[tid];
+    for (uint32_t i = tid; i < words; i += nth) {
+        const uint8_t *sp = s + head + 4 * i;
+        *reinterpret_cast<uint32_t *>(g + head + 4 * i) = (uint32_t)sp[0] | (uint32_t)sp[1] << 8 | (uint32_t)sp[2] << 16 | (uint32_t)sp[3] << 24;
+    }
+    if (tail0 + tid < n) g[tail0 + tid] = s[tail0 + tid];
+}
+
 __global__ void __launch_bounds__(UR_THREADS) unrle_maps(UrArgs a)
 {
     __shared__ uint32_t lds[4];
     const uint32_t b = a.slots[blockIdx.y], t = blockIdx.x, n = a.n[b];
     const UrBytes u = ur_load(a.x + (size_t)b * a.S, n, t * UR_TILE + threadIdx.x * UR_ITEMS);
     uint32_t total;
-    (void)ur_scan(ur_thread_map(u), lds, &total);
+    (void)ur_scan(bzd_ur_map(u.w, u.cnt, u.prev), lds, &total);
     if (threadIdx.x == 0) a.tmap[(size_t)b * a.T + t] = total;
 }
 
@@ -392,57 +426,45 @@ __global__ void __launch_bounds__(UR_THREADS) unrle_walk(UrArgs a)
     __shared__ uint8_t stage[EXPAND ? UR_STAGE : 4];
     const uint32_t b = a.slots[blockIdx.y], t = blockIdx.x, n = a.n[b];
     const size_t ti = (size_t)b * a.T + t;
-    uint32_t entry, total;
+    uint32_t entry, tile_total = 0xFFFFFFFFu;
     if (EXPAND) {
         entry = a.tstate[ti];
+        tile_total = a.tout[ti];
+        if (tile_total == 0) return;
     } else { // the tiles before this one, a thread each (T <= UR_THREADS: dec_ws's static_assert)
+        uint32_t total;
         const uint32_t m = threadIdx.x < t ? a.tmap[(size_t)b * a.T + threadIdx.x] : BZD_RL_ID;
         (void)ur_scan(m, lds, &total);
         entry = bzd_rl_apply(total, 0);
         if (threadIdx.x == 0) a.tstate[ti] = entry;
     }
-    const uint32_t i0 = t * UR_TILE + threadIdx.x * UR_ITEMS;
-    const UrBytes u = ur_load(a.x + (size_t)b * a.S, n, i0);
-    const uint32_t ex = ur_scan(ur_thread_map(u), lds, &total);
-    uint32_t s = bzd_rl_apply(ex, entry);
-    uint32_t outn = 0, prev = u.prev;
-#pragma unroll
-    for (int k = 0; k < (int)UR_ITEMS; k++) {
-        if ((uint32_t)k < u.cnt) {
-            const uint32_t c = u.at(k);
-            outn += s == 4 ? c : 1u;
-            s = bzd_rl_step(s, c == prev);
-            prev = c;
-        }
-    }
-    uint32_t tile_total;
-    const uint32_t o0 = block_excl_add(outn, lds, &tile_total);
+    const UrPlace p = ur_place(a, n, b, t, entry, tile_total, lds);
+    const UrBytes &u = p.u;
     if (!EXPAND) {
-        if (threadIdx.x == 0) a.tout[ti] = tile_total;
-        if (u.cnt && i0 + u.cnt == n) a.endstate[b] = s;
+        if (threadIdx.x == 0) a.tout[ti] = p.lim;
+        if (u.cnt && t * UR_TILE + threadIdx.x * UR_ITEMS + u.cnt == n) a.endstate[b] = p.s_end;
         return;
     }
-    if (tile_total == 0) return;
     const bool staged = tile_total <= UR_STAGE;
     uint8_t *g = a.out + a.obase[blockIdx.y] + a.toff[ti];
-    uint32_t o = o0;
-    s = bzd_rl_apply(ex, entry);
-    prev = u.prev;
-    // (every offset is checked against the tile's total, which is the sum the host laid the output out by)
+    // A loop of its own, a byte and a test at a time, where unrle_walk_win and unrle_walk_pieces go through bzd_ur_emit.  On text,
+    // where nearly every byte stands for itself, bzd_ur_emit's loop per byte of input made this kernel 8 % slower and the stage
+    // 3 %; on long runs bzd_ur_emit is five times faster here (profiles/r27_unrle_front_ab.txt has both).
+    uint32_t o = p.o0, s = p.s, prev = u.prev;
 #pragma unroll
     for (int k = 0; k < (int)UR_ITEMS; k++) {
         if ((uint32_t)k < u.cnt) {
-            const uint32_t c = u.at(k);
+            const uint32_t c = bzd_ur_at(u.w, k);
             if (s == 4) {
                 for (uint32_t q = 0; q < c; q++, o++)
-                    if (o < tile_total) {
+                    if (o < p.lim) {
                         if (staged)
                             stage[o] = (uint8_t)prev;
                         else
                             g[o] = (uint8_t)prev;
                     }
             } else {
-                if (o < tile_total) {
+                if (o < p.lim) {
                     if (staged)
                         stage[o] = (uint8_t)c;
                     else
@@ -456,15 +478,7 @@ __global__ void __launch_bounds__(UR_THREADS) unrle_walk(UrArgs a)
     }
     if (!staged) return;
     __syncthreads();
-    // the staged tile goes out in aligned words, its ragged edges byte by byte
-    const uint32_t head = min(tile_total, (uint32_t)((0 - (uintptr_t)g) & 3u));
-    const uint32_t words = (tile_total - head) / 4, tail0 = head + words * 4;
-    if (threadIdx.x < head) g[threadIdx.x] = stage[threadIdx.x];
-    for (uint32_t i = threadIdx.x; i < words; i += UR_THREADS) {
-        const uint8_t *sp = stage + head + 4 * i;
-        *reinterpret_cast<uint32_t *>(g + head + 4 * i) = (uint32_t)sp[0] | (uint32_t)sp[1] << 8 | (uint32_t)sp[2] << 16 | (uint32_t)sp[3] << 24;
-    }
-    if (tail0 + threadIdx.x < tile_total) g[tail0 + threadIdx.x] = stage[tail0 + threadIdx.x];
+    ur_copy_out(g, stage, p.lim, threadIdx.x, UR_THREADS);
 }
 
 // ---- random access: the expansion clipped to a window, and its CRC without the expansion -------------------------------
@@ -475,8 +489,6 @@ struct UwArgs {
     uint32_t *acc, *crc;       // [K] CRC accumulator (zeroed by the host), finished CRC
     const CrcTables *ct;
 };
-
-static_assert(UR_ITEMS == BZD_UR_ITEMS, "decode_core.h walks the same 16 bytes a thread");
 
 // unrle_walk<true> for a block of which only [wlo, whi) is wanted.  Not one byte outside the window is stored: the staged tile
 // is copied out from the window's first byte to its last, the byte stores of a tile too large to stage are clipped run by run.
@@ -493,47 +505,17 @@ __global__ void __launch_bounds__(UR_THREADS) unrle_walk_win(UrArgs a, UwArgs wa
     bzd_clip(toff, tile_total, lo, hi, &ca, &cb);
     if (ca == cb) return; // the tile lies outside the window
     const uint32_t tlo = ca - toff, thi = cb - toff; // the window inside the tile
-    const uint32_t entry = a.tstate[ti];
-    const UrBytes u = ur_load(a.x + (size_t)b * a.S, n, t * UR_TILE + threadIdx.x * UR_ITEMS);
-    uint32_t total;
-    const uint32_t ex = ur_scan(ur_thread_map(u), lds, &total);
-    const uint32_t s = bzd_rl_apply(ex, entry);
-    uint32_t outn = 0, sw = s, prev = u.prev;
-#pragma unroll
-    for (int k = 0; k < (int)UR_ITEMS; k++) {
-        if ((uint32_t)k < u.cnt) {
-            const uint32_t c = u.at(k);
-            outn += sw == 4 ? c : 1u;
-            sw = bzd_rl_step(sw, c == prev);
-            prev = c;
-        }
-    }
-    uint32_t summed;
-    const uint32_t o0 = block_excl_add(outn, lds, &summed);
-    // (tile_total is a.tout, what unrle_walk<false> summed over these same bytes and the host laid the output out by: it is
-    // needed before anything is loaded, for the early return, and it decides staged or not.  `summed` is this walk's own sum and
-    // equals it by construction; clipping to it as well keeps every position below both without relying on that.)
-    const uint32_t whi_t = min(thi, summed);
+    const UrPlace p = ur_place(a, n, b, t, a.tstate[ti], tile_total, lds);
+    const UrBytes &u = p.u;
+    const uint32_t whi_t = min(thi, p.lim);
     uint8_t *g = reinterpret_cast<uint8_t *>((uintptr_t)a.out + (uintptr_t)(wa.wbase[blockIdx.y] + (int64_t)toff));
     if (tile_total > UR_STAGE) {
-        bzd_ur_emit(u.w, u.cnt, u.prev, s, o0, tlo, whi_t, [&](uint32_t q, uint8_t v) { g[q] = v; });
+        bzd_ur_emit(u.w, u.cnt, u.prev, p.s, p.o0, tlo, whi_t, [&](uint32_t q, uint8_t v) { g[q] = v; });
         return;
     }
-    bzd_ur_emit(u.w, u.cnt, u.prev, s, o0, tlo, whi_t, [&](uint32_t q, uint8_t v) { stage[q] = v; });
+    bzd_ur_emit(u.w, u.cnt, u.prev, p.s, p.o0, tlo, whi_t, [&](uint32_t q, uint8_t v) { stage[q] = v; });
     __syncthreads();
-    if (whi_t <= tlo) return;
-    // stage[tlo, whi_t) goes out in aligned words, its ragged edges byte by byte
-    uint8_t *gw = g + tlo;
-    const uint8_t *sw0 = stage + tlo;
-    const uint32_t len = whi_t - tlo;
-    const uint32_t head = min(len, (uint32_t)((0 - (uintptr_t)gw) & 3u));
-    const uint32_t words = (len - head) / 4, tail0 = head + words * 4;
-    if (threadIdx.x < head) gw[threadIdx.x] = sw0[threadIdx.x];
-    for (uint32_t i = threadIdx.x; i < words; i += UR_THREADS) {
-        const uint8_t *sp = sw0 + head + 4 * i;
-        *reinterpret_cast<uint32_t *>(gw + head + 4 * i) = (uint32_t)sp[0] | (uint32_t)sp[1] << 8 | (uint32_t)sp[2] << 16 | (uint32_t)sp[3] << 24;
-    }
-    if (tail0 + threadIdx.x < len) gw[tail0 + threadIdx.x] = sw0[tail0 + threadIdx.x];
+    if (whi_t > tlo) ur_copy_out(g + tlo, stage + tlo, whi_t - tlo, threadIdx.x, UR_THREADS);
 }
 
 // ---- many ranges: one expansion of a tile, many destinations --------------------------------------------------------------
@@ -543,19 +525,6 @@ struct UpArgs {
     uint32_t Tp, nrefs;
     uint64_t out_total;         // bytes of `out`: no store at or behind it
 };
-
-// n bytes of LDS to global memory by the `nth` threads of which this is thread `tid`: aligned words, the ragged edges byte by byte
-__device__ __forceinline__ void ur_copy_out(uint8_t *g, const uint8_t *s, uint32_t n, uint32_t tid, uint32_t nth)
-{
-    const uint32_t head = min(n, (uint32_t)((0 - (uintptr_t)g) & 3u));
-    const uint32_t words = (n - head) / 4, tail0 = head + words * 4;
-    if (tid < head) g[tid] = s[tid];
-    for (uint32_t i = tid; i < words; i += nth) {
-        const uint8_t *sp = s + head + 4 * i;
-        *reinterpret_cast<uint32_t *>(g + head + 4 * i) = (uint32_t)sp[0] | (uint32_t)sp[1] << 8 | (uint32_t)sp[2] << 16 | (uint32_t)sp[3] << 24;
-    }
-    if (tail0 + tid < n) g[tail0 + tid] = s[tail0 + tid];
-}
 
 // unrle_walk_win for a block of which several pieces are wanted, each somewhere else: the tile is loaded, scanned and expanded
 // once, then stage[piece] goes to every piece that meets the tile -- a wavefront a piece where there are many, the workgroup
@@ -572,24 +541,10 @@ __global__ void __launch_bounds__(UR_THREADS) unrle_walk_pieces(UrArgs a, UpArgs
     const size_t cell = (size_t)blockIdx.y * pa.Tp + t;
     const uint32_t f1 = min(pa.tile_first[cell + 1], pa.nrefs), f0 = min(pa.tile_first[cell], f1);
     if (f0 == f1) return; // no piece meets the tile
-    const uint32_t toff = a.toff[ti], entry = a.tstate[ti];
-    const UrBytes u = ur_load(a.x + (size_t)b * a.S, n, t * UR_TILE + threadIdx.x * UR_ITEMS);
-    uint32_t total;
-    const uint32_t ex = ur_scan(ur_thread_map(u), lds, &total);
-    const uint32_t s = bzd_rl_apply(ex, entry);
-    uint32_t outn = 0, sw = s, prev = u.prev;
-#pragma unroll
-    for (int k = 0; k < (int)UR_ITEMS; k++) {
-        if ((uint32_t)k < u.cnt) {
-            const uint32_t c = u.at(k);
-            outn += sw == 4 ? c : 1u;
-            sw = bzd_rl_step(sw, c == prev);
-            prev = c;
-        }
-    }
-    uint32_t summed;
-    const uint32_t o0 = block_excl_add(outn, lds, &summed);
-    const uint32_t lim = min(tile_total, summed); // (equal by construction, as in unrle_walk_win)
+    const uint32_t toff = a.toff[ti];
+    const UrPlace p = ur_place(a, n, b, t, a.tstate[ti], tile_total, lds);
+    const UrBytes &u = p.u;
+    const uint32_t s = p.s, o0 = p.o0, lim = p.lim;
     const bool staged = tile_total <= UR_STAGE;
     if (staged) {
         bzd_ur_emit(u.w, u.cnt, u.prev, s, o0, 0u, lim, [&](uint32_t q, uint8_t v) { stage[q] = v; });
@@ -636,13 +591,9 @@ __global__ void __launch_bounds__(UR_THREADS) unrle_crc(UrArgs a, UwArgs wa)
         for (int k = 0; k < 8; k++) c = (c << 1) ^ ((c >> 31) ? CRC_POLY : 0u);
         tab[threadIdx.x] = c;
     }
-    const uint32_t entry = a.tstate[ti];
-    const UrBytes u = ur_load(a.x + (size_t)b * a.S, n, t * UR_TILE + threadIdx.x * UR_ITEMS);
-    uint32_t total;
-    const uint32_t ex = ur_scan(ur_thread_map(u), lds, &total); // (its barriers also publish the table)
-    uint32_t outn;
-    uint32_t crc = bzd_ur_fold(tab, u.w, u.cnt, u.prev, bzd_rl_apply(ex, entry), &outn);
-    uint32_t summed;
+    uint32_t s, outn, summed;
+    const UrBytes u = ur_enter(a, n, b, t, a.tstate[ti], lds, &s); // (its barriers also publish the table)
+    uint32_t crc = bzd_ur_fold(tab, u.w, u.cnt, u.prev, s, &outn);
     const uint32_t o0 = block_excl_add(outn, lds, &summed);
     if (outn) crc = gf_mul(crc, gf_pow_x_serial(wa.ct->pow2 + 3, summed - o0 - outn, 20)); // x^(8 m), m < 4096 * 255 < 2^20
 #pragma unroll
@@ -680,13 +631,10 @@ __global__ void __launch_bounds__(UR_THREADS) unrle_count(UrArgs a, UcArgs ca)
     __shared__ uint32_t wred[UR_THREADS / 64];
     const uint32_t b = a.slots[blockIdx.y], t = blockIdx.x, n = a.n[b];
     const size_t ti = (size_t)b * a.T + t;
-    const uint32_t entry = a.tstate[ti], i0 = t * UR_TILE + threadIdx.x * UR_ITEMS;
-    const UrBytes u = ur_load(a.x + (size_t)b * a.S, n, i0);
-    uint32_t total;
-    const uint32_t ex = ur_scan(ur_thread_map(u), lds, &total);
-    uint32_t outn, last = 256;
-    uint32_t d = bzd_ur_count(u.w, u.cnt, u.prev, bzd_rl_apply(ex, entry), ca.delim, &outn, &last);
-    if (u.cnt && i0 + u.cnt == n) ca.last[b] = last == ca.delim; // (one thread of one tile holds the block's last byte)
+    uint32_t s0, outn, last = 256;
+    const UrBytes u = ur_enter(a, n, b, t, a.tstate[ti], lds, &s0);
+    uint32_t d = bzd_ur_count(u.w, u.cnt, u.prev, s0, ca.delim, &outn, &last);
+    if (u.cnt && t * UR_TILE + threadIdx.x * UR_ITEMS + u.cnt == n) ca.last[b] = last == ca.delim; // (one thread of one tile holds the block's last byte)
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) d += __shfl_xor(d, s, 64);
     if ((threadIdx.x & 63u) == 0) wred[threadIdx.x >> 6] = d;
@@ -719,12 +667,8 @@ __global__ void __launch_bounds__(UR_THREADS) unrle_select(UrArgs a, UsArgs sa)
     }
     const uint32_t b = q.slot, n = min(a.n[b], a.S);
     const size_t ti = (size_t)b * a.T + q.tile;
-    const uint32_t entry = a.tstate[ti];
-    const UrBytes u = ur_load(a.x + (size_t)b * a.S, n, q.tile * UR_TILE + threadIdx.x * UR_ITEMS);
-    uint32_t total;
-    const uint32_t ex = ur_scan(ur_thread_map(u), lds, &total); // (its barriers also publish `found`)
-    const uint32_t s = bzd_rl_apply(ex, entry);
-    uint32_t outn, last = 256, dsum, osum;
+    uint32_t s, outn, last = 256, dsum, osum;
+    const UrBytes u = ur_enter(a, n, b, q.tile, a.tstate[ti], lds, &s); // (its barriers also publish `found`)
     const uint32_t d = bzd_ur_count(u.w, u.cnt, u.prev, s, sa.delim, &outn, &last);
     const uint32_t d0 = block_excl_add(d, lds, &dsum);
     const uint32_t o0 = block_excl_add(outn, lds, &osum);

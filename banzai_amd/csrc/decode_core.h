@@ -545,6 +545,46 @@ BZD_FN uint32_t bzd_rl_step(uint32_t s, bool eq) { return s == 4 ? 0u : (eq && s
 constexpr uint32_t BZD_UR_ITEMS = 16;
 BZD_FN uint32_t bzd_ur_at(const uint32_t *w, uint32_t k) { return (w[k >> 2] >> (8 * (k & 3))) & 255u; }
 
+// The stretch as a map of states: where each of the five states it could be entered in has got to behind its last byte.
+BZD_FN uint32_t bzd_ur_map(const uint32_t *w, uint32_t cnt, uint32_t prev)
+{
+    uint32_t st[5] = {0, 1, 2, 3, 4};
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t k = 0; k < BZD_UR_ITEMS; k++) {
+        if (k < cnt) {
+            const uint32_t c = bzd_ur_at(w, k);
+            const bool eq = c == prev;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int q = 0; q < 5; q++) st[q] = bzd_rl_step(st[q], eq);
+            prev = c;
+        }
+    }
+    return st[0] | st[1] << 3 | st[2] << 6 | st[3] << 9 | st[4] << 12;
+}
+
+// How many bytes the stretch expands to; *s_end = the state behind its last byte.
+BZD_FN uint32_t bzd_ur_size(const uint32_t *w, uint32_t cnt, uint32_t prev, uint32_t s, uint32_t *s_end)
+{
+    uint32_t o = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t k = 0; k < BZD_UR_ITEMS; k++) {
+        if (k < cnt) {
+            const uint32_t c = bzd_ur_at(w, k);
+            o += s == 4 ? c : 1u;
+            s = bzd_rl_step(s, c == prev);
+            prev = c;
+        }
+    }
+    *s_end = s;
+    return o;
+}
+
 // The CRC register (CRC-32/BZIP2 without its init and final XOR: the polynomial of the bytes alone) over what the stretch
 // expands to, *outn = how many bytes that is.  tab[v] = v * x^32 mod P.  Nothing is written: at most 16 * 255 table steps.
 BZD_FN uint32_t bzd_ur_fold(const uint32_t *tab, const uint32_t *w, uint32_t cnt, uint32_t prev, uint32_t s, uint32_t *outn)

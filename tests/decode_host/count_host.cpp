@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../banzai_amd/csrc/decode_core.h"
+#include "unrle_layout.h"
 
 static uint64_t rng_state;
 static uint64_t rnd()
@@ -33,64 +34,39 @@ static uint64_t below(uint64_t n) { return n ? rnd() % n : 0; }
         }                                                \
     } while (0)
 
-constexpr uint32_t THREADS = 256, ITEMS = BZD_UR_ITEMS, TILE = THREADS * ITEMS, NONE = 0xFFFFFFFFu;
-
-struct Thread { // what ur_load and the scan hand a thread
-    uint32_t w[4], cnt, prev, s;
-};
+constexpr uint32_t NONE = 0xFFFFFFFFu;
 
 // The block as the kernels see it; returns the delimiters the model counted, and checks every tile, every k and the last-byte flag.
 static uint64_t block_case(const std::vector<uint8_t> &x, uint32_t delim, const char *name)
 {
     const uint32_t n = (uint32_t)x.size();
     CHECK(n >= 1, "%s: an empty block", name);
-    // the serial expansion: libbz2's rule, byte by byte; where every byte behind the inverse BWT begins in the output
-    std::vector<uint8_t> out;
-    std::vector<uint32_t> state(n), begin(n + 1);
-    {
-        uint32_t s = 0, prev = 256;
-        for (uint32_t i = 0; i < n; i++) {
-            state[i] = s;
-            begin[i] = (uint32_t)out.size();
-            if (s == 4)
-                out.insert(out.end(), x[i], (uint8_t)prev);
-            else
-                out.push_back(x[i]);
-            s = bzd_rl_step(s, x[i] == prev);
-            prev = x[i];
-        }
-        begin[n] = (uint32_t)out.size();
-        CHECK(s != 4, "%s: the case ends in four equal bytes without a count", name);
-    }
+    const Serial truth = expand(x.data(), n);
+    const std::vector<uint8_t> &out = truth.out;
+    const std::vector<uint32_t> &begin = truth.begin;
+    CHECK(truth.end != 4, "%s: the case ends in four equal bytes without a count", name);
     std::vector<uint32_t> dpos; // the positions of the delimiters
     for (uint32_t p = 0; p < out.size(); p++)
         if (out[p] == delim) dpos.push_back(p);
 
-    const uint32_t tn = (n + TILE - 1) / TILE;
+    std::vector<Tile> tiles;
+    uint32_t bsize;
+    CHECK(lay_out(x.data(), n, tiles, &bsize) == truth.end && bsize == out.size(), "%s: the layout's end state or size", name);
+    const uint32_t tn = (uint32_t)tiles.size();
     uint64_t counted = 0;
     size_t dnext = 0; // delimiters of the tiles before this one
     uint32_t last_flag = NONE;
     for (uint32_t t = 0; t < tn; t++) {
-        std::vector<Thread> th(THREADS);
-        for (uint32_t j = 0; j < THREADS; j++) {
-            const uint32_t i0 = t * TILE + j * ITEMS;
-            Thread &u = th[j];
-            u.cnt = i0 < n ? (n - i0 < ITEMS ? n - i0 : ITEMS) : 0;
-            u.prev = 256;
-            u.s = 0;
-            u.w[0] = u.w[1] = u.w[2] = u.w[3] = 0;
-            for (uint32_t k = 0; k < u.cnt; k++) u.w[k >> 2] |= (uint32_t)x[i0 + k] << (8 * (k & 3)); // (no byte behind the block is read)
-            if (u.cnt) {
-                if (i0) u.prev = x[i0 - 1];
-                u.s = state[i0];
-            }
-        }
+        const std::vector<Thread> &th = tiles[t].th; // what ur_load and the scan hand the threads
+        CHECK(th.size() == THREADS, "%s: tile %u has %zu threads", name, t, th.size());
+        for (uint32_t j = 0; j < THREADS; j++)
+            if (th[j].cnt) CHECK(th[j].state == truth.state[t * TILE + j * ITEMS], "%s: tile %u thread %u is entered in state %u", name, t, j, th[j].state);
         // unrle_count: a count a thread, summed; the thread that holds the block's last byte writes the flag
         std::vector<uint32_t> d(THREADS), o(THREADS);
         uint32_t tcount = 0, tout = 0;
         for (uint32_t j = 0; j < THREADS; j++) {
             uint32_t last = 256;
-            d[j] = bzd_ur_count(th[j].w, th[j].cnt, th[j].prev, th[j].s, delim, &o[j], &last);
+            d[j] = bzd_ur_count(th[j].w, th[j].cnt, th[j].prev, th[j].state, delim, &o[j], &last);
             const uint32_t i0 = t * TILE + j * ITEMS;
             if (th[j].cnt && i0 + th[j].cnt == n) {
                 CHECK(last_flag == NONE, "%s: two threads hold the last byte", name);
@@ -101,6 +77,7 @@ static uint64_t block_case(const std::vector<uint8_t> &x, uint32_t delim, const 
             tout += o[j];
         }
         const uint32_t toff = begin[t * TILE];
+        CHECK(tiles[t].toff == toff && tiles[t].total == tout, "%s: tile %u is laid out at %u with %u bytes", name, t, tiles[t].toff, tiles[t].total);
         uint32_t want = 0;
         for (uint32_t p = toff; p < toff + tout; p++) want += out[p] == delim;
         CHECK(tcount == want, "%s: tile %u counts %u delimiters, the expansion holds %u", name, t, tcount, want);
@@ -109,7 +86,7 @@ static uint64_t block_case(const std::vector<uint8_t> &x, uint32_t delim, const 
             uint32_t found = NONE, d0 = 0, o0 = 0, hits = 0;
             for (uint32_t j = 0; j < THREADS; j++) {
                 if (k > d0 && k - d0 <= d[j]) {
-                    const uint32_t at = bzd_ur_select(th[j].w, th[j].cnt, th[j].prev, th[j].s, delim, k - d0);
+                    const uint32_t at = bzd_ur_select(th[j].w, th[j].cnt, th[j].prev, th[j].state, delim, k - d0);
                     CHECK(at != NONE && at < o[j], "%s: tile %u thread %u does not find its delimiter %u", name, t, j, k - d0);
                     found = toff + o0 + at;
                     hits++;
@@ -126,8 +103,8 @@ static uint64_t block_case(const std::vector<uint8_t> &x, uint32_t delim, const 
         }
         // a thread asked for more than it holds, or for nothing, says so
         for (uint32_t j = 0; j < THREADS; j += 37) {
-            CHECK(bzd_ur_select(th[j].w, th[j].cnt, th[j].prev, th[j].s, delim, d[j] + 1) == NONE, "%s: k beyond a thread's count", name);
-            CHECK(bzd_ur_select(th[j].w, th[j].cnt, th[j].prev, th[j].s, delim, 0) == NONE, "%s: k 0", name);
+            CHECK(bzd_ur_select(th[j].w, th[j].cnt, th[j].prev, th[j].state, delim, d[j] + 1) == NONE, "%s: k beyond a thread's count", name);
+            CHECK(bzd_ur_select(th[j].w, th[j].cnt, th[j].prev, th[j].state, delim, 0) == NONE, "%s: k 0", name);
         }
         dnext += tcount;
         counted += tcount;

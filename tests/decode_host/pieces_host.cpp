@@ -1,7 +1,7 @@
 // pieces_host.cpp -- what unrle_walk_pieces (banzai_amd/csrc/decode.hip) does with the tables bzp_pieces builds, as a CPU
 // program built with -fsanitize=address,undefined.  The kernel's per-thread text is decode_core.h's (bzd_ur_emit, bzd_piece_cut)
-// and the tables are decode_plan.h's; this file lays the threads out as the kernel does -- tiles of 4,096 bytes, 16 a thread,
-// entry states by composing state maps, offsets by prefix sums, a stage of 8,192 bytes -- and runs them one after the other:
+// and the tables are decode_plan.h's; the threads are laid out as the kernel lays them out (unrle_layout.h), with a stage of
+// 8,192 bytes, and run one after the other:
 // a tile that fits the stage is expanded into it once and copied to every piece that meets it, a larger one is emitted piece
 // by piece.  The stage and the output are heap buffers of exactly their size: a store outside either is a sanitizer report.
 //
@@ -15,8 +15,9 @@
 
 #include "../../include/bzhip.h"
 #include "../../banzai_amd/csrc/decode_plan.h"
+#include "unrle_layout.h"
 
-constexpr uint32_t ITEMS = BZD_UR_ITEMS, THREADS = 256, TILE = ITEMS * THREADS, STAGE = 8192;
+constexpr uint32_t STAGE = 8192;
 
 static uint64_t rng_state;
 static uint64_t rnd()
@@ -37,70 +38,6 @@ static uint64_t below(uint64_t n) { return n ? rnd() % n : 0; }
             exit(1);                                          \
         }                                                     \
     } while (0)
-
-struct Thread {
-    uint32_t w[4], cnt, prev, state, outn, off; // off: of its first output byte inside its tile
-};
-struct Tile {
-    uint32_t toff, total;
-    std::vector<Thread> th;
-};
-
-// the layout the kernel works from (unrle_maps, unrle_walk<false>, bzp_tile_sums); the block's decoded size
-static uint32_t lay_out(const std::vector<uint8_t> &x, std::vector<Tile> &tiles)
-{
-    const uint32_t n = (uint32_t)x.size();
-    tiles.clear();
-    uint32_t pre = BZD_RL_ID, sum = 0;
-    for (uint32_t t0 = 0; t0 < n; t0 += TILE) {
-        Tile tl;
-        tl.toff = sum;
-        tl.total = 0;
-        for (uint32_t i0 = t0; i0 < n && i0 < t0 + TILE; i0 += ITEMS) {
-            Thread th;
-            memset(th.w, 0, sizeof th.w);
-            th.cnt = n - i0 < ITEMS ? n - i0 : ITEMS;
-            th.prev = i0 ? x[i0 - 1] : 256u;
-            for (uint32_t k = 0; k < th.cnt; k++) th.w[k >> 2] |= (uint32_t)x[i0 + k] << (8 * (k & 3));
-            th.state = bzd_rl_apply(pre, 0);
-            uint32_t st[5] = {0, 1, 2, 3, 4}, prev = th.prev, s = th.state;
-            th.outn = 0;
-            for (uint32_t k = 0; k < th.cnt; k++) {
-                const uint32_t c = bzd_ur_at(th.w, k);
-                th.outn += s == 4 ? c : 1u;
-                s = bzd_rl_step(s, c == prev);
-                for (int q = 0; q < 5; q++) st[q] = bzd_rl_step(st[q], c == prev);
-                prev = c;
-            }
-            pre = bzd_rl_compose(pre, st[0] | st[1] << 3 | st[2] << 6 | st[3] << 9 | st[4] << 12);
-            th.off = tl.total;
-            tl.total += th.outn;
-            tl.th.push_back(th);
-        }
-        sum += tl.total;
-        tiles.push_back(tl);
-    }
-    return sum;
-}
-
-// the serial inverse RLE1 of the block: the truth
-static std::vector<uint8_t> expand(const std::vector<uint8_t> &x)
-{
-    std::vector<uint8_t> out;
-    uint32_t run = 0, prev = 256;
-    for (uint8_t c : x) {
-        if (run == 4) {
-            out.insert(out.end(), c, (uint8_t)prev);
-            run = 0;
-            prev = 256; // (the byte behind a count starts a new run whatever it is)
-            continue;
-        }
-        run = c == prev ? run + 1 : 1;
-        prev = c;
-        out.push_back(c);
-    }
-    return out;
-}
 
 // a block behind the inverse BWT: literals and runs, the counts behind four equal bytes small or (heavy) up to 255
 static std::vector<uint8_t> make_block(uint32_t n, bool heavy)
@@ -123,8 +60,9 @@ static void pieces_case(uint32_t n, bool heavy, uint32_t npieces)
 {
     const std::vector<uint8_t> x = make_block(n, heavy);
     std::vector<Tile> tiles;
-    const uint32_t size = lay_out(x, tiles);
-    const std::vector<uint8_t> full = expand(x);
+    uint32_t size;
+    (void)lay_out(x.data(), n, tiles, &size);
+    const std::vector<uint8_t> full = expand(x.data(), n).out;
     CHECK(full.size() == size, "the layout sums to %u bytes, the serial expansion has %zu", size, full.size());
     // pieces anywhere in the block, their destinations back to back: short ones, some in one tile, some over all of it
     std::vector<PieceRef> pc(npieces);

@@ -1,8 +1,7 @@
 // unrle_host.cpp -- what one thread of the decoder's random-access kernels does (banzai_amd/csrc/decode_core.h: bzd_ur_fold,
 // bzd_clip, bzd_ur_emit) and the CRC algebra around it (banzai_amd/csrc/crc_gf.h), as a CPU program built by
 // tests/test_index_api.py with -fsanitize=address,undefined.  The GPU kernels unrle_crc and unrle_walk_win compile the same
-// text; this file lays the threads out as they do -- tiles of 4,096 bytes, 16 a thread, entry states by composing state maps,
-// offsets by prefix sums -- and runs them one after the other.
+// text; unrle_layout.h lays the threads out as they do and this file runs them one after the other.
 //
 //   unrle_host <cases> <results>   cases: [u32 n][n bytes]... (a block behind the inverse BWT each)
 //                                  results: [u32 crc][u32 end state][u32 len][len bytes]... (CRC from the fold, never from the bytes)
@@ -18,16 +17,7 @@
 
 #include "../../banzai_amd/csrc/crc_gf.h"
 #include "../../banzai_amd/csrc/decode_core.h"
-
-constexpr uint32_t ITEMS = BZD_UR_ITEMS, THREADS = 256, TILE = ITEMS * THREADS;
-
-struct Thread {
-    uint32_t w[4], cnt, prev, state, outn, off; // off: of its first output byte inside its tile
-};
-struct Tile {
-    uint32_t toff, total;
-    std::vector<Thread> th;
-};
+#include "unrle_layout.h"
 
 static uint32_t g_tab[256], g_pow2[40];
 
@@ -43,41 +33,6 @@ static void tables()
         g_pow2[k] = p;
         p = gf_mul(p, p);
     }
-}
-
-// the layout the kernels work from: per thread its bytes, entry state, size and offset; per tile its offset in the block
-static uint32_t lay_out(const uint8_t *x, uint32_t n, std::vector<Tile> &tiles, uint32_t *bsize)
-{
-    tiles.clear();
-    uint32_t pre = BZD_RL_ID, sum = 0;
-    for (uint32_t t0 = 0; t0 < n; t0 += TILE) {
-        Tile tl;
-        tl.toff = sum;
-        tl.total = 0;
-        for (uint32_t i0 = t0; i0 < n && i0 < t0 + TILE; i0 += ITEMS) {
-            Thread th;
-            memset(th.w, 0, sizeof th.w);
-            th.cnt = n - i0 < ITEMS ? n - i0 : ITEMS;
-            th.prev = i0 ? x[i0 - 1] : 256u;
-            for (uint32_t k = 0; k < th.cnt; k++) th.w[k >> 2] |= (uint32_t)x[i0 + k] << (8 * (k & 3));
-            th.state = bzd_rl_apply(pre, 0);
-            uint32_t st[5] = {0, 1, 2, 3, 4}, prev = th.prev;
-            for (uint32_t k = 0; k < th.cnt; k++) {
-                const uint32_t c = bzd_ur_at(th.w, k);
-                for (int s = 0; s < 5; s++) st[s] = bzd_rl_step(st[s], c == prev);
-                prev = c;
-            }
-            pre = bzd_rl_compose(pre, st[0] | st[1] << 3 | st[2] << 6 | st[3] << 9 | st[4] << 12);
-            (void)bzd_ur_fold(g_tab, th.w, th.cnt, th.prev, th.state, &th.outn);
-            th.off = tl.total;
-            tl.total += th.outn;
-            tl.th.push_back(th);
-        }
-        sum += tl.total;
-        tiles.push_back(tl);
-    }
-    *bsize = sum;
-    return bzd_rl_apply(pre, 0);
 }
 
 // unrle_crc + unrle_crc_finish
@@ -144,9 +99,14 @@ int main(int argc, char **argv)
         if (n && fread(x, 1, n, fi) != n) return 2;
         uint32_t bsize, walked;
         const uint32_t end = lay_out(x, n, tiles, &bsize);
+        const Serial truth = expand(x, n);
         free(x);
         const uint32_t crc = crc_of_expansion(tiles, bsize);
         expand_window(tiles, 0, bsize, full, &walked);
+        if (full != truth.out || end != truth.end) {
+            fprintf(stderr, "unrle_host: case %ld, the layout's expansion or end state is not the serial one's\n", c);
+            exit(1);
+        }
         fwrite(&crc, 4, 1, fo);
         fwrite(&end, 4, 1, fo);
         fwrite(&bsize, 4, 1, fo);
