@@ -1003,8 +1003,11 @@ class PatternSet(_native.PatternSet):
         super().__init__(_ctx(9, device), pats, bool(ignore_case))
 
 
-def _regex_args(patterns, ignore_case, dotall, max_span):
-    """what Regex and regex_check are given -> (the expressions, the flags, the span), refused before a device is touched"""
+def _regex_args(patterns, ignore_case, dotall, max_span, word=False, line=False):
+    """what Regex and regex_check are given -> (the expressions, the flags, the span, the syntax word), refused before a device is
+    touched.  Assertions are always admitted."""
+    if word and line:
+        raise ValueError("word=True and line=True exclude each other")
     if isinstance(patterns, str):
         raise TypeError("a regular expression must be bytes-like, not str")
     if isinstance(patterns, (bytes, bytearray, memoryview)):
@@ -1023,38 +1026,46 @@ def _regex_args(patterns, ignore_case, dotall, max_span):
     if not 1 <= span <= _native.REGEX_MAX_SPAN:
         raise ValueError(f"max_span must lie in 1..{_native.REGEX_MAX_SPAN}, not {span}")
     flags = (_native.REGEX_FOLD_ASCII if ignore_case else 0) | (_native.REGEX_DOTALL if dotall else 0)
-    return exprs, flags, span
+    return exprs, flags, span, _native.REGEX_ASSERT | (_native.REGEX_WORD if word else 0) | (_native.REGEX_LINE if line else 0)
 
 
 class Regex(_native.PatternSet):
     """Regular expressions (bytes, or a list of 1..65536 of them, 1..4096 bytes each) compiled into one DFA that every start
     position of the decoded text walks on the device: grep -E.  The syntax is a subset of Python's `re` on bytes -- literals,
-    the usual escapes, \\d \\w \\s and their complements, `.`, classes, groups, `|`, `? * + {m} {m,} {m,n}`; anchors, \\b,
-    backreferences, lookaround and lazy quantifiers are refused with the expression's number and the byte.  It goes wherever
+    the usual escapes, \\d \\w \\s and their complements, `.`, classes, groups, `|`, `? * + {m} {m,} {m,n}`, and the assertions
+    ^ $ \\A \\Z \\b \\B anywhere in an expression, as `re` has them under re.MULTILINE: ^ at offset 0 of the whole decoded text
+    and behind every 0x0A, $ at its end and in front of every 0x0A (whatever `delim` a call is given), \\A and \\Z only at the two
+    ends, \\b between a byte of [0-9A-Za-z_] and one that is none (the text's ends count as none; folding changes nothing).  An
+    assertion sees the real neighbours, also outside the range of a search_range, so every route reports the same hits; it consumes
+    nothing, and an expression that can match the empty string (^, ^$, \\b) is refused.  Backreferences, lookaround and lazy
+    quantifiers are refused with the expression's number and the byte.  `word=True` matches every expression as grep -w does --
+    not preceded and not followed by a word byte, every length tried --, `line=True` as grep -x: ^(?:e)$.  It goes wherever
     `pattern` goes: search, search_range, grep, grep_count, IndexedReader.search and IndexedReader.grep.  A search reports ONE hit
     per start at which some expression matches: `len` is the longest match of at most `max_span` (1..256) bytes, `pattern` the
     lowest-numbered expression that matches exactly that length; overlapping starts are all hits.  A match longer than
     `max_span` is not found; `.info["unbounded"]` says that the expressions have such matches.  `ignore_case` folds ASCII
-    letters (re.IGNORECASE on bytes), `dotall` lets `.` take 0x0A.  `.info` carries the fields of bzh_regex_info."""
+    letters (re.IGNORECASE on bytes), `dotall` lets `.` take 0x0A.  `.info` carries the fields of bzh_regex_info and of
+    bzh_regex_look: `look_behind`, `look_ahead` (1: some assertion sees the byte in front of a start, behind a match; both 0
+    without assertions, and the automaton is what it was) and `contexts`."""
 
-    def __init__(self, patterns, ignore_case=False, dotall=False, max_span=256, device=0, _no_lds=False):
-        exprs, flags, span = _regex_args(patterns, ignore_case, dotall, max_span)
+    def __init__(self, patterns, ignore_case=False, dotall=False, max_span=256, word=False, line=False, device=0, _no_lds=False):
+        exprs, flags, span, syntax = _regex_args(patterns, ignore_case, dotall, max_span, word, line)
         self.device = device
-        super().__init__(_ctx(9, device), exprs, flags=flags | (_native.REGEX_NO_LDS if _no_lds else 0), regex=True, max_span=span)
+        super().__init__(_ctx(9, device), exprs, flags=flags | (_native.REGEX_NO_LDS if _no_lds else 0), regex=True, max_span=span, syntax=syntax)
 
 
-def regex_check(patterns, ignore_case=False, dotall=False, max_span=256):
+def regex_check(patterns, ignore_case=False, dotall=False, max_span=256, word=False, line=False):
     """The compile of Regex alone, on the host, without a device -> the dictionary Regex(...).info would hold; ValueError with the
-    compiler's message (the expression's number and the byte) for what it refuses (bzh_regex_check)."""
+    compiler's message (the expression's number and the byte) for what it refuses (bzh_regex_check_ex)."""
     import ctypes
-    exprs, flags, span = _regex_args(patterns, ignore_case, dotall, max_span)
+    exprs, flags, span, syntax = _regex_args(patterns, ignore_case, dotall, max_span, word, line)
     arr = (ctypes.c_char_p * len(exprs))(*exprs)
     lens = (ctypes.c_size_t * len(exprs))(*[len(e) for e in exprs])
-    info, err = _native.RegexInfo(), ctypes.create_string_buffer(256)
-    st = _native.lib().bzh_regex_check(arr, lens, len(exprs), flags, span, ctypes.byref(info), err, len(err))
+    info, look, err = _native.RegexInfo(), _native.RegexLook(), ctypes.create_string_buffer(256)
+    st = _native.lib().bzh_regex_check_ex(arr, lens, len(exprs), flags, span, syntax, ctypes.byref(info), ctypes.byref(look), err, len(err))
     if st != 0:
         raise ValueError(err.value.decode("latin-1"))
-    return info.as_dict()
+    return dict(info.as_dict(), **look.as_dict())
 
 
 def _pattern_arg(pattern):
@@ -1091,7 +1102,11 @@ def _search_range(index, fetch, pattern, offset, length, limit, device):
     pattern, limit = _pattern_arg(pattern), _limit_arg(limit)
     offset = _int_arg(offset, "offset")
     length = max(0, index.size - offset) if length is None else _int_arg(length, "length")
-    _, _, lo, hi = index.span(offset, length)
+    # an automaton with assertions looks at the byte in front of the range and at the byte behind it: the blocks of the widened
+    # range are decoded, so the compressed bytes of the widened span go up (the hits stay inside the wanted range)
+    look = getattr(pattern, "info", {})
+    back = min(offset, look.get("look_behind", 0)) if offset > 0 else 0
+    _, _, lo, hi = index.span(offset - back, length + back + look.get("look_ahead", 0))
     return _ctx(9, device).search_range(fetch(lo, hi), index.entries, pattern, offset, length, _points_arg(index),
                                         rindex.rec_cum if rindex is not None else None, rindex.delim if rindex is not None else None,
                                         limit, in_byte_base=lo)

@@ -194,6 +194,20 @@ class RegexInfo(ctypes.Structure):
 
 
 assert ctypes.sizeof(RegexInfo) == 40
+
+
+class RegexLook(ctypes.Structure):
+    """bzh_regex_look"""
+    _fields_ = [("look_behind", ctypes.c_uint32), ("look_ahead", ctypes.c_uint32), ("contexts", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+assert ctypes.sizeof(RegexLook) == 16
+REGEX_ASSERT = 1  # the syntax word of the _ex calls, apart from the flags
+REGEX_WORD = 2
+REGEX_LINE = 4
 REGEX_FOLD_ASCII = 1
 REGEX_DOTALL = 2
 REGEX_NO_LDS = 4
@@ -335,6 +349,11 @@ SIGNATURES = {
     "bzh_regex_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint32,
                                         ctypes.POINTER(ctypes.c_void_p)]),
     "bzh_regex_get_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RegexInfo)]),
+    "bzh_regex_create_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint32,
+                                           ctypes.c_uint, ctypes.POINTER(ctypes.c_void_p)]),
+    "bzh_regex_check_ex": (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p), szp, ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint32, ctypes.c_uint,
+                                          ctypes.POINTER(RegexInfo), ctypes.POINTER(RegexLook), ctypes.c_char_p, ctypes.c_size_t]),
+    "bzh_regex_get_look": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RegexLook)]),
     "bzh_regex_check": (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p), szp, ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint32,
                                        ctypes.POINTER(RegexInfo), ctypes.c_char_p, ctypes.c_size_t]),
     "bzh_search_set_room": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),
@@ -596,8 +615,10 @@ class PatternSet:
     """A compiled set of patterns on the device of `ctx` (bzh_patset_create / bzh_patset_destroy): what the search and grep
     calls of a Context take in place of one pattern.  It outlives the context it was made with."""
 
-    def __init__(self, ctx, patterns, ignore_case=False, flags=None, regex=False, max_span=0):
-        """regex: `patterns` are regular expressions (bzh_regex_create; flags: BZH_REGEX_*), .info is bzh_regex_info's"""
+    def __init__(self, ctx, patterns, ignore_case=False, flags=None, regex=False, max_span=0, syntax=0):
+        """regex: `patterns` are regular expressions (bzh_regex_create; flags: BZH_REGEX_*), .info is bzh_regex_info's and
+        bzh_regex_look's.  syntax: REGEX_ASSERT / REGEX_WORD / REGEX_LINE (bzh_regex_create_ex); 0 is bzh_regex_create itself, which
+        refuses every assertion"""
         self._h = None
         self._destroy = lib().bzh_patset_destroy  # kept so that close() still works during interpreter shutdown
         pats = [bytes(p) for p in patterns]
@@ -605,7 +626,9 @@ class PatternSet:
         lens = np.array([len(p) for p in pats] or [0], dtype=np.uintp)
         h = ctypes.c_void_p()
         fl = ((REGEX_FOLD_ASCII if regex else PATSET_FOLD_ASCII) if ignore_case else 0) if flags is None else flags
-        if regex:
+        if regex and syntax:
+            ctx.check(lib().bzh_regex_create_ex(ctx.handle, arr, ptr(lens, szp), len(pats), fl, max_span, syntax, ctypes.byref(h)))
+        elif regex:
             ctx.check(lib().bzh_regex_create(ctx.handle, arr, ptr(lens, szp), len(pats), fl, max_span, ctypes.byref(h)))
         else:
             ctx.check(lib().bzh_patset_create(ctx.handle, arr, ptr(lens, szp), len(pats), fl, ctypes.byref(h)))
@@ -613,6 +636,10 @@ class PatternSet:
         i = RegexInfo() if regex else PatsetInfo()
         ctx.check((lib().bzh_regex_get_info if regex else lib().bzh_patset_get_info)(h, ctypes.byref(i)))
         self.info = i.as_dict()
+        if regex:
+            look = RegexLook()
+            ctx.check(lib().bzh_regex_get_look(h, ctypes.byref(look)))
+            self.info.update(look.as_dict())
 
     @property
     def handle(self):

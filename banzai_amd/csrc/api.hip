@@ -1985,6 +1985,17 @@ static int search_range_args(bzh_ctx *ctx, const bzh_index_entry *idx, size_t co
     return BZH_OK;
 }
 
+// The range a range search DECODES: the wanted one, widened by the bytes an automaton with assertions looks at in front of it and
+// behind it (decode_range_sink_run widens alike, and clips to the output); the hits stay inside the wanted range.
+static void search_decoded_range(const ScanWhat &q, uint64_t off, uint64_t len, uint64_t *w_off, uint64_t *w_len)
+{
+    *w_off = off, *w_len = len;
+    if (!q.is_set || !q.set->looks()) return;
+    const uint64_t back = std::min<uint64_t>(off, q.set->look.look_behind), more = back + q.set->look.look_ahead;
+    *w_off = off - back;
+    *w_len = len > ~0ull - more ? ~0ull : len + more;
+}
+
 static int search_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
                                const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len, const ScanWhat &q,
                                unsigned flags, uint8_t delim, void *hits, size_t max, size_t *nhits)
@@ -1998,8 +2009,9 @@ static int search_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_
     BZH_TRY(decode_call_begin(ctx, n, call));
     BZH_TRY(search_range_args(ctx, idx, count, pts, npts, rec_cum, flags));
     size_t first = 0, last = 0;
-    uint64_t lo, hi;
-    BZH_TRY(bzh_index_span(idx, count, off, len, &first, &last, &lo, &hi));
+    uint64_t lo, hi, w_off, w_len;
+    search_decoded_range(q, off, len, &w_off, &w_len);
+    BZH_TRY(bzh_index_span(idx, count, w_off, w_len, &first, &last, &lo, &hi));
     BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(last - first, 1), ctx->max_batch)));
     int rc = decode_range_sink_run(ctx, (const uint8_t *)d_in, n, in_byte_base, idx, count, pts, npts, sink.records ? rec_cum : nullptr, off, len,
                                    sink);
@@ -2023,7 +2035,9 @@ static int search_range_host(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t
     size_t first = 0, last = 0;
     uint64_t lo = 0, hi = 0, base;
     size_t un;
-    BZH_TRY(bzh_index_span(idx, count, off, len, &first, &last, &lo, &hi));
+    uint64_t w_off, w_len;
+    search_decoded_range(q, off, len, &w_off, &w_len);
+    BZH_TRY(bzh_index_span(idx, count, w_off, w_len, &first, &last, &lo, &hi)); // (the widened span: what the device variant is to be handed)
     BZH_TRY(decode_stage_hull(ctx, in, n, in_byte_base, lo, hi, 0, &base, &un));
     return search_range_device(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, rec_cum, off, len, q, flags, delim, hits, max, nhits);
     });

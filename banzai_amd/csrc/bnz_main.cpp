@@ -11,7 +11,8 @@
 // leaves the device (bzh_search; with --index bzh_search_range over just the span's compressed bytes).
 // Grep: --grep writes the lines that hold a byte string, selected and compacted on the device (bzh_grep; with --index
 // bzh_grep_index).  Several strings (-e, --patterns) or --ignore-case: one compiled set, one pass (bzh_patset_create, bzh_*_patset*).
-// -E: the strings are regular expressions, compiled into one automaton that goes the set's way (bzh_regex_create).
+// -E: the strings are regular expressions, compiled into one automaton that goes the set's way (bzh_regex_create_ex; assertions are
+// always admitted).  -w, -x: the word and the line wrap of that call; without -E a string is escaped byte by byte and goes the same way.
 #include <cstdio>
 #include <cstdlib>
 #include <cerrno>
@@ -74,8 +75,15 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "     --patterns <file>      as -e for every line of <file> (not hex); an empty line is an error\n"
             "     --ignore-case          with --search or --grep: 'A'..'Z' and 'a'..'z' compare equal, nothing else does\n"
             "  -E --regex                with --search or --grep: <string>, every -e and every line of --patterns are regular\n"
-            "                            expressions (a subset of Python's re on bytes; no anchors); a start reports its longest\n"
-            "                            match of at most 256 bytes; not with --hex\n"
+            "                            expressions (a subset of Python's re on bytes); a start reports its longest match of\n"
+            "                            at most 256 bytes; not with --hex.  ^ $ \\A \\Z \\b \\B are Python's under re.MULTILINE:\n"
+            "                            ^ and $ at the two ends of the whole decoded data and around every '\\n', \\A and \\Z\n"
+            "                            at the two ends alone, \\b between a byte of [0-9A-Za-z_] and one that is none\n"
+            "  -w --word-regexp          with --search or --grep: a match is neither preceded nor followed by a byte of\n"
+            "                            [0-9A-Za-z_] (every length of it is tried)\n"
+            "  -x --line-regexp          with --search or --grep: a match is a whole line (of an -E expression e: ^(?:e)$)\n"
+            "                            Without -E the strings stay literal under -w and -x (with --hex too); -w and -x\n"
+            "                            exclude each other\n"
             "                            With any of these three --search prints a third column: the number of the\n"
             "                            string, from 0 in the order given (of equal strings the first)\n"
             "     --keep      or   -k    keep the input file\n"
@@ -130,7 +138,9 @@ int main(int argc, char **argv)
     std::string in_path, out_path, index_path, mkindex_path, needle;
     std::vector<std::string> pats; // the strings of a set, in the order given (-e: hex with --hex; --patterns: as they stand)
     std::vector<bool> pat_hex;
-    bool use_set = false, ignore_case = false, regex = false; // regex: every string is a regular expression (bzh_regex_create)
+    bool use_set = false, ignore_case = false, regex = false; // regex: every string is a regular expression (bzh_regex_create_ex)
+    bool word_re = false, line_re = false;                    // -w, -x: the wraps of bzh_regex_create_ex; a literal string is escaped for it
+    bzh_regex_look look{0, 0, 1, 0};                          // what the automaton looks at: a --range is widened by it
     auto read_patterns = [&](const std::string &path) {
         FILE *pf = fopen(path.c_str(), "rb");
         if (!pf) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + path + ": " + strerror(errno));
@@ -215,6 +225,8 @@ int main(int argc, char **argv)
             else if (a == "--patterns") expect = PATFILE;
             else if (a == "--ignore-case") ignore_case = true;
             else if (a == "-E" || a == "--regex") regex = true;
+            else if (a == "-w" || a == "--word-regexp") word_re = true;
+            else if (a == "-x" || a == "--line-regexp") line_re = true;
             else needle = a, pats.push_back(a), pat_hex.push_back(true);
         } else if (expect == PATTERN) {
             pats.push_back(a), pat_hex.push_back(true);
@@ -254,6 +266,8 @@ int main(int argc, char **argv)
             else if (a == "--patterns") expect = PATFILE;
             else if (a == "--ignore-case") ignore_case = true;
             else if (a == "--regex") regex = true;
+            else if (a == "--word-regexp") word_re = true;
+            else if (a == "--line-regexp") line_re = true;
             else if (a == "--stdout") set_output("", true);
             else if (a == "--") expect = NOARGS;
             else die(ERR_ARGS, "Unrecognised argument " + a);
@@ -264,6 +278,10 @@ int main(int argc, char **argv)
                 expect = PATTERN;
             } else if (a == "-E") {
                 regex = true;
+            } else if (a == "-w") {
+                word_re = true;
+            } else if (a == "-x") {
+                line_re = true;
             } else {
                 for (size_t c = 1; c < a.size(); c++) {
                     const char f = a[c];
@@ -287,7 +305,9 @@ int main(int argc, char **argv)
     if (expect == GREP) die(ERR_ARGS, "Argument '--grep' requires a string");
     if (expect == PATTERN) die(ERR_ARGS, "Argument '-e' requires a string");
     if (expect == PATFILE) die(ERR_ARGS, "Argument '--patterns' requires a file path");
-    use_set = use_set || ignore_case || regex;
+    if (word_re && line_re) die(ERR_ARGS, "'-w' and '-x' exclude each other");
+    if ((word_re || line_re) && !searching) die(ERR_ARGS, "'-w' and '-x' go with '--search' or '--grep'");
+    use_set = use_set || ignore_case || regex || word_re || line_re;
     if (use_set && !searching) die(ERR_ARGS, "'-e', '-E', '--patterns' and '--ignore-case' go with '--search' or '--grep'");
     if (regex && needle_hex) die(ERR_ARGS, "'-E' and '--hex' exclude each other: a regular expression writes a byte as \\xHH");
     if (use_set && pats.empty()) die(ERR_ARGS, "'--search' and '--grep' require a string, a '-e' or a '--patterns'");
@@ -319,6 +339,24 @@ int main(int argc, char **argv)
                 die(ERR_ARGS, "string " + std::to_string(k) + (regex ? " does not hold 1 to 4096 bytes" : " does not hold 1 to 256 bytes"));
         }
         if (use_set && pats.size() > BZH_PATSET_MAX_PATTERNS) die(ERR_ARGS, "more than 65536 strings");
+        if ((word_re || line_re) && !regex) { // a literal string under a wrap goes the regex way, every byte as \xHH: 256 bytes become 1,024
+            for (std::string &q : pats) {
+                std::string esc;
+                char h[8];
+                for (unsigned char ch : q) snprintf(h, sizeof h, "\\x%02X", ch), esc += h;
+                q = esc;
+            }
+            regex = true;
+        }
+        if (regex) { // the compile alone, on the host: what it refuses is refused before a file is read, and a --range knows its neighbours
+            std::vector<const uint8_t *> pp;
+            std::vector<size_t> pl;
+            for (const std::string &q : pats) pp.push_back((const uint8_t *)q.data()), pl.push_back(q.size());
+            char why[256] = "";
+            const int rc = bzh_regex_check_ex(pp.data(), pl.data(), pp.size(), ignore_case ? BZH_REGEX_FOLD_ASCII : 0, 0,
+                                              BZH_REGEX_ASSERT | (word_re ? BZH_REGEX_WORD : 0) | (line_re ? BZH_REGEX_LINE : 0), nullptr, &look, why, sizeof why);
+            if (rc != BZH_OK) die(rc == BZH_E_ARG ? ERR_ARGS : ERR_OUTPUT, std::string("error during search: ") + bzh_strerror(rc) + ": " + why);
+        }
     }
     const bool by_range = !ranges.empty() && !searching, make_index = !mkindex_path.empty();
     if (by_range && index_path.empty()) die(ERR_ARGS, "'--range' needs the '--index' of the input");
@@ -416,7 +454,9 @@ int main(int argc, char **argv)
             if (stat(in_path.c_str(), &sb) != 0) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + in_path + ": " + strerror(errno));
             if (!S_ISREG(sb.st_mode)) die(ERR_ARGS, "'--search --index' reads parts of a regular file: " + in_path + " is none");
             size_t first = 0, last = 0;
-            rs = bzh_index_span(ent.data(), count, want.off, want.len, &first, &last, &lo, &hi);
+            // (an automaton with assertions sees the byte in front of the range and the byte behind it: the widened span is read)
+            const uint64_t back = want.off < look.look_behind ? want.off : look.look_behind, more = back + look.look_ahead;
+            rs = bzh_index_span(ent.data(), count, want.off - back, want.len > UINT64_MAX - more ? UINT64_MAX : want.len + more, &first, &last, &lo, &hi);
             if (rs != BZH_OK) die(ERR_OUTPUT, std::string(doing) + bzh_strerror(rs));
             if (hi < lo || hi > (uint64_t)sb.st_size)
                 die(ERR_OUTPUT, std::string(doing) + "the index names bytes behind the end of " + in_path + ": it is not this file's");
@@ -444,7 +484,9 @@ int main(int argc, char **argv)
             std::vector<const uint8_t *> pp;
             std::vector<size_t> pl;
             for (const std::string &q : pats) pp.push_back((const uint8_t *)q.data()), pl.push_back(q.size());
-            if (regex) rs = bzh_regex_create(sctx, pp.data(), pl.data(), pp.size(), ignore_case ? BZH_REGEX_FOLD_ASCII : 0, 0, &set);
+            if (regex)
+                rs = bzh_regex_create_ex(sctx, pp.data(), pl.data(), pp.size(), ignore_case ? BZH_REGEX_FOLD_ASCII : 0, 0,
+                                         BZH_REGEX_ASSERT | (word_re ? BZH_REGEX_WORD : 0) | (line_re ? BZH_REGEX_LINE : 0), &set);
             else rs = bzh_patset_create(sctx, pp.data(), pl.data(), pp.size(), ignore_case ? BZH_PATSET_FOLD_ASCII : 0, &set);
             if (rs != BZH_OK) {
                 const std::string msg = std::string(doing) + bzh_strerror(rs) + ": " + bzh_last_error(sctx);

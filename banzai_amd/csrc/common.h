@@ -560,6 +560,9 @@ struct RecBuild { // bzh_decode_index_records*: the index build also counts the 
 struct WindowSink {
     const uint64_t front; // the decoders expand at *d_stage + front (whatever is carried between two windows lies in front of it)
     const uint32_t delim; // of the records, where the walk counts them (BackCount)
+    // bytes in front of and behind the wanted range that what is looked for looks at (an automaton with assertions): a range decode
+    // widens the decoded range by them, clipped to the output, and the sink still reports only what lies in the wanted range
+    uint32_t look_behind = 0, look_ahead = 0;
     WindowSink(uint64_t front_, uint32_t delim_) : front(front_), delim(delim_) {}
     // the wanted range [lo, hi) of the output; the output offset of the first window's first byte, the delimiters in front of it
     virtual void begin(uint64_t lo, uint64_t hi, uint64_t out_start, uint64_t rec_start) = 0;
@@ -626,10 +629,15 @@ struct bzh_patset {
     bool regex = false;    // regex.hip made it: the table is a DFA's (regex_plan.h), the matcher BzrMatcher
     bzh_regex_info rinfo{};
     uint32_t nterm = 0;    // of a regex: the terminal rows 1 .. nterm (a set's: info.distinct)
-    uint8_t *d_mem; // cls[256], first[256], pat_no[distinct], table[states * classes]
+    bzh_regex_look look{}; // of a regex with assertions: what it looks at (both 0: none, and the matcher is BzrMatcher)
+    uint32_t ctx_row = 0;  // ... the start row of context c in bits [8 c, 8 c + 8)
+    uint8_t *d_mem; // cls[256], first[256 * contexts], pat_no[distinct], table[states * classes]; with assertions pat_ctx[4 nterm], acc_mask[nterm]
     const uint8_t *d_cls;
     const uint16_t *d_first, *d_table;
     const uint32_t *d_pat_no;
+    const uint32_t *d_pat_ctx = nullptr;
+    const uint8_t *d_acc_mask = nullptr;
+    bool looks() const { return look.look_behind || look.look_ahead; }
 };
 struct BzmMatcher;
 BzmMatcher set_matcher(const bzh_patset *set, uint32_t delim, uint64_t lim);
@@ -638,6 +646,12 @@ template <bool LDS_ROWS>
 struct BzrMatcher;
 template <bool LDS_ROWS>
 BzrMatcher<LDS_ROWS> regex_matcher(const bzh_patset *set, uint32_t delim, uint64_t lim);
+// ... of a set with assertions (set->looks()), for a window of n bytes: edge_lo is the position no byte lies in front of, ctx_lo the
+// context that stands there (regex_core.h: the look-around variant)
+template <bool LDS_ROWS>
+struct BzrLookMatcher;
+template <bool LDS_ROWS>
+BzrLookMatcher<LDS_ROWS> regex_look_matcher(const bzh_patset *set, uint32_t delim, uint64_t lim, uint64_t n, uint64_t edge_lo, uint32_t ctx_lo);
 // search.hip: the search over decoded bytes in HBM.  A sink is what is looked for, where the hits go, and the walk over its windows
 // (search_plan.h): room() puts the carry in front of the window, window() runs the two passes and keeps the window's tail.
 struct SearchSink final : WindowSink {
@@ -646,14 +660,22 @@ struct SearchSink final : WindowSink {
     bool records;
     void *hits; // host: bzh_hit, or bzh_set_hit
     uint64_t max;
-    BzmSetWalk walk;
+    BzrLookWalk walk; // (window_look with a set that looks around)
     SearchSink(const uint8_t *pat_, size_t plen, unsigned flags, uint8_t delim_, bzh_hit *hits_, size_t max_)
         : WindowSink(BZF_FRONT, delim_), pat(bzf_pattern(pat_, (uint32_t)plen, delim_)), records((flags & BZH_SEARCH_RECORDS) != 0), hits(hits_), max(max_) {}
     SearchSink(const bzh_patset *set_, unsigned flags, uint8_t delim_, bzh_set_hit *hits_, size_t max_)
-        : WindowSink(BZF_FRONT, delim_), set(set_), records((flags & BZH_SEARCH_RECORDS) != 0), hits(hits_), max(max_) {}
+        : WindowSink(BZF_FRONT, delim_), set(set_), records((flags & BZH_SEARCH_RECORDS) != 0), hits(hits_), max(max_)
+    {
+        look_behind = set->look.look_behind, look_ahead = set->look.look_ahead;
+    }
+    bool looks() const { return set && set->looks(); }
     uint32_t plen() const { return set ? set->info.max_len : pat.plen; } // (of a set: its longest pattern's)
     size_t hit_size() const { return set ? sizeof(bzh_set_hit) : sizeof(bzh_hit); }
-    void begin(uint64_t lo, uint64_t hi, uint64_t out_start, uint64_t rec_start) override { walk.begin(plen(), front, max, lo, hi, out_start, rec_start); }
+    void begin(uint64_t lo, uint64_t hi, uint64_t out_start, uint64_t rec_start) override
+    {
+        walk.begin(plen(), front, max, lo, hi, out_start, rec_start);
+        walk.begin_look(look_behind, look_ahead);
+    }
     int room(bzh_ctx *ctx, uint64_t bytes, uint8_t **d_stage) override;
     int window(bzh_ctx *ctx, uint64_t bytes) override;
 };
@@ -679,7 +701,7 @@ struct GrepSink final : WindowSink {
     GrepSink(const bzh_patset *set_, unsigned flags, uint8_t delim_, void *d_out_, size_t cap, bzh_grep_entry *ent_, size_t max)
         : WindowSink(BZF_FRONT, delim_), set(set_), d_out((uint8_t *)d_out_), ent(ent_)
     {
-        walk.begin(set->info.max_len, (flags & BZH_GREP_INVERT) != 0, d_out != nullptr, cap, ent != nullptr, max);
+        walk.begin(set->info.max_len + set->look.look_ahead, (flags & BZH_GREP_INVERT) != 0, d_out != nullptr, cap, ent != nullptr, max); // (the hold-back grows by the byte behind a match)
     }
     void begin(uint64_t, uint64_t, uint64_t, uint64_t) override {}
     int room(bzh_ctx *ctx, uint64_t bytes, uint8_t **d_stage) override;

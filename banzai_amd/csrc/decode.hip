@@ -2276,8 +2276,13 @@ int decode_range_sink_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t 
 {
     size_t first, last;
     uint64_t byte_lo, byte_hi, clipped;
-    index_span(idx, count, off, len, &first, &last, &byte_lo, &byte_hi, &clipped);
+    index_span(idx, count, off, len, &first, &last, &byte_lo, &byte_hi, &clipped); // the wanted range, clipped to the output
     if (clipped == 0 || last <= first) return BZH_OK;
+    if (sink.look_behind || sink.look_ahead) { // the decoded range: the neighbours the sink looks at lie in it (the sink keeps to the wanted one)
+        const uint64_t w_off = off - std::min<uint64_t>(off, sink.look_behind), w_len = clipped + (off - w_off) + sink.look_ahead;
+        uint64_t w_clipped;
+        index_span(idx, count, w_off, w_len, &first, &last, &byte_lo, &byte_hi, &w_clipped);
+    }
     BZH_TRY(index_covered(ctx, idx, first, last - 1, in_byte_base, n));
     DecWs w;
     BZH_TRY(dec_ws(ctx, w));

@@ -113,9 +113,14 @@ __global__ void __launch_bounds__(BZF_THREADS) grep_scan(BzgTile *tile, uint32_t
 // ---- host side ---------------------------------------------------------------------------------------------------
 // f(the sink's matcher): its pattern, or its set or automaton bounded by the text's end
 template <class F>
-static void grep_matcher(const GrepSink &g, uint64_t n, F &&f)
+static void grep_matcher(const GrepSink &g, const BzgWindow &w, F &&f)
 {
-    if (g.set && g.set->regex) {
+    const uint64_t n = w.n;
+    if (g.set && g.set->looks()) { // the text begins at a record start: the text's edge at output offset 0, else the delimiter stands in front of it
+        const uint32_t ctx_lo = w.off_base + w.t_lo == 0 ? (uint32_t)BZR_LOOK_EDGE : bzr_ctx(g.delim);
+        if (g.set->rinfo.in_lds) f(regex_look_matcher<true>(g.set, g.delim, n, n, w.t_lo, ctx_lo));
+        else f(regex_look_matcher<false>(g.set, g.delim, n, n, w.t_lo, ctx_lo));
+    } else if (g.set && g.set->regex) {
         if (g.set->rinfo.in_lds) f(regex_matcher<true>(g.set, g.delim, n));
         else f(regex_matcher<false>(g.set, g.delim, n));
     } else if (g.set) f(set_matcher(g.set, g.delim, n));
@@ -138,7 +143,7 @@ static int grep_window_run(bzh_ctx *ctx, GrepSink &g, const uint8_t *d, const Bz
         BZH_TRY(reserve_cut(ctx, ctx->grep_tab, "the grep's tile tables", grow_mib,
                             [&](Carver &c) { c.put(tile, tiles), c.put(base, tiles), c.put(d_tot, BZG_TOTALS); }));
         GfArgs a{d, w, tile, base, nullptr, nullptr};
-        grep_matcher(g, w.n, [&](const auto &m) { grep_tiles<false><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
+        grep_matcher(g, w, [&](const auto &m) { grep_tiles<false><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
         grep_scan<<<dim3(1), BZF_THREADS, 0, st>>>(tile, tiles, base, w, d_tot);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(totals, d_tot, sizeof totals, hipMemcpyDeviceToHost, st));
@@ -149,7 +154,7 @@ static int grep_window_run(bzh_ctx *ctx, GrepSink &g, const uint8_t *d, const Bz
                 BZH_TRY(ctx->grep_ent.reserve(ctx, (size_t)totals[BZG_T_SEL] * sizeof(BzgEntry), "the grep's entries", grow_mib));
                 a.ent = ctx->grep_ent.as<BzgEntry>();
             }
-            grep_matcher(g, w.n, [&](const auto &m) { grep_tiles<true><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
+            grep_matcher(g, w, [&](const auto &m) { grep_tiles<true><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
             HIP_TRY(ctx, hipGetLastError());
             if (a.ent)
                 HIP_TRY(ctx, hipMemcpyAsync(g.ent + w.sel_base, a.ent, (size_t)totals[BZG_T_SEL] * sizeof(BzgEntry), hipMemcpyDeviceToHost, st));

@@ -13,27 +13,37 @@ static_assert(BZR_FOLD_ASCII == BZH_REGEX_FOLD_ASCII && BZR_DOTALL == BZH_REGEX_
               "regex_plan.h and bzhip.h name the same bounds");
 static_assert(BZR_MAX_SPAN == BZF_MAX_PATTERN, "a match lies inside the tile's halo and the carry");
 static_assert(BZR_LDS_ROWS == BZR_LDS_ENTRIES, "regex_core.h and regex_plan.h name the same bound");
-static_assert(sizeof(bzh_regex_info) == 40, "bzh_regex_info");
+static_assert(sizeof(bzh_regex_info) == 40 && sizeof(bzh_regex_look) == 16, "bzh_regex_info, bzh_regex_look");
+static_assert(BZR_SYN_ASSERT == BZH_REGEX_ASSERT && BZR_SYN_WORD == BZH_REGEX_WORD && BZR_SYN_LINE == BZH_REGEX_LINE, "one syntax word");
+static_assert(BZR_CTX_EDGE == BZR_LOOK_EDGE && BZR_CTX_NL == BZR_LOOK_NL && BZR_CTX_WORD == BZR_LOOK_WORD && BZR_CTX_OTHER == BZR_LOOK_OTHER,
+              "regex_plan.h and regex_core.h number the contexts alike");
 
 static bzh_regex_info regex_info(const BzrPlan &p)
 {
     return bzh_regex_info{p.expressions, p.min_len, p.max_len, p.states, p.classes, p.unbounded, p.in_lds, p.table_bytes()};
 }
 
-static int regex_create(bzh_ctx *ctx, const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags, uint32_t max_span, bzh_patset **out)
+static bzh_regex_look regex_look(const BzrPlan &p) { return bzh_regex_look{p.look_behind, p.look_ahead, p.contexts, 0}; }
+
+static int regex_create(bzh_ctx *ctx, const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags, uint32_t max_span, unsigned syntax,
+                        bzh_patset **out)
 {
     BzrPlan plan;
     char why[200];
-    if (!bzr_compile(exprs, lens, count, flags, max_span, plan, why, sizeof why)) {
+    if (!bzr_compile_ex(exprs, lens, count, flags, max_span, syntax, plan, why, sizeof why)) {
         bzh_set_error(ctx, "%s", why);
         return BZH_E_ARG;
     }
-    // one allocation: cls[256], first[256], pat_no[nterm], table[states * classes] -- every part 4-byte aligned
-    const size_t o_first = 256, o_pat = o_first + 512, o_tab = o_pat + plan.pat_no.size() * sizeof(uint32_t);
-    const size_t total = (o_tab + (size_t)plan.table_bytes() + 15) & ~(size_t)15;
+    // one allocation: cls[256], first[256 * contexts], pat_no[nterm], table[states * classes], and with assertions pat_ctx[4 nterm],
+    // acc_mask[nterm] -- every part 4-byte aligned
+    const size_t o_first = 256, o_pat = o_first + 512 * (size_t)plan.contexts, o_tab = o_pat + plan.pat_no.size() * sizeof(uint32_t);
+    const size_t o_pctx = (o_tab + (size_t)plan.table_bytes() + 3) & ~(size_t)3, o_mask = o_pctx + plan.pat_ctx.size() * sizeof(uint32_t);
+    const size_t total = (o_mask + plan.acc_mask.size() + 15) & ~(size_t)15;
     std::vector<uint8_t> img(total, 0);
     memcpy(img.data(), plan.cls, 256);
-    memcpy(img.data() + o_first, plan.first, 512);
+    memcpy(img.data() + o_first, plan.first, 512 * (size_t)plan.contexts);
+    if (!plan.pat_ctx.empty()) memcpy(img.data() + o_pctx, plan.pat_ctx.data(), plan.pat_ctx.size() * sizeof(uint32_t));
+    if (!plan.acc_mask.empty()) memcpy(img.data() + o_mask, plan.acc_mask.data(), plan.acc_mask.size());
     memcpy(img.data() + o_pat, plan.pat_no.data(), plan.pat_no.size() * sizeof(uint32_t));
     memcpy(img.data() + o_tab, plan.table.data(), (size_t)plan.table_bytes());
     bzh_patset *set = new bzh_patset{};
@@ -41,6 +51,8 @@ static int regex_create(bzh_ctx *ctx, const uint8_t *const *exprs, const size_t 
     set->regex = true;
     set->rinfo = regex_info(plan);
     set->nterm = plan.nterm;
+    set->look = regex_look(plan);
+    for (uint32_t c = 0; c < BZR_CONTEXTS; c++) set->ctx_row |= (uint32_t)plan.ctx_row[c] << (8 * c);
     set->info = bzh_patset_info{plan.expressions, plan.expressions, plan.min_len, plan.max_len, plan.states, plan.classes, plan.table_bytes()};
     hipError_t e = hipSetDevice(ctx->device);
     if (e == hipSuccess) e = hipMalloc((void **)&set->d_mem, total);
@@ -54,17 +66,19 @@ static int regex_create(bzh_ctx *ctx, const uint8_t *const *exprs, const size_t 
     set->d_first = reinterpret_cast<const uint16_t *>(set->d_mem + o_first);
     set->d_pat_no = reinterpret_cast<const uint32_t *>(set->d_mem + o_pat);
     set->d_table = reinterpret_cast<const uint16_t *>(set->d_mem + o_tab);
+    set->d_pat_ctx = reinterpret_cast<const uint32_t *>(set->d_mem + o_pctx);
+    set->d_acc_mask = set->d_mem + o_mask;
     *out = set;
     return BZH_OK;
 }
 
-extern "C" int bzh_regex_create(bzh_ctx *ctx, const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags, uint32_t max_span,
-                                bzh_patset **out)
+extern "C" int bzh_regex_create_ex(bzh_ctx *ctx, const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags, uint32_t max_span,
+                                   unsigned syntax, bzh_patset **out)
 {
     if (!ctx || !out) return BZH_E_ARG;
     *out = nullptr;
     try {
-        return regex_create(ctx, exprs, lens, count, flags, max_span, out);
+        return regex_create(ctx, exprs, lens, count, flags, max_span, syntax, out);
     } catch (const std::bad_alloc &) {
         bzh_set_error(ctx, "host allocation failed");
         return BZH_E_NOMEM;
@@ -74,6 +88,19 @@ extern "C" int bzh_regex_create(bzh_ctx *ctx, const uint8_t *const *exprs, const
     }
 }
 
+extern "C" int bzh_regex_create(bzh_ctx *ctx, const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags, uint32_t max_span,
+                                bzh_patset **out)
+{
+    return bzh_regex_create_ex(ctx, exprs, lens, count, flags, max_span, 0, out);
+}
+
+extern "C" int bzh_regex_get_look(const bzh_patset *set, bzh_regex_look *out)
+{
+    if (!set || !out || !set->regex) return BZH_E_ARG;
+    *out = set->look;
+    return BZH_OK;
+}
+
 extern "C" int bzh_regex_get_info(const bzh_patset *set, bzh_regex_info *out)
 {
     if (!set || !out || !set->regex) return BZH_E_ARG;
@@ -81,14 +108,15 @@ extern "C" int bzh_regex_get_info(const bzh_patset *set, bzh_regex_info *out)
     return BZH_OK;
 }
 
-extern "C" int bzh_regex_check(const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags, uint32_t max_span, bzh_regex_info *info,
-                               char *err, size_t errn)
+extern "C" int bzh_regex_check_ex(const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags, uint32_t max_span, unsigned syntax,
+                                  bzh_regex_info *info, bzh_regex_look *look, char *err, size_t errn)
 {
     char why[200] = "";
     try {
         BzrPlan plan;
-        if (bzr_compile(exprs, lens, count, flags, max_span, plan, why, sizeof why)) {
+        if (bzr_compile_ex(exprs, lens, count, flags, max_span, syntax, plan, why, sizeof why)) {
             if (info) *info = regex_info(plan);
+            if (look) *look = regex_look(plan);
             if (err && errn) err[0] = 0;
             return BZH_OK;
         }
@@ -105,6 +133,12 @@ extern "C" int bzh_regex_check(const uint8_t *const *exprs, const size_t *lens, 
     return BZH_E_ARG;
 }
 
+extern "C" int bzh_regex_check(const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags, uint32_t max_span, bzh_regex_info *info,
+                               char *err, size_t errn)
+{
+    return bzh_regex_check_ex(exprs, lens, count, flags, max_span, 0, info, nullptr, err, errn);
+}
+
 template <bool LDS_ROWS>
 BzrMatcher<LDS_ROWS> regex_matcher(const bzh_patset *set, uint32_t delim, uint64_t lim)
 {
@@ -113,3 +147,12 @@ BzrMatcher<LDS_ROWS> regex_matcher(const bzh_patset *set, uint32_t delim, uint64
 }
 template BzrMatcher<true> regex_matcher<true>(const bzh_patset *, uint32_t, uint64_t);
 template BzrMatcher<false> regex_matcher<false>(const bzh_patset *, uint32_t, uint64_t);
+
+template <bool LDS_ROWS>
+BzrLookMatcher<LDS_ROWS> regex_look_matcher(const bzh_patset *set, uint32_t delim, uint64_t lim, uint64_t n, uint64_t edge_lo, uint32_t ctx_lo)
+{
+    return BzrLookMatcher<LDS_ROWS>{regex_matcher<LDS_ROWS>(set, delim, lim).a,
+                                    BzrLook{set->d_acc_mask, set->d_pat_ctx, set->look.contexts, set->ctx_row, set->look.look_ahead, ctx_lo, edge_lo, n}};
+}
+template BzrLookMatcher<true> regex_look_matcher<true>(const bzh_patset *, uint32_t, uint64_t, uint64_t, uint64_t, uint32_t);
+template BzrLookMatcher<false> regex_look_matcher<false>(const bzh_patset *, uint32_t, uint64_t, uint64_t, uint64_t, uint32_t);

@@ -8,7 +8,8 @@
 // THE SYNTAX is a subset of Python's `re` on bytes: literal bytes; the escapes \\ \. \[ \] \( \) \| \* \+ \? \{ \} \^ \$ \- \/ \n \t
 // \r \f \v \0 \xHH, and a backslash in front of any other ASCII byte that is no letter or digit (what re.escape writes); \d \D \w \W \s \S (ASCII, \s = [ \t\n\r\f\v]); `.` (any byte but 0x0A, any byte with BZR_DOTALL); [...] and
 // [^...] with ranges and those escapes (a negated class does take 0x0A); ( ) and (?: ), both plain grouping; | ; ? * + {m} {m,}
-// {m,n}.  Refused, naming the expression and the byte: anchors, \b and every other escape, backreferences, lookaround, lazy and
+// {m,n}.  With BZR_SYN_ASSERT the assertions ^ $ \A \Z \b \B, anywhere but in a class or under a quantifier (below: THE ASSERTIONS).
+// Refused, naming the expression and the byte: without that bit anchors and \b, every other escape, backreferences, lookaround, lazy and
 // possessive quantifiers, named groups, inline flags, a `{` that opens no well-formed bound, a bound above 256, an unbalanced
 // bracket, an expression that matches the empty string, one whose shortest match exceeds max_span.  With BZR_FOLD_ASCII the bytes
 // 'A'..'Z' and 'a'..'z' compare equal, in literals and in classes (a class is folded, then negated): re.IGNORECASE on bytes.
@@ -22,6 +23,18 @@
 // it); the other rows follow, all in breadth-first order from the root.  Bytes no expression can take share the dead class 0.
 // min_len: the shortest path to a terminal; max_len: min(the longest match, max_span); unbounded: some match could be longer than
 // max_span -- a cycle on a path to a terminal, or an acyclic longest path above the span.
+//
+// THE ASSERTIONS (bzr_compile_ex with BZR_SYN_ASSERT; the word and the line wrap BZR_SYN_WORD / BZR_SYN_LINE put one in front of and
+// one behind every expression).  An assertion sees the byte in front of its place and the byte behind it as CONTEXTS -- the text's
+// edge, 0x0A, a word byte, any other byte -- and is a mask over the 16 pairs; in the NFA an epsilon edge that is open between two
+// contexts of its mask.  The byte classes then refine the contexts.  A closure stops at an assertion; a subset in which one waits
+// names the context of the byte it last took, and the assertion is resolved when the next byte is taken or the match ends: states
+// multiply by at most the context count, under the same bound.  first[] holds one row per DISTINCT start row (contexts, at most 4;
+// ctx_row[c] the row of context c in front of the start, row 0 the text edge's = the table's row 0), every terminal the contexts
+// behind a match in which it accepts (acc_mask) and the lowest-numbered accepting expression for each (pat_ctx); the
+// minimisation's first partition separates states by that whole record.  look_behind / look_ahead: some assertion depends on the
+// context in front / behind.  A list without assertions compiles to the same plan whether they are admitted or not, with both 0.
+// min_len, max_len and unbounded count consumed bytes.  A list that can match nowhere (a^b) is refused.
 #ifndef BZH_REGEX_PLAN_H
 #define BZH_REGEX_PLAN_H
 #include <stddef.h>
@@ -30,6 +43,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <map>
 #include <string>
 #include <unordered_map>
@@ -48,16 +62,33 @@ enum : uint32_t {
     BZR_MAX_STATES = 65535,
     BZR_LDS_ENTRIES = 2048, // a table of at most that many entries is staged into LDS by every workgroup (regex_core.h)
 };
+// the syntax word of bzr_compile_ex, apart from the flags: ASSERT admits ^ $ \A \Z \b \B; WORD and LINE wrap every expression
+enum : uint32_t { BZR_SYN_ASSERT = 1, BZR_SYN_WORD = 2, BZR_SYN_LINE = 4 };
+// THE CONTEXTS an assertion sees in front of and behind its place: the text's edge, 0x0A, a word byte [0-9A-Za-z_], any other byte
+enum : uint32_t { BZR_CTX_EDGE = 0, BZR_CTX_NL = 1, BZR_CTX_WORD = 2, BZR_CTX_OTHER = 3, BZR_CONTEXTS = 4 };
+static inline uint32_t bzr_ctx_of(uint32_t b) // of a byte (regex_core.h's bzr_ctx is the same rule on the device)
+{
+    if (b == '\n') return BZR_CTX_NL;
+    return (b >= '0' && b <= '9') || (b >= 'A' && b <= 'Z') || (b >= 'a' && b <= 'z') || b == '_' ? BZR_CTX_WORD : BZR_CTX_OTHER;
+}
+// an assertion as the pairs (context in front, context behind) it holds for: bit 4 * front + behind
+enum : uint8_t { BZR_AT_BOL, BZR_AT_EOL, BZR_AT_BOT, BZR_AT_EOT, BZR_AT_WORDB, BZR_AT_NWORDB, BZR_AT_NOWORD_FRONT, BZR_AT_NOWORD_BEHIND, BZR_AT_KINDS };
+static const uint16_t BZR_AT_MASK[BZR_AT_KINDS] = {0x00FF, 0x3333, 0x000F, 0x1111, 0x4B44, 0xB4BB, 0xF0FF, 0xBBBB};
 
 struct BzrPlan {
     uint64_t expressions = 0;
     uint32_t min_len = 0, max_len = 0, max_span = 0;
     uint32_t states = 0, classes = 0, nterm = 0; // rows and columns of the table, the terminal rows 1 .. nterm
     uint32_t unbounded = 0, in_lds = 0;
+    uint32_t look_behind = 0, look_ahead = 0; // some assertion looks at the byte in front of a start / behind a match
+    uint32_t contexts = 1;                    // distinct start rows: first[contexts * 256]
+    uint8_t ctx_row[BZR_CONTEXTS] = {0, 0, 0, 0}; // the start row of a start whose front context is c
     uint8_t cls[256];
-    uint16_t first[256];
+    uint16_t first[BZR_CONTEXTS * 256];
     std::vector<uint16_t> table;  // [states * classes]
     std::vector<uint32_t> pat_no; // [nterm]
+    std::vector<uint8_t> acc_mask; // [nterm] with assertions: the contexts behind a match in which the terminal accepts, bit c
+    std::vector<uint32_t> pat_ctx; // [nterm * 4] ... and the lowest-numbered expression that accepts there
     uint64_t table_bytes() const { return (uint64_t)table.size() * sizeof(uint16_t); }
 };
 
@@ -86,11 +117,11 @@ struct BzrSet256 { // a set of byte values
     bool operator<(const BzrSet256 &o) const { return memcmp(w, o.w, sizeof w) < 0; }
 };
 
-enum : uint8_t { BZR_N_SET, BZR_N_CAT, BZR_N_ALT, BZR_N_REP };
+enum : uint8_t { BZR_N_SET, BZR_N_CAT, BZR_N_ALT, BZR_N_REP, BZR_N_LOOK };
 enum : uint32_t { BZR_NONE = 0xFFFFFFFFu, BZR_INF = 0xFFFFFFFFu };
 struct BzrNode {
     uint8_t kind;
-    uint32_t set = 0;             // SET: its index
+    uint32_t set = 0;             // SET: its index; LOOK: its BZR_AT_ kind
     uint32_t lo = 0, hi = 0;      // REP: the bound (hi == BZR_INF: open)
     std::vector<uint32_t> kids;   // CAT, ALT: any number (a CAT of none matches the empty string); REP: one
 };
@@ -108,6 +139,8 @@ struct BzrParser {
     size_t i = 0;
     uint32_t nest = 0;
     bool bad = false;
+    bool look = false;  // assertions are admitted
+    uint32_t kinds = 0; // those met, bit BZR_AT_
 
     uint32_t fail(size_t at, const char *why)
     {
@@ -175,6 +208,12 @@ struct BzrParser {
             return fail(at, "an escape that is not supported"), false;
         }
     }
+    uint32_t look_node(uint32_t kind)
+    {
+        BzrNode x{BZR_N_LOOK, 0, 0, 0, {}};
+        x.set = kind, kinds |= 1u << kind;
+        return node(std::move(x));
+    }
     uint32_t klass() // p[i] == '['
     {
         const size_t open = i++;
@@ -236,6 +275,7 @@ struct BzrParser {
             return r;
         }
         if (c == '[') return klass();
+        if ((c == '^' || c == '$') && look) return i++, look_node(c == '^' ? BZR_AT_BOL : BZR_AT_EOL);
         if (c == '^' || c == '$') return fail(at, "anchors are not supported");
         if (c == '*' || c == '+' || c == '?') return fail(at, "a quantifier with nothing to repeat");
         if (c == '{') return fail(at, "a { that opens no well-formed bound");
@@ -247,6 +287,11 @@ struct BzrParser {
             return set_node(s);
         }
         if (c == '\\') {
+            if (look && i + 1 < n && (p[i + 1] == 'b' || p[i + 1] == 'B' || p[i + 1] == 'A' || p[i + 1] == 'Z')) {
+                const uint8_t e = p[i + 1];
+                i += 2;
+                return look_node(e == 'b' ? BZR_AT_WORDB : e == 'B' ? BZR_AT_NWORDB : e == 'A' ? BZR_AT_BOT : BZR_AT_EOT);
+            }
             bool multi;
             if (!escape(s, &multi)) return BZR_NONE;
         } else {
@@ -289,6 +334,7 @@ struct BzrParser {
         } else {
             return a;
         }
+        if (nodes[a].kind == BZR_N_LOOK && p[at - 1] != ')') return fail(at, "a quantifier with nothing to repeat"); // (as re: an assertion is nothing to repeat)
         if (i < n && (p[i] == '?' || p[i] == '+')) return fail(i, "lazy and possessive quantifiers are not supported");
         if (i < n && (p[i] == '*' || p[i] == '{')) return fail(i, "a quantifier behind a quantifier");
         BzrNode x{BZR_N_REP, 0, 0, 0, {}};
@@ -336,6 +382,7 @@ static inline uint64_t bzr_min_len(const std::vector<BzrNode> &nodes, const std:
     uint64_t r = 0;
     switch (x.kind) {
     case BZR_N_SET: return sets[x.set].none() ? cap : 1;
+    case BZR_N_LOOK: return 0;
     case BZR_N_CAT:
         for (uint32_t k : x.kids) r = std::min(cap, r + bzr_min_len(nodes, sets, k));
         return r;
@@ -350,8 +397,9 @@ static inline uint64_t bzr_min_len(const std::vector<BzrNode> &nodes, const std:
 // ---- the NFA ----------------------------------------------------------------------------------------------------------------------
 struct BzrNfa {
     struct St {
-        int32_t set;     // >= 0: takes a byte of that set to `e1`; -1: the edges e1, e2 take nothing
-        uint32_t e1, e2;
+        int32_t set;     // >= 0: takes a byte of that set to `e1`; -1: the edges e1, e2 take nothing; -2: e1 takes nothing and is
+        uint32_t e1, e2; // open only between two contexts of `mask`
+        uint16_t mask;
     };
     std::vector<St> st;
     std::vector<int32_t> accept; // the expression that accepts in a state, or -1
@@ -362,7 +410,7 @@ struct BzrNfa {
     uint32_t add(int32_t set)
     {
         if (st.size() >= 8u * BZR_MAX_NFA) over = true;
-        st.push_back(St{set, BZR_NONE, BZR_NONE});
+        st.push_back(St{set, BZR_NONE, BZR_NONE, 0});
         return (uint32_t)st.size() - 1;
     }
     void edge(uint32_t from, uint32_t to)
@@ -383,6 +431,10 @@ struct BzrNfa {
             if (++positions > BZR_MAX_NFA) over = true;
             *s = add((int32_t)x.set), *e = add(-1);
             st[*s].e1 = *e;
+            return;
+        case BZR_N_LOOK:
+            *s = add(-2), *e = add(-1);
+            st[*s].e1 = *e, st[*s].mask = BZR_AT_MASK[x.set];
             return;
         case BZR_N_CAT: {
             *s = *e = add(-1);
@@ -441,10 +493,13 @@ struct BzrNfa {
     }
 };
 
-// Compiles exprs[0 .. count) into `out`.  max_span: 1 .. 256, 0 = 256.  Returns true, or false with the reason in err[0 .. errn).
-static inline bool bzr_compile(const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags, uint32_t max_span, BzrPlan &out,
-                               char *err, size_t errn)
+// Compiles exprs[0 .. count) into `out`.  max_span: 1 .. 256, 0 = 256.  syntax: BZR_SYN_*.  Returns true, or false with the reason
+// in err[0 .. errn).  A list that holds no assertion compiles to the same plan whatever `syntax` admits.
+static inline bool bzr_compile_ex(const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags, uint32_t max_span, unsigned syntax,
+                                  BzrPlan &out, char *err, size_t errn)
 {
+    if (syntax & ~(unsigned)(BZR_SYN_ASSERT | BZR_SYN_WORD | BZR_SYN_LINE)) return snprintf(err, errn, "regex: syntax 0x%x, of which only 0x7 are defined", syntax), false;
+    if ((syntax & BZR_SYN_WORD) && (syntax & BZR_SYN_LINE)) return snprintf(err, errn, "regex: the word wrap and the line wrap exclude each other"), false;
     if (count == 0 || count > BZR_MAX_PATTERNS) return snprintf(err, errn, "regex: %zu expressions, outside 1..%u", count, (unsigned)BZR_MAX_PATTERNS), false;
     if (!exprs || !lens) return snprintf(err, errn, "regex: a null array"), false;
     if (flags & ~(unsigned)(BZR_FOLD_ASCII | BZR_DOTALL | BZR_NO_LDS)) return snprintf(err, errn, "regex: flags 0x%x, of which only 0x7 are defined", flags), false;
@@ -460,10 +515,20 @@ static inline bool bzr_compile(const uint8_t *const *exprs, const size_t *lens, 
     std::vector<BzrSet256> sets;
     std::map<BzrSet256, uint32_t> set_ix;
     std::vector<uint32_t> roots(count);
+    uint32_t kinds = 0; // the assertions met
     for (size_t i = 0; i < count; i++) {
         BzrParser ps{exprs[i], lens[i], i, flags, err, errn, nodes, sets, set_ix};
+        ps.look = (syntax & BZR_SYN_ASSERT) != 0;
         roots[i] = ps.top();
         if (ps.bad) return false;
+        kinds |= ps.kinds;
+        if (syntax & (BZR_SYN_WORD | BZR_SYN_LINE)) { // the wrap: an assertion, the expression, an assertion
+            const bool word = (syntax & BZR_SYN_WORD) != 0;
+            const uint32_t a = ps.look_node(word ? BZR_AT_NOWORD_FRONT : BZR_AT_BOL), b = ps.look_node(word ? BZR_AT_NOWORD_BEHIND : BZR_AT_EOL);
+            BzrNode x{BZR_N_CAT, 0, 0, 0, {a, roots[i], b}};
+            roots[i] = ps.node(std::move(x));
+            kinds |= ps.kinds;
+        }
         const uint64_t mn = bzr_min_len(nodes, sets, roots[i]);
         if (mn == 0) return snprintf(err, errn, "regex: expression %zu, byte 0: it matches the empty string", i), false;
         if (mn > max_span) return snprintf(err, errn, "regex: expression %zu, byte 0: its shortest match exceeds max_span %u", i, max_span), false;
@@ -489,9 +554,26 @@ static inline bool bzr_compile(const uint8_t *const *exprs, const size_t *lens, 
     for (auto &pe : ends) nfa.accept[pe.first] = (int32_t)pe.second;
 
     // the classes: bytes that lie in the same sets
+    const bool looks = kinds != 0;
+    for (uint32_t k = 0; k < BZR_AT_KINDS; k++)
+        if (kinds >> k & 1u) {
+            const uint16_t m = BZR_AT_MASK[k];
+            for (uint32_t c = 0; c < BZR_CONTEXTS; c++) {
+                if ((m >> (4 * c) & 15u) != (m & 15u)) out.look_behind = 1;
+                if ((m >> (4 * c) & 15u) != 0 && (m >> (4 * c) & 15u) != 15u) out.look_ahead = 1;
+            }
+        }
     uint32_t tmp[256] = {};
     uint32_t ncls = 1;
-    for (const BzrSet256 &s : sets) {
+    std::vector<BzrSet256> splits(sets); // with assertions the classes refine the contexts as well
+    if (looks) {
+        BzrSet256 nl, word;
+        for (uint32_t b = 0; b < 256; b++)
+            if (bzr_ctx_of(b) == BZR_CTX_NL) nl.add(b);
+            else if (bzr_ctx_of(b) == BZR_CTX_WORD) word.add(b);
+        splits.push_back(nl), splits.push_back(word);
+    }
+    for (const BzrSet256 &s : splits) {
         std::map<std::pair<uint32_t, bool>, uint32_t> split_ix;
         uint32_t next = 0;
         for (uint32_t b = 0; b < 256; b++) {
@@ -530,41 +612,94 @@ static inline bool bzr_compile(const uint8_t *const *exprs, const size_t *lens, 
             if (stamp[v] == tick) continue;
             stamp[v] = tick;
             const BzrNfa::St &x = nfa.st[v];
-            if (x.set >= 0 || nfa.accept[v] >= 0) cur.push_back(v);
-            if (x.set < 0) {
+            if (x.set >= 0 || x.set == -2 || nfa.accept[v] >= 0) cur.push_back(v); // (an assertion stops the closure: its contexts are not known yet)
+            if (x.set == -1) {
                 if (x.e1 != BZR_NONE) stack.push_back(x.e1);
                 if (x.e2 != BZR_NONE) stack.push_back(x.e2);
             }
         }
     };
+    // WITH ASSERTIONS a subset that holds one also names the context of the byte it last took (its last element, BZR_TAG | context):
+    // the assertion is resolved when the next byte is taken, or the match ends, and both contexts are known.  `open`: the states of
+    // a subset that take a byte or accept between the contexts pc and nc -- the subset itself, and what lies behind its assertions
+    // that hold there.  Without assertions open() is the subset, and everything below is what it was.
+    const uint32_t BZR_TAG = 0xFFFFFFF0u;
+    std::vector<uint32_t> stamp2(looks ? nfa.st.size() : 0, 0), ex;
+    uint32_t tick2 = 0;
+    auto tag_of = [&](const std::vector<uint32_t> &sub) { return !sub.empty() && sub.back() >= BZR_TAG ? sub.back() - BZR_TAG : 0u; };
+    auto open = [&](const std::vector<uint32_t> &sub, uint32_t pc, uint32_t nc) -> const std::vector<uint32_t> & {
+        if (!looks || sub.empty() || sub.back() < BZR_TAG) return sub;
+        ex.clear(), tick2++;
+        std::vector<uint32_t> todo(sub.begin(), sub.end() - 1);
+        while (!todo.empty()) {
+            const uint32_t v = todo.back();
+            todo.pop_back();
+            if (stamp2[v] == tick2) continue;
+            stamp2[v] = tick2;
+            const BzrNfa::St &x = nfa.st[v];
+            if (x.set == -2) {
+                if (x.mask >> (4 * pc + nc) & 1u) todo.push_back(x.e1);
+            } else if (x.set == -1) {
+                if (nfa.accept[v] >= 0) ex.push_back(v);
+                if (x.e1 != BZR_NONE) todo.push_back(x.e1);
+                if (x.e2 != BZR_NONE) todo.push_back(x.e2);
+            } else {
+                ex.push_back(v);
+            }
+        }
+        return ex;
+    };
+    auto seal = [&](uint32_t pc) { // cur, sorted, and the context it was entered from if an assertion waits in it
+        std::sort(cur.begin(), cur.end());
+        bool waits = false;
+        for (uint32_t v : cur) waits = waits || nfa.st[v].set == -2;
+        if (waits) cur.push_back(BZR_TAG + pc);
+    };
     std::vector<std::vector<uint32_t>> subset;
-    std::map<std::vector<uint32_t>, uint32_t> subset_ix; // (the root is not in it: where its subset recurs it gets a row of its own)
+    std::map<std::vector<uint32_t>, uint32_t> subset_ix; // (the roots are not in it: where a root's subset recurs it gets a row of its own)
     std::vector<uint32_t> trans;                          // [states * ncls], 0 = dead
-    std::vector<int32_t> acc;
-    std::vector<uint32_t> depth_of{0}; // breadth-first: a subset's number ascends with its depth
-    bool cut = false;                  // a row max_span deep has a live transition: no walk takes it, so it is left dead
+    std::vector<int32_t> acc;                             // the lowest expression that accepts, behind whichever context
+    std::vector<uint32_t> accid;                          // ... and the number of the whole record, one expression a context
+    std::vector<std::array<int32_t, BZR_CONTEXTS>> acc4;
+    std::map<std::array<int32_t, BZR_CONTEXTS>, uint32_t> acc_ix;
+    std::vector<uint32_t> depth_of; // breadth-first: a subset's number ascends with its depth
+    bool cut = false;               // a row max_span deep has a live transition: no walk takes it, so it is left dead
     tick++, cur.clear(), closure_add(0);
-    std::sort(cur.begin(), cur.end());
-    subset.push_back(cur);
+    seal(0);
+    const uint32_t NR = cur.back() >= BZR_TAG ? (uint32_t)BZR_CONTEXTS : 1u; // the roots: one a context in front of the start, if it is looked at
+    for (uint32_t r = 0; r < NR; r++) {
+        if (NR > 1) cur.back() = BZR_TAG + r;
+        subset.push_back(cur), depth_of.push_back(0);
+    }
+    uint32_t ctx_cls[256]; // the context of a class's bytes (with assertions the classes refine them)
+    for (uint32_t c = 0; c < ncls; c++) ctx_cls[c] = looks ? bzr_ctx_of(rep[c]) : 0u;
     for (uint32_t d = 0; d < subset.size(); d++) {
+        const uint32_t pc = tag_of(subset[d]);
+        std::array<int32_t, BZR_CONTEXTS> a4;
         int32_t a = -1;
-        for (uint32_t v : subset[d])
-            if (nfa.accept[v] >= 0 && (a < 0 || nfa.accept[v] < a)) a = nfa.accept[v];
-        acc.push_back(a);
+        for (uint32_t nc = 0; nc < BZR_CONTEXTS; nc++) {
+            a4[nc] = -1;
+            for (uint32_t v : open(subset[d], pc, nc))
+                if (nfa.accept[v] >= 0 && (a4[nc] < 0 || nfa.accept[v] < a4[nc])) a4[nc] = nfa.accept[v];
+            if (a4[nc] >= 0 && (a < 0 || a4[nc] < a)) a = a4[nc];
+        }
+        acc.push_back(a), acc4.push_back(a4);
+        accid.push_back(acc_ix.emplace(a4, (uint32_t)acc_ix.size()).first->second);
         trans.resize((size_t)(d + 1) * ncls, 0);
         for (uint32_t c = 0; c < ncls; c++) {
             if (c == dead_cls) continue;
+            const std::vector<uint32_t> &from = open(subset[d], pc, ctx_cls[c]); // (read before subset grows below)
             if (depth_of[d] >= max_span) {
-                for (uint32_t v : subset[d]) cut = cut || (nfa.st[v].set >= 0 && sets[nfa.st[v].set].has(rep[c]));
+                for (uint32_t v : from) cut = cut || (nfa.st[v].set >= 0 && sets[nfa.st[v].set].has(rep[c]));
                 continue;
             }
             tick++, cur.clear();
-            for (size_t j = 0; j < subset[d].size(); j++) { // (by index: subset grows below)
-                const BzrNfa::St &x = nfa.st[subset[d][j]];
+            for (uint32_t v : from) {
+                const BzrNfa::St &x = nfa.st[v];
                 if (x.set >= 0 && sets[x.set].has(rep[c])) closure_add(x.e1);
             }
             if (cur.empty()) continue;
-            std::sort(cur.begin(), cur.end());
+            seal(ctx_cls[c]);
             auto it = subset_ix.find(cur);
             if (it == subset_ix.end()) {
                 if (subset.size() > BZR_MAX_STATES)
@@ -622,8 +757,8 @@ static inline bool bzr_compile(const uint8_t *const *exprs, const size_t *lens, 
             const uint32_t s = work.back();
             work.pop_back();
             peeled[s] = 1;
-            if (s) { // (every state behind its transitions has its block)
-                sig[0] = (uint32_t)(acc[s] + 1);
+            if (s >= NR) { // (every state behind its transitions has its block)
+                sig[0] = accid[s] + 1;
                 for (uint32_t c = 0; c < ncls; c++) sig[c + 1] = trans[(size_t)s * ncls + c] ? block[trans[(size_t)s * ncls + c]] : 0u;
                 block[s] = sig_ix.emplace(key(), (uint32_t)sig_ix.size() + 1).first->second;
             }
@@ -632,12 +767,12 @@ static inline bool bzr_compile(const uint8_t *const *exprs, const size_t *lens, 
         }
         const uint32_t fixed = (uint32_t)sig_ix.size() + 1; // blocks [0, fixed) stand
         std::vector<uint32_t> rest;
-        for (uint32_t s = 1; s < S; s++)
+        for (uint32_t s = NR; s < S; s++)
             if (live[s] && !peeled[s]) rest.push_back(s);
         nblocks = fixed;
         if (!rest.empty()) {
-            std::map<int32_t, uint32_t> by_acc;
-            for (uint32_t s : rest) block[s] = fixed + by_acc.emplace(acc[s], (uint32_t)by_acc.size()).first->second;
+            std::map<uint32_t, uint32_t> by_acc;
+            for (uint32_t s : rest) block[s] = fixed + by_acc.emplace(accid[s], (uint32_t)by_acc.size()).first->second;
             uint32_t parts = (uint32_t)by_acc.size();
             std::vector<uint32_t> nb(rest.size());
             for (;;) {
@@ -658,7 +793,7 @@ static inline bool bzr_compile(const uint8_t *const *exprs, const size_t *lens, 
     }
     // the rows: the root, and a member of every block but 0; numbered in breadth-first order, the terminals first
     std::vector<uint32_t> member(nblocks, BZR_NONE);
-    for (uint32_t s = S; s-- > 1;) member[block[s]] = s;
+    for (uint32_t s = S; s-- > NR;) member[block[s]] = s;
     auto target = [&](uint32_t s, uint32_t c) { // the block behind a transition; 0: dead
         const uint32_t t = trans[(size_t)s * ncls + c];
         return t ? block[t] : 0u;
@@ -666,10 +801,11 @@ static inline bool bzr_compile(const uint8_t *const *exprs, const size_t *lens, 
     std::vector<uint32_t> order, seen(nblocks, 0); // blocks in breadth-first order from the root
     {
         size_t head = 0;
-        for (uint32_t c = 0; c < ncls; c++) {
-            const uint32_t b = target(0, c);
-            if (b && !seen[b]) seen[b] = 1, order.push_back(b);
-        }
+        for (uint32_t r = 0; r < NR; r++)
+            for (uint32_t c = 0; c < ncls; c++) {
+                const uint32_t b = target(r, c);
+                if (b && !seen[b]) seen[b] = 1, order.push_back(b);
+            }
         while (head < order.size()) {
             const uint32_t s = member[order[head++]];
             for (uint32_t c = 0; c < ncls; c++) {
@@ -682,6 +818,7 @@ static inline bool bzr_compile(const uint8_t *const *exprs, const size_t *lens, 
     uint32_t nterm = 0, next = 0;
     for (uint32_t b : order)
         if (acc[member[b]] >= 0) nterm++;
+    if (nterm == 0) return snprintf(err, errn, "regex: no expression can match anywhere: its assertions contradict each other"), false; // (a^b)
     out.pat_no.assign(nterm, 0);
     next = nterm;
     {
@@ -699,17 +836,42 @@ static inline bool bzr_compile(const uint8_t *const *exprs, const size_t *lens, 
     for (uint32_t b : order)
         for (uint32_t c = 0; c < ncls; c++) out.table[(size_t)num[b] * ncls + c] = (uint16_t)num[target(member[b], c)];
     for (uint32_t b = 0; b < 256; b++) out.first[b] = out.table[out.cls[b]];
+    // the start rows: one a context in front of the start, equal ones merged; row 0 is the text edge's and the table's row 0
+    out.contexts = 1;
+    std::vector<uint16_t> extra; // the rows of the further roots, as the table would hold them
+    for (uint32_t r = 1; r < NR; r++) {
+        uint16_t row[256];
+        for (uint32_t b = 0; b < 256; b++) row[b] = (uint16_t)num[target(r, out.cls[b])];
+        uint32_t same = 0;
+        while (same < out.contexts && memcmp(out.first + 256 * same, row, sizeof row)) same++;
+        out.ctx_row[r] = (uint8_t)same;
+        if (same < out.contexts) continue;
+        memcpy(out.first + 256 * out.contexts++, row, sizeof row);
+        for (uint32_t c = 0; c < ncls; c++) extra.push_back((uint16_t)num[target(r, c)]);
+    }
+    for (uint32_t r = out.contexts; r < BZR_CONTEXTS; r++) memset(out.first + 256 * r, 0, 512);
+    if (looks) { // what a terminal accepts behind every context
+        out.acc_mask.assign(nterm, 0), out.pat_ctx.assign((size_t)nterm * BZR_CONTEXTS, 0);
+        for (uint32_t b : order)
+            if (num[b] <= nterm)
+                for (uint32_t c = 0; c < BZR_CONTEXTS; c++)
+                    if (acc4[member[b]][c] >= 0) out.acc_mask[num[b] - 1] |= (uint8_t)(1u << c), out.pat_ctx[(size_t)(num[b] - 1) * BZR_CONTEXTS + c] = (uint32_t)acc4[member[b]][c];
+    }
 
     // min_len: breadth-first depth of the first terminal; the longest match: a topological order of the rows (every row lies on a
     // path to a terminal), which a cycle leaves incomplete
-    const uint32_t R = out.states;
+    // (the further start rows stand behind the table's for this)
+    std::vector<uint16_t> all(out.table);
+    all.insert(all.end(), extra.begin(), extra.end());
+    const uint32_t R = (uint32_t)(all.size() / ncls);
     {
         std::vector<uint32_t> depth(R, BZR_NONE), q{0};
         depth[0] = 0;
+        for (uint32_t r = out.states; r < R; r++) depth[r] = 0, q.push_back(r);
         out.min_len = 0;
         for (size_t h = 0; h < q.size() && !out.min_len; h++)
             for (uint32_t c = 0; c < ncls; c++) {
-                const uint32_t t = out.table[(size_t)q[h] * ncls + c];
+                const uint32_t t = all[(size_t)q[h] * ncls + c];
                 if (!t || depth[t] != BZR_NONE) continue;
                 depth[t] = depth[q[h]] + 1;
                 if (t <= nterm) {
@@ -719,8 +881,9 @@ static inline bool bzr_compile(const uint8_t *const *exprs, const size_t *lens, 
                 q.push_back(t);
             }
         std::vector<uint32_t> indeg(R, 0), longest(R, 0), ready{0};
-        for (size_t e = 0; e < out.table.size(); e++)
-            if (out.table[e]) indeg[out.table[e]]++;
+        for (uint32_t r = out.states; r < R; r++) ready.push_back(r);
+        for (size_t e = 0; e < all.size(); e++)
+            if (all[e]) indeg[all[e]]++;
         uint32_t done = 0, far = 0;
         while (!ready.empty()) {
             const uint32_t s = ready.back();
@@ -728,7 +891,7 @@ static inline bool bzr_compile(const uint8_t *const *exprs, const size_t *lens, 
             done++;
             if (s && s <= nterm) far = std::max(far, longest[s]);
             for (uint32_t c = 0; c < ncls; c++) {
-                const uint32_t t = out.table[(size_t)s * ncls + c];
+                const uint32_t t = all[(size_t)s * ncls + c];
                 if (!t) continue;
                 longest[t] = std::max(longest[t], longest[s] + 1);
                 if (--indeg[t] == 0) ready.push_back(t);
@@ -741,6 +904,12 @@ static inline bool bzr_compile(const uint8_t *const *exprs, const size_t *lens, 
     out.max_span = max_span;
     out.in_lds = !(flags & BZR_NO_LDS) && out.table.size() <= BZR_LDS_ENTRIES;
     return true;
+}
+
+static inline bool bzr_compile(const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags, uint32_t max_span, BzrPlan &out,
+                               char *err, size_t errn)
+{
+    return bzr_compile_ex(exprs, lens, count, flags, max_span, 0, out, err, errn);
 }
 
 #endif // BZH_REGEX_PLAN_H

@@ -753,7 +753,7 @@ BZH_API int bzh_grep_patset_index(bzh_ctx *ctx, const uint8_t *in, size_t n, con
  * their union -- a DFA anchored at its start, in the shape of a set's trie -- which every start position of the text walks.  The
  * syntax is a subset of Python's `re` on bytes: literal bytes; \\ \. \[ \] \( \) \| \* \+ \? \{ \} \^ \$ \- \/ \n \t \r \f \v \0
  * \xHH and a backslash in front of any other ASCII byte that is no letter or digit; \d \D \w \W \s \S (ASCII); `.` (any byte but 0x0A; any byte with BZH_REGEX_DOTALL); [...] and [^...] with ranges;
- * ( ) and (?: ), both plain grouping; | ; ? * + {m} {m,} {m,n}.  Anchors, \b, backreferences, lookaround, lazy and possessive
+ * ( ) and (?: ), both plain grouping; | ; ? * + {m} {m,} {m,n}.  Anchors and \b (admitted by the _ex calls below), backreferences, lookaround, lazy and possessive
  * quantifiers, named groups, inline flags, a { that opens no well-formed bound, a bound above 256, an unbalanced bracket, an
  * expression that matches the empty string and one whose shortest match exceeds max_span are refused with BZH_E_ARG, the
  * message naming the expression's number and the byte.  So is an automaton above 65,536 NFA positions or 65,535 DFA states.
@@ -782,6 +782,37 @@ BZH_API int bzh_regex_get_info(const bzh_patset *set, bzh_regex_info *out); /* B
  * err[0 .. errn) (null allowed). */
 BZH_API int bzh_regex_check(const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags, uint32_t max_span,
                             bzh_regex_info *info, char *err, size_t errn);
+
+/* ASSERTIONS.  The three calls above refuse every anchor and \b, as they always have.  The _ex calls take a SYNTAX word beside the
+ * flags: BZH_REGEX_ASSERT admits ^ $ \A \Z \b \B anywhere in an expression (a$\n^b, foo\b bar, (^|,)x; \b inside a class stays
+ * refused, and so does an assertion under a quantifier, as in Python).  ONE RULE on every route -- Python's `re` on bytes under
+ * re.MULTILINE:
+ *     ^    at output offset 0 of the whole decoded text, and behind every byte 0x0A
+ *     $    at the end of the whole decoded text, and in front of every byte 0x0A
+ *     \A   only at output offset 0            \Z   only at the end of the whole decoded text
+ *     \b   one neighbour is in [0-9A-Za-z_] and the other is not; the text's two ends count as "not".  \B: the opposite
+ * Line anchors are about 0x0A, as `.` is, whatever the `delim` of the call; folding does not change what a word byte is.  An
+ * assertion consumes nothing: min_len, max_len, max_span and a hit's len count consumed bytes, and an expression that can match the
+ * empty string (^, ^$, \b) stays refused.  A hit must lie in the wanted range; its assertions see the REAL neighbours, those outside
+ * the range included, so the hits are the same whichever route reports them and whatever the window size.
+ * BZH_REGEX_WORD matches every expression e as grep -w does: e, not preceded and not followed by a word byte -- Python's
+ * (?<![0-9A-Za-z_])(?:e)(?![0-9A-Za-z_]), every length of e tried.  BZH_REGEX_LINE matches ^(?:e)$, as grep -x.  The two exclude
+ * each other; either works without BZH_REGEX_ASSERT.
+ * THE RANGE ROUTES.  An automaton that looks around (bzh_regex_look) needs the byte in front of the wanted range and the byte
+ * behind it: bzh_search_patset_range* decode the blocks of [off - look_behind, off + len + look_ahead), clipped to the output, and
+ * still report only the hits wholly inside [off, off + len).  The _device variant must be handed the compressed bytes of that
+ * WIDENED span: bzh_index_span on the widened range. */
+enum { BZH_REGEX_ASSERT = 1, BZH_REGEX_WORD = 2, BZH_REGEX_LINE = 4 };
+typedef struct {
+    uint32_t look_behind, look_ahead; /* 0 or 1: some assertion sees the byte in front of a start / behind a match */
+    uint32_t contexts;                /* distinct start rows, 1..4 */
+    uint32_t reserved;
+} bzh_regex_look;    /* 16 bytes */
+BZH_API int bzh_regex_create_ex(bzh_ctx *ctx, const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags,
+                                uint32_t max_span, unsigned syntax, bzh_patset **out);
+BZH_API int bzh_regex_check_ex(const uint8_t *const *exprs, const size_t *lens, size_t count, unsigned flags, uint32_t max_span,
+                               unsigned syntax, bzh_regex_info *info, bzh_regex_look *look, char *err, size_t errn);
+BZH_API int bzh_regex_get_look(const bzh_patset *set, bzh_regex_look *out); /* BZH_E_ARG for a set of plain strings */
 
 /* ---- the encoder writes the index of its own stream: no decode pass to rediscover what it held -------------------------- */
 
