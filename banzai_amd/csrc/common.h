@@ -622,14 +622,14 @@ int decode_range_sink_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, uint64_t 
 int scan_room(bzh_ctx *ctx, const char *what, uint64_t carry, uint64_t bytes, uint64_t *staging_peak, uint8_t **d_stage, uint64_t *front);
 int scan_tiles(bzh_ctx *ctx, const char *who, uint64_t n, uint64_t *windows, uint64_t *tiles_sum, uint32_t *tiles);
 // patset.hip: a compiled set of patterns (patset_plan.h), resident on its device in one allocation of its own -- it belongs to no
-// context.  set_matcher: the set as the kernels take it, for a window whose matches end at or in front of lim
+// context.  (As the kernels take it: matcher_pick.h)
 struct bzh_patset {
     int device;
     bzh_patset_info info;
-    bool regex = false;    // regex.hip made it: the table is a DFA's (regex_plan.h), the matcher BzrMatcher
+    bool regex = false;    // regex.hip made it: the table is a DFA's (regex_plan.h), the matcher BzrMatcher<.., false>
     bzh_regex_info rinfo{};
     uint32_t nterm = 0;    // of a regex: the terminal rows 1 .. nterm (a set's: info.distinct)
-    bzh_regex_look look{}; // of a regex with assertions: what it looks at (both 0: none, and the matcher is BzrMatcher)
+    bzh_regex_look look{}; // of a regex with assertions: what it looks at (both 0: none; else the matcher is BzrMatcher<.., true>)
     uint32_t ctx_row = 0;  // ... the start row of context c in bits [8 c, 8 c + 8)
     uint8_t *d_mem; // cls[256], first[256 * contexts], pat_no[distinct], table[states * classes]; with assertions pat_ctx[4 nterm], acc_mask[nterm]
     const uint8_t *d_cls;
@@ -639,19 +639,6 @@ struct bzh_patset {
     const uint8_t *d_acc_mask = nullptr;
     bool looks() const { return look.look_behind || look.look_ahead; }
 };
-struct BzmMatcher;
-BzmMatcher set_matcher(const bzh_patset *set, uint32_t delim, uint64_t lim);
-// regex.hip: a set that bzh_regex_create made, as the kernels take it -- its table staged in LDS (set->rinfo.in_lds) or not
-template <bool LDS_ROWS>
-struct BzrMatcher;
-template <bool LDS_ROWS>
-BzrMatcher<LDS_ROWS> regex_matcher(const bzh_patset *set, uint32_t delim, uint64_t lim);
-// ... of a set with assertions (set->looks()), for a window of n bytes: edge_lo is the position no byte lies in front of, ctx_lo the
-// context that stands there (regex_core.h: the look-around variant)
-template <bool LDS_ROWS>
-struct BzrLookMatcher;
-template <bool LDS_ROWS>
-BzrLookMatcher<LDS_ROWS> regex_look_matcher(const bzh_patset *set, uint32_t delim, uint64_t lim, uint64_t n, uint64_t edge_lo, uint32_t ctx_lo);
 // search.hip: the search over decoded bytes in HBM.  A sink is what is looked for, where the hits go, and the walk over its windows
 // (search_plan.h): room() puts the carry in front of the window, window() runs the two passes and keeps the window's tail.
 struct SearchSink final : WindowSink {
@@ -660,7 +647,7 @@ struct SearchSink final : WindowSink {
     bool records;
     void *hits; // host: bzh_hit, or bzh_set_hit
     uint64_t max;
-    BzrLookWalk walk; // (window_look with a set that looks around)
+    BzmSetWalk walk; // (a single pattern keeps to BzfWalk's part of it)
     SearchSink(const uint8_t *pat_, size_t plen, unsigned flags, uint8_t delim_, bzh_hit *hits_, size_t max_)
         : WindowSink(BZF_FRONT, delim_), pat(bzf_pattern(pat_, (uint32_t)plen, delim_)), records((flags & BZH_SEARCH_RECORDS) != 0), hits(hits_), max(max_) {}
     SearchSink(const bzh_patset *set_, unsigned flags, uint8_t delim_, bzh_set_hit *hits_, size_t max_)

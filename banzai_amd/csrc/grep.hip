@@ -5,8 +5,7 @@
 // window, and the selected records.
 #include "common.h"
 #include "grep_core.h"
-#include "patset_core.h"
-#include "regex_core.h"
+#include "matcher_pick.h"
 
 static_assert(sizeof(bzh_grep_entry) == 32 && sizeof(BzgEntry) == sizeof(bzh_grep_entry), "an entry is four words");
 static_assert(sizeof(BzgTile) == 32 && sizeof(BzgBase) == 24, "the tile tables");
@@ -111,28 +110,14 @@ __global__ void __launch_bounds__(BZF_THREADS) grep_scan(BzgTile *tile, uint32_t
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-// f(the sink's matcher): its pattern, or its set or automaton bounded by the text's end
-template <class F>
-static void grep_matcher(const GrepSink &g, const BzgWindow &w, F &&f)
-{
-    const uint64_t n = w.n;
-    if (g.set && g.set->looks()) { // the text begins at a record start: the text's edge at output offset 0, else the delimiter stands in front of it
-        const uint32_t ctx_lo = w.off_base + w.t_lo == 0 ? (uint32_t)BZR_LOOK_EDGE : bzr_ctx(g.delim);
-        if (g.set->rinfo.in_lds) f(regex_look_matcher<true>(g.set, g.delim, n, n, w.t_lo, ctx_lo));
-        else f(regex_look_matcher<false>(g.set, g.delim, n, n, w.t_lo, ctx_lo));
-    } else if (g.set && g.set->regex) {
-        if (g.set->rinfo.in_lds) f(regex_matcher<true>(g.set, g.delim, n));
-        else f(regex_matcher<false>(g.set, g.delim, n));
-    } else if (g.set) f(set_matcher(g.set, g.delim, n));
-    else f(BzfOne{g.pat});
-}
-
 // The passes over the window w of d (16-byte aligned; w.n bytes lie there, and the aligned word that holds the last of them).  One
 // wait, for the window's totals; bytes and entries follow the stream and are there after the call's last wait.
 static int grep_window_run(bzh_ctx *ctx, GrepSink &g, const uint8_t *d, const BzgWindow &w, uint64_t bytes)
 {
     hipStream_t st = ctx->stream;
     bzh_grep_stats &gs = ctx->gstats;
+    // the text begins at a record start: the text's edge at output offset 0, else the delimiter stands in front of it
+    const BzfPick pick{w.n, w.n, w.t_lo, w.off_base + w.t_lo == 0 ? (uint32_t)BZR_LOOK_EDGE : bzr_ctx(g.delim)};
     uint32_t tiles;
     BZH_TRY(scan_tiles(ctx, "grep", w.n, &gs.windows, &gs.tiles, &tiles));
     uint64_t totals[BZG_TOTALS] = {0, 0, 0, w.t_lo, w.open_hit};
@@ -143,7 +128,7 @@ static int grep_window_run(bzh_ctx *ctx, GrepSink &g, const uint8_t *d, const Bz
         BZH_TRY(reserve_cut(ctx, ctx->grep_tab, "the grep's tile tables", grow_mib,
                             [&](Carver &c) { c.put(tile, tiles), c.put(base, tiles), c.put(d_tot, BZG_TOTALS); }));
         GfArgs a{d, w, tile, base, nullptr, nullptr};
-        grep_matcher(g, w, [&](const auto &m) { grep_tiles<false><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
+        pick_matcher(g.pat, g.set, g.delim, pick, [&](const auto &m) { grep_tiles<false><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
         grep_scan<<<dim3(1), BZF_THREADS, 0, st>>>(tile, tiles, base, w, d_tot);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(totals, d_tot, sizeof totals, hipMemcpyDeviceToHost, st));
@@ -154,7 +139,7 @@ static int grep_window_run(bzh_ctx *ctx, GrepSink &g, const uint8_t *d, const Bz
                 BZH_TRY(ctx->grep_ent.reserve(ctx, (size_t)totals[BZG_T_SEL] * sizeof(BzgEntry), "the grep's entries", grow_mib));
                 a.ent = ctx->grep_ent.as<BzgEntry>();
             }
-            grep_matcher(g, w, [&](const auto &m) { grep_tiles<true><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
+            pick_matcher(g.pat, g.set, g.delim, pick, [&](const auto &m) { grep_tiles<true><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
             HIP_TRY(ctx, hipGetLastError());
             if (a.ent)
                 HIP_TRY(ctx, hipMemcpyAsync(g.ent + w.sel_base, a.ent, (size_t)totals[BZG_T_SEL] * sizeof(BzgEntry), hipMemcpyDeviceToHost, st));

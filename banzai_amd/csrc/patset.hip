@@ -78,8 +78,3 @@ extern "C" int bzh_patset_get_info(const bzh_patset *set, bzh_patset_info *out)
     *out = set->info;
     return BZH_OK;
 }
-
-BzmMatcher set_matcher(const bzh_patset *set, uint32_t delim, uint64_t lim)
-{
-    return BzmMatcher{BzmSet{set->d_cls, set->d_first, set->d_table, set->d_pat_no, set->info.classes, (uint32_t)set->info.distinct, set->info.max_len, delim, lim}};
-}

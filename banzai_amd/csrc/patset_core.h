@@ -135,22 +135,22 @@ struct BzfHit { // bzh_hit
 struct BzfOneShared {
     __attribute__((aligned(4))) uint8_t pat[BZF_MAX_PATTERN];
 };
-struct BzfOne { // the single pattern of search_core.h
+template <class M>
+struct BzfOnePerStart { // count16 of a matcher M whose starts hold one hit each (the single pattern, an automaton): an empty base
+    template <class S>
+    BZF_MEM uint32_t count16(const BzfVec &own, uint32_t tid, uint64_t p0, const uint8_t *tile, const S &sh, uint32_t valid, uint32_t *hm) const
+    {
+        return (uint32_t)__builtin_popcount(*hm = static_cast<const M *>(this)->match16(own, tid, p0, tile, sh, valid));
+    }
+};
+struct BzfOne : BzfOnePerStart<BzfOne> { // the single pattern of search_core.h
     using Shared = BzfOneShared;
     using Hit = BzfHit;
     static constexpr bool BY_LIM = false;
     BzfPattern p;
     BZF_MEM uint32_t delim() const { return p.delim; }
     BZF_MEM BzfVec stage(const uint8_t *d, uint64_t n, uint64_t t0, uint32_t tid, uint8_t *tile, Shared &sh) const { return bzf_stage(d, n, t0, tid, p, tile, sh.pat); }
-    BZF_MEM uint32_t match16(const BzfVec &own, uint32_t tid, uint64_t, const uint8_t *tile, const Shared &sh, uint32_t valid) const
-    {
-        return bzf_match16(own, tid, p, tile, sh.pat, valid);
-    }
-    BZF_MEM uint32_t count16(const BzfVec &own, uint32_t tid, uint64_t p0, const uint8_t *tile, const Shared &sh, uint32_t valid, uint32_t *hm) const
-    {
-        *hm = match16(own, tid, p0, tile, sh, valid);
-        return (uint32_t)__builtin_popcount(*hm);
-    }
+    BZF_MEM uint32_t match16(const BzfVec &own, uint32_t tid, uint64_t, const uint8_t *tile, const Shared &sh, uint32_t valid) const { return bzf_match16(own, tid, p, tile, sh.pat, valid); }
     BZF_MEM uint64_t emit1(const Shared &, const uint8_t *, uint64_t, uint64_t off, uint64_t rec, Hit *out, uint64_t rank, uint64_t emit) const
     {
         if (rank < emit) out[rank] = Hit{off, rec};

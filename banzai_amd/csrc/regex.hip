@@ -1,6 +1,6 @@
 // regex.hip -- regular expressions on the device (bzh_regex_*): the compile is regex_plan.h's, host-only text; here its automaton
 // is uploaded as patset.hip uploads a trie -- one allocation that belongs to no context -- and becomes a bzh_patset of its own
-// kind, which search.hip's search_matcher and grep.hip's grep_matcher hand to their kernels as the matcher of regex_core.h.  Every
+// kind, which matcher_pick.h hands to the kernels of search.hip and grep.hip as the matcher of regex_core.h.  Every
 // window, carry, scan, sink and entry point is the set's.
 #include "common.h"
 #include "regex_core.h"
@@ -138,21 +138,3 @@ extern "C" int bzh_regex_check(const uint8_t *const *exprs, const size_t *lens, 
 {
     return bzh_regex_check_ex(exprs, lens, count, flags, max_span, 0, info, nullptr, err, errn);
 }
-
-template <bool LDS_ROWS>
-BzrMatcher<LDS_ROWS> regex_matcher(const bzh_patset *set, uint32_t delim, uint64_t lim)
-{
-    return BzrMatcher<LDS_ROWS>{BzrAuto{BzmSet{set->d_cls, set->d_first, set->d_table, set->d_pat_no, set->info.classes, set->nterm, set->info.max_len, delim, lim},
-                                        set->info.states * set->info.classes}};
-}
-template BzrMatcher<true> regex_matcher<true>(const bzh_patset *, uint32_t, uint64_t);
-template BzrMatcher<false> regex_matcher<false>(const bzh_patset *, uint32_t, uint64_t);
-
-template <bool LDS_ROWS>
-BzrLookMatcher<LDS_ROWS> regex_look_matcher(const bzh_patset *set, uint32_t delim, uint64_t lim, uint64_t n, uint64_t edge_lo, uint32_t ctx_lo)
-{
-    return BzrLookMatcher<LDS_ROWS>{regex_matcher<LDS_ROWS>(set, delim, lim).a,
-                                    BzrLook{set->d_acc_mask, set->d_pat_ctx, set->look.contexts, set->ctx_row, set->look.look_ahead, ctx_lo, edge_lo, n}};
-}
-template BzrLookMatcher<true> regex_look_matcher<true>(const bzh_patset *, uint32_t, uint64_t, uint64_t, uint64_t, uint32_t);
-template BzrLookMatcher<false> regex_look_matcher<false>(const bzh_patset *, uint32_t, uint64_t, uint64_t, uint64_t, uint32_t);

@@ -5,8 +5,7 @@
 // is a word a window, and the hits.
 #include "common.h"
 #include "search_core.h"
-#include "patset_core.h"
-#include "regex_core.h"
+#include "matcher_pick.h"
 
 static_assert(BZF_MAX_PATTERN == BZH_SEARCH_MAX_PATTERN, "search_core.h and bzhip.h name the same bound");
 static_assert(BZF_FRONT % 16 == 0 && BZF_FRONT >= BZF_MAX_PATTERN, "a window begins aligned, its carry in front of it");
@@ -140,20 +139,6 @@ int scan_tiles(bzh_ctx *ctx, const char *who, uint64_t n, uint64_t *windows, uin
 }
 
 // ---- host side: the search ---------------------------------------------------------------------------------------------------------
-// f(the sink's matcher): its pattern, or its set or automaton bounded by lim
-template <class F>
-static void search_matcher(const SearchSink &s, const BzfWindow &w, uint64_t lim, F &&f)
-{
-    if (s.looks()) { // (output offset 0 lies at position 0 - off_base: the text's edge stands in front of it)
-        if (s.set->rinfo.in_lds) f(regex_look_matcher<true>(s.set, s.delim, lim, w.n, 0 - w.off_base, BZR_LOOK_EDGE));
-        else f(regex_look_matcher<false>(s.set, s.delim, lim, w.n, 0 - w.off_base, BZR_LOOK_EDGE));
-    } else if (s.set && s.set->regex) {
-        if (s.set->rinfo.in_lds) f(regex_matcher<true>(s.set, s.delim, lim));
-        else f(regex_matcher<false>(s.set, s.delim, lim));
-    } else if (s.set) f(set_matcher(s.set, s.delim, lim));
-    else f(BzfOne{s.pat});
-}
-
 // The two passes over the window w of d (16-byte aligned; w.n bytes lie there, and the aligned word that holds the last of them).
 // One wait, for the window's two totals; the hits follow the stream to the caller's array and are there after the call's last wait.
 // lim: where a set's matches end (search_plan.h: BzmSetWalk).
@@ -161,6 +146,7 @@ static int search_window_run(bzh_ctx *ctx, SearchSink &s, const uint8_t *d, BzfW
 {
     hipStream_t st = ctx->stream;
     bzh_search_stats &ss = ctx->sstats;
+    const BzfPick pick{lim, w.n, 0 - w.off_base, BZR_LOOK_EDGE}; // (output offset 0 lies at position 0 - off_base: the text's edge stands in front of it)
     uint32_t tiles;
     BZH_TRY(scan_tiles(ctx, "search", w.n, &ss.windows, &ss.tiles, &tiles));
     uint64_t totals[2] = {0, 0};
@@ -171,7 +157,7 @@ static int search_window_run(bzh_ctx *ctx, SearchSink &s, const uint8_t *d, BzfW
             c.put(hbase, tiles), c.put(dbase, tiles), c.put(d_tot, 2), c.put(thits, tiles), c.put(tdel, tiles);
         }));
         SfArgs a{d, w, s.records ? 1u : 0u, thits, tdel, hbase, dbase, nullptr};
-        search_matcher(s, w, lim, [&](const auto &m) { search_tiles<false><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
+        pick_matcher(s.pat, s.set, s.delim, pick, [&](const auto &m) { search_tiles<false><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
         search_scan<<<dim3(1), BZF_THREADS, 0, st>>>(thits, tdel, tiles, hbase, dbase, d_tot);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(totals, d_tot, sizeof totals, hipMemcpyDeviceToHost, st));
@@ -182,12 +168,12 @@ static int search_window_run(bzh_ctx *ctx, SearchSink &s, const uint8_t *d, BzfW
             BZH_TRY(ctx->search_out.reserve(ctx, (size_t)emit * hs, "the search's hits", grow_mib));
             a.win.emit = emit;
             a.out = ctx->search_out.p;
-            search_matcher(s, w, lim, [&](const auto &m) { search_tiles<true><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
+            pick_matcher(s.pat, s.set, s.delim, pick, [&](const auto &m) { search_tiles<true><<<dim3(tiles), BZF_THREADS, 0, st>>>(a, m); });
             HIP_TRY(ctx, hipGetLastError());
             HIP_TRY(ctx, hipMemcpyAsync((uint8_t *)s.hits + (size_t)s.walk.rank * hs, a.out, (size_t)emit * hs, hipMemcpyDeviceToHost, st));
         }
     }
-    if (s.looks()) s.walk.advance_look(bytes, totals[0], totals[1], last);
+    if (s.set) s.walk.advance_set(bytes, totals[0], totals[1], last);
     else s.walk.advance(bytes, totals[0], totals[1]);
     ss.hits = s.walk.rank;
     return BZH_OK;
@@ -204,8 +190,8 @@ int SearchSink::window(bzh_ctx *ctx, uint64_t bytes)
 {
     const uint8_t *base = ctx->search_ws.p;
     uint64_t lim = 0; // (of a set's window)
-    const BzfWindow w = looks() ? walk.window_look(bytes, false, &lim) : set ? walk.window_set(bytes, false, &lim) : walk.window(bytes);
-    const uint64_t keep = looks() ? walk.carry_after_look(bytes) : walk.carry_after(bytes);
+    const BzfWindow w = set ? walk.window_set(bytes, false, &lim) : walk.window(bytes);
+    const uint64_t keep = set ? walk.carry_after_set(bytes) : walk.carry_after(bytes);
     if (keep) { // [n - keep, n): read before the passes' wait, written where no pass looks
         BZH_TRY(ctx->scan_carry.reserve(ctx, BZF_MAX_PATTERN + 16, "the search's carry")); // (with assertions up to 257 bytes)
         HIP_TRY(ctx, hipMemcpyAsync(ctx->scan_carry, base + w.n - keep, (size_t)keep, hipMemcpyDeviceToDevice, ctx->stream));
@@ -219,7 +205,7 @@ int search_raw_run(bzh_ctx *ctx, SearchSink &sink, const uint8_t *d_raw, size_t 
     sink.walk.begin(sink.plen(), 0, sink.max, 0, n, 0, 0);
     sink.walk.begin_look(sink.look_behind, sink.look_ahead);
     uint64_t lim = 0;
-    const BzfWindow w = sink.looks() ? sink.walk.window_look(n, true, &lim) : sink.set ? sink.walk.window_set(n, true, &lim) : sink.walk.window(n);
+    const BzfWindow w = sink.set ? sink.walk.window_set(n, true, &lim) : sink.walk.window(n);
     return search_window_run(ctx, sink, d_raw, w, lim, n, true);
 }
 
@@ -230,6 +216,6 @@ int search_finish(bzh_ctx *ctx, SearchSink &sink)
     if (!sink.set || !sink.walk.carry) return BZH_OK;
     sink.walk.front = sink.walk.carry;
     uint64_t lim = 0;
-    const BzfWindow w = sink.looks() ? sink.walk.window_look(0, true, &lim) : sink.walk.window_set(0, true, &lim);
+    const BzfWindow w = sink.walk.window_set(0, true, &lim);
     return search_window_run(ctx, sink, ctx->scan_carry, w, lim, 0, true);
 }

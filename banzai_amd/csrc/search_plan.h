@@ -86,14 +86,32 @@ struct BzfWalk {
     }
 };
 
-// THE WALK OF A SET SEARCH (bzh_search_patset*).  Hits are pairs (start, pattern) and ascend by start, then by length; with several
-// lengths "a window reports the matches that end inside it" would break that order, so the grep's hold-back is used instead:
-//   * a window that is not the last processes the STARTS in front of its last max_len - 1 bytes; those bytes are carried, and the
-//     next window, which sees every match from there to its end, processes them;
+// THE HOLD-BACK WALK of a set search (bzh_search_patset*; an automaton is a set here).  Hits are pairs (start, pattern) and ascend
+// by start, then by length; with several lengths "a window reports the matches that end inside it" would break that order, so the
+// grep's hold-back is used instead.  An automaton with assertions (regex_core.h: LOOK) sees one byte in front of a start
+// (look_behind) and one byte behind a match (look_ahead); NO ASSERTION is the case where both are 0, and ctxb stays 0 with them.
+// plen holds max_len.
+//   * a window that is not the last processes the STARTS in front of its last max_len - 1 + look_ahead bytes: a match from a
+//     processed start ends look_ahead bytes in front of the window's end at the latest, so the byte behind it lies in the window.
+//     The bytes held back are carried, and the next window, which sees every match from there to its end, processes them;
 //   * the last window processes every start; a match is bounded by *lim, the end of the text or of the wanted range;
-//   * the call therefore ends with a finishing window over the carry, without new bytes, when bytes are held back.
-// The delimiters of the carry were counted by the window that held it back, as above.  plen holds max_len.
+//   * the call therefore ends with a finishing window over the carry, without new bytes, when bytes are held back;
+//   * the carry keeps look_behind more bytes, in front of the first start no window has processed: CONTEXT ONLY (`ctxb` of them,
+//     none while the first unprocessed start is the first byte the call has seen).  Such a byte is never a start;
+//   * the delimiters of the carry were counted by the window that held it back, as above;
+//   * the longest carry is max_len + 1 = 257 bytes, below BZF_FRONT;
+//   * the position of output offset 0 in a window is 0 - off_base: there the context in front is the text's edge.
 struct BzmSetWalk : BzfWalk {
+    uint32_t look_behind = 0, look_ahead = 0;
+    uint64_t ctxb = 0; // bytes of the carry in front of the first unprocessed start
+
+    void begin_look(uint32_t look_behind_, uint32_t look_ahead_) { look_behind = look_behind_, look_ahead = look_ahead_, ctxb = 0; }
+    // the first start (output offset) the windows up to this one leave unprocessed
+    uint64_t next_start(uint64_t bytes, bool last) const
+    {
+        const uint64_t end = out_pos + bytes, keep = (uint64_t)plen - 1 + look_ahead, held = out_pos - carry + ctxb;
+        return last ? end : (end - held > keep ? end - keep : held);
+    }
     // the next window: `bytes` new bytes at `front`; last: nothing follows
     BzfWindow window_set(uint64_t bytes, bool last, uint64_t *lim) const
     {
@@ -105,9 +123,8 @@ struct BzmSetWalk : BzfWalk {
         w.rec_base = recs;
         w.s_lo = w.s_hi = front;
         *lim = w.n;
-        const uint64_t end = out_pos + bytes, keep = (uint64_t)plen - 1;
-        const uint64_t held = out_pos - carry;                              // the first start no window has processed
-        const uint64_t p_hi = last ? end : (end - held > keep ? end - keep : held);
+        const uint64_t end = out_pos + bytes, held = out_pos - carry + ctxb; // held: the first start no window has processed
+        const uint64_t p_hi = next_start(bytes, last);
         const uint64_t from = held > lo ? held : lo;
         const uint64_t bound = end < hi ? end : hi;                         // a reported match ends at or in front of it
         const uint64_t upto = p_hi < bound ? p_hi : bound;
@@ -118,61 +135,17 @@ struct BzmSetWalk : BzfWalk {
         }
         return w;
     }
-};
-
-// THE WALK OF A SEARCH WITH ASSERTIONS (regex_core.h: the look-around variant).  An assertion sees one byte in front of a start
-// (look_behind) and one byte behind a match (look_ahead); plen holds max_len as above.
-//   * a window that is not the last holds back max_len - 1 + look_ahead starts: a match from a processed start ends look_ahead bytes
-//     in front of the window's end at the latest, so the byte behind it lies in the window;
-//   * the carry keeps look_behind more bytes, in front of the first start no window has processed: CONTEXT ONLY (`ctxb` of them,
-//     none while the first unprocessed start is the first byte the call has seen).  Such a byte is never a start, and its
-//     delimiter was counted by the window that held it, as every byte of the carry;
-//   * the longest carry is max_len + 1 = 257 bytes, below BZF_FRONT;
-//   * the position of output offset 0 in a window is 0 - off_base: there the context in front is the text's edge.
-// With look_behind == look_ahead == 0 every figure is window_set's.
-struct BzrLookWalk : BzmSetWalk {
-    uint32_t look_behind = 0, look_ahead = 0;
-    uint64_t ctxb = 0; // bytes of the carry in front of the first unprocessed start
-
-    void begin_look(uint32_t look_behind_, uint32_t look_ahead_) { look_behind = look_behind_, look_ahead = look_ahead_, ctxb = 0; }
-    // the first start (output offset) the windows up to this one leave unprocessed
-    uint64_t next_start(uint64_t bytes, bool last) const
-    {
-        const uint64_t end = out_pos + bytes, keep = (uint64_t)plen - 1 + look_ahead, held = out_pos - carry + ctxb;
-        return last ? end : (end - held > keep ? end - keep : held);
-    }
-    BzfWindow window_look(uint64_t bytes, bool last, uint64_t *lim) const
-    {
-        BzfWindow w{};
-        w.n = front + bytes;
-        w.d_lo = front;
-        w.off_base = out_pos - front;
-        w.rank_base = rank;
-        w.rec_base = recs;
-        w.s_lo = w.s_hi = front;
-        *lim = w.n;
-        const uint64_t end = out_pos + bytes, held = out_pos - carry + ctxb;
-        const uint64_t p_hi = next_start(bytes, last);
-        const uint64_t from = held > lo ? held : lo;
-        const uint64_t bound = end < hi ? end : hi;
-        const uint64_t upto = p_hi < bound ? p_hi : bound;
-        if (upto > from) {
-            w.s_lo = front + (from - out_pos);
-            w.s_hi = front + (upto - out_pos);
-            *lim = front + (bound - out_pos);
-        }
-        return w;
-    }
     // bytes carried behind a window of `bytes` that is not the last: from look_behind bytes in front of the next start on, as far
     // as the call has seen any
-    uint64_t carry_after_look(uint64_t bytes) const
+    uint64_t carry_after_set(uint64_t bytes) const
     {
         const uint64_t seen = out_pos - carry, next = next_start(bytes, false);
         return out_pos + bytes - (next - seen > look_behind ? next - look_behind : seen);
     }
-    void advance_look(uint64_t bytes, uint64_t hits, uint64_t delims, bool last)
+    // the window is done; behind the last one nothing is carried
+    void advance_set(uint64_t bytes, uint64_t hits, uint64_t delims, bool last)
     {
-        const uint64_t next = next_start(bytes, last), keep = last ? 0 : carry_after_look(bytes);
+        const uint64_t next = next_start(bytes, last), keep = last ? 0 : carry_after_set(bytes);
         ctxb = last ? 0 : next - (out_pos + bytes - keep);
         carry = keep;
         out_pos += bytes;

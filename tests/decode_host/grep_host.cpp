@@ -1,7 +1,7 @@
 // grep_host.cpp -- the grep without a device, built with g++ -fsanitize=address,undefined.
 // (a) What one thread, one tile and the scan of grep_tiles / grep_scan do, run thread by thread and tile by tile in the kernel's
-//     layout: the tile front that the kernel itself compiles (banzai_amd/csrc/search_core.h: bzf_stage, bzf_match16, over the model
-//     LDS of tile_host.h), then banzai_amd/csrc/grep_core.h -- every phase for thread 0 .. 255 where the kernel has a barrier, the
+//     layout: the tile front that the kernel itself compiles (banzai_amd/csrc/search_core.h: bzf_stage, bzf_match16, through BzfOne over the model
+//     LDS of scan_host.h), then banzai_amd/csrc/grep_core.h -- every phase for thread 0 .. 255 where the kernel has a barrier, the
 //     counting pass, the scan, the gather -- against a naive split-and-find.  Every text is allocated as the kernel's contract
 //     states (16-byte aligned, up to the aligned word that holds its last byte) and every other buffer has its exact size, so a
 //     read or a store outside is a sanitizer report.
@@ -9,57 +9,20 @@
 //     window into a staging buffer that is allocated anew for every window, against the same naive split-and-find.
 //
 //   grep_host <seed> <cases>     exit status 0: everything held
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <vector>
-
+#define HOST_NAME "grep_host"
 #include "../../include/bzhip.h"
-#include "../../banzai_amd/csrc/grep_core.h"
-#include "../../banzai_amd/csrc/grep_plan.h"
-#include "../../banzai_amd/csrc/search_plan.h"
-#include "tile_host.h"
+#include "scan_host.h"
 
-static uint64_t rng_state;
-static uint64_t rnd()
-{
-    rng_state ^= rng_state << 13;
-    rng_state ^= rng_state >> 7;
-    rng_state ^= rng_state << 17;
-    return rng_state;
-}
-static uint64_t below(uint64_t n) { return n ? rnd() % n : 0; }
-
-#define CHECK(cond, ...)                                \
-    do {                                                \
-        if (!(cond)) {                                  \
-            fprintf(stderr, "grep_host: %s: ", #cond);  \
-            fprintf(stderr, __VA_ARGS__);               \
-            fprintf(stderr, "\n");                      \
-            exit(1);                                    \
-        }                                               \
-    } while (0)
-
-typedef std::vector<uint8_t> Bytes;
 struct Pattern {
     uint8_t pat[BZF_MAX_PATTERN];
     uint32_t plen, delim, invert;
 };
 static uint8_t slack_of(const Pattern &p) { return p.delim == 0xEE ? 0xED : 0xEE; } // (the letters are 'a' .. 'd')
-static bool same(const BzgEntry &a, const BzgEntry &b) { return a.record == b.record && a.off == b.off && a.len == b.len && a.out_off == b.out_off; }
 
 // ---- the truth: split at the delimiter, find in every record ("a match belongs to the record of its first byte") ---------------
-struct Truth {
-    Bytes out;
-    std::vector<BzgEntry> ent;
-    uint64_t nrecords;
-};
-static Truth naive(const Bytes &text, const Pattern &p)
+static GrepTruth naive(const Bytes &text, const Pattern &p)
 {
-    Truth tr;
+    GrepTruth tr;
     const uint64_t n = text.size();
     uint64_t start = 0, rec = 0;
     auto close = [&](uint64_t end) { // the record [start, end)
@@ -79,174 +42,13 @@ static Truth naive(const Bytes &text, const Pattern &p)
     return tr;
 }
 
-// ---- (a) the device ---------------------------------------------------------------------------------------------------------------
-struct Group : TileModel { // one workgroup: its LDS and its threads' registers
-    BzgShared *sh;
-    BzgThread th[BZF_THREADS];
-    Group() : sh(new BzgShared) {}
-    ~Group() { delete sh; }
-};
-#define EVERY for (uint32_t tid = 0; tid < BZF_THREADS; tid++)
-
-// the front of grep_tiles: the tile, the masks, the forward scan
-static void tile_front(const uint8_t *d, const BzgWindow &w, const Pattern &p, uint64_t t, Group &g)
-{
-    const BzfPattern bp = bzf_pattern(p.pat, p.plen, p.delim);
-    memset(g.sh, 0xAA, sizeof *g.sh); // (what a thread does not store is not known)
-    g.stage(d, w.n, t, bp);
-    EVERY {
-        const uint64_t p0 = t * BZF_TILE + tid * BZF_ITEMS;
-        bzg_masks(g.th[tid], w, p0, g.own[tid], p.delim, g.match(tid, bp, bzg_starts(w, p0)));
-        bzg_local(g.th[tid], p.invert);
-    }
-    EVERY bzg_count_p0(*g.sh, tid, g.th[tid]);
-    for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_f(*g.sh, tid, k);
-}
-
-static void tile_count(const uint8_t *d, const BzgWindow &w, const Pattern &p, uint64_t t, Group &g, BzgTile &out)
-{
-    tile_front(d, w, p, t, g);
-    EVERY bzg_count_p1(*g.sh, tid, g.th[tid], p.invert);
-    for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_s(*g.sh, tid, k);
-    bzg_count_p2(*g.sh, out);
-}
-
-static void tile_gather(const uint8_t *d, const BzgWindow &w, const Pattern &p, uint64_t t, Group &g, const BzgTile &x, const BzgBase &base,
-                        uint8_t *out, BzgEntry *ent)
-{
-    if (x.bytes == 0) return;
-    tile_front(d, w, p, t, g);
-    bool sel_first[BZF_THREADS];
-    uint32_t sm[BZF_THREADS], sdm[BZF_THREADS];
-    EVERY bzg_gather_p1(*g.sh, tid, g.th[tid], x, p.invert, &sel_first[tid]);
-    for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_b(*g.sh, tid, k);
-    EVERY bzg_gather_p2(*g.sh, tid, g.th[tid], x, sel_first[tid], &sm[tid], &sdm[tid]);
-    for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_s(*g.sh, tid, k);
-    CHECK(bzg_bytes(g.sh->s[0][BZF_THREADS - 1]) == x.bytes, "tile %llu: the gather selects %u bytes, the scan said %u", (unsigned long long)t,
-          bzg_bytes(g.sh->s[0][BZF_THREADS - 1]), x.bytes);
-    uint8_t *dst = out ? out + w.out_base + base.out : nullptr;
-    const uint32_t shift = (uint32_t)((uintptr_t)dst & 3u);
-    EVERY bzg_gather_p3(*g.sh, tid, (uint32_t)t, g.th[tid], x, base, w, g.tile + tid * BZF_ITEMS, sm[tid], sdm[tid], shift, dst != nullptr, ent);
-    if (dst) EVERY bzg_gather_p4(*g.sh, tid, dst, shift, x.bytes);
-}
-
-static void scan(std::vector<BzgTile> &tile, std::vector<BzgBase> &base, const BzgWindow &w, uint64_t *totals)
-{
-    BzgScanShared *sh = new BzgScanShared;
-    memset(sh, 0xAA, sizeof *sh);
-    const uint32_t tiles = (uint32_t)tile.size();
-    EVERY bzg_scan_a(*sh, tid, tile.data(), tiles);
-    bzg_scan_b(*sh, w, totals);
-    EVERY bzg_scan_c(*sh, tid, tile.data(), tiles, w);
-    bzg_scan_d(*sh);
-    EVERY bzg_scan_e(*sh, tid, tile.data(), tiles, w);
-    bzg_scan_f(*sh, totals);
-    EVERY bzg_scan_g(*sh, tid, tile.data(), tiles, base.data());
-    delete sh;
-}
-
-struct Sink { // GrepSink
-    Pattern p;
-    BzgWalk walk;
-    uint8_t *out;  // exactly walk.cap bytes (null: not asked for)
-    BzgEntry *ent; // exactly walk.max entries (null: not asked for)
-    uint64_t windows;
-};
-
-// grep_window_run: d is a Text of w.n bytes.  Returns where the tail starts.
-static uint64_t window_run(Sink &s, const uint8_t *d, const BzgWindow &w, uint64_t bytes)
-{
-    const uint64_t tiles = (w.n + BZF_TILE - 1) / BZF_TILE;
-    uint64_t totals[BZG_TOTALS] = {0, 0, 0, w.t_lo, w.open_hit};
-    s.windows++;
-    if (tiles && w.p_hi > w.p_lo) {
-        std::vector<BzgTile> tile(tiles);
-        std::vector<BzgBase> base(tiles);
-        Group g;
-        for (uint64_t t = 0; t < tiles; t++) tile_count(d, w, s.p, t, g, tile[t]);
-        scan(tile, base, w, totals);
-        if (s.walk.gather(totals)) {
-            std::vector<BzgEntry> ent((size_t)(s.walk.want_ent ? totals[BZG_T_SEL] : 0), BzgEntry{~0ull, ~0ull, ~0ull, ~0ull});
-            ent.shrink_to_fit();
-            for (uint64_t t = 0; t < tiles; t++)
-                tile_gather(d, w, s.p, t, g, tile[t], base[t], s.walk.want_out ? s.out : nullptr, s.walk.want_ent ? ent.data() : nullptr);
-            for (size_t k = 0; k < ent.size(); k++) s.ent[w.sel_base + k] = ent[k];
-        }
-    }
-    s.walk.advance(w, bytes, totals);
-    return totals[BZG_T_TAIL_START];
-}
-
-// grep_finish: tail = the carry's bytes
-static void finish(Sink &s, Bytes &carry)
-{
-    if (s.walk.held) {
-        CHECK(carry.size() == s.walk.carry, "the carry");
-        const Text held(carry.data(), carry.size(), slack_of(s.p));
-        const uint64_t ts = window_run(s, held.p, s.walk.window(s.walk.carry, 0, true), 0);
-        carry.erase(carry.begin(), carry.begin() + ts);
-    }
-    CHECK(carry.size() == s.walk.carry && s.walk.held == 0, "the tail");
-    bool copy, entry;
-    s.walk.tail_rooms(&copy, &entry);
-    const BzgEntry te = s.walk.tail_entry();
-    if (copy && !carry.empty()) memcpy(s.out + s.walk.out_bytes, carry.data(), carry.size());
-    s.walk.tail_done();
-    if (entry) s.ent[s.walk.sel - 1] = te;
-}
-
-// rooms: 0 = not asked for, 1 = above the need, 2 = the need, 3 = one below it, 4 = asked for with no room
-static uint64_t room_of(int kind, uint64_t need) { return kind == 1 ? need + 5 : kind == 2 ? need : kind == 3 ? (need ? need - 1 : 0) : 0; }
-
+// ---- (a) the device: scan_host.h's model with BzfOne, the single pattern ----------------------------------------------------------
 // one call: `blocks` lists the sizes of the windows' new bytes (empty: the raw call, one window over the text itself)
-static void run_call(const Bytes &text, const Pattern &p, const std::vector<uint64_t> &blocks, int out_kind, int ent_kind, const Truth &tr,
-                     uint64_t *carry_peak, uint64_t *windows)
+static void run_call(const Bytes &text, const Pattern &p, const std::vector<uint64_t> &blocks, int out_kind, int ent_kind, const GrepTruth &tr, uint64_t *carry_peak,
+                     uint64_t *windows)
 {
-    const uint64_t cap = room_of(out_kind, tr.out.size()), max = room_of(ent_kind, tr.ent.size());
-    uint8_t *out = out_kind ? (uint8_t *)malloc(cap ? cap : 1) : nullptr; // (4-byte aligned, exactly cap bytes: cap 0 has one nobody may touch)
-    std::vector<BzgEntry> ent((size_t)max);
-    ent.shrink_to_fit();
-    Sink s{p, BzgWalk{}, out, ent_kind ? ent.data() : nullptr, 0};
-    if (ent_kind && !max) s.ent = reinterpret_cast<BzgEntry *>(sizeof(BzgEntry)); // (asked for: non-null, never dereferenced)
-    s.walk.begin(p.plen, p.invert != 0, out_kind != 0, cap, ent_kind != 0, max);
-    Bytes carry;
-    if (blocks.empty()) {
-        const Text d(text.data(), text.size(), slack_of(p));
-        const uint64_t ts = window_run(s, d.p, s.walk.window(0, text.size(), true), text.size());
-        carry.assign(d.p + ts, d.p + text.size());
-    } else {
-        uint64_t at = 0;
-        for (uint64_t bytes : blocks) {
-            // GrepSink::room: a staging buffer of its own for every window, the carry in front of the new bytes
-            const uint64_t extra = bzg_front_extra(s.walk.carry, BZF_FRONT), front = extra + BZF_FRONT;
-            const Text stage(front + bytes, slack_of(p));
-            memset(stage.p, 0xCC, front);
-            CHECK(carry.size() == s.walk.carry && front >= carry.size(), "the carry fits in front");
-            if (!carry.empty()) memcpy(stage.p + front - carry.size(), carry.data(), carry.size());
-            if (bytes) memcpy(stage.p + front, &text[at], bytes);
-            at += bytes;
-            const uint64_t ts = window_run(s, stage.p, s.walk.window(front, bytes, false), bytes);
-            carry.assign(stage.p + ts, stage.p + front + bytes);
-        }
-        CHECK(at == text.size(), "the blocks are the text");
-    }
-    finish(s, carry);
-    CHECK(s.walk.sel == tr.ent.size() && s.walk.out_bytes == tr.out.size() && s.walk.nrecords() == tr.nrecords,
-          "counts: %llu selected of %llu bytes, %llu records; the truth %zu, %zu, %llu", (unsigned long long)s.walk.sel,
-          (unsigned long long)s.walk.out_bytes, (unsigned long long)s.walk.nrecords(), tr.ent.size(), tr.out.size(), (unsigned long long)tr.nrecords);
-    const bool over = (out_kind && tr.out.size() > cap) || (ent_kind && tr.ent.size() > max);
-    CHECK(s.walk.overflow() == over, "BZH_E_CAP exactly when a room that is asked for is too small");
-    if (!over) {
-        if (out_kind && !tr.out.empty()) CHECK(memcmp(out, tr.out.data(), tr.out.size()) == 0, "the selected bytes");
-        for (size_t k = 0; ent_kind && k < tr.ent.size(); k++)
-            CHECK(same(ent[k], tr.ent[k]), "entry %zu: record %llu off %llu len %llu out_off %llu, the truth %llu %llu %llu %llu", k,
-                  (unsigned long long)ent[k].record, (unsigned long long)ent[k].off, (unsigned long long)ent[k].len,
-                  (unsigned long long)ent[k].out_off, (unsigned long long)tr.ent[k].record, (unsigned long long)tr.ent[k].off,
-                  (unsigned long long)tr.ent[k].len, (unsigned long long)tr.ent[k].out_off);
-    }
-    if (carry_peak) *carry_peak = std::max(*carry_peak, s.walk.carry_peak);
-    if (windows) *windows = s.windows;
-    free(out);
+    const BzfOne m{{}, bzf_pattern(p.pat, p.plen, p.delim)};
+    grep_call(text, tr, [&](const BzgWindow &) { return m; }, p.plen, p.invert, slack_of(p), blocks, out_kind, ent_kind, carry_peak, windows);
 }
 
 // ---- texts -------------------------------------------------------------------------------------------------------------------------
@@ -274,7 +76,7 @@ static Bytes letters(uint64_t n, uint32_t delim, uint64_t density)
 static uint64_t seen_selected, seen_left; // records the truth selects and leaves out
 static void raw_case(const Bytes &text, const Pattern &p, uint64_t *runs)
 {
-    const Truth tr = naive(text, p);
+    const GrepTruth tr = naive(text, p);
     seen_selected += tr.ent.size(), seen_left += tr.nrecords - tr.ent.size();
     run_call(text, p, {}, 2, 2, tr, nullptr, nullptr);
     (*runs)++;
@@ -399,7 +201,7 @@ static void window_cases(uint64_t cases)
             for (auto &b : text) b = b == delim ? b : 'c';
             plant(text, below(n), p);
         }
-        const Truth tr = naive(text, p);
+        const GrepTruth tr = naive(text, p);
         const int out_kind = (int)below(5), ent_kind = (int)below(5);
         uint64_t windows = 0;
         run_call(text, p, wins, out_kind, ent_kind, tr, &carry_peak, &windows);

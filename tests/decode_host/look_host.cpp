@@ -3,55 +3,27 @@
 //     trees: seeded trees that hold ^ $ \A \Z \b \B in leading, inner and trailing places, matched here on the tree at every offset
 //     of seeded texts with two bounds and two spans; the word and line wraps; the identity of the plan for lists without assertions;
 //     the refusals without the syntax bit, the empty matches, a state count that crosses the bound only because of the contexts.
-// (b) The look-around matcher of banzai_amd/csrc/regex_core.h -- BzrLookMatcher<true> and <false>, the kernels' own text -- thread by
+// (b) The look-around matcher of banzai_amd/csrc/regex_core.h -- BzrMatcher<true, true> and <false, true>, the kernels' own text -- thread by
 //     thread and tile by tile over a model of the LDS: search and grep, the fixed places of the two extra bytes.
-// (c) The windows: BzrLookWalk (search_plan.h) and BzgWalk (grep_plan.h) with (b) as the device, against brute force per output
+// (c) The windows: BzmSetWalk with both looks (search_plan.h) and BzgWalk (grep_plan.h) with (b) as the device, against brute force per output
 //     byte, the decoded range widened as decode_range_sink_run widens it.
 //
 //   look_host <seed> <cases>                                exit status 0: everything held
 //   look_host hits EXPRFILE TEXTFILE FLAGS SPAN SYNTAX      one expression a line; prints "off pattern len" for every hit of the text
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+#define HOST_NAME "look_host"
 #include <time.h>
 
-#include <algorithm>
 #include <bitset>
 #include <set>
 #include <string>
-#include <vector>
 
 #include "../../include/bzhip.h"
-#include "../../banzai_amd/csrc/grep_plan.h"
 #include "../../banzai_amd/csrc/regex_core.h"
 #include "../../banzai_amd/csrc/regex_plan.h"
-#include "../../banzai_amd/csrc/search_plan.h"
-#include "tile_host.h"
+#include "regex_ex_host.h"
+#include "scan_host.h"
 
-static uint64_t rng_state;
-static uint64_t rnd()
-{
-    rng_state ^= rng_state << 13;
-    rng_state ^= rng_state >> 7;
-    rng_state ^= rng_state << 17;
-    return rng_state;
-}
-static uint64_t below(uint64_t n) { return n ? rnd() % n : 0; }
-
-#define CHECK(cond, ...)                                 \
-    do {                                                 \
-        if (!(cond)) {                                   \
-            fprintf(stderr, "look_host: %s: ", #cond);   \
-            fprintf(stderr, __VA_ARGS__);                \
-            fprintf(stderr, "\n");                       \
-            exit(1);                                     \
-        }                                                \
-    } while (0)
-#define EVERY for (uint32_t tid = 0; tid < BZF_THREADS; tid++)
-typedef std::vector<uint8_t> Bytes;
 typedef std::vector<Bytes> Pats;
-typedef unsigned long long ull;
 
 static_assert(sizeof(bzh_regex_look) == 16 && sizeof(bzh_regex_info) == 40, "the two records");
 static_assert((uint32_t)BZR_CTX_EDGE == (uint32_t)BZR_LOOK_EDGE && (uint32_t)BZR_CTX_NL == (uint32_t)BZR_LOOK_NL && (uint32_t)BZR_CTX_WORD == (uint32_t)BZR_LOOK_WORD &&
@@ -59,132 +31,9 @@ static_assert((uint32_t)BZR_CTX_EDGE == (uint32_t)BZR_LOOK_EDGE && (uint32_t)BZR
               "one numbering of the contexts");
 static_assert(BZF_TILE - 1 + BZF_MAX_PATTERN == BZF_TILE + BZF_MAX_PATTERN - 1, "a match of 256 bytes from tile byte 4,095 looks ahead at the tile array's last byte");
 
-template <class T>
-static T *exact(const T *src, size_t count) // a copy in an allocation of exactly its size (count 0: one byte nobody may touch)
-{
-    T *p = (T *)malloc(count ? count * sizeof(T) : 1);
-    if (!p) abort();
-    if (count) memcpy(p, src, count * sizeof(T));
-    return p;
-}
 static Bytes B(const char *s) { return Bytes(s, s + strlen(s)); }
 
 // ---- the harness's own expressions ---------------------------------------------------------------------------------------------------
-struct Ex {
-    enum Kind { SET, CAT, ALT, REP, LOOK } kind = SET;
-    std::bitset<256> set;
-    bool neg = false;
-    std::string text;     // SET, LOOK: how it is written
-    char look = 0;        // LOOK: ^ $ A Z b B, and < > for the word wrap's two ends
-    std::vector<Ex> kids;
-    uint32_t lo = 0, hi = 0;
-};
-static uint8_t twin(uint8_t b) { return b >= 'A' && b <= 'Z' ? (uint8_t)(b + 32) : b >= 'a' && b <= 'z' ? (uint8_t)(b - 32) : b; }
-static bool takes(const Ex &e, uint8_t b, bool fold) { return (e.set[b] || (fold && e.set[twin(b)])) != e.neg; }
-static bool wordb(uint8_t b) { return (b >= '0' && b <= '9') || (b >= 'a' && b <= 'z') || (b >= 'A' && b <= 'Z') || b == '_'; }
-// THE RULE of an assertion at position p of t[0, n), by its words and not by the contexts
-static bool holds(char look, const uint8_t *t, uint64_t n, uint64_t p)
-{
-    const bool wf = p > 0 && wordb(t[p - 1]), wb = p < n && wordb(t[p]);
-    switch (look) {
-    case '^': return p == 0 || t[p - 1] == '\n';
-    case '$': return p == n || t[p] == '\n';
-    case 'A': return p == 0;
-    case 'Z': return p == n;
-    case 'b': return wf != wb;
-    case 'B': return wf == wb;
-    case '<': return !wf;
-    default: return !wb;
-    }
-}
-typedef std::set<uint64_t> Ends;
-// the positions behind a match of e that begins at one of `in`, no byte at or behind lim taken; the text is t[0, n)
-static Ends ends(const Ex &e, const uint8_t *t, uint64_t n, uint64_t lim, const Ends &in, bool fold)
-{
-    Ends out;
-    switch (e.kind) {
-    case Ex::SET:
-        for (uint64_t p : in)
-            if (p < lim && takes(e, t[p], fold)) out.insert(p + 1);
-        return out;
-    case Ex::LOOK:
-        for (uint64_t p : in)
-            if (holds(e.look, t, n, p)) out.insert(p);
-        return out;
-    case Ex::CAT:
-        out = in;
-        for (const Ex &k : e.kids) out = ends(k, t, n, lim, out, fold);
-        return out;
-    case Ex::ALT:
-        for (const Ex &k : e.kids) {
-            const Ends x = ends(k, t, n, lim, in, fold);
-            out.insert(x.begin(), x.end());
-        }
-        return out;
-    default: {
-        Ends cur = in;
-        if (e.lo == 0) out = in;
-        for (uint32_t k = 1; e.hi == ~0u || k <= e.hi; k++) {
-            cur = ends(e.kids[0], t, n, lim, cur, fold);
-            if (cur.empty()) break;
-            if (k < e.lo) continue;
-            const size_t before = out.size();
-            out.insert(cur.begin(), cur.end());
-            if (out.size() == before && k > e.lo) break;
-        }
-        return out;
-    }
-    }
-}
-static uint64_t min_len(const Ex &e)
-{
-    uint64_t r = 0;
-    switch (e.kind) {
-    case Ex::SET: return 1;
-    case Ex::LOOK: return 0;
-    case Ex::CAT:
-        for (const Ex &k : e.kids) r += min_len(k);
-        return r;
-    case Ex::ALT:
-        r = ~0ull;
-        for (const Ex &k : e.kids) r = std::min(r, min_len(k));
-        return r;
-    default: return e.lo * min_len(e.kids[0]);
-    }
-}
-static bool has_look(const Ex &e)
-{
-    if (e.kind == Ex::LOOK) return true;
-    for (const Ex &k : e.kids)
-        if (has_look(k)) return true;
-    return false;
-}
-static std::string print(const Ex &e, bool top = false)
-{
-    std::string s;
-    switch (e.kind) {
-    case Ex::SET:
-    case Ex::LOOK: return e.text;
-    case Ex::CAT:
-        for (const Ex &k : e.kids) s += k.kind == Ex::ALT ? "(?:" + print(k) + ")" : print(k);
-        return s;
-    case Ex::ALT:
-        for (size_t i = 0; i < e.kids.size(); i++) s += (i ? "|" : "") + print(e.kids[i]);
-        return top ? s : "(" + s + ")";
-    default: {
-        const Ex &k = e.kids[0];
-        s = k.kind == Ex::SET ? print(k) : k.kind == Ex::ALT ? print(k) : "(" + print(k) + ")";
-        char q[40];
-        if (e.lo == 0 && e.hi == 1) return s + "?";
-        if (e.lo == 0 && e.hi == ~0u) return s + "*";
-        if (e.lo == 1 && e.hi == ~0u) return s + "+";
-        if (e.hi == ~0u) snprintf(q, sizeof q, "{%u,}", e.lo);
-        else if (e.hi == e.lo) snprintf(q, sizeof q, "{%u}", e.lo);
-        else snprintf(q, sizeof q, "{%u,%u}", e.lo, e.hi);
-        return s + q;
-    }
-    }
-}
 static const char ALPHA[] = "abAB01 _\n-z";
 static Ex lit(uint8_t b)
 {
@@ -285,10 +134,10 @@ struct Auto {
     Auto(const Auto &) = delete;
     bool looks() const { return plan.look_behind || plan.look_ahead; }
     template <bool L>
-    BzrLookMatcher<L> matcher(uint32_t delim, uint64_t lim, uint64_t n, uint64_t edge_lo, uint32_t ctx_lo) const
+    BzrMatcher<L, true> matcher(uint32_t delim, uint64_t lim, uint64_t n, uint64_t edge_lo, uint32_t ctx_lo) const
     {
-        return BzrLookMatcher<L>{BzrAuto{BzmSet{cls, first, table, pat_no, plan.classes, plan.nterm, plan.max_len, delim, lim}, plan.states * plan.classes},
-                                 BzrLook{acc_mask, pat_ctx, plan.contexts, ctx_row, plan.look_ahead, ctx_lo, edge_lo, n}};
+        return BzrMatcher<L, true>{{BzrAuto{BzmSet{cls, first, table, pat_no, plan.classes, plan.nterm, plan.max_len, delim, lim}, plan.states * plan.classes},
+                                        BzrLook{acc_mask, pat_ctx, plan.contexts, ctx_row, plan.look_ahead, ctx_lo, edge_lo, n}}, {}};
     }
     // the table walked without a tile, every invariant checked on the way: the hit at text[o ..) of text[0, n), bounded by lim
     bool walk(const uint8_t *text, uint64_t n, uint64_t o, uint64_t lim, uint32_t *pattern, uint32_t *len) const
@@ -463,185 +312,8 @@ static void part_compile(uint64_t cases)
            (ull)refused_big, (ull)contradictory);
 }
 
-// ---- (b) the device -----------------------------------------------------------------------------------------------------------------
-template <class M>
-struct Group { // one workgroup: its LDS and its threads' registers
-    uint8_t *tile;
-    typename M::Shared *msh;
-    BzgShared *sh;
-    BzfVec own[BZF_THREADS];
-    uint32_t hm[BZF_THREADS], nh[BZF_THREADS], dm[BZF_THREADS];
-    BzgThread th[BZF_THREADS];
-    Group() : msh(new typename M::Shared), sh(new BzgShared)
-    {
-        if (posix_memalign((void **)&tile, 16, BZF_TILE + BZF_MAX_PATTERN)) abort();
-    }
-    ~Group() { free(tile), delete msh, delete sh; }
-    void stage(const M &m, const uint8_t *d, uint64_t n, uint64_t t)
-    {
-        // what no thread stores is not known: 'w' is a word byte, so a look-ahead that reads it, or the zero behind the text, shows
-        memset(tile, 'w', BZF_TILE + BZF_MAX_PATTERN), memset((void *)msh, 0xAA, sizeof *msh), memset((void *)sh, 0xAA, sizeof *sh);
-        EVERY own[tid] = m.stage(d, n, t * BZF_TILE, tid, tile, *msh);
-    }
-};
-template <class M>
-static void search_front(const uint8_t *d, const BzfWindow &w, const M &m, bool records, uint64_t t, Group<M> &g)
-{
-    g.stage(m, d, w.n, t);
-    EVERY {
-        const uint64_t p0 = t * BZF_TILE + tid * BZF_ITEMS;
-        const BzfVec &v = g.own[tid];
-        g.nh[tid] = m.count16(v, tid, p0, g.tile, *g.msh, bzf_range_mask16(p0, w.s_lo, w.s_hi), &g.hm[tid]);
-        g.dm[tid] = records ? bzf_eq_mask16(v.x, v.y, v.z, v.w, m.delim()) & bzf_range_mask16(p0, w.d_lo, w.n) : 0u;
-    }
-}
-// search_window_run: both passes and the scan between them
-template <class M>
-static void search_run(const uint8_t *d, BzfWindow w, const M &m, bool records, const BzfWalk &walk, std::vector<BzmHit> &out, uint64_t *hits, uint64_t *delims)
-{
-    const uint32_t delim = m.delim();
-    const uint64_t tiles = (w.n + BZF_TILE - 1) / BZF_TILE;
-    std::vector<uint32_t> thits(tiles), tdel(tiles);
-    std::vector<uint64_t> hbase(tiles), dbase(tiles);
-    Group<M> g;
-    *hits = *delims = 0;
-    out.clear();
-    if (!(tiles && (w.s_hi > w.s_lo || records))) return;
-    for (uint64_t t = 0; t < tiles; t++) {
-        search_front(d, w, m, records, t, g);
-        uint64_t sum = 0;
-        EVERY sum += g.nh[tid], tdel[t] += (uint32_t)__builtin_popcount(g.dm[tid]);
-        thits[t] = (uint32_t)sum;
-    }
-    uint64_t rh = 0, rd = 0;
-    for (uint64_t t = 0; t < tiles; t++) hbase[t] = rh, dbase[t] = rd, rh += thits[t], rd += tdel[t];
-    *hits = rh, *delims = rd;
-    w.emit = walk.emit(rh);
-    out.assign((size_t)w.emit, BzmHit{~0ull, ~0ull, ~0u, ~0u});
-    out.shrink_to_fit();
-    for (uint64_t t = 0; t < tiles && w.emit; t++) {
-        if (thits[t] == 0 || hbase[t] >= w.emit) continue;
-        search_front(d, w, m, records, t, g);
-        uint64_t h0 = 0, dsum = 0;
-        EVERY {
-            const uint64_t p0 = t * BZF_TILE + tid * BZF_ITEMS;
-            uint64_t rank = hbase[t] + h0;
-            for (uint32_t hm = g.hm[tid]; hm; hm &= hm - 1u) {
-                const uint32_t k = (uint32_t)__builtin_ctz(hm);
-                if (rank >= w.emit) break;
-                const uint64_t pos = p0 + k;
-                uint64_t rec = 0;
-                if (records) {
-                    if (pos >= w.d_lo) {
-                        rec = w.rec_base + dbase[t] + dsum + bzf_delims_before(g.dm[tid], k);
-                    } else {
-                        const uint32_t gap = (uint32_t)std::min<uint64_t>(w.d_lo - pos, BZF_MAX_PATTERN);
-                        uint32_t c = 0;
-                        for (uint32_t j = 0; j < gap; j++) c += g.tile[tid * BZF_ITEMS + k + j] == delim;
-                        rec = w.rec_base - c;
-                    }
-                }
-                const uint64_t next = m.emit1(*g.msh, g.tile + tid * BZF_ITEMS + k, pos, w.off_base + pos, rec, out.data(), rank, w.emit);
-                CHECK(next == rank + 1, "a start yields exactly one hit");
-                rank = next;
-            }
-            h0 += g.nh[tid], dsum += (uint32_t)__builtin_popcount(g.dm[tid]);
-        }
-    }
-}
-static void same_hits(const std::vector<BzmHit> &got, const std::vector<BzmHit> &want, uint64_t nhits, uint64_t max, const char *what, uint64_t a)
-{
-    CHECK(nhits == want.size(), "%s (%llu): %llu hits, the truth has %zu", what, (ull)a, (ull)nhits, want.size());
-    const size_t m = (size_t)std::min<uint64_t>(max, want.size());
-    CHECK(got.size() >= m, "%s: %zu hits stored of %zu", what, got.size(), m);
-    for (size_t i = 0; i < m; i++)
-        CHECK(got[i].off == want[i].off && got[i].record == want[i].record && got[i].pattern == want[i].pattern && got[i].len == want[i].len,
-              "%s (%llu): hit %zu is (%llu, %llu, %u, %u), the truth (%llu, %llu, %u, %u)", what, (ull)a, i, (ull)got[i].off, (ull)got[i].record, got[i].pattern,
-              got[i].len, (ull)want[i].off, (ull)want[i].record, want[i].pattern, want[i].len);
-}
-
-// ---- the grep's device ---------------------------------------------------------------------------------------------------------------
-template <class M>
-static void grep_front(const uint8_t *d, const BzgWindow &w, const M &m, uint64_t t, Group<M> &g)
-{
-    g.stage(m, d, w.n, t);
-    EVERY {
-        const uint64_t p0 = t * BZF_TILE + tid * BZF_ITEMS;
-        bzg_masks(g.th[tid], w, p0, g.own[tid], m.delim(), m.match16(g.own[tid], tid, p0, g.tile, *g.msh, bzf_range_mask16(p0, w.p_lo, w.p_hi)));
-        bzg_local(g.th[tid], w.invert);
-    }
-    EVERY bzg_count_p0(*g.sh, tid, g.th[tid]);
-    for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_f(*g.sh, tid, k);
-}
-struct GrepCall { // GrepSink
-    const Auto *set;
-    uint32_t delim;
-    BzgWalk walk;
-    uint8_t *out;
-    BzgEntry *ent;
-};
-template <bool L>
-static uint64_t grep_run(GrepCall &s, const uint8_t *d, const BzgWindow &w, uint64_t bytes)
-{
-    typedef BzrLookMatcher<L> M;
-    // grep.hip's grep_matcher: the text begins at a record start
-    const M m = s.set->template matcher<L>(s.delim, w.n, w.n, w.t_lo, w.off_base + w.t_lo == 0 ? (uint32_t)BZR_LOOK_EDGE : bzr_ctx(s.delim));
-    const uint64_t tiles = (w.n + BZF_TILE - 1) / BZF_TILE;
-    uint64_t totals[BZG_TOTALS] = {0, 0, 0, w.t_lo, w.open_hit};
-    if (tiles && w.p_hi > w.p_lo) {
-        std::vector<BzgTile> tile(tiles);
-        std::vector<BzgBase> base(tiles);
-        Group<M> g;
-        for (uint64_t t = 0; t < tiles; t++) {
-            grep_front(d, w, m, t, g);
-            EVERY bzg_count_p1(*g.sh, tid, g.th[tid], w.invert);
-            for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_s(*g.sh, tid, k);
-            bzg_count_p2(*g.sh, tile[t]);
-        }
-        {
-            BzgScanShared *sh = new BzgScanShared;
-            memset((void *)sh, 0xAA, sizeof *sh);
-            const uint32_t nt = (uint32_t)tiles;
-            EVERY bzg_scan_a(*sh, tid, tile.data(), nt);
-            bzg_scan_b(*sh, w, totals);
-            EVERY bzg_scan_c(*sh, tid, tile.data(), nt, w);
-            bzg_scan_d(*sh);
-            EVERY bzg_scan_e(*sh, tid, tile.data(), nt, w);
-            bzg_scan_f(*sh, totals);
-            EVERY bzg_scan_g(*sh, tid, tile.data(), nt, base.data());
-            delete sh;
-        }
-        if (s.walk.gather(totals)) {
-            std::vector<BzgEntry> ent((size_t)(s.walk.want_ent ? totals[BZG_T_SEL] : 0), BzgEntry{~0ull, ~0ull, ~0ull, ~0ull});
-            ent.shrink_to_fit();
-            uint8_t *out = s.walk.want_out ? s.out : nullptr;
-            for (uint64_t t = 0; t < tiles; t++) {
-                const BzgTile &x = tile[t];
-                if (x.bytes == 0) continue;
-                grep_front(d, w, m, t, g);
-                bool sel_first[BZF_THREADS];
-                uint32_t sm[BZF_THREADS], sdm[BZF_THREADS];
-                EVERY bzg_gather_p1(*g.sh, tid, g.th[tid], x, w.invert, &sel_first[tid]);
-                for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_b(*g.sh, tid, k);
-                EVERY bzg_gather_p2(*g.sh, tid, g.th[tid], x, sel_first[tid], &sm[tid], &sdm[tid]);
-                for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_s(*g.sh, tid, k);
-                uint8_t *dst = out ? out + w.out_base + base[t].out : nullptr;
-                const uint32_t shift = (uint32_t)((uintptr_t)dst & 3u);
-                EVERY bzg_gather_p3(*g.sh, tid, (uint32_t)t, g.th[tid], x, base[t], w, g.tile + tid * BZF_ITEMS, sm[tid], sdm[tid], shift, dst != nullptr,
-                                    s.walk.want_ent ? ent.data() : nullptr);
-                if (dst) EVERY bzg_gather_p4(*g.sh, tid, dst, shift, x.bytes);
-            }
-            for (size_t k = 0; k < ent.size(); k++) s.ent[w.sel_base + k] = ent[k];
-        }
-    }
-    s.walk.advance(w, bytes, totals);
-    return totals[BZG_T_TAIL_START];
-}
-struct GrepTruth {
-    Bytes out;
-    std::vector<BzgEntry> ent;
-    uint64_t nrecords;
-};
+// ---- (b) the device: scan_host.h's model with BzrMatcher<true / false, true>.  What no thread stores is 'w' here (main): a word byte,
+// so a look-ahead that reads it, or the zero behind the text, shows ----------------------------------------------------------------------
 static GrepTruth grep_naive(const Bytes &text, const Auto &s, uint32_t delim, uint32_t invert)
 {
     GrepTruth tr;
@@ -664,52 +336,12 @@ static GrepTruth grep_naive(const Bytes &text, const Auto &s, uint32_t delim, ui
 }
 // one grep call over the whole of `text`; blocks: the windows' new bytes (empty: the raw call)
 template <bool L>
-static void grep_call(const Bytes &text, const Auto &set, uint32_t delim, uint32_t invert, const std::vector<uint64_t> &blocks)
+static void grep_auto(const Bytes &text, const Auto &set, uint32_t delim, uint32_t invert, const std::vector<uint64_t> &blocks)
 {
-    const GrepTruth tr = grep_naive(text, set, delim, invert);
-    uint8_t *out = (uint8_t *)malloc(tr.out.size() ? tr.out.size() : 1);
-    std::vector<BzgEntry> ent(tr.ent.size());
-    ent.shrink_to_fit();
-    GrepCall s{&set, delim, BzgWalk{}, out, ent.empty() ? reinterpret_cast<BzgEntry *>(sizeof(BzgEntry)) : ent.data()};
-    s.walk.begin(set.plan.max_len + set.plan.look_ahead, invert != 0, true, tr.out.size(), true, tr.ent.size()); // (GrepSink: the hold-back grows)
-    const uint8_t slack = 'w';
-    Bytes carry;
-    if (blocks.empty()) {
-        const Text d(text.data(), text.size(), slack);
-        const uint64_t ts = grep_run<L>(s, d.p, s.walk.window(0, text.size(), true), text.size());
-        carry.assign(d.p + ts, d.p + text.size());
-    } else {
-        uint64_t at = 0;
-        for (uint64_t bytes : blocks) {
-            const uint64_t extra = bzg_front_extra(s.walk.carry, BZF_FRONT), front = extra + BZF_FRONT;
-            const Text stage(front + bytes, slack);
-            memset(stage.p, 'w', front);
-            if (!carry.empty()) memcpy(stage.p + front - carry.size(), carry.data(), carry.size());
-            if (bytes) memcpy(stage.p + front, &text[at], bytes);
-            at += bytes;
-            const uint64_t ts = grep_run<L>(s, stage.p, s.walk.window(front, bytes, false), bytes);
-            carry.assign(stage.p + ts, stage.p + front + bytes);
-        }
-    }
-    if (s.walk.held) { // grep_finish
-        const Text held(carry.data(), carry.size(), slack);
-        const uint64_t ts = grep_run<L>(s, held.p, s.walk.window(s.walk.carry, 0, true), 0);
-        carry.erase(carry.begin(), carry.begin() + ts);
-    }
-    CHECK(carry.size() == s.walk.carry && s.walk.held == 0, "the tail");
-    bool copy, entry;
-    s.walk.tail_rooms(&copy, &entry);
-    const BzgEntry te = s.walk.tail_entry();
-    if (copy && !carry.empty()) memcpy(s.out + s.walk.out_bytes, carry.data(), carry.size());
-    s.walk.tail_done();
-    if (entry) s.ent[s.walk.sel - 1] = te;
-    CHECK(s.walk.sel == tr.ent.size() && s.walk.out_bytes == tr.out.size() && s.walk.nrecords() == tr.nrecords && !s.walk.overflow(),
-          "grep counts: %llu selected of %llu bytes, %llu records; the truth %zu, %zu, %llu", (ull)s.walk.sel, (ull)s.walk.out_bytes, (ull)s.walk.nrecords(),
-          tr.ent.size(), tr.out.size(), (ull)tr.nrecords);
-    if (!tr.out.empty()) CHECK(memcmp(out, tr.out.data(), tr.out.size()) == 0, "the selected bytes");
-    for (size_t k = 0; k < tr.ent.size(); k++)
-        CHECK(ent[k].record == tr.ent[k].record && ent[k].off == tr.ent[k].off && ent[k].len == tr.ent[k].len && ent[k].out_off == tr.ent[k].out_off, "grep entry %zu", k);
-    free(out);
+    // grep.hip's pick: the text begins at a record start; GrepSink: the hold-back grows by the byte behind a match
+    grep_call(text, grep_naive(text, set, delim, invert),
+              [&](const BzgWindow &w) { return set.matcher<L>(delim, w.n, w.n, w.t_lo, w.off_base + w.t_lo == 0 ? (uint32_t)BZR_LOOK_EDGE : bzr_ctx(delim)); },
+              set.plan.max_len + set.plan.look_ahead, invert, 'w', blocks, 2, 2);
 }
 
 // one raw search call with `max` hit slots; returns the hits
@@ -718,11 +350,11 @@ static uint64_t search_raw(const Bytes &src, const Auto &set, uint32_t delim, bo
 {
     const uint64_t n = src.size();
     const Text text(src.data(), n, 'w');
-    BzrLookWalk walk;
+    BzmSetWalk walk;
     walk.begin(set.plan.max_len, 0, max, 0, n, 0, 0);
     walk.begin_look(set.plan.look_behind, set.plan.look_ahead);
     uint64_t lim = 0, hits, delims;
-    const BzfWindow w = walk.window_look(n, true, &lim);
+    const BzfWindow w = walk.window_set(n, true, &lim);
     std::vector<BzmHit> out;
     search_run(text.p, w, set.matcher<L>(delim, lim, w.n, 0 - w.off_base, BZR_LOOK_EDGE), records, walk, out, &hits, &delims);
     same_hits(out, set.naive(text.p, n, 0, n, records, delim), hits, max, "raw", n);
@@ -736,8 +368,8 @@ static uint64_t search_both(const Bytes &src, const Auto &set, uint32_t delim, b
 }
 static void grep_both(const Bytes &text, const Auto &set, uint32_t delim, uint32_t invert, const std::vector<uint64_t> &blocks)
 {
-    grep_call<false>(text, set, delim, invert, blocks);
-    if (set.plan.table.size() <= BZR_LDS_ROWS) grep_call<true>(text, set, delim, invert, blocks);
+    grep_auto<false>(text, set, delim, invert, blocks);
+    if (set.plan.table.size() <= BZR_LDS_ROWS) grep_auto<true>(text, set, delim, invert, blocks);
 }
 static void plant(Bytes &text, uint64_t at, const Bytes &p)
 {
@@ -892,7 +524,7 @@ static void part_windows(uint64_t cases)
         const bool lds = below(2) != 0 && set.plan.table.size() <= BZR_LDS_ROWS;
         uint64_t rec_start = 0;
         for (uint64_t i = 0; i < start; i++) rec_start += truth[i] == '\n';
-        BzrLookWalk walk;
+        BzmSetWalk walk;
         walk.begin(set.plan.max_len, BZF_FRONT, max, lo, hi, start, records ? rec_start : 0);
         walk.begin_look(set.plan.look_behind, set.plan.look_ahead);
         std::vector<BzmHit> got((size_t)std::min<uint64_t>(max, want.size() + 8), BzmHit{~0ull, ~0ull, ~0u, ~0u});
@@ -907,7 +539,7 @@ static void part_windows(uint64_t cases)
             if (lds) search_run(d, w, set.matcher<true>('\n', lim, w.n, 0 - w.off_base, BZR_LOOK_EDGE), records, walk, out, &hits, &delims);
             else search_run(d, w, set.matcher<false>('\n', lim, w.n, 0 - w.off_base, BZR_LOOK_EDGE), records, walk, out, &hits, &delims);
             for (size_t i = 0; i < out.size(); i++) got.at((size_t)walk.rank + i) = out[i];
-            walk.advance_look(bytes, hits, delims, is_last);
+            walk.advance_set(bytes, hits, delims, is_last);
             windows++;
         };
         for (size_t at = first; at < last;) {
@@ -921,8 +553,8 @@ static void part_windows(uint64_t cases)
             if (!carry.empty()) memcpy(staging.p + BZF_FRONT - carry.size(), carry.data(), carry.size());
             memcpy(staging.p + BZF_FRONT, &truth[at_out], (size_t)bytes);
             uint64_t lim = 0;
-            const BzfWindow w = walk.window_look(bytes, false, &lim);
-            const uint64_t keep = walk.carry_after_look(bytes);
+            const BzfWindow w = walk.window_set(bytes, false, &lim);
+            const uint64_t keep = walk.carry_after_set(bytes);
             const Bytes next(staging.p + w.n - keep, staging.p + w.n);
             run(staging.p, w, lim, bytes, false);
             carry = next;
@@ -932,7 +564,7 @@ static void part_windows(uint64_t cases)
             const Text held(carry.data(), carry.size(), 'w');
             walk.front = walk.carry;
             uint64_t lim = 0;
-            const BzfWindow w = walk.window_look(0, true, &lim);
+            const BzfWindow w = walk.window_set(0, true, &lim);
             run(held.p, w, lim, 0, true);
             finished++;
         }
@@ -940,8 +572,8 @@ static void part_windows(uint64_t cases)
         // the grep over the same windows (it takes the whole text of the blocks it is given: both edges are the text's)
         const Bytes part(truth.begin() + start, truth.begin() + stop);
         const uint32_t delim = below(4) ? '\n' : 'x';
-        if (lds) grep_call<true>(part, set, delim, (uint32_t)below(2), wins);
-        else grep_call<false>(part, set, delim, (uint32_t)below(2), wins);
+        if (lds) grep_auto<true>(part, set, delim, (uint32_t)below(2), wins);
+        else grep_auto<false>(part, set, delim, (uint32_t)below(2), wins);
     }
     CHECK(finished > cases / 4 && tight > cases / 6 && found > cases, "the cases reach the edges: %llu finishing windows, %llu ranges on block edges, %llu hits", (ull)finished,
           (ull)tight, (ull)found);
@@ -977,11 +609,11 @@ static int mode_hits(char **argv)
     }
     CHECK(a.looks(), "the hits mode is for automata that look around");
     const Text t(text.data(), text.size(), 'w');
-    BzrLookWalk walk;
+    BzmSetWalk walk;
     walk.begin(a.plan.max_len, 0, ~0ull, 0, text.size(), 0, 0);
     walk.begin_look(a.plan.look_behind, a.plan.look_ahead);
     uint64_t lim = 0, hits, delims;
-    const BzfWindow w = walk.window_look(text.size(), true, &lim);
+    const BzfWindow w = walk.window_set(text.size(), true, &lim);
     std::vector<BzmHit> out;
     if (a.plan.in_lds) search_run(t.p, w, a.matcher<true>('\n', lim, w.n, 0, BZR_LOOK_EDGE), false, walk, out, &hits, &delims);
     else search_run(t.p, w, a.matcher<false>('\n', lim, w.n, 0, BZR_LOOK_EDGE), false, walk, out, &hits, &delims);
@@ -992,6 +624,7 @@ static int mode_hits(char **argv)
 int main(int argc, char **argv)
 {
     if (argc == 7 && !strcmp(argv[1], "hits")) return mode_hits(argv);
+    poison_tile = poison_front = 'w';
     rng_state = argc > 1 ? strtoull(argv[1], nullptr, 10) * 0x9E3779B97F4A7C15ull + 1 : 1;
     const uint64_t cases = argc > 2 ? strtoull(argv[2], nullptr, 10) : 200;
     part_compile(cases);

@@ -8,57 +8,17 @@
 // (c) The windows: BzmSetWalk (search_plan.h) and BzgWalk (grep_plan.h) with (b) as the device, against brute force per byte.
 //
 //   patset_host <seed> <cases>     exit status 0: everything held
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
+#define HOST_NAME "patset_host"
 #include <string>
-#include <vector>
 
 #include "../../include/bzhip.h"
-#include "../../banzai_amd/csrc/grep_plan.h"
-#include "../../banzai_amd/csrc/patset_core.h"
 #include "../../banzai_amd/csrc/patset_plan.h"
-#include "../../banzai_amd/csrc/search_plan.h"
-#include "tile_host.h"
+#include "scan_host.h"
 
-static uint64_t rng_state;
-static uint64_t rnd()
-{
-    rng_state ^= rng_state << 13;
-    rng_state ^= rng_state >> 7;
-    rng_state ^= rng_state << 17;
-    return rng_state;
-}
-static uint64_t below(uint64_t n) { return n ? rnd() % n : 0; }
-
-#define CHECK(cond, ...)                                  \
-    do {                                                  \
-        if (!(cond)) {                                    \
-            fprintf(stderr, "patset_host: %s: ", #cond);  \
-            fprintf(stderr, __VA_ARGS__);                 \
-            fprintf(stderr, "\n");                        \
-            exit(1);                                      \
-        }                                                 \
-    } while (0)
-#define EVERY for (uint32_t tid = 0; tid < BZF_THREADS; tid++)
-typedef std::vector<uint8_t> Bytes;
 typedef std::vector<Bytes> Pats;
-typedef unsigned long long ull;
 
 static_assert(sizeof(bzh_set_hit) == sizeof(BzmHit) && sizeof(BzmHit) == 24, "a set's hit is three words");
 static_assert(sizeof(bzh_grep_entry) == sizeof(BzgEntry), "an entry is four words");
-
-template <class T>
-static T *exact(const T *src, size_t count) // a copy in an allocation of exactly its size (count 0: one byte nobody may touch)
-{
-    T *p = (T *)malloc(count ? count * sizeof(T) : 1);
-    if (!p) abort();
-    if (count) memcpy(p, src, count * sizeof(T));
-    return p;
-}
 
 // ---- a compiled set as the device holds it, and the naive matcher ----------------------------------------------------------------
 struct Set {
@@ -226,185 +186,7 @@ static void part_compile()
     printf("compile: held\n");
 }
 
-// ---- (b) the device -----------------------------------------------------------------------------------------------------------------
-struct Group { // one workgroup: its LDS and its threads' registers
-    uint8_t *tile;
-    BzmShared *msh;
-    BzgShared *sh;
-    BzfVec own[BZF_THREADS];
-    uint32_t hm[BZF_THREADS], nh[BZF_THREADS], dm[BZF_THREADS];
-    BzgThread th[BZF_THREADS];
-    Group() : msh(new BzmShared), sh(new BzgShared)
-    {
-        if (posix_memalign((void **)&tile, 16, BZF_TILE + BZF_MAX_PATTERN)) abort();
-    }
-    ~Group() { free(tile), delete msh, delete sh; }
-    void stage(const BzmMatcher &m, const uint8_t *d, uint64_t n, uint64_t t)
-    {
-        memset(tile, 0xAA, BZF_TILE + BZF_MAX_PATTERN), memset(msh, 0xAA, sizeof *msh), memset(sh, 0xAA, sizeof *sh); // (what no thread stores is not known)
-        EVERY own[tid] = m.stage(d, n, t * BZF_TILE, tid, tile, *msh);
-    }
-};
-
-// search_tiles up to the counts of every thread
-static void search_front(const uint8_t *d, const BzfWindow &w, const BzmMatcher &m, bool records, uint64_t t, Group &g)
-{
-    g.stage(m, d, w.n, t);
-    EVERY {
-        const uint64_t p0 = t * BZF_TILE + tid * BZF_ITEMS;
-        const BzfVec &v = g.own[tid];
-        g.nh[tid] = m.count16(v, tid, p0, g.tile, *g.msh, bzf_range_mask16(p0, w.s_lo, w.s_hi), &g.hm[tid]);
-        CHECK(g.hm[tid] == m.match16(v, tid, p0, g.tile, *g.msh, bzf_range_mask16(p0, w.s_lo, w.s_hi)), "count16 and match16 name the same starts");
-        g.dm[tid] = records ? bzf_eq_mask16(v.x, v.y, v.z, v.w, m.delim()) & bzf_range_mask16(p0, w.d_lo, w.n) : 0u;
-    }
-}
-// search_window_run: both passes and the scan between them.  out: the window's hit slots, exactly w.emit of them
-static void search_run(const uint8_t *d, BzfWindow w, uint64_t lim, const Set &s, uint32_t delim, bool records, const BzfWalk &walk, std::vector<BzmHit> &out,
-                       uint64_t *hits, uint64_t *delims)
-{
-    const BzmMatcher m = s.matcher(delim, lim);
-    const uint64_t tiles = (w.n + BZF_TILE - 1) / BZF_TILE;
-    std::vector<uint32_t> thits(tiles), tdel(tiles);
-    std::vector<uint64_t> hbase(tiles), dbase(tiles);
-    Group g;
-    *hits = *delims = 0;
-    if (!(tiles && (w.s_hi > w.s_lo || records))) return;
-    for (uint64_t t = 0; t < tiles; t++) {
-        search_front(d, w, m, records, t, g);
-        uint64_t sum = 0;
-        EVERY sum += g.nh[tid], tdel[t] += (uint32_t)__builtin_popcount(g.dm[tid]);
-        CHECK(sum <= 4096ull * 256, "a tile's hits fit 32 bits");
-        thits[t] = (uint32_t)sum;
-    }
-    uint64_t rh = 0, rd = 0;
-    for (uint64_t t = 0; t < tiles; t++) hbase[t] = rh, dbase[t] = rd, rh += thits[t], rd += tdel[t];
-    *hits = rh, *delims = rd;
-    w.emit = walk.emit(rh);
-    out.assign((size_t)w.emit, BzmHit{~0ull, ~0ull, ~0u, ~0u});
-    out.shrink_to_fit();
-    for (uint64_t t = 0; t < tiles && w.emit; t++) {
-        if (thits[t] == 0 || hbase[t] >= w.emit) continue;
-        search_front(d, w, m, records, t, g);
-        uint64_t h0 = 0, dsum = 0;
-        EVERY {
-            const uint64_t p0 = t * BZF_TILE + tid * BZF_ITEMS;
-            uint64_t rank = hbase[t] + h0;
-            for (uint32_t hm = g.hm[tid]; hm; hm &= hm - 1u) {
-                const uint32_t k = (uint32_t)__builtin_ctz(hm);
-                if (rank >= w.emit) break;
-                const uint64_t pos = p0 + k;
-                uint64_t rec = 0;
-                if (records) {
-                    if (pos >= w.d_lo) {
-                        rec = w.rec_base + dbase[t] + dsum + bzf_delims_before(g.dm[tid], k);
-                    } else {
-                        const uint32_t gap = (uint32_t)std::min<uint64_t>(w.d_lo - pos, BZF_MAX_PATTERN - 1);
-                        uint32_t c = 0;
-                        for (uint32_t j = 0; j < gap; j++) c += g.tile[tid * BZF_ITEMS + k + j] == delim;
-                        rec = w.rec_base - c;
-                    }
-                }
-                rank = m.emit1(*g.msh, g.tile + tid * BZF_ITEMS + k, pos, w.off_base + pos, rec, out.data(), rank, w.emit);
-            }
-            h0 += g.nh[tid], dsum += (uint32_t)__builtin_popcount(g.dm[tid]);
-        }
-    }
-}
-
-static void same_hits(const std::vector<BzmHit> &got, const std::vector<BzmHit> &want, uint64_t nhits, uint64_t max, const char *what, uint64_t a)
-{
-    CHECK(nhits == want.size(), "%s (%llu): %llu hits, the truth has %zu", what, (ull)a, (ull)nhits, want.size());
-    const size_t m = (size_t)std::min<uint64_t>(max, want.size());
-    CHECK(got.size() >= m, "%s: %zu hits stored of %zu", what, got.size(), m);
-    for (size_t i = 0; i < m; i++) {
-        CHECK(got[i].off == want[i].off && got[i].record == want[i].record && got[i].pattern == want[i].pattern && got[i].len == want[i].len,
-              "%s (%llu): hit %zu is (%llu, %llu, %u, %u), the truth (%llu, %llu, %u, %u)", what, (ull)a, i, (ull)got[i].off, (ull)got[i].record,
-              got[i].pattern, got[i].len, (ull)want[i].off, (ull)want[i].record, want[i].pattern, want[i].len);
-        // the order, and no pair twice, said explicitly
-        if (i) CHECK(got[i - 1].off < got[i].off || (got[i - 1].off == got[i].off && got[i - 1].len < got[i].len), "%s: hit %zu is out of order or a duplicate", what, i);
-    }
-}
-
-// ---- the grep's device: grep_tiles and grep_scan with the set as the matcher -----------------------------------------------------------
-static void grep_front(const uint8_t *d, const BzgWindow &w, const BzmMatcher &m, uint64_t t, Group &g)
-{
-    g.stage(m, d, w.n, t);
-    EVERY {
-        const uint64_t p0 = t * BZF_TILE + tid * BZF_ITEMS;
-        const uint32_t starts = BzmMatcher::BY_LIM ? bzf_range_mask16(p0, w.p_lo, w.p_hi) : bzg_starts(w, p0);
-        bzg_masks(g.th[tid], w, p0, g.own[tid], m.delim(), m.match16(g.own[tid], tid, p0, g.tile, *g.msh, starts));
-        bzg_local(g.th[tid], w.invert);
-    }
-    EVERY bzg_count_p0(*g.sh, tid, g.th[tid]);
-    for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_f(*g.sh, tid, k);
-}
-struct GrepCall { // GrepSink
-    const Set *set;
-    uint32_t delim;
-    BzgWalk walk;
-    uint8_t *out;
-    BzgEntry *ent;
-};
-static uint64_t grep_run(GrepCall &s, const uint8_t *d, const BzgWindow &w, uint64_t bytes)
-{
-    const BzmMatcher m = s.set->matcher(s.delim, w.n);
-    const uint64_t tiles = (w.n + BZF_TILE - 1) / BZF_TILE;
-    uint64_t totals[BZG_TOTALS] = {0, 0, 0, w.t_lo, w.open_hit};
-    if (tiles && w.p_hi > w.p_lo) {
-        std::vector<BzgTile> tile(tiles);
-        std::vector<BzgBase> base(tiles);
-        Group g;
-        for (uint64_t t = 0; t < tiles; t++) {
-            grep_front(d, w, m, t, g);
-            EVERY bzg_count_p1(*g.sh, tid, g.th[tid], w.invert);
-            for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_s(*g.sh, tid, k);
-            bzg_count_p2(*g.sh, tile[t]);
-        }
-        {
-            BzgScanShared *sh = new BzgScanShared;
-            memset(sh, 0xAA, sizeof *sh);
-            const uint32_t nt = (uint32_t)tiles;
-            EVERY bzg_scan_a(*sh, tid, tile.data(), nt);
-            bzg_scan_b(*sh, w, totals);
-            EVERY bzg_scan_c(*sh, tid, tile.data(), nt, w);
-            bzg_scan_d(*sh);
-            EVERY bzg_scan_e(*sh, tid, tile.data(), nt, w);
-            bzg_scan_f(*sh, totals);
-            EVERY bzg_scan_g(*sh, tid, tile.data(), nt, base.data());
-            delete sh;
-        }
-        if (s.walk.gather(totals)) {
-            std::vector<BzgEntry> ent((size_t)(s.walk.want_ent ? totals[BZG_T_SEL] : 0), BzgEntry{~0ull, ~0ull, ~0ull, ~0ull});
-            ent.shrink_to_fit();
-            uint8_t *out = s.walk.want_out ? s.out : nullptr;
-            for (uint64_t t = 0; t < tiles; t++) {
-                const BzgTile &x = tile[t];
-                if (x.bytes == 0) continue;
-                grep_front(d, w, m, t, g);
-                bool sel_first[BZF_THREADS];
-                uint32_t sm[BZF_THREADS], sdm[BZF_THREADS];
-                EVERY bzg_gather_p1(*g.sh, tid, g.th[tid], x, w.invert, &sel_first[tid]);
-                for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_b(*g.sh, tid, k);
-                EVERY bzg_gather_p2(*g.sh, tid, g.th[tid], x, sel_first[tid], &sm[tid], &sdm[tid]);
-                for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_s(*g.sh, tid, k);
-                uint8_t *dst = out ? out + w.out_base + base[t].out : nullptr;
-                const uint32_t shift = (uint32_t)((uintptr_t)dst & 3u);
-                EVERY bzg_gather_p3(*g.sh, tid, (uint32_t)t, g.th[tid], x, base[t], w, g.tile + tid * BZF_ITEMS, sm[tid], sdm[tid], shift, dst != nullptr,
-                                    s.walk.want_ent ? ent.data() : nullptr);
-                if (dst) EVERY bzg_gather_p4(*g.sh, tid, dst, shift, x.bytes);
-            }
-            for (size_t k = 0; k < ent.size(); k++) s.ent[w.sel_base + k] = ent[k];
-        }
-    }
-    s.walk.advance(w, bytes, totals);
-    return totals[BZG_T_TAIL_START];
-}
-
-struct GrepTruth {
-    Bytes out;
-    std::vector<BzgEntry> ent;
-    uint64_t nrecords;
-};
+// ---- (b) the device: scan_host.h's model with BzmMatcher --------------------------------------------------------------------------
 static GrepTruth grep_naive(const Bytes &text, const Set &s, uint32_t delim, uint32_t invert)
 {
     GrepTruth tr;
@@ -425,62 +207,11 @@ static GrepTruth grep_naive(const Bytes &text, const Set &s, uint32_t delim, uin
     tr.nrecords = rec;
     return tr;
 }
-static uint64_t room_of(int kind, uint64_t need) { return kind == 1 ? need + 5 : kind == 2 ? need : kind == 3 ? (need ? need - 1 : 0) : 0; }
-
 // one grep call; blocks: the windows' new bytes (empty: the raw call)
-static void grep_call(const Bytes &text, const Set &set, uint32_t delim, uint32_t invert, const std::vector<uint64_t> &blocks, int out_kind, int ent_kind)
+static void grep_set(const Bytes &text, const Set &set, uint32_t delim, uint32_t invert, const std::vector<uint64_t> &blocks, int out_kind, int ent_kind)
 {
-    const GrepTruth tr = grep_naive(text, set, delim, invert);
-    const uint64_t cap = room_of(out_kind, tr.out.size()), max = room_of(ent_kind, tr.ent.size());
-    uint8_t *out = out_kind ? (uint8_t *)malloc(cap ? cap : 1) : nullptr;
-    std::vector<BzgEntry> ent((size_t)max);
-    ent.shrink_to_fit();
-    GrepCall s{&set, delim, BzgWalk{}, out, ent_kind ? ent.data() : nullptr};
-    if (ent_kind && !max) s.ent = reinterpret_cast<BzgEntry *>(sizeof(BzgEntry));
-    s.walk.begin(set.plan.max_len, invert != 0, out_kind != 0, cap, ent_kind != 0, max);
-    const uint8_t slack = delim == 0xEE ? 0xED : 0xEE;
-    Bytes carry;
-    if (blocks.empty()) {
-        const Text d(text.data(), text.size(), slack);
-        const uint64_t ts = grep_run(s, d.p, s.walk.window(0, text.size(), true), text.size());
-        carry.assign(d.p + ts, d.p + text.size());
-    } else {
-        uint64_t at = 0;
-        for (uint64_t bytes : blocks) {
-            const uint64_t extra = bzg_front_extra(s.walk.carry, BZF_FRONT), front = extra + BZF_FRONT;
-            const Text stage(front + bytes, slack);
-            memset(stage.p, 0xCC, front);
-            if (!carry.empty()) memcpy(stage.p + front - carry.size(), carry.data(), carry.size());
-            if (bytes) memcpy(stage.p + front, &text[at], bytes);
-            at += bytes;
-            const uint64_t ts = grep_run(s, stage.p, s.walk.window(front, bytes, false), bytes);
-            carry.assign(stage.p + ts, stage.p + front + bytes);
-        }
-    }
-    if (s.walk.held) { // grep_finish
-        const Text held(carry.data(), carry.size(), slack);
-        const uint64_t ts = grep_run(s, held.p, s.walk.window(s.walk.carry, 0, true), 0);
-        carry.erase(carry.begin(), carry.begin() + ts);
-    }
-    CHECK(carry.size() == s.walk.carry && s.walk.held == 0, "the tail");
-    bool copy, entry;
-    s.walk.tail_rooms(&copy, &entry);
-    const BzgEntry te = s.walk.tail_entry();
-    if (copy && !carry.empty()) memcpy(s.out + s.walk.out_bytes, carry.data(), carry.size());
-    s.walk.tail_done();
-    if (entry) s.ent[s.walk.sel - 1] = te;
-    CHECK(s.walk.sel == tr.ent.size() && s.walk.out_bytes == tr.out.size() && s.walk.nrecords() == tr.nrecords,
-          "grep counts: %llu selected of %llu bytes, %llu records; the truth %zu, %zu, %llu", (ull)s.walk.sel, (ull)s.walk.out_bytes,
-          (ull)s.walk.nrecords(), tr.ent.size(), tr.out.size(), (ull)tr.nrecords);
-    const bool over = (out_kind && tr.out.size() > cap) || (ent_kind && tr.ent.size() > max);
-    CHECK(s.walk.overflow() == over, "BZH_E_CAP exactly when a room that is asked for is too small");
-    if (!over) {
-        if (out_kind && !tr.out.empty()) CHECK(memcmp(out, tr.out.data(), tr.out.size()) == 0, "the selected bytes");
-        for (size_t k = 0; ent_kind && k < tr.ent.size(); k++)
-            CHECK(ent[k].record == tr.ent[k].record && ent[k].off == tr.ent[k].off && ent[k].len == tr.ent[k].len && ent[k].out_off == tr.ent[k].out_off,
-                  "grep entry %zu", k);
-    }
-    free(out);
+    grep_call(text, grep_naive(text, set, delim, invert), [&](const BzgWindow &w) { return set.matcher(delim, w.n); }, set.plan.max_len, invert,
+              (uint8_t)(delim == 0xEE ? 0xED : 0xEE), blocks, out_kind, ent_kind);
 }
 
 // one raw search call with `max` hit slots; returns the hits
@@ -494,7 +225,7 @@ static uint64_t search_raw(const Bytes &src, const Set &set, uint32_t delim, boo
     const BzfWindow w = walk.window_set(n, true, &lim);
     CHECK(lim == n || w.s_hi == w.s_lo, "the raw window ends at the text's end");
     std::vector<BzmHit> out;
-    search_run(text.p, w, lim, set, delim, records, walk, out, &hits, &delims);
+    search_run(text.p, w, set.matcher(delim, lim), records, walk, out, &hits, &delims);
     same_hits(out, set.naive(text.p, n, 0, n, records, delim), hits, max, "raw", n);
     CHECK(!records || delims == (uint64_t)std::count(text.p, text.p + n, (uint8_t)delim), "raw (%llu): delimiters", (ull)n);
     return hits;
@@ -531,7 +262,7 @@ static void part_matcher()
             Bytes text(n);
             for (auto &c : text) c = (uint8_t)"abcdABCD\nx"[below(10)];
             found += search_raw(text, set, '\n', true, ~0ull), cases++;
-            grep_call(text, set, '\n', 0, {}, 2, 2), grep_call(text, set, '\n', 1, {}, 2, 2);
+            grep_set(text, set, '\n', 0, {}, 2, 2), grep_set(text, set, '\n', 1, {}, 2, 2);
             // the fixed places: offset 0, ending at byte n - 1, across a thread edge, a wave edge, a tile edge -- every length there, the
             // chain's patterns at one start; the longest cut by the text's end while its prefixes still match
             for (uint32_t l : lens) {
@@ -548,7 +279,7 @@ static void part_matcher()
                 const uint64_t h = search_raw(t2, set, '\n', true, ~0ull);
                 CHECK(h >= planted, "planted %llu, found %llu", (ull)planted, (ull)h);
                 found += h, cases++;
-                grep_call(t2, set, '\n', 0, {}, 2, 2), grep_call(t2, set, '\n', 1, {}, 1, 0);
+                grep_set(t2, set, '\n', 0, {}, 2, 2), grep_set(t2, set, '\n', 1, {}, 1, 0);
             }
             // one byte value everywhere, the set every run of it up to 256: every slot, three, none; the delimiter a pattern byte
             {
@@ -561,8 +292,8 @@ static void part_matcher()
                 CHECK(search_raw(t3, rs, fold ? 'Z' : 'z', true, ~0ull) == want, "a buffer of one byte value");
                 CHECK(search_raw(t3, rs, 'z', true, 3) == want, "a buffer of one byte value, three slots");
                 CHECK(search_raw(t3, rs, 'z', false, 0) == want, "a buffer of one byte value, no slots");
-                grep_call(t3, rs, fold ? 'Z' : 'z', 0, {}, 2, 2);
-                grep_call(t3, rs, 'q', 0, {}, 2, 2), grep_call(t3, rs, 'q', 1, {}, 3, 3);
+                grep_set(t3, rs, fold ? 'Z' : 'z', 0, {}, 2, 2);
+                grep_set(t3, rs, 'q', 0, {}, 2, 2), grep_set(t3, rs, 'q', 1, {}, 3, 3);
                 cases += 3;
             }
         }
@@ -613,16 +344,20 @@ static void part_windows(uint64_t cases)
         for (uint64_t i = 0; i < start; i++) rec_start += truth[i] == '\n';
         BzmSetWalk walk;
         walk.begin(set.plan.max_len, BZF_FRONT, max, lo, hi, start, records ? rec_start : 0);
+        ZeroLookTwin zero; // (no assertion is the zero case)
+        zero.begin(set.plan.max_len, BZF_FRONT, max, lo, hi, start, records ? rec_start : 0);
         std::vector<BzmHit> got((size_t)std::min<uint64_t>(max, want.size() + 8), BzmHit{~0ull, ~0ull, ~0u, ~0u});
         Bytes carry;
         uint64_t at_out = start;
-        auto run = [&](const uint8_t *d, const BzfWindow &w, uint64_t lim, uint64_t bytes) {
+        auto run = [&](const uint8_t *d, const BzfWindow &w, uint64_t lim, uint64_t bytes, bool is_last) {
             CHECK(w.s_lo <= w.s_hi && w.s_hi <= lim && lim <= w.n, "window: starts [%llu, %llu) lim %llu n %llu", (ull)w.s_lo, (ull)w.s_hi, (ull)lim, (ull)w.n);
+            zero.window(walk, bytes, is_last, w, lim);
             std::vector<BzmHit> out;
             uint64_t hits, delims;
-            search_run(d, w, lim, set, '\n', records, walk, out, &hits, &delims);
+            search_run(d, w, set.matcher('\n', lim), records, walk, out, &hits, &delims);
             for (size_t i = 0; i < out.size(); i++) got.at((size_t)walk.rank + i) = out[i];
-            walk.advance(bytes, hits, delims);
+            walk.advance_set(bytes, hits, delims, is_last);
+            zero.advance(walk, bytes, hits, delims, is_last);
             windows++;
         };
         for (size_t at = first; at < last;) {
@@ -633,15 +368,15 @@ static void part_windows(uint64_t cases)
             wins.push_back(bytes);
             // SearchSink::room and ::window: a staging buffer of exactly these bytes, the carry in front of the window
             const Text staging(BZF_FRONT + bytes);
-            memset(staging.p, 0xCC, BZF_FRONT);
+            memset(staging.p, poison_front, BZF_FRONT);
             CHECK(carry.size() == walk.carry, "the carry");
             if (!carry.empty()) memcpy(staging.p + BZF_FRONT - carry.size(), carry.data(), carry.size());
             memcpy(staging.p + BZF_FRONT, &truth[at_out], (size_t)bytes);
             uint64_t lim = 0;
             const BzfWindow w = walk.window_set(bytes, false, &lim);
-            const uint64_t keep = walk.carry_after(bytes);
+            const uint64_t keep = walk.carry_after_set(bytes);
             const Bytes next(staging.p + w.n - keep, staging.p + w.n);
-            run(staging.p, w, lim, bytes);
+            run(staging.p, w, lim, bytes, false);
             carry = next;
             at_out += bytes, at += nbw;
         }
@@ -650,13 +385,13 @@ static void part_windows(uint64_t cases)
             walk.front = walk.carry;
             uint64_t lim = 0;
             const BzfWindow w = walk.window_set(0, true, &lim);
-            run(held.p, w, lim, 0);
+            run(held.p, w, lim, 0, true);
             finished++;
         }
         same_hits(got, want, walk.rank, max, "windows", c);
         // the grep over the same windows (it takes the whole text of the blocks it is given)
         const Bytes part(truth.begin() + start, truth.begin() + stop);
-        grep_call(part, set, '\n', (uint32_t)below(2), wins, (int)below(5), (int)below(5));
+        grep_set(part, set, '\n', (uint32_t)below(2), wins, (int)below(5), (int)below(5));
     }
     CHECK(finished > cases / 4 && cut > 0, "the cases reach the edges: %llu finishing windows, %llu long patterns cut by the range", (ull)finished, (ull)cut);
     printf("windows: %llu cases held, %llu windows, %llu finishing ones, %llu cut by the range\n", (ull)cases, (ull)windows, (ull)finished, (ull)cut);

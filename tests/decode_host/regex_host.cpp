@@ -2,157 +2,34 @@
 // (a) The compile of banzai_amd/csrc/regex_plan.h against a naive matcher over the harness's OWN expressions: seeded random trees of
 //     the grammar, printed for the compiler and matched here on the tree, at every offset of seeded texts, with two bounds and two
 //     spans; every refused form; the state bound; the blow-up; what folds and what does not.
-// (b) The matchers of banzai_amd/csrc/regex_core.h -- BzrMatcher<true> and BzrMatcher<false>, the kernels' own text -- thread by
+// (b) The matchers of banzai_amd/csrc/regex_core.h -- BzrMatcher<true, false> and BzrMatcher<false, false>, the kernels' own text -- thread by
 //     thread and tile by tile in the kernels' layout over a model of the LDS: both passes of search_tiles and the scan between them,
 //     both passes of grep_tiles with grep_core.h's phases and scan.  The table, the LDS model and every buffer have their exact sizes.
 // (c) The windows: BzmSetWalk (search_plan.h) and BzgWalk (grep_plan.h) with (b) as the device, against brute force per byte.
 //
 //   regex_host <seed> <cases>                          exit status 0: everything held
 //   regex_host hits EXPRFILE TEXTFILE FLAGS SPAN       one expression a line; prints "off pattern len" for every hit of the text
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <time.h>
-
-#include <algorithm>
+#define HOST_NAME "regex_host"
 #include <bitset>
 #include <set>
 #include <string>
-#include <vector>
 
 #include "../../include/bzhip.h"
-#include "../../banzai_amd/csrc/grep_plan.h"
 #include "../../banzai_amd/csrc/regex_core.h"
 #include "../../banzai_amd/csrc/regex_plan.h"
-#include "../../banzai_amd/csrc/search_plan.h"
-#include "tile_host.h"
+#include "regex_ex_host.h"
+#include "scan_host.h"
 
-static uint64_t rng_state;
-static uint64_t rnd()
-{
-    rng_state ^= rng_state << 13;
-    rng_state ^= rng_state >> 7;
-    rng_state ^= rng_state << 17;
-    return rng_state;
-}
-static uint64_t below(uint64_t n) { return n ? rnd() % n : 0; }
-
-#define CHECK(cond, ...)                                  \
-    do {                                                  \
-        if (!(cond)) {                                    \
-            fprintf(stderr, "regex_host: %s: ", #cond);   \
-            fprintf(stderr, __VA_ARGS__);                 \
-            fprintf(stderr, "\n");                        \
-            exit(1);                                      \
-        }                                                 \
-    } while (0)
-#define EVERY for (uint32_t tid = 0; tid < BZF_THREADS; tid++)
-typedef std::vector<uint8_t> Bytes;
 typedef std::vector<Bytes> Pats;
-typedef unsigned long long ull;
 
 static_assert(sizeof(bzh_set_hit) == sizeof(BzmHit) && sizeof(BzmHit) == 24, "a set's hit is three words");
 static_assert(sizeof(bzh_grep_entry) == sizeof(BzgEntry), "an entry is four words");
 static_assert(sizeof(bzh_regex_info) == 40, "bzh_regex_info");
 static_assert((uint32_t)BZR_LDS_ROWS == (uint32_t)BZR_LDS_ENTRIES, "one bound");
 
-template <class T>
-static T *exact(const T *src, size_t count) // a copy in an allocation of exactly its size (count 0: one byte nobody may touch)
-{
-    T *p = (T *)malloc(count ? count * sizeof(T) : 1);
-    if (!p) abort();
-    if (count) memcpy(p, src, count * sizeof(T));
-    return p;
-}
 static Bytes B(const char *s) { return Bytes(s, s + strlen(s)); }
 
 // ---- the harness's own expressions: a tree, its text for the compiler, and the naive matcher on the tree --------------------------
-struct Ex {
-    enum Kind { SET, CAT, ALT, REP } kind = SET;
-    std::bitset<256> set; // SET: the bytes as written (unfolded, not negated)
-    bool neg = false;
-    std::string text;     // SET: how it is written
-    std::vector<Ex> kids;
-    uint32_t lo = 0, hi = 0; // REP; hi == ~0u: open
-};
-static uint8_t twin(uint8_t b) { return b >= 'A' && b <= 'Z' ? (uint8_t)(b + 32) : b >= 'a' && b <= 'z' ? (uint8_t)(b - 32) : b; }
-static bool takes(const Ex &e, uint8_t b, bool fold) { return (e.set[b] || (fold && e.set[twin(b)])) != e.neg; }
-typedef std::set<uint64_t> Ends;
-// the positions behind a match of e that begins at one of `in`, no byte at or behind lim taken
-static Ends ends(const Ex &e, const uint8_t *t, uint64_t lim, const Ends &in, bool fold)
-{
-    Ends out;
-    switch (e.kind) {
-    case Ex::SET:
-        for (uint64_t p : in)
-            if (p < lim && takes(e, t[p], fold)) out.insert(p + 1);
-        return out;
-    case Ex::CAT:
-        out = in;
-        for (const Ex &k : e.kids) out = ends(k, t, lim, out, fold);
-        return out;
-    case Ex::ALT:
-        for (const Ex &k : e.kids) {
-            const Ends x = ends(k, t, lim, in, fold);
-            out.insert(x.begin(), x.end());
-        }
-        return out;
-    default: {
-        Ends cur = in; // out: what k >= lo rounds reach; it stops growing one round before nothing new can come
-        if (e.lo == 0) out = in;
-        for (uint32_t k = 1; e.hi == ~0u || k <= e.hi; k++) {
-            cur = ends(e.kids[0], t, lim, cur, fold);
-            if (cur.empty()) break;
-            if (k < e.lo) continue;
-            const size_t before = out.size();
-            out.insert(cur.begin(), cur.end());
-            if (out.size() == before && k > e.lo) break;
-        }
-        return out;
-    }
-    }
-}
-static uint64_t min_len(const Ex &e)
-{
-    uint64_t r = 0;
-    switch (e.kind) {
-    case Ex::SET: return 1;
-    case Ex::CAT:
-        for (const Ex &k : e.kids) r += min_len(k);
-        return r;
-    case Ex::ALT:
-        r = ~0ull;
-        for (const Ex &k : e.kids) r = std::min(r, min_len(k));
-        return r;
-    default: return e.lo * min_len(e.kids[0]);
-    }
-}
-static std::string print(const Ex &e, bool top = false)
-{
-    std::string s;
-    switch (e.kind) {
-    case Ex::SET: return e.text;
-    case Ex::CAT:
-        for (const Ex &k : e.kids) s += k.kind == Ex::ALT ? "(?:" + print(k) + ")" : print(k);
-        return s;
-    case Ex::ALT:
-        for (size_t i = 0; i < e.kids.size(); i++) s += (i ? "|" : "") + print(e.kids[i]);
-        return top ? s : "(" + s + ")";
-    default: {
-        const Ex &k = e.kids[0];
-        s = k.kind == Ex::SET ? print(k) : k.kind == Ex::ALT ? print(k) : "(" + print(k) + ")";
-        char q[40];
-        if (e.lo == 0 && e.hi == 1) return s + "?";
-        if (e.lo == 0 && e.hi == ~0u) return s + "*";
-        if (e.lo == 1 && e.hi == ~0u) return s + "+";
-        if (e.hi == ~0u) snprintf(q, sizeof q, "{%u,}", e.lo);
-        else if (e.hi == e.lo) snprintf(q, sizeof q, "{%u}", e.lo);
-        else snprintf(q, sizeof q, "{%u,%u}", e.lo, e.hi);
-        return s + q;
-    }
-    }
-}
 static const char ALPHA[] = "abAB01 _\n-z";
 static Ex lit(uint8_t b)
 {
@@ -257,9 +134,9 @@ struct Auto {
     ~Auto() { free(cls), free(first), free(table), free(pat_no); }
     Auto(const Auto &) = delete;
     template <bool L>
-    BzrMatcher<L> matcher(uint32_t delim, uint64_t lim) const
+    BzrMatcher<L, false> matcher(uint32_t delim, uint64_t lim) const
     {
-        return BzrMatcher<L>{BzrAuto{BzmSet{cls, first, table, pat_no, plan.classes, plan.nterm, plan.max_len, delim, lim}, plan.states * plan.classes}};
+        return BzrMatcher<L, false>{{BzrAuto{BzmSet{cls, first, table, pat_no, plan.classes, plan.nterm, plan.max_len, delim, lim}, plan.states * plan.classes}}, {}};
     }
     // the table walked without a tile, every invariant checked on the way: the hit at text[o ..) bounded by lim
     bool walk(const uint8_t *text, uint64_t o, uint64_t lim, uint32_t *pattern, uint32_t *len) const
@@ -365,7 +242,7 @@ static void part_compile(uint64_t cases)
                     uint64_t best = 0;
                     uint32_t who = 0;
                     for (uint32_t j = 0; j < exs.size(); j++) {
-                        const Ends en = ends(exs[j], t.p, lim, Ends{o}, fold);
+                        const Ends en = ends(exs[j], t.p, text.size(), lim, Ends{o}, fold);
                         for (uint64_t e : en) {
                             if (e - o > span) longer = true;
                             else if (e > o && e - o > best) best = e - o, who = j;
@@ -499,191 +376,7 @@ static void part_compile(uint64_t cases)
     printf("compile: held, %llu starts checked, %llu live, %llu seeded cases above a bound\n", (ull)checked, (ull)live, (ull)refused_big);
 }
 
-// ---- (b) the device -----------------------------------------------------------------------------------------------------------------
-template <class M>
-struct Group { // one workgroup: its LDS and its threads' registers
-    uint8_t *tile;
-    typename M::Shared *msh;
-    BzgShared *sh;
-    BzfVec own[BZF_THREADS];
-    uint32_t hm[BZF_THREADS], nh[BZF_THREADS], dm[BZF_THREADS];
-    BzgThread th[BZF_THREADS];
-    Group() : msh(new typename M::Shared), sh(new BzgShared)
-    {
-        if (posix_memalign((void **)&tile, 16, BZF_TILE + BZF_MAX_PATTERN)) abort();
-    }
-    ~Group() { free(tile), delete msh, delete sh; }
-    void stage(const M &m, const uint8_t *d, uint64_t n, uint64_t t)
-    {
-        memset(tile, 0xAA, BZF_TILE + BZF_MAX_PATTERN), memset((void *)msh, 0xAA, sizeof *msh), memset((void *)sh, 0xAA, sizeof *sh); // (what no thread stores is not known)
-        EVERY own[tid] = m.stage(d, n, t * BZF_TILE, tid, tile, *msh);
-    }
-};
-
-// search_tiles up to the counts of every thread
-template <class M>
-static void search_front(const uint8_t *d, const BzfWindow &w, const M &m, bool records, uint64_t t, Group<M> &g)
-{
-    g.stage(m, d, w.n, t);
-    EVERY {
-        const uint64_t p0 = t * BZF_TILE + tid * BZF_ITEMS;
-        const BzfVec &v = g.own[tid];
-        g.nh[tid] = m.count16(v, tid, p0, g.tile, *g.msh, bzf_range_mask16(p0, w.s_lo, w.s_hi), &g.hm[tid]);
-        CHECK(g.hm[tid] == m.match16(v, tid, p0, g.tile, *g.msh, bzf_range_mask16(p0, w.s_lo, w.s_hi)) && g.nh[tid] == (uint32_t)__builtin_popcount(g.hm[tid]),
-              "count16 and match16 name the same starts, one hit each");
-        g.dm[tid] = records ? bzf_eq_mask16(v.x, v.y, v.z, v.w, m.delim()) & bzf_range_mask16(p0, w.d_lo, w.n) : 0u;
-    }
-}
-// search_window_run: both passes and the scan between them.  out: the window's hit slots, exactly w.emit of them
-template <class M>
-static void search_run(const uint8_t *d, BzfWindow w, const M &m, bool records, const BzfWalk &walk, std::vector<BzmHit> &out, uint64_t *hits, uint64_t *delims)
-{
-    const uint32_t delim = m.delim();
-    const uint64_t tiles = (w.n + BZF_TILE - 1) / BZF_TILE;
-    std::vector<uint32_t> thits(tiles), tdel(tiles);
-    std::vector<uint64_t> hbase(tiles), dbase(tiles);
-    Group<M> g;
-    *hits = *delims = 0;
-    if (!(tiles && (w.s_hi > w.s_lo || records))) return;
-    for (uint64_t t = 0; t < tiles; t++) {
-        search_front(d, w, m, records, t, g);
-        uint64_t sum = 0;
-        EVERY sum += g.nh[tid], tdel[t] += (uint32_t)__builtin_popcount(g.dm[tid]);
-        thits[t] = (uint32_t)sum;
-    }
-    uint64_t rh = 0, rd = 0;
-    for (uint64_t t = 0; t < tiles; t++) hbase[t] = rh, dbase[t] = rd, rh += thits[t], rd += tdel[t];
-    *hits = rh, *delims = rd;
-    w.emit = walk.emit(rh);
-    out.assign((size_t)w.emit, BzmHit{~0ull, ~0ull, ~0u, ~0u});
-    out.shrink_to_fit();
-    for (uint64_t t = 0; t < tiles && w.emit; t++) {
-        if (thits[t] == 0 || hbase[t] >= w.emit) continue;
-        search_front(d, w, m, records, t, g);
-        uint64_t h0 = 0, dsum = 0;
-        EVERY {
-            const uint64_t p0 = t * BZF_TILE + tid * BZF_ITEMS;
-            uint64_t rank = hbase[t] + h0;
-            for (uint32_t hm = g.hm[tid]; hm; hm &= hm - 1u) {
-                const uint32_t k = (uint32_t)__builtin_ctz(hm);
-                if (rank >= w.emit) break;
-                const uint64_t pos = p0 + k;
-                uint64_t rec = 0;
-                if (records) {
-                    if (pos >= w.d_lo) {
-                        rec = w.rec_base + dbase[t] + dsum + bzf_delims_before(g.dm[tid], k);
-                    } else {
-                        const uint32_t gap = (uint32_t)std::min<uint64_t>(w.d_lo - pos, BZF_MAX_PATTERN - 1);
-                        uint32_t c = 0;
-                        for (uint32_t j = 0; j < gap; j++) c += g.tile[tid * BZF_ITEMS + k + j] == delim;
-                        rec = w.rec_base - c;
-                    }
-                }
-                const uint64_t next = m.emit1(*g.msh, g.tile + tid * BZF_ITEMS + k, pos, w.off_base + pos, rec, out.data(), rank, w.emit);
-                CHECK(next == rank + 1, "a start yields exactly one hit");
-                rank = next;
-            }
-            h0 += g.nh[tid], dsum += (uint32_t)__builtin_popcount(g.dm[tid]);
-        }
-    }
-}
-
-static void same_hits(const std::vector<BzmHit> &got, const std::vector<BzmHit> &want, uint64_t nhits, uint64_t max, const char *what, uint64_t a)
-{
-    CHECK(nhits == want.size(), "%s (%llu): %llu hits, the truth has %zu", what, (ull)a, (ull)nhits, want.size());
-    const size_t m = (size_t)std::min<uint64_t>(max, want.size());
-    CHECK(got.size() >= m, "%s: %zu hits stored of %zu", what, got.size(), m);
-    for (size_t i = 0; i < m; i++) {
-        CHECK(got[i].off == want[i].off && got[i].record == want[i].record && got[i].pattern == want[i].pattern && got[i].len == want[i].len,
-              "%s (%llu): hit %zu is (%llu, %llu, %u, %u), the truth (%llu, %llu, %u, %u)", what, (ull)a, i, (ull)got[i].off, (ull)got[i].record, got[i].pattern,
-              got[i].len, (ull)want[i].off, (ull)want[i].record, want[i].pattern, want[i].len);
-        if (i) CHECK(got[i - 1].off < got[i].off, "%s: hit %zu is out of order or a second one of its start", what, i);
-    }
-}
-
-// ---- the grep's device: grep_tiles and grep_scan with the automaton as the matcher ---------------------------------------------------
-template <class M>
-static void grep_front(const uint8_t *d, const BzgWindow &w, const M &m, uint64_t t, Group<M> &g)
-{
-    g.stage(m, d, w.n, t);
-    EVERY {
-        const uint64_t p0 = t * BZF_TILE + tid * BZF_ITEMS;
-        const uint32_t starts = M::BY_LIM ? bzf_range_mask16(p0, w.p_lo, w.p_hi) : bzg_starts(w, p0);
-        bzg_masks(g.th[tid], w, p0, g.own[tid], m.delim(), m.match16(g.own[tid], tid, p0, g.tile, *g.msh, starts));
-        bzg_local(g.th[tid], w.invert);
-    }
-    EVERY bzg_count_p0(*g.sh, tid, g.th[tid]);
-    for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_f(*g.sh, tid, k);
-}
-struct GrepCall { // GrepSink
-    const Auto *set;
-    uint32_t delim;
-    BzgWalk walk;
-    uint8_t *out;
-    BzgEntry *ent;
-};
-template <bool L>
-static uint64_t grep_run(GrepCall &s, const uint8_t *d, const BzgWindow &w, uint64_t bytes)
-{
-    typedef BzrMatcher<L> M;
-    const M m = s.set->template matcher<L>(s.delim, w.n);
-    const uint64_t tiles = (w.n + BZF_TILE - 1) / BZF_TILE;
-    uint64_t totals[BZG_TOTALS] = {0, 0, 0, w.t_lo, w.open_hit};
-    if (tiles && w.p_hi > w.p_lo) {
-        std::vector<BzgTile> tile(tiles);
-        std::vector<BzgBase> base(tiles);
-        Group<M> g;
-        for (uint64_t t = 0; t < tiles; t++) {
-            grep_front(d, w, m, t, g);
-            EVERY bzg_count_p1(*g.sh, tid, g.th[tid], w.invert);
-            for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_s(*g.sh, tid, k);
-            bzg_count_p2(*g.sh, tile[t]);
-        }
-        {
-            BzgScanShared *sh = new BzgScanShared;
-            memset((void *)sh, 0xAA, sizeof *sh);
-            const uint32_t nt = (uint32_t)tiles;
-            EVERY bzg_scan_a(*sh, tid, tile.data(), nt);
-            bzg_scan_b(*sh, w, totals);
-            EVERY bzg_scan_c(*sh, tid, tile.data(), nt, w);
-            bzg_scan_d(*sh);
-            EVERY bzg_scan_e(*sh, tid, tile.data(), nt, w);
-            bzg_scan_f(*sh, totals);
-            EVERY bzg_scan_g(*sh, tid, tile.data(), nt, base.data());
-            delete sh;
-        }
-        if (s.walk.gather(totals)) {
-            std::vector<BzgEntry> ent((size_t)(s.walk.want_ent ? totals[BZG_T_SEL] : 0), BzgEntry{~0ull, ~0ull, ~0ull, ~0ull});
-            ent.shrink_to_fit();
-            uint8_t *out = s.walk.want_out ? s.out : nullptr;
-            for (uint64_t t = 0; t < tiles; t++) {
-                const BzgTile &x = tile[t];
-                if (x.bytes == 0) continue;
-                grep_front(d, w, m, t, g);
-                bool sel_first[BZF_THREADS];
-                uint32_t sm[BZF_THREADS], sdm[BZF_THREADS];
-                EVERY bzg_gather_p1(*g.sh, tid, g.th[tid], x, w.invert, &sel_first[tid]);
-                for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_b(*g.sh, tid, k);
-                EVERY bzg_gather_p2(*g.sh, tid, g.th[tid], x, sel_first[tid], &sm[tid], &sdm[tid]);
-                for (uint32_t k = 0; k < 8; k++) EVERY bzg_step_s(*g.sh, tid, k);
-                uint8_t *dst = out ? out + w.out_base + base[t].out : nullptr;
-                const uint32_t shift = (uint32_t)((uintptr_t)dst & 3u);
-                EVERY bzg_gather_p3(*g.sh, tid, (uint32_t)t, g.th[tid], x, base[t], w, g.tile + tid * BZF_ITEMS, sm[tid], sdm[tid], shift, dst != nullptr,
-                                    s.walk.want_ent ? ent.data() : nullptr);
-                if (dst) EVERY bzg_gather_p4(*g.sh, tid, dst, shift, x.bytes);
-            }
-            for (size_t k = 0; k < ent.size(); k++) s.ent[w.sel_base + k] = ent[k];
-        }
-    }
-    s.walk.advance(w, bytes, totals);
-    return totals[BZG_T_TAIL_START];
-}
-
-struct GrepTruth {
-    Bytes out;
-    std::vector<BzgEntry> ent;
-    uint64_t nrecords;
-};
+// ---- (b) the device: scan_host.h's model with BzrMatcher<true / false, false> ---------------------------------------------------------
 static GrepTruth grep_naive(const Bytes &text, const Auto &s, uint32_t delim, uint32_t invert)
 {
     GrepTruth tr;
@@ -704,63 +397,12 @@ static GrepTruth grep_naive(const Bytes &text, const Auto &s, uint32_t delim, ui
     tr.nrecords = rec;
     return tr;
 }
-static uint64_t room_of(int kind, uint64_t need) { return kind == 1 ? need + 5 : kind == 2 ? need : kind == 3 ? (need ? need - 1 : 0) : 0; }
-
 // one grep call; blocks: the windows' new bytes (empty: the raw call)
 template <bool L>
-static void grep_call(const Bytes &text, const Auto &set, uint32_t delim, uint32_t invert, const std::vector<uint64_t> &blocks, int out_kind, int ent_kind)
+static void grep_auto(const Bytes &text, const Auto &set, uint32_t delim, uint32_t invert, const std::vector<uint64_t> &blocks, int out_kind, int ent_kind)
 {
-    const GrepTruth tr = grep_naive(text, set, delim, invert);
-    const uint64_t cap = room_of(out_kind, tr.out.size()), max = room_of(ent_kind, tr.ent.size());
-    uint8_t *out = out_kind ? (uint8_t *)malloc(cap ? cap : 1) : nullptr;
-    std::vector<BzgEntry> ent((size_t)max);
-    ent.shrink_to_fit();
-    GrepCall s{&set, delim, BzgWalk{}, out, ent_kind ? ent.data() : nullptr};
-    if (ent_kind && !max) s.ent = reinterpret_cast<BzgEntry *>(sizeof(BzgEntry));
-    s.walk.begin(set.plan.max_len, invert != 0, out_kind != 0, cap, ent_kind != 0, max);
-    const uint8_t slack = delim == 0xEE ? 0xED : 0xEE;
-    Bytes carry;
-    if (blocks.empty()) {
-        const Text d(text.data(), text.size(), slack);
-        const uint64_t ts = grep_run<L>(s, d.p, s.walk.window(0, text.size(), true), text.size());
-        carry.assign(d.p + ts, d.p + text.size());
-    } else {
-        uint64_t at = 0;
-        for (uint64_t bytes : blocks) {
-            const uint64_t extra = bzg_front_extra(s.walk.carry, BZF_FRONT), front = extra + BZF_FRONT;
-            const Text stage(front + bytes, slack);
-            memset(stage.p, 0xCC, front);
-            if (!carry.empty()) memcpy(stage.p + front - carry.size(), carry.data(), carry.size());
-            if (bytes) memcpy(stage.p + front, &text[at], bytes);
-            at += bytes;
-            const uint64_t ts = grep_run<L>(s, stage.p, s.walk.window(front, bytes, false), bytes);
-            carry.assign(stage.p + ts, stage.p + front + bytes);
-        }
-    }
-    if (s.walk.held) { // grep_finish
-        const Text held(carry.data(), carry.size(), slack);
-        const uint64_t ts = grep_run<L>(s, held.p, s.walk.window(s.walk.carry, 0, true), 0);
-        carry.erase(carry.begin(), carry.begin() + ts);
-    }
-    CHECK(carry.size() == s.walk.carry && s.walk.held == 0, "the tail");
-    bool copy, entry;
-    s.walk.tail_rooms(&copy, &entry);
-    const BzgEntry te = s.walk.tail_entry();
-    if (copy && !carry.empty()) memcpy(s.out + s.walk.out_bytes, carry.data(), carry.size());
-    s.walk.tail_done();
-    if (entry) s.ent[s.walk.sel - 1] = te;
-    CHECK(s.walk.sel == tr.ent.size() && s.walk.out_bytes == tr.out.size() && s.walk.nrecords() == tr.nrecords,
-          "grep counts: %llu selected of %llu bytes, %llu records; the truth %zu, %zu, %llu", (ull)s.walk.sel, (ull)s.walk.out_bytes, (ull)s.walk.nrecords(),
-          tr.ent.size(), tr.out.size(), (ull)tr.nrecords);
-    const bool over = (out_kind && tr.out.size() > cap) || (ent_kind && tr.ent.size() > max);
-    CHECK(s.walk.overflow() == over, "BZH_E_CAP exactly when a room that is asked for is too small");
-    if (!over) {
-        if (out_kind && !tr.out.empty()) CHECK(memcmp(out, tr.out.data(), tr.out.size()) == 0, "the selected bytes");
-        for (size_t k = 0; ent_kind && k < tr.ent.size(); k++)
-            CHECK(ent[k].record == tr.ent[k].record && ent[k].off == tr.ent[k].off && ent[k].len == tr.ent[k].len && ent[k].out_off == tr.ent[k].out_off,
-                  "grep entry %zu", k);
-    }
-    free(out);
+    grep_call(text, grep_naive(text, set, delim, invert), [&](const BzgWindow &w) { return set.matcher<L>(delim, w.n); }, set.plan.max_len, invert,
+              (uint8_t)(delim == 0xEE ? 0xED : 0xEE), blocks, out_kind, ent_kind);
 }
 
 // one raw search call with `max` hit slots; returns the hits
@@ -789,8 +431,8 @@ static uint64_t search_both(const Bytes &src, const Auto &set, uint32_t delim, b
 }
 static void grep_both(const Bytes &text, const Auto &set, uint32_t delim, uint32_t invert, const std::vector<uint64_t> &blocks, int out_kind, int ent_kind)
 {
-    grep_call<false>(text, set, delim, invert, blocks, out_kind, ent_kind);
-    if (set.plan.table.size() <= BZR_LDS_ROWS) grep_call<true>(text, set, delim, invert, blocks, out_kind, ent_kind);
+    grep_auto<false>(text, set, delim, invert, blocks, out_kind, ent_kind);
+    if (set.plan.table.size() <= BZR_LDS_ROWS) grep_auto<true>(text, set, delim, invert, blocks, out_kind, ent_kind);
 }
 
 static void plant(Bytes &text, uint64_t at, const Bytes &p)
@@ -902,17 +544,21 @@ static void part_windows(uint64_t cases)
         for (uint64_t i = 0; i < start; i++) rec_start += truth[i] == '\n';
         BzmSetWalk walk;
         walk.begin(set.plan.max_len, BZF_FRONT, max, lo, hi, start, records ? rec_start : 0);
+        ZeroLookTwin zero; // (no assertion is the zero case)
+        zero.begin(set.plan.max_len, BZF_FRONT, max, lo, hi, start, records ? rec_start : 0);
         std::vector<BzmHit> got((size_t)std::min<uint64_t>(max, want.size() + 8), BzmHit{~0ull, ~0ull, ~0u, ~0u});
         Bytes carry;
         uint64_t at_out = start;
-        auto run = [&](const uint8_t *d, const BzfWindow &w, uint64_t lim, uint64_t bytes) {
+        auto run = [&](const uint8_t *d, const BzfWindow &w, uint64_t lim, uint64_t bytes, bool is_last) {
             CHECK(w.s_lo <= w.s_hi && w.s_hi <= lim && lim <= w.n, "window: starts [%llu, %llu) lim %llu n %llu", (ull)w.s_lo, (ull)w.s_hi, (ull)lim, (ull)w.n);
+            zero.window(walk, bytes, is_last, w, lim);
             std::vector<BzmHit> out;
             uint64_t hits, delims;
             if (lds) search_run(d, w, set.matcher<true>('\n', lim), records, walk, out, &hits, &delims);
             else search_run(d, w, set.matcher<false>('\n', lim), records, walk, out, &hits, &delims);
             for (size_t i = 0; i < out.size(); i++) got.at((size_t)walk.rank + i) = out[i];
-            walk.advance(bytes, hits, delims);
+            walk.advance_set(bytes, hits, delims, is_last);
+            zero.advance(walk, bytes, hits, delims, is_last);
             windows++;
         };
         for (size_t at = first; at < last;) {
@@ -922,15 +568,15 @@ static void part_windows(uint64_t cases)
             if (at == first) wins.clear();
             wins.push_back(bytes);
             const Text staging(BZF_FRONT + bytes);
-            memset(staging.p, 0xCC, BZF_FRONT);
+            memset(staging.p, poison_front, BZF_FRONT);
             CHECK(carry.size() == walk.carry, "the carry");
             if (!carry.empty()) memcpy(staging.p + BZF_FRONT - carry.size(), carry.data(), carry.size());
             memcpy(staging.p + BZF_FRONT, &truth[at_out], (size_t)bytes);
             uint64_t lim = 0;
             const BzfWindow w = walk.window_set(bytes, false, &lim);
-            const uint64_t keep = walk.carry_after(bytes);
+            const uint64_t keep = walk.carry_after_set(bytes);
             const Bytes next(staging.p + w.n - keep, staging.p + w.n);
-            run(staging.p, w, lim, bytes);
+            run(staging.p, w, lim, bytes, false);
             carry = next;
             at_out += bytes, at += nbw;
         }
@@ -939,14 +585,14 @@ static void part_windows(uint64_t cases)
             walk.front = walk.carry;
             uint64_t lim = 0;
             const BzfWindow w = walk.window_set(0, true, &lim);
-            run(held.p, w, lim, 0);
+            run(held.p, w, lim, 0, true);
             finished++;
         }
         same_hits(got, want, walk.rank, max, "windows", c);
         // the grep over the same windows (it takes the whole text of the blocks it is given)
         const Bytes part(truth.begin() + start, truth.begin() + stop);
-        if (lds) grep_call<true>(part, set, '\n', (uint32_t)below(2), wins, (int)below(5), (int)below(5));
-        else grep_call<false>(part, set, '\n', (uint32_t)below(2), wins, (int)below(5), (int)below(5));
+        if (lds) grep_auto<true>(part, set, '\n', (uint32_t)below(2), wins, (int)below(5), (int)below(5));
+        else grep_auto<false>(part, set, '\n', (uint32_t)below(2), wins, (int)below(5), (int)below(5));
     }
     CHECK(finished > cases / 4 && cut > 0, "the cases reach the edges: %llu finishing windows, %llu long matches cut by the range", (ull)finished, (ull)cut);
     printf("windows: %llu cases held, %llu windows, %llu finishing ones, %llu cut by the range\n", (ull)cases, (ull)windows, (ull)finished, (ull)cut);

@@ -1,6 +1,6 @@
 // search_host.cpp -- the search without a device, built with g++ -fsanitize=address,undefined.
 // (a) What one thread of search_tiles does, run thread by thread and tile by tile in the kernel's layout: the tile front that the
-//     kernel itself compiles (banzai_amd/csrc/search_core.h: bzf_stage, bzf_match16, over the model LDS of tile_host.h), the
+//     kernel itself compiles (banzai_amd/csrc/search_core.h: bzf_stage, bzf_match16, through BzfOne over the model LDS of scan_host.h), the
 //     delimiter bits and the count of delimiters in front of a position, the counting pass, the scan of the tiles, the emitting
 //     pass -- against a naive scan.  Every text is allocated as the kernel's contract states (16-byte aligned, up to the aligned
 //     word that holds its last byte) and every other buffer has its exact size, so a read or a store outside is a sanitizer report.
@@ -8,37 +8,11 @@
 //     window into a staging buffer that is allocated anew for every window, against brute force per output byte.
 //
 //   search_host <seed> <cases>     exit status 0: everything held
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <vector>
-
+#define HOST_NAME "search_host"
 #include "../../include/bzhip.h"
-#include "../../banzai_amd/csrc/search_plan.h"
-#include "tile_host.h"
+#include "scan_host.h"
 
-static uint64_t rng_state;
-static uint64_t rnd()
-{
-    rng_state ^= rng_state << 13;
-    rng_state ^= rng_state >> 7;
-    rng_state ^= rng_state << 17;
-    return rng_state;
-}
-static uint64_t below(uint64_t n) { return n ? rnd() % n : 0; }
-
-#define CHECK(cond, ...)                                  \
-    do {                                                  \
-        if (!(cond)) {                                    \
-            fprintf(stderr, "search_host: %s: ", #cond);  \
-            fprintf(stderr, __VA_ARGS__);                 \
-            fprintf(stderr, "\n");                        \
-            exit(1);                                      \
-        }                                                 \
-    } while (0)
+static_assert(sizeof(bzh_hit) == sizeof(BzfHit) && sizeof(BzfHit) == 16, "a hit is two words");
 
 struct Pattern {
     uint8_t pat[BZF_MAX_PATTERN];
@@ -46,97 +20,22 @@ struct Pattern {
     bool records;
 };
 
-struct Tile : TileModel { // one workgroup's LDS and what its threads found
-    uint32_t hm[BZF_THREADS], dm[BZF_THREADS];
-};
-
-// the front of search_tiles, and the two masks of every thread
-static void tile_tests(const uint8_t *d, const BzfWindow &w, const Pattern &p, uint64_t t, Tile &tl)
+// search_window_run with the single pattern as the matcher: scan_host.h's model with BzfOne
+static void window_run(const uint8_t *d, const BzfWindow &w, const Pattern &p, const BzfWalk &walk, std::vector<BzfHit> &out, uint64_t *hits, uint64_t *delims)
 {
-    const BzfPattern bp = bzf_pattern(p.pat, p.plen, p.delim);
-    tl.stage(d, w.n, t, bp);
-    for (uint32_t tid = 0; tid < BZF_THREADS; tid++) {
-        const uint64_t p0 = t * BZF_TILE + tid * BZF_ITEMS;
-        const BzfVec &v = tl.own[tid];
-        tl.hm[tid] = tl.match(tid, bp, bzf_range_mask16(p0, w.s_lo, w.s_hi));
-        tl.dm[tid] = p.records ? bzf_eq_mask16(v.x, v.y, v.z, v.w, p.delim) & bzf_range_mask16(p0, w.d_lo, w.n) : 0u;
-    }
-}
-
-// search_window_run: both passes and the scan between them.  out: the window's hit slots, exactly w.emit of them.
-static void window_run(const uint8_t *d, BzfWindow w, const Pattern &p, const BzfWalk &walk, std::vector<bzh_hit> &out, uint64_t *hits,
-                       uint64_t *delims)
-{
-    const uint64_t tiles = (w.n + BZF_TILE - 1) / BZF_TILE;
-    std::vector<uint32_t> thits(tiles), tdel(tiles);
-    std::vector<uint64_t> hbase(tiles), dbase(tiles);
-    Tile tl;
-    for (uint64_t t = 0; t < tiles; t++) {
-        tile_tests(d, w, p, t, tl);
-        for (uint32_t tid = 0; tid < BZF_THREADS; tid++) {
-            thits[t] += (uint32_t)__builtin_popcount(tl.hm[tid]);
-            tdel[t] += (uint32_t)__builtin_popcount(tl.dm[tid]);
-        }
-    }
-    uint64_t rh = 0, rd = 0;
-    for (uint64_t t = 0; t < tiles; t++) hbase[t] = rh, dbase[t] = rd, rh += thits[t], rd += tdel[t];
-    *hits = rh, *delims = rd;
-    w.emit = walk.emit(rh);
-    out.assign((size_t)w.emit, bzh_hit{~0ull, ~0ull});
-    out.shrink_to_fit();
-    for (uint64_t t = 0; t < tiles && w.emit; t++) {
-        if (thits[t] == 0 || hbase[t] >= w.emit) continue;
-        tile_tests(d, w, p, t, tl);
-        uint64_t rank = hbase[t], dsum = 0;
-        for (uint32_t tid = 0; tid < BZF_THREADS; tid++) {
-            const uint64_t p0 = t * BZF_TILE + tid * BZF_ITEMS;
-            for (uint32_t k = 0; k < 16; k++) {
-                if (!(tl.hm[tid] >> k & 1u)) continue;
-                if (rank < w.emit) {
-                    const uint64_t pos = p0 + k;
-                    uint64_t rec = 0;
-                    if (p.records) {
-                        if (pos >= w.d_lo) {
-                            rec = w.rec_base + dbase[t] + dsum + bzf_delims_before(tl.dm[tid], k);
-                        } else {
-                            const uint32_t gap = (uint32_t)std::min<uint64_t>(w.d_lo - pos, BZF_MAX_PATTERN - 1);
-                            uint32_t c = 0;
-                            for (uint32_t j = 0; j < gap; j++) c += tl.tile[tid * BZF_ITEMS + k + j] == p.delim;
-                            rec = w.rec_base - c;
-                        }
-                    }
-                    out.at((size_t)rank) = bzh_hit{w.off_base + pos, rec};
-                }
-                rank++;
-            }
-            dsum += (uint32_t)__builtin_popcount(tl.dm[tid]);
-        }
-    }
+    search_run(d, w, BzfOne{{}, bzf_pattern(p.pat, p.plen, p.delim)}, p.records, walk, out, hits, delims);
 }
 
 // the truth: every start in [lo, hi - plen] of text[0, n), its record the delimiters in front of it
-static std::vector<bzh_hit> naive(const uint8_t *text, uint64_t n, const Pattern &p, uint64_t lo, uint64_t hi)
+static std::vector<BzfHit> naive(const uint8_t *text, uint64_t n, const Pattern &p, uint64_t lo, uint64_t hi)
 {
-    std::vector<bzh_hit> v;
+    std::vector<BzfHit> v;
     std::vector<uint64_t> cum(n + 1, 0);
     for (uint64_t i = 0; i < n; i++) cum[i + 1] = cum[i] + (text[i] == p.delim);
     hi = std::min(hi, n);
     for (uint64_t o = lo; o + p.plen <= hi; o++)
-        if (memcmp(text + o, p.pat, p.plen) == 0) v.push_back(bzh_hit{o, p.records ? cum[o] : 0});
+        if (memcmp(text + o, p.pat, p.plen) == 0) v.push_back(BzfHit{o, p.records ? cum[o] : 0});
     return v;
-}
-
-static void same(const std::vector<bzh_hit> &got, const std::vector<bzh_hit> &want, uint64_t nhits, uint64_t max, const char *what, uint64_t a,
-                 uint64_t b)
-{
-    CHECK(nhits == want.size(), "%s (%llu, %llu): %llu hits, the truth has %zu", what, (unsigned long long)a, (unsigned long long)b,
-          (unsigned long long)nhits, want.size());
-    const size_t m = (size_t)std::min<uint64_t>(max, want.size());
-    CHECK(got.size() >= m, "%s: %zu hits stored of %zu", what, got.size(), m);
-    for (size_t i = 0; i < m; i++)
-        CHECK(got[i].off == want[i].off && got[i].record == want[i].record, "%s (%llu, %llu): hit %zu is (%llu, %llu), the truth (%llu, %llu)", what,
-              (unsigned long long)a, (unsigned long long)b, i, (unsigned long long)got[i].off, (unsigned long long)got[i].record,
-              (unsigned long long)want[i].off, (unsigned long long)want[i].record);
 }
 
 // ---- (a) raw bytes: one window, no staging --------------------------------------------------------------------------------
@@ -146,11 +45,11 @@ static uint64_t raw_case(const uint8_t *src, uint64_t n, const Pattern &p, uint6
     const uint8_t *d = text.p;
     BzfWalk walk;
     walk.begin(p.plen, 0, max, 0, n, 0, 0);
-    std::vector<bzh_hit> out;
+    std::vector<BzfHit> out;
     uint64_t hits, delims;
     window_run(d, walk.window(n), p, walk, out, &hits, &delims);
-    const std::vector<bzh_hit> want = naive(d, n, p, 0, n);
-    same(out, want, hits, max, "raw", n, p.plen);
+    const std::vector<BzfHit> want = naive(d, n, p, 0, n);
+    same_hits(out, want, hits, max, "raw", n);
     CHECK(!p.records || delims == (uint64_t)std::count(d, d + n, (uint8_t)p.delim), "raw (%llu): %llu delimiters", (unsigned long long)n,
           (unsigned long long)delims);
     return hits;
@@ -231,7 +130,7 @@ static void part_b(uint64_t cases)
         for (size_t k = 0; k < last; k++) (k < first ? start : stop) += idx[k].out_len;
         stop += start;
         const uint64_t lo = below(2) ? start : start + below(stop - start), hi = below(2) ? stop : lo + below(stop - lo + 1);
-        const std::vector<bzh_hit> want = naive(truth.data(), total, p, lo, hi);
+        const std::vector<BzfHit> want = naive(truth.data(), total, p, lo, hi);
         const uint64_t maxes[] = {~0ull, want.size(), want.size() ? want.size() - 1 : 0, 0, below(want.size() + 2)};
         const uint64_t max = maxes[below(5)];
         const uint64_t room = below(3) ? 1 + below(600) : 1 + below(20000);
@@ -240,7 +139,7 @@ static void part_b(uint64_t cases)
         for (uint64_t i = 0; i < start; i++) rec_start += truth[i] == '\n';
         BzfWalk walk;
         walk.begin(plen, BZF_FRONT, max, lo, hi, start, p.records ? rec_start : 0);
-        std::vector<bzh_hit> got((size_t)std::min<uint64_t>(max, want.size() + 8), bzh_hit{~0ull, ~0ull});
+        std::vector<BzfHit> got((size_t)std::min<uint64_t>(max, want.size() + 8), BzfHit{~0ull, ~0ull});
         uint8_t carry[BZF_MAX_PATTERN];
         uint64_t at_out = start;
         for (size_t at = first; at < last;) {
@@ -250,7 +149,7 @@ static void part_b(uint64_t cases)
             // SearchSink::room: a staging buffer of exactly these bytes, the carry in front of the window
             const Text staging(BZF_FRONT + bytes);
             uint8_t *stage = staging.p;
-            memset(stage, 0xCC, BZF_FRONT);
+            memset(stage, poison_front, BZF_FRONT);
             if (walk.carry) memcpy(stage + BZF_FRONT - walk.carry, carry, (size_t)walk.carry);
             memcpy(stage + BZF_FRONT, &truth[at_out], (size_t)bytes);
             // SearchSink::window
@@ -261,7 +160,7 @@ static void part_b(uint64_t cases)
             CHECK(keep < plen && keep <= walk.carry + bytes, "carry");
             uint8_t next[BZF_MAX_PATTERN];
             memcpy(next, stage + w.n - keep, (size_t)keep);
-            std::vector<bzh_hit> out;
+            std::vector<BzfHit> out;
             uint64_t hits, delims;
             window_run(stage, w, p, walk, out, &hits, &delims);
             for (size_t i = 0; i < out.size(); i++) got.at((size_t)walk.rank + i) = out[i];
@@ -270,7 +169,7 @@ static void part_b(uint64_t cases)
             CHECK(walk.carry == keep, "carry kept");
             at_out += bytes, at += B, windows++, carried += keep != 0;
         }
-        same(got, want, walk.rank, max, "windows", c, plen);
+        same_hits(got, want, walk.rank, max, "windows", c);
     }
     printf("windows: %llu cases held, %llu windows, %llu carries\n", (unsigned long long)cases, (unsigned long long)windows,
            (unsigned long long)carried);

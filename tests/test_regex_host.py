@@ -1,7 +1,7 @@
 """CPU: regular expressions for search and grep without a device, as a stand-alone program with AddressSanitizer and UBSan
 (tests/decode_host/regex_host.cpp; nothing is loaded into Python under a sanitizer).  (a) The compile of
 banzai_amd/csrc/regex_plan.h against a naive matcher over the harness's own expression trees.  (b) The matchers of
-banzai_amd/csrc/regex_core.h, BzrMatcher<true> and BzrMatcher<false>, thread by thread and tile by tile in the kernels' layout,
+banzai_amd/csrc/regex_core.h, BzrMatcher<true, false> and BzrMatcher<false, false>, thread by thread and tile by tile in the kernels' layout,
 both passes of search_tiles and of grep_tiles and the scans between them.  (c) The windows, the hold-back and the finishing window
 of search_plan.h's BzmSetWalk and grep_plan.h's BzgWalk with (b) as the device, against brute force per output byte.  And the
 program's `hits` mode against Python's `re` (tests/regex_truth.py)."""

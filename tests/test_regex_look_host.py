@@ -2,8 +2,8 @@
 UBSan (tests/decode_host/look_host.cpp; nothing is loaded into Python under a sanitizer).  (a) The compile of
 banzai_amd/csrc/regex_plan.h with assertions admitted against a naive matcher over the harness's own expression trees, the identity
 of the plan for lists without assertions, the refusals.  (b) The look-around matcher of banzai_amd/csrc/regex_core.h,
-BzrLookMatcher<true> and BzrLookMatcher<false>, thread by thread and tile by tile in the kernels' layout.  (c) The windows of
-search_plan.h's BzrLookWalk and grep_plan.h's BzgWalk with (b) as the device, against brute force per output byte.  And the
+BzrMatcher<true, true> and BzrMatcher<false, true>, thread by thread and tile by tile in the kernels' layout.  (c) The windows of
+search_plan.h's BzmSetWalk and grep_plan.h's BzgWalk with (b) as the device, against brute force per output byte.  And the
 program's `hits` mode against Python's `re` under re.MULTILINE (tests/regex_look_truth.py)."""
 import os
 import random
