@@ -1120,17 +1120,30 @@ def search_range(data, index, pattern, offset=0, length=None, limit=None, device
     return _search_range(index, lambda lo, hi: view[lo:hi], pattern, offset, length, limit, device)
 
 
-def _grep(data, pattern, delim, invert, index, device, count_only):
+def _context_arg(before, after, context, who="grep"):
+    """before / after / context as grep's -B -A -C -> (before, after), each a uint32"""
+    if context is not None:
+        if before or after:
+            raise ValueError(f"{who}: context= stands for before= and after=; give it alone")
+        before = after = context
+    for name, v in (("before", before), ("after", after)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{who}: {name} must be an integer in [0, 2^32)")
+    return int(before), int(after)
+
+
+def _grep(data, pattern, delim, invert, index, device, count_only, before=0, after=0):
     view = _bytes_view(data, "grep")
     pattern, d = _pattern_arg(pattern), _delim_arg(delim)
     ctx = _ctx(9, device)
+    kw = {"before": before, "after": after} if before or after else {}
     if index is None:
-        return ctx.grep(view, pattern, d, bool(invert), count_only)
+        return ctx.grep(view, pattern, d, bool(invert), count_only, **kw)
     index = _index_arg(index)
-    return ctx.grep_index(view, index.entries, pattern, _points_arg(index), d, bool(invert), count_only)
+    return ctx.grep_index(view, index.entries, pattern, _points_arg(index), d, bool(invert), count_only, **kw)
 
 
-def grep(data, pattern, delim=b"\n", invert=False, index=None, device=0):
+def grep(data, pattern, delim=b"\n", invert=False, index=None, device=0, before=0, after=0, context=None):
     """The records (lines) of the DECODED bytes of `data` (bytes-like .bz2 stream(s)) in which a match of the byte string
     `pattern` (1..256 bytes) starts, or with `invert` those in which none does -> (bytes, entries): the selected records back to
     back, each with its delimiter, and a structured array with fields `record` (the number read_records takes), `off` and `len`
@@ -1138,8 +1151,12 @@ def grep(data, pattern, delim=b"\n", invert=False, index=None, device=0):
     they cross to the host, and every block is decoded once.  Everything decompress verifies is verified (bzh_grep).  With
     `index` (a BlockIndex or SyncIndex of `data`) the blocks go through the indexed front, in parallel segments where the index
     has sync points, and are checked against their entries (bzh_grep_index).  `pattern` may be a PatternSet: the records in
-    which a match of any of its patterns starts, in one pass (grep -F -f FILE, -e A -e B, -i)."""
-    return _grep(data, pattern, delim, invert, index, device, False)
+    which a match of any of its patterns starts, in one pass (grep -F -f FILE, -e A -e B, -i).
+    CONTEXT (grep -B -A -C): with `before` / `after` records of context, or `context` for both, every record within `before` in
+    front of a selected record or `after` behind one comes too, once and in order, chosen on the device in the same pass
+    (bzh_grep_set_context).  The entries then carry a bool field `context`: True for a record that is there only as context."""
+    before, after = _context_arg(before, after, context)
+    return _grep(data, pattern, delim, invert, index, device, False, before, after)
 
 
 def grep_count(data, pattern, delim=b"\n", invert=False, index=None, device=0):
@@ -1284,14 +1301,22 @@ class IndexedReader(io.RawIOBase):
         return _search_range(self.records if self.records is not None else self.index, self._fetch_comp, pattern, start, length, limit,
                              self._device)
 
-    def grep(self, pattern, limit=None):
+    def grep(self, pattern, limit=None, before=0, after=0):
         """The records that hold a hit of `pattern` -> a list of (record number, bytes), ascending and unique; a match that spans
         a delimiter belongs to the record of its first byte.  `limit` caps the hits looked at.  The reader must have been given
-        a RecordIndex; the records are fetched with one readv_records."""
+        a RecordIndex; the records are fetched with one readv_records.  `before` / `after`: the records that far in front of and
+        behind a hit record come too, clipped to the table."""
         if self.records is None:
             raise ValueError("grep needs a RecordIndex (build_record_index) as the reader's index")
+        before, after = _context_arg(before, after, None, "IndexedReader.grep")
         hits, _ = self.search(pattern, limit=limit)
         recs = [int(r) for r in np.unique(hits["record"])]
+        if recs and (before or after):
+            last, wide = self.records.nrecords - 1, []
+            for r in recs:  # ascending: the runs [r - before, r + after] merge into a sorted list without duplicates
+                lo = max(r - before, wide[-1] + 1 if wide else 0)
+                wide.extend(range(lo, min(r + after, last) + 1))
+            recs = wide
         return list(zip(recs, self.readv_records([(r, 1) for r in recs]))) if recs else []
 
     def read_records(self, first, count):

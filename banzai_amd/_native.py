@@ -168,6 +168,8 @@ GREP_ENTRY_DTYPE = np.dtype([("record", "<u8"), ("off", "<u8"), ("len", "<u8"), 
 assert GREP_ENTRY_DTYPE.itemsize == ctypes.sizeof(GrepEntry) == 32
 grepp = ctypes.POINTER(GrepEntry)
 GREP_INVERT = 1
+GREP_LEN_CONTEXT = 1 << 63  # BZH_GREP_LEN_CONTEXT: bit 63 of an entry's len marks a context record (bzh_grep_set_context)
+GREP_CONTEXT_ENTRY_DTYPE = np.dtype(GREP_ENTRY_DTYPE.descr + [("context", "?")])
 
 
 class PatsetInfo(ctypes.Structure):
@@ -221,6 +223,24 @@ class GrepStats(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class GrepContextStats(ctypes.Structure):
+    """bzh_grep_context_stats"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("matched", "context", "groups", "pending_peak")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def grep_context_rows(ent):
+    """entries as the C calls fill them -> GREP_CONTEXT_ENTRY_DTYPE: `len` the real length, `context` what bit 63 of it said"""
+    out = np.zeros(ent.size, dtype=GREP_CONTEXT_ENTRY_DTYPE)
+    for k in ("record", "off", "out_off"):
+        out[k] = ent[k]
+    out["len"] = ent["len"] & np.uint64(GREP_LEN_CONTEXT - 1)
+    out["context"] = (ent["len"] >> np.uint64(63)) != 0
+    return out
 
 
 class KStat(ctypes.Structure):
@@ -342,6 +362,8 @@ SIGNATURES = {
                                       ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint8, u8p, ctypes.c_size_t, grepp, ctypes.c_size_t,
                                       ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint64)]),
     "bzh_get_grep_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(GrepStats)]),
+    "bzh_grep_set_context": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]),
+    "bzh_get_grep_context_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(GrepContextStats)]),
     "bzh_patset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.c_size_t, ctypes.c_uint,
                                          ctypes.POINTER(ctypes.c_void_p)]),
     "bzh_patset_destroy": (None, [ctypes.c_void_p]),
@@ -1407,15 +1429,32 @@ class Context:
         fn, what, _ = Context._what(name, pattern)
         return fn, what, GREP_INVERT if invert else 0, d
 
-    def grep(self, data, pattern, delim=b"\n", invert=False, count_only=False):
+    def grep_set_context(self, before, after):
+        """bzh_grep_set_context: sticky, read by every grep call when it begins"""
+        self.check(lib().bzh_grep_set_context(self._h, before, after))
+
+    def _grep_with_context(self, before, after, run):
+        """run() between bzh_grep_set_context(before, after) and (0, 0): these wrappers leave no sticky setting behind.  With a
+        context the entries come as GREP_CONTEXT_ENTRY_DTYPE."""
+        if not (before or after):
+            return run()
+        self.grep_set_context(before, after)
+        try:
+            got = run()
+        finally:
+            self.grep_set_context(0, 0)
+        return (got[0], grep_context_rows(got[1])) if isinstance(got[1], np.ndarray) else got
+
+    def grep(self, data, pattern, delim=b"\n", invert=False, count_only=False, before=0, after=0):
         """bzh_grep: the records of the decoded bytes of `data` that hold `pattern` -> (bytes, entries), or (nrecs, out_total)"""
         a = np.frombuffer(data, dtype=np.uint8)
         n = a.size
         src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
         fn, what, fl, d = self._grep_what("bzh_grep", pattern, delim, invert)
-        return self._grep(lambda o, c, e, m, g, t: fn(self._h, ptr(src), n, *what, fl, d, o, c, e, m, g, t, None, None), count_only)
+        return self._grep_with_context(before, after, lambda: self._grep(
+            lambda o, c, e, m, g, t: fn(self._h, ptr(src), n, *what, fl, d, o, c, e, m, g, t, None, None), count_only))
 
-    def grep_index(self, comp, entries, pattern, points=None, delim=b"\n", invert=False, count_only=False):
+    def grep_index(self, comp, entries, pattern, points=None, delim=b"\n", invert=False, count_only=False, before=0, after=0):
         """bzh_grep_index over the whole indexed input `comp` -> as grep"""
         e, p = _entries(entries)
         q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
@@ -1423,7 +1462,8 @@ class Context:
         n = a.size
         src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
         fn, what, fl, d = self._grep_what("bzh_grep_index", pattern, delim, invert)
-        return self._grep(lambda o, c, en, m, g, t: fn(self._h, ptr(src), n, p, e.size, pp, q.size, *what, fl, d, o, c, en, m, g, t), count_only)
+        return self._grep_with_context(before, after, lambda: self._grep(
+            lambda o, c, en, m, g, t: fn(self._h, ptr(src), n, p, e.size, pp, q.size, *what, fl, d, o, c, en, m, g, t), count_only))
 
     def _grep_device(self, call, room):
         """the device variants: the bytes stay in the caller's device buffer -> (status, nrecs, out_total, entries)"""
@@ -1456,6 +1496,11 @@ class Context:
     def grep_stats(self):
         s = GrepStats()
         self.check(lib().bzh_get_grep_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
+
+    def grep_context_stats(self):
+        s = GrepContextStats()
+        self.check(lib().bzh_get_grep_context_stats(self._h, ctypes.byref(s)))
         return s.as_dict()
 
     def decode_ranges_stats(self):

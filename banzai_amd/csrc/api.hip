@@ -1878,9 +1878,11 @@ static SearchSink search_sink(const ScanWhat &q, unsigned flags, uint8_t delim, 
 {
     return q.is_set ? SearchSink(q.set, flags, delim, (bzh_set_hit *)hits, max) : SearchSink(q.pat, q.plen, flags, delim, (bzh_hit *)hits, max);
 }
-static GrepSink grep_sink(const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap, bzh_grep_entry *ent, size_t max)
+static GrepSink grep_sink(const bzh_ctx *ctx, const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap, bzh_grep_entry *ent, size_t max)
 {
-    return q.is_set ? GrepSink(q.set, flags, delim, d_out, cap, ent, max) : GrepSink(q.pat, q.plen, flags, delim, d_out, cap, ent, max);
+    GrepSink g = q.is_set ? GrepSink(q.set, flags, delim, d_out, cap, ent, max) : GrepSink(q.pat, q.plen, flags, delim, d_out, cap, ent, max);
+    g.set_context(ctx->grep_before, ctx->grep_after);
+    return g;
 }
 
 // the checks every search makes first; a sink is made of arguments that have passed them
@@ -2138,6 +2140,7 @@ static int grep_begin(bzh_ctx *ctx, const ScanWhat &q, unsigned flags, void *d_o
         return BZH_E_ARG;
     }
     memset(&ctx->gstats, 0, sizeof ctx->gstats);
+    memset(&ctx->gcstats, 0, sizeof ctx->gcstats);
     return BZH_OK;
 }
 
@@ -2150,12 +2153,12 @@ static int grep_end(bzh_ctx *ctx, GrepSink &g, const DecodeCall &call, int rc, s
     rc = decode_call_end(ctx, call, rc);
     HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
     if (rc != BZH_OK) return rc;
-    if (tail_entry) memcpy(&g.ent[g.walk.sel - 1], &g.tail_ent, sizeof g.tail_ent);
-    *nrecs = (size_t)g.walk.sel;
-    *out_total = g.walk.out_bytes;
-    if (g.walk.overflow()) {
-        bzh_set_error(ctx, "grep: %llu records of %llu bytes, room for %llu and %llu", (unsigned long long)g.walk.sel,
-                      (unsigned long long)g.walk.out_bytes, (unsigned long long)g.walk.max, (unsigned long long)g.walk.cap);
+    if (tail_entry) memcpy(&g.ent[g.sel() - 1], &g.tail_ent, sizeof g.tail_ent);
+    *nrecs = (size_t)g.sel();
+    *out_total = g.out_bytes();
+    if (g.overflow()) {
+        bzh_set_error(ctx, "grep: %llu records of %llu bytes, room for %llu and %llu", (unsigned long long)g.sel(),
+                      (unsigned long long)g.out_bytes(), (unsigned long long)g.walk.max, (unsigned long long)g.walk.cap);
         return BZH_E_CAP;
     }
     return BZH_OK;
@@ -2168,7 +2171,7 @@ static int grep_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const Scan
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_raw && n)) return BZH_E_ARG;
     BZH_TRY(grep_begin(ctx, q, flags, d_out, cap, ent, max, nrecs, out_total));
-    GrepSink g = grep_sink(q, flags, delim, d_out, cap, ent, max);
+    GrepSink g = grep_sink(ctx, q, flags, delim, d_out, cap, ent, max);
     if ((uintptr_t)d_raw & 15u) {
         bzh_set_error(ctx, "grep: the buffer is not 16-byte aligned");
         return BZH_E_ARG;
@@ -2187,7 +2190,7 @@ static int grep_device(bzh_ctx *ctx, const void *d_in, size_t n, const ScanWhat 
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_in && n)) return BZH_E_ARG;
     BZH_TRY(grep_begin(ctx, q, flags, d_out, cap, ent, max, nrecs, out_total));
-    GrepSink g = grep_sink(q, flags, delim, d_out, cap, ent, max);
+    GrepSink g = grep_sink(ctx, q, flags, delim, d_out, cap, ent, max);
     DecodeCall call;
     BZH_TRY(decode_call_begin(ctx, n, call));
     if (decoded_total) *decoded_total = 0;
@@ -2226,7 +2229,7 @@ static int grep_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_in && n) || (!idx && count) || (!pts && npts)) return BZH_E_ARG;
     BZH_TRY(grep_begin(ctx, q, flags, d_out, cap, ent, max, nrecs, out_total));
-    GrepSink g = grep_sink(q, flags, delim, d_out, cap, ent, max);
+    GrepSink g = grep_sink(ctx, q, flags, delim, d_out, cap, ent, max);
     DecodeCall call;
     BZH_TRY(decode_call_begin(ctx, n, call));
     BZH_TRY(search_range_args(ctx, idx, count, pts, npts, nullptr, 0));
@@ -2316,6 +2319,24 @@ extern "C" int bzh_get_grep_stats(const bzh_ctx *ctx, bzh_grep_stats *out)
     return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
     if (!ctx || !out) return BZH_E_ARG;
     *out = ctx->gstats;
+    return BZH_OK;
+    });
+}
+
+extern "C" int bzh_grep_set_context(bzh_ctx *ctx, uint32_t before, uint32_t after)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (!ctx) return BZH_E_ARG;
+    ctx->grep_before = before, ctx->grep_after = after;
+    return BZH_OK;
+    });
+}
+
+extern "C" int bzh_get_grep_context_stats(const bzh_ctx *ctx, bzh_grep_context_stats *out)
+{
+    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
+    if (!ctx || !out) return BZH_E_ARG;
+    *out = ctx->gcstats;
     return BZH_OK;
     });
 }

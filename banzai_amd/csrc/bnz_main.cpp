@@ -66,7 +66,12 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "     --grep <string>        write the lines of the decoded data that hold <string> (1 to 256 bytes) to standard\n"
             "                            out as they are, selected on the GPU; the input is kept\n"
             "     --invert               with --grep: the lines that do not hold <string>\n"
-            "     --line-number          with --grep: prefix each line with its number, from 1, and ':'\n"
+            "     --line-number          with --grep: prefix each line with its number, from 1, and ':' ('-' on a context line)\n"
+            "  -A --after-context <n>    with --grep: also write the <n> lines behind every selected line,\n"
+            "  -B --before-context <n>   ... the <n> lines in front of it,\n"
+            "  -C --context <n>          ... or both; every line once and in order, chosen on the device in the same pass,\n"
+            "                            a line '--' between two groups of lines that are not adjacent; --count still\n"
+            "                            prints the selected lines alone\n"
             "     --hex                  with --search or --grep: <string> is given as hex digits\n"
             "     --count                with --search: print the number of occurrences alone; with --grep: of lines\n"
             "     -e <string>            with --search or --grep, in place of their <string> or beside it, any number of\n"
@@ -134,7 +139,7 @@ const char *VERSION = "version alpha 0.3.1-hip";
 int main(int argc, char **argv)
 {
     if (argc <= 1) usage(false);
-    enum { ANY, NOARGS, OUTPATH, IDXPATH, MKIDXPATH, INTERVAL, RANGE, SEARCH, GREP, PATTERN, PATFILE } expect = ANY;
+    enum { ANY, NOARGS, OUTPATH, IDXPATH, MKIDXPATH, INTERVAL, RANGE, SEARCH, GREP, PATTERN, PATFILE, CTX_AFTER, CTX_BEFORE, CTX_BOTH } expect = ANY;
     std::string in_path, out_path, index_path, mkindex_path, needle;
     std::vector<std::string> pats; // the strings of a set, in the order given (-e: hex with --hex; --patterns: as they stand)
     std::vector<bool> pat_hex;
@@ -159,6 +164,8 @@ int main(int argc, char **argv)
     };
     bool searching = false, needle_hex = false, count_only = false;
     bool grepping = false, invert = false, line_number = false; // (--grep is a --search that writes lines: `searching` holds for both)
+    bool context_given = false; // -A, -B, -C: lines of context round every selected line
+    uint32_t ctx_before = 0, ctx_after = 0;
     bool interval_given = false;
     uint32_t interval = 256;
     std::vector<bzh_range> ranges;
@@ -208,6 +215,13 @@ int main(int argc, char **argv)
             if (!number(a, &v) || v > 32767) die(ERR_ARGS, "Argument '--interval' requires a number of groups, 0 to 32767");
             interval = (uint32_t)v;
             interval_given = true;
+            expect = ANY;
+        } else if (expect == CTX_AFTER || expect == CTX_BEFORE || expect == CTX_BOTH) {
+            uint64_t v = 0;
+            if (!number(a, &v) || v > UINT32_MAX) die(ERR_ARGS, "Arguments '-A', '-B' and '-C' require a number of lines, 0 to 4294967295");
+            if (expect != CTX_BEFORE) ctx_after = (uint32_t)v;
+            if (expect != CTX_AFTER) ctx_before = (uint32_t)v;
+            context_given = true;
             expect = ANY;
         } else if (expect == RANGE) {
             const size_t colon = a.find(':');
@@ -268,6 +282,9 @@ int main(int argc, char **argv)
             else if (a == "--regex") regex = true;
             else if (a == "--word-regexp") word_re = true;
             else if (a == "--line-regexp") line_re = true;
+            else if (a == "--after-context") expect = CTX_AFTER;
+            else if (a == "--before-context") expect = CTX_BEFORE;
+            else if (a == "--context") expect = CTX_BOTH;
             else if (a == "--stdout") set_output("", true);
             else if (a == "--") expect = NOARGS;
             else die(ERR_ARGS, "Unrecognised argument " + a);
@@ -282,6 +299,12 @@ int main(int argc, char **argv)
                 word_re = true;
             } else if (a == "-x") {
                 line_re = true;
+            } else if (a == "-A") {
+                expect = CTX_AFTER;
+            } else if (a == "-B") {
+                expect = CTX_BEFORE;
+            } else if (a == "-C") {
+                expect = CTX_BOTH;
             } else {
                 for (size_t c = 1; c < a.size(); c++) {
                     const char f = a[c];
@@ -304,6 +327,7 @@ int main(int argc, char **argv)
     if (expect == SEARCH) die(ERR_ARGS, "Argument '--search' requires a string");
     if (expect == GREP) die(ERR_ARGS, "Argument '--grep' requires a string");
     if (expect == PATTERN) die(ERR_ARGS, "Argument '-e' requires a string");
+    if (expect == CTX_AFTER || expect == CTX_BEFORE || expect == CTX_BOTH) die(ERR_ARGS, "Arguments '-A', '-B' and '-C' require a number of lines, 0 to 4294967295");
     if (expect == PATFILE) die(ERR_ARGS, "Argument '--patterns' requires a file path");
     if (word_re && line_re) die(ERR_ARGS, "'-w' and '-x' exclude each other");
     if ((word_re || line_re) && !searching) die(ERR_ARGS, "'-w' and '-x' go with '--search' or '--grep'");
@@ -314,10 +338,11 @@ int main(int argc, char **argv)
     if (!have_in) die(ERR_ARGS, "An input must be specified");
     if ((needle_hex || count_only) && !searching) die(ERR_ARGS, "'--hex' and '--count' go with '--search' or '--grep'");
     if ((invert || line_number) && !grepping) die(ERR_ARGS, "'--invert' and '--line-number' go with '--grep'");
-    if (grepping && !ranges.empty()) die(ERR_ARGS, "'--grep' takes an input, '--hex', '--invert', '--count', '--line-number' and '--index', nothing else");
+    if (context_given && !grepping) die(ERR_ARGS, "'-A', '-B' and '-C' go with '--grep'");
+    if (grepping && !ranges.empty()) die(ERR_ARGS, "'--grep' takes an input, '--hex', '--invert', '--count', '--line-number', '-A', '-B', '-C' and '--index', nothing else");
     if (searching) {
         if (decompress || recover || dstream || have_out || !mkindex_path.empty() || level_given || interval_given || keep == 0)
-            die(ERR_ARGS, grepping ? "'--grep' takes an input, '--hex', '--invert', '--count', '--line-number' and '--index', nothing else"
+            die(ERR_ARGS, grepping ? "'--grep' takes an input, '--hex', '--invert', '--count', '--line-number', '-A', '-B', '-C' and '--index', nothing else"
                                    : "'--search' takes an input, '--hex', '--count', '--index' and one '--range', nothing else");
         if (ranges.size() > 1 || (!ranges.empty() && index_path.empty())) die(ERR_ARGS, "'--search' takes one '--range', with the '--index' of the input");
         if (!index_path.empty() && in_stdin) die(ERR_ARGS, "'--search --index' reads parts of a file: standard in cannot be the input");
@@ -500,7 +525,9 @@ int main(int argc, char **argv)
         if (grepping) { // --grep: the selected lines come back compacted; a first try with a guess, a second with the exact rooms
             const unsigned gflags = invert ? BZH_GREP_INVERT : 0;
             std::vector<uint8_t> out(count_only ? 0 : (size_t)16 << 20);
-            std::vector<bzh_grep_entry> lines(count_only || !line_number ? 0 : (size_t)1 << 16);
+            const bool want_lines = !count_only && (line_number || context_given); // (with context: where the groups end)
+            std::vector<bzh_grep_entry> lines(want_lines ? (size_t)1 << 16 : 0);
+            if (context_given) bzh_grep_set_context(sctx, ctx_before, ctx_after);
             size_t nrecs = 0;
             uint64_t total = 0;
             for (int attempt = 0; attempt < 2; attempt++) {
@@ -519,8 +546,10 @@ int main(int argc, char **argv)
                                         out.size(), lp, lines.size(), &nrecs, &total);
                 if (rs != BZH_E_CAP || count_only || attempt) break;
                 out.resize((size_t)total);
-                if (line_number) lines.resize(nrecs);
+                if (want_lines) lines.resize(nrecs);
             }
+            bzh_grep_context_stats cstats{};
+            if (rs == BZH_OK) bzh_get_grep_context_stats(sctx, &cstats);
             if (rs != BZH_OK) {
                 const std::string msg = std::string("error during grep: ") + bzh_strerror(rs) + ": " + bzh_last_error(sctx);
                 bzh_patset_destroy(set);
@@ -531,11 +560,14 @@ int main(int argc, char **argv)
             bzh_destroy(sctx);
             bool ok = true;
             if (count_only) {
-                printf("%zu\n", nrecs);
-            } else if (line_number) {
+                printf("%llu\n", (unsigned long long)cstats.matched); // (without a context: nrecs)
+            } else if (want_lines) {
                 for (size_t k = 0; k < nrecs && ok; k++) {
-                    printf("%llu:", (unsigned long long)lines[k].record + 1);
-                    ok = fwrite(out.data() + lines[k].out_off, 1, (size_t)lines[k].len, stdout) == (size_t)lines[k].len;
+                    const bool is_context = (lines[k].len & BZH_GREP_LEN_CONTEXT) != 0;
+                    const size_t len = (size_t)(lines[k].len & ~BZH_GREP_LEN_CONTEXT);
+                    if (context_given && k && lines[k].record != lines[k - 1].record + 1) fputs("--\n", stdout);
+                    if (line_number) printf("%llu%c", (unsigned long long)lines[k].record + 1, is_context ? '-' : ':');
+                    ok = fwrite(out.data() + lines[k].out_off, 1, len, stdout) == len;
                 }
             } else if (total) {
                 ok = fwrite(out.data(), 1, (size_t)total, stdout) == (size_t)total;

@@ -71,6 +71,7 @@ using PinnedBuf = GrowBuf<true>;
 
 #include "search_plan.h" // the windows of a search and their carry: host-only text (tests/decode_host/search_host.cpp)
 #include "grep_plan.h" // the windows of a grep and their carry: host-only text (tests/decode_host/grep_host.cpp)
+#include "grep_ctx_plan.h" // ... with context records (tests/decode_host/grep_ctx_host.cpp)
 #include "batch.h" // geometry, Batch and its layout, the carver: host-only text (tests/workspace_host)
 
 // Kernel classes of the per-kernel roofline table (bzh_get_kernel_stats).  With profiling on, the launches of a
@@ -192,6 +193,8 @@ struct bzh_ctx {
     bzh_search_stats sstats{};      // of the last bzh_search* call
     DevBuf grep_tab, grep_ent;      // bzh_grep*: a window's tile tables, its entries
     bzh_grep_stats gstats{};        // of the last bzh_grep* call
+    bzh_grep_context_stats gcstats{};
+    uint32_t grep_before = 0, grep_after = 0; // bzh_grep_set_context
     struct DStream *dstrm = nullptr; // streaming decode (bzh_dstream_*, decode.hip): made by the first begin, freed by dstream_free
     size_t dstrm_window = 0, dstrm_staging = 0; // bzh_dstream_set_room: targets of the next begin (0: the defaults)
     // streaming encode (bzh_stream_*)
@@ -677,6 +680,8 @@ struct GrepSink final : WindowSink {
     uint8_t *d_out;      // device (null: not asked for)
     bzh_grep_entry *ent; // host (null: not asked for)
     BzgWalk walk;
+    BzcWalk cwalk;       // the walk instead of it when context records are asked for (grep_ctx_plan.h)
+    bool ctx_on = false;
     uint64_t at = 0;               // staging position of the window's first new byte
     const uint8_t *tail = nullptr; // device: where the carry lies
     BzgEntry tail_ent{};           // grep_finish: the open tail's entry
@@ -690,6 +695,16 @@ struct GrepSink final : WindowSink {
     {
         walk.begin(set->info.max_len + set->look.look_ahead, (flags & BZH_GREP_INVERT) != 0, d_out != nullptr, cap, ent != nullptr, max); // (the hold-back grows by the byte behind a match)
     }
+    // bzh_grep_set_context as the call found it: 0, 0 leaves the plain walk and its kernels
+    void set_context(uint32_t before, uint32_t after)
+    {
+        ctx_on = before || after;
+        if (ctx_on) cwalk.begin(walk.plen, walk.invert != 0, before, after, walk.want_out, walk.cap, walk.want_ent, walk.max);
+    }
+    uint64_t carry() const { return ctx_on ? cwalk.carry : walk.carry; }
+    uint64_t sel() const { return ctx_on ? cwalk.sel : walk.sel; }
+    uint64_t out_bytes() const { return ctx_on ? cwalk.out_bytes : walk.out_bytes; }
+    bool overflow() const { return ctx_on ? cwalk.overflow() : walk.overflow(); }
     void begin(uint64_t, uint64_t, uint64_t, uint64_t) override {}
     int room(bzh_ctx *ctx, uint64_t bytes, uint8_t **d_stage) override;
     int window(bzh_ctx *ctx, uint64_t bytes) override;

@@ -682,6 +682,28 @@ typedef struct {
 } bzh_grep_stats;
 BZH_API int bzh_get_grep_stats(const bzh_ctx *ctx, bzh_grep_stats *out);
 
+/* CONTEXT RECORDS: grep -B before -A after.  A setting of the context, like bzh_set_mode: it stays until it is set again, the
+ * default is 0, 0, and every bzh_grep* and bzh_grep_patset* call reads it when the call begins.  Any uint32_t value is valid.
+ * THE RULE.  A record is PRIMARY when the contract above selects it.  Record r is SELECTED when some primary p has
+ * p - before <= r <= p + after, clipped to the records that exist; the unterminated tail is a record like any other.  Every
+ * selected record comes out once, in ascending order; overlapping and touching contexts merge.  A selected record that is not
+ * primary is a CONTEXT RECORD: bit 63 of its entry's len is set (BZH_GREP_LEN_CONTEXT; never with 0, 0), the other bits are its
+ * length, and out_off stays the running sum of the lengths.  A GROUP is a maximal run of consecutive selected record numbers.
+ * Counts, rooms and bounds are the contract's, for the selected records, context records included.  With 0, 0 a call launches
+ * exactly the kernels it launches without this setting.  Between two windows the closed records that a later primary may
+ * still select -- at most `before` of them -- are carried with the open record; bzh_grep_stats.carry_peak counts their bytes. */
+#define BZH_GREP_LEN_CONTEXT (1ull << 63)
+BZH_API int bzh_grep_set_context(bzh_ctx *ctx, uint32_t before, uint32_t after);
+/* Counters of the last bzh_grep* call, beside bzh_grep_stats.  With context 0, 0: matched = selected and the rest 0 (groups are
+ * counted only when a context is set). */
+typedef struct {
+    uint64_t matched;      /* primary records: what grep -c prints */
+    uint64_t context;      /* context records */
+    uint64_t groups;       /* maximal runs of consecutive selected records */
+    uint64_t pending_peak; /* the most records carried undecided from one window to the next */
+} bzh_grep_context_stats;
+BZH_API int bzh_get_grep_context_stats(const bzh_ctx *ctx, bzh_grep_context_stats *out);
+
 /* ---- a set of patterns in one pass: grep -F -f FILE, -e A -e B, -i -------------------------------------------------------- */
 
 /* A pattern set is compiled on the host into a byte-class map and a trie without failure links, and lies on its device from
