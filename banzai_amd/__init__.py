@@ -45,7 +45,7 @@ import numpy as np
 
 from . import _native
 
-__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex", "RecordIndex", "build_record_index", "record_index_of", "decompress_records", "search", "search_range", "grep", "grep_count", "PatternSet", "Regex", "regex_check",
+__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex", "RecordIndex", "build_record_index", "record_index_of", "decompress_records", "search", "search_range", "grep", "grep_count", "matches", "matches_count", "PatternSet", "Regex", "regex_check",
            "IndexedReader", "build_sync_index", "SyncIndex", "encode_indexed", "encode_indexed_stream", "recover", "recover_stream", "Recovered", "RecoveredBlock", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
@@ -1164,6 +1164,44 @@ def grep_count(data, pattern, delim=b"\n", invert=False, index=None, device=0):
     return _grep(data, pattern, delim, invert, index, device, True)[0]
 
 
+def _matches(data, pattern, delim, index, device, count_only):
+    view = _bytes_view(data, "matches")
+    pattern = _pattern_arg(pattern)
+    d = None if delim is None else _delim_arg(delim)
+    ctx = _ctx(9, device)
+    if index is None:
+        return ctx.matches(view, pattern, d, count_only)
+    index = _index_arg(index)
+    return ctx.matches_index(view, index.entries, pattern, _points_arg(index), d, count_only)
+
+
+def _limit_matches(got, limit):
+    """the first `limit` matches of (bytes, entries) and their bytes"""
+    out, ent = got
+    if limit is None or len(ent) <= limit:
+        return got
+    ent = ent[:limit]
+    return out[:int(ent["out_off"][-1] + ent["len"][-1]) if limit else 0], ent
+
+
+def matches(data, pattern, delim=None, index=None, limit=None, device=0):
+    """What grep -o prints: the NON-OVERLAPPING, LEFTMOST-LONGEST matches of `pattern` in the DECODED bytes of `data` (bytes-like
+    .bz2 stream(s)) -> (bytes, entries): the matched parts back to back, with no separator, and a structured array with fields
+    `off` (in the decoded output), `record`, `pattern`, `len` and `out_off` (in the bytes returned), ascending by `off`.  The
+    selection walks a cursor over the whole decoded text: the next match is at the lowest offset at or behind the cursor that holds
+    one, it is the longest match there, and the cursor moves behind it -- b"aa" in b"aaaa" has three hits under search() and two
+    matches here.  With `delim` (one byte) `record` is the number of delimiters in front of the match, else 0; `pattern` is 0 for
+    a byte string.  `pattern` may be a PatternSet or a Regex.  `limit` caps what is returned, not the count (matches_count).  The
+    matches are selected and compacted on the device: only they cross to the host (bzh_match; with `index`, a BlockIndex or
+    SyncIndex of `data`, bzh_match_index)."""
+    return _limit_matches(_matches(data, pattern, delim, index, device, False), _limit_arg(limit))
+
+
+def matches_count(data, pattern, delim=None, index=None, device=0):
+    """The number of matches matches() would return; nothing but two words crosses to the host."""
+    return _matches(data, pattern, delim, index, device, True)[0]
+
+
 class IndexedReader(io.RawIOBase):
     """A seekable, read-only file of the DECODED bytes of `source`: bytes-like, or a seekable binary file holding .bz2
     stream(s).  Every read decodes just the blocks it touches (decompress_range); with a file source it fetches from the file
@@ -1318,6 +1356,15 @@ class IndexedReader(io.RawIOBase):
                 wide.extend(range(lo, min(r + after, last) + 1))
             recs = wide
         return list(zip(recs, self.readv_records([(r, 1) for r in recs]))) if recs else []
+
+    def matches(self, pattern, limit=None):
+        """matches() over the whole indexed source -> (bytes, entries); the position does not move.  Record numbers come when the
+        reader was given a RecordIndex."""
+        index = self.index
+        _, _, _, hi = index.span(0, index.size)
+        d = self.records.delim if self.records is not None else None
+        got = _ctx(9, self._device).matches_index(self._fetch_comp(0, hi), index.entries, _pattern_arg(pattern), _points_arg(index), d)
+        return _limit_matches(got, _limit_arg(limit))
 
     def read_records(self, first, count):
         """records first .. first + count - 1 as one bytes object (readv_records of one pair)"""

@@ -233,6 +233,27 @@ class GrepContextStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class MatchEntry(ctypes.Structure):
+    """bzh_match_entry: a selected match's offset in the decoded output, its record, pattern and length, and where it lies in `out`"""
+    _fields_ = [("off", ctypes.c_uint64), ("record", ctypes.c_uint64), ("pattern", ctypes.c_uint32), ("len", ctypes.c_uint32),
+                ("out_off", ctypes.c_uint64)]
+
+
+MATCH_DTYPE = np.dtype([("off", "<u8"), ("record", "<u8"), ("pattern", "<u4"), ("len", "<u4"), ("out_off", "<u8")])
+assert MATCH_DTYPE.itemsize == ctypes.sizeof(MatchEntry) == 32
+matchp = ctypes.POINTER(MatchEntry)
+MATCH_RECORDS = 1
+
+
+class MatchStats(ctypes.Structure):
+    """bzh_match_stats"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("matches", "out_bytes", "candidates", "entered_tiles", "open_tiles", "windows", "tiles",
+                                               "carry_peak", "staging_peak")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 def grep_context_rows(ent):
     """entries as the C calls fill them -> GREP_CONTEXT_ENTRY_DTYPE: `len` the real length, `context` what bit 63 of it said"""
     out = np.zeros(ent.size, dtype=GREP_CONTEXT_ENTRY_DTYPE)
@@ -362,6 +383,7 @@ SIGNATURES = {
                                       ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint8, u8p, ctypes.c_size_t, grepp, ctypes.c_size_t,
                                       ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint64)]),
     "bzh_get_grep_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(GrepStats)]),
+    "bzh_get_match_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MatchStats)]),
     "bzh_grep_set_context": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]),
     "bzh_get_grep_context_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(GrepContextStats)]),
     "bzh_patset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.c_size_t, ctypes.c_uint,
@@ -597,14 +619,21 @@ def record_spans(entries, rec_cum, ranges):
     return touched[:cnt.value].copy(), int(lo.value), int(hi.value)
 
 
+# bzh_match*: a grep's arguments with bzh_match_entry in place of bzh_grep_entry
+for _name in ("raw_device", "device", "", "index_device", "index"):
+    _res, _args = SIGNATURES["bzh_grep" + ("_" + _name if _name else "")]
+    SIGNATURES["bzh_match" + ("_" + _name if _name else "")] = (_res, [matchp if a is grepp else a for a in _args])
+
+
 def _patset_twin(name):
-    """bzh_search* -> bzh_search_patset*, bzh_grep* -> bzh_grep_patset*"""
-    return name.replace("bzh_search", "bzh_search_patset", 1).replace("bzh_grep", "bzh_grep_patset", 1)
+    """bzh_search* -> bzh_search_patset*, bzh_grep* -> bzh_grep_patset*, bzh_match* -> bzh_match_patset*"""
+    return name.replace("bzh_search", "bzh_search_patset", 1).replace("bzh_grep", "bzh_grep_patset", 1).replace("bzh_match", "bzh_match_patset", 1)
 
 
 # the calls that take a set: their twin's arguments with (pat, plen) replaced by the set, and the hits by bzh_set_hit
 for _name in ("bzh_search_raw_device", "bzh_search_device", "bzh_search", "bzh_search_range_device", "bzh_search_range",
-              "bzh_grep_raw_device", "bzh_grep_device", "bzh_grep", "bzh_grep_index_device", "bzh_grep_index"):
+              "bzh_grep_raw_device", "bzh_grep_device", "bzh_grep", "bzh_grep_index_device", "bzh_grep_index",
+              "bzh_match_raw_device", "bzh_match_device", "bzh_match", "bzh_match_index_device", "bzh_match_index"):
     _res, _args = SIGNATURES[_name]
     _at = next(k for k in range(len(_args) - 1) if _args[k] is u8p and _args[k + 1] is ctypes.c_size_t and _args[k + 2] is ctypes.c_uint)
     SIGNATURES[_patset_twin(_name)] = (_res, [ctypes.c_void_p if a is hitp else a for a in _args[:_at] + [ctypes.c_void_p] + _args[_at + 2:]])
@@ -1501,6 +1530,84 @@ class Context:
     def grep_context_stats(self):
         s = GrepContextStats()
         self.check(lib().bzh_get_grep_context_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
+
+    # ---- the matched parts alone: the selected matches' bytes and their entries (MATCH_DTYPE) -----------------------------------
+    def _match(self, call, count_only=False):
+        """_grep for bzh_match*: call(out pointer, cap, entries pointer, max, nmatches reference, out_total reference) -> status"""
+        got, total = ctypes.c_size_t(0), ctypes.c_uint64(0)
+        if count_only:
+            self.check(call(None, 0, None, 0, ctypes.byref(got), ctypes.byref(total)))
+            return int(got.value), int(total.value)
+        cap, room = self.GREP_GUESS
+        for _ in range(2):
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            ent = np.zeros(max(room, 1), dtype=MATCH_DTYPE)
+            st = call(ptr(out), cap, ent.ctypes.data_as(matchp), room, ctypes.byref(got), ctypes.byref(total))
+            if st == -4 and (total.value > cap or got.value > room):
+                cap, room = int(total.value), int(got.value)
+                continue
+            self.check(st)
+            return out[:int(total.value)].tobytes(), ent[:int(got.value)].copy()
+        raise BzhError(-5, "match: the second call selected more than the first")
+
+    @staticmethod
+    def _match_what(name, pattern, delim):
+        """(the C call, the arguments that name what is looked for, flags, delimiter); delim None: no record numbers"""
+        fl, d = Context._delim(delim)
+        fn, what, _ = Context._what(name, pattern)
+        return fn, what, MATCH_RECORDS if fl else 0, d
+
+    def matches(self, data, pattern, delim=None, count_only=False):
+        """bzh_match: the non-overlapping leftmost-longest matches of `pattern` in the decoded bytes of `data` -> (bytes, entries),
+        or (nmatches, out_total)"""
+        a = np.frombuffer(data, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        fn, what, fl, d = self._match_what("bzh_match", pattern, delim)
+        return self._match(lambda o, c, e, m, g, t: fn(self._h, ptr(src), n, *what, fl, d, o, c, e, m, g, t, None, None), count_only)
+
+    def matches_index(self, comp, entries, pattern, points=None, delim=None, count_only=False):
+        """bzh_match_index over the whole indexed input `comp` -> as matches"""
+        e, p = _entries(entries)
+        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
+        a = np.frombuffer(comp, dtype=np.uint8)
+        n = a.size
+        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        fn, what, fl, d = self._match_what("bzh_match_index", pattern, delim)
+        return self._match(lambda o, c, en, m, g, t: fn(self._h, ptr(src), n, p, e.size, pp, q.size, *what, fl, d, o, c, en, m, g, t), count_only)
+
+    def _match_device(self, call, room):
+        """the device variants: the bytes stay in the caller's device buffer -> (status, nmatches, out_total, entries)"""
+        got, total = ctypes.c_size_t(0), ctypes.c_uint64(0)
+        ent = np.zeros(max(room, 1), dtype=MATCH_DTYPE)
+        st = call(ent.ctypes.data_as(matchp) if room else None, room, ctypes.byref(got), ctypes.byref(total))
+        return st, int(got.value), int(total.value), ent[:min(room, int(got.value))].copy()
+
+    def match_raw_device(self, d_raw, n, pattern, d_out, cap, room, delim=None, flags=None):
+        """bzh_match_raw_device on integer device addresses; `room` entries -> (status, nmatches, out_total, entries)"""
+        fn, what, fl, d = self._match_what("bzh_match_raw_device", pattern, delim)
+        fl = fl if flags is None else flags
+        return self._match_device(lambda e, m, g, t: fn(self._h, ctypes.c_void_p(d_raw), n, *what, fl, d, ctypes.c_void_p(d_out), cap, e, m, g, t),
+                                  room)
+
+    def match_device(self, d_in, n, pattern, d_out, cap, room, delim=None):
+        """bzh_match_device on integer device addresses; `room` entries -> (status, nmatches, out_total, entries)"""
+        fn, what, fl, d = self._match_what("bzh_match_device", pattern, delim)
+        return self._match_device(lambda e, m, g, t: fn(self._h, ctypes.c_void_p(d_in), n, *what, fl, d, ctypes.c_void_p(d_out), cap, e, m, g, t,
+                                                        None, None), room)
+
+    def match_index_device(self, d_in, n, entries, pattern, d_out, cap, room, points=None, delim=None):
+        """bzh_match_index_device on integer device addresses; `room` entries -> (status, nmatches, out_total, entries)"""
+        e, p = _entries(entries)
+        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
+        fn, what, fl, d = self._match_what("bzh_match_index_device", pattern, delim)
+        return self._match_device(lambda en, m, g, t: fn(self._h, ctypes.c_void_p(d_in), n, p, e.size, pp, q.size, *what, fl, d,
+                                                         ctypes.c_void_p(d_out), cap, en, m, g, t), room)
+
+    def match_stats(self):
+        s = MatchStats()
+        self.check(lib().bzh_get_match_stats(self._h, ctypes.byref(s)))
         return s.as_dict()
 
     def decode_ranges_stats(self):

@@ -2341,6 +2341,201 @@ extern "C" int bzh_get_grep_context_stats(const bzh_ctx *ctx, bzh_grep_context_s
     });
 }
 
+// ---- the matched parts alone (match.hip: the kernels, the passes over a window, the staging and the carry; the routes are the
+// grep's, as a WindowSink of its own; the windows and the cursor: match_plan.h)
+static int match_begin(bzh_ctx *ctx, const ScanWhat &q, unsigned flags, void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches,
+                       uint64_t *out_total)
+{
+    if (!q.given() || !nmatches || !out_total || (!d_out && cap) || (!ent && max)) return BZH_E_ARG;
+    *nmatches = 0;
+    *out_total = 0;
+    BZH_TRY(scan_args(ctx, "match", q, flags, BZH_MATCH_RECORDS, "BZH_MATCH_RECORDS"));
+    if ((uintptr_t)d_out & 3u) {
+        bzh_set_error(ctx, "match: the output buffer is not 4-byte aligned");
+        return BZH_E_ARG;
+    }
+    memset(&ctx->mtstats, 0, sizeof ctx->mtstats);
+    return BZH_OK;
+}
+static MatchSink match_sink(const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap, bzh_match_entry *ent, size_t max)
+{
+    return q.is_set ? MatchSink(q.set, flags, delim, d_out, cap, ent, max) : MatchSink(q.pat, q.plen, flags, delim, d_out, cap, ent, max);
+}
+
+// rc: the status of the windows.  Behind them the starts held back (match_finish); bytes and entries follow the stream: whatever
+// the status, nothing is on its way to the caller's arrays when the call returns.
+static int match_end(bzh_ctx *ctx, MatchSink &s, const DecodeCall &call, int rc, size_t *nmatches, uint64_t *out_total)
+{
+    if (rc == BZH_OK) rc = match_finish(ctx, s);
+    rc = decode_call_end(ctx, call, rc);
+    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+    if (rc != BZH_OK) return rc;
+    *nmatches = (size_t)s.walk.sel;
+    *out_total = s.walk.out_bytes;
+    if (s.walk.overflow()) {
+        bzh_set_error(ctx, "match: %llu matches of %llu bytes, room for %llu and %llu", (unsigned long long)s.walk.sel,
+                      (unsigned long long)s.walk.out_bytes, (unsigned long long)s.walk.max, (unsigned long long)s.walk.cap);
+        return BZH_E_CAP;
+    }
+    return BZH_OK;
+}
+
+static int match_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap,
+                            bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_raw && n)) return BZH_E_ARG;
+    BZH_TRY(match_begin(ctx, q, flags, d_out, cap, ent, max, nmatches, out_total));
+    MatchSink s = match_sink(q, flags, delim, d_out, cap, ent, max);
+    if ((uintptr_t)d_raw & 15u) {
+        bzh_set_error(ctx, "match: the buffer is not 16-byte aligned");
+        return BZH_E_ARG;
+    }
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
+    const int rc = match_raw_run(ctx, s, (const uint8_t *)d_raw, n);
+    return match_end(ctx, s, call, rc, nmatches, out_total);
+    });
+}
+
+static int match_device(bzh_ctx *ctx, const void *d_in, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap,
+                        bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total, uint64_t *decoded_total, size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n)) return BZH_E_ARG;
+    BZH_TRY(match_begin(ctx, q, flags, d_out, cap, ent, max, nmatches, out_total));
+    MatchSink s = match_sink(q, flags, delim, d_out, cap, ent, max);
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
+    if (decoded_total) *decoded_total = 0;
+    if (consumed) *consumed = 0;
+    std::vector<uint64_t> cands;
+    BZH_TRY(decode_call_scan(ctx, call, d_in, n, cands));
+    size_t total = 0;
+    const int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, nullptr, nullptr, nullptr, &s);
+    if (decoded_total) *decoded_total = total;
+    return match_end(ctx, s, call, rc, nmatches, out_total);
+    });
+}
+
+static int match_host(bzh_ctx *ctx, const uint8_t *in, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, uint8_t *out, size_t cap,
+                      bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total, uint64_t *decoded_total, size_t *consumed)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n) || (!out && cap)) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BZH_TRY(decode_stage(ctx, in, n, grep_stage_room(out, cap)));
+    BZH_TRY(match_device(ctx, ctx->d_stage_in, n, q, flags, delim, out ? ctx->d_stage_out.p : nullptr, cap, ent, max, nmatches, out_total,
+                         decoded_total, consumed));
+    return decode_unstage(ctx, out, out ? (size_t)*out_total : 0);
+    });
+}
+
+static int match_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts,
+                              size_t npts, const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap, bzh_match_entry *ent, size_t max,
+                              size_t *nmatches, uint64_t *out_total)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n) || (!idx && count) || (!pts && npts)) return BZH_E_ARG;
+    BZH_TRY(match_begin(ctx, q, flags, d_out, cap, ent, max, nmatches, out_total));
+    MatchSink s = match_sink(q, flags, delim, d_out, cap, ent, max);
+    DecodeCall call;
+    BZH_TRY(decode_call_begin(ctx, n, call));
+    BZH_TRY(search_range_args(ctx, idx, count, pts, npts, nullptr, 0));
+    BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(count, 1), ctx->max_batch)));
+    const int rc = decode_range_sink_run(ctx, (const uint8_t *)d_in, n, 0, idx, count, pts, npts, nullptr, 0, ~0ull, s);
+    return match_end(ctx, s, call, rc, nmatches, out_total);
+    });
+}
+
+static int match_index_host(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts,
+                            size_t npts, const ScanWhat &q, unsigned flags, uint8_t delim, uint8_t *out, size_t cap, bzh_match_entry *ent, size_t max,
+                            size_t *nmatches, uint64_t *out_total)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!in && n) || (!idx && count) || (!pts && npts) || (!out && cap)) return BZH_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BZH_TRY(decode_stage(ctx, in, n, grep_stage_room(out, cap)));
+    BZH_TRY(match_index_device(ctx, ctx->d_stage_in, n, idx, count, pts, npts, q, flags, delim, out ? ctx->d_stage_out.p : nullptr, cap, ent, max,
+                               nmatches, out_total));
+    return decode_unstage(ctx, out, out ? (size_t)*out_total : 0);
+    });
+}
+
+// the public calls: a byte string, or a set
+extern "C" int bzh_match_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                                    void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total)
+{
+    return match_raw_device(ctx, d_raw, n, what_pat(pat, plen), flags, delim, d_out, cap, ent, max, nmatches, out_total);
+}
+extern "C" int bzh_match_patset_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                           void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total)
+{
+    return match_raw_device(ctx, d_raw, n, what_set(set), flags, delim, d_out, cap, ent, max, nmatches, out_total);
+}
+extern "C" int bzh_match_device(bzh_ctx *ctx, const void *d_in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                                void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total,
+                                uint64_t *decoded_total, size_t *consumed)
+{
+    return match_device(ctx, d_in, n, what_pat(pat, plen), flags, delim, d_out, cap, ent, max, nmatches, out_total, decoded_total, consumed);
+}
+extern "C" int bzh_match_patset_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                       void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total,
+                                       uint64_t *decoded_total, size_t *consumed)
+{
+    return match_device(ctx, d_in, n, what_set(set), flags, delim, d_out, cap, ent, max, nmatches, out_total, decoded_total, consumed);
+}
+extern "C" int bzh_match(bzh_ctx *ctx, const uint8_t *in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                         uint8_t *out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total,
+                         uint64_t *decoded_total, size_t *consumed)
+{
+    return match_host(ctx, in, n, what_pat(pat, plen), flags, delim, out, cap, ent, max, nmatches, out_total, decoded_total, consumed);
+}
+extern "C" int bzh_match_patset(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim, uint8_t *out,
+                                size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total, uint64_t *decoded_total,
+                                size_t *consumed)
+{
+    return match_host(ctx, in, n, what_set(set), flags, delim, out, cap, ent, max, nmatches, out_total, decoded_total, consumed);
+}
+extern "C" int bzh_match_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count,
+                                      const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                                      void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total)
+{
+    return match_index_device(ctx, d_in, n, idx, count, pts, npts, what_pat(pat, plen), flags, delim, d_out, cap, ent, max, nmatches, out_total);
+}
+extern "C" int bzh_match_patset_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count,
+                                             const bzh_sync_point *pts, size_t npts, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                             void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total)
+{
+    return match_index_device(ctx, d_in, n, idx, count, pts, npts, what_set(set), flags, delim, d_out, cap, ent, max, nmatches, out_total);
+}
+extern "C" int bzh_match_index(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count,
+                               const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                               uint8_t *out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total)
+{
+    return match_index_host(ctx, in, n, idx, count, pts, npts, what_pat(pat, plen), flags, delim, out, cap, ent, max, nmatches, out_total);
+}
+extern "C" int bzh_match_patset_index(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count,
+                                      const bzh_sync_point *pts, size_t npts, const bzh_patset *set, unsigned flags, uint8_t delim, uint8_t *out,
+                                      size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total)
+{
+    return match_index_host(ctx, in, n, idx, count, pts, npts, what_set(set), flags, delim, out, cap, ent, max, nmatches, out_total);
+}
+
+extern "C" int bzh_get_match_stats(const bzh_ctx *ctx, bzh_match_stats *out)
+{
+    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
+    if (!ctx || !out) return BZH_E_ARG;
+    *out = ctx->mtstats;
+    return BZH_OK;
+    });
+}
+
 extern "C" int bzh_get_decode_ranges_stats(const bzh_ctx *ctx, bzh_decode_ranges_stats *out)
 {
     return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {

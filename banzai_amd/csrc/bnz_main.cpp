@@ -10,9 +10,11 @@
 // Search: --search prints the offset and the line number of every occurrence of a byte string in the decoded data, which never
 // leaves the device (bzh_search; with --index bzh_search_range over just the span's compressed bytes).
 // Grep: --grep writes the lines that hold a byte string, selected and compacted on the device (bzh_grep; with --index
-// bzh_grep_index).  Several strings (-e, --patterns) or --ignore-case: one compiled set, one pass (bzh_patset_create, bzh_*_patset*).
+// bzh_grep_index); with -o the matched parts alone, the non-overlapping leftmost-longest matches (bzh_match, bzh_match_index); -b
+// prefixes byte offsets.  Several strings (-e, --patterns) or --ignore-case: one compiled set, one pass (bzh_patset_create, bzh_*_patset*).
 // -E: the strings are regular expressions, compiled into one automaton that goes the set's way (bzh_regex_create_ex; assertions are
 // always admitted).  -w, -x: the word and the line wrap of that call; without -E a string is escaped byte by byte and goes the same way.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cerrno>
@@ -67,6 +69,11 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "                            out as they are, selected on the GPU; the input is kept\n"
             "     --invert               with --grep: the lines that do not hold <string>\n"
             "     --line-number          with --grep: prefix each line with its number, from 1, and ':' ('-' on a context line)\n"
+            "  -o --only-matching        with --grep: write the matched parts alone, each on a line of its own: the matches\n"
+            "                            that do not overlap, leftmost first and the longest there, selected and compacted\n"
+            "                            on the device (bzh_match); --count still counts lines; not with --invert, -A, -B, -C\n"
+            "  -b --byte-offset          with --grep: prefix each line with the offset of its first byte in the decoded data\n"
+            "                            and ':' ('-' on a context line), behind the line number; with -o: of each match\n"
             "  -A --after-context <n>    with --grep: also write the <n> lines behind every selected line,\n"
             "  -B --before-context <n>   ... the <n> lines in front of it,\n"
             "  -C --context <n>          ... or both; every line once and in order, chosen on the device in the same pass,\n"
@@ -163,6 +170,7 @@ int main(int argc, char **argv)
         }
     };
     bool searching = false, needle_hex = false, count_only = false;
+    bool only_matching = false, byte_offset = false; // -o, -b
     bool grepping = false, invert = false, line_number = false; // (--grep is a --search that writes lines: `searching` holds for both)
     bool context_given = false; // -A, -B, -C: lines of context round every selected line
     uint32_t ctx_before = 0, ctx_after = 0;
@@ -275,6 +283,8 @@ int main(int argc, char **argv)
             else if (a == "--grep") expect = GREP;
             else if (a == "--invert") invert = true;
             else if (a == "--line-number") line_number = true;
+            else if (a == "--only-matching") only_matching = true;
+            else if (a == "--byte-offset") byte_offset = true;
             else if (a == "--hex") needle_hex = true;
             else if (a == "--count") count_only = true;
             else if (a == "--patterns") expect = PATFILE;
@@ -299,6 +309,10 @@ int main(int argc, char **argv)
                 word_re = true;
             } else if (a == "-x") {
                 line_re = true;
+            } else if (a == "-o") {
+                only_matching = true;
+            } else if (a == "-b") {
+                byte_offset = true;
             } else if (a == "-A") {
                 expect = CTX_AFTER;
             } else if (a == "-B") {
@@ -339,10 +353,13 @@ int main(int argc, char **argv)
     if ((needle_hex || count_only) && !searching) die(ERR_ARGS, "'--hex' and '--count' go with '--search' or '--grep'");
     if ((invert || line_number) && !grepping) die(ERR_ARGS, "'--invert' and '--line-number' go with '--grep'");
     if (context_given && !grepping) die(ERR_ARGS, "'-A', '-B' and '-C' go with '--grep'");
-    if (grepping && !ranges.empty()) die(ERR_ARGS, "'--grep' takes an input, '--hex', '--invert', '--count', '--line-number', '-A', '-B', '-C' and '--index', nothing else");
+    if ((only_matching || byte_offset) && !grepping) die(ERR_ARGS, "'-o' and '-b' go with '--grep'");
+    if (only_matching && (invert || context_given))
+        die(ERR_ARGS, "'-o' writes the matched parts alone: it does not go with '--invert', '-A', '-B' or '-C'");
+    if (grepping && !ranges.empty()) die(ERR_ARGS, "'--grep' takes an input, '--hex', '--invert', '--count', '--line-number', '-o', '-b', '-A', '-B', '-C' and '--index', nothing else");
     if (searching) {
         if (decompress || recover || dstream || have_out || !mkindex_path.empty() || level_given || interval_given || keep == 0)
-            die(ERR_ARGS, grepping ? "'--grep' takes an input, '--hex', '--invert', '--count', '--line-number', '-A', '-B', '-C' and '--index', nothing else"
+            die(ERR_ARGS, grepping ? "'--grep' takes an input, '--hex', '--invert', '--count', '--line-number', '-o', '-b', '-A', '-B', '-C' and '--index', nothing else"
                                    : "'--search' takes an input, '--hex', '--count', '--index' and one '--range', nothing else");
         if (ranges.size() > 1 || (!ranges.empty() && index_path.empty())) die(ERR_ARGS, "'--search' takes one '--range', with the '--index' of the input");
         if (!index_path.empty() && in_stdin) die(ERR_ARGS, "'--search --index' reads parts of a file: standard in cannot be the input");
@@ -522,10 +539,45 @@ int main(int argc, char **argv)
             if (regex && bzh_regex_get_info(set, &ri) == BZH_OK && ri.unbounded)
                 fprintf(stderr, "bnzhip: the expressions have matches longer than %d bytes: those are not found\n", BZH_REGEX_MAX_SPAN);
         }
+        if (grepping && only_matching && !count_only) { // --grep -o: the matched parts come back compacted, an entry each
+            const unsigned mflags = line_number ? BZH_MATCH_RECORDS : 0;
+            std::vector<uint8_t> out((size_t)16 << 20);
+            std::vector<bzh_match_entry> ms((size_t)1 << 16);
+            size_t nm = 0;
+            uint64_t total = 0;
+            for (int attempt = 0; attempt < 2; attempt++) {
+                if (set && index_path.empty())
+                    rs = bzh_match_patset(sctx, cp, comp.size(), set, mflags, '\n', out.data(), out.size(), ms.data(), ms.size(), &nm, &total, nullptr, nullptr);
+                else if (set)
+                    rs = bzh_match_patset_index(sctx, cp, comp.size(), ent.data(), ent.size(), pts.data(), pts.size(), set, mflags, '\n', out.data(),
+                                                out.size(), ms.data(), ms.size(), &nm, &total);
+                else if (index_path.empty())
+                    rs = bzh_match(sctx, cp, comp.size(), pat, needle.size(), mflags, '\n', out.data(), out.size(), ms.data(), ms.size(), &nm, &total,
+                                   nullptr, nullptr);
+                else
+                    rs = bzh_match_index(sctx, cp, comp.size(), ent.data(), ent.size(), pts.data(), pts.size(), pat, needle.size(), mflags, '\n',
+                                         out.data(), out.size(), ms.data(), ms.size(), &nm, &total);
+                if (rs != BZH_E_CAP || attempt) break;
+                out.resize(std::max<size_t>((size_t)total, 16));
+                ms.resize(std::max<size_t>(nm, 1));
+            }
+            const std::string msg = rs == BZH_OK ? "" : std::string("error during grep: ") + bzh_strerror(rs) + ": " + bzh_last_error(sctx);
+            bzh_patset_destroy(set);
+            bzh_destroy(sctx);
+            if (rs != BZH_OK) die(ERR_OUTPUT, msg);
+            bool ok = true;
+            for (size_t k = 0; k < nm && ok; k++) {
+                if (line_number) printf("%llu:", (unsigned long long)ms[k].record + 1);
+                if (byte_offset) printf("%llu:", (unsigned long long)ms[k].off);
+                ok = fwrite(out.data() + ms[k].out_off, 1, ms[k].len, stdout) == ms[k].len && fputc('\n', stdout) != EOF;
+            }
+            if (!ok || fflush(stdout) != 0) die(ERR_OUTPUT, "error during grep: write failed");
+            return SUCCESS;
+        }
         if (grepping) { // --grep: the selected lines come back compacted; a first try with a guess, a second with the exact rooms
             const unsigned gflags = invert ? BZH_GREP_INVERT : 0;
             std::vector<uint8_t> out(count_only ? 0 : (size_t)16 << 20);
-            const bool want_lines = !count_only && (line_number || context_given); // (with context: where the groups end)
+            const bool want_lines = !count_only && (line_number || context_given || byte_offset); // (with context: where the groups end)
             std::vector<bzh_grep_entry> lines(want_lines ? (size_t)1 << 16 : 0);
             if (context_given) bzh_grep_set_context(sctx, ctx_before, ctx_after);
             size_t nrecs = 0;
@@ -567,6 +619,7 @@ int main(int argc, char **argv)
                     const size_t len = (size_t)(lines[k].len & ~BZH_GREP_LEN_CONTEXT);
                     if (context_given && k && lines[k].record != lines[k - 1].record + 1) fputs("--\n", stdout);
                     if (line_number) printf("%llu%c", (unsigned long long)lines[k].record + 1, is_context ? '-' : ':');
+                    if (byte_offset) printf("%llu%c", (unsigned long long)lines[k].off, is_context ? '-' : ':');
                     ok = fwrite(out.data() + lines[k].out_off, 1, len, stdout) == len;
                 }
             } else if (total) {

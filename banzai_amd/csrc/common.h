@@ -72,6 +72,7 @@ using PinnedBuf = GrowBuf<true>;
 #include "search_plan.h" // the windows of a search and their carry: host-only text (tests/decode_host/search_host.cpp)
 #include "grep_plan.h" // the windows of a grep and their carry: host-only text (tests/decode_host/grep_host.cpp)
 #include "grep_ctx_plan.h" // ... with context records (tests/decode_host/grep_ctx_host.cpp)
+#include "match_plan.h" // the windows of bzh_match* and the cursor between them (tests/decode_host/match_host.cpp)
 #include "batch.h" // geometry, Batch and its layout, the carver: host-only text (tests/workspace_host)
 
 // Kernel classes of the per-kernel roofline table (bzh_get_kernel_stats).  With profiling on, the launches of a
@@ -195,6 +196,8 @@ struct bzh_ctx {
     bzh_grep_stats gstats{};        // of the last bzh_grep* call
     bzh_grep_context_stats gcstats{};
     uint32_t grep_before = 0, grep_after = 0; // bzh_grep_set_context
+    DevBuf match_tab, match_ent;    // bzh_match*: a window's tile tables, its entries
+    bzh_match_stats mtstats{};      // of the last bzh_match* call
     struct DStream *dstrm = nullptr; // streaming decode (bzh_dstream_*, decode.hip): made by the first begin, freed by dstream_free
     size_t dstrm_window = 0, dstrm_staging = 0; // bzh_dstream_set_room: targets of the next begin (0: the defaults)
     // streaming encode (bzh_stream_*)
@@ -711,6 +714,34 @@ struct GrepSink final : WindowSink {
 };
 int grep_raw_run(bzh_ctx *ctx, GrepSink &g, const uint8_t *d_raw, size_t n);
 int grep_finish(bzh_ctx *ctx, GrepSink &g, bool *tail_entry);
+// match.hip: the selected matches of decoded bytes in HBM, compacted into d_out.  A sink is what is looked for, where bytes and
+// entries go, and the walk over its windows (match_plan.h): a set search's hold-back and the cursor.  match_finish: the starts held
+// back, behind the last window.
+struct MatchSink final : WindowSink {
+    BzfPattern pat{};
+    const bzh_patset *set = nullptr; // what is looked for instead of pat
+    bool records;
+    uint8_t *d_out;  // device (null: not asked for)
+    bzh_match_entry *ent;  // host (null: not asked for)
+    MtWalk walk;
+    uint64_t at = 0; // staging position of the window's first new byte
+    MatchSink(const uint8_t *pat_, size_t plen, unsigned flags, uint8_t delim_, void *d_out_, size_t cap, bzh_match_entry *ent_, size_t max)
+        : WindowSink(BZF_FRONT, delim_), pat(bzf_pattern(pat_, (uint32_t)plen, delim_)), records((flags & BZH_MATCH_RECORDS) != 0), d_out((uint8_t *)d_out_), ent(ent_)
+    {
+        walk.begin((uint32_t)plen, 0, 0, false, d_out != nullptr, cap, ent != nullptr, max);
+    }
+    MatchSink(const bzh_patset *set_, unsigned flags, uint8_t delim_, void *d_out_, size_t cap, bzh_match_entry *ent_, size_t max)
+        : WindowSink(BZF_FRONT, delim_), set(set_), records((flags & BZH_MATCH_RECORDS) != 0), d_out((uint8_t *)d_out_), ent(ent_)
+    {
+        look_behind = set->look.look_behind, look_ahead = set->look.look_ahead;
+        walk.begin(set->info.max_len, look_behind, look_ahead, true, d_out != nullptr, cap, ent != nullptr, max);
+    }
+    void begin(uint64_t, uint64_t, uint64_t, uint64_t) override {} // (the whole output, from offset 0)
+    int room(bzh_ctx *ctx, uint64_t bytes, uint8_t **d_stage) override;
+    int window(bzh_ctx *ctx, uint64_t bytes) override;
+};
+int match_raw_run(bzh_ctx *ctx, MatchSink &s, const uint8_t *d_raw, size_t n);
+int match_finish(bzh_ctx *ctx, MatchSink &s);
 // recover.hip: the bits of the kept blocks, end to end from bit 32 of d_out, in one launch (the per-word rule: recover_gather.h)
 struct BzrDesc;
 int recover_gather_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const std::vector<BzrDesc> &descs, uint64_t body, uint32_t *d_out);

@@ -127,7 +127,8 @@ BZF_FN uint64_t bzm_emit1(const BzmSet &m, const BzmShared &sh, const uint8_t *t
 // ---- the matchers as search_tiles and grep_tiles see them ---------------------------------------------------------------------
 // Shared: what the matcher keeps in LDS beside the tile.  stage: a thread's part of the staging, a barrier follows.  match16: the
 // starts in `valid` that hold a match.  count16: the hits at those starts (*hm: the starts that hold one).  emit1: the hits of the
-// start at tile byte `text` into the hit slots, the rank behind them returned.  BY_LIM: the matcher bounds a match by lim itself,
+// start at tile byte `text` into the hit slots, the rank behind them returned.  longest1: the length of the longest match at a
+// start that match16 named (match.hip: the matched parts alone), *pattern the lowest-numbered one of that length.  BY_LIM: the matcher bounds a match by lim itself,
 // so every processed position is a start (a single pattern's starts end plen - 1 in front of the text's end instead).
 struct BzfHit { // bzh_hit
     uint64_t off, record;
@@ -156,6 +157,7 @@ struct BzfOne : BzfOnePerStart<BzfOne> { // the single pattern of search_core.h
         if (rank < emit) out[rank] = Hit{off, rec};
         return rank + 1;
     }
+    BZF_MEM uint32_t longest1(const Shared &, const uint8_t *, uint64_t, uint32_t *pattern) const { return *pattern = 0, p.plen; }
 };
 struct BzmMatcher { // the set
     using Shared = BzmShared;
@@ -175,6 +177,13 @@ struct BzmMatcher { // the set
     BZF_MEM uint64_t emit1(const Shared &sh, const uint8_t *text, uint64_t p, uint64_t off, uint64_t rec, Hit *out, uint64_t rank, uint64_t emit) const
     {
         return bzm_emit1(m, sh, text, p, off, rec, out, rank, emit);
+    }
+    BZF_MEM uint32_t longest1(const Shared &sh, const uint8_t *text, uint64_t p, uint32_t *pattern) const
+    {
+        uint32_t last = 0, best = 0; // (a walk's terminals ascend by length)
+        bzm_walk(m, sh, text, sh.first[text[0]], bzm_steps(m, p), [&](uint32_t st, uint32_t len) { return last = st, best = len, true; });
+        if (last) *pattern = m.pat_no[last - 1];
+        return best;
     }
 };
 

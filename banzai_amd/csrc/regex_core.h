@@ -197,6 +197,16 @@ struct BzrMatcher : BzrArgs<LOOK>, BzfOnePerStart<BzrMatcher<LDS_ROWS, LOOK>> {
         if (rank < emit) out[rank] = BzmHit{off, rec, pattern(st, ctx), len};
         return rank + 1;
     }
+    // the length of that hit alone, *pattern its expression (0: no match at this start)
+    BZF_MEM uint32_t longest1(const Shared &sh, const uint8_t *text, uint64_t p, uint32_t *pat) const
+    {
+        uint32_t len = 0, ctx = 0, before = 0;
+        if constexpr (LOOK) before = (p & (BZF_TILE - 1u)) ? (uint32_t)text[-1] : sh.prev;
+        const uint32_t st = walk<true>(sh, text, sh.first[row(p, before) + text[0]], p, &len, &ctx);
+        if (!st) return 0;
+        *pat = pattern(st, ctx);
+        return len;
+    }
     BZF_MEM uint32_t pattern(uint32_t st, uint32_t ctx) const // the lowest-numbered expression that accepts at terminal st (behind context ctx)
     {
         if constexpr (LOOK) return this->l.pat_ctx[(st - 1) * 4u + ctx];

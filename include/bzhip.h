@@ -836,6 +836,83 @@ BZH_API int bzh_regex_check_ex(const uint8_t *const *exprs, const size_t *lens, 
                                unsigned syntax, bzh_regex_info *info, bzh_regex_look *look, char *err, size_t errn);
 BZH_API int bzh_regex_get_look(const bzh_patset *set, bzh_regex_look *out); /* BZH_E_ARG for a set of plain strings */
 
+/* ---- the matched parts alone: grep -o, the non-overlapping leftmost-longest matches compacted on the device ---------------- */
+
+/* A search reports every start, overlapping ones included; a grep returns whole records.  bzh_match* selects what grep -o prints
+ * and returns only those bytes.
+ * THE RULE, over the whole decoded output (not line by line; for a pattern that cannot match the delimiter the two are the same).
+ * For a start s that holds a match, L(s) in 1..256 is the length of the LONGEST match there, assertions applied: plen for a byte
+ * string, the longest of the start's patterns for a set, what a search reports as len for an automaton; ties go to the lowest
+ * pattern number.  A cursor walks from 0: the next selected match is at the lowest s >= cursor that holds a match, and the cursor
+ * becomes s + L(s).  "aa" in "aaaa" has three hits under bzh_search and two matches here.
+ * OUTPUT.  The selected matches' bytes lie back to back in out, with no separator, in ascending off.  ent[k] describes the k-th
+ * match: `off` its first byte's offset in the decoded output, `len` its length, `pattern` its pattern's number (0 for a byte
+ * string), `out_off` where it lies in out, the running sum of len, `record` the number of delimiters in front of off with
+ * BZH_MATCH_RECORDS and 0 without it: a match belongs to the record of its first byte.
+ * COUNTS AND ROOM are a grep's: *nmatches and *out_total are always exact; an array that is null with zero room is not asked for;
+ * all of out, cap, ent, max null or zero is a counting call; room that is asked for and too small gives BZH_E_CAP, the call goes
+ * on counting, out and ent are then unspecified, and repeating the call with the exact room succeeds.
+ * BZH_E_ARG: a grep's cases; BZH_GREP_INVERT has no meaning here and any flag bit but BZH_MATCH_RECORDS is undefined.  The context
+ * setting of bzh_grep_set_context is not read.
+ * BOUNDS.  No read goes past the aligned 4-byte word that holds byte n - 1 of a text; no store goes outside out[0, *out_total),
+ * ent[0, *nmatches) and the kernels' own tables.  Every workgroup stores only entries and bytes of matches that start in its own
+ * tile of 4,096; no thread follows the chain of matches beyond a tile, or beyond its chunk of the tiles' 256-entry maps.
+ * A byte-range form does not exist: the selection inside a range depends on the text in front of it.  A maximum count (-m) is
+ * the caller's: read the first entries. */
+typedef struct {
+    uint64_t off;     /* of the match's first byte in the decoded output */
+    uint64_t record;  /* delimiters in front of off (BZH_MATCH_RECORDS), else 0 */
+    uint32_t pattern; /* the pattern's number; 0 for a byte string */
+    uint32_t len;     /* its bytes, 1..256 */
+    uint64_t out_off; /* of its first byte in out */
+} bzh_match_entry;    /* 32 bytes */
+enum { BZH_MATCH_RECORDS = 1 };
+
+/* The variants are a grep's, argument for argument: decoded bytes in HBM (d_raw 16-byte aligned), the full route (CRCs of blocks
+ * and streams verified, all or nothing), the indexed route over the whole file (no record table needed). */
+BZH_API int bzh_match_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                                 void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total);
+BZH_API int bzh_match_device(bzh_ctx *ctx, const void *d_in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                             void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total,
+                             uint64_t *decoded_total, size_t *consumed);
+BZH_API int bzh_match(bzh_ctx *ctx, const uint8_t *in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                      uint8_t *out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total,
+                      uint64_t *decoded_total, size_t *consumed);
+BZH_API int bzh_match_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count,
+                                   const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                                   void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total);
+BZH_API int bzh_match_index(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count,
+                            const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
+                            uint8_t *out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total);
+BZH_API int bzh_match_patset_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                        void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total);
+BZH_API int bzh_match_patset_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                    void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total,
+                                    uint64_t *decoded_total, size_t *consumed);
+BZH_API int bzh_match_patset(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
+                             uint8_t *out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total,
+                             uint64_t *decoded_total, size_t *consumed);
+BZH_API int bzh_match_patset_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count,
+                                          const bzh_sync_point *pts, size_t npts, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                          void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total);
+BZH_API int bzh_match_patset_index(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count,
+                                   const bzh_sync_point *pts, size_t npts, const bzh_patset *set, unsigned flags, uint8_t delim,
+                                   uint8_t *out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total);
+
+/* Counters of the last bzh_match* call. */
+typedef struct {
+    uint64_t matches;       /* selected (*nmatches) */
+    uint64_t out_bytes;     /* their bytes (*out_total) */
+    uint64_t candidates;    /* starts at or behind their window's cursor that hold a match */
+    uint64_t entered_tiles; /* tiles of 4,096 entered beyond their first byte: a selected match spans the edge in front */
+    uint64_t open_tiles;    /* tiles whose map from entry to exit is not constant */
+    uint64_t windows;       /* one for raw bytes, one a batch, the indexed walk's windows; one more where bytes were held back */
+    uint64_t tiles;         /* over all windows */
+    uint64_t carry_peak;    /* bytes of the longest carry */
+    uint64_t staging_peak;  /* bytes of the staging buffer */
+} bzh_match_stats;
+BZH_API int bzh_get_match_stats(const bzh_ctx *ctx, bzh_match_stats *out);
+
 /* ---- the encoder writes the index of its own stream: no decode pass to rediscover what it held -------------------------- */
 
 /* bzh_encode_device that also returns the index of the stream it writes: the entries bzh_decode_index would return for
