@@ -452,6 +452,7 @@ SIGNATURES = {
     "bzh_bwt_roundtrip_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, u64p]),
     "bzh_bwt": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u8p, u32p, u8p]),
     "bzh_mtf": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u8p, u16p, szp, u32p, u32p]),
+    "bzh_mtf_batch": (ctypes.c_int, [ctypes.c_void_p, u8p, u64p, u32p, ctypes.c_size_t, u8p, u16p, u32p, u32p, u32p]),
     "bzh_huffman": (ctypes.c_int, [ctypes.c_void_p, u16p, ctypes.c_size_t, ctypes.c_uint32, u32p, u8p,
                                    ctypes.c_size_t, u64p, u8p, u32p]),
 }
@@ -830,6 +831,30 @@ class Context:
         self.check(lib().bzh_mtf(self._h, ptr(a), n, ptr(hb), ptr(syms, u16p), ctypes.byref(m), ptr(freqs, u32p),
                                  ctypes.byref(ns)))
         return syms[:m.value].copy(), freqs, int(ns.value)
+
+    def mtf_batch(self, cols):
+        """cols: [(column bytes, has_byte)] -> [(syms, freqs, num_syms)], all columns in one launch (bzh_mtf_batch): their
+        number decides the tile of the walk, 4,096 bytes from 64 columns on"""
+        B = len(cols)
+        lens = np.array([len(c) for c, _ in cols], dtype=np.uint32)
+        offs = np.zeros(max(B, 1), dtype=np.uint64)
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+        cat = np.frombuffer(b"".join(bytes(c) for c, _ in cols) or b"\0", dtype=np.uint8).copy()
+        hb = np.zeros(max(B, 1) * 256, dtype=np.uint8)
+        for k, (_, h) in enumerate(cols):
+            hb[k * 256:(k + 1) * 256] = np.asarray(h, dtype=np.uint8)
+        syms = np.zeros(int(lens.sum()) + B + 1, dtype=np.uint16)
+        m = np.zeros(max(B, 1), dtype=np.uint32)
+        freqs = np.zeros(max(B, 1) * 258, dtype=np.uint32)
+        ns = np.zeros(max(B, 1), dtype=np.uint32)
+        lens_p = lens if B else np.zeros(1, np.uint32)
+        self.check(lib().bzh_mtf_batch(self._h, ptr(cat), ptr(offs, u64p), ptr(lens_p, u32p), B, ptr(hb), ptr(syms, u16p),
+                                       ptr(m, u32p), ptr(freqs, u32p), ptr(ns, u32p)))
+        res = []
+        for k in range(B):
+            o = int(offs[k]) + k
+            res.append((syms[o:o + int(m[k])].copy(), freqs[k * 258:(k + 1) * 258].copy(), int(ns[k])))
+        return res
 
     def huffman(self, syms, num_syms, freqs):
         s = np.ascontiguousarray(syms, dtype=np.uint16)

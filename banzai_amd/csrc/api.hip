@@ -507,35 +507,74 @@ extern "C" int bzh_bwt_roundtrip_device(bzh_ctx *ctx, size_t b0, size_t b1, uint
 }
 
 // ---- stage seam: MTF + RLE2 ---------------------------------------------------------------------------
+// All nblk columns run in ONE mtf_run, so nblk alone decides the tile size (mtf_tile_bytes): verification tooling that
+// brings chosen columns to the tiles of batches of 64 blocks and more, which whole streams reach only with the columns
+// their BWT happens to give.  Block k's symbols go to syms[offs[k] + k ..), lens[k] + 1 entries of room.
+extern "C" int bzh_mtf_batch(bzh_ctx *ctx, const uint8_t *bwt, const uint64_t *offs, const uint32_t *lens, size_t nblk,
+                             const uint8_t *has_byte, uint16_t *syms, uint32_t *m, uint32_t *freqs, uint32_t *num_syms)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx) return BZH_E_ARG;
+    if (!bwt || !offs || !lens || !has_byte || !syms || !m || !freqs || !num_syms) {
+        bzh_set_error(ctx, "bzh_mtf_batch: null pointer");
+        return BZH_E_ARG;
+    }
+    if (nblk == 0 || nblk > ctx->max_batch) {
+        bzh_set_error(ctx, "bzh_mtf_batch: %zu blocks outside 1..%u", nblk, ctx->max_batch);
+        return BZH_E_ARG;
+    }
+    const uint32_t B = (uint32_t)nblk;
+    uint32_t nmax = 0;
+    uint64_t ntotal = 0;
+    for (uint32_t b = 0; b < B; b++) {
+        if (lens[b] == 0 || lens[b] > ctx->M) {
+            bzh_set_error(ctx, "block %u length %u outside 1..%u", b, lens[b], ctx->M);
+            return BZH_E_ARG;
+        }
+        nmax = std::max(nmax, lens[b]);
+        ntotal += lens[b];
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    stats_begin(ctx);
+    BZH_TRY(ensure_arena(ctx, B));
+    Batch &bt = ctx->bt;
+    hipStream_t st = ctx->stream;
+    for (uint32_t b = 0; b < B; b++)
+        HIP_TRY(ctx, hipMemcpyAsync(bt.bwt + (size_t)b * bt.S, bwt + offs[b], lens[b], hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(bt.n, lens, B * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(bt.hasbyte, has_byte, (size_t)B * 256, hipMemcpyHostToDevice, st));
+    BZH_TRY(mtf_run(ctx, B, nmax, ntotal));
+    HIP_TRY(ctx, hipMemcpyAsync(m, bt.m, B * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(num_syms, bt.nsyms, B * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(freqs, bt.freqs, (size_t)B * 258 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, bzh_stream_wait(st));
+    for (uint32_t b = 0; b < B; b++) {
+        if (m[b] == 0 || m[b] > lens[b] + 1) {
+            bzh_set_error(ctx, "mtf produced m=%u for n=%u (block %u)", m[b], lens[b], b);
+            return BZH_E_HIP;
+        }
+    }
+    for (uint32_t b = 0; b < B; b++)
+        HIP_TRY(ctx, hipMemcpyAsync(syms + offs[b] + b, bt.syms + (size_t)b * (bt.S + 64), (size_t)m[b] * sizeof(uint16_t),
+                                    hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, bzh_stream_wait(st));
+    return BZH_OK;
+    });
+}
+
 extern "C" int bzh_mtf(bzh_ctx *ctx, const uint8_t *bwt, size_t n, const uint8_t *has_byte, uint16_t *syms,
                        size_t *m, uint32_t *freqs, uint32_t *num_syms)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || !bwt || !has_byte || !syms || !m || !freqs || !num_syms || n == 0 || n > ctx->M) return BZH_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    stats_begin(ctx);
-    BZH_TRY(ensure_arena(ctx, 1));
-    Batch &bt = ctx->bt;
-    hipStream_t st = ctx->stream;
-    uint32_t n32 = (uint32_t)n;
-    HIP_TRY(ctx, hipMemcpyAsync(bt.bwt, bwt, n, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(bt.n, &n32, sizeof n32, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(bt.hasbyte, has_byte, 256, hipMemcpyHostToDevice, st));
-    BZH_TRY(mtf_run(ctx, 1, n32));
+    const uint64_t off = 0;
+    const uint32_t len = (uint32_t)n;
     uint32_t m32 = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&m32, bt.m, sizeof m32, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(num_syms, bt.nsyms, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(freqs, bt.freqs, 258 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, bzh_stream_wait(st));
-    if (m32 == 0 || m32 > n32 + 1) {
-        bzh_set_error(ctx, "mtf produced m=%u for n=%u", m32, n32);
-        return BZH_E_HIP;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(syms, bt.syms, (size_t)m32 * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, bzh_stream_wait(st));
-    *m = m32;
-    return BZH_OK;
+    const int rc = bzh_mtf_batch(ctx, bwt, &off, &len, 1, has_byte, syms, &m32, freqs, num_syms);
+    if (rc == BZH_OK) *m = m32;
+    return rc;
     });
 }
 

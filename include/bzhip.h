@@ -1188,6 +1188,14 @@ BZH_API int bzh_bwt_roundtrip_device(bzh_ctx *ctx, size_t b0, size_t b1, uint64_
 BZH_API int bzh_mtf(bzh_ctx *ctx, const uint8_t *bwt, size_t n, const uint8_t *has_byte, uint16_t *syms, size_t *m,
             uint32_t *freqs, uint32_t *num_syms);
 
+/* Verification tooling: bzh_mtf on nblk columns in ONE launch, so that nblk decides the tile a wavefront walks (2,048
+ * bytes below 64 blocks, 4,096 from 64 on) and chosen columns reach the tiles that whole streams reach only with whatever
+ * their BWT gives.  Block k's column is bwt[offs[k] .. offs[k]+lens[k]), its present bytes has_byte[k*256..), its symbols
+ * go to syms[offs[k]+k ..) (lens[k]+1 entries of room), m[k], freqs[k*258..), num_syms[k].  BZH_E_ARG for nblk == 0,
+ * nblk > the context's max_batch, a length outside 1..block size, a null pointer. */
+BZH_API int bzh_mtf_batch(bzh_ctx *ctx, const uint8_t *bwt, const uint64_t *offs, const uint32_t *lens, size_t nblk,
+                  const uint8_t *has_byte, uint16_t *syms, uint32_t *m, uint32_t *freqs, uint32_t *num_syms);
+
 /* huffman::encode (lib/huffman.rs:313-575) of one block as a standalone bit string from bit 0;
  * code_lengths (optional) receives num_tables x 258 final lengths, *num_tables the count. */
 BZH_API int bzh_huffman(bzh_ctx *ctx, const uint16_t *syms, size_t m, uint32_t num_syms, const uint32_t *freqs,

@@ -19,7 +19,7 @@ def test_header_declares_expected_surface():
     syms = header_symbols()
     for need in ("bzh_create", "bzh_destroy", "bzh_encode", "bzh_encode_device", "bzh_plan_device",
                  "bzh_encode_range_device", "bzh_assemble_device", "bzh_rle1_split", "bzh_bwt", "bzh_mtf",
-                 "bzh_huffman", "bzh_crc32"):
+                 "bzh_mtf_batch", "bzh_huffman", "bzh_crc32"):
         assert need in syms
 
 

@@ -1,7 +1,8 @@
 """MTF + RLE2 on the MI355X, where the walk emits the RLE2 symbols itself (banzai_amd/csrc/mtf.hip): symbols, m, histogram
 and num_syms bit for bit the oracle's.  Through the stage seam one block runs with tiles of 2,048 bytes; whole streams of 64
 blocks and more run with tiles of 4,096.  The inputs sit on the edges of the layout: no run head at all, digit-count
-edges of the zero runs, runs across halves (1,024), tiles and several tiles, a head in the last position, a trailing run."""
+edges of the zero runs, runs across halves (1,024), tiles and several tiles, a head in the last position, a trailing run.
+The walk's list, chunk and tile edges and hand-built columns in tiles of 4,096: tests/mtf_cases.py, tests/test_gpu_mtf_edges.py."""
 import numpy as np
 import pytest
 
