@@ -511,10 +511,21 @@ def _points(points):
     return p, (p.ctypes.data_as(syncp) if p.size else None)
 
 
+def _points_or_none(points):
+    """_points; None: no points"""
+    return _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
+
+
+def _input(data):
+    """the bytes of any buffer as a contiguous uint8 array without a copy (of an empty one: a byte nobody reads), and their number"""
+    a = np.frombuffer(data, dtype=np.uint8)
+    return (np.ascontiguousarray(a) if a.size else np.zeros(1, np.uint8)), a.size
+
+
 def index_blob_write(entries, points=None, interval=0, consumed=0):
     """bzh_index_blob_write (pure host): the index file of these arrays -> bytes; interval 0: a block index blob (no points)"""
     e, ep = _entries(entries)
-    q, qp = _points(points if points is not None else np.zeros(0, dtype=SYNC_DTYPE))
+    q, qp = _points_or_none(points)
     need = int(lib().bzh_index_blob_size(e.size, q.size, interval))
     out = np.empty(max(need, 1), dtype=np.uint8)
     olen = ctypes.c_size_t(0)
@@ -972,9 +983,7 @@ class Context:
     # ---- decode (bzh_decode*) ----
     def decode_raw(self, data, cap):
         """one bzh_decode call into a buffer of `cap` bytes -> (status, bytes or None, size reported, input bytes consumed)"""
-        a = np.frombuffer(data, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        src, n = _input(data)
         out = np.empty(max(cap, 1), dtype=np.uint8)
         olen = ctypes.c_size_t(0)
         used = ctypes.c_size_t(0)
@@ -1059,9 +1068,7 @@ class Context:
         """one bzh_recover call into a buffer of `cap` bytes and a report of `max_entries` entries -> (status, bytes or None,
         size reported, entries as a structured array of RECOVER_DTYPE or None, entries reported).  The bytes are None unless
         they fit, the entries unless they do."""
-        a = np.frombuffer(data, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        src, n = _input(data)
         out = np.empty(max(cap, 1), dtype=np.uint8)
         ent = np.empty(max(max_entries, 1), dtype=RECOVER_DTYPE)
         olen, cnt = ctypes.c_size_t(0), ctypes.c_size_t(0)
@@ -1104,9 +1111,7 @@ class Context:
 
     def recover_stream_raw(self, data, entries, cap):
         """one bzh_recover_stream call into a buffer of `cap` bytes -> (status, bytes or None, size reported)"""
-        a = np.frombuffer(data, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        src, n = _input(data)
         e, p = _report(entries)
         out = np.empty(max(cap, 1), dtype=np.uint8)
         olen = ctypes.c_size_t(0)
@@ -1135,9 +1140,7 @@ class Context:
     def decode_index(self, data):
         """bzh_decode_index: the verified block index of the stream(s) in `data` -> (entries as a structured array of
         INDEX_DTYPE, decoded bytes in total, input bytes consumed)"""
-        a = np.frombuffer(data, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        src, n = _input(data)
         cnt, used, total = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint64(0)
         # room for every block the input can hold, so that the build runs once: a block is at least 174 bits (magic, CRC,
         # origPtr, one sector of the symbol map, one selector, two tables of three lengths, one symbol and the end of block).
@@ -1158,9 +1161,7 @@ class Context:
         compressed bytes from byte `in_byte_base` of that input on (all of it, or just the span of the range)"""
         if off < 0 or length < 0:
             raise ValueError("offset and length must not be negative")
-        a = np.frombuffer(data, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        src, n = _input(data)
         e, p = _entries(entries)
         total = int(e["out_off"][-1]) + int(e["out_len"][-1]) if e.size else 0
         cap = max(0, min(length, total - off))
@@ -1182,9 +1183,7 @@ class Context:
         """bzh_decode_index_sync: decode_index that also records a sync point every `interval` groups of every block ->
         (entries, points as a structured array of SYNC_DTYPE, decoded bytes in total, input bytes consumed).  One call sizes
         the two arrays, a second fills them."""
-        a = np.frombuffer(data, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        src, n = _input(data)
         cnt, npts, used, total = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint64(0)
         st = lib().bzh_decode_index_sync(self._h, ptr(src), n, interval, None, 0, ctypes.byref(cnt), None, 0, ctypes.byref(npts),
                                          ctypes.byref(total), ctypes.byref(used))
@@ -1202,9 +1201,7 @@ class Context:
         """bzh_decode_range_sync: decode_range with the blocks' entropy stage split at the sync points"""
         if off < 0 or length < 0:
             raise ValueError("offset and length must not be negative")
-        a = np.frombuffer(data, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        src, n = _input(data)
         e, p = _entries(entries)
         q, pp = _points(points)
         total = int(e["out_off"][-1]) + int(e["out_len"][-1]) if e.size else 0
@@ -1228,11 +1225,9 @@ class Context:
         """bzh_decode_ranges: the output bytes of every (off, len) of `ranges` in one call, every touched block decoded once ->
         (bytes of all ranges back to back, their offsets in it, their lengths).  `comp` holds the compressed bytes from byte
         `in_byte_base` of the indexed input on; `points`: sync points, or None"""
-        a = np.frombuffer(comp, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        src, n = _input(comp)
         e, p = _entries(entries)
-        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
+        q, pp = _points_or_none(points)
         r, rp = _ranges(ranges)
         total = int(e["out_off"][-1]) + int(e["out_len"][-1]) if e.size else 0
         off, ln = r["off"].astype(object), r["len"].astype(object)  # (Python ints: off + len does not wrap)
@@ -1248,7 +1243,7 @@ class Context:
         """bzh_decode_ranges_device on integer device addresses -> (status, out_total, offsets, lengths); the status is not
         raised, so that a caller can look at the sizes a BZH_E_CAP leaves"""
         e, p = _entries(entries)
-        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
+        q, pp = _points_or_none(points)
         r, rp = _ranges(ranges)
         offs, lens = np.zeros(max(r.size, 1), dtype=np.uintp), np.zeros(max(r.size, 1), dtype=np.uintp)
         got = ctypes.c_size_t(0)
@@ -1260,9 +1255,7 @@ class Context:
         """bzh_decode_index_records: decode_index_sync (interval 0: entries only) that also fills the record table ->
         (entries, points, rec_cum as a uint64 array of entries + 1 words, nrecords, decoded bytes in total, input bytes
         consumed).  One call sizes the arrays, a second fills them."""
-        a = np.frombuffer(data, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        src, n = _input(data)
         cnt, npts, used = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
         total, nrec = ctypes.c_uint64(0), ctypes.c_uint64(0)
         st = lib().bzh_decode_index_records(self._h, ptr(src), n, interval, delim, None, 0, ctypes.byref(cnt), None, 0, ctypes.byref(npts),
@@ -1304,12 +1297,10 @@ class Context:
     def decode_records_raw(self, comp, entries, rec_cum, ranges, cap, points=None, in_byte_base=0, delim=10):
         """one bzh_decode_records call with room for `cap` bytes -> (status, out_total, offsets, lengths, the buffer); nothing
         is raised, so that a caller can look at the sizes a BZH_E_CAP leaves"""
-        a = np.frombuffer(comp, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        src, n = _input(comp)
         e, p = _entries(entries)
         t, tp = _table(e, rec_cum)
-        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
+        q, pp = _points_or_none(points)
         r, rp = _ranges(ranges)
         out = np.empty(max(cap, 1), dtype=np.uint8)
         offs, lens = np.zeros(max(r.size, 1), dtype=np.uintp), np.zeros(max(r.size, 1), dtype=np.uintp)
@@ -1333,7 +1324,7 @@ class Context:
         """bzh_decode_records_device on integer device addresses -> (status, out_total, offsets, lengths); not raised"""
         e, p = _entries(entries)
         t, tp = _table(e, rec_cum)
-        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
+        q, pp = _points_or_none(points)
         r, rp = _ranges(ranges)
         offs, lens = np.zeros(max(r.size, 1), dtype=np.uintp), np.zeros(max(r.size, 1), dtype=np.uintp)
         got = ctypes.c_size_t(0)
@@ -1405,9 +1396,7 @@ class Context:
 
     def search(self, data, pattern, delim=None, limit=None, with_total=False):
         """bzh_search: every occurrence of `pattern` in the decoded bytes of `data` -> (hits, nhits[, out_total, consumed])"""
-        a = np.frombuffer(data, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        src, n = _input(data)
         fn, what, dt = self._what("bzh_search", pattern)
         fl, d = self._delim(delim)
         total, used = ctypes.c_uint64(0), ctypes.c_size_t(0)
@@ -1419,7 +1408,7 @@ class Context:
         """bzh_search_range (d_in: an integer device address and comp the byte count -> bzh_search_range_device): the hits wholly
         inside output [off, off + length) of the indexed input -> (hits, nhits).  Record numbers with rec_cum and delim."""
         e, p = _entries(entries)
-        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
+        q, pp = _points_or_none(points)
         fl, d = self._delim(delim)
         tp = _table(e, rec_cum)[1] if rec_cum is not None else None
         length = 2**64 - 1 if length is None else length
@@ -1428,9 +1417,7 @@ class Context:
             return self._search(lambda h, m, g: fn(self._h, ctypes.c_void_p(d_in), comp, in_byte_base, p, e.size, pp, q.size, tp, off, length,
                                                    *what, fl, d, h, m, g), limit, dt)
         fn, what, dt = self._what("bzh_search_range", pattern)
-        a = np.frombuffer(comp, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        src, n = _input(comp)
         return self._search(lambda h, m, g: fn(self._h, ptr(src), n, in_byte_base, p, e.size, pp, q.size, tp, off, length, *what, fl, d, h, m, g),
                             limit, dt)
 
@@ -1442,13 +1429,16 @@ class Context:
         self.check(lib().bzh_get_search_stats(self._h, ctypes.byref(s)))
         return s.as_dict()
 
-    # ---- grep: the selected records' bytes and their entries (GREP_ENTRY_DTYPE) ---------------------------------------------------
+    # ---- grep and the matched parts alone: the selected bytes and their entries.  One body per route for both families; a family is
+    # the prefix of its C calls, its entries (GREP_ENTRY_DTYPE, MATCH_DTYPE) and its flags ------------------------------------------
     GREP_GUESS = (1 << 20, 1 << 12)  # bytes and entries of the first try; more of either: once more, with the exact rooms
+    _ENTRIES = {"grep": (GREP_ENTRY_DTYPE, grepp), "match": (MATCH_DTYPE, matchp)}
 
-    def _grep(self, call, count_only=False):
-        """call(out pointer, cap, entries pointer, max, nrecs reference, out_total reference) -> status.  Returns (bytes,
+    def _scan(self, family, call, count_only=False):
+        """call(out pointer, cap, entries pointer, max, count reference, out_total reference) -> status.  Returns (bytes,
         entries): a first try with GREP_GUESS, a second with the exact rooms when either was too small.  count_only: a counting
-        call (no room is asked for) -> (nrecs, out_total)."""
+        call (no room is asked for) -> (count, out_total).  grep_status / match_status: the status of the last C call."""
+        dtype, entp = self._ENTRIES[family]
         got, total = ctypes.c_size_t(0), ctypes.c_uint64(0)
         if count_only:
             self.check(call(None, 0, None, 0, ctypes.byref(got), ctypes.byref(total)))
@@ -1456,15 +1446,21 @@ class Context:
         cap, room = self.GREP_GUESS
         for _ in range(2):
             out = np.empty(max(cap, 1), dtype=np.uint8)
-            ent = np.zeros(max(room, 1), dtype=GREP_ENTRY_DTYPE)
-            st = call(ptr(out), cap, ent.ctypes.data_as(grepp), room, ctypes.byref(got), ctypes.byref(total))
-            self.grep_status = st  # (of the last C call)
+            ent = np.zeros(max(room, 1), dtype=dtype)
+            st = call(ptr(out), cap, ent.ctypes.data_as(entp), room, ctypes.byref(got), ctypes.byref(total))
+            setattr(self, family + "_status", st)
             if st == -4 and (total.value > cap or got.value > room):
                 cap, room = int(total.value), int(got.value)
                 continue
             self.check(st)
             return out[:int(total.value)].tobytes(), ent[:int(got.value)].copy()
-        raise BzhError(-5, "grep: the second call selected more than the first")
+        raise BzhError(-5, family + ": the second call selected more than the first")
+
+    def _grep(self, call, count_only=False):
+        return self._scan("grep", call, count_only)
+
+    def _match(self, call, count_only=False):
+        return self._scan("match", call, count_only)
 
     @staticmethod
     def _grep_args(pattern, delim, invert):
@@ -1475,13 +1471,14 @@ class Context:
         return pat, plen, GREP_INVERT if invert else 0, d
 
     @staticmethod
-    def _grep_what(name, pattern, delim, invert):
-        """_grep_args for a byte string or a PatternSet -> (the C call, the arguments that name what is looked for, flags, delimiter)"""
+    def _scan_what(family, route, pattern, delim, invert=False):
+        """-> (the C call bzh_<family><route> for a byte string or a PatternSet, the arguments that name what is looked for, flags,
+        delimiter).  A grep needs a delimiter; a match numbers records when it is given one."""
         fl, d = Context._delim(delim)
-        if not fl:
+        if family == "grep" and not fl:
             raise ValueError("grep: the delimiter is one byte value")
-        fn, what, _ = Context._what(name, pattern)
-        return fn, what, GREP_INVERT if invert else 0, d
+        fn, what, _ = Context._what("bzh_" + family + route, pattern)
+        return fn, what, (GREP_INVERT if invert else 0) if family == "grep" else (MATCH_RECORDS if fl else 0), d
 
     def grep_set_context(self, before, after):
         """bzh_grep_set_context: sticky, read by every grep call when it begins"""
@@ -1499,53 +1496,58 @@ class Context:
             self.grep_set_context(0, 0)
         return (got[0], grep_context_rows(got[1])) if isinstance(got[1], np.ndarray) else got
 
+    def _host_call(self, family, data, pattern, delim, invert=False):
+        """the `call` of _scan for bzh_<family>; the arguments are looked at here, before any C call"""
+        src, n = _input(data)
+        fn, what, fl, d = self._scan_what(family, "", pattern, delim, invert)
+        return lambda o, c, e, m, g, t: fn(self._h, ptr(src), n, *what, fl, d, o, c, e, m, g, t, None, None)
+
+    def _index_call(self, family, comp, entries, pattern, points, delim, invert=False):
+        """... for bzh_<family>_index"""
+        e, p = _entries(entries)
+        q, pp = _points_or_none(points)
+        src, n = _input(comp)
+        fn, what, fl, d = self._scan_what(family, "_index", pattern, delim, invert)
+        return lambda o, c, en, m, g, t: fn(self._h, ptr(src), n, p, e.size, pp, q.size, *what, fl, d, o, c, en, m, g, t)
+
+    def _scan_on_device(self, family, route, head, pattern, d_out, cap, room, delim, invert=False, flags=None, tail=()):
+        """the device variants, on integer device addresses: bzh_<family><route>(head..., what, flags, delim, d_out, cap, `room`
+        entries, counts, tail...); the bytes stay in the caller's device buffer -> (status, count, out_total, entries)"""
+        fn, what, fl, d = self._scan_what(family, route, pattern, delim, invert)
+        dtype, entp = self._ENTRIES[family]
+        got, total = ctypes.c_size_t(0), ctypes.c_uint64(0)
+        ent = np.zeros(max(room, 1), dtype=dtype)
+        st = fn(self._h, *head, *what, fl if flags is None else flags, d, ctypes.c_void_p(d_out), cap, ent.ctypes.data_as(entp) if room else None,
+                room, ctypes.byref(got), ctypes.byref(total), *tail)
+        return st, int(got.value), int(total.value), ent[:min(room, int(got.value))].copy()
+
+    def _scan_index_device(self, family, d_in, n, entries, pattern, d_out, cap, room, points, delim, invert=False):
+        e, p = _entries(entries)
+        q, pp = _points_or_none(points)
+        return self._scan_on_device(family, "_index_device", (ctypes.c_void_p(d_in), n, p, e.size, pp, q.size), pattern, d_out, cap, room, delim,
+                                    invert)
+
     def grep(self, data, pattern, delim=b"\n", invert=False, count_only=False, before=0, after=0):
         """bzh_grep: the records of the decoded bytes of `data` that hold `pattern` -> (bytes, entries), or (nrecs, out_total)"""
-        a = np.frombuffer(data, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
-        fn, what, fl, d = self._grep_what("bzh_grep", pattern, delim, invert)
-        return self._grep_with_context(before, after, lambda: self._grep(
-            lambda o, c, e, m, g, t: fn(self._h, ptr(src), n, *what, fl, d, o, c, e, m, g, t, None, None), count_only))
+        call = self._host_call("grep", data, pattern, delim, invert)
+        return self._grep_with_context(before, after, lambda: self._grep(call, count_only))
 
     def grep_index(self, comp, entries, pattern, points=None, delim=b"\n", invert=False, count_only=False, before=0, after=0):
         """bzh_grep_index over the whole indexed input `comp` -> as grep"""
-        e, p = _entries(entries)
-        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
-        a = np.frombuffer(comp, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
-        fn, what, fl, d = self._grep_what("bzh_grep_index", pattern, delim, invert)
-        return self._grep_with_context(before, after, lambda: self._grep(
-            lambda o, c, en, m, g, t: fn(self._h, ptr(src), n, p, e.size, pp, q.size, *what, fl, d, o, c, en, m, g, t), count_only))
-
-    def _grep_device(self, call, room):
-        """the device variants: the bytes stay in the caller's device buffer -> (status, nrecs, out_total, entries)"""
-        got, total = ctypes.c_size_t(0), ctypes.c_uint64(0)
-        ent = np.zeros(max(room, 1), dtype=GREP_ENTRY_DTYPE)
-        st = call(ent.ctypes.data_as(grepp) if room else None, room, ctypes.byref(got), ctypes.byref(total))
-        return st, int(got.value), int(total.value), ent[:min(room, int(got.value))].copy()
+        call = self._index_call("grep", comp, entries, pattern, points, delim, invert)
+        return self._grep_with_context(before, after, lambda: self._grep(call, count_only))
 
     def grep_raw_device(self, d_raw, n, pattern, d_out, cap, room, delim=b"\n", invert=False, flags=None):
         """bzh_grep_raw_device on integer device addresses; `room` entries -> (status, nrecs, out_total, entries)"""
-        fn, what, fl, d = self._grep_what("bzh_grep_raw_device", pattern, delim, invert)
-        fl = fl if flags is None else flags
-        return self._grep_device(lambda e, m, g, t: fn(self._h, ctypes.c_void_p(d_raw), n, *what, fl, d, ctypes.c_void_p(d_out), cap, e, m, g, t),
-                                 room)
+        return self._scan_on_device("grep", "_raw_device", (ctypes.c_void_p(d_raw), n), pattern, d_out, cap, room, delim, invert, flags)
 
     def grep_device(self, d_in, n, pattern, d_out, cap, room, delim=b"\n", invert=False):
         """bzh_grep_device on integer device addresses; `room` entries -> (status, nrecs, out_total, entries)"""
-        fn, what, fl, d = self._grep_what("bzh_grep_device", pattern, delim, invert)
-        return self._grep_device(lambda e, m, g, t: fn(self._h, ctypes.c_void_p(d_in), n, *what, fl, d, ctypes.c_void_p(d_out), cap, e, m, g, t,
-                                                       None, None), room)
+        return self._scan_on_device("grep", "_device", (ctypes.c_void_p(d_in), n), pattern, d_out, cap, room, delim, invert, tail=(None, None))
 
     def grep_index_device(self, d_in, n, entries, pattern, d_out, cap, room, points=None, delim=b"\n", invert=False):
         """bzh_grep_index_device on integer device addresses; `room` entries -> (status, nrecs, out_total, entries)"""
-        e, p = _entries(entries)
-        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
-        fn, what, fl, d = self._grep_what("bzh_grep_index_device", pattern, delim, invert)
-        return self._grep_device(lambda en, m, g, t: fn(self._h, ctypes.c_void_p(d_in), n, p, e.size, pp, q.size, *what, fl, d,
-                                                        ctypes.c_void_p(d_out), cap, en, m, g, t), room)
+        return self._scan_index_device("grep", d_in, n, entries, pattern, d_out, cap, room, points, delim, invert)
 
     def grep_stats(self):
         s = GrepStats()
@@ -1557,78 +1559,26 @@ class Context:
         self.check(lib().bzh_get_grep_context_stats(self._h, ctypes.byref(s)))
         return s.as_dict()
 
-    # ---- the matched parts alone: the selected matches' bytes and their entries (MATCH_DTYPE) -----------------------------------
-    def _match(self, call, count_only=False):
-        """_grep for bzh_match*: call(out pointer, cap, entries pointer, max, nmatches reference, out_total reference) -> status"""
-        got, total = ctypes.c_size_t(0), ctypes.c_uint64(0)
-        if count_only:
-            self.check(call(None, 0, None, 0, ctypes.byref(got), ctypes.byref(total)))
-            return int(got.value), int(total.value)
-        cap, room = self.GREP_GUESS
-        for _ in range(2):
-            out = np.empty(max(cap, 1), dtype=np.uint8)
-            ent = np.zeros(max(room, 1), dtype=MATCH_DTYPE)
-            st = call(ptr(out), cap, ent.ctypes.data_as(matchp), room, ctypes.byref(got), ctypes.byref(total))
-            if st == -4 and (total.value > cap or got.value > room):
-                cap, room = int(total.value), int(got.value)
-                continue
-            self.check(st)
-            return out[:int(total.value)].tobytes(), ent[:int(got.value)].copy()
-        raise BzhError(-5, "match: the second call selected more than the first")
-
-    @staticmethod
-    def _match_what(name, pattern, delim):
-        """(the C call, the arguments that name what is looked for, flags, delimiter); delim None: no record numbers"""
-        fl, d = Context._delim(delim)
-        fn, what, _ = Context._what(name, pattern)
-        return fn, what, MATCH_RECORDS if fl else 0, d
-
     def matches(self, data, pattern, delim=None, count_only=False):
         """bzh_match: the non-overlapping leftmost-longest matches of `pattern` in the decoded bytes of `data` -> (bytes, entries),
-        or (nmatches, out_total)"""
-        a = np.frombuffer(data, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
-        fn, what, fl, d = self._match_what("bzh_match", pattern, delim)
-        return self._match(lambda o, c, e, m, g, t: fn(self._h, ptr(src), n, *what, fl, d, o, c, e, m, g, t, None, None), count_only)
+        or (nmatches, out_total); delim None: no record numbers"""
+        return self._match(self._host_call("match", data, pattern, delim), count_only)
 
     def matches_index(self, comp, entries, pattern, points=None, delim=None, count_only=False):
         """bzh_match_index over the whole indexed input `comp` -> as matches"""
-        e, p = _entries(entries)
-        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
-        a = np.frombuffer(comp, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
-        fn, what, fl, d = self._match_what("bzh_match_index", pattern, delim)
-        return self._match(lambda o, c, en, m, g, t: fn(self._h, ptr(src), n, p, e.size, pp, q.size, *what, fl, d, o, c, en, m, g, t), count_only)
-
-    def _match_device(self, call, room):
-        """the device variants: the bytes stay in the caller's device buffer -> (status, nmatches, out_total, entries)"""
-        got, total = ctypes.c_size_t(0), ctypes.c_uint64(0)
-        ent = np.zeros(max(room, 1), dtype=MATCH_DTYPE)
-        st = call(ent.ctypes.data_as(matchp) if room else None, room, ctypes.byref(got), ctypes.byref(total))
-        return st, int(got.value), int(total.value), ent[:min(room, int(got.value))].copy()
+        return self._match(self._index_call("match", comp, entries, pattern, points, delim), count_only)
 
     def match_raw_device(self, d_raw, n, pattern, d_out, cap, room, delim=None, flags=None):
         """bzh_match_raw_device on integer device addresses; `room` entries -> (status, nmatches, out_total, entries)"""
-        fn, what, fl, d = self._match_what("bzh_match_raw_device", pattern, delim)
-        fl = fl if flags is None else flags
-        return self._match_device(lambda e, m, g, t: fn(self._h, ctypes.c_void_p(d_raw), n, *what, fl, d, ctypes.c_void_p(d_out), cap, e, m, g, t),
-                                  room)
+        return self._scan_on_device("match", "_raw_device", (ctypes.c_void_p(d_raw), n), pattern, d_out, cap, room, delim, flags=flags)
 
     def match_device(self, d_in, n, pattern, d_out, cap, room, delim=None):
         """bzh_match_device on integer device addresses; `room` entries -> (status, nmatches, out_total, entries)"""
-        fn, what, fl, d = self._match_what("bzh_match_device", pattern, delim)
-        return self._match_device(lambda e, m, g, t: fn(self._h, ctypes.c_void_p(d_in), n, *what, fl, d, ctypes.c_void_p(d_out), cap, e, m, g, t,
-                                                        None, None), room)
+        return self._scan_on_device("match", "_device", (ctypes.c_void_p(d_in), n), pattern, d_out, cap, room, delim, tail=(None, None))
 
     def match_index_device(self, d_in, n, entries, pattern, d_out, cap, room, points=None, delim=None):
         """bzh_match_index_device on integer device addresses; `room` entries -> (status, nmatches, out_total, entries)"""
-        e, p = _entries(entries)
-        q, pp = _points(points) if points is not None else (np.empty(0, SYNC_DTYPE), None)
-        fn, what, fl, d = self._match_what("bzh_match_index_device", pattern, delim)
-        return self._match_device(lambda en, m, g, t: fn(self._h, ctypes.c_void_p(d_in), n, p, e.size, pp, q.size, *what, fl, d,
-                                                         ctypes.c_void_p(d_out), cap, en, m, g, t), room)
+        return self._scan_index_device("match", d_in, n, entries, pattern, d_out, cap, room, points, delim)
 
     def match_stats(self):
         s = MatchStats()
@@ -1647,9 +1597,7 @@ class Context:
 
     def decode_scan(self, data):
         """bzh_decode_scan -> [(bit position, kind)] of every block (0) and footer (1) magic in `data`, ascending"""
-        a = np.frombuffer(data, dtype=np.uint8)
-        n = a.size
-        src = np.ascontiguousarray(a) if n else np.zeros(1, np.uint8)
+        src, n = _input(data)
         cnt = ctypes.c_size_t(0)
         cap = 1024
         while True:

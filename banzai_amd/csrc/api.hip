@@ -300,14 +300,18 @@ extern "C" int bzh_debug_fault(bzh_ctx *ctx, int kind)
     });
 }
 
-extern "C" int bzh_get_stats(const bzh_ctx *ctx, bzh_stats *out)
+// what every bzh_get_*_stats call does: a copy of one block of the context's statistics
+template <typename T>
+static int stats_get(const bzh_ctx *ctx, T bzh_ctx::*block, T *out)
 {
     return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
     if (!ctx || !out) return BZH_E_ARG;
-    *out = ctx->stats;
+    *out = ctx->*block;
     return BZH_OK;
     });
 }
+
+extern "C" int bzh_get_stats(const bzh_ctx *ctx, bzh_stats *out) { return stats_get(ctx, &bzh_ctx::stats, out); }
 
 static void kstats_reset(bzh_ctx *ctx, bool keep_plan = false) // (keep_plan: the plan's classes stay in the table)
 {
@@ -1877,133 +1881,125 @@ extern "C" int bzh_decode_records(bzh_ctx *ctx, const uint8_t *in, size_t n, uin
     });
 }
 
-// ---- search (search.hip: the kernel, the passes over a window, the staging; the full search rides on decode_chain_run, the range
-// search on decode_range_sink_run, both as a WindowSink: decode.hip; the windows: search_plan.h)
-// the pattern and the flags of a search or a grep: `who` names the call, `flag` / `flag_name` the one flag it defines
-static int scan_args(bzh_ctx *ctx, const char *who, size_t plen, unsigned flags, unsigned flag, const char *flag_name)
-{
-    if (plen == 0 || plen > BZH_SEARCH_MAX_PATTERN) {
-        bzh_set_error(ctx, "%s: a pattern of %zu bytes, outside 1..%d", who, plen, BZH_SEARCH_MAX_PATTERN);
-        return BZH_E_ARG;
-    }
-    if (flags & ~flag) {
-        bzh_set_error(ctx, "%s: flags 0x%x, of which only %s is defined", who, flags, flag_name);
-        return BZH_E_ARG;
-    }
-    return BZH_OK;
-}
-
-// What a search or a grep looks for: a byte string, or a compiled set (bzh_*_patset*).  Every entry point below is one body for
-// both; the public calls only say which.
-struct ScanWhat {
-    const uint8_t *pat;
-    size_t plen;
-    const bzh_patset *set;
-    bool is_set;
-    bool given() const { return is_set ? set != nullptr : pat != nullptr; }
+// ---- search, grep, match (search.hip, grep.hip, match.hip: the kernels, the passes over a window, the staging and the carry,
+// each as a ScanSink: common.h; the windows: search_plan.h, grep_plan.h, match_plan.h).  Five routes take decoded or compressed
+// bytes to a sink, whichever it is: decoded bytes in HBM, the full decode (decode_chain_run) and the indexed one
+// (decode_range_sink_run) from the device, and the latter two from the host.  A family is a sink type and a ScanFamily; every
+// public call makes its sink and names its route.
+struct ScanFamily {
+    const char *name;      // in the messages
+    unsigned flag;         // the one flag it defines
+    const char *flag_name;
+    bool bytes;            // it writes bytes: out_total belongs to every call, the output buffer is 4-byte aligned
+    void (*clear)(bzh_ctx *); // the statistics of its last call
 };
+static void search_stats_clear(bzh_ctx *c) { memset(&c->sstats, 0, sizeof c->sstats); }
+static void grep_stats_clear(bzh_ctx *c) { memset(&c->gstats, 0, sizeof c->gstats), memset(&c->gcstats, 0, sizeof c->gcstats); }
+static void match_stats_clear(bzh_ctx *c) { memset(&c->mtstats, 0, sizeof c->mtstats); }
+static const ScanFamily SEARCH = {"search", BZH_SEARCH_RECORDS, "BZH_SEARCH_RECORDS", false, search_stats_clear};
+static const ScanFamily GREP = {"grep", BZH_GREP_INVERT, "BZH_GREP_INVERT", true, grep_stats_clear};
+static const ScanFamily MATCH = {"match", BZH_MATCH_RECORDS, "BZH_MATCH_RECORDS", true, match_stats_clear};
 static ScanWhat what_pat(const uint8_t *pat, size_t plen) { return ScanWhat{pat, plen, nullptr, false}; }
 static ScanWhat what_set(const bzh_patset *set) { return ScanWhat{nullptr, 0, set, true}; }
-static int scan_args(bzh_ctx *ctx, const char *who, const ScanWhat &q, unsigned flags, unsigned flag, const char *flag_name)
+
+// The checks every call makes first, in this order: the pointers (nothing has been written yet), then the caller's counts are
+// zeroed, then the pattern's length or the device of a set, the flags, the alignment of the output.  Behind them the statistics
+// are fresh and the sink is armed.
+static int scan_begin(bzh_ctx *ctx, const ScanFamily &f, ScanSink &s, size_t *count, uint64_t *out_total)
 {
-    if (!q.is_set) return scan_args(ctx, who, q.plen, flags, flag, flag_name);
-    if (q.set->device != ctx->device) {
-        bzh_set_error(ctx, "%s: the pattern set lies on device %d, the context on device %d", who, q.set->device, ctx->device);
+    const ScanArgs &a = s.args;
+    if (!a.what.given() || !count || (f.bytes && !out_total) || (!a.out && a.cap) || (!a.ent && a.max)) return BZH_E_ARG;
+    *count = 0;
+    if (out_total) *out_total = 0;
+    if (a.what.is_set && a.what.set->device != ctx->device) {
+        bzh_set_error(ctx, "%s: the pattern set lies on device %d, the context on device %d", f.name, a.what.set->device, ctx->device);
         return BZH_E_ARG;
     }
-    return scan_args(ctx, who, 1, flags, flag, flag_name);
-}
-static SearchSink search_sink(const ScanWhat &q, unsigned flags, uint8_t delim, void *hits, size_t max)
-{
-    return q.is_set ? SearchSink(q.set, flags, delim, (bzh_set_hit *)hits, max) : SearchSink(q.pat, q.plen, flags, delim, (bzh_hit *)hits, max);
-}
-static GrepSink grep_sink(const bzh_ctx *ctx, const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap, bzh_grep_entry *ent, size_t max)
-{
-    GrepSink g = q.is_set ? GrepSink(q.set, flags, delim, d_out, cap, ent, max) : GrepSink(q.pat, q.plen, flags, delim, d_out, cap, ent, max);
-    g.set_context(ctx->grep_before, ctx->grep_after);
-    return g;
-}
-
-// the checks every search makes first; a sink is made of arguments that have passed them
-static int search_begin(bzh_ctx *ctx, const ScanWhat &q, unsigned flags, void *hits, size_t max, size_t *nhits)
-{
-    if (!q.given() || !nhits || (!hits && max)) return BZH_E_ARG;
-    *nhits = 0;
-    BZH_TRY(scan_args(ctx, "search", q, flags, BZH_SEARCH_RECORDS, "BZH_SEARCH_RECORDS"));
-    memset(&ctx->sstats, 0, sizeof ctx->sstats);
+    if (!a.what.is_set && (a.what.plen == 0 || a.what.plen > BZH_SEARCH_MAX_PATTERN)) {
+        bzh_set_error(ctx, "%s: a pattern of %zu bytes, outside 1..%d", f.name, a.what.plen, BZH_SEARCH_MAX_PATTERN);
+        return BZH_E_ARG;
+    }
+    if (a.flags & ~f.flag) {
+        bzh_set_error(ctx, "%s: flags 0x%x, of which only %s is defined", f.name, a.flags, f.flag_name);
+        return BZH_E_ARG;
+    }
+    if (f.bytes && ((uintptr_t)a.out & 3u)) {
+        bzh_set_error(ctx, "%s: the output buffer is not 4-byte aligned", f.name);
+        return BZH_E_ARG;
+    }
+    f.clear(ctx);
+    s.arm(ctx);
     return BZH_OK;
 }
 
-// rc: the status of the work.  The hits follow the stream to the caller's array: whatever the status, nothing is on its way to it
-// when the call returns.
-static int search_end(bzh_ctx *ctx, const SearchSink &sink, int rc, size_t *nhits)
+// rc: the status of the windows.  Behind them what the sink held back; hits, bytes and entries follow the stream: whatever the
+// status, nothing is on its way to the caller's arrays when the call returns.
+static int scan_end(bzh_ctx *ctx, ScanSink &s, const DecodeCall &call, int rc, size_t *count, uint64_t *out_total)
 {
+    if (rc == BZH_OK) rc = s.finish(ctx);
+    rc = decode_call_end(ctx, call, rc);
     HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
     if (rc != BZH_OK) return rc;
-    *nhits = (size_t)sink.walk.rank;
-    if (sink.walk.rank > sink.max && sink.max) {
-        bzh_set_error(ctx, "search: %llu hits, room for %llu", (unsigned long long)sink.walk.rank, (unsigned long long)sink.max);
-        return BZH_E_CAP;
-    }
-    return BZH_OK;
+    return s.report(ctx, count, out_total);
 }
 
-static int search_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, void *hits, size_t max,
-                             size_t *nhits)
+static int scan_raw_device(bzh_ctx *ctx, const ScanFamily &f, ScanSink &s, const void *d_raw, size_t n, size_t *count, uint64_t *out_total)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_raw && n)) return BZH_E_ARG;
-    BZH_TRY(search_begin(ctx, q, flags, hits, max, nhits));
-    SearchSink sink = search_sink(q, flags, delim, hits, max);
+    BZH_TRY(scan_begin(ctx, f, s, count, out_total));
     if ((uintptr_t)d_raw & 15u) {
-        bzh_set_error(ctx, "search: the buffer is not 16-byte aligned");
+        bzh_set_error(ctx, "%s: the buffer is not 16-byte aligned", f.name);
         return BZH_E_ARG;
     }
     DecodeCall call;
     BZH_TRY(decode_call_begin(ctx, n, call));
-    int rc = search_raw_run(ctx, sink, (const uint8_t *)d_raw, n);
-    rc = decode_call_end(ctx, call, rc);
-    return search_end(ctx, sink, rc, nhits);
+    const int rc = s.raw(ctx, (const uint8_t *)d_raw, n);
+    return scan_end(ctx, s, call, rc, count, out_total);
     });
 }
 
-static int search_device(bzh_ctx *ctx, const void *d_in, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, void *hits, size_t max,
-                         size_t *nhits, uint64_t *out_total, size_t *consumed)
+static int scan_device(bzh_ctx *ctx, const ScanFamily &f, ScanSink &s, const void *d_in, size_t n, size_t *count, uint64_t *out_total,
+                       uint64_t *decoded_total, size_t *consumed)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_in && n)) return BZH_E_ARG;
-    BZH_TRY(search_begin(ctx, q, flags, hits, max, nhits));
-    SearchSink sink = search_sink(q, flags, delim, hits, max);
+    BZH_TRY(scan_begin(ctx, f, s, count, out_total));
     DecodeCall call;
     BZH_TRY(decode_call_begin(ctx, n, call));
-    if (out_total) *out_total = 0;
+    if (decoded_total) *decoded_total = 0;
     if (consumed) *consumed = 0;
     std::vector<uint64_t> cands;
     BZH_TRY(decode_call_scan(ctx, call, d_in, n, cands));
     size_t total = 0;
-    int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, nullptr, nullptr, nullptr, &sink);
-    if (out_total) *out_total = total;
-    if (rc == BZH_OK) rc = search_finish(ctx, sink);
-    rc = decode_call_end(ctx, call, rc);
-    return search_end(ctx, sink, rc, nhits);
+    const int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, nullptr, nullptr, nullptr, &s);
+    if (decoded_total) *decoded_total = total;
+    return scan_end(ctx, s, call, rc, count, out_total);
     });
 }
 
-static int search_host(bzh_ctx *ctx, const uint8_t *in, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, void *hits, size_t max,
-                       size_t *nhits, uint64_t *out_total, size_t *consumed)
+// the host variants: room for the bytes in the staging buffer of the output (asked for with no room: a buffer all the same)
+static size_t scan_stage_room(const void *out, size_t cap) { return out ? std::max<size_t>(cap, 16) : 0; }
+
+// ... the sink's output moves to it, and the bytes come back only behind BZH_OK
+static int scan_host(bzh_ctx *ctx, const ScanFamily &f, ScanSink &s, const uint8_t *in, size_t n, size_t *count, uint64_t *out_total,
+                     uint64_t *decoded_total, size_t *consumed)
 {
     return bzh_guard(ctx, [&]() -> int {
+    uint8_t *const out = (uint8_t *)s.args.out;
     if (ctx) stream_join(ctx);
-    if (!ctx || (!in && n)) return BZH_E_ARG;
+    if (!ctx || (!in && n) || (!out && s.args.cap)) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BZH_TRY(decode_stage(ctx, in, n));
-    return search_device(ctx, ctx->d_stage_in, n, q, flags, delim, hits, max, nhits, out_total, consumed);
+    BZH_TRY(decode_stage(ctx, in, n, scan_stage_room(out, s.args.cap)));
+    s.args.out = out ? ctx->d_stage_out.p : nullptr;
+    BZH_TRY(scan_device(ctx, f, s, ctx->d_stage_in, n, count, out_total, decoded_total, consumed));
+    return f.bytes ? decode_unstage(ctx, out, out ? (size_t)*out_total : 0) : BZH_OK;
     });
 }
 
-// the checks both variants of the range search make before any arithmetic on the arrays
+// the checks both variants of an indexed call make before any arithmetic on the arrays (flags: BZH_SEARCH_RECORDS asks for the table)
 static int search_range_args(bzh_ctx *ctx, const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts, size_t npts,
                              const uint64_t *rec_cum, unsigned flags)
 {
@@ -2026,120 +2022,152 @@ static int search_range_args(bzh_ctx *ctx, const bzh_index_entry *idx, size_t co
     return BZH_OK;
 }
 
-// The range a range search DECODES: the wanted one, widened by the bytes an automaton with assertions looks at in front of it and
-// behind it (decode_range_sink_run widens alike, and clips to the output); the hits stay inside the wanted range.
-static void search_decoded_range(const ScanWhat &q, uint64_t off, uint64_t len, uint64_t *w_off, uint64_t *w_len)
+// The part of the output an indexed call is about, with the record table that numbers its records: a range search's.  The indexed
+// grep and match take the whole output and no table: null.
+struct ScanRange {
+    uint64_t in_byte_base;
+    const uint64_t *rec_cum;
+    uint64_t off, len;
+};
+
+// The blocks a range search DECODES, and the bytes of the input that hold them: those of the wanted range, widened by the bytes an
+// automaton with assertions looks at in front of it and behind it (decode_range_sink_run widens alike, and clips to the output);
+// the hits stay inside the wanted range.
+static int scan_range_span(const ScanWhat &q, const ScanRange &r, const bzh_index_entry *idx, size_t count, size_t *blocks, uint64_t *lo,
+                           uint64_t *hi)
 {
-    *w_off = off, *w_len = len;
-    if (!q.is_set || !q.set->looks()) return;
-    const uint64_t back = std::min<uint64_t>(off, q.set->look.look_behind), more = back + q.set->look.look_ahead;
-    *w_off = off - back;
-    *w_len = len > ~0ull - more ? ~0ull : len + more;
+    uint64_t w_off = r.off, w_len = r.len;
+    if (q.is_set && q.set->looks()) {
+        const uint64_t back = std::min<uint64_t>(r.off, q.set->look.look_behind), more = back + q.set->look.look_ahead;
+        w_off = r.off - back;
+        w_len = r.len > ~0ull - more ? ~0ull : r.len + more;
+    }
+    size_t first = 0, last = 0;
+    BZH_TRY(bzh_index_span(idx, count, w_off, w_len, &first, &last, lo, hi));
+    *blocks = last - first;
+    return BZH_OK;
 }
 
-static int search_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
-                               const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len, const ScanWhat &q,
-                               unsigned flags, uint8_t delim, void *hits, size_t max, size_t *nhits)
+static int scan_index_device(bzh_ctx *ctx, const ScanFamily &f, ScanSink &s, const void *d_in, size_t n, const bzh_index_entry *idx,
+                             size_t count, const bzh_sync_point *pts, size_t npts, const ScanRange *range, size_t *found, uint64_t *out_total)
 {
     return bzh_guard(ctx, [&]() -> int {
     if (ctx) stream_join(ctx);
     if (!ctx || (!d_in && n) || (!idx && count) || (!pts && npts)) return BZH_E_ARG;
-    BZH_TRY(search_begin(ctx, q, flags, hits, max, nhits));
-    SearchSink sink = search_sink(q, flags, delim, hits, max);
+    BZH_TRY(scan_begin(ctx, f, s, found, out_total));
     DecodeCall call;
     BZH_TRY(decode_call_begin(ctx, n, call));
-    BZH_TRY(search_range_args(ctx, idx, count, pts, npts, rec_cum, flags));
-    size_t first = 0, last = 0;
-    uint64_t lo, hi, w_off, w_len;
-    search_decoded_range(q, off, len, &w_off, &w_len);
-    BZH_TRY(bzh_index_span(idx, count, w_off, w_len, &first, &last, &lo, &hi));
-    BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(last - first, 1), ctx->max_batch)));
-    int rc = decode_range_sink_run(ctx, (const uint8_t *)d_in, n, in_byte_base, idx, count, pts, npts, sink.records ? rec_cum : nullptr, off, len,
-                                   sink);
-    if (rc == BZH_OK) rc = search_finish(ctx, sink);
-    rc = decode_call_end(ctx, call, rc);
-    return search_end(ctx, sink, rc, nhits);
+    static const ScanRange whole = {0, nullptr, 0, ~0ull};
+    const ScanRange &r = range ? *range : whole;
+    const unsigned records = range ? s.args.flags & BZH_SEARCH_RECORDS : 0;
+    BZH_TRY(search_range_args(ctx, idx, count, pts, npts, r.rec_cum, records));
+    size_t blocks = count; // the arena: for the blocks of the range, or of the index
+    uint64_t lo, hi;
+    if (range) BZH_TRY(scan_range_span(s.args.what, r, idx, count, &blocks, &lo, &hi));
+    BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(blocks, 1), ctx->max_batch)));
+    const int rc = decode_range_sink_run(ctx, (const uint8_t *)d_in, n, r.in_byte_base, idx, count, pts, npts, records ? r.rec_cum : nullptr,
+                                         r.off, r.len, s);
+    return scan_end(ctx, s, call, rc, found, out_total);
     });
 }
 
-static int search_range_host(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
-                             const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len, const ScanWhat &q,
-                             unsigned flags, uint8_t delim, void *hits, size_t max, size_t *nhits)
+// Of a range only the hull of its blocks goes up, so its arguments are checked here too: nothing goes up for a call that is
+// refused.  Without a range the whole input goes up, as in scan_host.
+static int scan_index_host(bzh_ctx *ctx, const ScanFamily &f, ScanSink &s, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count,
+                           const bzh_sync_point *pts, size_t npts, const ScanRange *range, size_t *found, uint64_t *out_total)
 {
     return bzh_guard(ctx, [&]() -> int {
+    uint8_t *const out = (uint8_t *)s.args.out;
     if (ctx) stream_join(ctx);
-    if (!ctx || (!in && n) || (!idx && count) || (!pts && npts)) return BZH_E_ARG;
+    if (!ctx || (!in && n) || (!idx && count) || (!pts && npts) || (!out && s.args.cap)) return BZH_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BZH_TRY(search_begin(ctx, q, flags, hits, max, nhits)); // (the arguments are checked here too: nothing goes up for a call that is refused)
-    BZH_TRY(search_range_args(ctx, idx, count, pts, npts, rec_cum, flags));
-    // only the span goes up
-    size_t first = 0, last = 0;
-    uint64_t lo = 0, hi = 0, base;
-    size_t un;
-    uint64_t w_off, w_len;
-    search_decoded_range(q, off, len, &w_off, &w_len);
-    BZH_TRY(bzh_index_span(idx, count, w_off, w_len, &first, &last, &lo, &hi)); // (the widened span: what the device variant is to be handed)
-    BZH_TRY(decode_stage_hull(ctx, in, n, in_byte_base, lo, hi, 0, &base, &un));
-    return search_range_device(ctx, ctx->d_stage_in, un, base, idx, count, pts, npts, rec_cum, off, len, q, flags, delim, hits, max, nhits);
+    if (range) {
+        BZH_TRY(scan_begin(ctx, f, s, found, out_total));
+        BZH_TRY(search_range_args(ctx, idx, count, pts, npts, range->rec_cum, s.args.flags));
+        size_t blocks, un;
+        uint64_t lo = 0, hi = 0;
+        BZH_TRY(scan_range_span(s.args.what, *range, idx, count, &blocks, &lo, &hi)); // (the widened span: what the device variant is to be handed)
+        ScanRange staged = *range;
+        BZH_TRY(decode_stage_hull(ctx, in, n, range->in_byte_base, lo, hi, 0, &staged.in_byte_base, &un));
+        return scan_index_device(ctx, f, s, ctx->d_stage_in, un, idx, count, pts, npts, &staged, found, out_total);
+    }
+    BZH_TRY(decode_stage(ctx, in, n, scan_stage_room(out, s.args.cap)));
+    s.args.out = out ? ctx->d_stage_out.p : nullptr;
+    BZH_TRY(scan_index_device(ctx, f, s, ctx->d_stage_in, n, idx, count, pts, npts, nullptr, found, out_total));
+    return decode_unstage(ctx, out, out ? (size_t)*out_total : 0);
     });
 }
 
-// the public calls: a byte string, or a set
+// the public calls of the search: a byte string, or a set
 extern "C" int bzh_search_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
                                      bzh_hit *hits, size_t max, size_t *nhits)
 {
-    return search_raw_device(ctx, d_raw, n, what_pat(pat, plen), flags, delim, hits, max, nhits);
+    SearchSink s(what_pat(pat, plen), flags, delim, hits, max);
+    return scan_raw_device(ctx, SEARCH, s, d_raw, n, nhits, nullptr);
 }
 extern "C" int bzh_search_patset_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
                                             bzh_set_hit *hits, size_t max, size_t *nhits)
 {
-    return search_raw_device(ctx, d_raw, n, what_set(set), flags, delim, hits, max, nhits);
+    SearchSink s(what_set(set), flags, delim, hits, max);
+    return scan_raw_device(ctx, SEARCH, s, d_raw, n, nhits, nullptr);
 }
 extern "C" int bzh_search_device(bzh_ctx *ctx, const void *d_in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
                                  bzh_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed)
 {
-    return search_device(ctx, d_in, n, what_pat(pat, plen), flags, delim, hits, max, nhits, out_total, consumed);
+    SearchSink s(what_pat(pat, plen), flags, delim, hits, max);
+    return scan_device(ctx, SEARCH, s, d_in, n, nhits, nullptr, out_total, consumed);
 }
 extern "C" int bzh_search_patset_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
                                         bzh_set_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed)
 {
-    return search_device(ctx, d_in, n, what_set(set), flags, delim, hits, max, nhits, out_total, consumed);
+    SearchSink s(what_set(set), flags, delim, hits, max);
+    return scan_device(ctx, SEARCH, s, d_in, n, nhits, nullptr, out_total, consumed);
 }
 extern "C" int bzh_search(bzh_ctx *ctx, const uint8_t *in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
                           bzh_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed)
 {
-    return search_host(ctx, in, n, what_pat(pat, plen), flags, delim, hits, max, nhits, out_total, consumed);
+    SearchSink s(what_pat(pat, plen), flags, delim, hits, max);
+    return scan_host(ctx, SEARCH, s, in, n, nhits, nullptr, out_total, consumed);
 }
 extern "C" int bzh_search_patset(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
                                  bzh_set_hit *hits, size_t max, size_t *nhits, uint64_t *out_total, size_t *consumed)
 {
-    return search_host(ctx, in, n, what_set(set), flags, delim, hits, max, nhits, out_total, consumed);
+    SearchSink s(what_set(set), flags, delim, hits, max);
+    return scan_host(ctx, SEARCH, s, in, n, nhits, nullptr, out_total, consumed);
 }
 extern "C" int bzh_search_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
                                        size_t count, const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off,
                                        uint64_t len, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits,
                                        size_t max, size_t *nhits)
 {
-    return search_range_device(ctx, d_in, n, in_byte_base, idx, count, pts, npts, rec_cum, off, len, what_pat(pat, plen), flags, delim, hits, max, nhits);
+    SearchSink s(what_pat(pat, plen), flags, delim, hits, max);
+    const ScanRange range = {in_byte_base, rec_cum, off, len};
+    return scan_index_device(ctx, SEARCH, s, d_in, n, idx, count, pts, npts, &range, nhits, nullptr);
 }
 extern "C" int bzh_search_patset_range_device(bzh_ctx *ctx, const void *d_in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx,
                                               size_t count, const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off,
                                               uint64_t len, const bzh_patset *set, unsigned flags, uint8_t delim, bzh_set_hit *hits, size_t max,
                                               size_t *nhits)
 {
-    return search_range_device(ctx, d_in, n, in_byte_base, idx, count, pts, npts, rec_cum, off, len, what_set(set), flags, delim, hits, max, nhits);
+    SearchSink s(what_set(set), flags, delim, hits, max);
+    const ScanRange range = {in_byte_base, rec_cum, off, len};
+    return scan_index_device(ctx, SEARCH, s, d_in, n, idx, count, pts, npts, &range, nhits, nullptr);
 }
 extern "C" int bzh_search_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
                                 const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len,
                                 const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, bzh_hit *hits, size_t max, size_t *nhits)
 {
-    return search_range_host(ctx, in, n, in_byte_base, idx, count, pts, npts, rec_cum, off, len, what_pat(pat, plen), flags, delim, hits, max, nhits);
+    SearchSink s(what_pat(pat, plen), flags, delim, hits, max);
+    const ScanRange range = {in_byte_base, rec_cum, off, len};
+    return scan_index_host(ctx, SEARCH, s, in, n, idx, count, pts, npts, &range, nhits, nullptr);
 }
 extern "C" int bzh_search_patset_range(bzh_ctx *ctx, const uint8_t *in, size_t n, uint64_t in_byte_base, const bzh_index_entry *idx, size_t count,
                                        const bzh_sync_point *pts, size_t npts, const uint64_t *rec_cum, uint64_t off, uint64_t len,
                                        const bzh_patset *set, unsigned flags, uint8_t delim, bzh_set_hit *hits, size_t max, size_t *nhits)
 {
-    return search_range_host(ctx, in, n, in_byte_base, idx, count, pts, npts, rec_cum, off, len, what_set(set), flags, delim, hits, max, nhits);
+    SearchSink s(what_set(set), flags, delim, hits, max);
+    const ScanRange range = {in_byte_base, rec_cum, off, len};
+    return scan_index_host(ctx, SEARCH, s, in, n, idx, count, pts, npts, &range, nhits, nullptr);
 }
 
 extern "C" int bzh_search_set_room(bzh_ctx *ctx, size_t bytes)
@@ -2155,212 +2183,79 @@ extern "C" int bzh_search_set_room(bzh_ctx *ctx, size_t bytes)
     });
 }
 
-extern "C" int bzh_get_search_stats(const bzh_ctx *ctx, bzh_search_stats *out)
-{
-    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
-    if (!ctx || !out) return BZH_E_ARG;
-    *out = ctx->sstats;
-    return BZH_OK;
-    });
-}
+extern "C" int bzh_get_search_stats(const bzh_ctx *ctx, bzh_search_stats *out) { return stats_get(ctx, &bzh_ctx::sstats, out); }
 
-// ---- grep (grep.hip: the kernels, the passes over a window, the staging and the carry; the full grep rides on decode_chain_run,
-// the indexed one on decode_range_sink_run, as a WindowSink of its own; the windows: grep_plan.h)
-// the checks every grep makes first; a sink is made of arguments that have passed them
-static int grep_begin(bzh_ctx *ctx, const ScanWhat &q, unsigned flags, void *d_out, size_t cap, bzh_grep_entry *ent, size_t max,
-                      size_t *nrecs, uint64_t *out_total)
-{
-    if (!q.given() || !nrecs || !out_total || (!d_out && cap) || (!ent && max)) return BZH_E_ARG;
-    *nrecs = 0;
-    *out_total = 0;
-    BZH_TRY(scan_args(ctx, "grep", q, flags, BZH_GREP_INVERT, "BZH_GREP_INVERT"));
-    if ((uintptr_t)d_out & 3u) {
-        bzh_set_error(ctx, "grep: the output buffer is not 4-byte aligned");
-        return BZH_E_ARG;
-    }
-    memset(&ctx->gstats, 0, sizeof ctx->gstats);
-    memset(&ctx->gcstats, 0, sizeof ctx->gcstats);
-    return BZH_OK;
-}
-
-// rc: the status of the windows.  Behind them the bytes held back and the open tail (grep_finish); bytes and entries follow the
-// stream: whatever the status, nothing is on its way to the caller's arrays when the call returns.
-static int grep_end(bzh_ctx *ctx, GrepSink &g, const DecodeCall &call, int rc, size_t *nrecs, uint64_t *out_total)
-{
-    bool tail_entry = false;
-    if (rc == BZH_OK) rc = grep_finish(ctx, g, &tail_entry);
-    rc = decode_call_end(ctx, call, rc);
-    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
-    if (rc != BZH_OK) return rc;
-    if (tail_entry) memcpy(&g.ent[g.sel() - 1], &g.tail_ent, sizeof g.tail_ent);
-    *nrecs = (size_t)g.sel();
-    *out_total = g.out_bytes();
-    if (g.overflow()) {
-        bzh_set_error(ctx, "grep: %llu records of %llu bytes, room for %llu and %llu", (unsigned long long)g.sel(),
-                      (unsigned long long)g.out_bytes(), (unsigned long long)g.walk.max, (unsigned long long)g.walk.cap);
-        return BZH_E_CAP;
-    }
-    return BZH_OK;
-}
-
-static int grep_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap,
-                           bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
-{
-    return bzh_guard(ctx, [&]() -> int {
-    if (ctx) stream_join(ctx);
-    if (!ctx || (!d_raw && n)) return BZH_E_ARG;
-    BZH_TRY(grep_begin(ctx, q, flags, d_out, cap, ent, max, nrecs, out_total));
-    GrepSink g = grep_sink(ctx, q, flags, delim, d_out, cap, ent, max);
-    if ((uintptr_t)d_raw & 15u) {
-        bzh_set_error(ctx, "grep: the buffer is not 16-byte aligned");
-        return BZH_E_ARG;
-    }
-    DecodeCall call;
-    BZH_TRY(decode_call_begin(ctx, n, call));
-    const int rc = grep_raw_run(ctx, g, (const uint8_t *)d_raw, n);
-    return grep_end(ctx, g, call, rc, nrecs, out_total);
-    });
-}
-
-static int grep_device(bzh_ctx *ctx, const void *d_in, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap,
-                       bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total, uint64_t *decoded_total, size_t *consumed)
-{
-    return bzh_guard(ctx, [&]() -> int {
-    if (ctx) stream_join(ctx);
-    if (!ctx || (!d_in && n)) return BZH_E_ARG;
-    BZH_TRY(grep_begin(ctx, q, flags, d_out, cap, ent, max, nrecs, out_total));
-    GrepSink g = grep_sink(ctx, q, flags, delim, d_out, cap, ent, max);
-    DecodeCall call;
-    BZH_TRY(decode_call_begin(ctx, n, call));
-    if (decoded_total) *decoded_total = 0;
-    if (consumed) *consumed = 0;
-    std::vector<uint64_t> cands;
-    BZH_TRY(decode_call_scan(ctx, call, d_in, n, cands));
-    size_t total = 0;
-    const int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, nullptr, nullptr, nullptr, &g);
-    if (decoded_total) *decoded_total = total;
-    return grep_end(ctx, g, call, rc, nrecs, out_total);
-    });
-}
-
-// the host variants: room for the bytes in the staging buffer of the output (asked for with no room: a buffer all the same)
-static size_t grep_stage_room(const uint8_t *out, size_t cap) { return out ? std::max<size_t>(cap, 16) : 0; }
-
-static int grep_host(bzh_ctx *ctx, const uint8_t *in, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, uint8_t *out, size_t cap,
-                     bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total, uint64_t *decoded_total, size_t *consumed)
-{
-    return bzh_guard(ctx, [&]() -> int {
-    if (ctx) stream_join(ctx);
-    if (!ctx || (!in && n) || (!out && cap)) return BZH_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BZH_TRY(decode_stage(ctx, in, n, grep_stage_room(out, cap)));
-    BZH_TRY(grep_device(ctx, ctx->d_stage_in, n, q, flags, delim, out ? ctx->d_stage_out.p : nullptr, cap, ent, max, nrecs, out_total,
-                        decoded_total, consumed));
-    return decode_unstage(ctx, out, out ? (size_t)*out_total : 0);
-    });
-}
-
-static int grep_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts,
-                             size_t npts, const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap, bzh_grep_entry *ent, size_t max,
-                             size_t *nrecs, uint64_t *out_total)
-{
-    return bzh_guard(ctx, [&]() -> int {
-    if (ctx) stream_join(ctx);
-    if (!ctx || (!d_in && n) || (!idx && count) || (!pts && npts)) return BZH_E_ARG;
-    BZH_TRY(grep_begin(ctx, q, flags, d_out, cap, ent, max, nrecs, out_total));
-    GrepSink g = grep_sink(ctx, q, flags, delim, d_out, cap, ent, max);
-    DecodeCall call;
-    BZH_TRY(decode_call_begin(ctx, n, call));
-    BZH_TRY(search_range_args(ctx, idx, count, pts, npts, nullptr, 0));
-    BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(count, 1), ctx->max_batch)));
-    const int rc = decode_range_sink_run(ctx, (const uint8_t *)d_in, n, 0, idx, count, pts, npts, nullptr, 0, ~0ull, g);
-    return grep_end(ctx, g, call, rc, nrecs, out_total);
-    });
-}
-
-static int grep_index_host(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts,
-                           size_t npts, const ScanWhat &q, unsigned flags, uint8_t delim, uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max,
-                           size_t *nrecs, uint64_t *out_total)
-{
-    return bzh_guard(ctx, [&]() -> int {
-    if (ctx) stream_join(ctx);
-    if (!ctx || (!in && n) || (!idx && count) || (!pts && npts) || (!out && cap)) return BZH_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BZH_TRY(decode_stage(ctx, in, n, grep_stage_room(out, cap)));
-    BZH_TRY(grep_index_device(ctx, ctx->d_stage_in, n, idx, count, pts, npts, q, flags, delim, out ? ctx->d_stage_out.p : nullptr, cap, ent, max,
-                              nrecs, out_total));
-    return decode_unstage(ctx, out, out ? (size_t)*out_total : 0);
-    });
-}
-
-// the public calls: a byte string, or a set
+// ... of the grep (its context setting is read when the sink is armed)
 extern "C" int bzh_grep_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
                                    void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
 {
-    return grep_raw_device(ctx, d_raw, n, what_pat(pat, plen), flags, delim, d_out, cap, ent, max, nrecs, out_total);
+    GrepSink s(what_pat(pat, plen), flags, delim, d_out, cap, ent, max);
+    return scan_raw_device(ctx, GREP, s, d_raw, n, nrecs, out_total);
 }
 extern "C" int bzh_grep_patset_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
                                           void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
 {
-    return grep_raw_device(ctx, d_raw, n, what_set(set), flags, delim, d_out, cap, ent, max, nrecs, out_total);
+    GrepSink s(what_set(set), flags, delim, d_out, cap, ent, max);
+    return scan_raw_device(ctx, GREP, s, d_raw, n, nrecs, out_total);
 }
 extern "C" int bzh_grep_device(bzh_ctx *ctx, const void *d_in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
                                void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total,
                                uint64_t *decoded_total, size_t *consumed)
 {
-    return grep_device(ctx, d_in, n, what_pat(pat, plen), flags, delim, d_out, cap, ent, max, nrecs, out_total, decoded_total, consumed);
+    GrepSink s(what_pat(pat, plen), flags, delim, d_out, cap, ent, max);
+    return scan_device(ctx, GREP, s, d_in, n, nrecs, out_total, decoded_total, consumed);
 }
 extern "C" int bzh_grep_patset_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
                                       void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total,
                                       uint64_t *decoded_total, size_t *consumed)
 {
-    return grep_device(ctx, d_in, n, what_set(set), flags, delim, d_out, cap, ent, max, nrecs, out_total, decoded_total, consumed);
+    GrepSink s(what_set(set), flags, delim, d_out, cap, ent, max);
+    return scan_device(ctx, GREP, s, d_in, n, nrecs, out_total, decoded_total, consumed);
 }
 extern "C" int bzh_grep(bzh_ctx *ctx, const uint8_t *in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
                         uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total,
                         uint64_t *decoded_total, size_t *consumed)
 {
-    return grep_host(ctx, in, n, what_pat(pat, plen), flags, delim, out, cap, ent, max, nrecs, out_total, decoded_total, consumed);
+    GrepSink s(what_pat(pat, plen), flags, delim, out, cap, ent, max);
+    return scan_host(ctx, GREP, s, in, n, nrecs, out_total, decoded_total, consumed);
 }
 extern "C" int bzh_grep_patset(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim, uint8_t *out,
                                size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total, uint64_t *decoded_total,
                                size_t *consumed)
 {
-    return grep_host(ctx, in, n, what_set(set), flags, delim, out, cap, ent, max, nrecs, out_total, decoded_total, consumed);
+    GrepSink s(what_set(set), flags, delim, out, cap, ent, max);
+    return scan_host(ctx, GREP, s, in, n, nrecs, out_total, decoded_total, consumed);
 }
 extern "C" int bzh_grep_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count,
                                      const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
                                      void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
 {
-    return grep_index_device(ctx, d_in, n, idx, count, pts, npts, what_pat(pat, plen), flags, delim, d_out, cap, ent, max, nrecs, out_total);
+    GrepSink s(what_pat(pat, plen), flags, delim, d_out, cap, ent, max);
+    return scan_index_device(ctx, GREP, s, d_in, n, idx, count, pts, npts, nullptr, nrecs, out_total);
 }
 extern "C" int bzh_grep_patset_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count,
                                             const bzh_sync_point *pts, size_t npts, const bzh_patset *set, unsigned flags, uint8_t delim,
                                             void *d_out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
 {
-    return grep_index_device(ctx, d_in, n, idx, count, pts, npts, what_set(set), flags, delim, d_out, cap, ent, max, nrecs, out_total);
+    GrepSink s(what_set(set), flags, delim, d_out, cap, ent, max);
+    return scan_index_device(ctx, GREP, s, d_in, n, idx, count, pts, npts, nullptr, nrecs, out_total);
 }
 extern "C" int bzh_grep_index(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count,
                               const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
                               uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
 {
-    return grep_index_host(ctx, in, n, idx, count, pts, npts, what_pat(pat, plen), flags, delim, out, cap, ent, max, nrecs, out_total);
+    GrepSink s(what_pat(pat, plen), flags, delim, out, cap, ent, max);
+    return scan_index_host(ctx, GREP, s, in, n, idx, count, pts, npts, nullptr, nrecs, out_total);
 }
 extern "C" int bzh_grep_patset_index(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count,
                                      const bzh_sync_point *pts, size_t npts, const bzh_patset *set, unsigned flags, uint8_t delim, uint8_t *out,
                                      size_t cap, bzh_grep_entry *ent, size_t max, size_t *nrecs, uint64_t *out_total)
 {
-    return grep_index_host(ctx, in, n, idx, count, pts, npts, what_set(set), flags, delim, out, cap, ent, max, nrecs, out_total);
+    GrepSink s(what_set(set), flags, delim, out, cap, ent, max);
+    return scan_index_host(ctx, GREP, s, in, n, idx, count, pts, npts, nullptr, nrecs, out_total);
 }
 
-extern "C" int bzh_get_grep_stats(const bzh_ctx *ctx, bzh_grep_stats *out)
-{
-    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
-    if (!ctx || !out) return BZH_E_ARG;
-    *out = ctx->gstats;
-    return BZH_OK;
-    });
-}
+extern "C" int bzh_get_grep_stats(const bzh_ctx *ctx, bzh_grep_stats *out) { return stats_get(ctx, &bzh_ctx::gstats, out); }
 
 extern "C" int bzh_grep_set_context(bzh_ctx *ctx, uint32_t before, uint32_t after)
 {
@@ -2371,227 +2266,83 @@ extern "C" int bzh_grep_set_context(bzh_ctx *ctx, uint32_t before, uint32_t afte
     });
 }
 
-extern "C" int bzh_get_grep_context_stats(const bzh_ctx *ctx, bzh_grep_context_stats *out)
-{
-    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
-    if (!ctx || !out) return BZH_E_ARG;
-    *out = ctx->gcstats;
-    return BZH_OK;
-    });
-}
+extern "C" int bzh_get_grep_context_stats(const bzh_ctx *ctx, bzh_grep_context_stats *out) { return stats_get(ctx, &bzh_ctx::gcstats, out); }
 
-// ---- the matched parts alone (match.hip: the kernels, the passes over a window, the staging and the carry; the routes are the
-// grep's, as a WindowSink of its own; the windows and the cursor: match_plan.h)
-static int match_begin(bzh_ctx *ctx, const ScanWhat &q, unsigned flags, void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches,
-                       uint64_t *out_total)
-{
-    if (!q.given() || !nmatches || !out_total || (!d_out && cap) || (!ent && max)) return BZH_E_ARG;
-    *nmatches = 0;
-    *out_total = 0;
-    BZH_TRY(scan_args(ctx, "match", q, flags, BZH_MATCH_RECORDS, "BZH_MATCH_RECORDS"));
-    if ((uintptr_t)d_out & 3u) {
-        bzh_set_error(ctx, "match: the output buffer is not 4-byte aligned");
-        return BZH_E_ARG;
-    }
-    memset(&ctx->mtstats, 0, sizeof ctx->mtstats);
-    return BZH_OK;
-}
-static MatchSink match_sink(const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap, bzh_match_entry *ent, size_t max)
-{
-    return q.is_set ? MatchSink(q.set, flags, delim, d_out, cap, ent, max) : MatchSink(q.pat, q.plen, flags, delim, d_out, cap, ent, max);
-}
-
-// rc: the status of the windows.  Behind them the starts held back (match_finish); bytes and entries follow the stream: whatever
-// the status, nothing is on its way to the caller's arrays when the call returns.
-static int match_end(bzh_ctx *ctx, MatchSink &s, const DecodeCall &call, int rc, size_t *nmatches, uint64_t *out_total)
-{
-    if (rc == BZH_OK) rc = match_finish(ctx, s);
-    rc = decode_call_end(ctx, call, rc);
-    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
-    if (rc != BZH_OK) return rc;
-    *nmatches = (size_t)s.walk.sel;
-    *out_total = s.walk.out_bytes;
-    if (s.walk.overflow()) {
-        bzh_set_error(ctx, "match: %llu matches of %llu bytes, room for %llu and %llu", (unsigned long long)s.walk.sel,
-                      (unsigned long long)s.walk.out_bytes, (unsigned long long)s.walk.max, (unsigned long long)s.walk.cap);
-        return BZH_E_CAP;
-    }
-    return BZH_OK;
-}
-
-static int match_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap,
-                            bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total)
-{
-    return bzh_guard(ctx, [&]() -> int {
-    if (ctx) stream_join(ctx);
-    if (!ctx || (!d_raw && n)) return BZH_E_ARG;
-    BZH_TRY(match_begin(ctx, q, flags, d_out, cap, ent, max, nmatches, out_total));
-    MatchSink s = match_sink(q, flags, delim, d_out, cap, ent, max);
-    if ((uintptr_t)d_raw & 15u) {
-        bzh_set_error(ctx, "match: the buffer is not 16-byte aligned");
-        return BZH_E_ARG;
-    }
-    DecodeCall call;
-    BZH_TRY(decode_call_begin(ctx, n, call));
-    const int rc = match_raw_run(ctx, s, (const uint8_t *)d_raw, n);
-    return match_end(ctx, s, call, rc, nmatches, out_total);
-    });
-}
-
-static int match_device(bzh_ctx *ctx, const void *d_in, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap,
-                        bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total, uint64_t *decoded_total, size_t *consumed)
-{
-    return bzh_guard(ctx, [&]() -> int {
-    if (ctx) stream_join(ctx);
-    if (!ctx || (!d_in && n)) return BZH_E_ARG;
-    BZH_TRY(match_begin(ctx, q, flags, d_out, cap, ent, max, nmatches, out_total));
-    MatchSink s = match_sink(q, flags, delim, d_out, cap, ent, max);
-    DecodeCall call;
-    BZH_TRY(decode_call_begin(ctx, n, call));
-    if (decoded_total) *decoded_total = 0;
-    if (consumed) *consumed = 0;
-    std::vector<uint64_t> cands;
-    BZH_TRY(decode_call_scan(ctx, call, d_in, n, cands));
-    size_t total = 0;
-    const int rc = decode_chain_run(ctx, (const uint8_t *)d_in, n, nullptr, 0, &total, consumed, cands, nullptr, nullptr, nullptr, &s);
-    if (decoded_total) *decoded_total = total;
-    return match_end(ctx, s, call, rc, nmatches, out_total);
-    });
-}
-
-static int match_host(bzh_ctx *ctx, const uint8_t *in, size_t n, const ScanWhat &q, unsigned flags, uint8_t delim, uint8_t *out, size_t cap,
-                      bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total, uint64_t *decoded_total, size_t *consumed)
-{
-    return bzh_guard(ctx, [&]() -> int {
-    if (ctx) stream_join(ctx);
-    if (!ctx || (!in && n) || (!out && cap)) return BZH_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BZH_TRY(decode_stage(ctx, in, n, grep_stage_room(out, cap)));
-    BZH_TRY(match_device(ctx, ctx->d_stage_in, n, q, flags, delim, out ? ctx->d_stage_out.p : nullptr, cap, ent, max, nmatches, out_total,
-                         decoded_total, consumed));
-    return decode_unstage(ctx, out, out ? (size_t)*out_total : 0);
-    });
-}
-
-static int match_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts,
-                              size_t npts, const ScanWhat &q, unsigned flags, uint8_t delim, void *d_out, size_t cap, bzh_match_entry *ent, size_t max,
-                              size_t *nmatches, uint64_t *out_total)
-{
-    return bzh_guard(ctx, [&]() -> int {
-    if (ctx) stream_join(ctx);
-    if (!ctx || (!d_in && n) || (!idx && count) || (!pts && npts)) return BZH_E_ARG;
-    BZH_TRY(match_begin(ctx, q, flags, d_out, cap, ent, max, nmatches, out_total));
-    MatchSink s = match_sink(q, flags, delim, d_out, cap, ent, max);
-    DecodeCall call;
-    BZH_TRY(decode_call_begin(ctx, n, call));
-    BZH_TRY(search_range_args(ctx, idx, count, pts, npts, nullptr, 0));
-    BZH_TRY(ensure_arena(ctx, (uint32_t)std::min<size_t>(std::max<size_t>(count, 1), ctx->max_batch)));
-    const int rc = decode_range_sink_run(ctx, (const uint8_t *)d_in, n, 0, idx, count, pts, npts, nullptr, 0, ~0ull, s);
-    return match_end(ctx, s, call, rc, nmatches, out_total);
-    });
-}
-
-static int match_index_host(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count, const bzh_sync_point *pts,
-                            size_t npts, const ScanWhat &q, unsigned flags, uint8_t delim, uint8_t *out, size_t cap, bzh_match_entry *ent, size_t max,
-                            size_t *nmatches, uint64_t *out_total)
-{
-    return bzh_guard(ctx, [&]() -> int {
-    if (ctx) stream_join(ctx);
-    if (!ctx || (!in && n) || (!idx && count) || (!pts && npts) || (!out && cap)) return BZH_E_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BZH_TRY(decode_stage(ctx, in, n, grep_stage_room(out, cap)));
-    BZH_TRY(match_index_device(ctx, ctx->d_stage_in, n, idx, count, pts, npts, q, flags, delim, out ? ctx->d_stage_out.p : nullptr, cap, ent, max,
-                               nmatches, out_total));
-    return decode_unstage(ctx, out, out ? (size_t)*out_total : 0);
-    });
-}
-
-// the public calls: a byte string, or a set
+// ... of the matched parts alone
 extern "C" int bzh_match_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
                                     void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total)
 {
-    return match_raw_device(ctx, d_raw, n, what_pat(pat, plen), flags, delim, d_out, cap, ent, max, nmatches, out_total);
+    MatchSink s(what_pat(pat, plen), flags, delim, d_out, cap, ent, max);
+    return scan_raw_device(ctx, MATCH, s, d_raw, n, nmatches, out_total);
 }
 extern "C" int bzh_match_patset_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
                                            void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total)
 {
-    return match_raw_device(ctx, d_raw, n, what_set(set), flags, delim, d_out, cap, ent, max, nmatches, out_total);
+    MatchSink s(what_set(set), flags, delim, d_out, cap, ent, max);
+    return scan_raw_device(ctx, MATCH, s, d_raw, n, nmatches, out_total);
 }
 extern "C" int bzh_match_device(bzh_ctx *ctx, const void *d_in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
                                 void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total,
                                 uint64_t *decoded_total, size_t *consumed)
 {
-    return match_device(ctx, d_in, n, what_pat(pat, plen), flags, delim, d_out, cap, ent, max, nmatches, out_total, decoded_total, consumed);
+    MatchSink s(what_pat(pat, plen), flags, delim, d_out, cap, ent, max);
+    return scan_device(ctx, MATCH, s, d_in, n, nmatches, out_total, decoded_total, consumed);
 }
 extern "C" int bzh_match_patset_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim,
                                        void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total,
                                        uint64_t *decoded_total, size_t *consumed)
 {
-    return match_device(ctx, d_in, n, what_set(set), flags, delim, d_out, cap, ent, max, nmatches, out_total, decoded_total, consumed);
+    MatchSink s(what_set(set), flags, delim, d_out, cap, ent, max);
+    return scan_device(ctx, MATCH, s, d_in, n, nmatches, out_total, decoded_total, consumed);
 }
 extern "C" int bzh_match(bzh_ctx *ctx, const uint8_t *in, size_t n, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
                          uint8_t *out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total,
                          uint64_t *decoded_total, size_t *consumed)
 {
-    return match_host(ctx, in, n, what_pat(pat, plen), flags, delim, out, cap, ent, max, nmatches, out_total, decoded_total, consumed);
+    MatchSink s(what_pat(pat, plen), flags, delim, out, cap, ent, max);
+    return scan_host(ctx, MATCH, s, in, n, nmatches, out_total, decoded_total, consumed);
 }
 extern "C" int bzh_match_patset(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_patset *set, unsigned flags, uint8_t delim, uint8_t *out,
                                 size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total, uint64_t *decoded_total,
                                 size_t *consumed)
 {
-    return match_host(ctx, in, n, what_set(set), flags, delim, out, cap, ent, max, nmatches, out_total, decoded_total, consumed);
+    MatchSink s(what_set(set), flags, delim, out, cap, ent, max);
+    return scan_host(ctx, MATCH, s, in, n, nmatches, out_total, decoded_total, consumed);
 }
 extern "C" int bzh_match_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count,
                                       const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
                                       void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total)
 {
-    return match_index_device(ctx, d_in, n, idx, count, pts, npts, what_pat(pat, plen), flags, delim, d_out, cap, ent, max, nmatches, out_total);
+    MatchSink s(what_pat(pat, plen), flags, delim, d_out, cap, ent, max);
+    return scan_index_device(ctx, MATCH, s, d_in, n, idx, count, pts, npts, nullptr, nmatches, out_total);
 }
 extern "C" int bzh_match_patset_index_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_index_entry *idx, size_t count,
                                              const bzh_sync_point *pts, size_t npts, const bzh_patset *set, unsigned flags, uint8_t delim,
                                              void *d_out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total)
 {
-    return match_index_device(ctx, d_in, n, idx, count, pts, npts, what_set(set), flags, delim, d_out, cap, ent, max, nmatches, out_total);
+    MatchSink s(what_set(set), flags, delim, d_out, cap, ent, max);
+    return scan_index_device(ctx, MATCH, s, d_in, n, idx, count, pts, npts, nullptr, nmatches, out_total);
 }
 extern "C" int bzh_match_index(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count,
                                const bzh_sync_point *pts, size_t npts, const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim,
                                uint8_t *out, size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total)
 {
-    return match_index_host(ctx, in, n, idx, count, pts, npts, what_pat(pat, plen), flags, delim, out, cap, ent, max, nmatches, out_total);
+    MatchSink s(what_pat(pat, plen), flags, delim, out, cap, ent, max);
+    return scan_index_host(ctx, MATCH, s, in, n, idx, count, pts, npts, nullptr, nmatches, out_total);
 }
 extern "C" int bzh_match_patset_index(bzh_ctx *ctx, const uint8_t *in, size_t n, const bzh_index_entry *idx, size_t count,
                                       const bzh_sync_point *pts, size_t npts, const bzh_patset *set, unsigned flags, uint8_t delim, uint8_t *out,
                                       size_t cap, bzh_match_entry *ent, size_t max, size_t *nmatches, uint64_t *out_total)
 {
-    return match_index_host(ctx, in, n, idx, count, pts, npts, what_set(set), flags, delim, out, cap, ent, max, nmatches, out_total);
+    MatchSink s(what_set(set), flags, delim, out, cap, ent, max);
+    return scan_index_host(ctx, MATCH, s, in, n, idx, count, pts, npts, nullptr, nmatches, out_total);
 }
 
-extern "C" int bzh_get_match_stats(const bzh_ctx *ctx, bzh_match_stats *out)
-{
-    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
-    if (!ctx || !out) return BZH_E_ARG;
-    *out = ctx->mtstats;
-    return BZH_OK;
-    });
-}
+extern "C" int bzh_get_match_stats(const bzh_ctx *ctx, bzh_match_stats *out) { return stats_get(ctx, &bzh_ctx::mtstats, out); }
 
-extern "C" int bzh_get_decode_ranges_stats(const bzh_ctx *ctx, bzh_decode_ranges_stats *out)
-{
-    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
-    if (!ctx || !out) return BZH_E_ARG;
-    *out = ctx->qstats;
-    return BZH_OK;
-    });
-}
+extern "C" int bzh_get_decode_ranges_stats(const bzh_ctx *ctx, bzh_decode_ranges_stats *out) { return stats_get(ctx, &bzh_ctx::qstats, out); }
 
-extern "C" int bzh_get_decode_stats(const bzh_ctx *ctx, bzh_decode_stats *out)
-{
-    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
-    if (!ctx || !out) return BZH_E_ARG;
-    *out = ctx->dstats;
-    return BZH_OK;
-    });
-}
+extern "C" int bzh_get_decode_stats(const bzh_ctx *ctx, bzh_decode_stats *out) { return stats_get(ctx, &bzh_ctx::dstats, out); }
 
 // ---- many inputs (decode.hip's decode_many_run): one scan of the whole buffer, the arena for a batch of its candidates
 extern "C" int bzh_decode_many_device(bzh_ctx *ctx, const void *d_in, size_t n, const size_t *in_offs, const size_t *in_lens, size_t count,
@@ -2667,14 +2418,7 @@ extern "C" int bzh_decode_many(bzh_ctx *ctx, const uint8_t *const *ins, const si
     });
 }
 
-extern "C" int bzh_get_decode_many_stats(const bzh_ctx *ctx, bzh_decode_many_stats *out)
-{
-    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
-    if (!ctx || !out) return BZH_E_ARG;
-    *out = ctx->mstats;
-    return BZH_OK;
-    });
-}
+extern "C" int bzh_get_decode_many_stats(const bzh_ctx *ctx, bzh_decode_many_stats *out) { return stats_get(ctx, &bzh_ctx::mstats, out); }
 
 // ---- recovery (decode.hip's decode_recover_run; recover.hip's gather): per block what bzh_decode is per input
 extern "C" int bzh_recover_device(bzh_ctx *ctx, const void *d_in, size_t n, void *d_out, size_t cap, size_t *out_len, bzh_recover_entry *ent,
@@ -2727,14 +2471,7 @@ extern "C" int bzh_recover(bzh_ctx *ctx, const uint8_t *in, size_t n, uint8_t *o
     });
 }
 
-extern "C" int bzh_get_recover_stats(const bzh_ctx *ctx, bzh_recover_stats *out)
-{
-    return bzh_guard(const_cast<bzh_ctx *>(ctx), [&]() -> int {
-    if (!ctx || !out) return BZH_E_ARG;
-    *out = ctx->rstats;
-    return BZH_OK;
-    });
-}
+extern "C" int bzh_get_recover_stats(const bzh_ctx *ctx, bzh_recover_stats *out) { return stats_get(ctx, &bzh_ctx::rstats, out); }
 
 // The report is checked as a whole and the size set before anything is launched; then the magics, the gather and the frame.
 extern "C" int bzh_recover_stream_device(bzh_ctx *ctx, const void *d_in, size_t n, const bzh_recover_entry *ent, size_t count, void *d_out,

@@ -562,7 +562,7 @@ struct RecBuild { // bzh_decode_index_records*: the index build also counts the 
 };
 // A consumer of decoded windows (bzh_search*, bzh_grep*): the decoders expand WHOLE blocks, window after window, into a staging
 // buffer that the sink owns, and hand every window over once all of its blocks have passed their CRCs.  This is all decode.hip
-// knows of a search or a grep (search.hip, grep.hip: SearchSink, GrepSink).
+// knows of a search, a grep or a match (ScanSink below, and search.hip, grep.hip, match.hip: SearchSink, GrepSink, MatchSink).
 struct WindowSink {
     const uint64_t front; // the decoders expand at *d_stage + front (whatever is carried between two windows lies in front of it)
     const uint32_t delim; // of the records, where the walk counts them (BackCount)
@@ -645,21 +645,59 @@ struct bzh_patset {
     const uint8_t *d_acc_mask = nullptr;
     bool looks() const { return look.look_behind || look.look_ahead; }
 };
+// What a search, a grep or a match looks for: a byte string, or a compiled set (bzh_*_patset*).
+struct ScanWhat {
+    const uint8_t *pat;
+    size_t plen;
+    const bzh_patset *set;
+    bool is_set;
+    bool given() const { return is_set ? set != nullptr : pat != nullptr; }
+};
+// What a call of bzh_search* / bzh_grep* / bzh_match* was given beside its input, as the caller wrote it: nothing of it has been
+// checked.  out / cap: where the bytes go (device; a search writes none), ent / max: the entries or the hits (host).
+struct ScanArgs {
+    ScanWhat what;
+    unsigned flags;
+    void *out;
+    size_t cap;
+    void *ent;
+    size_t max;
+};
+// The sink of one such call, as api.hip's routes know it: a WindowSink for the decoders, and beside the windows what every route
+// does once a call -- the one window of decoded bytes that already lie in HBM, what is left behind the last window, and the
+// answer.  The constructor only keeps the arguments; arm() makes the walk of them once the route has checked them.
+struct ScanSink : WindowSink {
+    ScanArgs args;
+    ScanSink(const ScanWhat &q, unsigned flags, uint8_t delim_, void *out, size_t cap, void *ent, size_t max)
+        : WindowSink(BZF_FRONT, delim_), args{q, flags, out, cap, ent, max} {}
+    virtual void arm(const bzh_ctx *ctx) = 0;
+    // decoded bytes that already lie in HBM: one window, no staging, no carry
+    virtual int raw(bzh_ctx *ctx, const uint8_t *d_raw, size_t n) = 0;
+    // behind the last window: what was held back is processed where it lies, in the carry
+    virtual int finish(bzh_ctx *ctx) = 0;
+    // behind the last wait: the counts to the caller; BZH_E_CAP, with its text, where a room was too small
+    virtual int report(bzh_ctx *ctx, size_t *count, uint64_t *out_total) = 0;
+
+protected:
+    ~ScanSink() = default;
+};
 // search.hip: the search over decoded bytes in HBM.  A sink is what is looked for, where the hits go, and the walk over its windows
-// (search_plan.h): room() puts the carry in front of the window, window() runs the two passes and keeps the window's tail.
-struct SearchSink final : WindowSink {
+// (search_plan.h): room() puts the carry in front of the window, window() runs the two passes and keeps the window's tail;
+// finish() of a set search: the starts held back.
+struct SearchSink final : ScanSink {
     BzfPattern pat{};
     const bzh_patset *set = nullptr; // what is looked for instead of pat: hits are bzh_set_hit, the windows BzmSetWalk::window_set's
-    bool records;
-    void *hits; // host: bzh_hit, or bzh_set_hit
-    uint64_t max;
+    bool records = false;
+    void *hits = nullptr; // host: bzh_hit, or bzh_set_hit
+    uint64_t max = 0;
     BzmSetWalk walk; // (a single pattern keeps to BzfWalk's part of it)
-    SearchSink(const uint8_t *pat_, size_t plen, unsigned flags, uint8_t delim_, bzh_hit *hits_, size_t max_)
-        : WindowSink(BZF_FRONT, delim_), pat(bzf_pattern(pat_, (uint32_t)plen, delim_)), records((flags & BZH_SEARCH_RECORDS) != 0), hits(hits_), max(max_) {}
-    SearchSink(const bzh_patset *set_, unsigned flags, uint8_t delim_, bzh_set_hit *hits_, size_t max_)
-        : WindowSink(BZF_FRONT, delim_), set(set_), records((flags & BZH_SEARCH_RECORDS) != 0), hits(hits_), max(max_)
+    SearchSink(const ScanWhat &q, unsigned flags, uint8_t delim_, void *hits_, size_t max_) : ScanSink(q, flags, delim_, nullptr, 0, hits_, max_) {}
+    void arm(const bzh_ctx *) override
     {
-        look_behind = set->look.look_behind, look_ahead = set->look.look_ahead;
+        const ScanWhat &q = args.what;
+        if (q.is_set) set = q.set, look_behind = set->look.look_behind, look_ahead = set->look.look_ahead;
+        else pat = bzf_pattern(q.pat, (uint32_t)q.plen, delim);
+        records = (args.flags & BZH_SEARCH_RECORDS) != 0, hits = args.ent, max = args.max;
     }
     bool looks() const { return set && set->looks(); }
     uint32_t plen() const { return set ? set->info.max_len : pat.plen; } // (of a set: its longest pattern's)
@@ -671,34 +709,43 @@ struct SearchSink final : WindowSink {
     }
     int room(bzh_ctx *ctx, uint64_t bytes, uint8_t **d_stage) override;
     int window(bzh_ctx *ctx, uint64_t bytes) override;
+    int raw(bzh_ctx *ctx, const uint8_t *d_raw, size_t n) override;
+    int finish(bzh_ctx *ctx) override;
+    int report(bzh_ctx *ctx, size_t *nhits, uint64_t *) override;
 };
-int search_raw_run(bzh_ctx *ctx, SearchSink &sink, const uint8_t *d_raw, size_t n);
-int search_finish(bzh_ctx *ctx, SearchSink &sink); // of a set search: the starts held back, behind the last window
 // grep.hip: the selected records of decoded bytes in HBM, compacted into d_out.  A sink is what is looked for, where bytes and
 // entries go, and the walk over its windows (grep_plan.h): as the search's, with the whole open record carried (begin() has nothing
-// to say: a grep takes the whole output).  grep_finish: the bytes held back and the open tail, behind the last window.
-struct GrepSink final : WindowSink {
+// to say: a grep takes the whole output).  finish(): the bytes held back and the open tail, behind the last window.
+struct GrepSink final : ScanSink {
     BzfPattern pat{};
     const bzh_patset *set = nullptr; // what is looked for instead of pat; the walk keeps its rule with plen = the longest pattern's
-    uint8_t *d_out;      // device (null: not asked for)
-    bzh_grep_entry *ent; // host (null: not asked for)
+    uint8_t *d_out = nullptr;      // device (null: not asked for)
+    bzh_grep_entry *ent = nullptr; // host (null: not asked for)
     BzgWalk walk;
     BzcWalk cwalk;       // the walk instead of it when context records are asked for (grep_ctx_plan.h)
     bool ctx_on = false;
     uint64_t at = 0;               // staging position of the window's first new byte
     const uint8_t *tail = nullptr; // device: where the carry lies
-    BzgEntry tail_ent{};           // grep_finish: the open tail's entry
-    GrepSink(const uint8_t *pat_, size_t plen, unsigned flags, uint8_t delim_, void *d_out_, size_t cap, bzh_grep_entry *ent_, size_t max)
-        : WindowSink(BZF_FRONT, delim_), pat(bzf_pattern(pat_, (uint32_t)plen, delim_)), d_out((uint8_t *)d_out_), ent(ent_)
+    BzgEntry tail_ent{};           // finish(): the open tail's entry, which report() stores at ent[sel - 1] behind the last wait ...
+    bool tail_ent_due = false;     // ... where it is a selected record with room for its entry
+    GrepSink(const ScanWhat &q, unsigned flags, uint8_t delim_, void *d_out_, size_t cap, bzh_grep_entry *ent_, size_t max)
+        : ScanSink(q, flags, delim_, d_out_, cap, ent_, max) {}
+    // the context's bzh_grep_set_context as the call finds it
+    void arm(const bzh_ctx *ctx) override
     {
-        walk.begin((uint32_t)plen, (flags & BZH_GREP_INVERT) != 0, d_out != nullptr, cap, ent != nullptr, max);
+        const ScanWhat &q = args.what;
+        const bool invert = (args.flags & BZH_GREP_INVERT) != 0;
+        d_out = (uint8_t *)args.out, ent = (bzh_grep_entry *)args.ent;
+        if (q.is_set) {
+            set = q.set;
+            walk.begin(set->info.max_len + set->look.look_ahead, invert, d_out != nullptr, args.cap, ent != nullptr, args.max); // (the hold-back grows by the byte behind a match)
+        } else {
+            pat = bzf_pattern(q.pat, (uint32_t)q.plen, delim);
+            walk.begin((uint32_t)q.plen, invert, d_out != nullptr, args.cap, ent != nullptr, args.max);
+        }
+        set_context(ctx->grep_before, ctx->grep_after);
     }
-    GrepSink(const bzh_patset *set_, unsigned flags, uint8_t delim_, void *d_out_, size_t cap, bzh_grep_entry *ent_, size_t max)
-        : WindowSink(BZF_FRONT, delim_), set(set_), d_out((uint8_t *)d_out_), ent(ent_)
-    {
-        walk.begin(set->info.max_len + set->look.look_ahead, (flags & BZH_GREP_INVERT) != 0, d_out != nullptr, cap, ent != nullptr, max); // (the hold-back grows by the byte behind a match)
-    }
-    // bzh_grep_set_context as the call found it: 0, 0 leaves the plain walk and its kernels
+    // 0, 0 leaves the plain walk and its kernels
     void set_context(uint32_t before, uint32_t after)
     {
         ctx_on = before || after;
@@ -711,37 +758,42 @@ struct GrepSink final : WindowSink {
     void begin(uint64_t, uint64_t, uint64_t, uint64_t) override {}
     int room(bzh_ctx *ctx, uint64_t bytes, uint8_t **d_stage) override;
     int window(bzh_ctx *ctx, uint64_t bytes) override;
+    int raw(bzh_ctx *ctx, const uint8_t *d_raw, size_t n) override;
+    int finish(bzh_ctx *ctx) override;
+    int report(bzh_ctx *ctx, size_t *nrecs, uint64_t *out_total) override;
 };
-int grep_raw_run(bzh_ctx *ctx, GrepSink &g, const uint8_t *d_raw, size_t n);
-int grep_finish(bzh_ctx *ctx, GrepSink &g, bool *tail_entry);
 // match.hip: the selected matches of decoded bytes in HBM, compacted into d_out.  A sink is what is looked for, where bytes and
-// entries go, and the walk over its windows (match_plan.h): a set search's hold-back and the cursor.  match_finish: the starts held
+// entries go, and the walk over its windows (match_plan.h): a set search's hold-back and the cursor.  finish(): the starts held
 // back, behind the last window.
-struct MatchSink final : WindowSink {
+struct MatchSink final : ScanSink {
     BzfPattern pat{};
     const bzh_patset *set = nullptr; // what is looked for instead of pat
-    bool records;
-    uint8_t *d_out;  // device (null: not asked for)
-    bzh_match_entry *ent;  // host (null: not asked for)
+    bool records = false;
+    uint8_t *d_out = nullptr;       // device (null: not asked for)
+    bzh_match_entry *ent = nullptr; // host (null: not asked for)
     MtWalk walk;
     uint64_t at = 0; // staging position of the window's first new byte
-    MatchSink(const uint8_t *pat_, size_t plen, unsigned flags, uint8_t delim_, void *d_out_, size_t cap, bzh_match_entry *ent_, size_t max)
-        : WindowSink(BZF_FRONT, delim_), pat(bzf_pattern(pat_, (uint32_t)plen, delim_)), records((flags & BZH_MATCH_RECORDS) != 0), d_out((uint8_t *)d_out_), ent(ent_)
+    MatchSink(const ScanWhat &q, unsigned flags, uint8_t delim_, void *d_out_, size_t cap, bzh_match_entry *ent_, size_t max)
+        : ScanSink(q, flags, delim_, d_out_, cap, ent_, max) {}
+    void arm(const bzh_ctx *) override
     {
-        walk.begin((uint32_t)plen, 0, 0, false, d_out != nullptr, cap, ent != nullptr, max);
-    }
-    MatchSink(const bzh_patset *set_, unsigned flags, uint8_t delim_, void *d_out_, size_t cap, bzh_match_entry *ent_, size_t max)
-        : WindowSink(BZF_FRONT, delim_), set(set_), records((flags & BZH_MATCH_RECORDS) != 0), d_out((uint8_t *)d_out_), ent(ent_)
-    {
-        look_behind = set->look.look_behind, look_ahead = set->look.look_ahead;
-        walk.begin(set->info.max_len, look_behind, look_ahead, true, d_out != nullptr, cap, ent != nullptr, max);
+        const ScanWhat &q = args.what;
+        records = (args.flags & BZH_MATCH_RECORDS) != 0, d_out = (uint8_t *)args.out, ent = (bzh_match_entry *)args.ent;
+        if (q.is_set) {
+            set = q.set, look_behind = set->look.look_behind, look_ahead = set->look.look_ahead;
+            walk.begin(set->info.max_len, look_behind, look_ahead, true, d_out != nullptr, args.cap, ent != nullptr, args.max);
+        } else {
+            pat = bzf_pattern(q.pat, (uint32_t)q.plen, delim);
+            walk.begin((uint32_t)q.plen, 0, 0, false, d_out != nullptr, args.cap, ent != nullptr, args.max);
+        }
     }
     void begin(uint64_t, uint64_t, uint64_t, uint64_t) override {} // (the whole output, from offset 0)
     int room(bzh_ctx *ctx, uint64_t bytes, uint8_t **d_stage) override;
     int window(bzh_ctx *ctx, uint64_t bytes) override;
+    int raw(bzh_ctx *ctx, const uint8_t *d_raw, size_t n) override;
+    int finish(bzh_ctx *ctx) override;
+    int report(bzh_ctx *ctx, size_t *nmatches, uint64_t *out_total) override;
 };
-int match_raw_run(bzh_ctx *ctx, MatchSink &s, const uint8_t *d_raw, size_t n);
-int match_finish(bzh_ctx *ctx, MatchSink &s);
 // recover.hip: the bits of the kept blocks, end to end from bit 32 of d_out, in one launch (the per-word rule: recover_gather.h)
 struct BzrDesc;
 int recover_gather_run(bzh_ctx *ctx, const uint8_t *d_in, size_t n, const std::vector<BzrDesc> &descs, uint64_t body, uint32_t *d_out);

@@ -1,6 +1,6 @@
 // grep.hip -- the records of decoded bytes in HBM that hold a byte string, compacted into the caller's buffer (bzh_grep*): the two
-// passes over the tiles of a window, the scan between them, and the grep as a WindowSink of the decoders (common.h): its staging
-// room (search.hip's scan_room) and the carry between two windows.  The windows: grep_plan.h; the tile front: search_core.h; what
+// passes over the tiles of a window, the scan between them, and the grep as a ScanSink (common.h): its staging room (search.hip's
+// scan_room), the carry between two windows, what is left behind the last one, and the answer.  The windows: grep_plan.h; the tile front: search_core.h; what
 // one thread, one tile and the scan do behind it: grep_core.h.  The text never leaves the device: what comes back is five words a
 // window, and the selected records.
 #include "common.h"
@@ -361,38 +361,51 @@ int GrepSink::window(bzh_ctx *ctx, uint64_t bytes)
 }
 
 // Decoded bytes that already lie in HBM: one window, no staging, no carry.
-int grep_raw_run(bzh_ctx *ctx, GrepSink &g, const uint8_t *d_raw, size_t n)
+int GrepSink::raw(bzh_ctx *ctx, const uint8_t *d_raw, size_t n)
 {
-    if (g.ctx_on) return grep_ctx_window_run(ctx, g, d_raw, g.cwalk.window(0, n, true), n);
-    return grep_window_run(ctx, g, d_raw, g.walk.window(0, n, true), n);
+    if (ctx_on) return grep_ctx_window_run(ctx, *this, d_raw, cwalk.window(0, n, true), n);
+    return grep_window_run(ctx, *this, d_raw, walk.window(0, n, true), n);
 }
 
 // Behind the last window: the bytes held back are processed where they lie, in the carry; then the open tail, if it is a selected
-// record, goes out in one copy.  *tail_entry: the caller stores the tail's entry at ent[walk.sel - 1] behind its last wait.
-int grep_finish(bzh_ctx *ctx, GrepSink &g, bool *tail_entry)
+// record, goes out in one copy.  tail_ent_due: report() stores the tail's entry at ent[sel - 1] behind the call's last wait.
+int GrepSink::finish(bzh_ctx *ctx)
 {
-    *tail_entry = false;
+    tail_ent_due = false;
     bzh_grep_stats &gs = ctx->gstats;
-    if (g.ctx_on) { // the finishing window also where records are pending: a primary tail selects them
-        BzcWalk &cw = g.cwalk;
-        if (cw.held || cw.npend) BZH_TRY(grep_ctx_window_run(ctx, g, ctx->scan_carry, cw.window(cw.carry, 0, true), 0));
+    if (ctx_on) { // the finishing window also where records are pending: a primary tail selects them
+        BzcWalk &cw = cwalk;
+        if (cw.held || cw.npend) BZH_TRY(grep_ctx_window_run(ctx, *this, ctx->scan_carry, cw.window(cw.carry, 0, true), 0));
         bool copy = false;
-        cw.tail_rooms(&copy, tail_entry);
-        g.tail_ent = cw.tail_entry();
-        if (copy) HIP_TRY(ctx, hipMemcpyAsync(g.d_out + cw.out_bytes, g.tail, (size_t)cw.carry, hipMemcpyDeviceToDevice, ctx->stream));
+        cw.tail_rooms(&copy, &tail_ent_due);
+        tail_ent = cw.tail_entry();
+        if (copy) HIP_TRY(ctx, hipMemcpyAsync(d_out + cw.out_bytes, tail, (size_t)cw.carry, hipMemcpyDeviceToDevice, ctx->stream));
         cw.tail_done();
         gs.records = cw.nrecords(), gs.selected = cw.sel, gs.out_bytes = cw.out_bytes;
         ctx->gcstats = bzh_grep_context_stats{cw.matched, cw.context, cw.groups, cw.pending_peak};
         return BZH_OK;
     }
-    if (g.walk.held) BZH_TRY(grep_window_run(ctx, g, ctx->scan_carry, g.walk.window(g.walk.carry, 0, true), 0));
+    if (walk.held) BZH_TRY(grep_window_run(ctx, *this, ctx->scan_carry, walk.window(walk.carry, 0, true), 0));
     bool copy = false;
-    g.walk.tail_rooms(&copy, tail_entry);
-    g.tail_ent = g.walk.tail_entry();
-    if (copy)
-        HIP_TRY(ctx, hipMemcpyAsync(g.d_out + g.walk.out_bytes, g.tail, (size_t)g.walk.carry, hipMemcpyDeviceToDevice, ctx->stream));
-    g.walk.tail_done();
-    gs.records = g.walk.nrecords(), gs.selected = g.walk.sel, gs.out_bytes = g.walk.out_bytes;
-    ctx->gcstats = bzh_grep_context_stats{g.walk.sel, 0, 0, 0};
+    walk.tail_rooms(&copy, &tail_ent_due);
+    tail_ent = walk.tail_entry();
+    if (copy) HIP_TRY(ctx, hipMemcpyAsync(d_out + walk.out_bytes, tail, (size_t)walk.carry, hipMemcpyDeviceToDevice, ctx->stream));
+    walk.tail_done();
+    gs.records = walk.nrecords(), gs.selected = walk.sel, gs.out_bytes = walk.out_bytes;
+    ctx->gcstats = bzh_grep_context_stats{walk.sel, 0, 0, 0};
+    return BZH_OK;
+}
+
+// Bytes and entries have followed the stream to the caller's arrays; the tail's entry, the counts, and whether the rooms sufficed.
+int GrepSink::report(bzh_ctx *ctx, size_t *nrecs, uint64_t *out_total)
+{
+    if (tail_ent_due) memcpy(&ent[sel() - 1], &tail_ent, sizeof tail_ent);
+    *nrecs = (size_t)sel();
+    *out_total = out_bytes();
+    if (overflow()) {
+        bzh_set_error(ctx, "grep: %llu records of %llu bytes, room for %llu and %llu", (unsigned long long)sel(),
+                      (unsigned long long)out_bytes(), (unsigned long long)walk.max, (unsigned long long)walk.cap);
+        return BZH_E_CAP;
+    }
     return BZH_OK;
 }

@@ -239,15 +239,28 @@ int MatchSink::window(bzh_ctx *ctx, uint64_t bytes)
 }
 
 // Decoded bytes that already lie in HBM: one window, no staging, no carry.
-int match_raw_run(bzh_ctx *ctx, MatchSink &s, const uint8_t *d_raw, size_t n)
+int MatchSink::raw(bzh_ctx *ctx, const uint8_t *d_raw, size_t n)
 {
-    return match_window_run(ctx, s, d_raw, s.walk.window(0, n, true), n, true);
+    return match_window_run(ctx, *this, d_raw, walk.window(0, n, true), n, true);
 }
 
 // Behind the last window: the starts held back are processed where they lie, in the carry -- a window without new bytes, its
 // text the carry, every delimiter of which has been counted.
-int match_finish(bzh_ctx *ctx, MatchSink &s)
+int MatchSink::finish(bzh_ctx *ctx)
 {
-    if (!s.walk.walk.carry) return BZH_OK;
-    return match_window_run(ctx, s, ctx->scan_carry, s.walk.window(s.walk.walk.carry, 0, true), 0, true);
+    if (!walk.walk.carry) return BZH_OK;
+    return match_window_run(ctx, *this, ctx->scan_carry, walk.window(walk.walk.carry, 0, true), 0, true);
+}
+
+// Bytes and entries have followed the stream to the caller's arrays; the counts, and whether the rooms sufficed.
+int MatchSink::report(bzh_ctx *ctx, size_t *nmatches, uint64_t *out_total)
+{
+    *nmatches = (size_t)walk.sel;
+    *out_total = walk.out_bytes;
+    if (walk.overflow()) {
+        bzh_set_error(ctx, "match: %llu matches of %llu bytes, room for %llu and %llu", (unsigned long long)walk.sel,
+                      (unsigned long long)walk.out_bytes, (unsigned long long)walk.max, (unsigned long long)walk.cap);
+        return BZH_E_CAP;
+    }
+    return BZH_OK;
 }

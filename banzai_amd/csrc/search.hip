@@ -1,6 +1,6 @@
 // search.hip -- every occurrence of a byte string in decoded bytes that lie in HBM (bzh_search*): the kernel, the two passes over
-// one window, and the search as a WindowSink of the decoders (common.h), with the two host helpers it shares with the grep's sink:
-// the staging room and the tile count.  The windows and the carry: search_plan.h; the tile front -- load, staging, filter, verify,
+// one window, and the search as a ScanSink (common.h: the decoders' WindowSink, and what the routes of api.hip call once a call),
+// with the two host helpers it shares with the grep's sink: the staging room and the tile count.  The windows and the carry: search_plan.h; the tile front -- load, staging, filter, verify,
 // shared with grep_tiles -- and what one thread does behind it: search_core.h.  The bytes never leave the device: what comes back
 // is a word a window, and the hits.
 #include "common.h"
@@ -200,22 +200,33 @@ int SearchSink::window(bzh_ctx *ctx, uint64_t bytes)
 }
 
 // Decoded bytes that already lie in HBM: one window, no staging, no carry.
-int search_raw_run(bzh_ctx *ctx, SearchSink &sink, const uint8_t *d_raw, size_t n)
+int SearchSink::raw(bzh_ctx *ctx, const uint8_t *d_raw, size_t n)
 {
-    sink.walk.begin(sink.plen(), 0, sink.max, 0, n, 0, 0);
-    sink.walk.begin_look(sink.look_behind, sink.look_ahead);
+    walk.begin(plen(), 0, max, 0, n, 0, 0);
+    walk.begin_look(look_behind, look_ahead);
     uint64_t lim = 0;
-    const BzfWindow w = sink.set ? sink.walk.window_set(n, true, &lim) : sink.walk.window(n);
-    return search_window_run(ctx, sink, d_raw, w, lim, n, true);
+    const BzfWindow w = set ? walk.window_set(n, true, &lim) : walk.window(n);
+    return search_window_run(ctx, *this, d_raw, w, lim, n, true);
 }
 
 // Behind the last window of a set search: the starts held back are processed where they lie, in the carry -- a window without new
-// bytes, its text the carry, every delimiter of which has been counted.
-int search_finish(bzh_ctx *ctx, SearchSink &sink)
+// bytes, its text the carry, every delimiter of which has been counted.  (Behind raw() nothing is carried.)
+int SearchSink::finish(bzh_ctx *ctx)
 {
-    if (!sink.set || !sink.walk.carry) return BZH_OK;
-    sink.walk.front = sink.walk.carry;
+    if (!set || !walk.carry) return BZH_OK;
+    walk.front = walk.carry;
     uint64_t lim = 0;
-    const BzfWindow w = sink.walk.window_set(0, true, &lim);
-    return search_window_run(ctx, sink, ctx->scan_carry, w, lim, 0, true);
+    const BzfWindow w = walk.window_set(0, true, &lim);
+    return search_window_run(ctx, *this, ctx->scan_carry, w, lim, 0, true);
+}
+
+// The hits have followed the stream to the caller's array; the count, and whether the array had room for them.
+int SearchSink::report(bzh_ctx *ctx, size_t *nhits, uint64_t *)
+{
+    *nhits = (size_t)walk.rank;
+    if (walk.rank > max && max) {
+        bzh_set_error(ctx, "search: %llu hits, room for %llu", (unsigned long long)walk.rank, (unsigned long long)max);
+        return BZH_E_CAP;
+    }
+    return BZH_OK;
 }

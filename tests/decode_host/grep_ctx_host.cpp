@@ -220,7 +220,7 @@ static void ctx_call(const Bytes &text, const Pattern &p, uint32_t B, uint32_t A
             pend_truth_peak = std::max(pend_truth_peak, want);
         }
         CHECK(at == text.size(), "the blocks are the text");
-        if (s.walk.held || s.walk.npend) { // grep_finish: the finishing window, over the carry where it lies
+        if (s.walk.held || s.walk.npend) { // GrepSink::finish: the finishing window, over the carry where it lies
             const Text held(carry.data(), carry.size(), slack);
             const uint64_t ts = ctx_run(s, held.p, s.walk.window(s.walk.carry, 0, true), 0, m);
             carry.erase(carry.begin(), carry.begin() + ts);

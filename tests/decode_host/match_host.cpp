@@ -305,7 +305,7 @@ static Stats match_call(const Bytes &text, const What &q, bool records, const st
             with_matcher(q, mw, [&](const auto &m) { match_run(s, stage.p, mw, bytes, false, m); });
         }
         CHECK(at == text.size(), "the blocks are the text");
-        if (s.walk.walk.carry) { // match_finish
+        if (s.walk.walk.carry) { // MatchSink::finish
             CHECK(carry.size() == s.walk.walk.carry, "the carry");
             const Text held(carry.data(), carry.size(), slack);
             const MtWindow mw = s.walk.window(carry.size(), 0, true);

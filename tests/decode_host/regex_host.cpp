@@ -580,7 +580,7 @@ static void part_windows(uint64_t cases)
             carry = next;
             at_out += bytes, at += nbw;
         }
-        if (walk.carry) { // search_finish: the carry is the text
+        if (walk.carry) { // SearchSink::finish: the carry is the text
             const Text held(carry.data(), carry.size());
             walk.front = walk.carry;
             uint64_t lim = 0;

@@ -3,7 +3,7 @@
 // over the model LDS is the matcher interface of patset_core.h -- stage, match16, count16, emit1, the kernels' own text -- as
 // search_tiles and grep_tiles run it: Group<M> is the workgroup, search_front / search_run are search_tiles' two passes and
 // search_scan, grep_front / grep_run are grep_tiles' two passes and grep_scan with grep_core.h's phases, grep_call is GrepSink with
-// its windows, its staging, grep_finish and the tail.  A transcription of the kernels and nothing more: no truth, no case is here.
+// its windows, its staging, GrepSink::finish and the tail.  A transcription of the kernels and nothing more: no truth, no case is here.
 // The including program defines HOST_NAME, its name in a failing check's text, first.
 #ifndef BZH_SCAN_HOST_H
 #define BZH_SCAN_HOST_H
@@ -324,7 +324,7 @@ static void grep_call(const Bytes &text, const GrepTruth &tr, const MK &mk, uint
         }
         CHECK(at == text.size(), "the blocks are the text");
     }
-    if (s.walk.held) { // grep_finish: the bytes held back, where they lie
+    if (s.walk.held) { // GrepSink::finish: the bytes held back, where they lie
         CHECK(carry.size() == s.walk.carry, "the carry");
         const Text held(carry.data(), carry.size(), slack);
         const uint64_t ts = grep_run(s, held.p, s.walk.window(s.walk.carry, 0, true), 0, mk);
