@@ -221,6 +221,17 @@ __global__ void __launch_bounds__(256) mtf_prefix(Batch bt, int32_t *tlast, MtfT
 
 // ---- the walk: one wavefront per tile ---------------------------------------------------------------
 __device__ __forceinline__ int rdlane(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+// bit `bit` of v as a sign mask (0 or -1): one bit-field extract.  The empty statement keeps the compiler from seeing through
+// it: a ballot of `mask != 0` then compares the mask itself, where the compiler would shift v once more for a sign test.
+__device__ __forceinline__ int sign_of_bit(int v, int bit)
+{
+    int om = __builtin_amdgcn_sbfe(v, bit, 1);
+    asm("" : "+v"(om));
+    return om;
+}
+
+// (the comments `// part: NAME` in the walk are read by scripts/count_valu.py: it counts the compiled vector instructions of
+// the code between one such comment and the next, by the compiler's line table)
 
 // ---- the walk, parallel form: 64 run heads at a time ------------------------------------------------------------
 // Visiting the changed bytes of a tile one after the other is a scalar chain per byte (with ~160 byte values and
@@ -250,12 +261,14 @@ __global__ void __launch_bounds__(64) mtf_walk_par(Batch bt, const int32_t *tlas
     __shared__ uint32_t ls[4];
     __shared__ uint16_t Etab[256];         // list position of every name
     __shared__ __attribute__((aligned(16))) uint32_t MF[8]; // per chunk: the list places of its new symbols, one bit each
+    __shared__ uint4 NL[4];                // per chunk and 64 places: the word of MF (x, y), the new symbols above the word (z)
     // (the tile is walked in halves of 1024 bytes so that a wavefront needs under 5 KB of LDS: the walk is a chain of
     // dependent steps per wavefront, what hides its latency is the number of wavefronts a compute unit can hold)
     __shared__ uint8_t hsym[1024];     // names of the run heads of the half, in order
     __shared__ uint16_t hoff[1024];    // their offsets in the half
     __shared__ uint32_t hist[128];     // the tile's heads by position, two 16-bit counters a word (a tile has at most 4,096 heads)
-    const uint32_t num_names = build_names(bt.hasbyte + (size_t)b * 256, names, ls);
+    // (the same in every lane, and said so: what hangs on it -- regs, ebits -- then steers scalar branches, not lane masks)
+    const uint32_t num_names = (uint32_t)__builtin_amdgcn_readfirstlane((int)build_names(bt.hasbyte + (size_t)b * 256, names, ls));
     const int32_t *keys = tlast + ((size_t)b * MT + tile) * 256;
     const uint8_t *s = bt.bwt + (size_t)b * bt.S + base_p;
     uint16_t *out = bt.syms + (size_t)b * (bt.S + 64);
@@ -275,7 +288,8 @@ __global__ void __launch_bounds__(64) mtf_walk_par(Batch bt, const int32_t *tlas
     int k[4] = {keys[lane], keys[64 + lane], keys[128 + lane], keys[192 + lane]};
     int front;
     const uint32_t regs = (num_names + 63u) / 64u; // registers of 64 names in use (text: two or three of four)
-    const uint32_t ebits = num_names > 1u ? 32u - (uint32_t)__clz(num_names - 1u) : 1u; // bits of a list place
+    const uint32_t ebits = // bits of a list place
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)(num_names > 1u ? 32u - (uint32_t)__clz(num_names - 1u) : 1u));
     {
         uint32_t e[4] = {0, 0, 0, 0};
 #pragma unroll
@@ -311,8 +325,10 @@ __global__ void __launch_bounds__(64) mtf_walk_par(Batch bt, const int32_t *tlas
     }
     // ---- half by half: its run heads compacted into LDS (16 bytes a lane), then 64 run heads at a time
     uint32_t carry_last = (uint32_t)front;
+    const uint32_t lowlo = (uint32_t)((1ull << lane) - 1ull), lowhi = (uint32_t)(((1ull << lane) - 1ull) >> 32); // the lanes below me
 #pragma unroll 1
     for (uint32_t cbase = 0; cbase < tile_len; cbase += 1024) {
+        // part: half
         const uint4 raw = *reinterpret_cast<const uint4 *>(s + cbase + lane * 16); // (S is padded: the load stays inside the arena)
         uint32_t in[4] = {raw.x, raw.y, raw.z, raw.w};
 #pragma unroll
@@ -362,80 +378,87 @@ __global__ void __launch_bounds__(64) mtf_walk_par(Batch bt, const int32_t *tlas
         // 64 run heads at a time (one wavefront: program order is enough between the LDS phases)
 #pragma unroll 1
     for (uint32_t hb = 0; hb < H; hb += 64) {
+        // part: load+match-any
         const uint32_t idx = hb + (uint32_t)lane;
-        const bool act = idx < H;
+        // the lanes with a head: the first nact, a mask made on the scalar side
+        const uint32_t nact = H - hb < 64u ? H - hb : 64u;
+        const unsigned long long am = ~0ull >> (64u - nact);
+        const bool act = __builtin_amdgcn_inverse_ballot_w64(am);
         const uint32_t c = act ? hsym[idx] : 0u;
-        // lanes with my symbol (match-any over the 8 bits of the name)
-        const unsigned long long am = __ballot(act);
+        // (ebits is the same in every chunk; taken afresh here, each test on it is a scalar compare and branch of this chunk,
+        // where the compiler otherwise keeps eight lane masks across the loop and negates them with vector instructions)
+        uint32_t eb = ebits;
+        asm volatile("" : "+s"(eb));
+        // lanes with my symbol: match-any over the bits of the name.  Names are dense (build_names), so a name has no bit at
+        // or above ebits and a step over such a bit would keep every lane: the steps stop there (uniform).  One sign mask,
+        // one ballot and one three-input operation per half of the mask a bit (tile_rank, bwt_msd.h).
         uint32_t mlo = (uint32_t)am, mhi = (uint32_t)(am >> 32);
 #pragma unroll
         for (int bit = 0; bit < 8; bit++) {
-            const int om = ((int)(c << (31 - bit))) >> 31;
-            const unsigned long long bm = __builtin_amdgcn_ballot_w64(om != 0);
-            mlo &= ~((uint32_t)bm ^ (uint32_t)om);
-            mhi &= ~((uint32_t)(bm >> 32) ^ (uint32_t)om);
+            if (bit == 0 || (uint32_t)bit < eb) { // (ebits is 1 at least)
+                const int om = sign_of_bit((int)c, bit);
+                const unsigned long long bm = __builtin_amdgcn_ballot_w64(om != 0);
+                mlo = __builtin_amdgcn_bitop3_b32(mlo, (uint32_t)bm, (uint32_t)om, 0x90); // m & ~(bm ^ om)
+                mhi = __builtin_amdgcn_bitop3_b32(mhi, (uint32_t)(bm >> 32), (uint32_t)om, 0x90);
+            }
         }
-        const unsigned long long same = ((unsigned long long)mhi << 32) | mlo;
-        const unsigned long long lower = (1ull << lane) - 1ull, upto = (2ull << lane) - 1ull;
-        const unsigned long long below = same & lower;
-        const int p = below ? 63 - __clzll((long long)below) : -1; // previous occurrence in the chunk
-        const bool islast = act && (same & ~upto) == 0ull;
+        // part: pos+prefix-or+next-list
+        // the previous occurrence of my symbol in the chunk: the highest lane of the mask below me (p is read only where
+        // there is one)
+        const uint32_t blo = mlo & lowlo, bhi = mhi & lowhi;
+        const unsigned long long nobelow = __builtin_amdgcn_ballot_w64((blo | bhi) == 0u);
+        const unsigned long long firsts = am & nobelow; // new in the chunk: one lane per distinct symbol of the chunk
+        const bool isfirst = __builtin_amdgcn_inverse_ballot_w64(firsts);
+        const bool isrep = __builtin_amdgcn_inverse_ballot_w64(am & ~nobelow);
+        const int p = 63 - __builtin_clzll((((unsigned long long)bhi << 32) | blo) | 1ull);
         const int Eown = (int)Etab[c];
         // A = the lanes below me that are the LAST occurrence of their symbol before me: one lane per distinct symbol
         // seen so far.  They are all lower lanes except the predecessors q_v of the lanes v below me: a prefix OR of
-        // one bit per lane, six shuffle steps on the two halves of the mask.
-        uint32_t xlo = (act && p >= 0 && p < 32) ? 1u << p : 0u, xhi = (act && p >= 32) ? 1u << (p - 32) : 0u;
-        // (a prefix OR by data-parallel primitives, then one lane down: exclusive -- the predecessors of the lanes strictly below me)
-        xlo = wave_from_below(wave_incl_or(xlo));
-        xhi = wave_from_below(wave_incl_or(xhi));
-        const unsigned long long A = lower & ~(((unsigned long long)xhi << 32) | xlo);
-        int pos;
-        unsigned long long firsts = __ballot(act && p < 0); // one lane per distinct symbol of the chunk
+        // one bit per lane by data-parallel primitives on the two halves of the mask, then one lane down: exclusive.
+        const unsigned long long xb = (unsigned long long)(isrep ? 1u : 0u) << p;
+        const uint32_t ilo = wave_incl_or((uint32_t)xb), ihi = wave_incl_or((uint32_t)(xb >> 32));
+        const uint32_t xlo = wave_from_below(ilo), xhi = wave_from_below(ihi);
+        // the whole chunk's predecessors (lane 63 of the inclusive scan) are the lanes that are NOT the last of their symbol
+        const unsigned long long lasts =
+            am & ~(((unsigned long long)(uint32_t)rdlane((int)ihi, 63) << 32) | (uint32_t)rdlane((int)ilo, 63));
         const bool more = hb + 64 < H || !last_half;
         // MF: the places (in the list at chunk entry) of the chunk's new symbols, a bit each -- places are distinct
         if (lane < 8) MF[lane] = 0u;
-        if (act && p < 0) atomicOr(&MF[(uint32_t)Eown >> 5], 1u << ((uint32_t)Eown & 31u));
-        // a symbol that is new in the chunk: its place in the list at chunk entry + the new symbols BEFORE it in the chunk
-        // that were behind it in the list (one scalar step per distinct new symbol)
-        // = the lanes u below me among the chunk's first occurrences whose place E_u is larger than mine: a comparator over
-        // the ballots of the places' bits, most significant first (gt: lanes already known to be larger, eq: lanes that agree
-        // with me so far) -- at most eight steps whatever the number of new symbols, instead of a scalar step per new symbol
-        // (round 6; the kernel's time did not move, 522 against 514-527 us: the loop was not what it waits for)
-        int cntB;
+        if (isfirst) atomicOr(&MF[(uint32_t)Eown >> 5], 1u << ((uint32_t)Eown & 31u));
+        // One count over the lanes below me gives the position (v_mbcnt: the bits of a mask below my lane, added to a base):
+        //  * a symbol seen before in the chunk, last at lane p: the distinct symbols between p and me = A above lane p;
+        //  * a symbol that is new in the chunk: its place in the list at chunk entry + the new symbols BEFORE it in the chunk
+        //    that were behind it in the list = the lanes u below me among the chunk's first occurrences whose place E_u is
+        //    larger than mine: a comparator over the ballots of the places' bits, most significant first (gt: lanes already
+        //    known to be larger, eq: lanes that agree with me so far), on the two halves of the masks with my bit as a sign
+        //    mask.  A lane that is no first occurrence starts with eq = 0 and keeps its gt.
+        const unsigned long long ab = ~1ull << p;
+        uint32_t gtlo = isfirst ? 0u : __builtin_amdgcn_bitop3_b32((uint32_t)ab, xlo, xlo, 0x30); // above p, no predecessor
+        uint32_t gthi = isfirst ? 0u : __builtin_amdgcn_bitop3_b32((uint32_t)(ab >> 32), xhi, xhi, 0x30);
+        // part: places-comparator
         {
-            const bool isfirst = act && p < 0;
-            unsigned long long gt = 0ull, eq = firsts;
+            uint32_t eqlo = isfirst ? (uint32_t)firsts : 0u, eqhi = isfirst ? (uint32_t)(firsts >> 32) : 0u;
 #pragma unroll
             for (int bit = 7; bit >= 0; bit--) {
-                if ((uint32_t)bit >= ebits) continue; // (uniform: places are below the number of names)
-                const bool mine = ((uint32_t)Eown >> bit) & 1u;
-                const unsigned long long mb = __ballot(isfirst && mine);
-                gt |= mine ? 0ull : (eq & mb);
-                eq &= mine ? mb : ~mb;
-            }
-            cntB = (int)__popcll(gt & lower);
-        }
-        // the list when the next chunk begins: an unseen symbol moves back by the new symbols that were behind it = the
-        // bits of MF above its place (no loop over the new symbols: a shift and two population counts per name)
-        int eo[4] = {0, 0, 0, 0}, add[4] = {0, 0, 0, 0};
-        if (more) {
-            const uint4 ma = *reinterpret_cast<const uint4 *>(&MF[0]), mb = *reinterpret_cast<const uint4 *>(&MF[4]);
-            const unsigned long long W0 = ((unsigned long long)ma.y << 32) | ma.x, W1 = ((unsigned long long)ma.w << 32) | ma.z,
-                                     W2 = ((unsigned long long)mb.y << 32) | mb.x, W3 = ((unsigned long long)mb.w << 32) | mb.z;
-            const int T2 = (int)__popcll(W3), T1 = T2 + (int)__popcll(W2), T0 = T1 + (int)__popcll(W1);
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                if ((uint32_t)q < regs) {
-                    eo[q] = (int)Etab[q * 64 + lane];
-                    const uint32_t e = (uint32_t)eo[q], sel = e >> 6;
-                    const unsigned long long Ws = sel == 0u ? W0 : sel == 1u ? W1 : sel == 2u ? W2 : W3;
-                    const int Ts = sel == 0u ? T0 : sel == 1u ? T1 : sel == 2u ? T2 : 0;
-                    add[q] = (int)__popcll((Ws >> (e & 63u)) >> 1) + Ts;
-                }
+                if ((uint32_t)bit >= eb) continue; // (uniform: places are below the number of names)
+                const int om = sign_of_bit(Eown, bit);
+                const unsigned long long mb = __builtin_amdgcn_ballot_w64(om != 0) & firsts;
+                // In a first occurrence's lane eq stays inside firsts.  If no first occurrence has the bit, or all have it,
+                // such a lane's bit agrees with every lane of its eq: nothing moves to gt, nothing leaves eq (uniform skip; on
+                // text a chunk's new symbols sit at small places, and the high bits fall out here).
+                if (mb == 0ull || mb == firsts) continue;
+                uint32_t tlo = __builtin_amdgcn_bitop3_b32(eqlo, (uint32_t)mb, (uint32_t)om, 0x40); // eq & mb & ~om
+                uint32_t thi = __builtin_amdgcn_bitop3_b32(eqhi, (uint32_t)(mb >> 32), (uint32_t)om, 0x40);
+                asm("" : "+v"(tlo), "+v"(thi), "+v"(eqlo), "+v"(eqhi)); // (these first: eq is then updated in place, no copies)
+                gtlo |= tlo;
+                gthi |= thi;
+                eqlo = __builtin_amdgcn_bitop3_b32(eqlo, (uint32_t)mb, (uint32_t)om, 0x90); // eq & ~(mb ^ om)
+                eqhi = __builtin_amdgcn_bitop3_b32(eqhi, (uint32_t)(mb >> 32), (uint32_t)om, 0x90);
             }
         }
-        // a symbol seen before in the chunk, last at lane p: the distinct symbols between p and me
-        pos = p < 0 ? Eown + cntB : (int)__popcll(A & ~((2ull << p) - 1ull));
+        // part: pos+prefix-or+next-list
+        const int pos = (int)__builtin_amdgcn_mbcnt_hi(gthi, __builtin_amdgcn_mbcnt_lo(gtlo, isfirst ? (uint32_t)Eown : 0u));
+        // part: emit+hist+tail
         { // RLE2: digits of the zero run in front of every head (bijective base 2, lib/mtf.rs:46-65), then pos+1 (lib/mtf.rs:91-92)
             const int g = (int)(base_p + cbase) + (act ? (int)hoff[idx] : 0);
             int pg = (int)wave_from_below((uint32_t)g);
@@ -454,20 +477,38 @@ __global__ void __launch_bounds__(64) mtf_walk_par(Batch bt, const int32_t *tlas
             }
             fb += (uint32_t)__popc(zz & ((1u << d) - 1u));
             fa += d;
-            const uint32_t nact = H - hb < 64u ? H - hb : 64u;
             prevhead = rdlane(g, (int)nact - 1);
             woff += (uint32_t)rdlane((int)sc, 63);
         }
-        if (more) { // the list when the next chunk begins
+        // part: pos+prefix-or+next-list
+        // the list when the next chunk begins: an unseen symbol moves back by the new symbols that were behind it = the
+        // bits of MF above its place.  Four lanes lay out a record per 64 places -- the word of MF and the new symbols in the
+        // words above it -- and every name reads the record of its place with its own address: a shift and two population
+        // counts per name.  (The bit at an unseen name's own place is clear, MF holds new symbols only: no shift by one more;
+        // the names the chunk has seen are overwritten below.)
+        if (more) {
+            uint2 w = make_uint2(0u, 0u);
+            if (lane < 4) w = *reinterpret_cast<const uint2 *>(&MF[2 * lane]);
+            const uint32_t wc = (uint32_t)__popc(w.x) + (uint32_t)__popc(w.y);
+            const uint32_t above = BZH_DPP_SRC(wc, 0x101, 0xF) + BZH_DPP_SRC(wc, 0x102, 0xF) + BZH_DPP_SRC(wc, 0x103, 0xF); // row_shl:1..3
+            if (lane < 4) NL[lane] = make_uint4(w.x, w.y, above, 0u);
 #pragma unroll
-            for (int q = 0; q < 4; q++)
-                if ((uint32_t)q < regs) Etab[q * 64 + lane] = (uint16_t)(eo[q] + add[q]);
-            // (seen symbols are overwritten: position = distinct symbols whose last occurrence comes later)
-            const unsigned long long lasts = __ballot(islast);
-            if (islast) Etab[c] = (uint16_t)__popcll(lasts & ~upto);
+            for (int q = 0; q < 4; q++) {
+                if ((uint32_t)q < regs) {
+                    const uint32_t e = Etab[q * 64 + lane];
+                    const uint4 r = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(NL) + ((e >> 2) & 0x30u));
+                    Etab[q * 64 + lane] = (uint16_t)(e + r.z + (uint32_t)__popcll((((unsigned long long)r.y << 32) | r.x) >> (e & 63u)));
+                }
+            }
+            // (seen symbols are overwritten: position = distinct symbols whose last occurrence comes later = the last
+            // occurrences above my lane: all of them but mine and those below me)
+            if (__builtin_amdgcn_inverse_ballot_w64(lasts))
+                Etab[c] = (uint16_t)((uint32_t)__popcll(lasts) - 1u -
+                                     __builtin_amdgcn_mbcnt_hi((uint32_t)(lasts >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lasts, 0u)));
         }
     }
     }
+    // part: -
     // ---- the tile's histogram: one atomic per non-empty bin
     uint32_t *freqs = bt.freqs + (size_t)b * 258;
 #pragma unroll
