@@ -8,6 +8,10 @@
 // Every case is also expanded through windows -- all of them for an expansion of at most 48 bytes, 300 seeded ones and the
 // bytes around every tile seam otherwise -- each into a heap buffer of exactly the window's size, and compared with the same
 // bytes of the full expansion: a byte outside the window is a sanitizer report, a wrong one exit status 1.
+//
+//   unrle_host --layout <cases> <dump>   what lay_out() makes of every case, for tests/unrle_paths_model.py to be held against:
+//                                  [u32 tiles][u32 end state][u32 len] [u32 toff][u32 total] a tile
+//                                  [u32 state][u32 outn][u32 off] a thread, 256 a tile
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -74,10 +78,42 @@ static void expand_window(const std::vector<Tile> &tiles, uint32_t lo, uint32_t 
     free(buf);
 }
 
+// --layout: the tiles and threads as lay_out() places them, nothing expanded
+static int dump_layout(const char *cases, const char *dump)
+{
+    FILE *fi = fopen(cases, "rb"), *fo = fopen(dump, "wb");
+    if (!fi || !fo) return 2;
+    std::vector<Tile> tiles;
+    std::vector<uint32_t> words;
+    for (;;) {
+        uint32_t n;
+        if (fread(&n, 4, 1, fi) != 1) break;
+        std::vector<uint8_t> x(n ? n : 1);
+        if (n && fread(x.data(), 1, n, fi) != n) return 2;
+        uint32_t bsize;
+        const uint32_t end = lay_out(x.data(), n, tiles, &bsize);
+        words.assign({(uint32_t)tiles.size(), end, bsize});
+        for (const Tile &tl : tiles) {
+            words.push_back(tl.toff);
+            words.push_back(tl.total);
+        }
+        for (const Tile &tl : tiles)
+            for (const Thread &th : tl.th) {
+                words.push_back(th.state);
+                words.push_back(th.outn);
+                words.push_back(th.off);
+            }
+        if (fwrite(words.data(), 4, words.size(), fo) != words.size()) return 2;
+    }
+    fclose(fi);
+    return fclose(fo) ? 2 : 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc == 4 && strcmp(argv[1], "--layout") == 0) return dump_layout(argv[2], argv[3]);
     if (argc != 3) {
-        fprintf(stderr, "usage: unrle_host <cases> <results>\n");
+        fprintf(stderr, "usage: unrle_host [--layout] <cases> <results>\n");
         return 2;
     }
     tables();
