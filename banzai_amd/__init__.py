@@ -45,7 +45,7 @@ import numpy as np
 
 from . import _native
 
-__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex", "RecordIndex", "build_record_index", "record_index_of", "decompress_records", "search", "search_range", "grep", "grep_count", "matches", "matches_count", "PatternSet", "Regex", "regex_check",
+__all__ = ["encode", "encode_many", "encode_file", "decompress", "decompress_many", "decode", "decode_stream", "StreamDecompressor", "build_index", "decompress_range", "decompress_ranges", "BlockIndex", "RecordIndex", "build_record_index", "record_index_of", "decompress_records", "search", "search_range", "grep", "grep_count", "grep_many", "grep_many_count", "matches", "matches_count", "PatternSet", "Regex", "regex_check",
            "IndexedReader", "build_sync_index", "SyncIndex", "encode_indexed", "encode_indexed_stream", "recover", "recover_stream", "Recovered", "RecoveredBlock", "Context", "MultiContext", "BzhError"]
 
 Context = _native.Context
@@ -1162,6 +1162,57 @@ def grep(data, pattern, delim=b"\n", invert=False, index=None, device=0, before=
 def grep_count(data, pattern, delim=b"\n", invert=False, index=None, device=0):
     """The number of records grep() would return; nothing but two words crosses to the host."""
     return _grep(data, pattern, delim, invert, index, device, True)[0]
+
+
+def _grep_many(inputs, pattern, delim, invert, device, errors, count_only):
+    if errors not in ("raise", "return"):
+        raise ValueError('errors must be "raise" or "return"')
+    views = [_bytes_view(x, "grep_many") for x in inputs]
+    pattern, d = _pattern_arg(pattern), _delim_arg(delim)
+    if not views:
+        return []
+    ctx = _ctx(9, device)
+    out, group, size = [], [], 0
+
+    def run(group):
+        items, res = ctx.grep_many(group, pattern, d, bool(invert), count_only)
+        text, first, base = ctx.last_error(), True, len(out)
+        for k, it in enumerate(items):
+            st = int(it["status"])
+            if st != 0:  # (the library words the first failure of a call; the others carry their status)
+                err = BzhError(st, text if first else f"decode: input {k} failed")
+                first = False
+                if errors == "raise":
+                    err.args = (f"{err.args[0]} (item {base + k} of grep_many)",)
+                    raise err
+                out.append(err)
+            else:
+                out.append(int(it["selected"]) if count_only else res[k])
+
+    for v in views:
+        if group and size + len(v) + 1 > MANY_GROUP_LIMIT:
+            run(group)
+            group, size = [], 0
+        group.append(v)
+        size += len(v) + 1
+    run(group)
+    return out
+
+
+def grep_many(inputs, pattern, delim=b"\n", invert=False, device=0, errors="raise"):
+    """grep() over every item of `inputs` (bytes-like; each one or more complete bzip2 streams) in one pass on the GPU per group
+    of inputs (bzh_grep_many) -> [(bytes, entries)], item k equal to grep(inputs[k], pattern, delim, invert): the inputs are
+    decoded into one device buffer as many texts with walls between them -- no match crosses from one input into the next, record
+    numbers and offsets restart with every input, and an assertion of a Regex sees an input's two ends as the text's edges.
+    `pattern` is bytes, a PatternSet or a Regex.  A damaged item does not touch the others.  errors="raise": the first failed item
+    raises BzhError naming it; errors="return": the BzhError instance stands in that item's place.  Groups keep a call's inputs
+    below MANY_GROUP_LIMIT bytes, as decompress_many's do."""
+    return _grep_many(inputs, pattern, delim, invert, device, errors, False)
+
+
+def grep_many_count(inputs, pattern, delim=b"\n", invert=False, device=0, errors="raise"):
+    """The number of records grep_many() would return for every item -> [int]; only the counts cross to the host."""
+    return _grep_many(inputs, pattern, delim, invert, device, errors, True)
 
 
 def _matches(data, pattern, delim, index, device, count_only):

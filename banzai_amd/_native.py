@@ -225,6 +225,26 @@ class GrepStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class GrepManyItem(ctypes.Structure):
+    """bzh_grep_many_item: what bzh_grep says of one input of a bzh_grep_many* call"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("decoded", "records", "selected", "out_bytes")] + \
+               [("status", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
+GREP_MANY_ITEM_DTYPE = np.dtype([("decoded", "<u8"), ("records", "<u8"), ("selected", "<u8"), ("out_bytes", "<u8"), ("status", "<i4"),
+                                 ("reserved", "<u4")])
+assert GREP_MANY_ITEM_DTYPE.itemsize == ctypes.sizeof(GrepManyItem) == 40
+grepmanyp = ctypes.POINTER(GrepManyItem)
+
+
+class GrepManyStats(ctypes.Structure):
+    """bzh_grep_many_stats"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("inputs", "inputs_failed", "segments", "virtual_tiles", "shared_tiles", "staging_retries")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class GrepContextStats(ctypes.Structure):
     """bzh_grep_context_stats"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("matched", "context", "groups", "pending_peak")]
@@ -638,13 +658,25 @@ for _name in ("raw_device", "device", "", "index_device", "index"):
 
 
 def _patset_twin(name):
-    """bzh_search* -> bzh_search_patset*, bzh_grep* -> bzh_grep_patset*, bzh_match* -> bzh_match_patset*"""
-    return name.replace("bzh_search", "bzh_search_patset", 1).replace("bzh_grep", "bzh_grep_patset", 1).replace("bzh_match", "bzh_match_patset", 1)
+    """bzh_search* -> bzh_search_patset*, bzh_grep* -> bzh_grep_patset*, bzh_match* -> bzh_match_patset*,
+    bzh_grep_many* -> bzh_grep_many_patset*"""
+    for stem in ("bzh_grep_many", "bzh_search", "bzh_grep", "bzh_match"):
+        if name.startswith(stem):
+            return stem + "_patset" + name[len(stem):]
+    return name
 
+
+# bzh_grep_many*: many texts or inputs, what is looked for, the rooms, one item per input, the counts
+_many_tail = [u8p, ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_size_t, grepp, ctypes.c_size_t, grepmanyp, szp, u64p]
+SIGNATURES["bzh_grep_many_raw_device"] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, szp, szp, ctypes.c_size_t] + _many_tail)
+SIGNATURES["bzh_grep_many_device"] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, szp, szp, ctypes.c_size_t] + _many_tail)
+SIGNATURES["bzh_grep_many"] = (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(u8p), szp, ctypes.c_size_t] + _many_tail)
+SIGNATURES["bzh_get_grep_many_stats"] = (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(GrepManyStats)])
 
 # the calls that take a set: their twin's arguments with (pat, plen) replaced by the set, and the hits by bzh_set_hit
 for _name in ("bzh_search_raw_device", "bzh_search_device", "bzh_search", "bzh_search_range_device", "bzh_search_range",
               "bzh_grep_raw_device", "bzh_grep_device", "bzh_grep", "bzh_grep_index_device", "bzh_grep_index",
+              "bzh_grep_many_raw_device", "bzh_grep_many_device", "bzh_grep_many",
               "bzh_match_raw_device", "bzh_match_device", "bzh_match", "bzh_match_index_device", "bzh_match_index"):
     _res, _args = SIGNATURES[_name]
     _at = next(k for k in range(len(_args) - 1) if _args[k] is u8p and _args[k + 1] is ctypes.c_size_t and _args[k + 2] is ctypes.c_uint)
@@ -1548,6 +1580,83 @@ class Context:
     def grep_index_device(self, d_in, n, entries, pattern, d_out, cap, room, points=None, delim=b"\n", invert=False):
         """bzh_grep_index_device on integer device addresses; `room` entries -> (status, nrecs, out_total, entries)"""
         return self._scan_index_device("grep", d_in, n, entries, pattern, d_out, cap, room, points, delim, invert)
+
+    # ---- grep over many inputs (bzh_grep_many*) ----
+    def _grep_many_call(self, route, head, count, pattern, delim, invert, d_out, cap, room, flags=None):
+        """bzh_grep_many<route>(head..., what, flags, delim, out, cap, `room` entries, items, counts) -> (status, nrecs, out_total,
+        entries, items as a structured array of GREP_MANY_ITEM_DTYPE).  BZH_E_CAP (-4) is handed back like every status: the
+        counts and the items are exact then too."""
+        fn, what, fl, d = self._scan_what("grep", "_many" + route, pattern, delim, invert)
+        got, total = ctypes.c_size_t(0), ctypes.c_uint64(0)
+        ent = np.zeros(max(room, 1), dtype=GREP_ENTRY_DTYPE)
+        items = np.zeros(max(count, 1), dtype=GREP_MANY_ITEM_DTYPE)
+        st = fn(self._h, *head, *what, fl if flags is None else flags, d, d_out, cap, ent.ctypes.data_as(grepp) if room else None, room,
+                items.ctypes.data_as(grepmanyp) if count else None, ctypes.byref(got), ctypes.byref(total))
+        self.grep_status = st
+        return st, int(got.value), int(total.value), ent[:min(room, int(got.value))].copy(), items[:count].copy()
+
+    @staticmethod
+    def _segments(offs, lens):
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        if offs.size != lens.size:
+            raise ValueError("as many offsets as lengths")
+        return offs, lens, (ptr(offs, szp) if offs.size else None, ptr(lens, szp) if offs.size else None, offs.size)
+
+    def grep_many_raw_device(self, d_raw, n, offs, lens, pattern, d_out, cap, room, delim=b"\n", invert=False, flags=None):
+        """bzh_grep_many_raw_device on integer device addresses: the texts d_raw[offs[k], +lens[k]) -> as _grep_many_call"""
+        offs, lens, seg = self._segments(offs, lens)
+        return self._grep_many_call("_raw_device", (ctypes.c_void_p(d_raw), n, *seg), offs.size, pattern, delim, invert, ctypes.c_void_p(d_out), cap,
+                                    room, flags)
+
+    def grep_many_device(self, d_in, n, offs, lens, pattern, d_out, cap, room, delim=b"\n", invert=False):
+        """bzh_grep_many_device on integer device addresses: the inputs d_in[offs[k], +lens[k]) -> as _grep_many_call"""
+        offs, lens, seg = self._segments(offs, lens)
+        return self._grep_many_call("_device", (ctypes.c_void_p(d_in), n, *seg), offs.size, pattern, delim, invert, ctypes.c_void_p(d_out), cap, room)
+
+    def grep_many_host_raw(self, inputs, pattern, cap, room, delim=b"\n", invert=False):
+        """one bzh_grep_many call with rooms of `cap` bytes and `room` entries (0, 0: a counting call) -> (status, nrecs, out_total,
+        the out buffer, entries, items)"""
+        arrs = [np.frombuffer(x, dtype=np.uint8) for x in inputs]
+        count = len(arrs)
+        keep = [np.ascontiguousarray(a) if a.size else np.zeros(1, np.uint8) for a in arrs]
+        lens = np.array([a.size for a in arrs], dtype=np.uint64)
+        ins = (u8p * max(count, 1))(*[ptr(a) for a in keep])
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        st, got, total, ent, items = self._grep_many_call("", (ins, ptr(lens, szp) if count else None, count), count, pattern, delim, invert,
+                                                          ptr(out) if cap else None, cap, room)
+        return st, got, total, out, ent, items
+
+    def grep_many(self, inputs, pattern, delim=b"\n", invert=False, count_only=False):
+        """bzh_grep_many: every input grepped as bzh_grep greps it alone, in one pass -> (items, [(bytes, entries)]), a failed
+        input's pair None; count_only: (items, None) from a counting call.  The rooms are a first guess, then the exact ones."""
+        inputs = list(inputs)
+        if count_only:
+            st, _, _, _, _, items = self.grep_many_host_raw(inputs, pattern, 0, 0, delim, invert)
+            self.check(st)
+            return items, None
+        cap, room = self.GREP_GUESS
+        for _ in range(2):
+            st, got, total, out, ent, items = self.grep_many_host_raw(inputs, pattern, cap, room, delim, invert)
+            if st == -4 and (total > cap or got > room):
+                cap, room = total, got
+                continue
+            self.check(st)
+            res, e0 = [], 0
+            for it in items:
+                e = ent[e0:e0 + int(it["selected"])].copy()
+                b0 = int(e["out_off"][0]) if e.size else 0
+                if e.size:
+                    e["out_off"] -= np.uint64(b0)  # (as bzh_grep of the input alone numbers them)
+                res.append(None if it["status"] != 0 else (out[b0:b0 + int(it["out_bytes"])].tobytes(), e))
+                e0 += int(it["selected"])
+            return items, res
+        raise BzhError(-5, "grep many: the second call selected more than the first")
+
+    def grep_many_stats(self):
+        s = GrepManyStats()
+        self.check(lib().bzh_get_grep_many_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
 
     def grep_stats(self):
         s = GrepStats()

@@ -19,6 +19,7 @@
 #include "decode_records_plan.h"
 #include "decode_recover_plan.h"
 #include "encode_plan.h"
+#include "grep_many_plan.h"
 #include "recover_gather.h"
 #include "stream_index.h"
 
@@ -2419,6 +2420,212 @@ extern "C" int bzh_decode_many(bzh_ctx *ctx, const uint8_t *const *ins, const si
 }
 
 extern "C" int bzh_get_decode_many_stats(const bzh_ctx *ctx, bzh_decode_many_stats *out) { return stats_get(ctx, &bzh_ctx::mstats, out); }
+
+// ---- grep over many inputs (grep_many.hip's GrepSink::raw_many; the tables: grep_many_plan.h).  Three routes to the one segmented
+// pass: texts that lie in HBM, inputs decoded by bzh_decode_many_device into the grep's staging buffer, and the latter from the host.
+static_assert(sizeof(bzh_grep_many_item) == 40, "an item is five words");
+
+// what every route checks first, in scan_begin's order; behind it the statistics are fresh and the sink is armed
+static int grep_many_begin(bzh_ctx *ctx, GrepSink &s, size_t count, const void *a0, const void *a1, bzh_grep_many_item *items, size_t *nrecs,
+                           uint64_t *out_total)
+{
+    if (count && (!a0 || !a1 || !items)) {
+        bzh_set_error(ctx, "grep many: a null array for %zu inputs", count);
+        return BZH_E_ARG;
+    }
+    BZH_TRY(scan_begin(ctx, GREP, s, nrecs, out_total));
+    memset(&ctx->gmstats, 0, sizeof ctx->gmstats);
+    if (count) memset(items, 0, count * sizeof *items);
+    if (s.ctx_on) {
+        bzh_set_error(ctx, "grep many: context records are set (bzh_grep_set_context %u, %u) and are not built over many inputs; set 0, 0",
+                      ctx->grep_before, ctx->grep_after);
+        return BZH_E_ARG;
+    }
+    if (count > 0x7FFFFFFFull) {
+        bzh_set_error(ctx, "grep many: %zu inputs are beyond one call", count);
+        return BZH_E_ARG;
+    }
+    return BZH_OK;
+}
+
+// The pass over checked segments of d_raw, what the sink held back (nothing), the last wait, and the answer.  status: of every
+// input (null: all BZH_OK); a failed one has an empty segment.
+static int grep_many_pass(bzh_ctx *ctx, GrepSink &s, const uint8_t *d_raw, const uint64_t *offs, const uint64_t *lens, const int *status, size_t count,
+                          bzh_grep_many_item *items, size_t *nrecs, uint64_t *out_total)
+{
+    BzgmPlan plan;
+    bzh_grep_many_stats &gm = ctx->gmstats;
+    const bool built = plan.build(offs, lens, count);
+    gm.inputs = count, gm.segments = plan.nonempty, gm.virtual_tiles = plan.rows, gm.shared_tiles = plan.shared;
+    if (!built) {
+        bzh_set_error(ctx, "grep many: %llu virtual tiles are beyond one launch", (unsigned long long)plan.rows);
+        return BZH_E_ARG;
+    }
+    std::vector<uint64_t> tot(count * BZGM_TOTALS);
+    int rc = s.raw_many(ctx, d_raw, plan, tot.data());
+    if (rc == BZH_OK) rc = s.finish(ctx);
+    HIP_TRY(ctx, bzh_stream_wait(ctx->stream));
+    if (rc != BZH_OK) return rc;
+    for (size_t k = 0; k < count; k++) {
+        const uint64_t *t = &tot[k * BZGM_TOTALS];
+        items[k] = bzh_grep_many_item{lens[k], t[BZGM_T_RECORDS], t[BZGM_T_SEL], t[BZGM_T_BYTES], status ? status[k] : BZH_OK, 0};
+        if (items[k].status != BZH_OK) gm.inputs_failed++;
+    }
+    return s.report(ctx, nrecs, out_total);
+}
+
+static int grep_many_raw_device(bzh_ctx *ctx, GrepSink &s, const void *d_raw, size_t n, const size_t *offs, const size_t *lens, size_t count,
+                                bzh_grep_many_item *items, size_t *nrecs, uint64_t *out_total)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    static_assert(sizeof(size_t) == 8, "the segments are 64-bit words");
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_raw && n)) return BZH_E_ARG;
+    BZH_TRY(grep_many_begin(ctx, s, count, offs, lens, items, nrecs, out_total));
+    if ((uintptr_t)d_raw & 15u) {
+        bzh_set_error(ctx, "grep many: the buffer is not 16-byte aligned");
+        return BZH_E_ARG;
+    }
+    size_t bad = 0;
+    if (const char *what = bzgm_check((const uint64_t *)offs, (const uint64_t *)lens, count, n, &bad)) {
+        bzh_set_error(ctx, "grep many: segment %zu is bytes [%zu, +%zu): %s", bad, offs[bad], lens[bad], what);
+        return BZH_E_ARG;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return grep_many_pass(ctx, s, (const uint8_t *)d_raw, (const uint64_t *)offs, (const uint64_t *)lens, nullptr, count, items, nrecs, out_total);
+    });
+}
+
+// the first size of the staging buffer, from the compressed bytes: text rarely expands beyond six times
+static size_t grep_many_stage_guess(size_t n) { return n > (~(size_t)0 >> 4) ? n : 6 * n + ((size_t)1 << 20); }
+
+static int grep_many_device(bzh_ctx *ctx, GrepSink &s, const void *d_in, size_t n, const size_t *in_offs, const size_t *in_lens, size_t count,
+                            bzh_grep_many_item *items, size_t *nrecs, uint64_t *out_total)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!d_in && n)) return BZH_E_ARG;
+    BZH_TRY(grep_many_begin(ctx, s, count, in_offs, in_lens, items, nrecs, out_total));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<size_t> out_offs(count), out_lens(count);
+    std::vector<int> status(count);
+    size_t room = grep_many_stage_guess(n);
+    uint64_t retries = 0;
+    for (;;) { // (at most twice: the second room is the one the walk asked for)
+        BZH_TRY(ctx->search_ws.reserve(ctx, room + 16, "the grep's staging", grow_mib));
+        ctx->gstats.staging_peak = ctx->search_ws.cap;
+        const int rc = bzh_decode_many_device(ctx, d_in, n, in_offs, in_lens, count, ctx->search_ws.p, room, out_offs.data(), out_lens.data(),
+                                              status.data(), nullptr);
+        if (rc == BZH_E_CAP && !retries && count) {
+            // the walk's total, the gaps that failed inputs leave included: a failed input has out_lens 0, so the last offset
+            // and length alone fall short where trailing inputs failed behind placed blocks
+            room = std::max<size_t>((size_t)ctx->dstats.out_bytes, out_offs[count - 1] + out_lens[count - 1]);
+            retries++;
+            continue;
+        }
+        BZH_TRY(rc);
+        break;
+    }
+    // a failed input owns no byte: an empty segment where the one in front of it ends
+    std::vector<uint64_t> offs(count), lens(count);
+    uint64_t end = 0;
+    for (size_t k = 0; k < count; k++) {
+        const bool ok = status[k] == BZH_OK;
+        offs[k] = ok ? out_offs[k] : end, lens[k] = ok ? out_lens[k] : 0;
+        end = offs[k] + lens[k];
+    }
+    const uint64_t staging = ctx->gstats.staging_peak;
+    const int rc = grep_many_pass(ctx, s, ctx->search_ws.p, offs.data(), lens.data(), status.data(), count, items, nrecs, out_total);
+    ctx->gstats.staging_peak = staging; // (finish() leaves the other counters of the pass)
+    ctx->gmstats.staging_retries = retries;
+    return rc;
+    });
+}
+
+static int grep_many_host(bzh_ctx *ctx, GrepSink &s, const uint8_t *const *ins, const size_t *lens, size_t count, bzh_grep_many_item *items,
+                          size_t *nrecs, uint64_t *out_total)
+{
+    return bzh_guard(ctx, [&]() -> int {
+    uint8_t *const out = (uint8_t *)s.args.out;
+    if (ctx) stream_join(ctx);
+    if (!ctx || (!out && s.args.cap)) return BZH_E_ARG;
+    // (as scan_host: the device route begins the call, with the staged output in the caller's place -- a host buffer needs no
+    // alignment; here only what the packing itself reads)
+    if (count && (!ins || !lens || !items)) {
+        bzh_set_error(ctx, "grep many: a null array for %zu inputs", count);
+        return BZH_E_ARG;
+    }
+    if (!nrecs || !out_total) return BZH_E_ARG;
+    *nrecs = 0, *out_total = 0;
+    size_t total = 0;
+    std::vector<size_t> offs(count);
+    for (size_t k = 0; k < count; k++) {
+        if (!ins[k] && lens[k]) {
+            bzh_set_error(ctx, "grep many: input %zu is null with %zu bytes claimed", k, lens[k]);
+            return BZH_E_ARG;
+        }
+        offs[k] = total;
+        total += lens[k];
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BZH_TRY(ensure_stage(ctx, ctx->d_stage_in, total + 16));
+    if (out) BZH_TRY(ensure_stage(ctx, ctx->d_stage_out, scan_stage_room(out, s.args.cap)));
+    if (total) { // all inputs in one copy, back to back
+        ctx->many_pack.resize(total);
+        for (size_t k = 0; k < count; k++)
+            if (lens[k]) memcpy(ctx->many_pack.data() + offs[k], ins[k], lens[k]);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stage_in, ctx->many_pack.data(), total, hipMemcpyHostToDevice, ctx->stream));
+    }
+    s.args.out = out ? ctx->d_stage_out.p : nullptr;
+    BZH_TRY(grep_many_device(ctx, s, ctx->d_stage_in, total, offs.data(), lens, count, items, nrecs, out_total));
+    return decode_unstage(ctx, out, out ? (size_t)*out_total : 0);
+    });
+}
+
+extern "C" int bzh_grep_many_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const size_t *offs, const size_t *lens, size_t count,
+                                        const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, void *d_out, size_t cap,
+                                        bzh_grep_entry *ent, size_t max, bzh_grep_many_item *items, size_t *nrecs, uint64_t *out_total)
+{
+    GrepSink s(what_pat(pat, plen), flags, delim, d_out, cap, ent, max);
+    return grep_many_raw_device(ctx, s, d_raw, n, offs, lens, count, items, nrecs, out_total);
+}
+extern "C" int bzh_grep_many_patset_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const size_t *offs, const size_t *lens, size_t count,
+                                               const bzh_patset *set, unsigned flags, uint8_t delim, void *d_out, size_t cap,
+                                               bzh_grep_entry *ent, size_t max, bzh_grep_many_item *items, size_t *nrecs, uint64_t *out_total)
+{
+    GrepSink s(what_set(set), flags, delim, d_out, cap, ent, max);
+    return grep_many_raw_device(ctx, s, d_raw, n, offs, lens, count, items, nrecs, out_total);
+}
+extern "C" int bzh_grep_many_device(bzh_ctx *ctx, const void *d_in, size_t n, const size_t *in_offs, const size_t *in_lens, size_t count,
+                                    const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, void *d_out, size_t cap,
+                                    bzh_grep_entry *ent, size_t max, bzh_grep_many_item *items, size_t *nrecs, uint64_t *out_total)
+{
+    GrepSink s(what_pat(pat, plen), flags, delim, d_out, cap, ent, max);
+    return grep_many_device(ctx, s, d_in, n, in_offs, in_lens, count, items, nrecs, out_total);
+}
+extern "C" int bzh_grep_many_patset_device(bzh_ctx *ctx, const void *d_in, size_t n, const size_t *in_offs, const size_t *in_lens, size_t count,
+                                           const bzh_patset *set, unsigned flags, uint8_t delim, void *d_out, size_t cap,
+                                           bzh_grep_entry *ent, size_t max, bzh_grep_many_item *items, size_t *nrecs, uint64_t *out_total)
+{
+    GrepSink s(what_set(set), flags, delim, d_out, cap, ent, max);
+    return grep_many_device(ctx, s, d_in, n, in_offs, in_lens, count, items, nrecs, out_total);
+}
+extern "C" int bzh_grep_many(bzh_ctx *ctx, const uint8_t *const *ins, const size_t *lens, size_t count, const uint8_t *pat, size_t plen,
+                             unsigned flags, uint8_t delim, uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max,
+                             bzh_grep_many_item *items, size_t *nrecs, uint64_t *out_total)
+{
+    GrepSink s(what_pat(pat, plen), flags, delim, out, cap, ent, max);
+    return grep_many_host(ctx, s, ins, lens, count, items, nrecs, out_total);
+}
+extern "C" int bzh_grep_many_patset(bzh_ctx *ctx, const uint8_t *const *ins, const size_t *lens, size_t count, const bzh_patset *set,
+                                    unsigned flags, uint8_t delim, uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max,
+                                    bzh_grep_many_item *items, size_t *nrecs, uint64_t *out_total)
+{
+    GrepSink s(what_set(set), flags, delim, out, cap, ent, max);
+    return grep_many_host(ctx, s, ins, lens, count, items, nrecs, out_total);
+}
+
+extern "C" int bzh_get_grep_many_stats(const bzh_ctx *ctx, bzh_grep_many_stats *out) { return stats_get(ctx, &bzh_ctx::gmstats, out); }
 
 // ---- recovery (decode.hip's decode_recover_run; recover.hip's gather): per block what bzh_decode is per input
 extern "C" int bzh_recover_device(bzh_ctx *ctx, const void *d_in, size_t n, void *d_out, size_t cap, size_t *out_len, bzh_recover_entry *ent,

@@ -79,6 +79,12 @@ const char *VERSION = "version alpha 0.3.1-hip";
             "  -C --context <n>          ... or both; every line once and in order, chosen on the device in the same pass,\n"
             "                            a line '--' between two groups of lines that are not adjacent; --count still\n"
             "                            prints the selected lines alone\n"
+            "     --grep <string> <input_path> <input_path> ...\n"
+            "                            several inputs, with --grep only: every file's selected lines as 'name:line'\n"
+            "                            ('name:N:line' with --line-number, 'name:count' a file with --count), all files in\n"
+            "                            one pass on the GPU (bzh_grep_many); a file that fails is named on standard error,\n"
+            "                            the others are still written and the exit status is 3; not with -o, -b, -A, -B, -C, --index\n"
+            "     --no-filename          with --grep and several inputs: no 'name:' in front of the lines\n"
             "     --hex                  with --search or --grep: <string> is given as hex digits\n"
             "     --count                with --search: print the number of occurrences alone; with --grep: of lines\n"
             "     -e <string>            with --search or --grep, in place of their <string> or beside it, any number of\n"
@@ -193,8 +199,14 @@ int main(int argc, char **argv)
     bool have_in = false, in_stdin = false, out_stdout = false, have_out = false;
     int keep = -1, level = 9;
     bool decompress = false, recover = false, level_given = false, dstream = false;
+    std::vector<std::string> more_inputs; // the inputs behind the first: --grep takes several files (judged behind the last argument)
+    bool no_filename = false;
     auto set_input = [&](const std::string &p, bool is_stdin) {
-        if (have_in) die(ERR_ARGS, "Only one input may be specified");
+        if (have_in) {
+            if (is_stdin || in_stdin) die(ERR_ARGS, "Only one input may be specified");
+            more_inputs.push_back(p);
+            return;
+        }
         have_in = true;
         in_stdin = is_stdin;
         in_path = p;
@@ -287,6 +299,7 @@ int main(int argc, char **argv)
             else if (a == "--byte-offset") byte_offset = true;
             else if (a == "--hex") needle_hex = true;
             else if (a == "--count") count_only = true;
+            else if (a == "--no-filename") no_filename = true;
             else if (a == "--patterns") expect = PATFILE;
             else if (a == "--ignore-case") ignore_case = true;
             else if (a == "--regex") regex = true;
@@ -334,6 +347,12 @@ int main(int argc, char **argv)
         } else {
             set_input(a, false);
         }
+    }
+    if (!more_inputs.empty() && !grepping) die(ERR_ARGS, "Only one input may be specified");
+    if (no_filename && !grepping) die(ERR_ARGS, "'--no-filename' goes with '--grep'");
+    if (!more_inputs.empty()) { // several inputs go through one bzh_grep_many: what it does not do is refused by name
+        const char *opt = only_matching ? "-o" : byte_offset ? "-b" : context_given ? "-A', '-B' and '-C" : !index_path.empty() ? "--index" : nullptr;
+        if (opt) die(ERR_ARGS, std::string("'") + opt + "' takes one input: several inputs go with '--grep' and '--hex', '--invert', '--count', '--line-number', '--no-filename'");
     }
     if (expect == IDXPATH || expect == MKIDXPATH) die(ERR_ARGS, "Arguments '--index' and '--make-index' require a file path");
     if (expect == INTERVAL) die(ERR_ARGS, "Argument '--interval' requires a number of groups, 0 to 32767");
@@ -452,7 +471,27 @@ int main(int argc, char **argv)
         uint64_t lo = 0, hi = 0;
         const bzh_range want = ranges.empty() ? bzh_range{0, UINT64_MAX} : ranges[0];
         bool records = true;
-        if (!index_path.empty()) {
+        // --grep over several inputs: every file whole; one that cannot be read is named now, fails alone and is left out of the call
+        // (the library words the first failure of a call: that text must belong to a file that was handed to it)
+        std::vector<std::string> names;
+        std::vector<std::vector<uint8_t>> many;
+        const bool several = !more_inputs.empty();
+        bool unread = false;
+        if (several) {
+            std::vector<std::string> paths{in_path};
+            paths.insert(paths.end(), more_inputs.begin(), more_inputs.end());
+            for (const std::string &path : paths) {
+                std::vector<uint8_t> bytes;
+                FILE *sf = fopen(path.c_str(), "rb");
+                if (!sf || !slurp(sf, bytes)) {
+                    fprintf(stderr, "bnzhip: %s: %s\n", path.c_str(), sf ? "read failed" : strerror(errno));
+                    unread = true;
+                } else {
+                    names.push_back(path), many.push_back(std::move(bytes));
+                }
+                if (sf) fclose(sf);
+            }
+        } else if (!index_path.empty()) {
             FILE *xf = fopen(index_path.c_str(), "rb");
             if (!xf) die(ERR_FILESYSTEM, "[filesystem error] cannot open " + index_path + ": " + strerror(errno));
             const bool xok = slurp(xf, blob);
@@ -538,6 +577,59 @@ int main(int argc, char **argv)
             bzh_regex_info ri;
             if (regex && bzh_regex_get_info(set, &ri) == BZH_OK && ri.unbounded)
                 fprintf(stderr, "bnzhip: the expressions have matches longer than %d bytes: those are not found\n", BZH_REGEX_MAX_SPAN);
+        }
+        if (several) { // --grep over several inputs: one bzh_grep_many; a first try with a guess, a second with the exact rooms
+            const unsigned gflags = invert ? BZH_GREP_INVERT : 0;
+            std::vector<const uint8_t *> ins;
+            std::vector<size_t> lens;
+            for (const auto &m : many) ins.push_back(m.empty() ? &nothing : m.data()), lens.push_back(m.size());
+            std::vector<uint8_t> out(count_only ? 0 : (size_t)16 << 20);
+            std::vector<bzh_grep_entry> lines(count_only ? 0 : (size_t)1 << 16);
+            std::vector<bzh_grep_many_item> items(names.size());
+            size_t nrecs = 0;
+            uint64_t total = 0;
+            for (int attempt = 0; attempt < 2; attempt++) {
+                uint8_t *op = out.empty() ? nullptr : out.data();
+                bzh_grep_entry *lp = lines.empty() ? nullptr : lines.data();
+                if (set)
+                    rs = bzh_grep_many_patset(sctx, ins.data(), lens.data(), ins.size(), set, gflags, '\n', op, out.size(), lp, lines.size(), items.data(),
+                                              &nrecs, &total);
+                else
+                    rs = bzh_grep_many(sctx, ins.data(), lens.data(), ins.size(), pat, needle.size(), gflags, '\n', op, out.size(), lp, lines.size(),
+                                       items.data(), &nrecs, &total);
+                if (rs != BZH_E_CAP || count_only || attempt) break;
+                out.resize(std::max<size_t>((size_t)total, 16));
+                lines.resize(std::max<size_t>(nrecs, 1));
+            }
+            const std::string msg = rs == BZH_OK ? "" : std::string("error during grep: ") + bzh_strerror(rs) + ": " + bzh_last_error(sctx);
+            const std::string first_failure = bzh_last_error(sctx);
+            bzh_patset_destroy(set);
+            bzh_destroy(sctx);
+            if (rs != BZH_OK) die(ERR_OUTPUT, msg);
+            bool ok = true, failed = unread, worded = false;
+            size_t e = 0;
+            for (size_t k = 0; k < names.size() && ok; k++) {
+                const std::string prefix = no_filename ? "" : names[k] + ":";
+                if (items[k].status != BZH_OK) { // (the library words the first failure of a call; the others carry their status)
+                    failed = true;
+                    fprintf(stderr, "bnzhip: %s: %s%s%s\n", names[k].c_str(), bzh_strerror(items[k].status), worded ? "" : ": ", worded ? "" : first_failure.c_str());
+                    worded = true;
+                    continue;
+                }
+                if (count_only) {
+                    printf("%s%llu\n", prefix.c_str(), (unsigned long long)items[k].selected);
+                    continue;
+                }
+                for (uint64_t j = 0; j < items[k].selected && ok; j++, e++) {
+                    const size_t len = (size_t)lines[e].len;
+                    fputs(prefix.c_str(), stdout);
+                    if (line_number) printf("%llu:", (unsigned long long)lines[e].record + 1);
+                    ok = fwrite(out.data() + lines[e].out_off, 1, len, stdout) == len;
+                    if (ok && len && out[lines[e].out_off + len - 1] != '\n') ok = fputc('\n', stdout) != EOF; // (a last line without its newline)
+                }
+            }
+            if (!ok || fflush(stdout) != 0) die(ERR_OUTPUT, "error during grep: write failed");
+            return failed ? ERR_OUTPUT : SUCCESS;
         }
         if (grepping && only_matching && !count_only) { // --grep -o: the matched parts come back compacted, an entry each
             const unsigned mflags = line_number ? BZH_MATCH_RECORDS : 0;

@@ -196,6 +196,8 @@ struct bzh_ctx {
     bzh_grep_stats gstats{};        // of the last bzh_grep* call
     bzh_grep_context_stats gcstats{};
     uint32_t grep_before = 0, grep_after = 0; // bzh_grep_set_context
+    DevBuf grep_many_tab;             // bzh_grep_many*: the segment table, the virtual tile table, the segments' totals
+    bzh_grep_many_stats gmstats{};    // of the last bzh_grep_many* call
     DevBuf match_tab, match_ent;    // bzh_match*: a window's tile tables, its entries
     bzh_match_stats mtstats{};      // of the last bzh_match* call
     struct DStream *dstrm = nullptr; // streaming decode (bzh_dstream_*, decode.hip): made by the first begin, freed by dstream_free
@@ -759,6 +761,10 @@ struct GrepSink final : ScanSink {
     int room(bzh_ctx *ctx, uint64_t bytes, uint8_t **d_stage) override;
     int window(bzh_ctx *ctx, uint64_t bytes) override;
     int raw(bzh_ctx *ctx, const uint8_t *d_raw, size_t n) override;
+    // grep_many.hip: many texts that lie in one buffer in HBM, with walls between them (the tables: grep_many_plan.h) -- one
+    // segmented pass, no staging, no carry, no tail: finish() finds nothing left.  seg_totals: [texts][BZGM_TOTALS], on the host
+    // behind the pass's wait
+    int raw_many(bzh_ctx *ctx, const uint8_t *d_raw, const struct BzgmPlan &plan, uint64_t *seg_totals);
     int finish(bzh_ctx *ctx) override;
     int report(bzh_ctx *ctx, size_t *nrecs, uint64_t *out_total) override;
 };

@@ -192,6 +192,21 @@ struct BzgScanShared {
     uint32_t b[BZF_THREADS]; // backward: bit 1 "the chunk holds a delimiter", bit 0 SEL_END of its first; then SEL_TAIL behind it
     uint64_t c[3][BZF_THREADS]; // the chunk's selected bytes, selected records, delimiters; then those in front of it
 };
+// WHAT A ROW OF THE TABLE IS.  The scan walks a table of tiles in order; a policy says which tile of the buffer row t stands for,
+// whether a text begins with it (a wall in front of it: the hit state and the open record start anew, at *start) or ends with it
+// (a wall behind it: nothing behind it selects its tail), and the window its bytes are cut to.  BzgOneText, the default: the rows
+// are the tiles of one window, and no wall stands between two.  (Many texts in one table: grep_many_core.h.)
+#if defined(__HIPCC__)
+#define BZG_MEM __host__ __device__ __forceinline__
+#else
+#define BZG_MEM inline
+#endif
+struct BzgOneText {
+    BZG_MEM uint32_t tile_no(uint32_t t) const { return t; }
+    BZG_MEM bool enters(uint32_t, uint64_t *) const { return false; }
+    BZG_MEM bool leaves(uint32_t) const { return false; }
+    BZG_MEM const BzgWindow &window(uint32_t, const BzgWindow &w, BzgWindow &) const { return w; }
+};
 // The walks over a chunk wait for memory, tile after tile, and one workgroup has nothing else to run meanwhile: they take
 // BZG_BATCH tiles at a time, all loads first (the loops over a batch are unrolled, so a batch lies in registers).
 enum : uint32_t { BZG_BATCH = 8 };
@@ -217,7 +232,8 @@ BZF_FN void bzg_tile_fwd(const BzgTile &x, uint32_t t, uint32_t *hit, uint64_t *
     }
 }
 // phase A: the chunks forward
-BZF_FN void bzg_scan_a(BzgScanShared &sh, uint32_t tid, const BzgTile *tile, uint32_t tiles)
+template <class R = BzgOneText>
+BZF_FN void bzg_scan_a(BzgScanShared &sh, uint32_t tid, const BzgTile *tile, uint32_t tiles, const R &rows = R{})
 {
     uint32_t lo, hi, hit = 0, any = 0;
     uint64_t start = 0;
@@ -231,8 +247,9 @@ BZF_FN void bzg_scan_a(BzgScanShared &sh, uint32_t tid, const BzgTile *tile, uin
         BZG_UNROLL
         for (uint32_t j = 0; j < BZG_BATCH; j++)
             if (j < m) {
+                if (rows.enters(t0 + j, &start)) any = 1, hit = 0;
                 any |= x[j].nd != 0;
-                bzg_tile_fwd(x[j], t0 + j, &hit, &start);
+                bzg_tile_fwd(x[j], rows.tile_no(t0 + j), &hit, &start);
             }
     }
     sh.h[tid] = any << 1 | hit, sh.s[tid] = start;
@@ -252,7 +269,8 @@ BZF_FN void bzg_scan_b(BzgScanShared &sh, const BzgWindow &w, uint64_t *totals)
     totals[BZG_T_TAIL_START] = start, totals[BZG_T_TAIL_HIT] = hit;
 }
 // phase C: SEL_END and open_start of every tile; the chunks backward
-BZF_FN void bzg_scan_c(BzgScanShared &sh, uint32_t tid, BzgTile *tile, uint32_t tiles, const BzgWindow &w)
+template <class R = BzgOneText>
+BZF_FN void bzg_scan_c(BzgScanShared &sh, uint32_t tid, BzgTile *tile, uint32_t tiles, const BzgWindow &w, const R &rows = R{})
 {
     uint32_t lo, hi, hit = sh.h[tid], back = 0;
     uint64_t start = sh.s[tid];
@@ -266,6 +284,7 @@ BZF_FN void bzg_scan_c(BzgScanShared &sh, uint32_t tid, BzgTile *tile, uint32_t 
         BZG_UNROLL
         for (uint32_t j = 0; j < BZG_BATCH; j++)
             if (j < m) {
+                if (rows.enters(t0 + j, &start)) hit = 0;
                 uint32_t fl = x[j].flags & (BZG_HEAD_HIT | BZG_TAIL_HIT);
                 if (x[j].nd) {
                     const bool sel = (hit || (fl & BZG_HEAD_HIT)) != (w.invert != 0);
@@ -274,7 +293,7 @@ BZF_FN void bzg_scan_c(BzgScanShared &sh, uint32_t tid, BzgTile *tile, uint32_t 
                 }
                 tile[t0 + j].open_start = start;
                 tile[t0 + j].flags = fl;
-                bzg_tile_fwd(x[j], t0 + j, &hit, &start);
+                bzg_tile_fwd(x[j], rows.tile_no(t0 + j), &hit, &start);
             }
     }
     sh.b[tid] = back;
@@ -302,7 +321,8 @@ BZF_FN uint32_t bzg_tile_bytes(const BzgTile &x, uint32_t t, const BzgWindow &w)
     return bytes;
 }
 // phase E: SEL_TAIL and the bytes of every tile; the chunks' sums
-BZF_FN void bzg_scan_e(BzgScanShared &sh, uint32_t tid, BzgTile *tile, uint32_t tiles, const BzgWindow &w)
+template <class R = BzgOneText>
+BZF_FN void bzg_scan_e(BzgScanShared &sh, uint32_t tid, BzgTile *tile, uint32_t tiles, const BzgWindow &w, const R &rows = R{})
 {
     uint32_t lo, hi, cur = sh.b[tid];
     uint64_t bytes = 0, sel = 0, del = 0;
@@ -316,9 +336,11 @@ BZF_FN void bzg_scan_e(BzgScanShared &sh, uint32_t tid, BzgTile *tile, uint32_t 
         BZG_UNROLL
         for (uint32_t j = BZG_BATCH; j-- > 0;)
             if (j < m) {
+                if (rows.leaves(t0 + j)) cur = 0;
                 if (cur) x[j].flags |= BZG_SEL_TAIL;
                 if (x[j].nd) cur = (x[j].flags & BZG_SEL_END) != 0;
-                x[j].bytes = bzg_tile_bytes(x[j], t0 + j, w);
+                BzgWindow cut;
+                x[j].bytes = bzg_tile_bytes(x[j], rows.tile_no(t0 + j), rows.window(t0 + j, w, cut));
                 tile[t0 + j].flags = x[j].flags;
                 tile[t0 + j].bytes = x[j].bytes;
                 bytes += x[j].bytes, sel += x[j].inner_sel + ((x[j].flags & BZG_SEL_END) ? 1u : 0u), del += x[j].nd;

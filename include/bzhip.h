@@ -913,6 +913,74 @@ typedef struct {
 } bzh_match_stats;
 BZH_API int bzh_get_match_stats(const bzh_ctx *ctx, bzh_match_stats *out);
 
+/* ---- grep over many inputs in one pass: bzgrep PATTERN over a directory of .bz2 files ----------------------------------------- */
+
+/* THE RULE.  For every input k the call returns exactly what bzh_grep returns for input k alone: bytes, entries, counts and
+ * status.  The decoded inputs lie in one device buffer as many texts with walls between them:
+ *   - a match starts and ends inside one input; text split across the end of input k and the start of input k + 1 is no match;
+ *   - a non-empty tail without a delimiter is that input's last record; record numbers and `off` restart at 0 with every input;
+ *   - an assertion sees an input's two ends as the text's edges (\A ^ at its offset 0, \Z $ at its end, \b against nothing there),
+ *     whatever byte of a neighbour lies beside them in the buffer;
+ *   - a damaged input fails alone, as in bzh_decode_many: items[k].status, zero counts, none of its bytes scanned.
+ * OUTPUT.  The selected records of input 0, then of input 1, ...: their bytes back to back in out, their entries back to back in
+ * ent.  Input k's entries begin at ent[sum of items[j].selected, j < k], its bytes at the out_off of its first entry; `record` and
+ * `off` count from the input's start, `out_off` points into the call's out.  items[k] says what bzh_grep says of input k alone.
+ * COUNTS AND ROOM as in the grep contract: *nrecs, *out_total and every item are always exact, a null array with zero room is not
+ * asked for, all four null or zero is a counting call.  A room that is asked for and too small: nothing is gathered, BZH_E_CAP,
+ * and repeating the call with the exact rooms succeeds.  The call itself returns BZH_OK when it ran to the end, even if every
+ * input failed.
+ * BZH_E_ARG: the grep's cases; a null offs, lens or items with count > 0; a context whose bzh_grep_set_context is not 0, 0
+ * (context records over many inputs are not built); more than 2^31 - 1 virtual tiles (below).  count == 0 succeeds.  After any
+ * outcome the context stays usable.
+ * COST.  One workgroup per (input, 4,096-byte tile of the buffer that it meets): an input shorter than a tile still costs a tile's
+ * work, and a tile that several inputs meet is read once per input.  No atomics; one host wait before the gather. */
+typedef struct {
+    uint64_t decoded;   /* the input's decoded bytes (a raw segment's length) */
+    uint64_t records;   /* of them (nrecords) */
+    uint64_t selected;  /* of those */
+    uint64_t out_bytes; /* their bytes */
+    int32_t status;     /* BZH_OK, or what bzh_decode_many says of the input */
+    uint32_t reserved;  /* 0 */
+} bzh_grep_many_item;   /* 40 bytes */
+
+/* Texts that already lie in HBM, for instance bzh_decode_many_device's output: text k is d_raw[offs[k] .. offs[k] + lens[k]).
+ * The seam the kernels are tested through.  d_raw must be 16-byte aligned and readable to the aligned 4-byte word that holds byte
+ * n - 1, as for bzh_grep_raw_device.  The segments ascend and do not overlap; gaps are allowed and never scanned.  Anything else
+ * is BZH_E_ARG naming the segment. */
+BZH_API int bzh_grep_many_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const size_t *offs, const size_t *lens, size_t count,
+                                     const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, void *d_out, size_t cap,
+                                     bzh_grep_entry *ent, size_t max, bzh_grep_many_item *items, size_t *nrecs, uint64_t *out_total);
+/* Inputs as bzh_decode_many_device takes them, with its checks.  They are decoded into a staging buffer of the context, sized from
+ * the compressed bytes; where that is too small the buffer is sized once more from the total the walk reports and the decode runs
+ * again (bzh_grep_many_stats.staging_retries): the call never returns BZH_E_CAP for its own staging.  Then the one segmented pass. */
+BZH_API int bzh_grep_many_device(bzh_ctx *ctx, const void *d_in, size_t n, const size_t *in_offs, const size_t *in_lens, size_t count,
+                                 const uint8_t *pat, size_t plen, unsigned flags, uint8_t delim, void *d_out, size_t cap,
+                                 bzh_grep_entry *ent, size_t max, bzh_grep_many_item *items, size_t *nrecs, uint64_t *out_total);
+/* Host pointers as bzh_decode_many takes them: one H2D of all inputs, one D2H of the selected bytes (behind BZH_OK only). */
+BZH_API int bzh_grep_many(bzh_ctx *ctx, const uint8_t *const *ins, const size_t *lens, size_t count, const uint8_t *pat, size_t plen,
+                          unsigned flags, uint8_t delim, uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max,
+                          bzh_grep_many_item *items, size_t *nrecs, uint64_t *out_total);
+/* The same for a bzh_patset: a set of strings, or a regex with or without assertions. */
+BZH_API int bzh_grep_many_patset_raw_device(bzh_ctx *ctx, const void *d_raw, size_t n, const size_t *offs, const size_t *lens, size_t count,
+                                            const bzh_patset *set, unsigned flags, uint8_t delim, void *d_out, size_t cap,
+                                            bzh_grep_entry *ent, size_t max, bzh_grep_many_item *items, size_t *nrecs, uint64_t *out_total);
+BZH_API int bzh_grep_many_patset_device(bzh_ctx *ctx, const void *d_in, size_t n, const size_t *in_offs, const size_t *in_lens, size_t count,
+                                        const bzh_patset *set, unsigned flags, uint8_t delim, void *d_out, size_t cap,
+                                        bzh_grep_entry *ent, size_t max, bzh_grep_many_item *items, size_t *nrecs, uint64_t *out_total);
+BZH_API int bzh_grep_many_patset(bzh_ctx *ctx, const uint8_t *const *ins, const size_t *lens, size_t count, const bzh_patset *set,
+                                 unsigned flags, uint8_t delim, uint8_t *out, size_t cap, bzh_grep_entry *ent, size_t max,
+                                 bzh_grep_many_item *items, size_t *nrecs, uint64_t *out_total);
+
+/* Counters of the last bzh_grep_many* call (bzh_get_grep_stats is filled as well, summed over the inputs). */
+typedef struct {
+    uint64_t inputs, inputs_failed;
+    uint64_t segments;        /* non-empty texts: those that own a virtual tile */
+    uint64_t virtual_tiles;   /* workgroups of the counting pass */
+    uint64_t shared_tiles;    /* tiles of the buffer that more than one segment meets */
+    uint64_t staging_retries; /* 0 or 1: the decode ran again with the staging buffer sized from the walk's total */
+} bzh_grep_many_stats;
+BZH_API int bzh_get_grep_many_stats(const bzh_ctx *ctx, bzh_grep_many_stats *out);
+
 /* ---- the encoder writes the index of its own stream: no decode pass to rediscover what it held -------------------------- */
 
 /* bzh_encode_device that also returns the index of the stream it writes: the entries bzh_decode_index would return for
