@@ -25,7 +25,7 @@ def test_exit_codes_for_argument_errors(cli, tmp_path):
     """bnz/src/main.rs:11-14: 0 ok, 1 arguments, 2 filesystem, 3 output"""
     assert run(cli).returncode == 1                       # synopsis
     assert run(cli, "--bogus").returncode == 1
-    assert run(cli, "-x", "f").returncode == 1            # invalid short flag
+    assert run(cli, "-x", "f").returncode == 1            # -x (--line-regexp) without --search or --grep
     assert run(cli, "a", "b").returncode == 1             # two inputs
     assert run(cli, "--output").returncode == 1           # no input
     assert run(cli, "--output", "-k", "f").returncode == 1  # --output needs a path
